@@ -36,6 +36,11 @@ touches the GPU it starts three rocprofv3 --pmc child runs of the same command (
 separate passes, 3 steps each; live_pmc()); if that fails (or with --live-pmc 0, --lean, --cpu-seconds 0, N > 1) the line
 carries the committed profiles/rNN_pmc_summary*.json instead -- roofline.traffic_source says which, and why.
 
+--dump-outputs DIR: after the timed steps, what the timed path computed in its LAST step -- each frame's float RGBA image and
+(not --single-process, whose caller gets the image alone) the rays' end records, flags and step counts -- as DIR/<name>.npy
+in float32 / float64, at most 64 MB: beyond that a fixed, seeded sample of pixels and of rays, indexed over the whole frame
+(image_index, ray_index), so that two builds run with the same arguments can be compared output for output.
+
 Layout: THIS file holds the command line (parse), the launcher for N > 1 (self_launch), the shard construction
 (build_frames), measure() -- ONE timed region, the only place the headline clock runs -- and main(), which assembles the
 JSON line.  bench_common.py: constants, Workload (what is traced), Runtime (rank / group / context), Lanes (two frames in
@@ -59,7 +64,8 @@ sys.path.insert(0, ROOT)
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 from bench_common import (BYTES_PER_RAY, BYTES_PER_RAY_DIR, CAM, DISK, EV_EVERY, PEAK_FP64_VALU_TFLOPS, ClockSampler, Lanes, Runtime,  # noqa: F401
-                          Workload, emit, grid_for, hbm_copy_probe, merge_clock_samples, roofline_block, run_probes, spread, traced_with_events)
+                          DUMP_RAYS, Workload, dump_sample, emit, grid_for, hbm_copy_probe, image_rows, merge_clock_samples, roofline_block,
+                          run_probes, spread, traced_with_events, write_outputs)
 from bench_figures import (counters_for, host_buffer_figures, live_pmc, main_single_process, pipelined_figure,  # noqa: F401
                            pmc_traffic, strong_predicted, time_frame)
 
@@ -145,6 +151,9 @@ def parse(argv=None):
                     help="orbit workload, N > 1: tiles = every frame's tiles over all ranks + one gather per frame (the headline); "
                          "frames = whole frames dealt round-robin to the ranks, no tail, one gather at the end; both = the second "
                          "reported beside the first")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32 / "
+                         "float64, <= 64 MB: a fixed, seeded sample of pixels and rays of a larger frame)")
     a = ap.parse_args(argv)
     if a.lean:
         a.cpu_seconds, a.emulate_shards = 0.0, ""
@@ -220,7 +229,50 @@ def build_frames(rt, wl, W, H, S, fov_x, fov_y, pixels, jitter, sky):
     return frames, batch
 
 
-def measure(rt, wl, sky, nx, ny, ramp, overlap=False, whole_frames=False, reps=1):
+def frame_outputs(rt, frames, W, H, S):
+    """--dump-outputs: the step's results as its caller receives them -- every frame's float RGBA image and the rays' end
+    records, flags and step counts -- sampled over the whole frame and summed over the ranks (each pixel and ray is one
+    rank's, zero on the others), so every rank must call it.  Rays are indexed c * S * H * W + s * H * W + pixel."""
+    torch, dist = rt.torch, rt.dist
+    dev = frames[0].d_k0.device
+    images = []
+    for f in frames:
+        img = torch.zeros((W * H, 4), dtype=torch.float32, device=dev)
+        f.shade_f32(img, f.d_pixels)          # this rank's pixels, in frame order
+        images.append(img)
+    idx = dump_sample(len(frames) * S * W * H, DUMP_RAYS, seed=2)
+    d_idx = torch.from_numpy(idx).to(dev)
+    dir_only = frames[0]._traced == "dir"
+    has_obj = frames[0].spheres is not None and len(frames[0].spheres) > 0
+    rays = {"ray_exit_direction" if dir_only else "ray_end_state": torch.zeros((len(idx), 3 if dir_only else 6), dtype=torch.float64, device=dev),
+            "ray_flags": torch.zeros(len(idx), dtype=torch.float64, device=dev),
+            "ray_n_steps": torch.zeros(len(idx), dtype=torch.float64, device=dev),
+            "ray_n_accepted": torch.zeros(len(idx), dtype=torch.float64, device=dev)}
+    if has_obj:
+        rays["ray_object_id"] = torch.zeros(len(idx), dtype=torch.float64, device=dev)
+    for c, f in enumerate(frames):
+        # ray s * P + p of the frame is sample s of pixel d_pixels[p]
+        gid = (c * S * W * H + torch.arange(S, device=dev)[:, None] * (W * H) + f.d_pixels[None, :]).reshape(-1)
+        pos = torch.searchsorted(d_idx, gid).clamp_(max=len(idx) - 1)
+        src = torch.nonzero(d_idx[pos] == gid).squeeze(1)
+        dst = pos[src]
+        for k, v in (("ray_exit_direction" if dir_only else "ray_end_state", f.d_dir if dir_only else f.d_end), ("ray_flags", f.d_flags),
+                     ("ray_n_steps", f.d_steps), ("ray_n_accepted", f.d_acc), ("ray_object_id", f.d_obj)):
+            if k in rays:
+                rays[k][dst] = v[src].to(torch.float64)
+    if rt.world > 1:
+        for t in images + list(rays.values()):
+            dist.all_reduce(t)
+    torch.cuda.synchronize()
+    out = image_rows(images, W, H)
+    out["ray_index"] = idx.astype(np.float64)
+    for k, v in rays.items():
+        v = v.cpu().numpy()
+        out[k] = v if k in ("ray_end_state", "ray_exit_direction") else v.astype(np.float32)   # (integers, exact in float32)
+    return out
+
+
+def measure(rt, wl, sky, nx, ny, ramp, overlap=False, whole_frames=False, reps=1, dump=False):
     """One timed region over a frame of (width * nx) x (height * ny) pixels sharded over the ranks.
     Returns the figures of this rank (dt already the maximum over ranks).
       overlap (frame workload): two frames in flight -- consecutive frames alternate between two streams / contexts.
@@ -436,6 +488,8 @@ def measure(rt, wl, sky, nx, ny, ramp, overlap=False, whole_frames=False, reps=1
         reads = [r_ for r_ in reads if r_ is not None]
         rep_clock.append(float(np.mean(reads)) if reads else None)
         rep_events.append(kernel_ms[n_ev:])
+    # (before anything else runs the frames again: what the last timed step left in them)
+    outputs = frame_outputs(rt, frames, W, H, S) if dump else None
     dt = float(np.median(dts))
     sclk, sampled_rep_ms = None, None
     # the extra, SAMPLED repetition (not a headline sample).  Every step is a collective when N > 1: all ranks run it or none
@@ -524,7 +578,7 @@ def measure(rt, wl, sky, nx, ny, ramp, overlap=False, whole_frames=False, reps=1
                 steps_all=float(tot[1].item()), launch=rt.ctx.last_launch(), fr=fr, tcost=tcost,
                 visit=tile_cost.visit, root_share=root_share, calibration=calibration, sclk=sclk,
                 dts=dts, sclks=sclks, call_samples=call_samples, call_ms_mean=call_ms_mean, share=share,
-                sampled_rep_ms=sampled_rep_ms, per_rank=per_rank)
+                sampled_rep_ms=sampled_rep_ms, per_rank=per_rank, outputs=outputs)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -605,7 +659,10 @@ def main():
     world, rank = rt.world, rt.rank
 
     nx, ny = grid_for(world) if a.workload != "orbit" else (1, 1)   # orbit: ONE fixed frame over all ranks
-    m = measure(rt, wl, sky, nx, ny, a.ramp_seconds, reps=a.reps)
+    m = measure(rt, wl, sky, nx, ny, a.ramp_seconds, reps=a.reps, dump=a.dump_outputs is not None)
+    if rank == 0 and m["outputs"] is not None:
+        write_outputs(a.dump_outputs, m["outputs"])
+    m["outputs"] = None
     strong = frames_sharded = None
     per_step = lambda r: r["dt"] / a.steps    # noqa: E731  (dt = the median repetition of the region)
     if world > 1 and a.workload != "orbit":

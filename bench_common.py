@@ -502,3 +502,43 @@ def emit(out):
         pass
     sys.stdout.flush()
     print(json.dumps(out), flush=True)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# --dump-outputs DIR: what the timed path computed in its last step, as DIR/<name>.npy (float32 / float64), so that two
+# builds can be compared output for output.  A larger output is cut to a fixed, seeded sample of pixels and of rays,
+# indexed over the WHOLE frame (not a rank's shard): the files do not depend on how the tiles were dealt.
+# ----------------------------------------------------------------------------------------------------------------------
+DUMP_MAX_BYTES = 64 << 20
+DUMP_PIXELS = 1 << 20     # RGBA rows kept: 16 B + an 8-B index each (all of one 1024 x 1024 frame)
+DUMP_RAYS = 1 << 18       # rays kept: <= 48 + 16 B + an 8-B index each
+
+
+def dump_sample(total, cap, seed):
+    """Sorted flat indices: all of range(total) when it fits in cap, else a fixed, seeded sample of cap of them."""
+    if total <= cap:
+        return np.arange(total, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(total, cap, replace=False)).astype(np.int64)
+
+
+def image_rows(images, W, H):
+    """image_index / image_rgba of the frames' float RGBA images (torch [H*W, 4] float32 each): flat index
+    c * H * W + y * W + x over the frames c of a step."""
+    import torch
+    idx = dump_sample(len(images) * W * H, DUMP_PIXELS, seed=1)
+    rows = np.empty((len(idx), 4), dtype=np.float32)
+    for c, img in enumerate(images):
+        sel = (idx // (W * H)) == c
+        rows[sel] = img[torch.from_numpy(idx[sel] - c * W * H).to(img.device)].cpu().numpy()
+    return {"image_index": idx.astype(np.float64), "image_rgba": rows}
+
+
+def write_outputs(path, arrays):
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    bad = [k for k, v in arrays.items() if v.dtype not in (np.float32, np.float64)]
+    total = sum(v.nbytes for v in arrays.values())
+    if bad or total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} B (limit {DUMP_MAX_BYTES}), not float32 / float64: {bad}")
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)

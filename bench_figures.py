@@ -10,7 +10,7 @@ import time
 import numpy as np
 
 from bench_common import (BYTES_PER_RAY, BYTES_PER_RAY_DIR, CAM, DISK, EV_EVERY, PEAK_FP64_VALU_TFLOPS, ROOT, Lanes, Workload, emit,
-                          grid_for, ramp_clocks, roofline_block, traced_with_events)
+                          grid_for, image_rows, ramp_clocks, roofline_block, traced_with_events, write_outputs)
 
 def live_pmc(a, deadline_s=300.0):
     """HBM bytes and wave-level VALU instructions per launch of the trace kernel, measured in THIS run: three rocprofv3
@@ -542,6 +542,17 @@ def main_single_process(a):
     nx, ny = grid_for(N) if a.workload != "orbit" else (1, 1)
     frames, W, H, S = build(nx, ny)
     m = timed(frames)
+    if a.dump_outputs is not None:
+        # what the caller of bhg_frame_render receives: each frame's float RGBA image, here the last timed step's, still
+        # on the first device (bhg_frame_device_image)
+        import torch
+
+        class DeviceImage:
+            def __init__(self, f):
+                self.__cuda_array_interface__ = {"shape": (f.H * f.W, 4), "typestr": "<f4", "data": (f.device_image(), False), "version": 2}
+        images = [torch.as_tensor(DeviceImage(f), device=torch.device("cuda", devices[0])) for f in frames]
+        write_outputs(a.dump_outputs, image_rows(images, W, H))
+        del images
     pipelined = None
     if not a.lean:
         # two frames in flight: a second set of frame objects, steps alternating between the sets

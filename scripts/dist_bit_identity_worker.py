@@ -17,7 +17,8 @@ if distinct:
 else:
     dist.init_process_group("gloo")
 rank, world = dist.get_rank(), dist.get_world_size()
-W, H, S, T = 160, 96, 3, 32
+W, H, S = 160, 96, 3
+T = int(os.environ.get("BHG_TILE", "32"))   # tile edge; tests/test_gpu_multirank.py widens it to leave a rank without tiles
 cam = np.array([1e-4, 0.0, 30.0])
 sky = synthetic_sky(256, 128)
 jit = python_random_stream(42.0, 2 * S * W * H)

@@ -220,6 +220,7 @@ def main(argv=None):
         print(json.dumps([dict(name=s["name"], kind=s["kind"], cmd=s["cmd"][:3] + (["<inline>"] if s["kind"] == "bit_identity" else s["cmd"][3:]), env=s["env"]) for s in steps]))
         return 0
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)   # the C example is linked into build/, which a clean checkout lacks
     failed, predicted, c_sigs = [], {}, {}
     with open(a.out, "w") as log:
         for s in steps:

@@ -459,3 +459,28 @@ def test_bench_calibration_block_is_plain_arithmetic():
     # the sampler on a box without the sysfs file (this one): no thread, no figure
     smp = bc.ClockSampler(0).start()
     assert smp.stop() is None or isinstance(smp.stop(), dict)
+
+
+def test_bench_dump_outputs_sample_and_limit(tmp_path):
+    """bench.py --dump-outputs: a fixed, seeded sample of a large output (the same every run), all of a small one, and
+    nothing written that is not float32 / float64 or that passes 64 MB."""
+    import torch
+    import bench
+    import bench_common as bc
+    assert bench.parse(["--steps", "7", "--dump-outputs", str(tmp_path / "d")]).dump_outputs == str(tmp_path / "d")
+    assert bench.parse([]).dump_outputs is None and bench.parse(["--steps", "7"]).steps == 7
+    s = bc.dump_sample(5 * 2048 * 2048, bc.DUMP_RAYS, seed=2)
+    assert len(s) == bc.DUMP_RAYS and np.array_equal(s, bc.dump_sample(5 * 2048 * 2048, bc.DUMP_RAYS, seed=2))
+    assert (np.diff(s) > 0).all() and s[0] >= 0 and s[-1] < 5 * 2048 * 2048
+    assert np.array_equal(bc.dump_sample(100, bc.DUMP_RAYS, seed=2), np.arange(100))
+    # two 3 x 2 frames: every pixel, in frame order, frame after frame
+    imgs = [torch.arange(24, dtype=torch.float32).reshape(6, 4) + 100 * c for c in range(2)]
+    rows = bc.image_rows(imgs, 3, 2)
+    assert np.array_equal(rows["image_index"], np.arange(12)) and np.array_equal(rows["image_rgba"], torch.cat(imgs).numpy())
+    bc.write_outputs(str(tmp_path / "ok"), rows)
+    assert np.array_equal(np.load(tmp_path / "ok" / "image_rgba.npy"), rows["image_rgba"])
+    with pytest.raises(RuntimeError):
+        bc.write_outputs(str(tmp_path / "int"), {"x": np.zeros(3, dtype=np.int32)})
+    with pytest.raises(RuntimeError):
+        bc.write_outputs(str(tmp_path / "big"), {"x": np.zeros((64 << 20) // 8 + 1)})
+    assert not (tmp_path / "int").exists() and not (tmp_path / "big").exists()
