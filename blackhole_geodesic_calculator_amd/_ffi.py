@@ -15,8 +15,8 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BHGEO_LIB") or os.path.join(_HERE, "libbhgeo.so")  # BHGEO_LIB: A/B builds
 
-ABI_VERSION = 8
-ABI_COMPAT_MIN = 7    # bhg_abi_check serves bindings from this ABI on (8 only added bhg_trajectory_objects)
+ABI_VERSION = 9
+ABI_COMPAT_MIN = 7    # bhg_abi_check serves bindings from this ABI on (8 added bhg_trajectory_objects, 9 the redshift calls)
 
 OK = 0
 E_INVALID, E_NO_DEVICE, E_HIP, E_NOMEM = -1, -2, -3, -4
@@ -52,10 +52,33 @@ EXPORTS = (
     "bhg_frame_last_ms", "bhg_deal_tiles",
     "bhg_params_size", "bhg_camera_size", "bhg_scene_size", "bhg_frame_scene_size", "bhg_abi_check",
     "bhg_default_params_sized", "bhg_peak_probe", "bhg_trajectory_objects",
+    "bhg_redshift_size", "bhg_redshift_device", "bhg_redshift_host", "bhg_shade_scene_redshift_device", "bhg_frame_set_redshift",
 )
 PROBE_FMA, PROBE_STEP_MIX = 0, 1
 
 GATHER_AUTO, GATHER_COPY, GATHER_RCCL, GATHER_PEER, GATHER_COPY_PEERCALL = 0, 1, 2, 3, 4
+
+REDSHIFT_DISK, REDSHIFT_OBJECTS, REDSHIFT_SKY = 1, 2, 4
+_REDSHIFT_CLASS = {"disk": REDSHIFT_DISK, "objects": REDSHIFT_OBJECTS, "sky": REDSHIFT_SKY}
+
+
+class Redshift(C.Structure):
+    """bhg_redshift (ABI 9): apply = BHG_REDSHIFT_* classes whose colour is weighted by g^exponent (0 = off)."""
+    _fields_ = [("apply", C.c_uint32), ("disk_sense", C.c_int32), ("exponent", C.c_double)]
+
+
+def make_redshift(apply=("disk", "objects", "sky"), exponent=4.0, disk_sense=1) -> Redshift:
+    """apply: class names ("disk", "objects", "sky") or a BHG_REDSHIFT_* bit mask; () / 0 = off."""
+    rs = Redshift()
+    if isinstance(apply, (int, np.integer)):
+        rs.apply = int(apply)
+    else:
+        bad = [a for a in apply if a not in _REDSHIFT_CLASS]
+        if bad:
+            raise ValueError(f"unknown redshift class {bad}: use {sorted(_REDSHIFT_CLASS)}")
+        rs.apply = sum({_REDSHIFT_CLASS[a] for a in apply})
+    rs.disk_sense, rs.exponent = int(disk_sense), float(exponent)
+    return rs
 
 
 class Camera(C.Structure):
@@ -291,6 +314,20 @@ def load():
     L.bhg_deal_tiles.restype = C.c_int
     L.bhg_deal_tiles.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_double, C.c_int32,
                                  C.POINTER(C.c_int64), C.c_size_t, C.POINTER(C.c_size_t)]
+    L.bhg_redshift_size.restype = C.c_size_t
+    L.bhg_redshift_size.argtypes = []
+    L.bhg_redshift_device.restype = C.c_int
+    L.bhg_redshift_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Redshift), _dp, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.bhg_redshift_host.restype = C.c_int
+    L.bhg_redshift_host.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Redshift), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_size_t, C.c_void_p]
+    L.bhg_shade_scene_redshift_device.restype = C.c_int
+    L.bhg_shade_scene_redshift_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32,
+                                                  C.POINTER(Scene), C.POINTER(Params), C.POINTER(Redshift), _dp, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bhg_frame_set_redshift.restype = C.c_int
+    L.bhg_frame_set_redshift.argtypes = [C.c_void_p, C.POINTER(Redshift)]
     if L.bhg_version() != ABI_VERSION or not hasattr(L, "bhg_abi_check"):
         raise ImportError(f"libbhgeo ABI {L.bhg_version()} != expected {ABI_VERSION}: rebuild {LIB_PATH}")
     for name in ("bhg_params_size", "bhg_camera_size", "bhg_scene_size", "bhg_frame_scene_size"):
@@ -305,6 +342,8 @@ def load():
     # the handshake include/bhgeo.h asks of every binding: ABI version and the layout of every struct declared above
     if L.bhg_abi_check(ABI_VERSION, C.sizeof(Params), C.sizeof(Camera), C.sizeof(Scene), C.sizeof(FrameScene)) != OK:
         raise ImportError("libbhgeo: " + L.bhg_last_error().decode())
+    if L.bhg_redshift_size() != C.sizeof(Redshift):
+        raise ImportError(f"libbhgeo: bhg_redshift is {L.bhg_redshift_size()} bytes, this binding's {C.sizeof(Redshift)}")
     _lib = L
     return L
 
@@ -572,6 +611,14 @@ class Frame:
                 sc.lamps[j][q] = float(lm[j, q])
         _check(load().bhg_frame_set_scene(self._h, C.byref(sc)))
 
+    def set_redshift(self, apply=("disk", "objects", "sky"), exponent=4.0, disk_sense=1):
+        """Redshift in every later render (bhg_frame_set_redshift): the colour of a ray of a class in `apply` is weighted by
+        g^exponent.  apply=() or None: off -- the frame as without redshift, bit for bit."""
+        if apply is None or (not isinstance(apply, (int, np.integer)) and len(apply) == 0):
+            _check(load().bhg_frame_set_redshift(self._h, None))
+            return
+        _check(load().bhg_frame_set_redshift(self._h, C.byref(make_redshift(apply, exponent, disk_sense))))
+
     def render(self, params: "Params", out=None, to_host=True):
         """One frame: float32 [H, W, 4] (a new array, or `out`).  to_host=False: only enqueue; the image stays on the
         first device (device_image(), synchronize())."""
@@ -805,6 +852,43 @@ class Context:
                                                  C.c_void_p(d_object_id or None), int(n_pixels), int(samples),
                                                  C.byref(scene), C.c_void_p(d_rgba_f32), C.c_void_p(d_scatter or None),
                                                  C.c_void_p(stream or None)))
+
+    def redshift(self, k0, x0, params: Params, rs: Redshift, flags, end=None):
+        """bhg_redshift_host: g [N] of traced rays from their camera state (k0 [N, 3], x0 [3] or [N, 3]), end [N, 6] (or None) and
+        flags [N]."""
+        k0 = np.ascontiguousarray(k0, dtype=np.float64).reshape(-1, 3)
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        n = k0.shape[0]
+        if flags.shape != (n,) or (x0.shape != (3,) and x0.shape != (n, 3)):
+            raise ValueError("flags must be [N], x0 [3] or [N, 3]")
+        e = None if end is None else np.ascontiguousarray(end, dtype=np.float64)
+        if e is not None and e.shape != (n, 6):
+            raise ValueError("end must be [N, 6]")
+        g = np.empty(n, np.float64)
+        _check(load().bhg_redshift_host(self._h, C.byref(params), C.byref(rs), _addr(x0), 1 if x0.ndim == 1 else 0, _addr(k0),
+                                        None if e is None else _addr(e), _addr(flags), n, _addr(g)))
+        return g
+
+    def redshift_device(self, params: Params, rs: Redshift, n, d_k0, d_flags, d_g, x0_shared=None, d_x0=0, d_end=0, stream=0):
+        xs = None
+        if x0_shared is not None:
+            xs = (C.c_double * 3)(*[float(v) for v in x0_shared])
+        _check(load().bhg_redshift_device(self._h, C.byref(params), C.byref(rs), xs, C.c_void_p(d_x0 or None), C.c_void_p(d_k0),
+                                          C.c_void_p(d_end or None), C.c_void_p(d_flags), int(n), C.c_void_p(d_g),
+                                          C.c_void_p(stream or None)))
+
+    def shade_scene_redshift_device(self, d_end, d_flags, n_pixels, samples, scene: "Scene", params: Params, rs, x0_shared, d_k0,
+                                    d_rgba=0, d_rgba_f32=0, d_object_id=0, d_scatter=0, d_end_dir=0, stream=0):
+        """bhg_shade_scene_redshift_device: the scene shade with each ray's colour weighted by g^exponent (rs: Redshift or None =
+        off).  d_end = 0 with d_end_dir: a direction-only sky frame."""
+        xs = (C.c_double * 3)(*[float(v) for v in x0_shared])
+        _check(load().bhg_shade_scene_redshift_device(self._h, C.c_void_p(d_end or None), C.c_void_p(d_end_dir or None),
+                                                      C.c_void_p(d_flags), C.c_void_p(d_object_id or None), int(n_pixels),
+                                                      int(samples), C.byref(scene), C.byref(params),
+                                                      None if rs is None else C.byref(rs), xs, C.c_void_p(d_k0),
+                                                      C.c_void_p(d_rgba or None), C.c_void_p(d_rgba_f32 or None),
+                                                      C.c_void_p(d_scatter or None), C.c_void_p(stream or None)))
 
     def assemble_frame_f32_device(self, d_slabs, d_index, n_pixels, d_frame, stream=0):
         _check(load().bhg_assemble_frame_f32_device(self._h, C.c_void_p(d_slabs), C.c_void_p(d_index), int(n_pixels),

@@ -40,6 +40,10 @@ static_assert(sizeof(bhg_params) == 104, "bhg_params layout is part of the ABI")
 static_assert(sizeof(bhg_camera) == 128, "bhg_camera layout is part of the ABI");
 static_assert(sizeof(bhg_scene) == 664 && sizeof(bhg_frame_scene) == 664, "scene layouts are part of the ABI");
 static_assert(BHG_FLAG_HIT_DISK == bhg::BHG_FLAG_HIT_DISK_, "flag mismatch");
+static_assert(BHG_REDSHIFT_DISK == bhg::BHG_REDSHIFT_DISK_ && BHG_REDSHIFT_OBJECTS == bhg::BHG_REDSHIFT_OBJECTS_ &&
+                  BHG_REDSHIFT_SKY == bhg::BHG_REDSHIFT_SKY_,
+              "redshift class mismatch");
+static_assert(sizeof(bhg_redshift) == 16, "bhg_redshift layout is part of the ABI");
 
 namespace {
 
@@ -350,6 +354,47 @@ int validate(const bhg_params *p)
 
 }  // namespace
 
+namespace bhg {
+// Redshift settings against the trace parameters (include/bhgeo.h, "redshift"): *out = the kernels' parameters.  disk_r_in
+// < 0: no disk to check (none in the scene, or the disk class is not asked for).  Also used by bhgeo_frame.hip.
+int redshift_params(const bhg_params *p, const bhg_redshift *rs, double disk_r_in, const double *x0, RedshiftParams *out)
+{
+    int rc = validate(p);
+    if (rc != BHG_OK) return rc;
+    if (!rs) return fail(BHG_E_INVALID, "redshift settings are NULL");
+    if (rs->apply & ~(BHG_REDSHIFT_DISK | BHG_REDSHIFT_OBJECTS | BHG_REDSHIFT_SKY))
+        return fail(BHG_E_INVALID, "redshift apply has bits outside BHG_REDSHIFT_DISK | _OBJECTS | _SKY: " + std::to_string(rs->apply));
+    if (!std::isfinite(rs->exponent)) return fail(BHG_E_INVALID, "redshift exponent is not finite");
+    if (p->time_like) return fail(BHG_E_INVALID, "redshift is defined for null rays: time_like = 1 is refused");
+    if (rs->disk_sense != 1 && rs->disk_sense != -1)
+        return fail(BHG_E_INVALID, "redshift disk_sense must be +1 or -1, not " + std::to_string(rs->disk_sense));
+    // (s: the sense the formulas use, the traced picture's -- the received photon runs the traced curve mirrored in phi)
+    const double M = 0.5 * p->r_s, a = p->rhs_form == BHG_RHS_KERR_BL ? p->spin : 0.0, s = -(double)rs->disk_sense;
+    if (disk_r_in >= 0.0) {
+        // no timelike circular orbit at or inside the circular photon orbit of this sense (Boyer-Lindquist r)
+        const double r_ph = p->rhs_form == BHG_RHS_KERR_BL ? 2.0 * M * (1.0 + std::cos(2.0 / 3.0 * std::acos(-s * a / M))) : 3.0 * M;
+        const double r_in = std::sqrt(std::max(disk_r_in * disk_r_in - a * a, 0.0));
+        if (!(r_in > r_ph)) {
+            char msg[200];
+            std::snprintf(msg, sizeof msg, "redshift: disk_r_in %.17g (Boyer-Lindquist r %.17g) is at or inside the circular photon orbit "
+                          "r_ph = %.17g of disk_sense %d: no timelike circular orbit there", disk_r_in, r_in, r_ph, rs->disk_sense);
+            return fail(BHG_E_INVALID, msg);
+        }
+    }
+    if (x0 && !(std::isfinite(x0[0]) && std::isfinite(x0[1]) && std::isfinite(x0[2])))
+        return fail(BHG_E_INVALID, "camera origin is not finite");
+    std::memset(out, 0, sizeof(*out));
+    if (x0) std::memcpy(out->x0, x0, sizeof(out->x0));
+    out->r_s = p->r_s;
+    out->spin = a;
+    out->sense = (double)rs->disk_sense;
+    out->exponent = rs->exponent;
+    out->rhs = p->rhs_form;
+    out->apply = rs->apply;
+    return BHG_OK;
+}
+}  // namespace bhg
+
 extern "C" {
 
 int bhg_version(void) { return BHG_ABI_VERSION; }
@@ -371,6 +416,7 @@ size_t bhg_params_size(void) { return sizeof(bhg_params); }
 size_t bhg_camera_size(void) { return sizeof(bhg_camera); }
 size_t bhg_scene_size(void) { return sizeof(bhg_scene); }
 size_t bhg_frame_scene_size(void) { return sizeof(bhg_frame_scene); }
+size_t bhg_redshift_size(void) { return sizeof(bhg_redshift); }
 
 int bhg_abi_check(int abi_version, size_t params_size, size_t camera_size, size_t scene_size, size_t frame_scene_size)
 {
@@ -1234,7 +1280,8 @@ int bhg_shade_dir_device(bhg_context *c, const double *d_end_dir, const uint8_t 
 namespace {
 int shade_scene_impl(bhg_context *c, const double *d_end, const uint8_t *d_flags, const int8_t *d_object_id,
                      size_t n_pixels, int32_t samples, const bhg_scene *sc, double *d_rgba, float *d_rgba_f32,
-                     const int64_t *d_scatter, void *stream);
+                     const int64_t *d_scatter, void *stream, const double *d_end_dir = nullptr,
+                     const bhg::RedshiftParams *rs = nullptr, const double *d_k0 = nullptr);
 }
 
 extern "C" {
@@ -1260,7 +1307,8 @@ namespace {
 
 int shade_scene_impl(bhg_context *c, const double *d_end, const uint8_t *d_flags, const int8_t *d_object_id,
                      size_t n_pixels, int32_t samples, const bhg_scene *sc, double *d_rgba, float *d_rgba_f32,
-                     const int64_t *d_scatter, void *stream)
+                     const int64_t *d_scatter, void *stream, const double *d_end_dir, const bhg::RedshiftParams *rs,
+                     const double *d_k0)
 {
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
     if (!sc) return fail(BHG_E_INVALID, "scene is NULL");
@@ -1277,11 +1325,17 @@ int shade_scene_impl(bhg_context *c, const double *d_end, const uint8_t *d_flags
     for (int j = 0; j < sc->n_spheres; j++)
         if (!(sc->spheres[j][3] > 0.0)) return fail(BHG_E_INVALID, "sphere radii must be > 0");
     if (n_pixels == 0) return BHG_OK;
-    if (!d_end || !d_flags || !sc->d_sky) return fail(BHG_E_INVALID, "NULL device pointer");
+    if ((!d_end && !d_end_dir) || !d_flags || !sc->d_sky) return fail(BHG_E_INVALID, "NULL device pointer");
+    if (rs && !d_k0) return fail(BHG_E_INVALID, "redshift needs the camera directions d_k0");
     ENTER_DEVICE(c->device);
     bhg::ShadeArgs a;
     std::memset(&a, 0, sizeof(a));
     a.end = d_end;
+    a.dir = d_end ? nullptr : d_end_dir;
+    if (rs) {
+        a.rs = *rs;
+        a.k0 = d_k0;
+    }
     a.flags = d_flags;
     a.sky = sc->d_sky;
     a.rgba = d_rgba;
@@ -1313,6 +1367,83 @@ int shade_scene_impl(bhg_context *c, const double *d_end, const uint8_t *d_flags
 }  // namespace
 
 extern "C" {
+
+int bhg_shade_scene_redshift_device(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
+                                    const int8_t *d_object_id, size_t n_pixels, int32_t samples, const bhg_scene *sc,
+                                    const bhg_params *p, const bhg_redshift *rs, const double *x0_shared, const double *d_k0,
+                                    double *d_rgba, float *d_rgba_f32, const int64_t *d_scatter, void *stream)
+{
+    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
+    if (!sc) return fail(BHG_E_INVALID, "scene is NULL");
+    if (n_pixels && !d_rgba && !d_rgba_f32) return fail(BHG_E_INVALID, "NULL device pointer (d_rgba and d_rgba_f32)");
+    if (!d_end && (sc->disk_r_out > 0.0 || sc->n_spheres > 0))
+        return fail(BHG_E_INVALID, "d_end is NULL: a direction-only frame cannot have a disk or object spheres");
+    bhg::RedshiftParams rp;
+    const bool on = rs && rs->apply != 0;
+    if (on) {
+        if (!x0_shared) return fail(BHG_E_INVALID, "x0_shared is NULL");
+        const bool disk = sc->disk_r_out > 0.0 && (rs->apply & BHG_REDSHIFT_DISK);
+        int rc = bhg::redshift_params(p, rs, disk ? sc->disk_r_in : -1.0, x0_shared, &rp);
+        if (rc != BHG_OK) return rc;
+    }
+    return shade_scene_impl(c, d_end, d_flags, d_object_id, n_pixels, samples, sc, d_rgba, d_rgba_f32, d_scatter, stream,
+                            d_end_dir, on ? &rp : nullptr, d_k0);
+}
+
+int bhg_redshift_device(bhg_context *c, const bhg_params *p, const bhg_redshift *rs, const double *x0_shared,
+                        const double *d_x0, const double *d_k0, const double *d_end, const uint8_t *d_flags, size_t n,
+                        double *d_g, void *stream)
+{
+    // (the settings are checked before the context: a refusal names its figure with or without a device)
+    bhg::RedshiftParams rp;
+    int rc = bhg::redshift_params(p, rs, p && p->disk_r_out > 0.0 ? p->disk_r_in : -1.0, x0_shared, &rp);
+    if (rc != BHG_OK) return rc;
+    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
+    if (!x0_shared == !d_x0) return fail(BHG_E_INVALID, "exactly one of x0_shared / d_x0 must be given");
+    if (n == 0) return BHG_OK;
+    if (!d_k0 || !d_flags || !d_g) return fail(BHG_E_INVALID, "d_k0 / d_flags / d_g is NULL");
+    if (n > ((size_t)1 << 39)) return fail(BHG_E_INVALID, "n too large for one launch (at most 2^39 rays)");
+    ENTER_DEVICE(c->device);
+    bhg::RedshiftArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.p = rp;
+    a.x0 = d_x0;
+    a.k0 = d_k0;
+    a.end = d_end;
+    a.flags = d_flags;
+    a.g = d_g;
+    a.n = n;
+    HIP_TRY(bhg::launch_redshift(a, (hipStream_t)stream));
+    return BHG_OK;
+}
+
+int bhg_redshift_host(bhg_context *c, const bhg_params *p, const bhg_redshift *rs, const double *x0, int x0_is_shared,
+                      const double *k0, const double *end, const uint8_t *flags, size_t n, double *g)
+{
+    bhg::RedshiftParams rp;   // (checked here too, before the context and before any copy)
+    int rc = bhg::redshift_params(p, rs, p && p->disk_r_out > 0.0 ? p->disk_r_in : -1.0, x0_is_shared ? x0 : nullptr, &rp);
+    if (rc != BHG_OK) return rc;
+    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
+    if (!x0) return fail(BHG_E_INVALID, "x0 is NULL");
+    if (n == 0) return BHG_OK;
+    if (!k0 || !flags || !g) return fail(BHG_E_INVALID, "k0 / flags / g is NULL");
+    ENTER_DEVICE(c->device);
+    // one block: [x0 (per ray)][k0][end][g] doubles, then the flags
+    const size_t nx = x0_is_shared ? 0 : n * 3, ne = end ? n * 6 : 0;
+    rc = ensure(&c->d_in, &c->d_in_bytes, (nx + n * 3 + ne + n) * sizeof(double) + n);
+    if (rc != BHG_OK) return rc;
+    double *dx = (double *)c->d_in, *dk = dx + nx, *de = dk + n * 3, *dg = de + ne;
+    uint8_t *df = (uint8_t *)(dg + n);
+    if (nx) HIP_TRY(hipMemcpyAsync(dx, x0, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dk, k0, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (ne) HIP_TRY(hipMemcpyAsync(de, end, ne * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(df, flags, n, hipMemcpyHostToDevice, c->stream));
+    rc = bhg_redshift_device(c, p, rs, x0_is_shared ? x0 : nullptr, nx ? dx : nullptr, dk, ne ? de : nullptr, df, n, dg, c->stream);
+    if (rc != BHG_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(g, dg, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return BHG_OK;
+}
 
 int bhg_assemble_frame_f32_device(bhg_context *c, const float *d_slabs, const int64_t *d_index, size_t n_pixels,
                                   float *d_frame, void *stream)

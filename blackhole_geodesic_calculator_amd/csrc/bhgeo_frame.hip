@@ -35,6 +35,8 @@
 namespace bhg {
 int set_error(int code, const std::string &msg);   // bhgeo_capi.hip: the thread-local message of bhg_last_error()
 void host_copy(bhg_context *c, void *dst, const void *src, size_t bytes, size_t piece);   // bhgeo_capi.hip: multi-threaded memcpy in jobs of `piece` bytes
+// bhgeo_capi.hip: redshift settings checked against the trace parameters (disk_r_in < 0: no disk to check)
+int redshift_params(const bhg_params *p, const bhg_redshift *rs, double disk_r_in, const double *x0, RedshiftParams *out);
 }
 
 namespace {
@@ -199,6 +201,7 @@ struct bhg_frame {
     std::vector<float> sky, disk_tex;
     int32_t sky_w = 0, sky_h = 0, disk_w = 0, disk_h = 0;
     bhg_frame_scene scene;          // (its pointers are not used after bhg_frame_set_scene)
+    bhg_redshift rs = {0u, 1, 4.0}; // bhg_frame_set_redshift; apply = 0: off (the shade calls of ABI 8)
     // root (device of shard 0)
     DevBuf recv, perm, image;       // [n_dev * pmax][4] float, [H W] int64, [H W][4] float
     size_t pmax = 0;
@@ -584,6 +587,23 @@ try {
     return host_exception();
 }
 
+int bhg_frame_set_redshift(bhg_frame *f, const bhg_redshift *rs)
+{
+    if (!f) return fail(BHG_E_INVALID, "frame is NULL");
+    if (!rs || rs->apply == 0) {
+        f->rs.apply = 0;
+        return BHG_OK;
+    }
+    // what can be checked without the trace parameters (the metric and the disk are checked at every render)
+    if (rs->apply & ~(BHG_REDSHIFT_DISK | BHG_REDSHIFT_OBJECTS | BHG_REDSHIFT_SKY))
+        return fail(BHG_E_INVALID, "redshift apply has bits outside BHG_REDSHIFT_DISK | _OBJECTS | _SKY: " + std::to_string(rs->apply));
+    if (!std::isfinite(rs->exponent)) return fail(BHG_E_INVALID, "redshift exponent is not finite");
+    if (rs->disk_sense != 1 && rs->disk_sense != -1)
+        return fail(BHG_E_INVALID, "redshift disk_sense must be +1 or -1, not " + std::to_string(rs->disk_sense));
+    f->rs = *rs;
+    return BHG_OK;
+}
+
 int bhg_frame_render(bhg_frame *f, const bhg_params *p, float *rgba_host)
 try {
     if (!f || !p) return fail(BHG_E_INVALID, "frame / params is NULL");
@@ -602,6 +622,12 @@ try {
     Shard &root = f->sh[0];
     bhg_params prm = *p;
     if (prm.order_blocks == 0 && S > 1) prm.order_blocks = (uint32_t)S;   // the rays are S blocks of P (sample-major)
+    const bool redshift = f->rs.apply != 0;
+    if (redshift) {   // (refused before anything is enqueued)
+        bhg::RedshiftParams rp;
+        BHG_TRY(bhg::redshift_params(&prm, &f->rs, has_disk && (f->rs.apply & BHG_REDSHIFT_DISK) ? f->scene.disk_r_in : -1.0,
+                                     f->cam.origin, &rp));
+    }
 
     // -- every device: (rays, scene images once) trace, shade + sample mean into its slab ---------------------------
     for (size_t r = 0; r < world; r++) {
@@ -631,8 +657,16 @@ try {
             BHG_TRY(bhg_trace_dir_device(s.ctx, &prm, f->cam.origin, nullptr, s.k0.as<double>(), s.n, s.dir.as<double>(),
                                          s.flags.as<uint8_t>(), s.steps.as<uint32_t>(), s.acc.as<uint32_t>(), s.stream));
             if (f->profiling) HIP_TRY(hipEventRecord(s.evs[s.ev_used++].second, s.stream));
-            BHG_TRY(bhg_shade_dir_device(s.ctx, s.dir.as<double>(), s.flags.as<uint8_t>(), s.P, S, s.sky.as<float>(), f->sky_w,
-                                         f->sky_h, nullptr, dst, scatter, s.stream));
+            if (redshift) {   // (sky g needs only the camera state: still direction-only)
+                bhg_scene sc;
+                fill_scene(f, s, &sc);
+                BHG_TRY(bhg_shade_scene_redshift_device(s.ctx, nullptr, s.dir.as<double>(), s.flags.as<uint8_t>(), nullptr, s.P, S,
+                                                        &sc, &prm, &f->rs, f->cam.origin, s.k0.as<double>(), nullptr, dst,
+                                                        scatter, s.stream));
+            } else {
+                BHG_TRY(bhg_shade_dir_device(s.ctx, s.dir.as<double>(), s.flags.as<uint8_t>(), s.P, S, s.sky.as<float>(), f->sky_w,
+                                             f->sky_h, nullptr, dst, scatter, s.stream));
+            }
         } else {
             BHG_TRY(s.end.ensure(s.device, s.n * 6 * sizeof(double)));
             if (has_obj) BHG_TRY(s.obj.ensure(s.device, s.n));
@@ -643,8 +677,13 @@ try {
             if (f->profiling) HIP_TRY(hipEventRecord(s.evs[s.ev_used++].second, s.stream));
             bhg_scene sc;
             fill_scene(f, s, &sc);
-            BHG_TRY(bhg_shade_scene_f32_device(s.ctx, s.end.as<double>(), s.flags.as<uint8_t>(), has_obj ? s.obj.as<int8_t>() : nullptr,
-                                               s.P, S, &sc, dst, scatter, s.stream));
+            if (redshift)
+                BHG_TRY(bhg_shade_scene_redshift_device(s.ctx, s.end.as<double>(), nullptr, s.flags.as<uint8_t>(),
+                                                        has_obj ? s.obj.as<int8_t>() : nullptr, s.P, S, &sc, &prm, &f->rs,
+                                                        f->cam.origin, s.k0.as<double>(), nullptr, dst, scatter, s.stream));
+            else
+                BHG_TRY(bhg_shade_scene_f32_device(s.ctx, s.end.as<double>(), s.flags.as<uint8_t>(), has_obj ? s.obj.as<int8_t>() : nullptr,
+                                                   s.P, S, &sc, dst, scatter, s.stream));
         }
         s.dir_traced = dir_only;
     }

@@ -13,6 +13,7 @@
 
 #include "geodesic_kernels.h"
 #include "device_math.h"
+#include "kerr_start.h"
 
 namespace bhg {
 
@@ -144,8 +145,113 @@ __device__ __forceinline__ void object_colour(const ShadeArgs &A, const double *
     rgb[2] = A.sphere_rgb[j][2] * sum;
 }
 
+// ---- redshift ---------------------------------------------------------------------------------
+// g = nu_obs / nu_em = (k.u_obs) / (k.u_em) of one ray, fp64.  The observer is the ZAMO at the camera (in Schwarzschild the
+// static observer); the Killing constants E = -k_t, L = k_phi come from the CAMERA state (x_c, k0), where the trace starts
+// the ray: they are constants of the motion, and the integrator's drift of them stays out of g.  The emitter, by class:
+//   RS_DISK    Keplerian circular orbit of sense s at the hit radius (down to the photon orbit: inside the ISCO too)
+//   RS_OBJECT  at rest on the sphere (Schwarzschild: static; Kerr: the ZAMO at the hit point)
+//   RS_SKY     at rest at infinity
+// RS_DARK (horizon, start inside) gives 0, RS_NAN gives NaN.  e = the end position (disk / object classes only).
+enum RayClass { RS_DARK = 0, RS_DISK = 1, RS_OBJECT = 2, RS_SKY = 3, RS_NAN = 4 };
+
+// the class bhg_redshift_device gives a ray of these flags (the shade kernels use the branch ray_colour takes instead)
+__device__ __forceinline__ int ray_class(uint32_t fl)
+{
+    if (fl & (BHG_FLAG_HIT_HORIZON_ | BHG_FLAG_START_INSIDE_)) return RS_DARK;
+    if (fl & BHG_FLAG_NAN_) return RS_NAN;
+    if (fl == BHG_FLAG_HIT_OBJECT_) return RS_OBJECT;
+    if (fl == BHG_FLAG_HIT_DISK_) return RS_DISK;
+    return RS_SKY;   // exit sphere, lambda_end reached, step cap, stall: the shader colours them from the sky
+}
+
+// Kerr ZAMO at BL (r, theta): lapse alpha = sqrt(Sigma Delta / A) and frame-dragging rate omega = 2 M a r / A
+__device__ __forceinline__ void kerr_zamo(double M, double a, double r, double c2, double &alpha, double &omega)
+{
+    const double a2 = a * a, s2 = 1.0 - c2;
+    const double Sig = r * r + a2 * c2, Del = r * r - 2.0 * M * r + a2;
+    const double A = (r * r + a2) * (r * r + a2) - a2 * Del * s2;
+    alpha = sqrt(Sig * Del / A);
+    omega = 2.0 * M * a * r / A;
+}
+
+__device__ double redshift_g(const RedshiftParams &P, const double xc[3], const double kc[3], int cls, const double *e)
+{
+    if (cls == RS_DARK) return 0.0;
+    if (cls == RS_NAN || (cls != RS_SKY && !e)) return __builtin_nan("");
+    // The camera receives the traced ray run backwards.  Kerr is invariant under (t, phi) -> (-t, -phi), so that photon has the
+    // traced ray's E and L and runs the traced curve mirrored in phi, where a disk of sense s is the traced picture's disk of
+    // sense -s: the formulas below are the traced ray's, k.u of the TRACED picture, with the sense reversed.
+    const double M = 0.5 * P.r_s, s = -P.sense;
+    if (P.rhs == BHG_RHS_KERR_BL_) {
+        const double a = P.spin;
+        double px[3] = {xc[0], xc[1], xc[2]}, pk[3] = {kc[0], kc[1], kc[2]}, E, L;
+        kerr_cart_to_bl(a, M, 0.0, px, pk, E, L);     // the trace's own E and L, bit for bit
+        const double b = L / E;
+        double st, ct, alpha_c, omega_c;
+        sincos_pi4(px[1], st, ct);
+        kerr_zamo(M, a, px[0], ct * ct, alpha_c, omega_c);
+        const double O = (1.0 - omega_c * b) / alpha_c;   // -k.u_obs / E
+        if (cls == RS_SKY) return O;
+        const double R2 = e[0] * e[0] + e[1] * e[1];
+        if (cls == RS_DISK) {
+            const double r = sqrt(R2 - a * a), sr = sqrt(r), r32 = r * sr, saM = s * a * sqrt(M);
+            const double Om = s * sqrt(M) / (r32 + saM);
+            const double ut = (r32 + saM) / (sqrt(r32) * sqrt(r32 - 3.0 * M * sr + 2.0 * saM));
+            return O / (ut * (1.0 - Om * b));
+        }
+        // object: BL r, cos theta of the Cartesian hit point (x = sqrt(r^2 + a^2) sin th cos ph, z = r cos th)
+        const double z = e[2], bb = R2 + z * z - a * a;
+        const double r = sqrt(0.5 * (bb + sqrt(bb * bb + 4.0 * a * a * z * z)));
+        const double c = z / r;
+        double alpha_h, omega_h;
+        kerr_zamo(M, a, r, c * c, alpha_h, omega_h);
+        return O * alpha_h / (1.0 - omega_h * b);
+    }
+    // Schwarzschild (both Cartesian forms): f = 1 - r_s / r
+    const double rc = sqrt(xc[0] * xc[0] + xc[1] * xc[1] + xc[2] * xc[2]);
+    const double fc = 1.0 - P.r_s / rc;
+    if (cls == RS_SKY) return 1.0 / sqrt(fc);
+    if (cls == RS_OBJECT) {
+        const double rh = sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
+        return sqrt((1.0 - P.r_s / rh) / fc);
+    }
+    // disk: k^t at the camera from the null condition of the Christoffel form, b = L_z / E
+    const double h = P.r_s / (rc - P.r_s);
+    const double nk = (xc[0] * kc[0] + xc[1] * kc[1] + xc[2] * kc[2]) / rc;
+    const double kk = kc[0] * kc[0] + kc[1] * kc[1] + kc[2] * kc[2];
+    const double kt = sqrt((kk + h * nk * nk) / fc);
+    const double b = (xc[0] * kc[1] - xc[1] * kc[0]) / (fc * kt);
+    const double R = sqrt(e[0] * e[0] + e[1] * e[1]);
+    const double Om = s * sqrt(M) / (R * sqrt(R));
+    return sqrt(1.0 - 3.0 * M / R) / (sqrt(fc) * (1.0 - Om * b));
+}
+
+__global__ void __launch_bounds__(256) redshift_kernel(const RedshiftArgs A)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= A.n) return;
+    const double *xc = A.x0 ? A.x0 + i * 3 : A.p.x0;
+    A.g[i] = redshift_g(A.p, xc, A.k0 + i * 3, ray_class(A.flags[i]), A.end ? A.end + i * 6 : nullptr);
+}
+
+// the shade kernels' redshift instance: rgb *= g^n for a ray of a class the caller selected
+__device__ __forceinline__ void redshift_weigh(const ShadeArgs &A, uint64_t i, int cls, uint32_t bit, const double *e, double rgb[3])
+{
+    if (!(A.rs.apply & bit)) return;
+    const double g = redshift_g(A.rs, A.rs.x0, A.k0 + i * 3, cls, e), n = A.rs.exponent;
+    // the exponents of the model, 4 (bolometric) and 3 (specific intensity), as products (libm's pow was a third of the kernel)
+    const double g2 = g * g;
+    const double w = n == 4.0 ? g2 * g2 : (n == 3.0 ? g2 * g : pow(g, n));
+    rgb[0] *= w;
+    rgb[1] *= w;
+    rgb[2] *= w;
+}
+
 // The colour of ONE ray (sample s of pixel p): black for a horizon ray (:242-244), the disk's / an object's colour, or the
 // sky in its exit direction.
+// RS: the redshift instance (rgb *= g^n by class); without it the kernels are the frame path's as they were.
+template <bool RS>
 __device__ __forceinline__ void ray_colour(const ShadeArgs &A, uint64_t i, uint8_t fl, double c0, double c1, double c2, double rgb[3])
 {
     rgb[0] = rgb[1] = rgb[2] = 0.0;
@@ -153,10 +259,12 @@ __device__ __forceinline__ void ray_colour(const ShadeArgs &A, uint64_t i, uint8
     const double *e = A.end + i * 6;
     if (fl == BHG_FLAG_HIT_DISK_ && A.disk_r_out > 0.0 && A.end) {
         disk_colour(A, e, rgb);
+        if (RS) redshift_weigh(A, i, RS_DISK, BHG_REDSHIFT_DISK_, e, rgb);
         return;
     }
     if (fl == BHG_FLAG_HIT_OBJECT_ && A.object_id && A.end) {
         object_colour(A, e, (int)A.object_id[i], rgb);
+        if (RS) redshift_weigh(A, i, RS_OBJECT, BHG_REDSHIFT_OBJECTS_, e, rgb);
         return;
     }
     // theta = 1 - acos(d_z / |d|) / pi (:373), phi = atan2(d_y, d_x) / pi (:374); exit directions are not unit
@@ -166,6 +274,8 @@ __device__ __forceinline__ void ray_colour(const ShadeArgs &A, uint64_t i, uint8
     const double theta = 1.0 - atan2_fast(rho, c2) * 0.3183098861837907;
     const double phi = atan2_fast(c1, c0) * 0.3183098861837907;
     sky_lookup(A.sky, A.sky_w, A.sky_h, -phi, 2.0 * theta - 1.0, rgb);  // :375
+    // (start-inside rays carry the horizon flag: black above; a NaN ray is coloured as it always was, unweighted)
+    if (RS && !(fl & BHG_FLAG_NAN_)) redshift_weigh(A, i, RS_SKY, BHG_REDSHIFT_SKY_, nullptr, rgb);
 }
 
 __device__ __forceinline__ void write_pixel(const ShadeArgs &A, uint64_t p, const double acc[3])
@@ -191,6 +301,7 @@ __device__ __forceinline__ void write_pixel(const ShadeArgs &A, uint64_t p, cons
 // consecutive rays of the [S][P] layout (coalesced).  Against one thread per pixel walking its samples one after the
 // other (round 3; kept below for S > 256) this puts S times as many independent atan2 / texel-gather chains in flight:
 // the kernel is a latency chain per ray, not a bandwidth problem (131 MB in, 16 MB out per config-2 frame).
+template <bool RS>
 __global__ void __launch_bounds__(256) shade_reduce_kernel(const ShadeArgs A, const uint32_t ppb)
 {
     __shared__ double col[256 * 3];
@@ -203,7 +314,7 @@ __global__ void __launch_bounds__(256) shade_reduce_kernel(const ShadeArgs A, co
         // exit directions: the second half of the end records, or (direction-only traces of sky frames) an array of their own
         const double *d = A.dir ? A.dir + i * 3 : A.end + i * 6 + 3;
         double rgb[3];
-        ray_colour(A, i, A.flags[i], d[0], d[1], d[2], rgb);
+        ray_colour<RS>(A, i, A.flags[i], d[0], d[1], d[2], rgb);
         col[t * 3 + 0] = rgb[0];
         col[t * 3 + 1] = rgb[1];
         col[t * 3 + 2] = rgb[2];
@@ -223,6 +334,7 @@ __global__ void __launch_bounds__(256) shade_reduce_kernel(const ShadeArgs A, co
 }
 
 // More samples than a workgroup has threads: one thread per pixel, samples accumulated in registers in sample order.
+template <bool RS>
 __global__ void __launch_bounds__(256) shade_reduce_serial_kernel(const ShadeArgs A)
 {
     const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -232,7 +344,7 @@ __global__ void __launch_bounds__(256) shade_reduce_serial_kernel(const ShadeArg
         const uint64_t i = (uint64_t)s * A.n_pixels + p;
         const double *d = A.dir ? A.dir + i * 3 : A.end + i * 6 + 3;
         double rgb[3];
-        ray_colour(A, i, A.flags[i], d[0], d[1], d[2], rgb);
+        ray_colour<RS>(A, i, A.flags[i], d[0], d[1], d[2], rgb);
         acc[0] += rgb[0];
         acc[1] += rgb[1];
         acc[2] += rgb[2];
@@ -282,15 +394,31 @@ hipError_t launch_raygen(const RaygenArgs &a, hipStream_t s)
     return hipGetLastError();
 }
 
+hipError_t launch_redshift(const RedshiftArgs &a, hipStream_t s)
+{
+    if (a.n == 0) return hipSuccess;
+    BHG_LAUNCH(redshift_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_shade(const ShadeArgs &a, hipStream_t s)
 {
     if (a.n_pixels == 0) return hipSuccess;
+    const bool rs = a.rs.apply != 0;
     if (a.samples > 256) {
-        BHG_LAUNCH(shade_reduce_serial_kernel, dim3((unsigned)((a.n_pixels + 255) / 256)), dim3(256), 0, s, a);
+        const dim3 grid((unsigned)((a.n_pixels + 255) / 256));
+        if (rs)
+            BHG_LAUNCH(shade_reduce_serial_kernel<true>, grid, dim3(256), 0, s, a);
+        else
+            BHG_LAUNCH(shade_reduce_serial_kernel<false>, grid, dim3(256), 0, s, a);
         return hipGetLastError();
     }
     const uint32_t ppb = 256u / (uint32_t)a.samples;      // pixels per workgroup
-    BHG_LAUNCH(shade_reduce_kernel, dim3((unsigned)((a.n_pixels + ppb - 1) / ppb)), dim3(256), 0, s, a, ppb);
+    const dim3 grid((unsigned)((a.n_pixels + ppb - 1) / ppb));
+    if (rs)
+        BHG_LAUNCH(shade_reduce_kernel<true>, grid, dim3(256), 0, s, a, ppb);
+    else
+        BHG_LAUNCH(shade_reduce_kernel<false>, grid, dim3(256), 0, s, a, ppb);
     return hipGetLastError();
 }
 

@@ -27,6 +27,9 @@ constexpr uint32_t BHG_FLAG_NAN_ = 64u;
 constexpr uint32_t BHG_FLAG_HIT_DISK_ = 128u;
 constexpr uint32_t BHG_FLAG_HIT_OBJECT_ = 0x88u;
 constexpr int BHG_MAX_SPHERES_ = 8;
+constexpr uint32_t BHG_REDSHIFT_DISK_ = 1u;
+constexpr uint32_t BHG_REDSHIFT_OBJECTS_ = 2u;
+constexpr uint32_t BHG_REDSHIFT_SKY_ = 4u;
 constexpr int BHG_METHOD_DP54_ = 0;
 constexpr int BHG_METHOD_RK4_ = 1;
 constexpr int BHG_RHS_CHRISTOFFEL_ = 0;
@@ -98,6 +101,28 @@ struct RaygenArgs {
     double rot[9];          // row-major camera rotation
 };
 
+// redshift of a ray between the camera's ZAMO and its emitter (frame_kernels.hip, redshift_g):
+// the metric, the camera and the redshift settings of bhg_redshift
+struct RedshiftParams {
+    double x0[3];      // camera, BH-centred (a shared origin; redshift_kernel may read a per-ray one instead)
+    double r_s, spin;  // metric: r_s = 2M, Kerr a (rhs == BHG_RHS_KERR_BL_)
+    double sense;      // disk sense, +1 = counter-clockwise seen from +z, or -1
+    double exponent;   // colour weight g^exponent (shade kernels only)
+    int32_t rhs;       // BHG_RHS_*
+    uint32_t apply;    // BHG_REDSHIFT_* classes the shade kernels weigh; 0 = off
+};
+
+// one thread per ray: g[i] from the camera state (x0, k0) and the end record (bhg_redshift_device)
+struct RedshiftArgs {
+    RedshiftParams p;
+    const double *x0;      // [n][3] or nullptr -> p.x0
+    const double *k0;      // [n][3]
+    const double *end;     // [n][6] or nullptr (then only sky, horizon and NaN rays have a g; disk / object rays get NaN)
+    const uint8_t *flags;  // [n]
+    double *g;             // [n]
+    uint64_t n;
+};
+
 // shading + per-pixel multisample mean (frame_kernels.hip)
 struct ShadeArgs {
     const double *end;     // [S*n_pixels][6], or nullptr when dir is given
@@ -118,10 +143,15 @@ struct ShadeArgs {
     double spheres[BHG_MAX_SPHERES_][4];
     double sphere_rgb[BHG_MAX_SPHERES_][3];
     double lamps[4][4];  // {x, y, z, intensity}
+    // redshift (bhg_shade_scene_redshift_device): launch_shade takes the redshift instance of the shade kernels when
+    // rs.apply != 0; the other instance -- the frame path without redshift -- never reads these two members
+    const double *k0;      // [S*n_pixels][3] camera directions, or nullptr when rs.apply == 0
+    RedshiftParams rs;
 };
 
 hipError_t launch_raygen(const RaygenArgs &a, hipStream_t s);
 hipError_t launch_shade(const ShadeArgs &a, hipStream_t s);
+hipError_t launch_redshift(const RedshiftArgs &a, hipStream_t s);
 hipError_t launch_split_end(const double *end, uint64_t n, double *loc, double *dir, hipStream_t s);
 hipError_t launch_gather_rows4(const float *src, const int64_t *index, uint64_t n, float *dst, hipStream_t s);
 

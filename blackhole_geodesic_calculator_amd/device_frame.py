@@ -80,6 +80,8 @@ class DeviceFrame:
         self.sphere_rgb = None
         self.lamps = None
         self.d_obj = None
+        self.redshift = None     # _ffi.Redshift (set_redshift) or None: off
+        self._params = None      # the parameters of the last trace (the redshift shade needs its metric)
 
     def _stream(self):
         return torch.cuda.current_stream(self.dev).cuda_stream
@@ -118,6 +120,12 @@ class DeviceFrame:
         if self.d_obj is None:
             self.d_obj = torch.empty(self.n, dtype=torch.int8, device=self.dev)
 
+    def set_redshift(self, apply=("disk", "objects", "sky"), exponent=4.0, disk_sense=1):
+        """Weigh the colour of every ray of a class in `apply` ("disk", "objects", "sky") by g^exponent, g = nu_obs / nu_em
+        between the camera's ZAMO and the emitter (bhg_shade_scene_redshift_device; include/bhgeo.h).  apply=() or None:
+        off, the shade calls as without redshift."""
+        self.redshift = _ffi.make_redshift(apply, exponent, disk_sense) if apply else None
+
     def pixel_cost(self):
         """Attempted steps of the last trace summed over the samples of each pixel ([P], order of `pixels`): the
         measured cost dist.measured_tile_cost() orders and deals the tiles by."""
@@ -136,6 +144,7 @@ class DeviceFrame:
         if params.order_blocks == 0 and self.S > 1:
             params = _copy_params(params)
             params.order_blocks = self.S
+        self._params = params
         has_obj = self.spheres is not None and len(self.spheres) > 0
         self._dir_traced = self.directions_only and not has_obj and self.disk is None and not (params.disk_r_out > 0.0)
         self._traced = "dir" if self._dir_traced else "end"
@@ -175,8 +184,19 @@ class DeviceFrame:
             raise RuntimeError("the last trace wrote exit directions only, but the frame now has a disk / objects: trace() again")
         return traced
 
+    def _shade_redshift(self, form, d_rgba=0, d_rgba_f32=0, scatter=None):
+        self.ctx.shade_scene_redshift_device(self.d_end.data_ptr() if form == "end" else 0, self.d_flags.data_ptr(), self.P, self.S,
+                                             self.scene(), self._params, self.redshift, self.origin, self.d_k0.data_ptr(),
+                                             d_rgba=d_rgba, d_rgba_f32=d_rgba_f32,
+                                             d_object_id=0 if self.d_obj is None else self.d_obj.data_ptr(),
+                                             d_scatter=0 if scatter is None else scatter.data_ptr(),
+                                             d_end_dir=self.d_dir.data_ptr() if form == "dir" else 0, stream=self._stream())
+
     def shade(self):
         form = self._shade_form()
+        if self.redshift is not None:
+            self._shade_redshift(form, d_rgba=self.d_rgba.data_ptr())
+            return self.d_rgba
         if self.disk is not None or (self.spheres is not None and len(self.spheres) > 0):
             self.ctx.shade_scene_device(self.d_end.data_ptr(), self.d_flags.data_ptr(), self.P, self.S, self.scene(),
                                         self.d_rgba.data_ptr(),
@@ -196,6 +216,9 @@ class DeviceFrame:
         flat pixel ids): what layer.rect takes, without the fp64 intermediate."""
         form = self._shade_form()
         assert out.dtype == torch.float32 and out.is_contiguous()
+        if self.redshift is not None:
+            self._shade_redshift(form, d_rgba_f32=out.data_ptr(), scatter=scatter)
+            return out
         if form == "dir":
             self.ctx.shade_dir_device(self.d_dir.data_ptr(), self.d_flags.data_ptr(), self.P, self.S, self.d_sky.data_ptr(),
                                       self.sky_wh[0], self.sky_wh[1], d_rgba_f32=out.data_ptr(),
@@ -264,7 +287,12 @@ class FrameBatch:
                               d_n_accepted=self.d_acc.data_ptr(),
                               stream=torch.cuda.current_stream(self.dev).cuda_stream)
         for f in self.frames:    # (whole records, whatever the members were constructed with)
-            f._dir_traced, f._traced = False, "end"
+            f._dir_traced, f._traced, f._params = False, "end", params
+
+    def set_redshift(self, apply=("disk", "objects", "sky"), exponent=4.0, disk_sense=1):
+        """DeviceFrame.set_redshift for every member frame."""
+        for f in self.frames:
+            f.set_redshift(apply, exponent, disk_sense)
 
     def shade(self):
         return [f.shade() for f in self.frames]

@@ -63,7 +63,7 @@ class GeodesicIntegratorSchwarzschild:
                                 disk_r_out=disk[1] if disk else 0.0, spin=self.spin, time_like=self.time_like)
 
     # ------------------------------------------------------------------------------------
-    def trace(self, k0, x0, max_step=np.inf, curve_end=50.0, r_exit=0.0, disk=None, spheres=None):
+    def trace(self, k0, x0, max_step=np.inf, curve_end=50.0, r_exit=0.0, disk=None, spheres=None, redshift=None):
         """Batched solve.  k0[N,3] (or [...,3]); x0[3] shared origin or same leading shape as k0.
         r_exit: outward sphere-exit radius (Limited engine's ray_trace, Limited...py:273-278);
         disk=(R_in, R_out): thin disk in z = 0, first crossing inside the annulus ends the ray with
@@ -77,6 +77,9 @@ class GeodesicIntegratorSchwarzschild:
             ray_blackhole_hit[...]     uint8, 1 where the ray ended on the horizon
             flags[...], n_steps[...], n_accepted[...]
             object_id[...]             int8, only with spheres: index of the sphere hit, else -1
+            g[...]                     only with redshift=dict(disk_sense=+1 or -1): nu_obs / nu_em of each ray between
+                                       the camera's ZAMO and its emitter (disk in Keplerian orbit of that sense, object at
+                                       rest, sky at rest at infinity; 0 for horizon rays, NaN for NaN rays), bhg_redshift_host
         """
         k0 = np.asarray(k0, dtype=np.float64)
         lead = k0.shape[:-1]
@@ -98,6 +101,9 @@ class GeodesicIntegratorSchwarzschild:
         }
         if obj is not None:
             out["object_id"] = obj.reshape(lead)
+        if redshift is not None:
+            rs = _ffi.make_redshift(apply=(), disk_sense=redshift.get("disk_sense", 1))
+            out["g"] = self._ctx.redshift(k0f, x0f, self.params(max_step, curve_end, r_exit, disk), rs, flags, end).reshape(lead)
         return out
 
     # ------------------------------------------------------------------------------------

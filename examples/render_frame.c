@@ -5,7 +5,8 @@
  *       -Wl,-rpath,$PWD/blackhole_geodesic_calculator_amd -lm -o build/render_frame && build/render_frame [devices]
  *
  * `devices` is a comma-separated list of device indices (default "0"; "0,0" shards the frame over two contexts of one
- * GPU, "0,1,2,3,4,5,6,7" over the eight GPUs of a node).  This is the call sequence a compiled host would make in place
+ * GPU, "0,1,2,3,4,5,6,7" over the eight GPUs of a node).  A second argument `redshift` adds a thin disk (R 3..9) and turns
+ * redshift on for it (bhg_frame_set_redshift: the disk's colour weighted by g^4, disk counter-clockwise seen from +z).  This is the call sequence a compiled host would make in place
  * of the reference's frame loop (raytracer/RelativisticRenderEngine.py:152-267: render_scene -> ray_trace).
  */
 #include <math.h>
@@ -77,6 +78,15 @@ int main(int argc, char **argv)
     bhg_default_params(&p);
     p.lambda_end = 60.0;
     p.r_exit = 40.0;
+    if (argc > 2 && strcmp(argv[2], "redshift") == 0) {
+        sc.sky = NULL;   /* (keep the sky uploaded above) */
+        sc.disk_r_in = p.disk_r_in = 3.0, sc.disk_r_out = p.disk_r_out = 9.0;
+        const bhg_redshift rs = {BHG_REDSHIFT_DISK, +1, 4.0};
+        if (bhg_frame_set_scene(fr, &sc) != BHG_OK || bhg_frame_set_redshift(fr, &rs) != BHG_OK) {
+            fprintf(stderr, "redshift: %s\n", bhg_last_error());
+            return 4;
+        }
+    }
     float *rgba = malloc(sizeof(float) * W * H * 4);
     if (bhg_frame_render(fr, &p, rgba) != BHG_OK) {
         fprintf(stderr, "bhg_frame_render: %s\n", bhg_last_error());

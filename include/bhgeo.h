@@ -51,12 +51,17 @@
 extern "C" {
 #endif
 
-#define BHG_ABI_VERSION 8   /* 8: bhg_trajectory_objects (sampled curves that end on object spheres); nothing of ABI 7 changed.
+#define BHG_ABI_VERSION 9   /* 9: redshift -- bhg_redshift_device / _host, bhg_shade_scene_redshift_device, bhg_frame_set_redshift,
+                                  bhg_redshift_size, struct bhg_redshift;
+                                  nothing of ABI 8 changed.
+                               8: bhg_trajectory_objects (sampled curves that end on object spheres), the frame gather mode
+                                  BHG_FRAME_GATHER_COPY_PEERCALL; nothing of ABI 7 changed.
                                7: the binder's handshake -- bhg_abi_check, bhg_*_size, bhg_default_params_sized; bhg_peak_probe.
                                6: bhg_frame_* (library-owned frame, N devices), bhg_deal_tiles, bhg_params.time_like (104 bytes) */
 
 #define BHG_ABI_COMPAT_MIN 7 /* bhg_abi_check serves bindings written for this ABI or later: every symbol, struct layout and
-                                meaning they know is unchanged (ABI 8 only ADDED an entry point) */
+                                meaning they know is unchanged (ABIs 8 and 9 only ADDED entry points, a gather mode,
+                                a struct and constants) */
 
 /* return codes */
 #define BHG_OK 0
@@ -432,6 +437,56 @@ int bhg_frame_last_ms(bhg_frame *frame, float *trace_ms, float *root_ms);
  * returned in *n_out. */
 int bhg_deal_tiles(int32_t width, int32_t height, int32_t tile, int32_t world, const double *tile_cost, int32_t visit_by_cost,
                    double root_share, int32_t rank, int64_t *pixels, size_t capacity, size_t *n_out);
+
+/* --- redshift (ABI 9) --------------------------------------------------------------------------
+ * g = nu_obs / nu_em = (k.u_obs) / (k.u_em) per ray.  The observer is the ZAMO (zero-angular-momentum observer) at the
+ * camera -- in Schwarzschild the static observer; the ray's Killing constants come from its CAMERA state (x0, k0), not from
+ * its end record; the photon it receives runs the traced curve backwards (Kerr: mirrored in phi, by the (t, phi) -> (-t, -phi)
+ * symmetry, with the same E and L -- so the traced picture's disk has the opposite sense).  Emitters: the thin disk in
+ * Keplerian circular orbits of sense disk_sense (+1 = counter-clockwise seen from +z, -1 = clockwise: the half moving
+ * towards the camera is blueshifted), treated as Keplerian down to the photon orbit (inside the ISCO too: the model's choice); an
+ * object sphere at rest (Schwarzschild: static; Kerr: the ZAMO at the hit point); the sky at rest at infinity.  By flags:
+ * horizon and start-inside rays g = 0, BHG_FLAG_NAN rays NaN, BHG_FLAG_HIT_DISK / _HIT_OBJECT rays the disk / object g,
+ * every other ray (exit sphere, lambda_end, step cap, stall: the rays the shader colours from the sky) the sky's g.
+ * Shading with redshift multiplies a ray's RGB by g^exponent when its class is in `apply` (4: bolometric intensity,
+ * 3: specific intensity at a fixed frequency); hues are not changed.  Refused (BHG_E_INVALID): time_like = 1, a disk
+ * whose r_in lies at or inside the circular photon orbit of the traced picture's sense s = -disk_sense (Schwarzschild 3M;
+ * Kerr 2M[1 + cos(2/3 arccos(-s a / M))], in Boyer-Lindquist r = sqrt(r_in^2 - a^2)), a disk_sense other than +-1, an exponent
+ * that is not finite, apply bits outside BHG_REDSHIFT_DISK | _OBJECTS | _SKY.  The calls use no context workspace: each
+ * is one launch on the stream it is given, ordered like any other work on that stream. */
+#define BHG_REDSHIFT_DISK 1u
+#define BHG_REDSHIFT_OBJECTS 2u
+#define BHG_REDSHIFT_SKY 4u
+typedef struct bhg_redshift {
+    uint32_t apply;       /* BHG_REDSHIFT_* classes whose colour is weighted by g^exponent; 0 = off */
+    int32_t disk_sense;   /* +1 or -1 */
+    double exponent;      /* 4 = bolometric, 3 = specific intensity */
+} bhg_redshift;
+size_t bhg_redshift_size(void);
+/* d_g [n] = g of every ray of a bhg_trace*_device call (whatever `apply` says): x0_shared (HOST [3]) or d_x0 [n][3] and
+ * d_k0 [n][3] as given to the trace, its d_end [n][6] (may be NULL: then disk and object rays get NaN) and d_flags [n].
+ * p: the trace's parameters (metric, spin, disk).  Enqueues one launch on `stream` and returns. */
+int bhg_redshift_device(bhg_context *ctx, const bhg_params *p, const bhg_redshift *rs, const double *x0_shared,
+                        const double *d_x0, const double *d_k0, const double *d_end, const uint8_t *d_flags, size_t n,
+                        double *d_g, void *stream);
+/* The same on HOST arrays (x0_is_shared != 0: x0 is [3], else [n][3]; end may be NULL); blocking, on the context's stream.
+ * (Named _host: in C the struct's typedef name bhg_redshift and a function of that name cannot coexist.) */
+int bhg_redshift_host(bhg_context *ctx, const bhg_params *p, const bhg_redshift *rs, const double *x0, int x0_is_shared,
+                      const double *k0, const double *end, const uint8_t *flags, size_t n, double *g);
+/* bhg_shade_scene_device / _f32_device / bhg_shade_dir_device with redshift: each ray's colour is weighted by g^exponent
+ * inside the shade kernel (no g array).  The camera: x0_shared (HOST [3]) and d_k0 [samples * n_pixels][3], the directions
+ * the rays were traced from; p: the trace's parameters.  d_end [n][6] as there, or NULL for a direction-only sky frame:
+ * then d_end_dir [n][3] (bhg_trace_dir_device) and a scene without disk and spheres.  d_rgba (fp64) and / or d_rgba_f32
+ * (float RGBA, optionally scattered by d_scatter) -- either may be NULL, not both.  rs = NULL or apply = 0: exactly the
+ * call without redshift, bit for bit. */
+int bhg_shade_scene_redshift_device(bhg_context *ctx, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
+                                    const int8_t *d_object_id, size_t n_pixels, int32_t samples, const bhg_scene *scene,
+                                    const bhg_params *p, const bhg_redshift *rs, const double *x0_shared,
+                                    const double *d_k0, double *d_rgba, float *d_rgba_f32, const int64_t *d_scatter,
+                                    void *stream);
+/* Redshift in every later bhg_frame_render (every device, every gather mode; direction-only sky frames stay direction-only).
+ * rs = NULL or apply = 0: the frame without redshift, bit for bit.  Checked against the trace parameters at render. */
+int bhg_frame_set_redshift(bhg_frame *frame, const bhg_redshift *rs);
 
 /* Acceleration probe: acc[n][3] = -Gamma^i_{mu nu} k^mu k^nu at (x[n][3], k[n][3]); host buffers.
  * Lets tests compare the device RHS with the oracle's term by term.  With rhs_form = BHG_RHS_KERR_BL the triples
