@@ -634,22 +634,19 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres,
     c->last_stream = s;
     c->launched = true;
 
-    // Workspace, grown on demand (the first call at a new size allocates; steady-state calls do not):
-    //   ws      [n][8] doubles  only in a build without the inlined prepare: that pass's records {a0, h0, r0, 0, E, L} (the
-    //                           trace kernels work their start records out themselves; parked steps live in the waves' LDS pools)
+    // Workspace, grown on demand (the first call at a new size allocates; steady-state calls do not; the trace kernels work
+    // their start records out themselves and parked steps live in the waves' LDS pools, so there are no per-ray records):
     //   flags   [n] bytes       when the caller does not want flags
     //   n_steps / n_accepted [n] u32 when the caller does not want them (the kernels never test these pointers)
     const bool has_exit = p->r_exit > 0.0;
     const bool kerr = p->rhs_form == BHG_RHS_KERR_BL;
     // the kernels' right-hand-side id: the time-like Christoffel form is one of its own (the Kerr kernels take the norm at the start)
     const int rhs_id = (p->time_like && p->rhs_form == BHG_RHS_CHRISTOFFEL) ? bhg::BHG_RHS_CHRISTOFFEL_TL_ : p->rhs_form;
-    const bool needs_ws = bhg::needs_prepare_ws(p->rhs_form);   // only in a build without the inlined prepare
-    const size_t sz_ws = needs_ws ? n * 8 * sizeof(double) : 0;
     const size_t sz_flags = d_flags ? 0 : ((n + 7) & ~size_t(7));
     const size_t sz_u32 = n * sizeof(uint32_t);
     const size_t sz_steps = !d_n_steps ? sz_u32 : 0;
     const size_t sz_acc = !d_n_accepted ? sz_u32 : 0;
-    rc = ensure(&c->d_ws, &c->d_ws_bytes, sz_ws + sz_flags + sz_steps + sz_acc + 64);
+    rc = ensure(&c->d_ws, &c->d_ws_bytes, sz_flags + sz_steps + sz_acc + 64);
     if (rc != BHG_OK) return rc;
     if (!d_end && kerr) {
         // direction-only Kerr call: the end records are workspace (the Boyer-Lindquist states the finalize pass converts),
@@ -661,9 +658,9 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres,
         d_end_dir = nullptr;
     }
     char *wsb = (char *)c->d_ws;
-    uint8_t *w_flags = (uint8_t *)(wsb + sz_ws);
-    uint32_t *w_steps = (uint32_t *)(wsb + sz_ws + sz_flags);
-    uint32_t *w_acc = (uint32_t *)(wsb + sz_ws + sz_flags + sz_steps);
+    uint8_t *w_flags = (uint8_t *)wsb;
+    uint32_t *w_steps = (uint32_t *)(wsb + sz_flags);
+    uint32_t *w_acc = (uint32_t *)(wsb + sz_flags + sz_steps);
 
     bhg::TraceArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -672,7 +669,6 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres,
     a.end = d_end;
     // (Kerr end states are converted from Boyer-Lindquist by a pass over whole records: directions are split off after it)
     a.end_dir = kerr ? nullptr : d_end_dir;
-    a.ws = needs_ws ? (double *)c->d_ws : nullptr;
     a.flags = d_flags ? d_flags : w_flags;
     a.n_steps = d_n_steps ? d_n_steps : w_steps;
     a.n_accepted = d_n_accepted ? d_n_accepted : w_acc;
@@ -696,13 +692,9 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres,
     a.spin = p->spin;
     a.mu2 = p->time_like ? 1.0 : 0.0;
     a.r_hor = p->r_s;
-    a.from_records = 0;
-    a.ws_stride = 6;
     if (p->rhs_form == BHG_RHS_KERR_BL) {
         const double M = 0.5 * p->r_s;
         a.r_hor = (M + std::sqrt(M * M - p->spin * p->spin)) * (1.0 + BHG_KERR_HORIZON_MARGIN);
-        a.from_records = needs_ws ? 1 : 0;     // (only a build without the inlined prepare starts Kerr rays from records)
-        a.ws_stride = 8;
     }
     a.max_steps = p->max_steps ? p->max_steps : (1u << 20);
     a.min_step_cap = 40.0 * std::nextafter(std::fmax(p->lambda_end, 1.0), INFINITY) * 2.220446049250313e-16;
@@ -761,7 +753,6 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres,
                 std::fwrite(host, 1, sizeof(host), f);
                 std::fclose(f);
             }
-            HIP_TRY(hipMemset(dbuf + BHG_DIAG_HIST, 0, 131 * sizeof(unsigned long long)));   // (the histogram accumulates: one launch per dump)
         }
     }
 #endif
@@ -1568,7 +1559,6 @@ int bhg_trajectory_objects(bhg_context *c, const bhg_params *p, const double *sp
     if (p->rhs_form == BHG_RHS_KERR_BL) {
         const double M = 0.5 * p->r_s;
         a.r_hor = (M + std::sqrt(M * M - p->spin * p->spin)) * (1.0 + BHG_KERR_HORIZON_MARGIN);
-        a.from_records = 1;                    // (the trajectory kernel reads the prepare pass's records)
         a.ws_stride = 8;
     }
     a.max_steps = p->max_steps ? p->max_steps : (1u << 20);

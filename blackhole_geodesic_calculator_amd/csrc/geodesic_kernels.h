@@ -62,12 +62,11 @@ struct TraceArgs {
     // ---- chunk 2: parking (in the step loop's event branch), then the rare paths
     double *end_dir;             // nullptr, or [n][3]: FINAL states are written as their direction half only, here (end then
                                  // only holds the parked / resume records of rays that need them: a workspace)
-    double *ws;                  // [n][ws_stride] per-ray records: prepare {a0, h0, r0, 0, E, L}, park {a1, t, h, h_next, E, L}, resume {a, h, r, t, E, L}
-                                 // (park / resume records are written and read back by ONE wavefront of the trace kernel)
+    double *ws;                  // trajectory calls only (nullptr for a trace): [n][ws_stride] records {a0, h0, r0, 0, E, L}
+                                 // the prepare pass writes and the trajectory kernel starts from
     uint32_t max_steps;
-    int32_t ws_stride;           // doubles per ray record in ws: 6, or 8 for Kerr ({E, L} appended)
+    int32_t ws_stride;           // trajectory calls: doubles per record in ws, 6, or 8 for Kerr ({E, L} appended)
     int32_t n_spheres;           // object spheres inside the curved region (Schwarzschild forms only)
-    int32_t from_records;        // rays start from the records the prepare pass wrote (Kerr)
     const double *k0;            // [n][3]
     const double *x0;            // [n][3] or nullptr -> x0s
     unsigned long long *counter; // 8 slice counters (256 B apart), zero at launch
@@ -75,17 +74,13 @@ struct TraceArgs {
     uint64_t n;                  // rays in the call
     double k0s[3];               // the direction of a ONE-ray trajectory call (k0 == nullptr)
     double x0s[3];
-    int32_t inline_prepare;      // set by the launcher: no prepare launch, the trace waves work the start records out (Schwarzschild forms)
     int32_t order_blocks;        // work-order hint: n = order_blocks * order_block_len, batches are
     uint64_t order_block_len;    // handed out chunk-major over the blocks; 0/1 = plain order
     int8_t *object_id;           // [n] or nullptr: sphere index of rays that end with BHG_FLAG_HIT_OBJECT, else -1
-    unsigned long long *diag;    // diagnostic builds only (BHG_DIAG): [grid][8] per-wave stamps; + BHG_DIAG_HIST: event-coherence histogram
+    unsigned long long *diag;    // diagnostic builds only (BHG_DIAG): [grid][8] per-wave stamps
     uint32_t dbg_idx;            // diagnostic builds: ray whose controller trace is logged
     double spheres[BHG_MAX_SPHERES_][4];  // {cx, cy, cz, radius}, BH-centred
 };
-
-#define BHG_DIAG_HIST 400000   // u64 index into `diag`: H[0..64] iterations by lanes parking ONE short event, [65..129] the lanes
-                               // stepping in those iterations, [130] all parked steps (zeroed after every dump)
 
 // camera-ray generation (frame_kernels.hip)
 struct RaygenArgs {
@@ -155,13 +150,10 @@ hipError_t launch_redshift(const RedshiftArgs &a, hipStream_t s);
 hipError_t launch_split_end(const double *end, uint64_t n, double *loc, double *dir, hipStream_t s);
 hipError_t launch_gather_rows4(const float *src, const int64_t *index, uint64_t n, float *dst, hipStream_t s);
 
-// ev: nullptr, or 3 events recorded around prepare | trace on stream s
+// ev: nullptr, or 3 events recorded around prepare | trace on stream s (no prepare launch runs: the first two are back to back)
 // evt: bit 0 = sphere-exit event compiled in, bit 1 = disk-plane event, bit 2 = object spheres (then all three)
 hipError_t launch_trace(const TraceArgs &a, int method, int rhs, int evt, int grid, hipStream_t s, hipEvent_t *ev);
 hipError_t trace_occupancy(int method, int rhs, int evt, int *blocks_per_cu);
-// does a trace launch of this right-hand side read per-ray prepare records from TraceArgs::ws (Kerr always; every form
-// when the kernels were built with -DBHG_INLINE_PREPARE=0)?  The C-ABI layer sizes the workspace by it.
-bool needs_prepare_ws(int rhs);
 // Kerr: after the last pass of a call, Boyer-Lindquist end states -> Cartesian
 hipError_t launch_kerr_finalize(const TraceArgs &a, double *dir_out, hipStream_t s);
 // the Kerr instantiations live in their own translation unit (geodesic_kernels_kerr.hip: same source, same flags --

@@ -43,16 +43,6 @@
 #include "device_math.h"
 #include "kerr_start.h"
 
-// 1: the trace kernels work out the start records themselves (no prepare launch); 0: every form runs the prepare
-// pass (the code is then not compiled into the trace kernels at all).  The trajectory kernels always use the pass.
-// Steps run AHEAD of the step loop by the short drain (EV_AHEAD, RunsAhead below): on unless built with -DBHG_NO_AHEAD
-#if !defined(BHG_NO_AHEAD) && !defined(BHG_AHEAD)
-#define BHG_AHEAD 1
-#endif
-#ifndef BHG_INLINE_PREPARE
-#define BHG_INLINE_PREPARE 1
-#endif
-
 // slack factor on the disk pre-filter's excursion bound (tuning builds override it)
 #ifndef BHG_DISK_SLACK
 #define BHG_DISK_SLACK (1.0 + 1e-9)
@@ -525,7 +515,7 @@ __device__ __forceinline__ void entry_put(QEntry<RHS> &e, const double x[3], con
 
 // Kinds of event a parked step may hold (the `bits` word of its record; they never reach flags[]).
 constexpr uint32_t EV_HORIZON = 1u, EV_EXIT = 2u, EV_DISK = 4u, EV_OBJ = 8u;
-// ... and (BHG_AHEAD builds) a step that has NOT been computed yet: the lane's last accepted step ended close enough to
+// ... and a step that has NOT been computed yet: the lane's last accepted step ended close enough to
 // the exit sphere that the next one is expected to leave it, so the lane hands the ray -- a queue-style record: the state at
 // the step's start, the |h| to try, the radius there -- to the short drain, which runs the WHOLE step (stages, error norm,
 // controller, event tests) and then locates the exit; the lane takes a fresh ray one iteration earlier and the step is
@@ -539,25 +529,13 @@ constexpr uint32_t EV_REQUEUE = 32u;     // (marks the bits of a queue entry wri
 // source for R behind the stages) spilled 140-156 B per lane, part of it in the MAIN loop: +32 % time.  Handing a rejected
 // step back from P, its bits in `kind` (not even one more live word), leaves 52 B in the drains and nothing in the main loop.
 // Not the reduced form with the disk (<1,3> spills into its main loop with it).  The Boyer-Lindquist kernels: with the disk
-// (Kerr + disk -1.5 % time), not without (a Kerr exit-only frame +2.6 %).  BHG_NO_AHEAD builds without; BHG_AHEAD_NO_DISK
-// keeps the disk variants out.
+// (Kerr + disk -1.5 % time), not without (a Kerr exit-only frame +2.6 %, profiles/r06_ahead_kerr_ab.log).
 constexpr int EVT_EXIT = 1, EVT_DISK = 2, EVT_OBJ = 4;
 template <int RHS, int EVT>
 struct RunsAhead {
-#ifdef BHG_AHEAD
-#ifdef BHG_AHEAD_NO_DISK
-    static constexpr bool value = (EVT & 1 /* EVT_EXIT */) != 0 && (EVT & 2 /* EVT_DISK */) == 0 && RHS != BHG_RHS_KERR_BL_;
-#else
-    // Schwarzschild forms: every exit-sphere variant, with the disk the Christoffel form only (the reduced form's <1,3> spills into
-    // its main loop with it, seen in the ISA).  Boyer-Lindquist: WITH the disk only -- Kerr + disk -1.5 % time, a Kerr exit-only
-    // frame +2.6 % (profiles/r06_ahead_kerr_ab.log).
     static constexpr bool value = (EVT & 1 /* EVT_EXIT */) != 0 &&
                                   (RHS == BHG_RHS_KERR_BL_ ? (EVT & 2 /* EVT_DISK */) != 0
                                                            : ((EVT & 2 /* EVT_DISK */) == 0 || RHS == BHG_RHS_CHRISTOFFEL_));
-#endif
-#else
-    static constexpr bool value = false;
-#endif
 };
 
 // Boyer-Lindquist position (r, theta, phi) -> Cartesian: x = sqrt(r^2 + a^2) sin th cos ph, y = ... sin ph, z = r cos th.
@@ -843,7 +821,6 @@ __device__ __forceinline__ bool any_sphere_candidate_of(const TraceArgs &A, cons
     bl_position_to_cart(A.spin, x1, c1);
     return any_sphere_candidate(A, c0, c1);
 }
-// ray records in A.ws are A.ws_stride doubles apart: {a(3), w3, w4, w5} (+ {E, L} for Kerr, stride 8)  // template bitmask: which optional events are compiled in
 
 struct Lane {
     double x[3], v[3], a1[3];
@@ -961,18 +938,10 @@ __device__ __forceinline__ void store_result(const TraceArgs &A, uint32_t idx, c
     store_end_state(A, idx, x, v);
     // (flags, n_steps, n_accepted are never null here: the C-ABI layer points them at its workspace when the caller
     // passes NULL -- three pointer tests less in a path that runs in nearly every iteration of the step loop)
-#ifdef BHG_EXPERIMENT_NO_NARROW_STORES
-    // MEASUREMENT ONLY (round 6, VERDICT r05 task 4 i): the upper bound of what packing flags and both counters into one
-    // wider store could save -- they are not stored at all (results are then incomplete: never a product build)
-    (void)flags;
-    (void)n_att;
-    (void)n_acc;
-#else
     *at_offset(A.flags, idx) = (uint8_t)flags;
     const uint32_t o4 = idx * 4u;
     *at_offset(A.n_steps, o4) = n_att;
     *at_offset(A.n_accepted, o4) = n_acc;
-#endif
 }
 
 
@@ -1072,7 +1041,7 @@ __device__ __forceinline__ void initial_record(const TraceArgs &A, const Metric 
 }
 
 // Put rays base .. base+63 into the ray queue: coalesced loads of k0, x0; the start records {a0, h0, r0, E, L} are
-// worked out here, all lanes together (a build without BHG_INLINE_PREPARE loads the prepare pass's records instead).
+// worked out here, all lanes together.
 // Items that pass (h >= 0) take a free slot each (ballot/mbcnt ranks); the caller has made sure 64 are free.
 template <int RHS, bool ADAPTIVE, class LDS>
 __device__ __forceinline__ void fill_batch(const TraceArgs &A, LDS &Q, Wave &W, uint32_t lane, uint64_t base)
@@ -1080,65 +1049,33 @@ __device__ __forceinline__ void fill_batch(const TraceArgs &A, LDS &Q, Wave &W, 
     // (this function's arguments straight from the kernarg segment, see kernarg_base())
     BHG_KERNARG_PTR kp = kernarg_base();
     struct {
-        const double *k0, *x0, *ws;
+        const double *k0, *x0;
         uint64_t n;
-        int32_t ws_stride, from_records, inline_prepare;
         int8_t *object_id;
-    } C = {BHG_COLD(kp, k0), BHG_COLD(kp, x0), BHG_COLD(kp, ws), BHG_COLD(kp, n), BHG_COLD(kp, ws_stride), BHG_COLD(kp, from_records),
-           BHG_COLD(kp, inline_prepare), BHG_COLD(kp, object_id)};
-    // no prepare pass has run: the wave works the records out itself (Kerr: unless the rays come as prepared records)
-    const bool inline_prepare = BHG_INLINE_PREPARE && C.inline_prepare;
+    } C = {BHG_COLD(kp, k0), BHG_COLD(kp, x0), BHG_COLD(kp, n), BHG_COLD(kp, object_id)};
     const uint64_t i = base + lane;
     double px[3] = {0, 0, 0}, pk[3] = {0, 0, 0}, pa[3] = {0, 0, 0}, pr = 0.0, ph = -1.0;
     double pE = 0.0, pL = 0.0;
     if (i < C.n) {
-        if (C.from_records) {
-            const double *e = A.end + i * 6;
-            px[0] = e[0];
-            px[1] = e[1];
-            px[2] = e[2];
-            pk[0] = e[3];
-            pk[1] = e[4];
-            pk[2] = e[5];
-            const double *w = C.ws + i * (uint64_t)C.ws_stride;
-            pa[0] = w[0];
-            pa[1] = w[1];
-            pa[2] = w[2];
-            ph = w[3];
-            pr = w[4];
-            if (C.ws_stride == 8) {
-                pE = w[6];
-                pL = w[7];
-            }
+        pk[0] = C.k0[i * 3 + 0];
+        pk[1] = C.k0[i * 3 + 1];
+        pk[2] = C.k0[i * 3 + 2];
+        if (C.x0) {
+            px[0] = C.x0[i * 3 + 0];
+            px[1] = C.x0[i * 3 + 1];
+            px[2] = C.x0[i * 3 + 2];
         } else {
-            if (!inline_prepare) {
-                const double *w = C.ws + i * (uint64_t)C.ws_stride;
-                pa[0] = w[0];
-                pa[1] = w[1];
-                pa[2] = w[2];
-                ph = w[3];
-                pr = w[4];
-            }
-            pk[0] = C.k0[i * 3 + 0];
-            pk[1] = C.k0[i * 3 + 1];
-            pk[2] = C.k0[i * 3 + 2];
-            if (C.x0) {
-                px[0] = C.x0[i * 3 + 0];
-                px[1] = C.x0[i * 3 + 1];
-                px[2] = C.x0[i * 3 + 2];
-            } else {
-                const __attribute__((address_space(4))) double *xs = (const __attribute__((address_space(4))) double *)(kp + offsetof(TraceArgs, x0s));
-                px[0] = xs[0];
-                px[1] = xs[1];
-                px[2] = xs[2];
-            }
+            const __attribute__((address_space(4))) double *xs = (const __attribute__((address_space(4))) double *)(kp + offsetof(TraceArgs, x0s));
+            px[0] = xs[0];
+            px[1] = xs[1];
+            px[2] = xs[2];
         }
     }
     // All of this batch's loads must have landed HERE, for every lane: otherwise the compiler has
     // to assume they may still be in flight on the not-valid path and puts a vmcnt(0) in front of
     // the step code, which then waits for the previous iteration's result stores every iteration.
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only
-    if (inline_prepare && !C.from_records && i < C.n) {
+    if (i < C.n) {
         if (C.object_id) C.object_id[i] = (int8_t)-1;
         Metric met;
         met.r_s = A.r_s;
@@ -1516,9 +1453,10 @@ constexpr int PARK_ENDED = 0, PARK_RESUME = 1, PARK_UNCERTIFIED = 2, PARK_REQUEU
 
 // The short search itself, on a step whose stages are at hand: x, v, a1, t = the step's start, h = its signed length, t_new its
 // end, a2..a7 / xn / vn / r_new its stages and end state, h_next the controller's |h| for the step after it.  Called by the
-// drain (which recomputes the stages from the parked record, bit for bit) and -- BHG_INPLACE_MIN builds -- by the step loop
-// itself with the stages still in registers.  PARK_ENDED: the ray's result is stored.  PARK_RESUME: no terminal event, the
-// ray carries on from the step's end (the caller takes xn, vn, a7, t_new, r_new).  PARK_UNCERTIFIED: nothing touched.
+// drain, which recomputes the stages from the parked record, bit for bit (calling it from the step loop with the stages still
+// in registers was measured and not kept: DESIGN section 4.1, row (e)).  PARK_ENDED: the ray's result is stored.
+// PARK_RESUME: no terminal event, the ray carries on from the step's end (the caller takes xn, vn, a7, t_new, r_new).
+// PARK_UNCERTIFIED: nothing touched.
 template <int RHS, int EVT>
 __device__ __forceinline__ int dp54_short_core(const TraceArgs &A, const double x[3], const double v[3], const double a1[3], double t,
                                                double t_new, double h, const double a2[3], const double a3[3], const double a4[3],
@@ -1660,7 +1598,7 @@ __device__ __forceinline__ int dp54_short_core(const TraceArgs &A, const double 
 // whose event function is certified monotone over the step.  Returns PARK_UNCERTIFIED without having touched anything
 // when the certificate (or the iteration) fails: the step then goes to the long list.
 //
-// BHG_AHEAD builds: the same function also runs steps AHEAD of the loop (kind == EV_AHEAD): P is then a queue-style record --
+// The same function also runs steps AHEAD of the loop (kind == EV_AHEAD): P is then a queue-style record --
 // x, v, a1, t at the step's start, h_abs = the |h| the controller chose for it, r_cur = the radius there, the step counts
 // before it -- of a ray whose last step was ACCEPTED, and this is one whole pass of the step loop's body on it, operation
 // for operation: clamp, stages (the ONE stage computation both kinds of record share: a drain usually holds both), error
@@ -1678,9 +1616,7 @@ __device__ __forceinline__ int dp54_resolve_short(const TraceArgs &A, const Metr
 {
     const double t = P.t;
     double h_next = P.h_abs, h_try = P.r_cur;
-    bool ahead = false;
-#ifdef BHG_AHEAD
-    ahead = RunsAhead<RHS, EVT>::value && kind == EV_AHEAD;
+    const bool ahead = RunsAhead<RHS, EVT>::value && kind == EV_AHEAD;
     if (ahead) {
         // (the prologue's rare cases, trace_dp54_kernel: left to the loop -- the ray goes back as it came)
         if (!(P.h_abs > A.min_step_cap) || P.n_att >= A.max_steps) {
@@ -1690,7 +1626,6 @@ __device__ __forceinline__ int dp54_resolve_short(const TraceArgs &A, const Metr
         h_try = P.h_abs;
         if (h_try > A.max_step) h_try = A.max_step;    // rk.py:121-124, not after a rejection (this step follows an accepted one)
     }
-#endif
     // the step as the integrate loop took it (takes it): same operations on the same bits
     double t_new = t + h_try;
     if (t_new - A.lambda_end > 0.0) t_new = A.lambda_end;
@@ -1699,7 +1634,6 @@ __device__ __forceinline__ int dp54_resolve_short(const TraceArgs &A, const Metr
     dp54_stages<RHS>(P.x, P.v, P.a1, h, m, a2, a3, a4, a5, a6, a7, xn, vn, r_new);
     uint32_t ck = kind;         // what the short search is asked to locate
     bool search = true;
-#ifdef BHG_AHEAD
     if (ahead) {
         // (phase by phase, with scheduling barriers in between: left to itself the compiler overlaps the disk pre-filter, the
         // error norm and the search's polynomial and spills 150 B per lane -- some of it on the paths INTO the step loop)
@@ -1714,11 +1648,9 @@ __device__ __forceinline__ int dp54_resolve_short(const TraceArgs &A, const Metr
             !(RHS == BHG_RHS_KERR_BL_ ? disk_crossing_may_hit_bl<true>(A, P.x, P.v, xn, vn, h, P.a1, a2, a3, a4, a5, a6)
                                       : disk_crossing_may_hit<true>(A, P.x, P.v, xn, vn, h, P.a1, a2, a3, a4, a5, a6)))
             ev_d = false;
-#ifndef BHG_NO_SHARP_FILTER
         if (RHS == BHG_RHS_KERR_BL_ && (EVT & EVT_DISK) && ev_d &&
             !disk_crossing_may_hit_sharp<RHS>(A, P.x, P.v, xn, vn, h, P.a1, a2, a3, a4, a5, a6))
             ev_d = false;
-#endif
         __builtin_amdgcn_sched_barrier(0);
         const double h_abs = fabs(h);
         P.n_att++;
@@ -1748,7 +1680,6 @@ __device__ __forceinline__ int dp54_resolve_short(const TraceArgs &A, const Metr
             return PARK_UNCERTIFIED;
         }
     }
-#endif
     if (search) {
         const int outcome = dp54_short_core<RHS, EVT>(A, P.x, P.v, P.a1, t, t_new, h, a2, a3, a4, a5, a6, a7, xn, vn, ck, P.idx, P.n_att, P.n_acc);
         if (outcome == PARK_UNCERTIFIED && ahead) {
@@ -2131,13 +2062,8 @@ __device__ __forceinline__ void pop_rays(LDS &Q, Wave &W, Lane &L, uint32_t lane
     if (!L.active && L.pend == 0u && (int)rk < take) {
         const uint32_t s = Q.q_list[(W.q_head + (int)rk) & (QRING - 1)];
         SLOT_CHECK(Q, s, 1, 0, "pop");
-#ifdef BHG_AHEAD
         // (a queue entry's bits: 1 = the ray's last attempt was rejected -- only a step the drain ran ahead and rejected)
         L.rejected = slot_get<RHS>(Q.slot[s], L) & 1u;
-#else
-        (void)slot_get<RHS>(Q.slot[s], L);
-        L.rejected = 0u;
-#endif
         Q.free_list[W.n_free + (int)rk] = (uint8_t)s;
         L.active = 1u;
     }
@@ -2174,12 +2100,7 @@ __device__ __forceinline__ void swap_parked(LDS &Q, Wave &W, Lane &L, uint32_t l
         else
             Q.ev_list[NSLOT - 1 - W.n_evB - (int)lane_rank(mb)] = (uint8_t)s;
         L = T;
-#ifdef BHG_AHEAD
         L.rejected = tbits & 1u;
-#else
-        (void)tbits;
-        L.rejected = 0u;
-#endif
         L.pend = 0u;
         L.active = 1u;
     }
@@ -2475,7 +2396,6 @@ __global__ void __launch_bounds__(64, (RHS == BHG_RHS_KERR_BL_ ? BHG_KERR_WAVES_
                         !(RHS == BHG_RHS_KERR_BL_ ? disk_crossing_may_hit_bl<true>(A, L.x, L.v, xn, vn, h, L.a1, a2, a3, a4, a5, a6)
                                                   : disk_crossing_may_hit<true>(A, L.x, L.v, xn, vn, h, L.a1, a2, a3, a4, a5, a6)))
                         ev_d = false;
-#ifndef BHG_NO_SHARP_FILTER
                     // ... and, in Boyer-Lindquist coordinates, what that bound lets through against the exact one (a
                     // wave-wide skip when it let nothing through).  Measured: the chord bound passes 0.19 crossings per
                     // Schwarzschild ray that the drain then finds outside the annulus, and 0.69 per Kerr ray (dr/dlambda
@@ -2484,63 +2404,14 @@ __global__ void __launch_bounds__(64, (RHS == BHG_RHS_KERR_BL_ ? BHG_KERR_WAVES_
                     if (RHS == BHG_RHS_KERR_BL_ && (EVT & EVT_DISK) && __ballot(ev_d) != 0ull) {
                         if (ev_d && !disk_crossing_may_hit_sharp<RHS>(A, L.x, L.v, xn, vn, h, L.a1, a2, a3, a4, a5, a6)) ev_d = false;
                     }
-#endif
 #ifdef BHG_DIAG
                     if (EVT & EVT_DISK) {      // (inside the accepted branch: the ballots below count lanes of THIS branch only)
                         diag_cross += __builtin_popcountll(__ballot(diag_crossed)) ? 1 : 0;
                         diag_pass += __builtin_popcountll(__ballot(ev_d)) ? 1 : 0;
                     }
 #endif
-#ifdef BHG_DIAG
-                    if ((EVT & (EVT_EXIT | EVT_DISK)) && A.diag) {
-                        // round 6: how coherent are the short events?  Per iteration: k = lanes that park a step with ONE
-                        // candidate of a short kind (exit or disk alone) -> H[k]++, and the lanes stepping beside them
-                        const bool one_short = (ev_e != ev_d) && !ev_h && !ev_o;
-                        const uint64_t om = __ballot(one_short);
-                        if (om) {
-                            const int k = __builtin_popcountll(om);
-                            const unsigned long long act = (unsigned long long)__builtin_popcountll(__ballot(true));
-                            if (lane == (uint32_t)__builtin_ctzll(om)) {
-                                atomicAdd(A.diag + BHG_DIAG_HIST + k, 1ull);
-                                atomicAdd(A.diag + BHG_DIAG_HIST + 65 + k, act);
-                            }
-                        }
-                        const uint64_t am_ = __ballot(ev_h || ev_e || ev_d || ev_o);
-                        if (am_ && lane == (uint32_t)__builtin_ctzll(am_))
-                            atomicAdd(A.diag + BHG_DIAG_HIST + 130, (unsigned long long)__builtin_popcountll(am_));   // all parked steps
-                    }
-#endif
-                    bool park = ev_h || ev_e || ev_d || ev_o, ended_here = false;
-#ifdef BHG_INPLACE_MIN
-                    // EXPERIMENT, measured and NOT KEPT (round 6, VERDICT r05 task 2b; off unless built with
-                    // -DBHG_INPLACE_MIN=K): when at least K lanes of the wave hold a step with ONE candidate event of a short
-                    // kind in this same iteration, those lanes resolve it HERE, with the stages still in registers -- the
-                    // drain's own certificate, Newton steps and direction at the root (dp54_short_core: the same bits, checked
-                    // on 37.7 M rays) -- instead of parking it: no slot, no recomputed stages.  A failed certificate parks as
-                    // before.  Same box, K = 20 / 32 / 48 (profiles/r06_inplace_ab.log): config 3 +0.0 / +0.1 / -0.1 %, Kerr +
-                    // disk +0.2 / -0.7 / -0.8 %, config 4 -0.5 / -0.4 / -0.4 %, headline 0.  Why: events are NOT wave-coherent
-                    // under lane refill -- a ray parks once per ~10 steps, so SOME lane parks in 54 % of the iterations, 8-12
-                    // lanes at a time; iterations with >= 32 such lanes hold 14-28 % of the events
-                    // (profiles/r06_event_coherence.md) -- and a resolution run for k lanes costs what one run for 64 does.
-                    if (HasShort<true, EVT>::value) {
-                        const bool one_short = (ev_e != ev_d) && !ev_h && !ev_o;
-                        if (__builtin_popcountll(__ballot(one_short)) >= BHG_INPLACE_MIN) {
-                            if (one_short) {
-                                const int outcome = dp54_short_core<RHS, EVT>(A, L.x, L.v, L.a1, L.t, t_new, h, a2, a3, a4, a5, a6, a7, xn, vn,
-                                                                              ev_e ? EV_EXIT : EV_DISK, L.idx, L.n_att, L.n_acc);
-                                if (outcome == PARK_ENDED) {
-                                    park = false;
-                                    ended_here = true;
-                                } else if (outcome == PARK_RESUME) {
-                                    park = false;        // (a plane crossing outside the annulus: the step is taken like any other)
-                                }
-                            }
-                        }
-                    }
-#endif
-                    if (ended_here) {
-                        L.active = 0u;
-                    } else if (park) {
+                    const bool park = ev_h || ev_e || ev_d || ev_o;
+                    if (park) {
                         // Park the step: x, v, a1, t still hold its START (the event drain recomputes it from there),
                         // h_abs is already the controller's choice for the next step, the radius register takes the
                         // |h| this step tried.  The record goes into the wave's LDS pool when the lane is next served.
@@ -2562,7 +2433,6 @@ __global__ void __launch_bounds__(64, (RHS == BHG_RHS_KERR_BL_ ? BHG_KERR_WAVES_
                             store_result<false>(A, L.idx, L.x, L.v, BHG_FLAG_REACHED_END_, L.n_att, L.n_acc);
                             L.active = 0u;
                         }
-#ifdef BHG_AHEAD
                         else if (RunsAhead<RHS, EVT>::value) {
                             // Is the NEXT step expected to leave the exit sphere?  Radial extrapolation from the state just
                             // accepted: r + h (x.k) / r >= R_exit, written r (r - R_exit) + h x.k >= 0 (Boyer-Lindquist: r and
@@ -2583,7 +2453,6 @@ __global__ void __launch_bounds__(64, (RHS == BHG_RHS_KERR_BL_ ? BHG_KERR_WAVES_
                                 L.active = 0u;
                             }
                         }
-#endif
                     }
                 } else {
                     L.h_abs *= fmax(0.2, fac);
@@ -2702,9 +2571,10 @@ __global__ void __launch_bounds__(64) trace_rk4_kernel(const TraceArgs A)
 }
 
 // ------------------------------------------------------------------------------------------
-// Prepare pass (converged, one thread per ray): start-inside test, f0 = a(x0, k0), r0 and, for
-// DP5(4), scipy's initial step (common.py:68-134, order = 4).  Record ws[i] = {a0, h0, r0};
-// h0 = -1 marks a ray that is already final (start inside the hole).
+// Prepare pass of the lane-per-ray trajectory calls (converged, one thread per ray): start-inside test, f0 = a(x0, k0),
+// r0 and, for DP5(4), scipy's initial step (common.py:68-134, order = 4).  Record ws[i] = {a0, h0, r0} (A.ws_stride doubles
+// apart, {E, L} appended for Kerr); h0 = -1 marks a ray that is already final (start inside the hole).  The trace kernels
+// work the same records out in their queue fill (fill_batch).
 // ------------------------------------------------------------------------------------------
 template <int RHS, bool ADAPTIVE>
 __global__ void __launch_bounds__(256) prepare_kernel(const TraceArgs A)
@@ -3236,23 +3106,15 @@ __global__ void accel_kernel(const double *x, const double *k, double r_s, uint6
 // Launchers
 // ------------------------------------------------------------------------------------------
 template <int RHS, int EVT>
-static hipError_t launch_variant(const TraceArgs &a_in, int method, int grid, hipStream_t s, hipEvent_t *ev)
+static hipError_t launch_variant(const TraceArgs &a, int method, int grid, hipStream_t s, hipEvent_t *ev)
 {
-    const unsigned gp = (unsigned)((a_in.n + 255) / 256);
-    // Schwarzschild forms: the trace kernel's waves work out the start records themselves while they fill
-    // their ray queues (converged, 64 lanes wide) -- no prepare launch, no 40-byte record round trip per ray.
-    // Kerr too since round 4 (Cartesian -> Boyer-Lindquist, E and L without a trigonometric call, kerr_cart_to_bl);
-    // a build with BHG_INLINE_PREPARE 0 runs the prepare pass here and, for Kerr, starts the rays from its records.
-    TraceArgs a = a_in;
-    a.inline_prepare = BHG_INLINE_PREPARE ? 1 : 0;
-    if (ev) (void)hipEventRecord(ev[0], s);
-    if (!a.inline_prepare) {
-        if (method == BHG_METHOD_RK4_)
-            BHG_LAUNCH((prepare_kernel<RHS, false>), dim3(gp), dim3(256), 0, s, a);
-        else
-            BHG_LAUNCH((prepare_kernel<RHS, true>), dim3(gp), dim3(256), 0, s, a);
+    // No prepare launch: the trace kernel's waves work out the start records themselves while they fill their ray queues
+    // (converged, 64 lanes wide; Kerr: Cartesian -> Boyer-Lindquist, E and L, kerr_cart_to_bl).  ev[0] and ev[1] stay back
+    // to back so that the three timing slots keep their meaning (bhg_last_pass_ms: slot 0, the former prepare pass, is ~0).
+    if (ev) {
+        (void)hipEventRecord(ev[0], s);
+        (void)hipEventRecord(ev[1], s);
     }
-    if (ev) (void)hipEventRecord(ev[1], s);
     if (method == BHG_METHOD_RK4_)
         BHG_LAUNCH((trace_rk4_kernel<RHS, EVT>), dim3(grid), dim3(64), 0, s, a);
     else
@@ -3355,8 +3217,6 @@ hipError_t launch_trace(const TraceArgs &a, int method, int rhs, int evt, int gr
     return rhs == BHG_RHS_REDUCED_ ? launch_rhs<BHG_RHS_REDUCED_>(a, method, evt, grid, s, ev)
                                    : launch_rhs<BHG_RHS_CHRISTOFFEL_>(a, method, evt, grid, s, ev);
 }
-
-bool needs_prepare_ws(int) { return !BHG_INLINE_PREPARE; }
 
 hipError_t trace_occupancy(int method, int rhs, int evt, int *blocks_per_cu)
 {
