@@ -15,8 +15,9 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BHGEO_LIB") or os.path.join(_HERE, "libbhgeo.so")  # BHGEO_LIB: A/B builds
 
-ABI_VERSION = 9
-ABI_COMPAT_MIN = 7    # bhg_abi_check serves bindings from this ABI on (8 added bhg_trajectory_objects, 9 the redshift calls)
+ABI_VERSION = 10
+ABI_COMPAT_MIN = 7    # bhg_abi_check serves bindings from this ABI on (8 added bhg_trajectory_objects, 9 the redshift calls,
+                      # 10 the observer camera)
 
 OK = 0
 E_INVALID, E_NO_DEVICE, E_HIP, E_NOMEM = -1, -2, -3, -4
@@ -53,6 +54,8 @@ EXPORTS = (
     "bhg_params_size", "bhg_camera_size", "bhg_scene_size", "bhg_frame_scene_size", "bhg_abi_check",
     "bhg_default_params_sized", "bhg_peak_probe", "bhg_trajectory_objects",
     "bhg_redshift_size", "bhg_redshift_device", "bhg_redshift_host", "bhg_shade_scene_redshift_device", "bhg_frame_set_redshift",
+    "bhg_observer_size", "bhg_raygen_observer_device", "bhg_redshift_observer_device", "bhg_redshift_observer_host",
+    "bhg_shade_scene_redshift_observer_device", "bhg_frame_set_observer",
 )
 PROBE_FMA, PROBE_STEP_MIX = 0, 1
 
@@ -79,6 +82,25 @@ def make_redshift(apply=("disk", "objects", "sky"), exponent=4.0, disk_sense=1) 
         rs.apply = sum({_REDSHIFT_CLASS[a] for a in apply})
     rs.disk_sense, rs.exponent = int(disk_sense), float(exponent)
     return rs
+
+
+class Observer(C.Structure):
+    """bhg_observer (ABI 10): velocity beta relative to the ZAMO at the camera, world axes, |beta| < 1."""
+    _fields_ = [("beta", C.c_double * 3)]
+
+
+def make_observer(velocity):
+    """Observer of velocity beta (3 numbers), or None (the reference camera)."""
+    if velocity is None:
+        return None
+    b = np.asarray(velocity, dtype=np.float64).reshape(3)
+    obs = Observer()
+    obs.beta[:] = [float(v) for v in b]
+    return obs
+
+
+def _obs_ref(obs):
+    return None if obs is None else C.byref(obs)
 
 
 class Camera(C.Structure):
@@ -328,6 +350,25 @@ def load():
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bhg_frame_set_redshift.restype = C.c_int
     L.bhg_frame_set_redshift.argtypes = [C.c_void_p, C.POINTER(Redshift)]
+    L.bhg_observer_size.restype = C.c_size_t
+    L.bhg_observer_size.argtypes = []
+    L.bhg_raygen_observer_device.restype = C.c_int
+    L.bhg_raygen_observer_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Observer), _dp, C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_double, C.c_double, _dp, C.c_void_p, C.c_void_p, C.c_size_t,
+                                             C.c_void_p, C.c_void_p]
+    L.bhg_redshift_observer_device.restype = C.c_int
+    L.bhg_redshift_observer_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Redshift), C.POINTER(Observer), _dp,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.bhg_redshift_observer_host.restype = C.c_int
+    L.bhg_redshift_observer_host.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Redshift), C.POINTER(Observer), C.c_void_p,
+                                             C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.bhg_shade_scene_redshift_observer_device.restype = C.c_int
+    L.bhg_shade_scene_redshift_observer_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                           C.c_int32, C.POINTER(Scene), C.POINTER(Params), C.POINTER(Redshift),
+                                                           C.POINTER(Observer), _dp, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                           C.c_void_p, C.c_void_p]
+    L.bhg_frame_set_observer.restype = C.c_int
+    L.bhg_frame_set_observer.argtypes = [C.c_void_p, C.POINTER(Observer)]
     if L.bhg_version() != ABI_VERSION or not hasattr(L, "bhg_abi_check"):
         raise ImportError(f"libbhgeo ABI {L.bhg_version()} != expected {ABI_VERSION}: rebuild {LIB_PATH}")
     for name in ("bhg_params_size", "bhg_camera_size", "bhg_scene_size", "bhg_frame_scene_size"):
@@ -344,6 +385,8 @@ def load():
         raise ImportError("libbhgeo: " + L.bhg_last_error().decode())
     if L.bhg_redshift_size() != C.sizeof(Redshift):
         raise ImportError(f"libbhgeo: bhg_redshift is {L.bhg_redshift_size()} bytes, this binding's {C.sizeof(Redshift)}")
+    if L.bhg_observer_size() != C.sizeof(Observer):
+        raise ImportError(f"libbhgeo: bhg_observer is {L.bhg_observer_size()} bytes, this binding's {C.sizeof(Observer)}")
     _lib = L
     return L
 
@@ -619,6 +662,12 @@ class Frame:
             return
         _check(load().bhg_frame_set_redshift(self._h, C.byref(make_redshift(apply, exponent, disk_sense))))
 
+    def set_observer(self, velocity=None):
+        """The observer camera in every later render (bhg_frame_set_observer): the rays are what an observer at the camera moving
+        with velocity beta (3 numbers, world axes, relative to the ZAMO; observer.py has the common ones) sees.  None: the
+        reference camera again, bit for bit."""
+        _check(load().bhg_frame_set_observer(self._h, _obs_ref(make_observer(velocity))))
+
     def render(self, params: "Params", out=None, to_host=True):
         """One frame: float32 [H, W, 4] (a new array, or `out`).  to_host=False: only enqueue; the image stays on the
         first device (device_image(), synchronize())."""
@@ -836,6 +885,18 @@ class Context:
                                         r9, C.c_void_p(d_jitter), C.c_void_p(d_pixels or None), int(n_pixels),
                                         C.c_void_p(d_k0), C.c_void_p(stream or None)))
 
+    def raygen_observer_device(self, params: Params, obs, x0, width, height, samples, fov_x, fov_y, d_jitter, d_k0, n_pixels,
+                               d_pixels=0, rot=None, stream=0):
+        """bhg_raygen_observer_device: the camera rays of an observer (Observer, or None = bhg_raygen_device) at x0 [3]."""
+        r9 = None
+        if rot is not None:
+            r9 = (C.c_double * 9)(*[float(v) for v in np.asarray(rot, dtype=np.float64).reshape(9)])
+        xs = (C.c_double * 3)(*[float(v) for v in x0])
+        _check(load().bhg_raygen_observer_device(self._h, C.byref(params), _obs_ref(obs), xs, int(width), int(height), int(samples),
+                                                 float(fov_x), float(fov_y), r9, C.c_void_p(d_jitter),
+                                                 C.c_void_p(d_pixels or None), int(n_pixels), C.c_void_p(d_k0),
+                                                 C.c_void_p(stream or None)))
+
     def shade_device(self, d_end, d_flags, n_pixels, samples, d_sky, sky_w, sky_h, d_rgba, stream=0):
         _check(load().bhg_shade_device(self._h, C.c_void_p(d_end), C.c_void_p(d_flags), int(n_pixels), int(samples),
                                        C.c_void_p(d_sky), int(sky_w), int(sky_h), C.c_void_p(d_rgba),
@@ -870,6 +931,32 @@ class Context:
                                         None if e is None else _addr(e), _addr(flags), n, _addr(g)))
         return g
 
+    def redshift_observer(self, k0, x0, params: Params, rs: Redshift, obs, flags, end=None):
+        """bhg_redshift_observer_host: redshift() with g of the moving observer obs (Observer, or None = the ZAMO)."""
+        k0 = np.ascontiguousarray(k0, dtype=np.float64).reshape(-1, 3)
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        n = k0.shape[0]
+        if flags.shape != (n,) or (x0.shape != (3,) and x0.shape != (n, 3)):
+            raise ValueError("flags must be [N], x0 [3] or [N, 3]")
+        e = None if end is None else np.ascontiguousarray(end, dtype=np.float64)
+        if e is not None and e.shape != (n, 6):
+            raise ValueError("end must be [N, 6]")
+        g = np.empty(n, np.float64)
+        _check(load().bhg_redshift_observer_host(self._h, C.byref(params), C.byref(rs), _obs_ref(obs), _addr(x0),
+                                                 1 if x0.ndim == 1 else 0, _addr(k0), None if e is None else _addr(e), _addr(flags),
+                                                 n, _addr(g)))
+        return g
+
+    def redshift_observer_device(self, params: Params, rs: Redshift, obs, n, d_k0, d_flags, d_g, x0_shared=None, d_x0=0, d_end=0,
+                                 stream=0):
+        xs = None
+        if x0_shared is not None:
+            xs = (C.c_double * 3)(*[float(v) for v in x0_shared])
+        _check(load().bhg_redshift_observer_device(self._h, C.byref(params), C.byref(rs), _obs_ref(obs), xs,
+                                                   C.c_void_p(d_x0 or None), C.c_void_p(d_k0), C.c_void_p(d_end or None),
+                                                   C.c_void_p(d_flags), int(n), C.c_void_p(d_g), C.c_void_p(stream or None)))
+
     def redshift_device(self, params: Params, rs: Redshift, n, d_k0, d_flags, d_g, x0_shared=None, d_x0=0, d_end=0, stream=0):
         xs = None
         if x0_shared is not None:
@@ -889,6 +976,17 @@ class Context:
                                                       None if rs is None else C.byref(rs), xs, C.c_void_p(d_k0),
                                                       C.c_void_p(d_rgba or None), C.c_void_p(d_rgba_f32 or None),
                                                       C.c_void_p(d_scatter or None), C.c_void_p(stream or None)))
+
+    def shade_scene_redshift_observer_device(self, d_end, d_flags, n_pixels, samples, scene: "Scene", params: Params, rs, obs,
+                                             x0_shared, d_k0, d_rgba=0, d_rgba_f32=0, d_object_id=0, d_scatter=0, d_end_dir=0,
+                                             stream=0):
+        """bhg_shade_scene_redshift_observer_device: shade_scene_redshift_device with g of the observer obs (None: the ZAMO)."""
+        xs = (C.c_double * 3)(*[float(v) for v in x0_shared])
+        _check(load().bhg_shade_scene_redshift_observer_device(
+            self._h, C.c_void_p(d_end or None), C.c_void_p(d_end_dir or None), C.c_void_p(d_flags), C.c_void_p(d_object_id or None),
+            int(n_pixels), int(samples), C.byref(scene), C.byref(params), None if rs is None else C.byref(rs), _obs_ref(obs), xs,
+            C.c_void_p(d_k0), C.c_void_p(d_rgba or None), C.c_void_p(d_rgba_f32 or None), C.c_void_p(d_scatter or None),
+            C.c_void_p(stream or None)))
 
     def assemble_frame_f32_device(self, d_slabs, d_index, n_pixels, d_frame, stream=0):
         _check(load().bhg_assemble_frame_f32_device(self._h, C.c_void_p(d_slabs), C.c_void_p(d_index), int(n_pixels),

@@ -44,6 +44,7 @@ static_assert(BHG_REDSHIFT_DISK == bhg::BHG_REDSHIFT_DISK_ && BHG_REDSHIFT_OBJEC
                   BHG_REDSHIFT_SKY == bhg::BHG_REDSHIFT_SKY_,
               "redshift class mismatch");
 static_assert(sizeof(bhg_redshift) == 16, "bhg_redshift layout is part of the ABI");
+static_assert(sizeof(bhg_observer) == 24, "bhg_observer layout is part of the ABI");
 
 namespace {
 
@@ -393,6 +394,66 @@ int redshift_params(const bhg_params *p, const bhg_redshift *rs, double disk_r_i
     out->apply = rs->apply;
     return BHG_OK;
 }
+
+// Observer settings against the trace parameters and the camera (include/bhgeo.h, "the observer camera"): *out = the
+// kernels' parameters, on = 1.  x0 may be NULL (per-ray origins: nothing to check the position of).  Also used by
+// bhgeo_frame.hip.
+int observer_params(const bhg_params *p, const bhg_observer *obs, const double *x0, ObserverParams *out)
+{
+    int rc = validate(p);
+    if (rc != BHG_OK) return rc;
+    if (!obs) return fail(BHG_E_INVALID, "observer is NULL");
+    const double *b = obs->beta;
+    if (!(std::isfinite(b[0]) && std::isfinite(b[1]) && std::isfinite(b[2])))
+        return fail(BHG_E_INVALID, "observer beta is not finite");
+    const double b2 = b[0] * b[0] + b[1] * b[1] + b[2] * b[2];
+    if (!(b2 < 1.0)) {
+        char msg[160];
+        std::snprintf(msg, sizeof msg, "observer: |beta| = %.17g must be < 1", std::sqrt(b2));
+        return fail(BHG_E_INVALID, msg);
+    }
+    if (p->time_like) return fail(BHG_E_INVALID, "the observer camera makes null rays: time_like = 1 is refused");
+    std::memset(out, 0, sizeof(*out));
+    if (x0) {
+        if (!(std::isfinite(x0[0]) && std::isfinite(x0[1]) && std::isfinite(x0[2])))
+            return fail(BHG_E_INVALID, "camera origin is not finite");
+        const double M = 0.5 * p->r_s;
+        char msg[256];
+        if (p->rhs_form == BHG_RHS_KERR_BL) {
+            const double a = p->spin, rho2 = x0[0] * x0[0] + x0[1] * x0[1] + x0[2] * x0[2], bb = rho2 - a * a;
+            const double r = std::sqrt(0.5 * (bb + std::sqrt(bb * bb + 4.0 * a * a * x0[2] * x0[2])));
+            const double r_plus = M + std::sqrt(M * M - a * a);
+            if (!(r > r_plus)) {
+                std::snprintf(msg, sizeof msg, "observer: the camera's Boyer-Lindquist r = %.17g is at or inside the horizon r_+ = %.17g",
+                              r, r_plus);
+                return fail(BHG_E_INVALID, msg);
+            }
+            // inside the ergoregion g_tt > 0: the start conversion's root of the null condition (the one the trace and the
+            // redshift take k^t from) is no longer the tetrad's future-directed one, so the trace would follow another photon
+            const double c = x0[2] / r, r_ergo = M + std::sqrt(M * M - a * a * c * c);
+            if (!(r > r_ergo)) {
+                std::snprintf(msg, sizeof msg, "observer: the camera's Boyer-Lindquist r = %.17g is at or inside the ergosurface "
+                              "r_E(theta) = %.17g (cos theta = %.17g)", r, r_ergo, c);
+                return fail(BHG_E_INVALID, msg);
+            }
+            if (x0[0] == 0.0 && x0[1] == 0.0)
+                return fail(BHG_E_INVALID, "observer: a Kerr camera exactly on the axis (x = y = 0) has no azimuthal tetrad leg");
+        } else {
+            const double r = std::sqrt(x0[0] * x0[0] + x0[1] * x0[1] + x0[2] * x0[2]);
+            if (!(r > p->r_s)) {
+                std::snprintf(msg, sizeof msg, "observer: the camera's r = %.17g is at or inside the horizon r_s = %.17g", r, p->r_s);
+                return fail(BHG_E_INVALID, msg);
+            }
+        }
+        std::memcpy(out->x0, x0, sizeof(out->x0));
+    }
+    std::memcpy(out->beta, b, sizeof(out->beta));
+    out->r_s = p->r_s;
+    out->spin = p->rhs_form == BHG_RHS_KERR_BL ? p->spin : 0.0;
+    out->rhs = p->rhs_form;
+    out->on = 1;
+    return BHG_OK;
+}
 }  // namespace bhg
 
 extern "C" {
@@ -417,6 +478,7 @@ size_t bhg_camera_size(void) { return sizeof(bhg_camera); }
 size_t bhg_scene_size(void) { return sizeof(bhg_scene); }
 size_t bhg_frame_scene_size(void) { return sizeof(bhg_frame_scene); }
 size_t bhg_redshift_size(void) { return sizeof(bhg_redshift); }
+size_t bhg_observer_size(void) { return sizeof(bhg_observer); }
 
 int bhg_abi_check(int abi_version, size_t params_size, size_t camera_size, size_t scene_size, size_t frame_scene_size)
 {
@@ -1187,9 +1249,12 @@ int bhg_host_free(bhg_context *c, void *p)
     return BHG_OK;
 }
 
-int bhg_raygen_device(bhg_context *c, int32_t width, int32_t height, int32_t samples, double fov_x, double fov_y,
-                      const double *rot9, const double *d_jitter, const int64_t *d_pixels, size_t n_pixels,
-                      double *d_k0, void *stream)
+}  // extern "C"
+
+namespace {
+int raygen_impl(bhg_context *c, int32_t width, int32_t height, int32_t samples, double fov_x, double fov_y,
+                const double *rot9, const double *d_jitter, const int64_t *d_pixels, size_t n_pixels,
+                double *d_k0, void *stream, const bhg::ObserverParams *obs)
 {
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
     if (width <= 0 || height <= 0 || samples <= 0) return fail(BHG_E_INVALID, "width, height, samples must be > 0");
@@ -1215,8 +1280,31 @@ int bhg_raygen_device(bhg_context *c, int32_t width, int32_t height, int32_t sam
         a.rotate = std::memcmp(rot9, eye, sizeof(eye)) != 0;
         std::memcpy(a.rot, rot9, sizeof(a.rot));
     }
+    if (obs) a.obs = *obs;
     HIP_TRY(bhg::launch_raygen(a, (hipStream_t)stream));
     return BHG_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int bhg_raygen_device(bhg_context *c, int32_t width, int32_t height, int32_t samples, double fov_x, double fov_y,
+                      const double *rot9, const double *d_jitter, const int64_t *d_pixels, size_t n_pixels,
+                      double *d_k0, void *stream)
+{
+    return raygen_impl(c, width, height, samples, fov_x, fov_y, rot9, d_jitter, d_pixels, n_pixels, d_k0, stream, nullptr);
+}
+
+int bhg_raygen_observer_device(bhg_context *c, const bhg_params *p, const bhg_observer *obs, const double *x0, int32_t width,
+                               int32_t height, int32_t samples, double fov_x, double fov_y, const double *rot9,
+                               const double *d_jitter, const int64_t *d_pixels, size_t n_pixels, double *d_k0, void *stream)
+{
+    if (!obs) return bhg_raygen_device(c, width, height, samples, fov_x, fov_y, rot9, d_jitter, d_pixels, n_pixels, d_k0, stream);
+    if (!x0) return fail(BHG_E_INVALID, "x0 is NULL (the observer's tetrad depends on the camera position)");
+    bhg::ObserverParams op;
+    int rc = bhg::observer_params(p, obs, x0, &op);
+    if (rc != BHG_OK) return rc;
+    return raygen_impl(c, width, height, samples, fov_x, fov_y, rot9, d_jitter, d_pixels, n_pixels, d_k0, stream, &op);
 }
 
 int bhg_shade_device(bhg_context *c, const double *d_end, const uint8_t *d_flags, size_t n_pixels, int32_t samples,
@@ -1272,7 +1360,8 @@ namespace {
 int shade_scene_impl(bhg_context *c, const double *d_end, const uint8_t *d_flags, const int8_t *d_object_id,
                      size_t n_pixels, int32_t samples, const bhg_scene *sc, double *d_rgba, float *d_rgba_f32,
                      const int64_t *d_scatter, void *stream, const double *d_end_dir = nullptr,
-                     const bhg::RedshiftParams *rs = nullptr, const double *d_k0 = nullptr);
+                     const bhg::RedshiftParams *rs = nullptr, const double *d_k0 = nullptr,
+                     const bhg::ObserverParams *obs = nullptr);
 }
 
 extern "C" {
@@ -1299,7 +1388,7 @@ namespace {
 int shade_scene_impl(bhg_context *c, const double *d_end, const uint8_t *d_flags, const int8_t *d_object_id,
                      size_t n_pixels, int32_t samples, const bhg_scene *sc, double *d_rgba, float *d_rgba_f32,
                      const int64_t *d_scatter, void *stream, const double *d_end_dir, const bhg::RedshiftParams *rs,
-                     const double *d_k0)
+                     const double *d_k0, const bhg::ObserverParams *obs)
 {
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
     if (!sc) return fail(BHG_E_INVALID, "scene is NULL");
@@ -1326,6 +1415,7 @@ int shade_scene_impl(bhg_context *c, const double *d_end, const uint8_t *d_flags
     if (rs) {
         a.rs = *rs;
         a.k0 = d_k0;
+        if (obs) a.obs = *obs;
     }
     a.flags = d_flags;
     a.sky = sc->d_sky;
@@ -1364,6 +1454,17 @@ int bhg_shade_scene_redshift_device(bhg_context *c, const double *d_end, const d
                                     const bhg_params *p, const bhg_redshift *rs, const double *x0_shared, const double *d_k0,
                                     double *d_rgba, float *d_rgba_f32, const int64_t *d_scatter, void *stream)
 {
+    return bhg_shade_scene_redshift_observer_device(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs,
+                                                    nullptr, x0_shared, d_k0, d_rgba, d_rgba_f32, d_scatter, stream);
+}
+
+int bhg_shade_scene_redshift_observer_device(bhg_context *c, const double *d_end, const double *d_end_dir,
+                                             const uint8_t *d_flags, const int8_t *d_object_id, size_t n_pixels,
+                                             int32_t samples, const bhg_scene *sc, const bhg_params *p,
+                                             const bhg_redshift *rs, const bhg_observer *obs, const double *x0_shared,
+                                             const double *d_k0, double *d_rgba, float *d_rgba_f32,
+                                             const int64_t *d_scatter, void *stream)
+{
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
     if (!sc) return fail(BHG_E_INVALID, "scene is NULL");
     if (n_pixels && !d_rgba && !d_rgba_f32) return fail(BHG_E_INVALID, "NULL device pointer (d_rgba and d_rgba_f32)");
@@ -1377,18 +1478,36 @@ int bhg_shade_scene_redshift_device(bhg_context *c, const double *d_end, const d
         int rc = bhg::redshift_params(p, rs, disk ? sc->disk_r_in : -1.0, x0_shared, &rp);
         if (rc != BHG_OK) return rc;
     }
+    bhg::ObserverParams op;
+    if (on && obs) {
+        int rc = bhg::observer_params(p, obs, x0_shared, &op);
+        if (rc != BHG_OK) return rc;
+    }
     return shade_scene_impl(c, d_end, d_flags, d_object_id, n_pixels, samples, sc, d_rgba, d_rgba_f32, d_scatter, stream,
-                            d_end_dir, on ? &rp : nullptr, d_k0);
+                            d_end_dir, on ? &rp : nullptr, d_k0, on && obs ? &op : nullptr);
 }
 
 int bhg_redshift_device(bhg_context *c, const bhg_params *p, const bhg_redshift *rs, const double *x0_shared,
                         const double *d_x0, const double *d_k0, const double *d_end, const uint8_t *d_flags, size_t n,
                         double *d_g, void *stream)
 {
+    return bhg_redshift_observer_device(c, p, rs, nullptr, x0_shared, d_x0, d_k0, d_end, d_flags, n, d_g, stream);
+}
+
+int bhg_redshift_observer_device(bhg_context *c, const bhg_params *p, const bhg_redshift *rs, const bhg_observer *obs,
+                                 const double *x0_shared, const double *d_x0, const double *d_k0, const double *d_end,
+                                 const uint8_t *d_flags, size_t n, double *d_g, void *stream)
+{
     // (the settings are checked before the context: a refusal names its figure with or without a device)
     bhg::RedshiftParams rp;
     int rc = bhg::redshift_params(p, rs, p && p->disk_r_out > 0.0 ? p->disk_r_in : -1.0, x0_shared, &rp);
     if (rc != BHG_OK) return rc;
+    bhg::ObserverParams op;
+    std::memset(&op, 0, sizeof(op));
+    if (obs) {
+        rc = bhg::observer_params(p, obs, x0_shared, &op);
+        if (rc != BHG_OK) return rc;
+    }
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
     if (!x0_shared == !d_x0) return fail(BHG_E_INVALID, "exactly one of x0_shared / d_x0 must be given");
     if (n == 0) return BHG_OK;
@@ -1404,6 +1523,7 @@ int bhg_redshift_device(bhg_context *c, const bhg_params *p, const bhg_redshift 
     a.flags = d_flags;
     a.g = d_g;
     a.n = n;
+    a.obs = op;
     HIP_TRY(bhg::launch_redshift(a, (hipStream_t)stream));
     return BHG_OK;
 }
@@ -1411,9 +1531,21 @@ int bhg_redshift_device(bhg_context *c, const bhg_params *p, const bhg_redshift 
 int bhg_redshift_host(bhg_context *c, const bhg_params *p, const bhg_redshift *rs, const double *x0, int x0_is_shared,
                       const double *k0, const double *end, const uint8_t *flags, size_t n, double *g)
 {
+    return bhg_redshift_observer_host(c, p, rs, nullptr, x0, x0_is_shared, k0, end, flags, n, g);
+}
+
+int bhg_redshift_observer_host(bhg_context *c, const bhg_params *p, const bhg_redshift *rs, const bhg_observer *obs,
+                               const double *x0, int x0_is_shared, const double *k0, const double *end, const uint8_t *flags,
+                               size_t n, double *g)
+{
     bhg::RedshiftParams rp;   // (checked here too, before the context and before any copy)
     int rc = bhg::redshift_params(p, rs, p && p->disk_r_out > 0.0 ? p->disk_r_in : -1.0, x0_is_shared ? x0 : nullptr, &rp);
     if (rc != BHG_OK) return rc;
+    bhg::ObserverParams op;
+    if (obs) {
+        rc = bhg::observer_params(p, obs, x0_is_shared ? x0 : nullptr, &op);
+        if (rc != BHG_OK) return rc;
+    }
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
     if (!x0) return fail(BHG_E_INVALID, "x0 is NULL");
     if (n == 0) return BHG_OK;
@@ -1429,7 +1561,8 @@ int bhg_redshift_host(bhg_context *c, const bhg_params *p, const bhg_redshift *r
     HIP_TRY(hipMemcpyAsync(dk, k0, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (ne) HIP_TRY(hipMemcpyAsync(de, end, ne * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(df, flags, n, hipMemcpyHostToDevice, c->stream));
-    rc = bhg_redshift_device(c, p, rs, x0_is_shared ? x0 : nullptr, nx ? dx : nullptr, dk, ne ? de : nullptr, df, n, dg, c->stream);
+    rc = bhg_redshift_observer_device(c, p, rs, obs, x0_is_shared ? x0 : nullptr, nx ? dx : nullptr, dk, ne ? de : nullptr, df, n,
+                                      dg, c->stream);
     if (rc != BHG_OK) return rc;
     HIP_TRY(hipMemcpyAsync(g, dg, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));

@@ -37,6 +37,8 @@ int set_error(int code, const std::string &msg);   // bhgeo_capi.hip: the thread
 void host_copy(bhg_context *c, void *dst, const void *src, size_t bytes, size_t piece);   // bhgeo_capi.hip: multi-threaded memcpy in jobs of `piece` bytes
 // bhgeo_capi.hip: redshift settings checked against the trace parameters (disk_r_in < 0: no disk to check)
 int redshift_params(const bhg_params *p, const bhg_redshift *rs, double disk_r_in, const double *x0, RedshiftParams *out);
+// bhgeo_capi.hip: observer settings checked against the trace parameters and the camera
+int observer_params(const bhg_params *p, const bhg_observer *obs, const double *x0, ObserverParams *out);
 }
 
 namespace {
@@ -202,6 +204,9 @@ struct bhg_frame {
     int32_t sky_w = 0, sky_h = 0, disk_w = 0, disk_h = 0;
     bhg_frame_scene scene;          // (its pointers are not used after bhg_frame_set_scene)
     bhg_redshift rs = {0u, 1, 4.0}; // bhg_frame_set_redshift; apply = 0: off (the shade calls of ABI 8)
+    bool observer = false;          // bhg_frame_set_observer; false: the reference camera (the ray generation of ABI 9)
+    bhg_observer obs = {{0.0, 0.0, 0.0}};
+    double obs_key[6] = {};         // camera origin, r_s, spin, rhs_form the observer rays on the devices were made for
     // root (device of shard 0)
     DevBuf recv, perm, image;       // [n_dev * pmax][4] float, [H W] int64, [H W][4] float
     size_t pmax = 0;
@@ -247,7 +252,8 @@ void deal_tiles(bhg_frame *f)
     f->rendered = false;
 }
 
-int upload_shard_geometry(bhg_frame *f, Shard &s)
+// obs: nullptr, or the observer camera the rays are made for (checked by the caller)
+int upload_shard_geometry(bhg_frame *f, Shard &s, const bhg::ObserverParams *obs)
 {
     // pixel list, compact jitter [S][P][2] in list order, ray buffers
     const size_t S = (size_t)f->cam.samples, frame_px = (size_t)f->cam.width * (size_t)f->cam.height;
@@ -289,6 +295,7 @@ int upload_shard_geometry(bhg_frame *f, Shard &s)
     static const double eye[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     a.rotate = std::memcmp(f->cam.rot, eye, sizeof(eye)) != 0;
     std::memcpy(a.rot, f->cam.rot, sizeof(a.rot));
+    if (obs) a.obs = *obs;
     HIP_TRY(bhg::launch_raygen(a, s.stream));
     HIP_TRY(hipStreamSynchronize(s.stream));   // (jc and the pixel list are host temporaries of this call)
     // the shard's draws stay on the device (16 B per ray): a camera that rotates from frame to frame regenerates its rays
@@ -604,6 +611,22 @@ int bhg_frame_set_redshift(bhg_frame *f, const bhg_redshift *rs)
     return BHG_OK;
 }
 
+int bhg_frame_set_observer(bhg_frame *f, const bhg_observer *obs)
+{
+    if (!f) return fail(BHG_E_INVALID, "frame is NULL");
+    if (obs) {
+        // what can be checked without the trace parameters (the metric, the horizon and the axis are checked at every render)
+        const double *b = obs->beta;
+        if (!(std::isfinite(b[0]) && std::isfinite(b[1]) && std::isfinite(b[2])) || !(b[0] * b[0] + b[1] * b[1] + b[2] * b[2] < 1.0))
+            return fail(BHG_E_INVALID, "observer beta must be finite with |beta| < 1");
+        f->obs = *obs;
+    }
+    f->observer = obs != nullptr;
+    // the rays of the devices were made for the previous camera model: make them anew at the next render
+    for (auto &s : f->sh) s.rays_ready = false;
+    return BHG_OK;
+}
+
 int bhg_frame_render(bhg_frame *f, const bhg_params *p, float *rgba_host)
 try {
     if (!f || !p) return fail(BHG_E_INVALID, "frame / params is NULL");
@@ -628,11 +651,22 @@ try {
         BHG_TRY(bhg::redshift_params(&prm, &f->rs, has_disk && (f->rs.apply & BHG_REDSHIFT_DISK) ? f->scene.disk_r_in : -1.0,
                                      f->cam.origin, &rp));
     }
+    bhg::ObserverParams op;
+    if (f->observer) {
+        BHG_TRY(bhg::observer_params(&prm, &f->obs, f->cam.origin, &op));
+        // the tetrad depends on the camera position and the metric: rays made for others are made anew
+        const double key[6] = {op.x0[0], op.x0[1], op.x0[2], op.r_s, op.spin, (double)op.rhs};
+        if (std::memcmp(key, f->obs_key, sizeof(key)) != 0) {
+            for (auto &s : f->sh) s.rays_ready = false;
+            std::memcpy(f->obs_key, key, sizeof(key));
+        }
+    }
+    const bhg_observer *obs = f->observer ? &f->obs : nullptr;
 
     // -- every device: (rays, scene images once) trace, shade + sample mean into its slab ---------------------------
     for (size_t r = 0; r < world; r++) {
         Shard &s = f->sh[r];
-        if (!s.rays_ready) BHG_TRY(upload_shard_geometry(f, s));
+        if (!s.rays_ready) BHG_TRY(upload_shard_geometry(f, s, f->observer ? &op : nullptr));
         if (!s.scene_ready) BHG_TRY(upload_shard_scene(f, s));
     }
     for (size_t r = 0; r < world; r++) {
@@ -660,9 +694,9 @@ try {
             if (redshift) {   // (sky g needs only the camera state: still direction-only)
                 bhg_scene sc;
                 fill_scene(f, s, &sc);
-                BHG_TRY(bhg_shade_scene_redshift_device(s.ctx, nullptr, s.dir.as<double>(), s.flags.as<uint8_t>(), nullptr, s.P, S,
-                                                        &sc, &prm, &f->rs, f->cam.origin, s.k0.as<double>(), nullptr, dst,
-                                                        scatter, s.stream));
+                BHG_TRY(bhg_shade_scene_redshift_observer_device(s.ctx, nullptr, s.dir.as<double>(), s.flags.as<uint8_t>(), nullptr,
+                                                                 s.P, S, &sc, &prm, &f->rs, obs, f->cam.origin, s.k0.as<double>(),
+                                                                 nullptr, dst, scatter, s.stream));
             } else {
                 BHG_TRY(bhg_shade_dir_device(s.ctx, s.dir.as<double>(), s.flags.as<uint8_t>(), s.P, S, s.sky.as<float>(), f->sky_w,
                                              f->sky_h, nullptr, dst, scatter, s.stream));
@@ -678,9 +712,10 @@ try {
             bhg_scene sc;
             fill_scene(f, s, &sc);
             if (redshift)
-                BHG_TRY(bhg_shade_scene_redshift_device(s.ctx, s.end.as<double>(), nullptr, s.flags.as<uint8_t>(),
-                                                        has_obj ? s.obj.as<int8_t>() : nullptr, s.P, S, &sc, &prm, &f->rs,
-                                                        f->cam.origin, s.k0.as<double>(), nullptr, dst, scatter, s.stream));
+                BHG_TRY(bhg_shade_scene_redshift_observer_device(s.ctx, s.end.as<double>(), nullptr, s.flags.as<uint8_t>(),
+                                                                 has_obj ? s.obj.as<int8_t>() : nullptr, s.P, S, &sc, &prm, &f->rs,
+                                                                 obs, f->cam.origin, s.k0.as<double>(), nullptr, dst, scatter,
+                                                                 s.stream));
             else
                 BHG_TRY(bhg_shade_scene_f32_device(s.ctx, s.end.as<double>(), s.flags.as<uint8_t>(), has_obj ? s.obj.as<int8_t>() : nullptr,
                                                    s.P, S, &sc, dst, scatter, s.stream));

@@ -17,14 +17,11 @@
 
 namespace bhg {
 
-// d = (x_r + dx (u1 - 1/2), y_r + dy (u2 - 1/2), -1), rotated, normalised.  Operation order follows
-// the host restatement (raygen.py) so that an unrotated camera gives bit-identical directions
-// (the library is built with -ffp-contract=off).
-__global__ void __launch_bounds__(256) raygen_kernel(const RaygenArgs A)
+// d = (x_r + dx (u1 - 1/2), y_r + dy (u2 - 1/2), -1), rotated; ray i of P pixels.  Operation order follows the host
+// restatement (raygen.py) so that an unrotated camera gives bit-identical directions (the library is built with
+// -ffp-contract=off).  The caller divides by |d|.
+__device__ __forceinline__ double3 pinhole_dir(const RaygenArgs &A, uint64_t i, uint64_t P)
 {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t P = A.n_pixels;
-    if (i >= P * (uint64_t)A.samples) return;
     const uint64_t s = i / P, p = i - s * P;
     const int64_t pix = A.pixels ? A.pixels[p] : (int64_t)p;
     const int64_t py = pix / A.width, px = pix - py * A.width;
@@ -46,11 +43,121 @@ __global__ void __launch_bounds__(256) raygen_kernel(const RaygenArgs A)
         d1 = e1;
         d2 = e2;
     }
-    const double nrm = sqrt(d0 * d0 + d1 * d1 + d2 * d2);
-    double *o = A.k0 + i * 3;
-    o[0] = d0 / nrm;
-    o[1] = d1 / nrm;
-    o[2] = d2 / nrm;
+    return make_double3(d0, d1, d2);
+}
+
+// ---- the observer camera -----------------------------------------------------------------------
+// Kerr ZAMO at BL (r, theta): lapse alpha = sqrt(Sigma Delta / A) and frame-dragging rate omega = 2 M a r / A
+__device__ __forceinline__ void kerr_zamo(double M, double a, double r, double c2, double &alpha, double &omega)
+{
+    const double a2 = a * a, s2 = 1.0 - c2;
+    const double Sig = r * r + a2 * c2, Del = r * r - 2.0 * M * r + a2;
+    const double A = (r * r + a2) * (r * r + a2) - a2 * Del * s2;
+    alpha = sqrt(Sig * Del / A);
+    omega = 2.0 * M * a * r / A;
+}
+
+// Aberration, the observer's rest frame -> the ZAMO's: a unit look direction n' of an observer moving with beta gives
+//     n = (n' + gamma^2 / (gamma + 1) (n'.beta) beta - gamma beta) / (gamma (1 - beta.n'))
+// (point 2 of section 10 with (gamma - 1) beta_hat beta_hat = gamma^2 / (gamma + 1) beta beta: no division by |beta|).
+// c = gamma^2 / (gamma + 1).
+__device__ __forceinline__ void aberrate(const double b[3], double gamma, double c, const double np[3], double n[3])
+{
+    const double bn = b[0] * np[0] + b[1] * np[1] + b[2] * np[2];
+    const double iE = 1.0 / (gamma * (1.0 - bn));
+    const double cb = c * bn - gamma;
+    n[0] = (np[0] + cb * b[0]) * iE;
+    n[1] = (np[1] + cb * b[1]) * iE;
+    n[2] = (np[2] + cb * b[2]) * iE;
+}
+
+// The camera's ZAMO tetrad as an affine map of a ZAMO-frame look direction n to the coordinate direction k = T n + B
+// (up to the scale the caller normalises away).  Kerr: n = n_r r^ + n_th th^ + n_ph ph^ in the Euclidean spherical basis at
+// the camera's BL angles, (k^r, k^th, k^ph) = (sqrt(Delta / Sigma) n_r, n_th / sqrt(Sigma), omega / alpha + n_ph sqrt(Sigma) /
+// (sqrt(A) sin th)) mapped through the Jacobian of x = R sin th cos ph, y = R sin th sin ph, z = r cos th (R = sqrt(r^2 +
+// a^2)); the sin th of the phi column cancels.  Schwarzschild (both Cartesian forms): T = 1 - (1 - sqrt f) r^ r^, B = 0 --
+// what the Kerr map gives at a = 0.  The BL position comes from kerr_cart_to_bl itself (its E and L are not used).
+__device__ __forceinline__ void camera_tetrad(const ObserverParams &O, double T[9], double B[3])
+{
+    const double x = O.x0[0], y = O.x0[1], z = O.x0[2];
+    if (O.rhs != BHG_RHS_KERR_BL_) {
+        const double rc = sqrt(x * x + y * y + z * z), ir = 1.0 / rc;
+        const double rh[3] = {x * ir, y * ir, z * ir};
+        const double q = 1.0 - sqrt(1.0 - O.r_s * ir);   // 1 - sqrt f
+        for (int u = 0; u < 3; u++)
+            for (int v = 0; v < 3; v++) T[u * 3 + v] = (u == v ? 1.0 : 0.0) - q * rh[u] * rh[v];
+        B[0] = B[1] = B[2] = 0.0;
+        return;
+    }
+    const double a = O.spin, M = 0.5 * O.r_s, a2 = a * a;
+    double px[3] = {x, y, z}, pk[3] = {0.0, 0.0, 1.0}, E, L;
+    kerr_cart_to_bl(a, M, 0.0, px, pk, E, L);
+    const double r = px[0];
+    double st, ct;
+    sincos_pi4(px[1], st, ct);
+    const double iw = rsqrt_nr(__builtin_fma(y, y, x * x)), cp = x * iw, sp = y * iw;
+    double alpha, omega;
+    kerr_zamo(M, a, r, ct * ct, alpha, omega);
+    const double Sig = __builtin_fma(a2 * ct, ct, r * r), Del = __builtin_fma(-2.0 * M, r, r * r + a2);
+    const double R2 = r * r + a2, R = sqrt(R2);
+    const double Aq = R2 * R2 - a2 * Del * st * st;
+    const double sS = sqrt(Sig), cr = sqrt(Del / Sig), cth = 1.0 / sS, cph = sS / sqrt(Aq);   // (cph: times R, over sin th)
+    // Jacobian columns, scaled: cr d(x)/dr, cth d(x)/dth, cph d(x)/dph / sin th
+    const double Jr[3] = {cr * (r / R) * st * cp, cr * (r / R) * st * sp, cr * ct};
+    const double Jt[3] = {cth * R * ct * cp, cth * R * ct * sp, -cth * r * st};
+    const double Jp[3] = {-cph * R * sp, cph * R * cp, 0.0};
+    const double rh[3] = {st * cp, st * sp, ct}, th[3] = {ct * cp, ct * sp, -st}, ph[3] = {-sp, cp, 0.0};
+    for (int u = 0; u < 3; u++)
+        for (int v = 0; v < 3; v++) T[u * 3 + v] = Jr[u] * rh[v] + Jt[u] * th[v] + Jp[u] * ph[v];
+    const double wB = omega / alpha * R * st;   // (omega / alpha) d(x)/dphi
+    B[0] = -wB * sp;
+    B[1] = wB * cp;
+    B[2] = 0.0;
+}
+
+// OBS = false: the reference's camera, k0 = d / |d|.  OBS = true: d / |d| is the moving observer's rest-frame look direction
+// n', aberrated to the ZAMO frame and put through the camera tetrad, k0 = (T n + B) / |T n + B|.  The tetrad is one per
+// launch: the observer instance walks the rays grid-stride and forms it once per thread (a few hundred instructions, against
+// about a hundred per ray for the pinhole direction, the boost and the map).
+template <bool OBS>
+__global__ void __launch_bounds__(256) raygen_kernel(const RaygenArgs A)
+{
+    const uint64_t P = A.n_pixels;
+    if (!OBS) {
+        const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        if (i >= P * (uint64_t)A.samples) return;
+        const double3 d = pinhole_dir(A, i, P);
+        const double d0 = d.x, d1 = d.y, d2 = d.z;
+        const double nrm = sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+        double *o = A.k0 + i * 3;
+        o[0] = d0 / nrm;
+        o[1] = d1 / nrm;
+        o[2] = d2 / nrm;
+        return;
+    }
+    const uint64_t N = P * (uint64_t)A.samples;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    double T[9], B[3];
+    camera_tetrad(A.obs, T, B);
+    const double *b = A.obs.beta;
+    const double gamma = 1.0 / sqrt(1.0 - (b[0] * b[0] + b[1] * b[1] + b[2] * b[2]));
+    const double c = gamma * gamma / (gamma + 1.0);
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += stride) {
+        const double3 d = pinhole_dir(A, i, P);
+        const double d0 = d.x, d1 = d.y, d2 = d.z;
+        const double inrm = 1.0 / sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+        const double np[3] = {d0 * inrm, d1 * inrm, d2 * inrm};
+        double n[3];
+        aberrate(b, gamma, c, np, n);
+        const double k0 = __builtin_fma(T[0], n[0], __builtin_fma(T[1], n[1], __builtin_fma(T[2], n[2], B[0])));
+        const double k1 = __builtin_fma(T[3], n[0], __builtin_fma(T[4], n[1], __builtin_fma(T[5], n[2], B[1])));
+        const double k2 = __builtin_fma(T[6], n[0], __builtin_fma(T[7], n[1], __builtin_fma(T[8], n[2], B[2])));
+        const double ik = rsqrt_nr(__builtin_fma(k0, k0, __builtin_fma(k1, k1, k2 * k2)));
+        double *o = A.k0 + i * 3;
+        o[0] = k0 * ik;
+        o[1] = k1 * ik;
+        o[2] = k2 * ik;
+    }
 }
 
 // Bilinear lookup in an equirectangular RGBA float32 image.  Texture coordinates (u, v) in
@@ -165,16 +272,6 @@ __device__ __forceinline__ int ray_class(uint32_t fl)
     return RS_SKY;   // exit sphere, lambda_end reached, step cap, stall: the shader colours them from the sky
 }
 
-// Kerr ZAMO at BL (r, theta): lapse alpha = sqrt(Sigma Delta / A) and frame-dragging rate omega = 2 M a r / A
-__device__ __forceinline__ void kerr_zamo(double M, double a, double r, double c2, double &alpha, double &omega)
-{
-    const double a2 = a * a, s2 = 1.0 - c2;
-    const double Sig = r * r + a2 * c2, Del = r * r - 2.0 * M * r + a2;
-    const double A = (r * r + a2) * (r * r + a2) - a2 * Del * s2;
-    alpha = sqrt(Sig * Del / A);
-    omega = 2.0 * M * a * r / A;
-}
-
 __device__ double redshift_g(const RedshiftParams &P, const double xc[3], const double kc[3], int cls, const double *e)
 {
     if (cls == RS_DARK) return 0.0;
@@ -227,19 +324,69 @@ __device__ double redshift_g(const RedshiftParams &P, const double xc[3], const 
     return sqrt(1.0 - 3.0 * M / R) / (sqrt(fc) * (1.0 - Om * b));
 }
 
+// The moving observer's factor on the ZAMO's g (point 4): gamma (1 + beta.n), n the ray's ZAMO-frame
+// look direction, recovered from the camera state (x_c, k0) by the inverse of the camera tetrad.  Kerr: the BL velocity and
+// E, L of kerr_cart_to_bl, the local energy E_loc = (E - omega L) / alpha, k^t = E_loc / alpha, and the tetrad components
+//     n ~ (sqrt(Sigma / Delta) k^r,  sqrt(Sigma) k^th,  sqrt(A) sin th / sqrt(Sigma) (k^ph - omega k^t))
+// on the Euclidean spherical basis; Schwarzschild: n ~ k + (1 / sqrt f - 1) (k.r^) r^.  n is normalised (the null condition
+// makes it a unit vector up to rounding).
+__device__ double observer_doppler(const RedshiftParams &P, const double b[3], const double xc[3], const double kc[3])
+{
+    double bn;
+    if (P.rhs == BHG_RHS_KERR_BL_) {
+        const double a = P.spin, M = 0.5 * P.r_s, a2 = a * a;
+        double px[3] = {xc[0], xc[1], xc[2]}, pk[3] = {kc[0], kc[1], kc[2]}, E, L;
+        kerr_cart_to_bl(a, M, 0.0, px, pk, E, L);
+        const double r = px[0];
+        double st, ct, alpha, omega;
+        sincos_pi4(px[1], st, ct);
+        kerr_zamo(M, a, r, ct * ct, alpha, omega);
+        const double Sig = __builtin_fma(a2 * ct, ct, r * r), Del = __builtin_fma(-2.0 * M, r, r * r + a2);
+        const double R2 = r * r + a2, Aq = R2 * R2 - a2 * Del * st * st;
+        const double kt = (E - omega * L) / (alpha * alpha);
+        const double nr = sqrt(Sig / Del) * pk[0], nt = sqrt(Sig) * pk[1];
+        const double np = sqrt(Aq / Sig) * st * (pk[2] - omega * kt);
+        const double iw = rsqrt_nr(__builtin_fma(xc[1], xc[1], xc[0] * xc[0])), cp = xc[0] * iw, sp = xc[1] * iw;
+        const double br = (b[0] * cp + b[1] * sp) * st + b[2] * ct;
+        const double bt = (b[0] * cp + b[1] * sp) * ct - b[2] * st;
+        const double bp = b[1] * cp - b[0] * sp;
+        bn = (br * nr + bt * nt + bp * np) / sqrt(nr * nr + nt * nt + np * np);
+    } else {
+        const double rc = sqrt(xc[0] * xc[0] + xc[1] * xc[1] + xc[2] * xc[2]), ir = 1.0 / rc;
+        const double rh[3] = {xc[0] * ir, xc[1] * ir, xc[2] * ir};
+        const double q = (1.0 / sqrt(1.0 - P.r_s * ir) - 1.0) * (kc[0] * rh[0] + kc[1] * rh[1] + kc[2] * rh[2]);
+        const double n[3] = {kc[0] + q * rh[0], kc[1] + q * rh[1], kc[2] + q * rh[2]};
+        bn = (b[0] * n[0] + b[1] * n[1] + b[2] * n[2]) / sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    }
+    const double gamma = 1.0 / sqrt(1.0 - (b[0] * b[0] + b[1] * b[1] + b[2] * b[2]));
+    return gamma * (1.0 + bn);
+}
+
+// g of the camera's ZAMO (OBS = false: redshift_g as it stands), or of the moving observer (OBS = true)
+template <bool OBS>
+__device__ __forceinline__ double observer_g(const RedshiftParams &P, const ObserverParams &O, const double xc[3], const double kc[3],
+                                             int cls, const double *e)
+{
+    const double g = redshift_g(P, xc, kc, cls, e);
+    if (!OBS || cls == RS_DARK || cls == RS_NAN) return g;
+    return g * observer_doppler(P, O.beta, xc, kc);
+}
+
+template <bool OBS>
 __global__ void __launch_bounds__(256) redshift_kernel(const RedshiftArgs A)
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= A.n) return;
     const double *xc = A.x0 ? A.x0 + i * 3 : A.p.x0;
-    A.g[i] = redshift_g(A.p, xc, A.k0 + i * 3, ray_class(A.flags[i]), A.end ? A.end + i * 6 : nullptr);
+    A.g[i] = observer_g<OBS>(A.p, A.obs, xc, A.k0 + i * 3, ray_class(A.flags[i]), A.end ? A.end + i * 6 : nullptr);
 }
 
-// the shade kernels' redshift instance: rgb *= g^n for a ray of a class the caller selected
+// the shade kernels' redshift instances: rgb *= g^n for a ray of a class the caller selected (OBS: the moving observer's g)
+template <bool OBS>
 __device__ __forceinline__ void redshift_weigh(const ShadeArgs &A, uint64_t i, int cls, uint32_t bit, const double *e, double rgb[3])
 {
     if (!(A.rs.apply & bit)) return;
-    const double g = redshift_g(A.rs, A.rs.x0, A.k0 + i * 3, cls, e), n = A.rs.exponent;
+    const double g = observer_g<OBS>(A.rs, A.obs, A.rs.x0, A.k0 + i * 3, cls, e), n = A.rs.exponent;
     // the exponents of the model, 4 (bolometric) and 3 (specific intensity), as products (libm's pow was a third of the kernel)
     const double g2 = g * g;
     const double w = n == 4.0 ? g2 * g2 : (n == 3.0 ? g2 * g : pow(g, n));
@@ -250,8 +397,9 @@ __device__ __forceinline__ void redshift_weigh(const ShadeArgs &A, uint64_t i, i
 
 // The colour of ONE ray (sample s of pixel p): black for a horizon ray (:242-244), the disk's / an object's colour, or the
 // sky in its exit direction.
-// RS: the redshift instance (rgb *= g^n by class); without it the kernels are the frame path's as they were.
-template <bool RS>
+// RS: the redshift instance (rgb *= g^n by class); without it the kernels are the frame path's as they were.  OBS (with RS
+// only): g is the moving observer's.
+template <bool RS, bool OBS>
 __device__ __forceinline__ void ray_colour(const ShadeArgs &A, uint64_t i, uint8_t fl, double c0, double c1, double c2, double rgb[3])
 {
     rgb[0] = rgb[1] = rgb[2] = 0.0;
@@ -259,12 +407,12 @@ __device__ __forceinline__ void ray_colour(const ShadeArgs &A, uint64_t i, uint8
     const double *e = A.end + i * 6;
     if (fl == BHG_FLAG_HIT_DISK_ && A.disk_r_out > 0.0 && A.end) {
         disk_colour(A, e, rgb);
-        if (RS) redshift_weigh(A, i, RS_DISK, BHG_REDSHIFT_DISK_, e, rgb);
+        if (RS) redshift_weigh<OBS>(A, i, RS_DISK, BHG_REDSHIFT_DISK_, e, rgb);
         return;
     }
     if (fl == BHG_FLAG_HIT_OBJECT_ && A.object_id && A.end) {
         object_colour(A, e, (int)A.object_id[i], rgb);
-        if (RS) redshift_weigh(A, i, RS_OBJECT, BHG_REDSHIFT_OBJECTS_, e, rgb);
+        if (RS) redshift_weigh<OBS>(A, i, RS_OBJECT, BHG_REDSHIFT_OBJECTS_, e, rgb);
         return;
     }
     // theta = 1 - acos(d_z / |d|) / pi (:373), phi = atan2(d_y, d_x) / pi (:374); exit directions are not unit
@@ -275,7 +423,7 @@ __device__ __forceinline__ void ray_colour(const ShadeArgs &A, uint64_t i, uint8
     const double phi = atan2_fast(c1, c0) * 0.3183098861837907;
     sky_lookup(A.sky, A.sky_w, A.sky_h, -phi, 2.0 * theta - 1.0, rgb);  // :375
     // (start-inside rays carry the horizon flag: black above; a NaN ray is coloured as it always was, unweighted)
-    if (RS && !(fl & BHG_FLAG_NAN_)) redshift_weigh(A, i, RS_SKY, BHG_REDSHIFT_SKY_, nullptr, rgb);
+    if (RS && !(fl & BHG_FLAG_NAN_)) redshift_weigh<OBS>(A, i, RS_SKY, BHG_REDSHIFT_SKY_, nullptr, rgb);
 }
 
 __device__ __forceinline__ void write_pixel(const ShadeArgs &A, uint64_t p, const double acc[3])
@@ -301,7 +449,7 @@ __device__ __forceinline__ void write_pixel(const ShadeArgs &A, uint64_t p, cons
 // consecutive rays of the [S][P] layout (coalesced).  Against one thread per pixel walking its samples one after the
 // other (round 3; kept below for S > 256) this puts S times as many independent atan2 / texel-gather chains in flight:
 // the kernel is a latency chain per ray, not a bandwidth problem (131 MB in, 16 MB out per config-2 frame).
-template <bool RS>
+template <bool RS, bool OBS>
 __global__ void __launch_bounds__(256) shade_reduce_kernel(const ShadeArgs A, const uint32_t ppb)
 {
     __shared__ double col[256 * 3];
@@ -314,7 +462,7 @@ __global__ void __launch_bounds__(256) shade_reduce_kernel(const ShadeArgs A, co
         // exit directions: the second half of the end records, or (direction-only traces of sky frames) an array of their own
         const double *d = A.dir ? A.dir + i * 3 : A.end + i * 6 + 3;
         double rgb[3];
-        ray_colour<RS>(A, i, A.flags[i], d[0], d[1], d[2], rgb);
+        ray_colour<RS, OBS>(A, i, A.flags[i], d[0], d[1], d[2], rgb);
         col[t * 3 + 0] = rgb[0];
         col[t * 3 + 1] = rgb[1];
         col[t * 3 + 2] = rgb[2];
@@ -334,7 +482,7 @@ __global__ void __launch_bounds__(256) shade_reduce_kernel(const ShadeArgs A, co
 }
 
 // More samples than a workgroup has threads: one thread per pixel, samples accumulated in registers in sample order.
-template <bool RS>
+template <bool RS, bool OBS>
 __global__ void __launch_bounds__(256) shade_reduce_serial_kernel(const ShadeArgs A)
 {
     const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -344,7 +492,7 @@ __global__ void __launch_bounds__(256) shade_reduce_serial_kernel(const ShadeArg
         const uint64_t i = (uint64_t)s * A.n_pixels + p;
         const double *d = A.dir ? A.dir + i * 3 : A.end + i * 6 + 3;
         double rgb[3];
-        ray_colour<RS>(A, i, A.flags[i], d[0], d[1], d[2], rgb);
+        ray_colour<RS, OBS>(A, i, A.flags[i], d[0], d[1], d[2], rgb);
         acc[0] += rgb[0];
         acc[1] += rgb[1];
         acc[2] += rgb[2];
@@ -390,35 +538,46 @@ hipError_t launch_raygen(const RaygenArgs &a, hipStream_t s)
 {
     const uint64_t n = a.n_pixels * (uint64_t)a.samples;
     if (n == 0) return hipSuccess;
-    BHG_LAUNCH(raygen_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
+    const uint64_t blocks = (n + 255) / 256;
+    if (a.obs.on)   // grid-stride: at most 2048 workgroups (8 per CU), each thread forms the camera tetrad once
+        BHG_LAUNCH(raygen_kernel<true>, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, s, a);
+    else
+        BHG_LAUNCH(raygen_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
 hipError_t launch_redshift(const RedshiftArgs &a, hipStream_t s)
 {
     if (a.n == 0) return hipSuccess;
-    BHG_LAUNCH(redshift_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
+    if (a.obs.on)
+        BHG_LAUNCH(redshift_kernel<true>, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
+    else
+        BHG_LAUNCH(redshift_kernel<false>, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
 hipError_t launch_shade(const ShadeArgs &a, hipStream_t s)
 {
     if (a.n_pixels == 0) return hipSuccess;
-    const bool rs = a.rs.apply != 0;
+    const bool rs = a.rs.apply != 0, obs = rs && a.obs.on;
     if (a.samples > 256) {
         const dim3 grid((unsigned)((a.n_pixels + 255) / 256));
-        if (rs)
-            BHG_LAUNCH(shade_reduce_serial_kernel<true>, grid, dim3(256), 0, s, a);
+        if (obs)
+            BHG_LAUNCH((shade_reduce_serial_kernel<true, true>), grid, dim3(256), 0, s, a);
+        else if (rs)
+            BHG_LAUNCH((shade_reduce_serial_kernel<true, false>), grid, dim3(256), 0, s, a);
         else
-            BHG_LAUNCH(shade_reduce_serial_kernel<false>, grid, dim3(256), 0, s, a);
+            BHG_LAUNCH((shade_reduce_serial_kernel<false, false>), grid, dim3(256), 0, s, a);
         return hipGetLastError();
     }
     const uint32_t ppb = 256u / (uint32_t)a.samples;      // pixels per workgroup
     const dim3 grid((unsigned)((a.n_pixels + ppb - 1) / ppb));
-    if (rs)
-        BHG_LAUNCH(shade_reduce_kernel<true>, grid, dim3(256), 0, s, a, ppb);
+    if (obs)
+        BHG_LAUNCH((shade_reduce_kernel<true, true>), grid, dim3(256), 0, s, a, ppb);
+    else if (rs)
+        BHG_LAUNCH((shade_reduce_kernel<true, false>), grid, dim3(256), 0, s, a, ppb);
     else
-        BHG_LAUNCH(shade_reduce_kernel<false>, grid, dim3(256), 0, s, a, ppb);
+        BHG_LAUNCH((shade_reduce_kernel<false, false>), grid, dim3(256), 0, s, a, ppb);
     return hipGetLastError();
 }
 

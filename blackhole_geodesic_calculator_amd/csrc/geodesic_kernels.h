@@ -82,6 +82,15 @@ struct TraceArgs {
     double spheres[BHG_MAX_SPHERES_][4];  // {cx, cy, cz, radius}, BH-centred
 };
 
+// the moving observer of the observer camera (frame_kernels.hip): on = 0 is the reference's camera
+struct ObserverParams {
+    double x0[3];      // camera, BH-centred (raygen only; the redshift calls take the camera from their own arguments)
+    double beta[3];    // velocity relative to the ZAMO at the camera, world axes, |beta| < 1
+    double r_s, spin;  // metric (raygen only)
+    int32_t rhs;       // BHG_RHS_* (raygen only)
+    int32_t on;        // 0: no observer -- the kernels' reference instances are launched and never read this struct
+};
+
 // camera-ray generation (frame_kernels.hip)
 struct RaygenArgs {
     const double *jitter;   // [S*H*W*2] MT19937 doubles, sample-major then row-major pixels, (u1, u2); nullptr = pixel
@@ -94,6 +103,7 @@ struct RaygenArgs {
     int32_t width, height, samples, rotate;
     double fov_x, fov_y;
     double rot[9];          // row-major camera rotation
+    ObserverParams obs;     // the observer camera (bhg_raygen_observer_device); last, so that no other member moves
 };
 
 // redshift of a ray between the camera's ZAMO and its emitter (frame_kernels.hip, redshift_g):
@@ -116,6 +126,7 @@ struct RedshiftArgs {
     const uint8_t *flags;  // [n]
     double *g;             // [n]
     uint64_t n;
+    ObserverParams obs;    // beta and on only: g of a moving observer (bhg_redshift_observer_device)
 };
 
 // shading + per-pixel multisample mean (frame_kernels.hip)
@@ -142,6 +153,7 @@ struct ShadeArgs {
     // rs.apply != 0; the other instance -- the frame path without redshift -- never reads these two members
     const double *k0;      // [S*n_pixels][3] camera directions, or nullptr when rs.apply == 0
     RedshiftParams rs;
+    ObserverParams obs;    // beta and on only: the redshift instance's g is the moving observer's (rs.apply != 0 only)
 };
 
 hipError_t launch_raygen(const RaygenArgs &a, hipStream_t s);

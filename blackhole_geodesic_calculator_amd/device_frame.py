@@ -82,6 +82,8 @@ class DeviceFrame:
         self.d_obj = None
         self.redshift = None     # _ffi.Redshift (set_redshift) or None: off
         self._params = None      # the parameters of the last trace (the redshift shade needs its metric)
+        self.observer = None     # _ffi.Observer (set_observer) or None: the reference camera
+        self._ray_key = None     # what the observer rays in d_k0 were made for: (origin, r_s, spin, rhs_form)
 
     def _stream(self):
         return torch.cuda.current_stream(self.dev).cuda_stream
@@ -126,13 +128,35 @@ class DeviceFrame:
         off, the shade calls as without redshift."""
         self.redshift = _ffi.make_redshift(apply, exponent, disk_sense) if apply else None
 
+    def set_observer(self, velocity=None):
+        """The observer camera (bhg_raygen_observer_device): every pixel's direction is the look direction of
+        an observer at the camera moving with velocity beta (3 numbers, world axes, relative to the ZAMO; observer.py has the common
+        ones), and with redshift on, g is that observer's.  None: the reference camera.  The rays are made anew at the next
+        render(), and whenever the origin or the metric of the trace parameters changes."""
+        self.observer = _ffi.make_observer(velocity)
+        self._rays_ready = False
+        self._ray_key = None
+
+    def _observer_key(self, params):
+        return (tuple(float(v) for v in self.origin), float(params.r_s), float(params.spin), int(params.rhs_form))
+
     def pixel_cost(self):
         """Attempted steps of the last trace summed over the samples of each pixel ([P], order of `pixels`): the
         measured cost dist.measured_tile_cost() orders and deals the tiles by."""
         return self.d_steps.view(self.S, self.P).to(torch.int64).sum(0)
 
-    def generate_rays(self):
+    def generate_rays(self, params: _ffi.Params = None):
+        """params: the trace parameters (their metric) -- needed by the observer camera only."""
         self._traced = None      # new rays: results of an earlier trace belong to the old ones
+        if self.observer is not None:
+            if params is None:
+                raise RuntimeError("the observer camera needs the trace parameters: generate_rays(params)")
+            self.ctx.raygen_observer_device(params, self.observer, self.origin, self.W, self.H, self.S, self.fov_x, self.fov_y,
+                                            self.d_jitter.data_ptr(), self.d_k0.data_ptr(), self.P,
+                                            d_pixels=0 if self.d_pixels is None else self.d_pixels.data_ptr(),
+                                            rot=self.rot, stream=self._stream())
+            self._ray_key = self._observer_key(params)
+            return
         self.ctx.raygen_device(self.W, self.H, self.S, self.fov_x, self.fov_y, self.d_jitter.data_ptr(),
                                self.d_k0.data_ptr(), self.P,
                                d_pixels=0 if self.d_pixels is None else self.d_pixels.data_ptr(),
@@ -185,12 +209,16 @@ class DeviceFrame:
         return traced
 
     def _shade_redshift(self, form, d_rgba=0, d_rgba_f32=0, scatter=None):
-        self.ctx.shade_scene_redshift_device(self.d_end.data_ptr() if form == "end" else 0, self.d_flags.data_ptr(), self.P, self.S,
-                                             self.scene(), self._params, self.redshift, self.origin, self.d_k0.data_ptr(),
-                                             d_rgba=d_rgba, d_rgba_f32=d_rgba_f32,
-                                             d_object_id=0 if self.d_obj is None else self.d_obj.data_ptr(),
-                                             d_scatter=0 if scatter is None else scatter.data_ptr(),
-                                             d_end_dir=self.d_dir.data_ptr() if form == "dir" else 0, stream=self._stream())
+        kw = dict(d_rgba=d_rgba, d_rgba_f32=d_rgba_f32, d_object_id=0 if self.d_obj is None else self.d_obj.data_ptr(),
+                  d_scatter=0 if scatter is None else scatter.data_ptr(), d_end_dir=self.d_dir.data_ptr() if form == "dir" else 0,
+                  stream=self._stream())
+        d_end = self.d_end.data_ptr() if form == "end" else 0
+        if self.observer is not None:
+            self.ctx.shade_scene_redshift_observer_device(d_end, self.d_flags.data_ptr(), self.P, self.S, self.scene(), self._params,
+                                                          self.redshift, self.observer, self.origin, self.d_k0.data_ptr(), **kw)
+            return
+        self.ctx.shade_scene_redshift_device(d_end, self.d_flags.data_ptr(), self.P, self.S, self.scene(), self._params,
+                                             self.redshift, self.origin, self.d_k0.data_ptr(), **kw)
 
     def shade(self):
         form = self._shade_form()
@@ -231,8 +259,10 @@ class DeviceFrame:
 
     def render(self, params: _ffi.Params, regenerate_rays=False):
         """rays (cached: the engine re-seeds identically every frame) -> trace -> shade."""
+        if self.observer is not None and self._ray_key != self._observer_key(params):
+            regenerate_rays = True   # the observer's tetrad depends on the camera position and the metric
         if regenerate_rays or not getattr(self, "_rays_ready", False):
-            self.generate_rays()
+            self.generate_rays(params)
             self._rays_ready = True
         self.trace(params)
         return self.shade()

@@ -51,7 +51,10 @@
 extern "C" {
 #endif
 
-#define BHG_ABI_VERSION 9   /* 9: redshift -- bhg_redshift_device / _host, bhg_shade_scene_redshift_device, bhg_frame_set_redshift,
+#define BHG_ABI_VERSION 10  /* 10: the observer camera -- bhg_raygen_observer_device, bhg_redshift_observer_device / _host,
+                                  bhg_shade_scene_redshift_observer_device, bhg_frame_set_observer, bhg_observer_size,
+                                  struct bhg_observer; nothing of ABI 9 changed.
+                               9: redshift -- bhg_redshift_device / _host, bhg_shade_scene_redshift_device, bhg_frame_set_redshift,
                                   bhg_redshift_size, struct bhg_redshift;
                                   nothing of ABI 8 changed.
                                8: bhg_trajectory_objects (sampled curves that end on object spheres), the frame gather mode
@@ -60,8 +63,8 @@ extern "C" {
                                6: bhg_frame_* (library-owned frame, N devices), bhg_deal_tiles, bhg_params.time_like (104 bytes) */
 
 #define BHG_ABI_COMPAT_MIN 7 /* bhg_abi_check serves bindings written for this ABI or later: every symbol, struct layout and
-                                meaning they know is unchanged (ABIs 8 and 9 only ADDED entry points, a gather mode,
-                                a struct and constants) */
+                                meaning they know is unchanged (ABIs 8, 9 and 10 only ADDED entry points, a gather
+                                mode, structs and constants) */
 
 /* return codes */
 #define BHG_OK 0
@@ -404,7 +407,9 @@ int bhg_frame_set_scene(bhg_frame *frame, const bhg_frame_scene *scene);
  * depsgraph.scene.camera.matrix_world (RelativisticRenderEngine.py:182-183), field of view (:72-73) -- while the frame object,
  * its jitter stream (re-seeded identically every render, :189), tile dealing and device buffers stay: origin, rotation and field of view may change, width / height / samples may not.  A new origin costs
  * nothing (rays are directions; the origin goes into every trace call); a new rotation or field of view regenerates the
- * rays on the devices at the next render. */
+ * rays on the devices at the next render.  Once an observer is set (bhg_frame_set_observer, ABI 10), a new origin -- or new
+ * trace parameters with another metric -- regenerates the rays at the next render too: the observer's tetrad depends on
+ * the camera's position. */
 int bhg_frame_set_camera(bhg_frame *frame, const bhg_camera *cam);
 /* One frame.  rgba_host [height][width][4] float (pageable or page-locked): blocking, the image is there on return.
  * rgba_host = NULL: the render is only enqueued and the image stays on the first device (bhg_frame_device_image;
@@ -487,6 +492,50 @@ int bhg_shade_scene_redshift_device(bhg_context *ctx, const double *d_end, const
 /* Redshift in every later bhg_frame_render (every device, every gather mode; direction-only sky frames stay direction-only).
  * rs = NULL or apply = 0: the frame without redshift, bit for bit.  Checked against the trace parameters at render. */
 int bhg_frame_set_redshift(bhg_frame *frame, const bhg_redshift *rs);
+
+/* --- the observer camera (ABI 10) --------------------------------------------------------------
+ * The reference camera uses each pixel's pinhole direction d as the COORDINATE direction k0 at the camera.  The observer
+ * camera reads d as a unit look direction n' in the rest frame of an observer at the camera moving with velocity beta
+ * relative to the local ZAMO (world axes; in Schwarzschild the ZAMO is the static observer).  n' is aberrated to the ZAMO
+ * frame, n = (n' + gamma^2/(gamma+1) (n'.beta) beta - gamma beta) / (gamma (1 - beta.n')), and put through the ZAMO tetrad:
+ * Schwarzschild (both Cartesian forms) k = n - (1 - sqrt f)(n.r^) r^; Kerr (k^r, k^th, k^ph) = (sqrt(Delta/Sigma) n_r,
+ * n_th / sqrt(Sigma), omega/alpha + n_ph sqrt(Sigma) / (sqrt(A) sin th)) with n on the Euclidean spherical basis at the
+ * camera's BL angles, mapped to Cartesian by the Jacobian of the BL embedding.  k0 is normalised to unit Euclidean length
+ * (the trace's affine-parameter convention is unchanged).  beta = 0 is the ZAMO's own picture -- NOT the reference
+ * camera's.  The redshift g of a moving observer is the ZAMO's g times gamma (1 + beta.n), n recovered from (x0, k0).
+ * Refused (BHG_E_INVALID): |beta| >= 1 or non-finite, a camera at or inside the horizon (r_s; Kerr BL r_+ = M + sqrt(M^2 -
+ * a^2)), a Kerr camera at or inside the ergosurface r_E(theta) = M + sqrt(M^2 - a^2 cos^2 theta) (there g_tt > 0 and the
+ * start conversion's root of the null condition, which the trace and the redshift take k^t from, is not always the
+ * tetrad's), time_like = 1, a Kerr camera exactly on the BL axis (x = y = 0).  Near the axis the azimuthal basis vector is
+ * formed from x / w, y / w (w = sqrt(x^2 + y^2)) and frame dragging enters as omega R sin th: both stay well conditioned,
+ * but kerr_cart_to_bl's theta carries a relative error of about eps / (1 - cos theta), which the rays inherit.  Every call
+ * below takes obs = NULL as "no observer": then it is exactly its ABI 9 counterpart, bit for bit.  Per-ray origins
+ * (d_x0 of bhg_redshift_observer_device) are not checked against the horizon. */
+typedef struct bhg_observer {
+    double beta[3];       /* world axes, relative to the ZAMO at the camera, |beta| < 1 */
+} bhg_observer;
+size_t bhg_observer_size(void);
+/* bhg_raygen_device for an observer at x0 (HOST [3], BH-centred) in the metric of p (r_s, spin, rhs_form). */
+int bhg_raygen_observer_device(bhg_context *ctx, const bhg_params *p, const bhg_observer *obs, const double *x0, int32_t width,
+                               int32_t height, int32_t samples, double fov_x, double fov_y, const double *rot9,
+                               const double *d_jitter, const int64_t *d_pixels, size_t n_pixels, double *d_k0, void *stream);
+/* bhg_redshift_device / _host / bhg_shade_scene_redshift_device with g of the moving observer. */
+int bhg_redshift_observer_device(bhg_context *ctx, const bhg_params *p, const bhg_redshift *rs, const bhg_observer *obs,
+                                 const double *x0_shared, const double *d_x0, const double *d_k0, const double *d_end,
+                                 const uint8_t *d_flags, size_t n, double *d_g, void *stream);
+int bhg_redshift_observer_host(bhg_context *ctx, const bhg_params *p, const bhg_redshift *rs, const bhg_observer *obs,
+                               const double *x0, int x0_is_shared, const double *k0, const double *end, const uint8_t *flags,
+                               size_t n, double *g);
+int bhg_shade_scene_redshift_observer_device(bhg_context *ctx, const double *d_end, const double *d_end_dir,
+                                             const uint8_t *d_flags, const int8_t *d_object_id, size_t n_pixels,
+                                             int32_t samples, const bhg_scene *scene, const bhg_params *p,
+                                             const bhg_redshift *rs, const bhg_observer *obs, const double *x0_shared,
+                                             const double *d_k0, double *d_rgba, float *d_rgba_f32,
+                                             const int64_t *d_scatter, void *stream);
+/* The observer camera in every later bhg_frame_render (every device, every gather mode; with redshift, g is the observer's).
+ * obs = NULL: the reference camera again, bit for bit.  The rays are regenerated at the next render, and again whenever
+ * the origin or the trace parameters' metric changes.  Checked against the camera and the trace parameters at render. */
+int bhg_frame_set_observer(bhg_frame *frame, const bhg_observer *obs);
 
 /* Acceleration probe: acc[n][3] = -Gamma^i_{mu nu} k^mu k^nu at (x[n][3], k[n][3]); host buffers.
  * Lets tests compare the device RHS with the oracle's term by term.  With rhs_form = BHG_RHS_KERR_BL the triples

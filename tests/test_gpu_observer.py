@@ -1,0 +1,416 @@
+"""The observer camera (ABI 10) on the GPU: bhg_raygen_observer_device and the observer's g against the numpy restatement
+(tests/observer_reference.py); obs = NULL and bhg_frame_set_observer(NULL) bit for bit the ABI 9 calls; the shadow's known
+answers (Synge's angle for a static camera at r = 10 M, carried through the aberration for a falling one; the Kerr shadow's
+asymmetry); an orbiting camera's image against the reference shade with the observer's g; the library-owned frame on one
+device and on the {0, 0} loopback; the Python adaptors against the C calls."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import CAM
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import observer_reference as orf  # noqa: E402
+import redshift_reference as rr  # noqa: E402
+
+INC = np.radians(75.0)
+CAM3 = np.array([30 * np.sin(INC), 0.0, 30 * np.cos(INC)])
+# look down -x from +x, image x along world +y, image y along world +z
+LOOK_MINUS_X = np.array([[0.0, 0.0, 1.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0]])
+
+
+def _ffi():
+    from blackhole_geodesic_calculator_amd import _ffi as f
+    return f
+
+
+def _stream():
+    import torch
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _raygen(ctx, p, obs, x0, W, H, S, fov, rot=None, pixels=None, seed=42.0):
+    """(reference k0, observer k0) of one camera on the device."""
+    import torch
+    from blackhole_geodesic_calculator_amd.raygen import python_random_stream
+    jit = torch.as_tensor(np.asarray(python_random_stream(seed, 2 * S * W * H), np.float64)).cuda()
+    P = W * H if pixels is None else len(pixels)
+    d_px = None if pixels is None else torch.as_tensor(np.asarray(pixels, np.int64)).cuda()
+    ref = torch.empty((S * P, 3), dtype=torch.float64, device="cuda")
+    out = torch.empty_like(ref)
+    kw = dict(d_pixels=0 if d_px is None else d_px.data_ptr(), rot=rot, stream=_stream())
+    ctx.raygen_device(W, H, S, fov, fov, jit.data_ptr(), ref.data_ptr(), P, **kw)
+    ctx.raygen_observer_device(p, obs, x0, W, H, S, fov, fov, jit.data_ptr(), out.data_ptr(), P, **kw)
+    torch.cuda.synchronize()
+    return ref.cpu().numpy(), out.cpu().numpy()
+
+
+RAYGEN_CASES = [
+    ("schw", 0, 0.0, np.array([3.0, -4.0, 9.0]), [0.0, 0.0, 0.0]),
+    ("schw_boost", 0, 0.0, np.array([3.0, -4.0, 9.0]), [0.3, -0.5, 0.6]),
+    ("reduced_boost", 1, 0.0, np.array([-6.0, 2.0, 4.0]), [-0.7, 0.1, 0.2]),
+    ("kerr", 2, 0.9, np.array([8.0, 5.0, 3.0]), [0.0, 0.0, 0.0]),
+    ("kerr_boost", 2, 0.9, np.array([8.0, 5.0, 3.0]), [0.2, 0.55, -0.4]),
+    ("kerr_near_axis", 2, 0.9, np.array([1e-3, 0.0, 12.0]), [0.1, 0.2, -0.3]),
+]
+
+
+@pytest.mark.parametrize("case", RAYGEN_CASES, ids=[c[0] for c in RAYGEN_CASES])
+def test_raygen_against_restatement(ctx, case):
+    f = _ffi()
+    name, rhs, spin, x0, beta = case
+    p = f.make_params(r_s=2.0, rhs_form=rhs, spin=spin)
+    obs = f.make_observer(beta)
+    rot = np.array([[0.8, 0.0, 0.6], [0.0, 1.0, 0.0], [-0.6, 0.0, 0.8]])
+    W, H, S = 24, 16, 3
+    rng = np.random.default_rng(1)
+    for r9, px in ((None, None), (rot, rng.permutation(W * H)[:100])):
+        ref, k0 = _raygen(ctx, p, obs, x0, W, H, S, 0.9, rot=r9, pixels=px)
+        want = orf.observer_k0_rays(x0, ref, beta, 2.0, spin, rhs == 2)
+        err = np.abs(k0 - want).max()
+        tol = 1e-9 if name == "kerr_near_axis" else 1e-12   # (theta's conditioning near the axis)
+        assert err <= tol, err
+        assert np.abs(np.linalg.norm(k0, axis=1) - 1.0).max() <= 1e-15 * 4
+        assert np.abs(k0 - ref).max() > 1e-3     # not the reference camera
+
+
+def test_no_observer_is_abi9(ctx):
+    """obs = NULL: bhg_raygen_observer_device is bhg_raygen_device and the redshift / shade calls are their ABI 9 forms, bit for
+    bit."""
+    import torch
+    f = _ffi()
+    p = f.make_params(r_s=1.0, lambda_end=80.0, r_exit=40.0, disk_r_in=3.0, disk_r_out=9.0)
+    ref, k0 = _raygen(ctx, p, None, CAM3, 32, 24, 2, 0.9)
+    assert np.array_equal(ref, k0)
+    end, flags, _, _ = ctx.trace(ref, CAM3, p)
+    rs = f.make_redshift()
+    assert np.array_equal(ctx.redshift_observer(ref, CAM3, p, rs, None, flags, end), ctx.redshift(ref, CAM3, p, rs, flags, end),
+                          equal_nan=True)
+    from blackhole_geodesic_calculator_amd.device_frame import DeviceFrame, synthetic_sky
+    fr = DeviceFrame(ctx, 32, 24, 2, fov_x=0.9, fov_y=0.9, origin=CAM3, rotation_euler=(0.0, INC, 0.0))
+    fr.set_sky(synthetic_sky(256, 128))
+    fr.set_disk(3.0, 9.0)
+    fr.set_redshift(("disk", "sky"))
+    fr.generate_rays()
+    fr.trace(p)
+    today = fr.shade().clone()
+    d64 = torch.empty_like(today)
+    ctx.shade_scene_redshift_observer_device(fr.d_end.data_ptr(), fr.d_flags.data_ptr(), fr.P, fr.S, fr.scene(), p, fr.redshift,
+                                             None, fr.origin, fr.d_k0.data_ptr(), d_rgba=d64.data_ptr(), stream=_stream())
+    torch.cuda.synchronize()
+    assert torch.equal(d64, today)
+
+
+G_CASES = [
+    ("schw", 0, 0.0, (3.0, 9.0), [0.0, 0.0, 0.0]),
+    ("schw_boost", 0, 0.0, (3.0, 9.0), [0.0, 0.4, -0.3]),
+    ("reduced_boost", 1, 0.0, None, [0.5, 0.0, 0.2]),
+    ("kerr", 2, 0.45, (3.0, 9.0), [0.0, 0.0, 0.0]),
+    ("kerr_boost", 2, 0.45, (3.0, 9.0), [-0.3, 0.5, 0.1]),
+]
+
+
+@pytest.mark.parametrize("case", G_CASES, ids=[c[0] for c in G_CASES])
+def test_observer_g_against_restatement(ctx, case):
+    import torch
+    f = _ffi()
+    name, rhs, spin, disk, beta = case
+    kw = dict(r_s=1.0, lambda_end=80.0, r_exit=40.0, rhs_form=rhs, spin=spin)
+    if disk:
+        kw.update(disk_r_in=disk[0], disk_r_out=disk[1])
+    p = f.make_params(**kw)
+    obs = f.make_observer(beta)
+    rot = np.array([[np.cos(INC), 0, np.sin(INC)], [0, 1, 0], [-np.sin(INC), 0, np.cos(INC)]])
+    _, k0 = _raygen(ctx, p, obs, CAM3, 48, 32, 2, 1.2, rot=rot)
+    end, flags, _, _ = ctx.trace(k0, CAM3, p)
+    if disk:
+        assert (flags == 128).sum() > 20
+    rs = f.make_redshift()
+    g = ctx.redshift_observer(k0, CAM3, p, rs, obs, flags, end)
+    want = orf.observer_g_rays(CAM3, k0, end, flags, 1.0, beta, spin, rhs == 2, 1)
+    dark = (flags & 3) != 0
+    assert np.all(g[dark] == 0.0)
+    ok = ~dark & np.isfinite(want)
+    assert np.abs(g[ok] / want[ok] - 1.0).max() <= 1e-12
+    # the device form, per-ray origins included
+    d_g = torch.empty(len(k0), dtype=torch.float64, device="cuda")
+    d_k0, d_end, d_fl = (torch.as_tensor(a).cuda() for a in (k0, end, flags))
+    ctx.redshift_observer_device(p, rs, obs, len(k0), d_k0.data_ptr(), d_fl.data_ptr(), d_g.data_ptr(), x0_shared=CAM3,
+                                 d_end=d_end.data_ptr(), stream=_stream())
+    torch.cuda.synchronize()
+    assert np.array_equal(d_g.cpu().numpy(), g, equal_nan=True)
+    x0 = np.ascontiguousarray(np.tile(CAM3, (len(k0), 1)))
+    assert np.array_equal(ctx.redshift_observer(k0, x0, p, rs, obs, flags, end), g, equal_nan=True)
+    if np.any(beta):
+        assert np.abs(g[ok] / ctx.redshift(k0, CAM3, p, rs, flags, end)[ok] - 1.0).max() > 1e-3
+
+
+# ---- the shadow's known answers ------------------------------------------------------------------------------------------
+W_SH = 512
+FOV_SH = 1.2
+
+
+def _axis_pixels(W):
+    c = W // 2
+    return np.concatenate([c * W + np.arange(W), np.arange(W) * W + c])    # the central row, then the central column
+
+
+def _shadow_edges(ctx, p, obs, x0, rot=None):
+    """Horizon-flag runs along the central row and column: [(first, last) dark pixel of the row, of the column], the traced rays
+    and the rest-frame angle of every ray from the optical axis.  The rays carry the MT19937 jitter (up to half a pixel off the
+    pixel's nominal direction); the angles are the actual rays': the reference k0 is d / |d| = n' exactly."""
+    f = _ffi()
+    W = W_SH
+    pixels = _axis_pixels(W)
+    ref, k_obs = _raygen(ctx, p, f.make_observer([0.0, 0.0, 0.0]) if obs is None else obs, x0, W, W, 1, FOV_SH, rot=rot,
+                         pixels=pixels)
+    k0 = ref if obs is None else k_obs
+    axis = (np.eye(3) if rot is None else np.asarray(rot)) @ np.array([0.0, 0.0, -1.0])
+    ang = np.arccos(np.clip(ref @ axis, -1.0, 1.0))
+    _, flags, _, _ = ctx.trace(k0, x0, p)
+    dark = (flags & f.FLAG_HIT_HORIZON) != 0
+    row, col = dark[:W], dark[W:]
+    c = W // 2
+    assert row[c] and col[c] and not row[0] and not row[-1]
+    edges = []
+    for line in (row, col):
+        lo = c
+        while line[lo - 1]:
+            lo -= 1
+        hi = c
+        while line[hi + 1]:
+            hi += 1
+        assert line[lo:hi + 1].all() and not line[:lo].any() and not line[hi + 1:].any()   # one disc
+        edges.append((lo, hi))
+    return edges, k0, ang
+
+
+PIXEL = FOV_SH / W_SH * np.cos(np.radians(30.0)) ** 2    # the smallest angle one pixel spans near the edge (|angle| < 30 deg)
+
+
+def _assert_radius(edges, ang, alpha, tol=0.25 * PIXEL):
+    """On all four half-axes the shadow's edge, which lies between the last dark ray and the first lit one, is the angle alpha:
+    the last dark ray is no farther out than alpha + tol and the first lit ray no farther in than alpha - tol (tol a quarter of
+    a pixel: the integration's error near the critical curve)."""
+    W = W_SH
+    for j, (lo, hi) in enumerate(edges):
+        a = ang[j * W:(j + 1) * W]
+        for dark_edge, lit in ((hi, hi + 1), (lo, lo - 1)):
+            assert a[dark_edge] <= alpha + tol and a[lit] >= alpha - tol, (j, dark_edge, np.degrees([a[dark_edge], a[lit], alpha]))
+
+
+def _shadow_params(rhs=0, spin=0.0):
+    return _ffi().make_params(r_s=2.0, lambda_end=400.0, r_exit=40.0, max_step=0.1, rtol=1e-9, atol=1e-11, rhs_form=rhs, spin=spin)
+
+
+def test_shadow_synge_static_camera(ctx):
+    f = _ffi()
+    x0 = np.array([0.0, 0.0, 10.0])                                 # r = 10 M, looking at the hole (-z)
+    synge = np.arcsin(3.0 * np.sqrt(3.0) / 10.0 * np.sqrt(1.0 - 2.0 / 10.0))
+    p = _shadow_params()
+    edges, _, ang = _shadow_edges(ctx, p, f.make_observer([0.0, 0.0, 0.0]), x0)
+    _assert_radius(edges, ang, synge)
+    print(f"static observer at 10 M: Synge {np.degrees(synge):.3f} deg, edges {edges}")
+    # the reference camera (coordinate directions) does not give Synge's angle: its shadow is larger
+    ref_edges, _, ref_ang = _shadow_edges(ctx, p, None, x0)
+    with pytest.raises(AssertionError):
+        _assert_radius(ref_edges, ref_ang, synge)
+    assert ref_edges[0][1] - edges[0][1] > 5
+
+
+def test_shadow_falling_camera(ctx):
+    f = _ffi()
+    from blackhole_geodesic_calculator_amd import radial_infall_velocity
+    x0 = np.array([0.0, 0.0, 10.0])
+    beta = radial_infall_velocity(x0, 2.0) * 0.5 / np.sqrt(2.0 / 10.0)   # inward at 0.5
+    assert np.allclose(beta, [0.0, 0.0, -0.5])
+    synge = np.arcsin(3.0 * np.sqrt(3.0) / 10.0 * np.sqrt(1.0 - 2.0 / 10.0))
+    # the ZAMO sees the edge at angle synge from the look axis = beta_hat; the rest frame at theta' with
+    # cos theta = (cos theta' - b) / (1 - b cos theta') for the angles from -beta_hat ... here the look axis IS beta_hat:
+    # angles from beta_hat, cos theta' = (cos theta + b) / (1 + b cos theta)
+    b = 0.5
+    alpha_rest = np.arccos((np.cos(synge) + b) / (1.0 + b * np.cos(synge)))
+    edges, _, ang = _shadow_edges(ctx, _shadow_params(), f.make_observer(beta), x0)
+    _assert_radius(edges, ang, alpha_rest)
+    assert alpha_rest < synge - np.radians(3.0)     # the headlight effect shrinks the shadow
+    print(f"falling at 0.5: {np.degrees(alpha_rest):.3f} deg, edges {edges}")
+
+
+def test_kerr_zamo_shadow_asymmetry(ctx):
+    """A ZAMO on the equator of a = 0.9 M at r = 20 M (the retrograde edge, near 19 degrees, inside the field), looking at the hole, image x along +y (the sense of rotation at the camera).
+    Traced rays that leave towards +y are prograde (L > 0) and are captured only at smaller |b| than retrograde ones: the disc's
+    edge lies closer to the centre on the +y side, the shadow is shifted towards -y."""
+    f = _ffi()
+    x0 = np.array([20.0, 0.0, 0.0])
+    p = _shadow_params(rhs=2, spin=0.9)
+    edges, k0, _ = _shadow_edges(ctx, p, f.make_observer([0.0, 0.0, 0.0]), x0, rot=LOOK_MINUS_X)
+    (lo, hi), (clo, chi) = edges
+    c = W_SH // 2
+    E, L, _ = rr.kerr_E_L(x0, k0[hi], 1.0, 0.9)
+    assert L > 0          # the +y edge's rays are prograde
+    E, L, _ = rr.kerr_E_L(x0, k0[lo], 1.0, 0.9)
+    assert L < 0
+    assert (c - lo) - (hi - c) > 10, edges        # shifted towards -y (the side of the retrograde rays)
+    assert abs((c - clo) - (chi - c)) <= 1, edges  # symmetric in z
+    print(f"Kerr a = 0.9 ZAMO at 20 M: row edges {lo}, {hi} (centre {c}), column {clo}, {chi}")
+    # a = 0 is symmetric
+    e0, _, _ = _shadow_edges(ctx, _shadow_params(rhs=2, spin=0.0), f.make_observer([0.0, 0.0, 0.0]), x0, rot=LOOK_MINUS_X)
+    assert abs((c - e0[0][0]) - (e0[0][1] - c)) <= 1
+
+
+# ---- images ------------------------------------------------------------------------------------------------------------
+def _scene_frame(ctx, kerr, beta):
+    import torch
+    from blackhole_geodesic_calculator_amd.device_frame import DeviceFrame, synthetic_sky
+    W, H, S = 96, 64, 3
+    sky = synthetic_sky(512, 256)
+    disk_tex = synthetic_sky(256, 64, seed=3)
+    fr = DeviceFrame(ctx, W, H, S, fov_x=0.9, fov_y=0.9, sampling_seed=42.0, origin=CAM3, rotation_euler=(0.0, INC, 0.0))
+    fr.set_sky(sky)
+    fr.set_disk(3.0, 9.0, disk_tex, disk_phase=0.4, disk_mean=0.3, disk_stddev=0.25, disk_intensity=2.0)
+    sph = [[6.0, 3.0, 2.5, 1.5], [7.0, -4.0, 3.0, 1.0], [2.0, 6.0, -1.0, 1.2]]
+    rgb = [[1.0, 0.8, 0.6], [0.2, 0.9, 0.3], [0.5, 0.5, 1.0]]
+    lamps = [[20.0, 0.0, 20.0, 10.0], [10.0, -15.0, 5.0, 6.0]]
+    fr.set_objects(sph, rgb, lamps)
+    kw = dict(r_s=1.0, lambda_end=80.0, r_exit=40.0, disk_r_in=3.0, disk_r_out=9.0)
+    if kerr:
+        kw.update(rhs_form=2, spin=0.45)
+    p = _ffi().make_params(**kw)
+    fr.set_observer(beta)
+    fr.set_redshift(("disk", "objects", "sky"), 4.0, disk_sense=1)
+    rgba = fr.render(p).clone()
+    torch.cuda.synchronize()
+    ref = dict(disk=(3.0, 9.0), disk_tex=disk_tex, disk_profile=dict(phase=0.4, mean=0.3, stddev=0.25, intensity=2.0),
+               spheres=sph, sphere_rgb=np.array(rgb), lamps=lamps)
+    return fr, p, sky, ref, rgba.cpu().numpy()
+
+
+@pytest.mark.parametrize("kerr", [False, True])
+def test_orbiting_camera_image_against_reference(ctx, kerr):
+    """An observer on an inclined circular orbit through CAM3 (Schwarzschild: |beta| = sqrt(M / (r - 2M)) perpendicular to r^;
+    Kerr: the same velocity, a boosted observer): its rays are the restatement's, its image the reference shade weighted by
+    its own g."""
+    r = np.linalg.norm(CAM3)
+    beta = np.array([0.0, np.sqrt(0.5 / (r - 1.0)), 0.0])
+    fr, p, sky, ref, rgba = _scene_frame(ctx, kerr, beta)
+    spin = 0.45 if kerr else 0.0
+    end, flags, obj, k0 = fr.d_end.cpu().numpy(), fr.d_flags.cpu().numpy(), fr.d_obj.cpu().numpy(), fr.d_k0.cpu().numpy()
+    assert (flags == 128).sum() > 500 and (flags == 0x88).sum() > 50
+    g = orf.observer_g_rays(fr.origin, k0, end, flags, 1.0, beta, spin, kerr, 1)
+    want = rr.shade_scene_redshift(end, flags, obj, fr.P, fr.S, sky, g, 4.0, 7, **ref)
+    assert np.abs(rgba - want).max() < 1e-11
+    # the adaptor's own device calls give the same
+    import torch
+    d64 = torch.empty((fr.P, 4), dtype=torch.float64, device=fr.dev)
+    ctx.shade_scene_redshift_observer_device(fr.d_end.data_ptr(), fr.d_flags.data_ptr(), fr.P, fr.S, fr.scene(), fr._params,
+                                             fr.redshift, fr.observer, fr.origin, fr.d_k0.data_ptr(), d_rgba=d64.data_ptr(),
+                                             d_object_id=fr.d_obj.data_ptr(), stream=_stream())
+    torch.cuda.synchronize()
+    assert np.array_equal(d64.cpu().numpy(), rgba)
+    # None: the reference camera's frame again
+    fr.set_observer(None)
+    fr.set_redshift(None)
+    plain = fr.render(p).cpu().numpy()
+    assert np.abs(plain - rgba).max() > 1e-3
+
+
+def _frame(devices, W, H, S, cam, euler, **kw):
+    f = _ffi()
+    from blackhole_geodesic_calculator_amd.raygen import euler_xyz_matrix, python_random_stream
+    return f.Frame(devices, W, H, S, fov_x=0.9, fov_y=0.9, origin=cam, rot=euler_xyz_matrix(euler),
+                   jitter=python_random_stream(42.0, 2 * S * W * H), **kw)
+
+
+@pytest.mark.parametrize("scene", ["disk", "sky"])
+@pytest.mark.parametrize("kerr", [False, True])
+def test_frame_observer(ctx, scene, kerr):
+    """bhg_frame_set_observer: one device and the {0, 0} loopback (COPY and COPY_PEERCALL gathers) bit for bit; NULL gives the
+    frame without an observer bit for bit; a new origin regenerates the rays; the same image as DeviceFrame.set_observer."""
+    import torch
+    from blackhole_geodesic_calculator_amd.device_frame import DeviceFrame, synthetic_sky
+    f = _ffi()
+    W, H, S = 96, 64, 2
+    sky = synthetic_sky(512, 256)
+    kw = dict(r_s=1.0, lambda_end=80.0, r_exit=40.0)
+    if scene == "disk":
+        kw.update(disk_r_in=3.0, disk_r_out=9.0)
+    if kerr:
+        kw.update(rhs_form=2, spin=0.45)
+    p = f.make_params(**kw)
+    beta = [0.1, 0.3, -0.2]
+    cam2 = CAM3 * 0.8
+    images, moved = {}, {}
+    for name, devs, gather in (("one", [0], f.GATHER_AUTO), ("loop", [0, 0], f.GATHER_COPY),
+                               ("peercall", [0, 0], f.GATHER_COPY_PEERCALL)):
+        fr = _frame(devs, W, H, S, CAM3, (0.0, INC, 0.0), gather=gather, tile=16)
+        fr.set_scene(sky, disk=(3.0, 9.0) if scene == "disk" else None)
+        plain = fr.render(p)
+        fr.set_observer(beta)
+        fr.set_redshift(("disk", "sky"), 4.0, 1)
+        images[name] = fr.render(p)
+        assert np.abs(images[name] - plain).max() > 1e-3
+        fr.set_camera(fov_x=0.9, fov_y=0.9, origin=cam2, rot=_rot())
+        moved[name] = fr.render(p)
+        fr.set_camera(fov_x=0.9, fov_y=0.9, origin=CAM3, rot=_rot())
+        assert np.array_equal(fr.render(p), images[name])
+        fr.set_redshift(None)
+        fr.set_observer(None)
+        assert np.array_equal(fr.render(p), plain)
+        fr.close()
+    assert np.array_equal(images["one"], images["loop"]) and np.array_equal(images["one"], images["peercall"])
+    assert np.array_equal(moved["one"], moved["loop"]) and np.array_equal(moved["one"], moved["peercall"])
+    # a fresh frame at the new origin: the rays were made anew for it
+    fr = _frame([0], W, H, S, cam2, (0.0, INC, 0.0), tile=16)
+    fr.set_scene(sky, disk=(3.0, 9.0) if scene == "disk" else None)
+    fr.set_observer(beta)
+    fr.set_redshift(("disk", "sky"), 4.0, 1)
+    assert np.array_equal(fr.render(p), moved["one"])
+    fr.close()
+    # the Python adaptor
+    dfr = DeviceFrame(ctx, W, H, S, fov_x=0.9, fov_y=0.9, sampling_seed=42.0, origin=CAM3, rotation_euler=(0.0, INC, 0.0),
+                      directions_only=scene == "sky")
+    dfr.set_sky(sky)
+    if scene == "disk":
+        dfr.set_disk(3.0, 9.0)
+    dfr.set_observer(beta)
+    dfr.set_redshift(("disk", "sky"), 4.0, 1)
+    dfr.generate_rays(p)
+    dfr.trace(p)
+    out = torch.empty((W * H, 4), dtype=torch.float32, device=dfr.dev)
+    dfr.shade_f32(out)
+    torch.cuda.synchronize()
+    assert np.array_equal(out.cpu().numpy().reshape(H, W, 4), images["one"])
+
+
+def _rot():
+    from blackhole_geodesic_calculator_amd.raygen import euler_xyz_matrix
+    return euler_xyz_matrix((0.0, INC, 0.0))
+
+
+def test_frame_observer_refusals(ctx):
+    f = _ffi()
+    from blackhole_geodesic_calculator_amd.device_frame import synthetic_sky
+    fr = _frame([0], 32, 16, 1, CAM, (0.0, 0.0, 0.0), tile=16)
+    fr.set_scene(synthetic_sky(64, 32))
+    for bad in ([1.0, 0.0, 0.0], [np.nan, 0.0, 0.0]):
+        with pytest.raises(f.BhgError):
+            fr.set_observer(bad)
+    fr.set_observer([0.1, 0.0, 0.0])
+    # checked at render against the trace parameters: time_like, a Kerr camera on the axis
+    with pytest.raises(f.BhgError, match="time_like"):
+        fr.render(f.make_params(r_s=1.0, lambda_end=40.0, time_like=1))
+    fr.set_camera(fov_x=1.0, fov_y=1.0, origin=[0.0, 0.0, 30.0])
+    with pytest.raises(f.BhgError, match="axis"):
+        fr.render(f.make_params(r_s=1.0, lambda_end=40.0, rhs_form=2, spin=0.45))
+    fr.set_camera(fov_x=1.0, fov_y=1.0, origin=[0.95, 0.0, 0.0])      # BL r 0.84: outside r_+ = 0.72, inside r_E = 1
+    with pytest.raises(f.BhgError, match="ergosurface"):
+        fr.render(f.make_params(r_s=1.0, lambda_end=40.0, rhs_form=2, spin=0.45))
+    fr.set_camera(fov_x=1.0, fov_y=1.0, origin=[0.0, 0.0, 0.9])
+    with pytest.raises(f.BhgError, match="horizon"):
+        fr.render(f.make_params(r_s=1.0, lambda_end=40.0))
+    fr.close()
