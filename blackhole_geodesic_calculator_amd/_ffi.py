@@ -56,6 +56,7 @@ EXPORTS = (
     "bhg_redshift_size", "bhg_redshift_device", "bhg_redshift_host", "bhg_shade_scene_redshift_device", "bhg_frame_set_redshift",
     "bhg_observer_size", "bhg_raygen_observer_device", "bhg_redshift_observer_device", "bhg_redshift_observer_host",
     "bhg_shade_scene_redshift_observer_device", "bhg_frame_set_observer",
+    "bhg_object_textures_size", "bhg_shade_scene_textured_device", "bhg_frame_set_object_textures",
 )
 PROBE_FMA, PROBE_STEP_MIX = 0, 1
 
@@ -101,6 +102,49 @@ def make_observer(velocity):
 
 def _obs_ref(obs):
     return None if obs is None else C.byref(obs)
+
+
+OBJECT_LIT, OBJECT_EMISSIVE = 0, 1
+_OBJECT_MODE = {"lit": OBJECT_LIT, "emissive": OBJECT_EMISSIVE}
+
+
+class ObjectTextures(C.Structure):
+    """bhg_object_textures (BHG_OBJECT_TEXTURES, within ABI 10): per object sphere an equirectangular RGBA float32 texture
+    (or NULL: white), its size, the mode (OBJECT_LIT / OBJECT_EMISSIVE), the emission strength and the row-major body -> world
+    rotation (all zero = the identity)."""
+    _fields_ = [("tex", C.c_void_p * 8), ("tex_w", C.c_int32 * 8), ("tex_h", C.c_int32 * 8), ("mode", C.c_int32 * 8),
+                ("emission", C.c_double * 8), ("rot", (C.c_double * 9) * 8)]
+
+
+def make_object_textures(textures=None, rotations=None, modes=None, emission=None):
+    """(ObjectTextures, arrays to keep alive).  Per sphere, in the scene's order (at most 8, missing ones are zero):
+    textures -- None (NULL: white for a shade call, keep the current one for a frame), a float32 [h, w, 4] host array, or a
+    device texture as a tuple (address, w, h); rotations -- None (the identity) or a 3x3 body -> world rotation; modes --
+    "lit" / "emissive" or OBJECT_LIT / OBJECT_EMISSIVE (None: lit); emission -- the emissive strength (None: 0)."""
+    ot, keep = ObjectTextures(), []
+    if any(v is not None and len(v) > MAX_SPHERES for v in (textures, rotations, modes, emission)):
+        raise ValueError(f"at most {MAX_SPHERES} spheres")
+    for j, t in enumerate(textures or []):
+        if t is None:
+            continue
+        if isinstance(t, tuple):
+            ot.tex[j], ot.tex_w[j], ot.tex_h[j] = int(t[0]) or None, int(t[1]), int(t[2])
+            continue
+        a = np.ascontiguousarray(t, dtype=np.float32)
+        if a.ndim != 3 or a.shape[2] != 4:
+            raise ValueError(f"texture of sphere {j} must be [h, w, 4] float32, not {a.shape}")
+        ot.tex[j], ot.tex_w[j], ot.tex_h[j] = a.ctypes.data, a.shape[1], a.shape[0]
+        keep.append(a)
+    for j, r in enumerate(rotations if rotations is not None else []):
+        if r is not None:
+            ot.rot[j][:] = [float(v) for v in np.asarray(r, dtype=np.float64).reshape(9)]
+    for j, m in enumerate(modes if modes is not None else []):
+        if m is not None:
+            ot.mode[j] = _OBJECT_MODE[m] if isinstance(m, str) else int(m)
+    for j, k in enumerate(emission if emission is not None else []):
+        if k is not None:
+            ot.emission[j] = float(k)
+    return ot, keep
 
 
 class Camera(C.Structure):
@@ -369,6 +413,15 @@ def load():
                                                            C.c_void_p, C.c_void_p]
     L.bhg_frame_set_observer.restype = C.c_int
     L.bhg_frame_set_observer.argtypes = [C.c_void_p, C.POINTER(Observer)]
+    L.bhg_object_textures_size.restype = C.c_size_t
+    L.bhg_object_textures_size.argtypes = []
+    L.bhg_shade_scene_textured_device.restype = C.c_int
+    L.bhg_shade_scene_textured_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32,
+                                                  C.POINTER(Scene), C.POINTER(Params), C.POINTER(Redshift), C.POINTER(Observer),
+                                                  C.POINTER(ObjectTextures), _dp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]
+    L.bhg_frame_set_object_textures.restype = C.c_int
+    L.bhg_frame_set_object_textures.argtypes = [C.c_void_p, C.POINTER(ObjectTextures)]
     if L.bhg_version() != ABI_VERSION or not hasattr(L, "bhg_abi_check"):
         raise ImportError(f"libbhgeo ABI {L.bhg_version()} != expected {ABI_VERSION}: rebuild {LIB_PATH}")
     for name in ("bhg_params_size", "bhg_camera_size", "bhg_scene_size", "bhg_frame_scene_size"):
@@ -387,6 +440,9 @@ def load():
         raise ImportError(f"libbhgeo: bhg_redshift is {L.bhg_redshift_size()} bytes, this binding's {C.sizeof(Redshift)}")
     if L.bhg_observer_size() != C.sizeof(Observer):
         raise ImportError(f"libbhgeo: bhg_observer is {L.bhg_observer_size()} bytes, this binding's {C.sizeof(Observer)}")
+    if L.bhg_object_textures_size() != C.sizeof(ObjectTextures):
+        raise ImportError(f"libbhgeo: bhg_object_textures is {L.bhg_object_textures_size()} bytes, this binding's "
+                          f"{C.sizeof(ObjectTextures)}")
     _lib = L
     return L
 
@@ -667,6 +723,18 @@ class Frame:
         with velocity beta (3 numbers, world axes, relative to the ZAMO; observer.py has the common ones) sees.  None: the
         reference camera again, bit for bit."""
         _check(load().bhg_frame_set_observer(self._h, _obs_ref(make_observer(velocity))))
+
+    def set_object_textures(self, textures=None, rotations=None, modes=None, emission=None):
+        """Textured, oriented and emissive object spheres in every later render (bhg_frame_set_object_textures; DESIGN.md
+        section 11), per sphere of the scene: textures [h, w, 4] float32 host arrays (None: keep that sphere's current
+        texture, white if it never had one), 3x3 body -> world rotations (None: the identity), modes ("lit" / "emissive"),
+        emission strengths.  Only new images are uploaded.  All None: textures off -- the frame as without them, bit for bit."""
+        if textures is None and rotations is None and modes is None and emission is None:
+            _check(load().bhg_frame_set_object_textures(self._h, None))
+            return
+        ot, keep = make_object_textures(textures, rotations, modes, emission)
+        _check(load().bhg_frame_set_object_textures(self._h, C.byref(ot)))
+        del keep
 
     def render(self, params: "Params", out=None, to_host=True):
         """One frame: float32 [H, W, 4] (a new array, or `out`).  to_host=False: only enqueue; the image stays on the
@@ -987,6 +1055,17 @@ class Context:
             int(n_pixels), int(samples), C.byref(scene), C.byref(params), None if rs is None else C.byref(rs), _obs_ref(obs), xs,
             C.c_void_p(d_k0), C.c_void_p(d_rgba or None), C.c_void_p(d_rgba_f32 or None), C.c_void_p(d_scatter or None),
             C.c_void_p(stream or None)))
+
+    def shade_scene_textured_device(self, d_end, d_flags, n_pixels, samples, scene: "Scene", params, rs, obs, ot, x0_shared=None,
+                                    d_k0=0, d_rgba=0, d_rgba_f32=0, d_object_id=0, d_scatter=0, d_end_dir=0, stream=0):
+        """bhg_shade_scene_textured_device: shade_scene_redshift_observer_device with object textures ot (ObjectTextures whose
+        tex are device addresses, or None = without textures).  rs / obs / params may be None when redshift is off."""
+        xs = None if x0_shared is None else (C.c_double * 3)(*[float(v) for v in x0_shared])
+        _check(load().bhg_shade_scene_textured_device(
+            self._h, C.c_void_p(d_end or None), C.c_void_p(d_end_dir or None), C.c_void_p(d_flags), C.c_void_p(d_object_id or None),
+            int(n_pixels), int(samples), C.byref(scene), None if params is None else C.byref(params),
+            None if rs is None else C.byref(rs), _obs_ref(obs), None if ot is None else C.byref(ot), xs, C.c_void_p(d_k0 or None),
+            C.c_void_p(d_rgba or None), C.c_void_p(d_rgba_f32 or None), C.c_void_p(d_scatter or None), C.c_void_p(stream or None)))
 
     def assemble_frame_f32_device(self, d_slabs, d_index, n_pixels, d_frame, stream=0):
         _check(load().bhg_assemble_frame_f32_device(self._h, C.c_void_p(d_slabs), C.c_void_p(d_index), int(n_pixels),

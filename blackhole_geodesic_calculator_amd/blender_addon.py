@@ -34,6 +34,16 @@ Known deviations from the reference, all deliberate:
     filter of the image, not Blender's texture filter (which cannot be reproduced outside Blender): the images agree
     to the filter difference.  Needs the whole frame (no mark_* window: the window's RNG alignment is a host matter);
     with a window set the host path is used.
+  * textured, oriented and emissive objects (with `curved_space_objects` on): a traced mesh object
+    reads two custom properties -- `curved_space_texture`, the name of a `bpy.data.images` image wrapped on its sphere
+    (equirectangular, body +x the image's centre column, body +z its top row), and `curved_space_emission`, a float: above
+    0 the object glows with that strength (no lamps, no shadows: the reference's `emission` branch, :331-339), 0 or absent
+    it is lamp-lit with the texture as albedo.  Its orientation is the rotation part of `matrix_world` (columns normalised).
+    The host path reads the texture through a `bpy.data.textures` IMAGE texture's `evaluate((U, V, 0))`, as it shades the
+    sky; the device path uploads the image's pixels once (bhg_frame_set_object_textures) and turns the sphere per frame by
+    kernel argument.  The reference's literal mapping (arctan(n_y/n_x), read at (ph/2pi, th/pi)) folds the two
+    x-hemispheres and reads a quarter of the image: deliberately not reproduced.  A scene without these properties renders
+    exactly as before.
 """
 import warnings
 import os
@@ -149,6 +159,7 @@ class RelativisticRenderEngine(bpy.types.RenderEngine):
         want_objects = float(getattr(depsgraph.scene, "curved_space_objects", 0) or 0) != 0.0
         spheres = self.scene_spheres(depsgraph) if want_objects else np.zeros((0, 4))
         self._lit_spheres = spheres
+        self._sphere_looks = self.sphere_looks() if want_objects else []
         if getattr(self, "device_shading", False) and mark is None:
             yield from self.ray_trace_device(width, height, samples, buf, origin, rotation, spheres)
             return
@@ -172,11 +183,52 @@ class RelativisticRenderEngine(bpy.types.RenderEngine):
             loc = np.array(list(ob.location), dtype=np.float64)
             radius = 0.5 * max(float(d) for d in ob.dimensions)
             if radius > 0.0:
-                out.append([loc[0], loc[1], loc[2], radius])
-        out.sort(key=lambda s: float(np.linalg.norm(np.array(s[:3]) - self.bh_loc)))
+                out.append(([loc[0], loc[1], loc[2], radius], ob))
+        out.sort(key=lambda s: float(np.linalg.norm(np.array(s[0][:3]) - self.bh_loc)))
         if len(out) > 8:
             warnings.warn(f"{len(out)} mesh objects in the scene: only the 8 nearest to the hole are traced", RuntimeWarning)
-        return np.array(out[:8], dtype=np.float64).reshape(-1, 4)
+        self._sphere_objects = [ob for _, ob in out[:8]]
+        return np.array([sp for sp, _ in out[:8]], dtype=np.float64).reshape(-1, 4)
+
+    @staticmethod
+    def _custom(ob, key):
+        """A custom property of a Blender ID (ob["key"]), None when absent."""
+        get = getattr(ob, "get", None)
+        return get(key) if callable(get) else None
+
+    @staticmethod
+    def _orientation(ob):
+        """The rotation part of ob.matrix_world (body -> world, row-major) with its columns normalised to remove the scale;
+        the all-zero matrix (the identity by the library's convention) when there is none."""
+        mw = getattr(ob, "matrix_world", None)
+        if mw is None:
+            return np.zeros((3, 3))
+        m = np.array([[float(mw[i][k]) for k in range(3)] for i in range(3)], dtype=np.float64)
+        norms = np.linalg.norm(m, axis=0)
+        return m / norms if np.all(norms > 0.0) else np.zeros((3, 3))
+
+    def sphere_looks(self):
+        """Per traced sphere (scene_spheres' order): {"image": bpy.data.images name or None, "emission": float, "rot": 3x3} from
+        the custom properties curved_space_texture / curved_space_emission and the object's matrix_world."""
+        looks = []
+        for ob in getattr(self, "_sphere_objects", []):
+            name = self._custom(ob, "curved_space_texture")
+            name = str(name) if name else None
+            if name is not None and name not in bpy.data.images:
+                warnings.warn(f"curved_space_texture {name!r}: no such image in bpy.data.images (the object stays untextured)",
+                              RuntimeWarning)
+                name = None
+            emission = float(self._custom(ob, "curved_space_emission") or 0.0)
+            looks.append({"image": name, "emission": max(emission, 0.0), "rot": self._orientation(ob)})
+        return looks
+
+    def _object_texture(self, image_name):
+        """The bpy.data.textures IMAGE texture of an object image (made once, as the sky's, :111-112)."""
+        tex_name = image_name + "_tex"
+        if tex_name not in bpy.data.textures:
+            tex = bpy.data.textures.new(tex_name, "IMAGE")
+            tex.image = bpy.data.images[image_name]
+        return bpy.data.textures[tex_name]
 
     LAMP_INTENSITY = 10.0   # spacetime_hit's default `intensity` (:317)
 
@@ -206,6 +258,20 @@ class RelativisticRenderEngine(bpy.types.RenderEngine):
                 blocked = (disc > 0.0) & (((t0 > 1e-5) & (t0 < dist)) | ((t0 <= 1e-5) & (t1 > 1e-5))) & (index != q)
                 lit &= ~blocked
             color += np.where(lit, intensity * intensity * ndl / d2, 0.0)[:, None]
+        # textured / emissive objects: texel at the body-frame normal's angles
+        for j, look in enumerate(getattr(self, "_sphere_looks", [])):
+            m = index == j
+            if not m.any() or (look["image"] is None and not look["emission"] > 0.0):
+                continue
+            texel = np.ones((int(m.sum()), 3))
+            if look["image"] is not None:
+                R = look["rot"] if look["rot"].any() else np.eye(3)
+                nb = normal[m] @ R                                      # R^T n, row by row
+                U = np.arctan2(nb[:, 1], nb[:, 0]) / np.pi
+                V = 1.0 - 2.0 * np.arctan2(np.hypot(nb[:, 0], nb[:, 1]), nb[:, 2]) / np.pi
+                tex = self._object_texture(look["image"])
+                texel = np.array([tex.evaluate((float(u), float(v), 0)).xyz for u, v in zip(U, V)], dtype=np.float64)
+            color[m] = look["emission"] * texel if look["emission"] > 0.0 else color[m] * texel
         return color
 
     # ---- the whole frame on the device (opt-in, scene.device_shading) ------------------------------------------------
@@ -343,6 +409,7 @@ class RelativisticRenderEngine(bpy.types.RenderEngine):
             self.device_sky_uploaded = sky is not None
             fr.set_scene(sky, spheres=sp, sphere_rgb=None if sp is None else np.ones((len(sp), 3)), lamps=lamps)
             fr.sky_identity = sky_id
+            self._set_device_object_textures(fr)
             rgba = fr.render(self.GeoInt.params(self.max_integration_step, self.int_depth_curve_end))
             buf[:, :, :] = rgba.reshape(height, width, 4)
             self.last_device_frame = fr.info()
@@ -352,6 +419,54 @@ class RelativisticRenderEngine(bpy.types.RenderEngine):
         n = samples * height
         for i in range(n):       # progress: the frame is one launch per device, reported after the fact at ray_trace's cadence
             yield (i + 1) / n
+
+    def _image_identity(self, name):
+        """What tells an object image's content apart without reading it: name, size, file path; None (read and upload) while
+        it has unsaved edits."""
+        img = bpy.data.images[name]
+        if getattr(img, "is_dirty", False):
+            return None
+        size = getattr(img, "size", None) or (0, 0)
+        return (name, int(size[0]), int(size[1]), str(getattr(img, "filepath", "") or ""))
+
+    def _image_pixels(self, name):
+        """An image as float32 [h, w, 4], rows bottom-up (the library's convention, as for the sky)."""
+        img = bpy.data.images[name]
+        w, h = (int(v) for v in img.size)
+        px = np.empty(w * h * 4, dtype=np.float32)
+        if hasattr(img.pixels, "foreach_get"):
+            img.pixels.foreach_get(px)
+        else:
+            px[:] = np.asarray(img.pixels[:], dtype=np.float32)
+        return px.reshape(h, w, 4)
+
+    def _set_device_object_textures(self, fr):
+        """The traced spheres' looks on the library-owned frame: images are read and uploaded only when a slot's image is
+        another than the frame holds (an animation turns its sphere every frame: that is a kernel argument); a scene without
+        textured or emissive objects turns them off (the frame's shading as before, bit for bit)."""
+        looks = getattr(self, "_sphere_looks", [])
+        held = getattr(fr, "object_image_ids", None) or [None] * 8
+        if not any(l["image"] is not None or l["emission"] > 0.0 for l in looks):
+            fr.set_object_textures()
+            fr.object_image_ids = [None] * 8
+            return
+        textures, ids = [], list(held)
+        for j, look in enumerate(looks):
+            ident = None if look["image"] is None else self._image_identity(look["image"])
+            if look["image"] is None:
+                # (the slot's texture must be white: a slot that held an image is given a 1 x 1 white one)
+                textures.append(np.ones((1, 1, 4), np.float32) if held[j] != ("<white>",) else None)
+                ids[j] = ("<white>",)
+            elif ident is None or ident != held[j]:
+                textures.append(self._image_pixels(look["image"]))
+                ids[j] = ident
+            else:
+                textures.append(None)
+        fr.set_object_textures(textures=textures, rotations=[l["rot"] for l in looks],
+                               modes=["emissive" if l["emission"] > 0.0 else "lit" for l in looks],
+                               emission=[l["emission"] for l in looks])
+        fr.object_image_ids = ids
+        self.device_object_images_uploaded = sum(t is not None for t in textures)
 
     # ---- shading (:366-378), Blender's own texture filter ------------------------------------
     def background_hit(self, direction):

@@ -45,6 +45,8 @@ static_assert(BHG_REDSHIFT_DISK == bhg::BHG_REDSHIFT_DISK_ && BHG_REDSHIFT_OBJEC
               "redshift class mismatch");
 static_assert(sizeof(bhg_redshift) == 16, "bhg_redshift layout is part of the ABI");
 static_assert(sizeof(bhg_observer) == 24, "bhg_observer layout is part of the ABI");
+static_assert(sizeof(bhg_object_textures) == 800, "bhg_object_textures layout is part of the ABI");
+static_assert(BHG_OBJECT_LIT == bhg::BHG_OBJECT_LIT_ && BHG_OBJECT_EMISSIVE == bhg::BHG_OBJECT_EMISSIVE_, "object mode mismatch");
 
 namespace {
 
@@ -454,6 +456,66 @@ int observer_params(const bhg_params *p, const bhg_observer *obs, const double *
     out->on = 1;
     return BHG_OK;
 }
+
+// Object textures (include/bhgeo.h, "textured, oriented and emissive object spheres") for a scene of n_spheres spheres: slots
+// at or above n_spheres are not looked at.  *out = the kernels' table (an all-zero rotation becomes the identity), on = 1.
+// Also used by bhgeo_frame.hip (there with tex = the host arrays: only whether a slot has one matters).
+int object_texture_params(const bhg_object_textures *ot, int32_t n_spheres, ObjectTextureParams *out)
+{
+    if (!ot) return fail(BHG_E_INVALID, "object textures are NULL");
+    std::memset(out, 0, sizeof(*out));
+    const int n = n_spheres < 0 ? 0 : (n_spheres > BHG_MAX_SPHERES ? BHG_MAX_SPHERES : n_spheres);
+    char msg[256];
+    for (int j = 0; j < n; j++) {
+        if (ot->mode[j] != BHG_OBJECT_LIT && ot->mode[j] != BHG_OBJECT_EMISSIVE) {
+            std::snprintf(msg, sizeof msg, "object textures: sphere %d: mode %d is neither BHG_OBJECT_LIT (0) nor BHG_OBJECT_EMISSIVE (1)",
+                          j, (int)ot->mode[j]);
+            return fail(BHG_E_INVALID, msg);
+        }
+        if (!(std::isfinite(ot->emission[j]) && ot->emission[j] >= 0.0)) {
+            std::snprintf(msg, sizeof msg, "object textures: sphere %d: emission %.17g must be finite and >= 0", j, ot->emission[j]);
+            return fail(BHG_E_INVALID, msg);
+        }
+        if (ot->tex[j] && (ot->tex_w[j] < 1 || ot->tex_h[j] < 1)) {
+            std::snprintf(msg, sizeof msg, "object textures: sphere %d: texture size %d x %d must be at least 1 x 1", j,
+                          (int)ot->tex_w[j], (int)ot->tex_h[j]);
+            return fail(BHG_E_INVALID, msg);
+        }
+        const double *R = ot->rot[j];
+        bool zero = true, finite = true;
+        for (int q = 0; q < 9; q++) {
+            zero = zero && R[q] == 0.0;
+            finite = finite && std::isfinite(R[q]);
+        }
+        if (zero) {
+            static const double eye[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+            std::memcpy(out->rot[j], eye, sizeof(eye));
+        } else {
+            // |R^T R - I| <= 1e-9 element by element, and det R = +1 (an orthonormal R has det +-1)
+            double dev = finite ? 0.0 : INFINITY;
+            for (int u = 0; u < 3 && finite; u++)
+                for (int v = 0; v < 3; v++) {
+                    const double rtr = R[u] * R[v] + R[3 + u] * R[3 + v] + R[6 + u] * R[6 + v];
+                    dev = std::fmax(dev, std::fabs(rtr - (u == v ? 1.0 : 0.0)));
+                }
+            const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) +
+                               R[2] * (R[3] * R[7] - R[4] * R[6]);
+            if (!(dev <= 1e-9) || !(det > 0.0)) {
+                std::snprintf(msg, sizeof msg, "object textures: sphere %d: rotation is neither all zero nor a proper rotation "
+                              "(max |R^T R - I| = %.3g, det = %.17g)", j, dev, det);
+                return fail(BHG_E_INVALID, msg);
+            }
+            std::memcpy(out->rot[j], R, sizeof(out->rot[j]));
+        }
+        out->tex[j] = ot->tex[j];
+        out->tex_w[j] = ot->tex[j] ? ot->tex_w[j] : 0;
+        out->tex_h[j] = ot->tex[j] ? ot->tex_h[j] : 0;
+        out->mode[j] = ot->mode[j];
+        out->emission[j] = ot->emission[j];
+    }
+    out->on = 1;
+    return BHG_OK;
+}
 }  // namespace bhg
 
 extern "C" {
@@ -479,6 +541,7 @@ size_t bhg_scene_size(void) { return sizeof(bhg_scene); }
 size_t bhg_frame_scene_size(void) { return sizeof(bhg_frame_scene); }
 size_t bhg_redshift_size(void) { return sizeof(bhg_redshift); }
 size_t bhg_observer_size(void) { return sizeof(bhg_observer); }
+size_t bhg_object_textures_size(void) { return sizeof(bhg_object_textures); }
 
 int bhg_abi_check(int abi_version, size_t params_size, size_t camera_size, size_t scene_size, size_t frame_scene_size)
 {
@@ -1361,7 +1424,7 @@ int shade_scene_impl(bhg_context *c, const double *d_end, const uint8_t *d_flags
                      size_t n_pixels, int32_t samples, const bhg_scene *sc, double *d_rgba, float *d_rgba_f32,
                      const int64_t *d_scatter, void *stream, const double *d_end_dir = nullptr,
                      const bhg::RedshiftParams *rs = nullptr, const double *d_k0 = nullptr,
-                     const bhg::ObserverParams *obs = nullptr);
+                     const bhg::ObserverParams *obs = nullptr, const bhg::ObjectTextureParams *ot = nullptr);
 }
 
 extern "C" {
@@ -1388,7 +1451,7 @@ namespace {
 int shade_scene_impl(bhg_context *c, const double *d_end, const uint8_t *d_flags, const int8_t *d_object_id,
                      size_t n_pixels, int32_t samples, const bhg_scene *sc, double *d_rgba, float *d_rgba_f32,
                      const int64_t *d_scatter, void *stream, const double *d_end_dir, const bhg::RedshiftParams *rs,
-                     const double *d_k0, const bhg::ObserverParams *obs)
+                     const double *d_k0, const bhg::ObserverParams *obs, const bhg::ObjectTextureParams *ot)
 {
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
     if (!sc) return fail(BHG_E_INVALID, "scene is NULL");
@@ -1441,6 +1504,7 @@ int shade_scene_impl(bhg_context *c, const double *d_end, const uint8_t *d_flags
     std::memcpy(a.spheres, sc->spheres, sizeof(a.spheres));
     std::memcpy(a.sphere_rgb, sc->sphere_rgb, sizeof(a.sphere_rgb));
     std::memcpy(a.lamps, sc->lamps, sizeof(a.lamps));
+    if (ot) a.ot = *ot;
     HIP_TRY(bhg::launch_shade(a, (hipStream_t)stream));
     return BHG_OK;
 }
@@ -1458,12 +1522,14 @@ int bhg_shade_scene_redshift_device(bhg_context *c, const double *d_end, const d
                                                     nullptr, x0_shared, d_k0, d_rgba, d_rgba_f32, d_scatter, stream);
 }
 
-int bhg_shade_scene_redshift_observer_device(bhg_context *c, const double *d_end, const double *d_end_dir,
-                                             const uint8_t *d_flags, const int8_t *d_object_id, size_t n_pixels,
-                                             int32_t samples, const bhg_scene *sc, const bhg_params *p,
-                                             const bhg_redshift *rs, const bhg_observer *obs, const double *x0_shared,
-                                             const double *d_k0, double *d_rgba, float *d_rgba_f32,
-                                             const int64_t *d_scatter, void *stream)
+}  // extern "C"
+
+namespace {
+// bhg_shade_scene_redshift_observer_device with the textured instance's table (ot = nullptr: without textures)
+int shade_scene_rs_impl(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags, const int8_t *d_object_id,
+                        size_t n_pixels, int32_t samples, const bhg_scene *sc, const bhg_params *p, const bhg_redshift *rs,
+                        const bhg_observer *obs, const double *x0_shared, const double *d_k0, double *d_rgba, float *d_rgba_f32,
+                        const int64_t *d_scatter, void *stream, const bhg::ObjectTextureParams *ot)
 {
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
     if (!sc) return fail(BHG_E_INVALID, "scene is NULL");
@@ -1484,7 +1550,39 @@ int bhg_shade_scene_redshift_observer_device(bhg_context *c, const double *d_end
         if (rc != BHG_OK) return rc;
     }
     return shade_scene_impl(c, d_end, d_flags, d_object_id, n_pixels, samples, sc, d_rgba, d_rgba_f32, d_scatter, stream,
-                            d_end_dir, on ? &rp : nullptr, d_k0, on && obs ? &op : nullptr);
+                            d_end_dir, on ? &rp : nullptr, d_k0, on && obs ? &op : nullptr, ot);
+}
+}  // namespace
+
+extern "C" {
+
+int bhg_shade_scene_redshift_observer_device(bhg_context *c, const double *d_end, const double *d_end_dir,
+                                             const uint8_t *d_flags, const int8_t *d_object_id, size_t n_pixels,
+                                             int32_t samples, const bhg_scene *sc, const bhg_params *p,
+                                             const bhg_redshift *rs, const bhg_observer *obs, const double *x0_shared,
+                                             const double *d_k0, double *d_rgba, float *d_rgba_f32,
+                                             const int64_t *d_scatter, void *stream)
+{
+    return shade_scene_rs_impl(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs, obs, x0_shared, d_k0, d_rgba,
+                               d_rgba_f32, d_scatter, stream, nullptr);
+}
+
+int bhg_shade_scene_textured_device(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
+                                    const int8_t *d_object_id, size_t n_pixels, int32_t samples, const bhg_scene *sc,
+                                    const bhg_params *p, const bhg_redshift *rs, const bhg_observer *obs,
+                                    const bhg_object_textures *ot, const double *x0_shared, const double *d_k0, double *d_rgba,
+                                    float *d_rgba_f32, const int64_t *d_scatter, void *stream)
+{
+    if (!ot)
+        return bhg_shade_scene_redshift_observer_device(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs, obs,
+                                                        x0_shared, d_k0, d_rgba, d_rgba_f32, d_scatter, stream);
+    // (the table is checked before the context: a refusal names its sphere with or without a device)
+    if (!sc) return fail(BHG_E_INVALID, "scene is NULL");
+    bhg::ObjectTextureParams tp;
+    int rc = bhg::object_texture_params(ot, sc->n_spheres, &tp);
+    if (rc != BHG_OK) return rc;
+    return shade_scene_rs_impl(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs, obs, x0_shared, d_k0, d_rgba,
+                               d_rgba_f32, d_scatter, stream, &tp);
 }
 
 int bhg_redshift_device(bhg_context *c, const bhg_params *p, const bhg_redshift *rs, const double *x0_shared,

@@ -39,6 +39,8 @@ void host_copy(bhg_context *c, void *dst, const void *src, size_t bytes, size_t 
 int redshift_params(const bhg_params *p, const bhg_redshift *rs, double disk_r_in, const double *x0, RedshiftParams *out);
 // bhgeo_capi.hip: observer settings checked against the trace parameters and the camera
 int observer_params(const bhg_params *p, const bhg_observer *obs, const double *x0, ObserverParams *out);
+// bhgeo_capi.hip: object textures checked against a scene of n_spheres spheres
+int object_texture_params(const bhg_object_textures *ot, int32_t n_spheres, ObjectTextureParams *out);
 }
 
 namespace {
@@ -180,10 +182,12 @@ struct Shard {
     std::vector<int64_t> pixels;    // flat ids y * W + x, tile after tile
     size_t P = 0, n = 0;
     DevBuf pixels_d, jitter_d, k0, end, dir, flags, steps, acc, obj, slab, sky, disk_tex;
+    DevBuf otex[BHG_MAX_SPHERES];   // the object textures (bhg_frame_set_object_textures), slot by slot
     hipEvent_t done = nullptr;
     bool rays_ready = false;
     bool jitter_ready = false;      // jitter_d holds the draws of THIS pixel list (kept: a rotating camera regenerates the rays from it)
     bool scene_ready = false;
+    bool otex_ready = false;        // otex holds the frame's current object textures
     bool dir_traced = false;
     nccl_comm_t comm = nullptr;
     // profiling: HIP event pairs around the trace call of every profiled render since the last bhg_frame_last_ms()
@@ -207,6 +211,10 @@ struct bhg_frame {
     bool observer = false;          // bhg_frame_set_observer; false: the reference camera (the ray generation of ABI 9)
     bhg_observer obs = {{0.0, 0.0, 0.0}};
     double obs_key[6] = {};         // camera origin, r_s, spin, rhs_form the observer rays on the devices were made for
+    bool textured = false;          // bhg_frame_set_object_textures; false: the object shading without textures
+    bhg_object_textures ot = {};    // its rotations, modes and strengths (tex: not used, the images are otex)
+    std::vector<float> otex[BHG_MAX_SPHERES];    // host copies of the object textures, empty = white
+    int32_t otex_w[BHG_MAX_SPHERES] = {}, otex_h[BHG_MAX_SPHERES] = {};
     // root (device of shard 0)
     DevBuf recv, perm, image;       // [n_dev * pmax][4] float, [H W] int64, [H W][4] float
     size_t pmax = 0;
@@ -321,6 +329,36 @@ int upload_shard_scene(bhg_frame *f, Shard &s)
     return BHG_OK;
 }
 
+int upload_shard_textures(bhg_frame *f, Shard &s)
+{
+    HIP_TRY(hipSetDevice(s.device));
+    for (int j = 0; j < BHG_MAX_SPHERES; j++) {
+        const std::vector<float> &t = f->otex[j];
+        if (t.empty()) {
+            s.otex[j].release();
+            continue;
+        }
+        BHG_TRY(s.otex[j].ensure(s.device, t.size() * sizeof(float)));
+        HIP_TRY(hipMemcpyAsync(s.otex[j].p, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice, s.stream));
+    }
+    HIP_TRY(hipStreamSynchronize(s.stream));
+    s.otex_ready = true;
+    return BHG_OK;
+}
+
+// the frame's object textures as the shade call takes them: tex = the shard's device copies (s = nullptr: the host copies,
+// for the checks before a render)
+void fill_object_textures(const bhg_frame *f, const Shard *s, bhg_object_textures *ot)
+{
+    *ot = f->ot;
+    for (int j = 0; j < BHG_MAX_SPHERES; j++) {
+        const bool has = !f->otex[j].empty();
+        ot->tex[j] = !has ? nullptr : (s ? s->otex[j].as<float>() : f->otex[j].data());
+        ot->tex_w[j] = has ? f->otex_w[j] : 0;
+        ot->tex_h[j] = has ? f->otex_h[j] : 0;
+    }
+}
+
 int build_root(bhg_frame *f)
 {
     // receive block, frame permutation, image -- on the device of shard 0
@@ -390,6 +428,7 @@ void destroy_frame(bhg_frame *f)
         (void)hipSetDevice(s.device);
         for (DevBuf *b : {&s.pixels_d, &s.jitter_d, &s.k0, &s.end, &s.dir, &s.flags, &s.steps, &s.acc, &s.obj, &s.slab, &s.sky, &s.disk_tex})
             b->release();
+        for (DevBuf &b : s.otex) b.release();
         if (s.done) (void)hipEventDestroy(s.done);
         for (auto &e : s.evs) {
             (void)hipEventDestroy(e.first);
@@ -627,6 +666,53 @@ int bhg_frame_set_observer(bhg_frame *f, const bhg_observer *obs)
     return BHG_OK;
 }
 
+int bhg_frame_set_object_textures(bhg_frame *f, const bhg_object_textures *ot)
+try {
+    if (!f) return fail(BHG_E_INVALID, "frame is NULL");
+    if (!ot) {
+        // off: the frame's shading without textures, and the images freed (host and devices)
+        f->textured = false;
+        std::memset(&f->ot, 0, sizeof(f->ot));
+        for (int j = 0; j < BHG_MAX_SPHERES; j++) {
+            std::vector<float>().swap(f->otex[j]);
+            f->otex_w[j] = f->otex_h[j] = 0;
+        }
+        DeviceScope scope;
+        for (auto &s : f->sh) {
+            for (DevBuf &b : s.otex) b.release();
+            s.otex_ready = false;
+        }
+        return BHG_OK;
+    }
+    // the checks of the shade call, against the scene as it stands (and again at every render)
+    bhg::ObjectTextureParams tp;
+    BHG_TRY(bhg::object_texture_params(ot, f->scene.n_spheres, &tp));
+    // the new images are copied aside first: a refused host allocation leaves the frame as it was
+    const int n = f->scene.n_spheres;
+    std::vector<float> fresh[BHG_MAX_SPHERES];
+    bool images_changed = false;
+    for (int j = 0; j < n; j++)
+        if (ot->tex[j]) {
+            fresh[j].assign(ot->tex[j], ot->tex[j] + (size_t)ot->tex_w[j] * (size_t)ot->tex_h[j] * 4);
+            images_changed = true;
+        }
+    for (int j = 0; j < n; j++)
+        if (ot->tex[j]) {
+            f->otex[j].swap(fresh[j]);
+            f->otex_w[j] = ot->tex_w[j];
+            f->otex_h[j] = ot->tex_h[j];
+        }
+    f->ot = *ot;
+    for (int j = 0; j < BHG_MAX_SPHERES; j++) f->ot.tex[j] = nullptr;   // (no pointer of the caller's is kept)
+    f->textured = true;
+    // rotations, modes and strengths travel as kernel arguments: only new images are uploaded
+    if (images_changed)
+        for (auto &s : f->sh) s.otex_ready = false;
+    return BHG_OK;
+} catch (...) {
+    return host_exception();
+}
+
 int bhg_frame_render(bhg_frame *f, const bhg_params *p, float *rgba_host)
 try {
     if (!f || !p) return fail(BHG_E_INVALID, "frame / params is NULL");
@@ -662,12 +748,20 @@ try {
         }
     }
     const bhg_observer *obs = f->observer ? &f->obs : nullptr;
+    const bool textured = f->textured && has_obj;
+    if (textured) {   // (the table against the scene as it is now, before anything is enqueued)
+        bhg_object_textures ot;
+        fill_object_textures(f, nullptr, &ot);
+        bhg::ObjectTextureParams tp;
+        BHG_TRY(bhg::object_texture_params(&ot, f->scene.n_spheres, &tp));
+    }
 
     // -- every device: (rays, scene images once) trace, shade + sample mean into its slab ---------------------------
     for (size_t r = 0; r < world; r++) {
         Shard &s = f->sh[r];
         if (!s.rays_ready) BHG_TRY(upload_shard_geometry(f, s, f->observer ? &op : nullptr));
         if (!s.scene_ready) BHG_TRY(upload_shard_scene(f, s));
+        if (textured && !s.otex_ready) BHG_TRY(upload_shard_textures(f, s));
     }
     for (size_t r = 0; r < world; r++) {
         Shard &s = f->sh[r];
@@ -711,7 +805,13 @@ try {
             if (f->profiling) HIP_TRY(hipEventRecord(s.evs[s.ev_used++].second, s.stream));
             bhg_scene sc;
             fill_scene(f, s, &sc);
-            if (redshift)
+            if (textured) {
+                bhg_object_textures ot;
+                fill_object_textures(f, &s, &ot);
+                BHG_TRY(bhg_shade_scene_textured_device(s.ctx, s.end.as<double>(), nullptr, s.flags.as<uint8_t>(), s.obj.as<int8_t>(), s.P,
+                                                        S, &sc, &prm, redshift ? &f->rs : nullptr, obs, &ot, f->cam.origin,
+                                                        s.k0.as<double>(), nullptr, dst, scatter, s.stream));
+            } else if (redshift)
                 BHG_TRY(bhg_shade_scene_redshift_observer_device(s.ctx, s.end.as<double>(), nullptr, s.flags.as<uint8_t>(),
                                                                  has_obj ? s.obj.as<int8_t>() : nullptr, s.P, S, &sc, &prm, &f->rs,
                                                                  obs, f->cam.origin, s.k0.as<double>(), nullptr, dst, scatter,

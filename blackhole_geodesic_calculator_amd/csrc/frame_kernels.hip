@@ -252,6 +252,42 @@ __device__ __forceinline__ void object_colour(const ShadeArgs &A, const double *
     rgb[2] = A.sphere_rgb[j][2] * sum;
 }
 
+// The textured object colour: the texel is read at the angles of the body-frame normal n_b = R_j^T n in
+// the sky's convention -- U = atan2(n_b,y, n_b,x) / pi (body +x the image's centre column), V = 1 - 2 atan2(sqrt(n_b,x^2 +
+// n_b,y^2), n_b,z) / pi (body +z the top row), both scale-free atan2's as for the sky; a slot without a texture has a white
+// texel.  Lit: object_colour (sphere_rgb[j] times the lamp sum) times the texel; emissive: emission[j] * sphere_rgb[j] * texel,
+// no lamps, no shadows.  A white texel is an exact x 1.0: an untextured lit slot is object_colour bit for bit.  j is per lane:
+// the slot's members are read with a per-lane index, as spheres[j] is.
+__device__ __forceinline__ void object_colour_tex(const ShadeArgs &A, const double *e, int j, double rgb[3])
+{
+    rgb[0] = rgb[1] = rgb[2] = 0.0;
+    if (j < 0 || j >= A.n_spheres) return;
+    double texel[3] = {1.0, 1.0, 1.0};
+    const float *tex = A.ot.tex[j];
+    if (tex) {
+        const double *sp = A.spheres[j], *R = A.ot.rot[j];
+        const double inv_rho = 1.0 / sp[3];
+        const double n[3] = {(e[0] - sp[0]) * inv_rho, (e[1] - sp[1]) * inv_rho, (e[2] - sp[2]) * inv_rho};
+        const double b0 = R[0] * n[0] + R[3] * n[1] + R[6] * n[2];
+        const double b1 = R[1] * n[0] + R[4] * n[1] + R[7] * n[2];
+        const double b2 = R[2] * n[0] + R[5] * n[1] + R[8] * n[2];
+        const double U = atan2_fast(b1, b0) * 0.3183098861837907;
+        const double V = 1.0 - 2.0 * (atan2_fast(sqrt(b0 * b0 + b1 * b1), b2) * 0.3183098861837907);
+        sky_lookup(tex, A.ot.tex_w[j], A.ot.tex_h[j], U, V, texel);
+    }
+    if (A.ot.mode[j] == BHG_OBJECT_EMISSIVE_) {
+        const double k = A.ot.emission[j];
+        rgb[0] = k * (A.sphere_rgb[j][0] * texel[0]);
+        rgb[1] = k * (A.sphere_rgb[j][1] * texel[1]);
+        rgb[2] = k * (A.sphere_rgb[j][2] * texel[2]);
+        return;
+    }
+    object_colour(A, e, j, rgb);
+    rgb[0] *= texel[0];
+    rgb[1] *= texel[1];
+    rgb[2] *= texel[2];
+}
+
 // ---- redshift ---------------------------------------------------------------------------------
 // g = nu_obs / nu_em = (k.u_obs) / (k.u_em) of one ray, fp64.  The observer is the ZAMO at the camera (in Schwarzschild the
 // static observer); the Killing constants E = -k_t, L = k_phi come from the CAMERA state (x_c, k0), where the trace starts
@@ -398,8 +434,8 @@ __device__ __forceinline__ void redshift_weigh(const ShadeArgs &A, uint64_t i, i
 // The colour of ONE ray (sample s of pixel p): black for a horizon ray (:242-244), the disk's / an object's colour, or the
 // sky in its exit direction.
 // RS: the redshift instance (rgb *= g^n by class); without it the kernels are the frame path's as they were.  OBS (with RS
-// only): g is the moving observer's.
-template <bool RS, bool OBS>
+// only): g is the moving observer's.  TEX: object rays take the textured colour (object_colour_tex); nothing else differs.
+template <bool RS, bool OBS, bool TEX>
 __device__ __forceinline__ void ray_colour(const ShadeArgs &A, uint64_t i, uint8_t fl, double c0, double c1, double c2, double rgb[3])
 {
     rgb[0] = rgb[1] = rgb[2] = 0.0;
@@ -411,7 +447,10 @@ __device__ __forceinline__ void ray_colour(const ShadeArgs &A, uint64_t i, uint8
         return;
     }
     if (fl == BHG_FLAG_HIT_OBJECT_ && A.object_id && A.end) {
-        object_colour(A, e, (int)A.object_id[i], rgb);
+        if (TEX)
+            object_colour_tex(A, e, (int)A.object_id[i], rgb);
+        else
+            object_colour(A, e, (int)A.object_id[i], rgb);
         if (RS) redshift_weigh<OBS>(A, i, RS_OBJECT, BHG_REDSHIFT_OBJECTS_, e, rgb);
         return;
     }
@@ -449,7 +488,7 @@ __device__ __forceinline__ void write_pixel(const ShadeArgs &A, uint64_t p, cons
 // consecutive rays of the [S][P] layout (coalesced).  Against one thread per pixel walking its samples one after the
 // other (round 3; kept below for S > 256) this puts S times as many independent atan2 / texel-gather chains in flight:
 // the kernel is a latency chain per ray, not a bandwidth problem (131 MB in, 16 MB out per config-2 frame).
-template <bool RS, bool OBS>
+template <bool RS, bool OBS, bool TEX>
 __global__ void __launch_bounds__(256) shade_reduce_kernel(const ShadeArgs A, const uint32_t ppb)
 {
     __shared__ double col[256 * 3];
@@ -462,7 +501,7 @@ __global__ void __launch_bounds__(256) shade_reduce_kernel(const ShadeArgs A, co
         // exit directions: the second half of the end records, or (direction-only traces of sky frames) an array of their own
         const double *d = A.dir ? A.dir + i * 3 : A.end + i * 6 + 3;
         double rgb[3];
-        ray_colour<RS, OBS>(A, i, A.flags[i], d[0], d[1], d[2], rgb);
+        ray_colour<RS, OBS, TEX>(A, i, A.flags[i], d[0], d[1], d[2], rgb);
         col[t * 3 + 0] = rgb[0];
         col[t * 3 + 1] = rgb[1];
         col[t * 3 + 2] = rgb[2];
@@ -482,7 +521,7 @@ __global__ void __launch_bounds__(256) shade_reduce_kernel(const ShadeArgs A, co
 }
 
 // More samples than a workgroup has threads: one thread per pixel, samples accumulated in registers in sample order.
-template <bool RS, bool OBS>
+template <bool RS, bool OBS, bool TEX>
 __global__ void __launch_bounds__(256) shade_reduce_serial_kernel(const ShadeArgs A)
 {
     const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -492,7 +531,7 @@ __global__ void __launch_bounds__(256) shade_reduce_serial_kernel(const ShadeArg
         const uint64_t i = (uint64_t)s * A.n_pixels + p;
         const double *d = A.dir ? A.dir + i * 3 : A.end + i * 6 + 3;
         double rgb[3];
-        ray_colour<RS, OBS>(A, i, A.flags[i], d[0], d[1], d[2], rgb);
+        ray_colour<RS, OBS, TEX>(A, i, A.flags[i], d[0], d[1], d[2], rgb);
         acc[0] += rgb[0];
         acc[1] += rgb[1];
         acc[2] += rgb[2];
@@ -556,28 +595,39 @@ hipError_t launch_redshift(const RedshiftArgs &a, hipStream_t s)
     return hipGetLastError();
 }
 
-hipError_t launch_shade(const ShadeArgs &a, hipStream_t s)
+// one instance per (redshift, observer, textures): the template flags are the launch's run-time switches
+template <bool RS, bool OBS, bool TEX>
+void launch_shade_instance(const ShadeArgs &a, hipStream_t s)
 {
-    if (a.n_pixels == 0) return hipSuccess;
-    const bool rs = a.rs.apply != 0, obs = rs && a.obs.on;
     if (a.samples > 256) {
         const dim3 grid((unsigned)((a.n_pixels + 255) / 256));
-        if (obs)
-            BHG_LAUNCH((shade_reduce_serial_kernel<true, true>), grid, dim3(256), 0, s, a);
-        else if (rs)
-            BHG_LAUNCH((shade_reduce_serial_kernel<true, false>), grid, dim3(256), 0, s, a);
-        else
-            BHG_LAUNCH((shade_reduce_serial_kernel<false, false>), grid, dim3(256), 0, s, a);
-        return hipGetLastError();
+        BHG_LAUNCH((shade_reduce_serial_kernel<RS, OBS, TEX>), grid, dim3(256), 0, s, a);
+        return;
     }
     const uint32_t ppb = 256u / (uint32_t)a.samples;      // pixels per workgroup
     const dim3 grid((unsigned)((a.n_pixels + ppb - 1) / ppb));
+    BHG_LAUNCH((shade_reduce_kernel<RS, OBS, TEX>), grid, dim3(256), 0, s, a, ppb);
+}
+
+template <bool TEX>
+void launch_shade_tex(const ShadeArgs &a, hipStream_t s)
+{
+    const bool rs = a.rs.apply != 0, obs = rs && a.obs.on;
     if (obs)
-        BHG_LAUNCH((shade_reduce_kernel<true, true>), grid, dim3(256), 0, s, a, ppb);
+        launch_shade_instance<true, true, TEX>(a, s);
     else if (rs)
-        BHG_LAUNCH((shade_reduce_kernel<true, false>), grid, dim3(256), 0, s, a, ppb);
+        launch_shade_instance<true, false, TEX>(a, s);
     else
-        BHG_LAUNCH((shade_reduce_kernel<false, false>), grid, dim3(256), 0, s, a, ppb);
+        launch_shade_instance<false, false, TEX>(a, s);
+}
+
+hipError_t launch_shade(const ShadeArgs &a, hipStream_t s)
+{
+    if (a.n_pixels == 0) return hipSuccess;
+    if (a.ot.on)
+        launch_shade_tex<true>(a, s);
+    else
+        launch_shade_tex<false>(a, s);
     return hipGetLastError();
 }
 

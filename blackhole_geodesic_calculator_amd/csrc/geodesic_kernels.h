@@ -27,6 +27,8 @@ constexpr uint32_t BHG_FLAG_NAN_ = 64u;
 constexpr uint32_t BHG_FLAG_HIT_DISK_ = 128u;
 constexpr uint32_t BHG_FLAG_HIT_OBJECT_ = 0x88u;
 constexpr int BHG_MAX_SPHERES_ = 8;
+constexpr int32_t BHG_OBJECT_LIT_ = 0;
+constexpr int32_t BHG_OBJECT_EMISSIVE_ = 1;
 constexpr uint32_t BHG_REDSHIFT_DISK_ = 1u;
 constexpr uint32_t BHG_REDSHIFT_OBJECTS_ = 2u;
 constexpr uint32_t BHG_REDSHIFT_SKY_ = 4u;
@@ -89,6 +91,17 @@ struct ObserverParams {
     double r_s, spin;  // metric (raygen only)
     int32_t rhs;       // BHG_RHS_* (raygen only)
     int32_t on;        // 0: no observer -- the kernels' reference instances are launched and never read this struct
+};
+
+// textured, oriented and emissive object spheres (frame_kernels.hip): one slot per sphere.  on = 0: the
+// shade kernels' untextured instances are launched and never read this struct
+struct ObjectTextureParams {
+    const float *tex[BHG_MAX_SPHERES_];   // [h][w][4] RGBA float32 equirectangular, or nullptr (a white texel)
+    int32_t tex_w[BHG_MAX_SPHERES_], tex_h[BHG_MAX_SPHERES_];
+    int32_t mode[BHG_MAX_SPHERES_];       // BHG_OBJECT_LIT_ / BHG_OBJECT_EMISSIVE_
+    double emission[BHG_MAX_SPHERES_];    // emissive strength
+    double rot[BHG_MAX_SPHERES_][9];      // row-major body -> world (the C layer has put the identity for an all-zero matrix)
+    int32_t on;
 };
 
 // camera-ray generation (frame_kernels.hip)
@@ -154,6 +167,9 @@ struct ShadeArgs {
     const double *k0;      // [S*n_pixels][3] camera directions, or nullptr when rs.apply == 0
     RedshiftParams rs;
     ObserverParams obs;    // beta and on only: the redshift instance's g is the moving observer's (rs.apply != 0 only)
+    // object textures (bhg_shade_scene_textured_device): launch_shade takes the textured instance when ot.on != 0; last, so
+    // that no other member moves
+    ObjectTextureParams ot;
 };
 
 hipError_t launch_raygen(const RaygenArgs &a, hipStream_t s);

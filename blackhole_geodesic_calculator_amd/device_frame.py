@@ -84,6 +84,7 @@ class DeviceFrame:
         self._params = None      # the parameters of the last trace (the redshift shade needs its metric)
         self.observer = None     # _ffi.Observer (set_observer) or None: the reference camera
         self._ray_key = None     # what the observer rays in d_k0 were made for: (origin, r_s, spin, rhs_form)
+        self.object_textures = None   # set_object_textures: (device textures per sphere, rotations, modes, emission) or None
 
     def _stream(self):
         return torch.cuda.current_stream(self.dev).cuda_stream
@@ -136,6 +137,37 @@ class DeviceFrame:
         self.observer = _ffi.make_observer(velocity)
         self._rays_ready = False
         self._ray_key = None
+
+    def set_object_textures(self, textures=None, rotations=None, modes=None, emission=None):
+        """Textured, oriented and emissive object spheres (bhg_shade_scene_textured_device), per sphere of
+        set_objects(): textures [h, w, 4] float32 (kept on the device; None: keep that sphere's current texture, white if it
+        never had one), 3x3 body -> world rotations (None: the identity), modes ("lit" / "emissive"), emission strengths.
+        shade() and shade_f32() then take the textured call whenever the frame has spheres.  All None: textures off."""
+        if textures is None and rotations is None and modes is None and emission is None:
+            self.object_textures = None
+            return
+        dev = [None] * _ffi.MAX_SPHERES if self.object_textures is None else list(self.object_textures[0])
+        for j, t in enumerate(textures or []):
+            if t is not None:
+                a = np.ascontiguousarray(t, dtype=np.float32)
+                assert a.ndim == 3 and a.shape[2] == 4
+                dev[j] = torch.as_tensor(a).to(self.dev)
+        self.object_textures = (dev, rotations, modes, emission)
+
+    def _object_textures(self):
+        dev, rotations, modes, emission = self.object_textures
+        tex = [None if t is None else (t.data_ptr(), t.shape[1], t.shape[0]) for t in dev]
+        return _ffi.make_object_textures(tex, rotations, modes, emission)[0]
+
+    def _textured(self):
+        return self.object_textures is not None and self.spheres is not None and len(self.spheres) > 0
+
+    def _shade_textured(self, d_rgba=0, d_rgba_f32=0, scatter=None):
+        self.ctx.shade_scene_textured_device(self.d_end.data_ptr(), self.d_flags.data_ptr(), self.P, self.S, self.scene(), self._params,
+                                             self.redshift, self.observer, self._object_textures(), x0_shared=self.origin,
+                                             d_k0=self.d_k0.data_ptr(), d_rgba=d_rgba, d_rgba_f32=d_rgba_f32,
+                                             d_object_id=self.d_obj.data_ptr(), d_scatter=0 if scatter is None else scatter.data_ptr(),
+                                             stream=self._stream())
 
     def _observer_key(self, params):
         return (tuple(float(v) for v in self.origin), float(params.r_s), float(params.spin), int(params.rhs_form))
@@ -222,6 +254,9 @@ class DeviceFrame:
 
     def shade(self):
         form = self._shade_form()
+        if self._textured():
+            self._shade_textured(d_rgba=self.d_rgba.data_ptr())
+            return self.d_rgba
         if self.redshift is not None:
             self._shade_redshift(form, d_rgba=self.d_rgba.data_ptr())
             return self.d_rgba
@@ -244,6 +279,9 @@ class DeviceFrame:
         flat pixel ids): what layer.rect takes, without the fp64 intermediate."""
         form = self._shade_form()
         assert out.dtype == torch.float32 and out.is_contiguous()
+        if self._textured():
+            self._shade_textured(d_rgba_f32=out.data_ptr(), scatter=scatter)
+            return out
         if self.redshift is not None:
             self._shade_redshift(form, d_rgba_f32=out.data_ptr(), scatter=scatter)
             return out

@@ -54,6 +54,9 @@ extern "C" {
 #define BHG_ABI_VERSION 10  /* 10: the observer camera -- bhg_raygen_observer_device, bhg_redshift_observer_device / _host,
                                   bhg_shade_scene_redshift_observer_device, bhg_frame_set_observer, bhg_observer_size,
                                   struct bhg_observer; nothing of ABI 9 changed.
+                                  Later additions within ABI 10, found by symbol and announced by a feature macro:
+                                  BHG_OBJECT_TEXTURES (bhg_shade_scene_textured_device, bhg_frame_set_object_textures,
+                                  bhg_object_textures_size, struct bhg_object_textures).
                                9: redshift -- bhg_redshift_device / _host, bhg_shade_scene_redshift_device, bhg_frame_set_redshift,
                                   bhg_redshift_size, struct bhg_redshift;
                                   nothing of ABI 8 changed.
@@ -536,6 +539,45 @@ int bhg_shade_scene_redshift_observer_device(bhg_context *ctx, const double *d_e
  * obs = NULL: the reference camera again, bit for bit.  The rays are regenerated at the next render, and again whenever
  * the origin or the trace parameters' metric changes.  Checked against the camera and the trace parameters at render. */
 int bhg_frame_set_observer(bhg_frame *frame, const bhg_observer *obs);
+
+/* --- textured, oriented and emissive object spheres (within ABI 10) ----------------------------
+ * Each object sphere j gets an optional equirectangular RGBA float32 texture (rows bottom-up, as the sky), an orientation R_j
+ * (row-major, body -> world; the all-zero matrix means the identity, so a zero-initialised struct is valid) and a shading mode.
+ * For a ray that ends on sphere j at the entry point e: n = (e - c_j) / rho_j, n_b = R_j^T n, and the texel is read with the
+ * sky's bilinear filter (u wraps, v clamps) at U = atan2(n_b,y, n_b,x) / pi, V = 1 - 2 atan2(sqrt(n_b,x^2 + n_b,y^2), n_b,z) / pi:
+ * body +x is the image's centre column, body +z its top row.  A slot without a texture has a white texel.
+ *   BHG_OBJECT_LIT:      colour = sphere_rgb[j] * (the Lambert lamp sum with shadow rays) * texel
+ *   BHG_OBJECT_EMISSIVE: colour = emission[j] * sphere_rgb[j] * texel (no lamps, no shadows)
+ * Redshift weighs the colour as any object ray's (the emitter is at rest).  Refused (BHG_E_INVALID, the message names the
+ * sphere index), for slots below n_spheres only: a mode other than 0 / 1, a non-finite or negative emission, a texture with
+ * w or h < 1, a rotation that is neither all-zero nor orthonormal with det +1 (|R^T R - I| <= 1e-9).
+ * Member order: tex, tex_w, tex_h, mode, emission, rot (800 bytes). */
+#define BHG_OBJECT_TEXTURES 1
+#define BHG_OBJECT_LIT 0
+#define BHG_OBJECT_EMISSIVE 1
+typedef struct bhg_object_textures {
+    const float *tex[BHG_MAX_SPHERES];      /* [tex_h][tex_w][4] RGBA float32, or NULL (white) */
+    int32_t tex_w[BHG_MAX_SPHERES], tex_h[BHG_MAX_SPHERES];
+    int32_t mode[BHG_MAX_SPHERES];          /* BHG_OBJECT_LIT / BHG_OBJECT_EMISSIVE */
+    double emission[BHG_MAX_SPHERES];       /* emissive strength, finite and >= 0 */
+    double rot[BHG_MAX_SPHERES][9];         /* row-major body -> world rotation, or all zero (the identity) */
+} bhg_object_textures;
+size_t bhg_object_textures_size(void);
+/* bhg_shade_scene_redshift_observer_device with textured object spheres; tex[] holds DEVICE addresses.  ot = NULL is exactly
+ * that call, bit for bit; any other ot takes the textured kernel instances, and a zero-initialised ot gives that call's image
+ * bit for bit (a white texel is an exact x 1.0).  ot is checked before the context. */
+int bhg_shade_scene_textured_device(bhg_context *ctx, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
+                                    const int8_t *d_object_id, size_t n_pixels, int32_t samples, const bhg_scene *scene,
+                                    const bhg_params *p, const bhg_redshift *rs, const bhg_observer *obs,
+                                    const bhg_object_textures *ot, const double *x0_shared, const double *d_k0, double *d_rgba,
+                                    float *d_rgba_f32, const int64_t *d_scatter, void *stream);
+/* Textured object spheres in every later bhg_frame_render (every device, every gather mode) whose scene has spheres.  tex[]
+ * holds HOST arrays: they are copied here and uploaded to every device at the next render.  A NULL tex[j] keeps that slot's
+ * current texture (white if it never had one), as disk_tex does in bhg_frame_set_scene; a call that changes only rotations,
+ * modes or strengths uploads nothing.  ot = NULL turns textures off (the frame's shading without them, bit for bit) and frees
+ * them.  Slots are checked against the scene's n_spheres here and again at render; slots at or above it are ignored.  A
+ * refused host copy is BHG_E_NOMEM and leaves the frame as it was. */
+int bhg_frame_set_object_textures(bhg_frame *frame, const bhg_object_textures *ot);
 
 /* Acceleration probe: acc[n][3] = -Gamma^i_{mu nu} k^mu k^nu at (x[n][3], k[n][3]); host buffers.
  * Lets tests compare the device RHS with the oracle's term by term.  With rhs_form = BHG_RHS_KERR_BL the triples
