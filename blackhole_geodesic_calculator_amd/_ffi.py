@@ -7,6 +7,7 @@ touches the GPU; `load()` raises loudly when the shared library has not been bui
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 import sys
 
@@ -982,90 +983,81 @@ class Context:
                                                  C.byref(scene), C.c_void_p(d_rgba_f32), C.c_void_p(d_scatter or None),
                                                  C.c_void_p(stream or None)))
 
+    @staticmethod
+    def _redshift_host(call, k0, x0, flags, end):
+        """Marshalling of bhg_redshift_host / bhg_redshift_observer_host: call takes their arguments from x0 on."""
+        k0 = np.ascontiguousarray(k0, dtype=np.float64).reshape(-1, 3)
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        n = k0.shape[0]
+        if flags.shape != (n,) or (x0.shape != (3,) and x0.shape != (n, 3)):
+            raise ValueError("flags must be [N], x0 [3] or [N, 3]")
+        e = None if end is None else np.ascontiguousarray(end, dtype=np.float64)
+        if e is not None and e.shape != (n, 6):
+            raise ValueError("end must be [N, 6]")
+        g = np.empty(n, np.float64)
+        _check(call(_addr(x0), 1 if x0.ndim == 1 else 0, _addr(k0), None if e is None else _addr(e), _addr(flags), n, _addr(g)))
+        return g
+
     def redshift(self, k0, x0, params: Params, rs: Redshift, flags, end=None):
         """bhg_redshift_host: g [N] of traced rays from their camera state (k0 [N, 3], x0 [3] or [N, 3]), end [N, 6] (or None) and
         flags [N]."""
-        k0 = np.ascontiguousarray(k0, dtype=np.float64).reshape(-1, 3)
-        x0 = np.ascontiguousarray(x0, dtype=np.float64)
-        flags = np.ascontiguousarray(flags, dtype=np.uint8)
-        n = k0.shape[0]
-        if flags.shape != (n,) or (x0.shape != (3,) and x0.shape != (n, 3)):
-            raise ValueError("flags must be [N], x0 [3] or [N, 3]")
-        e = None if end is None else np.ascontiguousarray(end, dtype=np.float64)
-        if e is not None and e.shape != (n, 6):
-            raise ValueError("end must be [N, 6]")
-        g = np.empty(n, np.float64)
-        _check(load().bhg_redshift_host(self._h, C.byref(params), C.byref(rs), _addr(x0), 1 if x0.ndim == 1 else 0, _addr(k0),
-                                        None if e is None else _addr(e), _addr(flags), n, _addr(g)))
-        return g
+        return self._redshift_host(functools.partial(load().bhg_redshift_host, self._h, C.byref(params), C.byref(rs)), k0, x0, flags,
+                                   end)
 
     def redshift_observer(self, k0, x0, params: Params, rs: Redshift, obs, flags, end=None):
         """bhg_redshift_observer_host: redshift() with g of the moving observer obs (Observer, or None = the ZAMO)."""
-        k0 = np.ascontiguousarray(k0, dtype=np.float64).reshape(-1, 3)
-        x0 = np.ascontiguousarray(x0, dtype=np.float64)
-        flags = np.ascontiguousarray(flags, dtype=np.uint8)
-        n = k0.shape[0]
-        if flags.shape != (n,) or (x0.shape != (3,) and x0.shape != (n, 3)):
-            raise ValueError("flags must be [N], x0 [3] or [N, 3]")
-        e = None if end is None else np.ascontiguousarray(end, dtype=np.float64)
-        if e is not None and e.shape != (n, 6):
-            raise ValueError("end must be [N, 6]")
-        g = np.empty(n, np.float64)
-        _check(load().bhg_redshift_observer_host(self._h, C.byref(params), C.byref(rs), _obs_ref(obs), _addr(x0),
-                                                 1 if x0.ndim == 1 else 0, _addr(k0), None if e is None else _addr(e), _addr(flags),
-                                                 n, _addr(g)))
-        return g
+        return self._redshift_host(functools.partial(load().bhg_redshift_observer_host, self._h, C.byref(params), C.byref(rs),
+                                                     _obs_ref(obs)), k0, x0, flags, end)
+
+    @staticmethod
+    def _redshift_device(call, n, d_k0, d_flags, d_g, x0_shared, d_x0, d_end, stream):
+        """Marshalling of bhg_redshift_device / bhg_redshift_observer_device: call takes their arguments from x0_shared on."""
+        xs = None if x0_shared is None else (C.c_double * 3)(*[float(v) for v in x0_shared])
+        _check(call(xs, C.c_void_p(d_x0 or None), C.c_void_p(d_k0), C.c_void_p(d_end or None), C.c_void_p(d_flags), int(n),
+                    C.c_void_p(d_g), C.c_void_p(stream or None)))
 
     def redshift_observer_device(self, params: Params, rs: Redshift, obs, n, d_k0, d_flags, d_g, x0_shared=None, d_x0=0, d_end=0,
                                  stream=0):
-        xs = None
-        if x0_shared is not None:
-            xs = (C.c_double * 3)(*[float(v) for v in x0_shared])
-        _check(load().bhg_redshift_observer_device(self._h, C.byref(params), C.byref(rs), _obs_ref(obs), xs,
-                                                   C.c_void_p(d_x0 or None), C.c_void_p(d_k0), C.c_void_p(d_end or None),
-                                                   C.c_void_p(d_flags), int(n), C.c_void_p(d_g), C.c_void_p(stream or None)))
+        self._redshift_device(functools.partial(load().bhg_redshift_observer_device, self._h, C.byref(params), C.byref(rs),
+                                                _obs_ref(obs)), n, d_k0, d_flags, d_g, x0_shared, d_x0, d_end, stream)
 
     def redshift_device(self, params: Params, rs: Redshift, n, d_k0, d_flags, d_g, x0_shared=None, d_x0=0, d_end=0, stream=0):
-        xs = None
-        if x0_shared is not None:
-            xs = (C.c_double * 3)(*[float(v) for v in x0_shared])
-        _check(load().bhg_redshift_device(self._h, C.byref(params), C.byref(rs), xs, C.c_void_p(d_x0 or None), C.c_void_p(d_k0),
-                                          C.c_void_p(d_end or None), C.c_void_p(d_flags), int(n), C.c_void_p(d_g),
-                                          C.c_void_p(stream or None)))
+        self._redshift_device(functools.partial(load().bhg_redshift_device, self._h, C.byref(params), C.byref(rs)), n, d_k0, d_flags,
+                              d_g, x0_shared, d_x0, d_end, stream)
+
+    def _shade_scene(self, fn, extra, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, scene, params, rs, x0_shared, d_k0,
+                     d_rgba, d_rgba_f32, d_scatter, stream):
+        """Marshalling of the redshift, observer and textured shade calls: fn's arguments are bhg_shade_scene_redshift_device's
+        with `extra` (obs, then ot) after rs."""
+        xs = None if x0_shared is None else (C.c_double * 3)(*[float(v) for v in x0_shared])
+        _check(fn(self._h, C.c_void_p(d_end or None), C.c_void_p(d_end_dir or None), C.c_void_p(d_flags), C.c_void_p(d_object_id or None),
+                  int(n_pixels), int(samples), C.byref(scene), None if params is None else C.byref(params),
+                  None if rs is None else C.byref(rs), *extra, xs, C.c_void_p(d_k0 or None), C.c_void_p(d_rgba or None),
+                  C.c_void_p(d_rgba_f32 or None), C.c_void_p(d_scatter or None), C.c_void_p(stream or None)))
 
     def shade_scene_redshift_device(self, d_end, d_flags, n_pixels, samples, scene: "Scene", params: Params, rs, x0_shared, d_k0,
                                     d_rgba=0, d_rgba_f32=0, d_object_id=0, d_scatter=0, d_end_dir=0, stream=0):
         """bhg_shade_scene_redshift_device: the scene shade with each ray's colour weighted by g^exponent (rs: Redshift or None =
         off).  d_end = 0 with d_end_dir: a direction-only sky frame."""
-        xs = (C.c_double * 3)(*[float(v) for v in x0_shared])
-        _check(load().bhg_shade_scene_redshift_device(self._h, C.c_void_p(d_end or None), C.c_void_p(d_end_dir or None),
-                                                      C.c_void_p(d_flags), C.c_void_p(d_object_id or None), int(n_pixels),
-                                                      int(samples), C.byref(scene), C.byref(params),
-                                                      None if rs is None else C.byref(rs), xs, C.c_void_p(d_k0),
-                                                      C.c_void_p(d_rgba or None), C.c_void_p(d_rgba_f32 or None),
-                                                      C.c_void_p(d_scatter or None), C.c_void_p(stream or None)))
+        self._shade_scene(load().bhg_shade_scene_redshift_device, (), d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, scene,
+                          params, rs, x0_shared, d_k0, d_rgba, d_rgba_f32, d_scatter, stream)
 
     def shade_scene_redshift_observer_device(self, d_end, d_flags, n_pixels, samples, scene: "Scene", params: Params, rs, obs,
                                              x0_shared, d_k0, d_rgba=0, d_rgba_f32=0, d_object_id=0, d_scatter=0, d_end_dir=0,
                                              stream=0):
         """bhg_shade_scene_redshift_observer_device: shade_scene_redshift_device with g of the observer obs (None: the ZAMO)."""
-        xs = (C.c_double * 3)(*[float(v) for v in x0_shared])
-        _check(load().bhg_shade_scene_redshift_observer_device(
-            self._h, C.c_void_p(d_end or None), C.c_void_p(d_end_dir or None), C.c_void_p(d_flags), C.c_void_p(d_object_id or None),
-            int(n_pixels), int(samples), C.byref(scene), C.byref(params), None if rs is None else C.byref(rs), _obs_ref(obs), xs,
-            C.c_void_p(d_k0), C.c_void_p(d_rgba or None), C.c_void_p(d_rgba_f32 or None), C.c_void_p(d_scatter or None),
-            C.c_void_p(stream or None)))
+        self._shade_scene(load().bhg_shade_scene_redshift_observer_device, (_obs_ref(obs),), d_end, d_end_dir, d_flags, d_object_id,
+                          n_pixels, samples, scene, params, rs, x0_shared, d_k0, d_rgba, d_rgba_f32, d_scatter, stream)
 
     def shade_scene_textured_device(self, d_end, d_flags, n_pixels, samples, scene: "Scene", params, rs, obs, ot, x0_shared=None,
                                     d_k0=0, d_rgba=0, d_rgba_f32=0, d_object_id=0, d_scatter=0, d_end_dir=0, stream=0):
-        """bhg_shade_scene_textured_device: shade_scene_redshift_observer_device with object textures ot (ObjectTextures whose
-        tex are device addresses, or None = without textures).  rs / obs / params may be None when redshift is off."""
-        xs = None if x0_shared is None else (C.c_double * 3)(*[float(v) for v in x0_shared])
-        _check(load().bhg_shade_scene_textured_device(
-            self._h, C.c_void_p(d_end or None), C.c_void_p(d_end_dir or None), C.c_void_p(d_flags), C.c_void_p(d_object_id or None),
-            int(n_pixels), int(samples), C.byref(scene), None if params is None else C.byref(params),
-            None if rs is None else C.byref(rs), _obs_ref(obs), None if ot is None else C.byref(ot), xs, C.c_void_p(d_k0 or None),
-            C.c_void_p(d_rgba or None), C.c_void_p(d_rgba_f32 or None), C.c_void_p(d_scatter or None), C.c_void_p(stream or None)))
+        """bhg_shade_scene_textured_device, the general shade call: shade_scene_redshift_observer_device with object textures ot
+        (ObjectTextures whose tex are device addresses, or None = without textures).  rs / obs / params may be None when redshift
+        is off."""
+        self._shade_scene(load().bhg_shade_scene_textured_device, (_obs_ref(obs), None if ot is None else C.byref(ot)), d_end,
+                          d_end_dir, d_flags, d_object_id, n_pixels, samples, scene, params, rs, x0_shared, d_k0, d_rgba, d_rgba_f32,
+                          d_scatter, stream)
 
     def assemble_frame_f32_device(self, d_slabs, d_index, n_pixels, d_frame, stream=0):
         _check(load().bhg_assemble_frame_f32_device(self._h, C.c_void_p(d_slabs), C.c_void_p(d_index), int(n_pixels),

@@ -1347,6 +1347,110 @@ int raygen_impl(bhg_context *c, int32_t width, int32_t height, int32_t samples, 
     HIP_TRY(bhg::launch_raygen(a, (hipStream_t)stream));
     return BHG_OK;
 }
+
+// The one shade call: every bhg_shade*_device is this with some arguments NULL (include/bhgeo.h).  Its checks run in one
+// order, whichever entry point was taken, so that settings are refused with or without a device:
+//   1. the scene: present; samples, sky_w, sky_h > 0; n_spheres in [0, BHG_MAX_SPHERES], n_lamps in [0, 4]; a disk with
+//      r_out > r_in, stddev > 0 and a texture size > 0; sphere radii > 0
+//   2. the object-texture table, when given, against n_spheres
+//   3. redshift, when rs->apply != 0: x0_shared, the settings, and the observer when given
+//   4. the context
+//   5. n_pixels == 0 is BHG_OK: an EMPTY shard -- a rank without pixels: fewer tiles than ranks -- has no rays and no
+//      arrays, so no device array is looked at
+//   6. the device arrays: an output, end or end_dir, flags, the sky; end for a disk or spheres; object_id for spheres;
+//      k0 for redshift
+int shade(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags, const int8_t *d_object_id,
+          size_t n_pixels, int32_t samples, const bhg_scene *sc, const bhg_params *p, const bhg_redshift *rs,
+          const bhg_observer *obs, const bhg_object_textures *ot, const double *x0_shared, const double *d_k0, double *d_rgba,
+          float *d_rgba_f32, const int64_t *d_scatter, void *stream)
+{
+    if (!sc) return fail(BHG_E_INVALID, "scene is NULL");
+    if (samples <= 0 || sc->sky_w <= 0 || sc->sky_h <= 0) return fail(BHG_E_INVALID, "samples, sky_w, sky_h must be > 0");
+    if (sc->n_spheres < 0 || sc->n_spheres > BHG_MAX_SPHERES || sc->n_lamps < 0 || sc->n_lamps > 4)
+        return fail(BHG_E_INVALID, "n_spheres must be in [0, BHG_MAX_SPHERES], n_lamps in [0, 4]");
+    const bool has_disk = sc->disk_r_out > 0.0;
+    if (has_disk) {
+        if (!(sc->disk_r_out > sc->disk_r_in) || !(sc->disk_stddev > 0.0))
+            return fail(BHG_E_INVALID, "disk needs r_out > r_in and stddev > 0");
+        if (sc->d_disk_tex && (sc->disk_w <= 0 || sc->disk_h <= 0)) return fail(BHG_E_INVALID, "disk texture size must be > 0");
+    }
+    for (int j = 0; j < sc->n_spheres; j++)
+        if (!(sc->spheres[j][3] > 0.0)) return fail(BHG_E_INVALID, "sphere radii must be > 0");
+    bhg::ObjectTextureParams tp;
+    if (ot) {
+        int rc = bhg::object_texture_params(ot, sc->n_spheres, &tp);
+        if (rc != BHG_OK) return rc;
+    }
+    const bool on = rs && rs->apply != 0;
+    bhg::RedshiftParams rp;
+    bhg::ObserverParams op;
+    if (on) {
+        if (!x0_shared) return fail(BHG_E_INVALID, "x0_shared is NULL");
+        int rc = bhg::redshift_params(p, rs, has_disk && (rs->apply & BHG_REDSHIFT_DISK) ? sc->disk_r_in : -1.0, x0_shared, &rp);
+        if (rc != BHG_OK) return rc;
+        if (obs) {
+            rc = bhg::observer_params(p, obs, x0_shared, &op);
+            if (rc != BHG_OK) return rc;
+        }
+    }
+    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
+    if (n_pixels == 0) return BHG_OK;
+    if ((!d_rgba && !d_rgba_f32) || (!d_end && !d_end_dir) || !d_flags || !sc->d_sky)
+        return fail(BHG_E_INVALID, "NULL device pointer");
+    if (!d_end && (has_disk || sc->n_spheres > 0))
+        return fail(BHG_E_INVALID, "d_end is NULL: a direction-only frame cannot have a disk or object spheres");
+    if (sc->n_spheres > 0 && !d_object_id) return fail(BHG_E_INVALID, "object_id is NULL but the scene has spheres");
+    if (on && !d_k0) return fail(BHG_E_INVALID, "redshift needs the camera directions d_k0");
+    ENTER_DEVICE(c->device);
+    bhg::ShadeArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.end = d_end;
+    a.dir = d_end ? nullptr : d_end_dir;
+    if (on) {
+        a.rs = rp;
+        a.k0 = d_k0;
+        if (obs) a.obs = op;
+    }
+    a.flags = d_flags;
+    a.sky = sc->d_sky;
+    a.rgba = d_rgba;
+    a.rgba_f32 = d_rgba_f32;
+    a.scatter = d_scatter;
+    a.n_pixels = n_pixels;
+    a.samples = samples;
+    a.sky_w = sc->sky_w;
+    a.sky_h = sc->sky_h;
+    a.object_id = sc->n_spheres > 0 ? d_object_id : nullptr;
+    a.disk_tex = sc->d_disk_tex;
+    a.disk_w = sc->disk_w;
+    a.disk_h = sc->disk_h;
+    a.disk_r_in = sc->disk_r_in;
+    a.disk_r_out = sc->disk_r_out;
+    a.disk_phase = sc->disk_phase;
+    a.disk_mean = sc->disk_mean;
+    a.disk_stddev = sc->disk_stddev;
+    a.disk_intensity = sc->disk_intensity;
+    a.n_spheres = sc->n_spheres;
+    a.n_lamps = sc->n_lamps;
+    std::memcpy(a.spheres, sc->spheres, sizeof(a.spheres));
+    std::memcpy(a.sphere_rgb, sc->sphere_rgb, sizeof(a.sphere_rgb));
+    std::memcpy(a.lamps, sc->lamps, sizeof(a.lamps));
+    if (ot) a.ot = tp;
+    HIP_TRY(bhg::launch_shade(a, (hipStream_t)stream));
+    return BHG_OK;
+}
+
+// the scene of the sky-only calls: the sky and nothing else
+bhg_scene sky_scene(const float *d_sky, int32_t sky_w, int32_t sky_h)
+{
+    bhg_scene sc;
+    std::memset(&sc, 0, sizeof(sc));
+    sc.d_sky = d_sky;
+    sc.sky_w = sky_w;
+    sc.sky_h = sky_h;
+    return sc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1373,188 +1477,43 @@ int bhg_raygen_observer_device(bhg_context *c, const bhg_params *p, const bhg_ob
 int bhg_shade_device(bhg_context *c, const double *d_end, const uint8_t *d_flags, size_t n_pixels, int32_t samples,
                      const float *d_sky, int32_t sky_w, int32_t sky_h, double *d_rgba, void *stream)
 {
-    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
-    if (samples <= 0 || sky_w <= 0 || sky_h <= 0) return fail(BHG_E_INVALID, "samples, sky_w, sky_h must be > 0");
-    if (n_pixels == 0) return BHG_OK;
-    if (!d_end || !d_flags || !d_sky || !d_rgba) return fail(BHG_E_INVALID, "NULL device pointer");
-    ENTER_DEVICE(c->device);
-    bhg::ShadeArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.end = d_end;
-    a.flags = d_flags;
-    a.sky = d_sky;
-    a.rgba = d_rgba;
-    a.n_pixels = n_pixels;
-    a.samples = samples;
-    a.sky_w = sky_w;
-    a.sky_h = sky_h;
-    HIP_TRY(bhg::launch_shade(a, (hipStream_t)stream));
-    return BHG_OK;
+    const bhg_scene sc = sky_scene(d_sky, sky_w, sky_h);
+    return shade(c, d_end, nullptr, d_flags, nullptr, n_pixels, samples, &sc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                 d_rgba, nullptr, nullptr, stream);
 }
 
 int bhg_shade_dir_device(bhg_context *c, const double *d_end_dir, const uint8_t *d_flags, size_t n_pixels, int32_t samples,
                          const float *d_sky, int32_t sky_w, int32_t sky_h, double *d_rgba, float *d_rgba_f32,
                          const int64_t *d_scatter, void *stream)
 {
-    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
-    if (samples <= 0 || sky_w <= 0 || sky_h <= 0) return fail(BHG_E_INVALID, "samples, sky_w, sky_h must be > 0");
-    if (n_pixels == 0) return BHG_OK;
-    if (!d_end_dir || !d_flags || !d_sky || (!d_rgba && !d_rgba_f32)) return fail(BHG_E_INVALID, "NULL device pointer");
-    ENTER_DEVICE(c->device);
-    bhg::ShadeArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.dir = d_end_dir;
-    a.flags = d_flags;
-    a.sky = d_sky;
-    a.rgba = d_rgba;
-    a.rgba_f32 = d_rgba_f32;
-    a.scatter = d_scatter;
-    a.n_pixels = n_pixels;
-    a.samples = samples;
-    a.sky_w = sky_w;
-    a.sky_h = sky_h;
-    HIP_TRY(bhg::launch_shade(a, (hipStream_t)stream));
-    return BHG_OK;
+    const bhg_scene sc = sky_scene(d_sky, sky_w, sky_h);
+    return shade(c, nullptr, d_end_dir, d_flags, nullptr, n_pixels, samples, &sc, nullptr, nullptr, nullptr, nullptr, nullptr,
+                 nullptr, d_rgba, d_rgba_f32, d_scatter, stream);
 }
-
-}  // extern "C"
-
-namespace {
-int shade_scene_impl(bhg_context *c, const double *d_end, const uint8_t *d_flags, const int8_t *d_object_id,
-                     size_t n_pixels, int32_t samples, const bhg_scene *sc, double *d_rgba, float *d_rgba_f32,
-                     const int64_t *d_scatter, void *stream, const double *d_end_dir = nullptr,
-                     const bhg::RedshiftParams *rs = nullptr, const double *d_k0 = nullptr,
-                     const bhg::ObserverParams *obs = nullptr, const bhg::ObjectTextureParams *ot = nullptr);
-}
-
-extern "C" {
 
 int bhg_shade_scene_device(bhg_context *c, const double *d_end, const uint8_t *d_flags, const int8_t *d_object_id,
                            size_t n_pixels, int32_t samples, const bhg_scene *sc, double *d_rgba, void *stream)
 {
-    if (n_pixels && !d_rgba) return fail(BHG_E_INVALID, "NULL device pointer");
-    return shade_scene_impl(c, d_end, d_flags, d_object_id, n_pixels, samples, sc, d_rgba, nullptr, nullptr, stream);
+    return shade(c, d_end, nullptr, d_flags, d_object_id, n_pixels, samples, sc, nullptr, nullptr, nullptr, nullptr, nullptr,
+                 nullptr, d_rgba, nullptr, nullptr, stream);
 }
 
 int bhg_shade_scene_f32_device(bhg_context *c, const double *d_end, const uint8_t *d_flags, const int8_t *d_object_id,
                                size_t n_pixels, int32_t samples, const bhg_scene *sc, float *d_rgba_f32,
                                const int64_t *d_scatter, void *stream)
 {
-    if (n_pixels && !d_rgba_f32) return fail(BHG_E_INVALID, "NULL device pointer");
-    return shade_scene_impl(c, d_end, d_flags, d_object_id, n_pixels, samples, sc, nullptr, d_rgba_f32, d_scatter, stream);
+    return shade(c, d_end, nullptr, d_flags, d_object_id, n_pixels, samples, sc, nullptr, nullptr, nullptr, nullptr, nullptr,
+                 nullptr, nullptr, d_rgba_f32, d_scatter, stream);
 }
-
-}  // extern "C"
-
-namespace {
-
-int shade_scene_impl(bhg_context *c, const double *d_end, const uint8_t *d_flags, const int8_t *d_object_id,
-                     size_t n_pixels, int32_t samples, const bhg_scene *sc, double *d_rgba, float *d_rgba_f32,
-                     const int64_t *d_scatter, void *stream, const double *d_end_dir, const bhg::RedshiftParams *rs,
-                     const double *d_k0, const bhg::ObserverParams *obs, const bhg::ObjectTextureParams *ot)
-{
-    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
-    if (!sc) return fail(BHG_E_INVALID, "scene is NULL");
-    if (samples <= 0 || sc->sky_w <= 0 || sc->sky_h <= 0) return fail(BHG_E_INVALID, "samples, sky_w, sky_h must be > 0");
-    if (sc->n_spheres < 0 || sc->n_spheres > BHG_MAX_SPHERES || sc->n_lamps < 0 || sc->n_lamps > 4)
-        return fail(BHG_E_INVALID, "n_spheres must be in [0, BHG_MAX_SPHERES], n_lamps in [0, 4]");
-    // (an EMPTY shard -- a rank without pixels: fewer tiles than ranks -- has no rays and no arrays: nothing to check them against)
-    if (n_pixels > 0 && sc->n_spheres > 0 && !d_object_id) return fail(BHG_E_INVALID, "object_id is NULL but the scene has spheres");
-    if (sc->disk_r_out > 0.0) {
-        if (!(sc->disk_r_out > sc->disk_r_in) || !(sc->disk_stddev > 0.0))
-            return fail(BHG_E_INVALID, "disk needs r_out > r_in and stddev > 0");
-        if (sc->d_disk_tex && (sc->disk_w <= 0 || sc->disk_h <= 0)) return fail(BHG_E_INVALID, "disk texture size must be > 0");
-    }
-    for (int j = 0; j < sc->n_spheres; j++)
-        if (!(sc->spheres[j][3] > 0.0)) return fail(BHG_E_INVALID, "sphere radii must be > 0");
-    if (n_pixels == 0) return BHG_OK;
-    if ((!d_end && !d_end_dir) || !d_flags || !sc->d_sky) return fail(BHG_E_INVALID, "NULL device pointer");
-    if (rs && !d_k0) return fail(BHG_E_INVALID, "redshift needs the camera directions d_k0");
-    ENTER_DEVICE(c->device);
-    bhg::ShadeArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.end = d_end;
-    a.dir = d_end ? nullptr : d_end_dir;
-    if (rs) {
-        a.rs = *rs;
-        a.k0 = d_k0;
-        if (obs) a.obs = *obs;
-    }
-    a.flags = d_flags;
-    a.sky = sc->d_sky;
-    a.rgba = d_rgba;
-    a.rgba_f32 = d_rgba_f32;
-    a.scatter = d_scatter;
-    a.n_pixels = n_pixels;
-    a.samples = samples;
-    a.sky_w = sc->sky_w;
-    a.sky_h = sc->sky_h;
-    a.object_id = sc->n_spheres > 0 ? d_object_id : nullptr;
-    a.disk_tex = sc->d_disk_tex;
-    a.disk_w = sc->disk_w;
-    a.disk_h = sc->disk_h;
-    a.disk_r_in = sc->disk_r_in;
-    a.disk_r_out = sc->disk_r_out;
-    a.disk_phase = sc->disk_phase;
-    a.disk_mean = sc->disk_mean;
-    a.disk_stddev = sc->disk_stddev;
-    a.disk_intensity = sc->disk_intensity;
-    a.n_spheres = sc->n_spheres;
-    a.n_lamps = sc->n_lamps;
-    std::memcpy(a.spheres, sc->spheres, sizeof(a.spheres));
-    std::memcpy(a.sphere_rgb, sc->sphere_rgb, sizeof(a.sphere_rgb));
-    std::memcpy(a.lamps, sc->lamps, sizeof(a.lamps));
-    if (ot) a.ot = *ot;
-    HIP_TRY(bhg::launch_shade(a, (hipStream_t)stream));
-    return BHG_OK;
-}
-
-}  // namespace
-
-extern "C" {
 
 int bhg_shade_scene_redshift_device(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
                                     const int8_t *d_object_id, size_t n_pixels, int32_t samples, const bhg_scene *sc,
                                     const bhg_params *p, const bhg_redshift *rs, const double *x0_shared, const double *d_k0,
                                     double *d_rgba, float *d_rgba_f32, const int64_t *d_scatter, void *stream)
 {
-    return bhg_shade_scene_redshift_observer_device(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs,
-                                                    nullptr, x0_shared, d_k0, d_rgba, d_rgba_f32, d_scatter, stream);
+    return shade(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs, nullptr, nullptr, x0_shared, d_k0,
+                 d_rgba, d_rgba_f32, d_scatter, stream);
 }
-
-}  // extern "C"
-
-namespace {
-// bhg_shade_scene_redshift_observer_device with the textured instance's table (ot = nullptr: without textures)
-int shade_scene_rs_impl(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags, const int8_t *d_object_id,
-                        size_t n_pixels, int32_t samples, const bhg_scene *sc, const bhg_params *p, const bhg_redshift *rs,
-                        const bhg_observer *obs, const double *x0_shared, const double *d_k0, double *d_rgba, float *d_rgba_f32,
-                        const int64_t *d_scatter, void *stream, const bhg::ObjectTextureParams *ot)
-{
-    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
-    if (!sc) return fail(BHG_E_INVALID, "scene is NULL");
-    if (n_pixels && !d_rgba && !d_rgba_f32) return fail(BHG_E_INVALID, "NULL device pointer (d_rgba and d_rgba_f32)");
-    if (!d_end && (sc->disk_r_out > 0.0 || sc->n_spheres > 0))
-        return fail(BHG_E_INVALID, "d_end is NULL: a direction-only frame cannot have a disk or object spheres");
-    bhg::RedshiftParams rp;
-    const bool on = rs && rs->apply != 0;
-    if (on) {
-        if (!x0_shared) return fail(BHG_E_INVALID, "x0_shared is NULL");
-        const bool disk = sc->disk_r_out > 0.0 && (rs->apply & BHG_REDSHIFT_DISK);
-        int rc = bhg::redshift_params(p, rs, disk ? sc->disk_r_in : -1.0, x0_shared, &rp);
-        if (rc != BHG_OK) return rc;
-    }
-    bhg::ObserverParams op;
-    if (on && obs) {
-        int rc = bhg::observer_params(p, obs, x0_shared, &op);
-        if (rc != BHG_OK) return rc;
-    }
-    return shade_scene_impl(c, d_end, d_flags, d_object_id, n_pixels, samples, sc, d_rgba, d_rgba_f32, d_scatter, stream,
-                            d_end_dir, on ? &rp : nullptr, d_k0, on && obs ? &op : nullptr, ot);
-}
-}  // namespace
-
-extern "C" {
 
 int bhg_shade_scene_redshift_observer_device(bhg_context *c, const double *d_end, const double *d_end_dir,
                                              const uint8_t *d_flags, const int8_t *d_object_id, size_t n_pixels,
@@ -1563,8 +1522,8 @@ int bhg_shade_scene_redshift_observer_device(bhg_context *c, const double *d_end
                                              const double *d_k0, double *d_rgba, float *d_rgba_f32,
                                              const int64_t *d_scatter, void *stream)
 {
-    return shade_scene_rs_impl(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs, obs, x0_shared, d_k0, d_rgba,
-                               d_rgba_f32, d_scatter, stream, nullptr);
+    return shade(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs, obs, nullptr, x0_shared, d_k0, d_rgba,
+                 d_rgba_f32, d_scatter, stream);
 }
 
 int bhg_shade_scene_textured_device(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
@@ -1573,16 +1532,8 @@ int bhg_shade_scene_textured_device(bhg_context *c, const double *d_end, const d
                                     const bhg_object_textures *ot, const double *x0_shared, const double *d_k0, double *d_rgba,
                                     float *d_rgba_f32, const int64_t *d_scatter, void *stream)
 {
-    if (!ot)
-        return bhg_shade_scene_redshift_observer_device(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs, obs,
-                                                        x0_shared, d_k0, d_rgba, d_rgba_f32, d_scatter, stream);
-    // (the table is checked before the context: a refusal names its sphere with or without a device)
-    if (!sc) return fail(BHG_E_INVALID, "scene is NULL");
-    bhg::ObjectTextureParams tp;
-    int rc = bhg::object_texture_params(ot, sc->n_spheres, &tp);
-    if (rc != BHG_OK) return rc;
-    return shade_scene_rs_impl(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs, obs, x0_shared, d_k0, d_rgba,
-                               d_rgba_f32, d_scatter, stream, &tp);
+    return shade(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs, obs, ot, x0_shared, d_k0, d_rgba,
+                 d_rgba_f32, d_scatter, stream);
 }
 
 int bhg_redshift_device(bhg_context *c, const bhg_params *p, const bhg_redshift *rs, const double *x0_shared,

@@ -784,17 +784,6 @@ try {
             BHG_TRY(s.dir.ensure(s.device, s.n * 3 * sizeof(double)));
             BHG_TRY(bhg_trace_dir_device(s.ctx, &prm, f->cam.origin, nullptr, s.k0.as<double>(), s.n, s.dir.as<double>(),
                                          s.flags.as<uint8_t>(), s.steps.as<uint32_t>(), s.acc.as<uint32_t>(), s.stream));
-            if (f->profiling) HIP_TRY(hipEventRecord(s.evs[s.ev_used++].second, s.stream));
-            if (redshift) {   // (sky g needs only the camera state: still direction-only)
-                bhg_scene sc;
-                fill_scene(f, s, &sc);
-                BHG_TRY(bhg_shade_scene_redshift_observer_device(s.ctx, nullptr, s.dir.as<double>(), s.flags.as<uint8_t>(), nullptr,
-                                                                 s.P, S, &sc, &prm, &f->rs, obs, f->cam.origin, s.k0.as<double>(),
-                                                                 nullptr, dst, scatter, s.stream));
-            } else {
-                BHG_TRY(bhg_shade_dir_device(s.ctx, s.dir.as<double>(), s.flags.as<uint8_t>(), s.P, S, s.sky.as<float>(), f->sky_w,
-                                             f->sky_h, nullptr, dst, scatter, s.stream));
-            }
         } else {
             BHG_TRY(s.end.ensure(s.device, s.n * 6 * sizeof(double)));
             if (has_obj) BHG_TRY(s.obj.ensure(s.device, s.n));
@@ -802,24 +791,18 @@ try {
                                              f->cam.origin, nullptr, s.k0.as<double>(), s.n, s.end.as<double>(),
                                              s.flags.as<uint8_t>(), s.steps.as<uint32_t>(), s.acc.as<uint32_t>(),
                                              has_obj ? s.obj.as<int8_t>() : nullptr, s.stream));
-            if (f->profiling) HIP_TRY(hipEventRecord(s.evs[s.ev_used++].second, s.stream));
-            bhg_scene sc;
-            fill_scene(f, s, &sc);
-            if (textured) {
-                bhg_object_textures ot;
-                fill_object_textures(f, &s, &ot);
-                BHG_TRY(bhg_shade_scene_textured_device(s.ctx, s.end.as<double>(), nullptr, s.flags.as<uint8_t>(), s.obj.as<int8_t>(), s.P,
-                                                        S, &sc, &prm, redshift ? &f->rs : nullptr, obs, &ot, f->cam.origin,
-                                                        s.k0.as<double>(), nullptr, dst, scatter, s.stream));
-            } else if (redshift)
-                BHG_TRY(bhg_shade_scene_redshift_observer_device(s.ctx, s.end.as<double>(), nullptr, s.flags.as<uint8_t>(),
-                                                                 has_obj ? s.obj.as<int8_t>() : nullptr, s.P, S, &sc, &prm, &f->rs,
-                                                                 obs, f->cam.origin, s.k0.as<double>(), nullptr, dst, scatter,
-                                                                 s.stream));
-            else
-                BHG_TRY(bhg_shade_scene_f32_device(s.ctx, s.end.as<double>(), s.flags.as<uint8_t>(), has_obj ? s.obj.as<int8_t>() : nullptr,
-                                                   s.P, S, &sc, dst, scatter, s.stream));
         }
+        if (f->profiling) HIP_TRY(hipEventRecord(s.evs[s.ev_used++].second, s.stream));
+        // one shade call whatever the scene: a direction-only frame passes its exit directions (its sky g needs only the
+        // camera state), the others their whole end records
+        bhg_scene sc;
+        fill_scene(f, s, &sc);
+        bhg_object_textures ot;
+        if (textured) fill_object_textures(f, &s, &ot);
+        BHG_TRY(bhg_shade_scene_textured_device(s.ctx, dir_only ? nullptr : s.end.as<double>(), dir_only ? s.dir.as<double>() : nullptr,
+                                                s.flags.as<uint8_t>(), has_obj ? s.obj.as<int8_t>() : nullptr, s.P, S, &sc, &prm,
+                                                redshift ? &f->rs : nullptr, obs, textured ? &ot : nullptr, f->cam.origin,
+                                                s.k0.as<double>(), nullptr, dst, scatter, s.stream));
         s.dir_traced = dir_only;
     }
     // -- ONE gather onto the first device -----------------------------------------------------------------------------

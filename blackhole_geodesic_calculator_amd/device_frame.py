@@ -162,13 +162,6 @@ class DeviceFrame:
     def _textured(self):
         return self.object_textures is not None and self.spheres is not None and len(self.spheres) > 0
 
-    def _shade_textured(self, d_rgba=0, d_rgba_f32=0, scatter=None):
-        self.ctx.shade_scene_textured_device(self.d_end.data_ptr(), self.d_flags.data_ptr(), self.P, self.S, self.scene(), self._params,
-                                             self.redshift, self.observer, self._object_textures(), x0_shared=self.origin,
-                                             d_k0=self.d_k0.data_ptr(), d_rgba=d_rgba, d_rgba_f32=d_rgba_f32,
-                                             d_object_id=self.d_obj.data_ptr(), d_scatter=0 if scatter is None else scatter.data_ptr(),
-                                             stream=self._stream())
-
     def _observer_key(self, params):
         return (tuple(float(v) for v in self.origin), float(params.r_s), float(params.spin), int(params.rhs_form))
 
@@ -240,59 +233,27 @@ class DeviceFrame:
             raise RuntimeError("the last trace wrote exit directions only, but the frame now has a disk / objects: trace() again")
         return traced
 
-    def _shade_redshift(self, form, d_rgba=0, d_rgba_f32=0, scatter=None):
-        kw = dict(d_rgba=d_rgba, d_rgba_f32=d_rgba_f32, d_object_id=0 if self.d_obj is None else self.d_obj.data_ptr(),
-                  d_scatter=0 if scatter is None else scatter.data_ptr(), d_end_dir=self.d_dir.data_ptr() if form == "dir" else 0,
-                  stream=self._stream())
-        d_end = self.d_end.data_ptr() if form == "end" else 0
-        if self.observer is not None:
-            self.ctx.shade_scene_redshift_observer_device(d_end, self.d_flags.data_ptr(), self.P, self.S, self.scene(), self._params,
-                                                          self.redshift, self.observer, self.origin, self.d_k0.data_ptr(), **kw)
-            return
-        self.ctx.shade_scene_redshift_device(d_end, self.d_flags.data_ptr(), self.P, self.S, self.scene(), self._params,
-                                             self.redshift, self.origin, self.d_k0.data_ptr(), **kw)
+    def _shade(self, d_rgba=0, d_rgba_f32=0, scatter=None):
+        """The one shade call of both outputs (bhg_shade_scene_textured_device): redshift, the observer and the object textures
+        as set, each None when off."""
+        form = self._shade_form()
+        self.ctx.shade_scene_textured_device(self.d_end.data_ptr() if form == "end" else 0, self.d_flags.data_ptr(), self.P, self.S,
+                                             self.scene(), self._params, self.redshift, self.observer,
+                                             self._object_textures() if self._textured() else None, x0_shared=self.origin,
+                                             d_k0=self.d_k0.data_ptr(), d_rgba=d_rgba, d_rgba_f32=d_rgba_f32,
+                                             d_object_id=0 if self.d_obj is None else self.d_obj.data_ptr(),
+                                             d_scatter=0 if scatter is None else scatter.data_ptr(),
+                                             d_end_dir=self.d_dir.data_ptr() if form == "dir" else 0, stream=self._stream())
 
     def shade(self):
-        form = self._shade_form()
-        if self._textured():
-            self._shade_textured(d_rgba=self.d_rgba.data_ptr())
-            return self.d_rgba
-        if self.redshift is not None:
-            self._shade_redshift(form, d_rgba=self.d_rgba.data_ptr())
-            return self.d_rgba
-        if self.disk is not None or (self.spheres is not None and len(self.spheres) > 0):
-            self.ctx.shade_scene_device(self.d_end.data_ptr(), self.d_flags.data_ptr(), self.P, self.S, self.scene(),
-                                        self.d_rgba.data_ptr(),
-                                        d_object_id=0 if self.d_obj is None else self.d_obj.data_ptr(),
-                                        stream=self._stream())
-            return self.d_rgba
-        if form == "dir":
-            self.ctx.shade_dir_device(self.d_dir.data_ptr(), self.d_flags.data_ptr(), self.P, self.S, self.d_sky.data_ptr(),
-                                      self.sky_wh[0], self.sky_wh[1], d_rgba=self.d_rgba.data_ptr(), stream=self._stream())
-            return self.d_rgba
-        self.ctx.shade_device(self.d_end.data_ptr(), self.d_flags.data_ptr(), self.P, self.S, self.d_sky.data_ptr(),
-                              self.sky_wh[0], self.sky_wh[1], self.d_rgba.data_ptr(), stream=self._stream())
+        self._shade(d_rgba=self.d_rgba.data_ptr())
         return self.d_rgba
 
     def shade_f32(self, out, scatter=None):
         """Shade + sample mean written as float32 RGBA into `out` ([P, 4], or [H*W, 4] with scatter = this shard's
         flat pixel ids): what layer.rect takes, without the fp64 intermediate."""
-        form = self._shade_form()
         assert out.dtype == torch.float32 and out.is_contiguous()
-        if self._textured():
-            self._shade_textured(d_rgba_f32=out.data_ptr(), scatter=scatter)
-            return out
-        if self.redshift is not None:
-            self._shade_redshift(form, d_rgba_f32=out.data_ptr(), scatter=scatter)
-            return out
-        if form == "dir":
-            self.ctx.shade_dir_device(self.d_dir.data_ptr(), self.d_flags.data_ptr(), self.P, self.S, self.d_sky.data_ptr(),
-                                      self.sky_wh[0], self.sky_wh[1], d_rgba_f32=out.data_ptr(),
-                                      d_scatter=0 if scatter is None else scatter.data_ptr(), stream=self._stream())
-            return out
-        self.ctx.shade_scene_f32_device(self.d_end.data_ptr(), self.d_flags.data_ptr(), self.P, self.S, self.scene(),
-                                        out.data_ptr(), d_object_id=0 if self.d_obj is None else self.d_obj.data_ptr(),
-                                        d_scatter=0 if scatter is None else scatter.data_ptr(), stream=self._stream())
+        self._shade(d_rgba_f32=out.data_ptr(), scatter=scatter)
         return out
 
     def render(self, params: _ffi.Params, regenerate_rays=False):

@@ -565,7 +565,18 @@ typedef struct bhg_object_textures {
 size_t bhg_object_textures_size(void);
 /* bhg_shade_scene_redshift_observer_device with textured object spheres; tex[] holds DEVICE addresses.  ot = NULL is exactly
  * that call, bit for bit; any other ot takes the textured kernel instances, and a zero-initialised ot gives that call's image
- * bit for bit (a white texel is an exact x 1.0).  ot is checked before the context. */
+ * bit for bit (a white texel is an exact x 1.0).
+ * This is the general shade call: every other bhg_shade*_device is this call with some arguments NULL (bhg_shade_device and
+ * bhg_shade_dir_device with a scene of the sky alone).  All of them check in this order, so that settings are refused with or
+ * without a device:
+ *   1. the scene: not NULL; samples, sky_w, sky_h > 0; n_spheres in [0, BHG_MAX_SPHERES], n_lamps in [0, 4]; a disk with
+ *      r_out > r_in, stddev > 0 and (with a texture) disk_w, disk_h > 0; sphere radii > 0
+ *   2. ot, when not NULL, against n_spheres
+ *   3. with rs->apply != 0: x0_shared not NULL, the redshift settings against p, then obs when not NULL
+ *   4. ctx not NULL
+ *   5. n_pixels == 0: BHG_OK, no device array is looked at (an empty shard)
+ *   6. the device arrays: d_rgba or d_rgba_f32; d_end or d_end_dir; d_flags and the sky; d_end when the scene has a disk or
+ *      spheres; d_object_id when it has spheres; d_k0 with redshift on */
 int bhg_shade_scene_textured_device(bhg_context *ctx, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
                                     const int8_t *d_object_id, size_t n_pixels, int32_t samples, const bhg_scene *scene,
                                     const bhg_params *p, const bhg_redshift *rs, const bhg_observer *obs,

@@ -1,6 +1,7 @@
 """Textured, oriented and emissive object spheres on the GPU: the textured shade instances against the
 numpy restatement (tests/object_texture_reference.py) for both Schwarzschild forms and Kerr with redshift off, on and on with an
-observer; ot = NULL and a zero-initialised ot bit for bit the untextured call; a traced sphere whose texture encodes (U, V);
+observer; ot = NULL and a zero-initialised ot bit for bit the untextured call; every other shade entry point bit for bit the
+general call, and an empty call accepted by each; a traced sphere whose texture encodes (U, V);
 the library-owned frame on one device and on the {0, 0} loopback against DeviceFrame, rotation-only updates and textures off."""
 import os
 import sys
@@ -94,7 +95,7 @@ def _device_ot(T, keep):
 
 
 class _Shade:
-    """One synthetic frame on the device and the textured / untextured shade calls on it."""
+    """One synthetic frame on the device and the shade entry points on it."""
 
     def __init__(self, ctx, P, S, seed, rhs, spin):
         import torch
@@ -110,23 +111,46 @@ class _Shade:
                                   spheres=SPHERES, sphere_rgb=RGB, lamps=LAMPS, **PROFILE)
         self.params = f.make_params(r_s=1.0, lambda_end=80.0, r_exit=40.0, rhs_form=rhs, spin=spin, disk_r_in=DISK[0],
                                     disk_r_out=DISK[1])
+        # the sky alone: every ray that is not a horizon ray is a sky ray, read as end records or as their directions
+        self.keep += [torch.as_tensor(np.where(self.flags == 1, 1, 8).astype(np.uint8)).cuda(),
+                      torch.as_tensor(np.ascontiguousarray(self.end[:, 3:6])).cuda()]
+        self.d_fl_sky, self.d_dir = self.keep[-2:]
+        self.sky_scene = f.make_scene(self.d_sky.data_ptr(), 128, 64)
 
-    def run(self, rs, obs, ot, textured=True):
+    def run(self, rs, obs, ot, entry="textured", form="scene"):
+        """The fp64, float32 and scattered float32 images of one shade entry point (None: an output it does not write).  form:
+        "scene" (disk and spheres), or the sky alone -- "sky" from the end records, "dir" from their directions."""
         import torch
-        d64 = torch.empty((self.P, 4), dtype=torch.float64, device="cuda")
-        d32 = torch.empty((self.P, 4), dtype=torch.float32, device="cuda")
-        perm = torch.randperm(self.P, device="cuda")
-        sc = torch.zeros((self.P, 4), dtype=torch.float32, device="cuda")
-        for out in (dict(d_rgba=d64.data_ptr()), dict(d_rgba_f32=d32.data_ptr()), dict(d_rgba_f32=sc.data_ptr(), d_scatter=perm.data_ptr())):
-            kw = dict(d_object_id=self.d_obj.data_ptr(), stream=torch.cuda.current_stream().cuda_stream, **out)
-            if textured:
-                self.ctx.shade_scene_textured_device(self.d_end.data_ptr(), self.d_fl.data_ptr(), self.P, self.S, self.scene, self.params,
-                                                     rs, obs, ot, x0_shared=CAM3, d_k0=self.d_k0.data_ptr(), **kw)
-            else:
-                self.ctx.shade_scene_redshift_observer_device(self.d_end.data_ptr(), self.d_fl.data_ptr(), self.P, self.S, self.scene,
-                                                              self.params, rs, obs, CAM3, self.d_k0.data_ptr(), **kw)
+        c, P, S, st = self.ctx, self.P, self.S, torch.cuda.current_stream().cuda_stream
+        d_end, d_dir, d_fl, scene = self.d_end.data_ptr(), 0, self.d_fl.data_ptr(), self.scene
+        if form != "scene":
+            d_fl, scene = self.d_fl_sky.data_ptr(), self.sky_scene
+        if form == "dir":
+            d_end, d_dir = 0, self.d_dir.data_ptr()
+        d_sky, d_k0, d_obj = self.d_sky.data_ptr(), self.d_k0.data_ptr(), self.d_obj.data_ptr()
+        calls = {
+            "shade": lambda o: c.shade_device(d_end, d_fl, P, S, d_sky, 128, 64, o["d_rgba"], stream=st),
+            "shade_dir": lambda o: c.shade_dir_device(d_dir, d_fl, P, S, d_sky, 128, 64, stream=st, **o),
+            "shade_scene": lambda o: c.shade_scene_device(d_end, d_fl, P, S, scene, o["d_rgba"], d_object_id=d_obj, stream=st),
+            "shade_scene_f32": lambda o: c.shade_scene_f32_device(d_end, d_fl, P, S, scene, o["d_rgba_f32"], d_object_id=d_obj,
+                                                                  d_scatter=o.get("d_scatter", 0), stream=st),
+            "redshift": lambda o: c.shade_scene_redshift_device(d_end, d_fl, P, S, scene, self.params, rs, CAM3, d_k0, d_object_id=d_obj,
+                                                                d_end_dir=d_dir, stream=st, **o),
+            "redshift_observer": lambda o: c.shade_scene_redshift_observer_device(d_end, d_fl, P, S, scene, self.params, rs, obs, CAM3,
+                                                                                  d_k0, d_object_id=d_obj, d_end_dir=d_dir, stream=st, **o),
+            "textured": lambda o: c.shade_scene_textured_device(d_end, d_fl, P, S, scene, self.params, rs, obs, ot, x0_shared=CAM3,
+                                                                d_k0=d_k0, d_object_id=d_obj, d_end_dir=d_dir, stream=st, **o),
+        }
+        writes = {"shade": (0,), "shade_scene": (0,), "shade_scene_f32": (1, 2)}.get(entry, (0, 1, 2))
+        d64 = torch.full((P, 4), float("nan"), dtype=torch.float64, device="cuda")
+        d32 = torch.full((P, 4), float("nan"), dtype=torch.float32, device="cuda")
+        sc = torch.full((P, 4), float("nan"), dtype=torch.float32, device="cuda")
+        perm = torch.randperm(P, device="cuda")
+        outs = (dict(d_rgba=d64.data_ptr()), dict(d_rgba_f32=d32.data_ptr()), dict(d_rgba_f32=sc.data_ptr(), d_scatter=perm.data_ptr()))
+        for j in writes:
+            calls[entry](outs[j])
         torch.cuda.synchronize()
-        return d64.cpu().numpy(), d32.cpu().numpy(), sc[perm].cpu().numpy()
+        return tuple(img if j in writes else None for j, img in enumerate((d64.cpu().numpy(), d32.cpu().numpy(), sc[perm].cpu().numpy())))
 
 
 METRICS = [("christoffel", 0, 0.0), ("reduced", 1, 0.0), ("kerr", 2, 0.45)]
@@ -174,12 +198,62 @@ def test_null_and_zero_tables_are_the_untextured_call(ctx, rsmode):
             sh = _Shade(ctx, P, S, 7, rhs, spin)
             rs = None if rsmode == "off" else f.make_redshift(("disk", "objects", "sky"), 4.0, 1)
             obs = f.make_observer(BETA) if rsmode == "observer" else None
-            today = sh.run(rs, obs, None, textured=False)
+            today = sh.run(rs, obs, None, entry="redshift_observer")
             for ot in (None, f.ObjectTextures()):
                 got = sh.run(rs, obs, ot)
                 for a, b in zip(got, today):
                     assert np.array_equal(a, b)
 
+
+
+# (entry point, frame form, redshift): each entry point on the frames it is meant for
+ENTRIES = [("shade", "sky", "off"), ("shade_dir", "dir", "off"), ("shade_scene", "scene", "off"), ("shade_scene_f32", "scene", "off"),
+           ("redshift", "scene", "on"), ("redshift", "dir", "on"), ("redshift_observer", "scene", "observer"),
+           ("redshift_observer", "dir", "observer")]
+
+
+@pytest.mark.parametrize("entry,form,rsmode", ENTRIES)
+def test_every_entry_point_is_the_general_call(ctx, entry, form, rsmode):
+    """Each bhg_shade*_device writes the bytes of bhg_shade_scene_textured_device (ot = NULL) given the same inputs, with the
+    arguments it does not take NULL: fp64, float32 and scattered float32, end records and directions, redshift with and without
+    an observer."""
+    f = _ffi()
+    for P, S in ((700, 3), (5, 300)):
+        sh = _Shade(ctx, P, S, 9, 0, 0.0)
+        rs = None if rsmode == "off" else f.make_redshift(("disk", "objects", "sky"), 4.0, 1)
+        obs = f.make_observer(BETA) if rsmode == "observer" else None
+        got = sh.run(rs, obs, None, entry=entry, form=form)
+        want = sh.run(rs, obs, None, form=form)
+        assert all(np.isfinite(w).all() for w in want)
+        for g, w in zip(got, want):
+            assert g is None or np.array_equal(g, w), (entry, form, P, S)
+
+
+def test_every_entry_point_accepts_an_empty_call(ctx):
+    """n_pixels = 0 with a real context and every device array NULL is BHG_OK at all seven entry points: the empty shard of a
+    rank dealt no tiles (tests/test_gpu_multirank.py), here with a disk, spheres, redshift and the observer."""
+    import ctypes as C
+    f = _ffi()
+    L = f.load()
+    sc = C.byref(f.make_scene(0, 128, 64, disk=DISK, spheres=SPHERES, sphere_rgb=RGB, lamps=LAMPS, **PROFILE))
+    p = C.byref(f.make_params(r_s=1.0, lambda_end=80.0, r_exit=40.0, disk_r_in=DISK[0], disk_r_out=DISK[1]))
+    rs, obs, ot = C.byref(f.make_redshift()), C.byref(f.make_observer(BETA)), C.byref(f.ObjectTextures())
+    x0 = (C.c_double * 3)(*CAM3)
+    h = ctx._h
+    calls = {
+        "bhg_shade_device": lambda: L.bhg_shade_device(h, None, None, 0, 1, None, 128, 64, None, None),
+        "bhg_shade_dir_device": lambda: L.bhg_shade_dir_device(h, None, None, 0, 1, None, 128, 64, None, None, None, None),
+        "bhg_shade_scene_device": lambda: L.bhg_shade_scene_device(h, None, None, None, 0, 1, sc, None, None),
+        "bhg_shade_scene_f32_device": lambda: L.bhg_shade_scene_f32_device(h, None, None, None, 0, 1, sc, None, None, None),
+        "bhg_shade_scene_redshift_device": lambda: L.bhg_shade_scene_redshift_device(h, None, None, None, None, 0, 1, sc, p, rs, x0,
+                                                                                     None, None, None, None, None),
+        "bhg_shade_scene_redshift_observer_device": lambda: L.bhg_shade_scene_redshift_observer_device(
+            h, None, None, None, None, 0, 1, sc, p, rs, obs, x0, None, None, None, None, None),
+        "bhg_shade_scene_textured_device": lambda: L.bhg_shade_scene_textured_device(h, None, None, None, None, 0, 1, sc, p, rs, obs, ot,
+                                                                                     x0, None, None, None, None, None),
+    }
+    for name, call in calls.items():
+        assert call() == f.OK, (name, L.bhg_last_error().decode())
 
 def _uv_texture(TW, TH):
     """A texture whose texel centres hold their own (U, V): bilinear reads return (U, V) away from the seam and the poles."""

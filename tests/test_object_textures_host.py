@@ -173,7 +173,7 @@ def test_untextured_slot_size_and_high_slots_are_not_checked():
     ot.mode[2] = 4
     assert _shade_null_ctx(ot, n_spheres=2) == f.E_INVALID and "ctx is NULL" in L.bhg_last_error().decode()
     assert _shade_null_ctx(ot, n_spheres=3) == f.E_INVALID and "sphere 2" in L.bhg_last_error().decode()
-    # ot = NULL is the observer call (which checks the context first)
+    # ot = NULL: no table to check, and the call gets as far as the missing context
     assert _shade_null_ctx(None) == f.E_INVALID and "ctx is NULL" in L.bhg_last_error().decode()
     assert L.bhg_frame_set_object_textures(None, C.byref(ot)) == f.E_INVALID
     assert "frame" in L.bhg_last_error().decode()

@@ -214,6 +214,12 @@ def test_library_refuses(kw, what):
         assert f"{rr.photon_orbit(M, a, -kw.get('sense', 1)):.6g}"[:5] in msg, msg
     rc = lib.bhg_redshift_host(None, C.byref(p), C.byref(rs), C.addressof(x0), 1, None, None, None, 1, None)
     assert rc == _ffi.E_INVALID and what in lib.bhg_last_error().decode()
+    # the shade call checks the settings before the context too (the disk's r_in comes from the scene there)
+    sc = _ffi.make_scene(0, 16, 8, disk=(kw["disk_r_in"], 10.0) if "disk_r_in" in kw else None)
+    rc = lib.bhg_shade_scene_redshift_device(None, None, None, None, None, 1, 1, C.byref(sc), C.byref(p), C.byref(rs), x0, None, None,
+                                             None, None, None)
+    msg = lib.bhg_last_error().decode()
+    assert rc == _ffi.E_INVALID and what in msg and "ctx" not in msg, msg
 
 
 def test_library_refuses_a_disk_sense_other_than_plus_minus_one():
