@@ -58,6 +58,7 @@ EXPORTS = (
     "bhg_observer_size", "bhg_raygen_observer_device", "bhg_redshift_observer_device", "bhg_redshift_observer_host",
     "bhg_shade_scene_redshift_observer_device", "bhg_frame_set_observer",
     "bhg_object_textures_size", "bhg_shade_scene_textured_device", "bhg_frame_set_object_textures",
+    "bhg_polarisation_size", "bhg_polarisation_device", "bhg_polarisation_host", "bhg_shade_scene_polarised_device",
 )
 PROBE_FMA, PROBE_STEP_MIX = 0, 1
 
@@ -103,6 +104,29 @@ def make_observer(velocity):
 
 def _obs_ref(obs):
     return None if obs is None else C.byref(obs)
+
+
+POL_TABLE_MAX = 64
+
+
+class Polarisation(C.Structure):
+    """bhg_polarisation (BHG_POLARISATION, within ABI 10): the disk's degree table against the emission cosine, its sense and
+    image up (world axes at the camera)."""
+    _fields_ = [("disk_sense", C.c_int32), ("n_degree", C.c_int32), ("up", C.c_double * 3),
+                ("degree", C.c_double * POL_TABLE_MAX)]
+
+
+def make_polarisation(degree=0.1, disk_sense=1, up=(0.0, 1.0, 0.0)) -> Polarisation:
+    """degree: a constant, or a table of delta(mu_j) at mu_j = j / (n - 1) (1 to 64 numbers, linear between); disk_sense as
+    redshift's; up: image up on world axes."""
+    d = np.atleast_1d(np.asarray(degree, dtype=np.float64)).ravel()
+    if not 1 <= d.size <= POL_TABLE_MAX:
+        raise ValueError(f"the degree table has {d.size} entries: 1 to {POL_TABLE_MAX}")
+    pol = Polarisation()
+    pol.disk_sense, pol.n_degree = int(disk_sense), int(d.size)
+    pol.up[:] = [float(v) for v in np.asarray(up, dtype=np.float64).reshape(3)]
+    pol.degree[:d.size] = [float(v) for v in d]
+    return pol
 
 
 OBJECT_LIT, OBJECT_EMISSIVE = 0, 1
@@ -421,6 +445,21 @@ def load():
                                                   C.POINTER(Scene), C.POINTER(Params), C.POINTER(Redshift), C.POINTER(Observer),
                                                   C.POINTER(ObjectTextures), _dp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_void_p]
+    L.bhg_polarisation_size.restype = C.c_size_t
+    L.bhg_polarisation_size.argtypes = []
+    L.bhg_polarisation_device.restype = C.c_int
+    L.bhg_polarisation_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Polarisation), C.POINTER(Observer), _dp,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]
+    L.bhg_polarisation_host.restype = C.c_int
+    L.bhg_polarisation_host.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Polarisation), C.POINTER(Observer), C.c_void_p,
+                                        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]
+    L.bhg_shade_scene_polarised_device.restype = C.c_int
+    L.bhg_shade_scene_polarised_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                   C.c_int32, C.POINTER(Scene), C.POINTER(Params), C.POINTER(Redshift),
+                                                   C.POINTER(Observer), C.POINTER(ObjectTextures), _dp, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.POINTER(Polarisation), C.c_void_p, C.c_void_p]
     L.bhg_frame_set_object_textures.restype = C.c_int
     L.bhg_frame_set_object_textures.argtypes = [C.c_void_p, C.POINTER(ObjectTextures)]
     if L.bhg_version() != ABI_VERSION or not hasattr(L, "bhg_abi_check"):
@@ -441,6 +480,8 @@ def load():
         raise ImportError(f"libbhgeo: bhg_redshift is {L.bhg_redshift_size()} bytes, this binding's {C.sizeof(Redshift)}")
     if L.bhg_observer_size() != C.sizeof(Observer):
         raise ImportError(f"libbhgeo: bhg_observer is {L.bhg_observer_size()} bytes, this binding's {C.sizeof(Observer)}")
+    if L.bhg_polarisation_size() != C.sizeof(Polarisation):
+        raise ImportError(f"libbhgeo: bhg_polarisation is {L.bhg_polarisation_size()} bytes, this binding's {C.sizeof(Polarisation)}")
     if L.bhg_object_textures_size() != C.sizeof(ObjectTextures):
         raise ImportError(f"libbhgeo: bhg_object_textures is {L.bhg_object_textures_size()} bytes, this binding's "
                           f"{C.sizeof(ObjectTextures)}")
@@ -1058,6 +1099,46 @@ class Context:
         self._shade_scene(load().bhg_shade_scene_textured_device, (_obs_ref(obs), None if ot is None else C.byref(ot)), d_end,
                           d_end_dir, d_flags, d_object_id, n_pixels, samples, scene, params, rs, x0_shared, d_k0, d_rgba, d_rgba_f32,
                           d_scatter, stream)
+
+    def shade_scene_polarised_device(self, d_end, d_flags, n_pixels, samples, scene: "Scene", params, rs, obs, ot, pol, d_qu,
+                                     x0_shared=None, d_k0=0, d_rgba=0, d_rgba_f32=0, d_object_id=0, d_scatter=0, d_end_dir=0,
+                                     stream=0):
+        """bhg_shade_scene_polarised_device: shade_scene_textured_device with the Stokes images d_qu [n_pixels, 6] fp64 (pol:
+        Polarisation, or None = exactly the textured call)."""
+        xs = None if x0_shared is None else (C.c_double * 3)(*[float(v) for v in x0_shared])
+        _check(load().bhg_shade_scene_polarised_device(
+            self._h, C.c_void_p(d_end or None), C.c_void_p(d_end_dir or None), C.c_void_p(d_flags), C.c_void_p(d_object_id or None),
+            int(n_pixels), int(samples), C.byref(scene), None if params is None else C.byref(params),
+            None if rs is None else C.byref(rs), _obs_ref(obs), None if ot is None else C.byref(ot), xs, C.c_void_p(d_k0 or None),
+            C.c_void_p(d_rgba or None), C.c_void_p(d_rgba_f32 or None), C.c_void_p(d_scatter or None),
+            None if pol is None else C.byref(pol), C.c_void_p(d_qu or None), C.c_void_p(stream or None)))
+
+    def polarisation(self, k0, x0, params: Params, pol: Polarisation, obs, flags, end=None):
+        """bhg_polarisation_host: (evpa, degree, mu) [N] of traced rays from their camera state (k0 [N, 3], x0 [3] or [N, 3]), end
+        [N, 6] (or None) and flags [N]; obs: Observer or None (the ZAMO's screen)."""
+        k0 = np.ascontiguousarray(k0, dtype=np.float64).reshape(-1, 3)
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        n = k0.shape[0]
+        if flags.shape != (n,) or (x0.shape != (3,) and x0.shape != (n, 3)):
+            raise ValueError("flags must be [N], x0 [3] or [N, 3]")
+        e = None if end is None else np.ascontiguousarray(end, dtype=np.float64)
+        if e is not None and e.shape != (n, 6):
+            raise ValueError("end must be [N, 6]")
+        out = np.empty((3, n), np.float64)
+        _check(load().bhg_polarisation_host(self._h, C.byref(params), C.byref(pol), _obs_ref(obs), _addr(x0), 1 if x0.ndim == 1 else 0,
+                                            _addr(k0), None if e is None else _addr(e), _addr(flags), n, _addr(out[0]),
+                                            _addr(out[1]), _addr(out[2])))
+        return out[0], out[1], out[2]
+
+    def polarisation_device(self, params: Params, pol: Polarisation, obs, n, d_k0, d_flags, d_evpa, d_degree, d_mu=0,
+                            x0_shared=None, d_x0=0, d_end=0, stream=0):
+        """bhg_polarisation_device on device arrays (d_mu may be 0)."""
+        xs = None if x0_shared is None else (C.c_double * 3)(*[float(v) for v in x0_shared])
+        _check(load().bhg_polarisation_device(self._h, C.byref(params), C.byref(pol), _obs_ref(obs), xs, C.c_void_p(d_x0 or None),
+                                              C.c_void_p(d_k0), C.c_void_p(d_end or None), C.c_void_p(d_flags), int(n),
+                                              C.c_void_p(d_evpa), C.c_void_p(d_degree), C.c_void_p(d_mu or None),
+                                              C.c_void_p(stream or None)))
 
     def assemble_frame_f32_device(self, d_slabs, d_index, n_pixels, d_frame, stream=0):
         _check(load().bhg_assemble_frame_f32_device(self._h, C.c_void_p(d_slabs), C.c_void_p(d_index), int(n_pixels),

@@ -46,6 +46,7 @@ static_assert(BHG_REDSHIFT_DISK == bhg::BHG_REDSHIFT_DISK_ && BHG_REDSHIFT_OBJEC
 static_assert(sizeof(bhg_redshift) == 16, "bhg_redshift layout is part of the ABI");
 static_assert(sizeof(bhg_observer) == 24, "bhg_observer layout is part of the ABI");
 static_assert(sizeof(bhg_object_textures) == 800, "bhg_object_textures layout is part of the ABI");
+static_assert(sizeof(bhg_polarisation) == 544 && BHG_POL_TABLE_MAX == bhg::BHG_POL_TABLE_MAX_, "bhg_polarisation layout is part of the ABI");
 static_assert(BHG_OBJECT_LIT == bhg::BHG_OBJECT_LIT_ && BHG_OBJECT_EMISSIVE == bhg::BHG_OBJECT_EMISSIVE_, "object mode mismatch");
 
 namespace {
@@ -397,6 +398,45 @@ int redshift_params(const bhg_params *p, const bhg_redshift *rs, double disk_r_i
     return BHG_OK;
 }
 
+// A camera position a ZAMO tetrad exists at (include/bhgeo.h, "the observer camera"): finite, outside the horizon, and for Kerr
+// outside the ergosurface and off the BL axis.  who: the messages' prefix.  Used by the observer and polarisation checks.
+int camera_position_check(const bhg_params *p, const double *x0, const char *who)
+{
+    if (!(std::isfinite(x0[0]) && std::isfinite(x0[1]) && std::isfinite(x0[2])))
+        return fail(BHG_E_INVALID, "camera origin is not finite");
+    const double M = 0.5 * p->r_s;
+    char msg[256];
+    if (p->rhs_form == BHG_RHS_KERR_BL) {
+        const double a = p->spin, rho2 = x0[0] * x0[0] + x0[1] * x0[1] + x0[2] * x0[2], bb = rho2 - a * a;
+        const double r = std::sqrt(0.5 * (bb + std::sqrt(bb * bb + 4.0 * a * a * x0[2] * x0[2])));
+        const double r_plus = M + std::sqrt(M * M - a * a);
+        if (!(r > r_plus)) {
+            std::snprintf(msg, sizeof msg, "%s: the camera's Boyer-Lindquist r = %.17g is at or inside the horizon r_+ = %.17g",
+                          who, r, r_plus);
+            return fail(BHG_E_INVALID, msg);
+        }
+        // inside the ergoregion g_tt > 0: the start conversion's root of the null condition (the one the trace and the
+        // redshift take k^t from) is no longer the tetrad's future-directed one, so the trace would follow another photon
+        const double c = x0[2] / r, r_ergo = M + std::sqrt(M * M - a * a * c * c);
+        if (!(r > r_ergo)) {
+            std::snprintf(msg, sizeof msg, "%s: the camera's Boyer-Lindquist r = %.17g is at or inside the ergosurface "
+                          "r_E(theta) = %.17g (cos theta = %.17g)", who, r, r_ergo, c);
+            return fail(BHG_E_INVALID, msg);
+        }
+        if (x0[0] == 0.0 && x0[1] == 0.0) {
+            std::snprintf(msg, sizeof msg, "%s: a Kerr camera exactly on the axis (x = y = 0) has no azimuthal tetrad leg", who);
+            return fail(BHG_E_INVALID, msg);
+        }
+    } else {
+        const double r = std::sqrt(x0[0] * x0[0] + x0[1] * x0[1] + x0[2] * x0[2]);
+        if (!(r > p->r_s)) {
+            std::snprintf(msg, sizeof msg, "%s: the camera's r = %.17g is at or inside the horizon r_s = %.17g", who, r, p->r_s);
+            return fail(BHG_E_INVALID, msg);
+        }
+    }
+    return BHG_OK;
+}
+
 // Observer settings against the trace parameters and the camera (include/bhgeo.h, "the observer camera"): *out = the
 // kernels' parameters, on = 1.  x0 may be NULL (per-ray origins: nothing to check the position of).  Also used by
 // bhgeo_frame.hip.
@@ -417,41 +457,69 @@ int observer_params(const bhg_params *p, const bhg_observer *obs, const double *
     if (p->time_like) return fail(BHG_E_INVALID, "the observer camera makes null rays: time_like = 1 is refused");
     std::memset(out, 0, sizeof(*out));
     if (x0) {
-        if (!(std::isfinite(x0[0]) && std::isfinite(x0[1]) && std::isfinite(x0[2])))
-            return fail(BHG_E_INVALID, "camera origin is not finite");
-        const double M = 0.5 * p->r_s;
-        char msg[256];
-        if (p->rhs_form == BHG_RHS_KERR_BL) {
-            const double a = p->spin, rho2 = x0[0] * x0[0] + x0[1] * x0[1] + x0[2] * x0[2], bb = rho2 - a * a;
-            const double r = std::sqrt(0.5 * (bb + std::sqrt(bb * bb + 4.0 * a * a * x0[2] * x0[2])));
-            const double r_plus = M + std::sqrt(M * M - a * a);
-            if (!(r > r_plus)) {
-                std::snprintf(msg, sizeof msg, "observer: the camera's Boyer-Lindquist r = %.17g is at or inside the horizon r_+ = %.17g",
-                              r, r_plus);
-                return fail(BHG_E_INVALID, msg);
-            }
-            // inside the ergoregion g_tt > 0: the start conversion's root of the null condition (the one the trace and the
-            // redshift take k^t from) is no longer the tetrad's future-directed one, so the trace would follow another photon
-            const double c = x0[2] / r, r_ergo = M + std::sqrt(M * M - a * a * c * c);
-            if (!(r > r_ergo)) {
-                std::snprintf(msg, sizeof msg, "observer: the camera's Boyer-Lindquist r = %.17g is at or inside the ergosurface "
-                              "r_E(theta) = %.17g (cos theta = %.17g)", r, r_ergo, c);
-                return fail(BHG_E_INVALID, msg);
-            }
-            if (x0[0] == 0.0 && x0[1] == 0.0)
-                return fail(BHG_E_INVALID, "observer: a Kerr camera exactly on the axis (x = y = 0) has no azimuthal tetrad leg");
-        } else {
-            const double r = std::sqrt(x0[0] * x0[0] + x0[1] * x0[1] + x0[2] * x0[2]);
-            if (!(r > p->r_s)) {
-                std::snprintf(msg, sizeof msg, "observer: the camera's r = %.17g is at or inside the horizon r_s = %.17g", r, p->r_s);
-                return fail(BHG_E_INVALID, msg);
-            }
-        }
+        rc = camera_position_check(p, x0, "observer");
+        if (rc != BHG_OK) return rc;
         std::memcpy(out->x0, x0, sizeof(out->x0));
     }
     std::memcpy(out->beta, b, sizeof(out->beta));
     out->r_s = p->r_s;
     out->spin = p->rhs_form == BHG_RHS_KERR_BL ? p->spin : 0.0;
+    out->rhs = p->rhs_form;
+    out->on = 1;
+    return BHG_OK;
+}
+
+// Polarisation settings (include/bhgeo.h, "disk polarisation"): *out = the kernels' parameters, on = 1.  disk_r_in < 0: no
+// disk to check; rs: the redshift settings of the same call or NULL; obs: the observer or NULL; x0: the shared camera, or NULL
+// (per-ray origins: nothing to check the position of).
+int polarisation_params(const bhg_params *p, const bhg_polarisation *pol, const bhg_redshift *rs, const bhg_observer *obs,
+                        double disk_r_in, const double *x0, PolarisationParams *out)
+{
+    int rc = validate(p);
+    if (rc != BHG_OK) return rc;
+    if (!pol) return fail(BHG_E_INVALID, "polarisation settings are NULL");
+    if (pol->disk_sense != 1 && pol->disk_sense != -1)
+        return fail(BHG_E_INVALID, "polarisation disk_sense must be +1 or -1, not " + std::to_string(pol->disk_sense));
+    if (pol->n_degree < 1 || pol->n_degree > BHG_POL_TABLE_MAX)
+        return fail(BHG_E_INVALID, "polarisation n_degree must be in [1, 64], not " + std::to_string(pol->n_degree));
+    for (int j = 0; j < pol->n_degree; j++)
+        if (!(std::isfinite(pol->degree[j]) && pol->degree[j] >= 0.0 && pol->degree[j] <= 1.0)) {
+            char msg[160];
+            std::snprintf(msg, sizeof msg, "polarisation degree[%d] = %.17g must be finite and in [0, 1]", j, pol->degree[j]);
+            return fail(BHG_E_INVALID, msg);
+        }
+    const double *u = pol->up;
+    if (!(std::isfinite(u[0]) && std::isfinite(u[1]) && std::isfinite(u[2])) || (u[0] == 0.0 && u[1] == 0.0 && u[2] == 0.0))
+        return fail(BHG_E_INVALID, "polarisation up must be finite and not zero");
+    if (p->time_like) return fail(BHG_E_INVALID, "polarisation is defined for null rays: time_like = 1 is refused");
+    const double M = 0.5 * p->r_s, a = p->rhs_form == BHG_RHS_KERR_BL ? p->spin : 0.0, s = -(double)pol->disk_sense;
+    if (disk_r_in >= 0.0) {
+        // section 9's rule: no timelike circular orbit at or inside the photon orbit of the traced picture's sense
+        const double r_ph = p->rhs_form == BHG_RHS_KERR_BL ? 2.0 * M * (1.0 + std::cos(2.0 / 3.0 * std::acos(-s * a / M))) : 3.0 * M;
+        const double r_in = std::sqrt(std::max(disk_r_in * disk_r_in - a * a, 0.0));
+        if (!(r_in > r_ph)) {
+            char msg[220];
+            std::snprintf(msg, sizeof msg, "polarisation: disk_r_in %.17g (Boyer-Lindquist r %.17g) is at or inside the circular photon "
+                          "orbit r_ph = %.17g of disk_sense %d", disk_r_in, r_in, r_ph, pol->disk_sense);
+            return fail(BHG_E_INVALID, msg);
+        }
+    }
+    if (rs && rs->disk_sense != pol->disk_sense)
+        return fail(BHG_E_INVALID, "polarisation disk_sense " + std::to_string(pol->disk_sense) + " differs from the redshift's " +
+                                   std::to_string(rs->disk_sense));
+    if (x0) {
+        rc = camera_position_check(p, x0, "polarisation");
+        if (rc != BHG_OK) return rc;
+    }
+    std::memset(out, 0, sizeof(*out));
+    std::memcpy(out->degree, pol->degree, sizeof(double) * (size_t)pol->n_degree);
+    std::memcpy(out->up, pol->up, sizeof(out->up));
+    if (x0) std::memcpy(out->x0, x0, sizeof(out->x0));
+    if (obs) std::memcpy(out->beta, obs->beta, sizeof(out->beta));
+    out->r_s = p->r_s;
+    out->spin = a;
+    out->sense = (double)pol->disk_sense;
+    out->n_degree = pol->n_degree;
     out->rhs = p->rhs_form;
     out->on = 1;
     return BHG_OK;
@@ -542,6 +610,7 @@ size_t bhg_frame_scene_size(void) { return sizeof(bhg_frame_scene); }
 size_t bhg_redshift_size(void) { return sizeof(bhg_redshift); }
 size_t bhg_observer_size(void) { return sizeof(bhg_observer); }
 size_t bhg_object_textures_size(void) { return sizeof(bhg_object_textures); }
+size_t bhg_polarisation_size(void) { return sizeof(bhg_polarisation); }
 
 int bhg_abi_check(int abi_version, size_t params_size, size_t camera_size, size_t scene_size, size_t frame_scene_size)
 {
@@ -1354,15 +1423,16 @@ int raygen_impl(bhg_context *c, int32_t width, int32_t height, int32_t samples, 
 //      r_out > r_in, stddev > 0 and a texture size > 0; sphere radii > 0
 //   2. the object-texture table, when given, against n_spheres
 //   3. redshift, when rs->apply != 0: x0_shared, the settings, and the observer when given
+//   3b. polarisation, when pol is given: x0_shared, the settings (against p, the scene's disk, the redshift's sense, the camera)
 //   4. the context
 //   5. n_pixels == 0 is BHG_OK: an EMPTY shard -- a rank without pixels: fewer tiles than ranks -- has no rays and no
 //      arrays, so no device array is looked at
 //   6. the device arrays: an output, end or end_dir, flags, the sky; end for a disk or spheres; object_id for spheres;
-//      k0 for redshift
+//      k0 for redshift; qu and k0 for polarisation
 int shade(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags, const int8_t *d_object_id,
           size_t n_pixels, int32_t samples, const bhg_scene *sc, const bhg_params *p, const bhg_redshift *rs,
           const bhg_observer *obs, const bhg_object_textures *ot, const double *x0_shared, const double *d_k0, double *d_rgba,
-          float *d_rgba_f32, const int64_t *d_scatter, void *stream)
+          float *d_rgba_f32, const int64_t *d_scatter, const bhg_polarisation *pol, double *d_qu, void *stream)
 {
     if (!sc) return fail(BHG_E_INVALID, "scene is NULL");
     if (samples <= 0 || sc->sky_w <= 0 || sc->sky_h <= 0) return fail(BHG_E_INVALID, "samples, sky_w, sky_h must be > 0");
@@ -1393,6 +1463,17 @@ int shade(bhg_context *c, const double *d_end, const double *d_end_dir, const ui
             if (rc != BHG_OK) return rc;
         }
     }
+    bhg::PolarisationParams pp;
+    if (pol) {
+        if (!x0_shared) return fail(BHG_E_INVALID, "polarisation needs the shared camera origin x0_shared");
+        int rc = bhg::polarisation_params(p, pol, on ? rs : nullptr, obs, has_disk ? sc->disk_r_in : -1.0, x0_shared, &pp);
+        if (rc != BHG_OK) return rc;
+        if (obs) {
+            bhg::ObserverParams chk;
+            rc = bhg::observer_params(p, obs, x0_shared, &chk);
+            if (rc != BHG_OK) return rc;
+        }
+    }
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
     if (n_pixels == 0) return BHG_OK;
     if ((!d_rgba && !d_rgba_f32) || (!d_end && !d_end_dir) || !d_flags || !sc->d_sky)
@@ -1401,6 +1482,7 @@ int shade(bhg_context *c, const double *d_end, const double *d_end_dir, const ui
         return fail(BHG_E_INVALID, "d_end is NULL: a direction-only frame cannot have a disk or object spheres");
     if (sc->n_spheres > 0 && !d_object_id) return fail(BHG_E_INVALID, "object_id is NULL but the scene has spheres");
     if (on && !d_k0) return fail(BHG_E_INVALID, "redshift needs the camera directions d_k0");
+    if (pol && (!d_qu || !d_k0)) return fail(BHG_E_INVALID, "polarisation needs d_qu and the camera directions d_k0");
     ENTER_DEVICE(c->device);
     bhg::ShadeArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -1436,6 +1518,11 @@ int shade(bhg_context *c, const double *d_end, const double *d_end_dir, const ui
     std::memcpy(a.sphere_rgb, sc->sphere_rgb, sizeof(a.sphere_rgb));
     std::memcpy(a.lamps, sc->lamps, sizeof(a.lamps));
     if (ot) a.ot = tp;
+    if (pol) {
+        a.pol = pp;
+        a.pol.qu = d_qu;
+        a.k0 = d_k0;
+    }
     HIP_TRY(bhg::launch_shade(a, (hipStream_t)stream));
     return BHG_OK;
 }
@@ -1479,7 +1566,7 @@ int bhg_shade_device(bhg_context *c, const double *d_end, const uint8_t *d_flags
 {
     const bhg_scene sc = sky_scene(d_sky, sky_w, sky_h);
     return shade(c, d_end, nullptr, d_flags, nullptr, n_pixels, samples, &sc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                 d_rgba, nullptr, nullptr, stream);
+                 d_rgba, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int bhg_shade_dir_device(bhg_context *c, const double *d_end_dir, const uint8_t *d_flags, size_t n_pixels, int32_t samples,
@@ -1488,14 +1575,14 @@ int bhg_shade_dir_device(bhg_context *c, const double *d_end_dir, const uint8_t 
 {
     const bhg_scene sc = sky_scene(d_sky, sky_w, sky_h);
     return shade(c, nullptr, d_end_dir, d_flags, nullptr, n_pixels, samples, &sc, nullptr, nullptr, nullptr, nullptr, nullptr,
-                 nullptr, d_rgba, d_rgba_f32, d_scatter, stream);
+                 nullptr, d_rgba, d_rgba_f32, d_scatter, nullptr, nullptr, stream);
 }
 
 int bhg_shade_scene_device(bhg_context *c, const double *d_end, const uint8_t *d_flags, const int8_t *d_object_id,
                            size_t n_pixels, int32_t samples, const bhg_scene *sc, double *d_rgba, void *stream)
 {
     return shade(c, d_end, nullptr, d_flags, d_object_id, n_pixels, samples, sc, nullptr, nullptr, nullptr, nullptr, nullptr,
-                 nullptr, d_rgba, nullptr, nullptr, stream);
+                 nullptr, d_rgba, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int bhg_shade_scene_f32_device(bhg_context *c, const double *d_end, const uint8_t *d_flags, const int8_t *d_object_id,
@@ -1503,7 +1590,7 @@ int bhg_shade_scene_f32_device(bhg_context *c, const double *d_end, const uint8_
                                const int64_t *d_scatter, void *stream)
 {
     return shade(c, d_end, nullptr, d_flags, d_object_id, n_pixels, samples, sc, nullptr, nullptr, nullptr, nullptr, nullptr,
-                 nullptr, nullptr, d_rgba_f32, d_scatter, stream);
+                 nullptr, nullptr, d_rgba_f32, d_scatter, nullptr, nullptr, stream);
 }
 
 int bhg_shade_scene_redshift_device(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
@@ -1512,7 +1599,7 @@ int bhg_shade_scene_redshift_device(bhg_context *c, const double *d_end, const d
                                     double *d_rgba, float *d_rgba_f32, const int64_t *d_scatter, void *stream)
 {
     return shade(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs, nullptr, nullptr, x0_shared, d_k0,
-                 d_rgba, d_rgba_f32, d_scatter, stream);
+                 d_rgba, d_rgba_f32, d_scatter, nullptr, nullptr, stream);
 }
 
 int bhg_shade_scene_redshift_observer_device(bhg_context *c, const double *d_end, const double *d_end_dir,
@@ -1523,7 +1610,7 @@ int bhg_shade_scene_redshift_observer_device(bhg_context *c, const double *d_end
                                              const int64_t *d_scatter, void *stream)
 {
     return shade(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs, obs, nullptr, x0_shared, d_k0, d_rgba,
-                 d_rgba_f32, d_scatter, stream);
+                 d_rgba_f32, d_scatter, nullptr, nullptr, stream);
 }
 
 int bhg_shade_scene_textured_device(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
@@ -1532,8 +1619,91 @@ int bhg_shade_scene_textured_device(bhg_context *c, const double *d_end, const d
                                     const bhg_object_textures *ot, const double *x0_shared, const double *d_k0, double *d_rgba,
                                     float *d_rgba_f32, const int64_t *d_scatter, void *stream)
 {
+    return bhg_shade_scene_polarised_device(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs, obs, ot,
+                                            x0_shared, d_k0, d_rgba, d_rgba_f32, d_scatter, nullptr, nullptr, stream);
+}
+
+int bhg_shade_scene_polarised_device(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
+                                     const int8_t *d_object_id, size_t n_pixels, int32_t samples, const bhg_scene *sc,
+                                     const bhg_params *p, const bhg_redshift *rs, const bhg_observer *obs,
+                                     const bhg_object_textures *ot, const double *x0_shared, const double *d_k0, double *d_rgba,
+                                     float *d_rgba_f32, const int64_t *d_scatter, const bhg_polarisation *pol, double *d_qu,
+                                     void *stream)
+{
     return shade(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs, obs, ot, x0_shared, d_k0, d_rgba,
-                 d_rgba_f32, d_scatter, stream);
+                 d_rgba_f32, d_scatter, pol, d_qu, stream);
+}
+
+int bhg_polarisation_device(bhg_context *c, const bhg_params *p, const bhg_polarisation *pol, const bhg_observer *obs,
+                            const double *x0_shared, const double *d_x0, const double *d_k0, const double *d_end,
+                            const uint8_t *d_flags, size_t n, double *d_evpa, double *d_degree, double *d_mu, void *stream)
+{
+    // (the settings are checked before the context: a refusal names its figure with or without a device)
+    bhg::PolarisationParams pp;
+    int rc = bhg::polarisation_params(p, pol, nullptr, obs, p && p->disk_r_out > 0.0 ? p->disk_r_in : -1.0, x0_shared, &pp);
+    if (rc != BHG_OK) return rc;
+    if (obs) {
+        bhg::ObserverParams chk;
+        rc = bhg::observer_params(p, obs, x0_shared, &chk);
+        if (rc != BHG_OK) return rc;
+    }
+    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
+    if (!x0_shared == !d_x0) return fail(BHG_E_INVALID, "exactly one of x0_shared / d_x0 must be given");
+    if (n == 0) return BHG_OK;
+    if (!d_k0 || !d_flags || !d_evpa || !d_degree) return fail(BHG_E_INVALID, "d_k0 / d_flags / d_evpa / d_degree is NULL");
+    if (n > ((size_t)1 << 39)) return fail(BHG_E_INVALID, "n too large for one launch (at most 2^39 rays)");
+    ENTER_DEVICE(c->device);
+    bhg::PolarisationArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.p = pp;
+    a.x0 = d_x0;
+    a.k0 = d_k0;
+    a.end = d_end;
+    a.flags = d_flags;
+    a.evpa = d_evpa;
+    a.degree = d_degree;
+    a.mu = d_mu;
+    a.n = n;
+    HIP_TRY(bhg::launch_polarisation(a, obs != nullptr, (hipStream_t)stream));
+    return BHG_OK;
+}
+
+int bhg_polarisation_host(bhg_context *c, const bhg_params *p, const bhg_polarisation *pol, const bhg_observer *obs,
+                          const double *x0, int x0_is_shared, const double *k0, const double *end, const uint8_t *flags, size_t n,
+                          double *evpa, double *degree, double *mu)
+{
+    bhg::PolarisationParams pp;   // (checked here too, before the context and before any copy)
+    int rc = bhg::polarisation_params(p, pol, nullptr, obs, p && p->disk_r_out > 0.0 ? p->disk_r_in : -1.0,
+                                      x0_is_shared ? x0 : nullptr, &pp);
+    if (rc != BHG_OK) return rc;
+    if (obs) {
+        bhg::ObserverParams chk;
+        rc = bhg::observer_params(p, obs, x0_is_shared ? x0 : nullptr, &chk);
+        if (rc != BHG_OK) return rc;
+    }
+    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
+    if (!x0) return fail(BHG_E_INVALID, "x0 is NULL");
+    if (n == 0) return BHG_OK;
+    if (!k0 || !flags || !evpa || !degree) return fail(BHG_E_INVALID, "k0 / flags / evpa / degree is NULL");
+    ENTER_DEVICE(c->device);
+    // one block: [x0 (per ray)][k0][end][evpa][degree][mu] doubles, then the flags
+    const size_t nx = x0_is_shared ? 0 : n * 3, ne = end ? n * 6 : 0;
+    rc = ensure(&c->d_in, &c->d_in_bytes, (nx + n * 3 + ne + n * 3) * sizeof(double) + n);
+    if (rc != BHG_OK) return rc;
+    double *dx = (double *)c->d_in, *dk = dx + nx, *de = dk + n * 3, *dc = de + ne, *dd = dc + n, *dm = dd + n;
+    uint8_t *df = (uint8_t *)(dm + n);
+    if (nx) HIP_TRY(hipMemcpyAsync(dx, x0, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dk, k0, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (ne) HIP_TRY(hipMemcpyAsync(de, end, ne * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(df, flags, n, hipMemcpyHostToDevice, c->stream));
+    rc = bhg_polarisation_device(c, p, pol, obs, x0_is_shared ? x0 : nullptr, nx ? dx : nullptr, dk, ne ? de : nullptr, df, n, dc, dd,
+                                 dm, c->stream);
+    if (rc != BHG_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(evpa, dc, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(degree, dd, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (mu) HIP_TRY(hipMemcpyAsync(mu, dm, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return BHG_OK;
 }
 
 int bhg_redshift_device(bhg_context *c, const bhg_params *p, const bhg_redshift *rs, const double *x0_shared,

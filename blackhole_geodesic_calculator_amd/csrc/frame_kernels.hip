@@ -417,6 +417,232 @@ __global__ void __launch_bounds__(256) redshift_kernel(const RedshiftArgs A)
     A.g[i] = observer_g<OBS>(A.p, A.obs, xc, A.k0 + i * 3, ray_class(A.flags[i]), A.end ? A.end + i * 6 : nullptr);
 }
 
+// ---- disk polarisation -----------------------------------------------------------------------
+// The Walker-Penrose constant kappa = (A - i B)(r - i a cos th) of the traced ray k and a vector f, BL components (t, r, th, ph):
+//     A = (k^t f^r - k^r f^t) + a sin^2 th (k^r f^ph - k^ph f^r),  B = [(r^2 + a^2)(k^ph f^th - k^th f^ph) - a (k^t f^th - k^th f^t)] sin th
+__device__ __forceinline__ void kappa_bl(double r, double st, double ct, double a, const double k[4], const double f[4], double &re,
+                                         double &im)
+{
+    const double A = (k[0] * f[1] - k[1] * f[0]) + a * st * st * (k[1] * f[3] - k[3] * f[1]);
+    const double B = ((r * r + a * a) * (k[3] * f[2] - k[2] * f[3]) - a * (k[0] * f[2] - k[2] * f[0])) * st;
+    const double ac = a * ct;
+    re = A * r - B * ac;
+    im = -(A * ac + B * r);
+}
+
+// a = 0 in the Cartesian layout x = r n^ of Schwarzschild coordinates: kappa = r [(k^t f.n^ - k.n^ f^t) - i n^.(f x k)]
+__device__ __forceinline__ void kappa_cart(double rc, const double n[3], double kt, const double k[3], const double f[4], double &re,
+                                           double &im)
+{
+    const double A = kt * (n[0] * f[1] + n[1] * f[2] + n[2] * f[3]) - (n[0] * k[0] + n[1] * k[1] + n[2] * k[2]) * f[0];
+    const double B = n[0] * (f[2] * k[2] - f[3] * k[1]) + n[1] * (f[3] * k[0] - f[1] * k[2]) + n[2] * (f[1] * k[1] - f[2] * k[0]);
+    re = A * rc;
+    im = -B * rc;
+}
+
+// The screen legs of a ray whose look direction in the ZAMO frame is n (world axes): e_up = normalise(up - (up.n') n'),
+// e_left = e_up x n', n' the observer's rest-frame direction (OBS: de-aberrated, aberrate with -beta).  In the traced picture
+// the observer moves with -beta, so each leg X is lifted by that boost, X^0 = -gamma beta.X, X + gamma^2 / (gamma + 1) (beta.X)
+// beta: both legs are then orthogonal to k.  X[0..3] = (X^0, world-axis X) of e_left, X[4..7] of e_up.  false: up is along n'.
+template <bool OBS>
+__device__ __forceinline__ bool screen_legs(const PolarisationParams &P, const double n_in[3], double X[8])
+{
+    double n[3] = {n_in[0], n_in[1], n_in[2]};
+    const double *b = P.beta;
+    double gamma = 1.0, c = 0.0;
+    if (OBS) {
+        gamma = 1.0 / sqrt(1.0 - (b[0] * b[0] + b[1] * b[1] + b[2] * b[2]));
+        c = gamma * gamma / (gamma + 1.0);
+        const double nb[3] = {-b[0], -b[1], -b[2]};
+        aberrate(nb, gamma, c, n_in, n);
+        const double in = 1.0 / sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+        n[0] *= in;
+        n[1] *= in;
+        n[2] *= in;
+    }
+    const double *up = P.up;
+    const double un = up[0] * n[0] + up[1] * n[1] + up[2] * n[2];
+    const double w[3] = {up[0] - un * n[0], up[1] - un * n[1], up[2] - un * n[2]};
+    const double wn = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+    if (!(wn > 1e-12 * sqrt(up[0] * up[0] + up[1] * up[1] + up[2] * up[2]))) return false;
+    const double eu[3] = {w[0] / wn, w[1] / wn, w[2] / wn};
+    const double el[3] = {eu[1] * n[2] - eu[2] * n[1], eu[2] * n[0] - eu[0] * n[2], eu[0] * n[1] - eu[1] * n[0]};
+    for (int l = 0; l < 2; l++) {
+        const double *e = l ? eu : el;
+        double *x = X + 4 * l;
+        if (OBS) {
+            const double be = b[0] * e[0] + b[1] * e[1] + b[2] * e[2];
+            x[0] = -gamma * be;
+            x[1] = e[0] + c * be * b[0];
+            x[2] = e[1] + c * be * b[1];
+            x[3] = e[2] + c * be * b[2];
+        } else {
+            x[0] = 0.0;
+            x[1] = e[0];
+            x[2] = e[1];
+            x[3] = e[2];
+        }
+    }
+    return true;
+}
+
+// The degree table at mu (clamped to [0, 1]), linear between mu_j = j / (n - 1); one entry: a constant
+__device__ __forceinline__ double pol_degree(const PolarisationParams &P, double mu)
+{
+    const int n = P.n_degree;
+    if (n <= 1) return P.degree[0];
+    const double x = fmin(fmax(mu, 0.0), 1.0) * (double)(n - 1);
+    int j = (int)x;
+    j = j > n - 2 ? n - 2 : j;
+    const double t = x - (double)j;
+    return P.degree[j] + t * (P.degree[j + 1] - P.degree[j]);
+}
+
+// One disk ray ending at e (its end record: position, direction) from the camera state (xc, kc): the emission cosine mu and
+// the screen coefficients (c_L, c_U) of the emitted polarisation, both times the same nonzero factor (the 2x2 solve's
+// determinant, so chi = atan2(c_L, c_U) mod pi needs no division).  false: the screen is degenerate (up along the ray); mu is
+// set either way (it does not depend on the screen).  c_L = c_U = 0: f = 0, the photon leaves along the disk normal (mu = 1).
+// The camera: Kerr E, L from kerr_cart_to_bl (the trace's own), Carter Q = k_th^2 + cos^2 th (L^2 / sin^2 th - a^2 E^2);
+// Schwarzschild E = f k^t, the angular-momentum vector x x k.  The emitter: k rebuilt at the equator, BL r_h = sqrt(R^2 - a^2),
+// from those constants with only the signs of k^r and k^th from the end record (the integrator's drift stays out);
+// u Keplerian of sense s = -disk_sense (section 9); f = the vector orthogonal to u, e_th and k, which is the fluid frame's
+// z^ x n_f: f^th = 0, f^t = u_ph g_rr k^r, f^r = E u_ph + L u_t, f^ph = -u_t g_rr k^r.
+template <bool OBS>
+__device__ bool polarisation_disk(const PolarisationParams &P, const double xc[3], const double kc[3], const double *e, double &cL,
+                                  double &cU, double &mu)
+{
+    const double M = 0.5 * P.r_s, s = -P.sense;
+    double a, E, L, Q, n[3], X[8], kl[2] = {0.0, 0.0}, ku[2] = {0.0, 0.0};
+    bool legs;
+    if (P.rhs == BHG_RHS_KERR_BL_) {
+        a = P.spin;
+        const double a2 = a * a;
+        double px[3] = {xc[0], xc[1], xc[2]}, pk[3] = {kc[0], kc[1], kc[2]};
+        kerr_cart_to_bl(a, M, 0.0, px, pk, E, L);
+        const double r = px[0];
+        double st, ct, alpha, omega;
+        sincos_pi4(px[1], st, ct);
+        kerr_zamo(M, a, r, ct * ct, alpha, omega);
+        const double iw = rsqrt_nr(__builtin_fma(xc[1], xc[1], xc[0] * xc[0])), cp = xc[0] * iw, sp = xc[1] * iw;
+        const double Sig = __builtin_fma(a2 * ct, ct, r * r), Del = __builtin_fma(-2.0 * M, r, r * r + a2);
+        const double R2 = r * r + a2, Aq = R2 * R2 - a2 * Del * st * st;
+        const double kt = (E - omega * L) / (alpha * alpha);
+        const double kth = Sig * pk[1];
+        Q = kth * kth + ct * ct * (L * L / (st * st) - a2 * E * E);
+        const double sSD = sqrt(Sig / Del), sS = sqrt(Sig), sAS = sqrt(Aq / Sig);
+        const double nr = sSD * pk[0], nt = sS * pk[1], np = sAS * st * (pk[2] - omega * kt);
+        const double rh[3] = {st * cp, st * sp, ct}, th[3] = {ct * cp, ct * sp, -st}, ph[3] = {-sp, cp, 0.0};
+        const double inn = 1.0 / sqrt(nr * nr + nt * nt + np * np);
+        for (int j = 0; j < 3; j++) n[j] = (nr * rh[j] + nt * th[j] + np * ph[j]) * inn;
+        legs = screen_legs<OBS>(P, n, X);
+        const double k4[4] = {kt, pk[0], pk[1], pk[2]};
+        for (int l = 0; legs && l < 2; l++) {
+            const double *x = X + 4 * l;
+            const double xr = x[1] * rh[0] + x[2] * rh[1] + x[3] * rh[2];
+            const double xt = x[1] * th[0] + x[2] * th[1] + x[3] * th[2];
+            const double xp = x[1] * ph[0] + x[2] * ph[1];
+            const double f4[4] = {x[0] / alpha, xr / sSD, xt / sS, x[0] * omega / alpha + xp / (sAS * st)};
+            kappa_bl(r, st, ct, a, k4, f4, l ? ku[0] : kl[0], l ? ku[1] : kl[1]);
+        }
+    } else {
+        a = 0.0;
+        const double rc = sqrt(xc[0] * xc[0] + xc[1] * xc[1] + xc[2] * xc[2]), ir = 1.0 / rc;
+        const double rh[3] = {xc[0] * ir, xc[1] * ir, xc[2] * ir};
+        const double f = 1.0 - P.r_s * ir, h = P.r_s / (rc - P.r_s), sf = sqrt(f);
+        const double nk = rh[0] * kc[0] + rh[1] * kc[1] + rh[2] * kc[2];
+        const double kk = kc[0] * kc[0] + kc[1] * kc[1] + kc[2] * kc[2];
+        const double kt = sqrt((kk + h * nk * nk) / f);
+        E = f * kt;
+        const double Lx = xc[1] * kc[2] - xc[2] * kc[1], Ly = xc[2] * kc[0] - xc[0] * kc[2];
+        L = xc[0] * kc[1] - xc[1] * kc[0];
+        Q = Lx * Lx + Ly * Ly;
+        const double q = (1.0 / sf - 1.0) * nk;
+        const double m[3] = {kc[0] + q * rh[0], kc[1] + q * rh[1], kc[2] + q * rh[2]};
+        const double inn = 1.0 / sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]);
+        for (int j = 0; j < 3; j++) n[j] = m[j] * inn;
+        legs = screen_legs<OBS>(P, n, X);
+        for (int l = 0; legs && l < 2; l++) {
+            const double *x = X + 4 * l;
+            const double xr = (1.0 - sf) * (x[1] * rh[0] + x[2] * rh[1] + x[3] * rh[2]);
+            const double f4[4] = {x[0] / sf, x[1] - xr * rh[0], x[2] - xr * rh[1], x[3] - xr * rh[2]};
+            kappa_cart(rc, rh, kt, kc, f4, l ? ku[0] : kl[0], l ? ku[1] : kl[1]);
+        }
+    }
+    // the emitter, at the equator
+    const double a2 = a * a;
+    const double r = sqrt(e[0] * e[0] + e[1] * e[1] - a2), r2 = r * r, ir2 = 1.0 / r2;
+    const double sr = (e[0] * e[3] + e[1] * e[4]) < 0.0 ? -1.0 : 1.0, sth = e[5] > 0.0 ? -1.0 : 1.0;
+    const double Del = r2 - 2.0 * M * r + a2, Pp = (r2 + a2) * E - a * L, aEL = a * E - L;
+    const double kt = (-a * aEL + (r2 + a2) * Pp / Del) * ir2;
+    const double kp = (-aEL + a * Pp / Del) * ir2;
+    const double kr = sr * sqrt(fmax(Pp * Pp - Del * (Q + aEL * aEL), 0.0)) * ir2;
+    const double kth = sth * sqrt(fmax(Q, 0.0)) * ir2;
+    const double sq = sqrt(r), r32 = r * sq, saM = s * a * sqrt(M);
+    const double Om = s * sqrt(M) / (r32 + saM);
+    const double ut = (r32 + saM) / (sqrt(r32) * sqrt(r32 - 3.0 * M * sq + 2.0 * saM)), up = Om * ut;
+    const double gtt = -(1.0 - 2.0 * M / r), gtp = -2.0 * M * a / r, gpp = r2 + a2 + 2.0 * M * a2 / r, grr = r2 / Del;
+    const double u_t = gtt * ut + gtp * up, u_p = gtp * ut + gpp * up;
+    mu = fabs(r * kth) / (E * ut - L * up);
+    const double ft = u_p * grr * kr, fr = E * u_p + L * u_t, fp = -u_t * grr * kr;
+    const double A = (kt * fr - kr * ft) + a * (kr * fp - kp * fr);
+    const double B = kth * (a * ft - (r2 + a2) * fp);
+    const double re = A * r, im = -B * r;
+    // re + i im = c_L kappa_L + c_U kappa_U, Cramer's rule without the division by the determinant
+    cL = re * ku[1] - ku[0] * im;
+    cU = kl[0] * im - re * kl[1];
+    return legs;
+}
+
+// (chi, delta, mu) of one ray: disk rays their own, NaN rays (and disk rays without an end record) NaN, every other ray 0
+template <bool OBS>
+__device__ void polarisation_ray(const PolarisationParams &P, const double xc[3], const double kc[3], int cls, const double *e,
+                                 double out[3])
+{
+    if (cls != RS_DISK || !e) {
+        const double v = (cls == RS_NAN || cls == RS_DISK) ? __builtin_nan("") : 0.0;
+        out[0] = out[1] = out[2] = v;
+        return;
+    }
+    double cL, cU, mu;
+    const bool ok = polarisation_disk<OBS>(P, xc, kc, e, cL, cU, mu);
+    double chi = __builtin_nan("");      // no screen, or f = 0: no direction
+    if (ok && (cL != 0.0 || cU != 0.0)) {
+        chi = atan2(cL, cU);
+        chi = chi > 0.5 * M_PI ? chi - M_PI : (chi <= -0.5 * M_PI ? chi + M_PI : chi);
+    }
+    out[0] = chi;
+    out[1] = pol_degree(P, mu);
+    out[2] = mu;
+}
+
+template <bool OBS>
+__global__ void __launch_bounds__(256) polarisation_kernel(const PolarisationArgs A)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= A.n) return;
+    const double *xc = A.x0 ? A.x0 + i * 3 : A.p.x0;
+    double o[3];
+    polarisation_ray<OBS>(A.p, xc, A.k0 + i * 3, ray_class(A.flags[i]), A.end ? A.end + i * 6 : nullptr, o);
+    A.evpa[i] = o[0];
+    A.degree[i] = o[1];
+    if (A.mu) A.mu[i] = o[2];
+}
+
+// the shade kernels' polarised instances: (delta cos 2chi, delta sin 2chi) of a disk ray, (0, 0) where the per-ray chi is NaN
+// (a degenerate screen, or f = 0)
+// (cos 2chi = (c_U^2 - c_L^2) / (c_U^2 + c_L^2), sin 2chi = 2 c_L c_U / (c_U^2 + c_L^2): no trigonometry).  The observer's beta
+// is zero without one, where the boost and the lift are exact identities.
+__device__ __forceinline__ void polarisation_weigh(const ShadeArgs &A, uint64_t i, const double *e, double qu[2])
+{
+    double cL, cU, mu;
+    if (!polarisation_disk<true>(A.pol, A.pol.x0, A.k0 + i * 3, e, cL, cU, mu)) return;
+    const double den = cU * cU + cL * cL;
+    if (!(den > 0.0)) return;     // f = 0: the photon leaves along the disk normal, mu = 1 (chi NaN per ray)
+    const double d = pol_degree(A.pol, mu) / den;
+    qu[0] = d * (cU * cU - cL * cL);
+    qu[1] = d * (2.0 * cL * cU);
+}
+
 // the shade kernels' redshift instances: rgb *= g^n for a ray of a class the caller selected (OBS: the moving observer's g)
 template <bool OBS>
 __device__ __forceinline__ void redshift_weigh(const ShadeArgs &A, uint64_t i, int cls, uint32_t bit, const double *e, double rgb[3])
@@ -435,15 +661,19 @@ __device__ __forceinline__ void redshift_weigh(const ShadeArgs &A, uint64_t i, i
 // sky in its exit direction.
 // RS: the redshift instance (rgb *= g^n by class); without it the kernels are the frame path's as they were.  OBS (with RS
 // only): g is the moving observer's.  TEX: object rays take the textured colour (object_colour_tex); nothing else differs.
-template <bool RS, bool OBS, bool TEX>
-__device__ __forceinline__ void ray_colour(const ShadeArgs &A, uint64_t i, uint8_t fl, double c0, double c1, double c2, double rgb[3])
+// POL: a disk ray also gets its Stokes weights qu = (delta cos 2chi, delta sin 2chi), every other ray (0, 0); rgb is untouched.
+template <bool RS, bool OBS, bool TEX, bool POL>
+__device__ __forceinline__ void ray_colour(const ShadeArgs &A, uint64_t i, uint8_t fl, double c0, double c1, double c2, double rgb[3],
+                                           double qu[2])
 {
     rgb[0] = rgb[1] = rgb[2] = 0.0;
+    if (POL) qu[0] = qu[1] = 0.0;
     if (fl & BHG_FLAG_HIT_HORIZON_) return;
     const double *e = A.end + i * 6;
     if (fl == BHG_FLAG_HIT_DISK_ && A.disk_r_out > 0.0 && A.end) {
         disk_colour(A, e, rgb);
         if (RS) redshift_weigh<OBS>(A, i, RS_DISK, BHG_REDSHIFT_DISK_, e, rgb);
+        if (POL) polarisation_weigh(A, i, e, qu);
         return;
     }
     if (fl == BHG_FLAG_HIT_OBJECT_ && A.object_id && A.end) {
@@ -482,16 +712,29 @@ __device__ __forceinline__ void write_pixel(const ShadeArgs &A, uint64_t p, cons
     }
 }
 
+// the per-pixel means of (Q_r, Q_g, Q_b, U_r, U_g, U_b), at pixel p (never scattered)
+__device__ __forceinline__ void write_stokes(const ShadeArgs &A, uint64_t p, const double acc[6])
+{
+    const double inv_s = 1.0 / (double)A.samples;
+    double2 *o = reinterpret_cast<double2 *>(A.pol.qu + p * 6);
+    o[0] = make_double2(acc[0] * inv_s, acc[1] * inv_s);
+    o[1] = make_double2(acc[2] * inv_s, acc[3] * inv_s);
+    o[2] = make_double2(acc[4] * inv_s, acc[5] * inv_s);
+}
+
 // One thread per RAY, the S samples of a pixel staged in LDS and summed by one thread in sample order (:242-250: sbuf +=
 // colour, sample after sample -- the order is part of the result).  A workgroup of 256 threads takes PPB = 256 / S
 // pixels; thread t = s * PPB + q is sample s of the block's q-th pixel, so that for a fixed s the block reads PPB
 // consecutive rays of the [S][P] layout (coalesced).  Against one thread per pixel walking its samples one after the
 // other (round 3; kept below for S > 256) this puts S times as many independent atan2 / texel-gather chains in flight:
 // the kernel is a latency chain per ray, not a bandwidth problem (131 MB in, 16 MB out per config-2 frame).
-template <bool RS, bool OBS, bool TEX>
+// POL: each thread also stages the six Stokes products (Q, then U, of each channel; 9 doubles per thread in all, 18 KB per
+// workgroup) and the pixel's Q / U means go to pol.qu[p].
+template <bool RS, bool OBS, bool TEX, bool POL>
 __global__ void __launch_bounds__(256) shade_reduce_kernel(const ShadeArgs A, const uint32_t ppb)
 {
     __shared__ double col[256 * 3];
+    __shared__ double pcol[POL ? 256 * 6 : 1];
     const uint32_t t = threadIdx.x, S = (uint32_t)A.samples;
     const uint32_t s = t / ppb, q = t - s * ppb;
     const uint64_t p = (uint64_t)blockIdx.x * ppb + q;
@@ -501,7 +744,16 @@ __global__ void __launch_bounds__(256) shade_reduce_kernel(const ShadeArgs A, co
         // exit directions: the second half of the end records, or (direction-only traces of sky frames) an array of their own
         const double *d = A.dir ? A.dir + i * 3 : A.end + i * 6 + 3;
         double rgb[3];
-        ray_colour<RS, OBS, TEX>(A, i, A.flags[i], d[0], d[1], d[2], rgb);
+        if (POL) {
+            double qu[2];
+            ray_colour<RS, OBS, TEX, POL>(A, i, A.flags[i], d[0], d[1], d[2], rgb, qu);
+            for (int c = 0; c < 3; c++) {
+                pcol[t * 6 + c] = qu[0] * rgb[c];
+                pcol[t * 6 + 3 + c] = qu[1] * rgb[c];
+            }
+        } else {
+            ray_colour<RS, OBS, TEX, POL>(A, i, A.flags[i], d[0], d[1], d[2], rgb, nullptr);
+        }
         col[t * 3 + 0] = rgb[0];
         col[t * 3 + 1] = rgb[1];
         col[t * 3 + 2] = rgb[2];
@@ -517,26 +769,41 @@ __global__ void __launch_bounds__(256) shade_reduce_kernel(const ShadeArgs A, co
             acc[2] += c[2];
         }
         write_pixel(A, p, acc);
+        if (POL) {
+            double pacc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            for (uint32_t k = 0; k < S; k++) {
+                const double *c = pcol + (size_t)(k * ppb + q) * 6;
+                for (int m = 0; m < 6; m++) pacc[m] += c[m];
+            }
+            write_stokes(A, p, pacc);
+        }
     }
 }
 
 // More samples than a workgroup has threads: one thread per pixel, samples accumulated in registers in sample order.
-template <bool RS, bool OBS, bool TEX>
+template <bool RS, bool OBS, bool TEX, bool POL>
 __global__ void __launch_bounds__(256) shade_reduce_serial_kernel(const ShadeArgs A)
 {
     const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= A.n_pixels) return;
     double acc[3] = {0.0, 0.0, 0.0};
+    double pacc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int s = 0; s < A.samples; s++) {
         const uint64_t i = (uint64_t)s * A.n_pixels + p;
         const double *d = A.dir ? A.dir + i * 3 : A.end + i * 6 + 3;
-        double rgb[3];
-        ray_colour<RS, OBS, TEX>(A, i, A.flags[i], d[0], d[1], d[2], rgb);
+        double rgb[3], qu[2];
+        ray_colour<RS, OBS, TEX, POL>(A, i, A.flags[i], d[0], d[1], d[2], rgb, qu);
         acc[0] += rgb[0];
         acc[1] += rgb[1];
         acc[2] += rgb[2];
+        if (POL)
+            for (int c = 0; c < 3; c++) {
+                pacc[c] += qu[0] * rgb[c];
+                pacc[3 + c] += qu[1] * rgb[c];
+            }
     }
     write_pixel(A, p, acc);
+    if (POL) write_stokes(A, p, pacc);
 }
 
 // dst[i] = src[index[i]] for rows of four floats: puts the gathered per-rank slabs into frame order on the
@@ -595,39 +862,55 @@ hipError_t launch_redshift(const RedshiftArgs &a, hipStream_t s)
     return hipGetLastError();
 }
 
-// one instance per (redshift, observer, textures): the template flags are the launch's run-time switches
-template <bool RS, bool OBS, bool TEX>
+hipError_t launch_polarisation(const PolarisationArgs &a, bool obs, hipStream_t s)
+{
+    if (a.n == 0) return hipSuccess;
+    if (obs)
+        BHG_LAUNCH(polarisation_kernel<true>, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
+    else
+        BHG_LAUNCH(polarisation_kernel<false>, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// one instance per (redshift, observer, textures, polarisation): the template flags are the launch's run-time switches
+template <bool RS, bool OBS, bool TEX, bool POL>
 void launch_shade_instance(const ShadeArgs &a, hipStream_t s)
 {
     if (a.samples > 256) {
         const dim3 grid((unsigned)((a.n_pixels + 255) / 256));
-        BHG_LAUNCH((shade_reduce_serial_kernel<RS, OBS, TEX>), grid, dim3(256), 0, s, a);
+        BHG_LAUNCH((shade_reduce_serial_kernel<RS, OBS, TEX, POL>), grid, dim3(256), 0, s, a);
         return;
     }
     const uint32_t ppb = 256u / (uint32_t)a.samples;      // pixels per workgroup
     const dim3 grid((unsigned)((a.n_pixels + ppb - 1) / ppb));
-    BHG_LAUNCH((shade_reduce_kernel<RS, OBS, TEX>), grid, dim3(256), 0, s, a, ppb);
+    BHG_LAUNCH((shade_reduce_kernel<RS, OBS, TEX, POL>), grid, dim3(256), 0, s, a, ppb);
 }
 
-template <bool TEX>
+template <bool TEX, bool POL>
 void launch_shade_tex(const ShadeArgs &a, hipStream_t s)
 {
     const bool rs = a.rs.apply != 0, obs = rs && a.obs.on;
     if (obs)
-        launch_shade_instance<true, true, TEX>(a, s);
+        launch_shade_instance<true, true, TEX, POL>(a, s);
     else if (rs)
-        launch_shade_instance<true, false, TEX>(a, s);
+        launch_shade_instance<true, false, TEX, POL>(a, s);
     else
-        launch_shade_instance<false, false, TEX>(a, s);
+        launch_shade_instance<false, false, TEX, POL>(a, s);
 }
 
 hipError_t launch_shade(const ShadeArgs &a, hipStream_t s)
 {
     if (a.n_pixels == 0) return hipSuccess;
-    if (a.ot.on)
-        launch_shade_tex<true>(a, s);
-    else
-        launch_shade_tex<false>(a, s);
+    if (a.pol.on) {
+        if (a.ot.on)
+            launch_shade_tex<true, true>(a, s);
+        else
+            launch_shade_tex<false, true>(a, s);
+    } else if (a.ot.on) {
+        launch_shade_tex<true, false>(a, s);
+    } else {
+        launch_shade_tex<false, false>(a, s);
+    }
     return hipGetLastError();
 }
 

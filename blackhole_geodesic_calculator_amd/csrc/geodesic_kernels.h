@@ -104,6 +104,23 @@ struct ObjectTextureParams {
     int32_t on;
 };
 
+// disk polarisation (frame_kernels.hip, polarisation_disk): the camera, the metric, the caller's degree
+// table and image up.  on = 0: the shade kernels' unpolarised instances are launched and never read this struct
+constexpr int BHG_POL_TABLE_MAX_ = 64;
+struct PolarisationParams {
+    double degree[BHG_POL_TABLE_MAX_];  // delta(mu_j), mu_j = j / (n_degree - 1)
+    double up[3];      // image up, world axes at the camera
+    double x0[3];      // camera, BH-centred (a shared origin; polarisation_kernel may read a per-ray one instead)
+    double beta[3];    // the observer's velocity relative to the ZAMO, world axes; zero without an observer
+    double r_s, spin;  // metric: r_s = 2M, Kerr a (rhs == BHG_RHS_KERR_BL_)
+    double sense;      // disk sense, +1 = counter-clockwise seen from +z, or -1
+    int32_t n_degree;  // 1 .. BHG_POL_TABLE_MAX_
+    int32_t rhs;       // BHG_RHS_*
+    int32_t on;
+    int32_t pad;
+    double *qu;        // shade kernels: [n_pixels][6] (Q_r, Q_g, Q_b, U_r, U_g, U_b) fp64
+};
+
 // camera-ray generation (frame_kernels.hip)
 struct RaygenArgs {
     const double *jitter;   // [S*H*W*2] MT19937 doubles, sample-major then row-major pixels, (u1, u2); nullptr = pixel
@@ -167,14 +184,28 @@ struct ShadeArgs {
     const double *k0;      // [S*n_pixels][3] camera directions, or nullptr when rs.apply == 0
     RedshiftParams rs;
     ObserverParams obs;    // beta and on only: the redshift instance's g is the moving observer's (rs.apply != 0 only)
-    // object textures (bhg_shade_scene_textured_device): launch_shade takes the textured instance when ot.on != 0; last, so
-    // that no other member moves
+    // object textures (bhg_shade_scene_textured_device): launch_shade takes the textured instance when ot.on != 0
     ObjectTextureParams ot;
+    // polarisation (bhg_shade_scene_polarised_device): launch_shade takes the polarised instance when pol.on != 0; last, so
+    // that no other member moves
+    PolarisationParams pol;
+};
+
+// one thread per ray: (chi, delta, mu) from the camera state (x0, k0) and the end record (bhg_polarisation_device)
+struct PolarisationArgs {
+    PolarisationParams p;
+    const double *x0;      // [n][3] or nullptr -> p.x0
+    const double *k0;      // [n][3]
+    const double *end;     // [n][6] or nullptr (then disk rays get NaN)
+    const uint8_t *flags;  // [n]
+    double *evpa, *degree, *mu;  // [n] each; mu may be nullptr
+    uint64_t n;
 };
 
 hipError_t launch_raygen(const RaygenArgs &a, hipStream_t s);
 hipError_t launch_shade(const ShadeArgs &a, hipStream_t s);
 hipError_t launch_redshift(const RedshiftArgs &a, hipStream_t s);
+hipError_t launch_polarisation(const PolarisationArgs &a, bool obs, hipStream_t s);
 hipError_t launch_split_end(const double *end, uint64_t n, double *loc, double *dir, hipStream_t s);
 hipError_t launch_gather_rows4(const float *src, const int64_t *index, uint64_t n, float *dst, hipStream_t s);
 

@@ -84,6 +84,8 @@ class DeviceFrame:
         self._params = None      # the parameters of the last trace (the redshift shade needs its metric)
         self.observer = None     # _ffi.Observer (set_observer) or None: the reference camera
         self._ray_key = None     # what the observer rays in d_k0 were made for: (origin, r_s, spin, rhs_form)
+        self.polarisation = None      # _ffi.Polarisation (set_polarisation) or None: off
+        self.d_qu = None              # [P, 6] fp64 Stokes Q / U images (shade_stokes)
         self.object_textures = None   # set_object_textures: (device textures per sphere, rotations, modes, emission) or None
 
     def _stream(self):
@@ -137,6 +139,15 @@ class DeviceFrame:
         self.observer = _ffi.make_observer(velocity)
         self._rays_ready = False
         self._ray_key = None
+
+    def set_polarisation(self, degree=None, disk_sense=1):
+        """Disk polarisation for shade_stokes() (bhg_shade_scene_polarised_device): degree is a constant or
+        a table against the emission cosine (make_polarisation), image up the camera's rotated +y.  None: off.  shade() and
+        shade_f32() are the same either way."""
+        if degree is None:
+            self.polarisation = None
+            return
+        self.polarisation = _ffi.make_polarisation(degree, disk_sense, self.rot @ np.array([0.0, 1.0, 0.0]))
 
     def set_object_textures(self, textures=None, rotations=None, modes=None, emission=None):
         """Textured, oriented and emissive object spheres (bhg_shade_scene_textured_device), per sphere of
@@ -233,21 +244,31 @@ class DeviceFrame:
             raise RuntimeError("the last trace wrote exit directions only, but the frame now has a disk / objects: trace() again")
         return traced
 
-    def _shade(self, d_rgba=0, d_rgba_f32=0, scatter=None):
-        """The one shade call of both outputs (bhg_shade_scene_textured_device): redshift, the observer and the object textures
-        as set, each None when off."""
+    def _shade(self, d_rgba=0, d_rgba_f32=0, scatter=None, pol=None, d_qu=0):
+        """The one shade call of every output (bhg_shade_scene_polarised_device): redshift, the observer, the object textures
+        and the polarisation (shade_stokes only) as set, each None when off -- pol = None is the textured call exactly."""
         form = self._shade_form()
-        self.ctx.shade_scene_textured_device(self.d_end.data_ptr() if form == "end" else 0, self.d_flags.data_ptr(), self.P, self.S,
-                                             self.scene(), self._params, self.redshift, self.observer,
-                                             self._object_textures() if self._textured() else None, x0_shared=self.origin,
-                                             d_k0=self.d_k0.data_ptr(), d_rgba=d_rgba, d_rgba_f32=d_rgba_f32,
-                                             d_object_id=0 if self.d_obj is None else self.d_obj.data_ptr(),
-                                             d_scatter=0 if scatter is None else scatter.data_ptr(),
-                                             d_end_dir=self.d_dir.data_ptr() if form == "dir" else 0, stream=self._stream())
+        self.ctx.shade_scene_polarised_device(self.d_end.data_ptr() if form == "end" else 0, self.d_flags.data_ptr(), self.P, self.S,
+                                              self.scene(), self._params, self.redshift, self.observer,
+                                              self._object_textures() if self._textured() else None, pol, d_qu,
+                                              x0_shared=self.origin, d_k0=self.d_k0.data_ptr(), d_rgba=d_rgba, d_rgba_f32=d_rgba_f32,
+                                              d_object_id=0 if self.d_obj is None else self.d_obj.data_ptr(),
+                                              d_scatter=0 if scatter is None else scatter.data_ptr(),
+                                              d_end_dir=self.d_dir.data_ptr() if form == "dir" else 0, stream=self._stream())
 
     def shade(self):
         self._shade(d_rgba=self.d_rgba.data_ptr())
         return self.d_rgba
+
+    def shade_stokes(self):
+        """(rgba [P, 4], qu [P, 6]) fp64: shade() and the per-pixel means of (Q_r, Q_g, Q_b, U_r, U_g, U_b) of the disk's
+        polarisation (set_polarisation first)."""
+        if self.polarisation is None:
+            raise RuntimeError("set_polarisation() first")
+        if self.d_qu is None:
+            self.d_qu = torch.empty((self.P, 6), dtype=torch.float64, device=self.dev)
+        self._shade(d_rgba=self.d_rgba.data_ptr(), pol=self.polarisation, d_qu=self.d_qu.data_ptr())
+        return self.d_rgba, self.d_qu
 
     def shade_f32(self, out, scatter=None):
         """Shade + sample mean written as float32 RGBA into `out` ([P, 4], or [H*W, 4] with scatter = this shard's

@@ -63,7 +63,8 @@ class GeodesicIntegratorSchwarzschild:
                                 disk_r_out=disk[1] if disk else 0.0, spin=self.spin, time_like=self.time_like)
 
     # ------------------------------------------------------------------------------------
-    def trace(self, k0, x0, max_step=np.inf, curve_end=50.0, r_exit=0.0, disk=None, spheres=None, redshift=None):
+    def trace(self, k0, x0, max_step=np.inf, curve_end=50.0, r_exit=0.0, disk=None, spheres=None, redshift=None,
+              polarisation=None):
         """Batched solve.  k0[N,3] (or [...,3]); x0[3] shared origin or same leading shape as k0.
         r_exit: outward sphere-exit radius (Limited engine's ray_trace, Limited...py:273-278);
         disk=(R_in, R_out): thin disk in z = 0, first crossing inside the annulus ends the ray with
@@ -80,6 +81,11 @@ class GeodesicIntegratorSchwarzschild:
             g[...]                     only with redshift=dict(disk_sense=+1 or -1): nu_obs / nu_em of each ray between
                                        the camera's ZAMO and its emitter (disk in Keplerian orbit of that sense, object at
                                        rest, sky at rest at infinity; 0 for horizon rays, NaN for NaN rays), bhg_redshift_host
+            evpa[...], pol_degree[...], mu_em[...]
+                                       only with polarisation=dict(degree=..., disk_sense=..., up=...): the disk ray's
+                                       polarisation angle at the camera (from image up towards image left, in (-pi/2, pi/2]),
+                                       its degree (the table at mu) and emission cosine; NaN for NaN rays, 0 for every ray
+                                       that is not a disk ray (bhg_polarisation_host)
         """
         k0 = np.asarray(k0, dtype=np.float64)
         lead = k0.shape[:-1]
@@ -104,6 +110,10 @@ class GeodesicIntegratorSchwarzschild:
         if redshift is not None:
             rs = _ffi.make_redshift(apply=(), disk_sense=redshift.get("disk_sense", 1))
             out["g"] = self._ctx.redshift(k0f, x0f, self.params(max_step, curve_end, r_exit, disk), rs, flags, end).reshape(lead)
+        if polarisation is not None:
+            pol = _ffi.make_polarisation(**polarisation)
+            chi, deg, mu = self._ctx.polarisation(k0f, x0f, self.params(max_step, curve_end, r_exit, disk), pol, None, flags, end)
+            out["evpa"], out["pol_degree"], out["mu_em"] = chi.reshape(lead), deg.reshape(lead), mu.reshape(lead)
         return out
 
     # ------------------------------------------------------------------------------------

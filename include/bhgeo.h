@@ -56,7 +56,9 @@ extern "C" {
                                   struct bhg_observer; nothing of ABI 9 changed.
                                   Later additions within ABI 10, found by symbol and announced by a feature macro:
                                   BHG_OBJECT_TEXTURES (bhg_shade_scene_textured_device, bhg_frame_set_object_textures,
-                                  bhg_object_textures_size, struct bhg_object_textures).
+                                  bhg_object_textures_size, struct bhg_object_textures);
+                                  BHG_POLARISATION (bhg_polarisation_device / _host, bhg_shade_scene_polarised_device,
+                                  bhg_polarisation_size, struct bhg_polarisation).
                                9: redshift -- bhg_redshift_device / _host, bhg_shade_scene_redshift_device, bhg_frame_set_redshift,
                                   bhg_redshift_size, struct bhg_redshift;
                                   nothing of ABI 8 changed.
@@ -589,6 +591,60 @@ int bhg_shade_scene_textured_device(bhg_context *ctx, const double *d_end, const
  * them.  Slots are checked against the scene's n_spheres here and again at render; slots at or above it are ignored.  A
  * refused host copy is BHG_E_NOMEM and leaves the frame as it was. */
 int bhg_frame_set_object_textures(bhg_frame *frame, const bhg_object_textures *ot);
+
+/* --- disk polarisation (within ABI 10) ---------------------------------------------------------
+ * The linear polarisation of the thin disk's light at the camera: the emission is polarised in the disk plane and
+ * perpendicular to the photon in the fluid frame (electron scattering), f ~ z^ x n_f, with a degree delta the caller tabulates
+ * against the emission cosine mu = |n_f . z^|.  f is carried to the camera by the Walker-Penrose constant
+ *     kappa = (A - i B)(r - i a cos th),  A = (k^t f^r - k^r f^t) + a sin^2 th (k^r f^ph - k^ph f^r),
+ *                                         B = [(r^2 + a^2)(k^ph f^th - k^th f^ph) - a (k^t f^th - k^th f^t)] sin th
+ * (BL coordinates; Schwarzschild at a = 0) of the traced ray, with k at the disk rebuilt from the camera state's constants
+ * (Kerr E, L_z, Carter Q; Schwarzschild E and x x k) and only the signs of k^r, k^th taken from the end record.  The disk is
+ * redshift's Keplerian disk of sense disk_sense (section 9: the traced picture's sense is -disk_sense).  On the screen of the
+ * camera's observer -- the ZAMO, or with obs the moving observer of section 10 -- with the ray's look direction n and image
+ * up `up` (world axes): e_up = normalise(up - (up.n) n), e_left = e_up x n, and
+ *     chi = atan2(c_L, c_U) in (-pi/2, pi/2],  kappa_em = c_L kappa(k_c, E_left) + c_U kappa(k_c, E_up),
+ * measured from image up towards image left (the IAU convention).  up along n, or f = 0 (the photon leaves along the disk
+ * normal, mu = 1): chi = NaN, delta and mu as for any disk ray, and no contribution to Q and U.
+ * Per ray, by flags: BHG_FLAG_HIT_DISK rays (chi, delta, mu); BHG_FLAG_NAN rays, and disk rays without an end record, NaN;
+ * every other ray 0 (objects and sky are unpolarised).
+ * Refused (BHG_E_INVALID, the message names the figure), before the context: disk_sense other than +-1; n_degree outside
+ * [1, BHG_POL_TABLE_MAX]; a degree that is not finite or outside [0, 1]; an up that is not finite or zero; time_like = 1; a disk
+ * r_in at or inside the photon orbit of the traced sense (section 9's rule); a redshift disk_sense that differs from this one
+ * when both are given; a shared camera at or inside the horizon, inside the Kerr ergosurface or exactly on the Kerr BL axis
+ * (section 10's rules, with or without obs).
+ * Member order: disk_sense, n_degree, up, degree (544 bytes). */
+#define BHG_POLARISATION 1
+#define BHG_POL_TABLE_MAX 64
+typedef struct bhg_polarisation {
+    int32_t disk_sense;                 /* +1 / -1, bhg_redshift's meaning */
+    int32_t n_degree;                   /* 1 .. BHG_POL_TABLE_MAX */
+    double up[3];                       /* image up, world axes at the camera */
+    double degree[BHG_POL_TABLE_MAX];   /* delta(mu_j), mu_j = j / (n_degree - 1), linear between; in [0, 1] */
+} bhg_polarisation;
+size_t bhg_polarisation_size(void);
+/* Per ray, from the camera state (x0_shared [3] HOST, or d_x0 [n][3]; d_k0 [n][3]), d_end [n][6] (or NULL) and d_flags [n]:
+ * d_evpa [n] = chi, d_degree [n] = delta, d_mu [n] = mu (d_mu may be NULL).  obs NULL: the ZAMO's screen.  One launch on
+ * stream; no context workspace. */
+int bhg_polarisation_device(bhg_context *ctx, const bhg_params *p, const bhg_polarisation *pol, const bhg_observer *obs,
+                            const double *x0_shared, const double *d_x0, const double *d_k0, const double *d_end,
+                            const uint8_t *d_flags, size_t n, double *d_evpa, double *d_degree, double *d_mu, void *stream);
+/* bhg_polarisation_device on host arrays (x0 [3] with x0_is_shared != 0, else [n][3]; end may be NULL; mu may be NULL). */
+int bhg_polarisation_host(bhg_context *ctx, const bhg_params *p, const bhg_polarisation *pol, const bhg_observer *obs,
+                          const double *x0, int x0_is_shared, const double *k0, const double *end, const uint8_t *flags,
+                          size_t n, double *evpa, double *degree, double *mu);
+/* bhg_shade_scene_textured_device with the Stokes images: d_qu [n_pixels][6] fp64 = the per-pixel means (in sample order) of
+ * (Q_r, Q_g, Q_b, U_r, U_g, U_b), Q_c = delta cos 2chi rgb_c, U_c = delta sin 2chi rgb_c, rgb_c the ray's final colour (disk
+ * texture, g^n with redshift); written at pixel p, never scattered.  The colour outputs are bit for bit those of the textured
+ * call.  pol = NULL is exactly the textured call (which is this call with pol = NULL: one implementation, one checking order:
+ * after step 3 of the textured call's, pol against p and x0_shared -- which it needs -- and the redshift's disk_sense; in step
+ * 6, d_qu and d_k0). */
+int bhg_shade_scene_polarised_device(bhg_context *ctx, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
+                                     const int8_t *d_object_id, size_t n_pixels, int32_t samples, const bhg_scene *scene,
+                                     const bhg_params *p, const bhg_redshift *rs, const bhg_observer *obs,
+                                     const bhg_object_textures *ot, const double *x0_shared, const double *d_k0, double *d_rgba,
+                                     float *d_rgba_f32, const int64_t *d_scatter, const bhg_polarisation *pol, double *d_qu,
+                                     void *stream);
 
 /* Acceleration probe: acc[n][3] = -Gamma^i_{mu nu} k^mu k^nu at (x[n][3], k[n][3]); host buffers.
  * Lets tests compare the device RHS with the oracle's term by term.  With rhs_form = BHG_RHS_KERR_BL the triples
