@@ -59,6 +59,8 @@ EXPORTS = (
     "bhg_shade_scene_redshift_observer_device", "bhg_frame_set_observer",
     "bhg_object_textures_size", "bhg_shade_scene_textured_device", "bhg_frame_set_object_textures",
     "bhg_polarisation_size", "bhg_polarisation_device", "bhg_polarisation_host", "bhg_shade_scene_polarised_device",
+    "bhg_disk_thermal_size", "bhg_disk_thermal_device", "bhg_disk_thermal_host", "bhg_shade_scene_thermal_device",
+    "bhg_frame_set_disk_thermal",
 )
 PROBE_FMA, PROBE_STEP_MIX = 0, 1
 
@@ -127,6 +129,40 @@ def make_polarisation(degree=0.1, disk_sense=1, up=(0.0, 1.0, 0.0)) -> Polarisat
     pol.up[:] = [float(v) for v in np.asarray(up, dtype=np.float64).reshape(3)]
     pol.degree[:d.size] = [float(v) for v in d]
     return pol
+
+
+THERMAL_NU_MAX = 16
+
+
+class DiskThermal(C.Structure):
+    """bhg_disk_thermal (BHG_DISK_THERMAL, within ABI 10): the Novikov-Thorne disk's peak temperature, colour correction and
+    scale, and the frequencies [Hz] the R, G, B channels weigh."""
+    _fields_ = [("disk_sense", C.c_int32), ("n_nu", C.c_int32), ("t_peak", C.c_double), ("f_col", C.c_double),
+                ("scale", C.c_double), ("nu", C.c_double * THERMAL_NU_MAX), ("weight", (C.c_double * THERMAL_NU_MAX) * 3)]
+
+
+def make_disk_thermal(t_peak, nu, weights, f_col=1.0, scale=1.0, disk_sense=1) -> DiskThermal:
+    """t_peak [K]: the disk's largest emitted temperature; nu: 1 to 16 frequencies [Hz] shared by the channels; weights [3, n]:
+    each channel's weight of each frequency (any sign); f_col: colour correction; scale: overall factor; disk_sense as
+    redshift's."""
+    nu = np.atleast_1d(np.asarray(nu, dtype=np.float64)).ravel()
+    w = np.asarray(weights, dtype=np.float64)
+    if not 1 <= nu.size <= THERMAL_NU_MAX:
+        raise ValueError(f"the frequency table has {nu.size} entries: 1 to {THERMAL_NU_MAX}")
+    if w.shape != (3, nu.size):
+        raise ValueError(f"weights must be [3, {nu.size}], not {list(w.shape)}")
+    th = DiskThermal()
+    th.disk_sense, th.n_nu = int(disk_sense), int(nu.size)
+    th.t_peak, th.f_col, th.scale = float(t_peak), float(f_col), float(scale)
+    th.nu[:nu.size] = [float(v) for v in nu]
+    for c in range(3):
+        th.weight[c][:nu.size] = [float(v) for v in w[c]]
+    return th
+
+
+def narrowband(nu_r, nu_g, nu_b):
+    """(nu, weights) of narrow-band false colour: one frequency [Hz] per channel, weight 1 (make_disk_thermal(t, *narrowband(...)))."""
+    return np.array([nu_r, nu_g, nu_b], dtype=np.float64), np.eye(3)
 
 
 OBJECT_LIT, OBJECT_EMISSIVE = 0, 1
@@ -462,6 +498,23 @@ def load():
                                                    C.c_void_p, C.c_void_p, C.POINTER(Polarisation), C.c_void_p, C.c_void_p]
     L.bhg_frame_set_object_textures.restype = C.c_int
     L.bhg_frame_set_object_textures.argtypes = [C.c_void_p, C.POINTER(ObjectTextures)]
+    L.bhg_disk_thermal_size.restype = C.c_size_t
+    L.bhg_disk_thermal_size.argtypes = []
+    L.bhg_disk_thermal_device.restype = C.c_int
+    L.bhg_disk_thermal_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(DiskThermal), C.POINTER(Observer), _dp,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]
+    L.bhg_disk_thermal_host.restype = C.c_int
+    L.bhg_disk_thermal_host.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(DiskThermal), C.POINTER(Observer), C.c_void_p,
+                                        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.bhg_shade_scene_thermal_device.restype = C.c_int
+    L.bhg_shade_scene_thermal_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                 C.c_int32, C.POINTER(Scene), C.POINTER(Params), C.POINTER(Redshift),
+                                                 C.POINTER(Observer), C.POINTER(ObjectTextures), _dp, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.POINTER(Polarisation), C.c_void_p,
+                                                 C.POINTER(DiskThermal), C.c_void_p]
+    L.bhg_frame_set_disk_thermal.restype = C.c_int
+    L.bhg_frame_set_disk_thermal.argtypes = [C.c_void_p, C.POINTER(DiskThermal)]
     if L.bhg_version() != ABI_VERSION or not hasattr(L, "bhg_abi_check"):
         raise ImportError(f"libbhgeo ABI {L.bhg_version()} != expected {ABI_VERSION}: rebuild {LIB_PATH}")
     for name in ("bhg_params_size", "bhg_camera_size", "bhg_scene_size", "bhg_frame_scene_size"):
@@ -480,6 +533,8 @@ def load():
         raise ImportError(f"libbhgeo: bhg_redshift is {L.bhg_redshift_size()} bytes, this binding's {C.sizeof(Redshift)}")
     if L.bhg_observer_size() != C.sizeof(Observer):
         raise ImportError(f"libbhgeo: bhg_observer is {L.bhg_observer_size()} bytes, this binding's {C.sizeof(Observer)}")
+    if L.bhg_disk_thermal_size() != C.sizeof(DiskThermal):
+        raise ImportError(f"libbhgeo: bhg_disk_thermal is {L.bhg_disk_thermal_size()} bytes, this binding's {C.sizeof(DiskThermal)}")
     if L.bhg_polarisation_size() != C.sizeof(Polarisation):
         raise ImportError(f"libbhgeo: bhg_polarisation is {L.bhg_polarisation_size()} bytes, this binding's {C.sizeof(Polarisation)}")
     if L.bhg_object_textures_size() != C.sizeof(ObjectTextures):
@@ -777,6 +832,13 @@ class Frame:
         ot, keep = make_object_textures(textures, rotations, modes, emission)
         _check(load().bhg_frame_set_object_textures(self._h, C.byref(ot)))
         del keep
+
+    def set_disk_thermal(self, th=None):
+        """The thermal disk in every later render (bhg_frame_set_disk_thermal): th a DiskThermal
+        (make_disk_thermal), or a dict of make_disk_thermal's arguments.  None: off -- the frame as without it, bit for bit."""
+        if isinstance(th, dict):
+            th = make_disk_thermal(**th)
+        _check(load().bhg_frame_set_disk_thermal(self._h, None if th is None else C.byref(th)))
 
     def render(self, params: "Params", out=None, to_host=True):
         """One frame: float32 [H, W, 4] (a new array, or `out`).  to_host=False: only enqueue; the image stays on the
@@ -1112,6 +1174,46 @@ class Context:
             None if rs is None else C.byref(rs), _obs_ref(obs), None if ot is None else C.byref(ot), xs, C.c_void_p(d_k0 or None),
             C.c_void_p(d_rgba or None), C.c_void_p(d_rgba_f32 or None), C.c_void_p(d_scatter or None),
             None if pol is None else C.byref(pol), C.c_void_p(d_qu or None), C.c_void_p(stream or None)))
+
+    def shade_scene_thermal_device(self, d_end, d_flags, n_pixels, samples, scene: "Scene", params, rs, obs, ot, pol, d_qu, th,
+                                   x0_shared=None, d_k0=0, d_rgba=0, d_rgba_f32=0, d_object_id=0, d_scatter=0, d_end_dir=0,
+                                   stream=0):
+        """bhg_shade_scene_thermal_device: shade_scene_polarised_device with the thermal disk (th: DiskThermal, or None =
+        exactly the polarised call)."""
+        xs = None if x0_shared is None else (C.c_double * 3)(*[float(v) for v in x0_shared])
+        _check(load().bhg_shade_scene_thermal_device(
+            self._h, C.c_void_p(d_end or None), C.c_void_p(d_end_dir or None), C.c_void_p(d_flags), C.c_void_p(d_object_id or None),
+            int(n_pixels), int(samples), C.byref(scene), None if params is None else C.byref(params),
+            None if rs is None else C.byref(rs), _obs_ref(obs), None if ot is None else C.byref(ot), xs, C.c_void_p(d_k0 or None),
+            C.c_void_p(d_rgba or None), C.c_void_p(d_rgba_f32 or None), C.c_void_p(d_scatter or None),
+            None if pol is None else C.byref(pol), C.c_void_p(d_qu or None), None if th is None else C.byref(th),
+            C.c_void_p(stream or None)))
+
+    def disk_thermal(self, k0, x0, params: Params, th: DiskThermal, obs, flags, end=None):
+        """bhg_disk_thermal_host: (t_em [N], rgb [N, 3]) of traced rays from their camera state (k0 [N, 3], x0 [3] or [N, 3]),
+        end [N, 6] (or None) and flags [N]; obs: Observer or None (the ZAMO's g)."""
+        k0 = np.ascontiguousarray(k0, dtype=np.float64).reshape(-1, 3)
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        n = k0.shape[0]
+        if flags.shape != (n,) or (x0.shape != (3,) and x0.shape != (n, 3)):
+            raise ValueError("flags must be [N], x0 [3] or [N, 3]")
+        e = None if end is None else np.ascontiguousarray(end, dtype=np.float64)
+        if e is not None and e.shape != (n, 6):
+            raise ValueError("end must be [N, 6]")
+        t_em = np.empty(n, np.float64)
+        rgb = np.empty((n, 3), np.float64)
+        _check(load().bhg_disk_thermal_host(self._h, C.byref(params), C.byref(th), _obs_ref(obs), _addr(x0), 1 if x0.ndim == 1 else 0,
+                                            _addr(k0), None if e is None else _addr(e), _addr(flags), n, _addr(t_em), _addr(rgb)))
+        return t_em, rgb
+
+    def disk_thermal_device(self, params: Params, th: DiskThermal, obs, n, d_k0, d_flags, d_t_em, d_rgb, x0_shared=None, d_x0=0,
+                            d_end=0, stream=0):
+        """bhg_disk_thermal_device on device arrays (d_rgb [n, 3])."""
+        xs = None if x0_shared is None else (C.c_double * 3)(*[float(v) for v in x0_shared])
+        _check(load().bhg_disk_thermal_device(self._h, C.byref(params), C.byref(th), _obs_ref(obs), xs, C.c_void_p(d_x0 or None),
+                                              C.c_void_p(d_k0), C.c_void_p(d_end or None), C.c_void_p(d_flags), int(n),
+                                              C.c_void_p(d_t_em), C.c_void_p(d_rgb), C.c_void_p(stream or None)))
 
     def polarisation(self, k0, x0, params: Params, pol: Polarisation, obs, flags, end=None):
         """bhg_polarisation_host: (evpa, degree, mu) [N] of traced rays from their camera state (k0 [N, 3], x0 [3] or [N, 3]), end

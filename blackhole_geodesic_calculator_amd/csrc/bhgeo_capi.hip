@@ -47,6 +47,7 @@ static_assert(sizeof(bhg_redshift) == 16, "bhg_redshift layout is part of the AB
 static_assert(sizeof(bhg_observer) == 24, "bhg_observer layout is part of the ABI");
 static_assert(sizeof(bhg_object_textures) == 800, "bhg_object_textures layout is part of the ABI");
 static_assert(sizeof(bhg_polarisation) == 544 && BHG_POL_TABLE_MAX == bhg::BHG_POL_TABLE_MAX_, "bhg_polarisation layout is part of the ABI");
+static_assert(sizeof(bhg_disk_thermal) == 544 && BHG_THERMAL_NU_MAX == bhg::BHG_THERMAL_NU_MAX_, "bhg_disk_thermal layout is part of the ABI");
 static_assert(BHG_OBJECT_LIT == bhg::BHG_OBJECT_LIT_ && BHG_OBJECT_EMISSIVE == bhg::BHG_OBJECT_EMISSIVE_, "object mode mismatch");
 
 namespace {
@@ -359,6 +360,41 @@ int validate(const bhg_params *p)
 }  // namespace
 
 namespace bhg {
+// The thermal-disk settings on their own (include/bhgeo.h, "the thermal disk"): what can be checked without the trace
+// parameters.  Also used by bhgeo_frame.hip.
+int thermal_check(const bhg_disk_thermal *th)
+{
+    if (th->disk_sense != 1 && th->disk_sense != -1)
+        return fail(BHG_E_INVALID, "disk thermal disk_sense must be +1 or -1, not " + std::to_string(th->disk_sense));
+    if (th->n_nu < 1 || th->n_nu > BHG_THERMAL_NU_MAX)
+        return fail(BHG_E_INVALID, "disk thermal n_nu must be in [1, 16], not " + std::to_string(th->n_nu));
+    char msg[160];
+    for (int j = 0; j < th->n_nu; j++)
+        if (!(std::isfinite(th->nu[j]) && th->nu[j] > 0.0)) {
+            std::snprintf(msg, sizeof msg, "disk thermal nu[%d] = %.17g must be finite and > 0", j, th->nu[j]);
+            return fail(BHG_E_INVALID, msg);
+        }
+    for (int c = 0; c < 3; c++)
+        for (int j = 0; j < th->n_nu; j++)
+            if (!std::isfinite(th->weight[c][j])) {
+                std::snprintf(msg, sizeof msg, "disk thermal weight[%d][%d] = %.17g is not finite", c, j, th->weight[c][j]);
+                return fail(BHG_E_INVALID, msg);
+            }
+    if (!(std::isfinite(th->t_peak) && th->t_peak > 0.0)) {
+        std::snprintf(msg, sizeof msg, "disk thermal t_peak = %.17g must be finite and > 0", th->t_peak);
+        return fail(BHG_E_INVALID, msg);
+    }
+    if (!(std::isfinite(th->f_col) && th->f_col > 0.0)) {
+        std::snprintf(msg, sizeof msg, "disk thermal f_col = %.17g must be finite and > 0", th->f_col);
+        return fail(BHG_E_INVALID, msg);
+    }
+    if (!std::isfinite(th->scale)) {
+        std::snprintf(msg, sizeof msg, "disk thermal scale = %.17g is not finite", th->scale);
+        return fail(BHG_E_INVALID, msg);
+    }
+    return BHG_OK;
+}
+
 // Redshift settings against the trace parameters (include/bhgeo.h, "redshift"): *out = the kernels' parameters.  disk_r_in
 // < 0: no disk to check (none in the scene, or the disk class is not asked for).  Also used by bhgeo_frame.hip.
 int redshift_params(const bhg_params *p, const bhg_redshift *rs, double disk_r_in, const double *x0, RedshiftParams *out)
@@ -525,6 +561,122 @@ int polarisation_params(const bhg_params *p, const bhg_polarisation *pol, const 
     return BHG_OK;
 }
 
+// The Page-Thorne constants of the family a*  into *T: r_ms (Bardeen-Press-Teukolsky, a* signed), x0, the
+// roots of x^3 - 3x + 2a*, the c_i (a* = 0: the roots sqrt(3), 0, -sqrt(3) and c_2 = 0, the limit of a term that vanishes),
+// and 1 / max F^: a grid over x in (x0, 4 x0] brackets the one maximum, a golden-section search closes in on it (the maximum
+// is flat, so F^ there is good to the last bits long before x is).  M = 1: F^ is a function of x and a* alone.
+void thermal_constants(double astar, ThermalParams *T)
+{
+    const double z1 = 1.0 + std::cbrt(1.0 - astar * astar) * (std::cbrt(1.0 + astar) + std::cbrt(1.0 - astar));
+    const double z2 = std::sqrt(3.0 * astar * astar + z1 * z1);
+    const double r_ms = 3.0 + z2 - (astar < 0.0 ? -1.0 : 1.0) * std::sqrt((3.0 - z1) * (3.0 + z1 + 2.0 * z2));
+    T->astar = astar;
+    T->r_ms = r_ms;         // (in units of M: the caller scales it)
+    T->x0 = std::sqrt(r_ms);
+    if (astar == 0.0) {
+        T->xr[0] = std::sqrt(3.0);
+        T->xr[1] = 0.0;
+        T->xr[2] = -std::sqrt(3.0);
+    } else {
+        const double th = std::acos(astar) / 3.0, pi3 = M_PI / 3.0;
+        T->xr[0] = 2.0 * std::cos(th - pi3);
+        T->xr[1] = 2.0 * std::cos(th + pi3);
+        T->xr[2] = -2.0 * std::cos(th);
+    }
+    for (int i = 0; i < 3; i++) {
+        const double xi = T->xr[i], xj = T->xr[(i + 1) % 3], xk = T->xr[(i + 2) % 3];
+        T->c[i] = xi == 0.0 ? 0.0 : 3.0 * (xi - astar) * (xi - astar) / (xi * (xi - xj) * (xi - xk));
+    }
+    const double x0 = T->x0;
+    const int N = 3000;
+    int best = 1;
+    double fbest = -1.0;
+    for (int k = 1; k <= N; k++) {
+        const double f = page_thorne(*T, x0 * (1.0 + 3.0 * k / N));
+        if (f > fbest) {
+            fbest = f;
+            best = k;
+        }
+    }
+    double lo = x0 * (1.0 + 3.0 * (best - 1) / N), hi = x0 * (1.0 + 3.0 * (best + 1) / N);
+    const double gr = 0.5 * (std::sqrt(5.0) - 1.0);
+    double u = hi - gr * (hi - lo), v = lo + gr * (hi - lo), fu = page_thorne(*T, u), fv = page_thorne(*T, v);
+    for (int it = 0; it < 200 && hi - lo > 1e-15 * hi; it++) {
+        if (fu > fv) {
+            hi = v;
+            v = u;
+            fv = fu;
+            u = hi - gr * (hi - lo);
+            fu = page_thorne(*T, u);
+        } else {
+            lo = u;
+            u = v;
+            fu = fv;
+            v = lo + gr * (hi - lo);
+            fv = page_thorne(*T, v);
+        }
+    }
+    T->inv_fmax = 1.0 / std::max(std::max(fu, fv), fbest);
+}
+
+// Thermal-disk settings (include/bhgeo.h, "the thermal disk"): *out = the kernels' table, on = 1, and *rp = the metric, camera
+// and sense of the disk's g (apply 0: the caller puts its redshift's apply and exponent in when it has one).  disk_r_in < 0: no
+// disk to check; rs, pol: the redshift and polarisation settings of the same call, or NULL; x0: the shared camera, or NULL
+// (per-ray origins: nothing to check the position of).  Also used by bhgeo_frame.hip.
+int thermal_params(const bhg_params *p, const bhg_disk_thermal *th, const bhg_redshift *rs, const bhg_polarisation *pol,
+                   double disk_r_in, const double *x0, ThermalParams *out, RedshiftParams *rp)
+{
+    int rc = validate(p);
+    if (rc != BHG_OK) return rc;
+    if (!th) return fail(BHG_E_INVALID, "disk thermal settings are NULL");
+    rc = thermal_check(th);
+    if (rc != BHG_OK) return rc;
+    if (p->time_like) return fail(BHG_E_INVALID, "the thermal disk is seen by null rays: time_like = 1 is refused");
+    const double M = 0.5 * p->r_s, a = p->rhs_form == BHG_RHS_KERR_BL ? p->spin : 0.0, s = -(double)th->disk_sense;
+    if (disk_r_in >= 0.0) {
+        // section 9's rule: no timelike circular orbit at or inside the photon orbit of the traced picture's sense
+        const double r_ph = p->rhs_form == BHG_RHS_KERR_BL ? 2.0 * M * (1.0 + std::cos(2.0 / 3.0 * std::acos(-s * a / M))) : 3.0 * M;
+        const double r_in = std::sqrt(std::max(disk_r_in * disk_r_in - a * a, 0.0));
+        if (!(r_in > r_ph)) {
+            char msg[220];
+            std::snprintf(msg, sizeof msg, "disk thermal: disk_r_in %.17g (Boyer-Lindquist r %.17g) is at or inside the circular "
+                          "photon orbit r_ph = %.17g of disk_sense %d", disk_r_in, r_in, r_ph, th->disk_sense);
+            return fail(BHG_E_INVALID, msg);
+        }
+    }
+    if (rs && rs->disk_sense != th->disk_sense)
+        return fail(BHG_E_INVALID, "disk thermal disk_sense " + std::to_string(th->disk_sense) + " differs from the redshift's " +
+                                   std::to_string(rs->disk_sense));
+    if (pol && pol->disk_sense != th->disk_sense)
+        return fail(BHG_E_INVALID, "disk thermal disk_sense " + std::to_string(th->disk_sense) + " differs from the polarisation's " +
+                                   std::to_string(pol->disk_sense));
+    if (x0) {
+        rc = camera_position_check(p, x0, "disk thermal");
+        if (rc != BHG_OK) return rc;
+    }
+    std::memset(out, 0, sizeof(*out));
+    thermal_constants(s * a / M, out);
+    out->r_ms *= M;
+    // nu in units of k_B T_peak / h (h / k_B in K s, exact in the SI)
+    const double nu0_inv = 4.799243073366221e-11 / th->t_peak;
+    for (int j = 0; j < th->n_nu; j++) {
+        out->nu[j] = th->nu[j] * nu0_inv;
+        for (int c = 0; c < 3; c++) out->w[c][j] = th->weight[c][j];
+    }
+    out->t_peak = th->t_peak;
+    out->f_col = th->f_col;
+    out->scale = th->scale;
+    out->n_nu = th->n_nu;
+    out->on = 1;
+    std::memset(rp, 0, sizeof(*rp));
+    if (x0) std::memcpy(rp->x0, x0, sizeof(rp->x0));
+    rp->r_s = p->r_s;
+    rp->spin = a;
+    rp->sense = (double)th->disk_sense;
+    rp->rhs = p->rhs_form;
+    return BHG_OK;
+}
+
 // Object textures (include/bhgeo.h, "textured, oriented and emissive object spheres") for a scene of n_spheres spheres: slots
 // at or above n_spheres are not looked at.  *out = the kernels' table (an all-zero rotation becomes the identity), on = 1.
 // Also used by bhgeo_frame.hip (there with tex = the host arrays: only whether a slot has one matters).
@@ -611,6 +763,7 @@ size_t bhg_redshift_size(void) { return sizeof(bhg_redshift); }
 size_t bhg_observer_size(void) { return sizeof(bhg_observer); }
 size_t bhg_object_textures_size(void) { return sizeof(bhg_object_textures); }
 size_t bhg_polarisation_size(void) { return sizeof(bhg_polarisation); }
+size_t bhg_disk_thermal_size(void) { return sizeof(bhg_disk_thermal); }
 
 int bhg_abi_check(int abi_version, size_t params_size, size_t camera_size, size_t scene_size, size_t frame_scene_size)
 {
@@ -1424,15 +1577,18 @@ int raygen_impl(bhg_context *c, int32_t width, int32_t height, int32_t samples, 
 //   2. the object-texture table, when given, against n_spheres
 //   3. redshift, when rs->apply != 0: x0_shared, the settings, and the observer when given
 //   3b. polarisation, when pol is given: x0_shared, the settings (against p, the scene's disk, the redshift's sense, the camera)
+//   3c. the thermal disk, when th is given: the settings (against p, the scene's disk, the redshift's and polarisation's
+//      sense), x0_shared and the camera, and the observer when given
 //   4. the context
 //   5. n_pixels == 0 is BHG_OK: an EMPTY shard -- a rank without pixels: fewer tiles than ranks -- has no rays and no
 //      arrays, so no device array is looked at
 //   6. the device arrays: an output, end or end_dir, flags, the sky; end for a disk or spheres; object_id for spheres;
-//      k0 for redshift; qu and k0 for polarisation
+//      k0 for redshift; qu and k0 for polarisation; k0 for the thermal disk
 int shade(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags, const int8_t *d_object_id,
           size_t n_pixels, int32_t samples, const bhg_scene *sc, const bhg_params *p, const bhg_redshift *rs,
           const bhg_observer *obs, const bhg_object_textures *ot, const double *x0_shared, const double *d_k0, double *d_rgba,
-          float *d_rgba_f32, const int64_t *d_scatter, const bhg_polarisation *pol, double *d_qu, void *stream)
+          float *d_rgba_f32, const int64_t *d_scatter, const bhg_polarisation *pol, double *d_qu, const bhg_disk_thermal *th,
+          void *stream)
 {
     if (!sc) return fail(BHG_E_INVALID, "scene is NULL");
     if (samples <= 0 || sc->sky_w <= 0 || sc->sky_h <= 0) return fail(BHG_E_INVALID, "samples, sky_w, sky_h must be > 0");
@@ -1474,6 +1630,18 @@ int shade(bhg_context *c, const double *d_end, const double *d_end_dir, const ui
             if (rc != BHG_OK) return rc;
         }
     }
+    bhg::ThermalParams tp_th;
+    bhg::RedshiftParams rp_th;
+    bhg::ObserverParams op_th;
+    if (th) {
+        int rc = bhg::thermal_params(p, th, on ? rs : nullptr, pol, has_disk ? sc->disk_r_in : -1.0, x0_shared, &tp_th, &rp_th);
+        if (rc != BHG_OK) return rc;
+        if (!x0_shared) return fail(BHG_E_INVALID, "the thermal disk needs the shared camera origin x0_shared");
+        if (obs) {
+            rc = bhg::observer_params(p, obs, x0_shared, &op_th);
+            if (rc != BHG_OK) return rc;
+        }
+    }
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
     if (n_pixels == 0) return BHG_OK;
     if ((!d_rgba && !d_rgba_f32) || (!d_end && !d_end_dir) || !d_flags || !sc->d_sky)
@@ -1483,6 +1651,7 @@ int shade(bhg_context *c, const double *d_end, const double *d_end_dir, const ui
     if (sc->n_spheres > 0 && !d_object_id) return fail(BHG_E_INVALID, "object_id is NULL but the scene has spheres");
     if (on && !d_k0) return fail(BHG_E_INVALID, "redshift needs the camera directions d_k0");
     if (pol && (!d_qu || !d_k0)) return fail(BHG_E_INVALID, "polarisation needs d_qu and the camera directions d_k0");
+    if (th && !d_k0) return fail(BHG_E_INVALID, "the thermal disk needs the camera directions d_k0");
     ENTER_DEVICE(c->device);
     bhg::ShadeArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -1522,6 +1691,13 @@ int shade(bhg_context *c, const double *d_end, const double *d_end_dir, const ui
         a.pol = pp;
         a.pol.qu = d_qu;
         a.k0 = d_k0;
+    }
+    if (th) {
+        // the redshift instance, always: the disk's g from rs (metric, camera, sense), objects and sky as the caller's apply
+        a.th = tp_th;
+        if (!on) a.rs = rp_th;
+        a.k0 = d_k0;
+        if (obs) a.obs = op_th;
     }
     HIP_TRY(bhg::launch_shade(a, (hipStream_t)stream));
     return BHG_OK;
@@ -1566,7 +1742,7 @@ int bhg_shade_device(bhg_context *c, const double *d_end, const uint8_t *d_flags
 {
     const bhg_scene sc = sky_scene(d_sky, sky_w, sky_h);
     return shade(c, d_end, nullptr, d_flags, nullptr, n_pixels, samples, &sc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                 d_rgba, nullptr, nullptr, nullptr, nullptr, stream);
+                 d_rgba, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int bhg_shade_dir_device(bhg_context *c, const double *d_end_dir, const uint8_t *d_flags, size_t n_pixels, int32_t samples,
@@ -1575,14 +1751,14 @@ int bhg_shade_dir_device(bhg_context *c, const double *d_end_dir, const uint8_t 
 {
     const bhg_scene sc = sky_scene(d_sky, sky_w, sky_h);
     return shade(c, nullptr, d_end_dir, d_flags, nullptr, n_pixels, samples, &sc, nullptr, nullptr, nullptr, nullptr, nullptr,
-                 nullptr, d_rgba, d_rgba_f32, d_scatter, nullptr, nullptr, stream);
+                 nullptr, d_rgba, d_rgba_f32, d_scatter, nullptr, nullptr, nullptr, stream);
 }
 
 int bhg_shade_scene_device(bhg_context *c, const double *d_end, const uint8_t *d_flags, const int8_t *d_object_id,
                            size_t n_pixels, int32_t samples, const bhg_scene *sc, double *d_rgba, void *stream)
 {
     return shade(c, d_end, nullptr, d_flags, d_object_id, n_pixels, samples, sc, nullptr, nullptr, nullptr, nullptr, nullptr,
-                 nullptr, d_rgba, nullptr, nullptr, nullptr, nullptr, stream);
+                 nullptr, d_rgba, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int bhg_shade_scene_f32_device(bhg_context *c, const double *d_end, const uint8_t *d_flags, const int8_t *d_object_id,
@@ -1590,7 +1766,7 @@ int bhg_shade_scene_f32_device(bhg_context *c, const double *d_end, const uint8_
                                const int64_t *d_scatter, void *stream)
 {
     return shade(c, d_end, nullptr, d_flags, d_object_id, n_pixels, samples, sc, nullptr, nullptr, nullptr, nullptr, nullptr,
-                 nullptr, nullptr, d_rgba_f32, d_scatter, nullptr, nullptr, stream);
+                 nullptr, nullptr, d_rgba_f32, d_scatter, nullptr, nullptr, nullptr, stream);
 }
 
 int bhg_shade_scene_redshift_device(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
@@ -1599,7 +1775,7 @@ int bhg_shade_scene_redshift_device(bhg_context *c, const double *d_end, const d
                                     double *d_rgba, float *d_rgba_f32, const int64_t *d_scatter, void *stream)
 {
     return shade(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs, nullptr, nullptr, x0_shared, d_k0,
-                 d_rgba, d_rgba_f32, d_scatter, nullptr, nullptr, stream);
+                 d_rgba, d_rgba_f32, d_scatter, nullptr, nullptr, nullptr, stream);
 }
 
 int bhg_shade_scene_redshift_observer_device(bhg_context *c, const double *d_end, const double *d_end_dir,
@@ -1610,7 +1786,7 @@ int bhg_shade_scene_redshift_observer_device(bhg_context *c, const double *d_end
                                              const int64_t *d_scatter, void *stream)
 {
     return shade(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs, obs, nullptr, x0_shared, d_k0, d_rgba,
-                 d_rgba_f32, d_scatter, nullptr, nullptr, stream);
+                 d_rgba_f32, d_scatter, nullptr, nullptr, nullptr, stream);
 }
 
 int bhg_shade_scene_textured_device(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
@@ -1630,8 +1806,94 @@ int bhg_shade_scene_polarised_device(bhg_context *c, const double *d_end, const 
                                      float *d_rgba_f32, const int64_t *d_scatter, const bhg_polarisation *pol, double *d_qu,
                                      void *stream)
 {
+    return bhg_shade_scene_thermal_device(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs, obs, ot,
+                                          x0_shared, d_k0, d_rgba, d_rgba_f32, d_scatter, pol, d_qu, nullptr, stream);
+}
+
+int bhg_shade_scene_thermal_device(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
+                                   const int8_t *d_object_id, size_t n_pixels, int32_t samples, const bhg_scene *sc,
+                                   const bhg_params *p, const bhg_redshift *rs, const bhg_observer *obs,
+                                   const bhg_object_textures *ot, const double *x0_shared, const double *d_k0, double *d_rgba,
+                                   float *d_rgba_f32, const int64_t *d_scatter, const bhg_polarisation *pol, double *d_qu,
+                                   const bhg_disk_thermal *th, void *stream)
+{
     return shade(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs, obs, ot, x0_shared, d_k0, d_rgba,
-                 d_rgba_f32, d_scatter, pol, d_qu, stream);
+                 d_rgba_f32, d_scatter, pol, d_qu, th, stream);
+}
+
+int bhg_disk_thermal_device(bhg_context *c, const bhg_params *p, const bhg_disk_thermal *th, const bhg_observer *obs,
+                            const double *x0_shared, const double *d_x0, const double *d_k0, const double *d_end,
+                            const uint8_t *d_flags, size_t n, double *d_t_em, double *d_rgb, void *stream)
+{
+    // (the settings are checked before the context: a refusal names its figure with or without a device)
+    bhg::ThermalParams tp;
+    bhg::RedshiftParams rp;
+    int rc = bhg::thermal_params(p, th, nullptr, nullptr, p && p->disk_r_out > 0.0 ? p->disk_r_in : -1.0, x0_shared, &tp, &rp);
+    if (rc != BHG_OK) return rc;
+    bhg::ObserverParams op;
+    std::memset(&op, 0, sizeof(op));
+    if (obs) {
+        rc = bhg::observer_params(p, obs, x0_shared, &op);
+        if (rc != BHG_OK) return rc;
+    }
+    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
+    if (!x0_shared == !d_x0) return fail(BHG_E_INVALID, "exactly one of x0_shared / d_x0 must be given");
+    if (n == 0) return BHG_OK;
+    if (!d_k0 || !d_flags || !d_t_em || !d_rgb) return fail(BHG_E_INVALID, "d_k0 / d_flags / d_t_em / d_rgb is NULL");
+    if (n > ((size_t)1 << 39)) return fail(BHG_E_INVALID, "n too large for one launch (at most 2^39 rays)");
+    ENTER_DEVICE(c->device);
+    bhg::ThermalArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.t = tp;
+    a.p = rp;
+    a.obs = op;
+    a.x0 = d_x0;
+    a.k0 = d_k0;
+    a.end = d_end;
+    a.flags = d_flags;
+    a.t_em = d_t_em;
+    a.rgb = d_rgb;
+    a.n = n;
+    HIP_TRY(bhg::launch_disk_thermal(a, (hipStream_t)stream));
+    return BHG_OK;
+}
+
+int bhg_disk_thermal_host(bhg_context *c, const bhg_params *p, const bhg_disk_thermal *th, const bhg_observer *obs,
+                          const double *x0, int x0_is_shared, const double *k0, const double *end, const uint8_t *flags, size_t n,
+                          double *t_em, double *rgb)
+{
+    bhg::ThermalParams tp;    // (checked here too, before the context and before any copy)
+    bhg::RedshiftParams rp;
+    int rc = bhg::thermal_params(p, th, nullptr, nullptr, p && p->disk_r_out > 0.0 ? p->disk_r_in : -1.0,
+                                 x0_is_shared ? x0 : nullptr, &tp, &rp);
+    if (rc != BHG_OK) return rc;
+    if (obs) {
+        bhg::ObserverParams chk;
+        rc = bhg::observer_params(p, obs, x0_is_shared ? x0 : nullptr, &chk);
+        if (rc != BHG_OK) return rc;
+    }
+    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
+    if (!x0) return fail(BHG_E_INVALID, "x0 is NULL");
+    if (n == 0) return BHG_OK;
+    if (!k0 || !flags || !t_em || !rgb) return fail(BHG_E_INVALID, "k0 / flags / t_em / rgb is NULL");
+    ENTER_DEVICE(c->device);
+    // one block: [x0 (per ray)][k0][end][t_em][rgb] doubles, then the flags
+    const size_t nx = x0_is_shared ? 0 : n * 3, ne = end ? n * 6 : 0;
+    rc = ensure(&c->d_in, &c->d_in_bytes, (nx + n * 3 + ne + n * 4) * sizeof(double) + n);
+    if (rc != BHG_OK) return rc;
+    double *dx = (double *)c->d_in, *dk = dx + nx, *de = dk + n * 3, *dt = de + ne, *dc = dt + n;
+    uint8_t *df = (uint8_t *)(dc + n * 3);
+    if (nx) HIP_TRY(hipMemcpyAsync(dx, x0, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dk, k0, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (ne) HIP_TRY(hipMemcpyAsync(de, end, ne * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(df, flags, n, hipMemcpyHostToDevice, c->stream));
+    rc = bhg_disk_thermal_device(c, p, th, obs, x0_is_shared ? x0 : nullptr, nx ? dx : nullptr, dk, ne ? de : nullptr, df, n, dt, dc,
+                                 c->stream);
+    if (rc != BHG_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(t_em, dt, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(rgb, dc, n * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return BHG_OK;
 }
 
 int bhg_polarisation_device(bhg_context *c, const bhg_params *p, const bhg_polarisation *pol, const bhg_observer *obs,

@@ -41,6 +41,10 @@ int redshift_params(const bhg_params *p, const bhg_redshift *rs, double disk_r_i
 int observer_params(const bhg_params *p, const bhg_observer *obs, const double *x0, ObserverParams *out);
 // bhgeo_capi.hip: object textures checked against a scene of n_spheres spheres
 int object_texture_params(const bhg_object_textures *ot, int32_t n_spheres, ObjectTextureParams *out);
+// bhgeo_capi.hip: the thermal-disk settings on their own, and against the trace parameters, the disk and the camera
+int thermal_check(const bhg_disk_thermal *th);
+int thermal_params(const bhg_params *p, const bhg_disk_thermal *th, const bhg_redshift *rs, const bhg_polarisation *pol,
+                   double disk_r_in, const double *x0, ThermalParams *out, RedshiftParams *rp);
 }
 
 namespace {
@@ -214,6 +218,8 @@ struct bhg_frame {
     bool textured = false;          // bhg_frame_set_object_textures; false: the object shading without textures
     bhg_object_textures ot = {};    // its rotations, modes and strengths (tex: not used, the images are otex)
     std::vector<float> otex[BHG_MAX_SPHERES];    // host copies of the object textures, empty = white
+    bool thermal = false;           // bhg_frame_set_disk_thermal; false: the disk's colour of the scene
+    bhg_disk_thermal th = {};
     int32_t otex_w[BHG_MAX_SPHERES] = {}, otex_h[BHG_MAX_SPHERES] = {};
     // root (device of shard 0)
     DevBuf recv, perm, image;       // [n_dev * pmax][4] float, [H W] int64, [H W][4] float
@@ -666,6 +672,18 @@ int bhg_frame_set_observer(bhg_frame *f, const bhg_observer *obs)
     return BHG_OK;
 }
 
+int bhg_frame_set_disk_thermal(bhg_frame *f, const bhg_disk_thermal *th)
+{
+    if (!f) return fail(BHG_E_INVALID, "frame is NULL");
+    if (th) {
+        // what can be checked without the trace parameters (the metric, the disk and the camera are checked at every render)
+        BHG_TRY(bhg::thermal_check(th));
+        f->th = *th;
+    }
+    f->thermal = th != nullptr;
+    return BHG_OK;
+}
+
 int bhg_frame_set_object_textures(bhg_frame *f, const bhg_object_textures *ot)
 try {
     if (!f) return fail(BHG_E_INVALID, "frame is NULL");
@@ -755,6 +773,13 @@ try {
         bhg::ObjectTextureParams tp;
         BHG_TRY(bhg::object_texture_params(&ot, f->scene.n_spheres, &tp));
     }
+    const bhg_disk_thermal *th = f->thermal ? &f->th : nullptr;
+    if (th) {
+        bhg::ThermalParams tp;
+        bhg::RedshiftParams rp;
+        BHG_TRY(bhg::thermal_params(&prm, th, redshift ? &f->rs : nullptr, nullptr, has_disk ? f->scene.disk_r_in : -1.0,
+                                    f->cam.origin, &tp, &rp));
+    }
 
     // -- every device: (rays, scene images once) trace, shade + sample mean into its slab ---------------------------
     for (size_t r = 0; r < world; r++) {
@@ -799,10 +824,10 @@ try {
         fill_scene(f, s, &sc);
         bhg_object_textures ot;
         if (textured) fill_object_textures(f, &s, &ot);
-        BHG_TRY(bhg_shade_scene_textured_device(s.ctx, dir_only ? nullptr : s.end.as<double>(), dir_only ? s.dir.as<double>() : nullptr,
-                                                s.flags.as<uint8_t>(), has_obj ? s.obj.as<int8_t>() : nullptr, s.P, S, &sc, &prm,
-                                                redshift ? &f->rs : nullptr, obs, textured ? &ot : nullptr, f->cam.origin,
-                                                s.k0.as<double>(), nullptr, dst, scatter, s.stream));
+        BHG_TRY(bhg_shade_scene_thermal_device(s.ctx, dir_only ? nullptr : s.end.as<double>(), dir_only ? s.dir.as<double>() : nullptr,
+                                               s.flags.as<uint8_t>(), has_obj ? s.obj.as<int8_t>() : nullptr, s.P, S, &sc, &prm,
+                                               redshift ? &f->rs : nullptr, obs, textured ? &ot : nullptr, f->cam.origin,
+                                               s.k0.as<double>(), nullptr, dst, scatter, nullptr, nullptr, th, s.stream));
         s.dir_traced = dir_only;
     }
     // -- ONE gather onto the first device -----------------------------------------------------------------------------

@@ -643,6 +643,63 @@ __device__ __forceinline__ void polarisation_weigh(const ShadeArgs &A, uint64_t 
     qu[1] = d * (2.0 * cL * cU);
 }
 
+// ---- the thermal disk -------------------------------------------------------------------------
+// One disk ray ending at e, seen from the camera state (xc, kc): its emitted temperature t_em = T_peak tau, tau^4 =
+// F^(x) / max F^ (Page-Thorne, page_thorne), and what the camera sees of the colour-corrected blackbody f^-4 B_nu(f T) after
+// the redshift g (observer_g<OBS>: bhg_redshift_device's g, bit for bit): a blackbody at g f T, in units of k_B T_peak / h,
+//     I_c = scale sum_j w_cj nu_j^3 / (f^4 expm1(nu_j / (g f tau)))
+// At or inside r_ms everything is an exact 0 (no emission from the plunging region).  The frequency loop's bound and index are
+// wave-uniform: the table is read with scalar loads.
+template <bool OBS>
+__device__ __forceinline__ void disk_thermal(const ThermalParams &T, const RedshiftParams &P, const ObserverParams &O,
+                                             const double xc[3], const double kc[3], const double *e, double &t_em, double rgb[3])
+{
+    rgb[0] = rgb[1] = rgb[2] = 0.0;
+    t_em = 0.0;
+    const double a = P.spin;    // (0 but for Kerr): BL r of the hit, as redshift_g takes it
+    const double r = sqrt(e[0] * e[0] + e[1] * e[1] - a * a);
+    if (!(r > T.r_ms)) return;
+    const double x = sqrt(r / (0.5 * P.r_s));
+    const double tau = sqrt(sqrt(fmax(page_thorne(T, x), 0.0) * T.inv_fmax));
+    t_em = T.t_peak * tau;
+    const double g = observer_g<OBS>(P, O, xc, kc, RS_DISK, e);
+    const double y = (g * T.f_col) * tau, f2 = T.f_col * T.f_col, f4 = f2 * f2;
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int j = 0; j < T.n_nu; j++) {
+        const double nu = T.nu[j];
+        const double b = ((nu * nu) * nu) / (f4 * expm1(nu / y));
+        acc[0] = acc[0] + T.w[0][j] * b;
+        acc[1] = acc[1] + T.w[1][j] * b;
+        acc[2] = acc[2] + T.w[2][j] * b;
+    }
+    rgb[0] = T.scale * acc[0];
+    rgb[1] = T.scale * acc[1];
+    rgb[2] = T.scale * acc[2];
+}
+
+// (T_em, I_R, I_G, I_B) of one ray per thread: disk rays their own, NaN rays (and disk rays without an end record) NaN, every
+// other ray 0
+template <bool OBS>
+__global__ void __launch_bounds__(256) disk_thermal_kernel(const ThermalArgs A)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= A.n) return;
+    const int cls = ray_class(A.flags[i]);
+    const double *e = A.end ? A.end + i * 6 : nullptr;
+    double t, rgb[3];
+    if (cls != RS_DISK || !e) {
+        t = (cls == RS_NAN || cls == RS_DISK) ? __builtin_nan("") : 0.0;
+        rgb[0] = rgb[1] = rgb[2] = t;
+    } else {
+        const double *xc = A.x0 ? A.x0 + i * 3 : A.p.x0;
+        disk_thermal<OBS>(A.t, A.p, A.obs, xc, A.k0 + i * 3, e, t, rgb);
+    }
+    A.t_em[i] = t;
+    A.rgb[i * 3 + 0] = rgb[0];
+    A.rgb[i * 3 + 1] = rgb[1];
+    A.rgb[i * 3 + 2] = rgb[2];
+}
+
 // the shade kernels' redshift instances: rgb *= g^n for a ray of a class the caller selected (OBS: the moving observer's g)
 template <bool OBS>
 __device__ __forceinline__ void redshift_weigh(const ShadeArgs &A, uint64_t i, int cls, uint32_t bit, const double *e, double rgb[3])
@@ -662,7 +719,9 @@ __device__ __forceinline__ void redshift_weigh(const ShadeArgs &A, uint64_t i, i
 // RS: the redshift instance (rgb *= g^n by class); without it the kernels are the frame path's as they were.  OBS (with RS
 // only): g is the moving observer's.  TEX: object rays take the textured colour (object_colour_tex); nothing else differs.
 // POL: a disk ray also gets its Stokes weights qu = (delta cos 2chi, delta sin 2chi), every other ray (0, 0); rgb is untouched.
-template <bool RS, bool OBS, bool TEX, bool POL>
+// THERM (with RS only): a disk ray's colour is its thermal emission (disk_thermal, g already in it: the disk bit of rs.apply
+// is not applied again); objects and sky as rs.apply says.
+template <bool RS, bool OBS, bool TEX, bool POL, bool THERM>
 __device__ __forceinline__ void ray_colour(const ShadeArgs &A, uint64_t i, uint8_t fl, double c0, double c1, double c2, double rgb[3],
                                            double qu[2])
 {
@@ -671,8 +730,13 @@ __device__ __forceinline__ void ray_colour(const ShadeArgs &A, uint64_t i, uint8
     if (fl & BHG_FLAG_HIT_HORIZON_) return;
     const double *e = A.end + i * 6;
     if (fl == BHG_FLAG_HIT_DISK_ && A.disk_r_out > 0.0 && A.end) {
-        disk_colour(A, e, rgb);
-        if (RS) redshift_weigh<OBS>(A, i, RS_DISK, BHG_REDSHIFT_DISK_, e, rgb);
+        if (THERM) {
+            double t_em;
+            disk_thermal<OBS>(A.th, A.rs, A.obs, A.rs.x0, A.k0 + i * 3, e, t_em, rgb);
+        } else {
+            disk_colour(A, e, rgb);
+            if (RS) redshift_weigh<OBS>(A, i, RS_DISK, BHG_REDSHIFT_DISK_, e, rgb);
+        }
         if (POL) polarisation_weigh(A, i, e, qu);
         return;
     }
@@ -730,7 +794,7 @@ __device__ __forceinline__ void write_stokes(const ShadeArgs &A, uint64_t p, con
 // the kernel is a latency chain per ray, not a bandwidth problem (131 MB in, 16 MB out per config-2 frame).
 // POL: each thread also stages the six Stokes products (Q, then U, of each channel; 9 doubles per thread in all, 18 KB per
 // workgroup) and the pixel's Q / U means go to pol.qu[p].
-template <bool RS, bool OBS, bool TEX, bool POL>
+template <bool RS, bool OBS, bool TEX, bool POL, bool THERM>
 __global__ void __launch_bounds__(256) shade_reduce_kernel(const ShadeArgs A, const uint32_t ppb)
 {
     __shared__ double col[256 * 3];
@@ -746,13 +810,13 @@ __global__ void __launch_bounds__(256) shade_reduce_kernel(const ShadeArgs A, co
         double rgb[3];
         if (POL) {
             double qu[2];
-            ray_colour<RS, OBS, TEX, POL>(A, i, A.flags[i], d[0], d[1], d[2], rgb, qu);
+            ray_colour<RS, OBS, TEX, POL, THERM>(A, i, A.flags[i], d[0], d[1], d[2], rgb, qu);
             for (int c = 0; c < 3; c++) {
                 pcol[t * 6 + c] = qu[0] * rgb[c];
                 pcol[t * 6 + 3 + c] = qu[1] * rgb[c];
             }
         } else {
-            ray_colour<RS, OBS, TEX, POL>(A, i, A.flags[i], d[0], d[1], d[2], rgb, nullptr);
+            ray_colour<RS, OBS, TEX, POL, THERM>(A, i, A.flags[i], d[0], d[1], d[2], rgb, nullptr);
         }
         col[t * 3 + 0] = rgb[0];
         col[t * 3 + 1] = rgb[1];
@@ -781,7 +845,7 @@ __global__ void __launch_bounds__(256) shade_reduce_kernel(const ShadeArgs A, co
 }
 
 // More samples than a workgroup has threads: one thread per pixel, samples accumulated in registers in sample order.
-template <bool RS, bool OBS, bool TEX, bool POL>
+template <bool RS, bool OBS, bool TEX, bool POL, bool THERM>
 __global__ void __launch_bounds__(256) shade_reduce_serial_kernel(const ShadeArgs A)
 {
     const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -792,7 +856,7 @@ __global__ void __launch_bounds__(256) shade_reduce_serial_kernel(const ShadeArg
         const uint64_t i = (uint64_t)s * A.n_pixels + p;
         const double *d = A.dir ? A.dir + i * 3 : A.end + i * 6 + 3;
         double rgb[3], qu[2];
-        ray_colour<RS, OBS, TEX, POL>(A, i, A.flags[i], d[0], d[1], d[2], rgb, qu);
+        ray_colour<RS, OBS, TEX, POL, THERM>(A, i, A.flags[i], d[0], d[1], d[2], rgb, qu);
         acc[0] += rgb[0];
         acc[1] += rgb[1];
         acc[2] += rgb[2];
@@ -872,30 +936,47 @@ hipError_t launch_polarisation(const PolarisationArgs &a, bool obs, hipStream_t 
     return hipGetLastError();
 }
 
-// one instance per (redshift, observer, textures, polarisation): the template flags are the launch's run-time switches
-template <bool RS, bool OBS, bool TEX, bool POL>
+hipError_t launch_disk_thermal(const ThermalArgs &a, hipStream_t s)
+{
+    if (a.n == 0) return hipSuccess;
+    if (a.obs.on)
+        BHG_LAUNCH(disk_thermal_kernel<true>, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
+    else
+        BHG_LAUNCH(disk_thermal_kernel<false>, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// one instance per (redshift, observer, textures, polarisation, thermal): the template flags are the launch's run-time switches
+template <bool RS, bool OBS, bool TEX, bool POL, bool THERM>
 void launch_shade_instance(const ShadeArgs &a, hipStream_t s)
 {
     if (a.samples > 256) {
         const dim3 grid((unsigned)((a.n_pixels + 255) / 256));
-        BHG_LAUNCH((shade_reduce_serial_kernel<RS, OBS, TEX, POL>), grid, dim3(256), 0, s, a);
+        BHG_LAUNCH((shade_reduce_serial_kernel<RS, OBS, TEX, POL, THERM>), grid, dim3(256), 0, s, a);
         return;
     }
     const uint32_t ppb = 256u / (uint32_t)a.samples;      // pixels per workgroup
     const dim3 grid((unsigned)((a.n_pixels + ppb - 1) / ppb));
-    BHG_LAUNCH((shade_reduce_kernel<RS, OBS, TEX, POL>), grid, dim3(256), 0, s, a, ppb);
+    BHG_LAUNCH((shade_reduce_kernel<RS, OBS, TEX, POL, THERM>), grid, dim3(256), 0, s, a, ppb);
 }
 
+// the thermal instances are redshift instances (the disk's emission needs g); THERM = true is instantiated with RS = true only
 template <bool TEX, bool POL>
 void launch_shade_tex(const ShadeArgs &a, hipStream_t s)
 {
-    const bool rs = a.rs.apply != 0, obs = rs && a.obs.on;
-    if (obs)
-        launch_shade_instance<true, true, TEX, POL>(a, s);
-    else if (rs)
-        launch_shade_instance<true, false, TEX, POL>(a, s);
-    else
-        launch_shade_instance<false, false, TEX, POL>(a, s);
+    const bool therm = a.th.on != 0, rs = a.rs.apply != 0 || therm, obs = rs && a.obs.on;
+    if (therm) {
+        if (obs)
+            launch_shade_instance<true, true, TEX, POL, true>(a, s);
+        else
+            launch_shade_instance<true, false, TEX, POL, true>(a, s);
+    } else if (obs) {
+        launch_shade_instance<true, true, TEX, POL, false>(a, s);
+    } else if (rs) {
+        launch_shade_instance<true, false, TEX, POL, false>(a, s);
+    } else {
+        launch_shade_instance<false, false, TEX, POL, false>(a, s);
+    }
 }
 
 hipError_t launch_shade(const ShadeArgs &a, hipStream_t s)

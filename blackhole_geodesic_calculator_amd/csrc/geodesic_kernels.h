@@ -121,6 +121,36 @@ struct PolarisationParams {
     double *qu;        // shade kernels: [n_pixels][6] (Q_r, Q_g, Q_b, U_r, U_g, U_b) fp64
 };
 
+// the thermal disk (frame_kernels.hip, disk_thermal): the Page-Thorne constants the C layer computed for
+// the caller's (a*, sense), the frequency table and the channel weights.  The metric, the camera and the sense are the
+// RedshiftParams beside it (g is redshift_kernel's).  on = 0: the shade kernels' non-thermal instances are launched and never
+// read this struct
+constexpr int BHG_THERMAL_NU_MAX_ = 16;
+struct ThermalParams {
+    double nu[BHG_THERMAL_NU_MAX_];      // nu_j h / (k_B T_peak)
+    double w[3][BHG_THERMAL_NU_MAX_];    // the R, G, B weights of each frequency
+    double astar;      // a* = s a / M, s = -disk_sense (section 9's sense)
+    double x0;         // sqrt(r_ms / M)
+    double xr[3];      // the roots x_1, x_2, x_3 of x^3 - 3x + 2a*
+    double c[3];       // c_i = 3 (x_i - a*)^2 / (x_i (x_i - x_j)(x_i - x_k)); 0 for the root x_i = 0 (a* = 0)
+    double inv_fmax;   // 1 / max F^
+    double r_ms;       // the innermost stable circular orbit of the family (BL r)
+    double t_peak, f_col, scale;
+    int32_t n_nu;      // 1 .. BHG_THERMAL_NU_MAX_
+    int32_t on;
+};
+
+// The Page-Thorne flux shape F^(x), x = sqrt(r / M) > x0 (the caller keeps r > r_ms).  Host (the C layer's search for max F^)
+// and device share it; written out operation by operation as tests/disk_thermal_reference.py restates it: the library is
+// built with -ffp-contract=off, and near r_ms the bracket is a difference of terms of order (x - x0), so the order shows.
+__host__ __device__ inline double page_thorne(const ThermalParams &T, double x)
+{
+    const double x2 = x * x;
+    double b = (x - T.x0) - (1.5 * T.astar) * log(x / T.x0);
+    for (int i = 0; i < 3; i++) b = b - T.c[i] * log((x - T.xr[i]) / (T.x0 - T.xr[i]));
+    return b / ((x2 * x2) * ((x2 * x - 3.0 * x) + 2.0 * T.astar));
+}
+
 // camera-ray generation (frame_kernels.hip)
 struct RaygenArgs {
     const double *jitter;   // [S*H*W*2] MT19937 doubles, sample-major then row-major pixels, (u1, u2); nullptr = pixel
@@ -186,9 +216,12 @@ struct ShadeArgs {
     ObserverParams obs;    // beta and on only: the redshift instance's g is the moving observer's (rs.apply != 0 only)
     // object textures (bhg_shade_scene_textured_device): launch_shade takes the textured instance when ot.on != 0
     ObjectTextureParams ot;
-    // polarisation (bhg_shade_scene_polarised_device): launch_shade takes the polarised instance when pol.on != 0; last, so
-    // that no other member moves
+    // polarisation (bhg_shade_scene_polarised_device): launch_shade takes the polarised instance when pol.on != 0
     PolarisationParams pol;
+    // the thermal disk (bhg_shade_scene_thermal_device): launch_shade takes the thermal instance when th.on != 0 -- always a
+    // redshift instance, rs (metric, camera, sense) filled and rs.apply as the caller gave it or 0; last, so that no other
+    // member moves
+    ThermalParams th;
 };
 
 // one thread per ray: (chi, delta, mu) from the camera state (x0, k0) and the end record (bhg_polarisation_device)
@@ -202,10 +235,25 @@ struct PolarisationArgs {
     uint64_t n;
 };
 
+// one thread per ray: T_em and (I_R, I_G, I_B) from the camera state (x0, k0) and the end record (bhg_disk_thermal_device)
+struct ThermalArgs {
+    ThermalParams t;
+    RedshiftParams p;      // metric, camera, sense (apply unused): the disk g
+    ObserverParams obs;    // beta and on only: g of a moving observer
+    const double *x0;      // [n][3] or nullptr -> p.x0
+    const double *k0;      // [n][3]
+    const double *end;     // [n][6] or nullptr (then disk rays get NaN)
+    const uint8_t *flags;  // [n]
+    double *t_em;          // [n]
+    double *rgb;           // [n][3]
+    uint64_t n;
+};
+
 hipError_t launch_raygen(const RaygenArgs &a, hipStream_t s);
 hipError_t launch_shade(const ShadeArgs &a, hipStream_t s);
 hipError_t launch_redshift(const RedshiftArgs &a, hipStream_t s);
 hipError_t launch_polarisation(const PolarisationArgs &a, bool obs, hipStream_t s);
+hipError_t launch_disk_thermal(const ThermalArgs &a, hipStream_t s);
 hipError_t launch_split_end(const double *end, uint64_t n, double *loc, double *dir, hipStream_t s);
 hipError_t launch_gather_rows4(const float *src, const int64_t *index, uint64_t n, float *dst, hipStream_t s);
 

@@ -86,6 +86,7 @@ class DeviceFrame:
         self._ray_key = None     # what the observer rays in d_k0 were made for: (origin, r_s, spin, rhs_form)
         self.polarisation = None      # _ffi.Polarisation (set_polarisation) or None: off
         self.d_qu = None              # [P, 6] fp64 Stokes Q / U images (shade_stokes)
+        self.disk_thermal = None      # _ffi.DiskThermal (set_disk_thermal) or None: the disk's colour of the scene
         self.object_textures = None   # set_object_textures: (device textures per sphere, rotations, modes, emission) or None
 
     def _stream(self):
@@ -148,6 +149,17 @@ class DeviceFrame:
             self.polarisation = None
             return
         self.polarisation = _ffi.make_polarisation(degree, disk_sense, self.rot @ np.array([0.0, 1.0, 0.0]))
+
+    def set_disk_thermal(self, t_peak=None, nu=None, weights=None, f_col=1.0, scale=1.0, disk_sense=1):
+        """The thermal disk in every later shade (bhg_shade_scene_thermal_device): a disk ray's colour is
+        the redshifted Novikov-Thorne blackbody of peak temperature t_peak [K] weighed per channel over the frequencies nu [Hz]
+        (make_disk_thermal; narrowband() gives one frequency per channel).  t_peak may also be a DiskThermal.  None: off."""
+        if t_peak is None:
+            self.disk_thermal = None
+        elif isinstance(t_peak, _ffi.DiskThermal):
+            self.disk_thermal = t_peak
+        else:
+            self.disk_thermal = _ffi.make_disk_thermal(t_peak, nu, weights, f_col, scale, disk_sense)
 
     def set_object_textures(self, textures=None, rotations=None, modes=None, emission=None):
         """Textured, oriented and emissive object spheres (bhg_shade_scene_textured_device), per sphere of
@@ -245,16 +257,17 @@ class DeviceFrame:
         return traced
 
     def _shade(self, d_rgba=0, d_rgba_f32=0, scatter=None, pol=None, d_qu=0):
-        """The one shade call of every output (bhg_shade_scene_polarised_device): redshift, the observer, the object textures
-        and the polarisation (shade_stokes only) as set, each None when off -- pol = None is the textured call exactly."""
+        """The one shade call of every output (bhg_shade_scene_thermal_device): redshift, the observer, the object textures,
+        the polarisation (shade_stokes only) and the thermal disk as set, each None when off -- pol = None and no thermal disk
+        is the textured call exactly."""
         form = self._shade_form()
-        self.ctx.shade_scene_polarised_device(self.d_end.data_ptr() if form == "end" else 0, self.d_flags.data_ptr(), self.P, self.S,
-                                              self.scene(), self._params, self.redshift, self.observer,
-                                              self._object_textures() if self._textured() else None, pol, d_qu,
-                                              x0_shared=self.origin, d_k0=self.d_k0.data_ptr(), d_rgba=d_rgba, d_rgba_f32=d_rgba_f32,
-                                              d_object_id=0 if self.d_obj is None else self.d_obj.data_ptr(),
-                                              d_scatter=0 if scatter is None else scatter.data_ptr(),
-                                              d_end_dir=self.d_dir.data_ptr() if form == "dir" else 0, stream=self._stream())
+        self.ctx.shade_scene_thermal_device(self.d_end.data_ptr() if form == "end" else 0, self.d_flags.data_ptr(), self.P, self.S,
+                                            self.scene(), self._params, self.redshift, self.observer,
+                                            self._object_textures() if self._textured() else None, pol, d_qu, self.disk_thermal,
+                                            x0_shared=self.origin, d_k0=self.d_k0.data_ptr(), d_rgba=d_rgba, d_rgba_f32=d_rgba_f32,
+                                            d_object_id=0 if self.d_obj is None else self.d_obj.data_ptr(),
+                                            d_scatter=0 if scatter is None else scatter.data_ptr(),
+                                            d_end_dir=self.d_dir.data_ptr() if form == "dir" else 0, stream=self._stream())
 
     def shade(self):
         self._shade(d_rgba=self.d_rgba.data_ptr())
@@ -343,6 +356,11 @@ class FrameBatch:
         """DeviceFrame.set_redshift for every member frame."""
         for f in self.frames:
             f.set_redshift(apply, exponent, disk_sense)
+
+    def set_disk_thermal(self, t_peak=None, nu=None, weights=None, f_col=1.0, scale=1.0, disk_sense=1):
+        """DeviceFrame.set_disk_thermal for every member frame."""
+        for f in self.frames:
+            f.set_disk_thermal(t_peak, nu, weights, f_col, scale, disk_sense)
 
     def shade(self):
         return [f.shade() for f in self.frames]

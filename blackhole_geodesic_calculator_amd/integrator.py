@@ -64,7 +64,7 @@ class GeodesicIntegratorSchwarzschild:
 
     # ------------------------------------------------------------------------------------
     def trace(self, k0, x0, max_step=np.inf, curve_end=50.0, r_exit=0.0, disk=None, spheres=None, redshift=None,
-              polarisation=None):
+              polarisation=None, disk_thermal=None):
         """Batched solve.  k0[N,3] (or [...,3]); x0[3] shared origin or same leading shape as k0.
         r_exit: outward sphere-exit radius (Limited engine's ray_trace, Limited...py:273-278);
         disk=(R_in, R_out): thin disk in z = 0, first crossing inside the annulus ends the ray with
@@ -86,6 +86,12 @@ class GeodesicIntegratorSchwarzschild:
                                        polarisation angle at the camera (from image up towards image left, in (-pi/2, pi/2]),
                                        its degree (the table at mu) and emission cosine; NaN for NaN rays, 0 for every ray
                                        that is not a disk ray (bhg_polarisation_host)
+            t_em[...], thermal_rgb[..., 3]
+                                       only with disk_thermal=dict(t_peak=..., nu=..., weights=..., f_col=..., scale=...,
+                                       disk_sense=...): the disk ray's emitted Novikov-Thorne temperature [K] and the
+                                       redshifted blackbody the camera sees, weighed per channel (0 at and inside r_ms; NaN for
+                                       NaN rays, 0 for every ray that is not a disk ray; bhg_disk_thermal_host; DESIGN.md
+                                       section 13)
         """
         k0 = np.asarray(k0, dtype=np.float64)
         lead = k0.shape[:-1]
@@ -114,6 +120,10 @@ class GeodesicIntegratorSchwarzschild:
             pol = _ffi.make_polarisation(**polarisation)
             chi, deg, mu = self._ctx.polarisation(k0f, x0f, self.params(max_step, curve_end, r_exit, disk), pol, None, flags, end)
             out["evpa"], out["pol_degree"], out["mu_em"] = chi.reshape(lead), deg.reshape(lead), mu.reshape(lead)
+        if disk_thermal is not None:
+            th = _ffi.make_disk_thermal(**disk_thermal)
+            t_em, rgb = self._ctx.disk_thermal(k0f, x0f, self.params(max_step, curve_end, r_exit, disk), th, None, flags, end)
+            out["t_em"], out["thermal_rgb"] = t_em.reshape(lead), rgb.reshape(lead + (3,))
         return out
 
     # ------------------------------------------------------------------------------------

@@ -58,7 +58,9 @@ extern "C" {
                                   BHG_OBJECT_TEXTURES (bhg_shade_scene_textured_device, bhg_frame_set_object_textures,
                                   bhg_object_textures_size, struct bhg_object_textures);
                                   BHG_POLARISATION (bhg_polarisation_device / _host, bhg_shade_scene_polarised_device,
-                                  bhg_polarisation_size, struct bhg_polarisation).
+                                  bhg_polarisation_size, struct bhg_polarisation);
+                                  BHG_DISK_THERMAL (bhg_disk_thermal_device / _host, bhg_shade_scene_thermal_device,
+                                  bhg_frame_set_disk_thermal, bhg_disk_thermal_size, struct bhg_disk_thermal).
                                9: redshift -- bhg_redshift_device / _host, bhg_shade_scene_redshift_device, bhg_frame_set_redshift,
                                   bhg_redshift_size, struct bhg_redshift;
                                   nothing of ABI 8 changed.
@@ -645,6 +647,59 @@ int bhg_shade_scene_polarised_device(bhg_context *ctx, const double *d_end, cons
                                      const bhg_object_textures *ot, const double *x0_shared, const double *d_k0, double *d_rgba,
                                      float *d_rgba_f32, const int64_t *d_scatter, const bhg_polarisation *pol, double *d_qu,
                                      void *stream);
+
+/* --- the thermal disk (within ABI 10) ----------------------------------------------------------
+ * The thin disk as a Novikov-Thorne disk: the Page-Thorne (1974) flux of the circular-orbit family redshift's disk moves on
+ * (sense disk_sense, section 9; a* = s a / M with s = -disk_sense, M = r_s / 2, Kerr's BL r = sqrt(R^2 - a^2) of the hit,
+ * Schwarzschild's r = R), zero at and inside the family's r_ms (Bardeen-Press-Teukolsky), as a temperature
+ *     T(r) = t_peak (F(r) / max F)^(1/4)       (max over the disk's family, found by the library in double)
+ * and the colour-corrected blackbody f_col^-4 B_nu(f_col T) it emits, which the camera sees redshifted by the ray's g (the g of
+ * bhg_redshift_device, with obs that of bhg_redshift_observer_device): a blackbody at g f_col T.  The library ships no colour
+ * data: each of R, G, B is a weighted sum over the caller's n_nu frequencies nu_j [Hz] (weights of any sign), in units of
+ * nu0 = k_B t_peak / h:
+ *     I_c = scale sum_j weight[c][j] nuh_j^3 / (f_col^4 expm1(nuh_j / (g f_col tau))),  nuh_j = nu_j / nu0,  tau = T / t_peak
+ * Per ray, by flags: BHG_FLAG_HIT_DISK rays (T, I_R, I_G, I_B), 0 at and inside r_ms; BHG_FLAG_NAN rays, and disk rays without an
+ * end record, NaN; every other ray 0.  In the shade, (I_R, I_G, I_B) replaces a disk ray's colour (texture and radial profile
+ * are not used) and is not weighted by g^n again; objects and sky are weighted as rs says; Q / U (pol) take it as the ray's I.
+ * Refused (BHG_E_INVALID, the message names the figure), before the context: disk_sense other than +-1; n_nu outside
+ * [1, BHG_THERMAL_NU_MAX]; a nu that is not finite or not > 0; a weight that is not finite; t_peak or f_col not finite or not
+ * > 0; scale not finite; time_like = 1; a disk r_in at or inside the photon orbit of the traced sense (section 9's rule); a
+ * redshift or polarisation disk_sense that differs from this one; a shared camera at or inside the horizon, inside the Kerr
+ * ergosurface or exactly on the Kerr BL axis (section 10's rules).
+ * Member order: disk_sense, n_nu, t_peak, f_col, scale, nu, weight (544 bytes). */
+#define BHG_DISK_THERMAL 1
+#define BHG_THERMAL_NU_MAX 16
+typedef struct bhg_disk_thermal {
+    int32_t disk_sense;                             /* +1 / -1, bhg_redshift's meaning */
+    int32_t n_nu;                                   /* 1 .. BHG_THERMAL_NU_MAX */
+    double t_peak;                                  /* the largest emitted temperature over the disk [K] */
+    double f_col;                                   /* colour correction (1: a plain blackbody) */
+    double scale;                                   /* overall factor of I_c */
+    double nu[BHG_THERMAL_NU_MAX];                  /* frequencies [Hz], shared by the channels */
+    double weight[3][BHG_THERMAL_NU_MAX];           /* R, G, B weights of each frequency */
+} bhg_disk_thermal;
+size_t bhg_disk_thermal_size(void);
+/* Per ray, from the camera state (x0_shared [3] HOST, or d_x0 [n][3]; d_k0 [n][3]), d_end [n][6] (or NULL) and d_flags [n]:
+ * d_t_em [n] = T [K], d_rgb [n][3] = (I_R, I_G, I_B).  obs NULL: the ZAMO's g.  One launch on stream; no context workspace. */
+int bhg_disk_thermal_device(bhg_context *ctx, const bhg_params *p, const bhg_disk_thermal *th, const bhg_observer *obs,
+                            const double *x0_shared, const double *d_x0, const double *d_k0, const double *d_end,
+                            const uint8_t *d_flags, size_t n, double *d_t_em, double *d_rgb, void *stream);
+/* bhg_disk_thermal_device on host arrays (x0 [3] with x0_is_shared != 0, else [n][3]; end may be NULL). */
+int bhg_disk_thermal_host(bhg_context *ctx, const bhg_params *p, const bhg_disk_thermal *th, const bhg_observer *obs,
+                          const double *x0, int x0_is_shared, const double *k0, const double *end, const uint8_t *flags, size_t n,
+                          double *t_em, double *rgb);
+/* bhg_shade_scene_polarised_device with the thermal disk: a disk ray's colour is its I_c (above).  th = NULL is exactly the
+ * polarised call (which is this call with th = NULL: one implementation, one checking order: after step 3b, th against p, the
+ * scene's disk, the redshift's and polarisation's disk_sense, x0_shared -- which it needs -- and obs; in step 6, d_k0). */
+int bhg_shade_scene_thermal_device(bhg_context *ctx, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
+                                   const int8_t *d_object_id, size_t n_pixels, int32_t samples, const bhg_scene *scene,
+                                   const bhg_params *p, const bhg_redshift *rs, const bhg_observer *obs,
+                                   const bhg_object_textures *ot, const double *x0_shared, const double *d_k0, double *d_rgba,
+                                   float *d_rgba_f32, const int64_t *d_scatter, const bhg_polarisation *pol, double *d_qu,
+                                   const bhg_disk_thermal *th, void *stream);
+/* The thermal disk in every later render of the frame (its shade calls are bhg_shade_scene_thermal_device).  NULL: off, the
+ * frame as without it.  The settings that need no trace parameters are checked here, the rest at every render. */
+int bhg_frame_set_disk_thermal(bhg_frame *frame, const bhg_disk_thermal *th);
 
 /* Acceleration probe: acc[n][3] = -Gamma^i_{mu nu} k^mu k^nu at (x[n][3], k[n][3]); host buffers.
  * Lets tests compare the device RHS with the oracle's term by term.  With rhs_form = BHG_RHS_KERR_BL the triples

@@ -1,0 +1,402 @@
+"""The thermal disk on the GPU: bhg_disk_thermal_device / _host against the numpy restatement
+(tests/disk_thermal_reference.py) on the library's own traces, the redshift recovered from the colour alone, the thermal shade
+(bit for bit the per-ray colour at one sample, against the restatement's shade in every redshift / observer / texture /
+polarisation combination), "off is today", the library frame against DeviceFrame, the Doppler colour of an edge-on disk, and
+the Python adaptors."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import frame_rays
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import disk_thermal_reference as dt  # noqa: E402
+import polarisation_reference as pr  # noqa: E402
+import redshift_reference as rr  # noqa: E402
+
+INC = np.radians(60.0)
+CAM = np.array([30 * np.sin(INC), 0.0, 30 * np.cos(INC)])
+BETA = (0.3, -0.2, 0.1)
+T_PEAK, F_COL, SCALE = 1.2e4, 1.7, 2.5
+NU = (3.0e14, 6.0e14, 1.0e15, 1.5e15)
+W = np.array([[1.0, 0.5, 0.1, 0.0], [0.2, 1.0, 0.4, 0.1], [0.0, 0.1, 0.6, 1.0]])
+
+
+def _ffi():
+    from blackhole_geodesic_calculator_amd import _ffi as f
+    return f
+
+
+def _inclined_rays(n, seed=0, fov=0.7, inc=INC):
+    k = frame_rays(n, seed, fov)
+    c, s = np.cos(inc), np.sin(inc)
+    R = np.array([[c, 0, s], [0, 1, 0], [-s, 0, c]])
+    return k @ R.T
+
+
+def _th(sense=1, nu=NU, w=W):
+    return _ffi().make_disk_thermal(T_PEAK, nu, w, F_COL, SCALE, sense)
+
+
+def _g(ctx, k0, x0, p, sense, obs, flags, end):
+    """bhg_redshift_device's g (with obs bhg_redshift_observer_device's): the number the thermal disk takes."""
+    rs = _ffi().make_redshift(disk_sense=sense)
+    return ctx.redshift(k0, x0, p, rs, flags, end) if obs is None else ctx.redshift_observer(k0, x0, p, rs, obs, flags, end)
+
+
+def _device_thermal(ctx, p, th, obs, k0, end, flags, x0):
+    """bhg_disk_thermal_device, checked against the host form (the same launch) and returned."""
+    import torch
+    d_k0 = torch.as_tensor(np.ascontiguousarray(k0)).cuda()
+    d_end = None if end is None else torch.as_tensor(np.ascontiguousarray(end)).cuda()
+    d_fl = torch.as_tensor(np.ascontiguousarray(flags)).cuda()
+    t = torch.empty(len(k0), dtype=torch.float64, device="cuda")
+    rgb = torch.empty((len(k0), 3), dtype=torch.float64, device="cuda")
+    shared = np.asarray(x0).ndim == 1
+    d_x0 = None if shared else torch.as_tensor(np.ascontiguousarray(x0)).cuda()
+    ctx.disk_thermal_device(p, th, obs, len(k0), d_k0.data_ptr(), d_fl.data_ptr(), t.data_ptr(), rgb.data_ptr(),
+                            x0_shared=x0 if shared else None, d_x0=0 if shared else d_x0.data_ptr(),
+                            d_end=0 if d_end is None else d_end.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    t, rgb = t.cpu().numpy(), rgb.cpu().numpy()
+    ht, hrgb = ctx.disk_thermal(k0, x0, p, th, obs, flags, end)
+    assert np.array_equal(t, ht, equal_nan=True) and np.array_equal(rgb, hrgb, equal_nan=True)
+    return t, rgb
+
+
+def _close(a, b, rtol=1e-12):
+    """a == b where b is 0 or NaN; elsewhere within rtol of b, with a floor of rtol times b's largest value (rays at the inner
+    edge, where tau is small and the flux bracket a near cancellation)."""
+    assert np.array_equal(np.isnan(a), np.isnan(b))
+    z = b == 0.0
+    assert np.all(a[z] == 0.0)
+    ok = ~np.isnan(b) & ~z
+    scale = np.abs(b[ok]).max()
+    assert np.all(np.abs(a[ok] - b[ok]) <= rtol * np.maximum(np.abs(b[ok]), scale)), np.abs(a[ok] / b[ok] - 1).max()
+
+
+def _mix(flags, seed):
+    rng = np.random.default_rng(seed)
+    fl = flags.copy()
+    idx = rng.permutation(len(fl))[: len(fl) // 3]
+    fl[idx] = rng.choice(np.array([1, 3, 0x88, 8, 4, 16, 64, 65], np.uint8), len(idx))
+    return fl
+
+
+CASES = [
+    # name, rhs, spin (r_s = 1), sense, beta
+    ("schw", 0, 0.0, 1, None),
+    ("schw_reduced", 1, 0.0, -1, None),
+    ("kerr_pro", 2, 0.45, -1, None),
+    ("kerr_retro", 2, 0.45, 1, None),
+    ("schw_obs", 0, 0.0, 1, BETA),
+    ("kerr_obs", 2, 0.45, -1, BETA),
+]
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
+def test_per_ray_against_restatement(ctx, case):
+    f = _ffi()
+    name, rhs, spin, sense, beta = case
+    k0 = _inclined_rays(2500, seed=5)
+    p = f.make_params(r_s=1.0, lambda_end=80.0, r_exit=40.0, rhs_form=rhs, spin=spin, disk_r_in=3.0, disk_r_out=9.0)
+    end, flags = ctx.trace(k0, CAM, p)[:2]
+    assert (flags == 128).sum() > 300
+    th = _th(sense)
+    obs = f.make_observer(beta)
+    for fl in (flags, _mix(flags, 3)):
+        t, rgb = _device_thermal(ctx, p, th, obs, k0, end, fl, CAM)
+        g = _g(ctx, k0, CAM, p, sense, obs, fl, end)
+        wt, wrgb = dt.thermal_rays(end, fl, g, 1.0, spin, rhs == 2, sense, T_PEAK, NU, W, F_COL, SCALE)
+        _close(t, wt)
+        for c in range(3):
+            _close(rgb[:, c], wrgb[:, c])
+        assert np.all(t[fl == 128] >= 0.0) and (t[fl == 128] > 0.0).sum() > 100
+    if name == "kerr_retro":          # r_ms = 4.35 r_s > r_in: the plunging region is dark, exactly
+        t, rgb = _device_thermal(ctx, p, th, obs, k0, end, flags, CAM)
+        d = flags == 128
+        r = np.zeros(len(flags))
+        r[d] = np.sqrt(end[d, 0] ** 2 + end[d, 1] ** 2 - spin ** 2)
+        inside = d & (r < 4.3)
+        assert inside.sum() > 20 and np.all(t[inside] == 0.0) and np.all(rgb[inside] == 0.0)
+    # no end records: disk rays NaN
+    t, rgb = _device_thermal(ctx, p, th, obs, k0, None, flags, CAM)
+    assert np.all(np.isnan(t[flags == 128])) and np.all(np.isnan(rgb[flags == 128]))
+    if name in ("schw", "kerr_pro"):
+        x0 = np.tile(CAM, (len(k0), 1)) * np.linspace(0.8, 1.2, len(k0))[:, None]
+        end, flags = ctx.trace(k0, x0, p)[:2]
+        t, rgb = _device_thermal(ctx, p, th, obs, k0, end, flags, x0)
+        g = _g(ctx, k0, x0, p, sense, obs, flags, end)
+        wt, wrgb = dt.thermal_rays(end, flags, g, 1.0, spin, rhs == 2, sense, T_PEAK, NU, W, F_COL, SCALE)
+        _close(t, wt)
+        _close(rgb, wrgb)
+
+
+@pytest.mark.parametrize("rhs,spin,sense,beta", [(0, 0.0, 1, None), (2, 0.45, -1, None), (2, 0.45, 1, BETA), (0, 0.0, -1, BETA)])
+def test_colour_alone_gives_the_redshift(ctx, rhs, spin, sense, beta):
+    """Narrow-band channels: each disk ray's R / B ratio is that of a blackbody at T_obs; T_obs / (f_col T_em) is the ray's g."""
+    from scipy.optimize import brentq
+    f = _ffi()
+    k0 = _inclined_rays(1500, seed=11)
+    p = f.make_params(r_s=1.0, lambda_end=80.0, r_exit=40.0, rhs_form=rhs, spin=spin, disk_r_in=3.0, disk_r_out=9.0)
+    end, flags = ctx.trace(k0, CAM, p)[:2]
+    obs = f.make_observer(beta)
+    nu_r, nu_b = 2.0e14, 9.0e14
+    th = f.make_disk_thermal(T_PEAK, *f.narrowband(nu_r, 5.0e14, nu_b), f_col=F_COL, disk_sense=sense)
+    t, rgb = ctx.disk_thermal(k0, CAM, p, th, obs, flags, end)
+    g = _g(ctx, k0, CAM, p, sense, obs, flags, end)
+    use = np.flatnonzero((flags == 128) & (t > 0.3 * T_PEAK))
+    assert len(use) > 100
+    hr, hb = dt.H_OVER_K * nu_r, dt.H_OVER_K * nu_b
+    worst = 0.0
+    for i in use:
+        rho = rgb[i, 0] / rgb[i, 2]
+        fn = lambda lt: np.log((nu_r / nu_b) ** 3 * np.expm1(hb / np.exp(lt)) / np.expm1(hr / np.exp(lt))) - np.log(rho)
+        T_obs = np.exp(brentq(fn, np.log(100.0), np.log(1e6), xtol=1e-15, rtol=1e-15))
+        worst = max(worst, abs(T_obs / (F_COL * t[i]) / g[i] - 1.0))
+    assert worst <= 1e-9, worst
+
+
+# ---- the thermal shade -----------------------------------------------------------------------------------------------
+def _scene_frame(ctx, S, kerr=False):
+    import torch
+    from blackhole_geodesic_calculator_amd.device_frame import DeviceFrame, synthetic_sky
+    W_, H_ = (8, 6) if S > 256 else (40, 30)
+    sky = synthetic_sky(256, 128)
+    disk_tex = synthetic_sky(128, 32, seed=3)
+    fr = DeviceFrame(ctx, W_, H_, S, fov_x=0.9, fov_y=0.9, sampling_seed=42.0, origin=CAM, rotation_euler=(0.0, INC, 0.0))
+    fr.set_sky(sky)
+    fr.set_disk(3.0, 9.0, disk_tex, disk_phase=0.4, disk_mean=0.3, disk_stddev=0.25, disk_intensity=2.0)
+    sph = [[6.0, 3.0, 2.5, 1.5], [2.0, 6.0, -1.0, 1.2]]
+    rgb = [[1.0, 0.8, 0.6], [0.5, 0.5, 1.0]]
+    lamps = [[20.0, 0.0, 20.0, 10.0]]
+    fr.set_objects(sph, rgb, lamps)
+    kw = dict(r_s=1.0, lambda_end=80.0, r_exit=40.0, disk_r_in=3.0, disk_r_out=9.0)
+    if kerr:
+        kw.update(rhs_form=2, spin=0.45)
+    p = _ffi().make_params(**kw)
+    fr.generate_rays()
+    fr.trace(p)
+    torch.cuda.synchronize()
+    ref = dict(disk=(3.0, 9.0), disk_tex=disk_tex, disk_profile=dict(phase=0.4, mean=0.3, stddev=0.25, intensity=2.0),
+               spheres=sph, sphere_rgb=np.array(rgb), lamps=lamps)
+    return fr, p, sky, ref
+
+
+_CACHE = {}
+
+
+def _rays_of(ctx, fr, p, S, kerr, obs, sense):
+    """The frame's rays and their restated per-ray numbers (cached: every combination of a case shares them)."""
+    key = (S, kerr, obs)
+    if key not in _CACHE:
+        end, flags, obj, k0 = fr.d_end.cpu().numpy(), fr.d_flags.cpu().numpy(), fr.d_obj.cpu().numpy(), fr.d_k0.cpu().numpy()
+        ob = _ffi().make_observer(BETA if obs else None)
+        g = _g(ctx, k0, fr.origin, p, sense, ob, flags, end)
+        t, rgb = dt.thermal_rays(end, flags, g, 1.0, 0.45 if kerr else 0.0, kerr, sense, T_PEAK, NU, W, F_COL, SCALE)
+        up = fr.rot @ np.array([0.0, 1.0, 0.0])
+        chi, deg, _ = pr.pol_rays(fr.origin, k0, end, flags, 1.0, 0.45 if kerr else 0.0, kerr, sense, (0.0, 0.35, 0.2), up,
+                                  BETA if obs else None)
+        dev_t, dev_rgb = ctx.disk_thermal(k0, fr.origin, p, _th(sense), ob, flags, end)
+        _CACHE[key] = (end, flags, obj, k0, g, t, rgb, chi, deg, dev_rgb)
+    return _CACHE[key]
+
+
+@pytest.mark.parametrize("kerr", [False, True], ids=["schw", "kerr"])
+@pytest.mark.parametrize("S", [1, 5, 300])
+@pytest.mark.parametrize("rs,obs,tex,pol", [(r, o, t, q) for r in (False, True) for o in (False, True) for t in (False, True)
+                                            for q in (False, True)])
+def test_thermal_shade(ctx, S, rs, obs, tex, pol, kerr):
+    import torch
+    f = _ffi()
+    fr, p, sky, ref = _scene_frame(ctx, S, kerr)
+    sense = -1 if kerr else 1
+    if rs:
+        fr.set_redshift(("disk", "objects", "sky"), 4.0, disk_sense=sense)
+    if obs:
+        fr.observer = f.make_observer(BETA)
+    if tex:
+        fr.set_object_textures(rotations=[np.eye(3)], modes=["emissive"], emission=[2.0])
+    fr.set_disk_thermal(_th(sense))
+    if pol:
+        fr.set_polarisation((0.0, 0.35, 0.2), disk_sense=sense)
+        rgba, qu = fr.shade_stokes()
+        rgba, qu = rgba.clone(), qu.clone().cpu().numpy()
+    else:
+        rgba = fr.shade().clone()
+    t32 = torch.empty((fr.P, 4), dtype=torch.float32, device=fr.dev)
+    fr.shade_f32(t32)
+    end, flags, obj, k0, g, t, rgb, chi, deg, dev_rgb = _rays_of(ctx, fr, p, S, kerr, obs, sense)
+    base = None
+    if tex:
+        # textured objects: every ray's colour without the thermal disk from the library's own shade, one ray per "pixel"
+        # (tests/test_gpu_object_textures.py checks that colour against its restatement)
+        b = torch.empty((fr.P * fr.S, 4), dtype=torch.float64, device=fr.dev)
+        ctx.shade_scene_textured_device(fr.d_end.data_ptr(), fr.d_flags.data_ptr(), fr.P * fr.S, 1, fr.scene(), p, fr.redshift,
+                                        fr.observer, fr._object_textures(), x0_shared=fr.origin, d_k0=fr.d_k0.data_ptr(),
+                                        d_rgba=b.data_ptr(), d_object_id=fr.d_obj.data_ptr(),
+                                        stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        base = b.cpu().numpy()
+    got = rgba.cpu().numpy()
+    n = fr.P * fr.S
+    if S == 1:
+        d = flags == 128
+        assert d.sum() > 100
+        assert np.array_equal(got[d, :3], dev_rgb[d])     # the shade's disk colour is the per-ray colour, bit for bit
+    want = dt.shade_thermal(end, flags, obj, fr.P, fr.S, sky, g, rgb, 4.0, 7 if rs else 0, base=base, **ref)
+    scale = np.abs(want[:, :3]).max()
+    assert np.abs(got - want).max() <= 1e-11 * max(scale, 1.0)
+    # the f32 output is the fp64 image rounded
+    assert torch.equal(t32, rgba.to(torch.float32))
+    if pol:
+        one = dt.shade_thermal(end, flags, obj, n, 1, sky, g, rgb, 4.0, 7 if rs else 0, base=base, **ref)[:, :3]
+        disk = flags == 128
+        wq = pr.shade_stokes(np.where(disk[:, None], one, 0.0), np.where(disk, chi, np.nan), deg, fr.P, fr.S)
+        assert np.abs(qu - wq).max() <= 1e-11 * max(np.abs(wq).max(), 1.0)
+
+
+def test_scattered_f32_is_the_rounded_image(ctx):
+    import torch
+    fr, p, sky, ref = _scene_frame(ctx, 3)
+    fr.set_disk_thermal(_th(1))
+    rgba = fr.shade().clone()
+    perm = torch.randperm(fr.P, device=fr.dev)
+    out = torch.zeros((fr.P, 4), dtype=torch.float32, device=fr.dev)
+    fr.shade_f32(out, scatter=perm)
+    assert torch.equal(out[perm], rgba.to(torch.float32))
+
+
+def test_off_is_today(ctx):
+    import torch
+    f = _ffi()
+    fr, p, sky, _ = _scene_frame(ctx, 3)
+    fr.set_redshift(("objects", "sky"), 4.0)
+    today = fr.shade().clone()
+    fr.set_disk_thermal(_th(1))
+    assert not torch.equal(fr.shade(), today)
+    fr.set_disk_thermal(None)
+    assert torch.equal(fr.shade(), today)
+    d64 = torch.empty_like(today)
+    ctx.shade_scene_thermal_device(fr.d_end.data_ptr(), fr.d_flags.data_ptr(), fr.P, fr.S, fr.scene(), p, fr.redshift, None, None,
+                                   None, 0, None, x0_shared=fr.origin, d_k0=fr.d_k0.data_ptr(), d_rgba=d64.data_ptr(),
+                                   d_object_id=fr.d_obj.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert torch.equal(d64, today)
+    pol = f.make_polarisation(0.2, 1, fr.rot @ np.array([0.0, 1.0, 0.0]))
+    q1, q2 = torch.empty((fr.P, 6), dtype=torch.float64, device=fr.dev), torch.empty((fr.P, 6), dtype=torch.float64, device=fr.dev)
+    a1, a2 = torch.empty_like(today), torch.empty_like(today)
+    common = dict(x0_shared=fr.origin, d_k0=fr.d_k0.data_ptr(), d_object_id=fr.d_obj.data_ptr(),
+                  stream=torch.cuda.current_stream().cuda_stream)
+    ctx.shade_scene_polarised_device(fr.d_end.data_ptr(), fr.d_flags.data_ptr(), fr.P, fr.S, fr.scene(), p, fr.redshift, None, None,
+                                     pol, q1.data_ptr(), d_rgba=a1.data_ptr(), **common)
+    ctx.shade_scene_thermal_device(fr.d_end.data_ptr(), fr.d_flags.data_ptr(), fr.P, fr.S, fr.scene(), p, fr.redshift, None, None,
+                                   pol, q2.data_ptr(), None, d_rgba=a2.data_ptr(), **common)
+    torch.cuda.synchronize()
+    assert torch.equal(a1, a2) and torch.equal(q1, q2)
+
+
+# ---- the library's frame ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("devices", [[0], [0, 0]], ids=["one", "loopback"])
+def test_library_frame_matches_device_frame(ctx, devices):
+    """bhg_frame_set_disk_thermal on one device and the {0, 0} loopback: DeviceFrame's image; NULL gives today's frame."""
+    import torch
+    from blackhole_geodesic_calculator_amd.device_frame import DeviceFrame, synthetic_sky
+    from blackhole_geodesic_calculator_amd.raygen import euler_xyz_matrix, python_random_stream
+    f = _ffi()
+    W_, H_, S = 48, 32, 3
+    sky = synthetic_sky(128, 64)
+    p = f.make_params(r_s=1.0, lambda_end=80.0, r_exit=40.0, disk_r_in=3.0, disk_r_out=9.0)
+    th = _th(1)
+    gather = f.GATHER_AUTO if len(devices) == 1 else f.GATHER_COPY
+    lf = f.Frame(devices, W_, H_, S, fov_x=0.9, fov_y=0.9, origin=CAM, rot=euler_xyz_matrix((0.0, INC, 0.0)),
+                 jitter=python_random_stream(42.0, 2 * S * W_ * H_), gather=gather, tile=16)
+    try:
+        lf.set_scene(sky, disk=(3.0, 9.0))
+        lf.set_redshift(("sky",), 4.0, 1)
+        plain = lf.render(p)
+        lf.set_disk_thermal(th)
+        got = lf.render(p)
+        lf.set_disk_thermal(None)
+        assert np.array_equal(lf.render(p), plain)
+        lf.set_disk_thermal(dict(t_peak=T_PEAK, nu=NU, weights=W, f_col=F_COL, scale=SCALE, disk_sense=1))
+        assert np.array_equal(lf.render(p), got)
+    finally:
+        lf.close()
+    assert np.abs(got - plain).max() > 1e-3
+    dfr = DeviceFrame(ctx, W_, H_, S, fov_x=0.9, fov_y=0.9, sampling_seed=42.0, origin=CAM, rotation_euler=(0.0, INC, 0.0))
+    dfr.set_sky(sky)
+    dfr.set_disk(3.0, 9.0)
+    dfr.set_redshift(("sky",), 4.0, 1)
+    dfr.set_disk_thermal(th)
+    dfr.generate_rays()
+    dfr.trace(p)
+    out = torch.empty((W_ * H_, 4), dtype=torch.float32, device=dfr.dev)
+    dfr.shade_f32(out)
+    torch.cuda.synchronize()
+    assert np.array_equal(out.cpu().numpy().reshape(H_, W_, 4), got)
+
+
+# ---- the Doppler colour -------------------------------------------------------------------------------------------------
+def test_edge_on_doppler_colour(ctx):
+    """Seen edge-on, the half of the disk test_edge_on_doppler_asymmetry finds blueshifted is also bluer: a higher B / R."""
+    f = _ffi()
+    cam = np.array([30.0, 0.0, 0.6])
+    k = frame_rays(15000, seed=9, fov=0.8)
+    R = np.array([[0, 0, 1], [0, 1, 0], [-1, 0, 0]], float)
+    k0 = k @ R.T
+    p = f.make_params(r_s=1.0, lambda_end=80.0, r_exit=40.0, disk_r_in=3.0, disk_r_out=12.0)
+    end, flags, _, _ = ctx.trace(k0, cam, p)
+    near = (flags == 128) & (end[:, 0] > 0.0)
+    for sense in (1, -1):
+        th = f.make_disk_thermal(T_PEAK, *f.narrowband(2e14, 5e14, 9e14), disk_sense=sense)
+        t, rgb = ctx.disk_thermal(k0, cam, p, th, None, flags, end)
+        lit = near & (t > 0.0)
+        approaching = lit & (end[:, 1] * sense < 0.0)
+        receding = lit & (end[:, 1] * sense > 0.0)
+        assert approaching.sum() > 50 and receding.sum() > 50
+        br = rgb[:, 2] / rgb[:, 0]
+        assert np.median(br[approaching]) > np.median(br[receding]), sense
+
+
+# ---- the Python adaptors -----------------------------------------------------------------------------------------------
+def test_trace_adaptor(ctx):
+    from blackhole_geodesic_calculator_amd import GeodesicIntegratorKerr, GeodesicIntegratorSchwarzschild
+    f = _ffi()
+    k0 = _inclined_rays(1500, seed=13)
+    kw = dict(t_peak=T_PEAK, nu=NU, weights=W, f_col=F_COL, scale=SCALE, disk_sense=-1)
+    for gi in (GeodesicIntegratorSchwarzschild(mass=0.5, verbose=False, device=0),
+               GeodesicIntegratorKerr(mass=0.5, a=0.9, verbose=False, device=0)):
+        out = gi.trace(k0, CAM, curve_end=80.0, r_exit=40.0, disk=(3.0, 9.0), disk_thermal=kw)
+        p = gi.params(np.inf, 80.0, 40.0, (3.0, 9.0))
+        t, rgb = gi.context.disk_thermal(k0, CAM, p, f.make_disk_thermal(**kw), None, out["flags"], out["ray_end"])
+        assert np.array_equal(out["t_em"], t, equal_nan=True) and np.array_equal(out["thermal_rgb"], rgb, equal_nan=True)
+        assert out["thermal_rgb"].shape == (1500, 3) and (out["t_em"] > 0.0).sum() > 200
+
+
+def test_frame_batch_adaptor(ctx):
+    import torch
+    from blackhole_geodesic_calculator_amd.device_frame import DeviceFrame, FrameBatch, synthetic_sky
+    f = _ffi()
+    cams = [dict(origin=CAM, rotation_euler=(0.0, INC, 0.0)), dict(origin=(0.0, 20.0, 15.0), rotation_euler=(-0.9, 0.0, 3.14))]
+    p = f.make_params(r_s=1.0, lambda_end=80.0, r_exit=40.0, disk_r_in=3.0, disk_r_out=9.0)
+    sky = synthetic_sky(128, 64)
+    fb = FrameBatch(ctx, cams, 24, 16, 2, fov_x=0.9, fov_y=0.9, sampling_seed=42.0)
+    for fr in fb.frames:
+        fr.set_sky(sky)
+        fr.set_disk(3.0, 9.0)
+    fb.generate_rays()
+    fb.trace(p)
+    fb.set_disk_thermal(T_PEAK, NU, W, F_COL, SCALE, 1)
+    imgs = [x.clone() for x in fb.shade()]
+    for cam, img in zip(cams, imgs):
+        one = DeviceFrame(ctx, 24, 16, 2, fov_x=0.9, fov_y=0.9, sampling_seed=42.0, **cam)
+        one.set_sky(sky)
+        one.set_disk(3.0, 9.0)
+        one.set_disk_thermal(_th(1))
+        assert torch.equal(one.render(p), img)
