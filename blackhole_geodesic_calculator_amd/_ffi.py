@@ -61,6 +61,8 @@ EXPORTS = (
     "bhg_polarisation_size", "bhg_polarisation_device", "bhg_polarisation_host", "bhg_shade_scene_polarised_device",
     "bhg_disk_thermal_size", "bhg_disk_thermal_device", "bhg_disk_thermal_host", "bhg_shade_scene_thermal_device",
     "bhg_frame_set_disk_thermal",
+    "bhg_object_motion_size", "bhg_redshift_motion_device", "bhg_redshift_motion_host", "bhg_shade_scene_moving_device",
+    "bhg_frame_set_object_motion",
 )
 PROBE_FMA, PROBE_STEP_MIX = 0, 1
 
@@ -163,6 +165,28 @@ def make_disk_thermal(t_peak, nu, weights, f_col=1.0, scale=1.0, disk_sense=1) -
 def narrowband(nu_r, nu_g, nu_b):
     """(nu, weights) of narrow-band false colour: one frequency [Hz] per channel, weight 1 (make_disk_thermal(t, *narrowband(...)))."""
     return np.array([nu_r, nu_g, nu_b], dtype=np.float64), np.eye(3)
+
+
+class ObjectMotion(C.Structure):
+    """bhg_object_motion (BHG_OBJECT_MOTION, within ABI 10): each object sphere's centre velocity v and angular velocity w, world
+    axes, dx/dt and rad per unit t.  All zero: every sphere at rest."""
+    _fields_ = [("v", (C.c_double * 3) * MAX_SPHERES), ("w", (C.c_double * 3) * MAX_SPHERES)]
+
+
+def make_object_motion(velocity=None, angular_velocity=None) -> ObjectMotion:
+    """velocity, angular_velocity: [n][3] per sphere of the scene (n <= MAX_SPHERES), or None for zeros.  A sphere's surface
+    point x moves with v + w x (x - c); the Kerr v is relative to the ZAMO's flow (observer.circular_orbit_motion)."""
+    mo = ObjectMotion()
+    for name, arr in (("v", velocity), ("w", angular_velocity)):
+        if arr is None:
+            continue
+        a = np.asarray(arr, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != 3 or a.shape[0] > MAX_SPHERES:
+            raise ValueError(f"{name} must be [n, 3] with n <= {MAX_SPHERES}, not {list(a.shape)}")
+        dst = getattr(mo, name)
+        for j in range(a.shape[0]):
+            dst[j][:] = [float(x) for x in a[j]]
+    return mo
 
 
 OBJECT_LIT, OBJECT_EMISSIVE = 0, 1
@@ -515,6 +539,24 @@ def load():
                                                  C.POINTER(DiskThermal), C.c_void_p]
     L.bhg_frame_set_disk_thermal.restype = C.c_int
     L.bhg_frame_set_disk_thermal.argtypes = [C.c_void_p, C.POINTER(DiskThermal)]
+    L.bhg_object_motion_size.restype = C.c_size_t
+    L.bhg_object_motion_size.argtypes = []
+    L.bhg_redshift_motion_device.restype = C.c_int
+    L.bhg_redshift_motion_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Redshift), C.POINTER(Observer),
+                                             C.POINTER(ObjectMotion), C.c_void_p, C.c_int32, _dp, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.bhg_redshift_motion_host.restype = C.c_int
+    L.bhg_redshift_motion_host.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Redshift), C.POINTER(Observer),
+                                           C.POINTER(ObjectMotion), C.c_void_p, C.c_int32, C.c_void_p, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.bhg_shade_scene_moving_device.restype = C.c_int
+    L.bhg_shade_scene_moving_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                C.c_int32, C.POINTER(Scene), C.POINTER(Params), C.POINTER(Redshift),
+                                                C.POINTER(Observer), C.POINTER(ObjectTextures), _dp, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.POINTER(Polarisation), C.c_void_p,
+                                                C.POINTER(DiskThermal), C.POINTER(ObjectMotion), C.c_void_p]
+    L.bhg_frame_set_object_motion.restype = C.c_int
+    L.bhg_frame_set_object_motion.argtypes = [C.c_void_p, C.POINTER(ObjectMotion)]
     if L.bhg_version() != ABI_VERSION or not hasattr(L, "bhg_abi_check"):
         raise ImportError(f"libbhgeo ABI {L.bhg_version()} != expected {ABI_VERSION}: rebuild {LIB_PATH}")
     for name in ("bhg_params_size", "bhg_camera_size", "bhg_scene_size", "bhg_frame_scene_size"):
@@ -533,6 +575,8 @@ def load():
         raise ImportError(f"libbhgeo: bhg_redshift is {L.bhg_redshift_size()} bytes, this binding's {C.sizeof(Redshift)}")
     if L.bhg_observer_size() != C.sizeof(Observer):
         raise ImportError(f"libbhgeo: bhg_observer is {L.bhg_observer_size()} bytes, this binding's {C.sizeof(Observer)}")
+    if L.bhg_object_motion_size() != C.sizeof(ObjectMotion):
+        raise ImportError(f"libbhgeo: bhg_object_motion is {L.bhg_object_motion_size()} bytes, this binding's {C.sizeof(ObjectMotion)}")
     if L.bhg_disk_thermal_size() != C.sizeof(DiskThermal):
         raise ImportError(f"libbhgeo: bhg_disk_thermal is {L.bhg_disk_thermal_size()} bytes, this binding's {C.sizeof(DiskThermal)}")
     if L.bhg_polarisation_size() != C.sizeof(Polarisation):
@@ -840,6 +884,15 @@ class Frame:
             th = make_disk_thermal(**th)
         _check(load().bhg_frame_set_disk_thermal(self._h, None if th is None else C.byref(th)))
 
+    def set_object_motion(self, velocity=None, angular_velocity=None):
+        """Moving and spinning object spheres in every later render (bhg_frame_set_object_motion):
+        velocity, angular_velocity [n][3] per sphere of the scene (make_object_motion; observer.circular_orbit_motion gives an
+        orbit).  Both None: off -- the frame as without motion, bit for bit."""
+        if velocity is None and angular_velocity is None:
+            _check(load().bhg_frame_set_object_motion(self._h, None))
+            return
+        _check(load().bhg_frame_set_object_motion(self._h, C.byref(make_object_motion(velocity, angular_velocity))))
+
     def render(self, params: "Params", out=None, to_host=True):
         """One frame: float32 [H, W, 4] (a new array, or `out`).  to_host=False: only enqueue; the image stays on the
         first device (device_image(), synchronize())."""
@@ -1112,6 +1165,54 @@ class Context:
         """bhg_redshift_observer_host: redshift() with g of the moving observer obs (Observer, or None = the ZAMO)."""
         return self._redshift_host(functools.partial(load().bhg_redshift_observer_host, self._h, C.byref(params), C.byref(rs),
                                                      _obs_ref(obs)), k0, x0, flags, end)
+
+    @staticmethod
+    def _spheres_arg(spheres):
+        """(spheres [n][4] as a contiguous array or None, n) for the motion calls."""
+        if spheres is None:
+            return None, 0
+        sp = np.ascontiguousarray(spheres, dtype=np.float64).reshape(-1, 4)
+        return sp, sp.shape[0]
+
+    def redshift_motion(self, k0, x0, params: Params, rs: Redshift, obs, motion, spheres, flags, end=None, object_id=None):
+        """bhg_redshift_motion_host: redshift_observer() with moving object spheres (motion: ObjectMotion, or None = at rest;
+        spheres [n][4] of the trace; object_id [N] of the trace)."""
+        sp, n_sp = self._spheres_arg(spheres)
+        oid = None if object_id is None else np.ascontiguousarray(object_id, dtype=np.int8).reshape(-1)
+        k0 = np.ascontiguousarray(k0, dtype=np.float64).reshape(-1, 3)
+        if oid is not None and oid.shape != (k0.shape[0],):
+            raise ValueError("object_id must be [N]")
+        call = load().bhg_redshift_motion_host
+
+        def fn(x0p, shared, k0p, ep, fp, n, gp):
+            return call(self._h, C.byref(params), C.byref(rs), _obs_ref(obs), None if motion is None else C.byref(motion),
+                        None if sp is None else _addr(sp), n_sp, x0p, shared, k0p, ep, fp, None if oid is None else _addr(oid), n, gp)
+        return self._redshift_host(fn, k0, x0, flags, end)
+
+    def redshift_motion_device(self, params: Params, rs: Redshift, obs, motion, spheres, n, d_k0, d_flags, d_g, x0_shared=None,
+                               d_x0=0, d_end=0, d_object_id=0, stream=0):
+        """bhg_redshift_motion_device on device arrays (spheres: HOST [n][4])."""
+        sp, n_sp = self._spheres_arg(spheres)
+        xs = None if x0_shared is None else (C.c_double * 3)(*[float(v) for v in x0_shared])
+        _check(load().bhg_redshift_motion_device(self._h, C.byref(params), C.byref(rs), _obs_ref(obs),
+                                                 None if motion is None else C.byref(motion), None if sp is None else _addr(sp), n_sp,
+                                                 xs, C.c_void_p(d_x0 or None), C.c_void_p(d_k0), C.c_void_p(d_end or None),
+                                                 C.c_void_p(d_flags), C.c_void_p(d_object_id or None), int(n), C.c_void_p(d_g),
+                                                 C.c_void_p(stream or None)))
+
+    def shade_scene_moving_device(self, d_end, d_flags, n_pixels, samples, scene: "Scene", params, rs, obs, ot, pol, d_qu, th, mo,
+                                  x0_shared=None, d_k0=0, d_rgba=0, d_rgba_f32=0, d_object_id=0, d_scatter=0, d_end_dir=0,
+                                  stream=0):
+        """bhg_shade_scene_moving_device: shade_scene_thermal_device with moving object spheres (mo: ObjectMotion, or None =
+        exactly the thermal call)."""
+        xs = None if x0_shared is None else (C.c_double * 3)(*[float(v) for v in x0_shared])
+        _check(load().bhg_shade_scene_moving_device(
+            self._h, C.c_void_p(d_end or None), C.c_void_p(d_end_dir or None), C.c_void_p(d_flags), C.c_void_p(d_object_id or None),
+            int(n_pixels), int(samples), C.byref(scene), None if params is None else C.byref(params),
+            None if rs is None else C.byref(rs), _obs_ref(obs), None if ot is None else C.byref(ot), xs, C.c_void_p(d_k0 or None),
+            C.c_void_p(d_rgba or None), C.c_void_p(d_rgba_f32 or None), C.c_void_p(d_scatter or None),
+            None if pol is None else C.byref(pol), C.c_void_p(d_qu or None), None if th is None else C.byref(th),
+            None if mo is None else C.byref(mo), C.c_void_p(stream or None)))
 
     @staticmethod
     def _redshift_device(call, n, d_k0, d_flags, d_g, x0_shared, d_x0, d_end, stream):

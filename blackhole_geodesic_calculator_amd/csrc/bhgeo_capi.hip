@@ -48,6 +48,7 @@ static_assert(sizeof(bhg_observer) == 24, "bhg_observer layout is part of the AB
 static_assert(sizeof(bhg_object_textures) == 800, "bhg_object_textures layout is part of the ABI");
 static_assert(sizeof(bhg_polarisation) == 544 && BHG_POL_TABLE_MAX == bhg::BHG_POL_TABLE_MAX_, "bhg_polarisation layout is part of the ABI");
 static_assert(sizeof(bhg_disk_thermal) == 544 && BHG_THERMAL_NU_MAX == bhg::BHG_THERMAL_NU_MAX_, "bhg_disk_thermal layout is part of the ABI");
+static_assert(sizeof(bhg_object_motion) == 384, "bhg_object_motion layout is part of the ABI");
 static_assert(BHG_OBJECT_LIT == bhg::BHG_OBJECT_LIT_ && BHG_OBJECT_EMISSIVE == bhg::BHG_OBJECT_EMISSIVE_, "object mode mismatch");
 
 namespace {
@@ -677,6 +678,93 @@ int thermal_params(const bhg_params *p, const bhg_disk_thermal *th, const bhg_re
     return BHG_OK;
 }
 
+// Object motion on its own (include/bhgeo.h, "moving and spinning object spheres") for a scene of n_spheres spheres: every v and
+// w of the slots below n_spheres finite.  Also used by bhgeo_frame.hip.
+int motion_check(const bhg_object_motion *mo, int32_t n_spheres)
+{
+    if (!mo) return fail(BHG_E_INVALID, "object motion is NULL");
+    const int n = n_spheres < 0 ? 0 : (n_spheres > BHG_MAX_SPHERES ? BHG_MAX_SPHERES : n_spheres);
+    for (int j = 0; j < n; j++)
+        for (int q = 0; q < 3; q++)
+            if (!std::isfinite(mo->v[j][q]) || !std::isfinite(mo->w[j][q])) {
+                char msg[200];
+                std::snprintf(msg, sizeof msg, "object motion: sphere %d: v = (%.17g, %.17g, %.17g), w = (%.17g, %.17g, %.17g) must be finite",
+                              j, mo->v[j][0], mo->v[j][1], mo->v[j][2], mo->w[j][0], mo->w[j][1], mo->w[j][2]);
+                return fail(BHG_E_INVALID, msg);
+            }
+    return BHG_OK;
+}
+
+// Object motion against the spheres {c, rho} [n_spheres][4] and the metric of p (include/bhgeo.h): *out =
+// the kernels' table, moving = the spheres with a nonzero v or w, on = (moving != 0).  A moving sphere must stay outside the
+// horizon and its motion must be timelike on the whole sphere by the sufficient bounds of section 14.  Also used by
+// bhgeo_frame.hip.
+int motion_params(const bhg_params *p, const bhg_object_motion *mo, const double *spheres, int32_t n_spheres, MotionParams *out)
+{
+    int rc = motion_check(mo, n_spheres);
+    if (rc != BHG_OK) return rc;
+    rc = validate(p);
+    if (rc != BHG_OK) return rc;
+    std::memset(out, 0, sizeof(*out));
+    const int n = n_spheres < 0 ? 0 : (n_spheres > BHG_MAX_SPHERES ? BHG_MAX_SPHERES : n_spheres);
+    const bool kerr = p->rhs_form == BHG_RHS_KERR_BL;
+    const double M = 0.5 * p->r_s, a = kerr ? p->spin : 0.0, a2 = a * a;
+    char msg[320];
+    for (int j = 0; j < n; j++) {
+        const double *v = mo->v[j], *w = mo->w[j];
+        bool zero = true;
+        for (int q = 0; q < 3; q++) zero = zero && v[q] == 0.0 && w[q] == 0.0;
+        if (zero) continue;
+        if (!spheres) return fail(BHG_E_INVALID, "object motion needs the spheres");
+        const double *c = spheres + 4 * j, rho = c[3];
+        const double cn = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]), d = cn - rho;
+        const double vn = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]), wn = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+        if (!kerr) {
+            if (!(d > p->r_s)) {
+                std::snprintf(msg, sizeof msg, "object motion: sphere %d: a moving sphere must lie outside the horizon: |c| - rho = %.17g "
+                              "<= r_s = %.17g", j, d, p->r_s);
+                return fail(BHG_E_INVALID, msg);
+            }
+            const double bound = 1.0 - p->r_s / d, speed = vn + wn * rho;
+            if (!(speed < bound)) {
+                std::snprintf(msg, sizeof msg, "object motion: sphere %d: |v| + |w| rho = %.17g is not < f(|c| - rho) = %.17g: the motion "
+                              "is not timelike on the whole sphere by section 14's bound", j, speed, bound);
+                return fail(BHG_E_INVALID, msg);
+            }
+        } else {
+            const double r_plus = M + std::sqrt(M * M - a2);
+            const double r_lo = d > std::fabs(a) ? std::sqrt(d * d - a2) : 0.0, r_hi = cn + rho;
+            if (!(r_lo > r_plus)) {
+                std::snprintf(msg, sizeof msg, "object motion: sphere %d: a moving sphere must lie outside the horizon: its Boyer-Lindquist "
+                              "r can reach sqrt((|c| - rho)^2 - a^2) = %.17g <= r_+ = %.17g", j, r_lo, r_plus);
+                return fail(BHG_E_INVALID, msg);
+            }
+            // G: sqrt(g_phph) / alpha on the equator, the bound of a rigid rotation's ZAMO-relative speed per unit angular
+            // velocity at BL r; F: the bound |V| < F(r) of any velocity (section 14)
+            auto G = [&](double r) {
+                const double Del = r * r - 2.0 * M * r + a2, R2 = r * r + a2;
+                return (R2 * R2 - a2 * Del) / (r * r * std::sqrt(Del));
+            };
+            const double Del_lo = r_lo * r_lo - 2.0 * M * r_lo + a2, R2_lo = r_lo * r_lo + a2;
+            const double F_lo = r_lo * Del_lo / (R2_lo * std::sqrt(R2_lo));
+            const double wz = w[2], wp = std::sqrt(w[0] * w[0] + w[1] * w[1]);
+            const double D[3] = {v[0] + wz * c[1], v[1] - wz * c[0], v[2]};     // v - w_z z^ x c
+            const double Dn = std::sqrt(D[0] * D[0] + D[1] * D[1] + D[2] * D[2]) + wp * rho;
+            const double beta = std::fabs(wz) * std::max(G(r_lo), G(r_hi)) + Dn / F_lo;
+            if (!(beta < 1.0)) {
+                std::snprintf(msg, sizeof msg, "object motion: sphere %d: the bound %.17g on the ZAMO-relative speed is not < 1: the "
+                              "motion is not timelike on the whole sphere by section 14's bound", j, beta);
+                return fail(BHG_E_INVALID, msg);
+            }
+        }
+        std::memcpy(out->v[j], v, sizeof(out->v[j]));
+        std::memcpy(out->w[j], w, sizeof(out->w[j]));
+        out->moving |= 1u << j;
+    }
+    out->on = out->moving != 0;
+    return BHG_OK;
+}
+
 // Object textures (include/bhgeo.h, "textured, oriented and emissive object spheres") for a scene of n_spheres spheres: slots
 // at or above n_spheres are not looked at.  *out = the kernels' table (an all-zero rotation becomes the identity), on = 1.
 // Also used by bhgeo_frame.hip (there with tex = the host arrays: only whether a slot has one matters).
@@ -764,6 +852,7 @@ size_t bhg_observer_size(void) { return sizeof(bhg_observer); }
 size_t bhg_object_textures_size(void) { return sizeof(bhg_object_textures); }
 size_t bhg_polarisation_size(void) { return sizeof(bhg_polarisation); }
 size_t bhg_disk_thermal_size(void) { return sizeof(bhg_disk_thermal); }
+size_t bhg_object_motion_size(void) { return sizeof(bhg_object_motion); }
 
 int bhg_abi_check(int abi_version, size_t params_size, size_t camera_size, size_t scene_size, size_t frame_scene_size)
 {
@@ -1575,6 +1664,8 @@ int raygen_impl(bhg_context *c, int32_t width, int32_t height, int32_t samples, 
 //   1. the scene: present; samples, sky_w, sky_h > 0; n_spheres in [0, BHG_MAX_SPHERES], n_lamps in [0, 4]; a disk with
 //      r_out > r_in, stddev > 0 and a texture size > 0; sphere radii > 0
 //   2. the object-texture table, when given, against n_spheres
+//   2b. the object motion, when given, against n_spheres and the trace parameters (finite; moving spheres outside the horizon
+//      and timelike on the whole sphere)
 //   3. redshift, when rs->apply != 0: x0_shared, the settings, and the observer when given
 //   3b. polarisation, when pol is given: x0_shared, the settings (against p, the scene's disk, the redshift's sense, the camera)
 //   3c. the thermal disk, when th is given: the settings (against p, the scene's disk, the redshift's and polarisation's
@@ -1588,7 +1679,7 @@ int shade(bhg_context *c, const double *d_end, const double *d_end_dir, const ui
           size_t n_pixels, int32_t samples, const bhg_scene *sc, const bhg_params *p, const bhg_redshift *rs,
           const bhg_observer *obs, const bhg_object_textures *ot, const double *x0_shared, const double *d_k0, double *d_rgba,
           float *d_rgba_f32, const int64_t *d_scatter, const bhg_polarisation *pol, double *d_qu, const bhg_disk_thermal *th,
-          void *stream)
+          const bhg_object_motion *mo, void *stream)
 {
     if (!sc) return fail(BHG_E_INVALID, "scene is NULL");
     if (samples <= 0 || sc->sky_w <= 0 || sc->sky_h <= 0) return fail(BHG_E_INVALID, "samples, sky_w, sky_h must be > 0");
@@ -1605,6 +1696,11 @@ int shade(bhg_context *c, const double *d_end, const double *d_end_dir, const ui
     bhg::ObjectTextureParams tp;
     if (ot) {
         int rc = bhg::object_texture_params(ot, sc->n_spheres, &tp);
+        if (rc != BHG_OK) return rc;
+    }
+    bhg::MotionParams mp;
+    if (mo) {
+        int rc = bhg::motion_params(p, mo, &sc->spheres[0][0], sc->n_spheres, &mp);
         if (rc != BHG_OK) return rc;
     }
     const bool on = rs && rs->apply != 0;
@@ -1699,6 +1795,7 @@ int shade(bhg_context *c, const double *d_end, const double *d_end_dir, const ui
         a.k0 = d_k0;
         if (obs) a.obs = op_th;
     }
+    if (mo) a.mo = mp;     // (launch_shade takes the motion instance only when rs.apply weighs objects)
     HIP_TRY(bhg::launch_shade(a, (hipStream_t)stream));
     return BHG_OK;
 }
@@ -1742,7 +1839,7 @@ int bhg_shade_device(bhg_context *c, const double *d_end, const uint8_t *d_flags
 {
     const bhg_scene sc = sky_scene(d_sky, sky_w, sky_h);
     return shade(c, d_end, nullptr, d_flags, nullptr, n_pixels, samples, &sc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                 d_rgba, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+                 d_rgba, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int bhg_shade_dir_device(bhg_context *c, const double *d_end_dir, const uint8_t *d_flags, size_t n_pixels, int32_t samples,
@@ -1751,14 +1848,14 @@ int bhg_shade_dir_device(bhg_context *c, const double *d_end_dir, const uint8_t 
 {
     const bhg_scene sc = sky_scene(d_sky, sky_w, sky_h);
     return shade(c, nullptr, d_end_dir, d_flags, nullptr, n_pixels, samples, &sc, nullptr, nullptr, nullptr, nullptr, nullptr,
-                 nullptr, d_rgba, d_rgba_f32, d_scatter, nullptr, nullptr, nullptr, stream);
+                 nullptr, d_rgba, d_rgba_f32, d_scatter, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int bhg_shade_scene_device(bhg_context *c, const double *d_end, const uint8_t *d_flags, const int8_t *d_object_id,
                            size_t n_pixels, int32_t samples, const bhg_scene *sc, double *d_rgba, void *stream)
 {
     return shade(c, d_end, nullptr, d_flags, d_object_id, n_pixels, samples, sc, nullptr, nullptr, nullptr, nullptr, nullptr,
-                 nullptr, d_rgba, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+                 nullptr, d_rgba, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int bhg_shade_scene_f32_device(bhg_context *c, const double *d_end, const uint8_t *d_flags, const int8_t *d_object_id,
@@ -1766,7 +1863,7 @@ int bhg_shade_scene_f32_device(bhg_context *c, const double *d_end, const uint8_
                                const int64_t *d_scatter, void *stream)
 {
     return shade(c, d_end, nullptr, d_flags, d_object_id, n_pixels, samples, sc, nullptr, nullptr, nullptr, nullptr, nullptr,
-                 nullptr, nullptr, d_rgba_f32, d_scatter, nullptr, nullptr, nullptr, stream);
+                 nullptr, nullptr, d_rgba_f32, d_scatter, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int bhg_shade_scene_redshift_device(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
@@ -1775,7 +1872,7 @@ int bhg_shade_scene_redshift_device(bhg_context *c, const double *d_end, const d
                                     double *d_rgba, float *d_rgba_f32, const int64_t *d_scatter, void *stream)
 {
     return shade(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs, nullptr, nullptr, x0_shared, d_k0,
-                 d_rgba, d_rgba_f32, d_scatter, nullptr, nullptr, nullptr, stream);
+                 d_rgba, d_rgba_f32, d_scatter, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int bhg_shade_scene_redshift_observer_device(bhg_context *c, const double *d_end, const double *d_end_dir,
@@ -1786,7 +1883,7 @@ int bhg_shade_scene_redshift_observer_device(bhg_context *c, const double *d_end
                                              const int64_t *d_scatter, void *stream)
 {
     return shade(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs, obs, nullptr, x0_shared, d_k0, d_rgba,
-                 d_rgba_f32, d_scatter, nullptr, nullptr, nullptr, stream);
+                 d_rgba_f32, d_scatter, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int bhg_shade_scene_textured_device(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
@@ -1817,8 +1914,19 @@ int bhg_shade_scene_thermal_device(bhg_context *c, const double *d_end, const do
                                    float *d_rgba_f32, const int64_t *d_scatter, const bhg_polarisation *pol, double *d_qu,
                                    const bhg_disk_thermal *th, void *stream)
 {
+    return bhg_shade_scene_moving_device(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs, obs, ot, x0_shared,
+                                         d_k0, d_rgba, d_rgba_f32, d_scatter, pol, d_qu, th, nullptr, stream);
+}
+
+int bhg_shade_scene_moving_device(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
+                                  const int8_t *d_object_id, size_t n_pixels, int32_t samples, const bhg_scene *sc,
+                                  const bhg_params *p, const bhg_redshift *rs, const bhg_observer *obs,
+                                  const bhg_object_textures *ot, const double *x0_shared, const double *d_k0, double *d_rgba,
+                                  float *d_rgba_f32, const int64_t *d_scatter, const bhg_polarisation *pol, double *d_qu,
+                                  const bhg_disk_thermal *th, const bhg_object_motion *mo, void *stream)
+{
     return shade(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs, obs, ot, x0_shared, d_k0, d_rgba,
-                 d_rgba_f32, d_scatter, pol, d_qu, th, stream);
+                 d_rgba_f32, d_scatter, pol, d_qu, th, mo, stream);
 }
 
 int bhg_disk_thermal_device(bhg_context *c, const bhg_params *p, const bhg_disk_thermal *th, const bhg_observer *obs,
@@ -1979,10 +2087,28 @@ int bhg_redshift_observer_device(bhg_context *c, const bhg_params *p, const bhg_
                                  const double *x0_shared, const double *d_x0, const double *d_k0, const double *d_end,
                                  const uint8_t *d_flags, size_t n, double *d_g, void *stream)
 {
+    return bhg_redshift_motion_device(c, p, rs, obs, nullptr, nullptr, 0, x0_shared, d_x0, d_k0, d_end, d_flags, nullptr, n, d_g,
+                                      stream);
+}
+
+int bhg_redshift_motion_device(bhg_context *c, const bhg_params *p, const bhg_redshift *rs, const bhg_observer *obs,
+                               const bhg_object_motion *motion, const double *spheres, int32_t n_spheres,
+                               const double *x0_shared, const double *d_x0, const double *d_k0, const double *d_end,
+                               const uint8_t *d_flags, const int8_t *d_object_id, size_t n, double *d_g, void *stream)
+{
     // (the settings are checked before the context: a refusal names its figure with or without a device)
     bhg::RedshiftParams rp;
     int rc = bhg::redshift_params(p, rs, p && p->disk_r_out > 0.0 ? p->disk_r_in : -1.0, x0_shared, &rp);
     if (rc != BHG_OK) return rc;
+    bhg::MotionParams mp;
+    std::memset(&mp, 0, sizeof(mp));
+    if (motion) {
+        if (n_spheres < 0 || n_spheres > BHG_MAX_SPHERES)
+            return fail(BHG_E_INVALID, "n_spheres must be in [0, BHG_MAX_SPHERES], not " + std::to_string(n_spheres));
+        if (n_spheres > 0 && !spheres) return fail(BHG_E_INVALID, "spheres is NULL");
+        rc = bhg::motion_params(p, motion, spheres, n_spheres, &mp);
+        if (rc != BHG_OK) return rc;
+    }
     bhg::ObserverParams op;
     std::memset(&op, 0, sizeof(op));
     if (obs) {
@@ -1993,6 +2119,7 @@ int bhg_redshift_observer_device(bhg_context *c, const bhg_params *p, const bhg_
     if (!x0_shared == !d_x0) return fail(BHG_E_INVALID, "exactly one of x0_shared / d_x0 must be given");
     if (n == 0) return BHG_OK;
     if (!d_k0 || !d_flags || !d_g) return fail(BHG_E_INVALID, "d_k0 / d_flags / d_g is NULL");
+    if (mp.on && !d_object_id) return fail(BHG_E_INVALID, "moving object spheres need d_object_id");
     if (n > ((size_t)1 << 39)) return fail(BHG_E_INVALID, "n too large for one launch (at most 2^39 rays)");
     ENTER_DEVICE(c->device);
     bhg::RedshiftArgs a;
@@ -2005,7 +2132,14 @@ int bhg_redshift_observer_device(bhg_context *c, const bhg_params *p, const bhg_
     a.g = d_g;
     a.n = n;
     a.obs = op;
-    HIP_TRY(bhg::launch_redshift(a, (hipStream_t)stream));
+    if (mp.on) {
+        a.mo = mp;
+        a.object_id = d_object_id;
+        std::memcpy(a.spheres, spheres, sizeof(double) * 4 * (size_t)n_spheres);
+        HIP_TRY(bhg::launch_redshift_motion(a, (hipStream_t)stream));
+    } else {
+        HIP_TRY(bhg::launch_redshift(a, (hipStream_t)stream));
+    }
     return BHG_OK;
 }
 
@@ -2019,9 +2153,26 @@ int bhg_redshift_observer_host(bhg_context *c, const bhg_params *p, const bhg_re
                                const double *x0, int x0_is_shared, const double *k0, const double *end, const uint8_t *flags,
                                size_t n, double *g)
 {
+    return bhg_redshift_motion_host(c, p, rs, obs, nullptr, nullptr, 0, x0, x0_is_shared, k0, end, flags, nullptr, n, g);
+}
+
+int bhg_redshift_motion_host(bhg_context *c, const bhg_params *p, const bhg_redshift *rs, const bhg_observer *obs,
+                             const bhg_object_motion *motion, const double *spheres, int32_t n_spheres, const double *x0,
+                             int x0_is_shared, const double *k0, const double *end, const uint8_t *flags, const int8_t *object_id,
+                             size_t n, double *g)
+{
     bhg::RedshiftParams rp;   // (checked here too, before the context and before any copy)
     int rc = bhg::redshift_params(p, rs, p && p->disk_r_out > 0.0 ? p->disk_r_in : -1.0, x0_is_shared ? x0 : nullptr, &rp);
     if (rc != BHG_OK) return rc;
+    bhg::MotionParams mp;
+    std::memset(&mp, 0, sizeof(mp));
+    if (motion) {
+        if (n_spheres < 0 || n_spheres > BHG_MAX_SPHERES)
+            return fail(BHG_E_INVALID, "n_spheres must be in [0, BHG_MAX_SPHERES], not " + std::to_string(n_spheres));
+        if (n_spheres > 0 && !spheres) return fail(BHG_E_INVALID, "spheres is NULL");
+        rc = bhg::motion_params(p, motion, spheres, n_spheres, &mp);
+        if (rc != BHG_OK) return rc;
+    }
     bhg::ObserverParams op;
     if (obs) {
         rc = bhg::observer_params(p, obs, x0_is_shared ? x0 : nullptr, &op);
@@ -2031,19 +2182,22 @@ int bhg_redshift_observer_host(bhg_context *c, const bhg_params *p, const bhg_re
     if (!x0) return fail(BHG_E_INVALID, "x0 is NULL");
     if (n == 0) return BHG_OK;
     if (!k0 || !flags || !g) return fail(BHG_E_INVALID, "k0 / flags / g is NULL");
+    if (mp.on && !object_id) return fail(BHG_E_INVALID, "moving object spheres need object_id");
     ENTER_DEVICE(c->device);
-    // one block: [x0 (per ray)][k0][end][g] doubles, then the flags
-    const size_t nx = x0_is_shared ? 0 : n * 3, ne = end ? n * 6 : 0;
-    rc = ensure(&c->d_in, &c->d_in_bytes, (nx + n * 3 + ne + n) * sizeof(double) + n);
+    // one block: [x0 (per ray)][k0][end][g] doubles, then the flags, then the object ids (moving spheres only)
+    const size_t nx = x0_is_shared ? 0 : n * 3, ne = end ? n * 6 : 0, no = mp.on ? n : 0;
+    rc = ensure(&c->d_in, &c->d_in_bytes, (nx + n * 3 + ne + n) * sizeof(double) + n + no);
     if (rc != BHG_OK) return rc;
     double *dx = (double *)c->d_in, *dk = dx + nx, *de = dk + n * 3, *dg = de + ne;
     uint8_t *df = (uint8_t *)(dg + n);
+    int8_t *dob = (int8_t *)(df + n);
     if (nx) HIP_TRY(hipMemcpyAsync(dx, x0, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(dk, k0, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (ne) HIP_TRY(hipMemcpyAsync(de, end, ne * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(df, flags, n, hipMemcpyHostToDevice, c->stream));
-    rc = bhg_redshift_observer_device(c, p, rs, obs, x0_is_shared ? x0 : nullptr, nx ? dx : nullptr, dk, ne ? de : nullptr, df, n,
-                                      dg, c->stream);
+    if (no) HIP_TRY(hipMemcpyAsync(dob, object_id, no, hipMemcpyHostToDevice, c->stream));
+    rc = bhg_redshift_motion_device(c, p, rs, obs, motion, spheres, n_spheres, x0_is_shared ? x0 : nullptr, nx ? dx : nullptr, dk,
+                                    ne ? de : nullptr, df, no ? dob : nullptr, n, dg, c->stream);
     if (rc != BHG_OK) return rc;
     HIP_TRY(hipMemcpyAsync(g, dg, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));

@@ -45,6 +45,9 @@ int object_texture_params(const bhg_object_textures *ot, int32_t n_spheres, Obje
 int thermal_check(const bhg_disk_thermal *th);
 int thermal_params(const bhg_params *p, const bhg_disk_thermal *th, const bhg_redshift *rs, const bhg_polarisation *pol,
                    double disk_r_in, const double *x0, ThermalParams *out, RedshiftParams *rp);
+// bhgeo_capi.hip: object motion on its own (finite, for n_spheres spheres), and against the spheres and the trace parameters
+int motion_check(const bhg_object_motion *mo, int32_t n_spheres);
+int motion_params(const bhg_params *p, const bhg_object_motion *mo, const double *spheres, int32_t n_spheres, MotionParams *out);
 }
 
 namespace {
@@ -220,6 +223,8 @@ struct bhg_frame {
     std::vector<float> otex[BHG_MAX_SPHERES];    // host copies of the object textures, empty = white
     bool thermal = false;           // bhg_frame_set_disk_thermal; false: the disk's colour of the scene
     bhg_disk_thermal th = {};
+    bool moving = false;            // bhg_frame_set_object_motion; false: the object spheres at rest
+    bhg_object_motion mo = {};
     int32_t otex_w[BHG_MAX_SPHERES] = {}, otex_h[BHG_MAX_SPHERES] = {};
     // root (device of shard 0)
     DevBuf recv, perm, image;       // [n_dev * pmax][4] float, [H W] int64, [H W][4] float
@@ -684,6 +689,18 @@ int bhg_frame_set_disk_thermal(bhg_frame *f, const bhg_disk_thermal *th)
     return BHG_OK;
 }
 
+int bhg_frame_set_object_motion(bhg_frame *f, const bhg_object_motion *mo)
+{
+    if (!f) return fail(BHG_E_INVALID, "frame is NULL");
+    if (mo) {
+        // against the scene's spheres as they are now (the horizon and the timelike bound need the metric: checked at every render)
+        BHG_TRY(bhg::motion_check(mo, f->scene.n_spheres));
+        f->mo = *mo;
+    }
+    f->moving = mo != nullptr;
+    return BHG_OK;
+}
+
 int bhg_frame_set_object_textures(bhg_frame *f, const bhg_object_textures *ot)
 try {
     if (!f) return fail(BHG_E_INVALID, "frame is NULL");
@@ -780,6 +797,11 @@ try {
         BHG_TRY(bhg::thermal_params(&prm, th, redshift ? &f->rs : nullptr, nullptr, has_disk ? f->scene.disk_r_in : -1.0,
                                     f->cam.origin, &tp, &rp));
     }
+    const bhg_object_motion *mo = f->moving && has_obj ? &f->mo : nullptr;
+    if (mo) {
+        bhg::MotionParams mp;
+        BHG_TRY(bhg::motion_params(&prm, mo, &f->scene.spheres[0][0], f->scene.n_spheres, &mp));
+    }
 
     // -- every device: (rays, scene images once) trace, shade + sample mean into its slab ---------------------------
     for (size_t r = 0; r < world; r++) {
@@ -824,10 +846,10 @@ try {
         fill_scene(f, s, &sc);
         bhg_object_textures ot;
         if (textured) fill_object_textures(f, &s, &ot);
-        BHG_TRY(bhg_shade_scene_thermal_device(s.ctx, dir_only ? nullptr : s.end.as<double>(), dir_only ? s.dir.as<double>() : nullptr,
-                                               s.flags.as<uint8_t>(), has_obj ? s.obj.as<int8_t>() : nullptr, s.P, S, &sc, &prm,
-                                               redshift ? &f->rs : nullptr, obs, textured ? &ot : nullptr, f->cam.origin,
-                                               s.k0.as<double>(), nullptr, dst, scatter, nullptr, nullptr, th, s.stream));
+        BHG_TRY(bhg_shade_scene_moving_device(s.ctx, dir_only ? nullptr : s.end.as<double>(), dir_only ? s.dir.as<double>() : nullptr,
+                                              s.flags.as<uint8_t>(), has_obj ? s.obj.as<int8_t>() : nullptr, s.P, S, &sc, &prm,
+                                              redshift ? &f->rs : nullptr, obs, textured ? &ot : nullptr, f->cam.origin,
+                                              s.k0.as<double>(), nullptr, dst, scatter, nullptr, nullptr, th, mo, s.stream));
         s.dir_traced = dir_only;
     }
     // -- ONE gather onto the first device -----------------------------------------------------------------------------

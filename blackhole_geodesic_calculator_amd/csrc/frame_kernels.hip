@@ -417,6 +417,101 @@ __global__ void __launch_bounds__(256) redshift_kernel(const RedshiftArgs A)
     A.g[i] = observer_g<OBS>(A.p, A.obs, xc, A.k0 + i * 3, ray_class(A.flags[i]), A.end ? A.end + i * 6 : nullptr);
 }
 
+// ---- moving and spinning object spheres -------------------------------------------------------
+// g of an object ray that ends at e (its end record: position, direction) on a sphere of centre c whose surface moves with
+// V = v + w x (e - c) (world axes, dx/dt), from the camera state (xc, kc).  The formulas are the traced picture's, as
+// redshift_g's: there the emitter moves with -V (Kerr: relative to the traced ZAMO, whose flow it keeps), so with k_i V^i the
+// traced ray's covariant momentum contracted with V,
+//     Schwarzschild  g = 1 / (sqrt(f_c) u^t (1 + k_i V^i / E)),          u^t = 1 / sqrt(f - |V|^2 - h (n.V)^2)
+//     Kerr           g = O / (u^t (1 - omega b + k_i V^i / E)),          u^t = 1 / (alpha sqrt(1 - beta^2))
+// k at the hit is rebuilt from the camera's constants -- Schwarzschild E and the vector L = x_c x k0 (k_r = s_r sqrt(E^2 -
+// f L^2 / r^2) / f, k_perp = L x x / r^2), Kerr E, L and Carter's Q (k_r = s_r sqrt(R) / Delta, k_th = s_th sqrt(Theta)) --
+// with only the signs s_r (Kerr: and s_th) from the end record's direction.  V = 0 gives redshift_g's static / ZAMO g up to
+// rounding; the callers take redshift_g itself for a sphere at rest.
+__device__ double object_g_moving(const RedshiftParams &P, const double v[3], const double w[3], const double c[3], const double xc[3],
+                                  const double kc[3], const double *e)
+{
+    const double M = 0.5 * P.r_s;
+    const double x = e[0], y = e[1], z = e[2];
+    const double dx = x - c[0], dy = y - c[1], dz = z - c[2];
+    const double V[3] = {v[0] + (w[1] * dz - w[2] * dy), v[1] + (w[2] * dx - w[0] * dz), v[2] + (w[0] * dy - w[1] * dx)};
+    if (P.rhs == BHG_RHS_KERR_BL_) {
+        const double a = P.spin, a2 = a * a;
+        double px[3] = {xc[0], xc[1], xc[2]}, pk[3] = {kc[0], kc[1], kc[2]}, E, L;
+        kerr_cart_to_bl(a, M, 0.0, px, pk, E, L);     // the trace's own E and L, bit for bit
+        const double b = L / E;
+        double st_c, ct_c, alpha_c, omega_c;
+        sincos_pi4(px[1], st_c, ct_c);
+        kerr_zamo(M, a, px[0], ct_c * ct_c, alpha_c, omega_c);
+        const double O = (1.0 - omega_c * b) / alpha_c;   // -k.u_obs / E
+        const double kth_c = __builtin_fma(a2 * ct_c, ct_c, px[0] * px[0]) * pk[1];
+        const double Q = kth_c * kth_c + ct_c * ct_c * (L * L / (st_c * st_c) - a2 * E * E);
+        // the hit: BL r, cos / sin theta (x = sqrt(r^2 + a^2) sin th cos ph, z = r cos th)
+        const double rho2 = x * x + y * y, bb = rho2 + z * z - a2;
+        const double r = sqrt(0.5 * (bb + sqrt(bb * bb + 4.0 * a2 * z * z))), r2 = r * r, R2 = r2 + a2;
+        const double ct = z / r, rho = sqrt(rho2), st = rho / sqrt(R2);
+        double alpha, omega;
+        kerr_zamo(M, a, r, ct * ct, alpha, omega);
+        const double Sig = r2 + a2 * ct * ct, Del = r2 - 2.0 * M * r + a2, Aq = R2 * R2 - a2 * Del * st * st;
+        // V on the BL coordinate basis (the inverse Jacobian of the embedding)
+        const double vr_xy = x * V[0] + y * V[1];
+        const double Vr = (r * vr_xy + R2 * ct * V[2]) / Sig;
+        const double Vth = (sqrt(R2) * ct * vr_xy / rho - r * rho * V[2] / sqrt(R2)) / Sig;
+        const double Vph = (x * V[1] - y * V[0]) / rho2;
+        const double b2 = ((Sig / Del) * Vr * Vr + Sig * Vth * Vth + (Aq * st * st / Sig) * Vph * Vph) / (alpha * alpha);
+        const double ut = 1.0 / (alpha * sqrt(1.0 - b2));
+        // the photon at the hit from (E, L, Q); signs of k^r, k^th from the end direction
+        const double d0 = e[3], d1 = e[4], d2 = e[5], dxy = x * d0 + y * d1;
+        const double sr = (r2 * dxy + R2 * z * d2) < 0.0 ? -1.0 : 1.0;
+        const double sth = (R2 * z * dxy - r2 * rho2 * d2) < 0.0 ? -1.0 : 1.0;
+        const double Pp = R2 * E - a * L, aEL = a * E - L;
+        const double k_r = sr * sqrt(fmax(Pp * Pp - Del * (Q + aEL * aEL), 0.0)) / Del;
+        const double k_th = sth * sqrt(fmax(Q + ct * ct * (a2 * E * E - L * L / (st * st)), 0.0));
+        const double kV = k_r * Vr + k_th * Vth + L * Vph;
+        return O / (ut * ((1.0 - omega * b) + kV / E));
+    }
+    // Schwarzschild (both Cartesian forms): f = 1 - r_s / r, h = r_s / (r - r_s)
+    const double rc = sqrt(xc[0] * xc[0] + xc[1] * xc[1] + xc[2] * xc[2]);
+    const double fc = 1.0 - P.r_s / rc, hc = P.r_s / (rc - P.r_s);
+    const double nkc = (xc[0] * kc[0] + xc[1] * kc[1] + xc[2] * kc[2]) / rc;
+    const double kkc = kc[0] * kc[0] + kc[1] * kc[1] + kc[2] * kc[2];
+    const double E = fc * sqrt((kkc + hc * nkc * nkc) / fc);
+    const double Lv[3] = {xc[1] * kc[2] - xc[2] * kc[1], xc[2] * kc[0] - xc[0] * kc[2], xc[0] * kc[1] - xc[1] * kc[0]};
+    const double r2 = x * x + y * y + z * z, r = sqrt(r2), f = 1.0 - P.r_s / r, h = P.r_s / (r - P.r_s);
+    const double nV = (x * V[0] + y * V[1] + z * V[2]) / r, VV = V[0] * V[0] + V[1] * V[1] + V[2] * V[2];
+    const double ut = 1.0 / sqrt(f - VV - h * nV * nV);
+    const double LL = Lv[0] * Lv[0] + Lv[1] * Lv[1] + Lv[2] * Lv[2];
+    const double sr = (x * e[3] + y * e[4] + z * e[5]) < 0.0 ? -1.0 : 1.0;
+    const double k_r = sr * sqrt(fmax(E * E - f * LL / r2, 0.0)) / f;     // k_i n^i
+    const double xV[3] = {y * V[2] - z * V[1], z * V[0] - x * V[2], x * V[1] - y * V[0]};
+    const double kV = k_r * nV + (Lv[0] * xV[0] + Lv[1] * xV[1] + Lv[2] * xV[2]) / r2;
+    return 1.0 / (sqrt(fc) * ut * (1.0 + kV / E));
+}
+
+// observer_g with moving object spheres: an object ray whose sphere j moves takes object_g_moving (times the observer's
+// factor with OBS), every other ray observer_g<OBS> as it stands
+template <bool OBS>
+__device__ __forceinline__ double moving_g(const RedshiftParams &P, const ObserverParams &O, const MotionParams &mo,
+                                           const double (*spheres)[4], const double xc[3], const double kc[3], int cls,
+                                           const double *e, int j)
+{
+    if (cls != RS_OBJECT || !e || j < 0 || j >= BHG_MAX_SPHERES_ || !((mo.moving >> j) & 1u))
+        return observer_g<OBS>(P, O, xc, kc, cls, e);
+    const double g = object_g_moving(P, mo.v[j], mo.w[j], spheres[j], xc, kc, e);
+    return OBS ? g * observer_doppler(P, O.beta, xc, kc) : g;
+}
+
+template <bool OBS>
+__global__ void __launch_bounds__(256) redshift_motion_kernel(const RedshiftArgs A)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= A.n) return;
+    const double *xc = A.x0 ? A.x0 + i * 3 : A.p.x0;
+    const int cls = ray_class(A.flags[i]);
+    const int j = (cls == RS_OBJECT && A.object_id) ? (int)A.object_id[i] : -1;
+    A.g[i] = moving_g<OBS>(A.p, A.obs, A.mo, A.spheres, xc, A.k0 + i * 3, cls, A.end ? A.end + i * 6 : nullptr, j);
+}
+
 // ---- disk polarisation -----------------------------------------------------------------------
 // The Walker-Penrose constant kappa = (A - i B)(r - i a cos th) of the traced ray k and a vector f, BL components (t, r, th, ph):
 //     A = (k^t f^r - k^r f^t) + a sin^2 th (k^r f^ph - k^ph f^r),  B = [(r^2 + a^2)(k^ph f^th - k^th f^ph) - a (k^t f^th - k^th f^t)] sin th
@@ -714,6 +809,19 @@ __device__ __forceinline__ void redshift_weigh(const ShadeArgs &A, uint64_t i, i
     rgb[2] *= w;
 }
 
+// redshift_weigh for an object ray of sphere j with moving spheres (moving_g)
+template <bool OBS>
+__device__ __forceinline__ void redshift_weigh_moving(const ShadeArgs &A, uint64_t i, int j, const double *e, double rgb[3])
+{
+    if (!(A.rs.apply & BHG_REDSHIFT_OBJECTS_)) return;
+    const double g = moving_g<OBS>(A.rs, A.obs, A.mo, A.spheres, A.rs.x0, A.k0 + i * 3, RS_OBJECT, e, j), n = A.rs.exponent;
+    const double g2 = g * g;
+    const double w = n == 4.0 ? g2 * g2 : (n == 3.0 ? g2 * g : pow(g, n));
+    rgb[0] *= w;
+    rgb[1] *= w;
+    rgb[2] *= w;
+}
+
 // The colour of ONE ray (sample s of pixel p): black for a horizon ray (:242-244), the disk's / an object's colour, or the
 // sky in its exit direction.
 // RS: the redshift instance (rgb *= g^n by class); without it the kernels are the frame path's as they were.  OBS (with RS
@@ -721,7 +829,8 @@ __device__ __forceinline__ void redshift_weigh(const ShadeArgs &A, uint64_t i, i
 // POL: a disk ray also gets its Stokes weights qu = (delta cos 2chi, delta sin 2chi), every other ray (0, 0); rgb is untouched.
 // THERM (with RS only): a disk ray's colour is its thermal emission (disk_thermal, g already in it: the disk bit of rs.apply
 // is not applied again); objects and sky as rs.apply says.
-template <bool RS, bool OBS, bool TEX, bool POL, bool THERM>
+// MOV (with RS only): an object ray's g is that of its sphere's moving surface (moving_g); disk and sky rays as without it.
+template <bool RS, bool OBS, bool TEX, bool POL, bool THERM, bool MOV>
 __device__ __forceinline__ void ray_colour(const ShadeArgs &A, uint64_t i, uint8_t fl, double c0, double c1, double c2, double rgb[3],
                                            double qu[2])
 {
@@ -745,7 +854,10 @@ __device__ __forceinline__ void ray_colour(const ShadeArgs &A, uint64_t i, uint8
             object_colour_tex(A, e, (int)A.object_id[i], rgb);
         else
             object_colour(A, e, (int)A.object_id[i], rgb);
-        if (RS) redshift_weigh<OBS>(A, i, RS_OBJECT, BHG_REDSHIFT_OBJECTS_, e, rgb);
+        if (MOV)
+            redshift_weigh_moving<OBS>(A, i, (int)A.object_id[i], e, rgb);
+        else if (RS)
+            redshift_weigh<OBS>(A, i, RS_OBJECT, BHG_REDSHIFT_OBJECTS_, e, rgb);
         return;
     }
     // theta = 1 - acos(d_z / |d|) / pi (:373), phi = atan2(d_y, d_x) / pi (:374); exit directions are not unit
@@ -794,7 +906,7 @@ __device__ __forceinline__ void write_stokes(const ShadeArgs &A, uint64_t p, con
 // the kernel is a latency chain per ray, not a bandwidth problem (131 MB in, 16 MB out per config-2 frame).
 // POL: each thread also stages the six Stokes products (Q, then U, of each channel; 9 doubles per thread in all, 18 KB per
 // workgroup) and the pixel's Q / U means go to pol.qu[p].
-template <bool RS, bool OBS, bool TEX, bool POL, bool THERM>
+template <bool RS, bool OBS, bool TEX, bool POL, bool THERM, bool MOV>
 __global__ void __launch_bounds__(256) shade_reduce_kernel(const ShadeArgs A, const uint32_t ppb)
 {
     __shared__ double col[256 * 3];
@@ -810,13 +922,13 @@ __global__ void __launch_bounds__(256) shade_reduce_kernel(const ShadeArgs A, co
         double rgb[3];
         if (POL) {
             double qu[2];
-            ray_colour<RS, OBS, TEX, POL, THERM>(A, i, A.flags[i], d[0], d[1], d[2], rgb, qu);
+            ray_colour<RS, OBS, TEX, POL, THERM, MOV>(A, i, A.flags[i], d[0], d[1], d[2], rgb, qu);
             for (int c = 0; c < 3; c++) {
                 pcol[t * 6 + c] = qu[0] * rgb[c];
                 pcol[t * 6 + 3 + c] = qu[1] * rgb[c];
             }
         } else {
-            ray_colour<RS, OBS, TEX, POL, THERM>(A, i, A.flags[i], d[0], d[1], d[2], rgb, nullptr);
+            ray_colour<RS, OBS, TEX, POL, THERM, MOV>(A, i, A.flags[i], d[0], d[1], d[2], rgb, nullptr);
         }
         col[t * 3 + 0] = rgb[0];
         col[t * 3 + 1] = rgb[1];
@@ -845,7 +957,7 @@ __global__ void __launch_bounds__(256) shade_reduce_kernel(const ShadeArgs A, co
 }
 
 // More samples than a workgroup has threads: one thread per pixel, samples accumulated in registers in sample order.
-template <bool RS, bool OBS, bool TEX, bool POL, bool THERM>
+template <bool RS, bool OBS, bool TEX, bool POL, bool THERM, bool MOV>
 __global__ void __launch_bounds__(256) shade_reduce_serial_kernel(const ShadeArgs A)
 {
     const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -856,7 +968,7 @@ __global__ void __launch_bounds__(256) shade_reduce_serial_kernel(const ShadeArg
         const uint64_t i = (uint64_t)s * A.n_pixels + p;
         const double *d = A.dir ? A.dir + i * 3 : A.end + i * 6 + 3;
         double rgb[3], qu[2];
-        ray_colour<RS, OBS, TEX, POL, THERM>(A, i, A.flags[i], d[0], d[1], d[2], rgb, qu);
+        ray_colour<RS, OBS, TEX, POL, THERM, MOV>(A, i, A.flags[i], d[0], d[1], d[2], rgb, qu);
         acc[0] += rgb[0];
         acc[1] += rgb[1];
         acc[2] += rgb[2];
@@ -926,6 +1038,16 @@ hipError_t launch_redshift(const RedshiftArgs &a, hipStream_t s)
     return hipGetLastError();
 }
 
+hipError_t launch_redshift_motion(const RedshiftArgs &a, hipStream_t s)
+{
+    if (a.n == 0) return hipSuccess;
+    if (a.obs.on)
+        BHG_LAUNCH(redshift_motion_kernel<true>, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
+    else
+        BHG_LAUNCH(redshift_motion_kernel<false>, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_polarisation(const PolarisationArgs &a, bool obs, hipStream_t s)
 {
     if (a.n == 0) return hipSuccess;
@@ -946,37 +1068,48 @@ hipError_t launch_disk_thermal(const ThermalArgs &a, hipStream_t s)
     return hipGetLastError();
 }
 
-// one instance per (redshift, observer, textures, polarisation, thermal): the template flags are the launch's run-time switches
-template <bool RS, bool OBS, bool TEX, bool POL, bool THERM>
+// one instance per (redshift, observer, textures, polarisation, thermal, motion): the template flags are the launch's run-time
+// switches
+template <bool RS, bool OBS, bool TEX, bool POL, bool THERM, bool MOV>
 void launch_shade_instance(const ShadeArgs &a, hipStream_t s)
 {
     if (a.samples > 256) {
         const dim3 grid((unsigned)((a.n_pixels + 255) / 256));
-        BHG_LAUNCH((shade_reduce_serial_kernel<RS, OBS, TEX, POL, THERM>), grid, dim3(256), 0, s, a);
+        BHG_LAUNCH((shade_reduce_serial_kernel<RS, OBS, TEX, POL, THERM, MOV>), grid, dim3(256), 0, s, a);
         return;
     }
     const uint32_t ppb = 256u / (uint32_t)a.samples;      // pixels per workgroup
     const dim3 grid((unsigned)((a.n_pixels + ppb - 1) / ppb));
-    BHG_LAUNCH((shade_reduce_kernel<RS, OBS, TEX, POL, THERM>), grid, dim3(256), 0, s, a, ppb);
+    BHG_LAUNCH((shade_reduce_kernel<RS, OBS, TEX, POL, THERM, MOV>), grid, dim3(256), 0, s, a, ppb);
 }
 
-// the thermal instances are redshift instances (the disk's emission needs g); THERM = true is instantiated with RS = true only
-template <bool TEX, bool POL>
-void launch_shade_tex(const ShadeArgs &a, hipStream_t s)
+// the thermal instances are redshift instances (the disk's emission needs g); THERM = true is instantiated with RS = true only.
+// So are the motion instances, taken only when objects are weighted (motion changes nothing else): MOV = true with RS = true only
+template <bool TEX, bool POL, bool MOV>
+void launch_shade_mov(const ShadeArgs &a, hipStream_t s)
 {
     const bool therm = a.th.on != 0, rs = a.rs.apply != 0 || therm, obs = rs && a.obs.on;
     if (therm) {
         if (obs)
-            launch_shade_instance<true, true, TEX, POL, true>(a, s);
+            launch_shade_instance<true, true, TEX, POL, true, MOV>(a, s);
         else
-            launch_shade_instance<true, false, TEX, POL, true>(a, s);
+            launch_shade_instance<true, false, TEX, POL, true, MOV>(a, s);
     } else if (obs) {
-        launch_shade_instance<true, true, TEX, POL, false>(a, s);
+        launch_shade_instance<true, true, TEX, POL, false, MOV>(a, s);
     } else if (rs) {
-        launch_shade_instance<true, false, TEX, POL, false>(a, s);
-    } else {
-        launch_shade_instance<false, false, TEX, POL, false>(a, s);
+        launch_shade_instance<true, false, TEX, POL, false, MOV>(a, s);
+    } else if (!MOV) {
+        launch_shade_instance<false, false, TEX, POL, false, false>(a, s);
     }
+}
+
+template <bool TEX, bool POL>
+void launch_shade_tex(const ShadeArgs &a, hipStream_t s)
+{
+    if (a.mo.on && (a.rs.apply & BHG_REDSHIFT_OBJECTS_))
+        launch_shade_mov<TEX, POL, true>(a, s);
+    else
+        launch_shade_mov<TEX, POL, false>(a, s);
 }
 
 hipError_t launch_shade(const ShadeArgs &a, hipStream_t s)

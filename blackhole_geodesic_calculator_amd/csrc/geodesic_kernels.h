@@ -151,6 +151,16 @@ __host__ __device__ inline double page_thorne(const ThermalParams &T, double x)
     return b / ((x2 * x2) * ((x2 * x - 3.0 * x) + 2.0 * T.astar));
 }
 
+// moving and spinning object spheres (frame_kernels.hip, object_g_moving): sphere j's surface moves with
+// v[j] + w[j] x (x - c_j), world axes, coordinate velocities.  moving: bit j set when sphere j has a nonzero v or w (the others
+// take the at-rest g of redshift_g); on = 0: the kernels' instances without motion are launched and never read this struct
+struct MotionParams {
+    double v[BHG_MAX_SPHERES_][3];
+    double w[BHG_MAX_SPHERES_][3];
+    uint32_t moving;
+    int32_t on;
+};
+
 // camera-ray generation (frame_kernels.hip)
 struct RaygenArgs {
     const double *jitter;   // [S*H*W*2] MT19937 doubles, sample-major then row-major pixels, (u1, u2); nullptr = pixel
@@ -187,6 +197,11 @@ struct RedshiftArgs {
     double *g;             // [n]
     uint64_t n;
     ObserverParams obs;    // beta and on only: g of a moving observer (bhg_redshift_observer_device)
+    // moving object spheres (bhg_redshift_motion_device, launch_redshift_motion; launch_redshift never reads these): last, so
+    // that no other member moves
+    MotionParams mo;
+    const int8_t *object_id;                 // [n]: the sphere of each object ray
+    double spheres[BHG_MAX_SPHERES_][4];     // {cx, cy, cz, radius}
 };
 
 // shading + per-pixel multisample mean (frame_kernels.hip)
@@ -219,9 +234,11 @@ struct ShadeArgs {
     // polarisation (bhg_shade_scene_polarised_device): launch_shade takes the polarised instance when pol.on != 0
     PolarisationParams pol;
     // the thermal disk (bhg_shade_scene_thermal_device): launch_shade takes the thermal instance when th.on != 0 -- always a
-    // redshift instance, rs (metric, camera, sense) filled and rs.apply as the caller gave it or 0; last, so that no other
-    // member moves
+    // redshift instance, rs (metric, camera, sense) filled and rs.apply as the caller gave it or 0
     ThermalParams th;
+    // moving object spheres (bhg_shade_scene_moving_device): launch_shade takes the motion instance when mo.on != 0 and
+    // rs.apply weighs objects -- always a redshift instance; last, so that no other member moves
+    MotionParams mo;
 };
 
 // one thread per ray: (chi, delta, mu) from the camera state (x0, k0) and the end record (bhg_polarisation_device)
@@ -252,6 +269,7 @@ struct ThermalArgs {
 hipError_t launch_raygen(const RaygenArgs &a, hipStream_t s);
 hipError_t launch_shade(const ShadeArgs &a, hipStream_t s);
 hipError_t launch_redshift(const RedshiftArgs &a, hipStream_t s);
+hipError_t launch_redshift_motion(const RedshiftArgs &a, hipStream_t s);
 hipError_t launch_polarisation(const PolarisationArgs &a, bool obs, hipStream_t s);
 hipError_t launch_disk_thermal(const ThermalArgs &a, hipStream_t s);
 hipError_t launch_split_end(const double *end, uint64_t n, double *loc, double *dir, hipStream_t s);

@@ -88,6 +88,7 @@ class DeviceFrame:
         self.d_qu = None              # [P, 6] fp64 Stokes Q / U images (shade_stokes)
         self.disk_thermal = None      # _ffi.DiskThermal (set_disk_thermal) or None: the disk's colour of the scene
         self.object_textures = None   # set_object_textures: (device textures per sphere, rotations, modes, emission) or None
+        self.object_motion = None     # _ffi.ObjectMotion (set_object_motion) or None: the spheres at rest
 
     def _stream(self):
         return torch.cuda.current_stream(self.dev).cuda_stream
@@ -160,6 +161,16 @@ class DeviceFrame:
             self.disk_thermal = t_peak
         else:
             self.disk_thermal = _ffi.make_disk_thermal(t_peak, nu, weights, f_col, scale, disk_sense)
+
+    def set_object_motion(self, velocity=None, angular_velocity=None):
+        """Moving and spinning object spheres in every later shade (bhg_shade_scene_moving_device):
+        velocity and angular_velocity [n][3] per sphere of set_objects() (world axes, dx/dt and rad per unit t; None: zeros;
+        observer.circular_orbit_motion gives an orbit).  Only the redshift of object rays changes, and only with redshift on
+        objects.  Both None: off -- the images as without motion, bit for bit."""
+        if velocity is None and angular_velocity is None:
+            self.object_motion = None
+        else:
+            self.object_motion = _ffi.make_object_motion(velocity, angular_velocity)
 
     def set_object_textures(self, textures=None, rotations=None, modes=None, emission=None):
         """Textured, oriented and emissive object spheres (bhg_shade_scene_textured_device), per sphere of
@@ -257,17 +268,19 @@ class DeviceFrame:
         return traced
 
     def _shade(self, d_rgba=0, d_rgba_f32=0, scatter=None, pol=None, d_qu=0):
-        """The one shade call of every output (bhg_shade_scene_thermal_device): redshift, the observer, the object textures,
-        the polarisation (shade_stokes only) and the thermal disk as set, each None when off -- pol = None and no thermal disk
-        is the textured call exactly."""
+        """The one shade call of every output (bhg_shade_scene_moving_device): redshift, the observer, the object textures,
+        the polarisation (shade_stokes only), the thermal disk and the object motion as set, each None when off -- pol = None
+        and none of the others is the textured call exactly."""
         form = self._shade_form()
-        self.ctx.shade_scene_thermal_device(self.d_end.data_ptr() if form == "end" else 0, self.d_flags.data_ptr(), self.P, self.S,
-                                            self.scene(), self._params, self.redshift, self.observer,
-                                            self._object_textures() if self._textured() else None, pol, d_qu, self.disk_thermal,
-                                            x0_shared=self.origin, d_k0=self.d_k0.data_ptr(), d_rgba=d_rgba, d_rgba_f32=d_rgba_f32,
-                                            d_object_id=0 if self.d_obj is None else self.d_obj.data_ptr(),
-                                            d_scatter=0 if scatter is None else scatter.data_ptr(),
-                                            d_end_dir=self.d_dir.data_ptr() if form == "dir" else 0, stream=self._stream())
+        has_obj = self.spheres is not None and len(self.spheres) > 0
+        self.ctx.shade_scene_moving_device(self.d_end.data_ptr() if form == "end" else 0, self.d_flags.data_ptr(), self.P, self.S,
+                                           self.scene(), self._params, self.redshift, self.observer,
+                                           self._object_textures() if self._textured() else None, pol, d_qu, self.disk_thermal,
+                                           self.object_motion if has_obj else None,
+                                           x0_shared=self.origin, d_k0=self.d_k0.data_ptr(), d_rgba=d_rgba, d_rgba_f32=d_rgba_f32,
+                                           d_object_id=0 if self.d_obj is None else self.d_obj.data_ptr(),
+                                           d_scatter=0 if scatter is None else scatter.data_ptr(),
+                                           d_end_dir=self.d_dir.data_ptr() if form == "dir" else 0, stream=self._stream())
 
     def shade(self):
         self._shade(d_rgba=self.d_rgba.data_ptr())

@@ -80,7 +80,9 @@ class GeodesicIntegratorSchwarzschild:
             object_id[...]             int8, only with spheres: index of the sphere hit, else -1
             g[...]                     only with redshift=dict(disk_sense=+1 or -1): nu_obs / nu_em of each ray between
                                        the camera's ZAMO and its emitter (disk in Keplerian orbit of that sense, object at
-                                       rest, sky at rest at infinity; 0 for horizon rays, NaN for NaN rays), bhg_redshift_host
+                                       rest, sky at rest at infinity; 0 for horizon rays, NaN for NaN rays), bhg_redshift_host;
+                                       with redshift=dict(..., object_motion=dict(velocity=[n][3], angular_velocity=[n][3]))
+                                       the spheres move (bhg_redshift_motion_host)
             evpa[...], pol_degree[...], mu_em[...]
                                        only with polarisation=dict(degree=..., disk_sense=..., up=...): the disk ray's
                                        polarisation angle at the camera (from image up towards image left, in (-pi/2, pi/2]),
@@ -115,7 +117,13 @@ class GeodesicIntegratorSchwarzschild:
             out["object_id"] = obj.reshape(lead)
         if redshift is not None:
             rs = _ffi.make_redshift(apply=(), disk_sense=redshift.get("disk_sense", 1))
-            out["g"] = self._ctx.redshift(k0f, x0f, self.params(max_step, curve_end, r_exit, disk), rs, flags, end).reshape(lead)
+            om = redshift.get("object_motion")
+            if om is None:
+                out["g"] = self._ctx.redshift(k0f, x0f, self.params(max_step, curve_end, r_exit, disk), rs, flags, end).reshape(lead)
+            else:
+                mo = _ffi.make_object_motion(om.get("velocity"), om.get("angular_velocity"))
+                out["g"] = self._ctx.redshift_motion(k0f, x0f, self.params(max_step, curve_end, r_exit, disk), rs, None, mo, spheres,
+                                                     flags, end, obj).reshape(lead)
         if polarisation is not None:
             pol = _ffi.make_polarisation(**polarisation)
             chi, deg, mu = self._ctx.polarisation(k0f, x0f, self.params(max_step, curve_end, r_exit, disk), pol, None, flags, end)

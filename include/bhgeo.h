@@ -60,7 +60,9 @@ extern "C" {
                                   BHG_POLARISATION (bhg_polarisation_device / _host, bhg_shade_scene_polarised_device,
                                   bhg_polarisation_size, struct bhg_polarisation);
                                   BHG_DISK_THERMAL (bhg_disk_thermal_device / _host, bhg_shade_scene_thermal_device,
-                                  bhg_frame_set_disk_thermal, bhg_disk_thermal_size, struct bhg_disk_thermal).
+                                  bhg_frame_set_disk_thermal, bhg_disk_thermal_size, struct bhg_disk_thermal);
+                                  BHG_OBJECT_MOTION (bhg_redshift_motion_device / _host, bhg_shade_scene_moving_device,
+                                  bhg_frame_set_object_motion, bhg_object_motion_size, struct bhg_object_motion).
                                9: redshift -- bhg_redshift_device / _host, bhg_shade_scene_redshift_device, bhg_frame_set_redshift,
                                   bhg_redshift_size, struct bhg_redshift;
                                   nothing of ABI 8 changed.
@@ -552,8 +554,8 @@ int bhg_frame_set_observer(bhg_frame *frame, const bhg_observer *obs);
  * body +x is the image's centre column, body +z its top row.  A slot without a texture has a white texel.
  *   BHG_OBJECT_LIT:      colour = sphere_rgb[j] * (the Lambert lamp sum with shadow rays) * texel
  *   BHG_OBJECT_EMISSIVE: colour = emission[j] * sphere_rgb[j] * texel (no lamps, no shadows)
- * Redshift weighs the colour as any object ray's (the emitter is at rest).  Refused (BHG_E_INVALID, the message names the
- * sphere index), for slots below n_spheres only: a mode other than 0 / 1, a non-finite or negative emission, a texture with
+ * Redshift weighs the colour as any object ray's (the emitter at rest, or moving: section 14).  Refused (BHG_E_INVALID, the
+ * message names the sphere index), for slots below n_spheres only: a mode other than 0 / 1, a non-finite or negative emission, a texture with
  * w or h < 1, a rotation that is neither all-zero nor orthonormal with det +1 (|R^T R - I| <= 1e-9).
  * Member order: tex, tex_w, tex_h, mode, emission, rot (800 bytes). */
 #define BHG_OBJECT_TEXTURES 1
@@ -700,6 +702,60 @@ int bhg_shade_scene_thermal_device(bhg_context *ctx, const double *d_end, const 
 /* The thermal disk in every later render of the frame (its shade calls are bhg_shade_scene_thermal_device).  NULL: off, the
  * frame as without it.  The settings that need no trace parameters are checked here, the rest at every render. */
 int bhg_frame_set_disk_thermal(bhg_frame *frame, const bhg_disk_thermal *th);
+
+/* --- moving and spinning object spheres (within ABI 10) --------------------------------------------
+ * Each object sphere j {c_j, rho_j} gets a centre velocity v[j] and an angular velocity w[j]: world axes, coordinate
+ * quantities (dx/dt and rad per unit t, t the Schwarzschild / Boyer-Lindquist time; c = 1, lengths in the units of r_s).  Its
+ * surface point x moves with V(x) = v[j] + w[j] x (x - c_j).  The sphere stays where the scene puts it (no retarded
+ * positions).  The emitter of an object ray that ends on a moving sphere at x:
+ *   Schwarzschild (both Cartesian forms)  u = u^t (d_t + V),                   u^t = 1 / sqrt(f - |V|^2 - h (n.V)^2)
+ *   Kerr (BL)                             u = u^t (d_t + omega d_phi + V),     u^t = 1 / (alpha sqrt(1 - beta^2)),
+ *                                         beta^2 = (g_rr V^r^2 + g_thth V^th^2 + g_phph V^ph^2) / alpha^2
+ * V relative to the ZAMO's flow in Kerr; omega d_phi = omega z^ x x in the Cartesian embedding.  Motion is given in the picture
+ * disk_sense is given in (section 14 spells out which omega and which Keplerian Omega that is in Kerr).  The photon's momentum
+ * at x is rebuilt from the camera state's constants (Schwarzschild: E and the vector L = x0 x k0; Kerr: E, L and Carter's Q),
+ * with only the signs of its radial (Kerr: and polar) component from the end record; g = (p.u_obs) / (p.u_em), times the
+ * observer's gamma (1 + beta.n) with obs.  A sphere whose v and w are all zero is at rest exactly as without motion (the same
+ * formula, bit for bit).  Motion changes only the object rays' g: in the shade their colour (lit: the Lambert colour as it
+ * is, the reflected light taken as emitted in the surface's rest frame; emissive: texture x strength) is weighted by g^n when
+ * rs->apply has BHG_REDSHIFT_OBJECTS, and not at all otherwise.  Slots at or above n_spheres are not looked at.
+ * Refused (BHG_E_INVALID, the message names the sphere), before the context: a v or w that is not finite; a moving sphere
+ * that reaches the horizon (Schwarzschild |c| - rho <= r_s; Kerr r_lo = sqrt((|c| - rho)^2 - a^2) <= r_+ or |c| - rho <= |a|);
+ * a motion that the sufficient bound does not prove timelike on the whole sphere:
+ *   Schwarzschild  |v| + |w| rho < f(|c| - rho)
+ *   Kerr           |w_z| max(G(r_lo), G(|c| + rho)) + (|v - w_z z^ x c| + |w_perp| rho) / F(r_lo) < 1,
+ *                  G(r) = ((r^2 + a^2)^2 - a^2 Delta) / (r^2 sqrt(Delta)),  F(r) = r Delta / (r^2 + a^2)^(3/2).
+ * Member order: v, w (384 bytes); an all-zero struct is every sphere at rest. */
+#define BHG_OBJECT_MOTION 1
+typedef struct bhg_object_motion {
+    double v[BHG_MAX_SPHERES][3];     /* centre velocity dx/dt of each sphere, world axes */
+    double w[BHG_MAX_SPHERES][3];     /* angular velocity of each sphere about its centre [rad per unit t], world axes */
+} bhg_object_motion;
+size_t bhg_object_motion_size(void);
+/* bhg_redshift_observer_device / _host with moving object spheres: the spheres [n_spheres][4] {cx, cy, cz, radius} of the
+ * trace and its d_object_id [n] (object_id [n] for _host; may be NULL only when no ray hit an object).  motion = NULL: exactly
+ * bhg_redshift_observer_device / _host, bit for bit. */
+int bhg_redshift_motion_device(bhg_context *ctx, const bhg_params *p, const bhg_redshift *rs, const bhg_observer *obs,
+                               const bhg_object_motion *motion, const double *spheres, int32_t n_spheres,
+                               const double *x0_shared, const double *d_x0, const double *d_k0, const double *d_end,
+                               const uint8_t *d_flags, const int8_t *d_object_id, size_t n, double *d_g, void *stream);
+int bhg_redshift_motion_host(bhg_context *ctx, const bhg_params *p, const bhg_redshift *rs, const bhg_observer *obs,
+                             const bhg_object_motion *motion, const double *spheres, int32_t n_spheres, const double *x0,
+                             int x0_is_shared, const double *k0, const double *end, const uint8_t *flags, const int8_t *object_id,
+                             size_t n, double *g);
+/* bhg_shade_scene_thermal_device with moving object spheres: the general shade call.  mo = NULL, or an all-zero mo, is exactly
+ * the thermal call (which is this call with mo = NULL: one implementation, one checking order -- after step 2, the motion
+ * against n_spheres and the trace parameters). */
+int bhg_shade_scene_moving_device(bhg_context *ctx, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
+                                  const int8_t *d_object_id, size_t n_pixels, int32_t samples, const bhg_scene *scene,
+                                  const bhg_params *p, const bhg_redshift *rs, const bhg_observer *obs,
+                                  const bhg_object_textures *ot, const double *x0_shared, const double *d_k0, double *d_rgba,
+                                  float *d_rgba_f32, const int64_t *d_scatter, const bhg_polarisation *pol, double *d_qu,
+                                  const bhg_disk_thermal *th, const bhg_object_motion *mo, void *stream);
+/* Moving object spheres in every later render of the frame (every device, every gather mode; its shade calls are
+ * bhg_shade_scene_moving_device).  NULL: off, the frame as without it.  Checked against the scene's spheres here (those set
+ * at this call) and against the scene and the trace parameters at every render. */
+int bhg_frame_set_object_motion(bhg_frame *frame, const bhg_object_motion *mo);
 
 /* Acceleration probe: acc[n][3] = -Gamma^i_{mu nu} k^mu k^nu at (x[n][3], k[n][3]); host buffers.
  * Lets tests compare the device RHS with the oracle's term by term.  With rhs_form = BHG_RHS_KERR_BL the triples
