@@ -63,8 +63,13 @@ EXPORTS = (
     "bhg_frame_set_disk_thermal",
     "bhg_object_motion_size", "bhg_redshift_motion_device", "bhg_redshift_motion_host", "bhg_shade_scene_moving_device",
     "bhg_frame_set_object_motion",
+    "bhg_math_probe",
 )
 PROBE_FMA, PROBE_STEP_MIX = 0, 1
+# bhg_math_probe: op -> (doubles in, doubles out) per element
+MATH_RCP_NEWTON, MATH_RCP_NR, MATH_RSQRT_NR, MATH_SQRT_NR, MATH_ATAN2_FAST, MATH_SINCOS_PI4, MATH_RCP3_NR, MATH_KERR_CART_TO_BL = range(8)
+MATH_PROBE_SHAPE = {MATH_RCP_NEWTON: (1, 1), MATH_RCP_NR: (1, 1), MATH_RSQRT_NR: (1, 1), MATH_SQRT_NR: (1, 1),
+                    MATH_ATAN2_FAST: (2, 1), MATH_SINCOS_PI4: (1, 2), MATH_RCP3_NR: (3, 3), MATH_KERR_CART_TO_BL: (9, 8)}
 
 GATHER_AUTO, GATHER_COPY, GATHER_RCCL, GATHER_PEER, GATHER_COPY_PEERCALL = 0, 1, 2, 3, 4
 
@@ -568,6 +573,8 @@ def load():
     L.bhg_default_params_sized.argtypes = [C.POINTER(Params), C.c_size_t]
     L.bhg_peak_probe.restype = C.c_int
     L.bhg_peak_probe.argtypes = [C.c_void_p, C.c_int32, C.c_double, _dp]
+    L.bhg_math_probe.restype = C.c_int
+    L.bhg_math_probe.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
     # the handshake include/bhgeo.h asks of every binding: ABI version and the layout of every struct declared above
     if L.bhg_abi_check(ABI_VERSION, C.sizeof(Params), C.sizeof(Camera), C.sizeof(Scene), C.sizeof(FrameScene)) != OK:
         raise ImportError("libbhgeo: " + L.bhg_last_error().decode())
@@ -1002,6 +1009,20 @@ class Context:
         _check(load().bhg_peak_probe(self._h, int(kind), float(target_ms), out))
         return {"tflops": out[0], "ms": out[1], "valu_wave_insts": out[2], "quarter_rate_wave_insts": out[3],
                 "ms_fastest": out[4], "fp64_full_rate_clock_mhz": out[5]}
+
+    def math_probe(self, op, values):
+        """bhg_math_probe (a test hook): values [n] or [n, n_in] float64 through the device primitive `op` (MATH_*), one
+        element per thread -> [n] or [n, n_out] float64."""
+        if op not in MATH_PROBE_SHAPE:
+            raise ValueError(f"unknown math probe op {op}")
+        n_in, n_out = MATH_PROBE_SHAPE[op]
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        if (n_in == 1 and v.ndim != 1) or (n_in > 1 and (v.ndim != 2 or v.shape[1] != n_in)):
+            raise ValueError(f"values must have shape [n]" if n_in == 1 else f"values must have shape [n, {n_in}]")
+        n = v.shape[0]
+        out = np.empty((n,) if n_out == 1 else (n, n_out), np.float64)
+        _check(load().bhg_math_probe(self._h, int(op), v.ctypes.data, n, out.ctypes.data))
+        return out
 
     # -- host buffers -------------------------------------------------------------------
     def trace(self, k0, x0, params: Params, want_accepted=True, spheres=None, want_steps=True, pinned_results=True):

@@ -2456,4 +2456,25 @@ int bhg_peak_probe(bhg_context *c, int32_t kind, double target_ms, double out[6]
     return BHG_OK;
 }
 
+int bhg_math_probe(bhg_context *c, int32_t op, const double *in, size_t n, double *out)
+{
+    // (the refusals come before the context, as everywhere: a test needs no device for them)
+    int n_in = 0, n_out = 0;
+    if (!bhg::math_probe_shape(op, &n_in, &n_out)) return fail(BHG_E_INVALID, "unknown math probe op " + std::to_string(op));
+    if (n > 0 && (!in || !out)) return fail(BHG_E_INVALID, "math probe: in / out is NULL");
+    if (n > ((size_t)1 << 26)) return fail(BHG_E_INVALID, "math probe: at most 2^26 elements per call");
+    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
+    if (n == 0) return BHG_OK;
+    ENTER_DEVICE(c->device);
+    int rc = ensure(&c->d_in, &c->d_in_bytes, n * (size_t)n_in * sizeof(double));
+    if (rc != BHG_OK) return rc;
+    rc = ensure(&c->d_out, &c->d_out_bytes, n * (size_t)n_out * sizeof(double));
+    if (rc != BHG_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(c->d_in, in, n * (size_t)n_in * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(bhg::launch_math_probe(op, (const double *)c->d_in, n, (double *)c->d_out, c->stream));
+    HIP_TRY(hipMemcpyAsync(out, c->d_out, n * (size_t)n_out * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return BHG_OK;
+}
+
 }  // extern "C"

@@ -143,11 +143,15 @@ struct ThermalParams {
 // The Page-Thorne flux shape F^(x), x = sqrt(r / M) > x0 (the caller keeps r > r_ms).  Host (the C layer's search for max F^)
 // and device share it; written out operation by operation as tests/disk_thermal_reference.py restates it: the library is
 // built with -ffp-contract=off, and near r_ms the bracket is a difference of terms of order (x - x0), so the order shows.
+// The bracket vanishes like (x - x0)^2 at the inner edge while each term is of order (x - x0): every logarithm is taken as
+// log1p of d / (x0 - x_i), d = x - x0 (exact by Sterbenz near the edge), so that each term carries a RELATIVE error of an
+// epsilon and the flux eps / (x - x0) relative -- log(q) of the rounded quotient q = 1 + O(d) carried an absolute epsilon, the
+// flux eps / (x - x0)^2, and t_em was wrong by orders of magnitude inside r_ms (1 + 1e-8).
 __host__ __device__ inline double page_thorne(const ThermalParams &T, double x)
 {
-    const double x2 = x * x;
-    double b = (x - T.x0) - (1.5 * T.astar) * log(x / T.x0);
-    for (int i = 0; i < 3; i++) b = b - T.c[i] * log((x - T.xr[i]) / (T.x0 - T.xr[i]));
+    const double x2 = x * x, d = x - T.x0;
+    double b = d - (1.5 * T.astar) * log1p(d / T.x0);
+    for (int i = 0; i < 3; i++) b = b - T.c[i] * log1p(d / (T.x0 - T.xr[i]));
     return b / ((x2 * x2) * ((x2 * x - 3.0 * x) + 2.0 * T.astar));
 }
 
@@ -303,5 +307,9 @@ hipError_t launch_accel_kerr(const double *x, const double *k, double r_s, doubl
 // roofline calibration probes (probe_kernels.hip): kind 0 = pure v_fma_f64, 1 = the DP5(4) step loop's instruction mix
 hipError_t launch_probe(int kind, int grid, uint32_t iters, double *out, hipStream_t s);
 void probe_shape(int kind, uint32_t *valu_per_iter, uint32_t *quarter_per_iter);
+// the math probe (bhg_math_probe, a test hook): n elements through primitive `op` of device_math.h / kerr_start.h, one per thread;
+// math_probe_shape: the doubles per element in and out, false for an unknown op
+bool math_probe_shape(int op, int *n_in, int *n_out);
+hipError_t launch_math_probe(int op, const double *in, uint64_t n, double *out, hipStream_t s);
 
 }  // namespace bhg

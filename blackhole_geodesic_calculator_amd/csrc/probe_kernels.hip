@@ -12,10 +12,15 @@
 //           -> the issue-bound ceiling of a kernel with that mix ("issue_bound").
 //
 // Neither touches memory inside its loop; each lane writes one double at the end so that nothing is optimised away.
+//
+// Also here: math_probe_kernel (bhg_math_probe), a test hook that runs one element per thread through one of the hand-written
+// math primitives.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "geodesic_kernels.h"
+#include "device_math.h"
+#include "kerr_start.h"
 
 namespace bhg {
 
@@ -72,7 +77,71 @@ __global__ __launch_bounds__(64) void probe_mix_kernel(uint32_t iters, double a,
     out[(size_t)blockIdx.x * 64 + threadIdx.x] = s;
 }
 
+// bhg_math_probe: one element per thread through ONE of the hand-written primitives of device_math.h / kerr_start.h, so that a
+// test can compare each with a high-precision reference ulp by ulp.  This unit is built with the flags of the units that use
+// the primitives (-ffp-contract=off included): the probe measures the code the product runs.  in: n_in doubles per element,
+// out: n_out doubles per element (math_probe_shape).
+__global__ __launch_bounds__(256) void math_probe_kernel(int op, const double *in, uint64_t n, double *out)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    switch (op) {
+    case 0: out[i] = rcp_newton(in[i]); break;
+    case 1: out[i] = rcp_nr(in[i]); break;
+    case 2: out[i] = rsqrt_nr(in[i]); break;
+    case 3: out[i] = sqrt_nr(in[i]); break;
+    case 4: out[i] = atan2_fast(in[2 * i], in[2 * i + 1]); break;
+    case 5: {
+        double s, c;
+        sincos_pi4(in[i], s, c);
+        out[2 * i] = s;
+        out[2 * i + 1] = c;
+        break;
+    }
+    case 6: {
+        double o0, o1, o2;
+        rcp3_nr(in[3 * i], in[3 * i + 1], in[3 * i + 2], o0, o1, o2);
+        out[3 * i] = o0;
+        out[3 * i + 1] = o1;
+        out[3 * i + 2] = o2;
+        break;
+    }
+    default: {   // 7: kerr_cart_to_bl (a, M, mu2, x[3], k[3]) -> (r, theta, phi, dr, dtheta, dphi, E, L)
+        const double *p = in + 9 * i;
+        double x[3] = {p[3], p[4], p[5]}, k[3] = {p[6], p[7], p[8]}, E, L;
+        kerr_cart_to_bl(p[0], p[1], p[2], x, k, E, L);
+        double *o = out + 8 * i;
+        o[0] = x[0];
+        o[1] = x[1];
+        o[2] = x[2];
+        o[3] = k[0];
+        o[4] = k[1];
+        o[5] = k[2];
+        o[6] = E;
+        o[7] = L;
+        break;
+    }
+    }
+}
+
 }  // namespace
+
+// doubles per element of each bhg_math_probe operation; false for an unknown one
+bool math_probe_shape(int op, int *n_in, int *n_out)
+{
+    static const int shape[8][2] = {{1, 1}, {1, 1}, {1, 1}, {1, 1}, {2, 1}, {1, 2}, {3, 3}, {9, 8}};
+    if (op < 0 || op > 7) return false;
+    *n_in = shape[op][0];
+    *n_out = shape[op][1];
+    return true;
+}
+
+hipError_t launch_math_probe(int op, const double *in, uint64_t n, double *out, hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    BHG_LAUNCH(math_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, op, in, n, out);
+    return hipGetLastError();
+}
 
 // instructions per loop iteration of each probe: {VALU total, of which quarter-rate}
 void probe_shape(int kind, uint32_t *valu_per_iter, uint32_t *quarter_per_iter)

@@ -804,6 +804,28 @@ int bhg_last_launch(bhg_context *ctx, int32_t out[4]);
 #define BHG_PROBE_STEP_MIX 1
 int bhg_peak_probe(bhg_context *ctx, int32_t kind, double target_ms, double out[6]);
 
+/* A TEST HOOK, not part of the rendering surface (additive: the ABI number stays 10): n elements, one per thread, through ONE of
+ * the hand-written fp64 primitives of the kernels (csrc/device_math.h, csrc/kerr_start.h), compiled with the flags of the
+ * units that use them, so that a test can compare each with a high-precision reference ulp by ulp.
+ * in and out are HOST buffers; per element, in -> out:
+ *   BHG_MATH_RCP_NEWTON       x -> 1 / x                        BHG_MATH_RCP_NR   x -> 1 / x
+ *   BHG_MATH_RSQRT_NR         x -> 1 / sqrt(x)                  BHG_MATH_SQRT_NR  x -> sqrt(x)  (0 for x <= 0)
+ *   BHG_MATH_ATAN2_FAST       (y, x) -> atan2(y, x)             BHG_MATH_SINCOS_PI4  x -> (sin x, cos x)
+ *   BHG_MATH_RCP3_NR          (x0, x1, x2) -> (1/x0, 1/x1, 1/x2)
+ *   BHG_MATH_KERR_CART_TO_BL  (a, M, mu2, x[3], k[3]) -> (r, theta, phi, dr, dtheta, dphi, E, L)
+ * An unknown op and a NULL buffer with n > 0 are refused (BHG_E_INVALID, bhg_last_error); n = 0 is a no-op; at most 2^26
+ * elements per call.  Blocking; runs on the context's own stream. */
+#define BHG_MATH_PROBE 1
+#define BHG_MATH_RCP_NEWTON 0
+#define BHG_MATH_RCP_NR 1
+#define BHG_MATH_RSQRT_NR 2
+#define BHG_MATH_SQRT_NR 3
+#define BHG_MATH_ATAN2_FAST 4
+#define BHG_MATH_SINCOS_PI4 5
+#define BHG_MATH_RCP3_NR 6
+#define BHG_MATH_KERR_CART_TO_BL 7
+int bhg_math_probe(bhg_context *ctx, int32_t op, const double *in, size_t n, double *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,10 +53,43 @@ def flux_hat(x, K):
     x = np.asarray(x, float)
     x0, a = K["x0"], K["astar"]
     x2 = x * x
+    d = x - x0
+    b = d - (1.5 * a) * np.log1p(d / x0)
+    for i in range(3):
+        b = b - K["c"][i] * np.log1p(d / (x0 - K["xr"][i]))
+    return b / ((x2 * x2) * ((x2 * x - 3.0 * x) + 2.0 * a))
+
+
+def flux_hat_parent(x, K):
+    """F^(x) as the library formed it before the log1p form: each logarithm of a rounded quotient.  Kept so that the inner-edge
+    ladder test can show what it is there to catch."""
+    x = np.asarray(x, float)
+    x0, a = K["x0"], K["astar"]
+    x2 = x * x
     b = (x - x0) - (1.5 * a) * np.log(x / x0)
     for i in range(3):
         b = b - K["c"][i] * np.log((x - K["xr"][i]) / (x0 - K["xr"][i]))
     return b / ((x2 * x2) * ((x2 * x - 3.0 * x) + 2.0 * a))
+
+
+def flux_hat_mp(x, K, bits=300):
+    """F^(x) of ONE double x in mpmath at `bits` bits, from the same double constants x0, x_i, c_i, a* that the library holds (they
+    are inputs of the operation, not part of its error).  Returns an mpf."""
+    import mpmath as mp
+    with mp.workprec(bits):
+        x, x0, a = mp.mpf(float(x)), mp.mpf(K["x0"]), mp.mpf(K["astar"])
+        b = (x - x0) - mp.mpf(1.5) * a * mp.log(x / x0)
+        for i in range(3):
+            xi = mp.mpf(float(K["xr"][i]))
+            b -= mp.mpf(float(K["c"][i])) * mp.log((x - xi) / (x0 - xi))
+        return +(b / (x ** 4 * (x ** 3 - 3 * x + 2 * a)))
+
+
+def tau_mp(x, K, fmax, bits=300):
+    """tau = (F^ / max F^)^(1/4) in mpmath from flux_hat_mp (fmax a double: the normalisation is an input too); an mpf."""
+    import mpmath as mp
+    with mp.workprec(bits):
+        return +mp.root(flux_hat_mp(x, K, bits) / mp.mpf(fmax), 4)
 
 
 def schwarzschild_flux_hat(x):

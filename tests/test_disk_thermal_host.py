@@ -47,6 +47,49 @@ def test_flux_shape_matches_the_page_thorne_integral(astar):
     assert abs((dt.flux_hat(np.sqrt(r_peak), K) / fmax) ** 0.25 - 1.0) <= 1e-9
 
 
+LADDER_E = tuple(10.0 ** -k for k in range(2, 13))     # r = r_ms (1 + e)
+
+
+def _ladder(astar, flux):
+    """Per rung e: (e, |tau - tau_mp|, relative flux error, sign of F^) of `flux` against mpmath at the same double x."""
+    K = dt.constants(astar)
+    fmax, _ = dt.flux_max(K)
+    rows = []
+    for e in LADDER_E:
+        x = float(np.sqrt(K["r_ms"] * (1.0 + e)))
+        assert x > K["x0"]
+        F = float(flux(np.array([x]), K)[0])
+        F_mp = dt.flux_hat_mp(x, K)
+        t_mp = dt.tau_mp(x, K, fmax)
+        tau = np.sqrt(np.sqrt(max(F, 0.0) * (1.0 / fmax)))
+        rows.append((e, abs(float(tau - t_mp)), abs(float((F - F_mp) / F_mp)), F))
+    return rows
+
+
+@pytest.mark.parametrize("astar", [-0.998, -0.9, 0.0, 0.45, 0.9, 0.998])
+def test_flux_next_to_the_inner_edge_against_mpmath(astar, record_property):
+    """The ladder r = r_ms (1 + e), e = 1e-2 ... 1e-12: flux_hat (the library's order of operations) against the closed form in
+    mpmath at 300 bits from the same double constants and the same double x = sqrt(r).  |tau - tau_mp| <= 1e-9 on the whole
+    ladder, the relative flux error <= 1e-8 for e >= 1e-7, and F^ > 0 on every rung."""
+    rows = _ladder(astar, dt.flux_hat)
+    record_property("max_tau_error", max(r[1] for r in rows))
+    record_property("max_rel_flux_error_e_ge_1e-7", max(r[2] for r in rows if r[0] >= 0.99e-7))
+    for e, dtau, rel, F in rows:
+        print(f"a* = {astar:+.3f}  e = {e:.0e}  |dtau| = {dtau:.3e}  rel F = {rel:.3e}  F = {F:.3e}")
+    for e, dtau, rel, F in rows:
+        assert F > 0.0, (astar, e, F)
+        assert dtau <= 1e-9, (astar, e, dtau)
+        if e >= 0.99e-7:
+            assert rel <= 1e-8, (astar, e, rel)
+
+
+def test_the_ladder_catches_the_logarithm_of_a_rounded_quotient():
+    """The form the library had -- log(x / x0), log((x - x_i) / (x0 - x_i)) -- misses the ladder's bounds: the test above can fail."""
+    rows = _ladder(0.0, dt.flux_hat_parent) + _ladder(0.9, dt.flux_hat_parent)
+    assert max(r[1] for r in rows) > 1e-9
+    assert max(r[2] for r in rows if r[0] >= 0.99e-7) > 1e-8
+
+
 def test_schwarzschild_closed_form_and_peak():
     K = dt.constants(0.0)
     assert list(K["xr"]) == [np.sqrt(3.0), 0.0, -np.sqrt(3.0)] and K["c"][1] == 0.0 and K["r_ms"] == 6.0

@@ -400,3 +400,65 @@ def test_frame_batch_adaptor(ctx):
         one.set_disk(3.0, 9.0)
         one.set_disk_thermal(_th(1))
         assert torch.equal(one.render(p), img)
+
+
+# ---- next to the inner edge ------------------------------------------------------------------------------------------------
+LADDER_E = tuple(10.0 ** -k for k in range(2, 13))
+
+
+def _edge_records(r, a, cam):
+    """Hand-made disk hits at BL radii r (the record's R = sqrt(r^2 + a^2)), on two azimuths: (k0, end, flags)."""
+    R = np.sqrt(r * r + a * a)
+    end = np.zeros((2 * len(r), 6))
+    end[:len(r), 0] = R                        # azimuth 0: the record's radius is R itself
+    end[len(r):, 0], end[len(r):, 1] = R * np.cos(0.7), R * np.sin(0.7)
+    k0 = end[:, :3] - cam
+    k0 /= np.linalg.norm(k0, axis=1, keepdims=True)
+    end[:, 3:6] = k0
+    return k0, end, np.full(len(end), 128, np.uint8)
+
+
+@pytest.mark.parametrize("rhs,spin,sense", [(0, 0.0, 1), (2, 0.45, 1), (2, 0.45, -1)], ids=["schw", "kerr_retro", "kerr_pro"])
+def test_inner_edge_ladder_against_mpmath(ctx, record_property, rhs, spin, sense):
+    """Hand-made end records at r = r_ms (1 + e), e = 1e-2 ... 1e-12, through bhg_disk_thermal_host: t_em / t_peak against tau in
+    mpmath FROM THE RECORD (r = sqrt(R^2 - a^2), x = sqrt(r / M) at 300 bits), so the device's rounding of r and x is part of its
+    error: tau goes like sqrt(x - x0), so d tau = tau eps x0 / (2 (x - x0)), about 6e-11 at e = 1e-10 for a = 0 and a few times
+    that for Kerr.  Hence |tau - tau_mp| <= 1e-9 for e >= 1e-10; below, only 0 <= t_em <= t_em(1e-10) and finite.  At r = r_ms (1 -
+    e) everything is an exact zero, and nothing anywhere is negative or NaN.  (Not at the edge itself: the library's r_ms and the
+    record's sqrt(R^2 - a^2) each carry a rounding of their own.)"""
+    import mpmath as mp
+    f = _ffi()
+    r_s = 1.0
+    M, a, astar, K, fmax = dt.family(r_s, spin, rhs == 2, sense)
+    p = f.make_params(r_s=r_s, rhs_form=rhs, spin=spin)
+    th = _th(sense)
+    e = np.array(LADDER_E)
+    k0, end, flags = _edge_records(K["r_ms"] * M * (1.0 + e), a, CAM)
+    t, rgb = ctx.disk_thermal(k0, CAM, p, th, None, flags, end)
+    assert np.all(np.isfinite(t)) and np.all(np.isfinite(rgb)) and np.all(t >= 0.0) and np.all(rgb >= 0.0)
+    worst = 0.0
+    for i in range(len(end)):
+        ei = LADDER_E[i % len(e)]
+        with mp.workprec(300):
+            r = mp.sqrt(mp.mpf(end[i, 0]) ** 2 + mp.mpf(end[i, 1]) ** 2 - mp.mpf(a) ** 2)
+            x = mp.sqrt(r / mp.mpf(M))
+            x0, am = mp.mpf(K["x0"]), mp.mpf(K["astar"])
+            b = (x - x0) - mp.mpf(1.5) * am * mp.log(x / x0)
+            for j in range(3):
+                xj = mp.mpf(float(K["xr"][j]))
+                b -= mp.mpf(float(K["c"][j])) * mp.log((x - xj) / (x0 - xj))
+            F = b / (x ** 4 * (x ** 3 - 3 * x + 2 * am))
+            tau = mp.root(F / mp.mpf(fmax), 4) if F > 0 else mp.mpf(0)
+            d = abs(float(mp.mpf(t[i]) / mp.mpf(T_PEAK) - tau))
+        print(f"a* = {astar:+.2f}  e = {ei:.0e}  tau = {float(tau):.6e}  |t_em / t_peak - tau_mp| = {d:.3e}")
+        if ei >= 0.99e-10:
+            worst = max(worst, d)
+            assert d <= 1e-9, (astar, ei, d)
+            assert t[i] > 0.0 and np.all(rgb[i] >= 0.0)
+        else:
+            assert 0.0 <= t[i] <= t[(i // len(e)) * len(e) + 8], (astar, ei, t[i])     # (rung 8 is e = 1e-10)
+    record_property("max_tau_error_e_ge_1e-10", worst)
+    # inside: exact zeros
+    k0, end, flags = _edge_records(K["r_ms"] * M * (1.0 - e), a, CAM)
+    t, rgb = ctx.disk_thermal(k0, CAM, p, th, None, flags, end)
+    assert np.all(t == 0.0) and np.all(rgb == 0.0)

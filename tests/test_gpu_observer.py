@@ -414,3 +414,72 @@ def test_frame_observer_refusals(ctx):
     with pytest.raises(f.BhgError, match="horizon"):
         fr.render(f.make_params(r_s=1.0, lambda_end=40.0))
     fr.close()
+
+
+# ---- the observer raygen's grid-stride walk ----------------------------------------------------------------------------------
+CAP = 2048 * 256        # rays one trip of the observer instance covers: at most 2048 workgroups of 256
+
+
+def _observer_launch(ctx, p, obs, x0, W, H, S, fov, jit, pixels, rot):
+    """bhg_raygen_observer_device into a NaN-filled buffer (a ray the walk skipped stays NaN; one computed twice would only write
+    the same bits again): (reference k0, observer k0), host arrays."""
+    import torch
+    P = W * H if pixels is None else len(pixels)
+    d_px = None if pixels is None else torch.as_tensor(np.asarray(pixels, np.int64)).cuda()
+    ref = torch.full((S * P, 3), float("nan"), dtype=torch.float64, device="cuda")
+    out = torch.full((S * P, 3), float("nan"), dtype=torch.float64, device="cuda")
+    kw = dict(d_pixels=0 if d_px is None else d_px.data_ptr(), rot=rot, stream=_stream())
+    ctx.raygen_device(W, H, S, fov, fov, jit.data_ptr(), ref.data_ptr(), P, **kw)
+    ctx.raygen_observer_device(p, obs, x0, W, H, S, fov, fov, jit.data_ptr(), out.data_ptr(), P, **kw)
+    torch.cuda.synchronize()
+    return ref.cpu().numpy(), out.cpu().numpy()
+
+
+WALK_CASES = [
+    # name, rhs, spin, camera, beta, W, H, S, listed pixels (None = the whole frame), rotated
+    ("cap_exactly_schw", 0, 0.0, np.array([3.0, -4.0, 9.0]), [0.3, -0.5, 0.6], 1024, 512, 1, None, False),
+    ("cap_plus_one_row_kerr", 2, 0.9, np.array([8.0, 5.0, 3.0]), [0.2, 0.55, -0.4], 1024, 513, 1, None, False),
+    ("cap_plus_one_ray_schw", 0, 0.0, np.array([3.0, -4.0, 9.0]), [0.3, -0.5, 0.6], 1024, 1024, 1, CAP + 1, False),
+    ("three_trips_and_a_tail_kerr", 2, 0.9, np.array([8.0, 5.0, 3.0]), [0.2, 0.55, -0.4], 1024, 1024, 3, CAP + 4321, True),
+    ("three_trips_and_a_tail_schw", 1, 0.0, np.array([-6.0, 2.0, 4.0]), [-0.7, 0.1, 0.2], 1024, 1024, 3, CAP + 77, False),
+]
+
+
+@pytest.mark.parametrize("case", WALK_CASES, ids=[c[0] for c in WALK_CASES])
+def test_observer_raygen_walks_every_ray_once(ctx, case):
+    """The observer instance walks the rays grid-stride with at most 2048 workgroups of 256: N = 524 288 exactly (the cap, one
+    trip), just above it, and more than three trips with a ragged tail.  No ray is left out (the output starts as NaN); every ray
+    equals, bit for bit, the same ray from launches of fewer than 2048 workgroups each (pixel subsets: the non-compact jitter
+    stream indexes the same draws); and the restatement holds at the existing 1e-12 on the rays around every trip boundary, the
+    first and last rays and 2000 seeded ones (the restatement is a Python loop per ray)."""
+    import torch
+    f = _ffi()
+    name, rhs, spin, x0, beta, W, H, S, listed, rotated = case
+    p = f.make_params(r_s=2.0, rhs_form=rhs, spin=spin)
+    obs = f.make_observer(beta)
+    rot = np.array([[0.8, 0.0, 0.6], [0.0, 1.0, 0.0], [-0.6, 0.0, 0.8]]) if rotated else None
+    rng = np.random.default_rng(7)
+    jit = torch.as_tensor(rng.random(2 * S * W * H)).cuda()
+    pixels = None if listed is None else rng.permutation(W * H)[:listed]
+    P = W * H if pixels is None else len(pixels)
+    N = S * P
+    assert N >= CAP and (name.startswith("cap_exactly") == (N == CAP))
+    ref, k0 = _observer_launch(ctx, p, obs, x0, W, H, S, 0.9, jit, pixels, rot)
+    assert not np.any(np.isnan(k0)) and not np.any(np.isnan(ref))
+    # the same rays from launches of fewer than 2048 workgroups
+    ids = np.arange(W * H) if pixels is None else pixels
+    chunk = (2047 * 256) // S
+    parts = []
+    for lo in range(0, P, chunk):
+        sub = ids[lo:lo + chunk]
+        assert (S * len(sub) + 255) // 256 < 2048
+        parts.append(_observer_launch(ctx, p, obs, x0, W, H, S, 0.9, jit, sub, rot)[1].reshape(S, len(sub), 3))
+    small = np.concatenate(parts, 1).reshape(N, 3)
+    assert np.array_equal(k0, small)
+    # the restatement on the rays that matter
+    edge = np.concatenate([np.arange(t * CAP - 3, t * CAP + 3) for t in range(1, N // CAP + 1)] + [[0, 1, N - 2, N - 1]])
+    pick = np.unique(np.concatenate([edge[(edge >= 0) & (edge < N)], rng.integers(0, N, 2000)]))
+    want = orf.observer_k0_rays(x0, ref[pick], beta, 2.0, spin, rhs == 2)
+    err = np.abs(k0[pick] - want).max()
+    assert err <= 1e-12, err
+    assert np.abs(np.linalg.norm(k0, axis=1) - 1.0).max() <= 1e-15 * 4

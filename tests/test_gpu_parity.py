@@ -17,6 +17,8 @@ Stated tolerances (fp64):
     any 1e-16 noise exponentially, and S_i is exactly that amplification.  Median <= 1e-11.
 """
 import math
+import os
+import sys
 
 import numpy as np
 import pytest
@@ -1575,3 +1577,151 @@ def test_resident_rays_of_an_empty_pixel_list(ctx):
     out = rs.trace(_params(r_s=1.0, lambda_end=50.0), want=("end_dir", "flags"))
     assert out["end_dir"].shape == (0, 3) and out["flags"].shape == (0,)
     rs.close()
+
+
+# ---- the feature calls' host forms on empty and ragged sizes ---------------------------------------------------------------
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))      # the *_reference modules next to this file
+FEATURE_SIZES = (0, 1, 63, 64, 65, 257, (1 << 20) + 1)
+FEATURE_BIG = (1 << 20) + 65
+FEATURE_CAM = np.array([30 * np.sin(np.radians(75.0)), 0.0, 30 * np.cos(np.radians(75.0))])
+FEATURE_SPHERES = np.array([[6.0, 3.0, 2.5, 1.5], [7.0, -4.0, 3.0, 1.0], [2.0, 6.0, -1.0, 1.2]])
+FEATURE_BETA = (0.3, -0.2, 0.1)
+FEATURE_V = np.array([[0.1, 0.2, -0.05], [0.0, 0.0, 0.0], [-0.2, 0.05, 0.1]])
+FEATURE_W = np.array([[0.0, 0.0, 0.05], [0.0, 0.0, 0.0], [0.02, -0.01, 0.0]])
+FEATURE_TABLE = (0.0, 0.35, 0.2, 0.117)
+FEATURE_UP = (0.1, 1.0, 0.2)
+FEATURE_NU = (3.0e14, 6.0e14, 1.0e15, 1.5e15)
+FEATURE_WEIGHTS = np.array([[1.0, 0.5, 0.1, 0.0], [0.2, 1.0, 0.4, 0.1], [0.0, 0.1, 0.6, 1.0]])
+
+
+@pytest.fixture(scope="module")
+def feature_rays(ctx):
+    """2^20 + 65 traced rays of a Schwarzschild scene with a disk and three spheres, once from a shared camera and once from
+    per-ray cameras, some rays relabelled so that every class is among the first 64: {shared: (x0, k0, end, flags, obj)}."""
+    n = FEATURE_BIG
+    k = frame_rays(n, seed=91, fov=0.7)
+    inc = np.radians(75.0)
+    c, s = np.cos(inc), np.sin(inc)
+    k0 = np.ascontiguousarray(k @ np.array([[c, 0, s], [0, 1, 0], [-s, 0, c]]).T)
+    p = _params(r_s=1.0, lambda_end=80.0, r_exit=40.0, disk_r_in=3.0, disk_r_out=9.0)
+    out = {}
+    for shared in (True, False):
+        x0 = FEATURE_CAM if shared else np.tile(FEATURE_CAM, (n, 1)) * np.linspace(0.8, 1.2, n)[:, None]
+        end, flags, _, _, obj = ctx.trace(k0, x0, p, spheres=FEATURE_SPHERES)
+        flags = flags.copy()
+        flags[5::16] = np.resize(np.array([1, 3, 64, 65, 4, 16], np.uint8), len(flags[5::16]))
+        out[shared] = (x0, k0, np.array(end), flags, np.array(obj))
+        first = flags[:257]
+        assert (first == 128).sum() > 5 and (first == 0x88).sum() > 0 and (first == 8).sum() > 5, np.unique(first, return_counts=True)
+    return p, out
+
+
+def _feature_calls(ctx, p):
+    """name -> (call(x0, k0, end, flags, obj) -> tuple of arrays, the C call's number of output arrays)."""
+    from blackhole_geodesic_calculator_amd import _ffi as f
+    rs = f.make_redshift(disk_sense=1)
+    obs = f.make_observer(FEATURE_BETA)
+    mo = f.make_object_motion(FEATURE_V, FEATURE_W)
+    pol = f.make_polarisation(FEATURE_TABLE, 1, FEATURE_UP)
+    th = f.make_disk_thermal(1.2e4, FEATURE_NU, FEATURE_WEIGHTS, 1.7, 2.5, 1)
+    return {
+        "redshift": lambda x0, k0, end, fl, obj: (ctx.redshift(k0, x0, p, rs, fl, end),),
+        "redshift_observer": lambda x0, k0, end, fl, obj: (ctx.redshift_observer(k0, x0, p, rs, obs, fl, end),),
+        "redshift_motion": lambda x0, k0, end, fl, obj: (ctx.redshift_motion(k0, x0, p, rs, obs, mo, FEATURE_SPHERES, fl, end, obj),),
+        "polarisation": lambda x0, k0, end, fl, obj: ctx.polarisation(k0, x0, p, pol, obs, fl, end),
+        "disk_thermal": lambda x0, k0, end, fl, obj: ctx.disk_thermal(k0, x0, p, th, obs, fl, end),
+    }
+
+
+def _feature_restatement(name, x0, k0, end, fl, obj, got, ctx, p):
+    """The numpy restatement of one feature call at the tolerance its own GPU test uses."""
+    import disk_thermal_reference as dt
+    import object_motion_reference as om
+    import polarisation_reference as pr
+    import redshift_reference as rr
+    from blackhole_geodesic_calculator_amd import _ffi as f
+
+    def rel(g, want):
+        assert np.array_equal(np.isnan(g), np.isnan(want))
+        z = want == 0.0
+        assert np.all(g[z] == 0.0)
+        ok = ~np.isnan(want) & ~z
+        assert np.abs(g[ok] / want[ok] - 1.0).max(initial=0.0) <= 1e-12
+    zero3 = np.zeros((3, 3))
+    if name == "redshift":
+        rel(got[0], rr.g_rays(x0, k0, end, fl, 1.0, 0.0, False, 1))
+    elif name == "redshift_observer":
+        rel(got[0], om.g_rays_motion(x0, k0, end, fl, obj, FEATURE_SPHERES, zero3, zero3, 1.0, 0.0, False, 1, FEATURE_BETA))
+    elif name == "redshift_motion":
+        rel(got[0], om.g_rays_motion(x0, k0, end, fl, obj, FEATURE_SPHERES, FEATURE_V, FEATURE_W, 1.0, 0.0, False, 1, FEATURE_BETA))
+    elif name == "polarisation":
+        wc, wd, wm = pr.pol_rays(x0, k0, end, fl, 1.0, 0.0, False, 1, FEATURE_TABLE, FEATURE_UP, FEATURE_BETA)
+        chi, deg, mu = got
+        zero = (wd == 0.0) & (wm == 0.0) & (wc == 0.0)
+        nan = np.isnan(wd)
+        for a in got:
+            assert np.all(a[zero] == 0.0) and np.all(np.isnan(a[nan]))
+        d = ~zero & ~nan
+        assert np.array_equal(np.isnan(chi[d]), np.isnan(wc[d]))
+        ok = d & ~np.isnan(wc)
+        assert pr.chi_diff(chi[ok], wc[ok]).max(initial=0.0) <= 1e-10
+        assert np.abs(deg[d] - wd[d]).max(initial=0.0) <= 1e-12 and np.abs(mu[d] - wm[d]).max(initial=0.0) <= 1e-12
+    else:
+        g = ctx.redshift_observer(k0, x0, p, f.make_redshift(disk_sense=1), f.make_observer(FEATURE_BETA), fl, end)
+        wt, wrgb = dt.thermal_rays(end, fl, g, 1.0, 0.0, False, 1, 1.2e4, FEATURE_NU, FEATURE_WEIGHTS, 1.7, 2.5)
+        for a, b in ((got[0], wt), (got[1][:, 0], wrgb[:, 0]), (got[1][:, 1], wrgb[:, 1]), (got[1][:, 2], wrgb[:, 2])):
+            assert np.array_equal(np.isnan(a), np.isnan(b))
+            z = b == 0.0
+            assert np.all(a[z] == 0.0)
+            ok = ~np.isnan(b) & ~z
+            if ok.any():
+                scale = np.abs(b[ok]).max()
+                assert np.all(np.abs(a[ok] - b[ok]) <= 1e-12 * np.maximum(np.abs(b[ok]), scale))
+
+
+@pytest.mark.parametrize("name", ["redshift", "redshift_observer", "redshift_motion", "polarisation", "disk_thermal"])
+def test_feature_host_calls_on_empty_and_ragged_sizes(ctx, feature_rays, name):
+    """bhg_redshift_host, bhg_redshift_observer_host, bhg_redshift_motion_host, bhg_polarisation_host and bhg_disk_thermal_host
+    pack five to seven arrays into one device block by hand.  n = 0 is a no-op; every n in {1, 63, 64, 65, 257, 2^20 + 1} gives,
+    bit for bit, the first n elements of one larger call (the functions are per ray), with a shared and with per-ray x0, with
+    and without end records; n <= 257 also against the numpy restatements at the tolerances their own tests use."""
+    p, rays = feature_rays
+    call = _feature_calls(ctx, p)[name]
+    for shared in (True, False):
+        x0, k0, end, flags, obj = rays[shared]
+        for with_end in (True, False):
+            big = call(x0, k0, end if with_end else None, flags, obj)
+            assert all(len(b) == FEATURE_BIG for b in big)
+            for n in FEATURE_SIZES:
+                xs = x0 if shared else x0[:n]
+                got = call(xs, k0[:n], end[:n] if with_end else None, flags[:n], obj[:n])
+                assert len(got) == len(big)
+                for a, b in zip(got, big):
+                    assert a.shape == b[:n].shape and np.array_equal(a, b[:n], equal_nan=True), (name, shared, with_end, n)
+                if with_end and 0 < n <= 257:
+                    _feature_restatement(name, xs, k0[:n], end[:n], flags[:n], obj[:n], got, ctx, p)
+
+
+def test_feature_host_calls_with_no_rays_touch_nothing(ctx):
+    """n = 0 through the C calls themselves: success, and output buffers that hold a sentinel still hold it."""
+    import ctypes as C
+    from blackhole_geodesic_calculator_amd import _ffi as f
+    L = f.load()
+    p = _params(r_s=1.0)
+    rs, obs = f.make_redshift(disk_sense=1), f.make_observer(FEATURE_BETA)
+    mo = f.make_object_motion(FEATURE_V, FEATURE_W)
+    pol = f.make_polarisation(FEATURE_TABLE, 1, FEATURE_UP)
+    th = f.make_disk_thermal(1.2e4, FEATURE_NU, FEATURE_WEIGHTS, 1.7, 2.5, 1)
+    x0 = (C.c_double * 3)(*FEATURE_CAM)
+    k0, end = (C.c_double * 3)(0.0, 0.0, -1.0), (C.c_double * 6)()
+    fl, oid = (C.c_uint8 * 1)(128), (C.c_int8 * 1)(0)
+    sph = np.ascontiguousarray(FEATURE_SPHERES)
+    outs = [(C.c_double * 3)(-7.0, -7.0, -7.0) for _ in range(3)]
+    h, P = ctx._h, C.byref(p)
+    assert L.bhg_redshift_host(h, P, C.byref(rs), x0, 1, k0, end, fl, 0, outs[0]) == f.OK
+    assert L.bhg_redshift_observer_host(h, P, C.byref(rs), C.byref(obs), x0, 1, k0, end, fl, 0, outs[0]) == f.OK
+    assert L.bhg_redshift_motion_host(h, P, C.byref(rs), C.byref(obs), C.byref(mo), sph.ctypes.data_as(C.c_void_p), 3, x0, 1, k0, end,
+                                      fl, oid, 0, outs[0]) == f.OK
+    assert L.bhg_polarisation_host(h, P, C.byref(pol), C.byref(obs), x0, 1, k0, end, fl, 0, outs[0], outs[1], outs[2]) == f.OK
+    assert L.bhg_disk_thermal_host(h, P, C.byref(th), C.byref(obs), x0, 1, k0, end, fl, 0, outs[0], outs[1]) == f.OK
+    assert all(list(o) == [-7.0, -7.0, -7.0] for o in outs)

@@ -68,7 +68,7 @@ def test_kerr_at_zero_spin_is_schwarzschild():
             assert np.max(np.abs(a - b)) <= 1e-14
 
 
-def _numpy_kerr_cart_to_bl(x, k, a):
+def _numpy_kerr_cart_to_bl(x, k, a, mu2=0.0):
     """kerr_cart_to_bl (csrc/kerr_start.h) restated: BL position and velocity in closed form, E, L from the null condition."""
     r_ = np.sqrt(0.5 * ((x @ x - a * a) + np.sqrt((x @ x - a * a) ** 2 + 4 * a * a * x[2] ** 2)))
     c = x[2] / r_
@@ -82,7 +82,7 @@ def _numpy_kerr_cart_to_bl(x, k, a):
     u = np.array([(r_ * st * krho + R * ct * k[2]) * R / D, (R * ct * krho - r_ * st * k[2]) / D,
                   (cp * k[1] - sp * k[0]) / (R * st)])
     gtt, gtp, grr, gthth, gpp = rr.kerr_metric(r_, th, M, a)
-    S = grr * u[0] ** 2 + gthth * u[1] ** 2 + gpp * u[2] ** 2
+    S = grr * u[0] ** 2 + gthth * u[1] ** 2 + gpp * u[2] ** 2 + mu2
     B = gtp * u[2]
     kt = (-B - np.sqrt(B * B - gtt * S)) / gtt
     return -(gtt * kt + gtp * u[2]), gtp * kt + gpp * u[2]
