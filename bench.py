@@ -10,6 +10,14 @@ per-pixel RGBA to rank 0 (asynchronous, overlapping the next frame's trace).  Th
 (exit position and direction, 48 B/ray: what spacetime_ray_cast returns, :307-308 -- the headline since round 5);
 --dir-only gives the sky frame's form (exit directions only), reported beside the headline as sky_frame_dir_only.
 
+A PLAIN run (no --full) does what the headline needs and nothing else: set-up, clock ramp, warm-up, the timed region, the
+outputs of --dump-outputs, the JSON line -- with the roofline figures that the timed region's own HIP events give for free
+(kernel_ms is then the trace CALL's time; traffic from the committed profiles/ summary).  Everything that takes runs of its
+own -- the live counter passes, the calibration probes and the sampled repetition, the trace kernel's share of a call
+(--lean, the profiling form, keeps that one: it launches exactly what it always did), the check of the assembled frame, sky_frame_dir_only / full_records, regimes, strong_predicted, pipelined, host_buffer_call,
+cpu_baseline and, N > 1, the strong / frames_sharded regions -- is behind --full, where it runs as it always has.  What is said
+below about those figures is said of a --full run.
+
 The timed region -- EXACTLY --steps steps between barrier + synchronise -- is run --reps times (default 5); the headline is the
 MEDIAN repetition, every repetition is in the line (ms_per_step_samples) and so is every HIP-event sample of the trace kernel
 (roofline.kernel_ms_samples).  Nothing runs on the host between a repetition's barrier and its clock (round 5 built its clock
@@ -33,7 +41,7 @@ drives --gpus N devices, no torch.distributed, no PyTorch in the timed path -- w
 
 roofline.traffic and roofline.valu_insts_per_64_ray_steps are measured in the run itself on one GPU: before this process
 touches the GPU it starts three rocprofv3 --pmc child runs of the same command (FETCH_SIZE, WRITE_SIZE, SQ_INSTS_VALU in
-separate passes, 3 steps each; live_pmc()); if that fails (or with --live-pmc 0, --lean, --cpu-seconds 0, N > 1) the line
+separate passes, 3 steps each; live_pmc()); if that fails (or without --full, with --live-pmc 0, --lean, --cpu-seconds 0, N > 1) the line
 carries the committed profiles/rNN_pmc_summary*.json instead -- roofline.traffic_source says which, and why.
 
 --dump-outputs DIR: after the timed steps, what the timed path computed in its LAST step -- each frame's float RGBA image and
@@ -75,6 +83,12 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline, each in runs of its own after (the counter passes: "
+                         "before) the timed region: live rocprofv3 counter passes, calibration probes and the sampled repetition, the "
+                         "trace kernel's share of a call, the assembled-frame check, the other output form, the other step regimes, "
+                         "strong_predicted, pipelined, host_buffer_call, cpu_baseline, and at N > 1 the strong / frames_sharded regions.  "
+                         "Off by default: a plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line")
     ap.add_argument("--reps", type=int, default=5,
                     help="the headline's timed region -- EXACTLY --steps steps between barrier + synchronise -- is run this many times "
                          "back to back; every repetition's ms per step goes into the line (ms_per_step_samples), the headline is "
@@ -82,7 +96,7 @@ def parse(argv=None):
                          "1 = the single region of rounds 1-5")
     ap.add_argument("--probe-when", choices=["after_only", "before_warmup", "before_timed", "off"],
                     default=os.environ.get("BHGEO_PROBE_WHEN", "after_only"),
-                    help="where the roofline calibration probes (bhg_peak_probe, power-bound pure-FMA launches, 25 ms) run relative to "
+                    help="--full: where the roofline calibration probes (bhg_peak_probe, power-bound pure-FMA launches, 25 ms) run relative to "
                          "the headline's timed region: after_only (default since round 6: nothing power-hungry in front of a short "
                          "region), before_warmup (round 5: in front of the W warm-up steps, and again afterwards), before_timed, off")
     ap.add_argument("--clock-reads", type=int, default=int(os.environ.get("BHGEO_CLOCK_READS", "1")),
@@ -121,19 +135,20 @@ def parse(argv=None):
     ap.add_argument("--order", choices=["measured", "model", "none"], default="model",
                     help="tile order / dealing: by the attempted steps of one untimed calibration trace of the same frame "
                          "(dist.measured_tile_cost), by the shadow-edge model (plain frame only), or row-major")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline wall time (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: target CPU-baseline wall time (0 = skip)")
     ap.add_argument("--emulate-shards", type=str, default="2,4,8",
-                    help="N = 1, frame workload: also time rank 0's part of a world-N dealing of the SAME fixed frame -- its shard "
+                    help="--full, N = 1, frame workload: also time rank 0's part of a world-N dealing of the SAME fixed frame -- its shard "
                          "traced and shaded into the gather slab, a 1-rank RCCL gather of that slab, the root's assembly of the "
                          "N-rank frame -- for each N listed and report the predicted strong-scaling efficiency T1 / (N T_N) in "
                          "a strong_predicted block; '' = off")
     ap.add_argument("--live-pmc", type=int, default=1,
-                    help="1 (default, single GPU, not --lean): measure roofline.traffic and the VALU instruction count NOW, with "
+                    help="1 (default; --full, single GPU, not --lean): measure roofline.traffic and the VALU instruction count NOW, with "
                          "three rocprofv3 --pmc child runs of this same command (3 steps each) started before this process "
                          "touches the GPU; on any failure -- or 0 -- the line replays the committed profiles/ summary")
     ap.add_argument("--lean", action="store_true",
-                    help="profiling runs: the headline's timed region and nothing after it (no full_records, shard emulation, "
-                         "pipelined / host-buffer figures, CPU baseline), so that a profiler's per-kernel averages are the headline's")
+                    help="profiling runs, unchanged by --full and overriding it: the headline's timed region without the reads of the "
+                         "shader clock, then the 8 profiled calls that give the trace kernel's share of a call, and nothing else -- so "
+                         "that a profiler's per-kernel averages are the headline's")
     ap.add_argument("--single-process", action="store_true",
                     help="ONE process drives --gpus N devices through the library-owned frame (bhg_frame_*: tile dealing, per-device "
                          "contexts, one gather onto device 0 -- RCCL single-process mode when the devices are distinct); no "
@@ -156,7 +171,7 @@ def parse(argv=None):
                          "float64, <= 64 MB: a fixed, seeded sample of pixels and rays of a larger frame)")
     a = ap.parse_args(argv)
     if a.lean:
-        a.cpu_seconds, a.emulate_shards = 0.0, ""
+        a.cpu_seconds, a.emulate_shards, a.full = 0.0, "", False
     dw, ds = {"frame": (1024, 5), "disk": (1024, 1), "orbit": (2048, 16)}[a.workload]
     a.width = a.width or dw
     a.height = a.height or a.width
@@ -283,6 +298,7 @@ def measure(rt, wl, sky, nx, ny, ramp, overlap=False, whole_frames=False, reps=1
     from blackhole_geodesic_calculator_amd.raygen import python_random_stream
     a, torch, dist, world, rank = wl.a, rt.torch, rt.dist, rt.world, rt.rank
     W, H, S = a.width * nx, a.height * ny, a.samples
+    full = a.full      # (a plain run: nothing below that launches anything of its own beside ramp, warm-up and timed steps)
     # ---- synthetic input, resident in HBM before the timed region ----------------------------
     # this rank's tiles of the frame (all samples of a pixel together); jitter stream = the
     # reference's random.seed(42) MT19937 doubles; rays generated on device once (the engine
@@ -440,7 +456,7 @@ def measure(rt, wl, sky, nx, ny, ramp, overlap=False, whole_frames=False, reps=1
     # roofline calibration (bhg_peak_probe: the fp64 rate THIS box sustains) -- outside the headline's clock.  Since round 6
     # the probes run AFTER the timed region only (--probe-when after_only): they are power-bound pure-FMA launches, and the
     # driver's command times a 28-ms region five warm-up steps behind them (profiles/r06_driver_cmd_ab.log)
-    calibrate = not overlap and not whole_frames and not a.lean and a.probe_when != "off"
+    calibrate = full and not overlap and not whole_frames and not a.lean and a.probe_when != "off"
     calibration = {}
     def probes(when):        # (a probe that fails leaves the line without that part of `calibration`, not without its headline)
         try:
@@ -527,7 +543,7 @@ def measure(rt, wl, sky, nx, ny, ramp, overlap=False, whole_frames=False, reps=1
 
     # the frame really is the frame: rank 0's assembled image against a shade of ITS OWN pixels at their places
     # (outside the timed region; catches a slab / pixel-order mismatch)
-    if rank == 0 and len(frames) == 1 and not whole_frames:
+    if full and rank == 0 and len(frames) == 1 and not whole_frames:
         img = gatherer.image().reshape(-1, 4)
         own = torch.empty((fr.P, 4), dtype=torch.float32, device="cuda")
         fr.shade_f32(own)
@@ -557,17 +573,23 @@ def measure(rt, wl, sky, nx, ny, ramp, overlap=False, whole_frames=False, reps=1
     # carry on inside trace_*_kernel); Kerr adds a prepare and a finalize launch.  A few extra profiled calls
     # after the timed region (HIP events recorded by the library around prepare | trace on this same stream)
     # give the trace kernel's share of the call, applied to the call time measured inside the timed region
-    rt.ctx.set_profiling(True)
-    tr = []
-    for _ in range(8):
-        (batch or fr).trace(wl.params)
-        tr.append(rt.ctx.last_pass_ms())
-    rt.ctx.set_profiling(False)
-    torch.cuda.synchronize()
-    # (Kerr: prepare | trace | finalize; the Schwarzschild forms report 0 for the passes they do not have.  A SHARE of
-    # the profiled calls, not their absolute times: those calls are synchronous, the GPU idles between them)
-    share = float(np.median([t["trace"] / (t["prepare"] + t["trace"] + t["post"]) for t in tr]))
-    k_ms = call_ms * share
+    # (a plain run makes no such calls: share is None and kernel_ms is the call's time -- the same thing for the
+    # Schwarzschild forms, an upper bound of the trace kernel's time for Kerr.  A --lean run keeps them, as it always has:
+    # its line's kernel_ms / frac are what scripts/timed_region_stats.py compares a kernel trace with, and that script
+    # counts on these 8 launches behind the timed ones)
+    share = None
+    if full or a.lean:
+        rt.ctx.set_profiling(True)
+        tr = []
+        for _ in range(8):
+            (batch or fr).trace(wl.params)
+            tr.append(rt.ctx.last_pass_ms())
+        rt.ctx.set_profiling(False)
+        torch.cuda.synchronize()
+        # (Kerr: prepare | trace | finalize; the Schwarzschild forms report 0 for the passes they do not have.  A SHARE of
+        # the profiled calls, not their absolute times: those calls are synchronous, the GPU idles between them)
+        share = float(np.median([t["trace"] / (t["prepare"] + t["trace"] + t["post"]) for t in tr]))
+    k_ms = call_ms * (1.0 if share is None else share)
     frames_mine = len(range(rank, a.steps, world)) if whole_frames else a.steps
     tot = torch.tensor([n * (frames_mine if whole_frames else 1), ray_steps * (frames_mine if whole_frames else 1)], dtype=torch.float64, device="cuda")
     if world > 1:
@@ -650,7 +672,7 @@ def main():
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(a.gpus)     # (before anything touches the GPU)
     live = None
-    if a.live_pmc and not a.lean and a.cpu_seconds > 0 and a.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1:
+    if a.full and a.live_pmc and a.cpu_seconds > 0 and a.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         live = live_pmc(a)      # (child processes; this one has not touched the GPU yet)
     rt = Runtime(a)
     wl = Workload(a)
@@ -665,7 +687,7 @@ def main():
     m["outputs"] = None
     strong = frames_sharded = None
     per_step = lambda r: r["dt"] / a.steps    # noqa: E731  (dt = the median repetition of the region)
-    if world > 1 and a.workload != "orbit":
+    if a.full and world > 1 and a.workload != "orbit":
         # BASELINE.json's metric read as strong scaling: ONE fixed frame of the single-GPU size over all ranks.  The
         # headline of the sharded path has two frames in flight per rank (consecutive frames on alternating streams): a
         # shard's persistent launch ends with a tail of a few tens of microseconds, a quarter of a 1/8 shard's kernel --
@@ -679,7 +701,7 @@ def main():
         except Exception as e:   # noqa: BLE001
             seq = head = None
             strong = {"error": f"{type(e).__name__}: {e}"}
-    if world > 1 and a.workload != "orbit" and strong is None:
+    if a.full and world > 1 and a.workload != "orbit" and strong is None:
         strong = {"value": head["rays_all"] / per_step(head) / 1e6, "unit": "Mrays/s", "ms_per_step": per_step(head) * 1e3,
                   "ray_steps_per_s": head["steps_all"] / per_step(head), "scaling": "strong",
                   "frames_in_flight": 2 if head is not seq else 1,
@@ -689,14 +711,14 @@ def main():
                   "sequential": {"value": seq["rays_all"] / per_step(seq) / 1e6, "unit": "Mrays/s", "ms_per_step": per_step(seq) * 1e3,
                                  "trace_kernel_ms_rank0": seq["k_ms"]}}
         del seq, head
-    if world > 1 and a.workload == "orbit" and a.shard in ("frames", "both"):
+    if a.full and world > 1 and a.workload == "orbit" and a.shard in ("frames", "both"):
         # the 100-frame animation's other sharding: whole frames round-robin over the ranks
         try:
             wf = measure(rt, wl, sky, 1, 1, 0.0, whole_frames=True)
         except Exception as e:   # noqa: BLE001
             wf = None
             frames_sharded = {"error": f"{type(e).__name__}: {e}"}
-    if world > 1 and a.workload == "orbit" and a.shard in ("frames", "both") and frames_sharded is None:
+    if a.full and world > 1 and a.workload == "orbit" and a.shard in ("frames", "both") and frames_sharded is None:
         frames_sharded = {"value": wf["rays_all"] / wf["dt"] / 1e6, "unit": "Mrays/s", "ms_per_frame": wf["dt"] / a.steps * 1e3,
                           "ray_steps_per_s": wf["steps_all"] / wf["dt"], "trace_call_ms": wf["call_ms"],
                           "what": f"the same {a.steps} animation frames dealt round-robin to the {world} ranks as WHOLE frames (rank r renders "
@@ -736,6 +758,8 @@ def main():
             "dtype": "f64",
             "data": "synthetic",
             "config": {
+                "run": "full" if a.full else ("lean (a profiling run: the timed region unobserved + the profiled share calls)" if a.lean else
+                                                 "plain (the headline alone; --full adds what is measured and checked beside it)"),
                 "workload": wl.describe(W, H, S, world),
                 "regime": a.regime, "integrator": "DP5(4) scipy-RK45 controller" if wl.method == "dp54" else "RK4 h=0.1",
                 "rtol": 1e-3, "atol": 1e-6, "max_step": (0.1 if a.regime == "fine" else "inf"),
@@ -750,7 +774,7 @@ def main():
                 "launch": m["launch"],
                 "timed_region": f"{len(m['dts'])} repetition(s) of EXACTLY {a.steps} steps between barrier + synchronise (max over ranks each), "
                                 f"after {a.warmup} warm-up steps; value / ms_per_step = the MEDIAN repetition, every repetition in "
-                                f"ms_per_step_samples; calibration probes: {a.probe_when}",
+                                f"ms_per_step_samples; calibration probes: {a.probe_when if a.full else 'none (--full runs them)'}",
             },
             "roofline": roofline_block(wl, ray_steps, k_ms, call_ms, n, bytes_per_ray, traffic, traffic_source, valu_per_64,
                                        calibration=m["calibration"], sclk=m["sclk"], call_samples=m["call_samples"], share=m["share"],
@@ -765,7 +789,7 @@ def main():
         if frames_sharded is not None:
             out["frames_sharded"] = frames_sharded
         t1 = None
-        if world == 1 and a.workload == "frame" and not a.lean:
+        if a.full and world == 1 and a.workload == "frame":
             # the other output form of the same frame, same K / W, same clock: whole end states (81 B/ray: what north_star
             # names -- "exit position/direction written back" -- and the headline) against the exit directions alone that a
             # sky frame reads (57 B/ray; background_hit, :366-378)
@@ -785,7 +809,7 @@ def main():
                              "shaded from them" if other_dir else
                              "the same frame and K / W with whole end states written (x, k: 48 B/ray) and shaded from them")}
             secondary(out, "sky_frame_dir_only" if other_dir else "full_records", other_output_form)
-        if world == 1 and a.workload == "frame" and a.regime == "adaptive" and not a.lean:
+        if a.full and world == 1 and a.workload == "frame" and a.regime == "adaptive":
             # SURVEY section 8d asks for both step regimes: the fine one (max_step 0.1, ~490 steps per ray) and the fixed-step RK4
             # (h = 0.1, 500 steps per ray) on the same frame, a few steps each (40 and 16 ms per step), same output form
             def regimes():
@@ -804,15 +828,15 @@ def main():
                 fr.trace(wl.params)      # (leave the frame's buffers holding the adaptive result)
                 return regs
             secondary(out, "regimes", regimes)
-        if world == 1 and a.workload == "frame" and a.emulate_shards.strip():
+        if a.full and world == 1 and a.workload == "frame" and a.emulate_shards.strip():
             def predicted():
                 t1_ms, t1_call, _ = time_frame(fr, wl.params, a.steps, a.warmup, device=rt.local_rank, ramp=a.ramp_seconds)
                 return strong_predicted(rt, wl, sky, m, (t1_ms, t1_call))
             secondary(out, "strong_predicted", predicted)
-        if world == 1 and a.workload == "frame" and a.cpu_seconds > 0:   # (--cpu-seconds 0 = kernels only: profiling runs)
+        if a.full and world == 1 and a.workload == "frame" and a.cpu_seconds > 0:   # (--cpu-seconds 0 = kernels only: profiling runs)
             secondary(out, "pipelined", lambda: pipelined_figure(rt, fr, wl.params, a))
             secondary(out, "host_buffer_call", lambda: host_buffer_figures(rt.ctx, fr, CAM, wl.params, n))
-        if a.cpu_seconds > 0 and world == 1:   # the CPU baseline is an N = 1 figure (rank 0's host cores, nothing else running)
+        if a.full and a.cpu_seconds > 0 and world == 1:   # the CPU baseline is an N = 1 figure (rank 0's host cores, nothing else running)
             okw = dict(wl.okw)
             if a.workload == "orbit":
                 okw["spheres"] = wl.orbit_scene(a.steps - 1)[0]

@@ -455,6 +455,7 @@ def roofline_block(wl, ray_steps, k_ms, call_ms, n, bytes_per_ray, traffic, traf
     if call_samples:
         # every HIP-event sample of the timed region(s), not their mean: the trace call of every EV_EVERY-th step of each
         # repetition (ms) times the trace kernel's share of a call (1 for the Schwarzschild forms: one launch per call)
+        # (share None: a run without --full measures no share -- kernel_ms is then the call's time)
         sh = 1.0 if share is None else share
         k_samples = [[x * sh for x in r_] for r_ in call_samples]
         flat = [x for r_ in k_samples for x in r_]
@@ -462,7 +463,8 @@ def roofline_block(wl, ray_steps, k_ms, call_ms, n, bytes_per_ray, traffic, traf
         extra["kernel_ms_spread"] = spread(flat)
         extra["kernel_ms_mean"] = float(np.mean(flat)) if flat else None
         extra["kernel_ms_is"] = (f"median of the {len(flat)} HIP-event samples (every {EV_EVERY}th step of each repetition, on the stream the "
-                                 f"library launches on) x the trace kernel's share of a call ({sh:.4f})")
+                                 f"library launches on)" + (f" x the trace kernel's share of a call ({sh:.4f})" if share is not None else
+                                                            ": the trace CALL's time (the trace kernel's share of it is measured with --full)"))
     return {**_roofline_core(wl, ray_steps, k_ms, call_ms, n, bytes_per_ray, traffic, traffic_source, valu_per_64, achieved_tf), **extra}
 
 

@@ -1,6 +1,6 @@
 """bench_figures.py -- everything of the bench line that is NOT the headline's timed region: the PMC counters measured
-in the run (live_pmc) or replayed (pmc_traffic), the secondary blocks (full_records via time_frame, strong_predicted,
-pipelined, host_buffer_call, cpu_baseline) and the --single-process form.  The headline clock lives in bench.py's
+in the run (live_pmc, --full) or replayed (pmc_traffic), the secondary blocks of a --full run (full_records via time_frame,
+strong_predicted, pipelined, host_buffer_call, cpu_baseline) and the --single-process form.  The headline clock lives in bench.py's
 measure() and nowhere else.  See bench.py."""
 import json
 import os
@@ -447,12 +447,15 @@ def host_buffer_figures(ctx, fr, cam, params, n):
 def main_single_process(a):
     """The same workloads through bhg_frame_* (include/bhgeo.h; _ffi.Frame): one process, N devices, no torch.distributed
     and no torch in the timed path.  Weak scaling like the multi-process form (the frame grows with N over the same window
-    of directions) plus the fixed frame as `strong`; a step = one bhg_frame_render(..., NULL) per frame of the workload
-    (enqueue only: the image stays on device 0); both ends of the timed region wait for every device's stream."""
+    of directions) plus, with --full, two frames in flight as `pipelined` and the fixed frame as `strong`; a step = one
+    bhg_frame_render(..., NULL) per frame of the workload (enqueue only: the image stays on device 0); both ends of the
+    timed region wait for every device's stream."""
     from blackhole_geodesic_calculator_amd import _ffi
     from blackhole_geodesic_calculator_amd.sky import synthetic_sky
     from blackhole_geodesic_calculator_amd.raygen import euler_xyz_matrix, python_random_stream
     wl = Workload(a)
+    # (the option set of a bench.py without --full -- the previous commit's, run against this module: what it always did)
+    full = getattr(a, "full", not a.lean)
     devices = [int(v) for v in os.environ["BHGEO_DEVICES"].split(",")] if os.environ.get("BHGEO_DEVICES") else list(range(a.gpus))
     N = len(devices)
     sky = synthetic_sky(2048, 1024)
@@ -554,7 +557,7 @@ def main_single_process(a):
         write_outputs(a.dump_outputs, image_rows(images, W, H))
         del images
     pipelined = None
-    if not a.lean:
+    if full:
         # two frames in flight: a second set of frame objects, steps alternating between the sets
         fb, _, _, _ = build(nx, ny)
         p_ = timed(frames, fb)
@@ -566,7 +569,7 @@ def main_single_process(a):
     for f in frames:
         f.close()
     strong = None
-    if N > 1 and a.workload != "orbit":
+    if (full or a.lean) and N > 1 and a.workload != "orbit":      # (--lean: as it always did)
         fs, Ws, Hs, _ = build(1, 1)
         s_ = timed(fs)
         fb, _, _, _ = build(1, 1)

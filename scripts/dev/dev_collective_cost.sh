@@ -1,3 +1,4 @@
+# (no --full: kernel_ms is the trace CALL's time -- the kernel's own for this Schwarzschild frame, one launch per call)
 for m in 0 1; do
   if [ $m = 1 ]; then export BHGEO_FORCE_COLLECTIVE=1; else unset BHGEO_FORCE_COLLECTIVE; fi
   python bench.py --cpu-seconds 0 2>/dev/null | tail -1 | python -c "import json,sys; b=json.loads(sys.stdin.read()); print(b['ms_per_step'], b['roofline']['kernel_ms'], b['config']['collective'])"

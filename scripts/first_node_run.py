@@ -8,9 +8,9 @@ raytracer/RelativisticRenderEngine.py:210-216.  This script extracts maximum evi
 in a FRESH child process (this parent never touches the GPU, nothing is exec'ed over a process that did), writes ONE JSON
 line to gpurun_out/node_run.jsonl, and a failure does not stop the steps after it; the exit code is non-zero if any failed.
 
-  (i)   python bench.py --gpus N                      N = 1, 2, 4, 8: one process per GPU, torch.distributed over RCCL
+  (i)   python bench.py --full --gpus N               N = 1, 2, 4, 8: one process per GPU, torch.distributed over RCCL
         (+ --workload disk and --workload orbit at the largest N: BASELINE configs 3 and 4)
-  (ii)  python bench.py --single-process --gpus N     N = 2, 4, 8 with --frame-gather rccl | copy | peer (N = 1: auto)
+  (ii)  python bench.py --full --single-process --gpus N   N = 2, 4, 8 with --frame-gather rccl | copy | peer (N = 1: auto)
   (iii) examples/render_frame.c on devices 0,1,..,N-1 (plain C through the C ABI; compiled here with gcc)
   (iv)  the N-device image against the 1-device image, bit for bit (library-owned frame, every gather mode)
   (v)   the same through torch.distributed: N ranks' gathered frame (disk + objects + exit sphere) == the one-rank frame
@@ -65,7 +65,8 @@ def plan(a):
     """[{name, cmd, env, parse}]: the steps in order."""
     py = sys.executable
     Ns = [n for n in (1, 2, 4, 8) if n <= a.gpus]
-    common = ["--steps", str(a.steps), "--warmup", str(a.warmup)]
+    # (--full: the strong / strong_predicted / pipelined blocks and the calibration are what this run is for)
+    common = ["--steps", str(a.steps), "--warmup", str(a.warmup), "--full"]
     steps = []
     # what the node looks like: devices, xGMI links between them, NUMA placement (informational: never fails the run)
     steps.append(dict(name="topology", kind="info", env={}, cmd=["bash", "-c", "rocm-smi --showtopo 2>&1 | tail -60; rocm-smi --showuniqueid 2>&1 | tail -12"]))
@@ -84,7 +85,7 @@ def plan(a):
     if nmax > 1:
         env = {"BHGEO_BENCH_BACKEND": "gloo"} if a.standin else {}
         small = ["--width", "256", "--samples", "2"] if a.quick else []
-        for wl_, sw in (("disk", common), ("orbit", ["--steps", str(max(2, a.steps // 4)), "--warmup", "2"])):   # (an orbit step is 16 x a frame step)
+        for wl_, sw in (("disk", common), ("orbit", ["--steps", str(max(2, a.steps // 4)), "--warmup", "2", "--full"])):   # (an orbit step is 16 x a frame step)
             steps.append(dict(name=f"dist_n{nmax}_{wl_}", kind="bench", n=nmax, env=env,
                               cmd=[py, os.path.join(ROOT, "bench.py"), "--gpus", str(nmax), "--workload", wl_] + sw + small +
                                   ["--cpu-seconds", "0", "--live-pmc", "0"]))

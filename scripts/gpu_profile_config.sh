@@ -4,12 +4,13 @@
 # usage (on the box, from the repo root): bash scripts/gpu_profile_config.sh <name> [bench args]
 name=$1; shift
 R=${GRAFT_REPO_ROOT:-$PWD}
-O=$R/gpurun_out
+# where everything is written: $BHG_PROFILE_OUT, or profile_out/ under the repository (git ignores it)
+O=${BHG_PROFILE_OUT:-$R/profile_out}
 mkdir -p $O
-# (1) the plain line of this box, for the record; (2) the SAME command --lean under rocprofv3 --kernel-trace --stats: its own
+# (1) the --full line of this box, for the record; (2) the SAME command --lean under rocprofv3 --kernel-trace --stats: its own
 # JSON line (HIP events in that very process) + the per-launch trace, reduced to the timed region's launches
 # (scripts/timed_region_stats.py) -- the two must agree to 1 % (VERDICT r03 task 3)
-timeout 900 python3 $R/bench.py "$@" 2>/dev/null | tail -1 > $O/prof_${name}_bench_plain.json
+timeout 900 python3 $R/bench.py --full "$@" 2>/dev/null | tail -1 > $O/prof_${name}_bench_plain.json
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/kt_$name /tmp/pf_$name /tmp/pw_$name
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$name -- python3 $R/bench.py --lean "$@" > $O/prof_${name}_rocprof.log 2>&1

@@ -3,7 +3,8 @@
 # then two separate PMC passes (FETCH_SIZE, WRITE_SIZE) as MI355X_MICROARCH.md prescribes.
 # Usage (on the box, from the repo root): bash scripts/gpu_round.sh <tag> [bench args]
 tag=${1:-r1}; shift
-BARGS="$@"
+# (--full: the round's line carries every secondary block; with --cpu-seconds 0 the profiled runs below start no counter passes)
+BARGS="--full $@"
 mkdir -p gpurun_out
 R=${GRAFT_REPO_ROOT:-$PWD}
 timeout 1500 python -m pytest tests -x -q -m gpu 2>&1 | tail -6 | tee gpurun_out/pytest_gpu_$tag.log

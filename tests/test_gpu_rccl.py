@@ -98,7 +98,7 @@ def test_bench_self_launches_two_ranks_when_started_without_a_launcher():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(BHGEO_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--width", "256", "--samples", "2",
-                          "--steps", "4", "--warmup", "2", "--ramp-seconds", "0", "--cpu-seconds", "0"],
+                          "--steps", "4", "--warmup", "2", "--ramp-seconds", "0", "--cpu-seconds", "0", "--full"],
                          env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     last = out.stdout.strip().splitlines()[-1]
@@ -116,11 +116,11 @@ def test_bench_self_launches_two_ranks_when_started_without_a_launcher():
 def test_bench_measured_tile_order_two_ranks_and_single_gpu_blocks():
     """`--order measured`: the calibration trace prices the tiles, the tables are summed over the ranks (gloo here) and
     the tiles re-dealt; the frame check inside bench.py (rank 0's pixels at their places) runs on the re-dealt shards.
-    And the single-GPU line carries the blocks the contract and VERDICT round 2 name."""
+    And the single-GPU line of a --full run carries the blocks the contract and VERDICT round 2 name."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(BHGEO_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--width", "256", "--samples", "2",
-                          "--steps", "4", "--warmup", "2", "--ramp-seconds", "0", "--cpu-seconds", "0", "--order", "measured"],
+                          "--steps", "4", "--warmup", "2", "--ramp-seconds", "0", "--cpu-seconds", "0", "--order", "measured", "--full"],
                          env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
@@ -128,7 +128,7 @@ def test_bench_measured_tile_order_two_ranks_and_single_gpu_blocks():
     env.pop("BHGEO_BENCH_BACKEND")      # (the single-GPU line's rank-0 emulation issues a real 1-rank RCCL gather)
     env.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_port()))
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--width", "256", "--samples", "2", "--steps", "8",
-                          "--warmup", "2", "--ramp-seconds", "0", "--cpu-seconds", "0", "--emulate-shards", "2"],
+                          "--warmup", "2", "--ramp-seconds", "0", "--cpu-seconds", "0", "--emulate-shards", "2", "--full"],
                          env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
@@ -157,7 +157,7 @@ def test_bench_orbit_two_ranks_reports_whole_frame_sharding_beside_the_tile_figu
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(BHGEO_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "orbit", "--width", "256",
-                          "--samples", "2", "--steps", "6", "--warmup", "2", "--ramp-seconds", "0", "--cpu-seconds", "0"],
+                          "--samples", "2", "--steps", "6", "--warmup", "2", "--ramp-seconds", "0", "--cpu-seconds", "0", "--full"],
                          env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
@@ -175,7 +175,7 @@ def test_bench_single_process_mode(devices, workload):
     env.update(BHGEO_DEVICES=devices)
     n = len(devices.split(","))
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--single-process", "--gpus", str(n), "--workload", workload,
-                          "--width", "256", "--samples", "2", "--steps", "8", "--warmup", "2", "--ramp-seconds", "0"],
+                          "--width", "256", "--samples", "2", "--steps", "8", "--warmup", "2", "--ramp-seconds", "0", "--full"],
                          env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
@@ -188,14 +188,14 @@ def test_bench_single_process_mode(devices, workload):
 
 
 def test_bench_measures_traffic_live_with_rocprofv3_child_runs():
-    """The default single-GPU line measures roofline.traffic and the VALU instruction count in its own run: three
+    """The single-GPU line of a --full run measures roofline.traffic and the VALU instruction count in its own run: three
     rocprofv3 --pmc child runs of the same command, started before the parent touches the GPU."""
     import shutil
     if shutil.which("rocprofv3") is None:
         pytest.skip("rocprofv3 not on PATH")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--width", "256", "--samples", "2", "--steps", "4",
-                          "--warmup", "2", "--ramp-seconds", "0", "--cpu-seconds", "0.2", "--emulate-shards", ""],
+                          "--warmup", "2", "--ramp-seconds", "0", "--cpu-seconds", "0.2", "--emulate-shards", "", "--full"],
                          env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])

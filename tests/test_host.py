@@ -251,6 +251,18 @@ def test_bench_self_launch_relays_a_failing_launch(tmp_path):
     assert "torch.distributed" in out.stderr or "Traceback" in out.stderr or "Error" in out.stderr
 
 
+def test_bench_full_is_off_by_default_and_lean_overrides_it():
+    """bench.py --full: off in a plain run (the headline alone), on when asked for; --lean (profiling runs) overrides it."""
+    import importlib
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    plain = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert plain.full is False and (plain.steps, plain.warmup, plain.reps) == (20, 5, 5)
+    assert bench.parse(["--full"]).full is True
+    lean = bench.parse(["--full", "--lean"])
+    assert lean.full is False and lean.cpu_seconds == 0.0 and lean.emulate_shards == ""
+
+
 def test_bench_live_pmc_declines_cleanly(monkeypatch):
     """bench.live_pmc(): no rocprofv3 on PATH, or the run already under a profiler -> {"error": why} (the line then
     carries the committed profiles/ summary and roofline.traffic_source says so, with the reason); never an exception."""
