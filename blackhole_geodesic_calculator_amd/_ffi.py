@@ -64,7 +64,9 @@ EXPORTS = (
     "bhg_object_motion_size", "bhg_redshift_motion_device", "bhg_redshift_motion_host", "bhg_shade_scene_moving_device",
     "bhg_frame_set_object_motion",
     "bhg_math_probe",
+    "bhg_trace_start_device", "bhg_start_steps_match",
 )
+START_NONE, START_RECORD, START_REPLAY = 0, 1, 2   # BHG_START_*: the rays' initial steps kept across calls (BHG_START_STEPS)
 PROBE_FMA, PROBE_STEP_MIX = 0, 1
 # bhg_math_probe: op -> (doubles in, doubles out) per element
 MATH_RCP_NEWTON, MATH_RCP_NR, MATH_RSQRT_NR, MATH_SQRT_NR, MATH_ATAN2_FAST, MATH_SINCOS_PI4, MATH_RCP3_NR, MATH_KERR_CART_TO_BL = range(8)
@@ -385,6 +387,12 @@ def load():
                                    C.c_void_p]
     L.bhg_trace_dir_device.restype = C.c_int
     L.bhg_trace_dir_device.argtypes = L.bhg_trace_device.argtypes
+    L.bhg_trace_start_device.restype = C.c_int
+    L.bhg_trace_start_device.argtypes = [C.c_void_p, C.POINTER(Params), _dp, C.c_int32, _dp, C.c_void_p, C.c_void_p, C.c_size_t,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_int32, C.c_void_p]
+    L.bhg_start_steps_match.restype = C.c_int
+    L.bhg_start_steps_match.argtypes = [C.POINTER(Params), C.POINTER(Params)]
     L.bhg_shade_dir_device.restype = C.c_int
     L.bhg_shade_dir_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p,
                                        C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -593,6 +601,11 @@ def load():
                           f"{C.sizeof(ObjectTextures)}")
     _lib = L
     return L
+
+
+def start_steps_match(a: "Params", b: "Params") -> bool:
+    """bhg_start_steps_match: do the two parameter sets give every ray the same initial step?  (The library holds the list.)"""
+    return bool(load().bhg_start_steps_match(C.byref(a), C.byref(b)))
 
 
 def _check(rc):
@@ -1085,11 +1098,27 @@ class Context:
         return traj, nv, end, flags
 
     # -- device buffers (raw addresses, e.g. torch.Tensor.data_ptr()) -------------------
+    def _trace_start_device(self, params, n, d_k0, d_end, d_end_dir, xs, d_x0, d_flags, d_n_steps, d_n_accepted, stream, spheres,
+                            d_object_id, d_start_steps, start_mode):
+        """bhg_trace_start_device: the three device trace calls in one, with the rays' initial steps recorded into or
+        replayed from d_start_steps [n] float64 (start_mode START_RECORD / START_REPLAY; include/bhgeo.h has the rules)."""
+        sp = None if spheres is None else _spheres_array(spheres)
+        _check(load().bhg_trace_start_device(self._h, C.byref(params), None if sp is None else _np_dp(sp), 0 if sp is None else len(sp),
+                                             xs, C.c_void_p(d_x0 or None), C.c_void_p(d_k0), int(n), C.c_void_p(d_end or None),
+                                             C.c_void_p(d_end_dir or None), C.c_void_p(d_flags or None),
+                                             C.c_void_p(d_n_steps or None), C.c_void_p(d_n_accepted or None),
+                                             C.c_void_p(d_object_id or None), C.c_void_p(d_start_steps or None), int(start_mode),
+                                             C.c_void_p(stream or None)))
+
     def trace_device(self, params: Params, n, d_k0, d_end, x0_shared=None, d_x0=0, d_flags=0,
-                     d_n_steps=0, d_n_accepted=0, stream=0, spheres=None, d_object_id=0):
+                     d_n_steps=0, d_n_accepted=0, stream=0, spheres=None, d_object_id=0, d_start_steps=0, start_mode=START_NONE):
+        """d_start_steps, start_mode: see _trace_start_device; without them the plain calls of always."""
         xs = None
         if x0_shared is not None:
             xs = (C.c_double * 3)(*[float(v) for v in x0_shared])
+        if start_mode != START_NONE:
+            return self._trace_start_device(params, n, d_k0, d_end, 0, xs, d_x0, d_flags, d_n_steps, d_n_accepted, stream, spheres,
+                                            d_object_id, d_start_steps, start_mode)
         if spheres is not None:
             sp = _spheres_array(spheres)
             _check(load().bhg_trace_objects_device(self._h, C.byref(params), _np_dp(sp), len(sp), xs,
@@ -1104,12 +1133,17 @@ class Context:
                                        C.c_void_p(d_n_accepted or None), C.c_void_p(stream or None)))
 
     def trace_dir_device(self, params: Params, n, d_k0, d_end_dir, x0_shared=None, d_x0=0, d_flags=0,
-                         d_n_steps=0, d_n_accepted=0, stream=0):
+                         d_n_steps=0, d_n_accepted=0, stream=0, d_start_steps=0, start_mode=START_NONE):
         """bhg_trace_dir_device: like trace_device, but only the direction half of the end states is written
         (d_end_dir [n][3]) -- what a sky frame consumes."""
         xs = None
         if x0_shared is not None:
             xs = (C.c_double * 3)(*[float(v) for v in x0_shared])
+        if start_mode != START_NONE:
+            if not d_end_dir:
+                raise ValueError("end_dir is NULL")
+            return self._trace_start_device(params, n, d_k0, 0, d_end_dir, xs, d_x0, d_flags, d_n_steps, d_n_accepted, stream, None,
+                                            0, d_start_steps, start_mode)
         _check(load().bhg_trace_dir_device(self._h, C.byref(params), xs, C.c_void_p(d_x0 or None),
                                            C.c_void_p(d_k0), int(n), C.c_void_p(d_end_dir),
                                            C.c_void_p(d_flags or None), C.c_void_p(d_n_steps or None),

@@ -1041,14 +1041,17 @@ int validate_spheres(const bhg_params *p, const double *spheres, int32_t n_spher
 int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres, int32_t n_spheres,
                      const double *x0_shared, const double *d_x0, const double *d_k0, size_t n, double *d_end,
                      uint8_t *d_flags, uint32_t *d_n_steps, uint32_t *d_n_accepted, int8_t *d_object_id, void *stream,
-                     double *d_end_dir)
+                     double *d_end_dir, double *d_start_steps, int32_t start_mode)
 {
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
     int rc = validate(p);
     if (rc != BHG_OK) return rc;
     rc = validate_spheres(p, spheres, n_spheres);
     if (rc != BHG_OK) return rc;
+    if (start_mode != BHG_START_NONE && start_mode != BHG_START_RECORD && start_mode != BHG_START_REPLAY)
+        return fail(BHG_E_INVALID, "start_mode must be BHG_START_NONE, BHG_START_RECORD or BHG_START_REPLAY");
     if (n == 0) return BHG_OK;
+    if (start_mode != BHG_START_NONE && !d_start_steps) return fail(BHG_E_INVALID, "start_mode asks for d_start_steps, which is NULL");
     if (!d_k0 || (!d_end && !d_end_dir)) return fail(BHG_E_INVALID, "k0 / end is NULL");
     if (!x0_shared && !d_x0) return fail(BHG_E_INVALID, "neither x0_shared nor d_x0 given");
     if (n > bhg::BHG_MAX_RAYS_PER_LAUNCH) return fail(BHG_E_INVALID, "internal: more rays than one launch takes");
@@ -1147,6 +1150,9 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres,
         a.order_block_len = n / p->order_blocks;
     }
     a.object_id = d_object_id;
+    // the rays' initial steps kept by their owner (the DP5(4) kernels' queue fill; RK4 has none and never looks)
+    a.start_h = start_mode != BHG_START_NONE ? d_start_steps : nullptr;
+    a.start_mode = start_mode;
     a.n_spheres = n_spheres;
     for (int j = 0; j < n_spheres; j++)
         for (int q = 0; q < 4; q++) a.spheres[j][q] = spheres[4 * j + q];
@@ -1229,11 +1235,11 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres,
 int trace_device_impl(bhg_context *c, const bhg_params *p, const double *spheres, int32_t n_spheres,
                       const double *x0_shared, const double *d_x0, const double *d_k0, size_t n, double *d_end,
                       uint8_t *d_flags, uint32_t *d_n_steps, uint32_t *d_n_accepted, int8_t *d_object_id, void *stream,
-                      double *d_end_dir = nullptr)
+                      double *d_end_dir = nullptr, double *d_start_steps = nullptr, int32_t start_mode = BHG_START_NONE)
 {
     if (n <= bhg::BHG_MAX_RAYS_PER_LAUNCH)
         return trace_device_one(c, p, spheres, n_spheres, x0_shared, d_x0, d_k0, n, d_end, d_flags, d_n_steps, d_n_accepted,
-                                d_object_id, stream, d_end_dir);
+                                d_object_id, stream, d_end_dir, d_start_steps, start_mode);
     if (!p) return fail(BHG_E_INVALID, "params is NULL");
     if (n > 0xFFFFFFFFull) return fail(BHG_E_INVALID, "n must be < 2^32 per call");
     bhg_params q = *p;
@@ -1244,7 +1250,8 @@ int trace_device_impl(bhg_context *c, const bhg_params *p, const double *spheres
                                         d_k0 ? d_k0 + off * 3 : nullptr, m, d_end ? d_end + off * 6 : nullptr,
                                         d_flags ? d_flags + off : nullptr, d_n_steps ? d_n_steps + off : nullptr,
                                         d_n_accepted ? d_n_accepted + off : nullptr, d_object_id ? d_object_id + off : nullptr,
-                                        stream, d_end_dir ? d_end_dir + off * 3 : nullptr);
+                                        stream, d_end_dir ? d_end_dir + off * 3 : nullptr,
+                                        d_start_steps ? d_start_steps + off : nullptr, start_mode);
         if (rc != BHG_OK) return rc;
     }
     c->last_launch[3] = (int32_t)((n + bhg::BHG_MAX_RAYS_PER_LAUNCH - 1) / bhg::BHG_MAX_RAYS_PER_LAUNCH);
@@ -1279,6 +1286,28 @@ int bhg_trace_objects_device(bhg_context *c, const bhg_params *p, const double *
 {
     return trace_device_impl(c, p, spheres, n_spheres, x0_shared, d_x0, d_k0, n, d_end, d_flags, d_n_steps, d_n_accepted,
                              d_object_id, stream);
+}
+
+int bhg_trace_start_device(bhg_context *c, const bhg_params *p, const double *spheres, int32_t n_spheres,
+                           const double *x0_shared, const double *d_x0, const double *d_k0, size_t n, double *d_end,
+                           double *d_end_dir, uint8_t *d_flags, uint32_t *d_n_steps, uint32_t *d_n_accepted,
+                           int8_t *d_object_id, double *d_start_steps, int32_t start_mode, void *stream)
+{
+    if (n && !d_end && !d_end_dir) return fail(BHG_E_INVALID, "end / end_dir is NULL");
+    return trace_device_impl(c, p, spheres, n_spheres, x0_shared, d_x0, d_k0, n, d_end, d_flags, d_n_steps, d_n_accepted,
+                             d_object_id, stream, d_end ? nullptr : d_end_dir, d_start_steps, start_mode);
+}
+
+// THE list of what a ray's initial step depends on beside the ray itself (initial_record, geodesic_kernels.hip): the
+// controller's tolerances and limits and the metric.  The integrator is in it because only DP5(4) has such a step: a
+// recording RK4 call leaves the array as it was.  Compared bit for bit (a -0.0 or another NaN counts as a change: safe).
+int bhg_start_steps_match(const bhg_params *a, const bhg_params *b)
+{
+    if (!a || !b) return 0;
+    auto same = [](double x, double y) { return std::memcmp(&x, &y, sizeof(double)) == 0; };
+    return same(a->rtol, b->rtol) && same(a->atol, b->atol) && same(a->lambda_end, b->lambda_end) &&
+           same(a->max_step, b->max_step) && same(a->r_s, b->r_s) && same(a->spin, b->spin) &&
+           (a->time_like != 0) == (b->time_like != 0) && a->rhs_form == b->rhs_form && a->method == b->method;
 }
 
 int bhg_trace(bhg_context *c, const bhg_params *p, const double *x0, int x0_is_shared, const double *k0,

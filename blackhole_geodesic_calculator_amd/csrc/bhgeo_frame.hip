@@ -189,9 +189,14 @@ struct Shard {
     std::vector<int64_t> pixels;    // flat ids y * W + x, tile after tile
     size_t P = 0, n = 0;
     DevBuf pixels_d, jitter_d, k0, end, dir, flags, steps, acc, obj, slab, sky, disk_tex;
+    DevBuf start_h;                 // [n] doubles beside k0: the rays' initial steps, kept from render to render (BHG_START_STEPS)
     DevBuf otex[BHG_MAX_SPHERES];   // the object textures (bhg_frame_set_object_textures), slot by slot
     hipEvent_t done = nullptr;
     bool rays_ready = false;
+    bool start_ready = false;       // start_h holds the steps of the rays in k0, traced from start_origin with start_prm
+    bhg_params start_prm = {};
+    double start_origin[3] = {0, 0, 0};
+    void drop_rays() { rays_ready = start_ready = false; }   // the rays in k0 are to be made anew: their steps go with them
     bool jitter_ready = false;      // jitter_d holds the draws of THIS pixel list (kept: a rotating camera regenerates the rays from it)
     bool scene_ready = false;
     bool otex_ready = false;        // otex holds the frame's current object textures
@@ -262,7 +267,7 @@ void deal_tiles(bhg_frame *f)
         s.pixels.swap(px[r]);
         s.P = s.pixels.size();
         s.n = s.P * (size_t)f->cam.samples;
-        s.rays_ready = false;
+        s.drop_rays();
         s.jitter_ready = false;
         f->pmax = std::max(f->pmax, s.P);
     }
@@ -282,6 +287,7 @@ int upload_shard_geometry(bhg_frame *f, Shard &s, const bhg::ObserverParams *obs
     BHG_TRY(s.flags.ensure(s.device, s.n));
     BHG_TRY(s.steps.ensure(s.device, s.n * sizeof(uint32_t)));
     BHG_TRY(s.acc.ensure(s.device, s.n * sizeof(uint32_t)));
+    s.start_ready = false;   // (whoever asked for new rays has said so already; new rays never meet old steps)
     if (s.P == 0) {
         s.rays_ready = true;
         return BHG_OK;
@@ -602,7 +608,7 @@ int bhg_frame_set_camera(bhg_frame *f, const bhg_camera *cam)
     const bool dirs_change = cam->fov_x != f->cam.fov_x || cam->fov_y != f->cam.fov_y || std::memcmp(cam->rot, f->cam.rot, sizeof(cam->rot)) != 0;
     f->cam = *cam;
     if (dirs_change)
-        for (auto &s : f->sh) s.rays_ready = false;
+        for (auto &s : f->sh) s.drop_rays();
     return BHG_OK;
 }
 
@@ -673,7 +679,7 @@ int bhg_frame_set_observer(bhg_frame *f, const bhg_observer *obs)
     }
     f->observer = obs != nullptr;
     // the rays of the devices were made for the previous camera model: make them anew at the next render
-    for (auto &s : f->sh) s.rays_ready = false;
+    for (auto &s : f->sh) s.drop_rays();
     return BHG_OK;
 }
 
@@ -766,6 +772,8 @@ try {
     Shard &root = f->sh[0];
     bhg_params prm = *p;
     if (prm.order_blocks == 0 && S > 1) prm.order_blocks = (uint32_t)S;   // the rays are S blocks of P (sample-major)
+    const char *sc_env = std::getenv("BHGEO_START_CACHE");   // "0": every render works the initial steps out (A/B, short memory)
+    const bool start_cache = !(sc_env && sc_env[0] == '0' && sc_env[1] == 0);
     const bool redshift = f->rs.apply != 0;
     if (redshift) {   // (refused before anything is enqueued)
         bhg::RedshiftParams rp;
@@ -778,7 +786,7 @@ try {
         // the tetrad depends on the camera position and the metric: rays made for others are made anew
         const double key[6] = {op.x0[0], op.x0[1], op.x0[2], op.r_s, op.spin, (double)op.rhs};
         if (std::memcmp(key, f->obs_key, sizeof(key)) != 0) {
-            for (auto &s : f->sh) s.rays_ready = false;
+            for (auto &s : f->sh) s.drop_rays();
             std::memcpy(f->obs_key, key, sizeof(key));
         }
     }
@@ -827,17 +835,29 @@ try {
             }
             HIP_TRY(hipEventRecord(s.evs[s.ev_used].first, s.stream));
         }
-        if (dir_only) {
-            BHG_TRY(s.dir.ensure(s.device, s.n * 3 * sizeof(double)));
-            BHG_TRY(bhg_trace_dir_device(s.ctx, &prm, f->cam.origin, nullptr, s.k0.as<double>(), s.n, s.dir.as<double>(),
-                                         s.flags.as<uint8_t>(), s.steps.as<uint32_t>(), s.acc.as<uint32_t>(), s.stream));
-        } else {
-            BHG_TRY(s.end.ensure(s.device, s.n * 6 * sizeof(double)));
-            if (has_obj) BHG_TRY(s.obj.ensure(s.device, s.n));
-            BHG_TRY(bhg_trace_objects_device(s.ctx, &prm, has_obj ? &f->scene.spheres[0][0] : nullptr, f->scene.n_spheres,
-                                             f->cam.origin, nullptr, s.k0.as<double>(), s.n, s.end.as<double>(),
-                                             s.flags.as<uint8_t>(), s.steps.as<uint32_t>(), s.acc.as<uint32_t>(),
-                                             has_obj ? s.obj.as<int8_t>() : nullptr, s.stream));
+        // The shard owns its rays, so their initial steps outlive the render: recorded by the first trace of a ray set,
+        // replayed while the rays, the origin and what bhg_start_steps_match() lists stay as they were.  Not valid while a
+        // call is being issued: a failed enqueue leaves it so.
+        int32_t start_mode = BHG_START_NONE;
+        if (start_cache) {
+            const bool keep = s.start_ready && bhg_start_steps_match(&s.start_prm, &prm) &&
+                              std::memcmp(s.start_origin, f->cam.origin, sizeof(s.start_origin)) == 0;
+            s.start_ready = false;
+            BHG_TRY(s.start_h.ensure(s.device, s.n * sizeof(double)));
+            start_mode = keep ? BHG_START_REPLAY : BHG_START_RECORD;
+        }
+        if (dir_only) BHG_TRY(s.dir.ensure(s.device, s.n * 3 * sizeof(double)));
+        else BHG_TRY(s.end.ensure(s.device, s.n * 6 * sizeof(double)));
+        if (has_obj) BHG_TRY(s.obj.ensure(s.device, s.n));
+        BHG_TRY(bhg_trace_start_device(s.ctx, &prm, has_obj ? &f->scene.spheres[0][0] : nullptr, has_obj ? f->scene.n_spheres : 0,
+                                       f->cam.origin, nullptr, s.k0.as<double>(), s.n, dir_only ? nullptr : s.end.as<double>(),
+                                       dir_only ? s.dir.as<double>() : nullptr, s.flags.as<uint8_t>(), s.steps.as<uint32_t>(),
+                                       s.acc.as<uint32_t>(), has_obj ? s.obj.as<int8_t>() : nullptr, s.start_h.as<double>(),
+                                       start_mode, s.stream));
+        if (start_cache) {
+            s.start_prm = prm;
+            std::memcpy(s.start_origin, f->cam.origin, sizeof(s.start_origin));
+            s.start_ready = true;
         }
         if (f->profiling) HIP_TRY(hipEventRecord(s.evs[s.ev_used++].second, s.stream));
         // one shade call whatever the scene: a direction-only frame passes its exit directions (its sky g needs only the

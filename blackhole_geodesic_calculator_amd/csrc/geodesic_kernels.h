@@ -38,6 +38,9 @@ constexpr int BHG_RHS_CHRISTOFFEL_ = 0;
 constexpr int BHG_RHS_REDUCED_ = 1;
 constexpr int BHG_RHS_CHRISTOFFEL_TL_ = 3;   // internal: the Christoffel form with g(k, k) = -1 (bhg_params.time_like), own translation unit
 constexpr int BHG_RHS_KERR_BL_ = 2;
+constexpr int32_t BHG_START_NONE_ = 0;      // TraceArgs::start_mode: every call works its rays' initial steps out
+constexpr int32_t BHG_START_RECORD_ = 1;    // ... and stores them in start_h
+constexpr int32_t BHG_START_REPLAY_ = 2;    // start_h holds them (a recording call on the same rays and matching parameters)
 // rays per trace launch: the kernels form a ray's result offsets (idx * 48 at most) in 32 bits
 constexpr uint64_t BHG_MAX_RAYS_PER_LAUNCH = 1ull << 26;
 
@@ -82,6 +85,10 @@ struct TraceArgs {
     unsigned long long *diag;    // diagnostic builds only (BHG_DIAG): [grid][8] per-wave stamps
     uint32_t dbg_idx;            // diagnostic builds: ray whose controller trace is logged
     double spheres[BHG_MAX_SPHERES_][4];  // {cx, cy, cz, radius}, BH-centred
+    // the rays' initial steps kept across calls (DP5(4) trace kernels only, read in the queue fill; the RK4, prepare and
+    // trajectory kernels never look): last, so that no other member moves
+    double *start_h;             // [n] or nullptr
+    int32_t start_mode;          // BHG_START_*_
 };
 
 // the moving observer of the observer camera (frame_kernels.hip): on = 0 is the reference's camera

@@ -1042,6 +1042,10 @@ __device__ __forceinline__ void initial_record(const TraceArgs &A, const Metric 
 
 // Put rays base .. base+63 into the ray queue: coalesced loads of k0, x0; the start records {a0, h0, r0, E, L} are
 // worked out here, all lanes together.
+// The initial step h0 (DP5(4) only) depends on the ray, the tolerances, lambda_end, max_step and the metric alone, so an owner
+// of unchanged rays keeps it from call to call (TraceArgs::start_h, start_mode): a recording call stores each queued ray's h0,
+// a replaying call loads it -- with k0, in front of the vmcnt(0) below -- and works out a0 and r0 only.  The branch is
+// wave-uniform (a kernel argument); rays that start inside the hole are neither stored nor used.
 // Items that pass (h >= 0) take a free slot each (ballot/mbcnt ranks); the caller has made sure 64 are free.
 template <int RHS, bool ADAPTIVE, class LDS>
 __device__ __forceinline__ void fill_batch(const TraceArgs &A, LDS &Q, Wave &W, uint32_t lane, uint64_t base)
@@ -1052,14 +1056,20 @@ __device__ __forceinline__ void fill_batch(const TraceArgs &A, LDS &Q, Wave &W, 
         const double *k0, *x0;
         uint64_t n;
         int8_t *object_id;
-    } C = {BHG_COLD(kp, k0), BHG_COLD(kp, x0), BHG_COLD(kp, n), BHG_COLD(kp, object_id)};
+        double *start_h;
+        int32_t start_mode;
+    } C = {BHG_COLD(kp, k0), BHG_COLD(kp, x0), BHG_COLD(kp, n), BHG_COLD(kp, object_id), BHG_COLD(kp, start_h),
+           BHG_COLD(kp, start_mode)};
+    const bool replay = ADAPTIVE && C.start_mode == BHG_START_REPLAY_;
     const uint64_t i = base + lane;
+    double hs = 0.0;
     double px[3] = {0, 0, 0}, pk[3] = {0, 0, 0}, pa[3] = {0, 0, 0}, pr = 0.0, ph = -1.0;
     double pE = 0.0, pL = 0.0;
     if (i < C.n) {
         pk[0] = C.k0[i * 3 + 0];
         pk[1] = C.k0[i * 3 + 1];
         pk[2] = C.k0[i * 3 + 2];
+        if (replay) hs = C.start_h[i];
         if (C.x0) {
             px[0] = C.x0[i * 3 + 0];
             px[1] = C.x0[i * 3 + 1];
@@ -1097,7 +1107,13 @@ __device__ __forceinline__ void fill_batch(const TraceArgs &A, LDS &Q, Wave &W, 
             store_result(A, (uint32_t)i, cx, ck, BHG_FLAG_START_INSIDE_ | BHG_FLAG_HIT_HORIZON_, 0, 0);
         } else {
             ph = 0.0;
-            initial_record<RHS, ADAPTIVE>(A, met, px, pk, pa, pr, ph);
+            if (replay) {
+                initial_record<RHS, false>(A, met, px, pk, pa, pr, ph);
+                ph = hs >= 0.0 ? hs : 0.0;   // (a recorded step is >= 0; anything else fails in the step loop like NaN input)
+            } else {
+                initial_record<RHS, ADAPTIVE>(A, met, px, pk, pa, pr, ph);
+                if (ADAPTIVE && C.start_mode == BHG_START_RECORD_) C.start_h[i] = ph;
+            }
         }
     }
     const bool valid = ph >= 0.0;

@@ -8,6 +8,9 @@ device memory and the stream; all kernels are libbhgeo's.
 """
 from __future__ import annotations
 
+import itertools
+import os
+
 import numpy as np
 import torch
 
@@ -23,6 +26,67 @@ def _copy_params(p: _ffi.Params) -> _ffi.Params:
     return q
 
 
+# Rays are regenerated IN PLACE, and several frames may read one block of them (FrameBatch's members, a twin frame on a second
+# context): every generate_rays() stamps the block's storage with a new number, and whoever keeps something derived from the
+# rays keeps the stamp beside it.
+_ray_stamp = {}
+_next_stamp = itertools.count(1)
+
+
+def _rays_regenerated(d_k0):
+    _ray_stamp[d_k0.untyped_storage().data_ptr()] = next(_next_stamp)
+
+
+def _rays_key(d_k0):
+    return (d_k0.data_ptr(), d_k0.numel(), _ray_stamp.get(d_k0.untyped_storage().data_ptr(), 0))
+
+
+class StartSteps:
+    """The initial DP5(4) steps of a ray set its owner traces again and again (bhg_trace_start_device, include/bhgeo.h): an [n]
+    float64 array allocated at the first trace, recorded by it and replayed by every later trace for which the rays (their block,
+    its stamp, the origins) are the same and bhg_start_steps_match() accepts the parameters.  Scene changes -- disk, object
+    spheres, sky, shading -- never touch it.  Whoever writes into d_k0 in place by other means than generate_rays() calls
+    invalidate().  recorded / replayed count the traces of each kind; BHGEO_START_CACHE=0 in the environment or enabled=False
+    switch it off (every trace is then the plain call, and no memory is held: 8 B per ray otherwise)."""
+
+    def __init__(self, enabled=True):
+        self.enabled = bool(enabled)
+        self.d_h = None
+        self.key = self.params = self._pending = None
+        self.recorded = self.replayed = 0
+
+    def invalidate(self):
+        self.key = None
+
+    @property
+    def valid(self):
+        return self.key is not None
+
+    def plan(self, n, dev, key, params):
+        """(d_start_steps, start_mode) of the next trace call.  The steps count as not valid until done(): a call that raises
+        leaves them so."""
+        if not self.enabled or os.environ.get("BHGEO_START_CACHE", "") == "0":
+            self.key = None
+            return 0, _ffi.START_NONE
+        if self.d_h is None or self.d_h.numel() != n or self.d_h.device != dev:
+            self.d_h = torch.empty(n, dtype=torch.float64, device=dev)
+            self.key = None
+        replay = self.key is not None and self.key == key and _ffi.start_steps_match(self.params, params)
+        self.key = None
+        self._pending = (key, _copy_params(params), replay)
+        return self.d_h.data_ptr(), (_ffi.START_REPLAY if replay else _ffi.START_RECORD)
+
+    def done(self):
+        if self._pending is None:
+            return
+        self.key, self.params, replay = self._pending
+        self._pending = None
+        if replay:
+            self.replayed += 1
+        else:
+            self.recorded += 1
+
+
 class DeviceFrame:
     """All buffers of one frame shard on one GPU.
 
@@ -32,12 +96,14 @@ class DeviceFrame:
 
     def __init__(self, ctx: _ffi.Context, width, height, samples, *, fov_x=1.0, fov_y=1.0, sampling_seed=42.0,
                  origin=(1e-4, 0.0, 30.0), rotation_euler=(0.0, 0.0, 0.0), bh_loc=(0.0, 0.0, 0.0), pixels=None,
-                 jitter=None, device=None, buffers=None, directions_only=False):
+                 jitter=None, device=None, buffers=None, directions_only=False, start_cache=True):
         """directions_only: a frame without disk or objects reads only the exit DIRECTIONS of its rays (the sky
         lookup, :366-378) -- trace() then has the kernel write those alone (d_dir [n, 3], bhg_trace_dir_device: half
         the bytes written per ray and read by the shade kernel; d_end is not filled) and shade() / shade_f32() read
-        them.  With a disk or objects set the frame falls back to whole end records by itself."""
+        them.  With a disk or objects set the frame falls back to whole end records by itself.
+        start_cache: keep the rays' initial steps from trace to trace (StartSteps; 8 B per ray)."""
         self.ctx = ctx
+        self.start_steps = StartSteps(start_cache)
         self.directions_only = bool(directions_only)
         self.d_dir = None
         self._dir_traced = False
@@ -93,6 +159,17 @@ class DeviceFrame:
     def _stream(self):
         return torch.cuda.current_stream(self.dev).cuda_stream
 
+    @property
+    def d_k0(self):
+        """The rays' directions [n, 3].  Assigning another tensor (a twin frame reads its sibling's) drops what was kept for
+        the old one."""
+        return self._d_k0
+
+    @d_k0.setter
+    def d_k0(self, t):
+        self._d_k0 = t
+        self.start_steps.invalidate()
+
     def set_sky(self, sky_rgba_f32):
         """Equirectangular sky [TH, TW, 4] float32."""
         sky = np.ascontiguousarray(sky_rgba_f32, dtype=np.float32)
@@ -141,6 +218,7 @@ class DeviceFrame:
         self.observer = _ffi.make_observer(velocity)
         self._rays_ready = False
         self._ray_key = None
+        self.start_steps.invalidate()
 
     def set_polarisation(self, degree=None, disk_sense=1):
         """Disk polarisation for shade_stokes() (bhg_shade_scene_polarised_device): degree is a constant or
@@ -207,6 +285,8 @@ class DeviceFrame:
     def generate_rays(self, params: _ffi.Params = None):
         """params: the trace parameters (their metric) -- needed by the observer camera only."""
         self._traced = None      # new rays: results of an earlier trace belong to the old ones
+        self.start_steps.invalidate()
+        _rays_regenerated(self.d_k0)     # (... and so do the steps every other frame over this block keeps)
         if self.observer is not None:
             if params is None:
                 raise RuntimeError("the observer camera needs the trace parameters: generate_rays(params)")
@@ -231,20 +311,26 @@ class DeviceFrame:
         has_obj = self.spheres is not None and len(self.spheres) > 0
         self._dir_traced = self.directions_only and not has_obj and self.disk is None and not (params.disk_r_out > 0.0)
         self._traced = "dir" if self._dir_traced else "end"
+        # the initial steps belong to the rays and the origin they start from: recorded by the first trace, replayed after
+        origin = np.asarray(self.origin, dtype=np.float64)
+        d_h, mode = self.start_steps.plan(self.n, self.dev, (_rays_key(self.d_k0), origin.tobytes()), params)
         if self._dir_traced:
             if self.d_dir is None:
                 self.d_dir = torch.empty((self.n, 3), dtype=torch.float64, device=self.dev)
-            self.ctx.trace_dir_device(params, self.n, self.d_k0.data_ptr(), self.d_dir.data_ptr(), x0_shared=self.origin,
+            self.ctx.trace_dir_device(params, self.n, self.d_k0.data_ptr(), self.d_dir.data_ptr(), x0_shared=origin,
                                       d_flags=self.d_flags.data_ptr(), d_n_steps=self.d_steps.data_ptr(),
-                                      d_n_accepted=self.d_acc.data_ptr(), stream=self._stream())
+                                      d_n_accepted=self.d_acc.data_ptr(), stream=self._stream(), d_start_steps=d_h,
+                                      start_mode=mode)
+            self.start_steps.done()
             return
         if self.d_end is None:
             self.d_end = torch.empty((self.n, 6), dtype=torch.float64, device=self.dev)
-        self.ctx.trace_device(params, self.n, self.d_k0.data_ptr(), self.d_end.data_ptr(), x0_shared=self.origin,
+        self.ctx.trace_device(params, self.n, self.d_k0.data_ptr(), self.d_end.data_ptr(), x0_shared=origin,
                               d_flags=self.d_flags.data_ptr(), d_n_steps=self.d_steps.data_ptr(),
                               d_n_accepted=self.d_acc.data_ptr(), stream=self._stream(),
                               spheres=self.spheres if has_obj else None,
-                              d_object_id=self.d_obj.data_ptr() if has_obj else 0)
+                              d_object_id=self.d_obj.data_ptr() if has_obj else 0, d_start_steps=d_h, start_mode=mode)
+        self.start_steps.done()
 
     def scene(self):
         tex = self.d_disk_tex
@@ -320,9 +406,11 @@ class FrameBatch:
     into one block; shading stays per frame."""
 
     def __init__(self, ctx: _ffi.Context, cameras, width, height, samples, *, pixels=None, jitter=None, device=None,
-                 **frame_kw):
-        """cameras: list of dicts with origin=, rotation_euler= (and optionally bh_loc=)."""
+                 start_cache=True, **frame_kw):
+        """cameras: list of dicts with origin=, rotation_euler= (and optionally bh_loc=).
+        start_cache: keep the rays' initial steps from trace to trace (StartSteps), keyed on the members' rays and origins."""
         self.ctx = ctx
+        self.start_steps = StartSteps(start_cache)
         dev = torch.device("cuda", ctx.device) if device is None else device
         W, H, S = int(width), int(height), int(samples)
         P = W * H if pixels is None else len(pixels)
@@ -339,13 +427,14 @@ class FrameBatch:
         self.frames = []
         for j, cam in enumerate(cameras):
             sl = slice(j * n1, (j + 1) * n1)
-            f = DeviceFrame(ctx, W, H, S, pixels=pixels, jitter=jitter, device=dev,
+            f = DeviceFrame(ctx, W, H, S, pixels=pixels, jitter=jitter, device=dev, start_cache=start_cache,
                             buffers=(self.d_k0[sl], self.d_end[sl], self.d_flags[sl], self.d_steps[sl], self.d_acc[sl]),
                             **cam, **frame_kw)
             self.d_x0[sl] = torch.as_tensor(f.origin, device=dev)
             self.frames.append(f)
         self.n = m * n1
         self.dev = dev
+        self._origins = b"".join(np.asarray(f.origin, dtype=np.float64).tobytes() for f in self.frames)
 
     def generate_rays(self):
         for f in self.frames:
@@ -358,10 +447,14 @@ class FrameBatch:
         if params.order_blocks == 0 and nb > 1:
             params = _copy_params(params)
             params.order_blocks = nb
+        # (the members regenerate their rays in place, which stamps the block; d_x0 holds the origins they had at construction)
+        key = (_rays_key(self.d_k0), self.d_x0.data_ptr(), self._origins)
+        d_h, mode = self.start_steps.plan(self.n, self.dev, key, params)
         self.ctx.trace_device(params, self.n, self.d_k0.data_ptr(), self.d_end.data_ptr(), d_x0=self.d_x0.data_ptr(),
                               d_flags=self.d_flags.data_ptr(), d_n_steps=self.d_steps.data_ptr(),
                               d_n_accepted=self.d_acc.data_ptr(),
-                              stream=torch.cuda.current_stream(self.dev).cuda_stream)
+                              stream=torch.cuda.current_stream(self.dev).cuda_stream, d_start_steps=d_h, start_mode=mode)
+        self.start_steps.done()
         for f in self.frames:    # (whole records, whatever the members were constructed with)
             f._dir_traced, f._traced, f._params = False, "end", params
 

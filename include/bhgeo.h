@@ -62,7 +62,9 @@ extern "C" {
                                   BHG_DISK_THERMAL (bhg_disk_thermal_device / _host, bhg_shade_scene_thermal_device,
                                   bhg_frame_set_disk_thermal, bhg_disk_thermal_size, struct bhg_disk_thermal);
                                   BHG_OBJECT_MOTION (bhg_redshift_motion_device / _host, bhg_shade_scene_moving_device,
-                                  bhg_frame_set_object_motion, bhg_object_motion_size, struct bhg_object_motion).
+                                  bhg_frame_set_object_motion, bhg_object_motion_size, struct bhg_object_motion);
+                                  BHG_START_STEPS (bhg_trace_start_device, bhg_start_steps_match, BHG_START_*: the rays' initial
+                                  steps kept across calls on unchanged rays).
                                9: redshift -- bhg_redshift_device / _host, bhg_shade_scene_redshift_device, bhg_frame_set_redshift,
                                   bhg_redshift_size, struct bhg_redshift;
                                   nothing of ABI 8 changed.
@@ -294,6 +296,34 @@ int bhg_trace_objects_device(bhg_context *ctx, const bhg_params *p, const double
                              const double *x0_shared, const double *d_x0, const double *d_k0, size_t n,
                              double *d_end, uint8_t *d_flags, uint32_t *d_n_steps, uint32_t *d_n_accepted,
                              int8_t *d_object_id, void *stream);
+
+/* --- the rays' initial steps kept across calls (within ABI 10, BHG_START_STEPS) -------------------
+ * A DP5(4) trace call works out every ray's first step size (scipy's select_initial_step: a second right-hand side, square
+ * roots, divisions) before it integrates.  That step depends on the ray (x0, k0), on rtol, atol, lambda_end and max_step,
+ * on the metric (r_s, spin, time_like, rhs_form) and on nothing else -- not on the exit sphere, the disk, the object spheres,
+ * the step budget, the output form or the work-order hint.  A caller that OWNS its rays and traces them again and again (a
+ * static camera, an animation that moves objects only) keeps the steps in d_start_steps [n] doubles:
+ *   BHG_START_RECORD: the call of always, which also stores the step of every ray it integrates (rays that start inside the
+ *                     hole are neither written nor, later, used);
+ *   BHG_START_REPLAY: loads them instead (8 B per ray); valid after a recording call with the SAME d_x0 / x0_shared and d_k0
+ *                     contents, the same n and parameters for which bhg_start_steps_match() gives 1.  The results are the
+ *                     recording call's bit for bit.  The library cannot check that the rays are unchanged: the caller vouches.
+ *   BHG_START_NONE:   d_start_steps is ignored (may be NULL): bhg_trace_device / _dir_device / _objects_device are this.
+ * bhg_trace_start_device takes what those three take together: d_end [n][6], or -- d_end NULL -- d_end_dir [n][3]; spheres may
+ * be NULL with n_spheres = 0, d_object_id may be NULL.  BHG_METHOD_RK4 has no such step: the array is left untouched.  A call
+ * of more than 2^26 rays is split into launches and the array is walked along with d_k0.  When a recording call fails, treat
+ * the array as not recorded. */
+#define BHG_START_STEPS 1
+#define BHG_START_NONE 0
+#define BHG_START_RECORD 1
+#define BHG_START_REPLAY 2
+int bhg_trace_start_device(bhg_context *ctx, const bhg_params *p, const double *spheres, int32_t n_spheres,
+                           const double *x0_shared, const double *d_x0, const double *d_k0, size_t n, double *d_end,
+                           double *d_end_dir, uint8_t *d_flags, uint32_t *d_n_steps, uint32_t *d_n_accepted,
+                           int8_t *d_object_id, double *d_start_steps, int32_t start_mode, void *stream);
+/* 1 when the two parameter sets give every ray the same initial step (the list above, and the integrator: only DP5(4) records
+ * anything), else 0 -- also for a NULL argument.  THE one holder of that list: every owner of a d_start_steps array asks it. */
+int bhg_start_steps_match(const bhg_params *a, const bhg_params *b);
 
 /* --- the stages either side of the solve, on device ---------------------------------------- */
 /* Camera rays with the reference's multisample jitter (RelativisticRenderEngine.py:185-188,
