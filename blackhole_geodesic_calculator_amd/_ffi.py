@@ -65,7 +65,9 @@ EXPORTS = (
     "bhg_frame_set_object_motion",
     "bhg_math_probe",
     "bhg_trace_start_device", "bhg_start_steps_match",
+    "bhg_trace_crossings_device", "bhg_trace_crossings", "bhg_disk_layers_size", "bhg_shade_disk_layers_device",
 )
+MAX_CROSSINGS = 4   # BHG_MAX_CROSSINGS: disk crossings a crossings trace stores per ray (BHG_DISK_CROSSINGS)
 START_NONE, START_RECORD, START_REPLAY = 0, 1, 2   # BHG_START_*: the rays' initial steps kept across calls (BHG_START_STEPS)
 PROBE_FMA, PROBE_STEP_MIX = 0, 1
 # bhg_math_probe: op -> (doubles in, doubles out) per element
@@ -194,6 +196,18 @@ def make_object_motion(velocity=None, angular_velocity=None) -> ObjectMotion:
         for j in range(a.shape[0]):
             dst[j][:] = [float(x) for x in a[j]]
     return mo
+
+
+class DiskLayers(C.Structure):
+    """bhg_disk_layers (BHG_DISK_CROSSINGS, within ABI 10): the optically thin disk of the layered shade -- how many crossing
+    records a ray has at most and the opacity of one crossing."""
+    _fields_ = [("max_crossings", C.c_int32), ("pad", C.c_int32), ("opacity", C.c_double)]
+
+
+def make_disk_layers(max_crossings=3, opacity=1.0) -> DiskLayers:
+    """max_crossings: 1 .. MAX_CROSSINGS layers; opacity in (0, 1]: each crossing passes 1 - opacity of what lies behind it
+    (1: the opaque disk).  The library checks the ranges."""
+    return DiskLayers(int(max_crossings), 0, float(opacity))
 
 
 OBJECT_LIT, OBJECT_EMISSIVE = 0, 1
@@ -570,6 +584,19 @@ def load():
                                                 C.POINTER(DiskThermal), C.POINTER(ObjectMotion), C.c_void_p]
     L.bhg_frame_set_object_motion.restype = C.c_int
     L.bhg_frame_set_object_motion.argtypes = [C.c_void_p, C.POINTER(ObjectMotion)]
+    L.bhg_trace_crossings_device.restype = C.c_int
+    L.bhg_trace_crossings_device.argtypes = [C.c_void_p, C.POINTER(Params), _dp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bhg_trace_crossings.restype = C.c_int
+    L.bhg_trace_crossings.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int32,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bhg_disk_layers_size.restype = C.c_size_t
+    L.bhg_disk_layers_size.argtypes = []
+    L.bhg_shade_disk_layers_device.restype = C.c_int
+    L.bhg_shade_disk_layers_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                               C.c_int32, C.POINTER(Scene), C.POINTER(Params), C.POINTER(Redshift),
+                                               C.POINTER(Observer), _dp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.POINTER(DiskThermal), C.POINTER(DiskLayers), C.c_void_p]
     if L.bhg_version() != ABI_VERSION or not hasattr(L, "bhg_abi_check"):
         raise ImportError(f"libbhgeo ABI {L.bhg_version()} != expected {ABI_VERSION}: rebuild {LIB_PATH}")
     for name in ("bhg_params_size", "bhg_camera_size", "bhg_scene_size", "bhg_frame_scene_size"):
@@ -592,6 +619,8 @@ def load():
         raise ImportError(f"libbhgeo: bhg_observer is {L.bhg_observer_size()} bytes, this binding's {C.sizeof(Observer)}")
     if L.bhg_object_motion_size() != C.sizeof(ObjectMotion):
         raise ImportError(f"libbhgeo: bhg_object_motion is {L.bhg_object_motion_size()} bytes, this binding's {C.sizeof(ObjectMotion)}")
+    if L.bhg_disk_layers_size() != C.sizeof(DiskLayers):
+        raise ImportError(f"libbhgeo: bhg_disk_layers is {L.bhg_disk_layers_size()} bytes, this binding's {C.sizeof(DiskLayers)}")
     if L.bhg_disk_thermal_size() != C.sizeof(DiskThermal):
         raise ImportError(f"libbhgeo: bhg_disk_thermal is {L.bhg_disk_thermal_size()} bytes, this binding's {C.sizeof(DiskThermal)}")
     if L.bhg_polarisation_size() != C.sizeof(Polarisation):
@@ -1072,6 +1101,29 @@ class Context:
                                 _np_dp(end), flags.ctypes.data_as(_u8p), p_steps, p_acc))
         return end, flags, steps, acc
 
+    def trace_crossings(self, k0, x0, params: Params, max_crossings):
+        """bhg_trace_crossings: the trace that carries every ray THROUGH the disk of params and records its crossings (DP5(4), null
+        rays, no object spheres).  k0[N,3], x0[3] or [N,3] -> (end[N,6], flags[N], n_steps[N], n_accepted[N] -- those of the same
+        trace with the disk off --, cross[K,N,6] the first K = max_crossings crossing records in order, NaN where a ray has
+        none, n_cross[N] u8 every crossing counted)."""
+        k0 = np.ascontiguousarray(k0, dtype=np.float64)
+        if k0.ndim != 2 or k0.shape[1] != 3:
+            raise ValueError("k0 must have shape [N, 3]")
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        n = k0.shape[0]
+        if x0.shape != (3,) and x0.shape != (n, 3):
+            raise ValueError("x0 must have shape [3] or [N, 3]")
+        end = np.empty((n, 6), np.float64)
+        flags = np.empty(n, np.uint8)
+        steps = np.empty(n, np.uint32)
+        acc = np.empty(n, np.uint32)
+        cross = np.full((max(int(max_crossings), 0), n, 6), np.nan, np.float64)
+        n_cross = np.zeros(n, np.uint8)
+        _check(load().bhg_trace_crossings(self._h, C.byref(params), _addr(x0), 1 if x0.ndim == 1 else 0, _addr(k0), n,
+                                          int(max_crossings), _addr(end), _addr(flags), _addr(steps), _addr(acc), _addr(cross),
+                                          _addr(n_cross)))
+        return end, flags, steps, acc, cross, n_cross
+
     def trajectory(self, k0, x0, params: Params, n_points, spheres=None):
         """Sampled curves: (traj[N,6,T], n_valid[N], end[N,6], flags[N]); with spheres= (object spheres in the curved region,
         [[cx, cy, cz, radius], ...] BH-centred): (..., object_id[N]) -- bhg_trajectory_objects."""
@@ -1131,6 +1183,30 @@ class Context:
                                        C.c_void_p(d_k0), int(n), C.c_void_p(d_end),
                                        C.c_void_p(d_flags or None), C.c_void_p(d_n_steps or None),
                                        C.c_void_p(d_n_accepted or None), C.c_void_p(stream or None)))
+
+    def trace_crossings_device(self, params: Params, n, d_k0, max_crossings, d_end, d_cross, d_n_cross, x0_shared=None, d_x0=0,
+                               d_flags=0, d_n_steps=0, d_n_accepted=0, stream=0):
+        """bhg_trace_crossings_device: d_cross [max_crossings, n, 6] float64 and d_n_cross [n] uint8 beside trace_device's
+        outputs, which are those of the trace with the disk off."""
+        xs = None if x0_shared is None else (C.c_double * 3)(*[float(v) for v in x0_shared])
+        _check(load().bhg_trace_crossings_device(self._h, C.byref(params), xs, C.c_void_p(d_x0 or None), C.c_void_p(d_k0 or None),
+                                                 int(n), int(max_crossings), C.c_void_p(d_end or None), C.c_void_p(d_flags or None),
+                                                 C.c_void_p(d_n_steps or None), C.c_void_p(d_n_accepted or None),
+                                                 C.c_void_p(d_cross or None), C.c_void_p(d_n_cross or None),
+                                                 C.c_void_p(stream or None)))
+
+    def shade_disk_layers_device(self, d_end, d_flags, d_cross, d_n_cross, n_pixels, samples, scene: "Scene", layers: "DiskLayers",
+                                 params=None, rs=None, obs=None, th=None, x0_shared=None, d_k0=0, d_rgba=0, d_rgba_f32=0,
+                                 d_scatter=0, d_end_dir=0, stream=0):
+        """bhg_shade_disk_layers_device: the layered shade of a crossings trace -- the optically thin disk (layers: DiskLayers);
+        rs / obs / th as in shade_scene_thermal_device, None = off."""
+        xs = None if x0_shared is None else (C.c_double * 3)(*[float(v) for v in x0_shared])
+        _check(load().bhg_shade_disk_layers_device(
+            self._h, C.c_void_p(d_end or None), C.c_void_p(d_end_dir or None), C.c_void_p(d_flags or None),
+            C.c_void_p(d_cross or None), C.c_void_p(d_n_cross or None), int(n_pixels), int(samples), C.byref(scene),
+            None if params is None else C.byref(params), None if rs is None else C.byref(rs), _obs_ref(obs), xs,
+            C.c_void_p(d_k0 or None), C.c_void_p(d_rgba or None), C.c_void_p(d_rgba_f32 or None), C.c_void_p(d_scatter or None),
+            None if th is None else C.byref(th), None if layers is None else C.byref(layers), C.c_void_p(stream or None)))
 
     def trace_dir_device(self, params: Params, n, d_k0, d_end_dir, x0_shared=None, d_x0=0, d_flags=0,
                          d_n_steps=0, d_n_accepted=0, stream=0, d_start_steps=0, start_mode=START_NONE):

@@ -49,6 +49,7 @@ static_assert(sizeof(bhg_object_textures) == 800, "bhg_object_textures layout is
 static_assert(sizeof(bhg_polarisation) == 544 && BHG_POL_TABLE_MAX == bhg::BHG_POL_TABLE_MAX_, "bhg_polarisation layout is part of the ABI");
 static_assert(sizeof(bhg_disk_thermal) == 544 && BHG_THERMAL_NU_MAX == bhg::BHG_THERMAL_NU_MAX_, "bhg_disk_thermal layout is part of the ABI");
 static_assert(sizeof(bhg_object_motion) == 384, "bhg_object_motion layout is part of the ABI");
+static_assert(sizeof(bhg_disk_layers) == 16 && BHG_MAX_CROSSINGS == bhg::BHG_MAX_CROSSINGS_, "bhg_disk_layers layout is part of the ABI");
 static_assert(BHG_OBJECT_LIT == bhg::BHG_OBJECT_LIT_ && BHG_OBJECT_EMISSIVE == bhg::BHG_OBJECT_EMISSIVE_, "object mode mismatch");
 
 namespace {
@@ -853,6 +854,7 @@ size_t bhg_object_textures_size(void) { return sizeof(bhg_object_textures); }
 size_t bhg_polarisation_size(void) { return sizeof(bhg_polarisation); }
 size_t bhg_disk_thermal_size(void) { return sizeof(bhg_disk_thermal); }
 size_t bhg_object_motion_size(void) { return sizeof(bhg_object_motion); }
+size_t bhg_disk_layers_size(void) { return sizeof(bhg_disk_layers); }
 
 int bhg_abi_check(int abi_version, size_t params_size, size_t camera_size, size_t scene_size, size_t frame_scene_size)
 {
@@ -1036,12 +1038,22 @@ int validate_spheres(const bhg_params *p, const double *spheres, int32_t n_spher
     return BHG_OK;
 }
 
+// where a crossings trace (bhg_trace_crossings_device) puts its records: the layer stride is the CALL's ray count
+struct CrossOut {
+    double *cross;
+    uint8_t *n_cross;
+    int32_t max_cross;
+    size_t stride;
+};
+
 // ONE launch: n <= BHG_MAX_RAYS_PER_LAUNCH rays (the kernels form a ray's byte offsets in 32 bits).
 // d_end [n][6], or -- d_end == nullptr -- d_end_dir [n][3]: only the direction half of the final states is produced
+// cr: nullptr, or the call is a crossings trace -- the lane-per-ray kernel instead of the persistent one (the caller has checked
+// what that kernel does not cover)
 int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres, int32_t n_spheres,
                      const double *x0_shared, const double *d_x0, const double *d_k0, size_t n, double *d_end,
                      uint8_t *d_flags, uint32_t *d_n_steps, uint32_t *d_n_accepted, int8_t *d_object_id, void *stream,
-                     double *d_end_dir, double *d_start_steps, int32_t start_mode)
+                     double *d_end_dir, double *d_start_steps, int32_t start_mode, const CrossOut *cr = nullptr)
 {
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
     int rc = validate(p);
@@ -1162,56 +1174,68 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres,
                             : ((has_exit ? 1 : 0) | (p->disk_r_out > 0.0 ? 2 : 0));
     if (rhs_id == bhg::BHG_RHS_CHRISTOFFEL_TL_) evt = 7;    // (the time-like form exists in the all-events variant only)
 
-    // resident waves per CU of the trace kernel variant: asked of the runtime once per variant and context
-    const int vkey = ((p->method & 1) * 3 + (p->rhs_form % 3)) * 8 + evt + (rhs_id == bhg::BHG_RHS_CHRISTOFFEL_TL_ ? 48 : 0);
-    int per_cu = c->occupancy[vkey];
-    if (per_cu == 0) {
-        HIP_TRY(bhg::trace_occupancy(p->method, rhs_id, evt, &per_cu));
-        if (per_cu < 1) per_cu = 1;
-        if (per_cu > 32) per_cu = 32;
-        c->occupancy[vkey] = per_cu;
-    }
+    size_t grid = (n + 63) / 64;
+    int per_cu = 0;
+    if (cr) {
+        // the crossings trace: one lane per ray, no work counters, no resident-wave count
+        a.cross = cr->cross;
+        a.n_cross = cr->n_cross;
+        a.max_cross = cr->max_cross;
+        a.cross_stride = cr->stride;
+        HIP_TRY(bhg::launch_trace_crossings(a, rhs_id, s));
+        c->ev_valid = false;
+    } else {
+        // resident waves per CU of the trace kernel variant: asked of the runtime once per variant and context
+        const int vkey = ((p->method & 1) * 3 + (p->rhs_form % 3)) * 8 + evt + (rhs_id == bhg::BHG_RHS_CHRISTOFFEL_TL_ ? 48 : 0);
+        per_cu = c->occupancy[vkey];
+        if (per_cu == 0) {
+            HIP_TRY(bhg::trace_occupancy(p->method, rhs_id, evt, &per_cu));
+            if (per_cu < 1) per_cu = 1;
+            if (per_cu > 32) per_cu = 32;
+            c->occupancy[vkey] = per_cu;
+        }
 #ifdef BHG_TUNING
-    if (const char *ov = std::getenv("BHGEO_WAVES_PER_CU")) {  // tuning / diagnostic override
-        int v = std::atoi(ov);
-        if (v >= 1 && v <= 64) per_cu = v;
-    }
+        if (const char *ov = std::getenv("BHGEO_WAVES_PER_CU")) {  // tuning / diagnostic override
+            int v = std::atoi(ov);
+            if (v >= 1 && v <= 64) per_cu = v;
+        }
 #endif
-    // persistent waves: fill every resident wave slot once; never more waves than 64-ray batches
-    size_t batches = (n + 63) / 64;
-    size_t grid = (size_t)per_cu * (size_t)c->num_cus;
-    if (grid > batches) grid = batches;
+        // persistent waves: fill every resident wave slot once; never more waves than 64-ray batches
+        size_t batches = (n + 63) / 64;
+        grid = (size_t)per_cu * (size_t)c->num_cus;
+        if (grid > batches) grid = batches;
 #ifdef BHG_DIAG
-    {
-        static unsigned long long *dbuf = nullptr;
-        if (!dbuf) HIP_TRY(hipMalloc((void **)&dbuf, 65536 * 8 * sizeof(unsigned long long)));
-        a.diag = dbuf;
-        a.dbg_idx = std::getenv("BHGEO_DBG_IDX") ? (uint32_t)std::atoi(std::getenv("BHGEO_DBG_IDX")) : 0xFFFFFFFFu;
-        if (const char *path = std::getenv("BHGEO_DIAG_DUMP")) {
-            static unsigned long long host[65536 * 8];
-            HIP_TRY(hipDeviceSynchronize());
-            HIP_TRY(hipMemcpy(host, dbuf, sizeof(host), hipMemcpyDeviceToHost));
-            if (FILE *f = std::fopen(path, "wb")) {
-                std::fwrite(host, 1, sizeof(host), f);
-                std::fclose(f);
+        {
+            static unsigned long long *dbuf = nullptr;
+            if (!dbuf) HIP_TRY(hipMalloc((void **)&dbuf, 65536 * 8 * sizeof(unsigned long long)));
+            a.diag = dbuf;
+            a.dbg_idx = std::getenv("BHGEO_DBG_IDX") ? (uint32_t)std::atoi(std::getenv("BHGEO_DBG_IDX")) : 0xFFFFFFFFu;
+            if (const char *path = std::getenv("BHGEO_DIAG_DUMP")) {
+                static unsigned long long host[65536 * 8];
+                HIP_TRY(hipDeviceSynchronize());
+                HIP_TRY(hipMemcpy(host, dbuf, sizeof(host), hipMemcpyDeviceToHost));
+                if (FILE *f = std::fopen(path, "wb")) {
+                    std::fwrite(host, 1, sizeof(host), f);
+                    std::fclose(f);
+                }
             }
         }
-    }
 #endif
-    // ONE persistent launch finishes every ray: events are resolved and rays resumed inside the trace kernel, so
-    // the call only enqueues (Kerr: trace, finalize) and returns
-    if (!c->counters_clean) HIP_TRY(hipMemsetAsync(c->counter, 0, 2 * 8 * 256, s));   // first call, or after a failed enqueue
-    c->counters_clean = false;
-    HIP_TRY(bhg::launch_trace(a, p->method, rhs_id, evt, (int)grid, s, c->profiling ? c->ev : nullptr));
-    c->counter_set ^= 1;      // (the launch is in the stream: the next call of this context counts on the set it zeroes)
-    c->counters_clean = true;
-    c->ev_valid = c->profiling;
+        // ONE persistent launch finishes every ray: events are resolved and rays resumed inside the trace kernel, so
+        // the call only enqueues (Kerr: trace, finalize) and returns
+        if (!c->counters_clean) HIP_TRY(hipMemsetAsync(c->counter, 0, 2 * 8 * 256, s));   // first call, or after a failed enqueue
+        c->counters_clean = false;
+        HIP_TRY(bhg::launch_trace(a, p->method, rhs_id, evt, (int)grid, s, c->profiling ? c->ev : nullptr));
+        c->counter_set ^= 1;      // (the launch is in the stream: the next call of this context counts on the set it zeroes)
+        c->counters_clean = true;
+        c->ev_valid = c->profiling;
+    }
     c->last_launch[3] = 1;
     c->ev_post = false;
     if (p->rhs_form == BHG_RHS_KERR_BL) {
         // (direction-only calls: the finalize pass writes the Cartesian exit directions straight into d_end_dir)
         HIP_TRY(bhg::launch_kerr_finalize(a, d_end_dir, s));
-        if (c->profiling) {
+        if (c->profiling && !cr) {
             HIP_TRY(hipEventRecord(c->ev[3], s));
             c->ev_post = true;
         }
@@ -1235,23 +1259,27 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres,
 int trace_device_impl(bhg_context *c, const bhg_params *p, const double *spheres, int32_t n_spheres,
                       const double *x0_shared, const double *d_x0, const double *d_k0, size_t n, double *d_end,
                       uint8_t *d_flags, uint32_t *d_n_steps, uint32_t *d_n_accepted, int8_t *d_object_id, void *stream,
-                      double *d_end_dir = nullptr, double *d_start_steps = nullptr, int32_t start_mode = BHG_START_NONE)
+                      double *d_end_dir = nullptr, double *d_start_steps = nullptr, int32_t start_mode = BHG_START_NONE,
+                      const CrossOut *cr = nullptr)
 {
     if (n <= bhg::BHG_MAX_RAYS_PER_LAUNCH)
         return trace_device_one(c, p, spheres, n_spheres, x0_shared, d_x0, d_k0, n, d_end, d_flags, d_n_steps, d_n_accepted,
-                                d_object_id, stream, d_end_dir, d_start_steps, start_mode);
+                                d_object_id, stream, d_end_dir, d_start_steps, start_mode, cr);
     if (!p) return fail(BHG_E_INVALID, "params is NULL");
     if (n > 0xFFFFFFFFull) return fail(BHG_E_INVALID, "n must be < 2^32 per call");
     bhg_params q = *p;
     q.order_blocks = 0;
     for (size_t off = 0; off < n; off += bhg::BHG_MAX_RAYS_PER_LAUNCH) {
         const size_t m = std::min((size_t)bhg::BHG_MAX_RAYS_PER_LAUNCH, n - off);
+        // (a crossings trace: this launch's rays sit at offset off inside every layer of the call's record array)
+        CrossOut part{};
+        if (cr) part = CrossOut{cr->cross + off * 6, cr->n_cross + off, cr->max_cross, cr->stride};
         const int rc = trace_device_one(c, &q, spheres, n_spheres, x0_shared, d_x0 ? d_x0 + off * 3 : nullptr,
                                         d_k0 ? d_k0 + off * 3 : nullptr, m, d_end ? d_end + off * 6 : nullptr,
                                         d_flags ? d_flags + off : nullptr, d_n_steps ? d_n_steps + off : nullptr,
                                         d_n_accepted ? d_n_accepted + off : nullptr, d_object_id ? d_object_id + off : nullptr,
                                         stream, d_end_dir ? d_end_dir + off * 3 : nullptr,
-                                        d_start_steps ? d_start_steps + off : nullptr, start_mode);
+                                        d_start_steps ? d_start_steps + off : nullptr, start_mode, cr ? &part : nullptr);
         if (rc != BHG_OK) return rc;
     }
     c->last_launch[3] = (int32_t)((n + bhg::BHG_MAX_RAYS_PER_LAUNCH - 1) / bhg::BHG_MAX_RAYS_PER_LAUNCH);
@@ -1308,6 +1336,76 @@ int bhg_start_steps_match(const bhg_params *a, const bhg_params *b)
     return same(a->rtol, b->rtol) && same(a->atol, b->atol) && same(a->lambda_end, b->lambda_end) &&
            same(a->max_step, b->max_step) && same(a->r_s, b->r_s) && same(a->spin, b->spin) &&
            (a->time_like != 0) == (b->time_like != 0) && a->rhs_form == b->rhs_form && a->method == b->method;
+}
+
+// what the crossings trace covers, checked before the context (a refusal names its figure with or without a device)
+static int crossings_check(const bhg_params *p, int32_t max_crossings)
+{
+    int rc = validate(p);
+    if (rc != BHG_OK) return rc;
+    if (p->method != BHG_METHOD_DP54) return fail(BHG_E_INVALID, "the crossings trace is DP5(4) only: method must be BHG_METHOD_DP54");
+    if (p->time_like) return fail(BHG_E_INVALID, "the crossings trace covers null rays only: time_like must be 0");
+    if (!(p->disk_r_out > 0.0)) return fail(BHG_E_INVALID, "the crossings trace needs a disk: disk_r_out must be > 0");
+    if (max_crossings < 1 || max_crossings > BHG_MAX_CROSSINGS)
+        return fail(BHG_E_INVALID, "max_crossings must be in [1, BHG_MAX_CROSSINGS]");
+    return BHG_OK;
+}
+
+int bhg_trace_crossings_device(bhg_context *c, const bhg_params *p, const double *x0_shared, const double *d_x0,
+                               const double *d_k0, size_t n, int32_t max_crossings, double *d_end, uint8_t *d_flags,
+                               uint32_t *d_n_steps, uint32_t *d_n_accepted, double *d_cross, uint8_t *d_n_cross, void *stream)
+{
+    int rc = crossings_check(p, max_crossings);
+    if (rc != BHG_OK) return rc;
+    if (n && (!d_end || !d_cross || !d_n_cross)) return fail(BHG_E_INVALID, "end / cross / n_cross is NULL");
+    const CrossOut cr{d_cross, d_n_cross, max_crossings, n};
+    return trace_device_impl(c, p, nullptr, 0, x0_shared, d_x0, d_k0, n, d_end, d_flags, d_n_steps, d_n_accepted, nullptr, stream,
+                             nullptr, nullptr, BHG_START_NONE, &cr);
+}
+
+// the host-buffer call, plain: upload, one device call, download (the crossings trace is not a streaming path)
+int bhg_trace_crossings(bhg_context *c, const bhg_params *p, const double *x0, int x0_is_shared, const double *k0, size_t n,
+                        int32_t max_crossings, double *end, uint8_t *flags, uint32_t *n_steps, uint32_t *n_accepted,
+                        double *cross, uint8_t *n_cross)
+{
+    int rc = crossings_check(p, max_crossings);
+    if (rc != BHG_OK) return rc;
+    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
+    if (n == 0) return BHG_OK;
+    if (!x0 || !k0 || !end || !cross || !n_cross) return fail(BHG_E_INVALID, "x0 / k0 / end / cross / n_cross is NULL");
+    if (n > 0xFFFFFFFFull) return fail(BHG_E_INVALID, "n must be < 2^32 per call");
+    ENTER_DEVICE(c->device);
+    const size_t b3 = n * 3 * sizeof(double), b6 = 2 * b3, bc = (size_t)max_crossings * b6, bu = n * sizeof(uint32_t);
+    const size_t o_x0 = b3, o_end = o_x0 + (x0_is_shared ? 0 : b3), o_cross = o_end + b6, o_steps = o_cross + bc,
+                 o_acc = o_steps + bu, o_flags = o_acc + bu, o_nc = o_flags + ((n + 7) & ~size_t(7));
+    char *d = nullptr;
+    HIP_TRY(hipMalloc((void **)&d, o_nc + n));
+    struct Free {
+        char *d;
+        hipStream_t s;
+        ~Free()
+        {
+            (void)hipStreamSynchronize(s);
+            (void)hipFree(d);
+        }
+    } guard{d, c->stream};
+    hipStream_t s = c->stream;
+    HIP_TRY(hipMemcpyAsync(d, k0, b3, hipMemcpyHostToDevice, s));
+    if (!x0_is_shared) HIP_TRY(hipMemcpyAsync(d + o_x0, x0, b3, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_cross, cross, bc, hipMemcpyHostToDevice, s));
+    rc = bhg_trace_crossings_device(c, p, x0_is_shared ? x0 : nullptr, x0_is_shared ? nullptr : (const double *)(d + o_x0),
+                                    (const double *)d, n, max_crossings, (double *)(d + o_end), (uint8_t *)(d + o_flags),
+                                    (uint32_t *)(d + o_steps), (uint32_t *)(d + o_acc), (double *)(d + o_cross),
+                                    (uint8_t *)(d + o_nc), s);
+    if (rc != BHG_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(end, d + o_end, b6, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(cross, d + o_cross, bc, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(n_cross, d + o_nc, n, hipMemcpyDeviceToHost, s));
+    if (flags) HIP_TRY(hipMemcpyAsync(flags, d + o_flags, n, hipMemcpyDeviceToHost, s));
+    if (n_steps) HIP_TRY(hipMemcpyAsync(n_steps, d + o_steps, bu, hipMemcpyDeviceToHost, s));
+    if (n_accepted) HIP_TRY(hipMemcpyAsync(n_accepted, d + o_acc, bu, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return BHG_OK;
 }
 
 int bhg_trace(bhg_context *c, const bhg_params *p, const double *x0, int x0_is_shared, const double *k0,
@@ -1704,11 +1802,19 @@ int raygen_impl(bhg_context *c, int32_t width, int32_t height, int32_t samples, 
 //      arrays, so no device array is looked at
 //   6. the device arrays: an output, end or end_dir, flags, the sky; end for a disk or spheres; object_id for spheres;
 //      k0 for redshift; qu and k0 for polarisation; k0 for the thermal disk
+// ly: nullptr, or the call is the layered shade of a crossings trace (bhg_shade_disk_layers_device): checked after the scene
+// (step 1b: a disk, no spheres, max_crossings, opacity), its arrays with the others in step 6
+struct LayersIn {
+    const double *cross;
+    const uint8_t *n_cross;
+    const bhg_disk_layers *set;
+};
+
 int shade(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags, const int8_t *d_object_id,
           size_t n_pixels, int32_t samples, const bhg_scene *sc, const bhg_params *p, const bhg_redshift *rs,
           const bhg_observer *obs, const bhg_object_textures *ot, const double *x0_shared, const double *d_k0, double *d_rgba,
           float *d_rgba_f32, const int64_t *d_scatter, const bhg_polarisation *pol, double *d_qu, const bhg_disk_thermal *th,
-          const bhg_object_motion *mo, void *stream)
+          const bhg_object_motion *mo, void *stream, const LayersIn *ly = nullptr)
 {
     if (!sc) return fail(BHG_E_INVALID, "scene is NULL");
     if (samples <= 0 || sc->sky_w <= 0 || sc->sky_h <= 0) return fail(BHG_E_INVALID, "samples, sky_w, sky_h must be > 0");
@@ -1722,6 +1828,15 @@ int shade(bhg_context *c, const double *d_end, const double *d_end_dir, const ui
     }
     for (int j = 0; j < sc->n_spheres; j++)
         if (!(sc->spheres[j][3] > 0.0)) return fail(BHG_E_INVALID, "sphere radii must be > 0");
+    if (ly) {
+        if (!ly->set) return fail(BHG_E_INVALID, "disk layers: the settings are NULL");
+        if (!has_disk) return fail(BHG_E_INVALID, "disk layers need a disk in the scene: disk_r_out must be > 0");
+        if (sc->n_spheres > 0) return fail(BHG_E_INVALID, "disk layers do not go with object spheres: n_spheres must be 0");
+        if (ly->set->max_crossings < 1 || ly->set->max_crossings > BHG_MAX_CROSSINGS)
+            return fail(BHG_E_INVALID, "disk layers: max_crossings must be in [1, BHG_MAX_CROSSINGS]");
+        if (!(ly->set->opacity > 0.0) || !(ly->set->opacity <= 1.0))
+            return fail(BHG_E_INVALID, "disk layers: opacity must be in (0, 1]");
+    }
     bhg::ObjectTextureParams tp;
     if (ot) {
         int rc = bhg::object_texture_params(ot, sc->n_spheres, &tp);
@@ -1771,7 +1886,9 @@ int shade(bhg_context *c, const double *d_end, const double *d_end_dir, const ui
     if (n_pixels == 0) return BHG_OK;
     if ((!d_rgba && !d_rgba_f32) || (!d_end && !d_end_dir) || !d_flags || !sc->d_sky)
         return fail(BHG_E_INVALID, "NULL device pointer");
-    if (!d_end && (has_disk || sc->n_spheres > 0))
+    if (ly && (!ly->cross || !ly->n_cross)) return fail(BHG_E_INVALID, "disk layers: d_cross / d_n_cross is NULL");
+    // (the layered shade takes a disk ray's position from the crossing records: directions alone do for the rest)
+    if (!d_end && ((has_disk && !ly) || sc->n_spheres > 0))
         return fail(BHG_E_INVALID, "d_end is NULL: a direction-only frame cannot have a disk or object spheres");
     if (sc->n_spheres > 0 && !d_object_id) return fail(BHG_E_INVALID, "object_id is NULL but the scene has spheres");
     if (on && !d_k0) return fail(BHG_E_INVALID, "redshift needs the camera directions d_k0");
@@ -1825,6 +1942,14 @@ int shade(bhg_context *c, const double *d_end, const double *d_end_dir, const ui
         if (obs) a.obs = op_th;
     }
     if (mo) a.mo = mp;     // (launch_shade takes the motion instance only when rs.apply weighs objects)
+    if (ly) {
+        a.cross = ly->cross;
+        a.n_cross = ly->n_cross;
+        a.max_cross = ly->set->max_crossings;
+        a.transmit = 1.0 - ly->set->opacity;
+        HIP_TRY(bhg::launch_shade_layers(a, (hipStream_t)stream));
+        return BHG_OK;
+    }
     HIP_TRY(bhg::launch_shade(a, (hipStream_t)stream));
     return BHG_OK;
 }
@@ -1956,6 +2081,18 @@ int bhg_shade_scene_moving_device(bhg_context *c, const double *d_end, const dou
 {
     return shade(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs, obs, ot, x0_shared, d_k0, d_rgba,
                  d_rgba_f32, d_scatter, pol, d_qu, th, mo, stream);
+}
+
+int bhg_shade_disk_layers_device(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
+                                 const double *d_cross, const uint8_t *d_n_cross, size_t n_pixels, int32_t samples,
+                                 const bhg_scene *sc, const bhg_params *p, const bhg_redshift *rs, const bhg_observer *obs,
+                                 const double *x0_shared, const double *d_k0, double *d_rgba, float *d_rgba_f32,
+                                 const int64_t *d_scatter, const bhg_disk_thermal *th, const bhg_disk_layers *layers,
+                                 void *stream)
+{
+    const LayersIn ly{d_cross, d_n_cross, layers};
+    return shade(c, d_end, d_end_dir, d_flags, nullptr, n_pixels, samples, sc, p, rs, obs, nullptr, x0_shared, d_k0, d_rgba,
+                 d_rgba_f32, d_scatter, nullptr, nullptr, th, nullptr, stream, &ly);
 }
 
 int bhg_disk_thermal_device(bhg_context *c, const bhg_params *p, const bhg_disk_thermal *th, const bhg_observer *obs,

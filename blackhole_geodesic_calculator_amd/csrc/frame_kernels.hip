@@ -982,6 +982,97 @@ __global__ void __launch_bounds__(256) shade_reduce_serial_kernel(const ShadeArg
     if (POL) write_stokes(A, p, pacc);
 }
 
+// Disk layers (bhg_shade_disk_layers_device): the optically thin disk.  The ray was carried through the
+// disk by the crossings trace (disk_crossings_kernel: cross[m] the m-th crossing's record, n_cross the count, flags / end the
+// disk-off trace's); each crossing passes the fraction T = 1 - opacity of what lies behind it:
+//     w = 1;  for m < min(n_cross, max_cross) while w != 0:  rgb += w C(cross[m]);  w *= T
+//     if w != 0:  rgb += w * (what ray_colour gives the disk-off ray: black for the horizon, else the sky, weighted as rs says)
+// C is ray_colour's disk branch on the record: disk_colour and redshift_weigh, or (THERM) disk_thermal.  Sum and products in
+// this order (no contraction): the order is part of the result.  opacity = 1 (T = 0): layer 0 alone, nothing behind a disk
+// ray is looked at -- the opaque disk's image.
+template <bool RS, bool OBS, bool THERM>
+__device__ __forceinline__ void layers_colour(const ShadeArgs &A, uint64_t i, uint64_t n_rays, uint8_t fl, double c0, double c1,
+                                              double c2, double rgb[3])
+{
+    rgb[0] = rgb[1] = rgb[2] = 0.0;
+    double w = 1.0;
+    const uint32_t nc = A.n_cross[i], nl = nc < (uint32_t)A.max_cross ? nc : (uint32_t)A.max_cross;
+    for (uint32_t m = 0; m < nl && w != 0.0; m++) {
+        const double *e = A.cross + ((uint64_t)m * n_rays + i) * 6;
+        double c[3];
+        if (THERM) {
+            double t_em;
+            disk_thermal<OBS>(A.th, A.rs, A.obs, A.rs.x0, A.k0 + i * 3, e, t_em, c);
+        } else {
+            disk_colour(A, e, c);
+            if (RS) redshift_weigh<OBS>(A, i, RS_DISK, BHG_REDSHIFT_DISK_, e, c);
+        }
+        rgb[0] = rgb[0] + w * c[0];
+        rgb[1] = rgb[1] + w * c[1];
+        rgb[2] = rgb[2] + w * c[2];
+        w = w * A.transmit;
+    }
+    if (w != 0.0 && !(fl & (BHG_FLAG_HIT_HORIZON_ | BHG_FLAG_START_INSIDE_))) {
+        // (the disk-off trace's flags never carry the disk / object bit; it is masked so that no flag value makes ray_colour
+        // read the end record as a hit)
+        double sky[3];
+        ray_colour<RS, OBS, false, false, false, false>(A, i, (uint8_t)(fl & 0x7Fu), c0, c1, c2, sky, nullptr);
+        rgb[0] = rgb[0] + w * sky[0];
+        rgb[1] = rgb[1] + w * sky[1];
+        rgb[2] = rgb[2] + w * sky[2];
+    }
+}
+
+// shade_reduce_kernel's shape: one thread per RAY, the S samples of a pixel staged in LDS and summed in sample order
+template <bool RS, bool OBS, bool THERM>
+__global__ void __launch_bounds__(256) shade_layers_kernel(const ShadeArgs A, const uint32_t ppb)
+{
+    __shared__ double col[256 * 3];
+    const uint32_t t = threadIdx.x, S = (uint32_t)A.samples;
+    const uint32_t s = t / ppb, q = t - s * ppb;
+    const uint64_t p = (uint64_t)blockIdx.x * ppb + q;
+    const bool live = s < S && p < A.n_pixels;
+    if (live) {
+        const uint64_t i = (uint64_t)s * A.n_pixels + p;
+        const double *d = A.dir ? A.dir + i * 3 : A.end + i * 6 + 3;
+        double rgb[3];
+        layers_colour<RS, OBS, THERM>(A, i, (uint64_t)S * A.n_pixels, A.flags[i], d[0], d[1], d[2], rgb);
+        col[t * 3 + 0] = rgb[0];
+        col[t * 3 + 1] = rgb[1];
+        col[t * 3 + 2] = rgb[2];
+    }
+    __syncthreads();
+    if (s == 0 && live) {
+        double acc[3] = {0.0, 0.0, 0.0};
+        for (uint32_t k = 0; k < S; k++) {
+            const double *c = col + (size_t)(k * ppb + q) * 3;
+            acc[0] += c[0];
+            acc[1] += c[1];
+            acc[2] += c[2];
+        }
+        write_pixel(A, p, acc);
+    }
+}
+
+// more samples than a workgroup has threads: one thread per pixel (shade_reduce_serial_kernel's shape)
+template <bool RS, bool OBS, bool THERM>
+__global__ void __launch_bounds__(256) shade_layers_serial_kernel(const ShadeArgs A)
+{
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= A.n_pixels) return;
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int s = 0; s < A.samples; s++) {
+        const uint64_t i = (uint64_t)s * A.n_pixels + p;
+        const double *d = A.dir ? A.dir + i * 3 : A.end + i * 6 + 3;
+        double rgb[3];
+        layers_colour<RS, OBS, THERM>(A, i, (uint64_t)A.samples * A.n_pixels, A.flags[i], d[0], d[1], d[2], rgb);
+        acc[0] += rgb[0];
+        acc[1] += rgb[1];
+        acc[2] += rgb[2];
+    }
+    write_pixel(A, p, acc);
+}
+
 // dst[i] = src[index[i]] for rows of four floats: puts the gathered per-rank slabs into frame order on the
 // root GPU (index = the frame's permutation, computed once).  HBM-bound: 8 + 16 + 16 bytes per pixel.
 __global__ void __launch_bounds__(256) gather_rows4_kernel(const float4 *src, const int64_t *index, uint64_t n, float4 *dst)
@@ -1124,6 +1215,39 @@ hipError_t launch_shade(const ShadeArgs &a, hipStream_t s)
         launch_shade_tex<true, false>(a, s);
     } else {
         launch_shade_tex<false, false>(a, s);
+    }
+    return hipGetLastError();
+}
+
+template <bool RS, bool OBS, bool THERM>
+void launch_shade_layers_instance(const ShadeArgs &a, hipStream_t s)
+{
+    if (a.samples > 256) {
+        const dim3 grid((unsigned)((a.n_pixels + 255) / 256));
+        BHG_LAUNCH((shade_layers_serial_kernel<RS, OBS, THERM>), grid, dim3(256), 0, s, a);
+        return;
+    }
+    const uint32_t ppb = 256u / (uint32_t)a.samples;
+    const dim3 grid((unsigned)((a.n_pixels + ppb - 1) / ppb));
+    BHG_LAUNCH((shade_layers_kernel<RS, OBS, THERM>), grid, dim3(256), 0, s, a, ppb);
+}
+
+// the layered shade's five instances, chosen as launch_shade_mov chooses: thermal instances are redshift instances
+hipError_t launch_shade_layers(const ShadeArgs &a, hipStream_t s)
+{
+    if (a.n_pixels == 0) return hipSuccess;
+    const bool therm = a.th.on != 0, rs = a.rs.apply != 0 || therm, obs = rs && a.obs.on;
+    if (therm) {
+        if (obs)
+            launch_shade_layers_instance<true, true, true>(a, s);
+        else
+            launch_shade_layers_instance<true, false, true>(a, s);
+    } else if (obs) {
+        launch_shade_layers_instance<true, true, false>(a, s);
+    } else if (rs) {
+        launch_shade_layers_instance<true, false, false>(a, s);
+    } else {
+        launch_shade_layers_instance<false, false, false>(a, s);
     }
     return hipGetLastError();
 }

@@ -27,6 +27,7 @@ constexpr uint32_t BHG_FLAG_NAN_ = 64u;
 constexpr uint32_t BHG_FLAG_HIT_DISK_ = 128u;
 constexpr uint32_t BHG_FLAG_HIT_OBJECT_ = 0x88u;
 constexpr int BHG_MAX_SPHERES_ = 8;
+constexpr int BHG_MAX_CROSSINGS_ = 4;
 constexpr int32_t BHG_OBJECT_LIT_ = 0;
 constexpr int32_t BHG_OBJECT_EMISSIVE_ = 1;
 constexpr uint32_t BHG_REDSHIFT_DISK_ = 1u;
@@ -89,6 +90,11 @@ struct TraceArgs {
     // trajectory kernels never look): last, so that no other member moves
     double *start_h;             // [n] or nullptr
     int32_t start_mode;          // BHG_START_*_
+    // disk crossings (disk_crossings_kernel alone; no other kernel looks): last, so that no other member moves
+    int32_t max_cross;           // crossings stored per ray, 1 .. BHG_MAX_CROSSINGS_
+    double *cross;               // [max_cross][cross_stride][6]: record m of ray i, Cartesian, at (m * cross_stride + i) * 6
+    uint8_t *n_cross;            // [n]: crossings counted (saturating at 255), stored or not
+    uint64_t cross_stride;       // rays per layer of cross: the CALL's ray count (a launch may be a part of a call)
 };
 
 // the moving observer of the observer camera (frame_kernels.hip): on = 0 is the reference's camera
@@ -250,6 +256,12 @@ struct ShadeArgs {
     // moving object spheres (bhg_shade_scene_moving_device): launch_shade takes the motion instance when mo.on != 0 and
     // rs.apply weighs objects -- always a redshift instance; last, so that no other member moves
     MotionParams mo;
+    // disk layers (bhg_shade_disk_layers_device, launch_shade_layers; launch_shade never reads these): last, so that no other
+    // member moves
+    const double *cross;      // [max_cross][S*n_pixels][6]: the crossing records of the crossings trace
+    const uint8_t *n_cross;   // [S*n_pixels]
+    int32_t max_cross;        // layers in cross, 1 .. BHG_MAX_CROSSINGS_
+    double transmit;          // T = 1 - opacity of one disk crossing, 0 <= T < 1
 };
 
 // one thread per ray: (chi, delta, mu) from the camera state (x0, k0) and the end record (bhg_polarisation_device)
@@ -279,6 +291,8 @@ struct ThermalArgs {
 
 hipError_t launch_raygen(const RaygenArgs &a, hipStream_t s);
 hipError_t launch_shade(const ShadeArgs &a, hipStream_t s);
+// the layered shade of an optically thin disk (shade_layers_kernel): a.cross / n_cross / max_cross / transmit filled
+hipError_t launch_shade_layers(const ShadeArgs &a, hipStream_t s);
 hipError_t launch_redshift(const RedshiftArgs &a, hipStream_t s);
 hipError_t launch_redshift_motion(const RedshiftArgs &a, hipStream_t s);
 hipError_t launch_polarisation(const PolarisationArgs &a, bool obs, hipStream_t s);
@@ -290,6 +304,11 @@ hipError_t launch_gather_rows4(const float *src, const int64_t *index, uint64_t 
 // evt: bit 0 = sphere-exit event compiled in, bit 1 = disk-plane event, bit 2 = object spheres (then all three)
 hipError_t launch_trace(const TraceArgs &a, int method, int rhs, int evt, int grid, hipStream_t s, hipEvent_t *ev);
 hipError_t trace_occupancy(int method, int rhs, int evt, int *blocks_per_cu);
+// the disk-off trace that records every disk crossing (disk_crossings_kernel: one lane per ray, DP5(4), the Cartesian forms);
+// a.cross / n_cross / max_cross / cross_stride filled
+hipError_t launch_trace_crossings(const TraceArgs &a, int rhs, hipStream_t s);
+// ... its Kerr instance, in the Kerr translation unit; the caller runs launch_kerr_finalize on the end records afterwards
+hipError_t launch_trace_crossings_kerr(const TraceArgs &a, hipStream_t s);
 // Kerr: after the last pass of a call, Boyer-Lindquist end states -> Cartesian
 hipError_t launch_kerr_finalize(const TraceArgs &a, double *dir_out, hipStream_t s);
 // the Kerr instantiations live in their own translation unit (geodesic_kernels_kerr.hip: same source, same flags --

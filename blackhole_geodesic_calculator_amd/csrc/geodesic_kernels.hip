@@ -555,6 +555,20 @@ __device__ __forceinline__ void bl_position_to_cart(double a, const double q[3],
 // step's start enters it if the step ends inside, or if the chord between the step ends passes through
 // (closest point of the chord at s* = b / cc in (0, 1) with squared distance d0 - b^2 / cc < rho^2, written
 // without the division).
+// a Boyer-Lindquist state (q = (r, theta, phi), u its derivative) in the Cartesian frame the boundary speaks: position, then the
+// Jacobian of the embedding applied to u.  ONE definition for the finalize pass and for the crossing records.
+__device__ __forceinline__ void bl_record_to_cart(double a, const double q[3], const double u[3], double c[6])
+{
+    const double r = q[0], th = q[1], ph = q[2], u0 = u[0], u1 = u[1], u2 = u[2];
+    const double R = sqrt(r * r + a * a), st = sin(th), ct = cos(th), sp = sin(ph), cp = cos(ph);
+    c[0] = R * st * cp;
+    c[1] = R * st * sp;
+    c[2] = r * ct;
+    c[3] = (r / R * st * cp) * u0 + (R * ct * cp) * u1 + (-R * st * sp) * u2;
+    c[4] = (r / R * st * sp) * u0 + (R * ct * sp) * u1 + (R * st * cp) * u2;
+    c[5] = ct * u0 + (-r * st) * u1 + 0.0 * u2;
+}
+
 __device__ __forceinline__ bool sphere_candidate(const double sp[4], const double x0[3], const double x1[3], double &bb,
                                                  double &cc, bool &ends_inside)
 {
@@ -2707,12 +2721,9 @@ __global__ void __launch_bounds__(256) kerr_finalize_kernel(const TraceArgs A, d
         }
         return;
     }
-    const double r = e[0], th = e[1], ph = e[2], u0 = e[3], u1 = e[4], u2 = e[5], a = A.spin;
-    const double R = sqrt(r * r + a * a), st = sin(th), ct = cos(th), sp = sin(ph), cp = cos(ph);
-    const double c0 = R * st * cp, c1 = R * st * sp, c2 = r * ct;
-    const double c3 = (r / R * st * cp) * u0 + (R * ct * cp) * u1 + (-R * st * sp) * u2;
-    const double c4 = (r / R * st * sp) * u0 + (R * ct * sp) * u1 + (R * st * cp) * u2;
-    const double c5 = ct * u0 + (-r * st) * u1 + 0.0 * u2;
+    double c[6];
+    bl_record_to_cart(A.spin, e, e + 3, c);
+    const double c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3], c4 = c[4], c5 = c[5];
     if (dir_out) {
         dir_out[i * 3 + 0] = c3;
         dir_out[i * 3 + 1] = c4;
@@ -2731,6 +2742,53 @@ __global__ void __launch_bounds__(256) kerr_finalize_kernel(const TraceArgs A, d
 
 
 #endif  // BHG_TU_KERR
+
+// ------------------------------------------------------------------------------------------
+// One ATTEMPTED adaptive step of a lane-per-ray loop (the sampled-trajectory kernel, the disk-crossings kernel): rk.py:111-165
+// flattened as in the trace kernels, one attempt per call -- the step-size clamp and floor, the step budget, "already at
+// t_bound", the stages, the error norm and the controller, on the trace kernels' own helpers, so that the steps are theirs bit
+// for bit.  Returns DP54_ACCEPTED (xn, vn, a2 .. a7, r_new, t_new, h hold the step; h_abs the next step's size), DP54_REJECTED
+// (h_abs shrunk: attempt again from the same state) or the flag that ends the ray before the attempt.
+// ------------------------------------------------------------------------------------------
+constexpr uint32_t DP54_ACCEPTED = 0u, DP54_REJECTED = 0xFFFFFFFFu;
+template <int RHS>
+__device__ __forceinline__ uint32_t dp54_attempt(const TraceArgs &A, const Metric &met, const double x[3], const double v[3],
+                                                 const double a1[3], double t, double &h_abs, bool &rejected, uint32_t &n_att,
+                                                 uint32_t &n_acc, double &t_new, double &h, double a2[3], double a3[3], double a4[3],
+                                                 double a5[3], double a6[3], double a7[3], double xn[3], double vn[3], double &r_new)
+{
+    const double t_bound = A.lambda_end, max_step = A.max_step;
+    const double min_step = 10.0 * ulp_of(t);
+    if (!rejected) {
+        if (h_abs > max_step)
+            h_abs = max_step;
+        else if (h_abs < min_step)
+            h_abs = min_step;
+    }
+    if (h_abs < min_step) return BHG_FLAG_STEP_TOO_SMALL_;
+    if (n_att >= A.max_steps) return BHG_FLAG_MAX_STEPS_;
+    if (t == t_bound) return BHG_FLAG_REACHED_END_;
+    t_new = t + h_abs;
+    if (t_new - t_bound > 0.0) t_new = t_bound;
+    h = t_new - t;
+    h_abs = fabs(h);
+    dp54_stages<RHS>(x, v, a1, h, met, a2, a3, a4, a5, a6, a7, xn, vn, r_new);
+    n_att++;
+    double errsq = dp54_errsq(x, v, xn, vn, a1, a2, a3, a4, a5, a6, a7, h, A.rtol, A.atol);
+    if (!(r_new == r_new)) errsq = __builtin_nan("");
+    double fac = dp54_factor(errsq);
+    if (!(errsq < 1.0)) {
+        h_abs *= fmax(0.2, fac);
+        rejected = true;
+        return DP54_REJECTED;
+    }
+    fac = (errsq == 0.0) ? 10.0 : fmin(10.0, fac);
+    if (rejected) fac = fmin(1.0, fac);
+    h_abs *= fac;
+    rejected = false;
+    n_acc++;
+    return DP54_ACCEPTED;
+}
 
 // ------------------------------------------------------------------------------------------
 // Sampled trajectories: what calc_trajectory returns with nr_points_curve (RelativisticRenderEngine.py:
@@ -2753,7 +2811,7 @@ __global__ void __launch_bounds__(WAVE ? 256 : 64) trajectory_dp54_kernel(const 
     const uint32_t lane = threadIdx.x;
     const uint64_t i = WAVE ? (uint64_t)blockIdx.x : (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= A.n) return;
-    const double rtol = A.rtol, atol = A.atol, t_bound = A.lambda_end, max_step = A.max_step;
+    const double t_bound = A.lambda_end;
     double x[3], v[3], a1[3], h_abs, r_cur;
     Metric met;
     met.r_s = A.r_s;
@@ -2840,44 +2898,13 @@ __global__ void __launch_bounds__(WAVE ? 256 : 64) trajectory_dp54_kernel(const 
             n_att++;
             n_acc = n_att;
         } else {
-        const double min_step = 10.0 * ulp_of(t);
-        if (!rejected) {
-            if (h_abs > max_step)
-                h_abs = max_step;
-            else if (h_abs < min_step)
-                h_abs = min_step;
-        }
-        if (h_abs < min_step) {
-            flags = BHG_FLAG_STEP_TOO_SMALL_;
+        const uint32_t st = dp54_attempt<RHS>(A, met, x, v, a1, t, h_abs, rejected, n_att, n_acc, t_new, h, a2, a3, a4, a5, a6, a7, xn,
+                                              vn, r_new);
+        if (st == DP54_REJECTED) continue;
+        if (st != DP54_ACCEPTED) {
+            flags = st;
             break;
         }
-        if (n_att >= A.max_steps) {
-            flags = BHG_FLAG_MAX_STEPS_;
-            break;
-        }
-        if (t == t_bound) {
-            flags = BHG_FLAG_REACHED_END_;
-            break;
-        }
-        t_new = t + h_abs;
-        if (t_new - t_bound > 0.0) t_new = t_bound;
-        h = t_new - t;
-        h_abs = fabs(h);
-        dp54_stages<RHS>(x, v, a1, h, met, a2, a3, a4, a5, a6, a7, xn, vn, r_new);
-        n_att++;
-        double errsq = dp54_errsq(x, v, xn, vn, a1, a2, a3, a4, a5, a6, a7, h, rtol, atol);
-        if (!(r_new == r_new)) errsq = __builtin_nan("");
-        double fac = dp54_factor(errsq);
-        if (!(errsq < 1.0)) {
-            h_abs *= fmax(0.2, fac);
-            rejected = true;
-            continue;
-        }
-        fac = (errsq == 0.0) ? 10.0 : fmin(10.0, fac);
-        if (rejected) fac = fmin(1.0, fac);
-        h_abs *= fac;
-        rejected = false;
-        n_acc++;
         }
         // the step's interpolant: the dense output of the accepted DP5(4) step, or -- fixed steps -- its cubic Hermite interpolant
         Dense d;
@@ -3093,6 +3120,181 @@ hipError_t launch_trajectory(const TraceArgs &a, int rhs, int method, double *tr
         launch_trajectory_rhs<BHG_RHS_REDUCED_>(a, method, traj, n_valid, T, s);
     else
         launch_trajectory_rhs<BHG_RHS_CHRISTOFFEL_>(a, method, traj, n_valid, T, s);
+    return hipGetLastError();
+}
+#endif
+
+// ------------------------------------------------------------------------------------------
+// Disk crossings (bhg_trace_crossings_device): the ray is carried THROUGH the thin disk and every
+// plane crossing inside the annulus is recorded -- scipy's solve_ivp with the disk plane as a NON-terminal event g = z
+// (Kerr: cos theta), as oracle/scipy_reference.py has always run it.  The step sequence is that of the trace with the disk
+// off: disk_r_out plays no part in step control and a crossing never truncates a step; horizon, exit sphere and lambda_end
+// end the ray as they do there, and end / flags / n_steps / n_accepted are that trace's.
+// One LANE per ray, a plain loop: trajectory_dp54_kernel's step loop (the trace kernels' own stages, error norm,
+// controller, dense output and Brent search) without the sampling; the lane works its start record out itself.
+// Per accepted step: the sign-change rule of find_active_events (crossed_disk_plane: at most one root per step), the root
+// by brent_root on the step's dense output as settle_events finds it, counted when its cylindrical radius lies in
+// [disk_r_in, disk_r_out] and -- the step holding the ray's terminal event too -- when it is not later than that event's
+// root (scipy_reference's td <= te).  Record m of ray i is the dense-output state at the root, Cartesian (Kerr: converted
+// here, kerr_finalize_kernel's formulas), at cross[(m * cross_stride + i) * 6]; only the first max_cross are stored,
+// n_cross counts them all (saturating at 255); records a ray never reached are not written.
+// ------------------------------------------------------------------------------------------
+// (the trace kernels' register budgets: three waves per SIMD for the Cartesian forms, two for Kerr -- left to itself the compiler
+// takes 182 VGPRs for the Cartesian instances, two waves, and the Schwarzschild frames measure 13 % slower)
+template <int RHS>
+__global__ void __launch_bounds__(64, (RHS == BHG_RHS_KERR_BL_ ? BHG_KERR_WAVES_PER_SIMD : BHG_DP54_WAVES_PER_SIMD)) disk_crossings_kernel(const TraceArgs A)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= A.n) return;
+    const double t_bound = A.lambda_end;
+    const bool bl = RHS == BHG_RHS_KERR_BL_;
+    double x[3], v[3], a1[3], h_abs = 0.0, r_cur = 0.0;
+    Metric met;
+    met.r_s = A.r_s;
+    met.M = 0.5 * A.r_s;
+    met.a = A.spin;
+    met.E = met.L = 0.0;
+    for (int c = 0; c < 3; c++) {
+        v[c] = A.k0[i * 3 + c];
+        x[c] = A.x0 ? A.x0[i * 3 + c] : A.x0s[c];
+    }
+    {
+        const double cx[3] = {x[0], x[1], x[2]}, ck[3] = {v[0], v[1], v[2]};
+        double r0;
+        if (bl) {
+            kerr_cart_to_bl(met.a, met.M, A.mu2, x, v, met.E, met.L);
+            r0 = x[0];
+        } else {
+            r0 = sqrt(__builtin_fma(x[2], x[2], __builtin_fma(x[1], x[1], x[0] * x[0])));
+        }
+        if (r0 <= A.r_hor) {    // start inside: final at once, no crossings
+            A.n_cross[i] = 0;
+            store_result(A, (uint32_t)i, cx, ck, BHG_FLAG_START_INSIDE_ | BHG_FLAG_HIT_HORIZON_, 0, 0);
+            return;
+        }
+    }
+    initial_record<RHS, true>(A, met, x, v, a1, r_cur, h_abs);
+    double t = 0.0;
+    uint32_t n_att = 0, n_acc = 0, flags = 0, n_cross = 0;
+    bool rejected = false;
+    double xe[3] = {x[0], x[1], x[2]}, ve[3] = {v[0], v[1], v[2]};
+    for (;;) {
+        double a2[3], a3[3], a4[3], a5[3], a6[3], a7[3], xn[3], vn[3], r_new, t_new, h;
+        const uint32_t st = dp54_attempt<RHS>(A, met, x, v, a1, t, h_abs, rejected, n_att, n_acc, t_new, h, a2, a3, a4, a5, a6, a7, xn,
+                                              vn, r_new);
+        if (st == DP54_REJECTED) continue;
+        if (st != DP54_ACCEPTED) {
+            flags = st;
+            break;
+        }
+        const bool ev_h = ((r_cur - A.r_hor <= 0.0) && (r_new - A.r_hor >= 0.0)) ||
+                          ((r_cur - A.r_hor >= 0.0) && (r_new - A.r_hor <= 0.0));
+        const bool ev_e = (A.r_exit > 0.0) && (r_cur - A.r_exit <= 0.0) && (r_new - A.r_exit >= 0.0);
+        const bool ev_d = crossed_disk_plane<RHS>(x, xn);
+        uint32_t evflag = 0;
+        double t_stop = t_new;
+        if (ev_h || ev_e || ev_d) {
+            Dense d;
+            build_dense(d, t, h, x, v, a1, a2, a3, a4, a5, a6, a7);
+            auto g_z = [&](double tt) {
+                if (!bl) return dense_z(d, tt);
+                double q[3], sn, cs;
+                dense_pos(d, tt, q);
+                sincos_pi4(q[1], sn, cs);
+                return cs;
+            };
+            if (ev_h || ev_e) {
+                // the terminal events, settled as the trace kernels settle them (the earliest root wins, horizon before exit)
+                double best;
+                int obj;
+                evflag = settle_events<EVT_EXIT>(
+                    A, (ev_h ? EV_HORIZON : 0u) | (ev_e ? EV_EXIT : 0u), t, t_new, x, xn,
+                    [&](double tt, double Rr) { return dense_g(d, tt, Rr, bl); }, g_z,
+                    [&](double tt, double xq[3]) { dense_pos(d, tt, xq); }, bl, best, obj);
+                if (evflag) t_stop = best;
+            }
+            if (ev_d) {
+                const double root = brent_root(g_z, t, t_new);
+                double sx[3], sv[3];
+                dense_pos(d, root, sx);
+                // cylindrical radius of the crossing point, as settle_events takes it
+                double R;
+                if (bl) {
+                    double sn, cs;
+                    sincos_pi4(sx[1], sn, cs);
+                    R = sqrt(sx[0] * sx[0] + A.spin * A.spin) * fabs(sn);
+                } else {
+                    R = sqrt(sx[0] * sx[0] + sx[1] * sx[1]);
+                }
+                if (R >= A.disk_r_in && R <= A.disk_r_out && (!evflag || root <= t_stop)) {
+                    if (n_cross < (uint32_t)A.max_cross) {
+                        dense_dir(d, root, sv);
+                        if (bl) {
+                            double c[6];
+                            bl_record_to_cart(A.spin, sx, sv, c);
+                            for (int q = 0; q < 3; q++) {
+                                sx[q] = c[q];
+                                sv[q] = c[3 + q];
+                            }
+                        }
+                        double *o = A.cross + ((uint64_t)n_cross * A.cross_stride + i) * 6;
+                        reinterpret_cast<double2 *>(o)[0] = make_double2(sx[0], sx[1]);
+                        reinterpret_cast<double2 *>(o)[1] = make_double2(sx[2], sv[0]);
+                        reinterpret_cast<double2 *>(o)[2] = make_double2(sv[1], sv[2]);
+                    }
+                    n_cross++;
+                }
+            }
+            if (evflag) {
+                flags = evflag;
+                dense_pos(d, t_stop, xe);
+                dense_dir(d, t_stop, ve);
+                break;
+            }
+        }
+        for (int c = 0; c < 3; c++) {
+            xe[c] = xn[c];
+            ve[c] = vn[c];
+        }
+        if (t_new - t_bound >= 0.0) {
+            flags = BHG_FLAG_REACHED_END_;
+            break;
+        }
+        t = t_new;
+        r_cur = r_new;
+        for (int c = 0; c < 3; c++) {
+            x[c] = xn[c];
+            v[c] = vn[c];
+            a1[c] = a7[c];
+        }
+    }
+    if (flags & (BHG_FLAG_STEP_TOO_SMALL_ | BHG_FLAG_MAX_STEPS_)) {
+        for (int c = 0; c < 3; c++) {
+            xe[c] = x[c];
+            ve[c] = v[c];
+        }
+    }
+    A.n_cross[i] = (uint8_t)(n_cross < 255u ? n_cross : 255u);
+    store_result(A, (uint32_t)i, xe, ve, flags, n_att, n_acc);  // Kerr: still Boyer-Lindquist, finalised next
+}
+
+#if defined(BHG_TU_KERR)
+hipError_t launch_trace_crossings_kerr(const TraceArgs &a, hipStream_t s)
+{
+    if (a.n == 0) return hipSuccess;
+    BHG_LAUNCH((disk_crossings_kernel<BHG_RHS_KERR_BL_>), dim3((unsigned)((a.n + 63) / 64)), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+#elif !defined(BHG_TU_TIMELIKE)
+hipError_t launch_trace_crossings(const TraceArgs &a, int rhs, hipStream_t s)
+{
+    if (rhs == BHG_RHS_KERR_BL_) return launch_trace_crossings_kerr(a, s);
+    if (a.n == 0) return hipSuccess;
+    const dim3 grid((unsigned)((a.n + 63) / 64));
+    if (rhs == BHG_RHS_REDUCED_)
+        BHG_LAUNCH((disk_crossings_kernel<BHG_RHS_REDUCED_>), grid, dim3(64), 0, s, a);
+    else
+        BHG_LAUNCH((disk_crossings_kernel<BHG_RHS_CHRISTOFFEL_>), grid, dim3(64), 0, s, a);
     return hipGetLastError();
 }
 #endif

@@ -155,6 +155,9 @@ class DeviceFrame:
         self.disk_thermal = None      # _ffi.DiskThermal (set_disk_thermal) or None: the disk's colour of the scene
         self.object_textures = None   # set_object_textures: (device textures per sphere, rotations, modes, emission) or None
         self.object_motion = None     # _ffi.ObjectMotion (set_object_motion) or None: the spheres at rest
+        self.disk_layers = None       # _ffi.DiskLayers (set_disk_layers) or None: the opaque disk of the trace parameters
+        self.d_cross = None           # [max_crossings, n, 6] fp64 crossing records and
+        self.d_n_cross = None         # [n] uint8 crossing counts of the last crossings trace
 
     def _stream(self):
         return torch.cuda.current_stream(self.dev).cuda_stream
@@ -250,6 +253,29 @@ class DeviceFrame:
         else:
             self.object_motion = _ffi.make_object_motion(velocity, angular_velocity)
 
+    def set_disk_layers(self, max_crossings=None, opacity=1.0):
+        """Higher-order images of the disk (bhg_trace_crossings_device, bhg_shade_disk_layers_device):
+        trace() carries every ray THROUGH the disk and records its first max_crossings (1 .. 4) crossings, and shade() /
+        shade_f32() / render() composite them front to back, each crossing passing 1 - opacity of what lies behind it
+        (0 < opacity <= 1; 1 is the opaque disk).  Redshift, the observer and the thermal disk apply per layer.  Not with
+        object spheres, their textures or motion, nor shade_stokes() (ValueError there).  None: off -- every path the one
+        it was, bit for bit."""
+        self._traced = None      # what the last trace wrote belongs to the other kind of trace
+        if max_crossings is None:
+            self.disk_layers = None
+            return
+        if not 1 <= int(max_crossings) <= _ffi.MAX_CROSSINGS:
+            raise ValueError(f"max_crossings must be in [1, {_ffi.MAX_CROSSINGS}]")
+        if not 0.0 < float(opacity) <= 1.0:
+            raise ValueError("opacity must be in (0, 1]")
+        self.disk_layers = _ffi.make_disk_layers(max_crossings, opacity)
+
+    def _layers_check(self):
+        if (self.spheres is not None and len(self.spheres) > 0) or self.object_textures is not None or self.object_motion is not None:
+            raise ValueError("disk layers do not go with object spheres, object textures or object motion")
+        if self.disk is None:
+            raise ValueError("disk layers need a disk: set_disk() first")
+
     def set_object_textures(self, textures=None, rotations=None, modes=None, emission=None):
         """Textured, oriented and emissive object spheres (bhg_shade_scene_textured_device), per sphere of
         set_objects(): textures [h, w, 4] float32 (kept on the device; None: keep that sphere's current texture, white if it
@@ -308,11 +334,27 @@ class DeviceFrame:
             params = _copy_params(params)
             params.order_blocks = self.S
         self._params = params
+        origin = np.asarray(self.origin, dtype=np.float64)
+        if self.disk_layers is not None:
+            # the crossings trace: whole records, its own kernel; the kept initial steps are neither used nor touched
+            self._layers_check()
+            K = int(self.disk_layers.max_crossings)
+            if self.d_end is None:
+                self.d_end = torch.empty((self.n, 6), dtype=torch.float64, device=self.dev)
+            if self.d_cross is None or self.d_cross.shape[0] != K:
+                self.d_cross = torch.empty((K, self.n, 6), dtype=torch.float64, device=self.dev)
+                self.d_n_cross = torch.empty(self.n, dtype=torch.uint8, device=self.dev)
+            self._dir_traced, self._traced = False, None
+            self.ctx.trace_crossings_device(params, self.n, self.d_k0.data_ptr(), K, self.d_end.data_ptr(), self.d_cross.data_ptr(),
+                                            self.d_n_cross.data_ptr(), x0_shared=origin, d_flags=self.d_flags.data_ptr(),
+                                            d_n_steps=self.d_steps.data_ptr(), d_n_accepted=self.d_acc.data_ptr(),
+                                            stream=self._stream())
+            self._traced = "layers"
+            return
         has_obj = self.spheres is not None and len(self.spheres) > 0
         self._dir_traced = self.directions_only and not has_obj and self.disk is None and not (params.disk_r_out > 0.0)
         self._traced = "dir" if self._dir_traced else "end"
         # the initial steps belong to the rays and the origin they start from: recorded by the first trace, replayed after
-        origin = np.asarray(self.origin, dtype=np.float64)
         d_h, mode = self.start_steps.plan(self.n, self.dev, (_rays_key(self.d_k0), origin.tobytes()), params)
         if self._dir_traced:
             if self.d_dir is None:
@@ -358,6 +400,19 @@ class DeviceFrame:
         the polarisation (shade_stokes only), the thermal disk and the object motion as set, each None when off -- pol = None
         and none of the others is the textured call exactly."""
         form = self._shade_form()
+        if (form == "layers") != (self.disk_layers is not None):
+            raise RuntimeError("set_disk_layers() changed since the last trace: trace() again")
+        if form == "layers":
+            if pol is not None:
+                raise ValueError("disk layers have no Stokes images: shade_stokes() is not available with set_disk_layers()")
+            self._layers_check()
+            self.ctx.shade_disk_layers_device(self.d_end.data_ptr(), self.d_flags.data_ptr(), self.d_cross.data_ptr(),
+                                              self.d_n_cross.data_ptr(), self.P, self.S, self.scene(), self.disk_layers,
+                                              params=self._params, rs=self.redshift, obs=self.observer, th=self.disk_thermal,
+                                              x0_shared=self.origin, d_k0=self.d_k0.data_ptr(), d_rgba=d_rgba,
+                                              d_rgba_f32=d_rgba_f32, d_scatter=0 if scatter is None else scatter.data_ptr(),
+                                              stream=self._stream())
+            return
         has_obj = self.spheres is not None and len(self.spheres) > 0
         self.ctx.shade_scene_moving_device(self.d_end.data_ptr() if form == "end" else 0, self.d_flags.data_ptr(), self.P, self.S,
                                            self.scene(), self._params, self.redshift, self.observer,
@@ -375,6 +430,8 @@ class DeviceFrame:
     def shade_stokes(self):
         """(rgba [P, 4], qu [P, 6]) fp64: shade() and the per-pixel means of (Q_r, Q_g, Q_b, U_r, U_g, U_b) of the disk's
         polarisation (set_polarisation first)."""
+        if self.disk_layers is not None:
+            raise ValueError("disk layers have no Stokes images: shade_stokes() is not available with set_disk_layers()")
         if self.polarisation is None:
             raise RuntimeError("set_polarisation() first")
         if self.d_qu is None:

@@ -64,7 +64,7 @@ class GeodesicIntegratorSchwarzschild:
 
     # ------------------------------------------------------------------------------------
     def trace(self, k0, x0, max_step=np.inf, curve_end=50.0, r_exit=0.0, disk=None, spheres=None, redshift=None,
-              polarisation=None, disk_thermal=None):
+              polarisation=None, disk_thermal=None, disk_crossings=None):
         """Batched solve.  k0[N,3] (or [...,3]); x0[3] shared origin or same leading shape as k0.
         r_exit: outward sphere-exit radius (Limited engine's ray_trace, Limited...py:273-278);
         disk=(R_in, R_out): thin disk in z = 0, first crossing inside the annulus ends the ray with
@@ -94,7 +94,17 @@ class GeodesicIntegratorSchwarzschild:
                                        redshifted blackbody the camera sees, weighed per channel (0 at and inside r_ms; NaN for
                                        NaN rays, 0 for every ray that is not a disk ray; bhg_disk_thermal_host; DESIGN.md
                                        section 13)
+        disk_crossings=K (1 .. 4, with disk=; DP5(4), null rays, no spheres): the ray is carried THROUGH the disk and every
+        crossing inside the annulus is recorded (bhg_trace_crossings).  ray_end, flags, n_steps and
+        n_accepted are then those of the trace with the disk off (no ray has FLAG_HIT_DISK), and the dict also has
+            n_cross[...]               uint8, the ray's crossings (all of them, saturating at 255)
+            disk_cross[K, ..., 6]      the first K crossing records in order, position and direction; NaN where a ray has none
+        and redshift=, polarisation= and disk_thermal= return their arrays per LAYER -- g[K, ...], evpa[K, ...], ...,
+        thermal_rgb[K, ..., 3] -- each the per-ray call on disk_cross[m], NaN where a ray has no layer m.
         """
+        if disk_crossings is not None:
+            return self._trace_crossings(k0, x0, max_step, curve_end, r_exit, disk, spheres, redshift, polarisation, disk_thermal,
+                                         int(disk_crossings))
         k0 = np.asarray(k0, dtype=np.float64)
         lead = k0.shape[:-1]
         k0f = k0.reshape(-1, 3)
@@ -132,6 +142,57 @@ class GeodesicIntegratorSchwarzschild:
             th = _ffi.make_disk_thermal(**disk_thermal)
             t_em, rgb = self._ctx.disk_thermal(k0f, x0f, self.params(max_step, curve_end, r_exit, disk), th, None, flags, end)
             out["t_em"], out["thermal_rgb"] = t_em.reshape(lead), rgb.reshape(lead + (3,))
+        return out
+
+    def _trace_crossings(self, k0, x0, max_step, curve_end, r_exit, disk, spheres, redshift, polarisation, disk_thermal, K):
+        """trace(disk_crossings=K): the crossings trace, then the per-ray calls layer by layer on cross[m] with the flag array
+        n_cross > m ? FLAG_HIT_DISK : FLAG_HIT_HORIZON."""
+        if spheres is not None:
+            raise ValueError("disk_crossings does not go with object spheres")
+        if disk is None:
+            raise ValueError("disk_crossings needs disk=(R_in, R_out)")
+        if redshift is not None and redshift.get("object_motion") is not None:
+            raise ValueError("disk_crossings does not go with object motion")
+        k0 = np.asarray(k0, dtype=np.float64)
+        lead = k0.shape[:-1]
+        k0f = k0.reshape(-1, 3)
+        x0 = np.asarray(x0, dtype=np.float64)
+        x0f = x0 if x0.ndim == 1 else x0.reshape(-1, 3)
+        p = self.params(max_step, curve_end, r_exit, disk)
+        end, flags, steps, acc, cross, n_cross = self._ctx.trace_crossings(k0f, x0f, p, K)
+        out = {
+            "ray_end": end.reshape(lead + (6,)),
+            "ray_blackhole_hit": ((flags & _ffi.FLAG_HIT_HORIZON) != 0).astype(np.uint8).reshape(lead),
+            "flags": flags.reshape(lead),
+            "n_steps": steps.reshape(lead),
+            "n_accepted": acc.reshape(lead),
+            "n_cross": n_cross.reshape(lead),
+            "disk_cross": cross.reshape((K,) + lead + (6,)),
+        }
+        extras = {}
+        if redshift is not None:
+            rs = _ffi.make_redshift(apply=(), disk_sense=redshift.get("disk_sense", 1))
+            extras["g"] = lambda fl, e: (self._ctx.redshift(k0f, x0f, p, rs, fl, e),)
+        if polarisation is not None:
+            pol = _ffi.make_polarisation(**polarisation)
+            extras["evpa", "pol_degree", "mu_em"] = lambda fl, e: self._ctx.polarisation(k0f, x0f, p, pol, None, fl, e)
+        if disk_thermal is not None:
+            th = _ffi.make_disk_thermal(**disk_thermal)
+            extras["t_em", "thermal_rgb"] = lambda fl, e: self._ctx.disk_thermal(k0f, x0f, p, th, None, fl, e)
+        for names, call in extras.items():
+            names = (names,) if isinstance(names, str) else names
+            per_layer = [[] for _ in names]
+            for m in range(K):
+                has = n_cross > m
+                fl = np.where(has, _ffi.FLAG_HIT_DISK, _ffi.FLAG_HIT_HORIZON).astype(np.uint8)
+                # (the records a ray does not have are NaN in cross: the calls never read the record of a horizon-flagged ray)
+                for dst, arr in zip(per_layer, call(fl, np.ascontiguousarray(cross[m]))):
+                    arr = np.array(arr, dtype=np.float64)
+                    arr[~has] = np.nan
+                    dst.append(arr)
+            for name, arrs in zip(names, per_layer):
+                a = np.stack(arrs)
+                out[name] = a.reshape((K,) + lead + a.shape[2:])
         return out
 
     # ------------------------------------------------------------------------------------

@@ -64,7 +64,9 @@ extern "C" {
                                   BHG_OBJECT_MOTION (bhg_redshift_motion_device / _host, bhg_shade_scene_moving_device,
                                   bhg_frame_set_object_motion, bhg_object_motion_size, struct bhg_object_motion);
                                   BHG_START_STEPS (bhg_trace_start_device, bhg_start_steps_match, BHG_START_*: the rays' initial
-                                  steps kept across calls on unchanged rays).
+                                  steps kept across calls on unchanged rays);
+                                  BHG_DISK_CROSSINGS (bhg_trace_crossings_device, bhg_trace_crossings, bhg_shade_disk_layers_device,
+                                  bhg_disk_layers_size, struct bhg_disk_layers, BHG_MAX_CROSSINGS: higher-order disk images).
                                9: redshift -- bhg_redshift_device / _host, bhg_shade_scene_redshift_device, bhg_frame_set_redshift,
                                   bhg_redshift_size, struct bhg_redshift;
                                   nothing of ABI 8 changed.
@@ -786,6 +788,60 @@ int bhg_shade_scene_moving_device(bhg_context *ctx, const double *d_end, const d
  * bhg_shade_scene_moving_device).  NULL: off, the frame as without it.  Checked against the scene's spheres here (those set
  * at this call) and against the scene and the trace parameters at every render. */
 int bhg_frame_set_object_motion(bhg_frame *frame, const bhg_object_motion *mo);
+
+/* --- disk crossings and layers: higher-order images of the disk (within ABI 10) ---------------------
+ * The disk of bhg_params is opaque: a ray ends at its first plane crossing inside the annulus.  The crossings trace carries
+ * the ray THROUGH the disk instead and records every crossing inside the annulus -- scipy's solve_ivp with the disk plane as
+ * a non-terminal event g = z (Kerr: cos theta):
+ *   - the step sequence is that of the same call with the disk off: disk_r_out plays no part in step control, a crossing
+ *     never truncates a step; horizon, exit sphere and lambda_end end the ray as they do there, and end / flags / n_steps /
+ *     n_accepted are the disk-off trace's (no ray carries BHG_FLAG_HIT_DISK);
+ *   - an accepted step whose ends lie on both sides of the plane (scipy's sign-change rule: at most one root per step) has
+ *     its root found by the trace kernels' Brent search on the step's dense output; the crossing counts when its cylindrical
+ *     radius lies in [disk_r_in, disk_r_out] and, in the step that holds the ray's terminal event, when it is not later than
+ *     that event;
+ *   - d_n_cross [n] uint8 counts every crossing (saturating at 255); d_cross [max_crossings][n][6] fp64 holds the first
+ *     max_crossings (1 .. BHG_MAX_CROSSINGS) records: the dense-output state at the root, position then direction,
+ *     Cartesian.  Records a ray never reached are left as they were.  Rays that start inside have n_cross = 0.
+ * The layout is order-major: d_cross + m * n * 6 is an [n][6] end array that bhg_redshift_device, bhg_polarisation_device and
+ * bhg_disk_thermal_device take as it stands, with the flag array n_cross > m ? BHG_FLAG_HIT_DISK : BHG_FLAG_HIT_HORIZON.
+ * Covered: BHG_METHOD_DP54 with every rhs_form, null rays, no object spheres (one lane per ray; the persistent trace kernels
+ * are not involved).  Refused (BHG_E_INVALID), before the context: BHG_METHOD_RK4, time_like = 1, disk_r_out = 0,
+ * max_crossings outside [1, BHG_MAX_CROSSINGS].  Otherwise bhg_trace_device's conventions: d_flags / d_n_steps / d_n_accepted
+ * may be NULL, asynchronous on stream, calls of more than 2^26 rays are split into launches. */
+#define BHG_DISK_CROSSINGS 1
+#define BHG_MAX_CROSSINGS 4
+int bhg_trace_crossings_device(bhg_context *ctx, const bhg_params *p, const double *x0_shared, const double *d_x0,
+                               const double *d_k0, size_t n, int32_t max_crossings, double *d_end, uint8_t *d_flags,
+                               uint32_t *d_n_steps, uint32_t *d_n_accepted, double *d_cross, uint8_t *d_n_cross, void *stream);
+/* bhg_trace_crossings_device on host arrays (x0 [3] with x0_is_shared != 0, else [n][3]; flags, n_steps, n_accepted may be
+ * NULL).  Blocking.  cross is read first, so that records no ray reached come back as the caller left them. */
+int bhg_trace_crossings(bhg_context *ctx, const bhg_params *p, const double *x0, int x0_is_shared, const double *k0, size_t n,
+                        int32_t max_crossings, double *end, uint8_t *flags, uint32_t *n_steps, uint32_t *n_accepted,
+                        double *cross, uint8_t *n_cross);
+/* The optically thin disk: every crossing passes the fraction T = 1 - opacity of what lies behind it, 0 < opacity <= 1 (1: the
+ * opaque disk -- layer 0 alone, nothing behind it is looked at). */
+typedef struct bhg_disk_layers {
+    int32_t max_crossings;   /* layers in d_cross, 1 .. BHG_MAX_CROSSINGS */
+    int32_t pad;
+    double opacity;
+} bhg_disk_layers;
+size_t bhg_disk_layers_size(void);
+/* The layered shade of a crossings trace (d_end or d_end_dir, d_flags, d_cross, d_n_cross of S * n_pixels rays, ray
+ * s * n_pixels + p = sample s of pixel p): per ray, with w = 1,
+ *     for m < min(n_cross, max_crossings), while w != 0:   rgb += w C(cross[m]);   w *= T
+ *     if w != 0 and the ray did not end in the hole:        rgb += w sky(exit direction)
+ * then the pixel's samples are summed in sample order and divided by S.  C is the disk colour of
+ * bhg_shade_scene_redshift_observer_device for a disk ray with that end record (rs, obs may be NULL) or, th given, of
+ * bhg_shade_scene_thermal_device; the sky is weighted as rs says.  The scene needs a disk and no object spheres (refused
+ * otherwise, as are the settings those calls refuse, a max_crossings outside [1, BHG_MAX_CROSSINGS] and an opacity outside
+ * (0, 1] -- all before the context). */
+int bhg_shade_disk_layers_device(bhg_context *ctx, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
+                                 const double *d_cross, const uint8_t *d_n_cross, size_t n_pixels, int32_t samples,
+                                 const bhg_scene *scene, const bhg_params *p, const bhg_redshift *rs, const bhg_observer *obs,
+                                 const double *x0_shared, const double *d_k0, double *d_rgba, float *d_rgba_f32,
+                                 const int64_t *d_scatter, const bhg_disk_thermal *th, const bhg_disk_layers *layers,
+                                 void *stream);
 
 /* Acceleration probe: acc[n][3] = -Gamma^i_{mu nu} k^mu k^nu at (x[n][3], k[n][3]); host buffers.
  * Lets tests compare the device RHS with the oracle's term by term.  With rhs_form = BHG_RHS_KERR_BL the triples
