@@ -233,7 +233,7 @@ struct bhg_context {
     size_t pin_in_bytes = 0, pin_out_bytes = 0;
     hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_k[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
     HostCopyPool pool;
-    // per-ray workspace of the trace passes (prepare / event / resume records, internal flags)
+    // per-ray workspace of a trace call: the flags and step counts its caller does not want
     void *d_ws = nullptr;
     size_t d_ws_bytes = 0;
     void *d_endws = nullptr;   // end records as workspace of direction-only calls
@@ -243,7 +243,7 @@ struct bhg_context {
     // optional per-pass timing (bhg_set_profiling)
     bool profiling = false;
     bool ev_valid = false;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around prepare | trace | (Kerr) finalize
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // 0, 1 back to back | trace | 2 | (Kerr) finalize | 3
     bool ev_post = false;                                     // the last profiled call had a finalize pass
 };
 
@@ -327,6 +327,34 @@ bool is_pinned_range(const void *p, size_t bytes, void **dev_out)
 // validate_tol (scipy _ivp/common.py:44-51): an rtol below 100 eps is raised to 100 eps -- scipy warns and carries on, and so
 // does every solve the reference runs through solve_ivp (README.md:196)
 inline double scipy_rtol(double rtol) { return rtol < 100.0 * DBL_EPSILON ? 100.0 * DBL_EPSILON : rtol; }
+
+// What every kernel call takes from bhg_params (validated) and the object spheres: the integration settings, the metric, the
+// event radii.  Returns the kernels' right-hand-side id: the time-like Christoffel form is one of its own (the Kerr kernels take
+// the norm at the start).  The rays, the outputs, min_step_cap, the work order and the counters are the caller's.
+int fill_trace_args(bhg::TraceArgs &a, const bhg_params *p, const double *spheres, int32_t n_spheres)
+{
+    a.r_s = p->r_s;
+    a.lambda_end = p->lambda_end;
+    a.max_step = p->max_step;
+    a.rtol = scipy_rtol(p->rtol);
+    a.atol = p->atol;
+    a.h_fixed = p->h_fixed;
+    a.r_exit = p->r_exit;
+    a.disk_r_in = p->disk_r_in;
+    a.disk_r_out = p->disk_r_out;
+    a.spin = p->spin;
+    a.mu2 = p->time_like ? 1.0 : 0.0;
+    a.r_hor = p->r_s;
+    if (p->rhs_form == BHG_RHS_KERR_BL) {
+        const double M = 0.5 * p->r_s;
+        a.r_hor = (M + std::sqrt(M * M - p->spin * p->spin)) * (1.0 + BHG_KERR_HORIZON_MARGIN);
+    }
+    a.max_steps = p->max_steps ? p->max_steps : (1u << 20);
+    a.n_spheres = n_spheres;
+    for (int j = 0; j < n_spheres; j++)
+        for (int q = 0; q < 4; q++) a.spheres[j][q] = spheres[4 * j + q];
+    return (p->time_like && p->rhs_form == BHG_RHS_CHRISTOFFEL) ? bhg::BHG_RHS_CHRISTOFFEL_TL_ : p->rhs_form;
+}
 
 int validate(const bhg_params *p)
 {
@@ -1091,8 +1119,6 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres,
     //   n_steps / n_accepted [n] u32 when the caller does not want them (the kernels never test these pointers)
     const bool has_exit = p->r_exit > 0.0;
     const bool kerr = p->rhs_form == BHG_RHS_KERR_BL;
-    // the kernels' right-hand-side id: the time-like Christoffel form is one of its own (the Kerr kernels take the norm at the start)
-    const int rhs_id = (p->time_like && p->rhs_form == BHG_RHS_CHRISTOFFEL) ? bhg::BHG_RHS_CHRISTOFFEL_TL_ : p->rhs_form;
     const size_t sz_flags = d_flags ? 0 : ((n + 7) & ~size_t(7));
     const size_t sz_u32 = n * sizeof(uint32_t);
     const size_t sz_steps = !d_n_steps ? sz_u32 : 0;
@@ -1131,23 +1157,7 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres,
         a.x0s[1] = x0_shared[1];
         a.x0s[2] = x0_shared[2];
     }
-    a.r_s = p->r_s;
-    a.lambda_end = p->lambda_end;
-    a.max_step = p->max_step;
-    a.rtol = scipy_rtol(p->rtol);
-    a.atol = p->atol;
-    a.h_fixed = p->h_fixed;
-    a.r_exit = p->r_exit;
-    a.disk_r_in = p->disk_r_in;
-    a.disk_r_out = p->disk_r_out;
-    a.spin = p->spin;
-    a.mu2 = p->time_like ? 1.0 : 0.0;
-    a.r_hor = p->r_s;
-    if (p->rhs_form == BHG_RHS_KERR_BL) {
-        const double M = 0.5 * p->r_s;
-        a.r_hor = (M + std::sqrt(M * M - p->spin * p->spin)) * (1.0 + BHG_KERR_HORIZON_MARGIN);
-    }
-    a.max_steps = p->max_steps ? p->max_steps : (1u << 20);
+    const int rhs_id = fill_trace_args(a, p, spheres, n_spheres);
     a.min_step_cap = 40.0 * std::nextafter(std::fmax(p->lambda_end, 1.0), INFINITY) * 2.220446049250313e-16;
     // (lambda_end = 0: every ray is "already at t_bound" at its first step -- the rare-path prologue handles that, and an
     // infinite cap sends every lane there)
@@ -1165,9 +1175,6 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres,
     // the rays' initial steps kept by their owner (the DP5(4) kernels' queue fill; RK4 has none and never looks)
     a.start_h = start_mode != BHG_START_NONE ? d_start_steps : nullptr;
     a.start_mode = start_mode;
-    a.n_spheres = n_spheres;
-    for (int j = 0; j < n_spheres; j++)
-        for (int q = 0; q < 4; q++) a.spheres[j][q] = spheres[4 * j + q];
     // kernel variant: bit 0 exit sphere, bit 1 disk, bit 2 objects.  With objects: 5 = exit sphere and no disk (the
     // orbiting-sphere frames), otherwise 7, which tests for the exit sphere and the disk at run time
     int evt = n_spheres > 0 ? ((has_exit && !(p->disk_r_out > 0.0)) ? 5 : 7)
@@ -2412,14 +2419,10 @@ int bhg_trajectory_objects(bhg_context *c, const bhg_params *p, const double *sp
     if (rc != BHG_OK) return rc;
     rc = ensure(&c->d_out, &c->d_out_bytes, off_obj + n + 64);
     if (rc != BHG_OK) return rc;
-    // up to 2048 rays the kernel runs one wave per ray, prepares the ray itself and fills what it never reaches with NaN:
-    // no prepare records, no memset; the direction of a ONE-ray call (the engine's literal call) rides in the kernel arguments
+    // up to 2048 rays the kernel runs one wave per ray and fills what the ray never reaches with NaN: no memset; the direction
+    // of a ONE-ray call (the engine's literal call) rides in the kernel arguments
     const bool wave = bhg::trajectory_wave_per_ray(n);
     const bool one = n == 1 && x0_is_shared;
-    if (!wave) {
-        rc = ensure(&c->d_ws, &c->d_ws_bytes, n * 8 * sizeof(double) + 64);
-        if (rc != BHG_OK) return rc;
-    }
     double *d_k0 = one ? nullptr : (double *)c->d_in, *d_x0 = x0_is_shared ? nullptr : (double *)c->d_in + n * 3;
     char *o = (char *)c->d_out;
     hipStream_t s = c->stream;
@@ -2460,7 +2463,6 @@ int bhg_trajectory_objects(bhg_context *c, const bhg_params *p, const double *sp
     a.k0 = d_k0;
     a.x0 = d_x0;
     a.end = (double *)(os + off_end);
-    a.ws = wave ? nullptr : (double *)c->d_ws;
     if (one) {
         a.k0s[0] = k0[0];
         a.k0s[1] = k0[1];
@@ -2477,32 +2479,10 @@ int bhg_trajectory_objects(bhg_context *c, const bhg_params *p, const double *sp
         a.x0s[1] = x0[1];
         a.x0s[2] = x0[2];
     }
-    a.r_s = p->r_s;
-    a.lambda_end = p->lambda_end;
-    a.max_step = p->max_step;
-    a.rtol = scipy_rtol(p->rtol);
-    a.atol = p->atol;
-    a.h_fixed = p->h_fixed;
-    a.r_exit = p->r_exit;
-    a.disk_r_in = p->disk_r_in;
-    a.disk_r_out = p->disk_r_out;
-    a.spin = p->spin;
-    a.mu2 = p->time_like ? 1.0 : 0.0;
-    a.r_hor = p->r_s;
-    a.ws_stride = 6;
-    if (p->rhs_form == BHG_RHS_KERR_BL) {
-        const double M = 0.5 * p->r_s;
-        a.r_hor = (M + std::sqrt(M * M - p->spin * p->spin)) * (1.0 + BHG_KERR_HORIZON_MARGIN);
-        a.ws_stride = 8;
-    }
-    a.max_steps = p->max_steps ? p->max_steps : (1u << 20);
+    const int rhs_id = fill_trace_args(a, p, spheres, n_spheres);
     a.min_step_cap = 0.0;
-    a.n_spheres = n_spheres;
-    for (int j = 0; j < n_spheres; j++)
-        for (int q = 0; q < 4; q++) a.spheres[j][q] = spheres[4 * j + q];
     a.object_id = with_obj ? (int8_t *)(os + off_obj) : nullptr;
-    HIP_TRY(bhg::launch_trajectory(a, (p->time_like && p->rhs_form == BHG_RHS_CHRISTOFFEL) ? bhg::BHG_RHS_CHRISTOFFEL_TL_ : p->rhs_form, p->method,
-                                   d_traj, (uint32_t *)(os + off_nv), n_points, s));
+    HIP_TRY(bhg::launch_trajectory(a, rhs_id, p->method, d_traj, (uint32_t *)(os + off_nv), n_points, s));
     const size_t total = with_obj ? off_obj + n : off_flags + n;
     if (object_id && !with_obj) std::memset(object_id, 0xFF, n);      // (no spheres: no ray ends on one)
     if (direct) {

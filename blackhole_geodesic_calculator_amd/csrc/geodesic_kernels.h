@@ -68,10 +68,7 @@ struct TraceArgs {
     // ---- chunk 2: parking (in the step loop's event branch), then the rare paths
     double *end_dir;             // nullptr, or [n][3]: FINAL states are written as their direction half only, here (end then
                                  // only holds the parked / resume records of rays that need them: a workspace)
-    double *ws;                  // trajectory calls only (nullptr for a trace): [n][ws_stride] records {a0, h0, r0, 0, E, L}
-                                 // the prepare pass writes and the trajectory kernel starts from
     uint32_t max_steps;
-    int32_t ws_stride;           // trajectory calls: doubles per record in ws, 6, or 8 for Kerr ({E, L} appended)
     int32_t n_spheres;           // object spheres inside the curved region (Schwarzschild forms only)
     const double *k0;            // [n][3]
     const double *x0;            // [n][3] or nullptr -> x0s
@@ -86,8 +83,8 @@ struct TraceArgs {
     unsigned long long *diag;    // diagnostic builds only (BHG_DIAG): [grid][8] per-wave stamps
     uint32_t dbg_idx;            // diagnostic builds: ray whose controller trace is logged
     double spheres[BHG_MAX_SPHERES_][4];  // {cx, cy, cz, radius}, BH-centred
-    // the rays' initial steps kept across calls (DP5(4) trace kernels only, read in the queue fill; the RK4, prepare and
-    // trajectory kernels never look): last, so that no other member moves
+    // the rays' initial steps kept across calls (DP5(4) trace kernels only, read in the queue fill; the RK4 and the
+    // lane-per-ray kernels never look): last, so that no other member moves
     double *start_h;             // [n] or nullptr
     int32_t start_mode;          // BHG_START_*_
     // disk crossings (disk_crossings_kernel alone; no other kernel looks): last, so that no other member moves
@@ -300,7 +297,8 @@ hipError_t launch_disk_thermal(const ThermalArgs &a, hipStream_t s);
 hipError_t launch_split_end(const double *end, uint64_t n, double *loc, double *dir, hipStream_t s);
 hipError_t launch_gather_rows4(const float *src, const int64_t *index, uint64_t n, float *dst, hipStream_t s);
 
-// ev: nullptr, or 3 events recorded around prepare | trace on stream s (no prepare launch runs: the first two are back to back)
+// ev: nullptr, or 3 events on stream s: two back to back in front of the trace launch (every kernel starts its rays itself, no
+// pass runs ahead of it), one behind it
 // evt: bit 0 = sphere-exit event compiled in, bit 1 = disk-plane event, bit 2 = object spheres (then all three)
 hipError_t launch_trace(const TraceArgs &a, int method, int rhs, int evt, int grid, hipStream_t s, hipEvent_t *ev);
 hipError_t trace_occupancy(int method, int rhs, int evt, int *blocks_per_cu);
@@ -321,9 +319,9 @@ hipError_t launch_trace_timelike(const TraceArgs &a, int method, int grid, hipSt
 hipError_t trace_occupancy_timelike(int method, int *blocks_per_cu);
 hipError_t launch_trajectory_timelike(const TraceArgs &a, int method, double *traj, uint32_t *n_valid, uint32_t T, hipStream_t s);
 hipError_t launch_accel_timelike(const double *x, const double *k, double r_s, uint64_t n, double *acc, hipStream_t s);
-// prepare + one-lane-per-ray sampled trajectories (+ Kerr finalize); traj [n][6][T], n_valid [n]
+// sampled trajectories, one lane or one wave per ray (+ Kerr finalize); traj [n][6][T], n_valid [n]
 hipError_t launch_trajectory(const TraceArgs &a, int rhs, int method, double *traj, uint32_t *n_valid, uint32_t T, hipStream_t s);
-// does a trajectory call of n rays run one wave per ray (the kernel then prepares the ray itself and NaN-fills the tail)?
+// does a trajectory call of n rays run one wave per ray (the kernel then NaN-fills what a ray never reaches; the lane shape wants the block preset)?
 bool trajectory_wave_per_ray(uint64_t n);
 // rhs = Kerr: x, k and acc are Boyer-Lindquist (r, theta, phi) triples, E and L fixed by the null condition at each point
 hipError_t launch_accel(const double *x, const double *k, double r_s, double spin, double mu2, uint64_t n, double *acc, int rhs,

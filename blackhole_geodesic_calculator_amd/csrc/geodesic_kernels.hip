@@ -175,6 +175,18 @@ struct Metric {
     double E, L;  // per ray: E = -k_t, L = k_phi
 };
 
+// the metric of a call; the Killing constants are the ray's to fill in
+__device__ __forceinline__ Metric metric_of(double r_s, double spin)
+{
+    Metric m;
+    m.r_s = r_s;
+    m.M = 0.5 * r_s;
+    m.a = spin;
+    m.E = m.L = 0.0;
+    return m;
+}
+__device__ __forceinline__ Metric metric_of(const TraceArgs &A) { return metric_of(A.r_s, A.spin); }
+
 // Kerr in Boyer-Lindquist coordinates: x = (r, theta, phi), k = d/dlambda of those.  The body is
 // generated by tools/gen_kerr_rhs.py from the sympy-derived Christoffel symbols (the reference's
 // method, README.md:133-135, :182-184, applied to the Kerr metric of its goals list, README.md:218).
@@ -1000,8 +1012,8 @@ __device__ __forceinline__ uint64_t take_fetch(unsigned long long b, uint32_t sl
 }
 
 // f0 = a(x0, k0), r0 and, for DP5(4), scipy's initial step (select_initial_step, common.py:68-134, order = 4)
-// for one ray that starts outside the hole.  Used converged: by the prepare pass, or by all 64 lanes of a
-// wave while it fills its ray queue.
+// for one ray that starts outside the hole.  Used converged: by all 64 lanes of a wave while it fills its ray queue, or by
+// the lanes of a lane-per-ray kernel at its top (start_ray).
 template <int RHS, bool ADAPTIVE>
 __device__ __forceinline__ void initial_record(const TraceArgs &A, const Metric &met, const double px[3],
                                                const double pk[3], double pa[3], double &pr, double &ph)
@@ -1944,10 +1956,7 @@ __device__ __forceinline__ void drain_short(const TraceArgs &A, LDS &Q, Wave &W,
     int outcome = PARK_ENDED;
     Lane R;
     if (mine) {
-        Metric met;
-        met.r_s = A.r_s;
-        met.M = 0.5 * A.r_s;
-        met.a = A.spin;
+        Metric met = metric_of(A);
         met.E = P.E;
         met.L = P.Lz;
         if (ADAPTIVE)
@@ -2009,10 +2018,7 @@ __device__ __forceinline__ void drain_long(const TraceArgs &A, LDS &Q, Wave &W, 
         s = Q.ev_list[NSLOT - W.n_evB + (int)lane];
         SLOT_CHECK(Q, s, 3, 4, "drain_long take");
         const uint32_t kind = slot_get<RHS>(Q.slot[s], P);
-        Metric met;
-        met.r_s = A.r_s;
-        met.M = 0.5 * A.r_s;
-        met.a = A.spin;
+        Metric met = metric_of(A);
         met.E = P.E;
         met.L = P.Lz;
         outcome = dp54_resolve_long<RHS, EVT>(A, met, P, kind, R);
@@ -2273,11 +2279,7 @@ __global__ void __launch_bounds__(64, (RHS == BHG_RHS_KERR_BL_ ? BHG_KERR_WAVES_
     // went to scratch and came back with two scratch loads per iteration.)
     const double min_step_cap = A.min_step_cap;
     const uint32_t max_steps = A.max_steps;
-    Metric met;
-    met.r_s = A.r_s;
-    met.M = 0.5 * A.r_s;
-    met.a = A.spin;
-    met.E = met.L = 0.0;
+    Metric met = metric_of(A);
     // (Round 3 held the scalars every Kerr step reads in VGPRs, because that kernel spilled 67 SGPRs and fetched them back
     // with v_readlane ~130 times per iteration.  With the rare paths' arguments read from the kernarg segment at their use
     // sites -- kernarg_base() -- no trace kernel spills an SGPR any more, and the plain form measures 0.3 % faster.)
@@ -2516,11 +2518,7 @@ __global__ void __launch_bounds__(64) trace_rk4_kernel(const TraceArgs A)
     __shared__ LDS Q;
     const uint32_t lane = threadIdx.x;
     const double r_s = A.r_hor, t_bound = A.lambda_end, hf = A.h_fixed;  // r_s: horizon EVENT radius
-    Metric met;
-    met.r_s = A.r_s;
-    met.M = 0.5 * A.r_s;
-    met.a = A.spin;
-    met.E = met.L = 0.0;
+    Metric met = metric_of(A);
 
     Lane L;
 #pragma unroll
@@ -2600,84 +2598,16 @@ __global__ void __launch_bounds__(64) trace_rk4_kernel(const TraceArgs A)
     }
 }
 
-// ------------------------------------------------------------------------------------------
-// Prepare pass of the lane-per-ray trajectory calls (converged, one thread per ray): start-inside test, f0 = a(x0, k0),
-// r0 and, for DP5(4), scipy's initial step (common.py:68-134, order = 4).  Record ws[i] = {a0, h0, r0} (A.ws_stride doubles
-// apart, {E, L} appended for Kerr); h0 = -1 marks a ray that is already final (start inside the hole).  The trace kernels
-// work the same records out in their queue fill (fill_batch).
-// ------------------------------------------------------------------------------------------
-template <int RHS, bool ADAPTIVE>
-__global__ void __launch_bounds__(256) prepare_kernel(const TraceArgs A)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= A.n) return;
-    double px[3], pk[3], pa[3], pr = 0.0, ph = 0.0;
-    pk[0] = A.k0[i * 3 + 0];
-    pk[1] = A.k0[i * 3 + 1];
-    pk[2] = A.k0[i * 3 + 2];
-    if (A.x0) {
-        px[0] = A.x0[i * 3 + 0];
-        px[1] = A.x0[i * 3 + 1];
-        px[2] = A.x0[i * 3 + 2];
-    } else {
-        px[0] = A.x0s[0];
-        px[1] = A.x0s[1];
-        px[2] = A.x0s[2];
-    }
-    double *w = A.ws + i * (uint64_t)A.ws_stride;
-    if (A.object_id) A.object_id[i] = (int8_t)-1;
-    Metric met;
-    met.r_s = A.r_s;
-    met.M = 0.5 * A.r_s;
-    met.a = A.spin;
-    met.E = met.L = 0.0;
-    double cx[3] = {px[0], px[1], px[2]}, ck[3] = {pk[0], pk[1], pk[2]};  // Cartesian input, kept for start-inside
-    if (RHS == BHG_RHS_KERR_BL_) {
-        kerr_cart_to_bl(met.a, met.M, A.mu2, px, pk, met.E, met.L);
-    }
-    const double r0 = (RHS == BHG_RHS_KERR_BL_)
-                          ? px[0]
-                          : sqrt(__builtin_fma(px[2], px[2], __builtin_fma(px[1], px[1], px[0] * px[0])));
-    if (r0 <= A.r_hor) {
-        // 'start_inside_hole' (RelativisticRenderEngine.py:296, :311-313)
-        store_result(A, (uint32_t)i, cx, ck, BHG_FLAG_START_INSIDE_ | BHG_FLAG_HIT_HORIZON_, 0, 0);
-        w[3] = -1.0;
-        return;
-    }
-    initial_record<RHS, ADAPTIVE>(A, met, px, pk, pa, pr, ph);
-    w[0] = pa[0];
-    w[1] = pa[1];
-    w[2] = pa[2];
-    w[3] = ph;
-    w[4] = pr;
-    if (RHS == BHG_RHS_KERR_BL_) {
-        // the trace pass starts Kerr rays from records: BL state in the ray's end[] slot
-        w[5] = 0.0;
-        w[6] = met.E;
-        w[7] = met.L;
-        double *e = A.end + i * 6;
-        e[0] = px[0];
-        e[1] = px[1];
-        e[2] = px[2];
-        e[3] = pk[0];
-        e[4] = pk[1];
-        e[5] = pk[2];
-    }
-}
-
 #ifdef BHG_TU_KERR
 // Acceleration probe for the Boyer-Lindquist form: x = (r, theta, phi), k = d/dlambda of those; the Killing constants
-// E = -k_t, L = k_phi from the null condition AT THE POINT (the formula the prepare pass applies at the camera), then the
+// E = -k_t, L = k_phi from the null condition AT THE POINT (the formula every kernel's ray start applies at the camera, kerr_cart_to_bl), then the
 // right-hand side the trace kernels run (accel_kerr_bl).  acc is d^2 (r, theta, phi) / dlambda^2.
 __global__ void accel_kerr_kernel(const double *x, const double *k, double r_s, double spin, double mu2, uint64_t n, double *acc)
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const double q[3] = {x[3 * i], x[3 * i + 1], x[3 * i + 2]}, u[3] = {k[3 * i], k[3 * i + 1], k[3 * i + 2]};
-    Metric met;
-    met.r_s = r_s;
-    met.M = 0.5 * r_s;
-    met.a = spin;
+    Metric met = metric_of(r_s, spin);
     const double a = met.a, M = met.M, r = q[0];
     const double st = sin(q[1]), ct = cos(q[1]), s2 = st * st, c2 = ct * ct;
     const double Sig = r * r + a * a * c2, Del = r * r - 2.0 * M * r + a * a;
@@ -2744,19 +2674,69 @@ __global__ void __launch_bounds__(256) kerr_finalize_kernel(const TraceArgs A, d
 #endif  // BHG_TU_KERR
 
 // ------------------------------------------------------------------------------------------
-// One ATTEMPTED adaptive step of a lane-per-ray loop (the sampled-trajectory kernel, the disk-crossings kernel): rk.py:111-165
-// flattened as in the trace kernels, one attempt per call -- the step-size clamp and floor, the step budget, "already at
-// t_bound", the stages, the error norm and the controller, on the trace kernels' own helpers, so that the steps are theirs bit
-// for bit.  Returns DP54_ACCEPTED (xn, vn, a2 .. a7, r_new, t_new, h hold the step; h_abs the next step's size), DP54_REJECTED
-// (h_abs shrunk: attempt again from the same state) or the flag that ends the ray before the attempt.
+// The lane-per-ray loops (the sampled-trajectory kernel in both its shapes, the disk-crossings kernel): a plain loop per ray on
+// the trace kernels' own helpers, so that the steps are theirs bit for bit.  RayState is a ray between two steps, StepTry one
+// attempted step from it.  What the loops share works on the two -- the start, the attempt, the radial sign tests, accepting
+// a step, the final store; what differs stays in the kernels: sampling and fixed steps there, the crossing records here.
 // ------------------------------------------------------------------------------------------
+struct RayState {
+    double x[3], v[3], a1[3];   // position, direction, a(x, v) (Kerr: Boyer-Lindquist)
+    double t, h_abs, r_cur;     // affine parameter, the size of the next attempt, r at x
+    uint32_t n_att, n_acc;
+    bool rejected;              // the last attempt was rejected (rk.py's step_rejected)
+    Metric met;
+};
+struct StepTry {
+    double t_new, h;
+    double a2[3], a3[3], a4[3], a5[3], a6[3], a7[3];
+    double xn[3], vn[3], r_new;
+};
+
+// Start ray i: k0 and x0 (a ONE-ray call's ride in the kernel arguments), the metric, Kerr's Cartesian -> Boyer-Lindquist
+// conversion with E and L, the start-inside test and the start record {a0, r0, h0} -- fill_batch's steps, on the same functions
+// and the same bits.  xe, ve: the end state of a ray that takes no step.  Returns true for a start inside the hole: xe, ve are
+// then the Cartesian input, which the caller stores as the ray's result at once; S is not to be stepped.
+template <int RHS, bool ADAPTIVE>
+__device__ __forceinline__ bool start_ray(const TraceArgs &A, uint64_t i, RayState &S, double xe[3], double ve[3])
+{
+    for (int c = 0; c < 3; c++) {
+        ve[c] = S.v[c] = A.k0 ? A.k0[i * 3 + c] : A.k0s[c];
+        xe[c] = S.x[c] = A.x0 ? A.x0[i * 3 + c] : A.x0s[c];
+    }
+    S.met = metric_of(A);
+    double r0;
+    if (RHS == BHG_RHS_KERR_BL_) {
+        kerr_cart_to_bl(S.met.a, S.met.M, A.mu2, S.x, S.v, S.met.E, S.met.L);
+        r0 = S.x[0];
+    } else {
+        r0 = sqrt(__builtin_fma(S.x[2], S.x[2], __builtin_fma(S.x[1], S.x[1], S.x[0] * S.x[0])));
+    }
+    if (r0 <= A.r_hor) return true;    // 'start_inside_hole' (RelativisticRenderEngine.py:296, :311-313)
+    S.t = S.h_abs = S.r_cur = 0.0;
+    S.n_att = S.n_acc = 0;
+    S.rejected = false;
+    initial_record<RHS, ADAPTIVE>(A, S.met, S.x, S.v, S.a1, S.r_cur, S.h_abs);
+    for (int c = 0; c < 3; c++) {
+        xe[c] = S.x[c];
+        ve[c] = S.v[c];
+    }
+    return false;
+}
+
+// One ATTEMPTED adaptive step: rk.py:111-165 flattened as in the trace kernels, one attempt per call -- the step-size clamp and
+// floor, the step budget, "already at t_bound", the stages, the error norm and the controller.  Returns DP54_ACCEPTED (P holds
+// the step; S.h_abs the next step's size), DP54_REJECTED (S.h_abs shrunk: attempt again from the same state) or the flag that
+// ends the ray before the attempt.
 constexpr uint32_t DP54_ACCEPTED = 0u, DP54_REJECTED = 0xFFFFFFFFu;
 template <int RHS>
-__device__ __forceinline__ uint32_t dp54_attempt(const TraceArgs &A, const Metric &met, const double x[3], const double v[3],
-                                                 const double a1[3], double t, double &h_abs, bool &rejected, uint32_t &n_att,
-                                                 uint32_t &n_acc, double &t_new, double &h, double a2[3], double a3[3], double a4[3],
-                                                 double a5[3], double a6[3], double a7[3], double xn[3], double vn[3], double &r_new)
+__device__ __forceinline__ uint32_t dp54_attempt(const TraceArgs &A, RayState &S, StepTry &P)
 {
+    const Metric &met = S.met;
+    const double *x = S.x, *v = S.v, *a1 = S.a1, t = S.t;
+    double &h_abs = S.h_abs, &t_new = P.t_new, &h = P.h, &r_new = P.r_new;
+    bool &rejected = S.rejected;
+    uint32_t &n_att = S.n_att, &n_acc = S.n_acc;
+    double *a2 = P.a2, *a3 = P.a3, *a4 = P.a4, *a5 = P.a5, *a6 = P.a6, *a7 = P.a7, *xn = P.xn, *vn = P.vn;
     const double t_bound = A.lambda_end, max_step = A.max_step;
     const double min_step = 10.0 * ulp_of(t);
     if (!rejected) {
@@ -2790,10 +2770,50 @@ __device__ __forceinline__ uint32_t dp54_attempt(const TraceArgs &A, const Metri
     return DP54_ACCEPTED;
 }
 
+// the radial sign tests of a step (find_active_events on r - R): the horizon in either direction, the exit sphere outwards
+__device__ __forceinline__ void radial_events(const TraceArgs &A, const RayState &S, const StepTry &P, bool &ev_h, bool &ev_e)
+{
+    const double r_cur = S.r_cur, r_new = P.r_new;
+    ev_h = ((r_cur - A.r_hor <= 0.0) && (r_new - A.r_hor >= 0.0)) || ((r_cur - A.r_hor >= 0.0) && (r_new - A.r_hor <= 0.0));
+    ev_e = (A.r_exit > 0.0) && (r_cur - A.r_exit <= 0.0) && (r_new - A.r_exit >= 0.0);
+}
+
+// Accept a step that no event ends: its end is the ray's end state so far.  Returns true when that is lambda_end; otherwise
+// S moves on to it.
+__device__ __forceinline__ bool advance(const TraceArgs &A, RayState &S, const StepTry &P, double xe[3], double ve[3])
+{
+    for (int c = 0; c < 3; c++) {
+        xe[c] = P.xn[c];
+        ve[c] = P.vn[c];
+    }
+    if (P.t_new - A.lambda_end >= 0.0) return true;
+    S.t = P.t_new;
+    S.r_cur = P.r_new;
+    for (int c = 0; c < 3; c++) {
+        S.x[c] = P.xn[c];
+        S.v[c] = P.vn[c];
+        S.a1[c] = P.a7[c];
+    }
+    return false;
+}
+
+// The ray's result: (xe, ve), or -- the controller gave up -- the state the last attempt started from
+__device__ __forceinline__ void finish_ray(const TraceArgs &A, uint64_t i, const RayState &S, double xe[3], double ve[3],
+                                           uint32_t flags)
+{
+    if (flags & (BHG_FLAG_STEP_TOO_SMALL_ | BHG_FLAG_MAX_STEPS_)) {
+        for (int c = 0; c < 3; c++) {
+            xe[c] = S.x[c];
+            ve[c] = S.v[c];
+        }
+    }
+    store_result(A, (uint32_t)i, xe, ve, flags, S.n_att, S.n_acc);  // Kerr: still Boyer-Lindquist, finalised next
+}
+
 // ------------------------------------------------------------------------------------------
 // Sampled trajectories: what calc_trajectory returns with nr_points_curve (RelativisticRenderEngine.py:
 // 293-294; the curves of README Fig. 5/6).  A plain loop per ray -- this is the small-n plotting path, not the
-// frame path.  Same prepare record, same stages / error norm / factor helpers as
+// frame path.  Same start record (start_ray), same stages / error norm / factor helpers as
 // the integrate loop; after every accepted step the samples t_eval_j <= t are emitted through the step's
 // dense output (solve_ivp's t_eval semantics, ivp.py:706-723); rays that end early emit fewer samples.
 // Two shapes, same arithmetic and same bits: WAVE = false, one LANE per ray (many rays, few samples each); WAVE = true,
@@ -2812,118 +2832,68 @@ __global__ void __launch_bounds__(WAVE ? 256 : 64) trajectory_dp54_kernel(const 
     const uint64_t i = WAVE ? (uint64_t)blockIdx.x : (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= A.n) return;
     const double t_bound = A.lambda_end;
-    double x[3], v[3], a1[3], h_abs, r_cur;
-    Metric met;
-    met.r_s = A.r_s;
-    met.M = 0.5 * A.r_s;
-    met.a = A.spin;
-    met.E = met.L = 0.0;
     double *out = traj + i * 6 * (uint64_t)T;
-    if (WAVE) {
-        // one wave per ray: the wave works out the ray's start record itself -- the prepare pass's own functions, on the same
-        // bits, every lane alike -- and fills what the ray never reaches with NaN at the end: no prepare launch, no record
-        // round trip, no memset in front of a call that is one ray long (k0 of a ONE-ray call rides in the kernel arguments)
-        for (int c = 0; c < 3; c++) {
-            v[c] = A.k0 ? A.k0[i * 3 + c] : A.k0s[c];
-            x[c] = A.x0 ? A.x0[i * 3 + c] : A.x0s[c];
-        }
-        const double cx[3] = {x[0], x[1], x[2]}, ck[3] = {v[0], v[1], v[2]};
-        double r0;
-        if (RHS == BHG_RHS_KERR_BL_) {
-            kerr_cart_to_bl(met.a, met.M, A.mu2, x, v, met.E, met.L);
-            r0 = x[0];
-        } else {
-            r0 = sqrt(__builtin_fma(x[2], x[2], __builtin_fma(x[1], x[1], x[0] * x[0])));
-        }
-        if (r0 <= A.r_hor) {    // 'start_inside_hole' (RelativisticRenderEngine.py:296, :311-313)
+    RayState S;
+    double xe[3], ve[3];
+    if (start_ray<RHS, !FIXED>(A, i, S, xe, ve)) {
+        // final at once, no samples.  One wave per ray: every lane has worked the start out alike, all of them fill the sample
+        // block with NaN and lane 0 stores; one lane per ray: the host has preset the block
+        if (WAVE) {
             for (uint32_t j = lane; j < 6 * T; j += blockDim.x) out[j] = __builtin_nan("");
-            if (lane == 0) {
-                n_valid[i] = 0;
-                if (A.object_id) A.object_id[i] = (int8_t)-1;
-                store_result(A, (uint32_t)i, cx, ck, BHG_FLAG_START_INSIDE_ | BHG_FLAG_HIT_HORIZON_, 0, 0);
-            }
-            return;
+            if (lane != 0) return;
         }
-        h_abs = 0.0;
-        r_cur = 0.0;
-        initial_record<RHS, !FIXED>(A, met, x, v, a1, r_cur, h_abs);
-    } else {
-        const double *w = A.ws + i * (uint64_t)A.ws_stride;
-        a1[0] = w[0];
-        a1[1] = w[1];
-        a1[2] = w[2];
-        h_abs = w[3];
-        r_cur = w[4];
-        if (h_abs < 0.0) {  // start inside: the prepare pass has written the result
-            n_valid[i] = 0;
-            return;
-        }
-        if (RHS == BHG_RHS_KERR_BL_) {
-            const double *e = A.end + i * 6;
-            for (int c = 0; c < 3; c++) {
-                x[c] = e[c];
-                v[c] = e[3 + c];
-            }
-            met.E = w[6];
-            met.L = w[7];
-        } else {
-            for (int c = 0; c < 3; c++) {
-                v[c] = A.k0[i * 3 + c];
-                x[c] = A.x0 ? A.x0[i * 3 + c] : A.x0s[c];
-            }
-        }
+        n_valid[i] = 0;
+        if (A.object_id) A.object_id[i] = (int8_t)-1;
+        store_result(A, (uint32_t)i, xe, ve, BHG_FLAG_START_INSIDE_ | BHG_FLAG_HIT_HORIZON_, 0, 0);
+        return;
     }
     const double dt = t_bound / (double)(T - 1);
-    double t = 0.0;
-    uint32_t n_att = 0, n_acc = 0, next = 0, flags = 0;
+    uint32_t next = 0, flags = 0;
     int hit_obj = -1;        // bhg_trajectory_objects: the sphere the ray ends on
-    bool rejected = false;
-    double xe[3] = {x[0], x[1], x[2]}, ve[3] = {v[0], v[1], v[2]};
     for (;;) {
-        double t_new, h, a2[3], a3[3], a4[3], a5[3], a6[3], a7[3], xn[3], vn[3], r_new;
+        StepTry P;
         if (FIXED) {
             // classic RK4 with the fixed step h_fixed (the build's "R-fine" regime): no controller, every step accepted
-            if (t >= t_bound) {
+            if (S.t >= t_bound) {
                 flags = BHG_FLAG_REACHED_END_;
                 break;
             }
-            if (n_att >= A.max_steps) {
+            if (S.n_att >= A.max_steps) {
                 flags = BHG_FLAG_MAX_STEPS_;
                 break;
             }
-            t_new = t + A.h_fixed;
-            if (t_new - t_bound > 0.0) t_new = t_bound;
-            h = t_new - t;
-            rk4_step<RHS>(x, v, a1, h, met, xn, vn, a7, r_new);
-            n_att++;
-            n_acc = n_att;
+            P.t_new = S.t + A.h_fixed;
+            if (P.t_new - t_bound > 0.0) P.t_new = t_bound;
+            P.h = P.t_new - S.t;
+            rk4_step<RHS>(S.x, S.v, S.a1, P.h, S.met, P.xn, P.vn, P.a7, P.r_new);
+            S.n_att++;
+            S.n_acc = S.n_att;
         } else {
-        const uint32_t st = dp54_attempt<RHS>(A, met, x, v, a1, t, h_abs, rejected, n_att, n_acc, t_new, h, a2, a3, a4, a5, a6, a7, xn,
-                                              vn, r_new);
-        if (st == DP54_REJECTED) continue;
-        if (st != DP54_ACCEPTED) {
-            flags = st;
-            break;
-        }
+            const uint32_t st = dp54_attempt<RHS>(A, S, P);
+            if (st == DP54_REJECTED) continue;
+            if (st != DP54_ACCEPTED) {
+                flags = st;
+                break;
+            }
         }
         // the step's interpolant: the dense output of the accepted DP5(4) step, or -- fixed steps -- its cubic Hermite interpolant
         Dense d;
         Hermite hd;
         const bool bl = RHS == BHG_RHS_KERR_BL_;
         if (FIXED) {
-            hd.t0 = t;
-            hd.h = h;
+            hd.t0 = S.t;
+            hd.h = P.h;
 #pragma unroll
             for (int c = 0; c < 3; c++) {
-                hd.x0[c] = x[c];
-                hd.v0[c] = v[c];
-                hd.a0[c] = a1[c];
-                hd.x1[c] = xn[c];
-                hd.v1[c] = vn[c];
-                hd.a1[c] = a7[c];
+                hd.x0[c] = S.x[c];
+                hd.v0[c] = S.v[c];
+                hd.a0[c] = S.a1[c];
+                hd.x1[c] = P.xn[c];
+                hd.v1[c] = P.vn[c];
+                hd.a1[c] = P.a7[c];
             }
         } else {
-            build_dense(d, t, h, x, v, a1, a2, a3, a4, a5, a6, a7);
+            build_dense(d, S.t, P.h, S.x, S.v, S.a1, P.a2, P.a3, P.a4, P.a5, P.a6, P.a7);
         }
         auto state_at = [&](double tt, double sx[3], double sv[3]) {
             if (FIXED) {
@@ -2933,22 +2903,21 @@ __global__ void __launch_bounds__(WAVE ? 256 : 64) trajectory_dp54_kernel(const 
                 dense_dir(d, tt, sv);
             }
         };
-        const bool ev_h = ((r_cur - A.r_hor <= 0.0) && (r_new - A.r_hor >= 0.0)) ||
-                          ((r_cur - A.r_hor >= 0.0) && (r_new - A.r_hor <= 0.0));
-        const bool ev_e = (A.r_exit > 0.0) && (r_cur - A.r_exit <= 0.0) && (r_new - A.r_exit >= 0.0);
+        bool ev_h, ev_e;
+        radial_events(A, S, P, ev_h, ev_e);
         // the thin disk (LimitedRelativisticRenderEngine.py:283-286, :413-438): a plane crossing is terminal only inside the annulus
-        const bool ev_d = (A.disk_r_out > 0.0) && crossed_disk_plane<RHS>(x, xn);
+        const bool ev_d = (A.disk_r_out > 0.0) && crossed_disk_plane<RHS>(S.x, P.xn);
         // object spheres (bhg_trajectory_objects; the reference's collision stub, RelativisticRenderEngine.py:304-305): the
         // trace kernels' own chord rule on the step's ends
-        const bool ev_o = (A.n_spheres > 0) && any_sphere_candidate_of<RHS>(A, x, xn);
-        double t_stop = t_new;
+        const bool ev_o = (A.n_spheres > 0) && any_sphere_candidate_of<RHS>(A, S.x, P.xn);
+        double t_stop = P.t_new;
         uint32_t evflag = 0;
-        if (FIXED && !(ev_h || ev_e || ev_d || ev_o) && !(r_new == r_new)) {
+        if (FIXED && !(ev_h || ev_e || ev_d || ev_o) && !(P.r_new == P.r_new)) {
             // a fixed step that ends in a non-finite state (through the Boyer-Lindquist 1 / Delta singularity): the ray ends
             // there, flagged NaN by store_result; the step yields no samples
             for (int c = 0; c < 3; c++) {
-                xe[c] = xn[c];
-                ve[c] = vn[c];
+                xe[c] = P.xn[c];
+                ve[c] = P.vn[c];
             }
             flags = 0;
             break;
@@ -2960,7 +2929,7 @@ __global__ void __launch_bounds__(WAVE ? 256 : 64) trajectory_dp54_kernel(const 
             double best;
             int obj;
             evflag = settle_events<(EVT_EXIT | EVT_DISK | EVT_OBJ)>(
-                A, kind, t, t_new, x, xn,
+                A, kind, S.t, P.t_new, S.x, P.xn,
                 [&](double tt, double Rr) { return FIXED ? hermite_g(hd, tt, Rr, bl) : dense_g(d, tt, Rr, bl); },
                 [&](double tt) {
                     double q[3];
@@ -3013,7 +2982,7 @@ __global__ void __launch_bounds__(WAVE ? 256 : 64) trajectory_dp54_kernel(const 
             }
             double sx[3], sv[3];
             state_at(te, sx, sv);
-            if (bl) {
+            if (bl) {   // (not bl_record_to_cart: its c[5] has a + 0.0 * u2 term, which changes a -0.0 and the NaN propagation: other bits)
                 const double r = sx[0], th = sx[1], ph = sx[2], a = A.spin;
                 const double R = sqrt(r * r + a * a), st = sin(th), ct = cos(th), sp = sin(ph), cp = cos(ph);
                 const double u0 = sv[0], u1 = sv[1], u2 = sv[2];
@@ -3034,26 +3003,9 @@ __global__ void __launch_bounds__(WAVE ? 256 : 64) trajectory_dp54_kernel(const 
             state_at(t_stop, xe, ve);
             break;
         }
-        for (int c = 0; c < 3; c++) {
-            xe[c] = xn[c];
-            ve[c] = vn[c];
-        }
-        if (t_new - t_bound >= 0.0) {
+        if (advance(A, S, P, xe, ve)) {
             flags = BHG_FLAG_REACHED_END_;
             break;
-        }
-        t = t_new;
-        r_cur = r_new;
-        for (int c = 0; c < 3; c++) {
-            x[c] = xn[c];
-            v[c] = vn[c];
-            a1[c] = a7[c];
-        }
-    }
-    if (flags & (BHG_FLAG_STEP_TOO_SMALL_ | BHG_FLAG_MAX_STEPS_)) {
-        for (int c = 0; c < 3; c++) {
-            xe[c] = x[c];
-            ve[c] = v[c];
         }
     }
     if (WAVE) {     // samples the ray never reached read back as NaN
@@ -3063,30 +3015,28 @@ __global__ void __launch_bounds__(WAVE ? 256 : 64) trajectory_dp54_kernel(const 
     }
     n_valid[i] = next;
     if (A.object_id) A.object_id[i] = (int8_t)hit_obj;
-    store_result(A, (uint32_t)i, xe, ve, flags, n_att, n_acc);  // Kerr: still Boyer-Lindquist, finalised next
+    finish_ray(A, i, S, xe, ve, flags);
 }
 
 // one wave per ray while the rays are too few to fill the chip's lanes anyway (the C-ABI layer asks too: such a call needs
-// no memset of the sample block, no prepare records, and -- one ray -- no upload of k0)
+// no memset of the sample block and -- one ray -- no upload of k0)
 #ifndef BHG_TU_KERR
 #ifndef BHG_TU_TIMELIKE
 bool trajectory_wave_per_ray(uint64_t n) { return n <= 2048; }
 #endif
 #endif
 
-// prepare pass + sampled trajectories of one right-hand side
+// sampled trajectories of one right-hand side: ONE launch in either shape
 template <int RHS, bool FIXED>
 static void launch_trajectory_rhs_m(const TraceArgs &a, double *traj, uint32_t *n_valid, uint32_t T, hipStream_t s)
 {
-    const unsigned gp = (unsigned)((a.n + 255) / 256), gt = (unsigned)((a.n + 63) / 64);
     if (trajectory_wave_per_ray(a.n)) {
         // the engine's literal call is ONE ray with 10,000 samples: four waves share the samples (the step loop itself is one
         // wave's work however many run it: 43 us of the call; the samples 27 us with one wave)
         const unsigned threads = (a.n <= 64 && T >= 1024) ? 256u : 64u;   // (four waves = one per SIMD of a CU; eight measured slower than one)
         BHG_LAUNCH((trajectory_dp54_kernel<RHS, true, FIXED>), dim3((unsigned)a.n), dim3(threads), 0, s, a, traj, n_valid, T);
     } else {
-        BHG_LAUNCH((prepare_kernel<RHS, !FIXED>), dim3(gp), dim3(256), 0, s, a);
-        BHG_LAUNCH((trajectory_dp54_kernel<RHS, false, FIXED>), dim3(gt), dim3(64), 0, s, a, traj, n_valid, T);
+        BHG_LAUNCH((trajectory_dp54_kernel<RHS, false, FIXED>), dim3((unsigned)((a.n + 63) / 64)), dim3(64), 0, s, a, traj, n_valid, T);
     }
 }
 
@@ -3131,7 +3081,7 @@ hipError_t launch_trajectory(const TraceArgs &a, int rhs, int method, double *tr
 // off: disk_r_out plays no part in step control and a crossing never truncates a step; horizon, exit sphere and lambda_end
 // end the ray as they do there, and end / flags / n_steps / n_accepted are that trace's.
 // One LANE per ray, a plain loop: trajectory_dp54_kernel's step loop (the trace kernels' own stages, error norm,
-// controller, dense output and Brent search) without the sampling; the lane works its start record out itself.
+// controller, dense output and Brent search) without the sampling, on the same named state and helpers (RayState, StepTry).
 // Per accepted step: the sign-change rule of find_active_events (crossed_disk_plane: at most one root per step), the root
 // by brent_root on the step's dense output as settle_events finds it, counted when its cylindrical radius lies in
 // [disk_r_in, disk_r_out] and -- the step holding the ray's terminal event too -- when it is not later than that event's
@@ -3146,56 +3096,31 @@ __global__ void __launch_bounds__(64, (RHS == BHG_RHS_KERR_BL_ ? BHG_KERR_WAVES_
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= A.n) return;
-    const double t_bound = A.lambda_end;
     const bool bl = RHS == BHG_RHS_KERR_BL_;
-    double x[3], v[3], a1[3], h_abs = 0.0, r_cur = 0.0;
-    Metric met;
-    met.r_s = A.r_s;
-    met.M = 0.5 * A.r_s;
-    met.a = A.spin;
-    met.E = met.L = 0.0;
-    for (int c = 0; c < 3; c++) {
-        v[c] = A.k0[i * 3 + c];
-        x[c] = A.x0 ? A.x0[i * 3 + c] : A.x0s[c];
+    RayState S;
+    double xe[3], ve[3];
+    if (start_ray<RHS, true>(A, i, S, xe, ve)) {    // final at once, no crossings
+        A.n_cross[i] = 0;
+        store_result(A, (uint32_t)i, xe, ve, BHG_FLAG_START_INSIDE_ | BHG_FLAG_HIT_HORIZON_, 0, 0);
+        return;
     }
-    {
-        const double cx[3] = {x[0], x[1], x[2]}, ck[3] = {v[0], v[1], v[2]};
-        double r0;
-        if (bl) {
-            kerr_cart_to_bl(met.a, met.M, A.mu2, x, v, met.E, met.L);
-            r0 = x[0];
-        } else {
-            r0 = sqrt(__builtin_fma(x[2], x[2], __builtin_fma(x[1], x[1], x[0] * x[0])));
-        }
-        if (r0 <= A.r_hor) {    // start inside: final at once, no crossings
-            A.n_cross[i] = 0;
-            store_result(A, (uint32_t)i, cx, ck, BHG_FLAG_START_INSIDE_ | BHG_FLAG_HIT_HORIZON_, 0, 0);
-            return;
-        }
-    }
-    initial_record<RHS, true>(A, met, x, v, a1, r_cur, h_abs);
-    double t = 0.0;
-    uint32_t n_att = 0, n_acc = 0, flags = 0, n_cross = 0;
-    bool rejected = false;
-    double xe[3] = {x[0], x[1], x[2]}, ve[3] = {v[0], v[1], v[2]};
+    uint32_t flags = 0, n_cross = 0;
     for (;;) {
-        double a2[3], a3[3], a4[3], a5[3], a6[3], a7[3], xn[3], vn[3], r_new, t_new, h;
-        const uint32_t st = dp54_attempt<RHS>(A, met, x, v, a1, t, h_abs, rejected, n_att, n_acc, t_new, h, a2, a3, a4, a5, a6, a7, xn,
-                                              vn, r_new);
+        StepTry P;
+        const uint32_t st = dp54_attempt<RHS>(A, S, P);
         if (st == DP54_REJECTED) continue;
         if (st != DP54_ACCEPTED) {
             flags = st;
             break;
         }
-        const bool ev_h = ((r_cur - A.r_hor <= 0.0) && (r_new - A.r_hor >= 0.0)) ||
-                          ((r_cur - A.r_hor >= 0.0) && (r_new - A.r_hor <= 0.0));
-        const bool ev_e = (A.r_exit > 0.0) && (r_cur - A.r_exit <= 0.0) && (r_new - A.r_exit >= 0.0);
-        const bool ev_d = crossed_disk_plane<RHS>(x, xn);
+        bool ev_h, ev_e;
+        radial_events(A, S, P, ev_h, ev_e);
+        const bool ev_d = crossed_disk_plane<RHS>(S.x, P.xn);
         uint32_t evflag = 0;
-        double t_stop = t_new;
+        double t_stop = P.t_new;
         if (ev_h || ev_e || ev_d) {
             Dense d;
-            build_dense(d, t, h, x, v, a1, a2, a3, a4, a5, a6, a7);
+            build_dense(d, S.t, P.h, S.x, S.v, S.a1, P.a2, P.a3, P.a4, P.a5, P.a6, P.a7);
             auto g_z = [&](double tt) {
                 if (!bl) return dense_z(d, tt);
                 double q[3], sn, cs;
@@ -3208,13 +3133,13 @@ __global__ void __launch_bounds__(64, (RHS == BHG_RHS_KERR_BL_ ? BHG_KERR_WAVES_
                 double best;
                 int obj;
                 evflag = settle_events<EVT_EXIT>(
-                    A, (ev_h ? EV_HORIZON : 0u) | (ev_e ? EV_EXIT : 0u), t, t_new, x, xn,
+                    A, (ev_h ? EV_HORIZON : 0u) | (ev_e ? EV_EXIT : 0u), S.t, P.t_new, S.x, P.xn,
                     [&](double tt, double Rr) { return dense_g(d, tt, Rr, bl); }, g_z,
                     [&](double tt, double xq[3]) { dense_pos(d, tt, xq); }, bl, best, obj);
                 if (evflag) t_stop = best;
             }
             if (ev_d) {
-                const double root = brent_root(g_z, t, t_new);
+                const double root = brent_root(g_z, S.t, P.t_new);
                 double sx[3], sv[3];
                 dense_pos(d, root, sx);
                 // cylindrical radius of the crossing point, as settle_events takes it
@@ -3252,30 +3177,13 @@ __global__ void __launch_bounds__(64, (RHS == BHG_RHS_KERR_BL_ ? BHG_KERR_WAVES_
                 break;
             }
         }
-        for (int c = 0; c < 3; c++) {
-            xe[c] = xn[c];
-            ve[c] = vn[c];
-        }
-        if (t_new - t_bound >= 0.0) {
+        if (advance(A, S, P, xe, ve)) {
             flags = BHG_FLAG_REACHED_END_;
             break;
         }
-        t = t_new;
-        r_cur = r_new;
-        for (int c = 0; c < 3; c++) {
-            x[c] = xn[c];
-            v[c] = vn[c];
-            a1[c] = a7[c];
-        }
-    }
-    if (flags & (BHG_FLAG_STEP_TOO_SMALL_ | BHG_FLAG_MAX_STEPS_)) {
-        for (int c = 0; c < 3; c++) {
-            xe[c] = x[c];
-            ve[c] = v[c];
-        }
     }
     A.n_cross[i] = (uint8_t)(n_cross < 255u ? n_cross : 255u);
-    store_result(A, (uint32_t)i, xe, ve, flags, n_att, n_acc);  // Kerr: still Boyer-Lindquist, finalised next
+    finish_ray(A, i, S, xe, ve, flags);
 }
 
 #if defined(BHG_TU_KERR)
@@ -3310,10 +3218,7 @@ __global__ void accel_kernel(const double *x, const double *k, double r_s, uint6
     double px[3] = {x[3 * i], x[3 * i + 1], x[3 * i + 2]};
     double pk[3] = {k[3 * i], k[3 * i + 1], k[3 * i + 2]};
     double a[3], r;
-    Metric met;
-    met.r_s = r_s;
-    met.M = 0.5 * r_s;
-    met.a = met.E = met.L = 0.0;
+    const Metric met = metric_of(r_s, 0.0);
     accel<RHS>(px, pk, met, a, r);
     acc[3 * i] = a[0];
     acc[3 * i + 1] = a[1];
@@ -3326,9 +3231,9 @@ __global__ void accel_kernel(const double *x, const double *k, double r_s, uint6
 template <int RHS, int EVT>
 static hipError_t launch_variant(const TraceArgs &a, int method, int grid, hipStream_t s, hipEvent_t *ev)
 {
-    // No prepare launch: the trace kernel's waves work out the start records themselves while they fill their ray queues
-    // (converged, 64 lanes wide; Kerr: Cartesian -> Boyer-Lindquist, E and L, kerr_cart_to_bl).  ev[0] and ev[1] stay back
-    // to back so that the three timing slots keep their meaning (bhg_last_pass_ms: slot 0, the former prepare pass, is ~0).
+    // No launch ahead of this one: the trace kernel's waves work out the start records themselves while they fill their ray
+    // queues (converged, 64 lanes wide; Kerr: Cartesian -> Boyer-Lindquist, E and L, kerr_cart_to_bl).  ev[0] and ev[1] stay
+    // back to back so that the three timing slots keep their meaning (bhg_last_pass_ms: slot 0, once a pass of its own, is ~0).
     if (ev) {
         (void)hipEventRecord(ev[0], s);
         (void)hipEventRecord(ev[1], s);

@@ -100,8 +100,8 @@ __device__ __forceinline__ void sincos_pi4(double x, double &s, double &c)
 // (r, theta) block has determinant -(r^2 sin^2 th + R^2 cos^2 th) / R, R = sqrt(r^2 + a^2)):
 //     k_rho = cos ph k_x + sin ph k_y,   dphi = (cos ph k_y - sin ph k_x) / (R sin th),
 //     dr = (r sin th k_rho + R cos th k_z) R / D,   dtheta = (R cos th k_rho - r sin th k_z) / D.
-// About 330 instructions, 64 rays wide inside a trace wave's queue fill (the prepare pass uses the same function, so every
-// path starts a ray from bit-identical Boyer-Lindquist data).  A start ON the rotation axis (w = 0) has no azimuth: NaN, as
+// About 330 instructions, 64 rays wide inside a trace wave's queue fill (the lane-per-ray kernels' start_ray uses the same function, so
+// every path starts a ray from bit-identical Boyer-Lindquist data).  A start ON the rotation axis (w = 0) has no azimuth: NaN, as
 // the checker's 3x3 solve gives (0 / 0).
 __device__ __forceinline__ void kerr_cart_to_bl(double a, double M, double mu2, double px[3], double pk[3], double &E, double &L)
 {

@@ -1142,7 +1142,8 @@ def test_trajectory_kernel_shapes_give_the_same_bits(ctx):
     """bhg_trajectory runs one WAVE per ray up to 2048 rays (the engine's literal call: one ray, 10,000 samples, shared
     out over the 64 lanes) and one LANE per ray above: same arithmetic, so the same rays sampled either way must come
     back bit for bit, sample counts and NaN padding included; sample counts that are not multiples of 64 and a
-    trajectory cut short by the horizon are in the set."""
+    trajectory cut short by the horizon are in the set, and so are the fixed-step start, the time-like form and rays that
+    start inside the horizon (both shapes start a ray through the same helper and differ only in how they store such a ray)."""
     k = frame_rays(2100, seed=52)
     for kw, T in ((dict(r_s=1.0, lambda_end=50.0), 37), (dict(r_s=1.0, lambda_end=50.0, rhs_form=1, r_exit=31.0), 130),
                   (dict(r_s=1.0, lambda_end=40.0, rhs_form=2, spin=0.45), 65)):
@@ -1154,6 +1155,36 @@ def test_trajectory_kernel_shapes_give_the_same_bits(ctx):
             assert np.array_equal(a[:500], b, equal_nan=True)
         nv, flags = sub[1], sub[3]
         assert (nv == T).any() and ((nv < T) & ((flags & 1) != 0)).any()
+    # both shapes start a ray through one helper inside the kernel: (a) the fixed-step start (no initial step to select),
+    # Schwarzschild and Kerr, and (b) the time-like Christoffel form
+    kerr_cam, kerr_rot = np.array([2.0, -24.0, 14.0]), np.array([[1, 0, 0], [0, 0.5, 0.866], [0, -0.866, 0.5]])
+    for kw in (dict(r_s=1.0, lambda_end=50.0, method=1, h_fixed=0.25),
+               dict(r_s=1.0, lambda_end=40.0, rhs_form=2, spin=0.45, method=1, h_fixed=0.25),
+               dict(r_s=1.0, lambda_end=50.0, time_like=1)):
+        cam, kk = (CAM, k) if kw.get("rhs_form") != 2 else (kerr_cam, k @ kerr_rot)
+        big = ctx.trajectory(kk, cam, _params(**kw), 37)
+        sub = ctx.trajectory(kk[:500], cam, _params(**kw), 37)
+        for a, b in zip(big, sub):
+            assert np.array_equal(a[:500], b, equal_nan=True)
+        assert (sub[1] == 37).any()
+    # (c) per-ray origins, every 7th inside the horizon, one object sphere in the scene: a ray that starts inside is final at
+    # once in either shape -- no samples (the wave shape fills its block with NaN itself, the lane shape leaves the preset
+    # one), no object, and the end record is the Cartesian input
+    x0 = np.tile(CAM, (2100, 1))
+    x0[::7] = (0.3, 0.2, 0.6)
+    sphere = [[2.0, 1.0, 10.0, 1.5]]
+    big = ctx.trajectory(k, x0, _params(r_s=1.0, lambda_end=50.0), 37, spheres=sphere)
+    sub = ctx.trajectory(k[:500], x0[:500], _params(r_s=1.0, lambda_end=50.0), 37, spheres=sphere)
+    assert len(big) == 5 and len(sub) == 5
+    for a, b in zip(big, sub):
+        assert np.array_equal(a[:500], b, equal_nan=True)
+    for traj, nv, end, flags, obj in (big, sub):
+        inside = np.zeros(len(nv), bool)
+        inside[::7] = True
+        assert np.all(flags[inside] == 3) and np.all(nv[inside] == 0) and np.all(obj[inside] == -1)
+        assert np.isnan(traj[inside]).all()
+        assert not (flags[~inside] & 2).any()
+        assert inside.any() and (nv[~inside] == 37).any()
     # ... and up to 64 rays with 1024 samples or more, FOUR waves per ray share the samples (all four integrate the ray, every
     # lane alike): the same bits again, horizon rays and a sample count that is no multiple of 256 included
     k5 = frame_rays(70, seed=53, fov=0.16)
