@@ -607,14 +607,17 @@ __device__ __forceinline__ bool sphere_candidate(const double sp[4], const doubl
 
 // Did the step cross the disk plane z = 0?  Cartesian forms: sign change of z (either end on the plane counts,
 // like a scipy event).  Boyer-Lindquist: z = r cos(theta) with r > 0 changes sign when theta moves from one
-// interval [pi/2 + k pi, pi/2 + (k+1) pi) to another -- an integer comparison, no trigonometry in the loop
-// (cos(theta) is never exactly 0 for a double theta, so the closed/open ends cannot matter).
+// interval (pi/2 + k pi, pi/2 + (k+1) pi] to another -- an integer comparison, no trigonometry in the loop.
+// cos(theta) is never exactly 0 for a double theta, so scipy's <= / >= cannot matter; which side the interval's end
+// belongs to does, at one value: the double nearest pi/2 -- acos(0), the theta of every start in the equatorial plane --
+// lies BELOW pi/2 (its cosine is +6.1e-17), with the thetas under it.  Hence ceil, not floor: a ray that leaves the plane
+// downwards (theta growing) has its crossing at t = 0, as the reference has; one that leaves it upwards has none.
 template <int RHS>
 __device__ __forceinline__ bool crossed_disk_plane(const double x0[3], const double x1[3])
 {
     if (RHS == BHG_RHS_KERR_BL_) {
-        const double k0 = floor((x0[1] - 1.5707963267948966) * 0.3183098861837907);
-        const double k1 = floor((x1[1] - 1.5707963267948966) * 0.3183098861837907);
+        const double k0 = ceil((x0[1] - 1.5707963267948966) * 0.3183098861837907);
+        const double k1 = ceil((x1[1] - 1.5707963267948966) * 0.3183098861837907);
         return k0 != k1;
     }
     return ((x0[2] <= 0.0) && (x1[2] >= 0.0)) || ((x0[2] >= 0.0) && (x1[2] <= 0.0));

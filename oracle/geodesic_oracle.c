@@ -578,12 +578,45 @@ static void sampler_emit(sampler_t *sm, const dense_t *dn, double t_upto)
     }
 }
 
+/* optional crossings recorder (bhgo_trace_crossings): the disk plane as a NON-terminal event, as scipy_reference runs it.  The
+   params the step loop sees have the disk off, so step control and the terminal events are those of the disk-off trace; the
+   annulus lives here.  After each accepted step: the sign rule of check_events, one brentq root on the step's dense output,
+   counted when its cylindrical radius lies in the annulus and -- the step holding the ray's terminal event too -- when it
+   is not later than that event's root (scipy_reference's td <= te).  n counts every crossing; the first max_records are
+   kept, in the solver's own coordinates (Kerr: converted by the caller). */
+typedef struct {
+    double r_in, r_out;
+    uint32_t max_records, n;
+    size_t stride; /* rays per layer: record m at rec[m * stride * 6], time at t[m * stride] */
+    double *rec, *t;
+} crossings_t;
+
+static void crossings_step(crossings_t *cr, const evfun_t *base, const double y_old[6], const double y_new[6], double t_old,
+                           double t, double t_terminal)
+{
+    const int kerr = e_kerr(base);
+    const double z_old = kerr ? cos(y_old[3]) : y_old[5], z_new = kerr ? cos(y_new[3]) : y_new[5];
+    if (!(((z_old <= 0) && (z_new >= 0)) || ((z_old >= 0) && (z_new <= 0)))) return;
+    evfun_t e = *base;
+    e.zmode = 1;
+    const double r = brentq(&e, t_old, t);
+    double y[6];
+    dense_eval(e.dn, r, y);
+    const double R = kerr ? sqrt(y[1] * y[1] + e.rc->a * e.rc->a) * fabs(sin(y[3])) : sqrt(y[1] * y[1] + y[3] * y[3]);
+    if (!(R >= cr->r_in && R <= cr->r_out && r <= t_terminal)) return;
+    if (cr->n < cr->max_records) {
+        pack_end(y, cr->rec + (size_t)cr->n * cr->stride * 6);
+        cr->t[(size_t)cr->n * cr->stride] = r;
+    }
+    cr->n++;
+}
+
 /* ---------------------------------------------------------------------------------------
  * One ray, adaptive DP5(4): RungeKutta.__init__ (rk.py:84-104) + solve_ivp loop
  * (ivp.py:654-723) + _step_impl (rk.py:111-176)
  * ------------------------------------------------------------------------------------- */
 static void trace_dp54(const bhgo_params *p, const rayctx *rc, const double x0[3], const double k0[3], ray_result *res,
-                       sampler_t *sm)
+                       sampler_t *sm, crossings_t *cr)
 {
     double y[6] = {k0[0], x0[0], k0[1], x0[1], k0[2], x0[2]};
     double f[6], K[7][6], y_new[6], f_new[6];
@@ -678,10 +711,11 @@ static void trace_dp54(const bhgo_params *p, const rayctx *rc, const double x0[3
                   ((p->r_exit > 0.0) && (g_e <= 0) && (g_e_new >= 0)) ||
                   ((p->disk_r_out > 0.0) && (((z_old <= 0) && (z_new >= 0)) || ((z_old >= 0) && (z_new <= 0)))) ||
                   (p->n_spheres > 0);
-        if (any || sm) dense_build(&dn, t_old, t, y_old, K);
+        if (any || sm || cr) dense_build(&dn, t_old, t, y_old, K);
         if (any) {
             double t_root, y_root[6];
             uint32_t fl = check_events(p, g_h, g_h_new, g_e, g_e_new, y_old, y, &base, t_old, t, &t_root, y_root, &res->object_id);
+            if (cr) crossings_step(cr, &base, y_old, y, t_old, t, fl ? t_root : INFINITY);
             if (fl) {
                 res->flags |= fl;
                 t = t_root;
@@ -689,7 +723,8 @@ static void trace_dp54(const bhgo_params *p, const rayctx *rc, const double x0[3
                 if (sm) sampler_emit(sm, &dn, t);
                 break;
             }
-        }
+        } else if (cr)
+            crossings_step(cr, &base, y_old, y, t_old, t, INFINITY);
         if (sm) sampler_emit(sm, &dn, t);
         g_h = g_h_new;
         g_e = g_e_new;
@@ -844,7 +879,8 @@ static void bl_to_cart(const double q[3], const double u[3], double a, double x[
     for (int i = 0; i < 3; i++) k[i] = J[i][0] * u[0] + J[i][1] * u[1] + J[i][2] * u[2];
 }
 
-static void trace_one(const bhgo_params *p_in, const double x0[3], const double k0[3], ray_result *res, sampler_t *sm)
+static void trace_one(const bhgo_params *p_in, const double x0[3], const double k0[3], ray_result *res, sampler_t *sm,
+                      crossings_t *cr)
 {
     /* validate_tol (scipy _ivp/common.py:44-51): an rtol below 100 eps is raised to 100 eps (scipy warns and carries on) */
     bhgo_params pc = *p_in;
@@ -881,12 +917,19 @@ static void trace_one(const bhgo_params *p_in, const double x0[3], const double 
         if (p->method == BHGO_METHOD_RK4)
             trace_rk4(p, &rc, q, u, res, sm);
         else
-            trace_dp54(p, &rc, q, u, res, sm);
+            trace_dp54(p, &rc, q, u, res, sm, cr);
         /* res->end is {r, th, ph, ur, uth, uph}: back to Cartesian */
         double xe[3], ke[3];
         bl_to_cart(res->end, res->end + 3, a, xe, ke);
         memcpy(res->end, xe, sizeof(xe));
         memcpy(res->end + 3, ke, sizeof(ke));
+        if (cr)
+            for (uint32_t m = 0; m < cr->n && m < cr->max_records; m++) {
+                double *o = cr->rec + (size_t)m * cr->stride * 6;
+                bl_to_cart(o, o + 3, a, xe, ke);
+                memcpy(o, xe, sizeof(xe));
+                memcpy(o + 3, ke, sizeof(ke));
+            }
         if (sm)
             for (uint32_t j = 0; j < sm->next; j++) {
                 double qq[3], uu[3];
@@ -918,7 +961,7 @@ static void trace_one(const bhgo_params *p_in, const double x0[3], const double 
     if (p->method == BHGO_METHOD_RK4)
         trace_rk4(p, &rc, x0, k0, res, sm);
     else
-        trace_dp54(p, &rc, x0, k0, res, sm);
+        trace_dp54(p, &rc, x0, k0, res, sm, cr);
 }
 
 /* ---------------------------------------------------------------------------------------
@@ -952,7 +995,7 @@ int bhgo_trace(const bhgo_params *p, const double *x0, int x0_shared, const doub
     for (long long i = 0; i < nn; i++) {
         ray_result r;
         const double *xi = x0_shared ? x0 : x0 + 3 * i;
-        trace_one(p, xi, k0 + 3 * i, &r, NULL);
+        trace_one(p, xi, k0 + 3 * i, &r, NULL, NULL);
         memcpy(end + 6 * i, r.end, sizeof(double) * 6);
         if (flags) flags[i] = (uint8_t)r.flags;
         if (n_attempted) n_attempted[i] = r.n_attempted;
@@ -978,12 +1021,45 @@ int bhgo_trace_objects(const bhgo_params *p, const double *x0, int x0_shared, co
     for (long long i = 0; i < nn; i++) {
         ray_result r;
         r.object_id = -1;
-        trace_one(p, x0_shared ? x0 : x0 + 3 * i, k0 + 3 * i, &r, NULL);
+        trace_one(p, x0_shared ? x0 : x0 + 3 * i, k0 + 3 * i, &r, NULL, NULL);
         memcpy(end + 6 * i, r.end, sizeof(double) * 6);
         if (flags) flags[i] = (uint8_t)r.flags;
         if (n_attempted) n_attempted[i] = r.n_attempted;
         if (n_accepted) n_accepted[i] = r.n_accepted;
         if (object_id) object_id[i] = (r.flags == BHGO_FLAG_HIT_OBJECT) ? (int8_t)r.object_id : (int8_t)-1;
+    }
+    return 0;
+}
+
+/* Every disk crossing of a ray carried through the disk (the crossings_t rule above): end / flags / n_attempted / n_accepted /
+   t_end are those of bhgo_trace with the disk off; n_cross [n] counts every crossing, not saturated; cross [max_records][n][6]
+   (Cartesian) and t_cross [max_records][n] hold the first max_records and are left alone beyond them.  DP5(4), null rays, a
+   disk and no spheres: anything else is refused (-2), as the library refuses it. */
+int bhgo_trace_crossings(const bhgo_params *p, const double *x0, int x0_shared, const double *k0, size_t n,
+                         uint32_t max_records, double *end, uint8_t *flags, uint32_t *n_attempted, uint32_t *n_accepted,
+                         double *t_end, uint32_t *n_cross, double *cross, double *t_cross, int n_threads)
+{
+    if (!p || !x0 || !k0 || !end || !n_cross || !cross || !t_cross) return -1;
+    if (p->method != BHGO_METHOD_DP54 || p->time_like || p->n_spheres > 0 || !(p->disk_r_out > 0.0)) return -2;
+    bhgo_params off = *p;
+    off.disk_r_in = off.disk_r_out = 0.0;
+#ifdef _OPENMP
+    if (n_threads <= 0) n_threads = omp_get_max_threads();
+#else
+    n_threads = 1;
+#endif
+    long long nn = (long long)n;
+#pragma omp parallel for schedule(dynamic, 256) num_threads(n_threads)
+    for (long long i = 0; i < nn; i++) {
+        ray_result r;
+        crossings_t cr = {p->disk_r_in, p->disk_r_out, max_records, 0, n, cross + 6 * i, t_cross + i};
+        trace_one(&off, x0_shared ? x0 : x0 + 3 * i, k0 + 3 * i, &r, NULL, &cr);
+        memcpy(end + 6 * i, r.end, sizeof(double) * 6);
+        if (flags) flags[i] = (uint8_t)r.flags;
+        if (n_attempted) n_attempted[i] = r.n_attempted;
+        if (n_accepted) n_accepted[i] = r.n_accepted;
+        if (t_end) t_end[i] = r.t_end;
+        n_cross[i] = cr.n;
     }
     return 0;
 }
@@ -997,7 +1073,7 @@ int bhgo_trajectory(const bhgo_params *p, const double *x0, int x0_shared, const
     for (size_t i = 0; i < n; i++) {
         ray_result r;
         sampler_t sm = {T, 0, p->lambda_end, traj + i * 6 * (size_t)T};
-        trace_one(p, x0_shared ? x0 : x0 + 3 * i, k0 + 3 * i, &r, &sm);
+        trace_one(p, x0_shared ? x0 : x0 + 3 * i, k0 + 3 * i, &r, &sm, NULL);
         n_valid[i] = sm.next;
         if (flags) flags[i] = (uint8_t)r.flags;
     }

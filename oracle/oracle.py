@@ -102,6 +102,10 @@ def lib():
         L.bhgo_trajectory.restype = C.c_int
         L.bhgo_trajectory.argtypes = [C.POINTER(Params), dp, C.c_int, dp, C.c_size_t, C.c_uint32, dp,
                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]
+        L.bhgo_trace_crossings.restype = C.c_int
+        L.bhgo_trace_crossings.argtypes = [C.POINTER(Params), dp, C.c_int, dp, C.c_size_t, C.c_uint32, dp, C.POINTER(C.c_uint8),
+                                           C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), dp, C.POINTER(C.c_uint32), dp, dp,
+                                           C.c_int]
         L.bhgo_num_threads.restype = C.c_int
         _lib = L
     return _lib
@@ -143,6 +147,34 @@ def trace(k0, x0, n_threads=0, **kw):
             raise RuntimeError(f"bhgo_trace_objects failed: {rc}")
         out["object_id"] = obj
     return out
+
+
+def trace_crossings(k0, x0, max_records=16, n_threads=0, **kw):
+    """The ray carried through the disk: what trace() returns with the disk off, plus n_cross[N] (uint32, every crossing),
+    cross[max_records, N, 6] (Cartesian, NaN where there is none) and t_cross[max_records, N]."""
+    p = kw.pop("params", None) or make_params(**kw)
+    k0 = np.ascontiguousarray(np.atleast_2d(k0), dtype=np.float64)
+    x0 = np.ascontiguousarray(x0, dtype=np.float64)
+    n = k0.shape[0]
+    shared = 1 if x0.ndim == 1 else 0
+    if not shared:
+        assert x0.shape == (n, 3)
+    end = np.empty((n, 6))
+    flags = np.empty(n, np.uint8)
+    natt = np.empty(n, np.uint32)
+    nacc = np.empty(n, np.uint32)
+    tend = np.empty(n)
+    ncr = np.zeros(n, np.uint32)
+    cross = np.full((max_records, n, 6), np.nan)
+    tcr = np.full((max_records, n), np.nan)
+    u32 = C.POINTER(C.c_uint32)
+    rc = lib().bhgo_trace_crossings(C.byref(p), _dp(x0), shared, _dp(k0), n, max_records, _dp(end),
+                                    flags.ctypes.data_as(C.POINTER(C.c_uint8)), natt.ctypes.data_as(u32),
+                                    nacc.ctypes.data_as(u32), _dp(tend), ncr.ctypes.data_as(u32), _dp(cross), _dp(tcr), n_threads)
+    if rc != 0:
+        raise RuntimeError(f"bhgo_trace_crossings failed: {rc}")
+    return {"end": end, "flags": flags, "n_attempted": natt, "n_accepted": nacc, "t_end": tend, "n_cross": ncr, "cross": cross,
+            "t_cross": tcr}
 
 
 def trajectory(k0, x0, n_points, **kw):

@@ -204,3 +204,216 @@ def test_golden_conditions():
     assert tight[0, 2].sum() >= 4 and tight[1, 2].sum() >= 5
     tk = k["sens"][0, 0] <= BOUND_DISK[1] / COND
     assert tk.sum() >= 60 and tk[1].sum() >= 3
+
+
+# ---- the C oracle's crossings mode (oracle.trace_crossings) ------------------------------------------------------------------
+# What the GPU tests of tests/test_gpu_crossings_oracle.py hold the kernel to is held here, with no GPU, to the scipy records of
+# the two goldens, to the oracle's own disk-off trace and to live scipy in the settings the goldens lack.
+import crossings_reference as cx  # noqa: E402
+
+ORACLE_FORMS = [(0, 0.0), (1, 0.0), (2, 0.45)]
+ORACLE_FORM_IDS = ["christoffel", "reduced", "kerr"]
+COUNT_KEYS = ("n_cross", "flags", "n_attempted", "n_accepted")
+
+
+def _records_within(o, ref, S, kerr, keep=None):
+    """Every record of the reference is there and within BOUND_DISK + COND * S_i of it; nothing else is written."""
+    have = ~np.isnan(ref[..., 0])
+    if keep is not None:
+        have, o = have[:, keep], o[:, keep]
+        ref, S = ref[:, keep], S[:, keep]
+    assert np.array_equal(~np.isnan(o).any(2), have) and np.array_equal(~np.isnan(o).all(2), have)
+    diff = np.abs(o - ref).max(2)
+    tol = BOUND_DISK[1 if kerr else 0] + COND * S
+    assert np.all(diff[have] <= tol[have]), (diff[have] - tol[have]).max()
+    return float(diff[have].max(initial=0.0))
+
+
+@pytest.mark.parametrize("rhs,spin", ORACLE_FORMS, ids=ORACLE_FORM_IDS)
+def test_oracle_crossings_on_the_goldens(oracle, rhs, spin):
+    kerr = rhs == 2
+    g = load_golden("kerr_disk_crossings" if kerr else "disk_crossings")
+    fi = 0 if kerr else rhs
+    for d, (r_in, r_out) in enumerate(g["disks"]):
+        kw = dict(r_s=float(g["r_s"]), lambda_end=float(g["lambda_end"]), rtol=float(g["rtol"]), atol=float(g["atol"]),
+                  r_exit=0.0 if kerr else float(g["r_exit"]), rhs_form=rhs, spin=spin, disk_r_in=r_in, disk_r_out=r_out)
+        o = oracle.trace_crossings(g["k0"], g["x0"], max_records=4, **kw)
+        assert o["n_cross"].dtype == np.uint32 and o["cross"].shape == (4, len(g["k0"]), 6) and o["t_cross"].shape == (4, len(g["k0"]))
+        assert np.array_equal(o["n_cross"], g["n_cross"][fi, d]) and np.array_equal(o["flags"], g["flags"][fi])
+        assert np.array_equal(o["n_attempted"], g["n_attempted"][fi]) and np.array_equal(o["n_accepted"], g["n_accepted"][fi])
+        worst = _records_within(o["cross"], g["cross"][fi, d], g["sens"][fi, d], kerr)
+        print(f"{ORACLE_FORM_IDS[rhs]} disk {(r_in, r_out)}: worst |oracle - scipy| {worst:.3e}")
+        # the times are those of the records, in order, and none is later than the ray's end
+        have = ~np.isnan(o["t_cross"])
+        assert np.array_equal(have, ~np.isnan(o["cross"][..., 0]))
+        assert np.all(np.diff(o["t_cross"], axis=0)[have[1:]] > 0) and np.all((o["t_cross"] <= o["t_end"][None, :])[have])
+        # fewer records kept: the same count, the same first records
+        o2 = oracle.trace_crossings(g["k0"], g["x0"], max_records=2, **kw)
+        assert np.array_equal(o2["n_cross"], o["n_cross"]) and np.array_equal(o2["cross"], o["cross"][:2], equal_nan=True)
+
+
+def _golden_rays():
+    g, k = load_golden("disk_crossings"), load_golden("kerr_disk_crossings")
+    return {0: (g["k0"], g["x0"]), 1: (g["k0"], g["x0"]), 2: (k["k0"], k["x0"])}
+
+
+@pytest.mark.parametrize("r_exit", [0.0, 35.0])
+@pytest.mark.parametrize("rhs,spin", ORACLE_FORMS, ids=ORACLE_FORM_IDS)
+def test_oracle_crossings_leave_the_disk_off_trace_alone(oracle, rhs, spin, r_exit):
+    k0, x0 = _golden_rays()[rhs]
+    # (per-ray origins with every 7th inside the horizon, and a step budget that cuts some rays off)
+    x0 = x0.copy()
+    x0[::7] *= 0.02
+    for extra in (dict(), dict(max_steps=14), dict(rtol=1e-7, atol=1e-10, max_step=3.0)):
+        kw = dict(r_s=1.0, lambda_end=120.0, r_exit=r_exit, rhs_form=rhs, spin=spin, **extra)
+        off = oracle.trace(k0, x0, **kw)
+        o = oracle.trace_crossings(k0, x0, max_records=3, disk_r_in=1.2, disk_r_out=15.0, **kw)
+        for key in ("end", "flags", "n_attempted", "n_accepted", "t_end"):
+            assert np.array_equal(o[key], off[key]), key
+        inside = o["flags"] == 3
+        assert inside.sum() >= len(k0) // 7 and np.all(o["n_cross"][inside] == 0) and (o["n_cross"] > 0).sum() > 20
+        if "max_steps" in extra:
+            assert ((o["flags"] == 16) & (o["n_cross"] > 0)).sum() > 10
+
+
+def test_oracle_crossings_refuses_what_the_library_refuses(oracle):
+    k0, x0 = cx.tangent_ray()
+    for kw in (dict(method=1), dict(time_like=1), dict(spheres=[[8.0, 0.0, 0.0, 1.0]]), dict(disk_r_out=0.0)):
+        with pytest.raises(RuntimeError):
+            oracle.trace_crossings(k0, x0, **{**cx.MANY, **kw})
+
+
+# Kerr and the exit sphere: scipy_reference's Kerr solve has none, so the rule "a crossing counts only if it is not later than the
+# terminal event" is pinned in two links.  The oracle's r_exit = 0 solve is held to live scipy; the r_exit = 40 solve takes the
+# same steps up to the one that leaves the sphere (events play no part in step control), so its crossings must be the r_exit = 0
+# solve's with t_cross <= its own t_end, bit for bit.  The annulus reaches beyond the sphere, so that there is something to cut.
+KERR_EXIT = dict(r_s=1.0, lambda_end=120.0, rhs_form=2, disk_r_in=1.2, disk_r_out=80.0)
+KERR_EXIT_CAM = cx.inclined_camera(30.0, 75.0, y_off=0.5)
+
+
+@pytest.mark.parametrize("spin,seed", [(0.45, 0), (-0.3, 1)], ids=["a+0.45", "a-0.30"])
+def test_oracle_kerr_crossings_with_an_exit_sphere(oracle, spin, seed):
+    k0 = cx.exit_rays(KERR_EXIT_CAM, 40, np.random.default_rng(300 + seed))
+    kw = dict(spin=spin, **KERR_EXIT)
+    free = oracle.trace_crossings(k0, KERR_EXIT_CAM, max_records=8, **kw)
+    ex = oracle.trace_crossings(k0, KERR_EXIT_CAM, max_records=8, r_exit=40.0, **kw)
+    assert np.all(free["n_cross"] <= 8) and (ex["flags"] == 8).sum() > 10
+    keep = free["t_cross"] <= ex["t_end"][None, :]                   # (NaN compares false)
+    assert np.array_equal(ex["n_cross"], keep.sum(0))
+    assert (ex["n_cross"] < free["n_cross"]).sum() >= 8              # the rule cut something
+    want = np.where(keep[..., None], free["cross"], np.nan)          # (kept records are a prefix: times ascend)
+    assert np.array_equal(ex["cross"], want, equal_nan=True) and np.array_equal(ex["t_cross"], np.where(keep, free["t_cross"], np.nan), equal_nan=True)
+    # the exit solve's end is the disk-off trace's
+    off = oracle.trace(k0, KERR_EXIT_CAM, r_exit=40.0, **{a: b for a, b in kw.items() if not a.startswith("disk")})
+    assert np.array_equal(off["t_end"], ex["t_end"])
+    # ... and the r_exit = 0 solve against live scipy
+    _against_live_scipy(oracle, k0, KERR_EXIT_CAM, 2, K=8, spin=spin, **{a: b for a, b in KERR_EXIT.items() if a != "rhs_form"})
+
+
+def _against_live_scipy(oracle, k0, x0, rhs, K=4, disk_r_in=1.2, disk_r_out=15.0, **par):
+    ref = cx.scipy_set(k0, x0, rhs, (disk_r_in, disk_r_out), K=K, **par)
+    o = oracle.trace_crossings(k0, x0, max_records=K, rhs_form=rhs, disk_r_in=disk_r_in, disk_r_out=disk_r_out, **par)
+    keep = ref["stable"]
+    assert (~keep).sum() <= 0.10 * len(keep), int((~keep).sum())     # the selection is the reference's alone
+    for key in COUNT_KEYS:
+        assert np.array_equal(o[key][keep], ref[key][keep]), key
+    worst = _records_within(o["cross"], ref["cross"], ref["sens"], rhs == 2, keep)
+    d = np.abs(o["t_cross"] - ref["t_cross"])[:, keep]
+    print(f"{ORACLE_FORM_IDS[rhs]} {par}: {int(keep.sum())} of {len(keep)} rays, {int((~np.isnan(ref['cross'][:, keep, 0])).sum())} records, "
+          f"crossings per ray up to {int(ref['n_cross'].max())}, worst |oracle - scipy| {worst:.3e}, worst |t| {np.nanmax(d, initial=0.0):.3e}")
+    return ref, o
+
+
+LIVE_CAM = cx.inclined_camera(20.0, 70.0, y_off=0.3)
+LIVE = {
+    "r_s=2": dict(r_s=2.0, scale=2.0),
+    "tight": dict(rtol=1e-6, atol=1e-9),
+    "max_step": dict(max_step=0.5),
+    "origins": dict(origins=True),
+}
+
+
+@pytest.mark.parametrize("rhs,spin", [(0, 0.0), (1, 0.0), (2, 0.45), (2, -0.49)], ids=["christoffel", "reduced", "kerr+0.45", "kerr-0.49"])
+@pytest.mark.parametrize("case", list(LIVE))
+def test_oracle_crossings_against_live_scipy(oracle, case, rhs, spin):
+    par = dict(LIVE[case])
+    scale = par.pop("scale", 1.0)                # r_s = 2: every length doubled
+    origins = par.pop("origins", False)
+    n = 40 if rhs != 1 else 20                   # (the reduced form shares everything but the right-hand side with the other)
+    rng = np.random.default_rng(700 + 10 * list(LIVE).index(case) + rhs)
+    cam = LIVE_CAM * scale
+    k0 = cx.camera_rays(cam, n, rng, r_s=scale)
+    x0 = cam
+    if origins:
+        x0 = cam[None, :] + rng.normal(size=(n, 3)) * 1.5
+    par.setdefault("r_s", 1.0)
+    if rhs == 2:
+        par["spin"] = spin * scale
+    else:
+        par["r_exit"] = 25.0 * scale
+    _against_live_scipy(oracle, k0, x0, rhs, disk_r_in=1.2 * scale, disk_r_out=15.0 * scale, lambda_end=60.0 * scale, **par)
+
+
+@pytest.mark.parametrize("rhs", [0, 1], ids=["christoffel", "reduced"])
+@pytest.mark.parametrize("rtol", list(cx.MANY_COUNTS))
+def test_oracle_counts_many_crossings(oracle, rtol, rhs):
+    k0, x0 = cx.tangent_ray()
+    want, steps = cx.MANY_COUNTS[rtol]
+    o = oracle.trace_crossings(k0, x0, max_records=4, rtol=rtol, atol=rtol * 1e-3, rhs_form=rhs, **cx.MANY)
+    assert (int(o["n_cross"][0]), int(o["n_attempted"][0])) == (want, steps)
+    assert not np.isnan(o["cross"]).any()                          # four kept of the five and more
+    full = oracle.trace_crossings(k0, x0, max_records=16, rtol=rtol, atol=rtol * 1e-3, rhs_form=rhs, **cx.MANY)
+    assert np.array_equal(full["cross"][:4], o["cross"]) and (~np.isnan(full["t_cross"])).sum() == want
+
+
+@pytest.mark.parametrize("rhs", [0, 1], ids=["christoffel", "reduced"])
+def test_oracle_starts_in_the_plane(oracle, rhs):
+    everywhere = dict(disk_r_in=1e-3, disk_r_out=1e3)
+    for b, events in cx.IN_PLANE_EVENTS.items():
+        for sign in (1.0, -1.0):
+            k0 = cx.unit([-1.0, 0.0, sign * b / 30.0])
+            o = oracle.trace_crossings(k0, cx.IN_PLANE_CAM, rhs_form=rhs, **everywhere, **cx.IN_PLANE)
+            assert int(o["n_cross"][0]) == events and o["t_cross"][0, 0] == 0.0
+            assert np.array_equal(o["cross"][0, 0], np.concatenate([cx.IN_PLANE_CAM, k0]))
+            s = cx.scipy_solve(k0, cx.IN_PLANE_CAM, rhs, (1e-3, 1e3), **cx.IN_PLANE)
+            assert s["n_cross"] == events and s["t_cross"][0] == 0.0
+            # the annulus widened to hold the start: that event counts; an annulus that ends short of it: it does not
+            wide = oracle.trace_crossings(k0, cx.IN_PLANE_CAM, rhs_form=rhs, disk_r_in=3.0, disk_r_out=30.0, **cx.IN_PLANE)
+            short = oracle.trace_crossings(k0, cx.IN_PLANE_CAM, rhs_form=rhs, disk_r_in=3.0, disk_r_out=29.0, **cx.IN_PLANE)
+            assert wide["t_cross"][0, 0] == 0.0 and int(wide["n_cross"][0]) == int(short["n_cross"][0]) + 1
+    k0 = cx.unit([-1.0, 4.0 / 30.0, 0.0])                          # in the plane for good: every step "crosses"
+    for disk, events in (((1e-3, 1e3), 12), ((3.0, 12.0), 5)):
+        o = oracle.trace_crossings(k0, cx.IN_PLANE_CAM, rhs_form=rhs, disk_r_in=disk[0], disk_r_out=disk[1], **cx.IN_PLANE)
+        s = cx.scipy_solve(k0, cx.IN_PLANE_CAM, rhs, disk, **cx.IN_PLANE)
+        assert int(o["n_cross"][0]) == events == s["n_cross"]
+        # (z is 0 throughout: each root is its step's start, a sum of step sizes)
+        assert np.allclose(o["t_cross"][:events, 0], s["t_cross"], rtol=1e-12, atol=0.0) and np.all(o["cross"][:events, 0, 2] == 0.0)
+
+
+def test_oracle_starts_in_the_plane_kerr(oracle):
+    for kz, events in cx.KERR_PLANE_EVENTS.items():
+        k0 = cx.unit([-1.0, 0.35, kz])
+        o = oracle.trace_crossings(k0, cx.KERR_PLANE_CAM, disk_r_in=1e-3, disk_r_out=1e3, **cx.KERR_PLANE)
+        s = cx.scipy_solve(k0, cx.KERR_PLANE_CAM, 2, (1e-3, 1e3), r_s=1.0, spin=0.45, lambda_end=50.0)
+        assert int(o["n_cross"][0]) == events == s["n_cross"]
+        assert int(o["n_attempted"][0]) == s["n_attempted"] and int(o["flags"][0]) == s["flags"]
+        if events:
+            assert o["t_cross"][0, 0] == s["t_cross"][0] and o["t_cross"][0, 0] < 1e-14
+            assert abs(np.hypot(o["cross"][0, 0, 0], o["cross"][0, 0, 1]) - np.sqrt(100.25)) < 1e-12
+
+
+def test_randomised_draws_are_well_conditioned(oracle):
+    """The twelve default draws of tests/test_gpu_crossings_oracle.py::test_randomised_crossings, on the oracle alone: at least 100
+    records per form move by no more than BOUND_DISK / COND under the perturbations, so that the fixed part of the bound is what
+    holds them (measured: 836, 1106 and 303), and every class of ray and setting is among the draws."""
+    tight = [0, 0, 0]
+    seen = set()
+    for seed in range(12):
+        k0, x0, K, kw = cx.fuzz_draw(seed)
+        o = oracle.trace_crossings(k0, x0, max_records=K, **kw)
+        S, _ = cx.oracle_sensitivity(oracle, k0, x0, o, K, **kw)
+        tight[kw["rhs_form"]] += int((S <= BOUND_DISK[1 if kw["rhs_form"] == 2 else 0] / COND).sum())
+        seen |= {a for a in ("rtol", "max_step", "r_exit", "max_steps") if a in kw} | ({"origins"} if np.ndim(x0) == 2 else set())
+        seen |= {f"flag{int(v)}" for v in np.unique(o["flags"])} | {f"K{K}"}
+    assert min(tight) >= 100, tight
+    assert seen >= {"rtol", "max_step", "r_exit", "max_steps", "origins", "flag1", "flag3", "flag4", "flag8", "flag16", "K1", "K2", "K3", "K4"}, seen

@@ -3,9 +3,12 @@
 crossing), its layer arrays through the per-ray redshift call, the layered shade against the numpy restatement
 (tests/disk_layers_reference.py, fed the device's records) in its five instances, and the refusals.
 
-The Kerr golden has no exit sphere (the scipy reference's Kerr solve has none; the Schwarzschild golden has r_exit = 35): golden
-parity therefore never sees a Kerr crossing that shares its step with an exit event (the rule root <= terminal root).  For Kerr
-that rule is covered against the device's own disk-off and opaque traces only (tests 2 and 3, exit sphere at 40)."""
+The Kerr golden has no exit sphere (the scipy reference's Kerr solve has none; the Schwarzschild golden has r_exit = 35, beyond
+its disks): golden parity never sees a crossing that shares its step with an exit event (the rule root <= terminal root), and
+tests 2 and 3 (exit sphere at 40) compare the device with its own disk-off and opaque traces.  That rule, in all three forms, and
+everything else the goldens' one parameter set leaves out is held to the C oracle's crossings mode by
+tests/test_gpu_crossings_oracle.py (4133 Kerr rays with the exit sphere at 40 among them); the oracle's Kerr crossings with an
+exit sphere are pinned on the CPU by tests/test_disk_crossings_host.py."""
 import os
 import sys
 
