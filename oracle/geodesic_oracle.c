@@ -1070,9 +1070,12 @@ int bhgo_trajectory(const bhgo_params *p, const double *x0, int x0_shared, const
                     double *traj, uint32_t *n_valid, uint8_t *flags)
 {
     if (!p || !x0 || !k0 || !traj || !n_valid || T < 2) return -1;
-    for (size_t i = 0; i < n; i++) {
+    long long nn = (long long)n;
+    /* (rays are independent and write their own block: the same bits with any number of threads) */
+#pragma omp parallel for schedule(dynamic, 16)
+    for (long long i = 0; i < nn; i++) {
         ray_result r;
-        sampler_t sm = {T, 0, p->lambda_end, traj + i * 6 * (size_t)T};
+        sampler_t sm = {T, 0, p->lambda_end, traj + (size_t)i * 6 * (size_t)T};
         trace_one(p, x0_shared ? x0 : x0 + 3 * i, k0 + 3 * i, &r, &sm, NULL);
         n_valid[i] = sm.next;
         if (flags) flags[i] = (uint8_t)r.flags;

@@ -370,8 +370,10 @@ KERR_HORIZON_MARGIN = 1e-3  # terminal event at r = r_plus (1 + margin): BL coor
 
 
 def trace_ray_kerr(k0, x0, M=0.5, a=0.45, lambda_end=50.0, max_step=np.inf, rtol=1e-3, atol=1e-6, method="RK45",
-                   disk=None, time_like=False, spheres=None):
+                   disk=None, time_like=False, spheres=None, nr_points_curve=None):
     """One null geodesic in Kerr; state y = [ur, r, uth, th, uph, ph]; Cartesian in, Cartesian out.
+    nr_points_curve=T: as trace_ray's -- t_eval = linspace(0, lambda_end, T), and the samples solve_ivp emits, each converted
+    with bl_to_cart, come back as out["curve"] [6, m] (x, y, z, k_x, k_y, k_z rows); the step count is then not kept.
     disk=(R_in, R_out): thin disk in the equatorial plane z = r cos(th) = 0, annulus in the cylindrical
     radius sqrt(x^2 + y^2) = sqrt(r^2 + a^2) |sin th|; a NON-terminal event g = cos(th), the first crossing
     inside the annulus ends the ray there (same rule as trace_ray's disk)."""
@@ -414,7 +416,8 @@ def trace_ray_kerr(k0, x0, M=0.5, a=0.45, lambda_end=50.0, max_step=np.inf, rtol
 
         events.append(ev_disk)
     y0 = np.array([u0[0], q0[0], u0[1], q0[1], u0[2], q0[2]])
-    sol = solve_ivp(rhs, (0.0, lambda_end), y0, method=method, events=events, max_step=max_step, rtol=rtol, atol=atol)
+    t_eval = np.linspace(0.0, lambda_end, nr_points_curve) if nr_points_curve else None
+    sol = solve_ivp(rhs, (0.0, lambda_end), y0, method=method, events=events, max_step=max_step, rtol=rtol, atol=atol, t_eval=t_eval)
     n_acc_disk = None
     if sol.status == 1:
         cands = [(sol.t_events[i][-1], i) for i in range(1 + n_obj) if len(sol.t_events[i]) > 0]
@@ -437,7 +440,10 @@ def trace_ray_kerr(k0, x0, M=0.5, a=0.45, lambda_end=50.0, max_step=np.inf, rtol
     xe, ke = bl_to_cart((ye[1], ye[3], ye[5]), (ye[0], ye[2], ye[4]), a)
     out.update(flags=flags, end=np.concatenate([xe, ke]), end_bl=np.array([ye[1], ye[3], ye[5], ye[0], ye[2], ye[4]]),
                t_end=float(te), nfev=int(sol.nfev), n_attempted=(int(sol.nfev) - 2) // 6 if method == "RK45" else -1,
-               n_accepted=len(sol.t) - 1, E=E, L=L, sol=sol)
+               n_accepted=(len(sol.t) - 1) if t_eval is None else -1, E=E, L=L, sol=sol)
+    if t_eval is not None:
+        cols = [np.concatenate(bl_to_cart((y[1], y[3], y[5]), (y[0], y[2], y[4]), a)) for y in sol.y.T]
+        out["curve"] = np.array(cols).reshape(-1, 6).T
     if n_acc_disk is not None:
         out["n_accepted"] = n_acc_disk
         out["n_attempted"] = -1  # scipy integrated on past the disk
