@@ -64,11 +64,21 @@ EXPORTS = (
     "bhg_object_motion_size", "bhg_redshift_motion_device", "bhg_redshift_motion_host", "bhg_shade_scene_moving_device",
     "bhg_frame_set_object_motion",
     "bhg_math_probe",
-    "bhg_trace_start_device", "bhg_start_steps_match",
+    "bhg_trace_start_device", "bhg_start_steps_match", "bhg_trace_prefix_device", "bhg_prefix_clearance",
     "bhg_trace_crossings_device", "bhg_trace_crossings", "bhg_disk_layers_size", "bhg_shade_disk_layers_device",
 )
 MAX_CROSSINGS = 4   # BHG_MAX_CROSSINGS: disk crossings a crossings trace stores per ray (BHG_DISK_CROSSINGS)
 START_NONE, START_RECORD, START_REPLAY = 0, 1, 2   # BHG_START_*: the rays' initial steps kept across calls (BHG_START_STEPS)
+# BHG_PREFIX_*: the rays' start-up records kept across calls (BHG_START_PREFIX)
+PREFIX_NONE, PREFIX_RECORD, PREFIX_REPLAY = 0, 1, 2
+PREFIX_K_MAX, PREFIX_BYTES_PER_RAY = 4, 112
+
+
+class Prefix(C.Structure):
+    """bhg_prefix: d_records (device address), rho, mode in, used out (include/bhgeo.h has the rules)."""
+    _fields_ = [("d_records", C.c_void_p), ("rho", C.c_double), ("mode", C.c_int32), ("used", C.c_int32)]
+
+
 PROBE_FMA, PROBE_STEP_MIX = 0, 1
 # bhg_math_probe: op -> (doubles in, doubles out) per element
 MATH_RCP_NEWTON, MATH_RCP_NR, MATH_RSQRT_NR, MATH_SQRT_NR, MATH_ATAN2_FAST, MATH_SINCOS_PI4, MATH_RCP3_NR, MATH_KERR_CART_TO_BL = range(8)
@@ -405,6 +415,15 @@ def load():
     L.bhg_trace_start_device.argtypes = [C.c_void_p, C.POINTER(Params), _dp, C.c_int32, _dp, C.c_void_p, C.c_void_p, C.c_size_t,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_int32, C.c_void_p]
+    # (an addition within ABI 10, found by symbol: a library built before it -- BHGEO_LIB, an A/B against an older build -- serves
+    # everything else, and the owners of a start cache then keep the start steps alone: has_start_prefix())
+    if hasattr(L, "bhg_trace_prefix_device"):
+        L.bhg_trace_prefix_device.restype = C.c_int
+        L.bhg_trace_prefix_device.argtypes = [C.c_void_p, C.POINTER(Params), _dp, C.c_int32, _dp, C.c_void_p, C.c_void_p, C.c_size_t,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_int32, C.POINTER(Prefix), C.c_void_p]
+        L.bhg_prefix_clearance.restype = C.c_double
+        L.bhg_prefix_clearance.argtypes = [C.POINTER(Params), _dp, C.c_int32, _dp]
     L.bhg_start_steps_match.restype = C.c_int
     L.bhg_start_steps_match.argtypes = [C.POINTER(Params), C.POINTER(Params)]
     L.bhg_shade_dir_device.restype = C.c_int
@@ -635,6 +654,19 @@ def load():
 def start_steps_match(a: "Params", b: "Params") -> bool:
     """bhg_start_steps_match: do the two parameter sets give every ray the same initial step?  (The library holds the list.)"""
     return bool(load().bhg_start_steps_match(C.byref(a), C.byref(b)))
+
+
+def has_start_prefix() -> bool:
+    """Does the loaded library know the rays' start-up records (bhg_trace_prefix_device)?"""
+    return hasattr(load(), "bhg_trace_prefix_device")
+
+
+def prefix_clearance(params: "Params", x0, spheres=None) -> float:
+    """bhg_prefix_clearance: distance from x0 to the nearest event surface of a call with these parameters and spheres."""
+    sp = None if spheres is None else _spheres_array(spheres)
+    xs = (C.c_double * 3)(*[float(v) for v in x0])
+    return float(load().bhg_prefix_clearance(C.byref(params), None if sp is None or not len(sp) else _np_dp(sp),
+                                             0 if sp is None else len(sp), xs))
 
 
 def _check(rc):
@@ -1151,10 +1183,19 @@ class Context:
 
     # -- device buffers (raw addresses, e.g. torch.Tensor.data_ptr()) -------------------
     def _trace_start_device(self, params, n, d_k0, d_end, d_end_dir, xs, d_x0, d_flags, d_n_steps, d_n_accepted, stream, spheres,
-                            d_object_id, d_start_steps, start_mode):
+                            d_object_id, d_start_steps, start_mode, prefix=None):
         """bhg_trace_start_device: the three device trace calls in one, with the rays' initial steps recorded into or
-        replayed from d_start_steps [n] float64 (start_mode START_RECORD / START_REPLAY; include/bhgeo.h has the rules)."""
+        replayed from d_start_steps [n] float64 (start_mode START_RECORD / START_REPLAY; include/bhgeo.h has the rules).
+        prefix: a Prefix -- bhg_trace_prefix_device, the same call with the rays' start-up records; its rho / used are filled."""
         sp = None if spheres is None else _spheres_array(spheres)
+        if prefix is not None:
+            _check(load().bhg_trace_prefix_device(self._h, C.byref(params), None if sp is None else _np_dp(sp),
+                                                  0 if sp is None else len(sp), xs, C.c_void_p(d_x0 or None), C.c_void_p(d_k0), int(n),
+                                                  C.c_void_p(d_end or None), C.c_void_p(d_end_dir or None), C.c_void_p(d_flags or None),
+                                                  C.c_void_p(d_n_steps or None), C.c_void_p(d_n_accepted or None),
+                                                  C.c_void_p(d_object_id or None), C.c_void_p(d_start_steps or None), int(start_mode),
+                                                  C.byref(prefix), C.c_void_p(stream or None)))
+            return
         _check(load().bhg_trace_start_device(self._h, C.byref(params), None if sp is None else _np_dp(sp), 0 if sp is None else len(sp),
                                              xs, C.c_void_p(d_x0 or None), C.c_void_p(d_k0), int(n), C.c_void_p(d_end or None),
                                              C.c_void_p(d_end_dir or None), C.c_void_p(d_flags or None),
@@ -1163,14 +1204,15 @@ class Context:
                                              C.c_void_p(stream or None)))
 
     def trace_device(self, params: Params, n, d_k0, d_end, x0_shared=None, d_x0=0, d_flags=0,
-                     d_n_steps=0, d_n_accepted=0, stream=0, spheres=None, d_object_id=0, d_start_steps=0, start_mode=START_NONE):
-        """d_start_steps, start_mode: see _trace_start_device; without them the plain calls of always."""
+                     d_n_steps=0, d_n_accepted=0, stream=0, spheres=None, d_object_id=0, d_start_steps=0, start_mode=START_NONE,
+                     prefix=None):
+        """d_start_steps, start_mode, prefix: see _trace_start_device; without them the plain calls of always."""
         xs = None
         if x0_shared is not None:
             xs = (C.c_double * 3)(*[float(v) for v in x0_shared])
-        if start_mode != START_NONE:
+        if start_mode != START_NONE or prefix is not None:
             return self._trace_start_device(params, n, d_k0, d_end, 0, xs, d_x0, d_flags, d_n_steps, d_n_accepted, stream, spheres,
-                                            d_object_id, d_start_steps, start_mode)
+                                            d_object_id, d_start_steps, start_mode, prefix)
         if spheres is not None:
             sp = _spheres_array(spheres)
             _check(load().bhg_trace_objects_device(self._h, C.byref(params), _np_dp(sp), len(sp), xs,
@@ -1209,17 +1251,17 @@ class Context:
             None if th is None else C.byref(th), None if layers is None else C.byref(layers), C.c_void_p(stream or None)))
 
     def trace_dir_device(self, params: Params, n, d_k0, d_end_dir, x0_shared=None, d_x0=0, d_flags=0,
-                         d_n_steps=0, d_n_accepted=0, stream=0, d_start_steps=0, start_mode=START_NONE):
+                         d_n_steps=0, d_n_accepted=0, stream=0, d_start_steps=0, start_mode=START_NONE, prefix=None):
         """bhg_trace_dir_device: like trace_device, but only the direction half of the end states is written
         (d_end_dir [n][3]) -- what a sky frame consumes."""
         xs = None
         if x0_shared is not None:
             xs = (C.c_double * 3)(*[float(v) for v in x0_shared])
-        if start_mode != START_NONE:
+        if start_mode != START_NONE or prefix is not None:
             if not d_end_dir:
                 raise ValueError("end_dir is NULL")
             return self._trace_start_device(params, n, d_k0, 0, d_end_dir, xs, d_x0, d_flags, d_n_steps, d_n_accepted, stream, None,
-                                            0, d_start_steps, start_mode)
+                                            0, d_start_steps, start_mode, prefix)
         _check(load().bhg_trace_dir_device(self._h, C.byref(params), xs, C.c_void_p(d_x0 or None),
                                            C.c_void_p(d_k0), int(n), C.c_void_p(d_end_dir),
                                            C.c_void_p(d_flags or None), C.c_void_p(d_n_steps or None),

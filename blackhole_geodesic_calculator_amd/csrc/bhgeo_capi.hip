@@ -23,6 +23,7 @@
 
 #include "../../include/bhgeo.h"
 #include "geodesic_kernels.h"
+#include "prefix_clearance.h"
 
 static_assert(BHG_FLAG_HIT_HORIZON == bhg::BHG_FLAG_HIT_HORIZON_, "flag mismatch");
 static_assert(BHG_FLAG_START_INSIDE == bhg::BHG_FLAG_START_INSIDE_, "flag mismatch");
@@ -1081,13 +1082,20 @@ struct CrossOut {
 int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres, int32_t n_spheres,
                      const double *x0_shared, const double *d_x0, const double *d_k0, size_t n, double *d_end,
                      uint8_t *d_flags, uint32_t *d_n_steps, uint32_t *d_n_accepted, int8_t *d_object_id, void *stream,
-                     double *d_end_dir, double *d_start_steps, int32_t start_mode, const CrossOut *cr = nullptr)
+                     double *d_end_dir, double *d_start_steps, int32_t start_mode, const CrossOut *cr = nullptr,
+                     bhg_prefix *pf = nullptr)
 {
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
     int rc = validate(p);
     if (rc != BHG_OK) return rc;
     rc = validate_spheres(p, spheres, n_spheres);
     if (rc != BHG_OK) return rc;
+    if (pf) {
+        pf->used = BHG_PREFIX_NONE;
+        if (pf->mode != BHG_PREFIX_NONE && pf->mode != BHG_PREFIX_RECORD && pf->mode != BHG_PREFIX_REPLAY)
+            return fail(BHG_E_INVALID, "prefix mode must be BHG_PREFIX_NONE, BHG_PREFIX_RECORD or BHG_PREFIX_REPLAY");
+        if (n && pf->mode != BHG_PREFIX_NONE && !pf->d_records) return fail(BHG_E_INVALID, "prefix mode asks for d_records, which is NULL");
+    }
     if (start_mode != BHG_START_NONE && start_mode != BHG_START_RECORD && start_mode != BHG_START_REPLAY)
         return fail(BHG_E_INVALID, "start_mode must be BHG_START_NONE, BHG_START_RECORD or BHG_START_REPLAY");
     if (n == 0) return BHG_OK;
@@ -1175,6 +1183,22 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres,
     // the rays' initial steps kept by their owner (the DP5(4) kernels' queue fill; RK4 has none and never looks)
     a.start_h = start_mode != BHG_START_NONE ? d_start_steps : nullptr;
     a.start_mode = start_mode;
+    // the rays' start-up records kept by their owner: shared-origin calls of DP5(4) with the two Cartesian null forms, one launch
+    // (the planes' stride is the launch's n), a step budget the records cannot exhaust.  Anything else ignores them, as RK4
+    // ignores the start steps, and says so in pf->used.
+    bool pf_record = false;
+    double pf_rho = 0.0;
+    if (pf && pf->mode != BHG_PREFIX_NONE && !cr && !d_x0 && p->method == BHG_METHOD_DP54 &&
+        (rhs_id == bhg::BHG_RHS_CHRISTOFFEL_ || rhs_id == bhg::BHG_RHS_REDUCED_) && a.max_steps > (uint32_t)BHG_PREFIX_K_MAX) {
+        const double clear = bhg::prefix_clearance(a.r_hor, a.r_exit, a.disk_r_out > 0.0, spheres, n_spheres, x0_shared);
+        if (pf->mode == BHG_PREFIX_RECORD) {
+            pf_rho = bhg::prefix_rho(clear, x0_shared);
+            pf_record = pf_rho > 0.0;
+        } else if (bhg::prefix_replay_ok(clear, pf->rho)) {
+            a.prefix = (const double2 *)pf->d_records;
+            pf->used = BHG_PREFIX_REPLAY;
+        }
+    }
     // kernel variant: bit 0 exit sphere, bit 1 disk, bit 2 objects.  With objects: 5 = exit sphere and no disk (the
     // orbiting-sphere frames), otherwise 7, which tests for the exit sphere and the disk at run time
     int evt = n_spheres > 0 ? ((has_exit && !(p->disk_r_out > 0.0)) ? 5 : 7)
@@ -1231,6 +1255,12 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres,
         // ONE persistent launch finishes every ray: events are resolved and rays resumed inside the trace kernel, so
         // the call only enqueues (Kerr: trace, finalize) and returns
         if (!c->counters_clean) HIP_TRY(hipMemsetAsync(c->counter, 0, 2 * 8 * 256, s));   // first call, or after a failed enqueue
+        if (pf_record) {
+            // the recording pass, in front of the trace of always (which starts its rays itself: the records are for later calls)
+            HIP_TRY(bhg::launch_record_prefix(a, rhs_id, pf->d_records, pf_rho, s));
+            pf->rho = pf_rho;
+            pf->used = BHG_PREFIX_RECORD;
+        }
         c->counters_clean = false;
         HIP_TRY(bhg::launch_trace(a, p->method, rhs_id, evt, (int)grid, s, c->profiling ? c->ev : nullptr));
         c->counter_set ^= 1;      // (the launch is in the stream: the next call of this context counts on the set it zeroes)
@@ -1267,11 +1297,12 @@ int trace_device_impl(bhg_context *c, const bhg_params *p, const double *spheres
                       const double *x0_shared, const double *d_x0, const double *d_k0, size_t n, double *d_end,
                       uint8_t *d_flags, uint32_t *d_n_steps, uint32_t *d_n_accepted, int8_t *d_object_id, void *stream,
                       double *d_end_dir = nullptr, double *d_start_steps = nullptr, int32_t start_mode = BHG_START_NONE,
-                      const CrossOut *cr = nullptr)
+                      const CrossOut *cr = nullptr, bhg_prefix *pf = nullptr)
 {
     if (n <= bhg::BHG_MAX_RAYS_PER_LAUNCH)
         return trace_device_one(c, p, spheres, n_spheres, x0_shared, d_x0, d_k0, n, d_end, d_flags, d_n_steps, d_n_accepted,
-                                d_object_id, stream, d_end_dir, d_start_steps, start_mode, cr);
+                                d_object_id, stream, d_end_dir, d_start_steps, start_mode, cr, pf);
+    if (pf) pf->used = BHG_PREFIX_NONE;    // (a split call: the records' planes are strided by ONE launch's ray count)
     if (!p) return fail(BHG_E_INVALID, "params is NULL");
     if (n > 0xFFFFFFFFull) return fail(BHG_E_INVALID, "n must be < 2^32 per call");
     bhg_params q = *p;
@@ -1331,6 +1362,26 @@ int bhg_trace_start_device(bhg_context *c, const bhg_params *p, const double *sp
     if (n && !d_end && !d_end_dir) return fail(BHG_E_INVALID, "end / end_dir is NULL");
     return trace_device_impl(c, p, spheres, n_spheres, x0_shared, d_x0, d_k0, n, d_end, d_flags, d_n_steps, d_n_accepted,
                              d_object_id, stream, d_end ? nullptr : d_end_dir, d_start_steps, start_mode);
+}
+
+int bhg_trace_prefix_device(bhg_context *c, const bhg_params *p, const double *spheres, int32_t n_spheres,
+                            const double *x0_shared, const double *d_x0, const double *d_k0, size_t n, double *d_end,
+                            double *d_end_dir, uint8_t *d_flags, uint32_t *d_n_steps, uint32_t *d_n_accepted,
+                            int8_t *d_object_id, double *d_start_steps, int32_t start_mode, bhg_prefix *prefix, void *stream)
+{
+    if (n && !d_end && !d_end_dir) return fail(BHG_E_INVALID, "end / end_dir is NULL");
+    if (!prefix) return fail(BHG_E_INVALID, "prefix is NULL");
+    return trace_device_impl(c, p, spheres, n_spheres, x0_shared, d_x0, d_k0, n, d_end, d_flags, d_n_steps, d_n_accepted,
+                             d_object_id, stream, d_end ? nullptr : d_end_dir, d_start_steps, start_mode, nullptr, prefix);
+}
+
+double bhg_prefix_clearance(const bhg_params *p, const double *spheres, int32_t n_spheres, const double *x0)
+{
+    if (!p || !x0 || n_spheres < 0 || (n_spheres > 0 && !spheres)) return 0.0;
+    bhg::TraceArgs a;
+    std::memset(&a, 0, sizeof(a));
+    fill_trace_args(a, p, nullptr, 0);
+    return bhg::prefix_clearance(a.r_hor, a.r_exit, a.disk_r_out > 0.0, spheres, n_spheres, x0);
 }
 
 // THE list of what a ray's initial step depends on beside the ray itself (initial_record, geodesic_kernels.hip): the

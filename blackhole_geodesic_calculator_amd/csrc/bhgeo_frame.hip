@@ -190,6 +190,8 @@ struct Shard {
     size_t P = 0, n = 0;
     DevBuf pixels_d, jitter_d, k0, end, dir, flags, steps, acc, obj, slab, sky, disk_tex;
     DevBuf start_h;                 // [n] doubles beside k0: the rays' initial steps, kept from render to render (BHG_START_STEPS)
+    DevBuf start_rec;               // the rays' start-up records (BHG_START_PREFIX: 112 B per ray), written by the render that records
+    double start_rho = 0.0;         // start_h, for the ball of this radius about start_origin; 0 = none are held
     DevBuf otex[BHG_MAX_SPHERES];   // the object textures (bhg_frame_set_object_textures), slot by slot
     hipEvent_t done = nullptr;
     bool rays_ready = false;
@@ -443,7 +445,8 @@ void destroy_frame(bhg_frame *f)
         if (s.comm && rccl().ok()) (void)rccl().CommDestroy(s.comm);
     for (auto &s : f->sh) {
         (void)hipSetDevice(s.device);
-        for (DevBuf *b : {&s.pixels_d, &s.jitter_d, &s.k0, &s.end, &s.dir, &s.flags, &s.steps, &s.acc, &s.obj, &s.slab, &s.sky, &s.disk_tex})
+        for (DevBuf *b : {&s.pixels_d, &s.jitter_d, &s.k0, &s.end, &s.dir, &s.flags, &s.steps, &s.acc, &s.obj, &s.slab, &s.sky, &s.disk_tex,
+                           &s.start_h, &s.start_rec})
             b->release();
         for (DevBuf &b : s.otex) b.release();
         if (s.done) (void)hipEventDestroy(s.done);
@@ -774,6 +777,8 @@ try {
     if (prm.order_blocks == 0 && S > 1) prm.order_blocks = (uint32_t)S;   // the rays are S blocks of P (sample-major)
     const char *sc_env = std::getenv("BHGEO_START_CACHE");   // "0": every render works the initial steps out (A/B, short memory)
     const bool start_cache = !(sc_env && sc_env[0] == '0' && sc_env[1] == 0);
+    const char *sp_env = std::getenv("BHGEO_START_PREFIX");  // "0": the start steps alone, no start-up records (A/B, 112 B per ray less)
+    const bool start_prefix = start_cache && !(sp_env && sp_env[0] == '0' && sp_env[1] == 0);
     const bool redshift = f->rs.apply != 0;
     if (redshift) {   // (refused before anything is enqueued)
         bhg::RedshiftParams rp;
@@ -845,15 +850,30 @@ try {
             s.start_ready = false;
             BHG_TRY(s.start_h.ensure(s.device, s.n * sizeof(double)));
             start_mode = keep ? BHG_START_REPLAY : BHG_START_RECORD;
+            if (!keep) s.start_rho = 0.0;
+        }
+        // ... and so do their start-up records: written by the render that records the steps, handed to every later one with
+        // their rho -- the library holds each render's scene against it (an object sphere may have moved in) and says in
+        // pf.used what it did
+        bhg_prefix pf = {nullptr, 0.0, BHG_PREFIX_NONE, BHG_PREFIX_NONE};
+        if (start_prefix) {
+            BHG_TRY(s.start_rec.ensure(s.device, s.n * (size_t)BHG_PREFIX_BYTES_PER_RAY));
+            pf.d_records = s.start_rec.as<char>();
+            pf.rho = s.start_rho;
+            pf.mode = start_mode == BHG_START_RECORD ? BHG_PREFIX_RECORD : (s.start_rho > 0.0 ? BHG_PREFIX_REPLAY : BHG_PREFIX_NONE);
+            s.start_rho = 0.0;
+        } else {
+            s.start_rho = 0.0;
         }
         if (dir_only) BHG_TRY(s.dir.ensure(s.device, s.n * 3 * sizeof(double)));
         else BHG_TRY(s.end.ensure(s.device, s.n * 6 * sizeof(double)));
         if (has_obj) BHG_TRY(s.obj.ensure(s.device, s.n));
-        BHG_TRY(bhg_trace_start_device(s.ctx, &prm, has_obj ? &f->scene.spheres[0][0] : nullptr, has_obj ? f->scene.n_spheres : 0,
-                                       f->cam.origin, nullptr, s.k0.as<double>(), s.n, dir_only ? nullptr : s.end.as<double>(),
-                                       dir_only ? s.dir.as<double>() : nullptr, s.flags.as<uint8_t>(), s.steps.as<uint32_t>(),
-                                       s.acc.as<uint32_t>(), has_obj ? s.obj.as<int8_t>() : nullptr, s.start_h.as<double>(),
-                                       start_mode, s.stream));
+        BHG_TRY(bhg_trace_prefix_device(s.ctx, &prm, has_obj ? &f->scene.spheres[0][0] : nullptr, has_obj ? f->scene.n_spheres : 0,
+                                        f->cam.origin, nullptr, s.k0.as<double>(), s.n, dir_only ? nullptr : s.end.as<double>(),
+                                        dir_only ? s.dir.as<double>() : nullptr, s.flags.as<uint8_t>(), s.steps.as<uint32_t>(),
+                                        s.acc.as<uint32_t>(), has_obj ? s.obj.as<int8_t>() : nullptr, s.start_h.as<double>(),
+                                        start_mode, &pf, s.stream));
+        if (start_prefix) s.start_rho = pf.mode == BHG_PREFIX_RECORD ? (pf.used == BHG_PREFIX_RECORD ? pf.rho : 0.0) : pf.rho;
         if (start_cache) {
             s.start_prm = prm;
             std::memcpy(s.start_origin, f->cam.origin, sizeof(s.start_origin));

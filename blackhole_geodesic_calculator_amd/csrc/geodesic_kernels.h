@@ -42,6 +42,7 @@ constexpr int BHG_RHS_KERR_BL_ = 2;
 constexpr int32_t BHG_START_NONE_ = 0;      // TraceArgs::start_mode: every call works its rays' initial steps out
 constexpr int32_t BHG_START_RECORD_ = 1;    // ... and stores them in start_h
 constexpr int32_t BHG_START_REPLAY_ = 2;    // start_h holds them (a recording call on the same rays and matching parameters)
+constexpr int BHG_PREFIX_K_MAX_ = 4;        // accepted steps a start-up record holds at most (BHG_PREFIX_K_MAX)
 // rays per trace launch: the kernels form a ray's result offsets (idx * 48 at most) in 32 bits
 constexpr uint64_t BHG_MAX_RAYS_PER_LAUNCH = 1ull << 26;
 
@@ -92,6 +93,10 @@ struct TraceArgs {
     double *cross;               // [max_cross][cross_stride][6]: record m of ray i, Cartesian, at (m * cross_stride + i) * 6
     uint8_t *n_cross;            // [n]: crossings counted (saturating at 255), stored or not
     uint64_t cross_stride;       // rays per layer of cross: the CALL's ray count (a launch may be a part of a call)
+    // the rays' start-up records kept across calls (the queue fill of the DP5(4) kernels of the two Cartesian null forms; no other
+    // kernel looks): last, so that no other member moves
+    const double2 *prefix;       // nullptr, or [7][n] 16-byte planes written by record_prefix_kernel for THESE rays and a ball
+                                 // of radius rho about x0s that this call's event surfaces stay clear of
 };
 
 // the moving observer of the observer camera (frame_kernels.hip): on = 0 is the reference's camera
@@ -307,6 +312,9 @@ hipError_t trace_occupancy(int method, int rhs, int evt, int *blocks_per_cu);
 hipError_t launch_trace_crossings(const TraceArgs &a, int rhs, hipStream_t s);
 // ... its Kerr instance, in the Kerr translation unit; the caller runs launch_kerr_finalize on the end records afterwards
 hipError_t launch_trace_crossings_kerr(const TraceArgs &a, hipStream_t s);
+// the recording pass of the start-up records (record_prefix_kernel: one lane per ray; rhs Christoffel or reduced, a.x0 == nullptr):
+// rec [7][a.n] 16-byte planes, rho the radius about a.x0s the recorded steps stay inside
+hipError_t launch_record_prefix(const TraceArgs &a, int rhs, void *rec, double rho, hipStream_t s);
 // Kerr: after the last pass of a call, Boyer-Lindquist end states -> Cartesian
 hipError_t launch_kerr_finalize(const TraceArgs &a, double *dir_out, hipStream_t s);
 // the Kerr instantiations live in their own translation unit (geodesic_kernels_kerr.hip: same source, same flags --

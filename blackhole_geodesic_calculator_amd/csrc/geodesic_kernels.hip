@@ -1076,6 +1076,14 @@ __device__ __forceinline__ void initial_record(const TraceArgs &A, const Metric 
 // a replaying call loads it -- with k0, in front of the vmcnt(0) below -- and works out a0 and r0 only.  The branch is
 // wave-uniform (a kernel argument); rays that start inside the hole are neither stored nor used.
 // Items that pass (h >= 0) take a free slot each (ballot/mbcnt ranks); the caller has made sure 64 are free.
+// The same owner may keep much more than h0: the ray's whole state after its first accepted steps, as long as those stay in a
+// ball about the start point that no event surface reaches (TraceArgs::prefix, record_prefix_kernel below).
+// Which kernels look at such records: DP5(4) with the two Cartesian null forms (96-byte states; Kerr's are Boyer-Lindquist
+// with E and L, the time-like form and RK4 stay as they are).
+template <int RHS, bool ADAPTIVE>
+struct PrefixReplays {
+    static constexpr bool value = ADAPTIVE && (RHS == BHG_RHS_CHRISTOFFEL_ || RHS == BHG_RHS_REDUCED_);
+};
 template <int RHS, bool ADAPTIVE, class LDS>
 __device__ __forceinline__ void fill_batch(const TraceArgs &A, LDS &Q, Wave &W, uint32_t lane, uint64_t base)
 {
@@ -1091,10 +1099,51 @@ __device__ __forceinline__ void fill_batch(const TraceArgs &A, LDS &Q, Wave &W, 
            BHG_COLD(kp, start_mode)};
     const bool replay = ADAPTIVE && C.start_mode == BHG_START_REPLAY_;
     const uint64_t i = base + lane;
+    bool need = i < C.n;        // lanes whose ray is started here, from k0 and x0
+    if (PrefixReplays<RHS, ADAPTIVE>::value) {
+        // Start-up records (TraceArgs::prefix; record_prefix_kernel wrote them): a usable one is the ray's queue entry after its
+        // first n_att accepted steps -- it goes into the queue as it is, and only the lanes without one start their ray below
+        // (the whole start is skipped when no lane of the batch needs it).  Wave-uniform on a kernel argument.
+        const double2 *rec = BHG_COLD(kp, prefix);
+        if (rec) {
+            double2 rd[6];
+            uint4 ri = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+            for (int p = 0; p < 6; p++) rd[p] = make_double2(0.0, 0.0);
+            if (i < C.n) {
+#pragma unroll
+                for (int p = 0; p < 6; p++) rd[p] = rec[(uint64_t)p * C.n + i];
+                ri = reinterpret_cast<const uint4 *>(rec)[6ull * C.n + i];
+            }
+            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only: see below
+            const bool usable = i < C.n && ri.y != 0u;
+            const uint64_t umask = __ballot(usable);
+            const int ucnt = __builtin_popcountll(umask);
+            if (usable) {
+                if (C.object_id) C.object_id[i] = (int8_t)-1;
+                const uint32_t rk = lane_rank(umask);
+                const uint32_t s = Q.free_list[W.n_free - 1 - (int)rk];
+                SLOT_CHECK(Q, s, 0, 1, "fill");
+                Q.q_list[(W.q_head + W.q_count + (int)rk) & (QRING - 1)] = (uint8_t)s;
+                QEntry<RHS> &e = Q.slot[s];
+#pragma unroll
+                for (int p = 0; p < 6; p++) e.d[p] = rd[p];
+                e.i = make_uint4((uint32_t)i, ri.y, ri.z, 0u);
+            }
+            W.n_free -= ucnt;
+            W.q_count += ucnt;
+            need = need && !usable;
+            if (__ballot(need) == 0ull) {
+                wave_lds_sync();
+                INV_CHECK(W, "fill");
+                return;
+            }
+        }
+    }
     double hs = 0.0;
     double px[3] = {0, 0, 0}, pk[3] = {0, 0, 0}, pa[3] = {0, 0, 0}, pr = 0.0, ph = -1.0;
     double pE = 0.0, pL = 0.0;
-    if (i < C.n) {
+    if (need) {
         pk[0] = C.k0[i * 3 + 0];
         pk[1] = C.k0[i * 3 + 1];
         pk[2] = C.k0[i * 3 + 2];
@@ -1114,7 +1163,7 @@ __device__ __forceinline__ void fill_batch(const TraceArgs &A, LDS &Q, Wave &W, 
     // to assume they may still be in flight on the not-valid path and puts a vmcnt(0) in front of
     // the step code, which then waits for the previous iteration's result stores every iteration.
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only
-    if (i < C.n) {
+    if (need) {
         if (C.object_id) C.object_id[i] = (int8_t)-1;
         Metric met;
         met.r_s = A.r_s;
@@ -3206,6 +3255,73 @@ hipError_t launch_trace_crossings(const TraceArgs &a, int rhs, hipStream_t s)
         BHG_LAUNCH((disk_crossings_kernel<BHG_RHS_REDUCED_>), grid, dim3(64), 0, s, a);
     else
         BHG_LAUNCH((disk_crossings_kernel<BHG_RHS_CHRISTOFFEL_>), grid, dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+#endif
+
+// ------------------------------------------------------------------------------------------
+// Start-up records (bhg_trace_prefix_device).  scipy's start guess h0 is one to two decades below the
+// step a ray settles on, and the controller climbs there by its x10 clamp: three to four accepted steps next to the camera,
+// a quarter of all the attempts of a frame, whose outcome depends on the ray, the metric, the tolerances, lambda_end and
+// max_step -- and on nothing in the scene as long as no event surface comes near.  One LANE per ray takes every ray through
+// those leading attempts on the trace kernels' own start and step (start_ray, dp54_attempt, advance: the same bits) and keeps
+// the state in front of the first attempt that
+//   * is rejected, or ends the ray (lambda_end reached, the step budget, a step too small, NaN: these reject or flag), or
+//   * ends farther than rho from the start point, or
+//   * would be attempt number BHG_PREFIX_K_MAX_ + 1.
+// What is kept is a queue entry (QEntry: x, k, a, |h| to try next, r, lambda, attempted = accepted = depth, bits 0 -- the last
+// attempt was accepted), written as seven planes of 16 bytes per ray, rec[p * n + i], so that each of the queue fill's loads
+// is contiguous over a wave.  Depth 0 -- a start inside the hole among them -- says "start this ray yourself".
+// Every kept step lies in the ball of radius rho about the start point.  The event tests of the step loop act on step ends
+// (radii, the sign of z) and on the chord between them (object spheres), and a ball is convex: a trace whose horizon, exit
+// sphere, disk plane and object spheres all stay clear of that ball finds no event in these steps, takes them exactly as
+// they were taken here, and arrives at the kept state (the C layer holds every replaying call to that: prefix_clearance).
+// ------------------------------------------------------------------------------------------
+#if !defined(BHG_TU_KERR) && !defined(BHG_TU_TIMELIKE)
+template <int RHS>
+__global__ void __launch_bounds__(64) record_prefix_kernel(const TraceArgs A, double2 *rec, double rho)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= A.n) return;
+    RayState K;    // the state kept so far
+    for (int c = 0; c < 3; c++) K.x[c] = K.v[c] = K.a1[c] = 0.0;
+    K.t = K.h_abs = K.r_cur = 0.0;
+    K.n_att = K.n_acc = 0;
+    K.rejected = false;
+    double xe[3], ve[3];
+    uint32_t depth = 0;
+    if (!start_ray<RHS, true>(A, i, K, xe, ve)) {
+        const double o[3] = {K.x[0], K.x[1], K.x[2]};
+        const double rho2 = rho * rho;
+        while (depth < (uint32_t)BHG_PREFIX_K_MAX_) {
+            RayState T = K;
+            StepTry P;
+            if (dp54_attempt<RHS>(A, T, P) != DP54_ACCEPTED) break;
+            const double d[3] = {P.xn[0] - o[0], P.xn[1] - o[1], P.xn[2] - o[2]};
+            if (!(__builtin_fma(d[2], d[2], __builtin_fma(d[1], d[1], d[0] * d[0])) <= rho2)) break;
+            if (advance(A, T, P, xe, ve)) break;
+            K = T;
+            depth++;
+        }
+    }
+    const uint64_t n = A.n;
+    rec[0 * n + i] = make_double2(K.x[0], K.x[1]);
+    rec[1 * n + i] = make_double2(K.x[2], K.v[0]);
+    rec[2 * n + i] = make_double2(K.v[1], K.v[2]);
+    rec[3 * n + i] = make_double2(K.a1[0], K.a1[1]);
+    rec[4 * n + i] = make_double2(K.a1[2], K.h_abs);
+    rec[5 * n + i] = make_double2(K.r_cur, K.t);
+    reinterpret_cast<uint4 *>(rec)[6 * n + i] = make_uint4((uint32_t)i, depth, depth, 0u);
+}
+
+hipError_t launch_record_prefix(const TraceArgs &a, int rhs, void *rec, double rho, hipStream_t s)
+{
+    if (a.n == 0) return hipSuccess;
+    const dim3 grid((unsigned)((a.n + 63) / 64));
+    if (rhs == BHG_RHS_REDUCED_)
+        BHG_LAUNCH((record_prefix_kernel<BHG_RHS_REDUCED_>), grid, dim3(64), 0, s, a, (double2 *)rec, rho);
+    else
+        BHG_LAUNCH((record_prefix_kernel<BHG_RHS_CHRISTOFFEL_>), grid, dim3(64), 0, s, a, (double2 *)rec, rho);
     return hipGetLastError();
 }
 #endif

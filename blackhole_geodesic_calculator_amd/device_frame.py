@@ -47,13 +47,22 @@ class StartSteps:
     its stamp, the origins) are the same and bhg_start_steps_match() accepts the parameters.  Scene changes -- disk, object
     spheres, sky, shading -- never touch it.  Whoever writes into d_k0 in place by other means than generate_rays() calls
     invalidate().  recorded / replayed count the traces of each kind; BHGEO_START_CACHE=0 in the environment or enabled=False
-    switch it off (every trace is then the plain call, and no memory is held: 8 B per ray otherwise)."""
+    switch it off (every trace is then the plain call, and no memory is held: 8 B per ray otherwise).
+
+    A shared-origin owner (plan(shared_origin=True)) also keeps the rays' start-up records (bhg_trace_prefix_device: 112 B per
+    ray, allocated at the first trace): written by the trace that records the steps, handed to every replaying trace with the rho
+    they were written for -- the library tests each call's scene against it and reports what it did (prefix.used).
+    prefix_recorded / prefix_replayed / prefix_refused count those answers; BHGEO_START_PREFIX=0 switches the records alone off."""
 
     def __init__(self, enabled=True):
         self.enabled = bool(enabled)
         self.d_h = None
         self.key = self.params = self._pending = None
         self.recorded = self.replayed = 0
+        self.d_rec = None
+        self.rho = 0.0             # the records in d_rec were written with this radius (0: none are held)
+        self.prefix = None         # the _ffi.Prefix of the trace being planned, or None
+        self.prefix_recorded = self.prefix_replayed = self.prefix_refused = 0
 
     def invalidate(self):
         self.key = None
@@ -62,18 +71,32 @@ class StartSteps:
     def valid(self):
         return self.key is not None
 
-    def plan(self, n, dev, key, params):
-        """(d_start_steps, start_mode) of the next trace call.  The steps count as not valid until done(): a call that raises
-        leaves them so."""
+    def plan(self, n, dev, key, params, shared_origin=False):
+        """(d_start_steps, start_mode) of the next trace call, and self.prefix for it.  The steps count as not valid until
+        done(): a call that raises leaves them so."""
+        self.prefix = None
         if not self.enabled or os.environ.get("BHGEO_START_CACHE", "") == "0":
             self.key = None
+            self.rho = 0.0
             return 0, _ffi.START_NONE
         if self.d_h is None or self.d_h.numel() != n or self.d_h.device != dev:
             self.d_h = torch.empty(n, dtype=torch.float64, device=dev)
+            self.d_rec = None
             self.key = None
         replay = self.key is not None and self.key == key and _ffi.start_steps_match(self.params, params)
         self.key = None
         self._pending = (key, _copy_params(params), replay)
+        if shared_origin and os.environ.get("BHGEO_START_PREFIX", "") != "0" and _ffi.has_start_prefix():
+            if self.d_rec is None:
+                self.d_rec = torch.empty(n * _ffi.PREFIX_BYTES_PER_RAY, dtype=torch.uint8, device=dev)
+                self.rho = 0.0
+            if replay and self.rho > 0.0:
+                self.prefix = _ffi.Prefix(self.d_rec.data_ptr(), self.rho, _ffi.PREFIX_REPLAY, 0)
+            elif not replay:
+                self.prefix = _ffi.Prefix(self.d_rec.data_ptr(), 0.0, _ffi.PREFIX_RECORD, 0)
+                self.rho = 0.0
+        else:
+            self.rho = 0.0
         return self.d_h.data_ptr(), (_ffi.START_REPLAY if replay else _ffi.START_RECORD)
 
     def done(self):
@@ -81,6 +104,14 @@ class StartSteps:
             return
         self.key, self.params, replay = self._pending
         self._pending = None
+        if self.prefix is not None:
+            if self.prefix.mode == _ffi.PREFIX_RECORD:
+                self.rho = float(self.prefix.rho) if self.prefix.used == _ffi.PREFIX_RECORD else 0.0
+                self.prefix_recorded += self.prefix.used == _ffi.PREFIX_RECORD
+            elif self.prefix.used == _ffi.PREFIX_REPLAY:
+                self.prefix_replayed += 1
+            else:
+                self.prefix_refused += 1
         if replay:
             self.replayed += 1
         else:
@@ -101,7 +132,7 @@ class DeviceFrame:
         lookup, :366-378) -- trace() then has the kernel write those alone (d_dir [n, 3], bhg_trace_dir_device: half
         the bytes written per ray and read by the shade kernel; d_end is not filled) and shade() / shade_f32() read
         them.  With a disk or objects set the frame falls back to whole end records by itself.
-        start_cache: keep the rays' initial steps from trace to trace (StartSteps; 8 B per ray)."""
+        start_cache: keep the rays' initial steps and start-up records from trace to trace (StartSteps; 8 + 112 B per ray)."""
         self.ctx = ctx
         self.start_steps = StartSteps(start_cache)
         self.directions_only = bool(directions_only)
@@ -355,14 +386,15 @@ class DeviceFrame:
         self._dir_traced = self.directions_only and not has_obj and self.disk is None and not (params.disk_r_out > 0.0)
         self._traced = "dir" if self._dir_traced else "end"
         # the initial steps belong to the rays and the origin they start from: recorded by the first trace, replayed after
-        d_h, mode = self.start_steps.plan(self.n, self.dev, (_rays_key(self.d_k0), origin.tobytes()), params)
+        d_h, mode = self.start_steps.plan(self.n, self.dev, (_rays_key(self.d_k0), origin.tobytes()), params, shared_origin=True)
+        prefix = self.start_steps.prefix
         if self._dir_traced:
             if self.d_dir is None:
                 self.d_dir = torch.empty((self.n, 3), dtype=torch.float64, device=self.dev)
             self.ctx.trace_dir_device(params, self.n, self.d_k0.data_ptr(), self.d_dir.data_ptr(), x0_shared=origin,
                                       d_flags=self.d_flags.data_ptr(), d_n_steps=self.d_steps.data_ptr(),
                                       d_n_accepted=self.d_acc.data_ptr(), stream=self._stream(), d_start_steps=d_h,
-                                      start_mode=mode)
+                                      start_mode=mode, prefix=prefix)
             self.start_steps.done()
             return
         if self.d_end is None:
@@ -371,7 +403,8 @@ class DeviceFrame:
                               d_flags=self.d_flags.data_ptr(), d_n_steps=self.d_steps.data_ptr(),
                               d_n_accepted=self.d_acc.data_ptr(), stream=self._stream(),
                               spheres=self.spheres if has_obj else None,
-                              d_object_id=self.d_obj.data_ptr() if has_obj else 0, d_start_steps=d_h, start_mode=mode)
+                              d_object_id=self.d_obj.data_ptr() if has_obj else 0, d_start_steps=d_h, start_mode=mode,
+                              prefix=prefix)
         self.start_steps.done()
 
     def scene(self):

@@ -327,6 +327,47 @@ int bhg_trace_start_device(bhg_context *ctx, const bhg_params *p, const double *
  * anything), else 0 -- also for a NULL argument.  THE one holder of that list: every owner of a d_start_steps array asks it. */
 int bhg_start_steps_match(const bhg_params *a, const bhg_params *b);
 
+/* --- the rays' start-up records kept across calls (within ABI 10, BHG_START_PREFIX) ---------------
+ * scipy's start guess is one to two decades below the step a ray settles on, and the controller climbs there by its x10
+ * clamp: the first three or four accepted steps of every ray, a quarter of a frame's attempts, next to the camera.  Like the
+ * initial step they depend on the ray and on the parameters of bhg_start_steps_match() -- and on the scene only through the
+ * question whether an event surface comes near.  The owner of unchanged rays keeps them in bhg_prefix.d_records,
+ * BHG_PREFIX_BYTES_PER_RAY * n bytes of device memory, 16-byte aligned:
+ *   BHG_PREFIX_RECORD: in front of the call of always a recording pass takes every ray through its leading accepted steps,
+ *                      at most BHG_PREFIX_K_MAX, inside the ball of radius rho = 1/4 min(clearance, |x0|) about the start
+ *                      point (clearance: bhg_prefix_clearance of this call), and stores the state reached; rho is returned.
+ *   BHG_PREFIX_REPLAY: rays with a usable record enter the integration at that state (112 B loaded per ray; no k0, no initial
+ *                      step), the others start as always -- IF the call's own clearance still exceeds the rho handed back in
+ *                      (the scene may have changed: an object sphere moved in, a disk was set).  Otherwise the call runs
+ *                      without the records.  Results are the plain call's bit for bit either way, n_steps / n_accepted
+ *                      included (they count the replayed steps).
+ *   BHG_PREFIX_NONE:   bhg_trace_start_device.
+ * used says what the call did: BHG_PREFIX_RECORD (records written), BHG_PREFIX_REPLAY (records used) or BHG_PREFIX_NONE
+ * (refused, or out of scope).  In scope: x0_shared calls (d_x0 NULL) of BHG_METHOD_DP54 with BHG_RHS_CHRISTOFFEL or
+ * BHG_RHS_REDUCED, null rays, at most 2^26 rays, max_steps > BHG_PREFIX_K_MAX.  REPLAY is valid after a RECORD call with the
+ * same x0_shared and d_k0 contents, the same n and parameters for which bhg_start_steps_match() gives 1: the caller vouches,
+ * as for the start steps.  d_start_steps / start_mode keep their meaning for the rays that start as always. */
+#define BHG_START_PREFIX 1
+#define BHG_PREFIX_NONE 0
+#define BHG_PREFIX_RECORD 1
+#define BHG_PREFIX_REPLAY 2
+#define BHG_PREFIX_K_MAX 4
+#define BHG_PREFIX_BYTES_PER_RAY 112
+typedef struct bhg_prefix {
+    void *d_records;  /* device, BHG_PREFIX_BYTES_PER_RAY * n bytes */
+    double rho;       /* RECORD: out (0 when nothing was recorded); REPLAY: in */
+    int32_t mode;     /* in: BHG_PREFIX_* */
+    int32_t used;     /* out: BHG_PREFIX_* */
+} bhg_prefix;
+int bhg_trace_prefix_device(bhg_context *ctx, const bhg_params *p, const double *spheres, int32_t n_spheres,
+                            const double *x0_shared, const double *d_x0, const double *d_k0, size_t n, double *d_end,
+                            double *d_end_dir, uint8_t *d_flags, uint32_t *d_n_steps, uint32_t *d_n_accepted,
+                            int8_t *d_object_id, double *d_start_steps, int32_t start_mode, bhg_prefix *prefix, void *stream);
+/* Distance from x0 (HOST, 3 doubles, BH-centred) to the nearest event surface of a call with these parameters and object
+ * spheres: the horizon, the exit sphere, the disk plane when a disk is set, every sphere's surface.  0 for a start on or
+ * inside the horizon and for anything not finite.  A replaying call needs clearance > rho (1 + 1e-6): tangent is refused. */
+double bhg_prefix_clearance(const bhg_params *p, const double *spheres, int32_t n_spheres, const double *x0);
+
 /* --- the stages either side of the solve, on device ---------------------------------------- */
 /* Camera rays with the reference's multisample jitter (RelativisticRenderEngine.py:185-188,
  * :224-230).  d_jitter [samples*height*width*2]: the random.random() stream after
