@@ -65,6 +65,7 @@ EXPORTS = (
     "bhg_frame_set_object_motion",
     "bhg_math_probe",
     "bhg_trace_start_device", "bhg_start_steps_match", "bhg_trace_prefix_device", "bhg_prefix_clearance",
+    "bhg_prefix_deep_attempts",
     "bhg_trace_crossings_device", "bhg_trace_crossings", "bhg_disk_layers_size", "bhg_shade_disk_layers_device",
 )
 MAX_CROSSINGS = 4   # BHG_MAX_CROSSINGS: disk crossings a crossings trace stores per ray (BHG_DISK_CROSSINGS)
@@ -72,6 +73,8 @@ START_NONE, START_RECORD, START_REPLAY = 0, 1, 2   # BHG_START_*: the rays' init
 # BHG_PREFIX_*: the rays' start-up records kept across calls (BHG_START_PREFIX)
 PREFIX_NONE, PREFIX_RECORD, PREFIX_REPLAY = 0, 1, 2
 PREFIX_K_MAX, PREFIX_BYTES_PER_RAY = 4, 112
+# ... by the deep rule (BHG_PREFIX_RECORD_DEEP): rejected attempts kept, three quarters of the clear ball without object spheres
+PREFIX_RECORD_DEEP, PREFIX_DEEP_ACCEPTED, PREFIX_DEEP_ATTEMPTS = 4, 6, 12
 
 
 class Prefix(C.Structure):
@@ -424,6 +427,9 @@ def load():
                                               C.c_int32, C.POINTER(Prefix), C.c_void_p]
         L.bhg_prefix_clearance.restype = C.c_double
         L.bhg_prefix_clearance.argtypes = [C.POINTER(Params), _dp, C.c_int32, _dp]
+    if hasattr(L, "bhg_prefix_deep_attempts"):     # (a library from before the deep rule: has_deep_prefix())
+        L.bhg_prefix_deep_attempts.restype = C.c_int32
+        L.bhg_prefix_deep_attempts.argtypes = []
     L.bhg_start_steps_match.restype = C.c_int
     L.bhg_start_steps_match.argtypes = [C.POINTER(Params), C.POINTER(Params)]
     L.bhg_shade_dir_device.restype = C.c_int
@@ -659,6 +665,11 @@ def start_steps_match(a: "Params", b: "Params") -> bool:
 def has_start_prefix() -> bool:
     """Does the loaded library know the rays' start-up records (bhg_trace_prefix_device)?"""
     return hasattr(load(), "bhg_trace_prefix_device")
+
+
+def has_deep_prefix() -> bool:
+    """Does the loaded library take BHG_PREFIX_RECORD_DEEP (it then exports bhg_prefix_deep_attempts)?"""
+    return has_start_prefix() and hasattr(load(), "bhg_prefix_deep_attempts")
 
 
 def prefix_clearance(params: "Params", x0, spheres=None) -> float:

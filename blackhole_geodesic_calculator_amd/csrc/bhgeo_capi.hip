@@ -33,6 +33,9 @@ static_assert(BHG_FLAG_MAX_STEPS == bhg::BHG_FLAG_MAX_STEPS_, "flag mismatch");
 static_assert(BHG_FLAG_STEP_TOO_SMALL == bhg::BHG_FLAG_STEP_TOO_SMALL_, "flag mismatch");
 static_assert(BHG_FLAG_NAN == bhg::BHG_FLAG_NAN_, "flag mismatch");
 static_assert(BHG_FLAG_HIT_OBJECT == bhg::BHG_FLAG_HIT_OBJECT_ && BHG_MAX_SPHERES == bhg::BHG_MAX_SPHERES_, "object constants mismatch");
+static_assert(BHG_PREFIX_K_MAX == bhg::BHG_PREFIX_K_MAX_ && BHG_PREFIX_DEEP_ACCEPTED == bhg::BHG_PREFIX_DEEP_ACCEPTED_ &&
+                  BHG_PREFIX_DEEP_ATTEMPTS == bhg::BHG_PREFIX_DEEP_ATTEMPTS_ && BHG_PREFIX_DEEP_ACCEPTED <= BHG_PREFIX_DEEP_ATTEMPTS,
+              "start-up record limits mismatch");
 static_assert(BHG_METHOD_DP54 == bhg::BHG_METHOD_DP54_ && BHG_METHOD_RK4 == bhg::BHG_METHOD_RK4_, "method mismatch");
 static_assert(BHG_RHS_CHRISTOFFEL == bhg::BHG_RHS_CHRISTOFFEL_ && BHG_RHS_REDUCED == bhg::BHG_RHS_REDUCED_ &&
                   BHG_RHS_KERR_BL == bhg::BHG_RHS_KERR_BL_,
@@ -1092,8 +1095,9 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres,
     if (rc != BHG_OK) return rc;
     if (pf) {
         pf->used = BHG_PREFIX_NONE;
-        if (pf->mode != BHG_PREFIX_NONE && pf->mode != BHG_PREFIX_RECORD && pf->mode != BHG_PREFIX_REPLAY)
-            return fail(BHG_E_INVALID, "prefix mode must be BHG_PREFIX_NONE, BHG_PREFIX_RECORD or BHG_PREFIX_REPLAY");
+        if (pf->mode != BHG_PREFIX_NONE && pf->mode != BHG_PREFIX_RECORD && pf->mode != BHG_PREFIX_REPLAY &&
+            pf->mode != BHG_PREFIX_RECORD_DEEP)
+            return fail(BHG_E_INVALID, "prefix mode must be BHG_PREFIX_NONE, BHG_PREFIX_RECORD, BHG_PREFIX_REPLAY or BHG_PREFIX_RECORD_DEEP");
         if (n && pf->mode != BHG_PREFIX_NONE && !pf->d_records) return fail(BHG_E_INVALID, "prefix mode asks for d_records, which is NULL");
     }
     if (start_mode != BHG_START_NONE && start_mode != BHG_START_RECORD && start_mode != BHG_START_REPLAY)
@@ -1186,15 +1190,21 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres,
     // the rays' start-up records kept by their owner: shared-origin calls of DP5(4) with the two Cartesian null forms, one launch
     // (the planes' stride is the launch's n), a step budget the records cannot exhaust.  Anything else ignores them, as RK4
     // ignores the start steps, and says so in pf->used.
-    bool pf_record = false;
+    bool pf_record = false, pf_deep = false;
     double pf_rho = 0.0;
     if (pf && pf->mode != BHG_PREFIX_NONE && !cr && !d_x0 && p->method == BHG_METHOD_DP54 &&
         (rhs_id == bhg::BHG_RHS_CHRISTOFFEL_ || rhs_id == bhg::BHG_RHS_REDUCED_) && a.max_steps > (uint32_t)BHG_PREFIX_K_MAX) {
         const double clear = bhg::prefix_clearance(a.r_hor, a.r_exit, a.disk_r_out > 0.0, spheres, n_spheres, x0_shared);
+        // (a deep record holds up to BHG_PREFIX_DEEP_ATTEMPTS attempts: neither written nor -- the call cannot tell which rule
+        // wrote the records it is handed -- replayed under a step budget that those attempts would exhaust)
+        const bool deep_fits = a.max_steps > (uint32_t)BHG_PREFIX_DEEP_ATTEMPTS;
         if (pf->mode == BHG_PREFIX_RECORD) {
             pf_rho = bhg::prefix_rho(clear, x0_shared);
             pf_record = pf_rho > 0.0;
-        } else if (bhg::prefix_replay_ok(clear, pf->rho)) {
+        } else if (pf->mode == BHG_PREFIX_RECORD_DEEP) {
+            pf_rho = deep_fits ? bhg::prefix_rho_deep_call(clear, a.r_hor, x0_shared, n_spheres) : 0.0;
+            pf_record = pf_deep = pf_rho > 0.0;
+        } else if (deep_fits && bhg::prefix_replay_ok(clear, pf->rho)) {
             a.prefix = (const double2 *)pf->d_records;
             pf->used = BHG_PREFIX_REPLAY;
         }
@@ -1257,9 +1267,9 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres,
         if (!c->counters_clean) HIP_TRY(hipMemsetAsync(c->counter, 0, 2 * 8 * 256, s));   // first call, or after a failed enqueue
         if (pf_record) {
             // the recording pass, in front of the trace of always (which starts its rays itself: the records are for later calls)
-            HIP_TRY(bhg::launch_record_prefix(a, rhs_id, pf->d_records, pf_rho, s));
+            HIP_TRY(bhg::launch_record_prefix(a, rhs_id, pf->d_records, pf_rho, pf_deep, s));
             pf->rho = pf_rho;
-            pf->used = BHG_PREFIX_RECORD;
+            pf->used = pf_deep ? BHG_PREFIX_RECORD_DEEP : BHG_PREFIX_RECORD;
         }
         c->counters_clean = false;
         HIP_TRY(bhg::launch_trace(a, p->method, rhs_id, evt, (int)grid, s, c->profiling ? c->ev : nullptr));
@@ -1387,6 +1397,8 @@ double bhg_prefix_clearance(const bhg_params *p, const double *spheres, int32_t 
 // THE list of what a ray's initial step depends on beside the ray itself (initial_record, geodesic_kernels.hip): the
 // controller's tolerances and limits and the metric.  The integrator is in it because only DP5(4) has such a step: a
 // recording RK4 call leaves the array as it was.  Compared bit for bit (a -0.0 or another NaN counts as a change: safe).
+int32_t bhg_prefix_deep_attempts(void) { return BHG_PREFIX_DEEP_ATTEMPTS; }
+
 int bhg_start_steps_match(const bhg_params *a, const bhg_params *b)
 {
     if (!a || !b) return 0;

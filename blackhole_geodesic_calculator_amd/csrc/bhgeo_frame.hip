@@ -779,6 +779,8 @@ try {
     const bool start_cache = !(sc_env && sc_env[0] == '0' && sc_env[1] == 0);
     const char *sp_env = std::getenv("BHGEO_START_PREFIX");  // "0": the start steps alone, no start-up records (A/B, 112 B per ray less)
     const bool start_prefix = start_cache && !(sp_env && sp_env[0] == '0' && sp_env[1] == 0);
+    const char *dp_env = std::getenv("BHGEO_DEEP_PREFIX");   // "0": the records by BHG_PREFIX_RECORD, not BHG_PREFIX_RECORD_DEEP (A/B)
+    const int32_t record_mode = (dp_env && dp_env[0] == '0' && dp_env[1] == 0) ? BHG_PREFIX_RECORD : BHG_PREFIX_RECORD_DEEP;
     const bool redshift = f->rs.apply != 0;
     if (redshift) {   // (refused before anything is enqueued)
         bhg::RedshiftParams rp;
@@ -860,7 +862,7 @@ try {
             BHG_TRY(s.start_rec.ensure(s.device, s.n * (size_t)BHG_PREFIX_BYTES_PER_RAY));
             pf.d_records = s.start_rec.as<char>();
             pf.rho = s.start_rho;
-            pf.mode = start_mode == BHG_START_RECORD ? BHG_PREFIX_RECORD : (s.start_rho > 0.0 ? BHG_PREFIX_REPLAY : BHG_PREFIX_NONE);
+            pf.mode = start_mode == BHG_START_RECORD ? record_mode : (s.start_rho > 0.0 ? BHG_PREFIX_REPLAY : BHG_PREFIX_NONE);
             s.start_rho = 0.0;
         } else {
             s.start_rho = 0.0;
@@ -873,7 +875,7 @@ try {
                                         dir_only ? s.dir.as<double>() : nullptr, s.flags.as<uint8_t>(), s.steps.as<uint32_t>(),
                                         s.acc.as<uint32_t>(), has_obj ? s.obj.as<int8_t>() : nullptr, s.start_h.as<double>(),
                                         start_mode, &pf, s.stream));
-        if (start_prefix) s.start_rho = pf.mode == BHG_PREFIX_RECORD ? (pf.used == BHG_PREFIX_RECORD ? pf.rho : 0.0) : pf.rho;
+        if (start_prefix) s.start_rho = pf.mode == record_mode ? (pf.used == record_mode ? pf.rho : 0.0) : pf.rho;
         if (start_cache) {
             s.start_prm = prm;
             std::memcpy(s.start_origin, f->cam.origin, sizeof(s.start_origin));

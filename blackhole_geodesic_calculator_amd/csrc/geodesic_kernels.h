@@ -43,6 +43,8 @@ constexpr int32_t BHG_START_NONE_ = 0;      // TraceArgs::start_mode: every call
 constexpr int32_t BHG_START_RECORD_ = 1;    // ... and stores them in start_h
 constexpr int32_t BHG_START_REPLAY_ = 2;    // start_h holds them (a recording call on the same rays and matching parameters)
 constexpr int BHG_PREFIX_K_MAX_ = 4;        // accepted steps a start-up record holds at most (BHG_PREFIX_K_MAX)
+constexpr int BHG_PREFIX_DEEP_ACCEPTED_ = 6;    // ... a DEEP record: accepted steps at most (BHG_PREFIX_DEEP_ACCEPTED)
+constexpr int BHG_PREFIX_DEEP_ATTEMPTS_ = 12;   // ... and attempts, the rejected ones among them (BHG_PREFIX_DEEP_ATTEMPTS)
 // rays per trace launch: the kernels form a ray's result offsets (idx * 48 at most) in 32 bits
 constexpr uint64_t BHG_MAX_RAYS_PER_LAUNCH = 1ull << 26;
 
@@ -313,8 +315,9 @@ hipError_t launch_trace_crossings(const TraceArgs &a, int rhs, hipStream_t s);
 // ... its Kerr instance, in the Kerr translation unit; the caller runs launch_kerr_finalize on the end records afterwards
 hipError_t launch_trace_crossings_kerr(const TraceArgs &a, hipStream_t s);
 // the recording pass of the start-up records (record_prefix_kernel: one lane per ray; rhs Christoffel or reduced, a.x0 == nullptr):
-// rec [7][a.n] 16-byte planes, rho the radius about a.x0s the recorded steps stay inside
-hipError_t launch_record_prefix(const TraceArgs &a, int rhs, void *rec, double rho, hipStream_t s);
+// rec [7][a.n] 16-byte planes, rho the radius about a.x0s the recorded steps stay inside.  deep: the record carries on through
+// rejected attempts (BHG_PREFIX_RECORD_DEEP: at most BHG_PREFIX_DEEP_ACCEPTED_ accepted steps in BHG_PREFIX_DEEP_ATTEMPTS_ attempts)
+hipError_t launch_record_prefix(const TraceArgs &a, int rhs, void *rec, double rho, bool deep, hipStream_t s);
 // Kerr: after the last pass of a call, Boyer-Lindquist end states -> Cartesian
 hipError_t launch_kerr_finalize(const TraceArgs &a, double *dir_out, hipStream_t s);
 // the Kerr instantiations live in their own translation unit (geodesic_kernels_kerr.hip: same source, same flags --

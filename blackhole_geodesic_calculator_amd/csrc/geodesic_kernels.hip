@@ -1102,8 +1102,9 @@ __device__ __forceinline__ void fill_batch(const TraceArgs &A, LDS &Q, Wave &W, 
     bool need = i < C.n;        // lanes whose ray is started here, from k0 and x0
     if (PrefixReplays<RHS, ADAPTIVE>::value) {
         // Start-up records (TraceArgs::prefix; record_prefix_kernel wrote them): a usable one is the ray's queue entry after its
-        // first n_att accepted steps -- it goes into the queue as it is, and only the lanes without one start their ray below
-        // (the whole start is skipped when no lane of the batch needs it).  Wave-uniform on a kernel argument.
+        // first n_att attempts (a deep record: rejected ones among them, bit 0 of its last word set when the last one was) -- it
+        // goes into the queue as it is, and only the lanes without one start their ray below (the whole start is skipped when
+        // no lane of the batch needs it).  Wave-uniform on a kernel argument.
         const double2 *rec = BHG_COLD(kp, prefix);
         if (rec) {
             double2 rd[6];
@@ -1116,7 +1117,7 @@ __device__ __forceinline__ void fill_batch(const TraceArgs &A, LDS &Q, Wave &W, 
                 ri = reinterpret_cast<const uint4 *>(rec)[6ull * C.n + i];
             }
             __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only: see below
-            const bool usable = i < C.n && ri.y != 0u;
+            const bool usable = i < C.n && ri.y != 0u;     // (y: attempts, z: accepted steps)
             const uint64_t umask = __ballot(usable);
             const int ucnt = __builtin_popcountll(umask);
             if (usable) {
@@ -1128,7 +1129,7 @@ __device__ __forceinline__ void fill_batch(const TraceArgs &A, LDS &Q, Wave &W, 
                 QEntry<RHS> &e = Q.slot[s];
 #pragma unroll
                 for (int p = 0; p < 6; p++) e.d[p] = rd[p];
-                e.i = make_uint4((uint32_t)i, ri.y, ri.z, 0u);
+                e.i = make_uint4((uint32_t)i, ri.y, ri.z, ri.w);
             }
             W.n_free -= ucnt;
             W.q_count += ucnt;
@@ -3278,7 +3279,16 @@ hipError_t launch_trace_crossings(const TraceArgs &a, int rhs, hipStream_t s)
 // they were taken here, and arrives at the kept state (the C layer holds every replaying call to that: prefix_clearance).
 // ------------------------------------------------------------------------------------------
 #if !defined(BHG_TU_KERR) && !defined(BHG_TU_TIMELIKE)
-template <int RHS>
+// DEEP (BHG_PREFIX_RECORD_DEEP): the record does not stop at a rejected attempt.  A rejected attempt tests no event and moves
+// nothing: what it leaves -- the reduced |h|, the `rejected` bit that clamps the next factor to 1, the attempt count -- depends on
+// what an accepted step depends on, and the step loop takes a ray in that state from the queue already (the short drain hands
+// one back so: PARK_REQUEUE, bit 0 of the entry's last word, which the pop reads).  So the kept state is the one in front of
+//   * the first attempt that would end the ray or flag it, or
+//   * an accepted attempt that ends farther than rho from the start point (rejections in front of it are kept: same point,
+//     smaller h, bit set), or
+//   * accepted step number BHG_PREFIX_DEEP_ACCEPTED_ + 1 or attempt number BHG_PREFIX_DEEP_ATTEMPTS_ + 1,
+// and the last plane is (i, attempted, accepted, rejected).  A record is usable when attempted != 0.
+template <int RHS, bool DEEP>
 __global__ void __launch_bounds__(64) record_prefix_kernel(const TraceArgs A, double2 *rec, double rho)
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -3289,19 +3299,23 @@ __global__ void __launch_bounds__(64) record_prefix_kernel(const TraceArgs A, do
     K.n_att = K.n_acc = 0;
     K.rejected = false;
     double xe[3], ve[3];
-    uint32_t depth = 0;
     if (!start_ray<RHS, true>(A, i, K, xe, ve)) {
         const double o[3] = {K.x[0], K.x[1], K.x[2]};
         const double rho2 = rho * rho;
-        while (depth < (uint32_t)BHG_PREFIX_K_MAX_) {
+        const uint32_t acc_max = DEEP ? (uint32_t)BHG_PREFIX_DEEP_ACCEPTED_ : (uint32_t)BHG_PREFIX_K_MAX_;
+        while (K.n_acc < acc_max && (!DEEP || K.n_att < (uint32_t)BHG_PREFIX_DEEP_ATTEMPTS_)) {
             RayState T = K;
             StepTry P;
-            if (dp54_attempt<RHS>(A, T, P) != DP54_ACCEPTED) break;
+            const uint32_t st = dp54_attempt<RHS>(A, T, P);
+            if (DEEP && st == DP54_REJECTED) {
+                K = T;      // (x, v, a1, t as they were: the reduced h_abs, rejected, n_att)
+                continue;
+            }
+            if (st != DP54_ACCEPTED) break;
             const double d[3] = {P.xn[0] - o[0], P.xn[1] - o[1], P.xn[2] - o[2]};
             if (!(__builtin_fma(d[2], d[2], __builtin_fma(d[1], d[1], d[0] * d[0])) <= rho2)) break;
             if (advance(A, T, P, xe, ve)) break;
             K = T;
-            depth++;
         }
     }
     const uint64_t n = A.n;
@@ -3311,17 +3325,24 @@ __global__ void __launch_bounds__(64) record_prefix_kernel(const TraceArgs A, do
     rec[3 * n + i] = make_double2(K.a1[0], K.a1[1]);
     rec[4 * n + i] = make_double2(K.a1[2], K.h_abs);
     rec[5 * n + i] = make_double2(K.r_cur, K.t);
-    reinterpret_cast<uint4 *>(rec)[6 * n + i] = make_uint4((uint32_t)i, depth, depth, 0u);
+    reinterpret_cast<uint4 *>(rec)[6 * n + i] = make_uint4((uint32_t)i, K.n_att, K.n_acc, K.rejected ? 1u : 0u);
 }
 
-hipError_t launch_record_prefix(const TraceArgs &a, int rhs, void *rec, double rho, hipStream_t s)
+hipError_t launch_record_prefix(const TraceArgs &a, int rhs, void *rec, double rho, bool deep, hipStream_t s)
 {
     if (a.n == 0) return hipSuccess;
     const dim3 grid((unsigned)((a.n + 63) / 64));
-    if (rhs == BHG_RHS_REDUCED_)
-        BHG_LAUNCH((record_prefix_kernel<BHG_RHS_REDUCED_>), grid, dim3(64), 0, s, a, (double2 *)rec, rho);
-    else
-        BHG_LAUNCH((record_prefix_kernel<BHG_RHS_CHRISTOFFEL_>), grid, dim3(64), 0, s, a, (double2 *)rec, rho);
+    if (rhs == BHG_RHS_REDUCED_) {
+        if (deep)
+            BHG_LAUNCH((record_prefix_kernel<BHG_RHS_REDUCED_, true>), grid, dim3(64), 0, s, a, (double2 *)rec, rho);
+        else
+            BHG_LAUNCH((record_prefix_kernel<BHG_RHS_REDUCED_, false>), grid, dim3(64), 0, s, a, (double2 *)rec, rho);
+    } else {
+        if (deep)
+            BHG_LAUNCH((record_prefix_kernel<BHG_RHS_CHRISTOFFEL_, true>), grid, dim3(64), 0, s, a, (double2 *)rec, rho);
+        else
+            BHG_LAUNCH((record_prefix_kernel<BHG_RHS_CHRISTOFFEL_, false>), grid, dim3(64), 0, s, a, (double2 *)rec, rho);
+    }
     return hipGetLastError();
 }
 #endif

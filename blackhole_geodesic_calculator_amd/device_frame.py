@@ -52,7 +52,9 @@ class StartSteps:
     A shared-origin owner (plan(shared_origin=True)) also keeps the rays' start-up records (bhg_trace_prefix_device: 112 B per
     ray, allocated at the first trace): written by the trace that records the steps, handed to every replaying trace with the rho
     they were written for -- the library tests each call's scene against it and reports what it did (prefix.used).
-    prefix_recorded / prefix_replayed / prefix_refused count those answers; BHGEO_START_PREFIX=0 switches the records alone off."""
+    prefix_recorded / prefix_replayed / prefix_refused count those answers; BHGEO_START_PREFIX=0 switches the records alone off.
+    The records are written by the deep rule (BHG_PREFIX_RECORD_DEEP: rejected attempts kept, three quarters of the clear ball in
+    a scene without object spheres whose nearest surface is the horizon) where the library has it; BHGEO_DEEP_PREFIX=0 goes back to BHG_PREFIX_RECORD."""
 
     def __init__(self, enabled=True):
         self.enabled = bool(enabled)
@@ -93,7 +95,8 @@ class StartSteps:
             if replay and self.rho > 0.0:
                 self.prefix = _ffi.Prefix(self.d_rec.data_ptr(), self.rho, _ffi.PREFIX_REPLAY, 0)
             elif not replay:
-                self.prefix = _ffi.Prefix(self.d_rec.data_ptr(), 0.0, _ffi.PREFIX_RECORD, 0)
+                deep = os.environ.get("BHGEO_DEEP_PREFIX", "") != "0" and _ffi.has_deep_prefix()
+                self.prefix = _ffi.Prefix(self.d_rec.data_ptr(), 0.0, _ffi.PREFIX_RECORD_DEEP if deep else _ffi.PREFIX_RECORD, 0)
                 self.rho = 0.0
         else:
             self.rho = 0.0
@@ -105,9 +108,10 @@ class StartSteps:
         self.key, self.params, replay = self._pending
         self._pending = None
         if self.prefix is not None:
-            if self.prefix.mode == _ffi.PREFIX_RECORD:
-                self.rho = float(self.prefix.rho) if self.prefix.used == _ffi.PREFIX_RECORD else 0.0
-                self.prefix_recorded += self.prefix.used == _ffi.PREFIX_RECORD
+            if self.prefix.mode in (_ffi.PREFIX_RECORD, _ffi.PREFIX_RECORD_DEEP):
+                wrote = self.prefix.used == self.prefix.mode
+                self.rho = float(self.prefix.rho) if wrote else 0.0
+                self.prefix_recorded += wrote
             elif self.prefix.used == _ffi.PREFIX_REPLAY:
                 self.prefix_replayed += 1
             else:

@@ -341,9 +341,22 @@ int bhg_start_steps_match(const bhg_params *a, const bhg_params *b);
  *                      (the scene may have changed: an object sphere moved in, a disk was set).  Otherwise the call runs
  *                      without the records.  Results are the plain call's bit for bit either way, n_steps / n_accepted
  *                      included (they count the replayed steps).
+ *   BHG_PREFIX_RECORD_DEEP: RECORD by a second rule.  The recording pass carries on THROUGH
+ *                      rejected attempts -- a rejected attempt tests no event and moves nothing; it leaves a smaller step, the
+ *                      controller's "last attempt was rejected" bit and the attempt count, which depend on what an accepted
+ *                      step depends on -- and stops in front of the first attempt that would end or flag the ray, in front
+ *                      of an accepted step that leaves the ball, after BHG_PREFIX_DEEP_ACCEPTED accepted steps or after
+ *                      BHG_PREFIX_DEEP_ATTEMPTS attempts.  The ball: rho = 3/4 min(clearance, |x0|) in a call without object
+ *                      spheres whose nearest surface is the horizon (the one surface that cannot change without new
+ *                      records; REPLAY tests every call against rho all the same), the 1/4 of RECORD with any object
+ *                      sphere or where the exit sphere or the disk plane is nearer.  Same buffer, same 112 bytes per ray, replayed by
+ *                      the same BHG_PREFIX_REPLAY; needs max_steps > BHG_PREFIX_DEEP_ATTEMPTS, else nothing is written
+ *                      (used = BHG_PREFIX_NONE, rho = 0).
  *   BHG_PREFIX_NONE:   bhg_trace_start_device.
- * used says what the call did: BHG_PREFIX_RECORD (records written), BHG_PREFIX_REPLAY (records used) or BHG_PREFIX_NONE
- * (refused, or out of scope).  In scope: x0_shared calls (d_x0 NULL) of BHG_METHOD_DP54 with BHG_RHS_CHRISTOFFEL or
+ * used says what the call did: BHG_PREFIX_RECORD or BHG_PREFIX_RECORD_DEEP (records written by that rule), BHG_PREFIX_REPLAY
+ * (records used) or BHG_PREFIX_NONE (refused, or out of scope).  A REPLAY call cannot tell which rule wrote the records it is
+ * handed, so it uses none under a step budget that a deep record could exhaust: max_steps <= BHG_PREFIX_DEEP_ATTEMPTS is
+ * answered with BHG_PREFIX_NONE, the plain call's results as always.  (Mode 3 is no mode and stays BHG_E_INVALID.)  In scope: x0_shared calls (d_x0 NULL) of BHG_METHOD_DP54 with BHG_RHS_CHRISTOFFEL or
  * BHG_RHS_REDUCED, null rays, at most 2^26 rays, max_steps > BHG_PREFIX_K_MAX.  REPLAY is valid after a RECORD call with the
  * same x0_shared and d_k0 contents, the same n and parameters for which bhg_start_steps_match() gives 1: the caller vouches,
  * as for the start steps.  d_start_steps / start_mode keep their meaning for the rays that start as always. */
@@ -351,11 +364,14 @@ int bhg_start_steps_match(const bhg_params *a, const bhg_params *b);
 #define BHG_PREFIX_NONE 0
 #define BHG_PREFIX_RECORD 1
 #define BHG_PREFIX_REPLAY 2
+#define BHG_PREFIX_RECORD_DEEP 4 /* (3 stays no mode: callers were promised BHG_E_INVALID for it) */
 #define BHG_PREFIX_K_MAX 4
+#define BHG_PREFIX_DEEP_ACCEPTED 6  /* accepted steps a deep record holds at most */
+#define BHG_PREFIX_DEEP_ATTEMPTS 12 /* attempts a deep record holds at most, rejected ones included */
 #define BHG_PREFIX_BYTES_PER_RAY 112
 typedef struct bhg_prefix {
     void *d_records;  /* device, BHG_PREFIX_BYTES_PER_RAY * n bytes */
-    double rho;       /* RECORD: out (0 when nothing was recorded); REPLAY: in */
+    double rho;       /* RECORD, RECORD_DEEP: out (0 when nothing was recorded); REPLAY: in */
     int32_t mode;     /* in: BHG_PREFIX_* */
     int32_t used;     /* out: BHG_PREFIX_* */
 } bhg_prefix;
@@ -367,6 +383,9 @@ int bhg_trace_prefix_device(bhg_context *ctx, const bhg_params *p, const double 
  * spheres: the horizon, the exit sphere, the disk plane when a disk is set, every sphere's surface.  0 for a start on or
  * inside the horizon and for anything not finite.  A replaying call needs clearance > rho (1 + 1e-6): tangent is refused. */
 double bhg_prefix_clearance(const bhg_params *p, const double *spheres, int32_t n_spheres, const double *x0);
+/* BHG_PREFIX_DEEP_ATTEMPTS as the library was built with it.  A library that exports this symbol takes BHG_PREFIX_RECORD_DEEP
+ * (one without it answers that mode with BHG_E_INVALID): what a caller that loads the library at run time asks first. */
+int32_t bhg_prefix_deep_attempts(void);
 
 /* --- the stages either side of the solve, on device ---------------------------------------- */
 /* Camera rays with the reference's multisample jitter (RelativisticRenderEngine.py:185-188,
