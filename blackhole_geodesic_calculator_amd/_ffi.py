@@ -67,6 +67,7 @@ EXPORTS = (
     "bhg_trace_start_device", "bhg_start_steps_match", "bhg_trace_prefix_device", "bhg_prefix_clearance",
     "bhg_prefix_deep_attempts",
     "bhg_trace_crossings_device", "bhg_trace_crossings", "bhg_disk_layers_size", "bhg_shade_disk_layers_device",
+    "bhg_travel_time_device", "bhg_travel_time", "bhg_shade_disk_layers_retarded_device",
 )
 MAX_CROSSINGS = 4   # BHG_MAX_CROSSINGS: disk crossings a crossings trace stores per ray (BHG_DISK_CROSSINGS)
 START_NONE, START_RECORD, START_REPLAY = 0, 1, 2   # BHG_START_*: the rays' initial steps kept across calls (BHG_START_STEPS)
@@ -622,6 +623,19 @@ def load():
                                                C.c_int32, C.POINTER(Scene), C.POINTER(Params), C.POINTER(Redshift),
                                                C.POINTER(Observer), _dp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.POINTER(DiskThermal), C.POINTER(DiskLayers), C.c_void_p]
+    L.bhg_travel_time_device.restype = C.c_int
+    L.bhg_travel_time_device.argtypes = [C.c_void_p, C.POINTER(Params), _dp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]
+    L.bhg_travel_time.restype = C.c_int
+    L.bhg_travel_time.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int32,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bhg_shade_disk_layers_retarded_device.restype = C.c_int
+    L.bhg_shade_disk_layers_retarded_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_size_t, C.c_int32, C.POINTER(Scene), C.POINTER(Params),
+                                                        C.POINTER(Redshift), C.POINTER(Observer), _dp, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.POINTER(DiskThermal), C.POINTER(DiskLayers),
+                                                        C.c_void_p, C.c_double, C.c_void_p]
     if L.bhg_version() != ABI_VERSION or not hasattr(L, "bhg_abi_check"):
         raise ImportError(f"libbhgeo ABI {L.bhg_version()} != expected {ABI_VERSION}: rebuild {LIB_PATH}")
     for name in ("bhg_params_size", "bhg_camera_size", "bhg_scene_size", "bhg_frame_scene_size"):
@@ -1167,6 +1181,32 @@ class Context:
                                           _addr(n_cross)))
         return end, flags, steps, acc, cross, n_cross
 
+    def travel_time(self, k0, x0, params: Params, max_crossings=0):
+        """bhg_travel_time: the crossings trace with the coordinate time along each ray.  k0[N,3], x0[3] or
+        [N,3] -> (end, flags, n_steps, n_accepted, cross[K,N,6], n_cross[N] -- trace_crossings' --, t_end[N] the time to the ray's
+        end (+inf: the ray ended in the hole), t_cross[K,N] the time of each stored crossing, NaN where a ray has none).
+        max_crossings = 0 (the disk of params may then be off): no records, K = 0."""
+        k0 = np.ascontiguousarray(k0, dtype=np.float64)
+        if k0.ndim != 2 or k0.shape[1] != 3:
+            raise ValueError("k0 must have shape [N, 3]")
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        n = k0.shape[0]
+        if x0.shape != (3,) and x0.shape != (n, 3):
+            raise ValueError("x0 must have shape [3] or [N, 3]")
+        K = max(int(max_crossings), 0)
+        end = np.empty((n, 6), np.float64)
+        flags = np.empty(n, np.uint8)
+        steps = np.empty(n, np.uint32)
+        acc = np.empty(n, np.uint32)
+        cross = np.full((K, n, 6), np.nan, np.float64)
+        t_cross = np.full((K, n), np.nan, np.float64)
+        n_cross = np.zeros(n, np.uint8)
+        t_end = np.empty(n, np.float64)
+        _check(load().bhg_travel_time(self._h, C.byref(params), _addr(x0), 1 if x0.ndim == 1 else 0, _addr(k0), n,
+                                      int(max_crossings), _addr(end), _addr(flags), _addr(steps), _addr(acc),
+                                      _addr(cross) if K else None, _addr(n_cross), _addr(t_end), _addr(t_cross) if K else None))
+        return end, flags, steps, acc, cross, n_cross, t_end, t_cross
+
     def trajectory(self, k0, x0, params: Params, n_points, spheres=None):
         """Sampled curves: (traj[N,6,T], n_valid[N], end[N,6], flags[N]); with spheres= (object spheres in the curved region,
         [[cx, cy, cz, radius], ...] BH-centred): (..., object_id[N]) -- bhg_trajectory_objects."""
@@ -1247,6 +1287,31 @@ class Context:
                                                  C.c_void_p(d_n_steps or None), C.c_void_p(d_n_accepted or None),
                                                  C.c_void_p(d_cross or None), C.c_void_p(d_n_cross or None),
                                                  C.c_void_p(stream or None)))
+
+    def travel_time_device(self, params: Params, n, d_k0, max_crossings, d_end, d_t_end, d_cross=0, d_n_cross=0, d_t_cross=0,
+                           x0_shared=None, d_x0=0, d_flags=0, d_n_steps=0, d_n_accepted=0, stream=0):
+        """bhg_travel_time_device: trace_crossings_device plus d_t_end [n] float64 and d_t_cross [max_crossings, n] float64.
+        max_crossings = 0: d_cross, d_n_cross, d_t_cross may be 0."""
+        xs = None if x0_shared is None else (C.c_double * 3)(*[float(v) for v in x0_shared])
+        _check(load().bhg_travel_time_device(self._h, C.byref(params), xs, C.c_void_p(d_x0 or None), C.c_void_p(d_k0 or None),
+                                             int(n), int(max_crossings), C.c_void_p(d_end or None), C.c_void_p(d_flags or None),
+                                             C.c_void_p(d_n_steps or None), C.c_void_p(d_n_accepted or None),
+                                             C.c_void_p(d_cross or None), C.c_void_p(d_n_cross or None),
+                                             C.c_void_p(d_t_end or None), C.c_void_p(d_t_cross or None), C.c_void_p(stream or None)))
+
+    def shade_disk_layers_retarded_device(self, d_end, d_flags, d_cross, d_n_cross, d_t_cross, phase_rate, n_pixels, samples,
+                                          scene: "Scene", layers: "DiskLayers", params=None, rs=None, obs=None, th=None,
+                                          x0_shared=None, d_k0=0, d_rgba=0, d_rgba_f32=0, d_scatter=0, d_end_dir=0, stream=0):
+        """bhg_shade_disk_layers_retarded_device: shade_disk_layers_device with layer m of ray i drawn at the phase
+        disk_phase - phase_rate * t_cross[m][i] (d_t_cross [max_crossings, S * n_pixels] float64 of travel_time_device)."""
+        xs = None if x0_shared is None else (C.c_double * 3)(*[float(v) for v in x0_shared])
+        _check(load().bhg_shade_disk_layers_retarded_device(
+            self._h, C.c_void_p(d_end or None), C.c_void_p(d_end_dir or None), C.c_void_p(d_flags or None),
+            C.c_void_p(d_cross or None), C.c_void_p(d_n_cross or None), int(n_pixels), int(samples), C.byref(scene),
+            None if params is None else C.byref(params), None if rs is None else C.byref(rs), _obs_ref(obs), xs,
+            C.c_void_p(d_k0 or None), C.c_void_p(d_rgba or None), C.c_void_p(d_rgba_f32 or None), C.c_void_p(d_scatter or None),
+            None if th is None else C.byref(th), None if layers is None else C.byref(layers), C.c_void_p(d_t_cross or None),
+            float(phase_rate), C.c_void_p(stream or None)))
 
     def shade_disk_layers_device(self, d_end, d_flags, d_cross, d_n_cross, n_pixels, samples, scene: "Scene", layers: "DiskLayers",
                                  params=None, rs=None, obs=None, th=None, x0_shared=None, d_k0=0, d_rgba=0, d_rgba_f32=0,

@@ -1076,6 +1076,10 @@ struct CrossOut {
     uint8_t *n_cross;
     int32_t max_cross;
     size_t stride;
+    // a travel-time call (bhg_travel_time_device): t_end non-null, t_cross [max_cross][stride] beside cross; cross, n_cross and
+    // t_cross may then be null with max_cross = 0
+    double *t_end = nullptr;
+    double *t_cross = nullptr;
 };
 
 // ONE launch: n <= BHG_MAX_RAYS_PER_LAUNCH rays (the kernels form a ray's byte offsets in 32 bits).
@@ -1223,7 +1227,10 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres,
         a.n_cross = cr->n_cross;
         a.max_cross = cr->max_cross;
         a.cross_stride = cr->stride;
-        HIP_TRY(bhg::launch_trace_crossings(a, rhs_id, s));
+        if (cr->t_end)
+            HIP_TRY(bhg::launch_travel_time(a, rhs_id, cr->t_end, cr->t_cross, s));
+        else
+            HIP_TRY(bhg::launch_trace_crossings(a, rhs_id, s));
         c->ev_valid = false;
     } else {
         // resident waves per CU of the trace kernel variant: asked of the runtime once per variant and context
@@ -1321,7 +1328,9 @@ int trace_device_impl(bhg_context *c, const bhg_params *p, const double *spheres
         const size_t m = std::min((size_t)bhg::BHG_MAX_RAYS_PER_LAUNCH, n - off);
         // (a crossings trace: this launch's rays sit at offset off inside every layer of the call's record array)
         CrossOut part{};
-        if (cr) part = CrossOut{cr->cross + off * 6, cr->n_cross + off, cr->max_cross, cr->stride};
+        if (cr)
+            part = CrossOut{cr->cross ? cr->cross + off * 6 : nullptr, cr->n_cross ? cr->n_cross + off : nullptr, cr->max_cross,
+                            cr->stride, cr->t_end ? cr->t_end + off : nullptr, cr->t_cross ? cr->t_cross + off : nullptr};
         const int rc = trace_device_one(c, &q, spheres, n_spheres, x0_shared, d_x0 ? d_x0 + off * 3 : nullptr,
                                         d_k0 ? d_k0 + off * 3 : nullptr, m, d_end ? d_end + off * 6 : nullptr,
                                         d_flags ? d_flags + off : nullptr, d_n_steps ? d_n_steps + off : nullptr,
@@ -1471,6 +1480,95 @@ int bhg_trace_crossings(bhg_context *c, const bhg_params *p, const double *x0, i
     HIP_TRY(hipMemcpyAsync(end, d + o_end, b6, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(cross, d + o_cross, bc, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(n_cross, d + o_nc, n, hipMemcpyDeviceToHost, s));
+    if (flags) HIP_TRY(hipMemcpyAsync(flags, d + o_flags, n, hipMemcpyDeviceToHost, s));
+    if (n_steps) HIP_TRY(hipMemcpyAsync(n_steps, d + o_steps, bu, hipMemcpyDeviceToHost, s));
+    if (n_accepted) HIP_TRY(hipMemcpyAsync(n_accepted, d + o_acc, bu, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return BHG_OK;
+}
+
+// what the travel-time trace covers, checked before the context like the crossings trace's
+static int travel_time_check(const bhg_params *p, int32_t max_crossings, const double *t_end)
+{
+    int rc = validate(p);
+    if (rc != BHG_OK) return rc;
+    if (p->method != BHG_METHOD_DP54) return fail(BHG_E_INVALID, "the travel-time trace is DP5(4) only: method must be BHG_METHOD_DP54");
+    if (p->time_like) return fail(BHG_E_INVALID, "the travel-time trace covers null rays only: time_like must be 0");
+    if (max_crossings < 0 || max_crossings > BHG_MAX_CROSSINGS)
+        return fail(BHG_E_INVALID, "max_crossings must be in [0, BHG_MAX_CROSSINGS]");
+    if (max_crossings > 0 && !(p->disk_r_out > 0.0))
+        return fail(BHG_E_INVALID, "crossing times need a disk: disk_r_out must be > 0 when max_crossings > 0");
+    if (!t_end) return fail(BHG_E_INVALID, "t_end is NULL");
+    return BHG_OK;
+}
+
+int bhg_travel_time_device(bhg_context *c, const bhg_params *p, const double *x0_shared, const double *d_x0,
+                           const double *d_k0, size_t n, int32_t max_crossings, double *d_end, uint8_t *d_flags,
+                           uint32_t *d_n_steps, uint32_t *d_n_accepted, double *d_cross, uint8_t *d_n_cross, double *d_t_end,
+                           double *d_t_cross, void *stream)
+{
+    int rc = travel_time_check(p, max_crossings, d_t_end);
+    if (rc != BHG_OK) return rc;
+    if (n && !d_end) return fail(BHG_E_INVALID, "end is NULL");
+    if (n && max_crossings > 0 && (!d_cross || !d_n_cross || !d_t_cross))
+        return fail(BHG_E_INVALID, "cross / n_cross / t_cross is NULL with max_crossings > 0");
+    // (without records the kernel writes neither cross nor t_cross; n_cross is still counted when it is given and a disk is set)
+    const CrossOut cr{max_crossings > 0 ? d_cross : nullptr, d_n_cross, max_crossings, n, d_t_end, max_crossings > 0 ? d_t_cross : nullptr};
+    return trace_device_impl(c, p, nullptr, 0, x0_shared, d_x0, d_k0, n, d_end, d_flags, d_n_steps, d_n_accepted, nullptr, stream,
+                             nullptr, nullptr, BHG_START_NONE, &cr);
+}
+
+// the host-buffer call, as bhg_trace_crossings: upload, one device call, download (cross, n_cross and t_cross may be NULL with
+// max_crossings = 0)
+int bhg_travel_time(bhg_context *c, const bhg_params *p, const double *x0, int x0_is_shared, const double *k0, size_t n,
+                    int32_t max_crossings, double *end, uint8_t *flags, uint32_t *n_steps, uint32_t *n_accepted, double *cross,
+                    uint8_t *n_cross, double *t_end, double *t_cross)
+{
+    int rc = travel_time_check(p, max_crossings, t_end);
+    if (rc != BHG_OK) return rc;
+    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
+    if (n == 0) return BHG_OK;
+    if (!x0 || !k0 || !end) return fail(BHG_E_INVALID, "x0 / k0 / end is NULL");
+    if (max_crossings > 0 && (!cross || !n_cross || !t_cross))
+        return fail(BHG_E_INVALID, "cross / n_cross / t_cross is NULL with max_crossings > 0");
+    if (n > 0xFFFFFFFFull) return fail(BHG_E_INVALID, "n must be < 2^32 per call");
+    ENTER_DEVICE(c->device);
+    const size_t b3 = n * 3 * sizeof(double), b6 = 2 * b3, bc = (size_t)max_crossings * b6, bu = n * sizeof(uint32_t),
+                 bt = n * sizeof(double), btc = (size_t)max_crossings * bt;
+    const size_t o_x0 = b3, o_end = o_x0 + (x0_is_shared ? 0 : b3), o_cross = o_end + b6, o_te = o_cross + bc, o_tc = o_te + bt,
+                 o_steps = o_tc + btc, o_acc = o_steps + bu, o_flags = o_acc + bu, o_nc = o_flags + ((n + 7) & ~size_t(7));
+    char *d = nullptr;
+    HIP_TRY(hipMalloc((void **)&d, o_nc + n));
+    struct Free {
+        char *d;
+        hipStream_t s;
+        ~Free()
+        {
+            (void)hipStreamSynchronize(s);
+            (void)hipFree(d);
+        }
+    } guard{d, c->stream};
+    hipStream_t s = c->stream;
+    HIP_TRY(hipMemcpyAsync(d, k0, b3, hipMemcpyHostToDevice, s));
+    if (!x0_is_shared) HIP_TRY(hipMemcpyAsync(d + o_x0, x0, b3, hipMemcpyHostToDevice, s));
+    if (max_crossings > 0) {
+        HIP_TRY(hipMemcpyAsync(d + o_cross, cross, bc, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d + o_tc, t_cross, btc, hipMemcpyHostToDevice, s));
+    }
+    const bool want_nc = n_cross != nullptr;
+    rc = bhg_travel_time_device(c, p, x0_is_shared ? x0 : nullptr, x0_is_shared ? nullptr : (const double *)(d + o_x0),
+                                (const double *)d, n, max_crossings, (double *)(d + o_end), (uint8_t *)(d + o_flags),
+                                (uint32_t *)(d + o_steps), (uint32_t *)(d + o_acc), max_crossings > 0 ? (double *)(d + o_cross) : nullptr,
+                                want_nc ? (uint8_t *)(d + o_nc) : nullptr, (double *)(d + o_te),
+                                max_crossings > 0 ? (double *)(d + o_tc) : nullptr, s);
+    if (rc != BHG_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(end, d + o_end, b6, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(t_end, d + o_te, bt, hipMemcpyDeviceToHost, s));
+    if (max_crossings > 0) {
+        HIP_TRY(hipMemcpyAsync(cross, d + o_cross, bc, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(t_cross, d + o_tc, btc, hipMemcpyDeviceToHost, s));
+    }
+    if (want_nc) HIP_TRY(hipMemcpyAsync(n_cross, d + o_nc, n, hipMemcpyDeviceToHost, s));
     if (flags) HIP_TRY(hipMemcpyAsync(flags, d + o_flags, n, hipMemcpyDeviceToHost, s));
     if (n_steps) HIP_TRY(hipMemcpyAsync(n_steps, d + o_steps, bu, hipMemcpyDeviceToHost, s));
     if (n_accepted) HIP_TRY(hipMemcpyAsync(n_accepted, d + o_acc, bu, hipMemcpyDeviceToHost, s));
@@ -1878,6 +1976,9 @@ struct LayersIn {
     const double *cross;
     const uint8_t *n_cross;
     const bhg_disk_layers *set;
+    // the retarded shade (bhg_shade_disk_layers_retarded_device): nullptr / 0 = the plain layered shade's kernels
+    const double *t_cross = nullptr;
+    double phase_rate = 0.0;
 };
 
 int shade(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags, const int8_t *d_object_id,
@@ -2017,7 +2118,8 @@ int shade(bhg_context *c, const double *d_end, const double *d_end_dir, const ui
         a.n_cross = ly->n_cross;
         a.max_cross = ly->set->max_crossings;
         a.transmit = 1.0 - ly->set->opacity;
-        HIP_TRY(bhg::launch_shade_layers(a, (hipStream_t)stream));
+        const bool retarded = ly->t_cross && ly->phase_rate != 0.0;
+        HIP_TRY(bhg::launch_shade_layers(a, (hipStream_t)stream, retarded ? ly->t_cross : nullptr, ly->phase_rate));
         return BHG_OK;
     }
     HIP_TRY(bhg::launch_shade(a, (hipStream_t)stream));
@@ -2161,6 +2263,20 @@ int bhg_shade_disk_layers_device(bhg_context *c, const double *d_end, const doub
                                  void *stream)
 {
     const LayersIn ly{d_cross, d_n_cross, layers};
+    return shade(c, d_end, d_end_dir, d_flags, nullptr, n_pixels, samples, sc, p, rs, obs, nullptr, x0_shared, d_k0, d_rgba,
+                 d_rgba_f32, d_scatter, nullptr, nullptr, th, nullptr, stream, &ly);
+}
+
+int bhg_shade_disk_layers_retarded_device(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
+                                          const double *d_cross, const uint8_t *d_n_cross, size_t n_pixels, int32_t samples,
+                                          const bhg_scene *sc, const bhg_params *p, const bhg_redshift *rs, const bhg_observer *obs,
+                                          const double *x0_shared, const double *d_k0, double *d_rgba, float *d_rgba_f32,
+                                          const int64_t *d_scatter, const bhg_disk_thermal *th, const bhg_disk_layers *layers,
+                                          const double *d_t_cross, double phase_rate, void *stream)
+{
+    if (!std::isfinite(phase_rate)) return fail(BHG_E_INVALID, "phase_rate must be finite");
+    // (phase_rate == 0 or no times: the plain layered shade, its own kernels)
+    const LayersIn ly{d_cross, d_n_cross, layers, d_t_cross, phase_rate};
     return shade(c, d_end, d_end_dir, d_flags, nullptr, n_pixels, samples, sc, p, rs, obs, nullptr, x0_shared, d_k0, d_rgba,
                  d_rgba_f32, d_scatter, nullptr, nullptr, th, nullptr, stream, &ly);
 }

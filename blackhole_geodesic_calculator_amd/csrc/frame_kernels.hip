@@ -211,6 +211,26 @@ __device__ __forceinline__ void disk_colour(const ShadeArgs &A, const double *e,
     rgb[1] *= intensity;
     rgb[2] *= intensity;
 }
+// ... its twin at another phase: the retarded layers' 
+__device__ __forceinline__ void disk_colour_at(const ShadeArgs &A, const double *e, double phase, double rgb[3])
+{
+    const double x = e[0], y = e[1];
+    const double R = sqrt(x * x + y * y);
+    const double scale = (R - A.disk_r_in) / (A.disk_r_out - A.disk_r_in);
+    const double dm = scale - A.disk_mean;
+    const double intensity = A.disk_intensity * exp(-(dm * dm) / (2.0 * A.disk_stddev * A.disk_stddev)) /
+                             sqrt(2.0 * M_PI * A.disk_stddev);
+    double cx = x / R;
+    cx = cx > 1.0 ? 1.0 : (cx < -1.0 ? -1.0 : cx);
+    const double texture_x = (phase + acos(cx) * (y < 0.0 ? -1.0 : 1.0)) / M_PI;
+    if (A.disk_tex)
+        sky_lookup(A.disk_tex, A.disk_w, A.disk_h, texture_x, scale, rgb);
+    else
+        rgb[0] = rgb[1] = rgb[2] = 1.0;
+    rgb[0] *= intensity;
+    rgb[1] *= intensity;
+    rgb[2] *= intensity;
+}
 
 // Object colour: pure Lambert sum over point lamps with 1/d^2 falloff, light paths straight (flat space) as in
 // spacetime_hit (RelativisticRenderEngine.py:341-363: base_color = intensity, colour += base_color * intensity *
@@ -990,9 +1010,19 @@ __global__ void __launch_bounds__(256) shade_reduce_serial_kernel(const ShadeArg
 // C is ray_colour's disk branch on the record: disk_colour and redshift_weigh, or (THERM) disk_thermal.  Sum and products in
 // this order (no contraction): the order is part of the result.  opacity = 1 (T = 0): layer 0 alone, nothing behind a disk
 // ray is looked at -- the opaque disk's image.
-template <bool RS, bool OBS, bool THERM>
+// RET (bhg_shade_disk_layers_retarded_device), a compile-time switch by presence: empty, or one Retarded --
+// layer m of ray i is then coloured at the phase the disk had when the light left it, disk_phase - phase_rate * t_cross[m][i]; a
+// layer whose time is not finite is black and still absorbs.  The retarded instances take it as a kernel argument of their own
+// behind the others: ShadeArgs, and with it the argument block of every other shade kernel, is what it was.
+struct Retarded {
+    const double *t_cross;    // [max_cross][S*n_pixels]: the crossing times of the travel-time trace
+    double phase_rate;        // d(disk_phase) / dt, radians per unit of coordinate time
+};
+__device__ __forceinline__ const Retarded &only(const Retarded &r) { return r; }
+
+template <bool RS, bool OBS, bool THERM, class... RET>
 __device__ __forceinline__ void layers_colour(const ShadeArgs &A, uint64_t i, uint64_t n_rays, uint8_t fl, double c0, double c1,
-                                              double c2, double rgb[3])
+                                              double c2, double rgb[3], const RET &...ret)
 {
     rgb[0] = rgb[1] = rgb[2] = 0.0;
     double w = 1.0;
@@ -1004,7 +1034,16 @@ __device__ __forceinline__ void layers_colour(const ShadeArgs &A, uint64_t i, ui
             double t_em;
             disk_thermal<OBS>(A.th, A.rs, A.obs, A.rs.x0, A.k0 + i * 3, e, t_em, c);
         } else {
-            disk_colour(A, e, c);
+            if constexpr (sizeof...(RET) != 0) {
+                const Retarded &R = only(ret...);
+                const double tm = R.t_cross[(uint64_t)m * n_rays + i];
+                if (isfinite(tm))
+                    disk_colour_at(A, e, A.disk_phase - R.phase_rate * tm, c);
+                else
+                    c[0] = c[1] = c[2] = 0.0;
+            } else {
+                disk_colour(A, e, c);
+            }
             if (RS) redshift_weigh<OBS>(A, i, RS_DISK, BHG_REDSHIFT_DISK_, e, c);
         }
         rgb[0] = rgb[0] + w * c[0];
@@ -1024,8 +1063,8 @@ __device__ __forceinline__ void layers_colour(const ShadeArgs &A, uint64_t i, ui
 }
 
 // shade_reduce_kernel's shape: one thread per RAY, the S samples of a pixel staged in LDS and summed in sample order
-template <bool RS, bool OBS, bool THERM>
-__global__ void __launch_bounds__(256) shade_layers_kernel(const ShadeArgs A, const uint32_t ppb)
+template <bool RS, bool OBS, bool THERM, class... RET>
+__global__ void __launch_bounds__(256) shade_layers_kernel(const ShadeArgs A, const uint32_t ppb, const RET... ret)
 {
     __shared__ double col[256 * 3];
     const uint32_t t = threadIdx.x, S = (uint32_t)A.samples;
@@ -1036,7 +1075,7 @@ __global__ void __launch_bounds__(256) shade_layers_kernel(const ShadeArgs A, co
         const uint64_t i = (uint64_t)s * A.n_pixels + p;
         const double *d = A.dir ? A.dir + i * 3 : A.end + i * 6 + 3;
         double rgb[3];
-        layers_colour<RS, OBS, THERM>(A, i, (uint64_t)S * A.n_pixels, A.flags[i], d[0], d[1], d[2], rgb);
+        layers_colour<RS, OBS, THERM>(A, i, (uint64_t)S * A.n_pixels, A.flags[i], d[0], d[1], d[2], rgb, ret...);
         col[t * 3 + 0] = rgb[0];
         col[t * 3 + 1] = rgb[1];
         col[t * 3 + 2] = rgb[2];
@@ -1055,8 +1094,8 @@ __global__ void __launch_bounds__(256) shade_layers_kernel(const ShadeArgs A, co
 }
 
 // more samples than a workgroup has threads: one thread per pixel (shade_reduce_serial_kernel's shape)
-template <bool RS, bool OBS, bool THERM>
-__global__ void __launch_bounds__(256) shade_layers_serial_kernel(const ShadeArgs A)
+template <bool RS, bool OBS, bool THERM, class... RET>
+__global__ void __launch_bounds__(256) shade_layers_serial_kernel(const ShadeArgs A, const RET... ret)
 {
     const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= A.n_pixels) return;
@@ -1065,7 +1104,7 @@ __global__ void __launch_bounds__(256) shade_layers_serial_kernel(const ShadeArg
         const uint64_t i = (uint64_t)s * A.n_pixels + p;
         const double *d = A.dir ? A.dir + i * 3 : A.end + i * 6 + 3;
         double rgb[3];
-        layers_colour<RS, OBS, THERM>(A, i, (uint64_t)A.samples * A.n_pixels, A.flags[i], d[0], d[1], d[2], rgb);
+        layers_colour<RS, OBS, THERM>(A, i, (uint64_t)A.samples * A.n_pixels, A.flags[i], d[0], d[1], d[2], rgb, ret...);
         acc[0] += rgb[0];
         acc[1] += rgb[1];
         acc[2] += rgb[2];
@@ -1219,25 +1258,35 @@ hipError_t launch_shade(const ShadeArgs &a, hipStream_t s)
     return hipGetLastError();
 }
 
-template <bool RS, bool OBS, bool THERM>
-void launch_shade_layers_instance(const ShadeArgs &a, hipStream_t s)
+template <bool RS, bool OBS, bool THERM, class... RET>
+void launch_shade_layers_instance(const ShadeArgs &a, hipStream_t s, const RET &...ret)
 {
     if (a.samples > 256) {
         const dim3 grid((unsigned)((a.n_pixels + 255) / 256));
-        BHG_LAUNCH((shade_layers_serial_kernel<RS, OBS, THERM>), grid, dim3(256), 0, s, a);
+        BHG_LAUNCH((shade_layers_serial_kernel<RS, OBS, THERM, RET...>), grid, dim3(256), 0, s, a, ret...);
         return;
     }
     const uint32_t ppb = 256u / (uint32_t)a.samples;
     const dim3 grid((unsigned)((a.n_pixels + ppb - 1) / ppb));
-    BHG_LAUNCH((shade_layers_kernel<RS, OBS, THERM>), grid, dim3(256), 0, s, a, ppb);
+    BHG_LAUNCH((shade_layers_kernel<RS, OBS, THERM, RET...>), grid, dim3(256), 0, s, a, ppb, ret...);
 }
 
-// the layered shade's five instances, chosen as launch_shade_mov chooses: thermal instances are redshift instances
-hipError_t launch_shade_layers(const ShadeArgs &a, hipStream_t s)
+// the layered shade's five instances, chosen as launch_shade_mov chooses: thermal instances are redshift instances.  With
+// t_cross given (the C layer gives it only with a nonzero phase_rate) the three non-thermal ones have a retarded twin; the thermal
+// disk has no texture to turn, and its instances are the same with or without
+hipError_t launch_shade_layers(const ShadeArgs &a, hipStream_t s, const double *t_cross, double phase_rate)
 {
     if (a.n_pixels == 0) return hipSuccess;
     const bool therm = a.th.on != 0, rs = a.rs.apply != 0 || therm, obs = rs && a.obs.on;
-    if (therm) {
+    if (t_cross && !therm) {
+        const Retarded ret{t_cross, phase_rate};
+        if (obs)
+            launch_shade_layers_instance<true, true, false>(a, s, ret);
+        else if (rs)
+            launch_shade_layers_instance<true, false, false>(a, s, ret);
+        else
+            launch_shade_layers_instance<false, false, false>(a, s, ret);
+    } else if (therm) {
         if (obs)
             launch_shade_layers_instance<true, true, true>(a, s);
         else

@@ -91,7 +91,7 @@ struct TraceArgs {
     double *start_h;             // [n] or nullptr
     int32_t start_mode;          // BHG_START_*_
     // disk crossings (disk_crossings_kernel alone; no other kernel looks): last, so that no other member moves
-    int32_t max_cross;           // crossings stored per ray, 1 .. BHG_MAX_CROSSINGS_
+    int32_t max_cross;           // crossings stored per ray, 1 .. BHG_MAX_CROSSINGS_ (travel_time_kernel: 0 too)
     double *cross;               // [max_cross][cross_stride][6]: record m of ray i, Cartesian, at (m * cross_stride + i) * 6
     uint8_t *n_cross;            // [n]: crossings counted (saturating at 255), stored or not
     uint64_t cross_stride;       // rays per layer of cross: the CALL's ray count (a launch may be a part of a call)
@@ -296,7 +296,9 @@ struct ThermalArgs {
 hipError_t launch_raygen(const RaygenArgs &a, hipStream_t s);
 hipError_t launch_shade(const ShadeArgs &a, hipStream_t s);
 // the layered shade of an optically thin disk (shade_layers_kernel): a.cross / n_cross / max_cross / transmit filled
-hipError_t launch_shade_layers(const ShadeArgs &a, hipStream_t s);
+// t_cross: nullptr, or [max_cross][S*n_pixels], the crossing times of the travel-time trace -- the retarded instances then draw
+// layer m of ray i at a.disk_phase - phase_rate * t_cross[m][i] (bhg_shade_disk_layers_retarded_device)
+hipError_t launch_shade_layers(const ShadeArgs &a, hipStream_t s, const double *t_cross = nullptr, double phase_rate = 0.0);
 hipError_t launch_redshift(const RedshiftArgs &a, hipStream_t s);
 hipError_t launch_redshift_motion(const RedshiftArgs &a, hipStream_t s);
 hipError_t launch_polarisation(const PolarisationArgs &a, bool obs, hipStream_t s);
@@ -314,6 +316,11 @@ hipError_t trace_occupancy(int method, int rhs, int evt, int *blocks_per_cu);
 hipError_t launch_trace_crossings(const TraceArgs &a, int rhs, hipStream_t s);
 // ... its Kerr instance, in the Kerr translation unit; the caller runs launch_kerr_finalize on the end records afterwards
 hipError_t launch_trace_crossings_kerr(const TraceArgs &a, hipStream_t s);
+// the crossings trace with the coordinate time along each ray (travel_time_kernel): t_end [a.n], t_cross
+// [max_cross][cross_stride] beside a.cross.  a.max_cross = 0 and a.disk_r_out = 0 are allowed (a.cross, a.n_cross, t_cross may
+// then be null); the Kerr instance sits in the Kerr translation unit and wants launch_kerr_finalize after it
+hipError_t launch_travel_time(const TraceArgs &a, int rhs, double *t_end, double *t_cross, hipStream_t s);
+hipError_t launch_travel_time_kerr(const TraceArgs &a, double *t_end, double *t_cross, hipStream_t s);
 // the recording pass of the start-up records (record_prefix_kernel: one lane per ray; rhs Christoffel or reduced, a.x0 == nullptr):
 // rec [7][a.n] 16-byte planes, rho the radius about a.x0s the recorded steps stay inside.  deep: the record carries on through
 // rejected attempts (BHG_PREFIX_RECORD_DEEP: at most BHG_PREFIX_DEEP_ACCEPTED_ accepted steps in BHG_PREFIX_DEEP_ATTEMPTS_ attempts)

@@ -3261,6 +3261,217 @@ hipError_t launch_trace_crossings(const TraceArgs &a, int rhs, hipStream_t s)
 #endif
 
 // ------------------------------------------------------------------------------------------
+// Light travel time (bhg_travel_time_device): the crossings trace above, step for step, plus the
+// coordinate time t that elapses along the ray -- Schwarzschild / Boyer-Lindquist t, a function of position and the ray's
+// Killing constants alone:
+//     Schwarzschild (both forms):  dt/dlambda = E / (1 - r_s / r),  E = sqrt(f0 (|k0|^2 + h0 (n0.k0)^2)) at the start point
+//     Kerr:                        dt/dlambda = [E ((r^2 + a^2)^2 - Delta a^2 sin^2 theta) - 2 M a r L] / (Sigma Delta)
+// (kerr_rhs.inc's kt, which does not depend on the velocities; E, L as kerr_cart_to_bl leaves them in Metric).
+// Quadrature: 6-point Gauss-Legendre per accepted step on the step's own dense-output position, summed in step order; the
+// step that holds the ray's terminal event runs to the event's root only.  The time of a crossing is the time at the
+// start of its step plus the same rule on [lambda_j, root].  A node at r <= r_hor makes the ray's time and every time
+// after it +inf (the ray stepped across the hole: section 7's transparent centre); a ray that ends on the horizon or
+// starts inside has t_end = +inf, a ray flagged NaN has NaN.
+// A sibling of disk_crossings_kernel rather than a switch on it: that kernel's code stays as it is.  The position half of
+// the dense output is live on every accepted step here, so the kernel has the whole register file of one wave
+// (__launch_bounds__(64)) rather than the headline kernels' three-waves budget: this is a side path.
+// max_cross = 0 and disk_r_out = 0 are allowed: no plane test, no records (cross, n_cross, t_cross may then be null).  With the
+// disk off end / flags / n_steps / n_accepted are the PLAIN trace's bit for bit (with a disk: the crossings trace's).
+// ------------------------------------------------------------------------------------------
+// numpy.polynomial.legendre.leggauss(6) mapped to [0, 1]: nodes (1 + x) / 2, weights w / 2
+__device__ constexpr double GL6_X[6] = {0.033765242898423975, 0.16939530676686776, 0.38069040695840151,
+                                        0.61930959304159849, 0.83060469323313224, 0.96623475710157603};
+__device__ constexpr double GL6_W[6] = {0.085662246189584873, 0.18038078652406947, 0.23395696728634569,
+                                        0.23395696728634569, 0.18038078652406947, 0.085662246189584873};
+
+// dt/dlambda at the dense-output position q (Kerr: Boyer-Lindquist r, theta); inside: q lies at r <= r_hor
+template <int RHS>
+__device__ __forceinline__ double time_rate(const TraceArgs &A, const Metric &met, double E, const double q[3], bool &inside)
+{
+    if (RHS == BHG_RHS_KERR_BL_) {
+        const double r = q[0], a = met.a, M = met.M;
+        double sn, cs;
+        sincos_pi4(q[1], sn, cs);
+        const double r2 = r * r, a2 = a * a;
+        const double ra = r2 + a2, Sig = r2 + a2 * (cs * cs), Del = ra - 2.0 * M * r;
+        inside = inside || (r <= A.r_hor);
+        return (met.E * (ra * ra - Del * a2 * (sn * sn)) - 2.0 * M * a * r * met.L) / (Sig * Del);
+    }
+    const double r = sqrt(__builtin_fma(q[2], q[2], __builtin_fma(q[1], q[1], q[0] * q[0])));
+    inside = inside || (r <= A.r_hor);
+    return E / (1.0 - A.r_s / r);
+}
+
+// the rule on [d.t0, d.t0 + w]; +inf when a node lies inside the horizon radius
+template <int RHS>
+__device__ __forceinline__ double time_quadrature(const TraceArgs &A, const Metric &met, double E, const Dense &d, double w)
+{
+    double sum = 0.0;
+    bool inside = false;
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        double q[3];
+        dense_pos(d, __builtin_fma(w, GL6_X[k], d.t0), q);
+        sum = __builtin_fma(GL6_W[k], time_rate<RHS>(A, met, E, q, inside), sum);
+    }
+    return inside ? __builtin_inf() : w * sum;
+}
+
+template <int RHS>
+__global__ void __launch_bounds__(64) travel_time_kernel(const TraceArgs A, double *t_end, double *t_cross)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= A.n) return;
+    const bool bl = RHS == BHG_RHS_KERR_BL_;
+    const bool disk = A.disk_r_out > 0.0;
+    RayState S;
+    double xe[3], ve[3];
+    if (start_ray<RHS, true>(A, i, S, xe, ve)) {    // final at once, no crossings
+        if (A.n_cross) A.n_cross[i] = 0;
+        t_end[i] = __builtin_inf();
+        store_result(A, (uint32_t)i, xe, ve, BHG_FLAG_START_INSIDE_ | BHG_FLAG_HIT_HORIZON_, 0, 0);
+        return;
+    }
+    // Schwarzschild: E from the start state (Kerr: Metric::E)
+    double E = 0.0;
+    if (!bl) {
+        const double r0 = sqrt(__builtin_fma(S.x[2], S.x[2], __builtin_fma(S.x[1], S.x[1], S.x[0] * S.x[0])));
+        const double f0 = 1.0 - A.r_s / r0, h0 = A.r_s / (r0 - A.r_s);
+        const double nk = (S.x[0] * S.v[0] + S.x[1] * S.v[1] + S.x[2] * S.v[2]) / r0;
+        const double kk = S.v[0] * S.v[0] + S.v[1] * S.v[1] + S.v[2] * S.v[2];
+        E = sqrt(f0 * (kk + h0 * nk * nk));
+    }
+    double tt = 0.0;        // the time up to S.t
+    uint32_t flags = 0, n_cross = 0;
+    bool stored = false;    // the ray's result is in place already
+    for (;;) {
+        StepTry P;
+        const uint32_t st = dp54_attempt<RHS>(A, S, P);
+        if (st == DP54_REJECTED) continue;
+        if (st != DP54_ACCEPTED) {
+            flags = st;
+            break;
+        }
+        bool ev_h, ev_e;
+        radial_events(A, S, P, ev_h, ev_e);
+        const bool ev_d = disk && crossed_disk_plane<RHS>(S.x, P.xn);
+        uint32_t evflag = 0;
+        double t_stop = P.t_new;
+        Dense d;
+        build_dense_pos(d, S.t, P.h, S.x, S.v, S.a1, P.a2, P.a3, P.a4, P.a5, P.a6, P.a7);
+        if (ev_h || ev_e || ev_d) {
+            build_dense_dir(d, S.a1, P.a2, P.a3, P.a4, P.a5, P.a6, P.a7);
+            auto g_z = [&](double tq) {
+                if (!bl) return dense_z(d, tq);
+                double q[3], sn, cs;
+                dense_pos(d, tq, q);
+                sincos_pi4(q[1], sn, cs);
+                return cs;
+            };
+            if (ev_h || ev_e) {
+                // the terminal events, settled as the trace kernels settle them (the earliest root wins, horizon before exit)
+                double best;
+                int obj;
+                evflag = settle_events<EVT_EXIT>(
+                    A, (ev_h ? EV_HORIZON : 0u) | (ev_e ? EV_EXIT : 0u), S.t, P.t_new, S.x, P.xn,
+                    [&](double tq, double Rr) { return dense_g(d, tq, Rr, bl); }, g_z,
+                    [&](double tq, double xq[3]) { dense_pos(d, tq, xq); }, bl, best, obj);
+                if (evflag) t_stop = best;
+            }
+            if (ev_d) {
+                const double root = brent_root(g_z, S.t, P.t_new);
+                double sx[3], sv[3];
+                dense_pos(d, root, sx);
+                // cylindrical radius of the crossing point, as settle_events takes it
+                double R;
+                if (bl) {
+                    double sn, cs;
+                    sincos_pi4(sx[1], sn, cs);
+                    R = sqrt(sx[0] * sx[0] + A.spin * A.spin) * fabs(sn);
+                } else {
+                    R = sqrt(sx[0] * sx[0] + sx[1] * sx[1]);
+                }
+                if (R >= A.disk_r_in && R <= A.disk_r_out && (!evflag || root <= t_stop)) {
+                    if (n_cross < (uint32_t)A.max_cross) {
+                        dense_dir(d, root, sv);
+                        if (bl) {
+                            double c[6];
+                            bl_record_to_cart(A.spin, sx, sv, c);
+                            for (int q = 0; q < 3; q++) {
+                                sx[q] = c[q];
+                                sv[q] = c[3 + q];
+                            }
+                        }
+                        double *o = A.cross + ((uint64_t)n_cross * A.cross_stride + i) * 6;
+                        reinterpret_cast<double2 *>(o)[0] = make_double2(sx[0], sx[1]);
+                        reinterpret_cast<double2 *>(o)[1] = make_double2(sx[2], sv[0]);
+                        reinterpret_cast<double2 *>(o)[2] = make_double2(sv[1], sv[2]);
+                        t_cross[(uint64_t)n_cross * A.cross_stride + i] = tt + time_quadrature<RHS>(A, S.met, E, d, root - S.t);
+                    }
+                    n_cross++;
+                }
+            }
+        }
+        tt += time_quadrature<RHS>(A, S.met, E, d, t_stop - S.t);
+        if (evflag) {
+            flags = evflag;
+            // Disk off: the results are the plain trace's, bit for bit.  The trace kernels take a step whose ONE candidate event
+            // is the exit sphere through their certified Newton search first (dp54_short_core: the same root to 4 eps, another
+            // iterate) and leave everything else to the Brent search above; so does this.  It stores the ray's result itself.
+            // The time still runs to Brent's root, as it does with a disk: one definition of the time, two ulp apart at most.
+            if (!disk && ev_e && !ev_h &&
+                dp54_short_core<RHS, EVT_EXIT>(A, S.x, S.v, S.a1, S.t, P.t_new, P.h, P.a2, P.a3, P.a4, P.a5, P.a6, P.a7, P.xn, P.vn,
+                                               EV_EXIT, (uint32_t)i, S.n_att, S.n_acc) == PARK_ENDED) {
+                stored = true;
+                break;
+            }
+            dense_pos(d, t_stop, xe);
+            dense_dir(d, t_stop, ve);
+            break;
+        }
+        if (advance(A, S, P, xe, ve)) {
+            flags = BHG_FLAG_REACHED_END_;
+            break;
+        }
+    }
+    if (A.n_cross) A.n_cross[i] = (uint8_t)(n_cross < 255u ? n_cross : 255u);
+    if (stored) {
+        t_end[i] = tt;
+        return;
+    }
+    if (flags & BHG_FLAG_HIT_HORIZON_) tt = __builtin_inf();
+    // (the state finish_ray stores; store_result's own test for the NaN flag)
+    {
+        const bool gave_up = flags & (BHG_FLAG_STEP_TOO_SMALL_ | BHG_FLAG_MAX_STEPS_);
+        const double *fx = gave_up ? S.x : xe, *fv = gave_up ? S.v : ve;
+        if (!isfinite(((fx[0] + fx[1]) + (fx[2] + fv[0])) + (fv[1] + fv[2]))) tt = __builtin_nan("");
+    }
+    t_end[i] = tt;
+    finish_ray(A, i, S, xe, ve, flags);
+}
+
+#if defined(BHG_TU_KERR)
+hipError_t launch_travel_time_kerr(const TraceArgs &a, double *t_end, double *t_cross, hipStream_t s)
+{
+    if (a.n == 0) return hipSuccess;
+    BHG_LAUNCH((travel_time_kernel<BHG_RHS_KERR_BL_>), dim3((unsigned)((a.n + 63) / 64)), dim3(64), 0, s, a, t_end, t_cross);
+    return hipGetLastError();
+}
+#elif !defined(BHG_TU_TIMELIKE)
+hipError_t launch_travel_time(const TraceArgs &a, int rhs, double *t_end, double *t_cross, hipStream_t s)
+{
+    if (rhs == BHG_RHS_KERR_BL_) return launch_travel_time_kerr(a, t_end, t_cross, s);
+    if (a.n == 0) return hipSuccess;
+    const dim3 grid((unsigned)((a.n + 63) / 64));
+    if (rhs == BHG_RHS_REDUCED_)
+        BHG_LAUNCH((travel_time_kernel<BHG_RHS_REDUCED_>), grid, dim3(64), 0, s, a, t_end, t_cross);
+    else
+        BHG_LAUNCH((travel_time_kernel<BHG_RHS_CHRISTOFFEL_>), grid, dim3(64), 0, s, a, t_end, t_cross);
+    return hipGetLastError();
+}
+#endif
+
+// ------------------------------------------------------------------------------------------
 // Start-up records (bhg_trace_prefix_device).  scipy's start guess h0 is one to two decades below the
 // step a ray settles on, and the controller climbs there by its x10 clamp: three to four accepted steps next to the camera,
 // a quarter of all the attempts of a frame, whose outcome depends on the ray, the metric, the tolerances, lambda_end and

@@ -193,6 +193,9 @@ class DeviceFrame:
         self.disk_layers = None       # _ffi.DiskLayers (set_disk_layers) or None: the opaque disk of the trace parameters
         self.d_cross = None           # [max_crossings, n, 6] fp64 crossing records and
         self.d_n_cross = None         # [n] uint8 crossing counts of the last crossings trace
+        self.phase_rate = 0.0         # set_disk_layers(phase_rate=): d(disk_phase)/dt of the retarded shade, 0 = off
+        self.d_t_cross = None         # [max_crossings, n] fp64 crossing times and
+        self.d_t_end = None           # [n] fp64 times to the rays' ends of the last travel-time trace (phase_rate != 0 only)
 
     def _stream(self):
         return torch.cuda.current_stream(self.dev).cuda_stream
@@ -288,14 +291,21 @@ class DeviceFrame:
         else:
             self.object_motion = _ffi.make_object_motion(velocity, angular_velocity)
 
-    def set_disk_layers(self, max_crossings=None, opacity=1.0):
+    def set_disk_layers(self, max_crossings=None, opacity=1.0, phase_rate=0.0):
         """Higher-order images of the disk (bhg_trace_crossings_device, bhg_shade_disk_layers_device):
         trace() carries every ray THROUGH the disk and records its first max_crossings (1 .. 4) crossings, and shade() /
         shade_f32() / render() composite them front to back, each crossing passing 1 - opacity of what lies behind it
         (0 < opacity <= 1; 1 is the opaque disk).  Redshift, the observer and the thermal disk apply per layer.  Not with
         object spheres, their textures or motion, nor shade_stokes() (ValueError there).  None: off -- every path the one
-        it was, bit for bit."""
+        it was, bit for bit.
+        phase_rate (d(disk_phase)/dt as the animation turns the disk, radians per unit of coordinate time; DESIGN.md section
+        18): non-zero, trace() also keeps each crossing's light travel time (bhg_travel_time_device: d_t_cross, d_t_end) and
+        the shades draw layer m of a ray at disk_phase - phase_rate * t_cross[m] (bhg_shade_disk_layers_retarded_device).
+        Zero: the calls and the images of the plain layers."""
         self._traced = None      # what the last trace wrote belongs to the other kind of trace
+        if not np.isfinite(float(phase_rate)):
+            raise ValueError("phase_rate must be finite")
+        self.phase_rate = float(phase_rate) if max_crossings is not None else 0.0
         if max_crossings is None:
             self.disk_layers = None
             return
@@ -380,6 +390,17 @@ class DeviceFrame:
                 self.d_cross = torch.empty((K, self.n, 6), dtype=torch.float64, device=self.dev)
                 self.d_n_cross = torch.empty(self.n, dtype=torch.uint8, device=self.dev)
             self._dir_traced, self._traced = False, None
+            if self.phase_rate != 0.0:
+                if self.d_t_cross is None or self.d_t_cross.shape[0] != K:
+                    self.d_t_cross = torch.empty((K, self.n), dtype=torch.float64, device=self.dev)
+                    self.d_t_end = torch.empty(self.n, dtype=torch.float64, device=self.dev)
+                self.ctx.travel_time_device(params, self.n, self.d_k0.data_ptr(), K, self.d_end.data_ptr(), self.d_t_end.data_ptr(),
+                                            d_cross=self.d_cross.data_ptr(), d_n_cross=self.d_n_cross.data_ptr(),
+                                            d_t_cross=self.d_t_cross.data_ptr(), x0_shared=origin, d_flags=self.d_flags.data_ptr(),
+                                            d_n_steps=self.d_steps.data_ptr(), d_n_accepted=self.d_acc.data_ptr(),
+                                            stream=self._stream())
+                self._traced = "layers_t"
+                return
             self.ctx.trace_crossings_device(params, self.n, self.d_k0.data_ptr(), K, self.d_end.data_ptr(), self.d_cross.data_ptr(),
                                             self.d_n_cross.data_ptr(), x0_shared=origin, d_flags=self.d_flags.data_ptr(),
                                             d_n_steps=self.d_steps.data_ptr(), d_n_accepted=self.d_acc.data_ptr(),
@@ -437,7 +458,22 @@ class DeviceFrame:
         the polarisation (shade_stokes only), the thermal disk and the object motion as set, each None when off -- pol = None
         and none of the others is the textured call exactly."""
         form = self._shade_form()
-        if (form == "layers") != (self.disk_layers is not None):
+        if form == "layers_t":      # the layers of a travel-time trace: the crossing times are there
+            if self.disk_layers is None or self.phase_rate == 0.0:
+                raise RuntimeError("set_disk_layers() changed since the last trace: trace() again")
+            if pol is not None:
+                raise ValueError("disk layers have no Stokes images: shade_stokes() is not available with set_disk_layers()")
+            self._layers_check()
+            self.ctx.shade_disk_layers_retarded_device(self.d_end.data_ptr(), self.d_flags.data_ptr(), self.d_cross.data_ptr(),
+                                                       self.d_n_cross.data_ptr(), self.d_t_cross.data_ptr(), self.phase_rate,
+                                                       self.P, self.S, self.scene(), self.disk_layers, params=self._params,
+                                                       rs=self.redshift, obs=self.observer, th=self.disk_thermal,
+                                                       x0_shared=self.origin, d_k0=self.d_k0.data_ptr(), d_rgba=d_rgba,
+                                                       d_rgba_f32=d_rgba_f32,
+                                                       d_scatter=0 if scatter is None else scatter.data_ptr(),
+                                                       stream=self._stream())
+            return
+        if (form == "layers") != (self.disk_layers is not None) or (form == "layers" and self.phase_rate != 0.0):
             raise RuntimeError("set_disk_layers() changed since the last trace: trace() again")
         if form == "layers":
             if pol is not None:

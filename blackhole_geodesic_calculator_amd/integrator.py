@@ -64,7 +64,7 @@ class GeodesicIntegratorSchwarzschild:
 
     # ------------------------------------------------------------------------------------
     def trace(self, k0, x0, max_step=np.inf, curve_end=50.0, r_exit=0.0, disk=None, spheres=None, redshift=None,
-              polarisation=None, disk_thermal=None, disk_crossings=None):
+              polarisation=None, disk_thermal=None, disk_crossings=None, travel_time=False):
         """Batched solve.  k0[N,3] (or [...,3]); x0[3] shared origin or same leading shape as k0.
         r_exit: outward sphere-exit radius (Limited engine's ray_trace, Limited...py:273-278);
         disk=(R_in, R_out): thin disk in z = 0, first crossing inside the annulus ends the ray with
@@ -101,10 +101,19 @@ class GeodesicIntegratorSchwarzschild:
             disk_cross[K, ..., 6]      the first K crossing records in order, position and direction; NaN where a ray has none
         and redshift=, polarisation= and disk_thermal= return their arrays per LAYER -- g[K, ...], evpa[K, ...], ...,
         thermal_rgb[K, ..., 3] -- each the per-ray call on disk_cross[m], NaN where a ray has no layer m.
+        travel_time=True (DP5(4), null rays, no spheres; bhg_travel_time): the dict also has
+            t[...]                     the coordinate time that elapsed along the ray up to ray_end -- the light seen at camera
+                                       time t_c left there at t_c - t; +inf for rays that ended in the hole, NaN for NaN rays.
+                                       With an opaque disk=: the first crossing's time on rays flagged FLAG_HIT_DISK
+            t_cross[K, ...]            with disk_crossings=K: the time of each stored crossing, NaN where a ray has none ("t" is
+                                       then the time to the ray's end)
+        Every other key comes from the call that makes it without travel_time.
         """
+        if travel_time and spheres is not None:
+            raise ValueError("travel_time does not go with object spheres")
         if disk_crossings is not None:
             return self._trace_crossings(k0, x0, max_step, curve_end, r_exit, disk, spheres, redshift, polarisation, disk_thermal,
-                                         int(disk_crossings))
+                                         int(disk_crossings), travel_time)
         k0 = np.asarray(k0, dtype=np.float64)
         lead = k0.shape[:-1]
         k0f = k0.reshape(-1, 3)
@@ -142,9 +151,17 @@ class GeodesicIntegratorSchwarzschild:
             th = _ffi.make_disk_thermal(**disk_thermal)
             t_em, rgb = self._ctx.disk_thermal(k0f, x0f, self.params(max_step, curve_end, r_exit, disk), th, None, flags, end)
             out["t_em"], out["thermal_rgb"] = t_em.reshape(lead), rgb.reshape(lead + (3,))
+        if travel_time:
+            # the times of the same rays carried through the disk: the end's, or -- the opaque disk stopped the ray -- the first crossing's
+            tt = self._ctx.travel_time(k0f, x0f, self.params(max_step, curve_end, r_exit, disk), 1 if disk else 0)
+            t = tt[6]
+            if disk:
+                t = np.where(flags == _ffi.FLAG_HIT_DISK, tt[7][0], t)
+            out["t"] = t.reshape(lead)
         return out
 
-    def _trace_crossings(self, k0, x0, max_step, curve_end, r_exit, disk, spheres, redshift, polarisation, disk_thermal, K):
+    def _trace_crossings(self, k0, x0, max_step, curve_end, r_exit, disk, spheres, redshift, polarisation, disk_thermal, K,
+                         travel_time=False):
         """trace(disk_crossings=K): the crossings trace, then the per-ray calls layer by layer on cross[m] with the flag array
         n_cross > m ? FLAG_HIT_DISK : FLAG_HIT_HORIZON."""
         if spheres is not None:
@@ -159,7 +176,10 @@ class GeodesicIntegratorSchwarzschild:
         x0 = np.asarray(x0, dtype=np.float64)
         x0f = x0 if x0.ndim == 1 else x0.reshape(-1, 3)
         p = self.params(max_step, curve_end, r_exit, disk)
-        end, flags, steps, acc, cross, n_cross = self._ctx.trace_crossings(k0f, x0f, p, K)
+        if travel_time:
+            end, flags, steps, acc, cross, n_cross, t_end, t_cross = self._ctx.travel_time(k0f, x0f, p, K)
+        else:
+            end, flags, steps, acc, cross, n_cross = self._ctx.trace_crossings(k0f, x0f, p, K)
         out = {
             "ray_end": end.reshape(lead + (6,)),
             "ray_blackhole_hit": ((flags & _ffi.FLAG_HIT_HORIZON) != 0).astype(np.uint8).reshape(lead),
@@ -169,6 +189,8 @@ class GeodesicIntegratorSchwarzschild:
             "n_cross": n_cross.reshape(lead),
             "disk_cross": cross.reshape((K,) + lead + (6,)),
         }
+        if travel_time:
+            out["t"], out["t_cross"] = t_end.reshape(lead), t_cross.reshape((K,) + lead)
         extras = {}
         if redshift is not None:
             rs = _ffi.make_redshift(apply=(), disk_sense=redshift.get("disk_sense", 1))

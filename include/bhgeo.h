@@ -66,7 +66,9 @@ extern "C" {
                                   BHG_START_STEPS (bhg_trace_start_device, bhg_start_steps_match, BHG_START_*: the rays' initial
                                   steps kept across calls on unchanged rays);
                                   BHG_DISK_CROSSINGS (bhg_trace_crossings_device, bhg_trace_crossings, bhg_shade_disk_layers_device,
-                                  bhg_disk_layers_size, struct bhg_disk_layers, BHG_MAX_CROSSINGS: higher-order disk images).
+                                  bhg_disk_layers_size, struct bhg_disk_layers, BHG_MAX_CROSSINGS: higher-order disk images);
+                                  BHG_TRAVEL_TIME (bhg_travel_time_device, bhg_travel_time, bhg_shade_disk_layers_retarded_device:
+                                  the coordinate time along each ray, the disk layers at their retarded phase).
                                9: redshift -- bhg_redshift_device / _host, bhg_shade_scene_redshift_device, bhg_frame_set_redshift,
                                   bhg_redshift_size, struct bhg_redshift;
                                   nothing of ABI 8 changed.
@@ -902,6 +904,49 @@ int bhg_shade_disk_layers_device(bhg_context *ctx, const double *d_end, const do
                                  const double *x0_shared, const double *d_k0, double *d_rgba, float *d_rgba_f32,
                                  const int64_t *d_scatter, const bhg_disk_thermal *th, const bhg_disk_layers *layers,
                                  void *stream);
+
+/* --- light travel time (within ABI 10) ---------------------------------------------------------------
+ * The crossings trace with one more quantity per ray: dt >= 0, the Schwarzschild / Boyer-Lindquist coordinate time that elapses
+ * along the ray between its start point and a point on it.  Rays are traced backwards: the light seen at camera time t_c left
+ * that point at t_c - dt.  The integrand depends on position and the ray's constants only,
+ *     Schwarzschild (both forms):  dt/dlambda = E / (1 - r_s / r),  E = sqrt(f0 (|k0|^2 + h0 (n0.k0)^2)) at the start point,
+ *                                  f = 1 - r_s / r, h = r_s / (r - r_s)
+ *     Kerr:  dt/dlambda = [E ((r^2 + a^2)^2 - Delta a^2 sin^2 theta) - 2 M a r L] / (Sigma Delta)
+ * and is integrated with 6-point Gauss-Legendre per accepted step on the step's dense-output position, summed in step order;
+ * the step that holds the terminal event runs to the event's root.  The time of a crossing is the time at the start of its
+ * step plus the same rule up to the crossing's root.
+ *   - d_t_end [n] fp64: the time to the ray's end state.  +inf for rays flagged BHG_FLAG_HIT_HORIZON or BHG_FLAG_START_INSIDE
+ *     and for rays one of whose nodes lay at r <= the horizon radius (a ray that stepped across the hole at loose tolerances:
+ *     its time is as unphysical as its path, and the node test does not catch every such ray); NaN for rays flagged
+ *     BHG_FLAG_NAN; the time up to the returned state for BHG_FLAG_MAX_STEPS / BHG_FLAG_STEP_TOO_SMALL.
+ *   - d_t_cross [max_crossings][n] fp64 beside d_cross: the time of each stored crossing; +inf after such a node, finite in
+ *     front of a horizon ending.  Slots a ray never reached are left as they were, like d_cross's.
+ *   - everything else -- the steps, d_end, d_flags, d_n_steps, d_n_accepted, d_cross, d_n_cross -- is the crossings trace's on the
+ *     same input, bit for bit.
+ * max_crossings = 0 is allowed (d_cross, d_t_cross and d_n_cross may then be NULL), and so is disk_r_out = 0 with it: the
+ * times to the end only, d_end / d_flags / d_n_steps / d_n_accepted those of bhg_trace_device bit for bit (a lone exit-sphere
+ * event is then settled as the trace kernels settle it; d_t_end is the same with or without a disk).  Refused (BHG_E_INVALID), before the context: BHG_METHOD_RK4,
+ * time_like = 1, max_crossings outside [0, BHG_MAX_CROSSINGS], max_crossings > 0 with disk_r_out = 0, a NULL t_end. */
+#define BHG_TRAVEL_TIME 1
+int bhg_travel_time_device(bhg_context *ctx, const bhg_params *p, const double *x0_shared, const double *d_x0,
+                           const double *d_k0, size_t n, int32_t max_crossings, double *d_end, uint8_t *d_flags,
+                           uint32_t *d_n_steps, uint32_t *d_n_accepted, double *d_cross, uint8_t *d_n_cross, double *d_t_end,
+                           double *d_t_cross, void *stream);
+/* bhg_travel_time_device on host arrays, as bhg_trace_crossings.  Blocking.  cross and t_cross are read first. */
+int bhg_travel_time(bhg_context *ctx, const bhg_params *p, const double *x0, int x0_is_shared, const double *k0, size_t n,
+                    int32_t max_crossings, double *end, uint8_t *flags, uint32_t *n_steps, uint32_t *n_accepted, double *cross,
+                    uint8_t *n_cross, double *t_end, double *t_cross);
+/* bhg_shade_disk_layers_device with each layer drawn at the phase the disk had when the light left it: layer m of ray i is
+ * coloured with disk_phase - phase_rate * t_cross[m][i], phase_rate = d(disk_phase)/dt as the caller animates it (radians per
+ * unit of coordinate time), d_t_cross [max_crossings][S * n_pixels] from bhg_travel_time_device.  A layer whose time is not
+ * finite contributes black and still absorbs.  The thermal disk (th given) has no texture to turn: the times change nothing.
+ * phase_rate = 0 or d_t_cross = NULL is bhg_shade_disk_layers_device, kernel for kernel. */
+int bhg_shade_disk_layers_retarded_device(bhg_context *ctx, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
+                                          const double *d_cross, const uint8_t *d_n_cross, size_t n_pixels, int32_t samples,
+                                          const bhg_scene *scene, const bhg_params *p, const bhg_redshift *rs,
+                                          const bhg_observer *obs, const double *x0_shared, const double *d_k0, double *d_rgba,
+                                          float *d_rgba_f32, const int64_t *d_scatter, const bhg_disk_thermal *th,
+                                          const bhg_disk_layers *layers, const double *d_t_cross, double phase_rate, void *stream);
 
 /* Acceleration probe: acc[n][3] = -Gamma^i_{mu nu} k^mu k^nu at (x[n][3], k[n][3]); host buffers.
  * Lets tests compare the device RHS with the oracle's term by term.  With rhs_form = BHG_RHS_KERR_BL the triples
