@@ -68,7 +68,10 @@ EXPORTS = (
     "bhg_prefix_deep_attempts",
     "bhg_trace_crossings_device", "bhg_trace_crossings", "bhg_disk_layers_size", "bhg_shade_disk_layers_device",
     "bhg_travel_time_device", "bhg_travel_time", "bhg_shade_disk_layers_retarded_device",
+    "bhg_mesh_create", "bhg_mesh_destroy", "bhg_mesh_info", "bhg_mesh_bvh_host", "bhg_trace_mesh_device", "bhg_trace_mesh",
+    "bhg_shade_mesh_device",
 )
+MESH_MAX_SUBSTEPS = 1024   # BHG_MESH_MAX_SUBSTEPS: sub-chords per accepted step at most (BHG_MESH)
 MAX_CROSSINGS = 4   # BHG_MAX_CROSSINGS: disk crossings a crossings trace stores per ray (BHG_DISK_CROSSINGS)
 START_NONE, START_RECORD, START_REPLAY = 0, 1, 2   # BHG_START_*: the rays' initial steps kept across calls (BHG_START_STEPS)
 # BHG_PREFIX_*: the rays' start-up records kept across calls (BHG_START_PREFIX)
@@ -636,6 +639,26 @@ def load():
                                                         C.POINTER(Redshift), C.POINTER(Observer), _dp, C.c_void_p, C.c_void_p,
                                                         C.c_void_p, C.c_void_p, C.POINTER(DiskThermal), C.POINTER(DiskLayers),
                                                         C.c_void_p, C.c_double, C.c_void_p]
+    L.bhg_mesh_create.restype = C.c_int
+    L.bhg_mesh_create.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32,
+                                  C.POINTER(C.c_void_p)]
+    L.bhg_mesh_destroy.restype = None
+    L.bhg_mesh_destroy.argtypes = [C.c_void_p]
+    L.bhg_mesh_info.restype = C.c_int
+    L.bhg_mesh_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _dp]
+    L.bhg_mesh_bvh_host.restype = C.c_int
+    L.bhg_mesh_bvh_host.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.bhg_trace_mesh_device.restype = C.c_int
+    L.bhg_trace_mesh_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_double, _dp, C.c_void_p, C.c_void_p,
+                                        C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]
+    L.bhg_trace_mesh.restype = C.c_int
+    L.bhg_trace_mesh.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bhg_shade_mesh_device.restype = C.c_int
+    L.bhg_shade_mesh_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32,
+                                        C.POINTER(Scene), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if L.bhg_version() != ABI_VERSION or not hasattr(L, "bhg_abi_check"):
         raise ImportError(f"libbhgeo ABI {L.bhg_version()} != expected {ABI_VERSION}: rebuild {LIB_PATH}")
     for name in ("bhg_params_size", "bhg_camera_size", "bhg_scene_size", "bhg_frame_scene_size"):
@@ -669,6 +692,75 @@ def load():
                           f"{C.sizeof(ObjectTextures)}")
     _lib = L
     return L
+
+
+def _mesh_arrays(vertices, triangles):
+    V = np.ascontiguousarray(vertices, dtype=np.float64)
+    F = np.asarray(triangles)
+    if V.ndim != 2 or V.shape[1] != 3:
+        raise ValueError("vertices must have shape [nv, 3]")
+    if F.ndim != 2 or F.shape[1] != 3:
+        raise ValueError("triangles must have shape [nt, 3]")
+    if F.size and (F.min() < -2**31 or F.max() > 2**31 - 1):
+        raise ValueError("triangle indices must fit int32")
+    return V, np.ascontiguousarray(F, dtype=np.int32)
+
+
+def mesh_bvh_host(vertices, triangles, leaf_size=4):
+    """bhg_mesh_bvh_host: the flattened tree as the device gets it, built on the host (no context, no GPU) ->
+    dict(box[nn,6], skip[nn], first[nn], count[nn], order[nt]).  On a box miss at node i go to skip[i], otherwise to i + 1; a leaf
+    holds the triangles order[first : first + count]."""
+    V, F = _mesh_arrays(vertices, triangles)
+    nt = F.shape[0]
+    cap = max(2 * nt - 1, 1)
+    box = np.empty((cap, 6), np.float64)
+    skip, first, count = (np.empty(cap, np.int32) for _ in range(3))
+    order = np.empty(nt, np.int32)
+    nn = C.c_size_t(0)
+    _check(load().bhg_mesh_bvh_host(_addr(V), V.shape[0], _addr(F), nt, int(leaf_size), _addr(box), _addr(skip), _addr(first),
+                                    _addr(count), _addr(order), cap, C.byref(nn)))
+    n = nn.value
+    return {"box": box[:n].copy(), "skip": skip[:n].copy(), "first": first[:n].copy(), "count": count[:n].copy(), "order": order}
+
+
+class Mesh:
+    """bhg_mesh: a triangle mesh on a context's device.  vertices [nv, 3] float64, Cartesian and centred on
+    the hole; triangles [nt, 3] int32; vertex_normals [nv, 3] or None (flat shading).  Closes with its context."""
+
+    def __init__(self, ctx: "Context", vertices, triangles, vertex_normals=None, leaf_size=4):
+        V, F = _mesh_arrays(vertices, triangles)
+        N = None
+        if vertex_normals is not None:
+            N = np.ascontiguousarray(vertex_normals, dtype=np.float64)
+            if N.shape != V.shape:
+                raise ValueError("vertex_normals must have the shape of vertices")
+        h = C.c_void_p()
+        _check(load().bhg_mesh_create(ctx._h, _addr(V), V.shape[0], _addr(F), F.shape[0], None if N is None else _addr(N),
+                                      int(leaf_size), C.byref(h)))
+        self._h = h
+        self.ctx = ctx
+        self.n_vertices, self.n_triangles = V.shape[0], F.shape[0]
+        self.has_normals = N is not None
+        ctx._meshes.append(self)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load().bhg_mesh_destroy(self._h)
+            self._h = None
+            if self in self.ctx._meshes:
+                self.ctx._meshes.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """(n_nodes, depth, box[6]) of the tree"""
+        nn, depth, box = C.c_int64(0), C.c_int32(0), (C.c_double * 6)()
+        _check(load().bhg_mesh_info(self._h, C.byref(nn), C.byref(depth), box))
+        return nn.value, depth.value, np.array(box[:])
 
 
 def start_steps_match(a: "Params", b: "Params") -> bool:
@@ -1055,9 +1147,12 @@ class Context:
         self._h = h
         self.device = int(device)
         self.pinned = PinnedPool(ctx=self)
+        self._meshes = []
 
     def close(self):
         if getattr(self, "_h", None):
+            for m in list(getattr(self, "_meshes", ())):
+                m.close()
             self.pinned.close()
             load().bhg_destroy(self._h)
             self._h = None
@@ -1206,6 +1301,48 @@ class Context:
                                       int(max_crossings), _addr(end), _addr(flags), _addr(steps), _addr(acc),
                                       _addr(cross) if K else None, _addr(n_cross), _addr(t_end), _addr(t_cross) if K else None))
         return end, flags, steps, acc, cross, n_cross, t_end, t_cross
+
+    def trace_mesh(self, k0, x0, params: Params, mesh: "Mesh", max_chord):
+        """bhg_trace_mesh: the trace with a triangle mesh as one more terminal event.  k0[N,3], x0[3] or
+        [N,3] -> (end[N,6], flags[N], n_steps[N], n_accepted[N], tri_id[N] int32 the triangle a ray ends on or -1, bary[N,2] the
+        plane coordinates (u, v) of the hit in it, NaN for a ray that hits nothing)."""
+        k0 = np.ascontiguousarray(k0, dtype=np.float64)
+        if k0.ndim != 2 or k0.shape[1] != 3:
+            raise ValueError("k0 must have shape [N, 3]")
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        n = k0.shape[0]
+        if x0.shape != (3,) and x0.shape != (n, 3):
+            raise ValueError("x0 must have shape [3] or [N, 3]")
+        end = np.empty((n, 6), np.float64)
+        flags = np.empty(n, np.uint8)
+        steps = np.empty(n, np.uint32)
+        acc = np.empty(n, np.uint32)
+        tri_id = np.full(n, -1, np.int32)
+        bary = np.full((n, 2), np.nan, np.float64)
+        _check(load().bhg_trace_mesh(self._h, C.byref(params), None if mesh is None else mesh._h, float(max_chord), _addr(x0),
+                                     1 if x0.ndim == 1 else 0, _addr(k0), n, _addr(end), _addr(flags), _addr(steps), _addr(acc),
+                                     _addr(tri_id), _addr(bary)))
+        return end, flags, steps, acc, tri_id, bary
+
+    def trace_mesh_device(self, params: Params, mesh: "Mesh", max_chord, n, d_k0, d_end, d_tri_id, d_bary, x0_shared=None, d_x0=0,
+                          d_flags=0, d_n_steps=0, d_n_accepted=0, stream=0):
+        """bhg_trace_mesh_device: d_tri_id [n] int32 and d_bary [n, 2] float64 beside trace_device's outputs."""
+        xs = None if x0_shared is None else (C.c_double * 3)(*[float(v) for v in x0_shared])
+        _check(load().bhg_trace_mesh_device(self._h, C.byref(params), None if mesh is None else mesh._h, float(max_chord), xs,
+                                            C.c_void_p(d_x0 or None), C.c_void_p(d_k0 or None), int(n), C.c_void_p(d_end or None),
+                                            C.c_void_p(d_flags or None), C.c_void_p(d_n_steps or None),
+                                            C.c_void_p(d_n_accepted or None), C.c_void_p(d_tri_id or None),
+                                            C.c_void_p(d_bary or None), C.c_void_p(stream or None)))
+
+    def shade_mesh_device(self, d_end, d_flags, d_tri_id, d_bary, n_pixels, samples, scene: "Scene", mesh: "Mesh", d_tri_rgb=0,
+                          d_rgba=0, d_rgba_f32=0, d_scatter=0, stream=0):
+        """bhg_shade_mesh_device: the shade of a mesh trace -- mesh rays Lambert-lit and shadowed by the mesh, every other ray
+        shade_scene_device's.  d_tri_rgb [nt, 3] float32 or 0 (white)."""
+        _check(load().bhg_shade_mesh_device(self._h, C.c_void_p(d_end or None), C.c_void_p(d_flags or None),
+                                            C.c_void_p(d_tri_id or None), C.c_void_p(d_bary or None), int(n_pixels), int(samples),
+                                            C.byref(scene), None if mesh is None else mesh._h, C.c_void_p(d_tri_rgb or None),
+                                            C.c_void_p(d_rgba or None), C.c_void_p(d_rgba_f32 or None),
+                                            C.c_void_p(d_scatter or None), C.c_void_p(stream or None)))
 
     def trajectory(self, k0, x0, params: Params, n_points, spheres=None):
         """Sampled curves: (traj[N,6,T], n_valid[N], end[N,6], flags[N]); with spheres= (object spheres in the curved region,

@@ -24,6 +24,7 @@
 #include "../../include/bhgeo.h"
 #include "geodesic_kernels.h"
 #include "prefix_clearance.h"
+#include "mesh_bvh.h"
 
 static_assert(BHG_FLAG_HIT_HORIZON == bhg::BHG_FLAG_HIT_HORIZON_, "flag mismatch");
 static_assert(BHG_FLAG_START_INSIDE == bhg::BHG_FLAG_START_INSIDE_, "flag mismatch");
@@ -1080,6 +1081,8 @@ struct CrossOut {
     // t_cross may then be null with max_cross = 0
     double *t_end = nullptr;
     double *t_cross = nullptr;
+    // a mesh trace (bhg_trace_mesh_device): the mesh and its two outputs; nothing above is used then
+    const bhg::MeshArgs *mesh = nullptr;
 };
 
 // ONE launch: n <= BHG_MAX_RAYS_PER_LAUNCH rays (the kernels form a ray's byte offsets in 32 bits).
@@ -1227,7 +1230,9 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres,
         a.n_cross = cr->n_cross;
         a.max_cross = cr->max_cross;
         a.cross_stride = cr->stride;
-        if (cr->t_end)
+        if (cr->mesh)
+            HIP_TRY(bhg::launch_trace_mesh(a, *cr->mesh, rhs_id, s));
+        else if (cr->t_end)
             HIP_TRY(bhg::launch_travel_time(a, rhs_id, cr->t_end, cr->t_cross, s));
         else
             HIP_TRY(bhg::launch_trace_crossings(a, rhs_id, s));
@@ -1328,9 +1333,16 @@ int trace_device_impl(bhg_context *c, const bhg_params *p, const double *spheres
         const size_t m = std::min((size_t)bhg::BHG_MAX_RAYS_PER_LAUNCH, n - off);
         // (a crossings trace: this launch's rays sit at offset off inside every layer of the call's record array)
         CrossOut part{};
+        bhg::MeshArgs part_mesh;
         if (cr)
             part = CrossOut{cr->cross ? cr->cross + off * 6 : nullptr, cr->n_cross ? cr->n_cross + off : nullptr, cr->max_cross,
                             cr->stride, cr->t_end ? cr->t_end + off : nullptr, cr->t_cross ? cr->t_cross + off : nullptr};
+        if (cr && cr->mesh) {
+            part_mesh = *cr->mesh;
+            part_mesh.tri_id += off;
+            part_mesh.bary += off * 2;
+            part.mesh = &part_mesh;
+        }
         const int rc = trace_device_one(c, &q, spheres, n_spheres, x0_shared, d_x0 ? d_x0 + off * 3 : nullptr,
                                         d_k0 ? d_k0 + off * 3 : nullptr, m, d_end ? d_end + off * 6 : nullptr,
                                         d_flags ? d_flags + off : nullptr, d_n_steps ? d_n_steps + off : nullptr,
@@ -1569,6 +1581,231 @@ int bhg_travel_time(bhg_context *c, const bhg_params *p, const double *x0, int x
         HIP_TRY(hipMemcpyAsync(t_cross, d + o_tc, btc, hipMemcpyDeviceToHost, s));
     }
     if (want_nc) HIP_TRY(hipMemcpyAsync(n_cross, d + o_nc, n, hipMemcpyDeviceToHost, s));
+    if (flags) HIP_TRY(hipMemcpyAsync(flags, d + o_flags, n, hipMemcpyDeviceToHost, s));
+    if (n_steps) HIP_TRY(hipMemcpyAsync(n_steps, d + o_steps, bu, hipMemcpyDeviceToHost, s));
+    if (n_accepted) HIP_TRY(hipMemcpyAsync(n_accepted, d + o_acc, bu, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return BHG_OK;
+}
+
+// --- triangle meshes ---------------------------------------------------------------------------------
+
+}  // extern "C"
+
+// a mesh on one device: the flattened tree of mesh_bvh.h, the triangles in leaf order, the maps between the two numberings
+struct bhg_mesh {
+    int device = 0;
+    char *d = nullptr;        // one allocation
+    bhg::MeshView view{};
+    int64_t n_nodes = 0;
+    int32_t depth = 0;
+    double box[6] = {0, 0, 0, 0, 0, 0};
+    double d_min = 0.0, d_max = 0.0;
+};
+
+namespace {
+
+// what the mesh trace covers, checked before the context (a refusal names its figure with or without a device)
+int mesh_trace_check(const bhg_params *p, const bhg_mesh *mesh, double max_chord, const int32_t *tri_id, const double *bary)
+{
+    int rc = validate(p);
+    if (rc != BHG_OK) return rc;
+    if (p->method != BHG_METHOD_DP54) return fail(BHG_E_INVALID, "the mesh trace is DP5(4) only: method must be BHG_METHOD_DP54");
+    if (p->time_like) return fail(BHG_E_INVALID, "the mesh trace covers null rays only: time_like must be 0");
+    if (!mesh) return fail(BHG_E_INVALID, "mesh is NULL");
+    if (!std::isfinite(max_chord) || !(max_chord > 0.0)) return fail(BHG_E_INVALID, "max_chord must be finite and > 0");
+    if (!tri_id || !bary) return fail(BHG_E_INVALID, "tri_id / bary is NULL");
+    return BHG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bhg_mesh_bvh_host(const double *vertices, size_t n_vertices, const int32_t *triangles, size_t n_triangles, int32_t leaf_size,
+                      double *node_box, int32_t *node_skip, int32_t *node_first, int32_t *node_count, int32_t *tri_order, size_t cap,
+                      size_t *n_nodes)
+{
+    if (const char *why = bhg::mesh_refusal(vertices, n_vertices, triangles, n_triangles, leaf_size)) return fail(BHG_E_INVALID, why);
+    if (!n_nodes) return fail(BHG_E_INVALID, "n_nodes is NULL");
+    bhg::HostBvh t;
+    bhg::build_bvh(vertices, triangles, n_triangles, leaf_size, t);
+    const size_t nn = t.node_skip.size();
+    *n_nodes = nn;
+    if (nn > cap) return fail(BHG_E_INVALID, "the tree has more nodes than cap (2 * n_triangles - 1 always suffices)");
+    if (!node_box || !node_skip || !node_first || !node_count || !tri_order) return fail(BHG_E_INVALID, "an output array is NULL");
+    std::memcpy(node_box, t.node_box.data(), nn * 6 * sizeof(double));
+    std::memcpy(node_skip, t.node_skip.data(), nn * sizeof(int32_t));
+    std::memcpy(node_first, t.node_first.data(), nn * sizeof(int32_t));
+    std::memcpy(node_count, t.node_count.data(), nn * sizeof(int32_t));
+    std::memcpy(tri_order, t.tri_order.data(), n_triangles * sizeof(int32_t));
+    return BHG_OK;
+}
+
+int bhg_mesh_create(bhg_context *c, const double *vertices, size_t n_vertices, const int32_t *triangles, size_t n_triangles,
+                    const double *vertex_normals, int32_t leaf_size, bhg_mesh **out)
+{
+    if (!out) return fail(BHG_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (const char *why = bhg::mesh_refusal(vertices, n_vertices, triangles, n_triangles, leaf_size)) return fail(BHG_E_INVALID, why);
+    if (vertex_normals)
+        for (size_t i = 0; i < n_vertices * 3; i++)
+            if (!std::isfinite(vertex_normals[i])) return fail(BHG_E_INVALID, "mesh: every vertex normal must be finite");
+    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
+    ENTER_DEVICE(c->device);
+    bhg::HostBvh t;
+    bhg::build_bvh(vertices, triangles, n_triangles, leaf_size, t);
+    const size_t nn = t.node_skip.size(), nt = n_triangles;
+    // the device image: boxes | triangles (v0, e1, e2) | vertex normals | skip | first | count | order | slot
+    const size_t b_box = nn * 6 * sizeof(double), b_tri = nt * 9 * sizeof(double), b_nrm = vertex_normals ? b_tri : 0,
+                 b_node = (nn * sizeof(int32_t) + 7) & ~size_t(7), b_idx = (nt * sizeof(int32_t) + 7) & ~size_t(7);
+    const size_t o_tri = b_box, o_nrm = o_tri + b_tri, o_skip = o_nrm + b_nrm, o_first = o_skip + b_node, o_count = o_first + b_node,
+                 o_order = o_count + b_node, o_slot = o_order + b_idx, total = o_slot + b_idx;
+    std::vector<char> img(total, 0);
+    std::memcpy(img.data(), t.node_box.data(), b_box);
+    double *tri = (double *)(img.data() + o_tri), *nrm = (double *)(img.data() + o_nrm);
+    int32_t *slot_of = (int32_t *)(img.data() + o_slot);
+    double d_max = 0.0;
+    for (size_t k = 0; k < nt; k++) {
+        const int32_t f = t.tri_order[k];
+        slot_of[f] = (int32_t)k;
+        const double *v0 = vertices + (size_t)triangles[(size_t)f * 3] * 3, *v1 = vertices + (size_t)triangles[(size_t)f * 3 + 1] * 3,
+                     *v2 = vertices + (size_t)triangles[(size_t)f * 3 + 2] * 3;
+        for (int q = 0; q < 3; q++) {
+            tri[k * 9 + q] = v0[q];
+            tri[k * 9 + 3 + q] = v1[q] - v0[q];
+            tri[k * 9 + 6 + q] = v2[q] - v0[q];
+        }
+        for (const double *v : {v0, v1, v2}) d_max = std::max(d_max, std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]));
+        if (vertex_normals)
+            for (int j = 0; j < 3; j++)
+                for (int q = 0; q < 3; q++) nrm[k * 9 + j * 3 + q] = vertex_normals[(size_t)triangles[(size_t)f * 3 + j] * 3 + q];
+    }
+    std::memcpy(img.data() + o_skip, t.node_skip.data(), nn * sizeof(int32_t));
+    std::memcpy(img.data() + o_first, t.node_first.data(), nn * sizeof(int32_t));
+    std::memcpy(img.data() + o_count, t.node_count.data(), nn * sizeof(int32_t));
+    std::memcpy(img.data() + o_order, t.tri_order.data(), nt * sizeof(int32_t));
+    bhg_mesh *m = new (std::nothrow) bhg_mesh;
+    if (!m) return fail(BHG_E_NOMEM, "out of host memory");
+    hipError_t e = hipMalloc((void **)&m->d, total);
+    if (e == hipSuccess) e = hipMemcpy(m->d, img.data(), total, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (m->d) (void)hipFree(m->d);
+        delete m;
+        return fail_hip(e, "bhg_mesh_create: device image");
+    }
+    m->device = c->device;
+    m->n_nodes = (int64_t)nn;
+    m->depth = t.depth;
+    std::memcpy(m->box, t.node_box.data(), sizeof(m->box));
+    // every point of the mesh lies inside the root box and no farther from the origin than the farthest vertex
+    double d2 = 0.0;
+    for (int q = 0; q < 3; q++) {
+        const double gap = std::max(std::max(m->box[q], -m->box[3 + q]), 0.0);
+        d2 += gap * gap;
+    }
+    m->d_min = std::sqrt(d2) * (1.0 - 1e-14);
+    m->d_max = d_max * (1.0 + 1e-14);
+    bhg::MeshView &v = m->view;
+    v.node_box = (const double *)m->d;
+    v.tri = (const double *)(m->d + o_tri);
+    v.tri_normals = vertex_normals ? (const double *)(m->d + o_nrm) : nullptr;
+    v.node_skip = (const int32_t *)(m->d + o_skip);
+    v.node_first = (const int32_t *)(m->d + o_first);
+    v.node_count = (const int32_t *)(m->d + o_count);
+    v.tri_order = (const int32_t *)(m->d + o_order);
+    v.tri_slot = (const int32_t *)(m->d + o_slot);
+    v.n_nodes = (int32_t)nn;
+    v.n_tris = (int32_t)nt;
+    *out = m;
+    return BHG_OK;
+}
+
+void bhg_mesh_destroy(bhg_mesh *m)
+{
+    if (!m) return;
+    {
+        DeviceGuard g(m->device);
+        if (m->d) (void)hipFree(m->d);
+    }
+    delete m;
+}
+
+int bhg_mesh_info(const bhg_mesh *m, int64_t *n_nodes, int32_t *depth, double box[6])
+{
+    if (!m) return fail(BHG_E_INVALID, "mesh is NULL");
+    if (n_nodes) *n_nodes = m->n_nodes;
+    if (depth) *depth = m->depth;
+    if (box) std::memcpy(box, m->box, sizeof(m->box));
+    return BHG_OK;
+}
+
+int bhg_trace_mesh_device(bhg_context *c, const bhg_params *p, const bhg_mesh *mesh, double max_chord, const double *x0_shared,
+                          const double *d_x0, const double *d_k0, size_t n, double *d_end, uint8_t *d_flags, uint32_t *d_n_steps,
+                          uint32_t *d_n_accepted, int32_t *d_tri_id, double *d_bary, void *stream)
+{
+    int rc = mesh_trace_check(p, mesh, max_chord, d_tri_id, d_bary);
+    if (rc != BHG_OK) return rc;
+    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
+    if (mesh->device != c->device) return fail(BHG_E_INVALID, "the mesh lives on another device than the context");
+    if (n && !d_end) return fail(BHG_E_INVALID, "end is NULL");
+    bhg::MeshArgs g;
+    std::memset(&g, 0, sizeof(g));
+    g.mesh = mesh->view;
+    std::memcpy(g.box, mesh->box, sizeof(g.box));
+    g.d_min = mesh->d_min;
+    g.d_max = mesh->d_max;
+    g.max_chord = max_chord;
+    // BHGEO_MESH_CULL=0: every step of every ray samples its sub-chords (an A/B aid: the results are the same bits)
+    const char *cull = std::getenv("BHGEO_MESH_CULL");
+    g.cull = !(cull && cull[0] == '0' && cull[1] == 0);
+    g.tri_id = d_tri_id;
+    g.bary = d_bary;
+    CrossOut cr{nullptr, nullptr, 0, n};
+    cr.mesh = &g;
+    return trace_device_impl(c, p, nullptr, 0, x0_shared, d_x0, d_k0, n, d_end, d_flags, d_n_steps, d_n_accepted, nullptr, stream,
+                             nullptr, nullptr, BHG_START_NONE, &cr);
+}
+
+// the host-buffer call, as bhg_trace_crossings: upload, one device call, download.  bary is read first (a ray that hits nothing
+// leaves its slot as it was).  Blocking.
+int bhg_trace_mesh(bhg_context *c, const bhg_params *p, const bhg_mesh *mesh, double max_chord, const double *x0, int x0_is_shared,
+                   const double *k0, size_t n, double *end, uint8_t *flags, uint32_t *n_steps, uint32_t *n_accepted, int32_t *tri_id,
+                   double *bary)
+{
+    int rc = mesh_trace_check(p, mesh, max_chord, tri_id, bary);
+    if (rc != BHG_OK) return rc;
+    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
+    if (mesh->device != c->device) return fail(BHG_E_INVALID, "the mesh lives on another device than the context");
+    if (n == 0) return BHG_OK;
+    if (!x0 || !k0 || !end) return fail(BHG_E_INVALID, "x0 / k0 / end is NULL");
+    if (n > 0xFFFFFFFFull) return fail(BHG_E_INVALID, "n must be < 2^32 per call");
+    ENTER_DEVICE(c->device);
+    const size_t b3 = n * 3 * sizeof(double), b6 = 2 * b3, bb = n * 2 * sizeof(double), bu = n * sizeof(uint32_t);
+    const size_t o_x0 = b3, o_end = o_x0 + (x0_is_shared ? 0 : b3), o_bary = o_end + b6, o_steps = o_bary + bb, o_acc = o_steps + bu,
+                 o_tri = o_acc + bu, o_flags = o_tri + bu;
+    char *d = nullptr;
+    HIP_TRY(hipMalloc((void **)&d, o_flags + n));
+    struct Free {
+        char *d;
+        hipStream_t s;
+        ~Free()
+        {
+            (void)hipStreamSynchronize(s);
+            (void)hipFree(d);
+        }
+    } guard{d, c->stream};
+    hipStream_t s = c->stream;
+    HIP_TRY(hipMemcpyAsync(d, k0, b3, hipMemcpyHostToDevice, s));
+    if (!x0_is_shared) HIP_TRY(hipMemcpyAsync(d + o_x0, x0, b3, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_bary, bary, bb, hipMemcpyHostToDevice, s));
+    rc = bhg_trace_mesh_device(c, p, mesh, max_chord, x0_is_shared ? x0 : nullptr, x0_is_shared ? nullptr : (const double *)(d + o_x0),
+                               (const double *)d, n, (double *)(d + o_end), (uint8_t *)(d + o_flags), (uint32_t *)(d + o_steps),
+                               (uint32_t *)(d + o_acc), (int32_t *)(d + o_tri), (double *)(d + o_bary), s);
+    if (rc != BHG_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(end, d + o_end, b6, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(tri_id, d + o_tri, bu, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(bary, d + o_bary, bb, hipMemcpyDeviceToHost, s));
     if (flags) HIP_TRY(hipMemcpyAsync(flags, d + o_flags, n, hipMemcpyDeviceToHost, s));
     if (n_steps) HIP_TRY(hipMemcpyAsync(n_steps, d + o_steps, bu, hipMemcpyDeviceToHost, s));
     if (n_accepted) HIP_TRY(hipMemcpyAsync(n_accepted, d + o_acc, bu, hipMemcpyDeviceToHost, s));
@@ -2182,6 +2419,56 @@ int bhg_shade_scene_device(bhg_context *c, const double *d_end, const uint8_t *d
 {
     return shade(c, d_end, nullptr, d_flags, d_object_id, n_pixels, samples, sc, nullptr, nullptr, nullptr, nullptr, nullptr,
                  nullptr, d_rgba, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+// the mesh shade: the plain scene shade's checks, then shade_mesh_kernel.  Its own call: shade() above stays
+// what it is
+int bhg_shade_mesh_device(bhg_context *c, const double *d_end, const uint8_t *d_flags, const int32_t *d_tri_id, const double *d_bary,
+                          size_t n_pixels, int32_t samples, const bhg_scene *sc, const bhg_mesh *mesh, const float *d_tri_rgb,
+                          double *d_rgba, float *d_rgba_f32, const int64_t *d_scatter, void *stream)
+{
+    if (!sc) return fail(BHG_E_INVALID, "scene is NULL");
+    if (samples <= 0 || sc->sky_w <= 0 || sc->sky_h <= 0) return fail(BHG_E_INVALID, "samples, sky_w, sky_h must be > 0");
+    if (sc->n_spheres != 0) return fail(BHG_E_INVALID, "the mesh shade does not go with object spheres: n_spheres must be 0");
+    if (sc->n_lamps < 0 || sc->n_lamps > 4) return fail(BHG_E_INVALID, "n_lamps must be in [0, 4]");
+    const bool has_disk = sc->disk_r_out > 0.0;
+    if (has_disk) {
+        if (!(sc->disk_r_out > sc->disk_r_in) || !(sc->disk_stddev > 0.0))
+            return fail(BHG_E_INVALID, "disk needs r_out > r_in and stddev > 0");
+        if (sc->d_disk_tex && (sc->disk_w <= 0 || sc->disk_h <= 0)) return fail(BHG_E_INVALID, "disk texture size must be > 0");
+    }
+    if (!mesh) return fail(BHG_E_INVALID, "mesh is NULL");
+    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
+    if (mesh->device != c->device) return fail(BHG_E_INVALID, "the mesh lives on another device than the context");
+    if (n_pixels == 0) return BHG_OK;
+    if ((!d_rgba && !d_rgba_f32) || !d_end || !d_flags || !sc->d_sky || !d_tri_id || !d_bary)
+        return fail(BHG_E_INVALID, "NULL device pointer");
+    ENTER_DEVICE(c->device);
+    bhg::ShadeArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.end = d_end;
+    a.flags = d_flags;
+    a.sky = sc->d_sky;
+    a.rgba = d_rgba;
+    a.rgba_f32 = d_rgba_f32;
+    a.scatter = d_scatter;
+    a.n_pixels = n_pixels;
+    a.samples = samples;
+    a.sky_w = sc->sky_w;
+    a.sky_h = sc->sky_h;
+    a.disk_tex = sc->d_disk_tex;
+    a.disk_w = sc->disk_w;
+    a.disk_h = sc->disk_h;
+    a.disk_r_in = sc->disk_r_in;
+    a.disk_r_out = sc->disk_r_out;
+    a.disk_phase = sc->disk_phase;
+    a.disk_mean = sc->disk_mean;
+    a.disk_stddev = sc->disk_stddev;
+    a.disk_intensity = sc->disk_intensity;
+    a.n_lamps = sc->n_lamps;
+    std::memcpy(a.lamps, sc->lamps, sizeof(a.lamps));
+    HIP_TRY(bhg::launch_shade_mesh(a, mesh->view, d_tri_id, d_bary, d_tri_rgb, (hipStream_t)stream));
+    return BHG_OK;
 }
 
 int bhg_shade_scene_f32_device(bhg_context *c, const double *d_end, const uint8_t *d_flags, const int8_t *d_object_id,

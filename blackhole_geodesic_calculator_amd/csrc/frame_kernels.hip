@@ -1301,4 +1301,124 @@ hipError_t launch_shade_layers(const ShadeArgs &a, hipStream_t s, const double *
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------
+// The mesh shade (bhg_shade_mesh_device).  A ray that the mesh trace ended on triangle T at x (end record,
+// tri_id, bary) gets tri_rgb[T] times object_colour's Lambert lamp sum -- I^2 n.l / d^2, n.l clamped at 0 -- with
+//   n   the triangle's unit normal e1 x e2 / |e1 x e2|, or -- vertex normals given -- the normalised (1 - u - v) N0 + u N1 + v N2,
+//       turned to face the incoming ray (n . end_dir < 0);
+//   a lamp shadowed when the straight segment from x + 1e-5 l^ to the lamp meets any triangle (segment_first_hit in its any-hit
+//   form; 1e-5 is object_colour's epsilon).
+// Every other ray is the plain shade's ray_colour, bit for bit.  shade_reduce_kernel's shape and its serial twin.
+// ------------------------------------------------------------------------------------------
+struct MeshShade {
+    MeshView mesh;
+    const int32_t *tri_id;   // [S*n_pixels]
+    const double *bary;      // [S*n_pixels][2]
+    const float *tri_rgb;    // [nt][3] in the caller's numbering, or nullptr (white)
+};
+
+__device__ __forceinline__ void mesh_colour(const ShadeArgs &A, const MeshShade &G, uint64_t i, int32_t tri, double rgb[3])
+{
+    const double *e = A.end + i * 6;
+    const int32_t slot = G.mesh.tri_slot[tri];
+    const double *T = G.mesh.tri + (size_t)slot * 9;
+    double n[3];
+    if (G.mesh.tri_normals) {
+        const double *N = G.mesh.tri_normals + (size_t)slot * 9;
+        const double u = G.bary[i * 2], v = G.bary[i * 2 + 1], w = 1.0 - u - v;
+        for (int c = 0; c < 3; c++) n[c] = w * N[c] + u * N[3 + c] + v * N[6 + c];
+    } else {
+        n[0] = T[4] * T[8] - T[5] * T[7];
+        n[1] = T[5] * T[6] - T[3] * T[8];
+        n[2] = T[3] * T[7] - T[4] * T[6];
+    }
+    const double len = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    const double sgn = (n[0] * e[3] + n[1] * e[4] + n[2] * e[5]) > 0.0 ? -1.0 : 1.0;
+    for (int c = 0; c < 3; c++) n[c] = sgn * (n[c] / len);
+    double sum = 0.0;
+    for (int l = 0; l < A.n_lamps; l++) {
+        const double lv[3] = {A.lamps[l][0] - e[0], A.lamps[l][1] - e[1], A.lamps[l][2] - e[2]};
+        const double d2 = lv[0] * lv[0] + lv[1] * lv[1] + lv[2] * lv[2];
+        const double dist = sqrt(d2);
+        const double ld[3] = {lv[0] / dist, lv[1] / dist, lv[2] / dist};
+        const double ndl = n[0] * ld[0] + n[1] * ld[1] + n[2] * ld[2];
+        if (!(ndl > 0.0)) continue;
+        const double from[3] = {e[0] + 1e-5 * ld[0], e[1] + 1e-5 * ld[1], e[2] + 1e-5 * ld[2]};
+        const double to[3] = {A.lamps[l][0], A.lamps[l][1], A.lamps[l][2]};
+        double s_hit;
+        if (segment_first_hit<true>(G.mesh, from, to, s_hit) >= 0) continue;
+        sum += A.lamps[l][3] * A.lamps[l][3] * ndl / d2;
+    }
+    for (int c = 0; c < 3; c++) rgb[c] = (G.tri_rgb ? (double)G.tri_rgb[(size_t)tri * 3 + c] : 1.0) * sum;
+}
+
+__device__ __forceinline__ void mesh_ray_colour(const ShadeArgs &A, const MeshShade &G, uint64_t i, double rgb[3])
+{
+    const uint8_t fl = A.flags[i];
+    const int32_t tri = G.tri_id[i];
+    if (fl == BHG_FLAG_HIT_OBJECT_ && tri >= 0 && tri < G.mesh.n_tris) {
+        mesh_colour(A, G, i, tri, rgb);
+        return;
+    }
+    const double *d = A.end + i * 6 + 3;
+    ray_colour<false, false, false, false, false, false>(A, i, fl, d[0], d[1], d[2], rgb, nullptr);
+}
+
+__global__ void __launch_bounds__(256) shade_mesh_kernel(const ShadeArgs A, const MeshShade G, const uint32_t ppb)
+{
+    __shared__ double col[256 * 3];
+    const uint32_t t = threadIdx.x, S = (uint32_t)A.samples;
+    const uint32_t s = t / ppb, q = t - s * ppb;
+    const uint64_t p = (uint64_t)blockIdx.x * ppb + q;
+    const bool live = s < S && p < A.n_pixels;
+    if (live) {
+        double rgb[3];
+        mesh_ray_colour(A, G, (uint64_t)s * A.n_pixels + p, rgb);
+        col[t * 3 + 0] = rgb[0];
+        col[t * 3 + 1] = rgb[1];
+        col[t * 3 + 2] = rgb[2];
+    }
+    __syncthreads();
+    if (s == 0 && live) {
+        double acc[3] = {0.0, 0.0, 0.0};
+        for (uint32_t k = 0; k < S; k++) {
+            const double *c = col + (size_t)(k * ppb + q) * 3;
+            acc[0] += c[0];
+            acc[1] += c[1];
+            acc[2] += c[2];
+        }
+        write_pixel(A, p, acc);
+    }
+}
+
+// more samples than a workgroup has threads: one thread per pixel, in sample order
+__global__ void __launch_bounds__(256) shade_mesh_serial_kernel(const ShadeArgs A, const MeshShade G)
+{
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= A.n_pixels) return;
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int s = 0; s < A.samples; s++) {
+        double rgb[3];
+        mesh_ray_colour(A, G, (uint64_t)s * A.n_pixels + p, rgb);
+        acc[0] += rgb[0];
+        acc[1] += rgb[1];
+        acc[2] += rgb[2];
+    }
+    write_pixel(A, p, acc);
+}
+
+hipError_t launch_shade_mesh(const ShadeArgs &a, const MeshView &m, const int32_t *tri_id, const double *bary, const float *tri_rgb,
+                             hipStream_t s)
+{
+    if (a.n_pixels == 0) return hipSuccess;
+    const MeshShade g{m, tri_id, bary, tri_rgb};
+    if (a.samples > 256) {
+        BHG_LAUNCH(shade_mesh_serial_kernel, dim3((unsigned)((a.n_pixels + 255) / 256)), dim3(256), 0, s, a, g);
+        return hipGetLastError();
+    }
+    const uint32_t ppb = 256u / (uint32_t)a.samples;
+    BHG_LAUNCH(shade_mesh_kernel, dim3((unsigned)((a.n_pixels + ppb - 1) / ppb)), dim3(256), 0, s, a, g, ppb);
+    return hipGetLastError();
+}
+
 }  // namespace bhg

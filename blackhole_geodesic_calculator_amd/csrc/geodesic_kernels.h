@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mesh_traverse.h"
+
 // Every launcher returns hipGetLastError() as THIS launch's status.  That call reports -- and clears -- the last error any
 // earlier HIP call of the thread left behind, ours (a refused allocation) or another library's (a probing
 // hipPointerGetAttributes): it is read away before the launch, so that a launch that went through is not reported
@@ -321,6 +323,25 @@ hipError_t launch_trace_crossings_kerr(const TraceArgs &a, hipStream_t s);
 // then be null); the Kerr instance sits in the Kerr translation unit and wants launch_kerr_finalize after it
 hipError_t launch_travel_time(const TraceArgs &a, int rhs, double *t_end, double *t_cross, hipStream_t s);
 hipError_t launch_travel_time_kerr(const TraceArgs &a, double *t_end, double *t_cross, hipStream_t s);
+// the mesh trace (trace_mesh_kernel): the plain trace's steps with a triangle mesh as one more terminal
+// event.  The mesh and the two outputs ride beside TraceArgs, which stays what it is.  a.disk_r_out > 0: the disk is opaque, as in
+// the trace.  The Kerr instance sits in the Kerr translation unit and wants launch_kerr_finalize after it
+struct MeshArgs {
+    MeshView mesh;
+    double box[6];          // the root box
+    double d_min, d_max;    // every point of the mesh lies at a distance from the origin inside [d_min, d_max] (the Kerr cull)
+    double max_chord;
+    int32_t cull;           // 0: no whole-step cull (BHGEO_MESH_CULL=0)
+    int32_t *tri_id;        // [n]: the caller's triangle of a ray that ends on the mesh, else -1
+    double *bary;           // [n][2]: (u, v) of the refined point; untouched for a ray that hits nothing
+};
+constexpr int BHG_MESH_MAX_SUBSTEPS_ = 1024;
+hipError_t launch_trace_mesh(const TraceArgs &a, const MeshArgs &m, int rhs, hipStream_t s);
+hipError_t launch_trace_mesh_kerr(const TraceArgs &a, const MeshArgs &m, hipStream_t s);
+// the mesh shade (shade_mesh_kernel, frame_kernels.hip): a.end / flags / sky / disk / lamps as launch_shade's plain instance wants
+// them, n_spheres = 0; tri_rgb nullptr = white
+hipError_t launch_shade_mesh(const ShadeArgs &a, const MeshView &m, const int32_t *tri_id, const double *bary, const float *tri_rgb,
+                             hipStream_t s);
 // the recording pass of the start-up records (record_prefix_kernel: one lane per ray; rhs Christoffel or reduced, a.x0 == nullptr):
 // rec [7][a.n] 16-byte planes, rho the radius about a.x0s the recorded steps stay inside.  deep: the record carries on through
 // rejected attempts (BHG_PREFIX_RECORD_DEEP: at most BHG_PREFIX_DEEP_ACCEPTED_ accepted steps in BHG_PREFIX_DEEP_ATTEMPTS_ attempts)

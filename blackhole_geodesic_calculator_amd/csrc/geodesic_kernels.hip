@@ -3472,6 +3472,231 @@ hipError_t launch_travel_time(const TraceArgs &a, int rhs, double *t_end, double
 #endif
 
 // ------------------------------------------------------------------------------------------
+// Triangle meshes (bhg_trace_mesh_device): the trace's steps, unchanged, with a mesh as one more terminal
+// event.  travel_time_kernel's loop without the quadrature, on the same helpers; per accepted step [t, t + h]:
+//   * the terminal events of the trace (horizon, exit sphere, and -- a disk set -- the opaque disk) are settled by settle_events;
+//   * M = min(BHG_MESH_MAX_SUBSTEPS, max(1, ceil(L / max_chord))), L the Cartesian distance between the step's ends; the dense
+//     output is sampled at theta_m = m / M (Kerr: the Cartesian image of the Boyer-Lindquist sample) and consecutive samples are
+//     M straight sub-chords, tested in order against the tree (segment_first_hit: smallest s, ties to the smaller index);
+//   * sub-chords that start at or behind the terminal root are not looked at;
+//   * the first hit is moved onto the curve: brent_root on n_T . (x(lambda) - v0) over the sub-chord's interval (its ends lie on
+//     the curve, on opposite sides of the plane or on it); a root later than the terminal root loses to it;
+//   * the ray ends there with BHG_FLAG_HIT_OBJECT, end = the dense output at the root (Kerr: Boyer-Lindquist, finalised next),
+//     tri_id the triangle, bary the plane coordinates (u, v) of the refined point in it.
+// The whole-step cull: the sampled points deviate from the step's straight chord, per component, by at most
+// |h| (|qx1| / 4 + 0.385 |qx2| + 0.4725 |qx3|) (the maxima of th (1 - th), th (1 - th^2), th (1 - th^3) on [0, 1]); the box of
+// the step's ends widened by that holds every sub-chord, and a step whose box misses the root box has no hit.  Kerr: the same
+// bound on r, against the mesh's range of distances from the origin (a point at Boyer-Lindquist r lies at a Cartesian distance
+// in [r, sqrt(r^2 + a^2)]).
+// Disk off, a ray that meets no triangle has the plain trace's end / flags / n_steps / n_accepted bit for bit (the exit sphere's
+// certified Newton search, as in travel_time_kernel).
+// ------------------------------------------------------------------------------------------
+template <int RHS>
+__device__ __forceinline__ void mesh_point(const TraceArgs &A, const Dense &d, double t, double c[3])
+{
+    if (RHS == BHG_RHS_KERR_BL_) {
+        double q[3];
+        dense_pos(d, t, q);
+        bl_position_to_cart(A.spin, q, c);
+    } else {
+        dense_pos(d, t, c);
+    }
+}
+
+// may the step's polyline meet the mesh at all?
+template <int RHS>
+__device__ __forceinline__ bool mesh_step_candidate(const MeshArgs &G, const Dense &d, const double x0[3], const double x1[3],
+                                                    const double c0[3], const double c1[3], double spin)
+{
+    const double ah = fabs(d.h);
+    if (RHS == BHG_RHS_KERR_BL_) {
+        // the spans of r, theta, phi over the step's samples: |end - start| + twice the deviation from the straight line
+        double span[3], dev_r = 0.0;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const double dev = ah * (0.25 * fabs(d.qx[1][c]) + 0.385 * fabs(d.qx[2][c]) + 0.4725 * fabs(d.qx[3][c]));
+            span[c] = fabs(x1[c] - x0[c]) + 2.0 * dev;
+            if (c == 0) dev_r = dev;
+        }
+        const double slack = 1e-13 * (1.0 + fabs(x0[0]) + fabs(x1[0]));
+        const double r_lo = fmin(x0[0], x1[0]) - dev_r - slack, r_hi = fmax(x0[0], x1[0]) + dev_r + slack;
+        if (!(r_lo > 0.0)) return true;
+        // every sample lies in the ball of radius sqrt(r_hi^2 + a^2), and so does every sub-chord (a ball is convex)
+        const double R_hi = sqrt(r_hi * r_hi + spin * spin) * (1.0 + 1e-13);
+        if (R_hi < G.d_min) return false;
+        // every sample lies at a distance >= r_lo, but a chord between two such points dips below it: by the embedding's
+        // Jacobian (|dx/dr| <= 1, |dx/dtheta|, |dx/dphi| <= sqrt(r^2 + a^2)) no two samples are farther apart than len, and a
+        // chord of that length between points at distance >= r_lo stays at distance >= sqrt(r_lo^2 - len^2 / 4)
+        const double len = (span[0] + R_hi * (span[1] + span[2])) * (1.0 + 1e-13);
+        const double low2 = r_lo * r_lo - 0.25 * len * len;
+        return !(low2 > G.d_max * G.d_max * (1.0 + 1e-13));
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const double dev = ah * (0.25 * fabs(d.qx[1][c]) + 0.385 * fabs(d.qx[2][c]) + 0.4725 * fabs(d.qx[3][c]));
+        const double slack = 1e-13 * (1.0 + fabs(c0[c]) + fabs(c1[c]));
+        const double lo = fmin(c0[c], c1[c]) - dev - slack, hi = fmax(c0[c], c1[c]) + dev + slack;
+        if (lo > G.box[3 + c] || hi < G.box[c]) return false;
+    }
+    return true;
+}
+
+template <int RHS>
+__global__ void __launch_bounds__(64) trace_mesh_kernel(const TraceArgs A, const MeshArgs G)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= A.n) return;
+    const bool bl = RHS == BHG_RHS_KERR_BL_;
+    const bool disk = A.disk_r_out > 0.0;
+    RayState S;
+    double xe[3], ve[3];
+    if (start_ray<RHS, true>(A, i, S, xe, ve)) {    // final at once
+        G.tri_id[i] = -1;
+        store_result(A, (uint32_t)i, xe, ve, BHG_FLAG_START_INSIDE_ | BHG_FLAG_HIT_HORIZON_, 0, 0);
+        return;
+    }
+    uint32_t flags = 0;
+    int32_t tri = -1;
+    for (;;) {
+        StepTry P;
+        const uint32_t st = dp54_attempt<RHS>(A, S, P);
+        if (st == DP54_REJECTED) continue;
+        if (st != DP54_ACCEPTED) {
+            flags = st;
+            break;
+        }
+        bool ev_h, ev_e;
+        radial_events(A, S, P, ev_h, ev_e);
+        const bool ev_d = disk && crossed_disk_plane<RHS>(S.x, P.xn);
+        uint32_t evflag = 0;
+        double t_stop = P.t_new;
+        Dense d;
+        build_dense_pos(d, S.t, P.h, S.x, S.v, S.a1, P.a2, P.a3, P.a4, P.a5, P.a6, P.a7);
+        if (ev_h || ev_e || ev_d) {
+            auto g_z = [&](double tq) {
+                if (!bl) return dense_z(d, tq);
+                double q[3], sn, cs;
+                dense_pos(d, tq, q);
+                sincos_pi4(q[1], sn, cs);
+                return cs;
+            };
+            // the terminal events, settled as the trace kernels settle them (the earliest root wins: horizon, exit, disk)
+            double best;
+            int obj;
+            evflag = settle_events<EVT_EXIT | EVT_DISK>(
+                A, (ev_h ? EV_HORIZON : 0u) | (ev_e ? EV_EXIT : 0u) | (ev_d ? EV_DISK : 0u), S.t, P.t_new, S.x, P.xn,
+                [&](double tq, double Rr) { return dense_g(d, tq, Rr, bl); }, g_z,
+                [&](double tq, double xq[3]) { dense_pos(d, tq, xq); }, bl, best, obj);
+            if (evflag) t_stop = best;
+        }
+        // the mesh
+        double c0[3] = {S.x[0], S.x[1], S.x[2]}, c1[3] = {P.xn[0], P.xn[1], P.xn[2]};
+        if (bl) {
+            bl_position_to_cart(A.spin, S.x, c0);
+            bl_position_to_cart(A.spin, P.xn, c1);
+        }
+        if (!G.cull || mesh_step_candidate<RHS>(G, d, S.x, P.xn, c0, c1, A.spin)) {
+            const double dx = c1[0] - c0[0], dy = c1[1] - c0[1], dz = c1[2] - c0[2];
+            const double L = sqrt(dx * dx + dy * dy + dz * dz);
+            const double want = ceil(L / G.max_chord);
+            // (a NaN or huge quotient takes the cap)
+            const int M = !(want < (double)BHG_MESH_MAX_SUBSTEPS_) ? BHG_MESH_MAX_SUBSTEPS_ : (want < 1.0 ? 1 : (int)want);
+            double ta = S.t, pa[3];
+            mesh_point<RHS>(A, d, ta, pa);
+            for (int m = 0; m < M; m++) {
+                if (evflag && ta >= t_stop) break;
+                const double tb = m + 1 == M ? P.t_new : S.t + (P.h * (double)(m + 1)) / (double)M;
+                double pb[3], s_hit;
+                mesh_point<RHS>(A, d, tb, pb);
+                const int32_t hit = segment_first_hit<false>(G.mesh, pa, pb, s_hit);
+                if (hit >= 0) {
+                    const double *T = G.mesh.tri + (size_t)G.mesh.tri_slot[hit] * 9;
+                    const double e1[3] = {T[3], T[4], T[5]}, e2[3] = {T[6], T[7], T[8]};
+                    const double nT[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+                    auto g_T = [&](double tq) {
+                        double c[3];
+                        mesh_point<RHS>(A, d, tq, c);
+                        return nT[0] * (c[0] - T[0]) + nT[1] * (c[1] - T[1]) + nT[2] * (c[2] - T[2]);
+                    };
+                    // (the ends straddle the plane up to rounding: without a sign change -- both within rounding of the
+                    // plane -- the end nearer to it is the root, and Brent's search is never run without its bracket)
+                    const double ga = g_T(ta), gb = g_T(tb);
+                    double root;
+                    if (ga == 0.0)
+                        root = ta;
+                    else if (gb == 0.0)
+                        root = tb;
+                    else if ((ga < 0.0) == (gb < 0.0))
+                        root = fabs(ga) <= fabs(gb) ? ta : tb;
+                    else
+                        root = brent_root(g_T, ta, tb);
+                    if (!evflag || root <= t_stop) {
+                        double c[3];
+                        mesh_point<RHS>(A, d, root, c);
+                        const double w[3] = {c[0] - T[0], c[1] - T[1], c[2] - T[2]};
+                        const double nn = nT[0] * nT[0] + nT[1] * nT[1] + nT[2] * nT[2];
+                        const double we2[3] = {w[1] * e2[2] - w[2] * e2[1], w[2] * e2[0] - w[0] * e2[2], w[0] * e2[1] - w[1] * e2[0]};
+                        const double e1w[3] = {e1[1] * w[2] - e1[2] * w[1], e1[2] * w[0] - e1[0] * w[2], e1[0] * w[1] - e1[1] * w[0]};
+                        G.bary[i * 2 + 0] = (we2[0] * nT[0] + we2[1] * nT[1] + we2[2] * nT[2]) / nn;
+                        G.bary[i * 2 + 1] = (e1w[0] * nT[0] + e1w[1] * nT[1] + e1w[2] * nT[2]) / nn;
+                        tri = hit;
+                        evflag = BHG_FLAG_HIT_OBJECT_;
+                        t_stop = root;
+                    }
+                    // (a root behind the terminal event: that event ends the ray, and every later sub-chord starts behind it)
+                    break;
+                }
+                ta = tb;
+                pa[0] = pb[0];
+                pa[1] = pb[1];
+                pa[2] = pb[2];
+            }
+        }
+        if (evflag) {
+            flags = evflag;
+            // disk off and no triangle: the plain trace's bits (travel_time_kernel's rule for the exit sphere)
+            if (tri < 0 && !disk && ev_e && !ev_h &&
+                dp54_short_core<RHS, EVT_EXIT>(A, S.x, S.v, S.a1, S.t, P.t_new, P.h, P.a2, P.a3, P.a4, P.a5, P.a6, P.a7, P.xn, P.vn,
+                                               EV_EXIT, (uint32_t)i, S.n_att, S.n_acc) == PARK_ENDED) {
+                G.tri_id[i] = -1;
+                return;
+            }
+            build_dense_dir(d, S.a1, P.a2, P.a3, P.a4, P.a5, P.a6, P.a7);
+            dense_pos(d, t_stop, xe);
+            dense_dir(d, t_stop, ve);
+            break;
+        }
+        if (advance(A, S, P, xe, ve)) {
+            flags = BHG_FLAG_REACHED_END_;
+            break;
+        }
+    }
+    G.tri_id[i] = tri;
+    finish_ray(A, i, S, xe, ve, flags);
+}
+
+#if defined(BHG_TU_KERR)
+hipError_t launch_trace_mesh_kerr(const TraceArgs &a, const MeshArgs &m, hipStream_t s)
+{
+    if (a.n == 0) return hipSuccess;
+    BHG_LAUNCH((trace_mesh_kernel<BHG_RHS_KERR_BL_>), dim3((unsigned)((a.n + 63) / 64)), dim3(64), 0, s, a, m);
+    return hipGetLastError();
+}
+#elif !defined(BHG_TU_TIMELIKE)
+hipError_t launch_trace_mesh(const TraceArgs &a, const MeshArgs &m, int rhs, hipStream_t s)
+{
+    if (rhs == BHG_RHS_KERR_BL_) return launch_trace_mesh_kerr(a, m, s);
+    if (a.n == 0) return hipSuccess;
+    const dim3 grid((unsigned)((a.n + 63) / 64));
+    if (rhs == BHG_RHS_REDUCED_)
+        BHG_LAUNCH((trace_mesh_kernel<BHG_RHS_REDUCED_>), grid, dim3(64), 0, s, a, m);
+    else
+        BHG_LAUNCH((trace_mesh_kernel<BHG_RHS_CHRISTOFFEL_>), grid, dim3(64), 0, s, a, m);
+    return hipGetLastError();
+}
+#endif
+
+// ------------------------------------------------------------------------------------------
 // Start-up records (bhg_trace_prefix_device).  scipy's start guess h0 is one to two decades below the
 // step a ray settles on, and the controller climbs there by its x10 clamp: three to four accepted steps next to the camera,
 // a quarter of all the attempts of a frame, whose outcome depends on the ray, the metric, the tolerances, lambda_end and

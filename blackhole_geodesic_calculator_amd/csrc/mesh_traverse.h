@@ -1,0 +1,92 @@
+// mesh_traverse.h -- segment against the flattened BVH of mesh_bvh.h, on the device.  One function for
+// the mesh trace's sub-chords (first hit) and the mesh shade's shadow rays (any hit).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace bhg {
+
+// the device's view of a bhg_mesh: the tree, the triangles in leaf order and the maps between leaf order and the caller's
+struct MeshView {
+    const double *node_box;      // [n_nodes][6]: lo, hi (widened at build time)
+    const int32_t *node_skip;    // [n_nodes]
+    const int32_t *node_first;   // [n_nodes]: first leaf slot, -1 for an inner node
+    const int32_t *node_count;   // [n_nodes]: triangles of a leaf, 0 for an inner node
+    const double *tri;           // [nt][9]: v0, e1 = v1 - v0, e2 = v2 - v0 of the triangle in each leaf slot
+    const int32_t *tri_order;    // [nt]: leaf slot -> the caller's triangle
+    const int32_t *tri_slot;     // [nt]: the caller's triangle -> leaf slot
+    const double *tri_normals;   // nullptr, or [nt][9]: the vertex normals N0, N1, N2 of the triangle in each leaf slot
+    int32_t n_nodes, n_tris;
+};
+
+// Does the segment p + s d, 0 <= s <= s_max, meet the box?  The slab test with a relative slack on every comparison: the
+// boxes are widened by ulps, the quotients here are rounded, and a rejection must be certain.
+__device__ __forceinline__ bool segment_meets_box(const double *b, const double p[3], const double d[3], double s_max)
+{
+    double t_near = 0.0, t_far = s_max;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        if (d[c] == 0.0) {
+            if (p[c] < b[c] || p[c] > b[3 + c]) return false;
+        } else {
+            const double inv = 1.0 / d[c];
+            const double t1 = (b[c] - p[c]) * inv, t2 = (b[3 + c] - p[c]) * inv;
+            t_near = fmax(t_near, fmin(t1, t2));
+            t_far = fmin(t_far, fmax(t1, t2));
+        }
+    }
+    return t_near <= t_far + 1e-10 * (1.0 + fabs(t_near) + fabs(t_far));
+}
+
+// Moeller-Trumbore on the segment p + s d against the triangle (v0, e1, e2): two-sided, a zero determinant is no hit
+__device__ __forceinline__ bool segment_meets_triangle(const double *T, const double p[3], const double d[3], double &s, double &u,
+                                                       double &v)
+{
+    const double *v0 = T, *e1 = T + 3, *e2 = T + 6;
+    const double pv[3] = {d[1] * e2[2] - d[2] * e2[1], d[2] * e2[0] - d[0] * e2[2], d[0] * e2[1] - d[1] * e2[0]};
+    const double det = e1[0] * pv[0] + e1[1] * pv[1] + e1[2] * pv[2];
+    if (det == 0.0) return false;
+    const double inv = 1.0 / det;
+    const double tv[3] = {p[0] - v0[0], p[1] - v0[1], p[2] - v0[2]};
+    u = (tv[0] * pv[0] + tv[1] * pv[1] + tv[2] * pv[2]) * inv;
+    const double qv[3] = {tv[1] * e1[2] - tv[2] * e1[1], tv[2] * e1[0] - tv[0] * e1[2], tv[0] * e1[1] - tv[1] * e1[0]};
+    v = (d[0] * qv[0] + d[1] * qv[1] + d[2] * qv[2]) * inv;
+    s = (e2[0] * qv[0] + e2[1] * qv[1] + e2[2] * qv[2]) * inv;
+    return u >= 0.0 && v >= 0.0 && u + v <= 1.0 && s >= 0.0 && s <= 1.0;
+}
+
+// The segment p -> q against the tree.  First hit (ANY = false): the smallest s wins, a tie goes to the smaller index of the
+// caller's numbering -- whatever the tree's shape, so a box is only skipped when it starts behind the best s so far.  Returns
+// the caller's triangle (s in s_hit), or -1.  ANY = true: returns the first triangle met in traversal order, or -1.
+template <bool ANY>
+__device__ __forceinline__ int32_t segment_first_hit(const MeshView &M, const double p[3], const double q[3], double &s_hit)
+{
+    const double d[3] = {q[0] - p[0], q[1] - p[1], q[2] - p[2]};
+    double best = 1.0;
+    int32_t best_tri = -1;
+    for (int32_t i = 0; i < M.n_nodes;) {
+        if (!segment_meets_box(M.node_box + (size_t)i * 6, p, d, best)) {
+            i = M.node_skip[i];
+            continue;
+        }
+        const int32_t cnt = M.node_count[i], first = M.node_first[i];
+        for (int32_t k = 0; k < cnt; k++) {
+            double s, u, v;
+            if (!segment_meets_triangle(M.tri + (size_t)(first + k) * 9, p, d, s, u, v)) continue;
+            const int32_t id = M.tri_order[first + k];
+            if (ANY) {
+                s_hit = s;
+                return id;
+            }
+            if (best_tri < 0 || s < best || (s == best && id < best_tri)) {
+                best = s;
+                best_tri = id;
+            }
+        }
+        i++;
+    }
+    s_hit = best;
+    return best_tri;
+}
+
+}  // namespace bhg

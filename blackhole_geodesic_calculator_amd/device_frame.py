@@ -196,6 +196,11 @@ class DeviceFrame:
         self.phase_rate = 0.0         # set_disk_layers(phase_rate=): d(disk_phase)/dt of the retarded shade, 0 = off
         self.d_t_cross = None         # [max_crossings, n] fp64 crossing times and
         self.d_t_end = None           # [n] fp64 times to the rays' ends of the last travel-time trace (phase_rate != 0 only)
+        self.mesh = None              # _ffi.Mesh (set_mesh) or None: no triangle mesh in the curved region
+        self.mesh_chord = None        # max_chord of the mesh trace; None: a quarter of the trace parameters' r_s
+        self.d_tri_rgb = None         # [nt, 3] fp32 triangle colours, or None (white)
+        self.d_tri_id = None          # [n] int32 and
+        self.d_bary = None            # [n, 2] fp64 of the last mesh trace
 
     def _stream(self):
         return torch.cuda.current_stream(self.dev).cuda_stream
@@ -315,6 +320,42 @@ class DeviceFrame:
             raise ValueError("opacity must be in (0, 1]")
         self.disk_layers = _ffi.make_disk_layers(max_crossings, opacity)
 
+    def set_mesh(self, mesh=None, tri_rgb=None, chord=None, lamps=None):
+        """A triangle mesh in the curved region (bhg_trace_mesh_device, bhg_shade_mesh_device): trace()
+        ends a ray where its curve meets a triangle and keeps d_tri_id [n] int32 / d_bary [n, 2]; shade() / shade_f32() /
+        render() light the mesh rays (tri_rgb [nt, 3] per triangle, default white; the lamps of set_objects([], lamps=...) or
+        lamps=; shadows cast by the mesh itself), every other ray as without the mesh.  mesh: an _ffi.Mesh of this frame's
+        context, or (vertices, triangles).  chord: the sub-chord length of the trace, default a quarter of r_s.  Not with
+        object spheres, disk layers, redshift, polarisation, the thermal disk or shade_stokes() (ValueError).  The kept
+        initial steps and start-up records are neither used nor touched.  None: off -- every path the one it was, bit for bit."""
+        self._traced = None
+        if mesh is None:
+            self.mesh = self.d_tri_rgb = self.mesh_chord = None
+            return
+        if not isinstance(mesh, _ffi.Mesh):
+            mesh = _ffi.Mesh(self.ctx, mesh[0], mesh[1])
+        if mesh.ctx is not self.ctx:
+            raise ValueError("the mesh belongs to another context")
+        if chord is not None and not (np.isfinite(float(chord)) and float(chord) > 0.0):
+            raise ValueError("chord must be finite and > 0")
+        self.d_tri_rgb = None
+        if tri_rgb is not None:
+            rgb = np.ascontiguousarray(tri_rgb, dtype=np.float32)
+            if rgb.shape != (mesh.n_triangles, 3):
+                raise ValueError("tri_rgb must have shape [n_triangles, 3]")
+            self.d_tri_rgb = torch.as_tensor(rgb).to(self.dev)
+        self.mesh, self.mesh_chord = mesh, None if chord is None else float(chord)
+        if lamps is not None:
+            self.lamps = lamps
+        self._mesh_check()
+
+    def _mesh_check(self):
+        for name, on in (("object spheres", self.spheres is not None and len(self.spheres) > 0),
+                         ("disk layers", self.disk_layers is not None), ("redshift", self.redshift is not None),
+                         ("polarisation", self.polarisation is not None), ("the thermal disk", self.disk_thermal is not None)):
+            if on:
+                raise ValueError(f"a mesh does not go with {name}")
+
     def _layers_check(self):
         if (self.spheres is not None and len(self.spheres) > 0) or self.object_textures is not None or self.object_motion is not None:
             raise ValueError("disk layers do not go with object spheres, object textures or object motion")
@@ -380,6 +421,22 @@ class DeviceFrame:
             params.order_blocks = self.S
         self._params = params
         origin = np.asarray(self.origin, dtype=np.float64)
+        if self.mesh is not None:
+            # the mesh trace: whole records, its own kernel, the plain call; the kept initial steps are neither used nor touched
+            self._mesh_check()
+            if self.d_end is None:
+                self.d_end = torch.empty((self.n, 6), dtype=torch.float64, device=self.dev)
+            if self.d_tri_id is None:
+                self.d_tri_id = torch.empty(self.n, dtype=torch.int32, device=self.dev)
+                self.d_bary = torch.empty((self.n, 2), dtype=torch.float64, device=self.dev)
+            self._dir_traced, self._traced = False, None
+            chord = 0.25 * float(params.r_s) if self.mesh_chord is None else self.mesh_chord
+            self.ctx.trace_mesh_device(params, self.mesh, chord, self.n, self.d_k0.data_ptr(), self.d_end.data_ptr(),
+                                       self.d_tri_id.data_ptr(), self.d_bary.data_ptr(), x0_shared=origin,
+                                       d_flags=self.d_flags.data_ptr(), d_n_steps=self.d_steps.data_ptr(),
+                                       d_n_accepted=self.d_acc.data_ptr(), stream=self._stream())
+            self._traced = "mesh"
+            return
         if self.disk_layers is not None:
             # the crossings trace: whole records, its own kernel; the kept initial steps are neither used nor touched
             self._layers_check()
@@ -458,6 +515,18 @@ class DeviceFrame:
         the polarisation (shade_stokes only), the thermal disk and the object motion as set, each None when off -- pol = None
         and none of the others is the textured call exactly."""
         form = self._shade_form()
+        if (form == "mesh") != (self.mesh is not None):
+            raise RuntimeError("set_mesh() changed since the last trace: trace() again")
+        if form == "mesh":
+            if pol is not None:
+                raise ValueError("a mesh has no Stokes images: shade_stokes() is not available with set_mesh()")
+            self._mesh_check()
+            self.ctx.shade_mesh_device(self.d_end.data_ptr(), self.d_flags.data_ptr(), self.d_tri_id.data_ptr(),
+                                       self.d_bary.data_ptr(), self.P, self.S, self.scene(), self.mesh,
+                                       d_tri_rgb=0 if self.d_tri_rgb is None else self.d_tri_rgb.data_ptr(), d_rgba=d_rgba,
+                                       d_rgba_f32=d_rgba_f32, d_scatter=0 if scatter is None else scatter.data_ptr(),
+                                       stream=self._stream())
+            return
         if form == "layers_t":      # the layers of a travel-time trace: the crossing times are there
             if self.disk_layers is None or self.phase_rate == 0.0:
                 raise RuntimeError("set_disk_layers() changed since the last trace: trace() again")
@@ -505,6 +574,8 @@ class DeviceFrame:
         polarisation (set_polarisation first)."""
         if self.disk_layers is not None:
             raise ValueError("disk layers have no Stokes images: shade_stokes() is not available with set_disk_layers()")
+        if self.mesh is not None:
+            raise ValueError("a mesh has no Stokes images: shade_stokes() is not available with set_mesh()")
         if self.polarisation is None:
             raise RuntimeError("set_polarisation() first")
         if self.d_qu is None:

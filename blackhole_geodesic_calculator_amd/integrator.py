@@ -64,7 +64,7 @@ class GeodesicIntegratorSchwarzschild:
 
     # ------------------------------------------------------------------------------------
     def trace(self, k0, x0, max_step=np.inf, curve_end=50.0, r_exit=0.0, disk=None, spheres=None, redshift=None,
-              polarisation=None, disk_thermal=None, disk_crossings=None, travel_time=False):
+              polarisation=None, disk_thermal=None, disk_crossings=None, travel_time=False, mesh=None, mesh_chord=None):
         """Batched solve.  k0[N,3] (or [...,3]); x0[3] shared origin or same leading shape as k0.
         r_exit: outward sphere-exit radius (Limited engine's ray_trace, Limited...py:273-278);
         disk=(R_in, R_out): thin disk in z = 0, first crossing inside the annulus ends the ray with
@@ -108,7 +108,21 @@ class GeodesicIntegratorSchwarzschild:
             t_cross[K, ...]            with disk_crossings=K: the time of each stored crossing, NaN where a ray has none ("t" is
                                        then the time to the ray's end)
         Every other key comes from the call that makes it without travel_time.
+        mesh=Mesh or (vertices [nv, 3], triangles [nt, 3]) (DP5(4), null rays; bhg_trace_mesh): a triangle
+        mesh in the curved region, Cartesian and BH-centred.  The ray takes the steps it takes without the mesh; where the curve
+        meets a triangle it ends with FLAG_HIT_OBJECT and the dict also has
+            tri_id[...]                int32, the triangle hit, -1 for every other ray
+            bary[..., 2]               the plane coordinates (u, v) of the hit in that triangle, NaN for every other ray
+        mesh_chord (default 0.25 r_s): the length of the straight sub-chords each step is tested in.  Not with spheres=,
+        disk_crossings=, travel_time=, redshift=, polarisation= or disk_thermal=.
         """
+        if mesh is not None:
+            for name, given in (("spheres", spheres is not None), ("disk_crossings", disk_crossings is not None),
+                                ("travel_time", bool(travel_time)), ("redshift", redshift is not None),
+                                ("polarisation", polarisation is not None), ("disk_thermal", disk_thermal is not None)):
+                if given:
+                    raise ValueError(f"mesh does not go with {name}")
+            return self._trace_mesh(k0, x0, max_step, curve_end, r_exit, disk, mesh, mesh_chord)
         if travel_time and spheres is not None:
             raise ValueError("travel_time does not go with object spheres")
         if disk_crossings is not None:
@@ -159,6 +173,30 @@ class GeodesicIntegratorSchwarzschild:
                 t = np.where(flags == _ffi.FLAG_HIT_DISK, tt[7][0], t)
             out["t"] = t.reshape(lead)
         return out
+
+    def _trace_mesh(self, k0, x0, max_step, curve_end, r_exit, disk, mesh, mesh_chord):
+        """trace(mesh=): a mesh given as arrays lives for this call."""
+        own = not isinstance(mesh, _ffi.Mesh)
+        m = _ffi.Mesh(self._ctx, mesh[0], mesh[1]) if own else mesh
+        try:
+            k0 = np.asarray(k0, dtype=np.float64)
+            lead = k0.shape[:-1]
+            x0 = np.asarray(x0, dtype=np.float64)
+            chord = 0.25 * self.r_s if mesh_chord is None else float(mesh_chord)
+            end, flags, steps, acc, tri, bary = self._ctx.trace_mesh(k0.reshape(-1, 3), x0 if x0.ndim == 1 else x0.reshape(-1, 3),
+                                                                     self.params(max_step, curve_end, r_exit, disk), m, chord)
+        finally:
+            if own:
+                m.close()
+        return {
+            "ray_end": end.reshape(lead + (6,)),
+            "ray_blackhole_hit": ((flags & _ffi.FLAG_HIT_HORIZON) != 0).astype(np.uint8).reshape(lead),
+            "flags": flags.reshape(lead),
+            "n_steps": steps.reshape(lead),
+            "n_accepted": acc.reshape(lead),
+            "tri_id": tri.reshape(lead),
+            "bary": bary.reshape(lead + (2,)),
+        }
 
     def _trace_crossings(self, k0, x0, max_step, curve_end, r_exit, disk, spheres, redshift, polarisation, disk_thermal, K,
                          travel_time=False):

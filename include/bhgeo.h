@@ -68,7 +68,10 @@ extern "C" {
                                   BHG_DISK_CROSSINGS (bhg_trace_crossings_device, bhg_trace_crossings, bhg_shade_disk_layers_device,
                                   bhg_disk_layers_size, struct bhg_disk_layers, BHG_MAX_CROSSINGS: higher-order disk images);
                                   BHG_TRAVEL_TIME (bhg_travel_time_device, bhg_travel_time, bhg_shade_disk_layers_retarded_device:
-                                  the coordinate time along each ray, the disk layers at their retarded phase).
+                                  the coordinate time along each ray, the disk layers at their retarded phase);
+                                  BHG_MESH (bhg_mesh_create / _destroy / _info, bhg_mesh_bvh_host, bhg_trace_mesh_device,
+                                  bhg_trace_mesh, bhg_shade_mesh_device, struct bhg_mesh, BHG_MESH_MAX_SUBSTEPS: triangle meshes
+                                  in the curved region).
                                9: redshift -- bhg_redshift_device / _host, bhg_shade_scene_redshift_device, bhg_frame_set_redshift,
                                   bhg_redshift_size, struct bhg_redshift;
                                   nothing of ABI 8 changed.
@@ -947,6 +950,64 @@ int bhg_shade_disk_layers_retarded_device(bhg_context *ctx, const double *d_end,
                                           const bhg_observer *obs, const double *x0_shared, const double *d_k0, double *d_rgba,
                                           float *d_rgba_f32, const int64_t *d_scatter, const bhg_disk_thermal *th,
                                           const bhg_disk_layers *layers, const double *d_t_cross, double phase_rate, void *stream);
+
+/* --- triangle meshes in the curved region (within ABI 10) ---------------------------------------------
+ * A mesh is vertices [nv][3] fp64, Cartesian and centred on the hole (the frame object spheres are given in), and triangles
+ * [nt][3] int32.  Triangles are two-sided.  A ray takes exactly the steps it takes without the mesh; the mesh is one more
+ * terminal event, as an object sphere is.  THE HIT RULE, for each accepted DP5(4) step [lambda_j, lambda_j + h] in order:
+ *   - L = the distance between the Cartesian positions of the step's two ends (Kerr: of their Cartesian images),
+ *     M = min(BHG_MESH_MAX_SUBSTEPS, max(1, ceil(L / max_chord))); the step's dense-output position is sampled at
+ *     theta_m = m / M (Kerr: the Cartesian image of the Boyer-Lindquist dense output); consecutive samples form M sub-chords;
+ *   - the sub-chords are tested in order against every triangle with fp64 Moeller-Trumbore on the segment: a triangle counts when
+ *     0 <= s <= 1, u, v >= 0, u + v <= 1; a zero determinant is skipped.  On the first sub-chord that meets a triangle the
+ *     smallest s wins, a tie goes to the smaller triangle index: the tree only accelerates this, the answer does not depend on it;
+ *   - the hit is moved from the chord onto the curve: Brent's search for the root of n_T . (x(lambda) - v0) on the sub-chord's
+ *     parameter interval (an end exactly on the plane is the root; ends that do not straddle the plane -- both within rounding of
+ *     it -- give the end nearer to it).  The ray ends there with BHG_FLAG_HIT_OBJECT, end = the dense output at the root,
+ *     tri_id[i] = the triangle, bary[i] = (u, v), the plane coordinates of the refined point in that triangle,
+ *     u = ((x - v0) x e2) . n / |n|^2, v = (e1 x (x - v0)) . n / |n|^2, n = e1 x e2 (they may leave [0, 1] by the chord's sag);
+ *   - horizon, exit sphere and the opaque disk (disk_r_out > 0) are settled as the trace settles them and the earliest root wins:
+ *     a mesh root later than the terminal root loses, sub-chords that start at or behind the terminal root are not looked at.
+ * n_steps / n_accepted count up to and including the step that holds the hit.  A ray that hits nothing has tri_id = -1 and its
+ * bary slot untouched; with no disk set its end / flags / n_steps / n_accepted are bhg_trace_device's bit for bit, with a disk
+ * its flags and counts are the opaque-disk trace's and its end state that trace's within the disk bound of DESIGN section 16.
+ * Refused (BHG_E_INVALID) before anything is launched or written: BHG_METHOD_RK4, time_like = 1, a NULL mesh, max_chord not
+ * finite or <= 0, a NULL d_tri_id or d_bary, a mesh of another context's device.
+ * bhg_mesh_create builds the tree on the host (leaf_size triangles per leaf at most, 4 is a good default; leaf_size >= nt is
+ * brute force) and copies it to ctx's device.  vertex_normals: NULL, or [nv][3] for smooth shading.  Refused, nothing allocated:
+ * nt = 0, nv = 0, an index outside [0, nv), a non-finite vertex or normal, leaf_size < 1, nt or nv over 2^31 - 1.
+ * Environment: BHGEO_MESH_CULL=0 turns the whole-step cull off (the results are the same bits). */
+#define BHG_MESH 1
+#define BHG_MESH_MAX_SUBSTEPS 1024
+typedef struct bhg_mesh bhg_mesh;
+int bhg_mesh_create(bhg_context *ctx, const double *vertices, size_t n_vertices, const int32_t *triangles, size_t n_triangles,
+                    const double *vertex_normals, int32_t leaf_size, bhg_mesh **out);
+void bhg_mesh_destroy(bhg_mesh *mesh);
+/* the tree's node count, its depth (levels below the root) and the root box (lo x, y, z, hi x, y, z); any output may be NULL */
+int bhg_mesh_info(const bhg_mesh *mesh, int64_t *n_nodes, int32_t *depth, double box[6]);
+/* Host only, no context, no GPU: the flattened tree as the device gets it.  Nodes in depth-first order; on a box miss at node
+ * i go to node_skip[i] (> i), otherwise to i + 1; a leaf (node_count > 0) holds the triangles tri_order[node_first ..
+ * node_first + node_count - 1], an inner node has node_count = 0 and node_first = -1.  cap = the nodes the arrays hold
+ * (2 * n_triangles - 1 always suffices); *n_nodes is set even when cap is too small (BHG_E_INVALID then). */
+int bhg_mesh_bvh_host(const double *vertices, size_t n_vertices, const int32_t *triangles, size_t n_triangles, int32_t leaf_size,
+                      double *node_box, int32_t *node_skip, int32_t *node_first, int32_t *node_count, int32_t *tri_order, size_t cap,
+                      size_t *n_nodes);
+int bhg_trace_mesh_device(bhg_context *ctx, const bhg_params *p, const bhg_mesh *mesh, double max_chord,
+                          const double *x0_shared, const double *d_x0, const double *d_k0, size_t n, double *d_end,
+                          uint8_t *d_flags, uint32_t *d_n_steps, uint32_t *d_n_accepted, int32_t *d_tri_id, double *d_bary,
+                          void *stream);
+/* bhg_trace_mesh_device on host arrays, as bhg_trace_crossings.  Blocking.  bary is read first. */
+int bhg_trace_mesh(bhg_context *ctx, const bhg_params *p, const bhg_mesh *mesh, double max_chord, const double *x0,
+                   int x0_is_shared, const double *k0, size_t n, double *end, uint8_t *flags, uint32_t *n_steps,
+                   uint32_t *n_accepted, int32_t *tri_id, double *bary);
+/* The shade of a mesh trace.  A ray flagged BHG_FLAG_HIT_OBJECT with tri_id >= 0 gets tri_rgb[tri] (d_tri_rgb [nt][3] fp32, NULL =
+ * white) times the Lambert lamp sum of the object spheres, I^2 n.l / d^2 with n.l clamped at 0: n the triangle's unit normal --
+ * or, vertex normals given, the normalised (1 - u - v) N0 + u N1 + v N2 -- turned to face the incoming ray; a lamp is shadowed
+ * when the straight segment from x + 1e-5 l^ to the lamp meets any triangle.  Every other ray is bhg_shade_scene_device's, bit
+ * for bit.  Refused: a scene with n_spheres > 0, a NULL mesh, a mesh of another context's device. */
+int bhg_shade_mesh_device(bhg_context *ctx, const double *d_end, const uint8_t *d_flags, const int32_t *d_tri_id,
+                          const double *d_bary, size_t n_pixels, int32_t samples, const bhg_scene *scene, const bhg_mesh *mesh,
+                          const float *d_tri_rgb, double *d_rgba, float *d_rgba_f32, const int64_t *d_scatter, void *stream);
 
 /* Acceleration probe: acc[n][3] = -Gamma^i_{mu nu} k^mu k^nu at (x[n][3], k[n][3]); host buffers.
  * Lets tests compare the device RHS with the oracle's term by term.  With rhs_form = BHG_RHS_KERR_BL the triples
