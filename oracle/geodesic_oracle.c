@@ -42,6 +42,7 @@ void bhgo_set_debug(int v) { bhgo_debug = v; }
 #include <float.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <stdlib.h>
 #include <string.h>
 #ifdef _OPENMP
 #include <omp.h>
@@ -354,9 +355,10 @@ typedef struct {
     const dense_t *dn;
     const hermite_t *hm;
     double R;
-    int zmode; /* 0: g = r - R; 1: g = z (disk plane); 2: g = |x - c| - R (object sphere) */
+    int zmode; /* 0: g = r - R; 1: g = z (disk plane); 2: g = |x - c| - R (object sphere); 3: g = nrm . (x - c) (a triangle's plane) */
     const rayctx *rc;
     double c[3];
+    double nrm[3];
 } evfun_t;
 
 /* position of a state in the Cartesian frame the object spheres live in: the state's own x, y, z, or -- Boyer-Lindquist
@@ -388,6 +390,11 @@ static double ev_eval(const evfun_t *e, double t)
         cart_position(e->rc, y, xc);
         double dx = xc[0] - e->c[0], dy = xc[1] - e->c[1], dz = xc[2] - e->c[2];
         return sqrt(dx * dx + dy * dy + dz * dz) - e->R;
+    }
+    if (e->zmode == 3) {
+        double xc[3];
+        cart_position(e->rc, y, xc);
+        return e->nrm[0] * (xc[0] - e->c[0]) + e->nrm[1] * (xc[1] - e->c[1]) + e->nrm[2] * (xc[2] - e->c[2]);
     }
     return radius(e->rc, y) - e->R;
 }
@@ -611,12 +618,120 @@ static void crossings_step(crossings_t *cr, const evfun_t *base, const double y_
     cr->n++;
 }
 
+/* optional triangle mesh (bhgo_trace_mesh): the hit rule of DESIGN.md section 19 on this file's own step loop, a mesh as one more
+   terminal event.  After each accepted step [t_old, t], the terminal events of check_events settled first:
+     - L = the distance between the Cartesian positions of the step's ends, M = min(1024, max(1, ceil(L / max_chord))); the dense
+       output's position (Kerr: the Cartesian image of the Boyer-Lindquist one) at t_old + (h m) / M, the last one at t itself;
+     - the M sub-chords in order, each against EVERY triangle -- no tree, no box, no cull of any kind -- with plain fp64
+       Moeller-Trumbore (-ffp-contract=off, like the rest of the file): a zero determinant is skipped, the smallest s wins, a tie
+       goes to the smaller index; a sub-chord that starts at or behind the terminal root ends the search;
+     - the first hit is refined by brentq on n_T . (x(t) - v0) over the sub-chord's interval; without a bracket an end on the
+       plane, or otherwise the nearer end, is the root; a root later than the terminal root loses to it.
+   T holds (v0, e1 = v1 - v0, e2 = v2 - v0) per triangle in the caller's order. */
+#define BHGO_MESH_MAX_SUBSTEPS 1024
+typedef struct {
+    const double *T; /* [nt][9] */
+    size_t nt;
+    double max_chord;
+    int32_t tri;  /* out: the triangle, -1 for none */
+    double bary[2];
+    uint32_t M;   /* out: the sub-chord count of the step that holds the hit */
+} mesh_t;
+
+static int32_t mesh_segment_first_hit(const mesh_t *ms, const double p[3], const double q[3])
+{
+    const double d[3] = {q[0] - p[0], q[1] - p[1], q[2] - p[2]};
+    double best = 0.0;
+    int32_t best_tri = -1;
+    for (size_t j = 0; j < ms->nt; j++) {
+        const double *v0 = ms->T + 9 * j, *e1 = v0 + 3, *e2 = v0 + 6;
+        const double pv[3] = {d[1] * e2[2] - d[2] * e2[1], d[2] * e2[0] - d[0] * e2[2], d[0] * e2[1] - d[1] * e2[0]};
+        const double det = e1[0] * pv[0] + e1[1] * pv[1] + e1[2] * pv[2];
+        if (det == 0.0) continue;
+        const double inv = 1.0 / det;
+        const double tv[3] = {p[0] - v0[0], p[1] - v0[1], p[2] - v0[2]};
+        const double u = (tv[0] * pv[0] + tv[1] * pv[1] + tv[2] * pv[2]) * inv;
+        const double qv[3] = {tv[1] * e1[2] - tv[2] * e1[1], tv[2] * e1[0] - tv[0] * e1[2], tv[0] * e1[1] - tv[1] * e1[0]};
+        const double v = (d[0] * qv[0] + d[1] * qv[1] + d[2] * qv[2]) * inv;
+        const double s = (e2[0] * qv[0] + e2[1] * qv[1] + e2[2] * qv[2]) * inv;
+        if (!(u >= 0.0 && v >= 0.0 && u + v <= 1.0 && s >= 0.0 && s <= 1.0)) continue;
+        if (best_tri < 0 || s < best) { /* (ascending index: an equal s keeps the smaller one) */
+            best = s;
+            best_tri = (int32_t)j;
+        }
+    }
+    return best_tri;
+}
+
+/* returns 1 when the mesh ends the ray in this step (*t_hit the refined root; ms->tri, bary, M filled), else 0 */
+static int mesh_step(mesh_t *ms, const evfun_t *base, const double y_old[6], const double y_new[6], double t_old, double t,
+                     int have_terminal, double t_terminal, double *t_hit)
+{
+    double c0[3], c1[3];
+    cart_position(base->rc, y_old, c0);
+    cart_position(base->rc, y_new, c1);
+    const double dx = c1[0] - c0[0], dy = c1[1] - c0[1], dz = c1[2] - c0[2];
+    const double L = sqrt(dx * dx + dy * dy + dz * dz);
+    const double want = ceil(L / ms->max_chord);
+    /* (a NaN or huge quotient takes the cap) */
+    const int M = !(want < (double)BHGO_MESH_MAX_SUBSTEPS) ? BHGO_MESH_MAX_SUBSTEPS : (want < 1.0 ? 1 : (int)want);
+    const double h = t - t_old;
+    double ta = t_old, pa[3], y[6];
+    dense_eval(base->dn, ta, y);
+    cart_position(base->rc, y, pa);
+    for (int m = 0; m < M; m++) {
+        if (have_terminal && ta >= t_terminal) break;
+        const double tb = m + 1 == M ? t : t_old + (h * (double)(m + 1)) / (double)M;
+        double pb[3];
+        dense_eval(base->dn, tb, y);
+        cart_position(base->rc, y, pb);
+        const int32_t hit = mesh_segment_first_hit(ms, pa, pb);
+        if (hit >= 0) {
+            const double *v0 = ms->T + 9 * (size_t)hit, *e1 = v0 + 3, *e2 = v0 + 6;
+            evfun_t e = *base;
+            e.zmode = 3;
+            e.nrm[0] = e1[1] * e2[2] - e1[2] * e2[1];
+            e.nrm[1] = e1[2] * e2[0] - e1[0] * e2[2];
+            e.nrm[2] = e1[0] * e2[1] - e1[1] * e2[0];
+            memcpy(e.c, v0, sizeof(double) * 3);
+            const double ga = ev_eval(&e, ta), gb = ev_eval(&e, tb);
+            double root;
+            if (ga == 0.0)
+                root = ta;
+            else if (gb == 0.0)
+                root = tb;
+            else if ((ga < 0.0) == (gb < 0.0))
+                root = fabs(ga) <= fabs(gb) ? ta : tb;
+            else
+                root = brentq(&e, ta, tb);
+            if (have_terminal && !(root <= t_terminal)) return 0; /* that event ends the ray; every later sub-chord starts behind it */
+            double c[3];
+            dense_eval(base->dn, root, y);
+            cart_position(base->rc, y, c);
+            const double *n = e.nrm;
+            const double w[3] = {c[0] - v0[0], c[1] - v0[1], c[2] - v0[2]};
+            const double nn = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];
+            const double we2[3] = {w[1] * e2[2] - w[2] * e2[1], w[2] * e2[0] - w[0] * e2[2], w[0] * e2[1] - w[1] * e2[0]};
+            const double e1w[3] = {e1[1] * w[2] - e1[2] * w[1], e1[2] * w[0] - e1[0] * w[2], e1[0] * w[1] - e1[1] * w[0]};
+            ms->bary[0] = (we2[0] * n[0] + we2[1] * n[1] + we2[2] * n[2]) / nn;
+            ms->bary[1] = (e1w[0] * n[0] + e1w[1] * n[1] + e1w[2] * n[2]) / nn;
+            ms->tri = hit;
+            ms->M = (uint32_t)M;
+            *t_hit = root;
+            return 1;
+        }
+        ta = tb;
+        memcpy(pa, pb, sizeof(pa));
+    }
+    return 0;
+}
+
 /* ---------------------------------------------------------------------------------------
  * One ray, adaptive DP5(4): RungeKutta.__init__ (rk.py:84-104) + solve_ivp loop
  * (ivp.py:654-723) + _step_impl (rk.py:111-176)
  * ------------------------------------------------------------------------------------- */
 static void trace_dp54(const bhgo_params *p, const rayctx *rc, const double x0[3], const double k0[3], ray_result *res,
-                       sampler_t *sm, crossings_t *cr)
+                       sampler_t *sm, crossings_t *cr, mesh_t *ms)
 {
     double y[6] = {k0[0], x0[0], k0[1], x0[1], k0[2], x0[2]};
     double f[6], K[7][6], y_new[6], f_new[6];
@@ -706,25 +821,31 @@ static void trace_dp54(const bhgo_params *p, const rayctx *rc, const double x0[3
         double g_e_new = radius(rc, y) - p->r_exit;
         double z_old = rc->kerr ? cos(y_old[3]) : y_old[5], z_new = rc->kerr ? cos(y[3]) : y[5];
         dense_t dn;
-        evfun_t base = {0, &dn, NULL, 0.0, 0, rc, {0, 0, 0}};
+        evfun_t base = {0, &dn, NULL, 0.0, 0, rc, {0, 0, 0}, {0, 0, 0}};
         int any = (((g_h <= 0) && (g_h_new >= 0)) || ((g_h >= 0) && (g_h_new <= 0))) ||
                   ((p->r_exit > 0.0) && (g_e <= 0) && (g_e_new >= 0)) ||
                   ((p->disk_r_out > 0.0) && (((z_old <= 0) && (z_new >= 0)) || ((z_old >= 0) && (z_new <= 0)))) ||
                   (p->n_spheres > 0);
-        if (any || sm || cr) dense_build(&dn, t_old, t, y_old, K);
-        if (any) {
-            double t_root, y_root[6];
-            uint32_t fl = check_events(p, g_h, g_h_new, g_e, g_e_new, y_old, y, &base, t_old, t, &t_root, y_root, &res->object_id);
-            if (cr) crossings_step(cr, &base, y_old, y, t_old, t, fl ? t_root : INFINITY);
-            if (fl) {
-                res->flags |= fl;
-                t = t_root;
-                memcpy(y, y_root, sizeof(y));
-                if (sm) sampler_emit(sm, &dn, t);
-                break;
+        if (any || sm || cr || ms) dense_build(&dn, t_old, t, y_old, K);
+        double t_root = t, y_root[6];
+        uint32_t fl = 0;
+        if (any) fl = check_events(p, g_h, g_h_new, g_e, g_e_new, y_old, y, &base, t_old, t, &t_root, y_root, &res->object_id);
+        if (cr) crossings_step(cr, &base, y_old, y, t_old, t, fl ? t_root : INFINITY);
+        if (ms) {
+            double t_hit;
+            if (mesh_step(ms, &base, y_old, y, t_old, t, fl != 0, t_root, &t_hit)) {
+                fl = BHGO_FLAG_HIT_OBJECT;
+                t_root = t_hit;
+                dense_eval(&dn, t_hit, y_root);
             }
-        } else if (cr)
-            crossings_step(cr, &base, y_old, y, t_old, t, INFINITY);
+        }
+        if (fl) {
+            res->flags |= fl;
+            t = t_root;
+            memcpy(y, y_root, sizeof(y));
+            if (sm) sampler_emit(sm, &dn, t);
+            break;
+        }
         if (sm) sampler_emit(sm, &dn, t);
         g_h = g_h_new;
         g_e = g_e_new;
@@ -808,7 +929,7 @@ static void trace_rk4(const bhgo_params *p, const rayctx *rc, const double x0[3]
         memcpy(f, f_new, sizeof(f));
         double g_h_new = radius(rc, y) - rc->r_hor;
         double g_e_new = radius(rc, y) - p->r_exit;
-        evfun_t base = {1, NULL, &hm, 0.0, 0, rc, {0, 0, 0}};
+        evfun_t base = {1, NULL, &hm, 0.0, 0, rc, {0, 0, 0}, {0, 0, 0}};
         double t_root, y_root[6];
         uint32_t fl = check_events(p, g_h, g_h_new, g_e, g_e_new, hm.y0, hm.y1, &base, t_old, t, &t_root, y_root, &res->object_id);
         if (fl) {
@@ -880,7 +1001,7 @@ static void bl_to_cart(const double q[3], const double u[3], double a, double x[
 }
 
 static void trace_one(const bhgo_params *p_in, const double x0[3], const double k0[3], ray_result *res, sampler_t *sm,
-                      crossings_t *cr)
+                      crossings_t *cr, mesh_t *ms)
 {
     /* validate_tol (scipy _ivp/common.py:44-51): an rtol below 100 eps is raised to 100 eps (scipy warns and carries on) */
     bhgo_params pc = *p_in;
@@ -917,7 +1038,7 @@ static void trace_one(const bhgo_params *p_in, const double x0[3], const double 
         if (p->method == BHGO_METHOD_RK4)
             trace_rk4(p, &rc, q, u, res, sm);
         else
-            trace_dp54(p, &rc, q, u, res, sm, cr);
+            trace_dp54(p, &rc, q, u, res, sm, cr, ms);
         /* res->end is {r, th, ph, ur, uth, uph}: back to Cartesian */
         double xe[3], ke[3];
         bl_to_cart(res->end, res->end + 3, a, xe, ke);
@@ -961,7 +1082,7 @@ static void trace_one(const bhgo_params *p_in, const double x0[3], const double 
     if (p->method == BHGO_METHOD_RK4)
         trace_rk4(p, &rc, x0, k0, res, sm);
     else
-        trace_dp54(p, &rc, x0, k0, res, sm, cr);
+        trace_dp54(p, &rc, x0, k0, res, sm, cr, ms);
 }
 
 /* ---------------------------------------------------------------------------------------
@@ -995,7 +1116,7 @@ int bhgo_trace(const bhgo_params *p, const double *x0, int x0_shared, const doub
     for (long long i = 0; i < nn; i++) {
         ray_result r;
         const double *xi = x0_shared ? x0 : x0 + 3 * i;
-        trace_one(p, xi, k0 + 3 * i, &r, NULL, NULL);
+        trace_one(p, xi, k0 + 3 * i, &r, NULL, NULL, NULL);
         memcpy(end + 6 * i, r.end, sizeof(double) * 6);
         if (flags) flags[i] = (uint8_t)r.flags;
         if (n_attempted) n_attempted[i] = r.n_attempted;
@@ -1021,7 +1142,7 @@ int bhgo_trace_objects(const bhgo_params *p, const double *x0, int x0_shared, co
     for (long long i = 0; i < nn; i++) {
         ray_result r;
         r.object_id = -1;
-        trace_one(p, x0_shared ? x0 : x0 + 3 * i, k0 + 3 * i, &r, NULL, NULL);
+        trace_one(p, x0_shared ? x0 : x0 + 3 * i, k0 + 3 * i, &r, NULL, NULL, NULL);
         memcpy(end + 6 * i, r.end, sizeof(double) * 6);
         if (flags) flags[i] = (uint8_t)r.flags;
         if (n_attempted) n_attempted[i] = r.n_attempted;
@@ -1053,7 +1174,7 @@ int bhgo_trace_crossings(const bhgo_params *p, const double *x0, int x0_shared, 
     for (long long i = 0; i < nn; i++) {
         ray_result r;
         crossings_t cr = {p->disk_r_in, p->disk_r_out, max_records, 0, n, cross + 6 * i, t_cross + i};
-        trace_one(&off, x0_shared ? x0 : x0 + 3 * i, k0 + 3 * i, &r, NULL, &cr);
+        trace_one(&off, x0_shared ? x0 : x0 + 3 * i, k0 + 3 * i, &r, NULL, &cr, NULL);
         memcpy(end + 6 * i, r.end, sizeof(double) * 6);
         if (flags) flags[i] = (uint8_t)r.flags;
         if (n_attempted) n_attempted[i] = r.n_attempted;
@@ -1061,6 +1182,54 @@ int bhgo_trace_crossings(const bhgo_params *p, const double *x0, int x0_shared, 
         if (t_end) t_end[i] = r.t_end;
         n_cross[i] = cr.n;
     }
+    return 0;
+}
+
+/* The trace with a triangle mesh as one more terminal event (the mesh_t rule above): V [nv][3], F [nt][3] (indices into V).
+   end / flags / n_attempted / n_accepted as bhgo_trace (counts up to and including the hit step); tri [n] the triangle of a
+   BHGO_FLAG_HIT_OBJECT ray, -1 otherwise; bary [n][2] the plane coordinates of the refined point in it, NaN otherwise; M_hit [n]
+   the sub-chord count of the step that holds the hit, 0 otherwise.  Brute force over all nt triangles for every sub-chord.
+   Refused (-2), as the library refuses it: fixed-step RK4, time_like, object spheres, a max_chord that is not a positive finite
+   number; (-1): a missing array, no triangle, an index outside [0, nv). */
+int bhgo_trace_mesh(const bhgo_params *p, const double *x0, int x0_shared, const double *k0, size_t n, const double *V, size_t nv,
+                    const int32_t *F, size_t nt, double max_chord, double *end, uint8_t *flags, uint32_t *n_attempted,
+                    uint32_t *n_accepted, int32_t *tri, double *bary, uint32_t *M_hit, int n_threads)
+{
+    if (!p || !x0 || !k0 || !end || !V || !F || !tri || !bary || nt == 0 || nv == 0) return -1;
+    if (p->method != BHGO_METHOD_DP54 || p->time_like || p->n_spheres > 0 || !(max_chord > 0.0) || !isfinite(max_chord)) return -2;
+    for (size_t j = 0; j < 3 * nt; j++)
+        if (F[j] < 0 || (size_t)F[j] >= nv) return -1;
+    double *T = (double *)malloc(sizeof(double) * 9 * nt);
+    if (!T) return -3;
+    for (size_t j = 0; j < nt; j++) {
+        const double *a = V + 3 * (size_t)F[3 * j], *b = V + 3 * (size_t)F[3 * j + 1], *c = V + 3 * (size_t)F[3 * j + 2];
+        for (int q = 0; q < 3; q++) {
+            T[9 * j + q] = a[q];
+            T[9 * j + 3 + q] = b[q] - a[q];
+            T[9 * j + 6 + q] = c[q] - a[q];
+        }
+    }
+#ifdef _OPENMP
+    if (n_threads <= 0) n_threads = omp_get_max_threads();
+#else
+    n_threads = 1;
+#endif
+    long long nn = (long long)n;
+#pragma omp parallel for schedule(dynamic, 8) num_threads(n_threads)
+    for (long long i = 0; i < nn; i++) {
+        ray_result r;
+        mesh_t ms = {T, nt, max_chord, -1, {NAN, NAN}, 0};
+        trace_one(p, x0_shared ? x0 : x0 + 3 * i, k0 + 3 * i, &r, NULL, NULL, &ms);
+        memcpy(end + 6 * i, r.end, sizeof(double) * 6);
+        if (flags) flags[i] = (uint8_t)r.flags;
+        if (n_attempted) n_attempted[i] = r.n_attempted;
+        if (n_accepted) n_accepted[i] = r.n_accepted;
+        tri[i] = ms.tri;
+        bary[2 * i] = ms.bary[0];
+        bary[2 * i + 1] = ms.bary[1];
+        if (M_hit) M_hit[i] = ms.M;
+    }
+    free(T);
     return 0;
 }
 
@@ -1076,7 +1245,7 @@ int bhgo_trajectory(const bhgo_params *p, const double *x0, int x0_shared, const
     for (long long i = 0; i < nn; i++) {
         ray_result r;
         sampler_t sm = {T, 0, p->lambda_end, traj + (size_t)i * 6 * (size_t)T};
-        trace_one(p, x0_shared ? x0 : x0 + 3 * i, k0 + 3 * i, &r, &sm, NULL);
+        trace_one(p, x0_shared ? x0 : x0 + 3 * i, k0 + 3 * i, &r, &sm, NULL, NULL);
         n_valid[i] = sm.next;
         if (flags) flags[i] = (uint8_t)r.flags;
     }

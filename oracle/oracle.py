@@ -106,6 +106,10 @@ def lib():
         L.bhgo_trace_crossings.argtypes = [C.POINTER(Params), dp, C.c_int, dp, C.c_size_t, C.c_uint32, dp, C.POINTER(C.c_uint8),
                                            C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), dp, C.POINTER(C.c_uint32), dp, dp,
                                            C.c_int]
+        L.bhgo_trace_mesh.restype = C.c_int
+        L.bhgo_trace_mesh.argtypes = [C.POINTER(Params), dp, C.c_int, dp, C.c_size_t, dp, C.c_size_t, C.POINTER(C.c_int32), C.c_size_t,
+                                      C.c_double, dp, C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                      C.POINTER(C.c_int32), dp, C.POINTER(C.c_uint32), C.c_int]
         L.bhgo_num_threads.restype = C.c_int
         _lib = L
     return _lib
@@ -175,6 +179,36 @@ def trace_crossings(k0, x0, max_records=16, n_threads=0, **kw):
         raise RuntimeError(f"bhgo_trace_crossings failed: {rc}")
     return {"end": end, "flags": flags, "n_attempted": natt, "n_accepted": nacc, "t_end": tend, "n_cross": ncr, "cross": cross,
             "t_cross": tcr}
+
+
+def trace_mesh(k0, x0, V, F, max_chord, n_threads=0, **kw):
+    """The trace with a triangle mesh V[nv,3], F[nt,3] as one more terminal event (brute force over all
+    triangles): what trace() returns without t_end, plus tri[N] (int32, -1: no hit), bary[N,2] (NaN: no hit) and M[N] (the
+    sub-chord count of the step that holds the hit, 0 otherwise)."""
+    p = kw.pop("params", None) or make_params(**kw)
+    k0 = np.ascontiguousarray(np.atleast_2d(k0), dtype=np.float64)
+    x0 = np.ascontiguousarray(x0, dtype=np.float64)
+    V = np.ascontiguousarray(V, dtype=np.float64).reshape(-1, 3)
+    F = np.ascontiguousarray(F, dtype=np.int32).reshape(-1, 3)
+    n = k0.shape[0]
+    shared = 1 if x0.ndim == 1 else 0
+    if not shared:
+        assert x0.shape == (n, 3)
+    end = np.empty((n, 6))
+    flags = np.empty(n, np.uint8)
+    natt = np.empty(n, np.uint32)
+    nacc = np.empty(n, np.uint32)
+    tri = np.empty(n, np.int32)
+    bary = np.empty((n, 2))
+    m_hit = np.empty(n, np.uint32)
+    u32 = C.POINTER(C.c_uint32)
+    rc = lib().bhgo_trace_mesh(C.byref(p), _dp(x0), shared, _dp(k0), n, _dp(V), len(V), F.ctypes.data_as(C.POINTER(C.c_int32)), len(F),
+                               float(max_chord), _dp(end), flags.ctypes.data_as(C.POINTER(C.c_uint8)), natt.ctypes.data_as(u32),
+                               nacc.ctypes.data_as(u32), tri.ctypes.data_as(C.POINTER(C.c_int32)), _dp(bary), m_hit.ctypes.data_as(u32),
+                               n_threads)
+    if rc != 0:
+        raise RuntimeError(f"bhgo_trace_mesh failed: {rc}")
+    return {"end": end, "flags": flags, "n_attempted": natt, "n_accepted": nacc, "tri": tri, "bary": bary, "M": m_hit}
 
 
 def trajectory(k0, x0, n_points, **kw):
