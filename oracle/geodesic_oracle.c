@@ -596,12 +596,70 @@ typedef struct {
     uint32_t max_records, n;
     size_t stride; /* rays per layer: record m at rec[m * stride * 6], time at t[m * stride] */
     double *rec, *t;
+    /* bhgo_travel_time only (timed != 0): the coordinate time of DESIGN.md section 18.  tt is the sum over the accepted steps so
+       far, E the Schwarzschild ray's energy at its own start point (Kerr: rayctx's E, L), dt [m * stride] the time of record m */
+    int timed;
+    double tt, E;
+    double *dt;
 } crossings_t;
 
-static void crossings_step(crossings_t *cr, const evfun_t *base, const double y_old[6], const double y_new[6], double t_old,
-                           double t, double t_terminal)
+/* numpy.polynomial.legendre.leggauss(6) mapped to [0, 1], the kernel's 17-digit literals (GL6_X, GL6_W) */
+static const double GL6_X_[6] = {0.033765242898423975, 0.16939530676686776, 0.38069040695840151,
+                                 0.61930959304159849, 0.83060469323313224, 0.96623475710157603};
+static const double GL6_W_[6] = {0.085662246189584873, 0.18038078652406947, 0.23395696728634569,
+                                 0.23395696728634569, 0.18038078652406947, 0.085662246189584873};
+
+/* dt/dlambda in Boyer-Lindquist coordinates: kerr_rhs.inc's kt, which does not depend on the velocities */
+static double kt_kerr_bl(const rayctx *rc, const double y[6])
+{
+    const double r = y[1], th = y[3], ur = y[0], uth = y[2], uph = y[4];
+    const double E = rc->E, L = rc->L, M = rc->M, a = rc->a;
+    double ar, ath, aph, ktv;
+#define KERR_RCP3(o0, x0, o1, x1, o2, x2) const double o0 = 1.0 / (x0), o1 = 1.0 / (x1), o2 = 1.0 / (x2)
+#define KERR_SIN(x) sin(x)
+#define KERR_COS(x) cos(x)
+#include "kerr_rhs.inc"
+#undef KERR_RCP3
+#undef KERR_SIN
+#undef KERR_COS
+    (void)ar;
+    (void)ath;
+    (void)aph;
+    return ktv;
+}
+
+/* 6-point Gauss-Legendre of dt/dlambda on [d->t_old, d->t_old + w], on the step's dense-output position; a node at
+   r <= r_hor makes the rule +inf */
+static double time_rule(const bhgo_params *p, const rayctx *rc, double E, const dense_t *d, double w)
+{
+    double sum = 0.0;
+    int inside = 0;
+    for (int k = 0; k < 6; k++) {
+        double y[6];
+        dense_eval(d, d->t_old + w * GL6_X_[k], y);
+        const double r = radius(rc, y);
+        if (r <= rc->r_hor) inside = 1;
+        const double rate = rc->kerr ? kt_kerr_bl(rc, y) : E / (1.0 - p->r_s / r);
+        sum += GL6_W_[k] * rate;
+    }
+    return inside ? INFINITY : w * sum;
+}
+
+/* the Schwarzschild ray's conserved energy from its own start: E = sqrt(f0 (|k0|^2 + h0 (n0.k0)^2)) */
+static double energy_schw(const double x0[3], const double k0[3], double r_s)
+{
+    const double r0 = sqrt(x0[0] * x0[0] + x0[1] * x0[1] + x0[2] * x0[2]);
+    const double f0 = 1.0 - r_s / r0, h0 = r_s / (r0 - r_s);
+    const double nk = (x0[0] * k0[0] + x0[1] * k0[1] + x0[2] * k0[2]) / r0;
+    const double kk = k0[0] * k0[0] + k0[1] * k0[1] + k0[2] * k0[2];
+    return sqrt(f0 * (kk + h0 * nk * nk));
+}
+
+static void crossings_step(const bhgo_params *p, crossings_t *cr, const evfun_t *base, const double y_old[6], const double y_new[6],
+                           double t_old, double t, double t_terminal)
 {
     const int kerr = e_kerr(base);
+    if (!(cr->r_out > 0.0)) return; /* (bhgo_travel_time with the disk off) */
     const double z_old = kerr ? cos(y_old[3]) : y_old[5], z_new = kerr ? cos(y_new[3]) : y_new[5];
     if (!(((z_old <= 0) && (z_new >= 0)) || ((z_old >= 0) && (z_new <= 0)))) return;
     evfun_t e = *base;
@@ -614,6 +672,8 @@ static void crossings_step(crossings_t *cr, const evfun_t *base, const double y_
     if (cr->n < cr->max_records) {
         pack_end(y, cr->rec + (size_t)cr->n * cr->stride * 6);
         cr->t[(size_t)cr->n * cr->stride] = r;
+        /* the time at the start of the step plus the rule on [t_old, root] */
+        if (cr->timed) cr->dt[(size_t)cr->n * cr->stride] = cr->tt + time_rule(p, base->rc, cr->E, base->dn, r - t_old);
     }
     cr->n++;
 }
@@ -736,6 +796,7 @@ static void trace_dp54(const bhgo_params *p, const rayctx *rc, const double x0[3
     double y[6] = {k0[0], x0[0], k0[1], x0[1], k0[2], x0[2]};
     double f[6], K[7][6], y_new[6], f_new[6];
     const double t_bound = p->lambda_end;
+    if (cr && cr->timed && !rc->kerr) cr->E = energy_schw(x0, k0, p->r_s);
     double t = 0.0;
     memset(res, 0, sizeof(*res));
     res->object_id = -1;
@@ -830,7 +891,9 @@ static void trace_dp54(const bhgo_params *p, const rayctx *rc, const double x0[3
         double t_root = t, y_root[6];
         uint32_t fl = 0;
         if (any) fl = check_events(p, g_h, g_h_new, g_e, g_e_new, y_old, y, &base, t_old, t, &t_root, y_root, &res->object_id);
-        if (cr) crossings_step(cr, &base, y_old, y, t_old, t, fl ? t_root : INFINITY);
+        if (cr) crossings_step(p, cr, &base, y_old, y, t_old, t, fl ? t_root : INFINITY);
+        /* the step's share of the coordinate time, in step order; the step that holds the terminal event runs to its root */
+        if (cr && cr->timed) cr->tt += time_rule(p, rc, cr->E, &dn, (fl ? t_root : t) - t_old);
         if (ms) {
             double t_hit;
             if (mesh_step(ms, &base, y_old, y, t_old, t, fl != 0, t_root, &t_hit)) {
@@ -1173,7 +1236,7 @@ int bhgo_trace_crossings(const bhgo_params *p, const double *x0, int x0_shared, 
 #pragma omp parallel for schedule(dynamic, 256) num_threads(n_threads)
     for (long long i = 0; i < nn; i++) {
         ray_result r;
-        crossings_t cr = {p->disk_r_in, p->disk_r_out, max_records, 0, n, cross + 6 * i, t_cross + i};
+        crossings_t cr = {p->disk_r_in, p->disk_r_out, max_records, 0, n, cross + 6 * i, t_cross + i, 0, 0.0, 0.0, NULL};
         trace_one(&off, x0_shared ? x0 : x0 + 3 * i, k0 + 3 * i, &r, NULL, &cr, NULL);
         memcpy(end + 6 * i, r.end, sizeof(double) * 6);
         if (flags) flags[i] = (uint8_t)r.flags;
@@ -1181,6 +1244,48 @@ int bhgo_trace_crossings(const bhgo_params *p, const double *x0, int x0_shared, 
         if (n_accepted) n_accepted[i] = r.n_accepted;
         if (t_end) t_end[i] = r.t_end;
         n_cross[i] = cr.n;
+    }
+    return 0;
+}
+
+/* bhgo_trace_crossings plus the coordinate time along each ray (time_rule above): dt_end [n] the time to
+   the ray's end, dt_cross [max_records][n] the times of the records kept (left alone beyond them).  t_end / t_cross stay the
+   affine parameter.  A ray that ends on the horizon or starts inside has dt_end = +inf, a ray flagged NaN has NaN, a ray that
+   gave up (MAX_STEPS, STEP_TOO_SMALL) the sum so far; a node at r <= r_hor makes the sum, and with it every later time, +inf.
+   The disk may be off when max_records = 0 (cross, t_cross, dt_cross may then be NULL); otherwise refused as
+   bhgo_trace_crossings refuses. */
+int bhgo_travel_time(const bhgo_params *p, const double *x0, int x0_shared, const double *k0, size_t n, uint32_t max_records,
+                     double *end, uint8_t *flags, uint32_t *n_attempted, uint32_t *n_accepted, double *t_end, uint32_t *n_cross,
+                     double *cross, double *t_cross, double *dt_end, double *dt_cross, int n_threads)
+{
+    if (!p || !x0 || !k0 || !end || !n_cross || !dt_end) return -1;
+    if (max_records > 0 && (!cross || !t_cross || !dt_cross)) return -1;
+    if (p->method != BHGO_METHOD_DP54 || p->time_like || p->n_spheres > 0) return -2;
+    if (max_records > 0 && !(p->disk_r_out > 0.0)) return -2;
+    bhgo_params off = *p;
+    off.disk_r_in = off.disk_r_out = 0.0;
+#ifdef _OPENMP
+    if (n_threads <= 0) n_threads = omp_get_max_threads();
+#else
+    n_threads = 1;
+#endif
+    long long nn = (long long)n;
+#pragma omp parallel for schedule(dynamic, 256) num_threads(n_threads)
+    for (long long i = 0; i < nn; i++) {
+        ray_result r;
+        crossings_t cr = {p->disk_r_in, p->disk_r_out, max_records, 0, n, max_records ? cross + 6 * i : NULL,
+                          max_records ? t_cross + i : NULL, 1, 0.0, 0.0, max_records ? dt_cross + i : NULL};
+        trace_one(&off, x0_shared ? x0 : x0 + 3 * i, k0 + 3 * i, &r, NULL, &cr, NULL);
+        memcpy(end + 6 * i, r.end, sizeof(double) * 6);
+        if (flags) flags[i] = (uint8_t)r.flags;
+        if (n_attempted) n_attempted[i] = r.n_attempted;
+        if (n_accepted) n_accepted[i] = r.n_accepted;
+        if (t_end) t_end[i] = r.t_end;
+        n_cross[i] = cr.n;
+        double tt = cr.tt;
+        if (r.flags & (BHGO_FLAG_HIT_HORIZON | BHGO_FLAG_START_INSIDE)) tt = INFINITY;
+        if (r.flags & BHGO_FLAG_NAN) tt = NAN;
+        dt_end[i] = tt;
     }
     return 0;
 }

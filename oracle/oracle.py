@@ -106,6 +106,10 @@ def lib():
         L.bhgo_trace_crossings.argtypes = [C.POINTER(Params), dp, C.c_int, dp, C.c_size_t, C.c_uint32, dp, C.POINTER(C.c_uint8),
                                            C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), dp, C.POINTER(C.c_uint32), dp, dp,
                                            C.c_int]
+        L.bhgo_travel_time.restype = C.c_int
+        L.bhgo_travel_time.argtypes = [C.POINTER(Params), dp, C.c_int, dp, C.c_size_t, C.c_uint32, dp, C.POINTER(C.c_uint8),
+                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), dp, C.POINTER(C.c_uint32), dp, dp, dp, dp,
+                                       C.c_int]
         L.bhgo_trace_mesh.restype = C.c_int
         L.bhgo_trace_mesh.argtypes = [C.POINTER(Params), dp, C.c_int, dp, C.c_size_t, dp, C.c_size_t, C.POINTER(C.c_int32), C.c_size_t,
                                       C.c_double, dp, C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
@@ -179,6 +183,40 @@ def trace_crossings(k0, x0, max_records=16, n_threads=0, **kw):
         raise RuntimeError(f"bhgo_trace_crossings failed: {rc}")
     return {"end": end, "flags": flags, "n_attempted": natt, "n_accepted": nacc, "t_end": tend, "n_cross": ncr, "cross": cross,
             "t_cross": tcr}
+
+
+def travel_time(k0, x0, max_records=4, n_threads=0, **kw):
+    """trace_crossings plus the coordinate time along each ray: dt_end[N] (+inf on horizon and start-inside
+    rays and after a quadrature node at r <= r_hor, NaN on rays flagged NaN, the sum so far on rays that gave up) and
+    dt_cross[max_records, N] (NaN where there is no record).  t_end / t_cross stay the affine parameter.  max_records = 0 with the
+    disk off is allowed, as in the library."""
+    p = kw.pop("params", None) or make_params(**kw)
+    k0 = np.ascontiguousarray(np.atleast_2d(k0), dtype=np.float64)
+    x0 = np.ascontiguousarray(x0, dtype=np.float64)
+    n = k0.shape[0]
+    shared = 1 if x0.ndim == 1 else 0
+    if not shared:
+        assert x0.shape == (n, 3)
+    K = int(max_records)
+    end = np.empty((n, 6))
+    flags = np.empty(n, np.uint8)
+    natt = np.empty(n, np.uint32)
+    nacc = np.empty(n, np.uint32)
+    tend = np.empty(n)
+    ncr = np.zeros(n, np.uint32)
+    cross = np.full((K, n, 6), np.nan)
+    tcr = np.full((K, n), np.nan)
+    dte = np.empty(n)
+    dtc = np.full((K, n), np.nan)
+    u32 = C.POINTER(C.c_uint32)
+    some = (lambda a: _dp(a)) if K else (lambda a: None)
+    rc = lib().bhgo_travel_time(C.byref(p), _dp(x0), shared, _dp(k0), n, K, _dp(end), flags.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                natt.ctypes.data_as(u32), nacc.ctypes.data_as(u32), _dp(tend), ncr.ctypes.data_as(u32), some(cross),
+                                some(tcr), _dp(dte), some(dtc), n_threads)
+    if rc != 0:
+        raise RuntimeError(f"bhgo_travel_time failed: {rc}")
+    return {"end": end, "flags": flags, "n_attempted": natt, "n_accepted": nacc, "t_end": tend, "n_cross": ncr, "cross": cross,
+            "t_cross": tcr, "dt_end": dte, "dt_cross": dtc}
 
 
 def trace_mesh(k0, x0, V, F, max_chord, n_threads=0, **kw):

@@ -37,10 +37,12 @@ def _ffi():
     return f
 
 
-def _travel_time_device(ctx, p, k0, x0, K):
-    """bhg_travel_time_device on sentinel-filled arrays -> dict of host arrays."""
+def _travel_time_device(ctx, p, k0, x0, K, layers_allocated=None):
+    """bhg_travel_time_device on sentinel-filled arrays -> dict of host arrays (cross, t_cross: the K layers asked for, or all
+    layers_allocated of a larger allocation)."""
     import torch
     n = len(k0)
+    L = max(K, 1) if layers_allocated is None else layers_allocated
     d_k0 = torch.as_tensor(np.ascontiguousarray(k0)).cuda()
     shared = np.asarray(x0).ndim == 1
     d_x0 = None if shared else torch.as_tensor(np.ascontiguousarray(x0)).cuda()
@@ -48,8 +50,8 @@ def _travel_time_device(ctx, p, k0, x0, K):
     d_fl = torch.full((n,), 255, dtype=torch.uint8, device="cuda")
     d_st = torch.full((n,), -1, dtype=torch.int32, device="cuda")
     d_ac = torch.full((n,), -1, dtype=torch.int32, device="cuda")
-    d_cr = torch.full((max(K, 1), n, 6), SENTINEL, dtype=torch.float64, device="cuda")
-    d_tc = torch.full((max(K, 1), n), SENTINEL, dtype=torch.float64, device="cuda")
+    d_cr = torch.full((L, n, 6), SENTINEL, dtype=torch.float64, device="cuda")
+    d_tc = torch.full((L, n), SENTINEL, dtype=torch.float64, device="cuda")
     d_nc = torch.full((n,), 255, dtype=torch.uint8, device="cuda")
     d_te = torch.full((n,), SENTINEL, dtype=torch.float64, device="cuda")
     try:
@@ -59,9 +61,10 @@ def _travel_time_device(ctx, p, k0, x0, K):
                                d_n_steps=d_st.data_ptr(), d_n_accepted=d_ac.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
     finally:
         torch.cuda.synchronize()
+    keep = K if layers_allocated is None else L
     return dict(end=d_end.cpu().numpy(), flags=d_fl.cpu().numpy(), steps=d_st.cpu().numpy().astype(np.uint32),
-                acc=d_ac.cpu().numpy().astype(np.uint32), cross=d_cr.cpu().numpy()[:K], n_cross=d_nc.cpu().numpy(),
-                t_end=d_te.cpu().numpy(), t_cross=d_tc.cpu().numpy()[:K])
+                acc=d_ac.cpu().numpy().astype(np.uint32), cross=d_cr.cpu().numpy()[:keep], n_cross=d_nc.cpu().numpy(),
+                t_end=d_te.cpu().numpy(), t_cross=d_tc.cpu().numpy()[:keep])
 
 
 def _crossings_device(ctx, p, k0, x0, K):

@@ -55,7 +55,7 @@ class _Ray:
         k0, x0 = np.asarray(k0, float), np.asarray(x0, float)
         self.k0, self.x0, self.r_s, self.spin = k0, x0, r_s, spin
         if self.kerr:
-            assert r_exit == 0.0                     # (scipy_reference's Kerr solve has no exit sphere)
+            # (scipy_reference's own Kerr solve has no exit sphere; the solves below carry one as an event on Boyer-Lindquist r)
             M, a = 0.5 * r_s, spin
             fn = sr.kerr_rhs_lambdified()
             q0, u0 = sr.cart_to_bl(x0, k0, a)
