@@ -25,6 +25,7 @@
 #include "geodesic_kernels.h"
 #include "prefix_clearance.h"
 #include "mesh_bvh.h"
+#include "trace_call.h"
 
 static_assert(BHG_FLAG_HIT_HORIZON == bhg::BHG_FLAG_HIT_HORIZON_, "flag mismatch");
 static_assert(BHG_FLAG_START_INSIDE == bhg::BHG_FLAG_START_INSIDE_, "flag mismatch");
@@ -78,6 +79,12 @@ int fail_hip(hipError_t e, const char *what)
     do {                                                \
         hipError_t _e = (expr);                         \
         if (_e != hipSuccess) return fail_hip(_e, #expr); \
+    } while (0)
+// ... and a refusal or failure of one of the library's own checks and calls: handed on as it is
+#define BHG_TRY(expr)                      \
+    do {                                   \
+        const int _rc = (expr);            \
+        if (_rc != BHG_OK) return _rc;     \
     } while (0)
 
 }  // namespace
@@ -434,8 +441,7 @@ int thermal_check(const bhg_disk_thermal *th)
 // < 0: no disk to check (none in the scene, or the disk class is not asked for).  Also used by bhgeo_frame.hip.
 int redshift_params(const bhg_params *p, const bhg_redshift *rs, double disk_r_in, const double *x0, RedshiftParams *out)
 {
-    int rc = validate(p);
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(validate(p));
     if (!rs) return fail(BHG_E_INVALID, "redshift settings are NULL");
     if (rs->apply & ~(BHG_REDSHIFT_DISK | BHG_REDSHIFT_OBJECTS | BHG_REDSHIFT_SKY))
         return fail(BHG_E_INVALID, "redshift apply has bits outside BHG_REDSHIFT_DISK | _OBJECTS | _SKY: " + std::to_string(rs->apply));
@@ -513,8 +519,7 @@ int camera_position_check(const bhg_params *p, const double *x0, const char *who
 // bhgeo_frame.hip.
 int observer_params(const bhg_params *p, const bhg_observer *obs, const double *x0, ObserverParams *out)
 {
-    int rc = validate(p);
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(validate(p));
     if (!obs) return fail(BHG_E_INVALID, "observer is NULL");
     const double *b = obs->beta;
     if (!(std::isfinite(b[0]) && std::isfinite(b[1]) && std::isfinite(b[2])))
@@ -528,8 +533,7 @@ int observer_params(const bhg_params *p, const bhg_observer *obs, const double *
     if (p->time_like) return fail(BHG_E_INVALID, "the observer camera makes null rays: time_like = 1 is refused");
     std::memset(out, 0, sizeof(*out));
     if (x0) {
-        rc = camera_position_check(p, x0, "observer");
-        if (rc != BHG_OK) return rc;
+        BHG_TRY(camera_position_check(p, x0, "observer"));
         std::memcpy(out->x0, x0, sizeof(out->x0));
     }
     std::memcpy(out->beta, b, sizeof(out->beta));
@@ -546,8 +550,7 @@ int observer_params(const bhg_params *p, const bhg_observer *obs, const double *
 int polarisation_params(const bhg_params *p, const bhg_polarisation *pol, const bhg_redshift *rs, const bhg_observer *obs,
                         double disk_r_in, const double *x0, PolarisationParams *out)
 {
-    int rc = validate(p);
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(validate(p));
     if (!pol) return fail(BHG_E_INVALID, "polarisation settings are NULL");
     if (pol->disk_sense != 1 && pol->disk_sense != -1)
         return fail(BHG_E_INVALID, "polarisation disk_sense must be +1 or -1, not " + std::to_string(pol->disk_sense));
@@ -578,10 +581,7 @@ int polarisation_params(const bhg_params *p, const bhg_polarisation *pol, const 
     if (rs && rs->disk_sense != pol->disk_sense)
         return fail(BHG_E_INVALID, "polarisation disk_sense " + std::to_string(pol->disk_sense) + " differs from the redshift's " +
                                    std::to_string(rs->disk_sense));
-    if (x0) {
-        rc = camera_position_check(p, x0, "polarisation");
-        if (rc != BHG_OK) return rc;
-    }
+    if (x0) BHG_TRY(camera_position_check(p, x0, "polarisation"));
     std::memset(out, 0, sizeof(*out));
     std::memcpy(out->degree, pol->degree, sizeof(double) * (size_t)pol->n_degree);
     std::memcpy(out->up, pol->up, sizeof(out->up));
@@ -661,11 +661,9 @@ void thermal_constants(double astar, ThermalParams *T)
 int thermal_params(const bhg_params *p, const bhg_disk_thermal *th, const bhg_redshift *rs, const bhg_polarisation *pol,
                    double disk_r_in, const double *x0, ThermalParams *out, RedshiftParams *rp)
 {
-    int rc = validate(p);
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(validate(p));
     if (!th) return fail(BHG_E_INVALID, "disk thermal settings are NULL");
-    rc = thermal_check(th);
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(thermal_check(th));
     if (p->time_like) return fail(BHG_E_INVALID, "the thermal disk is seen by null rays: time_like = 1 is refused");
     const double M = 0.5 * p->r_s, a = p->rhs_form == BHG_RHS_KERR_BL ? p->spin : 0.0, s = -(double)th->disk_sense;
     if (disk_r_in >= 0.0) {
@@ -685,10 +683,7 @@ int thermal_params(const bhg_params *p, const bhg_disk_thermal *th, const bhg_re
     if (pol && pol->disk_sense != th->disk_sense)
         return fail(BHG_E_INVALID, "disk thermal disk_sense " + std::to_string(th->disk_sense) + " differs from the polarisation's " +
                                    std::to_string(pol->disk_sense));
-    if (x0) {
-        rc = camera_position_check(p, x0, "disk thermal");
-        if (rc != BHG_OK) return rc;
-    }
+    if (x0) BHG_TRY(camera_position_check(p, x0, "disk thermal"));
     std::memset(out, 0, sizeof(*out));
     thermal_constants(s * a / M, out);
     out->r_ms *= M;
@@ -735,10 +730,8 @@ int motion_check(const bhg_object_motion *mo, int32_t n_spheres)
 // bhgeo_frame.hip.
 int motion_params(const bhg_params *p, const bhg_object_motion *mo, const double *spheres, int32_t n_spheres, MotionParams *out)
 {
-    int rc = motion_check(mo, n_spheres);
-    if (rc != BHG_OK) return rc;
-    rc = validate(p);
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(motion_check(mo, n_spheres));
+    BHG_TRY(validate(p));
     std::memset(out, 0, sizeof(*out));
     const int n = n_spheres < 0 ? 0 : (n_spheres > BHG_MAX_SPHERES ? BHG_MAX_SPHERES : n_spheres);
     const bool kerr = p->rhs_form == BHG_RHS_KERR_BL;
@@ -1056,6 +1049,18 @@ int bhg_last_launch(bhg_context *c, int32_t out[4])
 
 }  // extern "C"
 
+// a mesh on one device: the flattened tree of mesh_bvh.h, the triangles in leaf order, the maps between
+// the two numberings
+struct bhg_mesh {
+    int device = 0;
+    char *d = nullptr;        // one allocation
+    bhg::MeshView view{};
+    int64_t n_nodes = 0;
+    int32_t depth = 0;
+    double box[6] = {0, 0, 0, 0, 0, 0};
+    double d_min = 0.0, d_max = 0.0;
+};
+
 namespace {
 
 int validate_spheres(const bhg_params *p, const double *spheres, int32_t n_spheres)
@@ -1071,35 +1076,25 @@ int validate_spheres(const bhg_params *p, const double *spheres, int32_t n_spher
     return BHG_OK;
 }
 
-// where a crossings trace (bhg_trace_crossings_device) puts its records: the layer stride is the CALL's ray count
-struct CrossOut {
-    double *cross;
-    uint8_t *n_cross;
-    int32_t max_cross;
-    size_t stride;
-    // a travel-time call (bhg_travel_time_device): t_end non-null, t_cross [max_cross][stride] beside cross; cross, n_cross and
-    // t_cross may then be null with max_cross = 0
-    double *t_end = nullptr;
-    double *t_cross = nullptr;
-    // a mesh trace (bhg_trace_mesh_device): the mesh and its two outputs; nothing above is used then
-    const bhg::MeshArgs *mesh = nullptr;
-};
+using bhg::TraceCall;
+using bhg::TraceKind;
 
-// ONE launch: n <= BHG_MAX_RAYS_PER_LAUNCH rays (the kernels form a ray's byte offsets in 32 bits).
-// d_end [n][6], or -- d_end == nullptr -- d_end_dir [n][3]: only the direction half of the final states is produced
-// cr: nullptr, or the call is a crossings trace -- the lane-per-ray kernel instead of the persistent one (the caller has checked
-// what that kernel does not cover)
-int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres, int32_t n_spheres,
-                     const double *x0_shared, const double *d_x0, const double *d_k0, size_t n, double *d_end,
-                     uint8_t *d_flags, uint32_t *d_n_steps, uint32_t *d_n_accepted, int8_t *d_object_id, void *stream,
-                     double *d_end_dir, double *d_start_steps, int32_t start_mode, const CrossOut *cr = nullptr,
-                     bhg_prefix *pf = nullptr)
+// ONE launch: tc.n <= BHG_MAX_RAYS_PER_LAUNCH rays (the kernels form a ray's byte offsets in 32 bits).
+// tc.kind other than PERSISTENT: a lane-per-ray kernel instead of the persistent one (the caller has checked what that kernel
+// does not cover)
+int trace_device_one(bhg_context *c, const bhg_params *p, const TraceCall &tc)
 {
+    const double *const spheres = tc.spheres, *const x0_shared = tc.x0_shared, *const d_x0 = tc.d_x0, *const d_k0 = tc.d_k0;
+    const int32_t n_spheres = tc.n_spheres, start_mode = tc.start_mode;
+    const size_t n = tc.n;
+    double *d_end = tc.d_end, *d_end_dir = tc.d_end_dir;
+    uint8_t *const d_flags = tc.d_flags;
+    uint32_t *const d_n_steps = tc.d_n_steps, *const d_n_accepted = tc.d_n_accepted;
+    bhg_prefix *const pf = tc.prefix;
+    const bool lanes = tc.kind != TraceKind::PERSISTENT;
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
-    int rc = validate(p);
-    if (rc != BHG_OK) return rc;
-    rc = validate_spheres(p, spheres, n_spheres);
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(validate(p));
+    BHG_TRY(validate_spheres(p, spheres, n_spheres));
     if (pf) {
         pf->used = BHG_PREFIX_NONE;
         if (pf->mode != BHG_PREFIX_NONE && pf->mode != BHG_PREFIX_RECORD && pf->mode != BHG_PREFIX_REPLAY &&
@@ -1110,12 +1105,12 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres,
     if (start_mode != BHG_START_NONE && start_mode != BHG_START_RECORD && start_mode != BHG_START_REPLAY)
         return fail(BHG_E_INVALID, "start_mode must be BHG_START_NONE, BHG_START_RECORD or BHG_START_REPLAY");
     if (n == 0) return BHG_OK;
-    if (start_mode != BHG_START_NONE && !d_start_steps) return fail(BHG_E_INVALID, "start_mode asks for d_start_steps, which is NULL");
+    if (start_mode != BHG_START_NONE && !tc.d_start_steps) return fail(BHG_E_INVALID, "start_mode asks for d_start_steps, which is NULL");
     if (!d_k0 || (!d_end && !d_end_dir)) return fail(BHG_E_INVALID, "k0 / end is NULL");
     if (!x0_shared && !d_x0) return fail(BHG_E_INVALID, "neither x0_shared nor d_x0 given");
     if (n > bhg::BHG_MAX_RAYS_PER_LAUNCH) return fail(BHG_E_INVALID, "internal: more rays than one launch takes");
     ENTER_DEVICE(c->device);
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = (hipStream_t)tc.stream;
     // Launches of one context share its work counters (launch K zeroes the set launch K + 1 counts on) and its workspace:
     // they must execute in the order they were issued.  On ONE stream they do; a call that arrives on ANOTHER stream than
     // the previous one is ordered behind it here (an event on the old stream, a wait on the new one) -- it then cannot
@@ -1142,13 +1137,11 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres,
     const size_t sz_u32 = n * sizeof(uint32_t);
     const size_t sz_steps = !d_n_steps ? sz_u32 : 0;
     const size_t sz_acc = !d_n_accepted ? sz_u32 : 0;
-    rc = ensure(&c->d_ws, &c->d_ws_bytes, sz_flags + sz_steps + sz_acc + 64);
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(ensure(&c->d_ws, &c->d_ws_bytes, sz_flags + sz_steps + sz_acc + 64));
     if (!d_end && kerr) {
         // direction-only Kerr call: the end records are workspace (the Boyer-Lindquist states the finalize pass converts),
         // final directions are split off into d_end_dir afterwards
-        rc = ensure(&c->d_endws, &c->d_endws_bytes, n * 6 * sizeof(double) + 64);
-        if (rc != BHG_OK) return rc;
+        BHG_TRY(ensure(&c->d_endws, &c->d_endws_bytes, n * 6 * sizeof(double) + 64));
         d_end = (double *)c->d_endws;
     } else if (d_end) {
         d_end_dir = nullptr;
@@ -1190,16 +1183,16 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres,
         a.order_blocks = (int32_t)p->order_blocks;
         a.order_block_len = n / p->order_blocks;
     }
-    a.object_id = d_object_id;
+    a.object_id = tc.d_object_id;
     // the rays' initial steps kept by their owner (the DP5(4) kernels' queue fill; RK4 has none and never looks)
-    a.start_h = start_mode != BHG_START_NONE ? d_start_steps : nullptr;
+    a.start_h = start_mode != BHG_START_NONE ? tc.d_start_steps : nullptr;
     a.start_mode = start_mode;
     // the rays' start-up records kept by their owner: shared-origin calls of DP5(4) with the two Cartesian null forms, one launch
     // (the planes' stride is the launch's n), a step budget the records cannot exhaust.  Anything else ignores them, as RK4
     // ignores the start steps, and says so in pf->used.
     bool pf_record = false, pf_deep = false;
     double pf_rho = 0.0;
-    if (pf && pf->mode != BHG_PREFIX_NONE && !cr && !d_x0 && p->method == BHG_METHOD_DP54 &&
+    if (pf && pf->mode != BHG_PREFIX_NONE && !lanes && !d_x0 && p->method == BHG_METHOD_DP54 &&
         (rhs_id == bhg::BHG_RHS_CHRISTOFFEL_ || rhs_id == bhg::BHG_RHS_REDUCED_) && a.max_steps > (uint32_t)BHG_PREFIX_K_MAX) {
         const double clear = bhg::prefix_clearance(a.r_hor, a.r_exit, a.disk_r_out > 0.0, spheres, n_spheres, x0_shared);
         // (a deep record holds up to BHG_PREFIX_DEEP_ATTEMPTS attempts: neither written nor -- the call cannot tell which rule
@@ -1224,18 +1217,31 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres,
 
     size_t grid = (n + 63) / 64;
     int per_cu = 0;
-    if (cr) {
-        // the crossings trace: one lane per ray, no work counters, no resident-wave count
-        a.cross = cr->cross;
-        a.n_cross = cr->n_cross;
-        a.max_cross = cr->max_cross;
-        a.cross_stride = cr->stride;
-        if (cr->mesh)
-            HIP_TRY(bhg::launch_trace_mesh(a, *cr->mesh, rhs_id, s));
-        else if (cr->t_end)
-            HIP_TRY(bhg::launch_travel_time(a, rhs_id, cr->t_end, cr->t_cross, s));
-        else
+    if (lanes) {
+        // a lane-per-ray trace: no work counters, no resident-wave count
+        a.cross = tc.cross;
+        a.n_cross = tc.n_cross;
+        a.max_cross = tc.max_cross;
+        a.cross_stride = tc.stride;
+        if (tc.kind == TraceKind::MESH) {
+            bhg::MeshArgs g;
+            std::memset(&g, 0, sizeof(g));
+            g.mesh = tc.mesh->view;
+            std::memcpy(g.box, tc.mesh->box, sizeof(g.box));
+            g.d_min = tc.mesh->d_min;
+            g.d_max = tc.mesh->d_max;
+            g.max_chord = tc.max_chord;
+            // BHGEO_MESH_CULL=0: every step of every ray samples its sub-chords (an A/B aid: the results are the same bits)
+            const char *cull = std::getenv("BHGEO_MESH_CULL");
+            g.cull = !(cull && cull[0] == '0' && cull[1] == 0);
+            g.tri_id = tc.tri_id;
+            g.bary = tc.bary;
+            HIP_TRY(bhg::launch_trace_mesh(a, g, rhs_id, s));
+        } else if (tc.kind == TraceKind::TRAVEL_TIME) {
+            HIP_TRY(bhg::launch_travel_time(a, rhs_id, tc.t_end, tc.t_cross, s));
+        } else {
             HIP_TRY(bhg::launch_trace_crossings(a, rhs_id, s));
+        }
         c->ev_valid = false;
     } else {
         // resident waves per CU of the trace kernel variant: asked of the runtime once per variant and context
@@ -1294,7 +1300,7 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres,
     if (p->rhs_form == BHG_RHS_KERR_BL) {
         // (direction-only calls: the finalize pass writes the Cartesian exit directions straight into d_end_dir)
         HIP_TRY(bhg::launch_kerr_finalize(a, d_end_dir, s));
-        if (c->profiling && !cr) {
+        if (c->profiling && !lanes) {
             HIP_TRY(hipEventRecord(c->ev[3], s));
             c->ev_post = true;
         }
@@ -1315,45 +1321,74 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const double *spheres,
 // A trace call of any size: launches of at most BHG_MAX_RAYS_PER_LAUNCH rays, one after the other on the caller's stream
 // (BASELINE's largest frame, 2048 x 2048 x 16 = 2^26 rays, is one launch).  Every ray is its own ODE: the split never
 // changes a result.  The work-order hint describes ONE launch's rays and is dropped for a split call.
-int trace_device_impl(bhg_context *c, const bhg_params *p, const double *spheres, int32_t n_spheres,
-                      const double *x0_shared, const double *d_x0, const double *d_k0, size_t n, double *d_end,
-                      uint8_t *d_flags, uint32_t *d_n_steps, uint32_t *d_n_accepted, int8_t *d_object_id, void *stream,
-                      double *d_end_dir = nullptr, double *d_start_steps = nullptr, int32_t start_mode = BHG_START_NONE,
-                      const CrossOut *cr = nullptr, bhg_prefix *pf = nullptr)
+int trace_device_impl(bhg_context *c, const bhg_params *p, const TraceCall &tc)
 {
-    if (n <= bhg::BHG_MAX_RAYS_PER_LAUNCH)
-        return trace_device_one(c, p, spheres, n_spheres, x0_shared, d_x0, d_k0, n, d_end, d_flags, d_n_steps, d_n_accepted,
-                                d_object_id, stream, d_end_dir, d_start_steps, start_mode, cr, pf);
-    if (pf) pf->used = BHG_PREFIX_NONE;    // (a split call: the records' planes are strided by ONE launch's ray count)
+    const size_t n = tc.n;
+    if (n <= bhg::BHG_MAX_RAYS_PER_LAUNCH) return trace_device_one(c, p, tc);
+    if (tc.prefix) tc.prefix->used = BHG_PREFIX_NONE;    // (a split call: the records' planes are strided by ONE launch's ray count)
     if (!p) return fail(BHG_E_INVALID, "params is NULL");
     if (n > 0xFFFFFFFFull) return fail(BHG_E_INVALID, "n must be < 2^32 per call");
     bhg_params q = *p;
     q.order_blocks = 0;
-    for (size_t off = 0; off < n; off += bhg::BHG_MAX_RAYS_PER_LAUNCH) {
-        const size_t m = std::min((size_t)bhg::BHG_MAX_RAYS_PER_LAUNCH, n - off);
-        // (a crossings trace: this launch's rays sit at offset off inside every layer of the call's record array)
-        CrossOut part{};
-        bhg::MeshArgs part_mesh;
-        if (cr)
-            part = CrossOut{cr->cross ? cr->cross + off * 6 : nullptr, cr->n_cross ? cr->n_cross + off : nullptr, cr->max_cross,
-                            cr->stride, cr->t_end ? cr->t_end + off : nullptr, cr->t_cross ? cr->t_cross + off : nullptr};
-        if (cr && cr->mesh) {
-            part_mesh = *cr->mesh;
-            part_mesh.tri_id += off;
-            part_mesh.bary += off * 2;
-            part.mesh = &part_mesh;
-        }
-        const int rc = trace_device_one(c, &q, spheres, n_spheres, x0_shared, d_x0 ? d_x0 + off * 3 : nullptr,
-                                        d_k0 ? d_k0 + off * 3 : nullptr, m, d_end ? d_end + off * 6 : nullptr,
-                                        d_flags ? d_flags + off : nullptr, d_n_steps ? d_n_steps + off : nullptr,
-                                        d_n_accepted ? d_n_accepted + off : nullptr, d_object_id ? d_object_id + off : nullptr,
-                                        stream, d_end_dir ? d_end_dir + off * 3 : nullptr,
-                                        d_start_steps ? d_start_steps + off : nullptr, start_mode, cr ? &part : nullptr);
-        if (rc != BHG_OK) return rc;
-    }
+    BHG_TRY(bhg::for_each_launch(tc, bhg::BHG_MAX_RAYS_PER_LAUNCH, [&](const TraceCall &part) { return trace_device_one(c, &q, part); }));
     c->last_launch[3] = (int32_t)((n + bhg::BHG_MAX_RAYS_PER_LAUNCH - 1) / bhg::BHG_MAX_RAYS_PER_LAUNCH);
     return BHG_OK;
 }
+
+// The round trip of a plain host-buffer call on the context's stream.  Every array is named once and gets a region of ONE device
+// block (bhg::StageLayout), the call's own or the context's d_in.  run() allocates, uploads, makes the _device call (which takes
+// its arrays from at()), downloads and waits; copies go in the order the arrays were named.  However the call ends, the stream is
+// drained and a block of the call's own is freed.
+class Staged {
+public:
+    static constexpr size_t NONE = ~size_t(0);   // the place of an array that is not there: at() gives null
+    Staged(bhg_context *ctx, bool own_block) : c(ctx), own(own_block) {}
+    ~Staged()
+    {
+        (void)hipStreamSynchronize(c->stream);
+        if (own) (void)hipFree(d);
+    }
+    // an input and an in-out array may be NULL (not there); an output that is NULL is optional: staged, not brought back
+    size_t in(const void *host, size_t bytes) { return host ? add(bytes, host, nullptr) : NONE; }
+    size_t out(void *host, size_t bytes) { return add(bytes, nullptr, host); }
+    size_t inout(void *host, size_t bytes) { return host ? add(bytes, host, host) : NONE; }
+    template <class T>
+    T *at(size_t off) const { return off == NONE ? nullptr : (T *)(d + off); }
+    template <class Call>
+    int run(Call &&device_call)
+    {
+        if (count > MAX) return fail(BHG_E_INVALID, "internal: more staged arrays than a call names");
+        if (own) {
+            HIP_TRY(hipMalloc((void **)&d, layout.total()));
+        } else {
+            BHG_TRY(ensure(&c->d_in, &c->d_in_bytes, layout.total()));
+            d = (char *)c->d_in;
+        }
+        for (int i = 0; i < count; i++)
+            if (r[i].up) HIP_TRY(hipMemcpyAsync(d + r[i].off, r[i].up, r[i].bytes, hipMemcpyHostToDevice, c->stream));
+        BHG_TRY(device_call());
+        for (int i = 0; i < count; i++)
+            if (r[i].down) HIP_TRY(hipMemcpyAsync(r[i].down, d + r[i].off, r[i].bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return BHG_OK;
+    }
+
+private:
+    static constexpr int MAX = 12;
+    size_t add(size_t bytes, const void *up, void *down)
+    {
+        const size_t off = layout.add(bytes);
+        if (count < MAX) r[count] = {off, bytes, up, down};
+        count++;
+        return off;
+    }
+    bhg_context *c;
+    bhg::StageLayout layout;
+    struct { size_t off, bytes; const void *up; void *down; } r[MAX];
+    int count = 0;
+    char *d = nullptr;
+    bool own;
+};
 
 }  // namespace
 
@@ -1363,8 +1398,8 @@ int bhg_trace_device(bhg_context *c, const bhg_params *p, const double *x0_share
                      const double *d_k0, size_t n, double *d_end, uint8_t *d_flags, uint32_t *d_n_steps,
                      uint32_t *d_n_accepted, void *stream)
 {
-    return trace_device_impl(c, p, nullptr, 0, x0_shared, d_x0, d_k0, n, d_end, d_flags, d_n_steps, d_n_accepted, nullptr,
-                             stream);
+    return trace_device_impl(c, p, {.x0_shared = x0_shared, .d_x0 = d_x0, .d_k0 = d_k0, .n = n, .d_end = d_end, .d_flags = d_flags,
+                                    .d_n_steps = d_n_steps, .d_n_accepted = d_n_accepted, .stream = stream});
 }
 
 int bhg_trace_dir_device(bhg_context *c, const bhg_params *p, const double *x0_shared, const double *d_x0,
@@ -1372,8 +1407,8 @@ int bhg_trace_dir_device(bhg_context *c, const bhg_params *p, const double *x0_s
                          uint32_t *d_n_accepted, void *stream)
 {
     if (n && !d_end_dir) return fail(BHG_E_INVALID, "end_dir is NULL");
-    return trace_device_impl(c, p, nullptr, 0, x0_shared, d_x0, d_k0, n, nullptr, d_flags, d_n_steps, d_n_accepted, nullptr,
-                             stream, d_end_dir);
+    return trace_device_impl(c, p, {.x0_shared = x0_shared, .d_x0 = d_x0, .d_k0 = d_k0, .n = n, .d_end_dir = d_end_dir,
+                                    .d_flags = d_flags, .d_n_steps = d_n_steps, .d_n_accepted = d_n_accepted, .stream = stream});
 }
 
 int bhg_trace_objects_device(bhg_context *c, const bhg_params *p, const double *spheres, int32_t n_spheres,
@@ -1381,8 +1416,9 @@ int bhg_trace_objects_device(bhg_context *c, const bhg_params *p, const double *
                              uint8_t *d_flags, uint32_t *d_n_steps, uint32_t *d_n_accepted, int8_t *d_object_id,
                              void *stream)
 {
-    return trace_device_impl(c, p, spheres, n_spheres, x0_shared, d_x0, d_k0, n, d_end, d_flags, d_n_steps, d_n_accepted,
-                             d_object_id, stream);
+    return trace_device_impl(c, p, {.spheres = spheres, .n_spheres = n_spheres, .x0_shared = x0_shared, .d_x0 = d_x0, .d_k0 = d_k0,
+                                    .n = n, .d_end = d_end, .d_flags = d_flags, .d_n_steps = d_n_steps,
+                                    .d_n_accepted = d_n_accepted, .d_object_id = d_object_id, .stream = stream});
 }
 
 int bhg_trace_start_device(bhg_context *c, const bhg_params *p, const double *spheres, int32_t n_spheres,
@@ -1391,8 +1427,10 @@ int bhg_trace_start_device(bhg_context *c, const bhg_params *p, const double *sp
                            int8_t *d_object_id, double *d_start_steps, int32_t start_mode, void *stream)
 {
     if (n && !d_end && !d_end_dir) return fail(BHG_E_INVALID, "end / end_dir is NULL");
-    return trace_device_impl(c, p, spheres, n_spheres, x0_shared, d_x0, d_k0, n, d_end, d_flags, d_n_steps, d_n_accepted,
-                             d_object_id, stream, d_end ? nullptr : d_end_dir, d_start_steps, start_mode);
+    return trace_device_impl(c, p, {.spheres = spheres, .n_spheres = n_spheres, .x0_shared = x0_shared, .d_x0 = d_x0, .d_k0 = d_k0,
+                                    .n = n, .d_end = d_end, .d_end_dir = d_end ? nullptr : d_end_dir, .d_flags = d_flags,
+                                    .d_n_steps = d_n_steps, .d_n_accepted = d_n_accepted, .d_object_id = d_object_id,
+                                    .d_start_steps = d_start_steps, .start_mode = start_mode, .stream = stream});
 }
 
 int bhg_trace_prefix_device(bhg_context *c, const bhg_params *p, const double *spheres, int32_t n_spheres,
@@ -1402,8 +1440,10 @@ int bhg_trace_prefix_device(bhg_context *c, const bhg_params *p, const double *s
 {
     if (n && !d_end && !d_end_dir) return fail(BHG_E_INVALID, "end / end_dir is NULL");
     if (!prefix) return fail(BHG_E_INVALID, "prefix is NULL");
-    return trace_device_impl(c, p, spheres, n_spheres, x0_shared, d_x0, d_k0, n, d_end, d_flags, d_n_steps, d_n_accepted,
-                             d_object_id, stream, d_end ? nullptr : d_end_dir, d_start_steps, start_mode, nullptr, prefix);
+    return trace_device_impl(c, p, {.spheres = spheres, .n_spheres = n_spheres, .x0_shared = x0_shared, .d_x0 = d_x0, .d_k0 = d_k0,
+                                    .n = n, .d_end = d_end, .d_end_dir = d_end ? nullptr : d_end_dir, .d_flags = d_flags,
+                                    .d_n_steps = d_n_steps, .d_n_accepted = d_n_accepted, .d_object_id = d_object_id,
+                                    .d_start_steps = d_start_steps, .start_mode = start_mode, .prefix = prefix, .stream = stream});
 }
 
 double bhg_prefix_clearance(const bhg_params *p, const double *spheres, int32_t n_spheres, const double *x0)
@@ -1432,8 +1472,7 @@ int bhg_start_steps_match(const bhg_params *a, const bhg_params *b)
 // what the crossings trace covers, checked before the context (a refusal names its figure with or without a device)
 static int crossings_check(const bhg_params *p, int32_t max_crossings)
 {
-    int rc = validate(p);
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(validate(p));
     if (p->method != BHG_METHOD_DP54) return fail(BHG_E_INVALID, "the crossings trace is DP5(4) only: method must be BHG_METHOD_DP54");
     if (p->time_like) return fail(BHG_E_INVALID, "the crossings trace covers null rays only: time_like must be 0");
     if (!(p->disk_r_out > 0.0)) return fail(BHG_E_INVALID, "the crossings trace needs a disk: disk_r_out must be > 0");
@@ -1446,12 +1485,11 @@ int bhg_trace_crossings_device(bhg_context *c, const bhg_params *p, const double
                                const double *d_k0, size_t n, int32_t max_crossings, double *d_end, uint8_t *d_flags,
                                uint32_t *d_n_steps, uint32_t *d_n_accepted, double *d_cross, uint8_t *d_n_cross, void *stream)
 {
-    int rc = crossings_check(p, max_crossings);
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(crossings_check(p, max_crossings));
     if (n && (!d_end || !d_cross || !d_n_cross)) return fail(BHG_E_INVALID, "end / cross / n_cross is NULL");
-    const CrossOut cr{d_cross, d_n_cross, max_crossings, n};
-    return trace_device_impl(c, p, nullptr, 0, x0_shared, d_x0, d_k0, n, d_end, d_flags, d_n_steps, d_n_accepted, nullptr, stream,
-                             nullptr, nullptr, BHG_START_NONE, &cr);
+    return trace_device_impl(c, p, {.kind = TraceKind::CROSSINGS, .x0_shared = x0_shared, .d_x0 = d_x0, .d_k0 = d_k0, .n = n,
+                                    .d_end = d_end, .d_flags = d_flags, .d_n_steps = d_n_steps, .d_n_accepted = d_n_accepted,
+                                    .stream = stream, .cross = d_cross, .n_cross = d_n_cross, .max_cross = max_crossings, .stride = n});
 }
 
 // the host-buffer call, plain: upload, one device call, download (the crossings trace is not a streaming path)
@@ -1459,51 +1497,28 @@ int bhg_trace_crossings(bhg_context *c, const bhg_params *p, const double *x0, i
                         int32_t max_crossings, double *end, uint8_t *flags, uint32_t *n_steps, uint32_t *n_accepted,
                         double *cross, uint8_t *n_cross)
 {
-    int rc = crossings_check(p, max_crossings);
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(crossings_check(p, max_crossings));
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
     if (n == 0) return BHG_OK;
     if (!x0 || !k0 || !end || !cross || !n_cross) return fail(BHG_E_INVALID, "x0 / k0 / end / cross / n_cross is NULL");
     if (n > 0xFFFFFFFFull) return fail(BHG_E_INVALID, "n must be < 2^32 per call");
     ENTER_DEVICE(c->device);
-    const size_t b3 = n * 3 * sizeof(double), b6 = 2 * b3, bc = (size_t)max_crossings * b6, bu = n * sizeof(uint32_t);
-    const size_t o_x0 = b3, o_end = o_x0 + (x0_is_shared ? 0 : b3), o_cross = o_end + b6, o_steps = o_cross + bc,
-                 o_acc = o_steps + bu, o_flags = o_acc + bu, o_nc = o_flags + ((n + 7) & ~size_t(7));
-    char *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, o_nc + n));
-    struct Free {
-        char *d;
-        hipStream_t s;
-        ~Free()
-        {
-            (void)hipStreamSynchronize(s);
-            (void)hipFree(d);
-        }
-    } guard{d, c->stream};
-    hipStream_t s = c->stream;
-    HIP_TRY(hipMemcpyAsync(d, k0, b3, hipMemcpyHostToDevice, s));
-    if (!x0_is_shared) HIP_TRY(hipMemcpyAsync(d + o_x0, x0, b3, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_cross, cross, bc, hipMemcpyHostToDevice, s));
-    rc = bhg_trace_crossings_device(c, p, x0_is_shared ? x0 : nullptr, x0_is_shared ? nullptr : (const double *)(d + o_x0),
-                                    (const double *)d, n, max_crossings, (double *)(d + o_end), (uint8_t *)(d + o_flags),
-                                    (uint32_t *)(d + o_steps), (uint32_t *)(d + o_acc), (double *)(d + o_cross),
-                                    (uint8_t *)(d + o_nc), s);
-    if (rc != BHG_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(end, d + o_end, b6, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(cross, d + o_cross, bc, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(n_cross, d + o_nc, n, hipMemcpyDeviceToHost, s));
-    if (flags) HIP_TRY(hipMemcpyAsync(flags, d + o_flags, n, hipMemcpyDeviceToHost, s));
-    if (n_steps) HIP_TRY(hipMemcpyAsync(n_steps, d + o_steps, bu, hipMemcpyDeviceToHost, s));
-    if (n_accepted) HIP_TRY(hipMemcpyAsync(n_accepted, d + o_acc, bu, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return BHG_OK;
+    const size_t b3 = n * 3 * sizeof(double), b6 = 2 * b3, bu = n * sizeof(uint32_t);
+    Staged st(c, true);
+    const size_t k = st.in(k0, b3), x = st.in(x0_is_shared ? nullptr : x0, b3), e = st.out(end, b6),
+                 cr = st.inout(cross, (size_t)max_crossings * b6), nc = st.out(n_cross, n), fl = st.out(flags, n),
+                 ns = st.out(n_steps, bu), na = st.out(n_accepted, bu);
+    return st.run([&] {
+        return bhg_trace_crossings_device(c, p, x0_is_shared ? x0 : nullptr, st.at<double>(x), st.at<double>(k), n, max_crossings,
+                                          st.at<double>(e), st.at<uint8_t>(fl), st.at<uint32_t>(ns), st.at<uint32_t>(na),
+                                          st.at<double>(cr), st.at<uint8_t>(nc), c->stream);
+    });
 }
 
 // what the travel-time trace covers, checked before the context like the crossings trace's
 static int travel_time_check(const bhg_params *p, int32_t max_crossings, const double *t_end)
 {
-    int rc = validate(p);
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(validate(p));
     if (p->method != BHG_METHOD_DP54) return fail(BHG_E_INVALID, "the travel-time trace is DP5(4) only: method must be BHG_METHOD_DP54");
     if (p->time_like) return fail(BHG_E_INVALID, "the travel-time trace covers null rays only: time_like must be 0");
     if (max_crossings < 0 || max_crossings > BHG_MAX_CROSSINGS)
@@ -1519,15 +1534,16 @@ int bhg_travel_time_device(bhg_context *c, const bhg_params *p, const double *x0
                            uint32_t *d_n_steps, uint32_t *d_n_accepted, double *d_cross, uint8_t *d_n_cross, double *d_t_end,
                            double *d_t_cross, void *stream)
 {
-    int rc = travel_time_check(p, max_crossings, d_t_end);
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(travel_time_check(p, max_crossings, d_t_end));
     if (n && !d_end) return fail(BHG_E_INVALID, "end is NULL");
     if (n && max_crossings > 0 && (!d_cross || !d_n_cross || !d_t_cross))
         return fail(BHG_E_INVALID, "cross / n_cross / t_cross is NULL with max_crossings > 0");
     // (without records the kernel writes neither cross nor t_cross; n_cross is still counted when it is given and a disk is set)
-    const CrossOut cr{max_crossings > 0 ? d_cross : nullptr, d_n_cross, max_crossings, n, d_t_end, max_crossings > 0 ? d_t_cross : nullptr};
-    return trace_device_impl(c, p, nullptr, 0, x0_shared, d_x0, d_k0, n, d_end, d_flags, d_n_steps, d_n_accepted, nullptr, stream,
-                             nullptr, nullptr, BHG_START_NONE, &cr);
+    return trace_device_impl(c, p, {.kind = TraceKind::TRAVEL_TIME, .x0_shared = x0_shared, .d_x0 = d_x0, .d_k0 = d_k0, .n = n,
+                                    .d_end = d_end, .d_flags = d_flags, .d_n_steps = d_n_steps, .d_n_accepted = d_n_accepted,
+                                    .stream = stream, .cross = max_crossings > 0 ? d_cross : nullptr, .n_cross = d_n_cross,
+                                    .max_cross = max_crossings, .stride = n, .t_end = d_t_end,
+                                    .t_cross = max_crossings > 0 ? d_t_cross : nullptr});
 }
 
 // the host-buffer call, as bhg_trace_crossings: upload, one device call, download (cross, n_cross and t_cross may be NULL with
@@ -1536,8 +1552,7 @@ int bhg_travel_time(bhg_context *c, const bhg_params *p, const double *x0, int x
                     int32_t max_crossings, double *end, uint8_t *flags, uint32_t *n_steps, uint32_t *n_accepted, double *cross,
                     uint8_t *n_cross, double *t_end, double *t_cross)
 {
-    int rc = travel_time_check(p, max_crossings, t_end);
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(travel_time_check(p, max_crossings, t_end));
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
     if (n == 0) return BHG_OK;
     if (!x0 || !k0 || !end) return fail(BHG_E_INVALID, "x0 / k0 / end is NULL");
@@ -1545,71 +1560,31 @@ int bhg_travel_time(bhg_context *c, const bhg_params *p, const double *x0, int x
         return fail(BHG_E_INVALID, "cross / n_cross / t_cross is NULL with max_crossings > 0");
     if (n > 0xFFFFFFFFull) return fail(BHG_E_INVALID, "n must be < 2^32 per call");
     ENTER_DEVICE(c->device);
-    const size_t b3 = n * 3 * sizeof(double), b6 = 2 * b3, bc = (size_t)max_crossings * b6, bu = n * sizeof(uint32_t),
-                 bt = n * sizeof(double), btc = (size_t)max_crossings * bt;
-    const size_t o_x0 = b3, o_end = o_x0 + (x0_is_shared ? 0 : b3), o_cross = o_end + b6, o_te = o_cross + bc, o_tc = o_te + bt,
-                 o_steps = o_tc + btc, o_acc = o_steps + bu, o_flags = o_acc + bu, o_nc = o_flags + ((n + 7) & ~size_t(7));
-    char *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, o_nc + n));
-    struct Free {
-        char *d;
-        hipStream_t s;
-        ~Free()
-        {
-            (void)hipStreamSynchronize(s);
-            (void)hipFree(d);
-        }
-    } guard{d, c->stream};
-    hipStream_t s = c->stream;
-    HIP_TRY(hipMemcpyAsync(d, k0, b3, hipMemcpyHostToDevice, s));
-    if (!x0_is_shared) HIP_TRY(hipMemcpyAsync(d + o_x0, x0, b3, hipMemcpyHostToDevice, s));
-    if (max_crossings > 0) {
-        HIP_TRY(hipMemcpyAsync(d + o_cross, cross, bc, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d + o_tc, t_cross, btc, hipMemcpyHostToDevice, s));
-    }
-    const bool want_nc = n_cross != nullptr;
-    rc = bhg_travel_time_device(c, p, x0_is_shared ? x0 : nullptr, x0_is_shared ? nullptr : (const double *)(d + o_x0),
-                                (const double *)d, n, max_crossings, (double *)(d + o_end), (uint8_t *)(d + o_flags),
-                                (uint32_t *)(d + o_steps), (uint32_t *)(d + o_acc), max_crossings > 0 ? (double *)(d + o_cross) : nullptr,
-                                want_nc ? (uint8_t *)(d + o_nc) : nullptr, (double *)(d + o_te),
-                                max_crossings > 0 ? (double *)(d + o_tc) : nullptr, s);
-    if (rc != BHG_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(end, d + o_end, b6, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(t_end, d + o_te, bt, hipMemcpyDeviceToHost, s));
-    if (max_crossings > 0) {
-        HIP_TRY(hipMemcpyAsync(cross, d + o_cross, bc, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(t_cross, d + o_tc, btc, hipMemcpyDeviceToHost, s));
-    }
-    if (want_nc) HIP_TRY(hipMemcpyAsync(n_cross, d + o_nc, n, hipMemcpyDeviceToHost, s));
-    if (flags) HIP_TRY(hipMemcpyAsync(flags, d + o_flags, n, hipMemcpyDeviceToHost, s));
-    if (n_steps) HIP_TRY(hipMemcpyAsync(n_steps, d + o_steps, bu, hipMemcpyDeviceToHost, s));
-    if (n_accepted) HIP_TRY(hipMemcpyAsync(n_accepted, d + o_acc, bu, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return BHG_OK;
+    const size_t b3 = n * 3 * sizeof(double), b6 = 2 * b3, bu = n * sizeof(uint32_t), bt = n * sizeof(double);
+    const bool records = max_crossings > 0;      // (without them cross and t_cross stay on the host, and n_cross is optional)
+    Staged st(c, true);
+    const size_t k = st.in(k0, b3), x = st.in(x0_is_shared ? nullptr : x0, b3), e = st.out(end, b6), te = st.out(t_end, bt),
+                 cr = st.inout(records ? cross : nullptr, (size_t)max_crossings * b6),
+                 tc = st.inout(records ? t_cross : nullptr, (size_t)max_crossings * bt),
+                 nc = n_cross ? st.out(n_cross, n) : Staged::NONE, fl = st.out(flags, n), ns = st.out(n_steps, bu),
+                 na = st.out(n_accepted, bu);
+    return st.run([&] {
+        return bhg_travel_time_device(c, p, x0_is_shared ? x0 : nullptr, st.at<double>(x), st.at<double>(k), n, max_crossings,
+                                      st.at<double>(e), st.at<uint8_t>(fl), st.at<uint32_t>(ns), st.at<uint32_t>(na), st.at<double>(cr),
+                                      st.at<uint8_t>(nc), st.at<double>(te), st.at<double>(tc), c->stream);
+    });
 }
 
 // --- triangle meshes ---------------------------------------------------------------------------------
 
 }  // extern "C"
 
-// a mesh on one device: the flattened tree of mesh_bvh.h, the triangles in leaf order, the maps between the two numberings
-struct bhg_mesh {
-    int device = 0;
-    char *d = nullptr;        // one allocation
-    bhg::MeshView view{};
-    int64_t n_nodes = 0;
-    int32_t depth = 0;
-    double box[6] = {0, 0, 0, 0, 0, 0};
-    double d_min = 0.0, d_max = 0.0;
-};
-
 namespace {
 
 // what the mesh trace covers, checked before the context (a refusal names its figure with or without a device)
 int mesh_trace_check(const bhg_params *p, const bhg_mesh *mesh, double max_chord, const int32_t *tri_id, const double *bary)
 {
-    int rc = validate(p);
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(validate(p));
     if (p->method != BHG_METHOD_DP54) return fail(BHG_E_INVALID, "the mesh trace is DP5(4) only: method must be BHG_METHOD_DP54");
     if (p->time_like) return fail(BHG_E_INVALID, "the mesh trace covers null rays only: time_like must be 0");
     if (!mesh) return fail(BHG_E_INVALID, "mesh is NULL");
@@ -1744,27 +1719,13 @@ int bhg_trace_mesh_device(bhg_context *c, const bhg_params *p, const bhg_mesh *m
                           const double *d_x0, const double *d_k0, size_t n, double *d_end, uint8_t *d_flags, uint32_t *d_n_steps,
                           uint32_t *d_n_accepted, int32_t *d_tri_id, double *d_bary, void *stream)
 {
-    int rc = mesh_trace_check(p, mesh, max_chord, d_tri_id, d_bary);
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(mesh_trace_check(p, mesh, max_chord, d_tri_id, d_bary));
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
     if (mesh->device != c->device) return fail(BHG_E_INVALID, "the mesh lives on another device than the context");
     if (n && !d_end) return fail(BHG_E_INVALID, "end is NULL");
-    bhg::MeshArgs g;
-    std::memset(&g, 0, sizeof(g));
-    g.mesh = mesh->view;
-    std::memcpy(g.box, mesh->box, sizeof(g.box));
-    g.d_min = mesh->d_min;
-    g.d_max = mesh->d_max;
-    g.max_chord = max_chord;
-    // BHGEO_MESH_CULL=0: every step of every ray samples its sub-chords (an A/B aid: the results are the same bits)
-    const char *cull = std::getenv("BHGEO_MESH_CULL");
-    g.cull = !(cull && cull[0] == '0' && cull[1] == 0);
-    g.tri_id = d_tri_id;
-    g.bary = d_bary;
-    CrossOut cr{nullptr, nullptr, 0, n};
-    cr.mesh = &g;
-    return trace_device_impl(c, p, nullptr, 0, x0_shared, d_x0, d_k0, n, d_end, d_flags, d_n_steps, d_n_accepted, nullptr, stream,
-                             nullptr, nullptr, BHG_START_NONE, &cr);
+    return trace_device_impl(c, p, {.kind = TraceKind::MESH, .x0_shared = x0_shared, .d_x0 = d_x0, .d_k0 = d_k0, .n = n, .d_end = d_end,
+                                    .d_flags = d_flags, .d_n_steps = d_n_steps, .d_n_accepted = d_n_accepted, .stream = stream,
+                                    .stride = n, .mesh = mesh, .max_chord = max_chord, .tri_id = d_tri_id, .bary = d_bary});
 }
 
 // the host-buffer call, as bhg_trace_crossings: upload, one device call, download.  bary is read first (a ray that hits nothing
@@ -1773,44 +1734,23 @@ int bhg_trace_mesh(bhg_context *c, const bhg_params *p, const bhg_mesh *mesh, do
                    const double *k0, size_t n, double *end, uint8_t *flags, uint32_t *n_steps, uint32_t *n_accepted, int32_t *tri_id,
                    double *bary)
 {
-    int rc = mesh_trace_check(p, mesh, max_chord, tri_id, bary);
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(mesh_trace_check(p, mesh, max_chord, tri_id, bary));
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
     if (mesh->device != c->device) return fail(BHG_E_INVALID, "the mesh lives on another device than the context");
     if (n == 0) return BHG_OK;
     if (!x0 || !k0 || !end) return fail(BHG_E_INVALID, "x0 / k0 / end is NULL");
     if (n > 0xFFFFFFFFull) return fail(BHG_E_INVALID, "n must be < 2^32 per call");
     ENTER_DEVICE(c->device);
-    const size_t b3 = n * 3 * sizeof(double), b6 = 2 * b3, bb = n * 2 * sizeof(double), bu = n * sizeof(uint32_t);
-    const size_t o_x0 = b3, o_end = o_x0 + (x0_is_shared ? 0 : b3), o_bary = o_end + b6, o_steps = o_bary + bb, o_acc = o_steps + bu,
-                 o_tri = o_acc + bu, o_flags = o_tri + bu;
-    char *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, o_flags + n));
-    struct Free {
-        char *d;
-        hipStream_t s;
-        ~Free()
-        {
-            (void)hipStreamSynchronize(s);
-            (void)hipFree(d);
-        }
-    } guard{d, c->stream};
-    hipStream_t s = c->stream;
-    HIP_TRY(hipMemcpyAsync(d, k0, b3, hipMemcpyHostToDevice, s));
-    if (!x0_is_shared) HIP_TRY(hipMemcpyAsync(d + o_x0, x0, b3, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_bary, bary, bb, hipMemcpyHostToDevice, s));
-    rc = bhg_trace_mesh_device(c, p, mesh, max_chord, x0_is_shared ? x0 : nullptr, x0_is_shared ? nullptr : (const double *)(d + o_x0),
-                               (const double *)d, n, (double *)(d + o_end), (uint8_t *)(d + o_flags), (uint32_t *)(d + o_steps),
-                               (uint32_t *)(d + o_acc), (int32_t *)(d + o_tri), (double *)(d + o_bary), s);
-    if (rc != BHG_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(end, d + o_end, b6, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(tri_id, d + o_tri, bu, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(bary, d + o_bary, bb, hipMemcpyDeviceToHost, s));
-    if (flags) HIP_TRY(hipMemcpyAsync(flags, d + o_flags, n, hipMemcpyDeviceToHost, s));
-    if (n_steps) HIP_TRY(hipMemcpyAsync(n_steps, d + o_steps, bu, hipMemcpyDeviceToHost, s));
-    if (n_accepted) HIP_TRY(hipMemcpyAsync(n_accepted, d + o_acc, bu, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return BHG_OK;
+    const size_t b3 = n * 3 * sizeof(double), b6 = 2 * b3, bu = n * sizeof(uint32_t);
+    Staged st(c, true);
+    const size_t k = st.in(k0, b3), x = st.in(x0_is_shared ? nullptr : x0, b3), e = st.out(end, b6), tr = st.out(tri_id, bu),
+                 ba = st.inout(bary, n * 2 * sizeof(double)), fl = st.out(flags, n), ns = st.out(n_steps, bu),
+                 na = st.out(n_accepted, bu);
+    return st.run([&] {
+        return bhg_trace_mesh_device(c, p, mesh, max_chord, x0_is_shared ? x0 : nullptr, st.at<double>(x), st.at<double>(k), n,
+                                     st.at<double>(e), st.at<uint8_t>(fl), st.at<uint32_t>(ns), st.at<uint32_t>(na),
+                                     st.at<int32_t>(tr), st.at<double>(ba), c->stream);
+    });
 }
 
 int bhg_trace(bhg_context *c, const bhg_params *p, const double *x0, int x0_is_shared, const double *k0,
@@ -1966,9 +1906,11 @@ int pipeline_impl(bhg_context *c, const bhg_params *p, const double *spheres, in
             HIP_TRY(hipEventRecord(c->ev_in[slot], c->s_in));
             HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_in[slot], 0));
         }
-        rc = trace_device_impl(c, p, spheres, n_spheres, io.x0_shared, per_ray_x0 ? d_x0 + off * 3 : nullptr, d_k0 + off * 3, m,
-                               dir_only ? nullptr : d_end + off * 6, d_flags + off, d_steps + off, d_acc + off,
-                               d_obj ? d_obj + off : nullptr, c->stream, dir_only ? d_dir + off * 3 : nullptr);
+        rc = trace_device_impl(c, p, {.spheres = spheres, .n_spheres = n_spheres, .x0_shared = io.x0_shared,
+                                      .d_x0 = per_ray_x0 ? d_x0 + off * 3 : nullptr, .d_k0 = d_k0 + off * 3, .n = m,
+                                      .d_end = dir_only ? nullptr : d_end + off * 6, .d_end_dir = dir_only ? d_dir + off * 3 : nullptr,
+                                      .d_flags = d_flags + off, .d_n_steps = d_steps + off, .d_n_accepted = d_acc + off,
+                                      .d_object_id = d_obj ? d_obj + off : nullptr, .stream = c->stream});
         if (rc != BHG_OK) return rc;
         if (split)
             HIP_TRY(bhg::launch_split_end(d_end + off * 6, m, io.loc ? d_loc + off * 3 : nullptr, io.dir ? d_dir + off * 3 : nullptr,
@@ -2002,10 +1944,8 @@ int bhg_trace_objects(bhg_context *c, const bhg_params *p, const double *spheres
                       uint32_t *n_accepted, int8_t *object_id)
 {
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
-    int rc = validate(p);
-    if (rc != BHG_OK) return rc;
-    rc = validate_spheres(p, spheres, n_spheres);
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(validate(p));
+    BHG_TRY(validate_spheres(p, spheres, n_spheres));
     if (n == 0) return BHG_OK;
     if (!x0 || !k0 || !end) return fail(BHG_E_INVALID, "x0 / k0 / end is NULL");
     if (n > 0xFFFFFFFFull) return fail(BHG_E_INVALID, "n must be < 2^32 per call");
@@ -2113,10 +2053,8 @@ int bhg_rays_trace(bhg_rays *r, const bhg_params *p, const double *spheres, int3
                    int8_t *object_id)
 {
     if (!r) return fail(BHG_E_INVALID, "rays is NULL");
-    int rc = validate(p);
-    if (rc != BHG_OK) return rc;
-    rc = validate_spheres(p, spheres, n_spheres);
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(validate(p));
+    BHG_TRY(validate_spheres(p, spheres, n_spheres));
     if (first > r->n || n > r->n - first) return fail(BHG_E_INVALID, "ray range out of bounds");
     if (n == 0) return BHG_OK;
     if (!end && !end_loc && !end_dir && !flags) return fail(BHG_E_INVALID, "no result array given");
@@ -2207,121 +2145,63 @@ int raygen_impl(bhg_context *c, int32_t width, int32_t height, int32_t samples, 
 //      arrays, so no device array is looked at
 //   6. the device arrays: an output, end or end_dir, flags, the sky; end for a disk or spheres; object_id for spheres;
 //      k0 for redshift; qu and k0 for polarisation; k0 for the thermal disk
-// ly: nullptr, or the call is the layered shade of a crossings trace (bhg_shade_disk_layers_device): checked after the scene
-// (step 1b: a disk, no spheres, max_crossings, opacity), its arrays with the others in step 6
-struct LayersIn {
-    const double *cross;
-    const uint8_t *n_cross;
-    const bhg_disk_layers *set;
+// layered: the call is the layered shade of a crossings trace (bhg_shade_disk_layers_device): checked after the scene (step 1b: a
+// disk, no spheres, max_crossings, opacity), its arrays with the others in step 6
+struct ShadeCall {
+    const double *end = nullptr, *end_dir = nullptr;   // [n][6], or -- end null -- [n][3]
+    const uint8_t *flags = nullptr;
+    const int8_t *object_id = nullptr;
+    size_t n_pixels = 0;
+    int32_t samples = 0;
+    const bhg_scene *sc = nullptr;       // the settings: all but the scene may be NULL
+    const bhg_params *p = nullptr;
+    const bhg_redshift *rs = nullptr;
+    const bhg_observer *obs = nullptr;
+    const bhg_object_textures *ot = nullptr;
+    const double *x0_shared = nullptr, *k0 = nullptr;
+    double *rgba = nullptr;
+    float *rgba_f32 = nullptr;
+    const int64_t *scatter = nullptr;
+    const bhg_polarisation *pol = nullptr;
+    double *qu = nullptr;
+    const bhg_disk_thermal *th = nullptr;
+    const bhg_object_motion *mo = nullptr;
+    void *stream = nullptr;
+    bool layered = false;
+    const double *cross = nullptr;
+    const uint8_t *n_cross = nullptr;
+    const bhg_disk_layers *layers = nullptr;
     // the retarded shade (bhg_shade_disk_layers_retarded_device): nullptr / 0 = the plain layered shade's kernels
     const double *t_cross = nullptr;
     double phase_rate = 0.0;
 };
 
-int shade(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags, const int8_t *d_object_id,
-          size_t n_pixels, int32_t samples, const bhg_scene *sc, const bhg_params *p, const bhg_redshift *rs,
-          const bhg_observer *obs, const bhg_object_textures *ot, const double *x0_shared, const double *d_k0, double *d_rgba,
-          float *d_rgba_f32, const int64_t *d_scatter, const bhg_polarisation *pol, double *d_qu, const bhg_disk_thermal *th,
-          const bhg_object_motion *mo, void *stream, const LayersIn *ly = nullptr)
+// step 1 of shade()'s checks, and the mesh shade's (which goes with no object spheres and says so in its own words): the scene
+// is there; samples and the sky's size; spheres and lamps; the disk
+int scene_check(const bhg_scene *sc, int32_t samples, bool mesh)
 {
     if (!sc) return fail(BHG_E_INVALID, "scene is NULL");
     if (samples <= 0 || sc->sky_w <= 0 || sc->sky_h <= 0) return fail(BHG_E_INVALID, "samples, sky_w, sky_h must be > 0");
-    if (sc->n_spheres < 0 || sc->n_spheres > BHG_MAX_SPHERES || sc->n_lamps < 0 || sc->n_lamps > 4)
+    if (mesh) {
+        if (sc->n_spheres != 0) return fail(BHG_E_INVALID, "the mesh shade does not go with object spheres: n_spheres must be 0");
+        if (sc->n_lamps < 0 || sc->n_lamps > 4) return fail(BHG_E_INVALID, "n_lamps must be in [0, 4]");
+    } else if (sc->n_spheres < 0 || sc->n_spheres > BHG_MAX_SPHERES || sc->n_lamps < 0 || sc->n_lamps > 4) {
         return fail(BHG_E_INVALID, "n_spheres must be in [0, BHG_MAX_SPHERES], n_lamps in [0, 4]");
-    const bool has_disk = sc->disk_r_out > 0.0;
-    if (has_disk) {
+    }
+    if (sc->disk_r_out > 0.0) {
         if (!(sc->disk_r_out > sc->disk_r_in) || !(sc->disk_stddev > 0.0))
             return fail(BHG_E_INVALID, "disk needs r_out > r_in and stddev > 0");
         if (sc->d_disk_tex && (sc->disk_w <= 0 || sc->disk_h <= 0)) return fail(BHG_E_INVALID, "disk texture size must be > 0");
     }
-    for (int j = 0; j < sc->n_spheres; j++)
-        if (!(sc->spheres[j][3] > 0.0)) return fail(BHG_E_INVALID, "sphere radii must be > 0");
-    if (ly) {
-        if (!ly->set) return fail(BHG_E_INVALID, "disk layers: the settings are NULL");
-        if (!has_disk) return fail(BHG_E_INVALID, "disk layers need a disk in the scene: disk_r_out must be > 0");
-        if (sc->n_spheres > 0) return fail(BHG_E_INVALID, "disk layers do not go with object spheres: n_spheres must be 0");
-        if (ly->set->max_crossings < 1 || ly->set->max_crossings > BHG_MAX_CROSSINGS)
-            return fail(BHG_E_INVALID, "disk layers: max_crossings must be in [1, BHG_MAX_CROSSINGS]");
-        if (!(ly->set->opacity > 0.0) || !(ly->set->opacity <= 1.0))
-            return fail(BHG_E_INVALID, "disk layers: opacity must be in (0, 1]");
-    }
-    bhg::ObjectTextureParams tp;
-    if (ot) {
-        int rc = bhg::object_texture_params(ot, sc->n_spheres, &tp);
-        if (rc != BHG_OK) return rc;
-    }
-    bhg::MotionParams mp;
-    if (mo) {
-        int rc = bhg::motion_params(p, mo, &sc->spheres[0][0], sc->n_spheres, &mp);
-        if (rc != BHG_OK) return rc;
-    }
-    const bool on = rs && rs->apply != 0;
-    bhg::RedshiftParams rp;
-    bhg::ObserverParams op;
-    if (on) {
-        if (!x0_shared) return fail(BHG_E_INVALID, "x0_shared is NULL");
-        int rc = bhg::redshift_params(p, rs, has_disk && (rs->apply & BHG_REDSHIFT_DISK) ? sc->disk_r_in : -1.0, x0_shared, &rp);
-        if (rc != BHG_OK) return rc;
-        if (obs) {
-            rc = bhg::observer_params(p, obs, x0_shared, &op);
-            if (rc != BHG_OK) return rc;
-        }
-    }
-    bhg::PolarisationParams pp;
-    if (pol) {
-        if (!x0_shared) return fail(BHG_E_INVALID, "polarisation needs the shared camera origin x0_shared");
-        int rc = bhg::polarisation_params(p, pol, on ? rs : nullptr, obs, has_disk ? sc->disk_r_in : -1.0, x0_shared, &pp);
-        if (rc != BHG_OK) return rc;
-        if (obs) {
-            bhg::ObserverParams chk;
-            rc = bhg::observer_params(p, obs, x0_shared, &chk);
-            if (rc != BHG_OK) return rc;
-        }
-    }
-    bhg::ThermalParams tp_th;
-    bhg::RedshiftParams rp_th;
-    bhg::ObserverParams op_th;
-    if (th) {
-        int rc = bhg::thermal_params(p, th, on ? rs : nullptr, pol, has_disk ? sc->disk_r_in : -1.0, x0_shared, &tp_th, &rp_th);
-        if (rc != BHG_OK) return rc;
-        if (!x0_shared) return fail(BHG_E_INVALID, "the thermal disk needs the shared camera origin x0_shared");
-        if (obs) {
-            rc = bhg::observer_params(p, obs, x0_shared, &op_th);
-            if (rc != BHG_OK) return rc;
-        }
-    }
-    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
-    if (n_pixels == 0) return BHG_OK;
-    if ((!d_rgba && !d_rgba_f32) || (!d_end && !d_end_dir) || !d_flags || !sc->d_sky)
-        return fail(BHG_E_INVALID, "NULL device pointer");
-    if (ly && (!ly->cross || !ly->n_cross)) return fail(BHG_E_INVALID, "disk layers: d_cross / d_n_cross is NULL");
-    // (the layered shade takes a disk ray's position from the crossing records: directions alone do for the rest)
-    if (!d_end && ((has_disk && !ly) || sc->n_spheres > 0))
-        return fail(BHG_E_INVALID, "d_end is NULL: a direction-only frame cannot have a disk or object spheres");
-    if (sc->n_spheres > 0 && !d_object_id) return fail(BHG_E_INVALID, "object_id is NULL but the scene has spheres");
-    if (on && !d_k0) return fail(BHG_E_INVALID, "redshift needs the camera directions d_k0");
-    if (pol && (!d_qu || !d_k0)) return fail(BHG_E_INVALID, "polarisation needs d_qu and the camera directions d_k0");
-    if (th && !d_k0) return fail(BHG_E_INVALID, "the thermal disk needs the camera directions d_k0");
-    ENTER_DEVICE(c->device);
-    bhg::ShadeArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.end = d_end;
-    a.dir = d_end ? nullptr : d_end_dir;
-    if (on) {
-        a.rs = rp;
-        a.k0 = d_k0;
-        if (obs) a.obs = op;
-    }
-    a.flags = d_flags;
+    return BHG_OK;
+}
+
+// the scene's sky, disk and lamps into the kernels' arguments (the spheres are shade()'s own)
+void fill_scene_args(bhg::ShadeArgs &a, const bhg_scene *sc)
+{
     a.sky = sc->d_sky;
-    a.rgba = d_rgba;
-    a.rgba_f32 = d_rgba_f32;
-    a.scatter = d_scatter;
-    a.n_pixels = n_pixels;
-    a.samples = samples;
     a.sky_w = sc->sky_w;
     a.sky_h = sc->sky_h;
-    a.object_id = sc->n_spheres > 0 ? d_object_id : nullptr;
     a.disk_tex = sc->d_disk_tex;
     a.disk_w = sc->disk_w;
     a.disk_h = sc->disk_h;
@@ -2331,35 +2211,120 @@ int shade(bhg_context *c, const double *d_end, const double *d_end_dir, const ui
     a.disk_mean = sc->disk_mean;
     a.disk_stddev = sc->disk_stddev;
     a.disk_intensity = sc->disk_intensity;
-    a.n_spheres = sc->n_spheres;
     a.n_lamps = sc->n_lamps;
+    std::memcpy(a.lamps, sc->lamps, sizeof(a.lamps));
+}
+
+int shade(bhg_context *c, const ShadeCall &s)
+{
+    const bhg_scene *const sc = s.sc;
+    BHG_TRY(scene_check(sc, s.samples, false));
+    const bool has_disk = sc->disk_r_out > 0.0;
+    for (int j = 0; j < sc->n_spheres; j++)
+        if (!(sc->spheres[j][3] > 0.0)) return fail(BHG_E_INVALID, "sphere radii must be > 0");
+    if (s.layered) {
+        if (!s.layers) return fail(BHG_E_INVALID, "disk layers: the settings are NULL");
+        if (!has_disk) return fail(BHG_E_INVALID, "disk layers need a disk in the scene: disk_r_out must be > 0");
+        if (sc->n_spheres > 0) return fail(BHG_E_INVALID, "disk layers do not go with object spheres: n_spheres must be 0");
+        if (s.layers->max_crossings < 1 || s.layers->max_crossings > BHG_MAX_CROSSINGS)
+            return fail(BHG_E_INVALID, "disk layers: max_crossings must be in [1, BHG_MAX_CROSSINGS]");
+        if (!(s.layers->opacity > 0.0) || !(s.layers->opacity <= 1.0))
+            return fail(BHG_E_INVALID, "disk layers: opacity must be in (0, 1]");
+    }
+    bhg::ObjectTextureParams tp;
+    if (s.ot) {
+        BHG_TRY(bhg::object_texture_params(s.ot, sc->n_spheres, &tp));
+    }
+    bhg::MotionParams mp;
+    if (s.mo) {
+        BHG_TRY(bhg::motion_params(s.p, s.mo, &sc->spheres[0][0], sc->n_spheres, &mp));
+    }
+    const bool on = s.rs && s.rs->apply != 0;
+    bhg::RedshiftParams rp;
+    bhg::ObserverParams op;
+    if (on) {
+        if (!s.x0_shared) return fail(BHG_E_INVALID, "x0_shared is NULL");
+        BHG_TRY(bhg::redshift_params(s.p, s.rs, has_disk && (s.rs->apply & BHG_REDSHIFT_DISK) ? sc->disk_r_in : -1.0, s.x0_shared, &rp));
+        if (s.obs) {
+            BHG_TRY(bhg::observer_params(s.p, s.obs, s.x0_shared, &op));
+        }
+    }
+    bhg::PolarisationParams pp;
+    if (s.pol) {
+        if (!s.x0_shared) return fail(BHG_E_INVALID, "polarisation needs the shared camera origin x0_shared");
+        BHG_TRY(bhg::polarisation_params(s.p, s.pol, on ? s.rs : nullptr, s.obs, has_disk ? sc->disk_r_in : -1.0, s.x0_shared, &pp));
+        if (s.obs) {
+            bhg::ObserverParams chk;
+            BHG_TRY(bhg::observer_params(s.p, s.obs, s.x0_shared, &chk));
+        }
+    }
+    bhg::ThermalParams tp_th;
+    bhg::RedshiftParams rp_th;
+    bhg::ObserverParams op_th;
+    if (s.th) {
+        BHG_TRY(bhg::thermal_params(s.p, s.th, on ? s.rs : nullptr, s.pol, has_disk ? sc->disk_r_in : -1.0, s.x0_shared, &tp_th, &rp_th));
+        if (!s.x0_shared) return fail(BHG_E_INVALID, "the thermal disk needs the shared camera origin x0_shared");
+        if (s.obs) {
+            BHG_TRY(bhg::observer_params(s.p, s.obs, s.x0_shared, &op_th));
+        }
+    }
+    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
+    if (s.n_pixels == 0) return BHG_OK;
+    if ((!s.rgba && !s.rgba_f32) || (!s.end && !s.end_dir) || !s.flags || !sc->d_sky)
+        return fail(BHG_E_INVALID, "NULL device pointer");
+    if (s.layered && (!s.cross || !s.n_cross)) return fail(BHG_E_INVALID, "disk layers: d_cross / d_n_cross is NULL");
+    // (the layered shade takes a disk ray's position from the crossing records: directions alone do for the rest)
+    if (!s.end && ((has_disk && !s.layered) || sc->n_spheres > 0))
+        return fail(BHG_E_INVALID, "d_end is NULL: a direction-only frame cannot have a disk or object spheres");
+    if (sc->n_spheres > 0 && !s.object_id) return fail(BHG_E_INVALID, "object_id is NULL but the scene has spheres");
+    if (on && !s.k0) return fail(BHG_E_INVALID, "redshift needs the camera directions d_k0");
+    if (s.pol && (!s.qu || !s.k0)) return fail(BHG_E_INVALID, "polarisation needs d_qu and the camera directions d_k0");
+    if (s.th && !s.k0) return fail(BHG_E_INVALID, "the thermal disk needs the camera directions d_k0");
+    ENTER_DEVICE(c->device);
+    bhg::ShadeArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.end = s.end;
+    a.dir = s.end ? nullptr : s.end_dir;
+    if (on) {
+        a.rs = rp;
+        a.k0 = s.k0;
+        if (s.obs) a.obs = op;
+    }
+    a.flags = s.flags;
+    a.rgba = s.rgba;
+    a.rgba_f32 = s.rgba_f32;
+    a.scatter = s.scatter;
+    a.n_pixels = s.n_pixels;
+    a.samples = s.samples;
+    fill_scene_args(a, sc);
+    a.object_id = sc->n_spheres > 0 ? s.object_id : nullptr;
+    a.n_spheres = sc->n_spheres;
     std::memcpy(a.spheres, sc->spheres, sizeof(a.spheres));
     std::memcpy(a.sphere_rgb, sc->sphere_rgb, sizeof(a.sphere_rgb));
-    std::memcpy(a.lamps, sc->lamps, sizeof(a.lamps));
-    if (ot) a.ot = tp;
-    if (pol) {
+    if (s.ot) a.ot = tp;
+    if (s.pol) {
         a.pol = pp;
-        a.pol.qu = d_qu;
-        a.k0 = d_k0;
+        a.pol.qu = s.qu;
+        a.k0 = s.k0;
     }
-    if (th) {
+    if (s.th) {
         // the redshift instance, always: the disk's g from rs (metric, camera, sense), objects and sky as the caller's apply
         a.th = tp_th;
         if (!on) a.rs = rp_th;
-        a.k0 = d_k0;
-        if (obs) a.obs = op_th;
+        a.k0 = s.k0;
+        if (s.obs) a.obs = op_th;
     }
-    if (mo) a.mo = mp;     // (launch_shade takes the motion instance only when rs.apply weighs objects)
-    if (ly) {
-        a.cross = ly->cross;
-        a.n_cross = ly->n_cross;
-        a.max_cross = ly->set->max_crossings;
-        a.transmit = 1.0 - ly->set->opacity;
-        const bool retarded = ly->t_cross && ly->phase_rate != 0.0;
-        HIP_TRY(bhg::launch_shade_layers(a, (hipStream_t)stream, retarded ? ly->t_cross : nullptr, ly->phase_rate));
+    if (s.mo) a.mo = mp;     // (launch_shade takes the motion instance only when rs.apply weighs objects)
+    if (s.layered) {
+        a.cross = s.cross;
+        a.n_cross = s.n_cross;
+        a.max_cross = s.layers->max_crossings;
+        a.transmit = 1.0 - s.layers->opacity;
+        const bool retarded = s.t_cross && s.phase_rate != 0.0;
+        HIP_TRY(bhg::launch_shade_layers(a, (hipStream_t)s.stream, retarded ? s.t_cross : nullptr, s.phase_rate));
         return BHG_OK;
     }
-    HIP_TRY(bhg::launch_shade(a, (hipStream_t)stream));
+    HIP_TRY(bhg::launch_shade(a, (hipStream_t)s.stream));
     return BHG_OK;
 }
 
@@ -2401,8 +2366,7 @@ int bhg_shade_device(bhg_context *c, const double *d_end, const uint8_t *d_flags
                      const float *d_sky, int32_t sky_w, int32_t sky_h, double *d_rgba, void *stream)
 {
     const bhg_scene sc = sky_scene(d_sky, sky_w, sky_h);
-    return shade(c, d_end, nullptr, d_flags, nullptr, n_pixels, samples, &sc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                 d_rgba, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+    return shade(c, {.end = d_end, .flags = d_flags, .n_pixels = n_pixels, .samples = samples, .sc = &sc, .rgba = d_rgba, .stream = stream});
 }
 
 int bhg_shade_dir_device(bhg_context *c, const double *d_end_dir, const uint8_t *d_flags, size_t n_pixels, int32_t samples,
@@ -2410,15 +2374,15 @@ int bhg_shade_dir_device(bhg_context *c, const double *d_end_dir, const uint8_t 
                          const int64_t *d_scatter, void *stream)
 {
     const bhg_scene sc = sky_scene(d_sky, sky_w, sky_h);
-    return shade(c, nullptr, d_end_dir, d_flags, nullptr, n_pixels, samples, &sc, nullptr, nullptr, nullptr, nullptr, nullptr,
-                 nullptr, d_rgba, d_rgba_f32, d_scatter, nullptr, nullptr, nullptr, nullptr, stream);
+    return shade(c, {.end_dir = d_end_dir, .flags = d_flags, .n_pixels = n_pixels, .samples = samples, .sc = &sc, .rgba = d_rgba,
+                     .rgba_f32 = d_rgba_f32, .scatter = d_scatter, .stream = stream});
 }
 
 int bhg_shade_scene_device(bhg_context *c, const double *d_end, const uint8_t *d_flags, const int8_t *d_object_id,
                            size_t n_pixels, int32_t samples, const bhg_scene *sc, double *d_rgba, void *stream)
 {
-    return shade(c, d_end, nullptr, d_flags, d_object_id, n_pixels, samples, sc, nullptr, nullptr, nullptr, nullptr, nullptr,
-                 nullptr, d_rgba, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+    return shade(c, {.end = d_end, .flags = d_flags, .object_id = d_object_id, .n_pixels = n_pixels, .samples = samples, .sc = sc,
+                     .rgba = d_rgba, .stream = stream});
 }
 
 // the mesh shade: the plain scene shade's checks, then shade_mesh_kernel.  Its own call: shade() above stays
@@ -2427,16 +2391,7 @@ int bhg_shade_mesh_device(bhg_context *c, const double *d_end, const uint8_t *d_
                           size_t n_pixels, int32_t samples, const bhg_scene *sc, const bhg_mesh *mesh, const float *d_tri_rgb,
                           double *d_rgba, float *d_rgba_f32, const int64_t *d_scatter, void *stream)
 {
-    if (!sc) return fail(BHG_E_INVALID, "scene is NULL");
-    if (samples <= 0 || sc->sky_w <= 0 || sc->sky_h <= 0) return fail(BHG_E_INVALID, "samples, sky_w, sky_h must be > 0");
-    if (sc->n_spheres != 0) return fail(BHG_E_INVALID, "the mesh shade does not go with object spheres: n_spheres must be 0");
-    if (sc->n_lamps < 0 || sc->n_lamps > 4) return fail(BHG_E_INVALID, "n_lamps must be in [0, 4]");
-    const bool has_disk = sc->disk_r_out > 0.0;
-    if (has_disk) {
-        if (!(sc->disk_r_out > sc->disk_r_in) || !(sc->disk_stddev > 0.0))
-            return fail(BHG_E_INVALID, "disk needs r_out > r_in and stddev > 0");
-        if (sc->d_disk_tex && (sc->disk_w <= 0 || sc->disk_h <= 0)) return fail(BHG_E_INVALID, "disk texture size must be > 0");
-    }
+    BHG_TRY(scene_check(sc, samples, true));
     if (!mesh) return fail(BHG_E_INVALID, "mesh is NULL");
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
     if (mesh->device != c->device) return fail(BHG_E_INVALID, "the mesh lives on another device than the context");
@@ -2448,25 +2403,12 @@ int bhg_shade_mesh_device(bhg_context *c, const double *d_end, const uint8_t *d_
     std::memset(&a, 0, sizeof(a));
     a.end = d_end;
     a.flags = d_flags;
-    a.sky = sc->d_sky;
     a.rgba = d_rgba;
     a.rgba_f32 = d_rgba_f32;
     a.scatter = d_scatter;
     a.n_pixels = n_pixels;
     a.samples = samples;
-    a.sky_w = sc->sky_w;
-    a.sky_h = sc->sky_h;
-    a.disk_tex = sc->d_disk_tex;
-    a.disk_w = sc->disk_w;
-    a.disk_h = sc->disk_h;
-    a.disk_r_in = sc->disk_r_in;
-    a.disk_r_out = sc->disk_r_out;
-    a.disk_phase = sc->disk_phase;
-    a.disk_mean = sc->disk_mean;
-    a.disk_stddev = sc->disk_stddev;
-    a.disk_intensity = sc->disk_intensity;
-    a.n_lamps = sc->n_lamps;
-    std::memcpy(a.lamps, sc->lamps, sizeof(a.lamps));
+    fill_scene_args(a, sc);
     HIP_TRY(bhg::launch_shade_mesh(a, mesh->view, d_tri_id, d_bary, d_tri_rgb, (hipStream_t)stream));
     return BHG_OK;
 }
@@ -2475,8 +2417,8 @@ int bhg_shade_scene_f32_device(bhg_context *c, const double *d_end, const uint8_
                                size_t n_pixels, int32_t samples, const bhg_scene *sc, float *d_rgba_f32,
                                const int64_t *d_scatter, void *stream)
 {
-    return shade(c, d_end, nullptr, d_flags, d_object_id, n_pixels, samples, sc, nullptr, nullptr, nullptr, nullptr, nullptr,
-                 nullptr, nullptr, d_rgba_f32, d_scatter, nullptr, nullptr, nullptr, nullptr, stream);
+    return shade(c, {.end = d_end, .flags = d_flags, .object_id = d_object_id, .n_pixels = n_pixels, .samples = samples, .sc = sc,
+                     .rgba_f32 = d_rgba_f32, .scatter = d_scatter, .stream = stream});
 }
 
 int bhg_shade_scene_redshift_device(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
@@ -2484,8 +2426,9 @@ int bhg_shade_scene_redshift_device(bhg_context *c, const double *d_end, const d
                                     const bhg_params *p, const bhg_redshift *rs, const double *x0_shared, const double *d_k0,
                                     double *d_rgba, float *d_rgba_f32, const int64_t *d_scatter, void *stream)
 {
-    return shade(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs, nullptr, nullptr, x0_shared, d_k0,
-                 d_rgba, d_rgba_f32, d_scatter, nullptr, nullptr, nullptr, nullptr, stream);
+    return shade(c, {.end = d_end, .end_dir = d_end_dir, .flags = d_flags, .object_id = d_object_id, .n_pixels = n_pixels,
+                     .samples = samples, .sc = sc, .p = p, .rs = rs, .x0_shared = x0_shared, .k0 = d_k0, .rgba = d_rgba,
+                     .rgba_f32 = d_rgba_f32, .scatter = d_scatter, .stream = stream});
 }
 
 int bhg_shade_scene_redshift_observer_device(bhg_context *c, const double *d_end, const double *d_end_dir,
@@ -2495,8 +2438,9 @@ int bhg_shade_scene_redshift_observer_device(bhg_context *c, const double *d_end
                                              const double *d_k0, double *d_rgba, float *d_rgba_f32,
                                              const int64_t *d_scatter, void *stream)
 {
-    return shade(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs, obs, nullptr, x0_shared, d_k0, d_rgba,
-                 d_rgba_f32, d_scatter, nullptr, nullptr, nullptr, nullptr, stream);
+    return shade(c, {.end = d_end, .end_dir = d_end_dir, .flags = d_flags, .object_id = d_object_id, .n_pixels = n_pixels,
+                     .samples = samples, .sc = sc, .p = p, .rs = rs, .obs = obs, .x0_shared = x0_shared, .k0 = d_k0, .rgba = d_rgba,
+                     .rgba_f32 = d_rgba_f32, .scatter = d_scatter, .stream = stream});
 }
 
 int bhg_shade_scene_textured_device(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
@@ -2538,8 +2482,10 @@ int bhg_shade_scene_moving_device(bhg_context *c, const double *d_end, const dou
                                   float *d_rgba_f32, const int64_t *d_scatter, const bhg_polarisation *pol, double *d_qu,
                                   const bhg_disk_thermal *th, const bhg_object_motion *mo, void *stream)
 {
-    return shade(c, d_end, d_end_dir, d_flags, d_object_id, n_pixels, samples, sc, p, rs, obs, ot, x0_shared, d_k0, d_rgba,
-                 d_rgba_f32, d_scatter, pol, d_qu, th, mo, stream);
+    return shade(c, {.end = d_end, .end_dir = d_end_dir, .flags = d_flags, .object_id = d_object_id, .n_pixels = n_pixels,
+                     .samples = samples, .sc = sc, .p = p, .rs = rs, .obs = obs, .ot = ot, .x0_shared = x0_shared, .k0 = d_k0,
+                     .rgba = d_rgba, .rgba_f32 = d_rgba_f32, .scatter = d_scatter, .pol = pol, .qu = d_qu, .th = th, .mo = mo,
+                     .stream = stream});
 }
 
 int bhg_shade_disk_layers_device(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
@@ -2549,9 +2495,8 @@ int bhg_shade_disk_layers_device(bhg_context *c, const double *d_end, const doub
                                  const int64_t *d_scatter, const bhg_disk_thermal *th, const bhg_disk_layers *layers,
                                  void *stream)
 {
-    const LayersIn ly{d_cross, d_n_cross, layers};
-    return shade(c, d_end, d_end_dir, d_flags, nullptr, n_pixels, samples, sc, p, rs, obs, nullptr, x0_shared, d_k0, d_rgba,
-                 d_rgba_f32, d_scatter, nullptr, nullptr, th, nullptr, stream, &ly);
+    return bhg_shade_disk_layers_retarded_device(c, d_end, d_end_dir, d_flags, d_cross, d_n_cross, n_pixels, samples, sc, p, rs, obs,
+                                                 x0_shared, d_k0, d_rgba, d_rgba_f32, d_scatter, th, layers, nullptr, 0.0, stream);
 }
 
 int bhg_shade_disk_layers_retarded_device(bhg_context *c, const double *d_end, const double *d_end_dir, const uint8_t *d_flags,
@@ -2563,9 +2508,10 @@ int bhg_shade_disk_layers_retarded_device(bhg_context *c, const double *d_end, c
 {
     if (!std::isfinite(phase_rate)) return fail(BHG_E_INVALID, "phase_rate must be finite");
     // (phase_rate == 0 or no times: the plain layered shade, its own kernels)
-    const LayersIn ly{d_cross, d_n_cross, layers, d_t_cross, phase_rate};
-    return shade(c, d_end, d_end_dir, d_flags, nullptr, n_pixels, samples, sc, p, rs, obs, nullptr, x0_shared, d_k0, d_rgba,
-                 d_rgba_f32, d_scatter, nullptr, nullptr, th, nullptr, stream, &ly);
+    return shade(c, {.end = d_end, .end_dir = d_end_dir, .flags = d_flags, .n_pixels = n_pixels, .samples = samples, .sc = sc, .p = p,
+                     .rs = rs, .obs = obs, .x0_shared = x0_shared, .k0 = d_k0, .rgba = d_rgba, .rgba_f32 = d_rgba_f32,
+                     .scatter = d_scatter, .th = th, .stream = stream, .layered = true, .cross = d_cross, .n_cross = d_n_cross,
+                     .layers = layers, .t_cross = d_t_cross, .phase_rate = phase_rate});
 }
 
 int bhg_disk_thermal_device(bhg_context *c, const bhg_params *p, const bhg_disk_thermal *th, const bhg_observer *obs,
@@ -2575,13 +2521,11 @@ int bhg_disk_thermal_device(bhg_context *c, const bhg_params *p, const bhg_disk_
     // (the settings are checked before the context: a refusal names its figure with or without a device)
     bhg::ThermalParams tp;
     bhg::RedshiftParams rp;
-    int rc = bhg::thermal_params(p, th, nullptr, nullptr, p && p->disk_r_out > 0.0 ? p->disk_r_in : -1.0, x0_shared, &tp, &rp);
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(bhg::thermal_params(p, th, nullptr, nullptr, p && p->disk_r_out > 0.0 ? p->disk_r_in : -1.0, x0_shared, &tp, &rp));
     bhg::ObserverParams op;
     std::memset(&op, 0, sizeof(op));
     if (obs) {
-        rc = bhg::observer_params(p, obs, x0_shared, &op);
-        if (rc != BHG_OK) return rc;
+        BHG_TRY(bhg::observer_params(p, obs, x0_shared, &op));
     }
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
     if (!x0_shared == !d_x0) return fail(BHG_E_INVALID, "exactly one of x0_shared / d_x0 must be given");
@@ -2611,36 +2555,25 @@ int bhg_disk_thermal_host(bhg_context *c, const bhg_params *p, const bhg_disk_th
 {
     bhg::ThermalParams tp;    // (checked here too, before the context and before any copy)
     bhg::RedshiftParams rp;
-    int rc = bhg::thermal_params(p, th, nullptr, nullptr, p && p->disk_r_out > 0.0 ? p->disk_r_in : -1.0,
-                                 x0_is_shared ? x0 : nullptr, &tp, &rp);
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(bhg::thermal_params(p, th, nullptr, nullptr, p && p->disk_r_out > 0.0 ? p->disk_r_in : -1.0, x0_is_shared ? x0 : nullptr,
+                                &tp, &rp));
     if (obs) {
         bhg::ObserverParams chk;
-        rc = bhg::observer_params(p, obs, x0_is_shared ? x0 : nullptr, &chk);
-        if (rc != BHG_OK) return rc;
+        BHG_TRY(bhg::observer_params(p, obs, x0_is_shared ? x0 : nullptr, &chk));
     }
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
     if (!x0) return fail(BHG_E_INVALID, "x0 is NULL");
     if (n == 0) return BHG_OK;
     if (!k0 || !flags || !t_em || !rgb) return fail(BHG_E_INVALID, "k0 / flags / t_em / rgb is NULL");
     ENTER_DEVICE(c->device);
-    // one block: [x0 (per ray)][k0][end][t_em][rgb] doubles, then the flags
-    const size_t nx = x0_is_shared ? 0 : n * 3, ne = end ? n * 6 : 0;
-    rc = ensure(&c->d_in, &c->d_in_bytes, (nx + n * 3 + ne + n * 4) * sizeof(double) + n);
-    if (rc != BHG_OK) return rc;
-    double *dx = (double *)c->d_in, *dk = dx + nx, *de = dk + n * 3, *dt = de + ne, *dc = dt + n;
-    uint8_t *df = (uint8_t *)(dc + n * 3);
-    if (nx) HIP_TRY(hipMemcpyAsync(dx, x0, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(dk, k0, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (ne) HIP_TRY(hipMemcpyAsync(de, end, ne * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(df, flags, n, hipMemcpyHostToDevice, c->stream));
-    rc = bhg_disk_thermal_device(c, p, th, obs, x0_is_shared ? x0 : nullptr, nx ? dx : nullptr, dk, ne ? de : nullptr, df, n, dt, dc,
-                                 c->stream);
-    if (rc != BHG_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(t_em, dt, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(rgb, dc, n * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return BHG_OK;
+    const size_t b1 = n * sizeof(double);
+    Staged st(c, false);
+    const size_t dx = st.in(x0_is_shared ? nullptr : x0, 3 * b1), dk = st.in(k0, 3 * b1), de = st.in(end, 6 * b1),
+                 df = st.in(flags, n), dt = st.out(t_em, b1), dc = st.out(rgb, 3 * b1);
+    return st.run([&] {
+        return bhg_disk_thermal_device(c, p, th, obs, x0_is_shared ? x0 : nullptr, st.at<double>(dx), st.at<double>(dk), st.at<double>(de),
+                                       st.at<uint8_t>(df), n, st.at<double>(dt), st.at<double>(dc), c->stream);
+    });
 }
 
 int bhg_polarisation_device(bhg_context *c, const bhg_params *p, const bhg_polarisation *pol, const bhg_observer *obs,
@@ -2649,12 +2582,10 @@ int bhg_polarisation_device(bhg_context *c, const bhg_params *p, const bhg_polar
 {
     // (the settings are checked before the context: a refusal names its figure with or without a device)
     bhg::PolarisationParams pp;
-    int rc = bhg::polarisation_params(p, pol, nullptr, obs, p && p->disk_r_out > 0.0 ? p->disk_r_in : -1.0, x0_shared, &pp);
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(bhg::polarisation_params(p, pol, nullptr, obs, p && p->disk_r_out > 0.0 ? p->disk_r_in : -1.0, x0_shared, &pp));
     if (obs) {
         bhg::ObserverParams chk;
-        rc = bhg::observer_params(p, obs, x0_shared, &chk);
-        if (rc != BHG_OK) return rc;
+        BHG_TRY(bhg::observer_params(p, obs, x0_shared, &chk));
     }
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
     if (!x0_shared == !d_x0) return fail(BHG_E_INVALID, "exactly one of x0_shared / d_x0 must be given");
@@ -2682,37 +2613,25 @@ int bhg_polarisation_host(bhg_context *c, const bhg_params *p, const bhg_polaris
                           double *evpa, double *degree, double *mu)
 {
     bhg::PolarisationParams pp;   // (checked here too, before the context and before any copy)
-    int rc = bhg::polarisation_params(p, pol, nullptr, obs, p && p->disk_r_out > 0.0 ? p->disk_r_in : -1.0,
-                                      x0_is_shared ? x0 : nullptr, &pp);
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(bhg::polarisation_params(p, pol, nullptr, obs, p && p->disk_r_out > 0.0 ? p->disk_r_in : -1.0, x0_is_shared ? x0 : nullptr,
+                                     &pp));
     if (obs) {
         bhg::ObserverParams chk;
-        rc = bhg::observer_params(p, obs, x0_is_shared ? x0 : nullptr, &chk);
-        if (rc != BHG_OK) return rc;
+        BHG_TRY(bhg::observer_params(p, obs, x0_is_shared ? x0 : nullptr, &chk));
     }
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
     if (!x0) return fail(BHG_E_INVALID, "x0 is NULL");
     if (n == 0) return BHG_OK;
     if (!k0 || !flags || !evpa || !degree) return fail(BHG_E_INVALID, "k0 / flags / evpa / degree is NULL");
     ENTER_DEVICE(c->device);
-    // one block: [x0 (per ray)][k0][end][evpa][degree][mu] doubles, then the flags
-    const size_t nx = x0_is_shared ? 0 : n * 3, ne = end ? n * 6 : 0;
-    rc = ensure(&c->d_in, &c->d_in_bytes, (nx + n * 3 + ne + n * 3) * sizeof(double) + n);
-    if (rc != BHG_OK) return rc;
-    double *dx = (double *)c->d_in, *dk = dx + nx, *de = dk + n * 3, *dc = de + ne, *dd = dc + n, *dm = dd + n;
-    uint8_t *df = (uint8_t *)(dm + n);
-    if (nx) HIP_TRY(hipMemcpyAsync(dx, x0, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(dk, k0, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (ne) HIP_TRY(hipMemcpyAsync(de, end, ne * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(df, flags, n, hipMemcpyHostToDevice, c->stream));
-    rc = bhg_polarisation_device(c, p, pol, obs, x0_is_shared ? x0 : nullptr, nx ? dx : nullptr, dk, ne ? de : nullptr, df, n, dc, dd,
-                                 dm, c->stream);
-    if (rc != BHG_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(evpa, dc, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(degree, dd, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (mu) HIP_TRY(hipMemcpyAsync(mu, dm, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return BHG_OK;
+    const size_t b1 = n * sizeof(double);
+    Staged st(c, false);
+    const size_t dx = st.in(x0_is_shared ? nullptr : x0, 3 * b1), dk = st.in(k0, 3 * b1), de = st.in(end, 6 * b1),
+                 df = st.in(flags, n), dc = st.out(evpa, b1), dd = st.out(degree, b1), dm = st.out(mu, b1);
+    return st.run([&] {
+        return bhg_polarisation_device(c, p, pol, obs, x0_is_shared ? x0 : nullptr, st.at<double>(dx), st.at<double>(dk), st.at<double>(de),
+                                       st.at<uint8_t>(df), n, st.at<double>(dc), st.at<double>(dd), st.at<double>(dm), c->stream);
+    });
 }
 
 int bhg_redshift_device(bhg_context *c, const bhg_params *p, const bhg_redshift *rs, const double *x0_shared,
@@ -2737,22 +2656,19 @@ int bhg_redshift_motion_device(bhg_context *c, const bhg_params *p, const bhg_re
 {
     // (the settings are checked before the context: a refusal names its figure with or without a device)
     bhg::RedshiftParams rp;
-    int rc = bhg::redshift_params(p, rs, p && p->disk_r_out > 0.0 ? p->disk_r_in : -1.0, x0_shared, &rp);
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(bhg::redshift_params(p, rs, p && p->disk_r_out > 0.0 ? p->disk_r_in : -1.0, x0_shared, &rp));
     bhg::MotionParams mp;
     std::memset(&mp, 0, sizeof(mp));
     if (motion) {
         if (n_spheres < 0 || n_spheres > BHG_MAX_SPHERES)
             return fail(BHG_E_INVALID, "n_spheres must be in [0, BHG_MAX_SPHERES], not " + std::to_string(n_spheres));
         if (n_spheres > 0 && !spheres) return fail(BHG_E_INVALID, "spheres is NULL");
-        rc = bhg::motion_params(p, motion, spheres, n_spheres, &mp);
-        if (rc != BHG_OK) return rc;
+        BHG_TRY(bhg::motion_params(p, motion, spheres, n_spheres, &mp));
     }
     bhg::ObserverParams op;
     std::memset(&op, 0, sizeof(op));
     if (obs) {
-        rc = bhg::observer_params(p, obs, x0_shared, &op);
-        if (rc != BHG_OK) return rc;
+        BHG_TRY(bhg::observer_params(p, obs, x0_shared, &op));
     }
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
     if (!x0_shared == !d_x0) return fail(BHG_E_INVALID, "exactly one of x0_shared / d_x0 must be given");
@@ -2801,21 +2717,18 @@ int bhg_redshift_motion_host(bhg_context *c, const bhg_params *p, const bhg_reds
                              size_t n, double *g)
 {
     bhg::RedshiftParams rp;   // (checked here too, before the context and before any copy)
-    int rc = bhg::redshift_params(p, rs, p && p->disk_r_out > 0.0 ? p->disk_r_in : -1.0, x0_is_shared ? x0 : nullptr, &rp);
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(bhg::redshift_params(p, rs, p && p->disk_r_out > 0.0 ? p->disk_r_in : -1.0, x0_is_shared ? x0 : nullptr, &rp));
     bhg::MotionParams mp;
     std::memset(&mp, 0, sizeof(mp));
     if (motion) {
         if (n_spheres < 0 || n_spheres > BHG_MAX_SPHERES)
             return fail(BHG_E_INVALID, "n_spheres must be in [0, BHG_MAX_SPHERES], not " + std::to_string(n_spheres));
         if (n_spheres > 0 && !spheres) return fail(BHG_E_INVALID, "spheres is NULL");
-        rc = bhg::motion_params(p, motion, spheres, n_spheres, &mp);
-        if (rc != BHG_OK) return rc;
+        BHG_TRY(bhg::motion_params(p, motion, spheres, n_spheres, &mp));
     }
     bhg::ObserverParams op;
     if (obs) {
-        rc = bhg::observer_params(p, obs, x0_is_shared ? x0 : nullptr, &op);
-        if (rc != BHG_OK) return rc;
+        BHG_TRY(bhg::observer_params(p, obs, x0_is_shared ? x0 : nullptr, &op));
     }
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
     if (!x0) return fail(BHG_E_INVALID, "x0 is NULL");
@@ -2823,24 +2736,15 @@ int bhg_redshift_motion_host(bhg_context *c, const bhg_params *p, const bhg_reds
     if (!k0 || !flags || !g) return fail(BHG_E_INVALID, "k0 / flags / g is NULL");
     if (mp.on && !object_id) return fail(BHG_E_INVALID, "moving object spheres need object_id");
     ENTER_DEVICE(c->device);
-    // one block: [x0 (per ray)][k0][end][g] doubles, then the flags, then the object ids (moving spheres only)
-    const size_t nx = x0_is_shared ? 0 : n * 3, ne = end ? n * 6 : 0, no = mp.on ? n : 0;
-    rc = ensure(&c->d_in, &c->d_in_bytes, (nx + n * 3 + ne + n) * sizeof(double) + n + no);
-    if (rc != BHG_OK) return rc;
-    double *dx = (double *)c->d_in, *dk = dx + nx, *de = dk + n * 3, *dg = de + ne;
-    uint8_t *df = (uint8_t *)(dg + n);
-    int8_t *dob = (int8_t *)(df + n);
-    if (nx) HIP_TRY(hipMemcpyAsync(dx, x0, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(dk, k0, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (ne) HIP_TRY(hipMemcpyAsync(de, end, ne * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(df, flags, n, hipMemcpyHostToDevice, c->stream));
-    if (no) HIP_TRY(hipMemcpyAsync(dob, object_id, no, hipMemcpyHostToDevice, c->stream));
-    rc = bhg_redshift_motion_device(c, p, rs, obs, motion, spheres, n_spheres, x0_is_shared ? x0 : nullptr, nx ? dx : nullptr, dk,
-                                    ne ? de : nullptr, df, no ? dob : nullptr, n, dg, c->stream);
-    if (rc != BHG_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(g, dg, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return BHG_OK;
+    const size_t b1 = n * sizeof(double);
+    Staged st(c, false);
+    const size_t dx = st.in(x0_is_shared ? nullptr : x0, 3 * b1), dk = st.in(k0, 3 * b1), de = st.in(end, 6 * b1),
+                 df = st.in(flags, n), dob = st.in(mp.on ? object_id : nullptr, n), dg = st.out(g, b1);
+    return st.run([&] {
+        return bhg_redshift_motion_device(c, p, rs, obs, motion, spheres, n_spheres, x0_is_shared ? x0 : nullptr, st.at<double>(dx),
+                                          st.at<double>(dk), st.at<double>(de), st.at<uint8_t>(df), st.at<int8_t>(dob), n,
+                                          st.at<double>(dg), c->stream);
+    });
 }
 
 int bhg_assemble_frame_f32_device(bhg_context *c, const float *d_slabs, const int64_t *d_index, size_t n_pixels,
@@ -2989,15 +2893,12 @@ int bhg_trajectory_objects(bhg_context *c, const bhg_params *p, const double *sp
 int bhg_acceleration(bhg_context *c, const bhg_params *p, const double *x, const double *k, size_t n, double *acc)
 {
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
-    int rc = validate(p);
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(validate(p));
     if (n == 0) return BHG_OK;
     if (!x || !k || !acc) return fail(BHG_E_INVALID, "x / k / acc is NULL");
     ENTER_DEVICE(c->device);
-    rc = ensure(&c->d_in, &c->d_in_bytes, n * 6 * sizeof(double));
-    if (rc != BHG_OK) return rc;
-    rc = ensure(&c->d_out, &c->d_out_bytes, n * 3 * sizeof(double));
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(ensure(&c->d_in, &c->d_in_bytes, n * 6 * sizeof(double)));
+    BHG_TRY(ensure(&c->d_out, &c->d_out_bytes, n * 3 * sizeof(double)));
     double *dx = (double *)c->d_in, *dk = dx + 3 * n;
     HIP_TRY(hipMemcpyAsync(dx, x, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(dk, k, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -3017,8 +2918,7 @@ int bhg_peak_probe(bhg_context *c, int32_t kind, double target_ms, double out[6]
     ENTER_DEVICE(c->device);
     const int per_cu = 12;                       // the Schwarzschild trace kernels' residency (3 waves per SIMD)
     const int grid = per_cu * c->num_cus;
-    int rc = ensure(&c->d_out, &c->d_out_bytes, (size_t)grid * 64 * sizeof(double));
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(ensure(&c->d_out, &c->d_out_bytes, (size_t)grid * 64 * sizeof(double)));
     hipEvent_t e0 = nullptr, e1 = nullptr;
     HIP_TRY(hipEventCreate(&e0));
     hipError_t he = hipEventCreate(&e1);
@@ -3078,10 +2978,8 @@ int bhg_math_probe(bhg_context *c, int32_t op, const double *in, size_t n, doubl
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
     if (n == 0) return BHG_OK;
     ENTER_DEVICE(c->device);
-    int rc = ensure(&c->d_in, &c->d_in_bytes, n * (size_t)n_in * sizeof(double));
-    if (rc != BHG_OK) return rc;
-    rc = ensure(&c->d_out, &c->d_out_bytes, n * (size_t)n_out * sizeof(double));
-    if (rc != BHG_OK) return rc;
+    BHG_TRY(ensure(&c->d_in, &c->d_in_bytes, n * (size_t)n_in * sizeof(double)));
+    BHG_TRY(ensure(&c->d_out, &c->d_out_bytes, n * (size_t)n_out * sizeof(double)));
     HIP_TRY(hipMemcpyAsync(c->d_in, in, n * (size_t)n_in * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(bhg::launch_math_probe(op, (const double *)c->d_in, n, (double *)c->d_out, c->stream));
     HIP_TRY(hipMemcpyAsync(out, c->d_out, n * (size_t)n_out * sizeof(double), hipMemcpyDeviceToHost, c->stream));

@@ -6,8 +6,8 @@ directions, flags, n_steps, n_accepted and object_id -- between a plain call, a 
 rays, through the raw entry point (every kernel variant, the shapes at which the indexing can go wrong), through the owners of
 a cache (DeviceFrame, FrameBatch, the library's bhg_frame) and across everything that must, or must not, invalidate one.
 
-The split of a call of more than 2^26 rays walks d_start_steps along with d_k0 (trace_device_impl, bhgeo_capi.hip): that size
-cannot be reached in a test and no tuning hook lowers the limit, so the offset is checked by reading, not here.
+The split of a call of more than 2^26 rays walks d_start_steps along with d_k0 (TraceCall::slice, csrc/trace_call.h): that size
+cannot be reached in a GPU test, so the offset is checked at a limit of 64 rays by tests/test_trace_call_host.py, not here.
 """
 import numpy as np
 import pytest
