@@ -70,8 +70,10 @@ EXPORTS = (
     "bhg_travel_time_device", "bhg_travel_time", "bhg_shade_disk_layers_retarded_device",
     "bhg_mesh_create", "bhg_mesh_destroy", "bhg_mesh_info", "bhg_mesh_bvh_host", "bhg_trace_mesh_device", "bhg_trace_mesh",
     "bhg_shade_mesh_device",
+    "bhg_mesh_material_size", "bhg_shade_mesh_material_device", "bhg_frame_set_mesh",
 )
 MESH_MAX_SUBSTEPS = 1024   # BHG_MESH_MAX_SUBSTEPS: sub-chords per accepted step at most (BHG_MESH)
+MESH_TEXTURES_MAX = 8      # BHG_MESH_TEXTURES_MAX: images a mesh material holds at most (BHG_MESH_MATERIAL)
 MAX_CROSSINGS = 4   # BHG_MAX_CROSSINGS: disk crossings a crossings trace stores per ray (BHG_DISK_CROSSINGS)
 START_NONE, START_RECORD, START_REPLAY = 0, 1, 2   # BHG_START_*: the rays' initial steps kept across calls (BHG_START_STEPS)
 # BHG_PREFIX_*: the rays' start-up records kept across calls (BHG_START_PREFIX)
@@ -268,6 +270,61 @@ def make_object_textures(textures=None, rotations=None, modes=None, emission=Non
         if k is not None:
             ot.emission[j] = float(k)
     return ot, keep
+
+
+class MeshMaterialStruct(C.Structure):
+    """struct bhg_mesh_material (include/bhgeo.h)."""
+    _fields_ = [("tri_rgb", C.c_void_p), ("tri_uv", C.c_void_p), ("tri_tex", C.c_void_p), ("tex", C.c_void_p * 8),
+                ("tex_w", C.c_int32 * 8), ("tex_h", C.c_int32 * 8), ("n_tex", C.c_int32), ("emission", C.c_double)]
+
+
+class MeshMaterial:
+    """A mesh's surface (bhg_mesh_material), as host arrays: tri_rgb [nt, 3] float32 per triangle (None:
+    white), tri_uv [nt, 3, 2] float32 per corner in the triangle's vertex order (None: no textures), tri_tex [nt] int32 image
+    slot per triangle (< 0: none; None: slot 0), textures: up to 8 [h, w, 4] float32 RGBA images, row 0 at V = 0, repeating in
+    both directions; emission >= 0 is added to the lamp sum.  colour = tri_rgb * texel * (lamp_sum + emission)."""
+
+    def __init__(self, tri_rgb=None, tri_uv=None, tri_tex=None, textures=(), emission=0.0):
+        self.tri_rgb = None if tri_rgb is None else np.ascontiguousarray(tri_rgb, dtype=np.float32)
+        self.tri_uv = None if tri_uv is None else np.ascontiguousarray(tri_uv, dtype=np.float32)
+        self.tri_tex = None if tri_tex is None else np.ascontiguousarray(tri_tex, dtype=np.int32)
+        self.textures = [np.ascontiguousarray(t, dtype=np.float32) for t in textures]
+        self.emission = float(emission)
+        if self.tri_rgb is not None and (self.tri_rgb.ndim != 2 or self.tri_rgb.shape[1] != 3):
+            raise ValueError("tri_rgb must have shape [n_triangles, 3]")
+        if self.tri_uv is not None and self.tri_uv.shape[1:] != (3, 2):
+            raise ValueError("tri_uv must have shape [n_triangles, 3, 2]")
+        if self.tri_tex is not None and self.tri_tex.ndim != 1:
+            raise ValueError("tri_tex must have shape [n_triangles]")
+        if len(self.textures) > MESH_TEXTURES_MAX:
+            raise ValueError(f"at most {MESH_TEXTURES_MAX} textures")
+        for j, t in enumerate(self.textures):
+            if t.ndim != 3 or t.shape[2] != 4:
+                raise ValueError(f"texture {j} must be [h, w, 4] float32, not {t.shape}")
+
+    def check_triangles(self, nt):
+        for name in ("tri_rgb", "tri_uv", "tri_tex"):
+            a = getattr(self, name)
+            if a is not None and a.shape[0] != nt:
+                raise ValueError(f"{name} must have one entry per triangle ({nt}), not {a.shape[0]}")
+
+    def arrays(self):
+        """(tri_rgb, tri_uv, tri_tex, *textures): the host arrays in the order struct() takes addresses, None where not given."""
+        return (self.tri_rgb, self.tri_uv, self.tri_tex, *self.textures)
+
+    def struct(self, addresses=None):
+        """The C struct over this material's host arrays, or over `addresses` -- one per entry of arrays(), 0 / None for an
+        array that is not given: the device copies."""
+        if addresses is None:
+            addresses = [None if a is None else a.ctypes.data for a in self.arrays()]
+        m = MeshMaterialStruct()
+        m.tri_rgb, m.tri_uv, m.tri_tex = (a or None for a in addresses[:3])
+        for j, t in enumerate(self.textures):
+            m.tex[j] = addresses[3 + j] or None
+            m.tex_w[j], m.tex_h[j] = t.shape[1], t.shape[0]
+        m.n_tex = len(self.textures)
+        m.emission = self.emission
+        return m
 
 
 class Camera(C.Structure):
@@ -659,6 +716,15 @@ def load():
     L.bhg_shade_mesh_device.restype = C.c_int
     L.bhg_shade_mesh_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32,
                                         C.POINTER(Scene), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bhg_mesh_material_size.restype = C.c_size_t
+    L.bhg_mesh_material_size.argtypes = []
+    L.bhg_shade_mesh_material_device.restype = C.c_int
+    L.bhg_shade_mesh_material_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32,
+                                                 C.POINTER(Scene), C.c_void_p, C.POINTER(MeshMaterialStruct), C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bhg_frame_set_mesh.restype = C.c_int
+    L.bhg_frame_set_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32, C.c_double,
+                                     C.POINTER(MeshMaterialStruct)]
     if L.bhg_version() != ABI_VERSION or not hasattr(L, "bhg_abi_check"):
         raise ImportError(f"libbhgeo ABI {L.bhg_version()} != expected {ABI_VERSION}: rebuild {LIB_PATH}")
     for name in ("bhg_params_size", "bhg_camera_size", "bhg_scene_size", "bhg_frame_scene_size"):
@@ -690,6 +756,9 @@ def load():
     if L.bhg_object_textures_size() != C.sizeof(ObjectTextures):
         raise ImportError(f"libbhgeo: bhg_object_textures is {L.bhg_object_textures_size()} bytes, this binding's "
                           f"{C.sizeof(ObjectTextures)}")
+    if L.bhg_mesh_material_size() != C.sizeof(MeshMaterialStruct):
+        raise ImportError(f"libbhgeo: bhg_mesh_material is {L.bhg_mesh_material_size()} bytes, this binding's "
+                          f"{C.sizeof(MeshMaterialStruct)}")
     _lib = L
     return L
 
@@ -1091,6 +1160,30 @@ class Frame:
             return
         _check(load().bhg_frame_set_object_motion(self._h, C.byref(make_object_motion(velocity, angular_velocity))))
 
+    def set_mesh(self, vertices=None, triangles=None, vertex_normals=None, leaf_size=4, chord=None, material=None):
+        """A triangle mesh in every later render (bhg_frame_set_mesh): vertices [nv, 3] float64, Cartesian
+        and centred on the hole, triangles [nt, 3] int32, vertex_normals [nv, 3] or None (flat shading), chord the sub-chord
+        length of the trace (None: a quarter of r_s at render time), material a MeshMaterial or None (white, no emission).
+        Everything is copied.  Not with scene spheres, redshift, the thermal disk, object motion or object textures (refused
+        at render).  set_mesh(None): off -- the frame as without a mesh, bit for bit."""
+        if vertices is None:
+            _check(load().bhg_frame_set_mesh(self._h, None, 0, None, 0, None, 0, 0.0, None))
+            return
+        V, F = _mesh_arrays(vertices, triangles)
+        N = None
+        if vertex_normals is not None:
+            N = np.ascontiguousarray(vertex_normals, dtype=np.float64)
+            if N.shape != V.shape:
+                raise ValueError("vertex_normals must have the shape of vertices")
+        if chord is not None and not (np.isfinite(float(chord)) and float(chord) > 0.0):
+            raise ValueError("chord must be finite and > 0")
+        m = None
+        if material is not None:
+            material.check_triangles(F.shape[0])
+            m = material.struct()
+        _check(load().bhg_frame_set_mesh(self._h, _addr(V), V.shape[0], _addr(F), F.shape[0], None if N is None else _addr(N),
+                                         int(leaf_size), 0.0 if chord is None else float(chord), None if m is None else C.byref(m)))
+
     def render(self, params: "Params", out=None, to_host=True):
         """One frame: float32 [H, W, 4] (a new array, or `out`).  to_host=False: only enqueue; the image stays on the
         first device (device_image(), synchronize())."""
@@ -1343,6 +1436,17 @@ class Context:
                                             C.byref(scene), None if mesh is None else mesh._h, C.c_void_p(d_tri_rgb or None),
                                             C.c_void_p(d_rgba or None), C.c_void_p(d_rgba_f32 or None),
                                             C.c_void_p(d_scatter or None), C.c_void_p(stream or None)))
+
+    def shade_mesh_material_device(self, d_end, d_flags, d_tri_id, d_bary, n_pixels, samples, scene: "Scene", mesh: "Mesh", material,
+                                   d_rgba=0, d_rgba_f32=0, d_scatter=0, stream=0):
+        """bhg_shade_mesh_material_device: shade_mesh_device with a material (a MeshMaterialStruct of DEVICE addresses) in place of
+        d_tri_rgb -- mesh rays get tri_rgb * texel * (lamp_sum + emission)."""
+        _check(load().bhg_shade_mesh_material_device(self._h, C.c_void_p(d_end or None), C.c_void_p(d_flags or None),
+                                                     C.c_void_p(d_tri_id or None), C.c_void_p(d_bary or None), n_pixels, samples,
+                                                     C.byref(scene), None if mesh is None else mesh._h,
+                                                     None if material is None else C.byref(material), C.c_void_p(d_rgba or None),
+                                                     C.c_void_p(d_rgba_f32 or None), C.c_void_p(d_scatter or None),
+                                                     C.c_void_p(stream or None)))
 
     def trajectory(self, k0, x0, params: Params, n_points, spheres=None):
         """Sampled curves: (traj[N,6,T], n_valid[N], end[N,6], flags[N]); with spheres= (object spheres in the curved region,

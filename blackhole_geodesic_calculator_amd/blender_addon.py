@@ -44,6 +44,12 @@ Known deviations from the reference, all deliberate:
     kernel argument.  The reference's literal mapping (arctan(n_y/n_x), read at (ph/2pi, th/pi)) folds the two
     x-hemispheres and reads a quarter of the image: deliberately not reproduced.  A scene without these properties renders
     exactly as before.
+  * scene.curved_space_meshes (default 0): with the device path, every mesh object but the black-hole
+    marker is traced as its TRIANGLES, not as its bounding sphere -- the evaluated mesh's loop_triangles through matrix_world,
+    the active UV layer per corner, `curved_space_texture` as the image on those UVs (at most 8 distinct images),
+    the largest `curved_space_emission` as the mesh's emission, smooth shading when every polygon is smooth
+    (bhg_frame_set_mesh; the mesh is uploaded only when it changed).  On the host path or with a mark_* window: one warning,
+    and the render as with 0.
 """
 import warnings
 import os
@@ -160,8 +166,20 @@ class RelativisticRenderEngine(bpy.types.RenderEngine):
         spheres = self.scene_spheres(depsgraph) if want_objects else np.zeros((0, 4))
         self._lit_spheres = spheres
         self._sphere_looks = self.sphere_looks() if want_objects else []
-        if getattr(self, "device_shading", False) and mark is None:
-            yield from self.ray_trace_device(width, height, samples, buf, origin, rotation, spheres)
+        on_device = getattr(self, "device_shading", False) and mark is None
+        # mesh objects as their triangles (scene.curved_space_meshes): the device path only
+        want_meshes = float(getattr(depsgraph.scene, "curved_space_meshes", 0) or 0) != 0.0
+        if want_meshes and not on_device:
+            warnings.warn("curved_space_meshes needs the device path (device_shading = 1 and no mark_* window): rendering as with "
+                          "curved_space_meshes = 0", RuntimeWarning)
+            want_meshes = False
+        if on_device:
+            mesh = None
+            if want_meshes:
+                # (a mesh does not go with object spheres: every mesh object is its triangles now)
+                spheres, self._lit_spheres, self._sphere_looks = np.zeros((0, 4)), np.zeros((0, 4)), []
+                mesh = self.scene_mesh(depsgraph)
+            yield from self.ray_trace_device(width, height, samples, buf, origin, rotation, spheres, mesh=mesh)
             return
         tracer = FrameTracer(
             self.GeoInt, width, height, samples, fov_x=self.field_of_view_x, fov_y=self.field_of_view_y,
@@ -189,6 +207,108 @@ class RelativisticRenderEngine(bpy.types.RenderEngine):
             warnings.warn(f"{len(out)} mesh objects in the scene: only the 8 nearest to the hole are traced", RuntimeWarning)
         self._sphere_objects = [ob for _, ob in out[:8]]
         return np.array([sp for sp, _ in out[:8]], dtype=np.float64).reshape(-1, 4)
+
+    MESH_IMAGES_MAX = 8      # _ffi.MESH_TEXTURES_MAX: image slots of a mesh material
+
+    def scene_mesh(self, depsgraph):
+        """Every MESH object of the scene but the black-hole marker as ONE triangle mesh, BH-centred (scene.curved_space_meshes):
+        dict(vertices [nv, 3] float64, triangles [nt, 3] int32, normals [nv, 3] or None, tri_uv [nt, 3, 2] float32 or None,
+        tri_tex [nt] int32, images: the slots' bpy.data.images names, emission, offsets: per object (first vertex, first
+        triangle)); None without triangles.  Geometry is the evaluated object's: calc_loop_triangles(), loop_triangles
+        (.vertices, .loops), vertices[].co through matrix_world; UVs uv_layers.active.data[loop].uv per corner -- all read with
+        foreach_get into numpy buffers.  tri_tex is the slot of the object's curved_space_texture image (-1: none; at most 8
+        distinct images), emission the largest curved_space_emission; vertex normals are passed only when every polygon of
+        every object is smooth."""
+        bh = getattr(depsgraph.scene, "blackhole_obj", None)
+        V, F, N, UV, TEX, offsets, images = [], [], [], [], [], [], []
+        emission, smooth, any_uv, nv, nt, dropped = 0.0, True, False, 0, 0, 0
+        for ob in depsgraph.scene.objects:
+            if ob.type != "MESH" or ob is bh:
+                continue
+            ev = ob.evaluated_get(depsgraph) if hasattr(ob, "evaluated_get") else ob
+            me = ev.to_mesh()
+            try:
+                me.calc_loop_triangles()
+                n_v, n_t = len(me.vertices), len(me.loop_triangles)
+                if n_v == 0 or n_t == 0:
+                    continue
+                co = np.empty(n_v * 3, dtype=np.float32)
+                me.vertices.foreach_get("co", co)
+                tri = np.empty(n_t * 3, dtype=np.int32)
+                me.loop_triangles.foreach_get("vertices", tri)
+                mw = np.array([[float(ev.matrix_world[i][k]) for k in range(4)] for i in range(4)], dtype=np.float64)
+                co = co.reshape(n_v, 3).astype(np.float64)
+                V.append(co @ mw[:3, :3].T + mw[:3, 3] - self.bh_loc)
+                F.append(tri.reshape(n_t, 3) + nv)
+                flags = np.empty(len(me.polygons), dtype=bool)
+                me.polygons.foreach_get("use_smooth", flags)
+                smooth = smooth and bool(flags.all())
+                nrm = np.empty(n_v * 3, dtype=np.float32)
+                me.vertices.foreach_get("normal", nrm)
+                # (normals go with the inverse transpose; the kernel normalises them)
+                N.append(nrm.reshape(n_v, 3).astype(np.float64) @ np.linalg.inv(mw[:3, :3]))
+                uv = np.zeros((n_t, 3, 2), dtype=np.float32)
+                slot = -1
+                layer = getattr(getattr(me, "uv_layers", None), "active", None)
+                name = self._custom(ob, "curved_space_texture")
+                name = str(name) if name else None
+                if name is not None and name not in bpy.data.images:
+                    warnings.warn(f"curved_space_texture {name!r}: no such image in bpy.data.images (the object stays untextured)",
+                                  RuntimeWarning)
+                    name = None
+                if layer is not None and name is not None:
+                    loops = np.empty(n_t * 3, dtype=np.int32)
+                    me.loop_triangles.foreach_get("loops", loops)
+                    luv = np.empty(len(layer.data) * 2, dtype=np.float32)
+                    layer.data.foreach_get("uv", luv)
+                    uv = luv.reshape(-1, 2)[loops].reshape(n_t, 3, 2)
+                    if name in images:
+                        slot = images.index(name)
+                    elif len(images) < self.MESH_IMAGES_MAX:
+                        images.append(name)
+                        slot = len(images) - 1
+                    else:
+                        dropped += 1
+                    any_uv = any_uv or slot >= 0
+                UV.append(uv)
+                TEX.append(np.full(n_t, slot, dtype=np.int32))
+                emission = max(emission, float(self._custom(ob, "curved_space_emission") or 0.0))
+                offsets.append((nv, nt))
+                nv, nt = nv + n_v, nt + n_t
+            finally:
+                if hasattr(ev, "to_mesh_clear"):
+                    ev.to_mesh_clear()
+        if dropped:
+            warnings.warn(f"more than {self.MESH_IMAGES_MAX} distinct curved_space_texture images: {dropped} object(s) stay "
+                          "untextured", RuntimeWarning)
+        if nt == 0:
+            return None
+        return {"vertices": np.concatenate(V), "triangles": np.concatenate(F).astype(np.int32),
+                "normals": np.concatenate(N) if smooth else None,
+                "tri_uv": np.ascontiguousarray(np.concatenate(UV)) if any_uv else None, "tri_tex": np.concatenate(TEX),
+                "images": images if any_uv else [], "emission": emission, "offsets": offsets}
+
+    def _set_device_mesh(self, fr, mesh):
+        """The scene's mesh on the library-owned frame: set_mesh only when vertices, triangles, normals or the material differ
+        from what the frame holds (images by _image_identity) -- an animation of a static mesh uploads nothing."""
+        held = getattr(fr, "mesh_held", None)
+        if mesh is None:
+            if held is not None:
+                fr.set_mesh(None)
+            fr.mesh_held = None
+            return
+        ids = [self._image_identity(n) for n in mesh["images"]]
+        same = held is not None and all(i is not None for i in ids) and ids == held["ids"] and \
+            mesh["emission"] == held["emission"] and \
+            all((mesh[k] is None) == (held[k] is None) and (mesh[k] is None or np.array_equal(mesh[k], held[k]))
+                for k in ("vertices", "triangles", "normals", "tri_uv", "tri_tex"))
+        if same:
+            return
+        from . import _ffi
+        material = _ffi.MeshMaterial(tri_uv=mesh["tri_uv"], tri_tex=mesh["tri_tex"] if mesh["tri_uv"] is not None else None,
+                                     textures=[self._image_pixels(n) for n in mesh["images"]], emission=mesh["emission"])
+        fr.set_mesh(mesh["vertices"], mesh["triangles"], vertex_normals=mesh["normals"], material=material)
+        fr.mesh_held = {**{k: mesh[k] for k in ("vertices", "triangles", "normals", "tri_uv", "tri_tex", "emission")}, "ids": ids}
 
     @staticmethod
     def _custom(ob, key):
@@ -348,7 +468,7 @@ class RelativisticRenderEngine(bpy.types.RenderEngine):
             px[:] = np.asarray(img.pixels[:], dtype=np.float32)
         return px.reshape(h, w, 4)
 
-    def ray_trace_device(self, width, height, samples, buf, origin, rotation, spheres):
+    def ray_trace_device(self, width, height, samples, buf, origin, rotation, spheres, mesh=None):
         """The generator protocol of ray_trace with everything between the jitter stream and the averaged pixels on
         the GPU(s): a library-owned frame (bhg_frame_*, include/bhgeo.h; _ffi.Frame -- ctypes only, no PyTorch: Blender's
         bundled Python has none).  Per listed device ONE ray-generation launch, ONE trace launch for all samples, ONE
@@ -390,6 +510,7 @@ class RelativisticRenderEngine(bpy.types.RenderEngine):
             if len(spheres) > 0:
                 sp = np.array(spheres, dtype=np.float64).reshape(-1, 4)
                 sp[:, 0:3] -= self.bh_loc                    # the solver and the shade kernel work BH-centred
+            if len(spheres) > 0 or mesh is not None:
                 all_lamps = getattr(self, "lamps", [])
                 if len(all_lamps) > 4:
                     # (the host path sums over every lamp; the device scene holds four -- say so instead of quietly
@@ -410,6 +531,7 @@ class RelativisticRenderEngine(bpy.types.RenderEngine):
             fr.set_scene(sky, spheres=sp, sphere_rgb=None if sp is None else np.ones((len(sp), 3)), lamps=lamps)
             fr.sky_identity = sky_id
             self._set_device_object_textures(fr)
+            self._set_device_mesh(fr, mesh)
             rgba = fr.render(self.GeoInt.params(self.max_integration_step, self.int_depth_curve_end))
             buf[:, :, :] = rgba.reshape(height, width, 4)
             self.last_device_frame = fr.info()
@@ -493,6 +615,7 @@ class CUSTOM_RENDER_PT_blackhole(RenderButtonsPanel, Panel):
              ("field_of_view_y", "field_of_view_y"), ("sampling_seed", "Sampling seed"), ("sky_image", "Sky image"),
              ("mark_x_min", "mark_x_min"), ("mark_x_max", "mark_x_max"), ("mark_y_min", "mark_y_min"),
              ("mark_y_max", "mark_y_max"), ("curved_space_objects", "Objects in curved space (0/1)"),
+             ("curved_space_meshes", "Mesh objects as triangles (0/1)"),
              ("device_shading", "Shade on the GPU (0/1)"), ("render_devices", "GPUs to render on"))
 
     def draw(self, context):
@@ -521,6 +644,7 @@ PROPS = [
 # the number of GPUs the device path shards the image over
 EXTRA_PROPS = [
     ("curved_space_objects", bpy.props.FloatProperty(name="curved_space_objects", default=0)),
+    ("curved_space_meshes", bpy.props.FloatProperty(name="curved_space_meshes", default=0)),
     ("device_shading", bpy.props.FloatProperty(name="device_shading", default=0)),
     ("render_devices", bpy.props.FloatProperty(name="render_devices", default=1)),
 ]

@@ -851,6 +851,45 @@ int object_texture_params(const bhg_object_textures *ot, int32_t n_spheres, Obje
     out->on = 1;
     return BHG_OK;
 }
+
+// A mesh material (include/bhgeo.h, "mesh material") for a mesh of nt triangles.  host_arrays: tri_uv and tri_tex are host
+// arrays and are scanned (bhg_frame_set_mesh); otherwise only the struct's own fields are looked at.  Also used by
+// bhgeo_frame.hip.
+int mesh_material_check(const bhg_mesh_material *m, size_t nt, bool host_arrays)
+{
+    if (!m) return fail(BHG_E_INVALID, "mesh material is NULL");
+    char msg[256];
+    if (!(std::isfinite(m->emission) && m->emission >= 0.0)) {
+        std::snprintf(msg, sizeof msg, "mesh material: emission %.17g must be finite and >= 0", m->emission);
+        return fail(BHG_E_INVALID, msg);
+    }
+    if (m->n_tex < 0 || m->n_tex > BHG_MESH_TEXTURES_MAX) {
+        std::snprintf(msg, sizeof msg, "mesh material: n_tex %d must be in [0, BHG_MESH_TEXTURES_MAX]", (int)m->n_tex);
+        return fail(BHG_E_INVALID, msg);
+    }
+    for (int j = 0; j < m->n_tex; j++)
+        if (!m->tex[j] || m->tex_w[j] < 1 || m->tex_h[j] < 1) {
+            std::snprintf(msg, sizeof msg, "mesh material: tex[%d] must be an image of at least 1 x 1 (tex_w %d, tex_h %d%s)", j,
+                          (int)m->tex_w[j], (int)m->tex_h[j], m->tex[j] ? "" : ", NULL image");
+            return fail(BHG_E_INVALID, msg);
+        }
+    if (m->tri_uv && m->n_tex == 0) return fail(BHG_E_INVALID, "mesh material: tri_uv is given but n_tex is 0");
+    if (!host_arrays) return BHG_OK;
+    if (m->tri_uv)
+        for (size_t i = 0; i < nt * 6; i++)
+            if (!(std::fabs((double)m->tri_uv[i]) <= 1048576.0)) {   // (NaN fails the comparison too)
+                std::snprintf(msg, sizeof msg, "mesh material: tri_uv of triangle %zu is not finite or beyond 2^20 in magnitude", i / 6);
+                return fail(BHG_E_INVALID, msg);
+            }
+    if (m->tri_tex)
+        for (size_t i = 0; i < nt; i++)
+            if (m->tri_tex[i] >= m->n_tex) {
+                std::snprintf(msg, sizeof msg, "mesh material: tri_tex[%zu] = %d is not below n_tex = %d", i, (int)m->tri_tex[i],
+                              (int)m->n_tex);
+                return fail(BHG_E_INVALID, msg);
+            }
+    return BHG_OK;
+}
 }  // namespace bhg
 
 extern "C" {
@@ -881,6 +920,7 @@ size_t bhg_polarisation_size(void) { return sizeof(bhg_polarisation); }
 size_t bhg_disk_thermal_size(void) { return sizeof(bhg_disk_thermal); }
 size_t bhg_object_motion_size(void) { return sizeof(bhg_object_motion); }
 size_t bhg_disk_layers_size(void) { return sizeof(bhg_disk_layers); }
+size_t bhg_mesh_material_size(void) { return sizeof(bhg_mesh_material); }
 
 int bhg_abi_check(int abi_version, size_t params_size, size_t camera_size, size_t scene_size, size_t frame_scene_size)
 {
@@ -2410,6 +2450,48 @@ int bhg_shade_mesh_device(bhg_context *c, const double *d_end, const uint8_t *d_
     a.samples = samples;
     fill_scene_args(a, sc);
     HIP_TRY(bhg::launch_shade_mesh(a, mesh->view, d_tri_id, d_bary, d_tri_rgb, (hipStream_t)stream));
+    return BHG_OK;
+}
+
+// the mesh material shade: bhg_shade_mesh_device's checks and the material's, then
+// shade_mesh_material_kernel
+int bhg_shade_mesh_material_device(bhg_context *c, const double *d_end, const uint8_t *d_flags, const int32_t *d_tri_id,
+                                   const double *d_bary, size_t n_pixels, int32_t samples, const bhg_scene *sc, const bhg_mesh *mesh,
+                                   const bhg_mesh_material *mat, double *d_rgba, float *d_rgba_f32, const int64_t *d_scatter,
+                                   void *stream)
+{
+    BHG_TRY(scene_check(sc, samples, true));
+    if (!mesh) return fail(BHG_E_INVALID, "mesh is NULL");
+    BHG_TRY(bhg::mesh_material_check(mat, (size_t)mesh->view.n_tris, false));
+    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
+    if (mesh->device != c->device) return fail(BHG_E_INVALID, "the mesh lives on another device than the context");
+    if (n_pixels == 0) return BHG_OK;
+    if ((!d_rgba && !d_rgba_f32) || !d_end || !d_flags || !sc->d_sky || !d_tri_id || !d_bary)
+        return fail(BHG_E_INVALID, "NULL device pointer");
+    ENTER_DEVICE(c->device);
+    bhg::ShadeArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.end = d_end;
+    a.flags = d_flags;
+    a.rgba = d_rgba;
+    a.rgba_f32 = d_rgba_f32;
+    a.scatter = d_scatter;
+    a.n_pixels = n_pixels;
+    a.samples = samples;
+    fill_scene_args(a, sc);
+    bhg::MeshMaterialArgs m;
+    std::memset(&m, 0, sizeof(m));
+    m.tri_rgb = mat->tri_rgb;
+    m.tri_uv = mat->tri_uv;
+    m.tri_tex = mat->tri_tex;
+    for (int j = 0; j < mat->n_tex; j++) {
+        m.tex[j] = mat->tex[j];
+        m.tex_w[j] = mat->tex_w[j];
+        m.tex_h[j] = mat->tex_h[j];
+    }
+    m.n_tex = mat->n_tex;
+    m.emission = mat->emission;
+    HIP_TRY(bhg::launch_shade_mesh_material(a, mesh->view, d_tri_id, d_bary, m, (hipStream_t)stream));
     return BHG_OK;
 }
 

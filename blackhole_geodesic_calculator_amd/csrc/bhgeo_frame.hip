@@ -30,6 +30,7 @@
 
 #include "../../include/bhgeo.h"
 #include "geodesic_kernels.h"
+#include "mesh_bvh.h"
 #include "tile_dealing.h"
 
 namespace bhg {
@@ -48,6 +49,8 @@ int thermal_params(const bhg_params *p, const bhg_disk_thermal *th, const bhg_re
 // bhgeo_capi.hip: object motion on its own (finite, for n_spheres spheres), and against the spheres and the trace parameters
 int motion_check(const bhg_object_motion *mo, int32_t n_spheres);
 int motion_params(const bhg_params *p, const bhg_object_motion *mo, const double *spheres, int32_t n_spheres, MotionParams *out);
+// ... and of a mesh material (host_arrays: tri_uv / tri_tex are host arrays and are scanned)
+int mesh_material_check(const bhg_mesh_material *m, size_t nt, bool host_arrays);
 }
 
 namespace {
@@ -193,6 +196,10 @@ struct Shard {
     DevBuf start_rec;               // the rays' start-up records (BHG_START_PREFIX: 112 B per ray), written by the render that records
     double start_rho = 0.0;         // start_h, for the ball of this radius about start_origin; 0 = none are held
     DevBuf otex[BHG_MAX_SPHERES];   // the object textures (bhg_frame_set_object_textures), slot by slot
+    // the mesh (bhg_frame_set_mesh): this device's copy, its material's arrays and images, the mesh trace's hit records
+    bhg_mesh *mesh = nullptr;
+    DevBuf m_rgb, m_uv, m_slot, m_img[BHG_MESH_TEXTURES_MAX], tri, bary;
+    bool mesh_ready = false;        // mesh and the material buffers hold the frame's current mesh
     hipEvent_t done = nullptr;
     bool rays_ready = false;
     bool start_ready = false;       // start_h holds the steps of the rays in k0, traced from start_origin with start_prm
@@ -233,6 +240,21 @@ struct bhg_frame {
     bool moving = false;            // bhg_frame_set_object_motion; false: the object spheres at rest
     bhg_object_motion mo = {};
     int32_t otex_w[BHG_MAX_SPHERES] = {}, otex_h[BHG_MAX_SPHERES] = {};
+    // bhg_frame_set_mesh: host copies of the mesh and its material (uploaded to every device on the next render)
+    struct Mesh {
+        std::vector<double> vertices, normals;      // normals empty: flat shading
+        std::vector<int32_t> triangles;
+        int32_t leaf_size = 4;
+        double max_chord = 0.0;                     // 0: a quarter of the render's r_s
+        std::vector<float> tri_rgb, tri_uv;         // empty: white / no textures
+        std::vector<int32_t> tri_tex;               // empty: slot 0 for every triangle
+        std::vector<float> img[BHG_MESH_TEXTURES_MAX];
+        int32_t img_w[BHG_MESH_TEXTURES_MAX] = {}, img_h[BHG_MESH_TEXTURES_MAX] = {};
+        int32_t n_tex = 0;
+        double emission = 0.0;
+    };
+    bool meshed = false;            // bhg_frame_set_mesh; false: no mesh, the plain render
+    Mesh mesh;
     // root (device of shard 0)
     DevBuf recv, perm, image;       // [n_dev * pmax][4] float, [H W] int64, [H W][4] float
     size_t pmax = 0;
@@ -365,6 +387,57 @@ int upload_shard_textures(bhg_frame *f, Shard &s)
     return BHG_OK;
 }
 
+void release_shard_mesh(Shard &s)
+{
+    if (s.mesh) bhg_mesh_destroy(s.mesh);
+    s.mesh = nullptr;
+    for (DevBuf *b : {&s.m_rgb, &s.m_uv, &s.m_slot, &s.tri, &s.bary}) b->release();
+    for (DevBuf &b : s.m_img) b.release();
+    s.mesh_ready = false;
+}
+
+// the frame's mesh on this shard's device: the tree is built by bhg_mesh_create, once per device (mesh_bvh.h hands its tree to
+// nobody but that call), the material's arrays and images go up beside it
+int upload_shard_mesh(bhg_frame *f, Shard &s)
+{
+    const bhg_frame::Mesh &m = f->mesh;
+    release_shard_mesh(s);
+    HIP_TRY(hipSetDevice(s.device));
+    BHG_TRY(bhg_mesh_create(s.ctx, m.vertices.data(), m.vertices.size() / 3, m.triangles.data(), m.triangles.size() / 3,
+                            m.normals.empty() ? nullptr : m.normals.data(), m.leaf_size, &s.mesh));
+    HIP_TRY(hipSetDevice(s.device));
+    const auto up = [&](DevBuf &b, const void *src, size_t bytes) -> int {
+        if (bytes == 0) return BHG_OK;
+        BHG_TRY(b.ensure(s.device, bytes));
+        HIP_TRY(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s.stream));
+        return BHG_OK;
+    };
+    BHG_TRY(up(s.m_rgb, m.tri_rgb.data(), m.tri_rgb.size() * sizeof(float)));
+    BHG_TRY(up(s.m_uv, m.tri_uv.data(), m.tri_uv.size() * sizeof(float)));
+    BHG_TRY(up(s.m_slot, m.tri_tex.data(), m.tri_tex.size() * sizeof(int32_t)));
+    for (int j = 0; j < m.n_tex; j++) BHG_TRY(up(s.m_img[j], m.img[j].data(), m.img[j].size() * sizeof(float)));
+    HIP_TRY(hipStreamSynchronize(s.stream));
+    s.mesh_ready = true;
+    return BHG_OK;
+}
+
+// the frame's material as the shade call takes it, on this shard's device
+void fill_mesh_material(const bhg_frame *f, const Shard &s, bhg_mesh_material *mat)
+{
+    const bhg_frame::Mesh &m = f->mesh;
+    std::memset(mat, 0, sizeof(*mat));
+    mat->tri_rgb = m.tri_rgb.empty() ? nullptr : s.m_rgb.as<float>();
+    mat->tri_uv = m.tri_uv.empty() ? nullptr : s.m_uv.as<float>();
+    mat->tri_tex = m.tri_tex.empty() ? nullptr : s.m_slot.as<int32_t>();
+    for (int j = 0; j < m.n_tex; j++) {
+        mat->tex[j] = s.m_img[j].as<float>();
+        mat->tex_w[j] = m.img_w[j];
+        mat->tex_h[j] = m.img_h[j];
+    }
+    mat->n_tex = m.n_tex;
+    mat->emission = m.emission;
+}
+
 // the frame's object textures as the shade call takes them: tex = the shard's device copies (s = nullptr: the host copies,
 // for the checks before a render)
 void fill_object_textures(const bhg_frame *f, const Shard *s, bhg_object_textures *ot)
@@ -449,6 +522,7 @@ void destroy_frame(bhg_frame *f)
                            &s.start_h, &s.start_rec})
             b->release();
         for (DevBuf &b : s.otex) b.release();
+        release_shard_mesh(s);
         if (s.done) (void)hipEventDestroy(s.done);
         for (auto &e : s.evs) {
             (void)hipEventDestroy(e.first);
@@ -757,6 +831,56 @@ try {
     return host_exception();
 }
 
+int bhg_frame_set_mesh(bhg_frame *f, const double *vertices, size_t n_vertices, const int32_t *triangles, size_t n_triangles,
+                       const double *vertex_normals, int32_t leaf_size, double max_chord, const bhg_mesh_material *material)
+try {
+    if (!f) return fail(BHG_E_INVALID, "frame is NULL");
+    if (!vertices) {
+        // off: the plain render again, the mesh freed (host and devices)
+        f->meshed = false;
+        f->mesh = bhg_frame::Mesh();
+        DeviceScope scope;
+        for (auto &s : f->sh) release_shard_mesh(s);
+        return BHG_OK;
+    }
+    // bhg_mesh_create's checks and the material's, before anything of the frame's changes
+    if (const char *why = bhg::mesh_refusal(vertices, n_vertices, triangles, n_triangles, leaf_size)) return fail(BHG_E_INVALID, why);
+    if (vertex_normals)
+        for (size_t i = 0; i < n_vertices * 3; i++)
+            if (!std::isfinite(vertex_normals[i])) return fail(BHG_E_INVALID, "mesh: every vertex normal must be finite");
+    if (!std::isfinite(max_chord) || max_chord < 0.0)
+        return fail(BHG_E_INVALID, "max_chord must be finite and >= 0 (0: a quarter of r_s)");
+    if (material) BHG_TRY(bhg::mesh_material_check(material, n_triangles, true));
+    // the new mesh is copied aside first: a refused host allocation leaves the frame as it was
+    bhg_frame::Mesh m;
+    const size_t nt = n_triangles;
+    m.vertices.assign(vertices, vertices + n_vertices * 3);
+    m.triangles.assign(triangles, triangles + nt * 3);
+    if (vertex_normals) m.normals.assign(vertex_normals, vertex_normals + n_vertices * 3);
+    m.leaf_size = leaf_size;
+    m.max_chord = max_chord;
+    if (material) {
+        if (material->tri_rgb) m.tri_rgb.assign(material->tri_rgb, material->tri_rgb + nt * 3);
+        if (material->tri_uv) {
+            m.tri_uv.assign(material->tri_uv, material->tri_uv + nt * 6);
+            if (material->tri_tex) m.tri_tex.assign(material->tri_tex, material->tri_tex + nt);
+            m.n_tex = material->n_tex;
+            for (int j = 0; j < m.n_tex; j++) {
+                m.img_w[j] = material->tex_w[j];
+                m.img_h[j] = material->tex_h[j];
+                m.img[j].assign(material->tex[j], material->tex[j] + (size_t)m.img_w[j] * (size_t)m.img_h[j] * 4);
+            }
+        }
+        m.emission = material->emission;
+    }
+    f->mesh = std::move(m);
+    f->meshed = true;
+    for (auto &s : f->sh) s.mesh_ready = false;
+    return BHG_OK;
+} catch (...) {
+    return host_exception();
+}
+
 int bhg_frame_render(bhg_frame *f, const bhg_params *p, float *rgba_host)
 try {
     if (!f || !p) return fail(BHG_E_INVALID, "frame / params is NULL");
@@ -768,7 +892,13 @@ try {
     const size_t world = f->sh.size(), HW = (size_t)f->cam.width * (size_t)f->cam.height;
     const int S = f->cam.samples;
     const bool has_obj = f->scene.n_spheres > 0, has_disk = f->scene.disk_r_out > 0.0;
-    const bool dir_only = !has_obj && !has_disk;
+    const bool meshed = f->meshed;
+    if (meshed) {   // (refused before anything is enqueued)
+        const char *with = has_obj ? "scene spheres" : f->rs.apply != 0 ? "redshift" : f->thermal ? "the thermal disk"
+                           : f->moving ? "object motion" : f->textured ? "object textures" : nullptr;
+        if (with) return fail(BHG_E_INVALID, std::string("a mesh does not go with ") + with);
+    }
+    const bool dir_only = !has_obj && !has_disk && !meshed;
     const bool loopback = world == 1 && f->gather == BHG_FRAME_GATHER_RCCL;   // (see build_root)
     const bool peer = f->gather == BHG_FRAME_GATHER_PEER;     // every device's shade stores straight into the image
     const bool gathered = (world > 1 && !peer) || loopback;
@@ -824,6 +954,7 @@ try {
         if (!s.rays_ready) BHG_TRY(upload_shard_geometry(f, s, f->observer ? &op : nullptr));
         if (!s.scene_ready) BHG_TRY(upload_shard_scene(f, s));
         if (textured && !s.otex_ready) BHG_TRY(upload_shard_textures(f, s));
+        if (meshed && !s.mesh_ready) BHG_TRY(upload_shard_mesh(f, s));
     }
     for (size_t r = 0; r < world; r++) {
         Shard &s = f->sh[r];
@@ -841,6 +972,26 @@ try {
                 s.evs.emplace_back(e0, e1);
             }
             HIP_TRY(hipEventRecord(s.evs[s.ev_used].first, s.stream));
+        }
+        if (meshed) {
+            // the mesh trace: whole records, its own kernel, the plain call; the shard's kept initial steps and start-up records
+            // are neither used nor touched (they are still valid when the mesh is turned off)
+            BHG_TRY(s.end.ensure(s.device, s.n * 6 * sizeof(double)));
+            BHG_TRY(s.tri.ensure(s.device, s.n * sizeof(int32_t)));
+            BHG_TRY(s.bary.ensure(s.device, s.n * 2 * sizeof(double)));
+            const double chord = f->mesh.max_chord > 0.0 ? f->mesh.max_chord : 0.25 * prm.r_s;
+            BHG_TRY(bhg_trace_mesh_device(s.ctx, &prm, s.mesh, chord, f->cam.origin, nullptr, s.k0.as<double>(), s.n, s.end.as<double>(),
+                                          s.flags.as<uint8_t>(), s.steps.as<uint32_t>(), s.acc.as<uint32_t>(), s.tri.as<int32_t>(),
+                                          s.bary.as<double>(), s.stream));
+            if (f->profiling) HIP_TRY(hipEventRecord(s.evs[s.ev_used++].second, s.stream));
+            bhg_scene sc;
+            fill_scene(f, s, &sc);
+            bhg_mesh_material mat;
+            fill_mesh_material(f, s, &mat);
+            BHG_TRY(bhg_shade_mesh_material_device(s.ctx, s.end.as<double>(), s.flags.as<uint8_t>(), s.tri.as<int32_t>(),
+                                                   s.bary.as<double>(), s.P, S, &sc, s.mesh, &mat, nullptr, dst, scatter, s.stream));
+            s.dir_traced = false;
+            continue;
         }
         // The shard owns its rays, so their initial steps outlive the render: recorded by the first trace of a ray set,
         // replayed while the rays, the origin and what bhg_start_steps_match() lists stay as they were.  Not valid while a

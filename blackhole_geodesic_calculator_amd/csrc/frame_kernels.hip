@@ -1421,4 +1421,129 @@ hipError_t launch_shade_mesh(const ShadeArgs &a, const MeshView &m, const int32_
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------
+// The mesh material shade (bhg_shade_mesh_material_device): a mesh ray gets albedo * (lamp_sum + emission),
+// albedo = tri_rgb[T] * texel.  lamp_sum is mesh_colour's sum itself -- called with a white MeshShade, its three channels are
+// 1.0 * sum -- so the normal, the facing rule, the shadow segment and the traversal are the one definition.  x * 1.0 and
+// sum + 0.0 are exact: without UVs and with emission = 0 the colour is mesh_colour's tri_rgb[T] * sum, bit for bit.
+// The kernels are shade_mesh_kernel's and its serial twin's, with the material as one more argument struct.
+// ------------------------------------------------------------------------------------------
+// x mod n for an integer-valued x and a small positive integer n, in floating point as sky_lookup wraps its column: the
+// quotient's rounding can only be off by one period, which the two selects put right.  (The device form of the material is
+// not scanned: the last select keeps a non-finite coordinate inside the image.)
+__device__ __forceinline__ int wrap_index(double x, double n)
+{
+    double w = __builtin_fma(-n, floor(x * (1.0 / n)), x);
+    w = w < 0.0 ? w + n : (w >= n ? w - n : w);
+    return (w >= 0.0 && w < n) ? (int)w : 0;
+}
+
+// bilinear, repeating in both directions; row 0 is V = 0 (include/bhgeo.h has the definition)
+__device__ __forceinline__ void mesh_texel(const float *tex, int W, int H, double U, double V, double rgb[3])
+{
+    const double Wd = (double)W, Hd = (double)H;
+    const double fx = U * Wd - 0.5, fy = V * Hd - 0.5;
+    const double x0f = floor(fx), y0f = floor(fy);
+    const double ax = fx - x0f, ay = fy - y0f;
+    const int x0 = wrap_index(x0f, Wd), y0 = wrap_index(y0f, Hd);
+    const int x1 = (x0 + 1 == W) ? 0 : x0 + 1, y1 = (y0 + 1 == H) ? 0 : y0 + 1;
+    const float4 t00 = reinterpret_cast<const float4 *>(tex)[(long)y0 * W + x0];
+    const float4 t01 = reinterpret_cast<const float4 *>(tex)[(long)y0 * W + x1];
+    const float4 t10 = reinterpret_cast<const float4 *>(tex)[(long)y1 * W + x0];
+    const float4 t11 = reinterpret_cast<const float4 *>(tex)[(long)y1 * W + x1];
+    const double w00 = (1.0 - ax) * (1.0 - ay), w01 = ax * (1.0 - ay), w10 = (1.0 - ax) * ay, w11 = ax * ay;
+    rgb[0] = __builtin_fma(w11, (double)t11.x, __builtin_fma(w10, (double)t10.x, __builtin_fma(w01, (double)t01.x, w00 * (double)t00.x)));
+    rgb[1] = __builtin_fma(w11, (double)t11.y, __builtin_fma(w10, (double)t10.y, __builtin_fma(w01, (double)t01.y, w00 * (double)t00.y)));
+    rgb[2] = __builtin_fma(w11, (double)t11.z, __builtin_fma(w10, (double)t10.z, __builtin_fma(w01, (double)t01.z, w00 * (double)t00.z)));
+}
+
+// G.tri_rgb == nullptr (launch_shade_mesh_material sees to it): mesh_colour leaves the lamp sum in every channel
+__device__ __forceinline__ void mesh_material_ray_colour(const ShadeArgs &A, const MeshShade &G, const MeshMaterialArgs &M, uint64_t i,
+                                                         double rgb[3])
+{
+    const uint8_t fl = A.flags[i];
+    const int32_t tri = G.tri_id[i];
+    if (fl == BHG_FLAG_HIT_OBJECT_ && tri >= 0 && tri < G.mesh.n_tris) {
+        mesh_colour(A, G, i, tri, rgb);
+        const double light = rgb[0] + M.emission;
+        double albedo[3] = {1.0, 1.0, 1.0};
+        if (M.tri_rgb)
+            for (int c = 0; c < 3; c++) albedo[c] = (double)M.tri_rgb[(size_t)tri * 3 + c];
+        const int32_t slot = !M.tri_uv ? -1 : (M.tri_tex ? M.tri_tex[tri] : 0);
+        if (slot >= 0 && slot < M.n_tex) {
+            // the triangle's six corner coordinates: one contiguous 24-byte read
+            const float2 *uv = reinterpret_cast<const float2 *>(M.tri_uv) + (size_t)tri * 3;
+            const float2 c0 = uv[0], c1 = uv[1], c2 = uv[2];
+            const double u = G.bary[i * 2], v = G.bary[i * 2 + 1], w = 1.0 - u - v;
+            const double U = w * (double)c0.x + u * (double)c1.x + v * (double)c2.x;
+            const double V = w * (double)c0.y + u * (double)c1.y + v * (double)c2.y;
+            double texel[3];
+            mesh_texel(M.tex[slot], M.tex_w[slot], M.tex_h[slot], U, V, texel);
+            for (int c = 0; c < 3; c++) albedo[c] *= texel[c];
+        }
+        for (int c = 0; c < 3; c++) rgb[c] = albedo[c] * light;
+        return;
+    }
+    const double *d = A.end + i * 6 + 3;
+    ray_colour<false, false, false, false, false, false>(A, i, fl, d[0], d[1], d[2], rgb, nullptr);
+}
+
+__global__ void __launch_bounds__(256) shade_mesh_material_kernel(const ShadeArgs A, const MeshShade G, const MeshMaterialArgs M,
+                                                                  const uint32_t ppb)
+{
+    __shared__ double col[256 * 3];
+    const uint32_t t = threadIdx.x, S = (uint32_t)A.samples;
+    const uint32_t s = t / ppb, q = t - s * ppb;
+    const uint64_t p = (uint64_t)blockIdx.x * ppb + q;
+    const bool live = s < S && p < A.n_pixels;
+    if (live) {
+        double rgb[3];
+        mesh_material_ray_colour(A, G, M, (uint64_t)s * A.n_pixels + p, rgb);
+        col[t * 3 + 0] = rgb[0];
+        col[t * 3 + 1] = rgb[1];
+        col[t * 3 + 2] = rgb[2];
+    }
+    __syncthreads();
+    if (s == 0 && live) {
+        double acc[3] = {0.0, 0.0, 0.0};
+        for (uint32_t k = 0; k < S; k++) {
+            const double *c = col + (size_t)(k * ppb + q) * 3;
+            acc[0] += c[0];
+            acc[1] += c[1];
+            acc[2] += c[2];
+        }
+        write_pixel(A, p, acc);
+    }
+}
+
+// more samples than a workgroup has threads: one thread per pixel, in sample order
+__global__ void __launch_bounds__(256) shade_mesh_material_serial_kernel(const ShadeArgs A, const MeshShade G, const MeshMaterialArgs M)
+{
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= A.n_pixels) return;
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int s = 0; s < A.samples; s++) {
+        double rgb[3];
+        mesh_material_ray_colour(A, G, M, (uint64_t)s * A.n_pixels + p, rgb);
+        acc[0] += rgb[0];
+        acc[1] += rgb[1];
+        acc[2] += rgb[2];
+    }
+    write_pixel(A, p, acc);
+}
+
+hipError_t launch_shade_mesh_material(const ShadeArgs &a, const MeshView &m, const int32_t *tri_id, const double *bary,
+                                      const MeshMaterialArgs &M, hipStream_t s)
+{
+    if (a.n_pixels == 0) return hipSuccess;
+    const MeshShade g{m, tri_id, bary, nullptr};
+    if (a.samples > 256) {
+        BHG_LAUNCH(shade_mesh_material_serial_kernel, dim3((unsigned)((a.n_pixels + 255) / 256)), dim3(256), 0, s, a, g, M);
+        return hipGetLastError();
+    }
+    const uint32_t ppb = 256u / (uint32_t)a.samples;
+    BHG_LAUNCH(shade_mesh_material_kernel, dim3((unsigned)((a.n_pixels + ppb - 1) / ppb)), dim3(256), 0, s, a, g, M, ppb);
+    return hipGetLastError();
+}
+
 }  // namespace bhg

@@ -32,6 +32,7 @@ constexpr int BHG_MAX_SPHERES_ = 8;
 constexpr int BHG_MAX_CROSSINGS_ = 4;
 constexpr int32_t BHG_OBJECT_LIT_ = 0;
 constexpr int32_t BHG_OBJECT_EMISSIVE_ = 1;
+constexpr int BHG_MESH_TEXTURES_MAX_ = 8;
 constexpr uint32_t BHG_REDSHIFT_DISK_ = 1u;
 constexpr uint32_t BHG_REDSHIFT_OBJECTS_ = 2u;
 constexpr uint32_t BHG_REDSHIFT_SKY_ = 4u;
@@ -342,6 +343,18 @@ hipError_t launch_trace_mesh_kerr(const TraceArgs &a, const MeshArgs &m, hipStre
 // them, n_spheres = 0; tri_rgb nullptr = white
 hipError_t launch_shade_mesh(const ShadeArgs &a, const MeshView &m, const int32_t *tri_id, const double *bary, const float *tri_rgb,
                              hipStream_t s);
+// the mesh material shade (shade_mesh_material_kernel): the material rides in an argument struct of its own
+struct MeshMaterialArgs {
+    const float *tri_rgb;    // [nt][3] in the caller's numbering, or nullptr (white)
+    const float *tri_uv;     // [nt][3][2] in the caller's numbering, or nullptr (no textures)
+    const int32_t *tri_tex;  // [nt] image slot (< 0 or >= n_tex: none), or nullptr (slot 0)
+    const float *tex[BHG_MESH_TEXTURES_MAX_];   // [h][w][4] RGBA float32, row 0 at V = 0
+    int32_t tex_w[BHG_MESH_TEXTURES_MAX_], tex_h[BHG_MESH_TEXTURES_MAX_];
+    int32_t n_tex;
+    double emission;
+};
+hipError_t launch_shade_mesh_material(const ShadeArgs &a, const MeshView &m, const int32_t *tri_id, const double *bary,
+                                      const MeshMaterialArgs &mat, hipStream_t s);
 // the recording pass of the start-up records (record_prefix_kernel: one lane per ray; rhs Christoffel or reduced, a.x0 == nullptr):
 // rec [7][a.n] 16-byte planes, rho the radius about a.x0s the recorded steps stay inside.  deep: the record carries on through
 // rejected attempts (BHG_PREFIX_RECORD_DEEP: at most BHG_PREFIX_DEEP_ACCEPTED_ accepted steps in BHG_PREFIX_DEEP_ATTEMPTS_ attempts)

@@ -199,6 +199,7 @@ class DeviceFrame:
         self.mesh = None              # _ffi.Mesh (set_mesh) or None: no triangle mesh in the curved region
         self.mesh_chord = None        # max_chord of the mesh trace; None: a quarter of the trace parameters' r_s
         self.d_tri_rgb = None         # [nt, 3] fp32 triangle colours, or None (white)
+        self.mesh_material = None     # set_mesh(material=): (_ffi.MeshMaterial, its struct over the device copies, the copies)
         self.d_tri_id = None          # [n] int32 and
         self.d_bary = None            # [n, 2] fp64 of the last mesh trace
 
@@ -320,17 +321,21 @@ class DeviceFrame:
             raise ValueError("opacity must be in (0, 1]")
         self.disk_layers = _ffi.make_disk_layers(max_crossings, opacity)
 
-    def set_mesh(self, mesh=None, tri_rgb=None, chord=None, lamps=None):
+    def set_mesh(self, mesh=None, tri_rgb=None, chord=None, lamps=None, material=None):
         """A triangle mesh in the curved region (bhg_trace_mesh_device, bhg_shade_mesh_device): trace()
         ends a ray where its curve meets a triangle and keeps d_tri_id [n] int32 / d_bary [n, 2]; shade() / shade_f32() /
         render() light the mesh rays (tri_rgb [nt, 3] per triangle, default white; the lamps of set_objects([], lamps=...) or
         lamps=; shadows cast by the mesh itself), every other ray as without the mesh.  mesh: an _ffi.Mesh of this frame's
         context, or (vertices, triangles).  chord: the sub-chord length of the trace, default a quarter of r_s.  Not with
         object spheres, disk layers, redshift, polarisation, the thermal disk or shade_stokes() (ValueError).  The kept
-        initial steps and start-up records are neither used nor touched.  None: off -- every path the one it was, bit for bit."""
+        initial steps and start-up records are neither used nor touched.  None: off -- every path the one it was, bit for bit.
+        material: an _ffi.MeshMaterial (per-corner UVs, image textures, emission; bhg_shade_mesh_material_device, DESIGN.md
+        section 20) in place of tri_rgb -- both together are a ValueError; without it the shade is the existing call."""
+        if material is not None and tri_rgb is not None:
+            raise ValueError("material and tri_rgb together: the material carries the triangle colours")
         self._traced = None
         if mesh is None:
-            self.mesh = self.d_tri_rgb = self.mesh_chord = None
+            self.mesh = self.d_tri_rgb = self.mesh_chord = self.mesh_material = None
             return
         if not isinstance(mesh, _ffi.Mesh):
             mesh = _ffi.Mesh(self.ctx, mesh[0], mesh[1])
@@ -338,7 +343,11 @@ class DeviceFrame:
             raise ValueError("the mesh belongs to another context")
         if chord is not None and not (np.isfinite(float(chord)) and float(chord) > 0.0):
             raise ValueError("chord must be finite and > 0")
-        self.d_tri_rgb = None
+        self.d_tri_rgb = self.mesh_material = None
+        if material is not None:
+            material.check_triangles(mesh.n_triangles)
+            dev = [None if a is None else torch.as_tensor(a).to(self.dev) for a in material.arrays()]
+            self.mesh_material = (material, material.struct([0 if t is None else t.data_ptr() for t in dev]), dev)
         if tri_rgb is not None:
             rgb = np.ascontiguousarray(tri_rgb, dtype=np.float32)
             if rgb.shape != (mesh.n_triangles, 3):
@@ -521,6 +530,12 @@ class DeviceFrame:
             if pol is not None:
                 raise ValueError("a mesh has no Stokes images: shade_stokes() is not available with set_mesh()")
             self._mesh_check()
+            if self.mesh_material is not None:
+                self.ctx.shade_mesh_material_device(self.d_end.data_ptr(), self.d_flags.data_ptr(), self.d_tri_id.data_ptr(),
+                                                    self.d_bary.data_ptr(), self.P, self.S, self.scene(), self.mesh,
+                                                    self.mesh_material[1], d_rgba=d_rgba, d_rgba_f32=d_rgba_f32,
+                                                    d_scatter=0 if scatter is None else scatter.data_ptr(), stream=self._stream())
+                return
             self.ctx.shade_mesh_device(self.d_end.data_ptr(), self.d_flags.data_ptr(), self.d_tri_id.data_ptr(),
                                        self.d_bary.data_ptr(), self.P, self.S, self.scene(), self.mesh,
                                        d_tri_rgb=0 if self.d_tri_rgb is None else self.d_tri_rgb.data_ptr(), d_rgba=d_rgba,

@@ -71,7 +71,9 @@ extern "C" {
                                   the coordinate time along each ray, the disk layers at their retarded phase);
                                   BHG_MESH (bhg_mesh_create / _destroy / _info, bhg_mesh_bvh_host, bhg_trace_mesh_device,
                                   bhg_trace_mesh, bhg_shade_mesh_device, struct bhg_mesh, BHG_MESH_MAX_SUBSTEPS: triangle meshes
-                                  in the curved region).
+                                  in the curved region);
+                                  BHG_MESH_MATERIAL (bhg_shade_mesh_material_device, bhg_frame_set_mesh, bhg_mesh_material_size,
+                                  struct bhg_mesh_material, BHG_MESH_TEXTURES_MAX: textured, emissive meshes, meshes on bhg_frame).
                                9: redshift -- bhg_redshift_device / _host, bhg_shade_scene_redshift_device, bhg_frame_set_redshift,
                                   bhg_redshift_size, struct bhg_redshift;
                                   nothing of ABI 8 changed.
@@ -1008,6 +1010,51 @@ int bhg_trace_mesh(bhg_context *ctx, const bhg_params *p, const bhg_mesh *mesh, 
 int bhg_shade_mesh_device(bhg_context *ctx, const double *d_end, const uint8_t *d_flags, const int32_t *d_tri_id,
                           const double *d_bary, size_t n_pixels, int32_t samples, const bhg_scene *scene, const bhg_mesh *mesh,
                           const float *d_tri_rgb, double *d_rgba, float *d_rgba_f32, const int64_t *d_scatter, void *stream);
+
+/* --- mesh material: per-corner UVs, image textures, emission; meshes on bhg_frame (within ABI 10) -------
+ * A mesh ray (BHG_FLAG_HIT_OBJECT, 0 <= tri_id < nt) gets albedo * (lamp_sum + emission): lamp_sum is bhg_shade_mesh_device's
+ * Lambert sum (same normal, facing rule, 1e-5 shadow segment), albedo = tri_rgb[tri] (NULL: 1) * texel.  Every other ray is
+ * bhg_shade_scene_device's, bit for bit.
+ * THE TEXEL.  With (u, v) = bary[i], w = 1 - u - v and the triangle's corner UVs (U0, V0), (U1, V1), (U2, V2):
+ * U = w U0 + u U1 + v U2, V likewise, in fp64 from the fp32 corners; u, v are not clamped (they may leave [0, 1] by the chord's
+ * sag: the UV is extrapolated linearly).  fx = U W - 0.5, fy = V H - 0.5, x0 = floor(fx), y0 = floor(fy), ax = fx - x0,
+ * ay = fy - y0; columns x0 mod W and (x0 + 1) mod W, rows y0 mod H and (y0 + 1) mod H (the mathematical mod: the image repeats in
+ * both directions); row 0 is V = 0; texel = (1 - ax)(1 - ay) t00 + ax (1 - ay) t01 + (1 - ax) ay t10 + ax ay t11 on RGB, alpha is
+ * ignored.  A triangle with tri_tex < 0 (or, in the device form, >= n_tex) and a material without tri_uv have texel 1.
+ * All per-triangle arrays are in the caller's numbering.  A material with tri_uv = NULL and emission = 0 gives
+ * bhg_shade_mesh_device's image with the same tri_rgb, bit for bit.
+ * Refused (BHG_E_INVALID, the message names the field) before anything is launched or written: what bhg_shade_mesh_device
+ * refuses; a NULL material; emission negative or not finite; n_tex outside [0, BHG_MESH_TEXTURES_MAX]; a slot < n_tex with a
+ * NULL image or w, h < 1; tri_uv given with n_tex = 0.  The host-array form (bhg_frame_set_mesh) scans the arrays and also
+ * refuses a non-finite UV or |uv| > 2^20 (the floating-point wrap would stop being exact) and a tri_tex entry >= n_tex. */
+#define BHG_MESH_MATERIAL 1
+#define BHG_MESH_TEXTURES_MAX 8
+typedef struct bhg_mesh_material {
+    const float   *tri_rgb;   /* [nt][3] caller's numbering, NULL = white (as bhg_shade_mesh_device) */
+    const float   *tri_uv;    /* [nt][3][2] per-corner (u, v), corners in the triangle's vertex order; NULL = no textures */
+    const int32_t *tri_tex;   /* [nt] image slot per triangle, < 0 = none; NULL = slot 0 for every triangle */
+    const float   *tex[BHG_MESH_TEXTURES_MAX];      /* [h][w][4] float RGBA, rows bottom-up (the sky's convention) */
+    int32_t        tex_w[BHG_MESH_TEXTURES_MAX], tex_h[BHG_MESH_TEXTURES_MAX];
+    int32_t        n_tex;
+    double         emission;  /* >= 0 */
+} bhg_mesh_material;
+size_t bhg_mesh_material_size(void);
+/* bhg_shade_mesh_device with a material in place of d_tri_rgb; every pointer of *mat is a device pointer. */
+int bhg_shade_mesh_material_device(bhg_context *ctx, const double *d_end, const uint8_t *d_flags, const int32_t *d_tri_id,
+                                   const double *d_bary, size_t n_pixels, int32_t samples, const bhg_scene *scene,
+                                   const bhg_mesh *mesh, const bhg_mesh_material *mat, double *d_rgba, float *d_rgba_f32,
+                                   const int64_t *d_scatter, void *stream);
+/* A mesh on the library-owned frame.  All arrays are on the host and are copied; nothing is referenced after the call.  material
+ * may be NULL (white, no emission); vertices = NULL turns the mesh off (the other arguments are ignored) and the next render is
+ * the plain one, bit for bit -- the shards' kept start steps and start-up records are neither used nor touched while a mesh is
+ * set.  max_chord = 0: a quarter of the r_s of each render's parameters.  The mesh (its tree is built per device) and the images
+ * are uploaded to every listed device at the next render.  Each shard then traces with bhg_trace_mesh_device (whole end records:
+ * bhg_frame_info's direction-only field is 0) and shades with bhg_shade_mesh_material_device, in every gather mode.
+ * Refused, the frame left as it was: what bhg_mesh_create and the material refuse; max_chord negative or not finite.
+ * bhg_frame_render refuses (before anything is enqueued, "a mesh does not go with ...") a mesh together with scene spheres,
+ * redshift, the thermal disk, object motion or object textures. */
+int bhg_frame_set_mesh(bhg_frame *frame, const double *vertices, size_t n_vertices, const int32_t *triangles, size_t n_triangles,
+                       const double *vertex_normals, int32_t leaf_size, double max_chord, const bhg_mesh_material *material);
 
 /* Acceleration probe: acc[n][3] = -Gamma^i_{mu nu} k^mu k^nu at (x[n][3], k[n][3]); host buffers.
  * Lets tests compare the device RHS with the oracle's term by term.  With rhs_form = BHG_RHS_KERR_BL the triples
