@@ -39,6 +39,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "geodesic_kernels.h"
 #include "device_math.h"
 #include "kerr_start.h"
@@ -324,13 +326,6 @@ __device__ __forceinline__ void dense_dir(const Dense &d, double t, double v[3])
     }
 }
 
-__device__ __forceinline__ double dense_z(const Dense &d, double t)
-{
-    double x[3];
-    dense_pos(d, t, x);
-    return x[2];
-}
-
 // g(t) = r(t) - R; `bl`: the state is Boyer-Lindquist (r is the first coordinate)
 __device__ __forceinline__ double dense_g(const Dense &d, double t, double R, bool bl = false)
 {
@@ -338,6 +333,33 @@ __device__ __forceinline__ double dense_g(const Dense &d, double t, double R, bo
     dense_pos(d, t, x);
     if (bl) return x[0] - R;
     return sqrt_nr(__builtin_fma(x[2], x[2], __builtin_fma(x[1], x[1], x[0] * x[0]))) - R;
+}
+
+// The disk-plane event function at the interpolated position q: z, or -- Boyer-Lindquist -- cos(theta) (z = r cos(theta),
+// r > 0; the RHS's own sincos: about an ulp, a quarter of libm's cos with its large-argument ladder), once per Brent iterate
+__device__ __forceinline__ double plane_g(const double q[3], bool bl)
+{
+    if (!bl) return q[2];
+    double sn, cs;
+    sincos_pi4(q[1], sn, cs);
+    return cs;
+}
+
+__device__ __forceinline__ double dense_plane_g(const Dense &d, double t, bool bl)
+{
+    double q[3];
+    dense_pos(d, t, q);
+    return plane_g(q, bl);
+}
+
+// cylindrical radius of the point q, which the disk's annulus is tested on; Boyer-Lindquist: sqrt(x^2 + y^2) =
+// sqrt(r^2 + a^2) |sin theta|
+__device__ __forceinline__ double disk_radius(const TraceArgs &A, const double q[3], bool bl)
+{
+    if (!bl) return sqrt(q[0] * q[0] + q[1] * q[1]);
+    double sn, cs;
+    sincos_pi4(q[1], sn, cs);
+    return sqrt(q[0] * q[0] + A.spin * A.spin) * fabs(sn);
 }
 
 // Brent's method on g(t) = r(t) - R over [ta, tb], xtol = rtol = 4 eps (ivp.py:51-76).
@@ -1386,15 +1408,7 @@ __device__ __forceinline__ uint32_t settle_events(const TraceArgs &A, uint32_t k
         const double r = brent_root([&](double tt) { return g_z(tt); }, t, t_new);
         double xe[3];
         pos(r, xe);
-        // cylindrical radius of the crossing point; Boyer-Lindquist: sqrt(x^2 + y^2) = sqrt(r^2 + a^2) |sin theta|
-        double R;
-        if (bl) {
-            double sn, cs;
-            sincos_pi4(xe[1], sn, cs);
-            R = sqrt(xe[0] * xe[0] + A.spin * A.spin) * fabs(sn);
-        } else {
-            R = sqrt(xe[0] * xe[0] + xe[1] * xe[1]);
-        }
+        const double R = disk_radius(A, xe, bl);
         if (R >= A.disk_r_in && R <= A.disk_r_out && r < best) {
             best = r;
             fl = BHG_FLAG_HIT_DISK_;
@@ -1664,14 +1678,7 @@ __device__ __forceinline__ int dp54_short_core(const TraceArgs &A, const double 
     eval(th, g, dg, xe);        // xe = position at the root
     bool terminal = true;
     if (is_disk) {
-        double Rc;
-        if (BL) {
-            double sn, cs;
-            sincos_pi4(xe[1], sn, cs);
-            Rc = sqrt(xe[0] * xe[0] + A.spin * A.spin) * fabs(sn);
-        } else {
-            Rc = sqrt(xe[0] * xe[0] + xe[1] * xe[1]);
-        }
+        const double Rc = disk_radius(A, xe, BL);
         terminal = Rc >= A.disk_r_in && Rc <= A.disk_r_out;
     }
     if (terminal) {
@@ -1816,14 +1823,7 @@ __device__ __forceinline__ int dp54_resolve_long(const TraceArgs &A, const Metri
     int obj;
     const uint32_t fl = settle_events<EVT>(
         A, kind, t, t_new, P.x, xn, [&](double tt, double Rr) { return dense_g(d, tt, Rr, BL); },
-        [&](double tt) {
-            if (!BL) return dense_z(d, tt);
-            double q[3];
-            dense_pos(d, tt, q);
-            double sn, cs;             // z = r cos(theta), r > 0; the RHS's own sincos (about an ulp, a quarter of
-            sincos_pi4(q[1], sn, cs);  // libm's cos with its large-argument ladder) -- once per Brent iterate
-            return cs;
-        },
+        [&](double tt) { return dense_plane_g(d, tt, BL); },
         [&](double tt, double xq[3]) { dense_pos(d, tt, xq); }, BL, best, obj);
     if (fl) {
         double xe[3], ve[3];
@@ -1938,10 +1938,7 @@ __device__ __forceinline__ int rk4_resolve_parked(const TraceArgs &A, const Metr
         [&](double tt) {
             double xx[3], vv[3];
             hermite_eval(d, tt, xx, vv);
-            if (!BL) return xx[2];
-            double sn, cs;
-            sincos_pi4(xx[1], sn, cs);
-            return cs;
+            return plane_g(xx, BL);
         },
         [&](double tt, double xq[3]) {
             double vv[3];
@@ -2727,10 +2724,19 @@ __global__ void __launch_bounds__(256) kerr_finalize_kernel(const TraceArgs A, d
 #endif  // BHG_TU_KERR
 
 // ------------------------------------------------------------------------------------------
-// The lane-per-ray loops (the sampled-trajectory kernel in both its shapes, the disk-crossings kernel): a plain loop per ray on
-// the trace kernels' own helpers, so that the steps are theirs bit for bit.  RayState is a ray between two steps, StepTry one
-// attempted step from it.  What the loops share works on the two -- the start, the attempt, the radial sign tests, accepting
-// a step, the final store; what differs stays in the kernels: sampling and fixed steps there, the crossing records here.
+// The lane-per-ray loops (the sampled-trajectory kernel in both its shapes, the disk-crossings, travel-time and mesh kernels,
+// the start-up records): a plain loop per ray on the trace kernels' own helpers, so that the steps are theirs bit for bit.
+// RayState is a ray between two steps, StepTry one attempted step from it.  What the loops share works on the two and has ONE
+// definition here: the start and the start-inside result (start_ray, store_start_inside), the attempt (dp54_attempt), the
+// radial sign tests, the event settlement on the step's dense output (settle_dense), the crossing record (record_crossing:
+// crossings and travel time), the exit sphere taken as the plain trace takes it (exit_as_plain_trace: travel time and mesh),
+// accepting a step, the final store, and on the host the launch (launch_lanes).  What differs stays in the kernels, which
+// stay separate __global__ functions with register budgets of their own: sampling and fixed steps, the time quadrature, the
+// mesh test, the kept state.
+// Each loop spells out its own three lines "attempt; rejected: again; not accepted: the flag ends the ray".  A helper that
+// loops until an attempt is accepted gives the compiler an inner loop to hoist the ray's invariants out of, which it keeps
+// in registers across the attempts: disk_crossings_kernel's scratch went from 60 to 148 bytes with it, and the wave-per-ray
+// trajectory kernel from three waves per SIMD to two.
 // ------------------------------------------------------------------------------------------
 struct RayState {
     double x[3], v[3], a1[3];   // position, direction, a(x, v) (Kerr: Boyer-Lindquist)
@@ -2863,6 +2869,102 @@ __device__ __forceinline__ void finish_ray(const TraceArgs &A, uint64_t i, const
     store_result(A, (uint32_t)i, xe, ve, flags, S.n_att, S.n_acc);  // Kerr: still Boyer-Lindquist, finalised next
 }
 
+// The result of a ray that starts inside the hole (start_ray returned true): final at once, the Cartesian input, no step.
+// Each kernel adds its own outputs.
+__device__ __forceinline__ void store_start_inside(const TraceArgs &A, uint64_t i, const double xe[3], const double ve[3])
+{
+    store_result(A, (uint32_t)i, xe, ve, BHG_FLAG_START_INSIDE_ | BHG_FLAG_HIT_HORIZON_, 0, 0);
+}
+
+// The event settlement of an accepted step S -> P on its dense output d (position half built): settle_events with the three
+// callables of the dense output
+template <int RHS, int EVT>
+__device__ __forceinline__ uint32_t settle_dense(const TraceArgs &A, uint32_t kind, const RayState &S, const StepTry &P, const Dense &d,
+                                                 double &best, int &obj)
+{
+    constexpr bool BL = RHS == BHG_RHS_KERR_BL_;
+    return settle_events<EVT>(
+        A, kind, S.t, P.t_new, S.x, P.xn, [&](double tt, double Rr) { return dense_g(d, tt, Rr, BL); },
+        [&](double tt) { return dense_plane_g(d, tt, BL); }, [&](double tt, double xq[3]) { dense_pos(d, tt, xq); }, BL, best, obj);
+}
+
+// The disk-plane crossing of a step [d.t0, t_new] whose ends lie on opposite sides of the plane (crossed_disk_plane: at most one
+// root per step), d its dense output with both halves built.  The root by brent_root as settle_events finds it; the crossing
+// counts when its cylindrical radius lies in [disk_r_in, disk_r_out] and -- evflag: the step holds the ray's terminal event
+// too, at t_stop -- when it is not later than that event's root (scipy_reference's td <= te).  A crossing that counts bumps
+// n_cross; while records are left (max_cross) its dense-output state, Cartesian (Kerr: converted here, kerr_finalize_kernel's
+// formulas), goes to slot m = the count before it, cross[(m * cross_stride + i) * 6].  Returns that slot, or -1 when nothing
+// was stored; `root` is the crossing's parameter.
+template <int RHS>
+__device__ __forceinline__ int record_crossing(const TraceArgs &A, uint64_t i, const Dense &d, double t_new, uint32_t evflag,
+                                               double t_stop, uint32_t &n_cross, double &root)
+{
+    const bool bl = RHS == BHG_RHS_KERR_BL_;
+    root = brent_root([&](double tt) { return dense_plane_g(d, tt, bl); }, d.t0, t_new);
+    double sx[3], sv[3];
+    dense_pos(d, root, sx);
+    const double R = disk_radius(A, sx, bl);
+    if (!(R >= A.disk_r_in && R <= A.disk_r_out && (!evflag || root <= t_stop))) return -1;
+    const uint32_t m = n_cross++;
+    if (!(m < (uint32_t)A.max_cross)) return -1;
+    dense_dir(d, root, sv);
+    if (bl) {
+        double c[6];
+        bl_record_to_cart(A.spin, sx, sv, c);
+        for (int q = 0; q < 3; q++) {
+            sx[q] = c[q];
+            sv[q] = c[3 + q];
+        }
+    }
+    double *o = A.cross + ((uint64_t)m * A.cross_stride + i) * 6;
+    reinterpret_cast<double2 *>(o)[0] = make_double2(sx[0], sx[1]);
+    reinterpret_cast<double2 *>(o)[1] = make_double2(sx[2], sv[0]);
+    reinterpret_cast<double2 *>(o)[2] = make_double2(sv[1], sv[2]);
+    return (int)m;
+}
+
+// Disk off: the results are the plain trace's, bit for bit.  The trace kernels take a step whose ONE candidate event is the
+// exit sphere through their certified Newton search first (dp54_short_core: the same root as Brent's to 4 eps, another
+// iterate) and leave everything else to the Brent search of settle_events; so does a kernel that asks here for a step whose
+// terminal event it has settled.  True: the search held and has stored the ray's result (end, flags, step counts) itself.
+template <int RHS>
+__device__ __forceinline__ bool exit_as_plain_trace(const TraceArgs &A, uint64_t i, const RayState &S, const StepTry &P,
+                                                    bool ev_h, bool ev_e)
+{
+    return !(A.disk_r_out > 0.0) && ev_e && !ev_h &&
+           dp54_short_core<RHS, EVT_EXIT>(A, S.x, S.v, S.a1, S.t, P.t_new, P.h, P.a2, P.a3, P.a4, P.a5, P.a6, P.a7, P.xn, P.vn,
+                                          EV_EXIT, (uint32_t)i, S.n_att, S.n_acc) == PARK_ENDED;
+}
+
+// Host side.  The right-hand sides this translation unit instantiates: f(std::integral_constant<int, RHS>) for the one asked
+// for (the Kerr and the time-like unit hold one each)
+template <class F>
+static void with_rhs(int rhs, const F &f)
+{
+#if defined(BHG_TU_KERR)
+    f(std::integral_constant<int, BHG_RHS_KERR_BL_>{});
+#elif defined(BHG_TU_TIMELIKE)
+    f(std::integral_constant<int, BHG_RHS_CHRISTOFFEL_TL_>{});
+#else
+    if (rhs == BHG_RHS_REDUCED_)
+        f(std::integral_constant<int, BHG_RHS_REDUCED_>{});
+    else
+        f(std::integral_constant<int, BHG_RHS_CHRISTOFFEL_>{});
+#endif
+}
+
+// one lane per ray, 64 rays to a workgroup
+static dim3 lane_grid(uint64_t n) { return dim3((unsigned)((n + 63) / 64)); }
+
+// The launch of a lane-per-ray kernel: launch(RHS, grid) launches the instance; an empty call launches nothing
+template <class F>
+static hipError_t launch_lanes(const TraceArgs &a, int rhs, const F &launch)
+{
+    if (a.n == 0) return hipSuccess;
+    with_rhs(rhs, [&](auto R) { launch(R, lane_grid(a.n)); });
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------
 // Sampled trajectories: what calc_trajectory returns with nr_points_curve (RelativisticRenderEngine.py:
 // 293-294; the curves of README Fig. 5/6).  A plain loop per ray -- this is the small-n plotting path, not the
@@ -2897,7 +2999,7 @@ __global__ void __launch_bounds__(WAVE ? 256 : 64) trajectory_dp54_kernel(const 
         }
         n_valid[i] = 0;
         if (A.object_id) A.object_id[i] = (int8_t)-1;
-        store_result(A, (uint32_t)i, xe, ve, BHG_FLAG_START_INSIDE_ | BHG_FLAG_HIT_HORIZON_, 0, 0);
+        store_start_inside(A, i, xe, ve);
         return;
     }
     const double dt = t_bound / (double)(T - 1);
@@ -2981,32 +3083,22 @@ __global__ void __launch_bounds__(WAVE ? 256 : 64) trajectory_dp54_kernel(const 
             const uint32_t kind = (ev_h ? EV_HORIZON : 0u) | (ev_e ? EV_EXIT : 0u) | (ev_d ? EV_DISK : 0u) | (ev_o ? EV_OBJ : 0u);
             double best;
             int obj;
-            evflag = settle_events<(EVT_EXIT | EVT_DISK | EVT_OBJ)>(
-                A, kind, S.t, P.t_new, S.x, P.xn,
-                [&](double tt, double Rr) { return FIXED ? hermite_g(hd, tt, Rr, bl) : dense_g(d, tt, Rr, bl); },
-                [&](double tt) {
-                    double q[3];
-                    if (FIXED) {
-                        double vv[3];
+            if (FIXED) {
+                evflag = settle_events<(EVT_EXIT | EVT_DISK | EVT_OBJ)>(
+                    A, kind, S.t, P.t_new, S.x, P.xn, [&](double tt, double Rr) { return hermite_g(hd, tt, Rr, bl); },
+                    [&](double tt) {
+                        double q[3], vv[3];
                         hermite_eval(hd, tt, q, vv);
-                        if (!bl) return q[2];
-                    } else {
-                        if (!bl) return dense_z(d, tt);
-                        dense_pos(d, tt, q);
-                    }
-                    double sn, cs;
-                    sincos_pi4(q[1], sn, cs);
-                    return cs;
-                },
-                [&](double tt, double xq[3]) {
-                    if (FIXED) {
+                        return plane_g(q, bl);
+                    },
+                    [&](double tt, double xq[3]) {
                         double vv[3];
                         hermite_eval(hd, tt, xq, vv);
-                    } else {
-                        dense_pos(d, tt, xq);
-                    }
-                },
-                bl, best, obj);
+                    },
+                    bl, best, obj);
+            } else {
+                evflag = settle_dense<RHS, (EVT_EXIT | EVT_DISK | EVT_OBJ)>(A, kind, S, P, d, best, obj);
+            }
             if (evflag) {
                 t_stop = best;
                 hit_obj = obj;
@@ -3089,7 +3181,7 @@ static void launch_trajectory_rhs_m(const TraceArgs &a, double *traj, uint32_t *
         const unsigned threads = (a.n <= 64 && T >= 1024) ? 256u : 64u;   // (four waves = one per SIMD of a CU; eight measured slower than one)
         BHG_LAUNCH((trajectory_dp54_kernel<RHS, true, FIXED>), dim3((unsigned)a.n), dim3(threads), 0, s, a, traj, n_valid, T);
     } else {
-        BHG_LAUNCH((trajectory_dp54_kernel<RHS, false, FIXED>), dim3((unsigned)((a.n + 63) / 64)), dim3(64), 0, s, a, traj, n_valid, T);
+        BHG_LAUNCH((trajectory_dp54_kernel<RHS, false, FIXED>), lane_grid(a.n), dim3(64), 0, s, a, traj, n_valid, T);
     }
 }
 
@@ -3119,10 +3211,7 @@ hipError_t launch_trajectory(const TraceArgs &a, int rhs, int method, double *tr
 {
     if (rhs == BHG_RHS_KERR_BL_) return launch_trajectory_kerr(a, method, traj, n_valid, T, s);
     if (rhs == BHG_RHS_CHRISTOFFEL_TL_) return launch_trajectory_timelike(a, method, traj, n_valid, T, s);
-    if (rhs == BHG_RHS_REDUCED_)
-        launch_trajectory_rhs<BHG_RHS_REDUCED_>(a, method, traj, n_valid, T, s);
-    else
-        launch_trajectory_rhs<BHG_RHS_CHRISTOFFEL_>(a, method, traj, n_valid, T, s);
+    with_rhs(rhs, [&](auto R) { launch_trajectory_rhs<R.value>(a, method, traj, n_valid, T, s); });
     return hipGetLastError();
 }
 #endif
@@ -3154,7 +3243,7 @@ __global__ void __launch_bounds__(64, (RHS == BHG_RHS_KERR_BL_ ? BHG_KERR_WAVES_
     double xe[3], ve[3];
     if (start_ray<RHS, true>(A, i, S, xe, ve)) {    // final at once, no crossings
         A.n_cross[i] = 0;
-        store_result(A, (uint32_t)i, xe, ve, BHG_FLAG_START_INSIDE_ | BHG_FLAG_HIT_HORIZON_, 0, 0);
+        store_start_inside(A, i, xe, ve);
         return;
     }
     uint32_t flags = 0, n_cross = 0;
@@ -3174,54 +3263,21 @@ __global__ void __launch_bounds__(64, (RHS == BHG_RHS_KERR_BL_ ? BHG_KERR_WAVES_
         if (ev_h || ev_e || ev_d) {
             Dense d;
             build_dense(d, S.t, P.h, S.x, S.v, S.a1, P.a2, P.a3, P.a4, P.a5, P.a6, P.a7);
-            auto g_z = [&](double tt) {
-                if (!bl) return dense_z(d, tt);
-                double q[3], sn, cs;
-                dense_pos(d, tt, q);
-                sincos_pi4(q[1], sn, cs);
-                return cs;
-            };
             if (ev_h || ev_e) {
-                // the terminal events, settled as the trace kernels settle them (the earliest root wins, horizon before exit)
+                // the terminal events, settled as the trace kernels settle them (the earliest root wins, horizon before exit).
+                // (settle_dense's call, written out: through the helper this kernel, alone on a three-waves budget, takes 16
+                // and 8 more bytes of scratch)
                 double best;
                 int obj;
                 evflag = settle_events<EVT_EXIT>(
                     A, (ev_h ? EV_HORIZON : 0u) | (ev_e ? EV_EXIT : 0u), S.t, P.t_new, S.x, P.xn,
-                    [&](double tt, double Rr) { return dense_g(d, tt, Rr, bl); }, g_z,
+                    [&](double tt, double Rr) { return dense_g(d, tt, Rr, bl); }, [&](double tt) { return dense_plane_g(d, tt, bl); },
                     [&](double tt, double xq[3]) { dense_pos(d, tt, xq); }, bl, best, obj);
                 if (evflag) t_stop = best;
             }
             if (ev_d) {
-                const double root = brent_root(g_z, S.t, P.t_new);
-                double sx[3], sv[3];
-                dense_pos(d, root, sx);
-                // cylindrical radius of the crossing point, as settle_events takes it
-                double R;
-                if (bl) {
-                    double sn, cs;
-                    sincos_pi4(sx[1], sn, cs);
-                    R = sqrt(sx[0] * sx[0] + A.spin * A.spin) * fabs(sn);
-                } else {
-                    R = sqrt(sx[0] * sx[0] + sx[1] * sx[1]);
-                }
-                if (R >= A.disk_r_in && R <= A.disk_r_out && (!evflag || root <= t_stop)) {
-                    if (n_cross < (uint32_t)A.max_cross) {
-                        dense_dir(d, root, sv);
-                        if (bl) {
-                            double c[6];
-                            bl_record_to_cart(A.spin, sx, sv, c);
-                            for (int q = 0; q < 3; q++) {
-                                sx[q] = c[q];
-                                sv[q] = c[3 + q];
-                            }
-                        }
-                        double *o = A.cross + ((uint64_t)n_cross * A.cross_stride + i) * 6;
-                        reinterpret_cast<double2 *>(o)[0] = make_double2(sx[0], sx[1]);
-                        reinterpret_cast<double2 *>(o)[1] = make_double2(sx[2], sv[0]);
-                        reinterpret_cast<double2 *>(o)[2] = make_double2(sv[1], sv[2]);
-                    }
-                    n_cross++;
-                }
+                double root;
+                record_crossing<RHS>(A, i, d, P.t_new, evflag, t_stop, n_cross, root);
             }
             if (evflag) {
                 flags = evflag;
@@ -3242,21 +3298,13 @@ __global__ void __launch_bounds__(64, (RHS == BHG_RHS_KERR_BL_ ? BHG_KERR_WAVES_
 #if defined(BHG_TU_KERR)
 hipError_t launch_trace_crossings_kerr(const TraceArgs &a, hipStream_t s)
 {
-    if (a.n == 0) return hipSuccess;
-    BHG_LAUNCH((disk_crossings_kernel<BHG_RHS_KERR_BL_>), dim3((unsigned)((a.n + 63) / 64)), dim3(64), 0, s, a);
-    return hipGetLastError();
+    return launch_lanes(a, BHG_RHS_KERR_BL_, [&](auto R, dim3 grid) { BHG_LAUNCH((disk_crossings_kernel<R.value>), grid, dim3(64), 0, s, a); });
 }
 #elif !defined(BHG_TU_TIMELIKE)
 hipError_t launch_trace_crossings(const TraceArgs &a, int rhs, hipStream_t s)
 {
     if (rhs == BHG_RHS_KERR_BL_) return launch_trace_crossings_kerr(a, s);
-    if (a.n == 0) return hipSuccess;
-    const dim3 grid((unsigned)((a.n + 63) / 64));
-    if (rhs == BHG_RHS_REDUCED_)
-        BHG_LAUNCH((disk_crossings_kernel<BHG_RHS_REDUCED_>), grid, dim3(64), 0, s, a);
-    else
-        BHG_LAUNCH((disk_crossings_kernel<BHG_RHS_CHRISTOFFEL_>), grid, dim3(64), 0, s, a);
-    return hipGetLastError();
+    return launch_lanes(a, rhs, [&](auto R, dim3 grid) { BHG_LAUNCH((disk_crossings_kernel<R.value>), grid, dim3(64), 0, s, a); });
 }
 #endif
 
@@ -3272,9 +3320,10 @@ hipError_t launch_trace_crossings(const TraceArgs &a, int rhs, hipStream_t s)
 // start of its step plus the same rule on [lambda_j, root].  A node at r <= r_hor makes the ray's time and every time
 // after it +inf (the ray stepped across the hole: section 7's transparent centre); a ray that ends on the horizon or
 // starts inside has t_end = +inf, a ray flagged NaN has NaN.
-// A sibling of disk_crossings_kernel rather than a switch on it: that kernel's code stays as it is.  The position half of
-// the dense output is live on every accepted step here, so the kernel has the whole register file of one wave
-// (__launch_bounds__(64)) rather than the headline kernels' three-waves budget: this is a side path.
+// A kernel of its own beside disk_crossings_kernel, not a switch on it; the two share the crossing record (record_crossing)
+// and the helpers above.  The position half of the dense output is live on every accepted step here, so the kernel has the
+// whole register file of one wave (__launch_bounds__(64)) rather than the headline kernels' three-waves budget: this is a
+// side path.
 // max_cross = 0 and disk_r_out = 0 are allowed: no plane test, no records (cross, n_cross, t_cross may then be null).  With the
 // disk off end / flags / n_steps / n_accepted are the PLAIN trace's bit for bit (with a disk: the crossings trace's).
 // ------------------------------------------------------------------------------------------
@@ -3329,7 +3378,7 @@ __global__ void __launch_bounds__(64) travel_time_kernel(const TraceArgs A, doub
     if (start_ray<RHS, true>(A, i, S, xe, ve)) {    // final at once, no crossings
         if (A.n_cross) A.n_cross[i] = 0;
         t_end[i] = __builtin_inf();
-        store_result(A, (uint32_t)i, xe, ve, BHG_FLAG_START_INSIDE_ | BHG_FLAG_HIT_HORIZON_, 0, 0);
+        store_start_inside(A, i, xe, ve);
         return;
     }
     // Schwarzschild: E from the start state (Kerr: Metric::E)
@@ -3361,67 +3410,25 @@ __global__ void __launch_bounds__(64) travel_time_kernel(const TraceArgs A, doub
         build_dense_pos(d, S.t, P.h, S.x, S.v, S.a1, P.a2, P.a3, P.a4, P.a5, P.a6, P.a7);
         if (ev_h || ev_e || ev_d) {
             build_dense_dir(d, S.a1, P.a2, P.a3, P.a4, P.a5, P.a6, P.a7);
-            auto g_z = [&](double tq) {
-                if (!bl) return dense_z(d, tq);
-                double q[3], sn, cs;
-                dense_pos(d, tq, q);
-                sincos_pi4(q[1], sn, cs);
-                return cs;
-            };
             if (ev_h || ev_e) {
                 // the terminal events, settled as the trace kernels settle them (the earliest root wins, horizon before exit)
                 double best;
                 int obj;
-                evflag = settle_events<EVT_EXIT>(
-                    A, (ev_h ? EV_HORIZON : 0u) | (ev_e ? EV_EXIT : 0u), S.t, P.t_new, S.x, P.xn,
-                    [&](double tq, double Rr) { return dense_g(d, tq, Rr, bl); }, g_z,
-                    [&](double tq, double xq[3]) { dense_pos(d, tq, xq); }, bl, best, obj);
+                evflag = settle_dense<RHS, EVT_EXIT>(A, (ev_h ? EV_HORIZON : 0u) | (ev_e ? EV_EXIT : 0u), S, P, d, best, obj);
                 if (evflag) t_stop = best;
             }
             if (ev_d) {
-                const double root = brent_root(g_z, S.t, P.t_new);
-                double sx[3], sv[3];
-                dense_pos(d, root, sx);
-                // cylindrical radius of the crossing point, as settle_events takes it
-                double R;
-                if (bl) {
-                    double sn, cs;
-                    sincos_pi4(sx[1], sn, cs);
-                    R = sqrt(sx[0] * sx[0] + A.spin * A.spin) * fabs(sn);
-                } else {
-                    R = sqrt(sx[0] * sx[0] + sx[1] * sx[1]);
-                }
-                if (R >= A.disk_r_in && R <= A.disk_r_out && (!evflag || root <= t_stop)) {
-                    if (n_cross < (uint32_t)A.max_cross) {
-                        dense_dir(d, root, sv);
-                        if (bl) {
-                            double c[6];
-                            bl_record_to_cart(A.spin, sx, sv, c);
-                            for (int q = 0; q < 3; q++) {
-                                sx[q] = c[q];
-                                sv[q] = c[3 + q];
-                            }
-                        }
-                        double *o = A.cross + ((uint64_t)n_cross * A.cross_stride + i) * 6;
-                        reinterpret_cast<double2 *>(o)[0] = make_double2(sx[0], sx[1]);
-                        reinterpret_cast<double2 *>(o)[1] = make_double2(sx[2], sv[0]);
-                        reinterpret_cast<double2 *>(o)[2] = make_double2(sv[1], sv[2]);
-                        t_cross[(uint64_t)n_cross * A.cross_stride + i] = tt + time_quadrature<RHS>(A, S.met, E, d, root - S.t);
-                    }
-                    n_cross++;
-                }
+                double root;
+                const int m = record_crossing<RHS>(A, i, d, P.t_new, evflag, t_stop, n_cross, root);
+                if (m >= 0) t_cross[(uint64_t)m * A.cross_stride + i] = tt + time_quadrature<RHS>(A, S.met, E, d, root - S.t);
             }
         }
         tt += time_quadrature<RHS>(A, S.met, E, d, t_stop - S.t);
         if (evflag) {
             flags = evflag;
-            // Disk off: the results are the plain trace's, bit for bit.  The trace kernels take a step whose ONE candidate event
-            // is the exit sphere through their certified Newton search first (dp54_short_core: the same root to 4 eps, another
-            // iterate) and leave everything else to the Brent search above; so does this.  It stores the ray's result itself.
-            // The time still runs to Brent's root, as it does with a disk: one definition of the time, two ulp apart at most.
-            if (!disk && ev_e && !ev_h &&
-                dp54_short_core<RHS, EVT_EXIT>(A, S.x, S.v, S.a1, S.t, P.t_new, P.h, P.a2, P.a3, P.a4, P.a5, P.a6, P.a7, P.xn, P.vn,
-                                               EV_EXIT, (uint32_t)i, S.n_att, S.n_acc) == PARK_ENDED) {
+            // (disk off: the plain trace's bits.  The time still runs to Brent's root, as it does with a disk: one definition
+            // of the time, two ulp apart at most)
+            if (exit_as_plain_trace<RHS>(A, i, S, P, ev_h, ev_e)) {
                 stored = true;
                 break;
             }
@@ -3453,28 +3460,20 @@ __global__ void __launch_bounds__(64) travel_time_kernel(const TraceArgs A, doub
 #if defined(BHG_TU_KERR)
 hipError_t launch_travel_time_kerr(const TraceArgs &a, double *t_end, double *t_cross, hipStream_t s)
 {
-    if (a.n == 0) return hipSuccess;
-    BHG_LAUNCH((travel_time_kernel<BHG_RHS_KERR_BL_>), dim3((unsigned)((a.n + 63) / 64)), dim3(64), 0, s, a, t_end, t_cross);
-    return hipGetLastError();
+    return launch_lanes(a, BHG_RHS_KERR_BL_, [&](auto R, dim3 grid) { BHG_LAUNCH((travel_time_kernel<R.value>), grid, dim3(64), 0, s, a, t_end, t_cross); });
 }
 #elif !defined(BHG_TU_TIMELIKE)
 hipError_t launch_travel_time(const TraceArgs &a, int rhs, double *t_end, double *t_cross, hipStream_t s)
 {
     if (rhs == BHG_RHS_KERR_BL_) return launch_travel_time_kerr(a, t_end, t_cross, s);
-    if (a.n == 0) return hipSuccess;
-    const dim3 grid((unsigned)((a.n + 63) / 64));
-    if (rhs == BHG_RHS_REDUCED_)
-        BHG_LAUNCH((travel_time_kernel<BHG_RHS_REDUCED_>), grid, dim3(64), 0, s, a, t_end, t_cross);
-    else
-        BHG_LAUNCH((travel_time_kernel<BHG_RHS_CHRISTOFFEL_>), grid, dim3(64), 0, s, a, t_end, t_cross);
-    return hipGetLastError();
+    return launch_lanes(a, rhs, [&](auto R, dim3 grid) { BHG_LAUNCH((travel_time_kernel<R.value>), grid, dim3(64), 0, s, a, t_end, t_cross); });
 }
 #endif
 
 // ------------------------------------------------------------------------------------------
 // Triangle meshes (bhg_trace_mesh_device): the trace's steps, unchanged, with a mesh as one more terminal
-// event.  travel_time_kernel's loop without the quadrature, on the same helpers; per accepted step [t, t + h]:
-//   * the terminal events of the trace (horizon, exit sphere, and -- a disk set -- the opaque disk) are settled by settle_events;
+// event.  A lane-per-ray loop on the shared helpers above; per accepted step [t, t + h]:
+//   * the terminal events of the trace (horizon, exit sphere, and -- a disk set -- the opaque disk) are settled by settle_dense;
 //   * M = min(BHG_MESH_MAX_SUBSTEPS, max(1, ceil(L / max_chord))), L the Cartesian distance between the step's ends; the dense
 //     output is sampled at theta_m = m / M (Kerr: the Cartesian image of the Boyer-Lindquist sample) and consecutive samples are
 //     M straight sub-chords, tested in order against the tree (segment_first_hit: smallest s, ties to the smaller index);
@@ -3489,7 +3488,7 @@ hipError_t launch_travel_time(const TraceArgs &a, int rhs, double *t_end, double
 // bound on r, against the mesh's range of distances from the origin (a point at Boyer-Lindquist r lies at a Cartesian distance
 // in [r, sqrt(r^2 + a^2)]).
 // Disk off, a ray that meets no triangle has the plain trace's end / flags / n_steps / n_accepted bit for bit (the exit sphere's
-// certified Newton search, as in travel_time_kernel).
+// certified Newton search: exit_as_plain_trace).
 // ------------------------------------------------------------------------------------------
 template <int RHS>
 __device__ __forceinline__ void mesh_point(const TraceArgs &A, const Dense &d, double t, double c[3])
@@ -3552,7 +3551,7 @@ __global__ void __launch_bounds__(64) trace_mesh_kernel(const TraceArgs A, const
     double xe[3], ve[3];
     if (start_ray<RHS, true>(A, i, S, xe, ve)) {    // final at once
         G.tri_id[i] = -1;
-        store_result(A, (uint32_t)i, xe, ve, BHG_FLAG_START_INSIDE_ | BHG_FLAG_HIT_HORIZON_, 0, 0);
+        store_start_inside(A, i, xe, ve);
         return;
     }
     uint32_t flags = 0;
@@ -3573,20 +3572,11 @@ __global__ void __launch_bounds__(64) trace_mesh_kernel(const TraceArgs A, const
         Dense d;
         build_dense_pos(d, S.t, P.h, S.x, S.v, S.a1, P.a2, P.a3, P.a4, P.a5, P.a6, P.a7);
         if (ev_h || ev_e || ev_d) {
-            auto g_z = [&](double tq) {
-                if (!bl) return dense_z(d, tq);
-                double q[3], sn, cs;
-                dense_pos(d, tq, q);
-                sincos_pi4(q[1], sn, cs);
-                return cs;
-            };
             // the terminal events, settled as the trace kernels settle them (the earliest root wins: horizon, exit, disk)
+            const uint32_t kind = (ev_h ? EV_HORIZON : 0u) | (ev_e ? EV_EXIT : 0u) | (ev_d ? EV_DISK : 0u);
             double best;
             int obj;
-            evflag = settle_events<EVT_EXIT | EVT_DISK>(
-                A, (ev_h ? EV_HORIZON : 0u) | (ev_e ? EV_EXIT : 0u) | (ev_d ? EV_DISK : 0u), S.t, P.t_new, S.x, P.xn,
-                [&](double tq, double Rr) { return dense_g(d, tq, Rr, bl); }, g_z,
-                [&](double tq, double xq[3]) { dense_pos(d, tq, xq); }, bl, best, obj);
+            evflag = settle_dense<RHS, EVT_EXIT | EVT_DISK>(A, kind, S, P, d, best, obj);
             if (evflag) t_stop = best;
         }
         // the mesh
@@ -3654,10 +3644,8 @@ __global__ void __launch_bounds__(64) trace_mesh_kernel(const TraceArgs A, const
         }
         if (evflag) {
             flags = evflag;
-            // disk off and no triangle: the plain trace's bits (travel_time_kernel's rule for the exit sphere)
-            if (tri < 0 && !disk && ev_e && !ev_h &&
-                dp54_short_core<RHS, EVT_EXIT>(A, S.x, S.v, S.a1, S.t, P.t_new, P.h, P.a2, P.a3, P.a4, P.a5, P.a6, P.a7, P.xn, P.vn,
-                                               EV_EXIT, (uint32_t)i, S.n_att, S.n_acc) == PARK_ENDED) {
+            // disk off and no triangle: the plain trace's bits
+            if (tri < 0 && exit_as_plain_trace<RHS>(A, i, S, P, ev_h, ev_e)) {
                 G.tri_id[i] = -1;
                 return;
             }
@@ -3678,21 +3666,13 @@ __global__ void __launch_bounds__(64) trace_mesh_kernel(const TraceArgs A, const
 #if defined(BHG_TU_KERR)
 hipError_t launch_trace_mesh_kerr(const TraceArgs &a, const MeshArgs &m, hipStream_t s)
 {
-    if (a.n == 0) return hipSuccess;
-    BHG_LAUNCH((trace_mesh_kernel<BHG_RHS_KERR_BL_>), dim3((unsigned)((a.n + 63) / 64)), dim3(64), 0, s, a, m);
-    return hipGetLastError();
+    return launch_lanes(a, BHG_RHS_KERR_BL_, [&](auto R, dim3 grid) { BHG_LAUNCH((trace_mesh_kernel<R.value>), grid, dim3(64), 0, s, a, m); });
 }
 #elif !defined(BHG_TU_TIMELIKE)
 hipError_t launch_trace_mesh(const TraceArgs &a, const MeshArgs &m, int rhs, hipStream_t s)
 {
     if (rhs == BHG_RHS_KERR_BL_) return launch_trace_mesh_kerr(a, m, s);
-    if (a.n == 0) return hipSuccess;
-    const dim3 grid((unsigned)((a.n + 63) / 64));
-    if (rhs == BHG_RHS_REDUCED_)
-        BHG_LAUNCH((trace_mesh_kernel<BHG_RHS_REDUCED_>), grid, dim3(64), 0, s, a, m);
-    else
-        BHG_LAUNCH((trace_mesh_kernel<BHG_RHS_CHRISTOFFEL_>), grid, dim3(64), 0, s, a, m);
-    return hipGetLastError();
+    return launch_lanes(a, rhs, [&](auto R, dim3 grid) { BHG_LAUNCH((trace_mesh_kernel<R.value>), grid, dim3(64), 0, s, a, m); });
 }
 #endif
 
@@ -3766,20 +3746,12 @@ __global__ void __launch_bounds__(64) record_prefix_kernel(const TraceArgs A, do
 
 hipError_t launch_record_prefix(const TraceArgs &a, int rhs, void *rec, double rho, bool deep, hipStream_t s)
 {
-    if (a.n == 0) return hipSuccess;
-    const dim3 grid((unsigned)((a.n + 63) / 64));
-    if (rhs == BHG_RHS_REDUCED_) {
+    return launch_lanes(a, rhs, [&](auto R, dim3 grid) {
         if (deep)
-            BHG_LAUNCH((record_prefix_kernel<BHG_RHS_REDUCED_, true>), grid, dim3(64), 0, s, a, (double2 *)rec, rho);
+            BHG_LAUNCH((record_prefix_kernel<R.value, true>), grid, dim3(64), 0, s, a, (double2 *)rec, rho);
         else
-            BHG_LAUNCH((record_prefix_kernel<BHG_RHS_REDUCED_, false>), grid, dim3(64), 0, s, a, (double2 *)rec, rho);
-    } else {
-        if (deep)
-            BHG_LAUNCH((record_prefix_kernel<BHG_RHS_CHRISTOFFEL_, true>), grid, dim3(64), 0, s, a, (double2 *)rec, rho);
-        else
-            BHG_LAUNCH((record_prefix_kernel<BHG_RHS_CHRISTOFFEL_, false>), grid, dim3(64), 0, s, a, (double2 *)rec, rho);
-    }
-    return hipGetLastError();
+            BHG_LAUNCH((record_prefix_kernel<R.value, false>), grid, dim3(64), 0, s, a, (double2 *)rec, rho);
+    });
 }
 #endif
 
