@@ -2368,6 +2368,63 @@ int shade(bhg_context *c, const ShadeCall &s)
     return BHG_OK;
 }
 
+// The mesh shades, bhg_shade_mesh_device and bhg_shade_mesh_material_device, as one call record; shade() above stays what it is.
+// The checks, in the order their refusals are seen: the scene; the mesh; the material (the material call only, a NULL one
+// refused); the context and its device; n_pixels == 0 is BHG_OK; the device arrays
+struct MeshShadeCall {
+    ShadeCall s;                              // end, flags, n_pixels, samples, sc, the three outputs and the stream: nothing else is read
+    const int32_t *tri_id = nullptr;
+    const double *bary = nullptr;             // [n][2]
+    const bhg_mesh *mesh = nullptr;
+    const float *tri_rgb = nullptr;           // the plain call's colours
+    bool material = false;
+    const bhg_mesh_material *mat = nullptr;   // the material call's; NULL for the plain call
+};
+
+int shade_mesh(bhg_context *c, const MeshShadeCall &m)
+{
+    const ShadeCall &s = m.s;
+    BHG_TRY(scene_check(s.sc, s.samples, true));
+    if (!m.mesh) return fail(BHG_E_INVALID, "mesh is NULL");
+    if (m.material) {
+        BHG_TRY(bhg::mesh_material_check(m.mat, (size_t)m.mesh->view.n_tris, false));
+    }
+    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
+    if (m.mesh->device != c->device) return fail(BHG_E_INVALID, "the mesh lives on another device than the context");
+    if (s.n_pixels == 0) return BHG_OK;
+    if ((!s.rgba && !s.rgba_f32) || !s.end || !s.flags || !s.sc->d_sky || !m.tri_id || !m.bary)
+        return fail(BHG_E_INVALID, "NULL device pointer");
+    ENTER_DEVICE(c->device);
+    bhg::ShadeArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.end = s.end;
+    a.flags = s.flags;
+    a.rgba = s.rgba;
+    a.rgba_f32 = s.rgba_f32;
+    a.scatter = s.scatter;
+    a.n_pixels = s.n_pixels;
+    a.samples = s.samples;
+    fill_scene_args(a, s.sc);
+    if (!m.material) {
+        HIP_TRY(bhg::launch_shade_mesh(a, m.mesh->view, m.tri_id, m.bary, m.tri_rgb, (hipStream_t)s.stream));
+        return BHG_OK;
+    }
+    bhg::MeshMaterialArgs ma;
+    std::memset(&ma, 0, sizeof(ma));
+    ma.tri_rgb = m.mat->tri_rgb;
+    ma.tri_uv = m.mat->tri_uv;
+    ma.tri_tex = m.mat->tri_tex;
+    for (int j = 0; j < m.mat->n_tex; j++) {
+        ma.tex[j] = m.mat->tex[j];
+        ma.tex_w[j] = m.mat->tex_w[j];
+        ma.tex_h[j] = m.mat->tex_h[j];
+    }
+    ma.n_tex = m.mat->n_tex;
+    ma.emission = m.mat->emission;
+    HIP_TRY(bhg::launch_shade_mesh_material(a, m.mesh->view, m.tri_id, m.bary, ma, (hipStream_t)s.stream));
+    return BHG_OK;
+}
+
 // the scene of the sky-only calls: the sky and nothing else
 bhg_scene sky_scene(const float *d_sky, int32_t sky_w, int32_t sky_h)
 {
@@ -2425,74 +2482,24 @@ int bhg_shade_scene_device(bhg_context *c, const double *d_end, const uint8_t *d
                      .rgba = d_rgba, .stream = stream});
 }
 
-// the mesh shade: the plain scene shade's checks, then shade_mesh_kernel.  Its own call: shade() above stays
-// what it is
+// the mesh shades (DESIGN.md sections 19 and 20): one call (shade_mesh() above), without and with a material
 int bhg_shade_mesh_device(bhg_context *c, const double *d_end, const uint8_t *d_flags, const int32_t *d_tri_id, const double *d_bary,
                           size_t n_pixels, int32_t samples, const bhg_scene *sc, const bhg_mesh *mesh, const float *d_tri_rgb,
                           double *d_rgba, float *d_rgba_f32, const int64_t *d_scatter, void *stream)
 {
-    BHG_TRY(scene_check(sc, samples, true));
-    if (!mesh) return fail(BHG_E_INVALID, "mesh is NULL");
-    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
-    if (mesh->device != c->device) return fail(BHG_E_INVALID, "the mesh lives on another device than the context");
-    if (n_pixels == 0) return BHG_OK;
-    if ((!d_rgba && !d_rgba_f32) || !d_end || !d_flags || !sc->d_sky || !d_tri_id || !d_bary)
-        return fail(BHG_E_INVALID, "NULL device pointer");
-    ENTER_DEVICE(c->device);
-    bhg::ShadeArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.end = d_end;
-    a.flags = d_flags;
-    a.rgba = d_rgba;
-    a.rgba_f32 = d_rgba_f32;
-    a.scatter = d_scatter;
-    a.n_pixels = n_pixels;
-    a.samples = samples;
-    fill_scene_args(a, sc);
-    HIP_TRY(bhg::launch_shade_mesh(a, mesh->view, d_tri_id, d_bary, d_tri_rgb, (hipStream_t)stream));
-    return BHG_OK;
+    return shade_mesh(c, {.s = {.end = d_end, .flags = d_flags, .n_pixels = n_pixels, .samples = samples, .sc = sc, .rgba = d_rgba,
+                                .rgba_f32 = d_rgba_f32, .scatter = d_scatter, .stream = stream},
+                          .tri_id = d_tri_id, .bary = d_bary, .mesh = mesh, .tri_rgb = d_tri_rgb});
 }
 
-// the mesh material shade: bhg_shade_mesh_device's checks and the material's, then
-// shade_mesh_material_kernel
 int bhg_shade_mesh_material_device(bhg_context *c, const double *d_end, const uint8_t *d_flags, const int32_t *d_tri_id,
                                    const double *d_bary, size_t n_pixels, int32_t samples, const bhg_scene *sc, const bhg_mesh *mesh,
                                    const bhg_mesh_material *mat, double *d_rgba, float *d_rgba_f32, const int64_t *d_scatter,
                                    void *stream)
 {
-    BHG_TRY(scene_check(sc, samples, true));
-    if (!mesh) return fail(BHG_E_INVALID, "mesh is NULL");
-    BHG_TRY(bhg::mesh_material_check(mat, (size_t)mesh->view.n_tris, false));
-    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
-    if (mesh->device != c->device) return fail(BHG_E_INVALID, "the mesh lives on another device than the context");
-    if (n_pixels == 0) return BHG_OK;
-    if ((!d_rgba && !d_rgba_f32) || !d_end || !d_flags || !sc->d_sky || !d_tri_id || !d_bary)
-        return fail(BHG_E_INVALID, "NULL device pointer");
-    ENTER_DEVICE(c->device);
-    bhg::ShadeArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.end = d_end;
-    a.flags = d_flags;
-    a.rgba = d_rgba;
-    a.rgba_f32 = d_rgba_f32;
-    a.scatter = d_scatter;
-    a.n_pixels = n_pixels;
-    a.samples = samples;
-    fill_scene_args(a, sc);
-    bhg::MeshMaterialArgs m;
-    std::memset(&m, 0, sizeof(m));
-    m.tri_rgb = mat->tri_rgb;
-    m.tri_uv = mat->tri_uv;
-    m.tri_tex = mat->tri_tex;
-    for (int j = 0; j < mat->n_tex; j++) {
-        m.tex[j] = mat->tex[j];
-        m.tex_w[j] = mat->tex_w[j];
-        m.tex_h[j] = mat->tex_h[j];
-    }
-    m.n_tex = mat->n_tex;
-    m.emission = mat->emission;
-    HIP_TRY(bhg::launch_shade_mesh_material(a, mesh->view, d_tri_id, d_bary, m, (hipStream_t)stream));
-    return BHG_OK;
+    return shade_mesh(c, {.s = {.end = d_end, .flags = d_flags, .n_pixels = n_pixels, .samples = samples, .sc = sc, .rgba = d_rgba,
+                                .rgba_f32 = d_rgba_f32, .scatter = d_scatter, .stream = stream},
+                          .tri_id = d_tri_id, .bary = d_bary, .mesh = mesh, .material = true, .mat = mat});
 }
 
 int bhg_shade_scene_f32_device(bhg_context *c, const double *d_end, const uint8_t *d_flags, const int8_t *d_object_id,

@@ -918,17 +918,34 @@ __device__ __forceinline__ void write_stokes(const ShadeArgs &A, uint64_t p, con
     o[2] = make_double2(acc[4] * inv_s, acc[5] * inv_s);
 }
 
+// One ray's colour, as the skeleton below calls it: a type per shade family, ray(A, i, rgb, qu, extra...) the colour of ray i
+// (sample s of pixel p: i = s * n_pixels + p), qu its Stokes weights where STOKES says that the family has them.  The scene
+// shade's is ray_colour in the ray's exit direction: the second half of the end records, or (direction-only traces of sky
+// frames) an array of their own
+template <bool RS, bool OBS, bool TEX, bool POL, bool THERM, bool MOV>
+struct SceneColour {
+    static constexpr bool STOKES = POL;
+    static __device__ __forceinline__ void ray(const ShadeArgs &A, uint64_t i, double rgb[3], double qu[2])
+    {
+        const double *d = A.dir ? A.dir + i * 3 : A.end + i * 6 + 3;
+        ray_colour<RS, OBS, TEX, POL, THERM, MOV>(A, i, A.flags[i], d[0], d[1], d[2], rgb, qu);
+    }
+};
+
+// The pixel reduction under every shade (COLOUR: SceneColour, LayersColour, MeshColour; EXTRA: the argument structs a family
+// has beside ShadeArgs, handed on to COLOUR::ray).
 // One thread per RAY, the S samples of a pixel staged in LDS and summed by one thread in sample order (:242-250: sbuf +=
 // colour, sample after sample -- the order is part of the result).  A workgroup of 256 threads takes PPB = 256 / S
 // pixels; thread t = s * PPB + q is sample s of the block's q-th pixel, so that for a fixed s the block reads PPB
 // consecutive rays of the [S][P] layout (coalesced).  Against one thread per pixel walking its samples one after the
 // other (round 3; kept below for S > 256) this puts S times as many independent atan2 / texel-gather chains in flight:
 // the kernel is a latency chain per ray, not a bandwidth problem (131 MB in, 16 MB out per config-2 frame).
-// POL: each thread also stages the six Stokes products (Q, then U, of each channel; 9 doubles per thread in all, 18 KB per
-// workgroup) and the pixel's Q / U means go to pol.qu[p].
-template <bool RS, bool OBS, bool TEX, bool POL, bool THERM, bool MOV>
-__global__ void __launch_bounds__(256) shade_reduce_kernel(const ShadeArgs A, const uint32_t ppb)
+// POL (COLOUR::STOKES): each thread also stages the six Stokes products (Q, then U, of each channel; 9 doubles per thread in
+// all, 18 KB per workgroup) and the pixel's Q / U means go to pol.qu[p].
+template <class COLOUR, class... EXTRA>
+__global__ void __launch_bounds__(256) shade_pixels_kernel(const ShadeArgs A, const uint32_t ppb, const EXTRA... x)
 {
+    constexpr bool POL = COLOUR::STOKES;
     __shared__ double col[256 * 3];
     __shared__ double pcol[POL ? 256 * 6 : 1];
     const uint32_t t = threadIdx.x, S = (uint32_t)A.samples;
@@ -936,20 +953,13 @@ __global__ void __launch_bounds__(256) shade_reduce_kernel(const ShadeArgs A, co
     const uint64_t p = (uint64_t)blockIdx.x * ppb + q;
     const bool live = s < S && p < A.n_pixels;
     if (live) {
-        const uint64_t i = (uint64_t)s * A.n_pixels + p;
-        // exit directions: the second half of the end records, or (direction-only traces of sky frames) an array of their own
-        const double *d = A.dir ? A.dir + i * 3 : A.end + i * 6 + 3;
-        double rgb[3];
-        if (POL) {
-            double qu[2];
-            ray_colour<RS, OBS, TEX, POL, THERM, MOV>(A, i, A.flags[i], d[0], d[1], d[2], rgb, qu);
+        double rgb[3], qu[2];
+        COLOUR::ray(A, (uint64_t)s * A.n_pixels + p, rgb, POL ? qu : nullptr, x...);
+        if (POL)
             for (int c = 0; c < 3; c++) {
                 pcol[t * 6 + c] = qu[0] * rgb[c];
                 pcol[t * 6 + 3 + c] = qu[1] * rgb[c];
             }
-        } else {
-            ray_colour<RS, OBS, TEX, POL, THERM, MOV>(A, i, A.flags[i], d[0], d[1], d[2], rgb, nullptr);
-        }
         col[t * 3 + 0] = rgb[0];
         col[t * 3 + 1] = rgb[1];
         col[t * 3 + 2] = rgb[2];
@@ -977,18 +987,17 @@ __global__ void __launch_bounds__(256) shade_reduce_kernel(const ShadeArgs A, co
 }
 
 // More samples than a workgroup has threads: one thread per pixel, samples accumulated in registers in sample order.
-template <bool RS, bool OBS, bool TEX, bool POL, bool THERM, bool MOV>
-__global__ void __launch_bounds__(256) shade_reduce_serial_kernel(const ShadeArgs A)
+template <class COLOUR, class... EXTRA>
+__global__ void __launch_bounds__(256) shade_pixels_serial_kernel(const ShadeArgs A, const EXTRA... x)
 {
+    constexpr bool POL = COLOUR::STOKES;
     const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= A.n_pixels) return;
     double acc[3] = {0.0, 0.0, 0.0};
     double pacc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int s = 0; s < A.samples; s++) {
-        const uint64_t i = (uint64_t)s * A.n_pixels + p;
-        const double *d = A.dir ? A.dir + i * 3 : A.end + i * 6 + 3;
         double rgb[3], qu[2];
-        ray_colour<RS, OBS, TEX, POL, THERM, MOV>(A, i, A.flags[i], d[0], d[1], d[2], rgb, qu);
+        COLOUR::ray(A, (uint64_t)s * A.n_pixels + p, rgb, qu, x...);
         acc[0] += rgb[0];
         acc[1] += rgb[1];
         acc[2] += rgb[2];
@@ -1062,55 +1071,17 @@ __device__ __forceinline__ void layers_colour(const ShadeArgs &A, uint64_t i, ui
     }
 }
 
-// shade_reduce_kernel's shape: one thread per RAY, the S samples of a pixel staged in LDS and summed in sample order
-template <bool RS, bool OBS, bool THERM, class... RET>
-__global__ void __launch_bounds__(256) shade_layers_kernel(const ShadeArgs A, const uint32_t ppb, const RET... ret)
-{
-    __shared__ double col[256 * 3];
-    const uint32_t t = threadIdx.x, S = (uint32_t)A.samples;
-    const uint32_t s = t / ppb, q = t - s * ppb;
-    const uint64_t p = (uint64_t)blockIdx.x * ppb + q;
-    const bool live = s < S && p < A.n_pixels;
-    if (live) {
-        const uint64_t i = (uint64_t)s * A.n_pixels + p;
+// the layered shade's colour type: the exit direction as SceneColour reads it, RET the skeleton's extra argument
+template <bool RS, bool OBS, bool THERM>
+struct LayersColour {
+    static constexpr bool STOKES = false;
+    template <class... RET>
+    static __device__ __forceinline__ void ray(const ShadeArgs &A, uint64_t i, double rgb[3], double *, const RET &...ret)
+    {
         const double *d = A.dir ? A.dir + i * 3 : A.end + i * 6 + 3;
-        double rgb[3];
-        layers_colour<RS, OBS, THERM>(A, i, (uint64_t)S * A.n_pixels, A.flags[i], d[0], d[1], d[2], rgb, ret...);
-        col[t * 3 + 0] = rgb[0];
-        col[t * 3 + 1] = rgb[1];
-        col[t * 3 + 2] = rgb[2];
+        layers_colour<RS, OBS, THERM>(A, i, (uint64_t)(uint32_t)A.samples * A.n_pixels, A.flags[i], d[0], d[1], d[2], rgb, ret...);
     }
-    __syncthreads();
-    if (s == 0 && live) {
-        double acc[3] = {0.0, 0.0, 0.0};
-        for (uint32_t k = 0; k < S; k++) {
-            const double *c = col + (size_t)(k * ppb + q) * 3;
-            acc[0] += c[0];
-            acc[1] += c[1];
-            acc[2] += c[2];
-        }
-        write_pixel(A, p, acc);
-    }
-}
-
-// more samples than a workgroup has threads: one thread per pixel (shade_reduce_serial_kernel's shape)
-template <bool RS, bool OBS, bool THERM, class... RET>
-__global__ void __launch_bounds__(256) shade_layers_serial_kernel(const ShadeArgs A, const RET... ret)
-{
-    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= A.n_pixels) return;
-    double acc[3] = {0.0, 0.0, 0.0};
-    for (int s = 0; s < A.samples; s++) {
-        const uint64_t i = (uint64_t)s * A.n_pixels + p;
-        const double *d = A.dir ? A.dir + i * 3 : A.end + i * 6 + 3;
-        double rgb[3];
-        layers_colour<RS, OBS, THERM>(A, i, (uint64_t)A.samples * A.n_pixels, A.flags[i], d[0], d[1], d[2], rgb, ret...);
-        acc[0] += rgb[0];
-        acc[1] += rgb[1];
-        acc[2] += rgb[2];
-    }
-    write_pixel(A, p, acc);
-}
+};
 
 // dst[i] = src[index[i]] for rows of four floats: puts the gathered per-rank slabs into frame order on the
 // root GPU (index = the frame's permutation, computed once).  HBM-bound: 8 + 16 + 16 bytes per pixel.
@@ -1158,61 +1129,52 @@ hipError_t launch_raygen(const RaygenArgs &a, hipStream_t s)
     return hipGetLastError();
 }
 
+// the launch of the per-ray kernels: one thread per ray, the observer's instance or the plain one
+template <class ARGS>
+hipError_t launch_per_ray(void (*with_obs)(ARGS), void (*plain)(ARGS), bool obs, const ARGS &a, uint64_t n, hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    BHG_LAUNCH(obs ? with_obs : plain, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_redshift(const RedshiftArgs &a, hipStream_t s)
 {
-    if (a.n == 0) return hipSuccess;
-    if (a.obs.on)
-        BHG_LAUNCH(redshift_kernel<true>, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
-    else
-        BHG_LAUNCH(redshift_kernel<false>, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
-    return hipGetLastError();
+    return launch_per_ray(redshift_kernel<true>, redshift_kernel<false>, a.obs.on != 0, a, a.n, s);
 }
 
 hipError_t launch_redshift_motion(const RedshiftArgs &a, hipStream_t s)
 {
-    if (a.n == 0) return hipSuccess;
-    if (a.obs.on)
-        BHG_LAUNCH(redshift_motion_kernel<true>, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
-    else
-        BHG_LAUNCH(redshift_motion_kernel<false>, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
-    return hipGetLastError();
+    return launch_per_ray(redshift_motion_kernel<true>, redshift_motion_kernel<false>, a.obs.on != 0, a, a.n, s);
 }
 
 hipError_t launch_polarisation(const PolarisationArgs &a, bool obs, hipStream_t s)
 {
-    if (a.n == 0) return hipSuccess;
-    if (obs)
-        BHG_LAUNCH(polarisation_kernel<true>, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
-    else
-        BHG_LAUNCH(polarisation_kernel<false>, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
-    return hipGetLastError();
+    return launch_per_ray(polarisation_kernel<true>, polarisation_kernel<false>, obs, a, a.n, s);
 }
 
 hipError_t launch_disk_thermal(const ThermalArgs &a, hipStream_t s)
 {
-    if (a.n == 0) return hipSuccess;
-    if (a.obs.on)
-        BHG_LAUNCH(disk_thermal_kernel<true>, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
-    else
-        BHG_LAUNCH(disk_thermal_kernel<false>, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
-    return hipGetLastError();
+    return launch_per_ray(disk_thermal_kernel<true>, disk_thermal_kernel<false>, a.obs.on != 0, a, a.n, s);
 }
 
-// one instance per (redshift, observer, textures, polarisation, thermal, motion): the template flags are the launch's run-time
-// switches
-template <bool RS, bool OBS, bool TEX, bool POL, bool THERM, bool MOV>
-void launch_shade_instance(const ShadeArgs &a, hipStream_t s)
+// the launch of the pixel reduction, for every shade family: the LDS kernel with PPB = 256 / S pixels per workgroup, or -- more
+// samples than a workgroup has threads -- the serial one
+template <class COLOUR, class... EXTRA>
+void launch_shade_pixels(const ShadeArgs &a, hipStream_t s, const EXTRA &...x)
 {
     if (a.samples > 256) {
         const dim3 grid((unsigned)((a.n_pixels + 255) / 256));
-        BHG_LAUNCH((shade_reduce_serial_kernel<RS, OBS, TEX, POL, THERM, MOV>), grid, dim3(256), 0, s, a);
+        BHG_LAUNCH((shade_pixels_serial_kernel<COLOUR, EXTRA...>), grid, dim3(256), 0, s, a, x...);
         return;
     }
     const uint32_t ppb = 256u / (uint32_t)a.samples;      // pixels per workgroup
     const dim3 grid((unsigned)((a.n_pixels + ppb - 1) / ppb));
-    BHG_LAUNCH((shade_reduce_kernel<RS, OBS, TEX, POL, THERM, MOV>), grid, dim3(256), 0, s, a, ppb);
+    BHG_LAUNCH((shade_pixels_kernel<COLOUR, EXTRA...>), grid, dim3(256), 0, s, a, ppb, x...);
 }
 
+// the scene shade: one instance per (redshift, observer, textures, polarisation, thermal, motion), the template flags are the
+// launch's run-time switches.
 // the thermal instances are redshift instances (the disk's emission needs g); THERM = true is instantiated with RS = true only.
 // So are the motion instances, taken only when objects are weighted (motion changes nothing else): MOV = true with RS = true only
 template <bool TEX, bool POL, bool MOV>
@@ -1221,15 +1183,15 @@ void launch_shade_mov(const ShadeArgs &a, hipStream_t s)
     const bool therm = a.th.on != 0, rs = a.rs.apply != 0 || therm, obs = rs && a.obs.on;
     if (therm) {
         if (obs)
-            launch_shade_instance<true, true, TEX, POL, true, MOV>(a, s);
+            launch_shade_pixels<SceneColour<true, true, TEX, POL, true, MOV>>(a, s);
         else
-            launch_shade_instance<true, false, TEX, POL, true, MOV>(a, s);
+            launch_shade_pixels<SceneColour<true, false, TEX, POL, true, MOV>>(a, s);
     } else if (obs) {
-        launch_shade_instance<true, true, TEX, POL, false, MOV>(a, s);
+        launch_shade_pixels<SceneColour<true, true, TEX, POL, false, MOV>>(a, s);
     } else if (rs) {
-        launch_shade_instance<true, false, TEX, POL, false, MOV>(a, s);
+        launch_shade_pixels<SceneColour<true, false, TEX, POL, false, MOV>>(a, s);
     } else if (!MOV) {
-        launch_shade_instance<false, false, TEX, POL, false, false>(a, s);
+        launch_shade_pixels<SceneColour<false, false, TEX, POL, false, false>>(a, s);
     }
 }
 
@@ -1258,19 +1220,6 @@ hipError_t launch_shade(const ShadeArgs &a, hipStream_t s)
     return hipGetLastError();
 }
 
-template <bool RS, bool OBS, bool THERM, class... RET>
-void launch_shade_layers_instance(const ShadeArgs &a, hipStream_t s, const RET &...ret)
-{
-    if (a.samples > 256) {
-        const dim3 grid((unsigned)((a.n_pixels + 255) / 256));
-        BHG_LAUNCH((shade_layers_serial_kernel<RS, OBS, THERM, RET...>), grid, dim3(256), 0, s, a, ret...);
-        return;
-    }
-    const uint32_t ppb = 256u / (uint32_t)a.samples;
-    const dim3 grid((unsigned)((a.n_pixels + ppb - 1) / ppb));
-    BHG_LAUNCH((shade_layers_kernel<RS, OBS, THERM, RET...>), grid, dim3(256), 0, s, a, ppb, ret...);
-}
-
 // the layered shade's five instances, chosen as launch_shade_mov chooses: thermal instances are redshift instances.  With
 // t_cross given (the C layer gives it only with a nonzero phase_rate) the three non-thermal ones have a retarded twin; the thermal
 // disk has no texture to turn, and its instances are the same with or without
@@ -1281,22 +1230,22 @@ hipError_t launch_shade_layers(const ShadeArgs &a, hipStream_t s, const double *
     if (t_cross && !therm) {
         const Retarded ret{t_cross, phase_rate};
         if (obs)
-            launch_shade_layers_instance<true, true, false>(a, s, ret);
+            launch_shade_pixels<LayersColour<true, true, false>>(a, s, ret);
         else if (rs)
-            launch_shade_layers_instance<true, false, false>(a, s, ret);
+            launch_shade_pixels<LayersColour<true, false, false>>(a, s, ret);
         else
-            launch_shade_layers_instance<false, false, false>(a, s, ret);
+            launch_shade_pixels<LayersColour<false, false, false>>(a, s, ret);
     } else if (therm) {
         if (obs)
-            launch_shade_layers_instance<true, true, true>(a, s);
+            launch_shade_pixels<LayersColour<true, true, true>>(a, s);
         else
-            launch_shade_layers_instance<true, false, true>(a, s);
+            launch_shade_pixels<LayersColour<true, false, true>>(a, s);
     } else if (obs) {
-        launch_shade_layers_instance<true, true, false>(a, s);
+        launch_shade_pixels<LayersColour<true, true, false>>(a, s);
     } else if (rs) {
-        launch_shade_layers_instance<true, false, false>(a, s);
+        launch_shade_pixels<LayersColour<true, false, false>>(a, s);
     } else {
-        launch_shade_layers_instance<false, false, false>(a, s);
+        launch_shade_pixels<LayersColour<false, false, false>>(a, s);
     }
     return hipGetLastError();
 }
@@ -1308,7 +1257,7 @@ hipError_t launch_shade_layers(const ShadeArgs &a, hipStream_t s, const double *
 //       turned to face the incoming ray (n . end_dir < 0);
 //   a lamp shadowed when the straight segment from x + 1e-5 l^ to the lamp meets any triangle (segment_first_hit in its any-hit
 //   form; 1e-5 is object_colour's epsilon).
-// Every other ray is the plain shade's ray_colour, bit for bit.  shade_reduce_kernel's shape and its serial twin.
+// Every other ray is the plain shade's ray_colour, bit for bit.
 // ------------------------------------------------------------------------------------------
 struct MeshShade {
     MeshView mesh;
@@ -1364,69 +1313,12 @@ __device__ __forceinline__ void mesh_ray_colour(const ShadeArgs &A, const MeshSh
     ray_colour<false, false, false, false, false, false>(A, i, fl, d[0], d[1], d[2], rgb, nullptr);
 }
 
-__global__ void __launch_bounds__(256) shade_mesh_kernel(const ShadeArgs A, const MeshShade G, const uint32_t ppb)
-{
-    __shared__ double col[256 * 3];
-    const uint32_t t = threadIdx.x, S = (uint32_t)A.samples;
-    const uint32_t s = t / ppb, q = t - s * ppb;
-    const uint64_t p = (uint64_t)blockIdx.x * ppb + q;
-    const bool live = s < S && p < A.n_pixels;
-    if (live) {
-        double rgb[3];
-        mesh_ray_colour(A, G, (uint64_t)s * A.n_pixels + p, rgb);
-        col[t * 3 + 0] = rgb[0];
-        col[t * 3 + 1] = rgb[1];
-        col[t * 3 + 2] = rgb[2];
-    }
-    __syncthreads();
-    if (s == 0 && live) {
-        double acc[3] = {0.0, 0.0, 0.0};
-        for (uint32_t k = 0; k < S; k++) {
-            const double *c = col + (size_t)(k * ppb + q) * 3;
-            acc[0] += c[0];
-            acc[1] += c[1];
-            acc[2] += c[2];
-        }
-        write_pixel(A, p, acc);
-    }
-}
-
-// more samples than a workgroup has threads: one thread per pixel, in sample order
-__global__ void __launch_bounds__(256) shade_mesh_serial_kernel(const ShadeArgs A, const MeshShade G)
-{
-    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= A.n_pixels) return;
-    double acc[3] = {0.0, 0.0, 0.0};
-    for (int s = 0; s < A.samples; s++) {
-        double rgb[3];
-        mesh_ray_colour(A, G, (uint64_t)s * A.n_pixels + p, rgb);
-        acc[0] += rgb[0];
-        acc[1] += rgb[1];
-        acc[2] += rgb[2];
-    }
-    write_pixel(A, p, acc);
-}
-
-hipError_t launch_shade_mesh(const ShadeArgs &a, const MeshView &m, const int32_t *tri_id, const double *bary, const float *tri_rgb,
-                             hipStream_t s)
-{
-    if (a.n_pixels == 0) return hipSuccess;
-    const MeshShade g{m, tri_id, bary, tri_rgb};
-    if (a.samples > 256) {
-        BHG_LAUNCH(shade_mesh_serial_kernel, dim3((unsigned)((a.n_pixels + 255) / 256)), dim3(256), 0, s, a, g);
-        return hipGetLastError();
-    }
-    const uint32_t ppb = 256u / (uint32_t)a.samples;
-    BHG_LAUNCH(shade_mesh_kernel, dim3((unsigned)((a.n_pixels + ppb - 1) / ppb)), dim3(256), 0, s, a, g, ppb);
-    return hipGetLastError();
-}
-
 // ------------------------------------------------------------------------------------------
 // The mesh material shade (bhg_shade_mesh_material_device): a mesh ray gets albedo * (lamp_sum + emission),
 // albedo = tri_rgb[T] * texel.  lamp_sum is mesh_colour's sum itself -- called with a white MeshShade, its three channels are
 // 1.0 * sum -- so the normal, the facing rule, the shadow segment and the traversal are the one definition.  x * 1.0 and
 // sum + 0.0 are exact: without UVs and with emission = 0 the colour is mesh_colour's tri_rgb[T] * sum, bit for bit.
-// The kernels are shade_mesh_kernel's and its serial twin's, with the material as one more argument struct.
+// The material is one more argument struct behind MeshShade (MeshColour, below the colour functions).
 // ------------------------------------------------------------------------------------------
 // x mod n for an integer-valued x and a small positive integer n, in floating point as sky_lookup wraps its column: the
 // quotient's rounding can only be off by one period, which the two selects put right.  (The device form of the material is
@@ -1488,61 +1380,33 @@ __device__ __forceinline__ void mesh_material_ray_colour(const ShadeArgs &A, con
     ray_colour<false, false, false, false, false, false>(A, i, fl, d[0], d[1], d[2], rgb, nullptr);
 }
 
-__global__ void __launch_bounds__(256) shade_mesh_material_kernel(const ShadeArgs A, const MeshShade G, const MeshMaterialArgs M,
-                                                                  const uint32_t ppb)
-{
-    __shared__ double col[256 * 3];
-    const uint32_t t = threadIdx.x, S = (uint32_t)A.samples;
-    const uint32_t s = t / ppb, q = t - s * ppb;
-    const uint64_t p = (uint64_t)blockIdx.x * ppb + q;
-    const bool live = s < S && p < A.n_pixels;
-    if (live) {
-        double rgb[3];
-        mesh_material_ray_colour(A, G, M, (uint64_t)s * A.n_pixels + p, rgb);
-        col[t * 3 + 0] = rgb[0];
-        col[t * 3 + 1] = rgb[1];
-        col[t * 3 + 2] = rgb[2];
+// the mesh shades' colour type: one overload per family, told apart by the argument structs that ride behind ShadeArgs
+struct MeshColour {
+    static constexpr bool STOKES = false;
+    static __device__ __forceinline__ void ray(const ShadeArgs &A, uint64_t i, double rgb[3], double *, const MeshShade &G)
+    {
+        mesh_ray_colour(A, G, i, rgb);
     }
-    __syncthreads();
-    if (s == 0 && live) {
-        double acc[3] = {0.0, 0.0, 0.0};
-        for (uint32_t k = 0; k < S; k++) {
-            const double *c = col + (size_t)(k * ppb + q) * 3;
-            acc[0] += c[0];
-            acc[1] += c[1];
-            acc[2] += c[2];
-        }
-        write_pixel(A, p, acc);
+    static __device__ __forceinline__ void ray(const ShadeArgs &A, uint64_t i, double rgb[3], double *, const MeshShade &G,
+                                               const MeshMaterialArgs &M)
+    {
+        mesh_material_ray_colour(A, G, M, i, rgb);
     }
-}
+};
 
-// more samples than a workgroup has threads: one thread per pixel, in sample order
-__global__ void __launch_bounds__(256) shade_mesh_material_serial_kernel(const ShadeArgs A, const MeshShade G, const MeshMaterialArgs M)
+hipError_t launch_shade_mesh(const ShadeArgs &a, const MeshView &m, const int32_t *tri_id, const double *bary, const float *tri_rgb,
+                             hipStream_t s)
 {
-    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= A.n_pixels) return;
-    double acc[3] = {0.0, 0.0, 0.0};
-    for (int s = 0; s < A.samples; s++) {
-        double rgb[3];
-        mesh_material_ray_colour(A, G, M, (uint64_t)s * A.n_pixels + p, rgb);
-        acc[0] += rgb[0];
-        acc[1] += rgb[1];
-        acc[2] += rgb[2];
-    }
-    write_pixel(A, p, acc);
+    if (a.n_pixels == 0) return hipSuccess;
+    launch_shade_pixels<MeshColour>(a, s, MeshShade{m, tri_id, bary, tri_rgb});
+    return hipGetLastError();
 }
 
 hipError_t launch_shade_mesh_material(const ShadeArgs &a, const MeshView &m, const int32_t *tri_id, const double *bary,
                                       const MeshMaterialArgs &M, hipStream_t s)
 {
     if (a.n_pixels == 0) return hipSuccess;
-    const MeshShade g{m, tri_id, bary, nullptr};
-    if (a.samples > 256) {
-        BHG_LAUNCH(shade_mesh_material_serial_kernel, dim3((unsigned)((a.n_pixels + 255) / 256)), dim3(256), 0, s, a, g, M);
-        return hipGetLastError();
-    }
-    const uint32_t ppb = 256u / (uint32_t)a.samples;
-    BHG_LAUNCH(shade_mesh_material_kernel, dim3((unsigned)((a.n_pixels + ppb - 1) / ppb)), dim3(256), 0, s, a, g, M, ppb);
+    launch_shade_pixels<MeshColour>(a, s, MeshShade{m, tri_id, bary, nullptr}, M);
     return hipGetLastError();
 }
 

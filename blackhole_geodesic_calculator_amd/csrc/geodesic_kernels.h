@@ -298,7 +298,7 @@ struct ThermalArgs {
 
 hipError_t launch_raygen(const RaygenArgs &a, hipStream_t s);
 hipError_t launch_shade(const ShadeArgs &a, hipStream_t s);
-// the layered shade of an optically thin disk (shade_layers_kernel): a.cross / n_cross / max_cross / transmit filled
+// the layered shade of an optically thin disk (LayersColour under shade_pixels_kernel): a.cross / n_cross / max_cross / transmit filled
 // t_cross: nullptr, or [max_cross][S*n_pixels], the crossing times of the travel-time trace -- the retarded instances then draw
 // layer m of ray i at a.disk_phase - phase_rate * t_cross[m][i] (bhg_shade_disk_layers_retarded_device)
 hipError_t launch_shade_layers(const ShadeArgs &a, hipStream_t s, const double *t_cross = nullptr, double phase_rate = 0.0);
@@ -339,11 +339,11 @@ struct MeshArgs {
 constexpr int BHG_MESH_MAX_SUBSTEPS_ = 1024;
 hipError_t launch_trace_mesh(const TraceArgs &a, const MeshArgs &m, int rhs, hipStream_t s);
 hipError_t launch_trace_mesh_kerr(const TraceArgs &a, const MeshArgs &m, hipStream_t s);
-// the mesh shade (shade_mesh_kernel, frame_kernels.hip): a.end / flags / sky / disk / lamps as launch_shade's plain instance wants
+// the mesh shade (MeshColour under shade_pixels_kernel, frame_kernels.hip): a.end / flags / sky / disk / lamps as launch_shade's plain instance wants
 // them, n_spheres = 0; tri_rgb nullptr = white
 hipError_t launch_shade_mesh(const ShadeArgs &a, const MeshView &m, const int32_t *tri_id, const double *bary, const float *tri_rgb,
                              hipStream_t s);
-// the mesh material shade (shade_mesh_material_kernel): the material rides in an argument struct of its own
+// the mesh material shade (MeshColour with the material): the material rides in an argument struct of its own
 struct MeshMaterialArgs {
     const float *tri_rgb;    // [nt][3] in the caller's numbering, or nullptr (white)
     const float *tri_uv;     // [nt][3][2] in the caller's numbering, or nullptr (no textures)

@@ -16,7 +16,7 @@ frame_ms = trace + shade of the five frames per step; trace_ms / shade_ms = the 
 the like-for-like figure; the disk-off line's shade colours the sky alone, so shade_ms and frame_ratio also hold the colouring
 of the disk.  Host wall clock around synchronised blocks; medians over --reps blocks of each.  Run it under `rocprofv3
 --kernel-trace --stats -- python scripts/bench_disk_crossings.py` for the kernels' own times (disk_crossings_kernel,
-shade_layers_kernel)."""
+shade_pixels_kernel<LayersColour<...>>)."""
 import argparse
 import json
 import os

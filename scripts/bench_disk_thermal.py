@@ -9,7 +9,7 @@ frame_ms = trace + shade of the five frames per step; shade_ms = the five shade 
 the thermal disk: only the shade kernels take their thermal instance).  --redshift: redshift on objects and sky (g^4) in both
 blocks; without it the off block takes the plain instance and the on block the redshift one (the thermal disk needs g).  Host
 wall clock around synchronised blocks; medians over --reps blocks of each.  Run it under `rocprofv3 --kernel-trace --stats --
-python scripts/bench_disk_thermal.py` for the shade kernels' own times (shade_reduce_kernel<..., false> / <..., true>)."""
+python scripts/bench_disk_thermal.py` for the shade kernels' own times (shade_pixels_kernel<SceneColour<..., THERM = false / true, ...>>)."""
 import argparse
 import json
 import os

@@ -2,8 +2,8 @@
 19's cost scene: one 1024 x 1024 ray set (the camera at r = 30, 80 degrees from the axis, exit sphere at 40) and a sphere of
 --tris triangles (an octahedron subdivided onto radius 2 at (-5, 3, 1), behind the hole).  Timed in alternating blocks:
 
-    shade_plain     bhg_shade_mesh_device, tri_rgb only (shade_mesh_kernel)
-    shade_flat      bhg_shade_mesh_material_device, tri_rgb only (shade_mesh_material_kernel without a texel)
+    shade_plain     bhg_shade_mesh_device, tri_rgb only (shade_pixels_kernel<MeshColour, MeshShade>)
+    shade_flat      bhg_shade_mesh_material_device, tri_rgb only (shade_pixels_kernel<MeshColour, MeshShade, MeshMaterialArgs> without a texel)
     shade_textured  bhg_shade_mesh_material_device with per-corner UVs and a 1024 x 512 image
     frame           a whole _ffi.Frame.render of the textured mesh on one device, the image left on the device
 

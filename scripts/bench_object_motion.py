@@ -9,7 +9,7 @@ its fp64 RGBA image by DeviceFrame.shade() -- the sphere at rest, or moving and 
 frame_ms = trace + shade of one frame per step; shade_ms = the shade call alone on the block's last frame (the trace does not
 change with motion: only the shade kernel takes its motion instance).  Host wall clock around synchronised blocks; medians over --reps blocks of each.
 Run it under `rocprofv3 --kernel-trace --stats -- python scripts/bench_object_motion.py` for the shade kernels' own times
-(shade_reduce_kernel<true, false, false, false, false, false> / <..., true>)."""
+(shade_pixels_kernel<SceneColour<true, false, false, false, false, false>> / <..., true>>)."""
 import argparse
 import json
 import os

@@ -9,7 +9,7 @@ argument, DeviceFrame.set_object_textures without a texture), lit by the workloa
 frame_ms = set_objects + trace + shade_f32 per step; shade_ms = shade_f32 alone (the trace does not change with textures: only
 the shade kernels take their textured instance).  Host wall clock around synchronised blocks; medians over --reps blocks of
 each.  Run it under `rocprofv3 --kernel-trace --stats -- python scripts/bench_object_textures.py` for the shade kernels' own
-times (shade_reduce_kernel<false, false, false> / <false, false, true>)."""
+times (shade_pixels_kernel<SceneColour<false, false, TEX = false / true, ...>>)."""
 import argparse
 import json
 import os

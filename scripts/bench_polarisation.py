@@ -8,7 +8,7 @@ table (on: the same image plus the [P, 6] Q / U image) -- in alternating blocks 
 frame_ms = trace + shade of the five frames per step; shade_ms = the five shade calls alone (the trace does not change with
 polarisation: only the shade kernels take their polarised instance).  Host wall clock around synchronised blocks; medians over
 --reps blocks of each.  Run it under `rocprofv3 --kernel-trace --stats -- python scripts/bench_polarisation.py` for the shade
-kernels' own times (shade_reduce_kernel<..., false> / <..., true>)."""
+kernels' own times (shade_pixels_kernel<SceneColour<..., POL = false / true, ...>>)."""
 import argparse
 import json
 import os

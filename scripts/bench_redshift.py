@@ -8,7 +8,7 @@ weighted by g^4) in alternating blocks on the same frames.  Prints one JSON line
 frame_ms = trace + shade of the five frames per step; shade_ms = the five shade calls alone (the trace does not change with
 redshift: only the shade kernels take their redshift instance).  Host wall clock around synchronised blocks; medians over
 --reps blocks of each.  Run it under `rocprofv3 --kernel-trace --stats -- python scripts/bench_redshift.py` for the shade
-kernels' own times (shade_reduce_kernel<false> / <true>)."""
+kernels' own times (shade_pixels_kernel<SceneColour<RS = false / true, ...>>)."""
 import argparse
 import json
 import os

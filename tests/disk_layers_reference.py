@@ -1,4 +1,4 @@
-"""numpy restatement of the layered disk shade (bhg_shade_disk_layers_device, shade_layers_kernel) --
+"""numpy restatement of the layered disk shade (bhg_shade_disk_layers_device, layers_colour under shade_pixels_kernel) --
 TEST INFRASTRUCTURE ONLY.
 
 The optically thin disk: a ray that the crossings trace carried through the disk has the records cross[m] of its first crossings;
