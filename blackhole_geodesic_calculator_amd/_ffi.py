@@ -71,7 +71,11 @@ EXPORTS = (
     "bhg_mesh_create", "bhg_mesh_destroy", "bhg_mesh_info", "bhg_mesh_bvh_host", "bhg_trace_mesh_device", "bhg_trace_mesh",
     "bhg_shade_mesh_device",
     "bhg_mesh_material_size", "bhg_shade_mesh_material_device", "bhg_frame_set_mesh",
+    "bhg_mesh_instances_create", "bhg_mesh_instances_set", "bhg_mesh_instances_destroy", "bhg_mesh_instances_info",
+    "bhg_mesh_instance_box_host", "bhg_trace_mesh_instances_device", "bhg_trace_mesh_instances",
+    "bhg_shade_mesh_instances_device", "bhg_frame_set_mesh_instances",
 )
+MESH_INSTANCES_MAX = 64    # BHG_MESH_INSTANCES_MAX: rigid placements an instance set holds at most (BHG_MESH_INSTANCES)
 MESH_MAX_SUBSTEPS = 1024   # BHG_MESH_MAX_SUBSTEPS: sub-chords per accepted step at most (BHG_MESH)
 MESH_TEXTURES_MAX = 8      # BHG_MESH_TEXTURES_MAX: images a mesh material holds at most (BHG_MESH_MATERIAL)
 MAX_CROSSINGS = 4   # BHG_MAX_CROSSINGS: disk crossings a crossings trace stores per ray (BHG_DISK_CROSSINGS)
@@ -722,6 +726,30 @@ def load():
     L.bhg_shade_mesh_material_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32,
                                                  C.POINTER(Scene), C.c_void_p, C.POINTER(MeshMaterialStruct), C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bhg_mesh_instances_create.restype = C.c_int
+    L.bhg_mesh_instances_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]
+    L.bhg_mesh_instances_set.restype = C.c_int
+    L.bhg_mesh_instances_set.argtypes = [C.c_void_p, C.c_void_p]
+    L.bhg_mesh_instances_destroy.restype = None
+    L.bhg_mesh_instances_destroy.argtypes = [C.c_void_p]
+    L.bhg_mesh_instances_info.restype = C.c_int
+    L.bhg_mesh_instances_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), _dp]
+    L.bhg_mesh_instance_box_host.restype = C.c_int
+    L.bhg_mesh_instance_box_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bhg_trace_mesh_instances_device.restype = C.c_int
+    L.bhg_trace_mesh_instances_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_double, _dp, C.c_void_p, C.c_void_p,
+                                                  C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]
+    L.bhg_trace_mesh_instances.restype = C.c_int
+    L.bhg_trace_mesh_instances.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_double, C.c_void_p, C.c_int, C.c_void_p,
+                                           C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]
+    L.bhg_shade_mesh_instances_device.restype = C.c_int
+    L.bhg_shade_mesh_instances_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                  C.c_int32, C.POINTER(Scene), C.c_void_p, C.POINTER(MeshMaterialStruct), C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bhg_frame_set_mesh_instances.restype = C.c_int
+    L.bhg_frame_set_mesh_instances.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.bhg_frame_set_mesh.restype = C.c_int
     L.bhg_frame_set_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32, C.c_double,
                                      C.POINTER(MeshMaterialStruct)]
@@ -810,10 +838,13 @@ class Mesh:
         self.ctx = ctx
         self.n_vertices, self.n_triangles = V.shape[0], F.shape[0]
         self.has_normals = N is not None
+        self._instances = []
         ctx._meshes.append(self)
 
     def close(self):
         if getattr(self, "_h", None):
+            for inst in list(getattr(self, "_instances", ())):
+                inst.close()
             load().bhg_mesh_destroy(self._h)
             self._h = None
             if self in self.ctx._meshes:
@@ -830,6 +861,81 @@ class Mesh:
         nn, depth, box = C.c_int64(0), C.c_int32(0), (C.c_double * 6)()
         _check(load().bhg_mesh_info(self._h, C.byref(nn), C.byref(depth), box))
         return nn.value, depth.value, np.array(box[:])
+
+
+def _instance_transforms(transforms):
+    T = np.ascontiguousarray(transforms, dtype=np.float64)
+    if T.ndim == 3 and T.shape[1:] == (3, 4):
+        # [K, 3, 4] = (R | t) -> R row-major, then t
+        T = np.ascontiguousarray(np.concatenate([T[:, :, :3].reshape(-1, 9), T[:, :, 3]], axis=1))
+    if T.ndim != 2 or T.shape[1] != 12:
+        raise ValueError("transforms must have shape [K, 12] (R row-major, then t) or [K, 3, 4] (R | t)")
+    return T
+
+
+def rigid_transform(matrix):
+    """The rigid record nearest to a 4 x 4 (or 3 x 4) affine matrix -> [12] float64, R row-major then t.  R is the polar part of
+    the upper 3 x 3 block (U V^T of its SVD: the rotation nearest in the Frobenius norm, any scale dropped), t the last column.
+    Matrices kept in float32 are orthonormal only to about 1e-7, which bhg_mesh_instances_create refuses; this makes them exact to
+    rounding.  A block with a reflection (det <= 0) or a collapsed axis is refused."""
+    M = np.asarray(matrix, dtype=np.float64)
+    if M.shape not in ((4, 4), (3, 4)) or not np.all(np.isfinite(M)):
+        raise ValueError("matrix must be a finite 4 x 4 or 3 x 4 array")
+    A = M[:3, :3]
+    if not np.linalg.det(A) > 0.0:
+        raise ValueError("matrix must not mirror or collapse: det of the 3 x 3 block must be > 0")
+    U, _, Vt = np.linalg.svd(A)
+    return np.concatenate([(U @ Vt).reshape(9), M[:3, 3]])
+
+
+def mesh_instance_box_host(local_box, transform):
+    """bhg_mesh_instance_box_host: the world box (lo, hi) of a local box (lo, hi) under one rigid transform [12]; no GPU."""
+    lb = np.ascontiguousarray(local_box, dtype=np.float64).reshape(6)
+    T = np.asarray(transform, dtype=np.float64)
+    T = _instance_transforms(T.reshape((1,) + T.shape))
+    out = np.empty(6, np.float64)
+    _check(load().bhg_mesh_instance_box_host(_addr(lb), _addr(T), _addr(out)))
+    return out
+
+
+class MeshInstances:
+    """bhg_mesh_instances: K rigid placements of one Mesh.  transforms [K, 12] (R row-major, then t) or
+    [K, 3, 4] (R | t), x_world = R x_local + t.  set(transforms) moves them: K x 18 doubles go to the device, no tree is touched.
+    Closes with its mesh."""
+
+    def __init__(self, mesh: "Mesh", transforms):
+        T = _instance_transforms(transforms)
+        h = C.c_void_p()
+        _check(load().bhg_mesh_instances_create(mesh.ctx._h, mesh._h, T.shape[0], _addr(T), C.byref(h)))
+        self._h = h
+        self.mesh = mesh
+        self.n = T.shape[0]
+        mesh._instances.append(self)
+
+    def set(self, transforms):
+        T = _instance_transforms(transforms)
+        if T.shape[0] != self.n:
+            raise ValueError(f"set takes the {self.n} transforms the set was created with, not {T.shape[0]}")
+        _check(load().bhg_mesh_instances_set(self._h, _addr(T)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load().bhg_mesh_instances_destroy(self._h)
+            self._h = None
+            if self in self.mesh._instances:
+                self.mesh._instances.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """(n, box[6]): the number of instances and the union of their world boxes"""
+        n, box = C.c_int32(0), (C.c_double * 6)()
+        _check(load().bhg_mesh_instances_info(self._h, C.byref(n), box))
+        return n.value, np.array(box[:])
 
 
 def start_steps_match(a: "Params", b: "Params") -> bool:
@@ -1184,6 +1290,22 @@ class Frame:
         _check(load().bhg_frame_set_mesh(self._h, _addr(V), V.shape[0], _addr(F), F.shape[0], None if N is None else _addr(N),
                                          int(leaf_size), 0.0 if chord is None else float(chord), None if m is None else C.byref(m)))
 
+    def set_mesh_instances(self, transforms=None, inst_rgb=None):
+        """Rigid placements of the frame's mesh in every later render (bhg_frame_set_mesh_instances):
+        transforms [K, 12] (R row-major, then t) or [K, 3, 4] (R | t), inst_rgb [K, 3] float32 or None.  Calling it again with
+        other transforms moves the instances: the records go to the devices, nothing of the mesh is rebuilt or uploaded.
+        None (or no transforms): off -- the plain mesh render, bit for bit.  set_mesh() turns instances off as well."""
+        if transforms is None or len(transforms) == 0:
+            _check(load().bhg_frame_set_mesh_instances(self._h, 0, None, None))
+            return
+        T = _instance_transforms(transforms)
+        rgb = None
+        if inst_rgb is not None:
+            rgb = np.ascontiguousarray(inst_rgb, dtype=np.float32)
+            if rgb.shape != (T.shape[0], 3):
+                raise ValueError("inst_rgb must have shape [K, 3]")
+        _check(load().bhg_frame_set_mesh_instances(self._h, T.shape[0], _addr(T), None if rgb is None else _addr(rgb)))
+
     def render(self, params: "Params", out=None, to_host=True):
         """One frame: float32 [H, W, 4] (a new array, or `out`).  to_host=False: only enqueue; the image stays on the
         first device (device_image(), synchronize())."""
@@ -1427,6 +1549,40 @@ class Context:
                                             C.c_void_p(d_n_accepted or None), C.c_void_p(d_tri_id or None),
                                             C.c_void_p(d_bary or None), C.c_void_p(stream or None)))
 
+    def trace_mesh_instances(self, k0, x0, params: Params, instances: "MeshInstances", max_chord):
+        """bhg_trace_mesh_instances: trace_mesh over the rigid placements of an instance set ->
+        (end[N,6], flags[N], n_steps[N], n_accepted[N], tri_id[N] the triangle within the mesh or -1, inst_id[N] int32 the instance
+        or -1, bary[N,2] the plane coordinates in the instance's frame, NaN for a ray that hits nothing)."""
+        k0 = np.ascontiguousarray(k0, dtype=np.float64)
+        if k0.ndim != 2 or k0.shape[1] != 3:
+            raise ValueError("k0 must have shape [N, 3]")
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        n = k0.shape[0]
+        if x0.shape != (3,) and x0.shape != (n, 3):
+            raise ValueError("x0 must have shape [3] or [N, 3]")
+        end = np.empty((n, 6), np.float64)
+        flags = np.empty(n, np.uint8)
+        steps = np.empty(n, np.uint32)
+        acc = np.empty(n, np.uint32)
+        tri_id = np.full(n, -1, np.int32)
+        inst_id = np.full(n, -1, np.int32)
+        bary = np.full((n, 2), np.nan, np.float64)
+        _check(load().bhg_trace_mesh_instances(self._h, C.byref(params), None if instances is None else instances._h,
+                                               float(max_chord), _addr(x0), 1 if x0.ndim == 1 else 0, _addr(k0), n, _addr(end),
+                                               _addr(flags), _addr(steps), _addr(acc), _addr(tri_id), _addr(inst_id), _addr(bary)))
+        return end, flags, steps, acc, tri_id, inst_id, bary
+
+    def trace_mesh_instances_device(self, params: Params, instances: "MeshInstances", max_chord, n, d_k0, d_end, d_tri_id, d_inst_id,
+                                    d_bary, x0_shared=None, d_x0=0, d_flags=0, d_n_steps=0, d_n_accepted=0, stream=0):
+        """bhg_trace_mesh_instances_device: trace_mesh_device with an instance set in place of the mesh, plus d_inst_id [n] int32."""
+        xs = None if x0_shared is None else (C.c_double * 3)(*[float(v) for v in x0_shared])
+        _check(load().bhg_trace_mesh_instances_device(self._h, C.byref(params), None if instances is None else instances._h,
+                                                      float(max_chord), xs, C.c_void_p(d_x0 or None), C.c_void_p(d_k0 or None),
+                                                      int(n), C.c_void_p(d_end or None), C.c_void_p(d_flags or None),
+                                                      C.c_void_p(d_n_steps or None), C.c_void_p(d_n_accepted or None),
+                                                      C.c_void_p(d_tri_id or None), C.c_void_p(d_inst_id or None),
+                                                      C.c_void_p(d_bary or None), C.c_void_p(stream or None)))
+
     def shade_mesh_device(self, d_end, d_flags, d_tri_id, d_bary, n_pixels, samples, scene: "Scene", mesh: "Mesh", d_tri_rgb=0,
                           d_rgba=0, d_rgba_f32=0, d_scatter=0, stream=0):
         """bhg_shade_mesh_device: the shade of a mesh trace -- mesh rays Lambert-lit and shadowed by the mesh, every other ray
@@ -1436,6 +1592,21 @@ class Context:
                                             C.byref(scene), None if mesh is None else mesh._h, C.c_void_p(d_tri_rgb or None),
                                             C.c_void_p(d_rgba or None), C.c_void_p(d_rgba_f32 or None),
                                             C.c_void_p(d_scatter or None), C.c_void_p(stream or None)))
+
+    def shade_mesh_instances_device(self, d_end, d_flags, d_tri_id, d_inst_id, d_bary, n_pixels, samples, scene: "Scene",
+                                    instances: "MeshInstances", material=None, d_inst_rgb=0, d_rgba=0, d_rgba_f32=0, d_scatter=0,
+                                    stream=0):
+        """bhg_shade_mesh_instances_device: shade_mesh_material_device over an instance set -- mesh rays get
+        albedo * inst_rgb[inst] * (lamp_sum + emission).  material a MeshMaterialStruct of DEVICE addresses or None (white),
+        d_inst_rgb [K, 3] float32 or 0."""
+        _check(load().bhg_shade_mesh_instances_device(self._h, C.c_void_p(d_end or None), C.c_void_p(d_flags or None),
+                                                      C.c_void_p(d_tri_id or None), C.c_void_p(d_inst_id or None),
+                                                      C.c_void_p(d_bary or None), int(n_pixels), int(samples), C.byref(scene),
+                                                      None if instances is None else instances._h,
+                                                      None if material is None else C.byref(material),
+                                                      C.c_void_p(d_inst_rgb or None), C.c_void_p(d_rgba or None),
+                                                      C.c_void_p(d_rgba_f32 or None), C.c_void_p(d_scatter or None),
+                                                      C.c_void_p(stream or None)))
 
     def shade_mesh_material_device(self, d_end, d_flags, d_tri_id, d_bary, n_pixels, samples, scene: "Scene", mesh: "Mesh", material,
                                    d_rgba=0, d_rgba_f32=0, d_scatter=0, stream=0):

@@ -50,6 +50,12 @@ Known deviations from the reference, all deliberate:
     the largest `curved_space_emission` as the mesh's emission, smooth shading when every polygon is smooth
     (bhg_frame_set_mesh; the mesh is uploaded only when it changed).  On the host path or with a mark_* window: one warning,
     and the render as with 0.
+  * scene.curved_space_mesh_instances (default 0): with curved_space_meshes = 1 on the device path, traced
+    mesh objects that share ONE mesh datablock (or a single object), whose matrix_world is a rotation times one common per-axis
+    scale (to 1e-6) and that agree in `curved_space_texture` and `curved_space_emission`, are rigid instances of one mesh: the
+    frame gets the datablock once, in its own coordinates with the scale baked in, and one instance per object (translation minus
+    the hole's location).  A later render whose baked arrays and images are the ones held only moves the instances
+    (bhg_frame_set_mesh_instances: nothing is rebuilt or uploaded).  Any other scene takes the concatenated path above, silently.
 """
 import warnings
 import os
@@ -210,6 +216,61 @@ class RelativisticRenderEngine(bpy.types.RenderEngine):
 
     MESH_IMAGES_MAX = 8      # _ffi.MESH_TEXTURES_MAX: image slots of a mesh material
 
+    @staticmethod
+    def _evaluated_geometry(ob, depsgraph):
+        """(co [nv * 3] float32, triangles [nt * 3] int32) of the object's evaluated mesh, in its own coordinates."""
+        ev = ob.evaluated_get(depsgraph) if hasattr(ob, "evaluated_get") else ob
+        me = ev.to_mesh()
+        try:
+            me.calc_loop_triangles()
+            co = np.empty(len(me.vertices) * 3, dtype=np.float32)
+            me.vertices.foreach_get("co", co)
+            tri = np.empty(len(me.loop_triangles) * 3, dtype=np.int32)
+            me.loop_triangles.foreach_get("vertices", tri)
+            return co, tri
+        finally:
+            if hasattr(ev, "to_mesh_clear"):
+                ev.to_mesh_clear()
+
+    def _mesh_instance_plan(self, depsgraph, objects):
+        """(scale [3], records [K, 12]) when the traced mesh objects are rigid instances of one mesh (scene.curved_space_mesh_instances;
+        the module docstring has the rule), else None.  A record is the rigid part of matrix_world nearest to it
+        (_ffi.rigid_transform: Blender's matrices are float32) with the hole's location taken off the translation."""
+        from . import _ffi
+        if not objects or len(objects) > _ffi.MESH_INSTANCES_MAX:
+            return None
+        data = [getattr(ob, "data", None) for ob in objects]
+        if len(objects) > 1 and (data[0] is None or any(d is not data[0] for d in data)):
+            return None
+        looks = {(str(self._custom(ob, "curved_space_texture") or ""), float(self._custom(ob, "curved_space_emission") or 0.0))
+                 for ob in objects}
+        if len(looks) != 1:
+            return None
+        # linked duplicates may carry modifiers of their own: the EVALUATED meshes have to be one mesh too
+        first = self._evaluated_geometry(objects[0], depsgraph)
+        for ob in objects[1:]:
+            other = self._evaluated_geometry(ob, depsgraph)
+            if any(a.shape != b.shape or not np.array_equal(a, b) for a, b in zip(first, other)):
+                return None
+        scale, records = None, []
+        for ob in objects:
+            ev = ob.evaluated_get(depsgraph) if hasattr(ob, "evaluated_get") else ob
+            mw = np.array([[float(ev.matrix_world[i][k]) for k in range(4)] for i in range(4)], dtype=np.float64)
+            s = np.linalg.norm(mw[:3, :3], axis=0)
+            if not np.all(s > 0.0):
+                return None
+            R = mw[:3, :3] / s
+            if np.abs(R.T @ R - np.eye(3)).max() > 1e-6 or not np.linalg.det(R) > 0.0:
+                return None
+            if scale is None:
+                scale = s
+            elif np.abs(s - scale).max() > 1e-6 * scale.max():
+                return None
+            rigid = np.eye(4)
+            rigid[:3, :3], rigid[:3, 3] = R, mw[:3, 3] - self.bh_loc
+            records.append(_ffi.rigid_transform(rigid))
+        return scale, np.stack(records)
+
     def scene_mesh(self, depsgraph):
         """Every MESH object of the scene but the black-hole marker as ONE triangle mesh, BH-centred (scene.curved_space_meshes):
         dict(vertices [nv, 3] float64, triangles [nt, 3] int32, normals [nv, 3] or None, tri_uv [nt, 3, 2] float32 or None,
@@ -218,13 +279,17 @@ class RelativisticRenderEngine(bpy.types.RenderEngine):
         (.vertices, .loops), vertices[].co through matrix_world; UVs uv_layers.active.data[loop].uv per corner -- all read with
         foreach_get into numpy buffers.  tri_tex is the slot of the object's curved_space_texture image (-1: none; at most 8
         distinct images), emission the largest curved_space_emission; vertex normals are passed only when every polygon of
-        every object is smooth."""
+        every object is smooth.  With scene.curved_space_mesh_instances on and objects that are rigid instances of one mesh
+        (_mesh_instance_plan): that mesh once, in its own coordinates with the common scale baked in, and instances [K, 12], the
+        objects' placements; otherwise instances is None."""
         bh = getattr(depsgraph.scene, "blackhole_obj", None)
         V, F, N, UV, TEX, offsets, images = [], [], [], [], [], [], []
         emission, smooth, any_uv, nv, nt, dropped = 0.0, True, False, 0, 0, 0
-        for ob in depsgraph.scene.objects:
-            if ob.type != "MESH" or ob is bh:
-                continue
+        objects = [ob for ob in depsgraph.scene.objects if ob.type == "MESH" and ob is not bh]
+        plan = None
+        if float(getattr(depsgraph.scene, "curved_space_mesh_instances", 0) or 0) != 0.0:
+            plan = self._mesh_instance_plan(depsgraph, objects)
+        for ob in objects[:1] if plan is not None else objects:
             ev = ob.evaluated_get(depsgraph) if hasattr(ob, "evaluated_get") else ob
             me = ev.to_mesh()
             try:
@@ -238,7 +303,10 @@ class RelativisticRenderEngine(bpy.types.RenderEngine):
                 me.loop_triangles.foreach_get("vertices", tri)
                 mw = np.array([[float(ev.matrix_world[i][k]) for k in range(4)] for i in range(4)], dtype=np.float64)
                 co = co.reshape(n_v, 3).astype(np.float64)
-                V.append(co @ mw[:3, :3].T + mw[:3, 3] - self.bh_loc)
+                # into the world about the hole, or (instances place it) the datablock's own coordinates with the scale baked in
+                A = mw[:3, :3] if plan is None else np.diag(plan[0])
+                V.append(co @ A.T + mw[:3, 3] - self.bh_loc if plan is None else co @ A.T)
+                local_co = co
                 F.append(tri.reshape(n_t, 3) + nv)
                 flags = np.empty(len(me.polygons), dtype=bool)
                 me.polygons.foreach_get("use_smooth", flags)
@@ -246,7 +314,8 @@ class RelativisticRenderEngine(bpy.types.RenderEngine):
                 nrm = np.empty(n_v * 3, dtype=np.float32)
                 me.vertices.foreach_get("normal", nrm)
                 # (normals go with the inverse transpose; the kernel normalises them)
-                N.append(nrm.reshape(n_v, 3).astype(np.float64) @ np.linalg.inv(mw[:3, :3]))
+                local_nrm = nrm.reshape(n_v, 3).astype(np.float64)
+                N.append(local_nrm @ np.linalg.inv(A))
                 uv = np.zeros((n_t, 3, 2), dtype=np.float32)
                 slot = -1
                 layer = getattr(getattr(me, "uv_layers", None), "active", None)
@@ -286,7 +355,10 @@ class RelativisticRenderEngine(bpy.types.RenderEngine):
         return {"vertices": np.concatenate(V), "triangles": np.concatenate(F).astype(np.int32),
                 "normals": np.concatenate(N) if smooth else None,
                 "tri_uv": np.ascontiguousarray(np.concatenate(UV)) if any_uv else None, "tri_tex": np.concatenate(TEX),
-                "images": images if any_uv else [], "emission": emission, "offsets": offsets}
+                "images": images if any_uv else [], "emission": emission, "offsets": offsets,
+                "instances": None if plan is None else plan[1],
+                # (instanced: the datablock's arrays before the scale, and the scale -- what _set_device_mesh compares)
+                "local": None if plan is None else {"co": local_co, "normals": local_nrm, "scale": plan[0]}}
 
     def _set_device_mesh(self, fr, mesh):
         """The scene's mesh on the library-owned frame: set_mesh only when vertices, triangles, normals or the material differ
@@ -298,17 +370,37 @@ class RelativisticRenderEngine(bpy.types.RenderEngine):
             fr.mesh_held = None
             return
         ids = [self._image_identity(n) for n in mesh["images"]]
+        # An instanced mesh is its datablock's arrays times the objects' common scale.  The scale is read off float32 matrices and
+        # moves in its last digits from render to render, so the baked arrays do too: a held instanced mesh is the one wanted when
+        # the arrays BEFORE the scale are the same bits and the scale is the held one to the rule's own 1e-6 (the tolerance within
+        # which the objects' scales count as one).  Any change of the datablock itself, however small, is a new mesh.
+        local, held_local = mesh.get("local"), None if held is None else held.get("local")
+        rescaled = local is not None and held_local is not None and np.array_equal(local["co"], held_local["co"]) and \
+            np.array_equal(local["normals"], held_local["normals"]) and \
+            np.abs(local["scale"] - held_local["scale"]).max() <= 1e-6 * held_local["scale"].max()
+
+        def same_array(key, a, b):
+            return (rescaled and key in ("vertices", "normals")) or np.array_equal(a, b)
+
         same = held is not None and all(i is not None for i in ids) and ids == held["ids"] and \
             mesh["emission"] == held["emission"] and \
-            all((mesh[k] is None) == (held[k] is None) and (mesh[k] is None or np.array_equal(mesh[k], held[k]))
+            all((mesh[k] is None) == (held[k] is None) and (mesh[k] is None or same_array(k, mesh[k], held[k]))
                 for k in ("vertices", "triangles", "normals", "tri_uv", "tri_tex"))
-        if same:
-            return
-        from . import _ffi
-        material = _ffi.MeshMaterial(tri_uv=mesh["tri_uv"], tri_tex=mesh["tri_tex"] if mesh["tri_uv"] is not None else None,
-                                     textures=[self._image_pixels(n) for n in mesh["images"]], emission=mesh["emission"])
-        fr.set_mesh(mesh["vertices"], mesh["triangles"], vertex_normals=mesh["normals"], material=material)
-        fr.mesh_held = {**{k: mesh[k] for k in ("vertices", "triangles", "normals", "tri_uv", "tri_tex", "emission")}, "ids": ids}
+        if not same:
+            from . import _ffi
+            material = _ffi.MeshMaterial(tri_uv=mesh["tri_uv"], tri_tex=mesh["tri_tex"] if mesh["tri_uv"] is not None else None,
+                                         textures=[self._image_pixels(n) for n in mesh["images"]], emission=mesh["emission"])
+            fr.set_mesh(mesh["vertices"], mesh["triangles"], vertex_normals=mesh["normals"], material=material)
+            fr.mesh_held = {**{k: mesh[k] for k in ("vertices", "triangles", "normals", "tri_uv", "tri_tex", "emission")}, "ids": ids,
+                            "instances": None, "local": local}      # (set_mesh turns instances off)
+        # the placements: moved objects of a held mesh upload their records and nothing else
+        inst, held_inst = mesh.get("instances"), fr.mesh_held.get("instances")
+        if inst is None:
+            if held_inst is not None:
+                fr.set_mesh_instances(None)
+        elif held_inst is None or not np.array_equal(inst, held_inst):
+            fr.set_mesh_instances(inst)
+        fr.mesh_held["instances"] = inst
 
     @staticmethod
     def _custom(ob, key):
@@ -616,6 +708,7 @@ class CUSTOM_RENDER_PT_blackhole(RenderButtonsPanel, Panel):
              ("mark_x_min", "mark_x_min"), ("mark_x_max", "mark_x_max"), ("mark_y_min", "mark_y_min"),
              ("mark_y_max", "mark_y_max"), ("curved_space_objects", "Objects in curved space (0/1)"),
              ("curved_space_meshes", "Mesh objects as triangles (0/1)"),
+             ("curved_space_mesh_instances", "Linked duplicates as instances (0/1)"),
              ("device_shading", "Shade on the GPU (0/1)"), ("render_devices", "GPUs to render on"))
 
     def draw(self, context):
@@ -645,6 +738,7 @@ PROPS = [
 EXTRA_PROPS = [
     ("curved_space_objects", bpy.props.FloatProperty(name="curved_space_objects", default=0)),
     ("curved_space_meshes", bpy.props.FloatProperty(name="curved_space_meshes", default=0)),
+    ("curved_space_mesh_instances", bpy.props.FloatProperty(name="curved_space_mesh_instances", default=0)),
     ("device_shading", bpy.props.FloatProperty(name="device_shading", default=0)),
     ("render_devices", bpy.props.FloatProperty(name="render_devices", default=1)),
 ]

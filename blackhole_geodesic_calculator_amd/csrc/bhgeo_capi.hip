@@ -19,6 +19,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/bhgeo.h"
@@ -1099,9 +1100,66 @@ struct bhg_mesh {
     int32_t depth = 0;
     double box[6] = {0, 0, 0, 0, 0, 0};
     double d_min = 0.0, d_max = 0.0;
+    uint64_t serial = 0;      // its entry in live_meshes, which an instance set checks before it trusts its pointer
+};
+
+// K rigid placements of one mesh: the device records, and what the host works out from them in O(K)
+struct bhg_mesh_instances {
+    bhg_context *ctx = nullptr;
+    int device = 0;               // ctx's (the set may be destroyed after its context)
+    const bhg_mesh *mesh = nullptr;
+    uint64_t mesh_serial = 0;
+    int32_t n = 0;
+    double *d_rec = nullptr;      // [n][BHG_MESH_INSTANCE_DOUBLES_]
+    double box[6] = {0, 0, 0, 0, 0, 0};     // the union of the world boxes
+    double d_min = 0.0, d_max = 0.0;
+    // The records are written by _set on the context's stream and read by traces and shades on whatever stream their caller
+    // names: the set orders the two itself, so that no caller has to.
+    //   * h_rec: two page-locked host copies, used in turn; a copy's event (ev_copy) is waited for on the host before its buffer
+    //     is filled again, so a queued copy always reads what its _set wrote;
+    //   * a reader's stream waits for the last copy (ev_copy[last]) before it launches, and leaves ev_read behind it; a reader on
+    //     another stream than the one before waits for that one's ev_read first, so the last ev_read stands for every reader;
+    //   * _set makes the context's stream wait for ev_read before the copy: no kernel still reads what it overwrites.
+    // (mutable: a reader holds the set const, and reads)
+    double *h_rec[2] = {nullptr, nullptr};
+    hipEvent_t ev_copy[2] = {nullptr, nullptr};
+    mutable hipEvent_t ev_read = nullptr;
+    mutable hipStream_t read_stream = nullptr;
+    mutable bool was_read = false;
+    int last = -1;                // the host copy of the latest _set (-1: the creating upload, synchronous)
 };
 
 namespace {
+
+// the meshes that exist, by address and serial number (an address may come back after a destroy; a serial never does)
+std::mutex live_meshes_lock;
+std::unordered_map<const bhg_mesh *, uint64_t> live_meshes;
+uint64_t live_meshes_next = 1;
+
+// BHGEO_MESH_CULL=0: every step of every ray samples its sub-chords, and no instance's world box is looked at (an A/B aid: the
+// results are the same bits)
+bool mesh_culls_on()
+{
+    const char *cull = std::getenv("BHGEO_MESH_CULL");
+    return !(cull && cull[0] == '0' && cull[1] == 0);
+}
+
+// A kernel on stream s is about to read the set's records / has been launched (bhg_mesh_instances has the protocol)
+hipError_t instances_before_read(const bhg_mesh_instances *in, hipStream_t s)
+{
+    if (in->last >= 0)
+        if (hipError_t e = hipStreamWaitEvent(s, in->ev_copy[in->last], 0)) return e;
+    if (in->was_read && in->read_stream != s)
+        if (hipError_t e = hipStreamWaitEvent(s, in->ev_read, 0)) return e;
+    return hipSuccess;
+}
+
+hipError_t instances_after_read(const bhg_mesh_instances *in, hipStream_t s)
+{
+    in->read_stream = s;
+    in->was_read = true;
+    return hipEventRecord(in->ev_read, s);
+}
 
 int validate_spheres(const bhg_params *p, const double *spheres, int32_t n_spheres)
 {
@@ -1271,12 +1329,27 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const TraceCall &tc)
             g.d_min = tc.mesh->d_min;
             g.d_max = tc.mesh->d_max;
             g.max_chord = tc.max_chord;
-            // BHGEO_MESH_CULL=0: every step of every ray samples its sub-chords (an A/B aid: the results are the same bits)
-            const char *cull = std::getenv("BHGEO_MESH_CULL");
-            g.cull = !(cull && cull[0] == '0' && cull[1] == 0);
+            g.cull = mesh_culls_on();
             g.tri_id = tc.tri_id;
             g.bary = tc.bary;
-            HIP_TRY(bhg::launch_trace_mesh(a, g, rhs_id, s));
+            if (tc.instances) {
+                // the placements: the whole-step cull against their union, the records beside
+                const bhg_mesh_instances *in = tc.instances;
+                std::memcpy(g.box, in->box, sizeof(g.box));
+                g.d_min = in->d_min;
+                g.d_max = in->d_max;
+                bhg::MeshInstanceArgs ia;
+                std::memset(&ia, 0, sizeof(ia));
+                ia.rec = in->d_rec;
+                ia.n = in->n;
+                ia.inst_id = tc.inst_id;
+                ia.cull = g.cull;       // (BHGEO_MESH_CULL=0 takes the instances' world boxes out as well)
+                HIP_TRY(instances_before_read(in, s));
+                HIP_TRY(bhg::launch_trace_mesh_instances(a, g, ia, rhs_id, s));
+                HIP_TRY(instances_after_read(in, s));
+            } else {
+                HIP_TRY(bhg::launch_trace_mesh(a, g, rhs_id, s));
+            }
         } else if (tc.kind == TraceKind::TRAVEL_TIME) {
             HIP_TRY(bhg::launch_travel_time(a, rhs_id, tc.t_end, tc.t_cross, s));
         } else {
@@ -1732,6 +1805,11 @@ int bhg_mesh_create(bhg_context *c, const double *vertices, size_t n_vertices, c
     v.tri_slot = (const int32_t *)(m->d + o_slot);
     v.n_nodes = (int32_t)nn;
     v.n_tris = (int32_t)nt;
+    {
+        std::lock_guard<std::mutex> lock(live_meshes_lock);
+        m->serial = live_meshes_next++;
+        live_meshes[m] = m->serial;
+    }
     *out = m;
     return BHG_OK;
 }
@@ -1739,6 +1817,10 @@ int bhg_mesh_create(bhg_context *c, const double *vertices, size_t n_vertices, c
 void bhg_mesh_destroy(bhg_mesh *m)
 {
     if (!m) return;
+    {
+        std::lock_guard<std::mutex> lock(live_meshes_lock);
+        live_meshes.erase(m);
+    }
     {
         DeviceGuard g(m->device);
         if (m->d) (void)hipFree(m->d);
@@ -1790,6 +1872,254 @@ int bhg_trace_mesh(bhg_context *c, const bhg_params *p, const bhg_mesh *mesh, do
         return bhg_trace_mesh_device(c, p, mesh, max_chord, x0_is_shared ? x0 : nullptr, st.at<double>(x), st.at<double>(k), n,
                                      st.at<double>(e), st.at<uint8_t>(fl), st.at<uint32_t>(ns), st.at<uint32_t>(na),
                                      st.at<int32_t>(tr), st.at<double>(ba), c->stream);
+    });
+}
+
+// --- mesh instances -----------------------------------------------------------------------------------
+
+}  // extern "C"
+
+namespace {
+
+// the world box of a local box under x -> R x + t: centre R c + t, half extents |R| h, widened outward by the builder's ulps of
+// the largest magnitude involved -- the box, the translation and the local box, whose roundings in p' = R^T (p - t) it has to cover
+void instance_world_box(const double lb[6], const double T[12], double wb[6])
+{
+    const double c[3] = {0.5 * (lb[0] + lb[3]), 0.5 * (lb[1] + lb[4]), 0.5 * (lb[2] + lb[5])};
+    const double h[3] = {0.5 * (lb[3] - lb[0]), 0.5 * (lb[4] - lb[1]), 0.5 * (lb[5] - lb[2])};
+    double mag = 0.0;
+    for (int q = 0; q < 3; q++) {
+        const double *R = T + 3 * q;
+        const double wc = R[0] * c[0] + R[1] * c[1] + R[2] * c[2] + T[9 + q];
+        const double wh = std::fabs(R[0]) * h[0] + std::fabs(R[1]) * h[1] + std::fabs(R[2]) * h[2];
+        wb[q] = wc - wh;
+        wb[3 + q] = wc + wh;
+        mag = std::max(mag, std::fabs(wc) + wh);
+        mag = std::max(mag, std::fabs(T[9 + q]));
+        mag = std::max(mag, std::max(std::fabs(lb[q]), std::fabs(lb[3 + q])));
+    }
+    const double w = bhg::BVH_BOX_ULPS * 2.220446049250313e-16 * std::max(mag, 2.2250738585072014e-308);
+    for (int q = 0; q < 3; q++) {
+        wb[q] -= w;
+        wb[3 + q] += w;
+    }
+}
+
+}  // namespace
+
+namespace bhg {
+// n rigid transforms, or the reason they are refused (bhgeo_frame.hip checks the frame's with it)
+int mesh_instance_transforms_check(int32_t n, const double *T)
+{
+    if (n < 1 || n > BHG_MESH_INSTANCES_MAX) return fail(BHG_E_INVALID, "mesh instances: n must be in [1, BHG_MESH_INSTANCES_MAX]");
+    if (!T) return fail(BHG_E_INVALID, "mesh instances: transforms is NULL");
+    for (int32_t j = 0; j < n; j++) {
+        const double *R = T + (size_t)j * 12;
+        for (int q = 0; q < 12; q++)
+            if (!std::isfinite(R[q])) return fail(BHG_E_INVALID, "mesh instances: every entry of transforms must be finite");
+        for (int a = 0; a < 3; a++)
+            for (int b = 0; b < 3; b++) {
+                const double g = R[a] * R[b] + R[3 + a] * R[3 + b] + R[6 + a] * R[6 + b];
+                if (!(std::fabs(g - (a == b ? 1.0 : 0.0)) <= 1e-9))
+                    return fail(BHG_E_INVALID, "mesh instances: transforms must be rigid, R^T R within 1e-9 of the identity");
+            }
+        const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+        if (!(det > 0.0)) return fail(BHG_E_INVALID, "mesh instances: transforms must be rotations, det R > 0");
+    }
+    return BHG_OK;
+}
+}  // namespace bhg
+
+namespace {
+
+using bhg::mesh_instance_transforms_check;
+
+bool mesh_is_live(const bhg_mesh *m, uint64_t serial)
+{
+    std::lock_guard<std::mutex> lock(live_meshes_lock);
+    auto it = live_meshes.find(m);
+    return it != live_meshes.end() && it->second == serial;
+}
+
+// the records of n checked transforms against the mesh's root box, and the set's union box and range of distances
+void instance_records(const bhg_mesh *mesh, int32_t n, const double *T, double *rec, double box[6], double &d_min, double &d_max)
+{
+    double t_max = 0.0, near2 = INFINITY;
+    for (int32_t j = 0; j < n; j++) {
+        double *r = rec + (size_t)j * bhg::BHG_MESH_INSTANCE_DOUBLES_;
+        std::memcpy(r, T + (size_t)j * 12, 12 * sizeof(double));
+        instance_world_box(mesh->box, r, r + 12);
+        double d2 = 0.0;
+        for (int q = 0; q < 3; q++) {
+            box[q] = j ? std::min(box[q], r[12 + q]) : r[12 + q];
+            box[3 + q] = j ? std::max(box[3 + q], r[15 + q]) : r[15 + q];
+            const double gap = std::max(std::max(r[12 + q], -r[15 + q]), 0.0);
+            d2 += gap * gap;
+        }
+        near2 = std::min(near2, d2);
+        t_max = std::max(t_max, std::sqrt(r[9] * r[9] + r[10] * r[10] + r[11] * r[11]));
+    }
+    // a point of instance j lies no farther from the origin than |t_j| + the mesh's farthest vertex, and inside its world box
+    d_min = std::sqrt(near2) * (1.0 - 1e-14);
+    d_max = (t_max + mesh->d_max) * (1.0 + 1e-14);
+}
+
+int instances_trace_check(const bhg_params *p, const bhg_mesh_instances *inst, double max_chord, const int32_t *tri_id,
+                          const int32_t *inst_id, const double *bary)
+{
+    BHG_TRY(validate(p));
+    if (p->method != BHG_METHOD_DP54) return fail(BHG_E_INVALID, "the mesh trace is DP5(4) only: method must be BHG_METHOD_DP54");
+    if (p->time_like) return fail(BHG_E_INVALID, "the mesh trace covers null rays only: time_like must be 0");
+    if (!inst) return fail(BHG_E_INVALID, "mesh instances: inst is NULL");
+    if (!std::isfinite(max_chord) || !(max_chord > 0.0)) return fail(BHG_E_INVALID, "max_chord must be finite and > 0");
+    if (!tri_id || !bary) return fail(BHG_E_INVALID, "tri_id / bary is NULL");
+    if (!inst_id) return fail(BHG_E_INVALID, "inst_id is NULL");
+    return BHG_OK;
+}
+
+int instances_usable(const bhg_context *c, const bhg_mesh_instances *inst)
+{
+    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
+    if (inst->ctx != c) return fail(BHG_E_INVALID, "mesh instances: the instance set belongs to another context");
+    if (!mesh_is_live(inst->mesh, inst->mesh_serial)) return fail(BHG_E_INVALID, "mesh instances: the set's mesh has been destroyed");
+    return BHG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bhg_mesh_instance_box_host(const double local_box[6], const double transform[12], double world_box[6])
+{
+    if (!local_box || !world_box) return fail(BHG_E_INVALID, "mesh instances: local_box / world_box is NULL");
+    for (int q = 0; q < 6; q++)
+        if (!std::isfinite(local_box[q])) return fail(BHG_E_INVALID, "mesh instances: local_box must be finite");
+    BHG_TRY(mesh_instance_transforms_check(1, transform));
+    instance_world_box(local_box, transform, world_box);
+    return BHG_OK;
+}
+
+int bhg_mesh_instances_create(bhg_context *c, const bhg_mesh *mesh, int32_t n, const double *transforms, bhg_mesh_instances **out)
+{
+    if (!out) return fail(BHG_E_INVALID, "out is NULL");
+    *out = nullptr;
+    BHG_TRY(mesh_instance_transforms_check(n, transforms));
+    if (!mesh) return fail(BHG_E_INVALID, "mesh is NULL");
+    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
+    if (mesh->device != c->device) return fail(BHG_E_INVALID, "the mesh lives on another device than the context");
+    ENTER_DEVICE(c->device);
+    bhg_mesh_instances *in = new (std::nothrow) bhg_mesh_instances;
+    if (!in) return fail(BHG_E_NOMEM, "out of host memory");
+    in->ctx = c;
+    in->device = c->device;
+    in->mesh = mesh;
+    in->mesh_serial = mesh->serial;
+    in->n = n;
+    const size_t bytes = (size_t)n * bhg::BHG_MESH_INSTANCE_DOUBLES_ * sizeof(double);
+    hipError_t e = hipMalloc((void **)&in->d_rec, bytes);
+    for (int k = 0; k < 2 && e == hipSuccess; k++) {
+        e = hipHostMalloc((void **)&in->h_rec[k], bytes, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&in->ev_copy[k], hipEventDisableTiming);
+    }
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&in->ev_read, hipEventDisableTiming);
+    if (e == hipSuccess) {
+        instance_records(mesh, n, transforms, in->h_rec[0], in->box, in->d_min, in->d_max);
+        e = hipMemcpy(in->d_rec, in->h_rec[0], bytes, hipMemcpyHostToDevice);     // (done when the call returns)
+    }
+    if (e != hipSuccess) {
+        bhg_mesh_instances_destroy(in);
+        return fail_hip(e, "bhg_mesh_instances_create: device records");
+    }
+    *out = in;
+    return BHG_OK;
+}
+
+int bhg_mesh_instances_set(bhg_mesh_instances *in, const double *transforms)
+{
+    if (!in) return fail(BHG_E_INVALID, "mesh instances: inst is NULL");
+    BHG_TRY(mesh_instance_transforms_check(in->n, transforms));
+    BHG_TRY(instances_usable(in->ctx, in));
+    ENTER_DEVICE(in->ctx->device);
+    const int k = in->last < 0 ? 1 : in->last ^ 1;
+    const size_t bytes = (size_t)in->n * bhg::BHG_MESH_INSTANCE_DOUBLES_ * sizeof(double);
+    HIP_TRY(hipEventSynchronize(in->ev_copy[k]));     // (the copy that read this host buffer last, two _set calls ago: done)
+    double box[6], d_min, d_max;
+    instance_records(in->mesh, in->n, transforms, in->h_rec[k], box, d_min, d_max);
+    // behind every kernel that reads the records now, whatever its stream; the readers to come wait for ev_copy[k]
+    hipStream_t s = in->ctx->stream;
+    if (in->was_read && in->read_stream != s) HIP_TRY(hipStreamWaitEvent(s, in->ev_read, 0));
+    HIP_TRY(hipMemcpyAsync(in->d_rec, in->h_rec[k], bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(in->ev_copy[k], s));
+    in->last = k;
+    std::memcpy(in->box, box, sizeof(box));
+    in->d_min = d_min;
+    in->d_max = d_max;
+    return BHG_OK;
+}
+
+void bhg_mesh_instances_destroy(bhg_mesh_instances *in)
+{
+    if (!in) return;
+    {
+        DeviceGuard g(in->device);
+        // (what is still queued -- a copy, a kernel that reads the records -- runs out first)
+        for (int k = 0; k < 2; k++) {
+            if (in->ev_copy[k]) {
+                (void)hipEventSynchronize(in->ev_copy[k]);
+                (void)hipEventDestroy(in->ev_copy[k]);
+            }
+            if (in->h_rec[k]) (void)hipHostFree(in->h_rec[k]);
+        }
+        if (in->ev_read) {
+            (void)hipEventSynchronize(in->ev_read);
+            (void)hipEventDestroy(in->ev_read);
+        }
+        if (in->d_rec) (void)hipFree(in->d_rec);
+    }
+    delete in;
+}
+
+int bhg_mesh_instances_info(const bhg_mesh_instances *in, int32_t *n, double box[6])
+{
+    if (!in) return fail(BHG_E_INVALID, "mesh instances: inst is NULL");
+    if (n) *n = in->n;
+    if (box) std::memcpy(box, in->box, sizeof(in->box));
+    return BHG_OK;
+}
+
+int bhg_trace_mesh_instances_device(bhg_context *c, const bhg_params *p, const bhg_mesh_instances *inst, double max_chord,
+                                    const double *x0_shared, const double *d_x0, const double *d_k0, size_t n, double *d_end,
+                                    uint8_t *d_flags, uint32_t *d_n_steps, uint32_t *d_n_accepted, int32_t *d_tri_id,
+                                    int32_t *d_inst_id, double *d_bary, void *stream)
+{
+    BHG_TRY(instances_trace_check(p, inst, max_chord, d_tri_id, d_inst_id, d_bary));
+    BHG_TRY(instances_usable(c, inst));
+    if (n && !d_end) return fail(BHG_E_INVALID, "end is NULL");
+    return trace_device_impl(c, p, {.kind = TraceKind::MESH, .x0_shared = x0_shared, .d_x0 = d_x0, .d_k0 = d_k0, .n = n, .d_end = d_end,
+                                    .d_flags = d_flags, .d_n_steps = d_n_steps, .d_n_accepted = d_n_accepted, .stream = stream,
+                                    .stride = n, .mesh = inst->mesh, .max_chord = max_chord, .tri_id = d_tri_id, .bary = d_bary,
+                                    .instances = inst, .inst_id = d_inst_id});
+}
+
+int bhg_trace_mesh_instances(bhg_context *c, const bhg_params *p, const bhg_mesh_instances *inst, double max_chord, const double *x0,
+                             int x0_is_shared, const double *k0, size_t n, double *end, uint8_t *flags, uint32_t *n_steps,
+                             uint32_t *n_accepted, int32_t *tri_id, int32_t *inst_id, double *bary)
+{
+    BHG_TRY(instances_trace_check(p, inst, max_chord, tri_id, inst_id, bary));
+    BHG_TRY(instances_usable(c, inst));
+    if (n == 0) return BHG_OK;
+    if (!x0 || !k0 || !end) return fail(BHG_E_INVALID, "x0 / k0 / end is NULL");
+    if (n > 0xFFFFFFFFull) return fail(BHG_E_INVALID, "n must be < 2^32 per call");
+    ENTER_DEVICE(c->device);
+    const size_t b3 = n * 3 * sizeof(double), b6 = 2 * b3, bu = n * sizeof(uint32_t);
+    Staged st(c, true);
+    const size_t k = st.in(k0, b3), x = st.in(x0_is_shared ? nullptr : x0, b3), e = st.out(end, b6), tr = st.out(tri_id, bu),
+                 ii = st.out(inst_id, bu), ba = st.inout(bary, n * 2 * sizeof(double)), fl = st.out(flags, n),
+                 ns = st.out(n_steps, bu), na = st.out(n_accepted, bu);
+    return st.run([&] {
+        return bhg_trace_mesh_instances_device(c, p, inst, max_chord, x0_is_shared ? x0 : nullptr, st.at<double>(x), st.at<double>(k),
+                                               n, st.at<double>(e), st.at<uint8_t>(fl), st.at<uint32_t>(ns), st.at<uint32_t>(na),
+                                               st.at<int32_t>(tr), st.at<int32_t>(ii), st.at<double>(ba), c->stream);
     });
 }
 
@@ -2379,12 +2709,23 @@ struct MeshShadeCall {
     const float *tri_rgb = nullptr;           // the plain call's colours
     bool material = false;
     const bhg_mesh_material *mat = nullptr;   // the material call's; NULL for the plain call
+    // the instanced call (mesh stays NULL: the set's mesh is taken once the set has been checked; mat may be NULL: white)
+    const bhg_mesh_instances *instances = nullptr;
+    const int32_t *inst_id = nullptr;
+    const float *inst_rgb = nullptr;
 };
 
-int shade_mesh(bhg_context *c, const MeshShadeCall &m)
+int shade_mesh(bhg_context *c, const MeshShadeCall &call)
 {
+    MeshShadeCall m = call;
     const ShadeCall &s = m.s;
     BHG_TRY(scene_check(s.sc, s.samples, true));
+    if (m.instances) {
+        // (the set's mesh pointer is only trusted once the set is known to be this context's and its mesh alive)
+        BHG_TRY(instances_usable(c, m.instances));
+        m.mesh = m.instances->mesh;
+        m.material = m.mat != nullptr;
+    }
     if (!m.mesh) return fail(BHG_E_INVALID, "mesh is NULL");
     if (m.material) {
         BHG_TRY(bhg::mesh_material_check(m.mat, (size_t)m.mesh->view.n_tris, false));
@@ -2394,6 +2735,7 @@ int shade_mesh(bhg_context *c, const MeshShadeCall &m)
     if (s.n_pixels == 0) return BHG_OK;
     if ((!s.rgba && !s.rgba_f32) || !s.end || !s.flags || !s.sc->d_sky || !m.tri_id || !m.bary)
         return fail(BHG_E_INVALID, "NULL device pointer");
+    if (m.instances && !m.inst_id) return fail(BHG_E_INVALID, "inst_id is NULL");
     ENTER_DEVICE(c->device);
     bhg::ShadeArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -2405,22 +2747,32 @@ int shade_mesh(bhg_context *c, const MeshShadeCall &m)
     a.n_pixels = s.n_pixels;
     a.samples = s.samples;
     fill_scene_args(a, s.sc);
-    if (!m.material) {
+    if (!m.material && !m.instances) {
         HIP_TRY(bhg::launch_shade_mesh(a, m.mesh->view, m.tri_id, m.bary, m.tri_rgb, (hipStream_t)s.stream));
         return BHG_OK;
     }
     bhg::MeshMaterialArgs ma;
-    std::memset(&ma, 0, sizeof(ma));
-    ma.tri_rgb = m.mat->tri_rgb;
-    ma.tri_uv = m.mat->tri_uv;
-    ma.tri_tex = m.mat->tri_tex;
-    for (int j = 0; j < m.mat->n_tex; j++) {
-        ma.tex[j] = m.mat->tex[j];
-        ma.tex_w[j] = m.mat->tex_w[j];
-        ma.tex_h[j] = m.mat->tex_h[j];
+    std::memset(&ma, 0, sizeof(ma));     // (the instanced call without a material: white, no emission)
+    if (m.mat) {
+        ma.tri_rgb = m.mat->tri_rgb;
+        ma.tri_uv = m.mat->tri_uv;
+        ma.tri_tex = m.mat->tri_tex;
+        for (int j = 0; j < m.mat->n_tex; j++) {
+            ma.tex[j] = m.mat->tex[j];
+            ma.tex_w[j] = m.mat->tex_w[j];
+            ma.tex_h[j] = m.mat->tex_h[j];
+        }
+        ma.n_tex = m.mat->n_tex;
+        ma.emission = m.mat->emission;
     }
-    ma.n_tex = m.mat->n_tex;
-    ma.emission = m.mat->emission;
+    if (m.instances) {
+        const hipStream_t st = (hipStream_t)s.stream;
+        HIP_TRY(instances_before_read(m.instances, st));
+        HIP_TRY(bhg::launch_shade_mesh_instances(a, m.mesh->view, m.tri_id, m.bary, ma, m.instances->d_rec, m.instances->n, mesh_culls_on(),
+                                                 m.inst_id, m.inst_rgb, st));
+        HIP_TRY(instances_after_read(m.instances, st));
+        return BHG_OK;
+    }
     HIP_TRY(bhg::launch_shade_mesh_material(a, m.mesh->view, m.tri_id, m.bary, ma, (hipStream_t)s.stream));
     return BHG_OK;
 }
@@ -2500,6 +2852,19 @@ int bhg_shade_mesh_material_device(bhg_context *c, const double *d_end, const ui
     return shade_mesh(c, {.s = {.end = d_end, .flags = d_flags, .n_pixels = n_pixels, .samples = samples, .sc = sc, .rgba = d_rgba,
                                 .rgba_f32 = d_rgba_f32, .scatter = d_scatter, .stream = stream},
                           .tri_id = d_tri_id, .bary = d_bary, .mesh = mesh, .material = true, .mat = mat});
+}
+
+// ... over an instance set: mat and d_inst_rgb are optional
+int bhg_shade_mesh_instances_device(bhg_context *c, const double *d_end, const uint8_t *d_flags, const int32_t *d_tri_id,
+                                    const int32_t *d_inst_id, const double *d_bary, size_t n_pixels, int32_t samples,
+                                    const bhg_scene *sc, const bhg_mesh_instances *inst, const bhg_mesh_material *mat,
+                                    const float *d_inst_rgb, double *d_rgba, float *d_rgba_f32, const int64_t *d_scatter, void *stream)
+{
+    if (!inst) return fail(BHG_E_INVALID, "mesh instances: inst is NULL");
+    return shade_mesh(c, {.s = {.end = d_end, .flags = d_flags, .n_pixels = n_pixels, .samples = samples, .sc = sc, .rgba = d_rgba,
+                                .rgba_f32 = d_rgba_f32, .scatter = d_scatter, .stream = stream},
+                          .tri_id = d_tri_id, .bary = d_bary, .mat = mat, .instances = inst, .inst_id = d_inst_id,
+                          .inst_rgb = d_inst_rgb});
 }
 
 int bhg_shade_scene_f32_device(bhg_context *c, const double *d_end, const uint8_t *d_flags, const int8_t *d_object_id,

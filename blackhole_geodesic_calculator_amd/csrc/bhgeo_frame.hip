@@ -51,6 +51,8 @@ int motion_check(const bhg_object_motion *mo, int32_t n_spheres);
 int motion_params(const bhg_params *p, const bhg_object_motion *mo, const double *spheres, int32_t n_spheres, MotionParams *out);
 // ... and of a mesh material (host_arrays: tri_uv / tri_tex are host arrays and are scanned)
 int mesh_material_check(const bhg_mesh_material *m, size_t nt, bool host_arrays);
+// ... and of the transforms of mesh instances
+int mesh_instance_transforms_check(int32_t n, const double *T);
 }
 
 namespace {
@@ -200,6 +202,11 @@ struct Shard {
     bhg_mesh *mesh = nullptr;
     DevBuf m_rgb, m_uv, m_slot, m_img[BHG_MESH_TEXTURES_MAX], tri, bary;
     bool mesh_ready = false;        // mesh and the material buffers hold the frame's current mesh
+    // the mesh's instances (bhg_frame_set_mesh_instances): this device's set over mesh, the colours, the trace's third record
+    bhg_mesh_instances *inst = nullptr;
+    int32_t inst_n = 0;
+    DevBuf inst_rgb, inst_id;
+    bool inst_ready = false;        // inst holds the frame's current transforms, inst_rgb its colours
     hipEvent_t done = nullptr;
     bool rays_ready = false;
     bool start_ready = false;       // start_h holds the steps of the rays in k0, traced from start_origin with start_prm
@@ -255,6 +262,9 @@ struct bhg_frame {
     };
     bool meshed = false;            // bhg_frame_set_mesh; false: no mesh, the plain render
     Mesh mesh;
+    // bhg_frame_set_mesh_instances: host copies (empty: the mesh where its vertices put it)
+    std::vector<double> inst;       // [n][12]
+    std::vector<float> inst_rgb;    // [n][3], or empty
     // root (device of shard 0)
     DevBuf recv, perm, image;       // [n_dev * pmax][4] float, [H W] int64, [H W][4] float
     size_t pmax = 0;
@@ -387,8 +397,19 @@ int upload_shard_textures(bhg_frame *f, Shard &s)
     return BHG_OK;
 }
 
+void release_shard_instances(Shard &s)
+{
+    if (s.inst) bhg_mesh_instances_destroy(s.inst);
+    s.inst = nullptr;
+    s.inst_n = 0;
+    s.inst_rgb.release();
+    s.inst_id.release();
+    s.inst_ready = false;
+}
+
 void release_shard_mesh(Shard &s)
 {
+    release_shard_instances(s);     // (a set does not outlive its mesh)
     if (s.mesh) bhg_mesh_destroy(s.mesh);
     s.mesh = nullptr;
     for (DevBuf *b : {&s.m_rgb, &s.m_uv, &s.m_slot, &s.tri, &s.bary}) b->release();
@@ -418,6 +439,31 @@ int upload_shard_mesh(bhg_frame *f, Shard &s)
     for (int j = 0; j < m.n_tex; j++) BHG_TRY(up(s.m_img[j], m.img[j].data(), m.img[j].size() * sizeof(float)));
     HIP_TRY(hipStreamSynchronize(s.stream));
     s.mesh_ready = true;
+    return BHG_OK;
+}
+
+// the frame's instances on this shard's device, over the shard's mesh: a set of the same size is moved (the records go up,
+// nothing else), another size makes a new set
+int upload_shard_instances(bhg_frame *f, Shard &s)
+{
+    const int32_t n = (int32_t)(f->inst.size() / 12);
+    HIP_TRY(hipSetDevice(s.device));
+    if (s.inst && s.inst_n == n) {
+        BHG_TRY(bhg_mesh_instances_set(s.inst, f->inst.data()));
+    } else {
+        release_shard_instances(s);
+        BHG_TRY(bhg_mesh_instances_create(s.ctx, s.mesh, n, f->inst.data(), &s.inst));
+        s.inst_n = n;
+    }
+    HIP_TRY(hipSetDevice(s.device));
+    if (f->inst_rgb.empty()) {
+        s.inst_rgb.release();
+    } else {
+        BHG_TRY(s.inst_rgb.ensure(s.device, f->inst_rgb.size() * sizeof(float)));
+        HIP_TRY(hipMemcpyAsync(s.inst_rgb.p, f->inst_rgb.data(), f->inst_rgb.size() * sizeof(float), hipMemcpyHostToDevice, s.stream));
+        HIP_TRY(hipStreamSynchronize(s.stream));
+    }
+    s.inst_ready = true;
     return BHG_OK;
 }
 
@@ -839,6 +885,8 @@ try {
         // off: the plain render again, the mesh freed (host and devices)
         f->meshed = false;
         f->mesh = bhg_frame::Mesh();
+        f->inst.clear();
+        f->inst_rgb.clear();
         DeviceScope scope;
         for (auto &s : f->sh) release_shard_mesh(s);
         return BHG_OK;
@@ -875,7 +923,36 @@ try {
     }
     f->mesh = std::move(m);
     f->meshed = true;
-    for (auto &s : f->sh) s.mesh_ready = false;
+    f->inst.clear();            // (new arrays: the instances are off)
+    f->inst_rgb.clear();
+    for (auto &s : f->sh) s.mesh_ready = s.inst_ready = false;
+    return BHG_OK;
+} catch (...) {
+    return host_exception();
+}
+
+int bhg_frame_set_mesh_instances(bhg_frame *f, int32_t n, const double *transforms, const float *inst_rgb)
+try {
+    if (!f) return fail(BHG_E_INVALID, "frame is NULL");
+    if (!f->meshed) return fail(BHG_E_INVALID, "mesh instances: the frame holds no mesh (bhg_frame_set_mesh first)");
+    if (n == 0) {
+        // off: the plain mesh render again
+        f->inst.clear();
+        f->inst_rgb.clear();
+        DeviceScope scope;
+        for (auto &s : f->sh) release_shard_instances(s);
+        return BHG_OK;
+    }
+    BHG_TRY(bhg::mesh_instance_transforms_check(n, transforms));
+    if (inst_rgb)
+        for (int32_t i = 0; i < n * 3; i++)
+            if (!std::isfinite(inst_rgb[i])) return fail(BHG_E_INVALID, "mesh instances: every entry of inst_rgb must be finite");
+    std::vector<double> T(transforms, transforms + (size_t)n * 12);
+    std::vector<float> rgb;
+    if (inst_rgb) rgb.assign(inst_rgb, inst_rgb + (size_t)n * 3);
+    f->inst = std::move(T);
+    f->inst_rgb = std::move(rgb);
+    for (auto &s : f->sh) s.inst_ready = false;
     return BHG_OK;
 } catch (...) {
     return host_exception();
@@ -893,6 +970,7 @@ try {
     const int S = f->cam.samples;
     const bool has_obj = f->scene.n_spheres > 0, has_disk = f->scene.disk_r_out > 0.0;
     const bool meshed = f->meshed;
+    const bool instanced = meshed && !f->inst.empty();
     if (meshed) {   // (refused before anything is enqueued)
         const char *with = has_obj ? "scene spheres" : f->rs.apply != 0 ? "redshift" : f->thermal ? "the thermal disk"
                            : f->moving ? "object motion" : f->textured ? "object textures" : nullptr;
@@ -955,6 +1033,7 @@ try {
         if (!s.scene_ready) BHG_TRY(upload_shard_scene(f, s));
         if (textured && !s.otex_ready) BHG_TRY(upload_shard_textures(f, s));
         if (meshed && !s.mesh_ready) BHG_TRY(upload_shard_mesh(f, s));
+        if (instanced && !s.inst_ready) BHG_TRY(upload_shard_instances(f, s));
     }
     for (size_t r = 0; r < world; r++) {
         Shard &s = f->sh[r];
@@ -980,16 +1059,32 @@ try {
             BHG_TRY(s.tri.ensure(s.device, s.n * sizeof(int32_t)));
             BHG_TRY(s.bary.ensure(s.device, s.n * 2 * sizeof(double)));
             const double chord = f->mesh.max_chord > 0.0 ? f->mesh.max_chord : 0.25 * prm.r_s;
-            BHG_TRY(bhg_trace_mesh_device(s.ctx, &prm, s.mesh, chord, f->cam.origin, nullptr, s.k0.as<double>(), s.n, s.end.as<double>(),
-                                          s.flags.as<uint8_t>(), s.steps.as<uint32_t>(), s.acc.as<uint32_t>(), s.tri.as<int32_t>(),
-                                          s.bary.as<double>(), s.stream));
+            // (over the instances: the same two calls in their instanced forms, and the third record)
+            if (instanced) {
+                BHG_TRY(s.inst_id.ensure(s.device, s.n * sizeof(int32_t)));
+                BHG_TRY(bhg_trace_mesh_instances_device(s.ctx, &prm, s.inst, chord, f->cam.origin, nullptr, s.k0.as<double>(), s.n,
+                                                        s.end.as<double>(), s.flags.as<uint8_t>(), s.steps.as<uint32_t>(),
+                                                        s.acc.as<uint32_t>(), s.tri.as<int32_t>(), s.inst_id.as<int32_t>(),
+                                                        s.bary.as<double>(), s.stream));
+            } else {
+                BHG_TRY(bhg_trace_mesh_device(s.ctx, &prm, s.mesh, chord, f->cam.origin, nullptr, s.k0.as<double>(), s.n,
+                                              s.end.as<double>(), s.flags.as<uint8_t>(), s.steps.as<uint32_t>(), s.acc.as<uint32_t>(),
+                                              s.tri.as<int32_t>(), s.bary.as<double>(), s.stream));
+            }
             if (f->profiling) HIP_TRY(hipEventRecord(s.evs[s.ev_used++].second, s.stream));
             bhg_scene sc;
             fill_scene(f, s, &sc);
             bhg_mesh_material mat;
             fill_mesh_material(f, s, &mat);
-            BHG_TRY(bhg_shade_mesh_material_device(s.ctx, s.end.as<double>(), s.flags.as<uint8_t>(), s.tri.as<int32_t>(),
-                                                   s.bary.as<double>(), s.P, S, &sc, s.mesh, &mat, nullptr, dst, scatter, s.stream));
+            if (instanced) {
+                BHG_TRY(bhg_shade_mesh_instances_device(s.ctx, s.end.as<double>(), s.flags.as<uint8_t>(), s.tri.as<int32_t>(),
+                                                        s.inst_id.as<int32_t>(), s.bary.as<double>(), s.P, S, &sc, s.inst, &mat,
+                                                        f->inst_rgb.empty() ? nullptr : s.inst_rgb.as<float>(), nullptr, dst, scatter,
+                                                        s.stream));
+            } else {
+                BHG_TRY(bhg_shade_mesh_material_device(s.ctx, s.end.as<double>(), s.flags.as<uint8_t>(), s.tri.as<int32_t>(),
+                                                       s.bary.as<double>(), s.P, S, &sc, s.mesh, &mat, nullptr, dst, scatter, s.stream));
+            }
             s.dir_traced = false;
             continue;
         }

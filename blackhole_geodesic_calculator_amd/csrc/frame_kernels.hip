@@ -1349,6 +1349,26 @@ __device__ __forceinline__ void mesh_texel(const float *tex, int W, int H, doubl
     rgb[2] = __builtin_fma(w11, (double)t11.z, __builtin_fma(w10, (double)t10.z, __builtin_fma(w01, (double)t01.z, w00 * (double)t00.z)));
 }
 
+// tri_rgb[T] * texel at the hit's (u, v): the material's albedo, the mesh's own whichever instance was hit
+__device__ __forceinline__ void mesh_material_albedo(const MeshShade &G, const MeshMaterialArgs &M, uint64_t i, int32_t tri, double albedo[3])
+{
+    albedo[0] = albedo[1] = albedo[2] = 1.0;
+    if (M.tri_rgb)
+        for (int c = 0; c < 3; c++) albedo[c] = (double)M.tri_rgb[(size_t)tri * 3 + c];
+    const int32_t slot = !M.tri_uv ? -1 : (M.tri_tex ? M.tri_tex[tri] : 0);
+    if (slot >= 0 && slot < M.n_tex) {
+        // the triangle's six corner coordinates: one contiguous 24-byte read
+        const float2 *uv = reinterpret_cast<const float2 *>(M.tri_uv) + (size_t)tri * 3;
+        const float2 c0 = uv[0], c1 = uv[1], c2 = uv[2];
+        const double u = G.bary[i * 2], v = G.bary[i * 2 + 1], w = 1.0 - u - v;
+        const double U = w * (double)c0.x + u * (double)c1.x + v * (double)c2.x;
+        const double V = w * (double)c0.y + u * (double)c1.y + v * (double)c2.y;
+        double texel[3];
+        mesh_texel(M.tex[slot], M.tex_w[slot], M.tex_h[slot], U, V, texel);
+        for (int c = 0; c < 3; c++) albedo[c] *= texel[c];
+    }
+}
+
 // G.tri_rgb == nullptr (launch_shade_mesh_material sees to it): mesh_colour leaves the lamp sum in every channel
 __device__ __forceinline__ void mesh_material_ray_colour(const ShadeArgs &A, const MeshShade &G, const MeshMaterialArgs &M, uint64_t i,
                                                          double rgb[3])
@@ -1358,26 +1378,82 @@ __device__ __forceinline__ void mesh_material_ray_colour(const ShadeArgs &A, con
     if (fl == BHG_FLAG_HIT_OBJECT_ && tri >= 0 && tri < G.mesh.n_tris) {
         mesh_colour(A, G, i, tri, rgb);
         const double light = rgb[0] + M.emission;
-        double albedo[3] = {1.0, 1.0, 1.0};
-        if (M.tri_rgb)
-            for (int c = 0; c < 3; c++) albedo[c] = (double)M.tri_rgb[(size_t)tri * 3 + c];
-        const int32_t slot = !M.tri_uv ? -1 : (M.tri_tex ? M.tri_tex[tri] : 0);
-        if (slot >= 0 && slot < M.n_tex) {
-            // the triangle's six corner coordinates: one contiguous 24-byte read
-            const float2 *uv = reinterpret_cast<const float2 *>(M.tri_uv) + (size_t)tri * 3;
-            const float2 c0 = uv[0], c1 = uv[1], c2 = uv[2];
-            const double u = G.bary[i * 2], v = G.bary[i * 2 + 1], w = 1.0 - u - v;
-            const double U = w * (double)c0.x + u * (double)c1.x + v * (double)c2.x;
-            const double V = w * (double)c0.y + u * (double)c1.y + v * (double)c2.y;
-            double texel[3];
-            mesh_texel(M.tex[slot], M.tex_w[slot], M.tex_h[slot], U, V, texel);
-            for (int c = 0; c < 3; c++) albedo[c] *= texel[c];
-        }
+        double albedo[3];
+        mesh_material_albedo(G, M, i, tri, albedo);
         for (int c = 0; c < 3; c++) rgb[c] = albedo[c] * light;
         return;
     }
     const double *d = A.end + i * 6 + 3;
     ray_colour<false, false, false, false, false, false>(A, i, fl, d[0], d[1], d[2], rgb, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------
+// The instanced mesh shade (bhg_shade_mesh_instances_device).  A ray that the instanced trace ended on
+// triangle T of instance j gets albedo * inst_rgb[j] * (lamp_sum + emission), the material's albedo and emission those of the
+// mesh, shared by all instances.  lamp_sum is mesh_colour's with
+//   n   formed in the instance's frame as mesh_colour forms it, flat or interpolated, rotated by R_j, and only then normalised
+//       and turned to face the incoming ray;
+//   a lamp shadowed when the segment from x + 1e-5 l^ to the lamp meets any triangle of any instance (segment_first_hit_instances
+//       in its any-hit form: index order, the world box first).
+// One instance under the identity: 1 x + 0 y + 0 z and x - 0 are exact, the colour is the material shade's, bit for bit.
+// ------------------------------------------------------------------------------------------
+struct MeshInstanceShade {
+    const double *rec;         // [n][BHG_MESH_INSTANCE_DOUBLES_]
+    int32_t n;
+    int32_t boxes;             // 0: the shadow segments look at no world box (BHGEO_MESH_CULL=0)
+    const int32_t *inst_id;    // [S*n_pixels]
+    const float *inst_rgb;     // [n][3], or nullptr
+};
+
+__device__ __forceinline__ void mesh_instance_ray_colour(const ShadeArgs &A, const MeshShade &G, const MeshMaterialArgs &M,
+                                                         const MeshInstanceShade &I, uint64_t i, double rgb[3])
+{
+    const uint8_t fl = A.flags[i];
+    const int32_t tri = G.tri_id[i], inst = I.inst_id[i];
+    if (!(fl == BHG_FLAG_HIT_OBJECT_ && tri >= 0 && tri < G.mesh.n_tris && inst >= 0 && inst < I.n)) {
+        const double *d = A.end + i * 6 + 3;
+        ray_colour<false, false, false, false, false, false>(A, i, fl, d[0], d[1], d[2], rgb, nullptr);
+        return;
+    }
+    const double *e = A.end + i * 6;
+    const int32_t slot = G.mesh.tri_slot[tri];
+    const double *T = G.mesh.tri + (size_t)slot * 9;
+    double m[3], n[3];
+    if (G.mesh.tri_normals) {
+        const double *N = G.mesh.tri_normals + (size_t)slot * 9;
+        const double u = G.bary[i * 2], v = G.bary[i * 2 + 1], w = 1.0 - u - v;
+        for (int c = 0; c < 3; c++) m[c] = w * N[c] + u * N[3 + c] + v * N[6 + c];
+    } else {
+        m[0] = T[4] * T[8] - T[5] * T[7];
+        m[1] = T[5] * T[6] - T[3] * T[8];
+        m[2] = T[3] * T[7] - T[4] * T[6];
+    }
+    instance_rotate_out(I.rec + (size_t)inst * BHG_MESH_INSTANCE_DOUBLES_, m, n);
+    const double len = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    const double sgn = (n[0] * e[3] + n[1] * e[4] + n[2] * e[5]) > 0.0 ? -1.0 : 1.0;
+    for (int c = 0; c < 3; c++) n[c] = sgn * (n[c] / len);
+    double sum = 0.0;
+    for (int l = 0; l < A.n_lamps; l++) {
+        const double lv[3] = {A.lamps[l][0] - e[0], A.lamps[l][1] - e[1], A.lamps[l][2] - e[2]};
+        const double d2 = lv[0] * lv[0] + lv[1] * lv[1] + lv[2] * lv[2];
+        const double dist = sqrt(d2);
+        const double ld[3] = {lv[0] / dist, lv[1] / dist, lv[2] / dist};
+        const double ndl = n[0] * ld[0] + n[1] * ld[1] + n[2] * ld[2];
+        if (!(ndl > 0.0)) continue;
+        const double from[3] = {e[0] + 1e-5 * ld[0], e[1] + 1e-5 * ld[1], e[2] + 1e-5 * ld[2]};
+        const double to[3] = {A.lamps[l][0], A.lamps[l][1], A.lamps[l][2]};
+        double s_hit;
+        int32_t by;
+        if (segment_first_hit_instances<true>(G.mesh, I.rec, I.n, I.boxes != 0, from, to, s_hit, by) >= 0) continue;
+        sum += A.lamps[l][3] * A.lamps[l][3] * ndl / d2;
+    }
+    // (1.0 * sum, as mesh_colour leaves it in a white mesh's channels)
+    const double light = 1.0 * sum + M.emission;
+    double albedo[3];
+    mesh_material_albedo(G, M, i, tri, albedo);
+    if (I.inst_rgb)
+        for (int c = 0; c < 3; c++) albedo[c] *= (double)I.inst_rgb[(size_t)inst * 3 + c];
+    for (int c = 0; c < 3; c++) rgb[c] = albedo[c] * light;
 }
 
 // the mesh shades' colour type: one overload per family, told apart by the argument structs that ride behind ShadeArgs
@@ -1394,6 +1470,16 @@ struct MeshColour {
     }
 };
 
+// ... and the instanced one: a functor of its own under the same skeleton
+struct MeshInstanceColour {
+    static constexpr bool STOKES = false;
+    static __device__ __forceinline__ void ray(const ShadeArgs &A, uint64_t i, double rgb[3], double *, const MeshShade &G,
+                                               const MeshMaterialArgs &M, const MeshInstanceShade &I)
+    {
+        mesh_instance_ray_colour(A, G, M, I, i, rgb);
+    }
+};
+
 hipError_t launch_shade_mesh(const ShadeArgs &a, const MeshView &m, const int32_t *tri_id, const double *bary, const float *tri_rgb,
                              hipStream_t s)
 {
@@ -1407,6 +1493,15 @@ hipError_t launch_shade_mesh_material(const ShadeArgs &a, const MeshView &m, con
 {
     if (a.n_pixels == 0) return hipSuccess;
     launch_shade_pixels<MeshColour>(a, s, MeshShade{m, tri_id, bary, nullptr}, M);
+    return hipGetLastError();
+}
+
+hipError_t launch_shade_mesh_instances(const ShadeArgs &a, const MeshView &m, const int32_t *tri_id, const double *bary,
+                                       const MeshMaterialArgs &M, const double *rec, int32_t n_inst, bool boxes,
+                                       const int32_t *inst_id, const float *inst_rgb, hipStream_t s)
+{
+    if (a.n_pixels == 0) return hipSuccess;
+    launch_shade_pixels<MeshInstanceColour>(a, s, MeshShade{m, tri_id, bary, nullptr}, M, MeshInstanceShade{rec, n_inst, boxes ? 1 : 0, inst_id, inst_rgb});
     return hipGetLastError();
 }
 

@@ -339,6 +339,18 @@ struct MeshArgs {
 constexpr int BHG_MESH_MAX_SUBSTEPS_ = 1024;
 hipError_t launch_trace_mesh(const TraceArgs &a, const MeshArgs &m, int rhs, hipStream_t s);
 hipError_t launch_trace_mesh_kerr(const TraceArgs &a, const MeshArgs &m, hipStream_t s);
+// the mesh trace over K rigid placements of the one tree (trace_mesh_instances_kernel).  The records ride
+// in an argument struct of their own; m.box is the union of the placements' world boxes and m.d_min, m.d_max the set's range of
+// distances from the origin, so the whole-step cull is the plain kernel's
+constexpr int BHG_MESH_INSTANCES_MAX_ = 64;
+struct MeshInstanceArgs {
+    const double *rec;      // [n][BHG_MESH_INSTANCE_DOUBLES_] (mesh_traverse.h): R row-major, t, the world box; unchanged during the launch
+    int32_t n;              // 1 .. BHG_MESH_INSTANCES_MAX_
+    int32_t cull;           // 0: no instance's world box is looked at (BHGEO_MESH_CULL=0, as MeshArgs::cull)
+    int32_t *inst_id;       // [a.n]: the placement of a ray that ends on the mesh, else -1
+};
+hipError_t launch_trace_mesh_instances(const TraceArgs &a, const MeshArgs &m, const MeshInstanceArgs &in, int rhs, hipStream_t s);
+hipError_t launch_trace_mesh_instances_kerr(const TraceArgs &a, const MeshArgs &m, const MeshInstanceArgs &in, hipStream_t s);
 // the mesh shade (MeshColour under shade_pixels_kernel, frame_kernels.hip): a.end / flags / sky / disk / lamps as launch_shade's plain instance wants
 // them, n_spheres = 0; tri_rgb nullptr = white
 hipError_t launch_shade_mesh(const ShadeArgs &a, const MeshView &m, const int32_t *tri_id, const double *bary, const float *tri_rgb,
@@ -355,6 +367,11 @@ struct MeshMaterialArgs {
 };
 hipError_t launch_shade_mesh_material(const ShadeArgs &a, const MeshView &m, const int32_t *tri_id, const double *bary,
                                       const MeshMaterialArgs &mat, hipStream_t s);
+// the instanced mesh shade (MeshInstanceColour): the material shade over the records of an instance set --
+// rec [n_inst][BHG_MESH_INSTANCE_DOUBLES_], inst_id [S * n_pixels], inst_rgb [n_inst][3] or nullptr
+hipError_t launch_shade_mesh_instances(const ShadeArgs &a, const MeshView &m, const int32_t *tri_id, const double *bary,
+                                       const MeshMaterialArgs &mat, const double *rec, int32_t n_inst, bool boxes,
+                                       const int32_t *inst_id, const float *inst_rgb, hipStream_t s);
 // the recording pass of the start-up records (record_prefix_kernel: one lane per ray; rhs Christoffel or reduced, a.x0 == nullptr):
 // rec [7][a.n] 16-byte planes, rho the radius about a.x0s the recorded steps stay inside.  deep: the record carries on through
 // rejected attempts (BHG_PREFIX_RECORD_DEEP: at most BHG_PREFIX_DEEP_ACCEPTED_ accepted steps in BHG_PREFIX_DEEP_ATTEMPTS_ attempts)

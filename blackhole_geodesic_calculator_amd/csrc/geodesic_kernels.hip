@@ -3540,8 +3540,40 @@ __device__ __forceinline__ bool mesh_step_candidate(const MeshArgs &G, const Den
     return true;
 }
 
-template <int RHS>
-__global__ void __launch_bounds__(64) trace_mesh_kernel(const TraceArgs A, const MeshArgs G)
+// Where the mesh stands: as it lies -- the trace of section 19 --, or in K rigid placements of the one
+// tree.  One ray loop (trace_mesh_ray) asks either for the first hit of a sub-chord, for a point in the frame of the placement
+// that was hit, and to keep that placement's index.
+struct MeshAsItLies {
+    __device__ __forceinline__ int32_t first_hit(const MeshView &M, const double pa[3], const double pb[3], double &s_hit, int32_t &inst) const
+    {
+        return segment_first_hit<false>(M, pa, pb, s_hit);
+    }
+    __device__ __forceinline__ void to_local(int32_t, const double c[3], double l[3]) const
+    {
+        l[0] = c[0];
+        l[1] = c[1];
+        l[2] = c[2];
+    }
+    __device__ __forceinline__ void keep(uint64_t, int32_t) const {}
+};
+
+// The placements of an instance set: the walk over them is mesh_traverse.h's (wave-uniform, the records by scalar loads).
+struct MeshPlacements {
+    const MeshInstanceArgs &I;
+    __device__ __forceinline__ int32_t first_hit(const MeshView &M, const double pa[3], const double pb[3], double &s_hit, int32_t &inst) const
+    {
+        return segment_first_hit_instances<false>(M, I.rec, I.n, I.cull != 0, pa, pb, s_hit, inst);
+    }
+    // (the placement that was hit differs from lane to lane: its record is read as any array is)
+    __device__ __forceinline__ void to_local(int32_t inst, const double c[3], double l[3]) const
+    {
+        instance_into_frame(I.rec + (size_t)inst * BHG_MESH_INSTANCE_DOUBLES_, c, l);
+    }
+    __device__ __forceinline__ void keep(uint64_t i, int32_t inst) const { I.inst_id[i] = inst; }
+};
+
+template <int RHS, class Where>
+__device__ __forceinline__ void trace_mesh_ray(const TraceArgs &A, const MeshArgs &G, const Where &W)
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= A.n) return;
@@ -3551,11 +3583,12 @@ __global__ void __launch_bounds__(64) trace_mesh_kernel(const TraceArgs A, const
     double xe[3], ve[3];
     if (start_ray<RHS, true>(A, i, S, xe, ve)) {    // final at once
         G.tri_id[i] = -1;
+        W.keep(i, -1);
         store_start_inside(A, i, xe, ve);
         return;
     }
     uint32_t flags = 0;
-    int32_t tri = -1;
+    int32_t tri = -1, inst = -1;
     for (;;) {
         StepTry P;
         const uint32_t st = dp54_attempt<RHS>(A, S, P);
@@ -3598,14 +3631,16 @@ __global__ void __launch_bounds__(64) trace_mesh_kernel(const TraceArgs A, const
                 const double tb = m + 1 == M ? P.t_new : S.t + (P.h * (double)(m + 1)) / (double)M;
                 double pb[3], s_hit;
                 mesh_point<RHS>(A, d, tb, pb);
-                const int32_t hit = segment_first_hit<false>(G.mesh, pa, pb, s_hit);
+                int32_t on = 0;
+                const int32_t hit = W.first_hit(G.mesh, pa, pb, s_hit, on);
                 if (hit >= 0) {
                     const double *T = G.mesh.tri + (size_t)G.mesh.tri_slot[hit] * 9;
                     const double e1[3] = {T[3], T[4], T[5]}, e2[3] = {T[6], T[7], T[8]};
                     const double nT[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
                     auto g_T = [&](double tq) {
-                        double c[3];
-                        mesh_point<RHS>(A, d, tq, c);
+                        double cw[3], c[3];
+                        mesh_point<RHS>(A, d, tq, cw);
+                        W.to_local(on, cw, c);
                         return nT[0] * (c[0] - T[0]) + nT[1] * (c[1] - T[1]) + nT[2] * (c[2] - T[2]);
                     };
                     // (the ends straddle the plane up to rounding: without a sign change -- both within rounding of the
@@ -3621,8 +3656,9 @@ __global__ void __launch_bounds__(64) trace_mesh_kernel(const TraceArgs A, const
                     else
                         root = brent_root(g_T, ta, tb);
                     if (!evflag || root <= t_stop) {
-                        double c[3];
-                        mesh_point<RHS>(A, d, root, c);
+                        double cw[3], c[3];
+                        mesh_point<RHS>(A, d, root, cw);
+                        W.to_local(on, cw, c);
                         const double w[3] = {c[0] - T[0], c[1] - T[1], c[2] - T[2]};
                         const double nn = nT[0] * nT[0] + nT[1] * nT[1] + nT[2] * nT[2];
                         const double we2[3] = {w[1] * e2[2] - w[2] * e2[1], w[2] * e2[0] - w[0] * e2[2], w[0] * e2[1] - w[1] * e2[0]};
@@ -3630,6 +3666,7 @@ __global__ void __launch_bounds__(64) trace_mesh_kernel(const TraceArgs A, const
                         G.bary[i * 2 + 0] = (we2[0] * nT[0] + we2[1] * nT[1] + we2[2] * nT[2]) / nn;
                         G.bary[i * 2 + 1] = (e1w[0] * nT[0] + e1w[1] * nT[1] + e1w[2] * nT[2]) / nn;
                         tri = hit;
+                        inst = on;
                         evflag = BHG_FLAG_HIT_OBJECT_;
                         t_stop = root;
                     }
@@ -3647,6 +3684,7 @@ __global__ void __launch_bounds__(64) trace_mesh_kernel(const TraceArgs A, const
             // disk off and no triangle: the plain trace's bits
             if (tri < 0 && exit_as_plain_trace<RHS>(A, i, S, P, ev_h, ev_e)) {
                 G.tri_id[i] = -1;
+                W.keep(i, -1);
                 return;
             }
             build_dense_dir(d, S.a1, P.a2, P.a3, P.a4, P.a5, P.a6, P.a7);
@@ -3660,7 +3698,21 @@ __global__ void __launch_bounds__(64) trace_mesh_kernel(const TraceArgs A, const
         }
     }
     G.tri_id[i] = tri;
+    W.keep(i, inst);
     finish_ray(A, i, S, xe, ve, flags);
+}
+
+template <int RHS>
+__global__ void __launch_bounds__(64) trace_mesh_kernel(const TraceArgs A, const MeshArgs G)
+{
+    trace_mesh_ray<RHS>(A, G, MeshAsItLies{});
+}
+
+// ... in K rigid placements (bhg_trace_mesh_instances_device): G carries the set's union box and its range of distances
+template <int RHS>
+__global__ void __launch_bounds__(64) trace_mesh_instances_kernel(const TraceArgs A, const MeshArgs G, const MeshInstanceArgs I)
+{
+    trace_mesh_ray<RHS>(A, G, MeshPlacements{I});
 }
 
 #if defined(BHG_TU_KERR)
@@ -3673,6 +3725,21 @@ hipError_t launch_trace_mesh(const TraceArgs &a, const MeshArgs &m, int rhs, hip
 {
     if (rhs == BHG_RHS_KERR_BL_) return launch_trace_mesh_kerr(a, m, s);
     return launch_lanes(a, rhs, [&](auto R, dim3 grid) { BHG_LAUNCH((trace_mesh_kernel<R.value>), grid, dim3(64), 0, s, a, m); });
+}
+#endif
+
+#if defined(BHG_TU_KERR)
+hipError_t launch_trace_mesh_instances_kerr(const TraceArgs &a, const MeshArgs &m, const MeshInstanceArgs &in, hipStream_t s)
+{
+    return launch_lanes(a, BHG_RHS_KERR_BL_,
+                        [&](auto R, dim3 grid) { BHG_LAUNCH((trace_mesh_instances_kernel<R.value>), grid, dim3(64), 0, s, a, m, in); });
+}
+#elif !defined(BHG_TU_TIMELIKE)
+hipError_t launch_trace_mesh_instances(const TraceArgs &a, const MeshArgs &m, const MeshInstanceArgs &in, int rhs, hipStream_t s)
+{
+    if (rhs == BHG_RHS_KERR_BL_) return launch_trace_mesh_instances_kerr(a, m, in, s);
+    return launch_lanes(a, rhs,
+                        [&](auto R, dim3 grid) { BHG_LAUNCH((trace_mesh_instances_kernel<R.value>), grid, dim3(64), 0, s, a, m, in); });
 }
 #endif
 

@@ -1,5 +1,6 @@
 // mesh_traverse.h -- segment against the flattened BVH of mesh_bvh.h, on the device.  One function for
-// the mesh trace's sub-chords (first hit) and the mesh shade's shadow rays (any hit).
+// the mesh trace's sub-chords (first hit) and the mesh shade's shadow rays (any hit), and its form over K rigid placements of
+// the one tree.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -84,6 +85,66 @@ __device__ __forceinline__ int32_t segment_first_hit(const MeshView &M, const do
             }
         }
         i++;
+    }
+    s_hit = best;
+    return best_tri;
+}
+
+// ---- K rigid placements of the tree --------------------------------------------------------------------
+// Instance j is rec[j]: R row-major, t, then its world box lo, hi (x_world = R x_local + t).  The records do not change during
+// a launch and are read through the constant address space: where j is uniform over the wave they come by scalar loads, into
+// SGPRs.  That is why the walk below has no early way out: every lane goes through j = 0 .. n - 1, and skips inside it.
+constexpr int BHG_MESH_INSTANCE_DOUBLES_ = 18;
+typedef const double __attribute__((address_space(4))) *InstanceRecords;
+
+// p' = R^T (p - t): c in the world, l in the frame of the instance whose record starts at r
+template <class Rec>
+__device__ __forceinline__ void instance_into_frame(Rec r, const double c[3], double l[3])
+{
+    const double w[3] = {c[0] - r[9], c[1] - r[10], c[2] - r[11]};
+    l[0] = r[0] * w[0] + r[3] * w[1] + r[6] * w[2];
+    l[1] = r[1] * w[0] + r[4] * w[1] + r[7] * w[2];
+    l[2] = r[2] * w[0] + r[5] * w[1] + r[8] * w[2];
+}
+
+// n = R m: a direction of the instance's frame in the world
+template <class Rec>
+__device__ __forceinline__ void instance_rotate_out(Rec r, const double m[3], double n[3])
+{
+    n[0] = r[0] * m[0] + r[1] * m[1] + r[2] * m[2];
+    n[1] = r[3] * m[0] + r[4] * m[1] + r[5] * m[2];
+    n[2] = r[6] * m[0] + r[7] * m[1] + r[8] * m[2];
+}
+
+// The segment p -> q in the world against every placement, in index order.  A placement's world box is met before the segment
+// is taken into its frame, where segment_first_hit runs against the one tree; the chord parameter is the same in both frames.
+// First hit (ANY = false): the smallest s wins, a tie goes to the smaller instance (a later one must be strictly nearer), then to
+// the smaller triangle.  ANY = true: is any triangle of any placement met at all (the first placement that says so is kept).
+// Returns the caller's triangle within the mesh (s in s_hit, the placement in inst), or -1.  boxes = false: no world box is
+// looked at, every placement is walked (BHGEO_MESH_CULL=0: the same results).
+template <bool ANY>
+__device__ __forceinline__ int32_t segment_first_hit_instances(const MeshView &M, const double *records, int32_t n, bool boxes,
+                                                               const double p[3], const double q[3], double &s_hit, int32_t &inst)
+{
+    const double d[3] = {q[0] - p[0], q[1] - p[1], q[2] - p[2]};
+    const InstanceRecords rec = (InstanceRecords)(uintptr_t)records;
+    double best = 1.0;
+    int32_t best_tri = -1;
+    for (int32_t j = 0; j < n; j++) {
+        double r[BHG_MESH_INSTANCE_DOUBLES_];
+#pragma unroll
+        for (int k = 0; k < BHG_MESH_INSTANCE_DOUBLES_; k++) r[k] = rec[(size_t)j * BHG_MESH_INSTANCE_DOUBLES_ + k];
+        if (ANY && best_tri >= 0) continue;
+        if (boxes && !segment_meets_box(r + 12, p, d, best)) continue;
+        double lp[3], lq[3], s;
+        instance_into_frame(r, p, lp);
+        instance_into_frame(r, q, lq);
+        const int32_t hit = segment_first_hit<ANY>(M, lp, lq, s);
+        if (hit >= 0 && (best_tri < 0 || s < best)) {
+            best = s;
+            best_tri = hit;
+            inst = j;
+        }
     }
     s_hit = best;
     return best_tri;

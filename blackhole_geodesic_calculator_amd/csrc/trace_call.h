@@ -40,6 +40,9 @@ struct TraceCall {
     double max_chord = 0.0;
     int32_t *tri_id = nullptr;
     double *bary = nullptr;
+    // ... in the rigid placements of an instance set (with mesh: the set's mesh), and the third output inst_id [n]
+    const bhg_mesh_instances *instances = nullptr;
+    int32_t *inst_id = nullptr;
 
     // The call for rays [off, off + m): every per-ray array advanced by off times its elements per ray, null staying null; the
     // records' layers keep their stride (these rays sit at offset off inside every layer).  The start-up records are dropped:
@@ -52,7 +55,8 @@ struct TraceCall {
         skip(off * 3, t.d_x0, t.d_k0, t.d_end_dir);
         skip(off * 6, t.d_end, t.cross);
         skip(off * 2, t.bary);
-        skip(off, t.d_flags, t.d_n_steps, t.d_n_accepted, t.d_object_id, t.d_start_steps, t.n_cross, t.t_end, t.t_cross, t.tri_id);
+        skip(off, t.d_flags, t.d_n_steps, t.d_n_accepted, t.d_object_id, t.d_start_steps, t.n_cross, t.t_end, t.t_cross, t.tri_id,
+             t.inst_id);
         return t;
     }
     template <class... T>

@@ -200,6 +200,9 @@ class DeviceFrame:
         self.mesh_chord = None        # max_chord of the mesh trace; None: a quarter of the trace parameters' r_s
         self.d_tri_rgb = None         # [nt, 3] fp32 triangle colours, or None (white)
         self.mesh_material = None     # set_mesh(material=): (_ffi.MeshMaterial, its struct over the device copies, the copies)
+        self.mesh_instances = None    # _ffi.MeshInstances (set_mesh(instances=)) or None: the mesh where its vertices put it
+        self.d_inst_rgb = None        # [K, 3] float32 or None
+        self.d_inst_id = None         # [n] int32 of the last instanced trace
         self.d_tri_id = None          # [n] int32 and
         self.d_bary = None            # [n, 2] fp64 of the last mesh trace
 
@@ -321,7 +324,7 @@ class DeviceFrame:
             raise ValueError("opacity must be in (0, 1]")
         self.disk_layers = _ffi.make_disk_layers(max_crossings, opacity)
 
-    def set_mesh(self, mesh=None, tri_rgb=None, chord=None, lamps=None, material=None):
+    def set_mesh(self, mesh=None, tri_rgb=None, chord=None, lamps=None, material=None, instances=None, inst_rgb=None):
         """A triangle mesh in the curved region (bhg_trace_mesh_device, bhg_shade_mesh_device): trace()
         ends a ray where its curve meets a triangle and keeps d_tri_id [n] int32 / d_bary [n, 2]; shade() / shade_f32() /
         render() light the mesh rays (tri_rgb [nt, 3] per triangle, default white; the lamps of set_objects([], lamps=...) or
@@ -330,10 +333,18 @@ class DeviceFrame:
         object spheres, disk layers, redshift, polarisation, the thermal disk or shade_stokes() (ValueError).  The kept
         initial steps and start-up records are neither used nor touched.  None: off -- every path the one it was, bit for bit.
         material: an _ffi.MeshMaterial (per-corner UVs, image textures, emission; bhg_shade_mesh_material_device, DESIGN.md
-        section 20) in place of tri_rgb -- both together are a ValueError; without it the shade is the existing call."""
+        section 20) in place of tri_rgb -- both together are a ValueError; without it the shade is the existing call.
+        instances: [K, 12] or [K, 3, 4] rigid placements of the mesh (bhg_trace_mesh_instances_device,
+        bhg_shade_mesh_instances_device) -- trace() also keeps d_inst_id [n]; inst_rgb [K, 3] float32
+        multiplies the albedo per instance.  set_mesh_instances(T) moves them afterwards."""
         if material is not None and tri_rgb is not None:
             raise ValueError("material and tri_rgb together: the material carries the triangle colours")
+        if inst_rgb is not None and instances is None:
+            raise ValueError("inst_rgb goes with instances=")
         self._traced = None
+        if self.mesh_instances is not None:
+            self.mesh_instances.close()
+        self.mesh_instances = self.d_inst_rgb = None
         if mesh is None:
             self.mesh = self.d_tri_rgb = self.mesh_chord = self.mesh_material = None
             return
@@ -357,6 +368,29 @@ class DeviceFrame:
         if lamps is not None:
             self.lamps = lamps
         self._mesh_check()
+        if instances is not None:
+            self.mesh_instances = _ffi.MeshInstances(mesh, instances)
+            if inst_rgb is not None:
+                rgb = np.ascontiguousarray(inst_rgb, dtype=np.float32)
+                if rgb.shape != (self.mesh_instances.n, 3):
+                    raise ValueError("inst_rgb must have shape [K, 3]")
+                self.d_inst_rgb = torch.as_tensor(rgb).to(self.dev)
+
+    def set_mesh_instances(self, transforms=None):
+        """Move the instances of set_mesh(instances=): K x 18 doubles go to the device, nothing is rebuilt (bhg_mesh_instances_set).
+        Another K makes a new set (inst_rgb is then dropped); None turns instances off -- the mesh where its vertices put it."""
+        if self.mesh is None:
+            raise ValueError("set_mesh_instances() wants a mesh: set_mesh() first")
+        self._traced = None
+        T = None if transforms is None else _ffi._instance_transforms(transforms)
+        if T is not None and self.mesh_instances is not None and T.shape[0] == self.mesh_instances.n:
+            self.mesh_instances.set(T)
+            return
+        if self.mesh_instances is not None:
+            self.mesh_instances.close()
+        self.mesh_instances = self.d_inst_rgb = None
+        if T is not None:
+            self.mesh_instances = _ffi.MeshInstances(self.mesh, T)
 
     def _mesh_check(self):
         for name, on in (("object spheres", self.spheres is not None and len(self.spheres) > 0),
@@ -440,6 +474,16 @@ class DeviceFrame:
                 self.d_bary = torch.empty((self.n, 2), dtype=torch.float64, device=self.dev)
             self._dir_traced, self._traced = False, None
             chord = 0.25 * float(params.r_s) if self.mesh_chord is None else self.mesh_chord
+            if self.mesh_instances is not None:
+                if self.d_inst_id is None:
+                    self.d_inst_id = torch.empty(self.n, dtype=torch.int32, device=self.dev)
+                self.ctx.trace_mesh_instances_device(params, self.mesh_instances, chord, self.n, self.d_k0.data_ptr(),
+                                                     self.d_end.data_ptr(), self.d_tri_id.data_ptr(), self.d_inst_id.data_ptr(),
+                                                     self.d_bary.data_ptr(), x0_shared=origin, d_flags=self.d_flags.data_ptr(),
+                                                     d_n_steps=self.d_steps.data_ptr(), d_n_accepted=self.d_acc.data_ptr(),
+                                                     stream=self._stream())
+                self._traced = "mesh"
+                return
             self.ctx.trace_mesh_device(params, self.mesh, chord, self.n, self.d_k0.data_ptr(), self.d_end.data_ptr(),
                                        self.d_tri_id.data_ptr(), self.d_bary.data_ptr(), x0_shared=origin,
                                        d_flags=self.d_flags.data_ptr(), d_n_steps=self.d_steps.data_ptr(),
@@ -530,6 +574,17 @@ class DeviceFrame:
             if pol is not None:
                 raise ValueError("a mesh has no Stokes images: shade_stokes() is not available with set_mesh()")
             self._mesh_check()
+            if self.mesh_instances is not None:
+                # (the instanced shade takes tri_rgb= as a material that holds nothing else)
+                mat = self.mesh_material[1] if self.mesh_material is not None else (
+                    None if self.d_tri_rgb is None else _ffi.MeshMaterial().struct([self.d_tri_rgb.data_ptr(), 0, 0]))
+                self.ctx.shade_mesh_instances_device(self.d_end.data_ptr(), self.d_flags.data_ptr(), self.d_tri_id.data_ptr(),
+                                                     self.d_inst_id.data_ptr(), self.d_bary.data_ptr(), self.P, self.S, self.scene(),
+                                                     self.mesh_instances, mat,
+                                                     d_inst_rgb=0 if self.d_inst_rgb is None else self.d_inst_rgb.data_ptr(),
+                                                     d_rgba=d_rgba, d_rgba_f32=d_rgba_f32,
+                                                     d_scatter=0 if scatter is None else scatter.data_ptr(), stream=self._stream())
+                return
             if self.mesh_material is not None:
                 self.ctx.shade_mesh_material_device(self.d_end.data_ptr(), self.d_flags.data_ptr(), self.d_tri_id.data_ptr(),
                                                     self.d_bary.data_ptr(), self.P, self.S, self.scene(), self.mesh,

@@ -64,7 +64,8 @@ class GeodesicIntegratorSchwarzschild:
 
     # ------------------------------------------------------------------------------------
     def trace(self, k0, x0, max_step=np.inf, curve_end=50.0, r_exit=0.0, disk=None, spheres=None, redshift=None,
-              polarisation=None, disk_thermal=None, disk_crossings=None, travel_time=False, mesh=None, mesh_chord=None):
+              polarisation=None, disk_thermal=None, disk_crossings=None, travel_time=False, mesh=None, mesh_chord=None,
+              mesh_instances=None):
         """Batched solve.  k0[N,3] (or [...,3]); x0[3] shared origin or same leading shape as k0.
         r_exit: outward sphere-exit radius (Limited engine's ray_trace, Limited...py:273-278);
         disk=(R_in, R_out): thin disk in z = 0, first crossing inside the annulus ends the ray with
@@ -115,14 +116,20 @@ class GeodesicIntegratorSchwarzschild:
             bary[..., 2]               the plane coordinates (u, v) of the hit in that triangle, NaN for every other ray
         mesh_chord (default 0.25 r_s): the length of the straight sub-chords each step is tested in.  Not with spheres=,
         disk_crossings=, travel_time=, redshift=, polarisation= or disk_thermal=.
+        mesh_instances=T ([K, 12]: R row-major then t, or [K, 3, 4]: R | t; with mesh=): the mesh stands in
+        K rigid placements x_world = R x_local + t instead of where its vertices put it, and the dict also has
+            inst_id[...]               int32, the placement hit, -1 for every other ray (tri_id counts within the mesh, bary lies
+                                       in the placement's frame)
         """
+        if mesh_instances is not None and mesh is None:
+            raise ValueError("mesh_instances goes with mesh=")
         if mesh is not None:
             for name, given in (("spheres", spheres is not None), ("disk_crossings", disk_crossings is not None),
                                 ("travel_time", bool(travel_time)), ("redshift", redshift is not None),
                                 ("polarisation", polarisation is not None), ("disk_thermal", disk_thermal is not None)):
                 if given:
                     raise ValueError(f"mesh does not go with {name}")
-            return self._trace_mesh(k0, x0, max_step, curve_end, r_exit, disk, mesh, mesh_chord)
+            return self._trace_mesh(k0, x0, max_step, curve_end, r_exit, disk, mesh, mesh_chord, mesh_instances)
         if travel_time and spheres is not None:
             raise ValueError("travel_time does not go with object spheres")
         if disk_crossings is not None:
@@ -174,21 +181,32 @@ class GeodesicIntegratorSchwarzschild:
             out["t"] = t.reshape(lead)
         return out
 
-    def _trace_mesh(self, k0, x0, max_step, curve_end, r_exit, disk, mesh, mesh_chord):
-        """trace(mesh=): a mesh given as arrays lives for this call."""
+    def _trace_mesh(self, k0, x0, max_step, curve_end, r_exit, disk, mesh, mesh_chord, instances=None):
+        """trace(mesh=): a mesh given as arrays lives for this call, and so does the instance set of mesh_instances=."""
         own = not isinstance(mesh, _ffi.Mesh)
         m = _ffi.Mesh(self._ctx, mesh[0], mesh[1]) if own else mesh
+        inst = inst_id = None
         try:
             k0 = np.asarray(k0, dtype=np.float64)
             lead = k0.shape[:-1]
             x0 = np.asarray(x0, dtype=np.float64)
+            x0f = x0 if x0.ndim == 1 else x0.reshape(-1, 3)
             chord = 0.25 * self.r_s if mesh_chord is None else float(mesh_chord)
-            end, flags, steps, acc, tri, bary = self._ctx.trace_mesh(k0.reshape(-1, 3), x0 if x0.ndim == 1 else x0.reshape(-1, 3),
-                                                                     self.params(max_step, curve_end, r_exit, disk), m, chord)
+            if instances is None:
+                end, flags, steps, acc, tri, bary = self._ctx.trace_mesh(k0.reshape(-1, 3), x0f,
+                                                                         self.params(max_step, curve_end, r_exit, disk), m, chord)
+            else:
+                inst = _ffi.MeshInstances(m, instances)
+                end, flags, steps, acc, tri, inst_id, bary = self._ctx.trace_mesh_instances(
+                    k0.reshape(-1, 3), x0f, self.params(max_step, curve_end, r_exit, disk), inst, chord)
         finally:
+            if inst is not None:
+                inst.close()
             if own:
                 m.close()
+        extra = {} if inst_id is None else {"inst_id": inst_id.reshape(lead)}
         return {
+            **extra,
             "ray_end": end.reshape(lead + (6,)),
             "ray_blackhole_hit": ((flags & _ffi.FLAG_HIT_HORIZON) != 0).astype(np.uint8).reshape(lead),
             "flags": flags.reshape(lead),

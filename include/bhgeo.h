@@ -73,7 +73,10 @@ extern "C" {
                                   bhg_trace_mesh, bhg_shade_mesh_device, struct bhg_mesh, BHG_MESH_MAX_SUBSTEPS: triangle meshes
                                   in the curved region);
                                   BHG_MESH_MATERIAL (bhg_shade_mesh_material_device, bhg_frame_set_mesh, bhg_mesh_material_size,
-                                  struct bhg_mesh_material, BHG_MESH_TEXTURES_MAX: textured, emissive meshes, meshes on bhg_frame).
+                                  struct bhg_mesh_material, BHG_MESH_TEXTURES_MAX: textured, emissive meshes, meshes on bhg_frame);
+                                  BHG_MESH_INSTANCES (bhg_mesh_instances_create / _set / _destroy / _info, bhg_mesh_instance_box_host,
+                                  bhg_trace_mesh_instances_device, bhg_trace_mesh_instances, bhg_shade_mesh_instances_device, bhg_frame_set_mesh_instances, struct bhg_mesh_instances,
+                                  BHG_MESH_INSTANCES_MAX: rigid placements of one mesh, moved without a rebuild).
                                9: redshift -- bhg_redshift_device / _host, bhg_shade_scene_redshift_device, bhg_frame_set_redshift,
                                   bhg_redshift_size, struct bhg_redshift;
                                   nothing of ABI 8 changed.
@@ -1055,6 +1058,74 @@ int bhg_shade_mesh_material_device(bhg_context *ctx, const double *d_end, const 
  * redshift, the thermal disk, object motion or object textures. */
 int bhg_frame_set_mesh(bhg_frame *frame, const double *vertices, size_t n_vertices, const int32_t *triangles, size_t n_triangles,
                        const double *vertex_normals, int32_t leaf_size, double max_chord, const bhg_mesh_material *material);
+
+/* --- mesh instances: K rigid placements of one built mesh (within ABI 10) ---------------------------------
+ * Instance j is a rotation R_j and a translation t_j, 12 doubles: R row-major, then t; x_world = R_j x_local + t_j, both centred
+ * on the hole as the vertices are.  A ray takes exactly the steps, sub-chords, M and ordering against horizon, exit sphere and
+ * disk of the mesh trace above; only the test of a sub-chord changes:
+ *   * for each instance the sub-chord's two ends go to the instance's frame, p' = R_j^T (p - t_j), and the first-hit test of the
+ *     mesh trace runs there against the one tree.  The chord parameter s is the same in both frames; over all instances the
+ *     smallest s wins, a tie goes to the smaller instance index, then to the smaller triangle index;
+ *   * the hit is moved onto the curve in the winning instance's frame: Brent's search on n_T . (R_j^T (x(lambda) - t_j) - v0),
+ *     with the mesh trace's fallback when the ends do not bracket;
+ *   * end is the dense output at the root, in world coordinates; tri_id the caller's triangle within the mesh; inst_id [n] int32
+ *     the instance, -1 for a ray that ends on no triangle; bary the plane coordinates in the instance's frame.
+ * What only accelerates this (BHGEO_MESH_CULL=0 turns all of it off, the whole-step cull and the instances' boxes, in the trace
+ * and in the shade's shadow segments: the results are the same bits): each instance has a world box -- centre
+ * R c + t, half extents |R| h of the tree's root box, widened outward as the builder widens boxes -- that a sub-chord must meet
+ * before it is transformed; the whole-step cull runs against the union of these boxes (Kerr: the largest |t_j| plus the mesh's
+ * farthest vertex, and the smallest distance from the origin to an instance box).  All of it is worked out on the host in O(K)
+ * by _create and _set.  The loop over the instances is linear: BHG_MESH_INSTANCES_MAX of them at most.
+ * bhg_mesh_instances_set takes new transforms for the same n: the records are copied aside and their upload is enqueued on the
+ * context's own stream; no tree is touched and nothing else is uploaded.  The set orders the upload against the calls that read
+ * it, whatever stream they name: it runs behind every trace and shade enqueued before it, and those enqueued after it wait for
+ * it.  Nothing waits on the host, but a third _set while the first one's upload is still queued.
+ * An instance set is destroyed by the caller; destroying its mesh first leaves a set that every call refuses.
+ * Refused (BHG_E_INVALID, the message names the field) before anything is launched or written: what bhg_trace_mesh_device
+ * refuses; n outside [1, BHG_MESH_INSTANCES_MAX]; a NULL or non-finite transform entry; R^T R further than 1e-9 from the
+ * identity in any entry, or det R <= 0; a NULL d_inst_id; an instance set of another context or of a destroyed mesh. */
+#define BHG_MESH_INSTANCES 1
+#define BHG_MESH_INSTANCES_MAX 64
+typedef struct bhg_mesh_instances bhg_mesh_instances;
+int bhg_mesh_instances_create(bhg_context *ctx, const bhg_mesh *mesh, int32_t n, const double *transforms /* host [n][12] */,
+                              bhg_mesh_instances **out);
+int bhg_mesh_instances_set(bhg_mesh_instances *inst, const double *transforms /* host [n][12] */);
+void bhg_mesh_instances_destroy(bhg_mesh_instances *inst);
+/* n and the union of the instances' world boxes (lo, hi); either may be NULL */
+int bhg_mesh_instances_info(const bhg_mesh_instances *inst, int32_t *n, double box[6]);
+/* The world box (lo, hi) an instance gets from a local box (lo, hi) and one transform: host arithmetic, no context, no GPU. */
+int bhg_mesh_instance_box_host(const double local_box[6], const double transform[12], double world_box[6]);
+/* bhg_trace_mesh_device with an instance set in place of the mesh, plus d_inst_id [n] int32. */
+int bhg_trace_mesh_instances_device(bhg_context *ctx, const bhg_params *p, const bhg_mesh_instances *inst, double max_chord,
+                                    const double *x0_shared, const double *d_x0, const double *d_k0, size_t n, double *d_end,
+                                    uint8_t *d_flags, uint32_t *d_n_steps, uint32_t *d_n_accepted, int32_t *d_tri_id,
+                                    int32_t *d_inst_id, double *d_bary, void *stream);
+/* ... on host arrays, as bhg_trace_mesh.  Blocking.  bary is read first. */
+int bhg_trace_mesh_instances(bhg_context *ctx, const bhg_params *p, const bhg_mesh_instances *inst, double max_chord,
+                             const double *x0, int x0_is_shared, const double *k0, size_t n, double *end, uint8_t *flags,
+                             uint32_t *n_steps, uint32_t *n_accepted, int32_t *tri_id, int32_t *inst_id, double *bary);
+/* The shade of an instanced trace: bhg_shade_mesh_material_device over an instance set.  A mesh ray (BHG_FLAG_HIT_OBJECT,
+ * 0 <= tri_id < nt, 0 <= inst_id < n) gets albedo * inst_rgb[inst] * (lamp_sum + emission).  The material -- UVs, images, emission
+ * -- is the mesh's, shared by all instances; mat = NULL is white without emission.  d_inst_rgb [n][3] fp32 (NULL: none) multiplies
+ * the albedo, so that copies can be told apart.  lamp_sum is the mesh shade's: the normal is formed in the instance's frame, flat or
+ * interpolated, rotated by R_j, then normalised and turned to face the ray; a lamp is shadowed when the segment to it meets any
+ * triangle of any instance (index order, the instance's world box first).  One instance under the identity is
+ * bhg_shade_mesh_material_device's image, bit for bit.
+ * Refused: what bhg_shade_mesh_material_device refuses (but a NULL mat); a NULL inst or d_inst_id; an instance set of another
+ * context or of a destroyed mesh. */
+int bhg_shade_mesh_instances_device(bhg_context *ctx, const double *d_end, const uint8_t *d_flags, const int32_t *d_tri_id,
+                                    const int32_t *d_inst_id, const double *d_bary, size_t n_pixels, int32_t samples,
+                                    const bhg_scene *scene, const bhg_mesh_instances *inst, const bhg_mesh_material *mat,
+                                    const float *d_inst_rgb, double *d_rgba, float *d_rgba_f32, const int64_t *d_scatter,
+                                    void *stream);
+/* Instances of the frame's mesh: n rigid placements (host [n][12], copied), inst_rgb host [n][3] fp32 or NULL.  Each shard then
+ * traces with bhg_trace_mesh_instances_device and shades with bhg_shade_mesh_instances_device, the frame's material shared by all
+ * instances, in every gather mode.  Calling it again with other transforms for the same n moves the instances: at the next render
+ * the records go to every device (bhg_mesh_instances_set) -- no tree is built, no array or image of the mesh is uploaded.
+ * n = 0 turns instances off: the next render is the plain mesh render, bit for bit.  bhg_frame_set_mesh, with new arrays or NULL,
+ * turns them off too.  Refused, the frame left as it was: a frame without a mesh; what bhg_mesh_instances_create refuses of n and
+ * the transforms; a non-finite inst_rgb.  bhg_frame_render's "a mesh does not go with ..." cases hold as they are. */
+int bhg_frame_set_mesh_instances(bhg_frame *frame, int32_t n, const double *transforms, const float *inst_rgb);
 
 /* Acceleration probe: acc[n][3] = -Gamma^i_{mu nu} k^mu k^nu at (x[n][3], k[n][3]); host buffers.
  * Lets tests compare the device RHS with the oracle's term by term.  With rhs_form = BHG_RHS_KERR_BL the triples
