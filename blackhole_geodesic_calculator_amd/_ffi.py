@@ -74,7 +74,12 @@ EXPORTS = (
     "bhg_mesh_instances_create", "bhg_mesh_instances_set", "bhg_mesh_instances_destroy", "bhg_mesh_instances_info",
     "bhg_mesh_instance_box_host", "bhg_trace_mesh_instances_device", "bhg_trace_mesh_instances",
     "bhg_shade_mesh_instances_device", "bhg_frame_set_mesh_instances",
+    "bhg_mesh_refit", "bhg_mesh_refit_device", "bhg_mesh_refit_info", "bhg_mesh_bvh_refit_host", "bhg_mesh_refit_schedule_host",
+    "bhg_mesh_boxes_host", "bhg_mesh_range", "bhg_frame_refit_mesh", "bhg_frame_mesh_refit_info",
 )
+# the rebuild_ratio of Frame.refit_mesh and the add-on when none is given (DESIGN.md section 22 has the table it is read off: at
+# area_now / area_build = 1.13 the refitted tree traced as fast as a fresh one, at 1.55 it lost more than the rebuild costs)
+MESH_REBUILD_RATIO = 1.5
 MESH_INSTANCES_MAX = 64    # BHG_MESH_INSTANCES_MAX: rigid placements an instance set holds at most (BHG_MESH_INSTANCES)
 MESH_MAX_SUBSTEPS = 1024   # BHG_MESH_MAX_SUBSTEPS: sub-chords per accepted step at most (BHG_MESH)
 MESH_TEXTURES_MAX = 8      # BHG_MESH_TEXTURES_MAX: images a mesh material holds at most (BHG_MESH_MATERIAL)
@@ -750,6 +755,26 @@ def load():
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bhg_frame_set_mesh_instances.restype = C.c_int
     L.bhg_frame_set_mesh_instances.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.bhg_mesh_refit.restype = C.c_int
+    L.bhg_mesh_refit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bhg_mesh_refit_device.restype = C.c_int
+    L.bhg_mesh_refit_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bhg_mesh_refit_info.restype = C.c_int
+    L.bhg_mesh_refit_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), _dp, _dp]
+    L.bhg_mesh_bvh_refit_host.restype = C.c_int
+    L.bhg_mesh_bvh_refit_host.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_size_t, C.c_void_p, _dp]
+    L.bhg_mesh_refit_schedule_host.restype = C.c_int
+    L.bhg_mesh_refit_schedule_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p,
+                                               C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.bhg_mesh_range.restype = C.c_int
+    L.bhg_mesh_range.argtypes = [C.c_void_p, _dp, _dp]
+    L.bhg_mesh_boxes_host.restype = C.c_int
+    L.bhg_mesh_boxes_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    L.bhg_frame_refit_mesh.restype = C.c_int
+    L.bhg_frame_refit_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double]
+    L.bhg_frame_mesh_refit_info.restype = C.c_int
+    L.bhg_frame_mesh_refit_info.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint64), _dp, _dp]
     L.bhg_frame_set_mesh.restype = C.c_int
     L.bhg_frame_set_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32, C.c_double,
                                      C.POINTER(MeshMaterialStruct)]
@@ -820,6 +845,43 @@ def mesh_bvh_host(vertices, triangles, leaf_size=4):
     return {"box": box[:n].copy(), "skip": skip[:n].copy(), "first": first[:n].copy(), "count": count[:n].copy(), "order": order}
 
 
+def _topology_arrays(tree):
+    return tuple(np.ascontiguousarray(tree[k], dtype=np.int32) for k in ("skip", "first", "count", "order"))
+
+
+def mesh_bvh_refit_host(vertices, triangles, tree):
+    """bhg_mesh_bvh_refit_host: the CPU statement of the refit kernels (no context, no GPU).  tree: a dict
+    with mesh_bvh_host's skip, first, count and order -> (box[nn, 6] refitted to `vertices` and widened, the tree's area sum)."""
+    V, F = _mesh_arrays(vertices, triangles)
+    skip, first, count, order = _topology_arrays(tree)
+    box = np.empty((len(skip), 6), np.float64)
+    area = C.c_double(0.0)
+    _check(load().bhg_mesh_bvh_refit_host(_addr(V), V.shape[0], _addr(F), F.shape[0], _addr(skip), _addr(first), _addr(count),
+                                          _addr(order), len(skip), _addr(box), C.byref(area)))
+    return box, area.value
+
+
+def mesh_refit_schedule_host(tree):
+    """bhg_mesh_refit_schedule_host: the refit's bottom-up schedule for mesh_bvh_host's tree -> (level_nodes[n_inner],
+    level_off[34]): level_nodes[level_off[d]:level_off[d + 1]] are the inner nodes d levels below the root; deepest level first."""
+    skip, first, count, order = _topology_arrays(tree)
+    cap = max(len(order) - 1, 1)
+    nodes, off = np.empty(cap, np.int32), np.empty(34, np.int32)
+    n = C.c_size_t(0)
+    _check(load().bhg_mesh_refit_schedule_host(_addr(skip), _addr(first), _addr(count), _addr(order), len(skip), len(order),
+                                               _addr(nodes), _addr(off), cap, C.byref(n)))
+    return nodes[:n.value].copy(), off
+
+
+def _device_f64(a, shape, what):
+    """The device address of a float64, C-contiguous device array of the given shape: anything with data_ptr() (a torch tensor)."""
+    if tuple(a.shape) != tuple(shape):
+        raise ValueError(f"{what} must have shape {list(shape)}")
+    if "float64" not in str(a.dtype) or not a.is_contiguous() or not getattr(a, "is_cuda", True):
+        raise ValueError(f"{what} must be a contiguous float64 device array")
+    return a.data_ptr()
+
+
 class Mesh:
     """bhg_mesh: a triangle mesh on a context's device.  vertices [nv, 3] float64, Cartesian and centred on
     the hole; triangles [nt, 3] int32; vertex_normals [nv, 3] or None (flat shading).  Closes with its context."""
@@ -861,6 +923,45 @@ class Mesh:
         nn, depth, box = C.c_int64(0), C.c_int32(0), (C.c_double * 6)()
         _check(load().bhg_mesh_info(self._h, C.byref(nn), C.byref(depth), box))
         return nn.value, depth.value, np.array(box[:])
+
+    def refit(self, vertices, vertex_normals=None, stream=0):
+        """New vertex positions [nv, 3] (and vertex normals, for a mesh created with them) into the built mesh: the tree is
+        refitted on the device, nothing is rebuilt (bhg_mesh_refit / bhg_mesh_refit_device).  numpy arrays
+        go through the host call; anything with data_ptr() (a torch tensor on the mesh's device, float64, contiguous) through the
+        device call on `stream`.  Blocking.  Instance sets of the mesh need a set() afterwards."""
+        dev = hasattr(vertices, "data_ptr")
+        if vertex_normals is not None and hasattr(vertex_normals, "data_ptr") != dev:
+            raise ValueError("vertices and vertex_normals must both be host arrays or both device arrays")
+        shape = (self.n_vertices, 3)
+        if dev:
+            dv = _device_f64(vertices, shape, "vertices")
+            dn = None if vertex_normals is None else _device_f64(vertex_normals, shape, "vertex_normals")
+            _check(load().bhg_mesh_refit_device(self.ctx._h, self._h, C.c_void_p(dv), C.c_void_p(dn), C.c_void_p(stream or None)))
+            return
+        V = np.ascontiguousarray(vertices, dtype=np.float64)
+        N = None if vertex_normals is None else np.ascontiguousarray(vertex_normals, dtype=np.float64)
+        if V.shape != shape or (N is not None and N.shape != shape):
+            raise ValueError(f"vertices (and vertex_normals) must have the mesh's shape {list(shape)}")
+        _check(load().bhg_mesh_refit(self.ctx._h, self._h, _addr(V), None if N is None else _addr(N)))
+
+    def refit_info(self):
+        """(generation, area_build, area_now): refits so far, and the tree's area sum at creation and now (bhg_mesh_refit_info)"""
+        g, a, b = C.c_uint64(0), C.c_double(0.0), C.c_double(0.0)
+        _check(load().bhg_mesh_refit_info(self._h, C.byref(g), C.byref(a), C.byref(b)))
+        return g.value, a.value, b.value
+
+    def distance_range(self):
+        """(d_min, d_max): the distances from the origin the mesh lies between (bhg_mesh_range)"""
+        lo, hi = C.c_double(0.0), C.c_double(0.0)
+        _check(load().bhg_mesh_range(self._h, C.byref(lo), C.byref(hi)))
+        return lo.value, hi.value
+
+    def download_boxes(self):
+        """(box[nn, 6], tri[nt, 9]): the device's node boxes and slot records v0, e1, e2 (bhg_mesh_boxes_host; blocking)"""
+        nn = self.info()[0]
+        box, tri = np.empty((nn, 6), np.float64), np.empty((self.n_triangles, 9), np.float64)
+        _check(load().bhg_mesh_boxes_host(self._h, _addr(box), _addr(tri), nn))
+        return box, tri
 
 
 def _instance_transforms(transforms):
@@ -910,6 +1011,7 @@ class MeshInstances:
         self._h = h
         self.mesh = mesh
         self.n = T.shape[0]
+        self.transforms = T.copy()      # (the latest: a refit of the mesh wants them set again)
         mesh._instances.append(self)
 
     def set(self, transforms):
@@ -917,6 +1019,7 @@ class MeshInstances:
         if T.shape[0] != self.n:
             raise ValueError(f"set takes the {self.n} transforms the set was created with, not {T.shape[0]}")
         _check(load().bhg_mesh_instances_set(self._h, _addr(T)))
+        self.transforms = T.copy()
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1274,6 +1377,7 @@ class Frame:
         at render).  set_mesh(None): off -- the frame as without a mesh, bit for bit."""
         if vertices is None:
             _check(load().bhg_frame_set_mesh(self._h, None, 0, None, 0, None, 0, 0.0, None))
+            self._mesh_nv = None
             return
         V, F = _mesh_arrays(vertices, triangles)
         N = None
@@ -1289,6 +1393,30 @@ class Frame:
             m = material.struct()
         _check(load().bhg_frame_set_mesh(self._h, _addr(V), V.shape[0], _addr(F), F.shape[0], None if N is None else _addr(N),
                                          int(leaf_size), 0.0 if chord is None else float(chord), None if m is None else C.byref(m)))
+        self._mesh_nv = V.shape[0]
+
+    def refit_mesh(self, vertices, vertex_normals=None, rebuild_ratio=None):
+        """New vertex positions [nv, 3] (and vertex normals, for a mesh set with them) for the frame's mesh (bhg_frame_refit_mesh;
+        DESIGN.md section 22): at the next render each device refits its tree on the device instead of building it anew --
+        the image is the one set_mesh() with the deformed vertices gives, bit for bit; the material, the instances and their
+        colours stay.  rebuild_ratio: a device whose tree's area sum has grown past this multiple of what it was when built
+        rebuilds from the held triangles instead (None: MESH_REBUILD_RATIO; <= 0: never; 1: always)."""
+        nv = getattr(self, "_mesh_nv", None)
+        if nv is None:
+            raise ValueError("refit_mesh() wants a mesh: set_mesh() first")
+        V = np.ascontiguousarray(vertices, dtype=np.float64)
+        N = None if vertex_normals is None else np.ascontiguousarray(vertex_normals, dtype=np.float64)
+        if V.shape != (nv, 3) or (N is not None and N.shape != (nv, 3)):
+            raise ValueError(f"vertices (and vertex_normals) must have the mesh's shape [{nv}, 3]")
+        ratio = MESH_REBUILD_RATIO if rebuild_ratio is None else float(rebuild_ratio)
+        _check(load().bhg_frame_refit_mesh(self._h, _addr(V), None if N is None else _addr(N), ratio))
+
+    def mesh_refit_info(self, shard=0):
+        """(generation, area_build, area_now) of the mesh on the frame's device number `shard` (bhg_frame_mesh_refit_info): the
+        refits since that device last built its tree, and the tree's area sum when built and now"""
+        g, a, b = C.c_uint64(0), C.c_double(0.0), C.c_double(0.0)
+        _check(load().bhg_frame_mesh_refit_info(self._h, int(shard), C.byref(g), C.byref(a), C.byref(b)))
+        return g.value, a.value, b.value
 
     def set_mesh_instances(self, transforms=None, inst_rgb=None):
         """Rigid placements of the frame's mesh in every later render (bhg_frame_set_mesh_instances):

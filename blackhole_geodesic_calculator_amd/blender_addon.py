@@ -56,6 +56,11 @@ Known deviations from the reference, all deliberate:
     frame gets the datablock once, in its own coordinates with the scale baked in, and one instance per object (translation minus
     the hole's location).  A later render whose baked arrays and images are the ones held only moves the instances
     (bhg_frame_set_mesh_instances: nothing is rebuilt or uploaded).  Any other scene takes the concatenated path above, silently.
+  * scene.curved_space_mesh_refit (default 0): with curved_space_meshes = 1 on the device path, a render whose
+    mesh differs from the one the frame holds in vertex positions only -- the triangle indices, UVs, images and emission the same
+    bits, the vertex count the same -- sends the vertices alone and every device refits its tree on the device
+    (bhg_frame_refit_mesh): an armature, a shape key, cloth, a wave modifier.  This holds for the concatenated mesh and for the
+    single datablock of curved_space_mesh_instances alike.  Anything else takes the full path above, silently.
 """
 import warnings
 import os
@@ -357,6 +362,7 @@ class RelativisticRenderEngine(bpy.types.RenderEngine):
                 "tri_uv": np.ascontiguousarray(np.concatenate(UV)) if any_uv else None, "tri_tex": np.concatenate(TEX),
                 "images": images if any_uv else [], "emission": emission, "offsets": offsets,
                 "instances": None if plan is None else plan[1],
+                "refit": float(getattr(depsgraph.scene, "curved_space_mesh_refit", 0) or 0) != 0.0,
                 # (instanced: the datablock's arrays before the scale, and the scale -- what _set_device_mesh compares)
                 "local": None if plan is None else {"co": local_co, "normals": local_nrm, "scale": plan[0]}}
 
@@ -386,7 +392,21 @@ class RelativisticRenderEngine(bpy.types.RenderEngine):
             mesh["emission"] == held["emission"] and \
             all((mesh[k] is None) == (held[k] is None) and (mesh[k] is None or same_array(k, mesh[k], held[k]))
                 for k in ("vertices", "triangles", "normals", "tri_uv", "tri_tex"))
-        if not same:
+        # scene.curved_space_mesh_refit: everything but the vertex positions is what the frame holds -- the
+        # triangle indices, UVs, images and emission the same bits, the vertex count the same -- and a coordinate differs: the new
+        # vertices (and normals) go to the frame, whose devices refit their trees; the instances stay and the frame re-sets them
+        refit = not same and bool(mesh.get("refit")) and held is not None and all(i is not None for i in ids) and \
+            ids == held["ids"] and mesh["emission"] == held["emission"] and mesh["vertices"].shape == held["vertices"].shape and \
+            (mesh["normals"] is None) == (held["normals"] is None) and \
+            all((mesh[k] is None) == (held[k] is None) and (mesh[k] is None or np.array_equal(mesh[k], held[k]))
+                for k in ("triangles", "tri_uv", "tri_tex")) and \
+            not same_array("vertices", mesh["vertices"], held["vertices"])
+        self.device_mesh_action = "kept" if same else "refit" if refit else "set"
+        if refit:
+            from . import _ffi
+            fr.refit_mesh(mesh["vertices"], mesh["normals"], rebuild_ratio=_ffi.MESH_REBUILD_RATIO)
+            fr.mesh_held.update(vertices=mesh["vertices"], normals=mesh["normals"], local=local)
+        elif not same:
             from . import _ffi
             material = _ffi.MeshMaterial(tri_uv=mesh["tri_uv"], tri_tex=mesh["tri_tex"] if mesh["tri_uv"] is not None else None,
                                          textures=[self._image_pixels(n) for n in mesh["images"]], emission=mesh["emission"])
@@ -709,6 +729,7 @@ class CUSTOM_RENDER_PT_blackhole(RenderButtonsPanel, Panel):
              ("mark_y_max", "mark_y_max"), ("curved_space_objects", "Objects in curved space (0/1)"),
              ("curved_space_meshes", "Mesh objects as triangles (0/1)"),
              ("curved_space_mesh_instances", "Linked duplicates as instances (0/1)"),
+             ("curved_space_mesh_refit", "Deforming meshes refit, not rebuilt (0/1)"),
              ("device_shading", "Shade on the GPU (0/1)"), ("render_devices", "GPUs to render on"))
 
     def draw(self, context):
@@ -739,6 +760,7 @@ EXTRA_PROPS = [
     ("curved_space_objects", bpy.props.FloatProperty(name="curved_space_objects", default=0)),
     ("curved_space_meshes", bpy.props.FloatProperty(name="curved_space_meshes", default=0)),
     ("curved_space_mesh_instances", bpy.props.FloatProperty(name="curved_space_mesh_instances", default=0)),
+    ("curved_space_mesh_refit", bpy.props.FloatProperty(name="curved_space_mesh_refit", default=0)),
     ("device_shading", bpy.props.FloatProperty(name="device_shading", default=0)),
     ("render_devices", bpy.props.FloatProperty(name="render_devices", default=1)),
 ]

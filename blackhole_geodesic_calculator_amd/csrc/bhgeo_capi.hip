@@ -26,6 +26,7 @@
 #include "geodesic_kernels.h"
 #include "prefix_clearance.h"
 #include "mesh_bvh.h"
+#include "mesh_refit.h"
 #include "trace_call.h"
 
 static_assert(BHG_FLAG_HIT_HORIZON == bhg::BHG_FLAG_HIT_HORIZON_, "flag mismatch");
@@ -1101,6 +1102,16 @@ struct bhg_mesh {
     double box[6] = {0, 0, 0, 0, 0, 0};
     double d_min = 0.0, d_max = 0.0;
     uint64_t serial = 0;      // its entry in live_meshes, which an instance set checks before it trusts its pointer
+    // the refit: what _create leaves on the device for it beside the view's arrays, and what it keeps count of
+    int32_t n_vertices = 0;
+    bool has_normals = false;
+    const int32_t *slot_vert = nullptr;     // in d, [nt][3]: the caller's vertex indices of the triangle in each leaf slot
+    const int32_t *level_nodes = nullptr;   // in d, [n_inner]: the inner nodes grouped by level (mesh_bvh.h, inner_levels)
+    std::vector<int32_t> level_off;         // [BVH_MAX_DEPTH + 2]
+    int32_t n_inner = 0;
+    char *d_refit = nullptr;  // the first refit's allocation, kept: summary | area [nn] | staging of host vertices and normals
+    uint64_t generation = 0;  // +1 per successful refit
+    double area_build = 0.0, area_now = 0.0;
 };
 
 // K rigid placements of one mesh: the device records, and what the host works out from them in O(K)
@@ -1109,6 +1120,7 @@ struct bhg_mesh_instances {
     int device = 0;               // ctx's (the set may be destroyed after its context)
     const bhg_mesh *mesh = nullptr;
     uint64_t mesh_serial = 0;
+    uint64_t mesh_generation = 0; // the mesh's at _create / _set: the world boxes come from the local box of that generation
     int32_t n = 0;
     double *d_rec = nullptr;      // [n][BHG_MESH_INSTANCE_DOUBLES_]
     double box[6] = {0, 0, 0, 0, 0, 0};     // the union of the world boxes
@@ -1744,19 +1756,26 @@ int bhg_mesh_create(bhg_context *c, const double *vertices, size_t n_vertices, c
     bhg::HostBvh t;
     bhg::build_bvh(vertices, triangles, n_triangles, leaf_size, t);
     const size_t nn = t.node_skip.size(), nt = n_triangles;
-    // the device image: boxes | triangles (v0, e1, e2) | vertex normals | skip | first | count | order | slot
+    // the refit's schedule: the inner nodes by level
+    std::vector<int32_t> level_nodes, level_off;
+    if (!bhg::inner_levels(t.node_skip.data(), t.node_count.data(), nn, level_nodes, level_off))
+        return fail(BHG_E_INVALID, "bhg_mesh_create: the tree is deeper than BVH_MAX_DEPTH");
+    // the device image: boxes | triangles (v0, e1, e2) | vertex normals | skip | first | count | order | slot | and for the refit
+    // the vertex indices per slot | the inner nodes by level
     const size_t b_box = nn * 6 * sizeof(double), b_tri = nt * 9 * sizeof(double), b_nrm = vertex_normals ? b_tri : 0,
-                 b_node = (nn * sizeof(int32_t) + 7) & ~size_t(7), b_idx = (nt * sizeof(int32_t) + 7) & ~size_t(7);
+                 b_node = (nn * sizeof(int32_t) + 7) & ~size_t(7), b_idx = (nt * sizeof(int32_t) + 7) & ~size_t(7),
+                 b_sv = (nt * 3 * sizeof(int32_t) + 7) & ~size_t(7), b_lv = (level_nodes.size() * sizeof(int32_t) + 7) & ~size_t(7);
     const size_t o_tri = b_box, o_nrm = o_tri + b_tri, o_skip = o_nrm + b_nrm, o_first = o_skip + b_node, o_count = o_first + b_node,
-                 o_order = o_count + b_node, o_slot = o_order + b_idx, total = o_slot + b_idx;
+                 o_order = o_count + b_node, o_slot = o_order + b_idx, o_sv = o_slot + b_idx, o_lv = o_sv + b_sv, total = o_lv + b_lv;
     std::vector<char> img(total, 0);
     std::memcpy(img.data(), t.node_box.data(), b_box);
     double *tri = (double *)(img.data() + o_tri), *nrm = (double *)(img.data() + o_nrm);
-    int32_t *slot_of = (int32_t *)(img.data() + o_slot);
+    int32_t *slot_of = (int32_t *)(img.data() + o_slot), *slot_vert = (int32_t *)(img.data() + o_sv);
     double d_max = 0.0;
     for (size_t k = 0; k < nt; k++) {
         const int32_t f = t.tri_order[k];
         slot_of[f] = (int32_t)k;
+        for (int j = 0; j < 3; j++) slot_vert[k * 3 + j] = triangles[(size_t)f * 3 + j];
         const double *v0 = vertices + (size_t)triangles[(size_t)f * 3] * 3, *v1 = vertices + (size_t)triangles[(size_t)f * 3 + 1] * 3,
                      *v2 = vertices + (size_t)triangles[(size_t)f * 3 + 2] * 3;
         for (int q = 0; q < 3; q++) {
@@ -1773,6 +1792,7 @@ int bhg_mesh_create(bhg_context *c, const double *vertices, size_t n_vertices, c
     std::memcpy(img.data() + o_first, t.node_first.data(), nn * sizeof(int32_t));
     std::memcpy(img.data() + o_count, t.node_count.data(), nn * sizeof(int32_t));
     std::memcpy(img.data() + o_order, t.tri_order.data(), nt * sizeof(int32_t));
+    if (!level_nodes.empty()) std::memcpy(img.data() + o_lv, level_nodes.data(), level_nodes.size() * sizeof(int32_t));
     bhg_mesh *m = new (std::nothrow) bhg_mesh;
     if (!m) return fail(BHG_E_NOMEM, "out of host memory");
     hipError_t e = hipMalloc((void **)&m->d, total);
@@ -1805,6 +1825,13 @@ int bhg_mesh_create(bhg_context *c, const double *vertices, size_t n_vertices, c
     v.tri_slot = (const int32_t *)(m->d + o_slot);
     v.n_nodes = (int32_t)nn;
     v.n_tris = (int32_t)nt;
+    m->n_vertices = (int32_t)n_vertices;
+    m->has_normals = vertex_normals != nullptr;
+    m->slot_vert = (const int32_t *)(m->d + o_sv);
+    m->level_nodes = (const int32_t *)(m->d + o_lv);
+    m->level_off = level_off;
+    m->n_inner = (int32_t)level_nodes.size();
+    m->area_build = m->area_now = bhg::area_sum(t.node_box.data(), nn);
     {
         std::lock_guard<std::mutex> lock(live_meshes_lock);
         m->serial = live_meshes_next++;
@@ -1824,6 +1851,7 @@ void bhg_mesh_destroy(bhg_mesh *m)
     {
         DeviceGuard g(m->device);
         if (m->d) (void)hipFree(m->d);
+        if (m->d_refit) (void)hipFree(m->d_refit);
     }
     delete m;
 }
@@ -1834,6 +1862,191 @@ int bhg_mesh_info(const bhg_mesh *m, int64_t *n_nodes, int32_t *depth, double bo
     if (n_nodes) *n_nodes = m->n_nodes;
     if (depth) *depth = m->depth;
     if (box) std::memcpy(box, m->box, sizeof(m->box));
+    return BHG_OK;
+}
+
+// --- the refit of a mesh's tree -----------------------------------------------------------------------
+
+}  // extern "C"
+
+namespace {
+
+// what both refit calls refuse before the device is touched
+int refit_check(const bhg_context *c, const bhg_mesh *m, const double *vertices, const double *vertex_normals)
+{
+    if (!m) return fail(BHG_E_INVALID, "mesh is NULL");
+    if (!vertices) return fail(BHG_E_INVALID, "mesh refit: vertices is NULL");
+    if (vertex_normals && !m->has_normals)
+        return fail(BHG_E_INVALID, "mesh refit: vertex_normals given to a mesh that was created without them");
+    if (!vertex_normals && m->has_normals)
+        return fail(BHG_E_INVALID, "mesh refit: vertex_normals is NULL for a mesh that was created with them");
+    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
+    if (m->device != c->device) return fail(BHG_E_INVALID, "the mesh lives on another device than the context");
+    return BHG_OK;
+}
+
+// the refit's own device memory, allocated by the first refit and kept: summary | area [nn] | vertices [nv][3] | normals [nv][3]
+// (the last two stage the host form's arrays)
+struct RefitScratch {
+    bhg::MeshRefitSummary *summary;
+    double *area, *vertices, *normals;
+};
+
+int refit_scratch(bhg_mesh *m, RefitScratch &r)
+{
+    const size_t b_sum = (sizeof(bhg::MeshRefitSummary) + 7) & ~size_t(7), b_area = (size_t)m->n_nodes * sizeof(double),
+                 b_v = (size_t)m->n_vertices * 3 * sizeof(double);
+    if (!m->d_refit) HIP_TRY(hipMalloc((void **)&m->d_refit, b_sum + b_area + b_v * (m->has_normals ? 2 : 1)));
+    r.summary = (bhg::MeshRefitSummary *)m->d_refit;
+    r.area = (double *)(m->d_refit + b_sum);
+    r.vertices = (double *)(m->d_refit + b_sum + b_area);
+    r.normals = m->has_normals ? (double *)(m->d_refit + b_sum + b_area + b_v) : nullptr;
+    return BHG_OK;
+}
+
+// d_v, d_n: device arrays.  scan: they have not been looked at yet (the device form).  The device is c's and current.
+int refit_run(bhg_context *c, bhg_mesh *m, const RefitScratch &r, const double *d_v, const double *d_n, bool scan, hipStream_t s)
+{
+    bhg::MeshRefitArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.vertices = d_v;
+    a.normals = d_n;
+    a.n_vertices = m->n_vertices;
+    a.n_tris = m->view.n_tris;
+    a.n_nodes = m->view.n_nodes;
+    a.n_inner = m->n_inner;
+    a.slot_vert = m->slot_vert;
+    a.node_skip = m->view.node_skip;
+    a.node_first = m->view.node_first;
+    a.node_count = m->view.node_count;
+    a.level_nodes = m->level_nodes;
+    std::memcpy(a.level_off, m->level_off.data(), sizeof(a.level_off));
+    a.node_box = const_cast<double *>(m->view.node_box);
+    a.tri = const_cast<double *>(m->view.tri);
+    a.tri_normals = const_cast<double *>(m->view.tri_normals);
+    a.area = r.area;
+    a.summary = r.summary;
+    bhg::MeshRefitSummary sum;
+    // nothing of the mesh is written before everything queued on the context's stream and on s is done
+    if (c->stream != s) HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemsetAsync(r.summary, 0, sizeof(sum), s));
+    if (scan) {
+        HIP_TRY(bhg::launch_mesh_refit_scan(a, s));
+        HIP_TRY(hipMemcpyAsync(&sum, r.summary, sizeof(sum), hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    if (scan && (sum.nonfinite & 1u)) return fail(BHG_E_INVALID, "mesh: every vertex must be finite");
+    if (scan && (sum.nonfinite & 2u)) return fail(BHG_E_INVALID, "mesh: every vertex normal must be finite");
+    HIP_TRY(bhg::launch_mesh_refit(a, s));
+    HIP_TRY(hipMemcpyAsync(&sum, r.summary, sizeof(sum), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    // box, d_min, d_max: bhg_mesh_create's formulas (the square root is monotone: the largest |v| is the root of the largest |v|^2)
+    std::memcpy(m->box, sum.box, sizeof(m->box));
+    double d2 = 0.0;
+    for (int q = 0; q < 3; q++) {
+        const double gap = std::max(std::max(m->box[q], -m->box[3 + q]), 0.0);
+        d2 += gap * gap;
+    }
+    double far2;
+    std::memcpy(&far2, &sum.d2_max, sizeof(far2));
+    m->d_min = std::sqrt(d2) * (1.0 - 1e-14);
+    m->d_max = std::sqrt(far2) * (1.0 + 1e-14);
+    m->area_now = sum.area;
+    m->generation++;
+    return BHG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bhg_mesh_refit(bhg_context *c, bhg_mesh *m, const double *vertices, const double *vertex_normals)
+{
+    BHG_TRY(refit_check(c, m, vertices, vertex_normals));
+    const size_t n3 = (size_t)m->n_vertices * 3;
+    for (size_t i = 0; i < n3; i++)
+        if (!std::isfinite(vertices[i])) return fail(BHG_E_INVALID, "mesh: every vertex must be finite");
+    if (vertex_normals)
+        for (size_t i = 0; i < n3; i++)
+            if (!std::isfinite(vertex_normals[i])) return fail(BHG_E_INVALID, "mesh: every vertex normal must be finite");
+    ENTER_DEVICE(c->device);
+    RefitScratch r;
+    BHG_TRY(refit_scratch(m, r));
+    // (the staging arrays are the refit's own: a refit is blocking, so no earlier one still reads them)
+    HIP_TRY(hipMemcpyAsync(r.vertices, vertices, n3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (vertex_normals) HIP_TRY(hipMemcpyAsync(r.normals, vertex_normals, n3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    return refit_run(c, m, r, r.vertices, r.normals, false, c->stream);
+}
+
+int bhg_mesh_refit_device(bhg_context *c, bhg_mesh *m, const double *d_vertices, const double *d_vertex_normals, void *stream)
+{
+    BHG_TRY(refit_check(c, m, d_vertices, d_vertex_normals));
+    ENTER_DEVICE(c->device);
+    RefitScratch r;
+    BHG_TRY(refit_scratch(m, r));
+    return refit_run(c, m, r, d_vertices, d_vertex_normals, true, (hipStream_t)stream);
+}
+
+int bhg_mesh_refit_info(const bhg_mesh *m, uint64_t *generation, double *area_build, double *area_now)
+{
+    if (!m) return fail(BHG_E_INVALID, "mesh is NULL");
+    if (generation) *generation = m->generation;
+    if (area_build) *area_build = m->area_build;
+    if (area_now) *area_now = m->area_now;
+    return BHG_OK;
+}
+
+int bhg_mesh_range(const bhg_mesh *m, double *d_min, double *d_max)
+{
+    if (!m) return fail(BHG_E_INVALID, "mesh is NULL");
+    if (d_min) *d_min = m->d_min;
+    if (d_max) *d_max = m->d_max;
+    return BHG_OK;
+}
+
+int bhg_mesh_bvh_refit_host(const double *vertices, size_t n_vertices, const int32_t *triangles, size_t n_triangles,
+                            const int32_t *node_skip, const int32_t *node_first, const int32_t *node_count, const int32_t *tri_order,
+                            size_t n_nodes, double *node_box, double *area)
+{
+    if (const char *why = bhg::mesh_refusal(vertices, n_vertices, triangles, n_triangles, 1)) return fail(BHG_E_INVALID, why);
+    if (const char *why = bhg::topology_refusal(node_skip, node_first, node_count, tri_order, n_nodes, n_triangles))
+        return fail(BHG_E_INVALID, why);
+    if (!node_box) return fail(BHG_E_INVALID, "node_box is NULL");
+    std::vector<int32_t> level_nodes, level_off;
+    if (!bhg::inner_levels(node_skip, node_count, n_nodes, level_nodes, level_off))
+        return fail(BHG_E_INVALID, "mesh topology: the tree is deeper than 32 levels");
+    bhg::fit_boxes(vertices, triangles, node_skip, node_first, node_count, tri_order, n_nodes, node_box);
+    if (area) *area = bhg::area_sum(node_box, n_nodes);
+    return BHG_OK;
+}
+
+int bhg_mesh_refit_schedule_host(const int32_t *node_skip, const int32_t *node_first, const int32_t *node_count,
+                                 const int32_t *tri_order, size_t n_nodes, size_t n_triangles, int32_t *level_nodes,
+                                 int32_t *level_off /* [34] */, size_t cap, size_t *n_inner)
+{
+    if (const char *why = bhg::topology_refusal(node_skip, node_first, node_count, tri_order, n_nodes, n_triangles))
+        return fail(BHG_E_INVALID, why);
+    if (!n_inner) return fail(BHG_E_INVALID, "n_inner is NULL");
+    std::vector<int32_t> nodes, off;
+    if (!bhg::inner_levels(node_skip, node_count, n_nodes, nodes, off))
+        return fail(BHG_E_INVALID, "mesh topology: the tree is deeper than 32 levels");
+    *n_inner = nodes.size();
+    if (nodes.size() > cap) return fail(BHG_E_INVALID, "the tree has more inner nodes than cap (n_triangles - 1 always suffices)");
+    if (!level_off || (!level_nodes && !nodes.empty())) return fail(BHG_E_INVALID, "an output array is NULL");
+    if (!nodes.empty()) std::memcpy(level_nodes, nodes.data(), nodes.size() * sizeof(int32_t));
+    std::memcpy(level_off, off.data(), off.size() * sizeof(int32_t));
+    return BHG_OK;
+}
+
+int bhg_mesh_boxes_host(const bhg_mesh *m, double *node_box, double *tri, size_t cap)
+{
+    if (!m) return fail(BHG_E_INVALID, "mesh is NULL");
+    if (!node_box) return fail(BHG_E_INVALID, "node_box is NULL");
+    if (cap < (size_t)m->n_nodes) return fail(BHG_E_INVALID, "the tree has more nodes than cap (bhg_mesh_info gives n_nodes)");
+    ENTER_DEVICE(m->device);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(node_box, m->view.node_box, (size_t)m->n_nodes * 6 * sizeof(double), hipMemcpyDeviceToHost));
+    if (tri) HIP_TRY(hipMemcpy(tri, m->view.tri, (size_t)m->view.n_tris * 9 * sizeof(double), hipMemcpyDeviceToHost));
     return BHG_OK;
 }
 
@@ -1977,11 +2190,14 @@ int instances_trace_check(const bhg_params *p, const bhg_mesh_instances *inst, d
     return BHG_OK;
 }
 
-int instances_usable(const bhg_context *c, const bhg_mesh_instances *inst)
+// reading: the call traces or shades with the set's world boxes, which a refit of the mesh since the last _set has left stale
+int instances_usable(const bhg_context *c, const bhg_mesh_instances *inst, bool reading = true)
 {
     if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
     if (inst->ctx != c) return fail(BHG_E_INVALID, "mesh instances: the instance set belongs to another context");
     if (!mesh_is_live(inst->mesh, inst->mesh_serial)) return fail(BHG_E_INVALID, "mesh instances: the set's mesh has been destroyed");
+    if (reading && inst->mesh_generation != inst->mesh->generation)
+        return fail(BHG_E_INVALID, "mesh instances: the set's mesh has been refitted, call bhg_mesh_instances_set after bhg_mesh_refit");
     return BHG_OK;
 }
 
@@ -2014,6 +2230,7 @@ int bhg_mesh_instances_create(bhg_context *c, const bhg_mesh *mesh, int32_t n, c
     in->device = c->device;
     in->mesh = mesh;
     in->mesh_serial = mesh->serial;
+    in->mesh_generation = mesh->generation;
     in->n = n;
     const size_t bytes = (size_t)n * bhg::BHG_MESH_INSTANCE_DOUBLES_ * sizeof(double);
     hipError_t e = hipMalloc((void **)&in->d_rec, bytes);
@@ -2038,7 +2255,7 @@ int bhg_mesh_instances_set(bhg_mesh_instances *in, const double *transforms)
 {
     if (!in) return fail(BHG_E_INVALID, "mesh instances: inst is NULL");
     BHG_TRY(mesh_instance_transforms_check(in->n, transforms));
-    BHG_TRY(instances_usable(in->ctx, in));
+    BHG_TRY(instances_usable(in->ctx, in, false));
     ENTER_DEVICE(in->ctx->device);
     const int k = in->last < 0 ? 1 : in->last ^ 1;
     const size_t bytes = (size_t)in->n * bhg::BHG_MESH_INSTANCE_DOUBLES_ * sizeof(double);
@@ -2051,6 +2268,7 @@ int bhg_mesh_instances_set(bhg_mesh_instances *in, const double *transforms)
     HIP_TRY(hipMemcpyAsync(in->d_rec, in->h_rec[k], bytes, hipMemcpyHostToDevice, s));
     HIP_TRY(hipEventRecord(in->ev_copy[k], s));
     in->last = k;
+    in->mesh_generation = in->mesh->generation;
     std::memcpy(in->box, box, sizeof(box));
     in->d_min = d_min;
     in->d_max = d_max;

@@ -202,6 +202,7 @@ struct Shard {
     bhg_mesh *mesh = nullptr;
     DevBuf m_rgb, m_uv, m_slot, m_img[BHG_MESH_TEXTURES_MAX], tri, bary;
     bool mesh_ready = false;        // mesh and the material buffers hold the frame's current mesh
+    bool mesh_refit = false;        // ... but for the vertices (bhg_frame_refit_mesh): the next render refits (or rebuilds) the tree
     // the mesh's instances (bhg_frame_set_mesh_instances): this device's set over mesh, the colours, the trace's third record
     bhg_mesh_instances *inst = nullptr;
     int32_t inst_n = 0;
@@ -259,6 +260,7 @@ struct bhg_frame {
         int32_t img_w[BHG_MESH_TEXTURES_MAX] = {}, img_h[BHG_MESH_TEXTURES_MAX] = {};
         int32_t n_tex = 0;
         double emission = 0.0;
+        double rebuild_ratio = 0.0;                 // of the latest bhg_frame_refit_mesh
     };
     bool meshed = false;            // bhg_frame_set_mesh; false: no mesh, the plain render
     Mesh mesh;
@@ -414,7 +416,7 @@ void release_shard_mesh(Shard &s)
     s.mesh = nullptr;
     for (DevBuf *b : {&s.m_rgb, &s.m_uv, &s.m_slot, &s.tri, &s.bary}) b->release();
     for (DevBuf &b : s.m_img) b.release();
-    s.mesh_ready = false;
+    s.mesh_ready = s.mesh_refit = false;
 }
 
 // the frame's mesh on this shard's device: the tree is built by bhg_mesh_create, once per device (mesh_bvh.h hands its tree to
@@ -439,6 +441,39 @@ int upload_shard_mesh(bhg_frame *f, Shard &s)
     for (int j = 0; j < m.n_tex; j++) BHG_TRY(up(s.m_img[j], m.img[j].data(), m.img[j].size() * sizeof(float)));
     HIP_TRY(hipStreamSynchronize(s.stream));
     s.mesh_ready = true;
+    s.mesh_refit = false;
+    return BHG_OK;
+}
+
+// New vertices into the shard's mesh (bhg_frame_refit_mesh): the tree is refitted on the device; past the
+// rebuild ratio this device builds it anew from the held triangles.  The material's buffers stay as they are.  An instance set
+// over the mesh is set again (a rebuilt mesh: made again) by upload_shard_instances, which the render runs next.
+int refit_shard_mesh(bhg_frame *f, Shard &s)
+{
+    const bhg_frame::Mesh &m = f->mesh;
+    const double *normals = m.normals.empty() ? nullptr : m.normals.data();
+    const double ratio = m.rebuild_ratio;
+    HIP_TRY(hipSetDevice(s.device));
+    HIP_TRY(hipStreamSynchronize(s.stream));    // (no kernel of an earlier render still reads the mesh)
+    bool rebuild = ratio > 0.0 && ratio <= 1.0;         // (a ratio of 1 or below: always)
+    if (!rebuild) {
+        BHG_TRY(bhg_mesh_refit(s.ctx, s.mesh, m.vertices.data(), normals));
+        double built = 0.0, now = 0.0;
+        BHG_TRY(bhg_mesh_refit_info(s.mesh, nullptr, &built, &now));
+        rebuild = ratio > 0.0 && built > 0.0 && now > ratio * built;
+    }
+    if (rebuild) {
+        release_shard_instances(s);     // (a set does not outlive its mesh)
+        bhg_mesh_destroy(s.mesh);
+        s.mesh = nullptr;
+        s.mesh_ready = false;
+        BHG_TRY(bhg_mesh_create(s.ctx, m.vertices.data(), m.vertices.size() / 3, m.triangles.data(), m.triangles.size() / 3, normals,
+                                m.leaf_size, &s.mesh));
+        s.mesh_ready = true;
+    }
+    HIP_TRY(hipSetDevice(s.device));
+    s.inst_ready = false;
+    s.mesh_refit = false;
     return BHG_OK;
 }
 
@@ -931,6 +966,33 @@ try {
     return host_exception();
 }
 
+int bhg_frame_refit_mesh(bhg_frame *f, const double *vertices, const double *vertex_normals, double rebuild_ratio)
+try {
+    if (!f) return fail(BHG_E_INVALID, "frame is NULL");
+    if (!f->meshed) return fail(BHG_E_INVALID, "mesh refit: the frame holds no mesh (bhg_frame_set_mesh first)");
+    if (!vertices) return fail(BHG_E_INVALID, "mesh refit: vertices is NULL");
+    bhg_frame::Mesh &m = f->mesh;
+    if (vertex_normals && m.normals.empty())
+        return fail(BHG_E_INVALID, "mesh refit: vertex_normals given to a mesh that was created without them");
+    if (!vertex_normals && !m.normals.empty())
+        return fail(BHG_E_INVALID, "mesh refit: vertex_normals is NULL for a mesh that was created with them");
+    if (std::isnan(rebuild_ratio)) return fail(BHG_E_INVALID, "mesh refit: rebuild_ratio is NaN");
+    const size_t n3 = m.vertices.size();
+    for (size_t i = 0; i < n3; i++)
+        if (!std::isfinite(vertices[i])) return fail(BHG_E_INVALID, "mesh: every vertex must be finite");
+    if (vertex_normals)
+        for (size_t i = 0; i < n3; i++)
+            if (!std::isfinite(vertex_normals[i])) return fail(BHG_E_INVALID, "mesh: every vertex normal must be finite");
+    std::copy(vertices, vertices + n3, m.vertices.begin());
+    if (vertex_normals) std::copy(vertex_normals, vertex_normals + n3, m.normals.begin());
+    m.rebuild_ratio = rebuild_ratio;
+    // a device that holds the mesh refits it at the next render; one that does not yet uploads the new vertices anyway
+    for (auto &s : f->sh) s.mesh_refit = s.mesh_ready;
+    return BHG_OK;
+} catch (...) {
+    return host_exception();
+}
+
 int bhg_frame_set_mesh_instances(bhg_frame *f, int32_t n, const double *transforms, const float *inst_rgb)
 try {
     if (!f) return fail(BHG_E_INVALID, "frame is NULL");
@@ -1033,6 +1095,7 @@ try {
         if (!s.scene_ready) BHG_TRY(upload_shard_scene(f, s));
         if (textured && !s.otex_ready) BHG_TRY(upload_shard_textures(f, s));
         if (meshed && !s.mesh_ready) BHG_TRY(upload_shard_mesh(f, s));
+        if (meshed && s.mesh_refit) BHG_TRY(refit_shard_mesh(f, s));
         if (instanced && !s.inst_ready) BHG_TRY(upload_shard_instances(f, s));
     }
     for (size_t r = 0; r < world; r++) {
@@ -1324,6 +1387,14 @@ try {
     return build_root(f);
 } catch (...) {
     return host_exception();
+}
+
+int bhg_frame_mesh_refit_info(const bhg_frame *f, int32_t shard, uint64_t *generation, double *area_build, double *area_now)
+{
+    if (!f) return fail(BHG_E_INVALID, "frame is NULL");
+    if (shard < 0 || (size_t)shard >= f->sh.size()) return fail(BHG_E_INVALID, "shard must be in [0, the frame's devices)");
+    if (!f->sh[(size_t)shard].mesh) return fail(BHG_E_INVALID, "this device holds no mesh (none set, or no render since)");
+    return bhg_mesh_refit_info(f->sh[(size_t)shard].mesh, generation, area_build, area_now);
 }
 
 int bhg_frame_info(const bhg_frame *f, int64_t out[8])

@@ -50,6 +50,121 @@ inline const char *mesh_refusal(const double *vertices, size_t nv, const int32_t
     return nullptr;
 }
 
+// The boxes of a tree whose topology stands (what the builder ends with, and all a refit does).  A leaf's box
+// is the exact min / max over its triangles' vertices, an inner node's the union of its two children's, children before parents;
+// then every box is widened outward by BVH_BOX_ULPS ulps of its own largest magnitude: a parent's magnitude is at least its
+// children's, so a widened child stays inside its widened parent.  The refit kernels (mesh_refit.hip) do these operations on
+// these operands in this order: the same bits.
+inline void fit_boxes(const double *V, const int32_t *F, const int32_t *node_skip, const int32_t *node_first, const int32_t *node_count,
+                      const int32_t *order, size_t nn, double *node_box)
+{
+    for (size_t i = nn; i-- > 0;) {
+        double *b = &node_box[i * 6];
+        if (node_count[i] > 0) {
+            for (int c = 0; c < 3; c++) {
+                b[c] = INFINITY;
+                b[3 + c] = -INFINITY;
+            }
+            for (int32_t k = 0; k < node_count[i]; k++) {
+                const int32_t t = order[(size_t)node_first[i] + k];
+                for (int j = 0; j < 3; j++)
+                    for (int c = 0; c < 3; c++) {
+                        const double x = V[(size_t)F[(size_t)t * 3 + j] * 3 + c];
+                        b[c] = std::min(b[c], x);
+                        b[3 + c] = std::max(b[3 + c], x);
+                    }
+            }
+        } else {
+            const size_t l = i + 1, r = (size_t)node_skip[l];
+            for (int c = 0; c < 3; c++) {
+                b[c] = std::min(node_box[l * 6 + c], node_box[r * 6 + c]);
+                b[3 + c] = std::max(node_box[l * 6 + 3 + c], node_box[r * 6 + 3 + c]);
+            }
+        }
+    }
+    for (size_t i = 0; i < nn; i++) {
+        double *b = &node_box[i * 6];
+        double mag = 0.0;
+        for (int c = 0; c < 6; c++) mag = std::max(mag, std::fabs(b[c]));
+        const double w = BVH_BOX_ULPS * 2.220446049250313e-16 * std::max(mag, 2.2250738585072014e-308);
+        for (int c = 0; c < 3; c++) {
+            b[c] -= w;
+            b[3 + c] += w;
+        }
+    }
+}
+
+// The tree's area sum: the sum over all nodes of dx dy + dy dz + dz dx of the widened box, the figure a
+// refitted tree's degradation is read from.  Reduced in one fixed order, which the device's reduction (mesh_refit.hip) restates:
+// BVH_AREA_LANES partial sums, lane l over the nodes l, l + BVH_AREA_LANES, ... in rising order, then a halving tree over the lanes.
+constexpr int BVH_AREA_LANES = 256;
+inline double box_area(const double *b)
+{
+    const double dx = b[3] - b[0], dy = b[4] - b[1], dz = b[5] - b[2];
+    return dx * dy + dy * dz + dz * dx;
+}
+inline double area_sum(const double *node_box, size_t nn)
+{
+    double lane[BVH_AREA_LANES];
+    for (int l = 0; l < BVH_AREA_LANES; l++) lane[l] = 0.0;
+    for (size_t i = 0; i < nn; i++) lane[i % BVH_AREA_LANES] += box_area(node_box + i * 6);
+    for (int s = BVH_AREA_LANES / 2; s > 0; s >>= 1)
+        for (int l = 0; l < s; l++) lane[l] += lane[l + s];
+    return lane[0];
+}
+
+// nullptr when (node_skip, node_first, node_count, tri_order) is a tree of build_bvh's kind over nt triangles that fit_boxes and
+// inner_levels may walk, else the reason: every index in range, skip links forward, both children of an inner node present, every
+// leaf slot in exactly one leaf
+inline const char *topology_refusal(const int32_t *node_skip, const int32_t *node_first, const int32_t *node_count,
+                                    const int32_t *tri_order, size_t nn, size_t nt)
+{
+    if (!node_skip || !node_first || !node_count || !tri_order) return "mesh topology: an array is NULL";
+    if (nn == 0 || nn > 0x7FFFFFFFull || nt == 0 || nt > 0x7FFFFFFFull) return "mesh topology: n_nodes and n_triangles must be in [1, 2^31 - 1]";
+    size_t next_slot = 0;
+    for (size_t i = 0; i < nn; i++) {
+        if (node_skip[i] <= (int64_t)i || (size_t)node_skip[i] > nn) return "mesh topology: node_skip must lie in (i, n_nodes]";
+        if (node_count[i] < 0) return "mesh topology: node_count must be >= 0";
+        if (node_count[i] > 0) {
+            // (pre-order: the leaves hold the slots in rising order, without gaps)
+            if (node_first[i] < 0 || (size_t)node_first[i] != next_slot || (size_t)node_count[i] > nt - next_slot)
+                return "mesh topology: the leaves must hold the slots 0 .. n_triangles - 1 in order";
+            if ((size_t)node_skip[i] != i + 1) return "mesh topology: a leaf's node_skip must be i + 1";
+            next_slot += (size_t)node_count[i];
+        } else {
+            if (i + 2 >= nn || (size_t)node_skip[i + 1] >= nn || node_skip[(size_t)node_skip[i + 1]] != node_skip[i])
+                return "mesh topology: an inner node must have two children that end where it ends";
+        }
+    }
+    if (next_slot != nt) return "mesh topology: the leaves must hold the slots 0 .. n_triangles - 1 in order";
+    for (size_t k = 0; k < nt; k++)
+        if (tri_order[k] < 0 || (size_t)tri_order[k] >= nt) return "mesh topology: tri_order must lie in [0, n_triangles)";
+    return nullptr;
+}
+
+// The bottom-up schedule of a refit: the inner nodes grouped by level -- level_nodes[level_off[d] ..
+// level_off[d + 1]) are the inner nodes d levels below the root, in rising index order -- so that the levels are walked deepest
+// first and the nodes of one level in any order.  false: the tree is deeper than BVH_MAX_DEPTH (not one of build_bvh's).
+inline bool inner_levels(const int32_t *node_skip, const int32_t *node_count, size_t nn, std::vector<int32_t> &level_nodes,
+                         std::vector<int32_t> &level_off)
+{
+    std::vector<int32_t> depth(nn, 0);
+    std::vector<size_t> width(BVH_MAX_DEPTH + 1, 0);
+    for (size_t i = 0; i < nn; i++) {
+        if (node_count[i] > 0) continue;
+        if (depth[i] >= BVH_MAX_DEPTH) return false;
+        depth[i + 1] = depth[(size_t)node_skip[i + 1]] = depth[i] + 1;
+        width[(size_t)depth[i]]++;
+    }
+    level_off.assign(BVH_MAX_DEPTH + 2, 0);
+    for (int d = 0; d <= BVH_MAX_DEPTH; d++) level_off[(size_t)d + 1] = level_off[(size_t)d] + (int32_t)width[(size_t)d];
+    level_nodes.assign((size_t)level_off[BVH_MAX_DEPTH + 1], 0);
+    std::vector<int32_t> at(level_off.begin(), level_off.end() - 1);
+    for (size_t i = 0; i < nn; i++)
+        if (node_count[i] == 0) level_nodes[(size_t)at[(size_t)depth[i]]++] = (int32_t)i;
+    return true;
+}
+
 // the mesh has passed mesh_refusal
 inline void build_bvh(const double *V, const int32_t *F, size_t nt, int32_t leaf_size, HostBvh &out)
 {
@@ -109,45 +224,17 @@ inline void build_bvh(const double *V, const int32_t *F, size_t nt, int32_t leaf
         stack[sp++] = Range{mid, r.hi, r.depth + 1};   // the right child, after the whole left subtree
         stack[sp++] = Range{r.lo, mid, r.depth + 1};
     }
-    // skip links and boxes, children before parents (pre-order: every child has a larger index than its parent)
+    // skip links, children before parents (pre-order: every child has a larger index than its parent); then the boxes
     const size_t nn = out.node_skip.size();
     for (size_t i = nn; i-- > 0;) {
-        double *b = &out.node_box[i * 6];
         if (out.node_count[i] > 0) {
             out.node_skip[i] = (int32_t)(i + 1);
-            for (int c = 0; c < 3; c++) {
-                b[c] = INFINITY;
-                b[3 + c] = -INFINITY;
-            }
-            for (int32_t k = 0; k < out.node_count[i]; k++) {
-                const int32_t t = order[(size_t)out.node_first[i] + k];
-                for (int j = 0; j < 3; j++)
-                    for (int c = 0; c < 3; c++) {
-                        const double x = V[(size_t)F[(size_t)t * 3 + j] * 3 + c];
-                        b[c] = std::min(b[c], x);
-                        b[3 + c] = std::max(b[3 + c], x);
-                    }
-            }
         } else {
             const size_t l = i + 1, r = (size_t)out.node_skip[l];
             out.node_skip[i] = out.node_skip[r];
-            for (int c = 0; c < 3; c++) {
-                b[c] = std::min(out.node_box[l * 6 + c], out.node_box[r * 6 + c]);
-                b[3 + c] = std::max(out.node_box[l * 6 + 3 + c], out.node_box[r * 6 + 3 + c]);
-            }
         }
     }
-    // widen: a parent's magnitude is at least its children's, so a widened child stays inside its widened parent
-    for (size_t i = 0; i < nn; i++) {
-        double *b = &out.node_box[i * 6];
-        double mag = 0.0;
-        for (int c = 0; c < 6; c++) mag = std::max(mag, std::fabs(b[c]));
-        const double w = BVH_BOX_ULPS * 2.220446049250313e-16 * std::max(mag, 2.2250738585072014e-308);
-        for (int c = 0; c < 3; c++) {
-            b[c] -= w;
-            b[3 + c] += w;
-        }
-    }
+    fit_boxes(V, F, out.node_skip.data(), out.node_first.data(), out.node_count.data(), order.data(), nn, out.node_box.data());
 }
 
 }  // namespace bhg

@@ -392,6 +392,18 @@ class DeviceFrame:
         if T is not None:
             self.mesh_instances = _ffi.MeshInstances(self.mesh, T)
 
+    def refit_mesh(self, vertices, vertex_normals=None):
+        """New vertex positions (and vertex normals) for the held mesh, its tree refitted on the device (Mesh.refit; DESIGN.md
+        section 22): numpy arrays, or float64 tensors on the frame's device.  Held instances are set again with their
+        transforms, so the next trace is current.  The frame's own stream is waited for first: no trace still reads the mesh."""
+        if self.mesh is None:
+            raise ValueError("refit_mesh() wants a mesh: set_mesh() first")
+        torch.cuda.current_stream(self.dev).synchronize()
+        self.mesh.refit(vertices, vertex_normals, stream=self._stream())
+        self._traced = None
+        if self.mesh_instances is not None:
+            self.mesh_instances.set(self.mesh_instances.transforms)
+
     def _mesh_check(self):
         for name, on in (("object spheres", self.spheres is not None and len(self.spheres) > 0),
                          ("disk layers", self.disk_layers is not None), ("redshift", self.redshift is not None),

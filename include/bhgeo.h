@@ -76,7 +76,10 @@ extern "C" {
                                   struct bhg_mesh_material, BHG_MESH_TEXTURES_MAX: textured, emissive meshes, meshes on bhg_frame);
                                   BHG_MESH_INSTANCES (bhg_mesh_instances_create / _set / _destroy / _info, bhg_mesh_instance_box_host,
                                   bhg_trace_mesh_instances_device, bhg_trace_mesh_instances, bhg_shade_mesh_instances_device, bhg_frame_set_mesh_instances, struct bhg_mesh_instances,
-                                  BHG_MESH_INSTANCES_MAX: rigid placements of one mesh, moved without a rebuild).
+                                  BHG_MESH_INSTANCES_MAX: rigid placements of one mesh, moved without a rebuild);
+                                  BHG_MESH_REFIT (bhg_mesh_refit, bhg_mesh_refit_device, bhg_mesh_refit_info, bhg_mesh_bvh_refit_host,
+                                  bhg_mesh_refit_schedule_host, bhg_mesh_boxes_host, bhg_mesh_range, bhg_frame_refit_mesh, bhg_frame_mesh_refit_info: new vertices into a built mesh, its tree
+                                  refitted on the device).
                                9: redshift -- bhg_redshift_device / _host, bhg_shade_scene_redshift_device, bhg_frame_set_redshift,
                                   bhg_redshift_size, struct bhg_redshift;
                                   nothing of ABI 8 changed.
@@ -1126,6 +1129,66 @@ int bhg_shade_mesh_instances_device(bhg_context *ctx, const double *d_end, const
  * turns them off too.  Refused, the frame left as it was: a frame without a mesh; what bhg_mesh_instances_create refuses of n and
  * the transforms; a non-finite inst_rgb.  bhg_frame_render's "a mesh does not go with ..." cases hold as they are. */
 int bhg_frame_set_mesh_instances(bhg_frame *frame, int32_t n, const double *transforms, const float *inst_rgb);
+
+/* --- deforming meshes: new vertices into a built mesh, its tree refitted on the device (within ABI 10) ----
+ * A refit gives a mesh new vertex positions (and vertex normals).  n_vertices and the triangles are the mesh's own: the tree's
+ * topology, the leaf order and the skip links stay, the per-slot triangle records and every box are written anew by kernels, and
+ * nothing is built, allocated (after the first refit) or uploaded but the vertices.  Every box is the exact min / max over what
+ * lies below it, widened by the builder's rule, so it contains its triangles as a freshly built tree's boxes do; and since the
+ * tree only accelerates the hit rule above, a trace or shade of the refitted mesh gives the bits of one on a mesh created fresh
+ * from the same vertices.  What a refit cannot keep is the tree's QUALITY: boxes of a tree split for other positions overlap
+ * more.  bhg_mesh_refit_info reports the tree's area sum -- the sum over all nodes of dx dy + dy dz + dz dx of the widened box,
+ * in one fixed order -- as it was at creation (area_build, from the host's tree) and as the last refit left it (area_now); their
+ * ratio is the figure to decide a rebuild (bhg_mesh_destroy + bhg_mesh_create) by.  area_build is 0 only when every product
+ * underflows (a mesh whose vertices all lie at the origin); the ratio is then not formed and says nothing.  generation is 0 at
+ * creation and +1 per successful refit.
+ * Both calls are blocking: they wait for everything queued on the context's stream and on `stream` before the first write to the
+ * mesh, and for their own work before they return; box, d_min and d_max of the mesh are then those bhg_mesh_create would set.
+ * Ordering against kernels that read the mesh on OTHER streams is the caller's job, as for any device buffer the caller writes.
+ * bhg_mesh_refit takes host arrays and works on the context's stream; bhg_mesh_refit_device takes device arrays -- vertices
+ * deformed on the GPU -- which are scanned for non-finite values by a first device pass before anything is written.
+ * Refused (BHG_E_INVALID, the message names the field), the mesh untouched: a NULL mesh or vertices; a mesh of another context's
+ * device; a non-finite vertex or normal; normals given to a mesh created without them, or omitted for a mesh created with them.
+ * An instance set records its mesh's generation at _create and _set (its world boxes come from the mesh's local box): every trace
+ * or shade with a set whose mesh has been refitted since is refused before anything is launched, "call bhg_mesh_instances_set
+ * after bhg_mesh_refit"; _set, with the same transforms or others, makes the set current. */
+#define BHG_MESH_REFIT 1
+int bhg_mesh_refit(bhg_context *ctx, bhg_mesh *mesh, const double *vertices /* host [nv][3] */,
+                   const double *vertex_normals /* host [nv][3], or NULL */);
+int bhg_mesh_refit_device(bhg_context *ctx, bhg_mesh *mesh, const double *d_vertices, const double *d_vertex_normals, void *stream);
+/* any output may be NULL */
+int bhg_mesh_refit_info(const bhg_mesh *mesh, uint64_t *generation, double *area_build, double *area_now);
+/* The range of distances from the origin the mesh lies in, as the whole-step cull of the Kerr trace uses it: d_min from the root
+ * box, d_max from the farthest vertex a triangle names; set by bhg_mesh_create and by every refit.  Either output may be NULL. */
+int bhg_mesh_range(const bhg_mesh *mesh, double *d_min, double *d_max);
+/* Host only, no context, no GPU: the CPU statement of the refit kernels.  Given vertices, triangles and a topology as
+ * bhg_mesh_bvh_host returns it, writes the refitted, widened node_box [n_nodes][6] and (area may be NULL) the area sum.  With
+ * the vertices the topology was built from, node_box is bhg_mesh_bvh_host's bit for bit.  Refused: what bhg_mesh_create
+ * refuses of vertices and triangles; a topology that is not a tree of bhg_mesh_bvh_host's kind over n_triangles slots. */
+int bhg_mesh_bvh_refit_host(const double *vertices, size_t n_vertices, const int32_t *triangles, size_t n_triangles,
+                            const int32_t *node_skip, const int32_t *node_first, const int32_t *node_count, const int32_t *tri_order,
+                            size_t n_nodes, double *node_box, double *area);
+/* Host only: the bottom-up schedule the refit walks.  level_nodes[level_off[d] .. level_off[d + 1]) are the inner nodes d levels
+ * below the root, d = 0 .. 32 (level_off holds 34 entries); the levels are done deepest first, so every inner node comes after
+ * both its children.  cap = the entries level_nodes holds (n_triangles - 1 always suffices); *n_inner is set even when cap is
+ * too small (BHG_E_INVALID then). */
+int bhg_mesh_refit_schedule_host(const int32_t *node_skip, const int32_t *node_first, const int32_t *node_count,
+                                 const int32_t *tri_order, size_t n_nodes, size_t n_triangles, int32_t *level_nodes,
+                                 int32_t *level_off, size_t cap, size_t *n_inner);
+/* New vertices (and vertex normals: given exactly when the mesh was set with them) for the mesh of the library-owned frame;
+ * host arrays of the mesh's n_vertices, copied.  At the next render each device that holds the mesh refits it (bhg_mesh_refit)
+ * instead of building it anew; the material and its images, the instances and their colours stay, and the frame sets its
+ * instance sets again by itself.  The render is the one bhg_frame_set_mesh with the deformed vertices gives, bit for bit.
+ * rebuild_ratio: a device whose area_now would exceed rebuild_ratio * area_build builds its tree anew from the held triangles
+ * and the new vertices instead; <= 0: never rebuild; a value in (0, 1], and so 1: always rebuild.
+ * Refused, the frame left as it was: a frame without a mesh; what bhg_mesh_refit refuses; a NaN rebuild_ratio. */
+int bhg_frame_refit_mesh(bhg_frame *frame, const double *vertices, const double *vertex_normals, double rebuild_ratio);
+/* bhg_mesh_refit_info of the mesh that device number `shard` of the frame holds (in the order of the frame's device list): a
+ * rebuilt mesh starts at generation 0 again.  Refused: a shard outside the list; a device that holds no mesh yet. */
+int bhg_frame_mesh_refit_info(const bhg_frame *frame, int32_t shard, uint64_t *generation, double *area_build, double *area_now);
+/* A blocking download of the device's boxes [n_nodes][6] and (tri may be NULL) slot records [nt][9] = v0, e1, e2 per leaf slot,
+ * for tests and diagnosis.  cap = the nodes node_box holds. */
+int bhg_mesh_boxes_host(const bhg_mesh *mesh, double *node_box, double *tri, size_t cap);
 
 /* Acceleration probe: acc[n][3] = -Gamma^i_{mu nu} k^mu k^nu at (x[n][3], k[n][3]); host buffers.
  * Lets tests compare the device RHS with the oracle's term by term.  With rhs_form = BHG_RHS_KERR_BL the triples
