@@ -65,7 +65,7 @@ EXPORTS = (
     "bhg_frame_set_object_motion",
     "bhg_math_probe",
     "bhg_trace_start_device", "bhg_start_steps_match", "bhg_trace_prefix_device", "bhg_prefix_clearance",
-    "bhg_prefix_deep_attempts",
+    "bhg_prefix_deep_attempts", "bhg_prefix_wide_accepted", "bhg_prefix_owner_next", "bhg_frame_prefix_info",
     "bhg_trace_crossings_device", "bhg_trace_crossings", "bhg_disk_layers_size", "bhg_shade_disk_layers_device",
     "bhg_travel_time_device", "bhg_travel_time", "bhg_shade_disk_layers_retarded_device",
     "bhg_mesh_create", "bhg_mesh_destroy", "bhg_mesh_info", "bhg_mesh_bvh_host", "bhg_trace_mesh_device", "bhg_trace_mesh",
@@ -90,11 +90,19 @@ PREFIX_NONE, PREFIX_RECORD, PREFIX_REPLAY = 0, 1, 2
 PREFIX_K_MAX, PREFIX_BYTES_PER_RAY = 4, 112
 # ... by the deep rule (BHG_PREFIX_RECORD_DEEP): rejected attempts kept, three quarters of the clear ball without object spheres
 PREFIX_RECORD_DEEP, PREFIX_DEEP_ACCEPTED, PREFIX_DEEP_ATTEMPTS = 4, 6, 12
+# ... by the wide rule (BHG_PREFIX_RECORD_WIDE): the deep rule in fifteen sixteenths of the ball, up to eight accepted steps
+PREFIX_RECORD_WIDE, PREFIX_WIDE_ACCEPTED = 5, 8
 
 
 class Prefix(C.Structure):
     """bhg_prefix: d_records (device address), rho, mode in, used out (include/bhgeo.h has the rules)."""
     _fields_ = [("d_records", C.c_void_p), ("rho", C.c_double), ("mode", C.c_int32), ("used", C.c_int32)]
+
+
+class PrefixOwner(C.Structure):
+    """bhg_prefix_owner: what bhg_prefix_owner_next keeps of a ray set's records between calls."""
+    _fields_ = [("rho", C.c_double), ("refused_run", C.c_int32), ("roomy_run", C.c_int32), ("clean_run", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 PROBE_FMA, PROBE_STEP_MIX = 0, 1
@@ -500,6 +508,13 @@ def load():
     if hasattr(L, "bhg_prefix_deep_attempts"):     # (a library from before the deep rule: has_deep_prefix())
         L.bhg_prefix_deep_attempts.restype = C.c_int32
         L.bhg_prefix_deep_attempts.argtypes = []
+    if hasattr(L, "bhg_prefix_wide_accepted"):     # (a library from before the wide rule: has_wide_prefix())
+        L.bhg_prefix_wide_accepted.restype = C.c_int32
+        L.bhg_prefix_wide_accepted.argtypes = []
+        L.bhg_prefix_owner_next.restype = C.c_int32
+        L.bhg_prefix_owner_next.argtypes = [C.POINTER(PrefixOwner), C.c_int32, C.c_int32, C.POINTER(Params), _dp, C.c_int32, _dp, C.POINTER(Prefix)]
+        L.bhg_frame_prefix_info.restype = C.c_int
+        L.bhg_frame_prefix_info.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Prefix)]
     L.bhg_start_steps_match.restype = C.c_int
     L.bhg_start_steps_match.argtypes = [C.POINTER(Params), C.POINTER(Params)]
     L.bhg_shade_dir_device.restype = C.c_int
@@ -1056,6 +1071,22 @@ def has_deep_prefix() -> bool:
     return has_start_prefix() and hasattr(load(), "bhg_prefix_deep_attempts")
 
 
+def has_wide_prefix() -> bool:
+    """Does the loaded library take BHG_PREFIX_RECORD_WIDE and decide an owner's re-recording (it then exports
+    bhg_prefix_wide_accepted and bhg_prefix_owner_next)?"""
+    return has_deep_prefix() and hasattr(load(), "bhg_prefix_wide_accepted")
+
+
+def prefix_owner_next(owner: "PrefixOwner", rule: int, params: "Params", x0, spheres=None, last: "Prefix" = None,
+                      promote: int = PREFIX_NONE) -> int:
+    """bhg_prefix_owner_next: what the owner's next call asks for -- PREFIX_REPLAY, rule or promote (record now, by that rule) or
+    PREFIX_NONE."""
+    sp = None if spheres is None else _spheres_array(spheres)
+    xs = (C.c_double * 3)(*[float(v) for v in x0])
+    return int(load().bhg_prefix_owner_next(C.byref(owner), rule, promote, C.byref(params), None if sp is None or not len(sp) else _np_dp(sp),
+                                            0 if sp is None else len(sp), xs, None if last is None else C.byref(last)))
+
+
 def prefix_clearance(params: "Params", x0, spheres=None) -> float:
     """bhg_prefix_clearance: distance from x0 to the nearest event surface of a call with these parameters and spheres."""
     sp = None if spheres is None else _spheres_array(spheres)
@@ -1417,6 +1448,13 @@ class Frame:
         g, a, b = C.c_uint64(0), C.c_double(0.0), C.c_double(0.0)
         _check(load().bhg_frame_mesh_refit_info(self._h, int(shard), C.byref(g), C.byref(a), C.byref(b)))
         return g.value, a.value, b.value
+
+    def prefix_info(self, shard=0):
+        """(mode, used, rho) of the last render's trace call on the frame's device number `shard` (bhg_frame_prefix_info): what it
+        asked of the rays' start-up records, what the library answered, the records' radius"""
+        pf = Prefix(None, 0.0, PREFIX_NONE, PREFIX_NONE)
+        _check(load().bhg_frame_prefix_info(self._h, int(shard), C.byref(pf)))
+        return pf.mode, pf.used, pf.rho
 
     def set_mesh_instances(self, transforms=None, inst_rgb=None):
         """Rigid placements of the frame's mesh in every later render (bhg_frame_set_mesh_instances):

@@ -40,6 +40,13 @@ static_assert(BHG_FLAG_HIT_OBJECT == bhg::BHG_FLAG_HIT_OBJECT_ && BHG_MAX_SPHERE
 static_assert(BHG_PREFIX_K_MAX == bhg::BHG_PREFIX_K_MAX_ && BHG_PREFIX_DEEP_ACCEPTED == bhg::BHG_PREFIX_DEEP_ACCEPTED_ &&
                   BHG_PREFIX_DEEP_ATTEMPTS == bhg::BHG_PREFIX_DEEP_ATTEMPTS_ && BHG_PREFIX_DEEP_ACCEPTED <= BHG_PREFIX_DEEP_ATTEMPTS,
               "start-up record limits mismatch");
+static_assert(BHG_PREFIX_WIDE_ACCEPTED == bhg::BHG_PREFIX_WIDE_ACCEPTED_ && BHG_PREFIX_DEEP_ACCEPTED <= BHG_PREFIX_WIDE_ACCEPTED &&
+                  BHG_PREFIX_WIDE_ACCEPTED <= BHG_PREFIX_DEEP_ATTEMPTS,
+              "wide start-up record limits mismatch");
+static_assert(BHG_PREFIX_NONE == bhg::PREFIX_MODE_NONE && BHG_PREFIX_RECORD == bhg::PREFIX_MODE_RECORD &&
+                  BHG_PREFIX_REPLAY == bhg::PREFIX_MODE_REPLAY && BHG_PREFIX_RECORD_DEEP == bhg::PREFIX_MODE_RECORD_DEEP &&
+                  BHG_PREFIX_RECORD_WIDE == bhg::PREFIX_MODE_RECORD_WIDE,
+              "start-up record modes mismatch");
 static_assert(BHG_METHOD_DP54 == bhg::BHG_METHOD_DP54_ && BHG_METHOD_RK4 == bhg::BHG_METHOD_RK4_, "method mismatch");
 static_assert(BHG_RHS_CHRISTOFFEL == bhg::BHG_RHS_CHRISTOFFEL_ && BHG_RHS_REDUCED == bhg::BHG_RHS_REDUCED_ &&
                   BHG_RHS_KERR_BL == bhg::BHG_RHS_KERR_BL_,
@@ -1208,8 +1215,9 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const TraceCall &tc)
     if (pf) {
         pf->used = BHG_PREFIX_NONE;
         if (pf->mode != BHG_PREFIX_NONE && pf->mode != BHG_PREFIX_RECORD && pf->mode != BHG_PREFIX_REPLAY &&
-            pf->mode != BHG_PREFIX_RECORD_DEEP)
-            return fail(BHG_E_INVALID, "prefix mode must be BHG_PREFIX_NONE, BHG_PREFIX_RECORD, BHG_PREFIX_REPLAY or BHG_PREFIX_RECORD_DEEP");
+            pf->mode != BHG_PREFIX_RECORD_DEEP && pf->mode != BHG_PREFIX_RECORD_WIDE)
+            return fail(BHG_E_INVALID,
+                        "prefix mode must be BHG_PREFIX_NONE, BHG_PREFIX_RECORD, BHG_PREFIX_REPLAY, BHG_PREFIX_RECORD_DEEP or BHG_PREFIX_RECORD_WIDE");
         if (n && pf->mode != BHG_PREFIX_NONE && !pf->d_records) return fail(BHG_E_INVALID, "prefix mode asks for d_records, which is NULL");
     }
     if (start_mode != BHG_START_NONE && start_mode != BHG_START_RECORD && start_mode != BHG_START_REPLAY)
@@ -1301,6 +1309,7 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const TraceCall &tc)
     // (the planes' stride is the launch's n), a step budget the records cannot exhaust.  Anything else ignores them, as RK4
     // ignores the start steps, and says so in pf->used.
     bool pf_record = false, pf_deep = false;
+    uint32_t pf_acc_max = (uint32_t)BHG_PREFIX_DEEP_ACCEPTED;
     double pf_rho = 0.0;
     if (pf && pf->mode != BHG_PREFIX_NONE && !lanes && !d_x0 && p->method == BHG_METHOD_DP54 &&
         (rhs_id == bhg::BHG_RHS_CHRISTOFFEL_ || rhs_id == bhg::BHG_RHS_REDUCED_) && a.max_steps > (uint32_t)BHG_PREFIX_K_MAX) {
@@ -1314,6 +1323,12 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const TraceCall &tc)
         } else if (pf->mode == BHG_PREFIX_RECORD_DEEP) {
             pf_rho = deep_fits ? bhg::prefix_rho_deep_call(clear, a.r_hor, x0_shared, n_spheres) : 0.0;
             pf_record = pf_deep = pf_rho > 0.0;
+        } else if (pf->mode == BHG_PREFIX_RECORD_WIDE) {
+            // (the deep recorder in the wider ball, with room for the accepted steps that ball holds; where the rule keeps the
+            // deep call's ball it keeps its cap, and the records are that call's byte for byte)
+            pf_rho = deep_fits ? bhg::prefix_rho_wide_call(clear, a.r_hor, x0_shared, n_spheres) : 0.0;
+            pf_record = pf_deep = pf_rho > 0.0;
+            if (pf_rho > bhg::prefix_rho_deep_call(clear, a.r_hor, x0_shared, n_spheres)) pf_acc_max = (uint32_t)BHG_PREFIX_WIDE_ACCEPTED;
         } else if (deep_fits && bhg::prefix_replay_ok(clear, pf->rho)) {
             a.prefix = (const double2 *)pf->d_records;
             pf->used = BHG_PREFIX_REPLAY;
@@ -1410,9 +1425,9 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const TraceCall &tc)
         if (!c->counters_clean) HIP_TRY(hipMemsetAsync(c->counter, 0, 2 * 8 * 256, s));   // first call, or after a failed enqueue
         if (pf_record) {
             // the recording pass, in front of the trace of always (which starts its rays itself: the records are for later calls)
-            HIP_TRY(bhg::launch_record_prefix(a, rhs_id, pf->d_records, pf_rho, pf_deep, s));
+            HIP_TRY(bhg::launch_record_prefix(a, rhs_id, pf->d_records, pf_rho, pf_deep, pf_acc_max, s));
             pf->rho = pf_rho;
-            pf->used = pf_deep ? BHG_PREFIX_RECORD_DEEP : BHG_PREFIX_RECORD;
+            pf->used = pf->mode;
         }
         c->counters_clean = false;
         HIP_TRY(bhg::launch_trace(a, p->method, rhs_id, evt, (int)grid, s, c->profiling ? c->ev : nullptr));
@@ -1580,11 +1595,38 @@ double bhg_prefix_clearance(const bhg_params *p, const double *spheres, int32_t 
     return bhg::prefix_clearance(a.r_hor, a.r_exit, a.disk_r_out > 0.0, spheres, n_spheres, x0);
 }
 
+int32_t bhg_prefix_deep_attempts(void) { return BHG_PREFIX_DEEP_ATTEMPTS; }
+int32_t bhg_prefix_wide_accepted(void) { return BHG_PREFIX_WIDE_ACCEPTED; }
+
+// when an owner records again: bhg::PrefixOwner (prefix_clearance.h) on the call's own clearance, for bhg_frame_render and the binding alike
+static_assert(sizeof(bhg_prefix_owner) == 24, "bhg_prefix_owner layout is part of the ABI");
+int32_t bhg_prefix_owner_next(bhg_prefix_owner *o, int32_t rule, int32_t promote, const bhg_params *p, const double *spheres,
+                              int32_t n_spheres, const double *x0, const bhg_prefix *last)
+{
+    if (!o || !p || !x0 || n_spheres < 0 || (n_spheres > 0 && !spheres)) return BHG_PREFIX_NONE;
+    if (rule != BHG_PREFIX_RECORD && rule != BHG_PREFIX_RECORD_DEEP && rule != BHG_PREFIX_RECORD_WIDE) return BHG_PREFIX_NONE;
+    if (promote != BHG_PREFIX_NONE && promote != BHG_PREFIX_RECORD_DEEP && promote != BHG_PREFIX_RECORD_WIDE) return BHG_PREFIX_NONE;
+    bhg::TraceArgs a;
+    std::memset(&a, 0, sizeof(a));
+    fill_trace_args(a, p, nullptr, 0);
+    const double clear = bhg::prefix_clearance(a.r_hor, a.r_exit, a.disk_r_out > 0.0, spheres, n_spheres, x0);
+    bhg::PrefixOwner w;
+    w.rho = o->rho;
+    w.refused_run = o->refused_run;
+    w.roomy_run = o->roomy_run;
+    w.clean_run = o->clean_run;
+    const int ask = w.next(rule, clear, a.r_hor, x0, n_spheres, last ? last->mode : BHG_PREFIX_NONE, last ? last->used : BHG_PREFIX_NONE,
+                           last ? last->rho : 0.0, promote);
+    o->rho = w.rho;
+    o->clean_run = w.clean_run;
+    o->refused_run = w.refused_run;
+    o->roomy_run = w.roomy_run;
+    return ask;
+}
+
 // THE list of what a ray's initial step depends on beside the ray itself (initial_record, geodesic_kernels.hip): the
 // controller's tolerances and limits and the metric.  The integrator is in it because only DP5(4) has such a step: a
 // recording RK4 call leaves the array as it was.  Compared bit for bit (a -0.0 or another NaN counts as a change: safe).
-int32_t bhg_prefix_deep_attempts(void) { return BHG_PREFIX_DEEP_ATTEMPTS; }
-
 int bhg_start_steps_match(const bhg_params *a, const bhg_params *b)
 {
     if (!a || !b) return 0;

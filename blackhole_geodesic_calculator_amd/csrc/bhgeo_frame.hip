@@ -31,6 +31,7 @@
 #include "../../include/bhgeo.h"
 #include "geodesic_kernels.h"
 #include "mesh_bvh.h"
+#include "prefix_clearance.h"
 #include "tile_dealing.h"
 
 namespace bhg {
@@ -196,7 +197,8 @@ struct Shard {
     DevBuf pixels_d, jitter_d, k0, end, dir, flags, steps, acc, obj, slab, sky, disk_tex;
     DevBuf start_h;                 // [n] doubles beside k0: the rays' initial steps, kept from render to render (BHG_START_STEPS)
     DevBuf start_rec;               // the rays' start-up records (BHG_START_PREFIX: 112 B per ray), written by the render that records
-    double start_rho = 0.0;         // start_h, for the ball of this radius about start_origin; 0 = none are held
+    bhg::PrefixOwner start_owner;   // ... their radius (0: none are held) and when to record them again, scene change by scene change
+    bhg_prefix start_last = {nullptr, 0.0, BHG_PREFIX_NONE, BHG_PREFIX_NONE};   // what the last render asked for and was told
     DevBuf otex[BHG_MAX_SPHERES];   // the object textures (bhg_frame_set_object_textures), slot by slot
     // the mesh (bhg_frame_set_mesh): this device's copy, its material's arrays and images, the mesh trace's hit records
     bhg_mesh *mesh = nullptr;
@@ -1050,7 +1052,13 @@ try {
     const char *sp_env = std::getenv("BHGEO_START_PREFIX");  // "0": the start steps alone, no start-up records (A/B, 112 B per ray less)
     const bool start_prefix = start_cache && !(sp_env && sp_env[0] == '0' && sp_env[1] == 0);
     const char *dp_env = std::getenv("BHGEO_DEEP_PREFIX");   // "0": the records by BHG_PREFIX_RECORD, not BHG_PREFIX_RECORD_DEEP (A/B)
-    const int32_t record_mode = (dp_env && dp_env[0] == '0' && dp_env[1] == 0) ? BHG_PREFIX_RECORD : BHG_PREFIX_RECORD_DEEP;
+    // the records are written by BHG_PREFIX_RECORD_DEEP and, after a long run of replaying renders, again by BHG_PREFIX_RECORD_WIDE
+    // (bhg::PrefixOwner: promote).  BHGEO_WIDE_PREFIX "1": by the wide rule from the first render; "0": never (A/B)
+    const char *wp_env = std::getenv("BHGEO_WIDE_PREFIX");
+    const bool no_deep = dp_env && dp_env[0] == '0' && dp_env[1] == 0;
+    const bool wide_off = wp_env && wp_env[0] == '0' && wp_env[1] == 0, wide_now = wp_env && wp_env[0] == '1' && wp_env[1] == 0;
+    const int32_t record_mode = no_deep ? BHG_PREFIX_RECORD : wide_now ? BHG_PREFIX_RECORD_WIDE : BHG_PREFIX_RECORD_DEEP;
+    const int32_t promote_mode = (no_deep || wide_off || wide_now) ? BHG_PREFIX_NONE : BHG_PREFIX_RECORD_WIDE;
     const bool redshift = f->rs.apply != 0;
     if (redshift) {   // (refused before anything is enqueued)
         bhg::RedshiftParams rp;
@@ -1161,20 +1169,28 @@ try {
             s.start_ready = false;
             BHG_TRY(s.start_h.ensure(s.device, s.n * sizeof(double)));
             start_mode = keep ? BHG_START_REPLAY : BHG_START_RECORD;
-            if (!keep) s.start_rho = 0.0;
         }
         // ... and so do their start-up records: written by the render that records the steps, handed to every later one with
         // their rho -- the library holds each render's scene against it (an object sphere may have moved in) and says in
-        // pf.used what it did
+        // pf.used what it did.  A scene that stays inside the ball, or one that has left a small ball far behind, has them
+        // written again by a render that replays its steps (bhg::PrefixOwner has the rules).
         bhg_prefix pf = {nullptr, 0.0, BHG_PREFIX_NONE, BHG_PREFIX_NONE};
         if (start_prefix) {
             BHG_TRY(s.start_rec.ensure(s.device, s.n * (size_t)BHG_PREFIX_BYTES_PER_RAY));
             pf.d_records = s.start_rec.as<char>();
-            pf.rho = s.start_rho;
-            pf.mode = start_mode == BHG_START_RECORD ? record_mode : (s.start_rho > 0.0 ? BHG_PREFIX_REPLAY : BHG_PREFIX_NONE);
-            s.start_rho = 0.0;
+            if (start_mode == BHG_START_RECORD) {
+                s.start_owner = bhg::PrefixOwner();
+                pf.mode = record_mode;
+            } else {
+                const double *sph = has_obj ? &f->scene.spheres[0][0] : nullptr;
+                const int32_t n_sph = has_obj ? f->scene.n_spheres : 0;
+                // (r_s is the horizon of every call that writes records: a Kerr render holds none, and none is NONE at once)
+                pf.mode = s.start_owner.next(record_mode, bhg_prefix_clearance(&prm, sph, n_sph, f->cam.origin), prm.r_s, f->cam.origin,
+                                             n_sph, s.start_last.mode, s.start_last.used, s.start_last.rho, promote_mode);
+                pf.rho = s.start_owner.rho;
+            }
         } else {
-            s.start_rho = 0.0;
+            s.start_owner = bhg::PrefixOwner();
         }
         if (dir_only) BHG_TRY(s.dir.ensure(s.device, s.n * 3 * sizeof(double)));
         else BHG_TRY(s.end.ensure(s.device, s.n * 6 * sizeof(double)));
@@ -1184,7 +1200,7 @@ try {
                                         dir_only ? s.dir.as<double>() : nullptr, s.flags.as<uint8_t>(), s.steps.as<uint32_t>(),
                                         s.acc.as<uint32_t>(), has_obj ? s.obj.as<int8_t>() : nullptr, s.start_h.as<double>(),
                                         start_mode, &pf, s.stream));
-        if (start_prefix) s.start_rho = pf.mode == record_mode ? (pf.used == record_mode ? pf.rho : 0.0) : pf.rho;
+        s.start_last = pf;
         if (start_cache) {
             s.start_prm = prm;
             std::memcpy(s.start_origin, f->cam.origin, sizeof(s.start_origin));
@@ -1395,6 +1411,14 @@ int bhg_frame_mesh_refit_info(const bhg_frame *f, int32_t shard, uint64_t *gener
     if (shard < 0 || (size_t)shard >= f->sh.size()) return fail(BHG_E_INVALID, "shard must be in [0, the frame's devices)");
     if (!f->sh[(size_t)shard].mesh) return fail(BHG_E_INVALID, "this device holds no mesh (none set, or no render since)");
     return bhg_mesh_refit_info(f->sh[(size_t)shard].mesh, generation, area_build, area_now);
+}
+
+int bhg_frame_prefix_info(const bhg_frame *f, int32_t shard, bhg_prefix *last)
+{
+    if (!f || !last) return fail(BHG_E_INVALID, "bad argument");
+    if (shard < 0 || (size_t)shard >= f->sh.size()) return fail(BHG_E_INVALID, "shard must be in [0, the frame's devices)");
+    *last = f->sh[(size_t)shard].start_last;
+    return BHG_OK;
 }
 
 int bhg_frame_info(const bhg_frame *f, int64_t out[8])

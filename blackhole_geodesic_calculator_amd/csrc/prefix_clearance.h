@@ -8,7 +8,8 @@
 // surface reaches the ball, a full trace finds no event in those steps and arrives at the recorded state.  So:
 //   clearance = distance from the start point to the nearest event surface of a call's scene,
 //   rho       = PREFIX_RHO_FRACTION * min(clearance, |x0|), fixed when the records are written
-//               (deep records, BHG_PREFIX_RECORD_DEEP: PREFIX_RHO_FRACTION_DEEP of it while the scene holds no object sphere),
+//               (deep records, BHG_PREFIX_RECORD_DEEP: PREFIX_RHO_FRACTION_DEEP of it while the scene holds no object sphere;
+//               wide records, BHG_PREFIX_RECORD_WIDE: PREFIX_RHO_FRACTION_WIDE of it there),
 //   a call replays only while its own clearance > rho (1 + PREFIX_MARGIN): the one validity test, whichever rule wrote them.
 #pragma once
 #include <cmath>
@@ -18,7 +19,7 @@ namespace bhg {
 // A quarter: with K_MAX = 4 steps that each grow by at most the controller's factor 10, the steps kept are the climb from scipy's
 // start guess (h0 ~ 0.01) to the settled step size (~ the distance to the hole), and a small ball survives more scene changes
 // (an object sphere moving about).  It is NOT true that a larger ball holds no more steps, as this comment used to say: a
-// headline ray (camera at r = 30, r_s = 2: clearance 29) takes three climbing steps that end 0.01, 0.08 and 0.8 from the camera,
+// headline ray (camera at r = 30, r_s = 1: clearance 29) takes three climbing steps that end 0.01, 0.08 and 0.8 from the camera,
 // a fourth of 7 to 20, which leaves the quarter ball (7.25) for 90 % of the rays, and a fifth that takes 2 to 3 attempts.
 // Attempts kept per ray, of 12.33, on 400 seeded headline rays (scipy RK45 at the bench's tolerances):
 //   rho                 stop at the first rejection, <= 4 accepted    rejections kept, <= 6 accepted
@@ -26,11 +27,22 @@ namespace bhg {
 //   14.5   (1/2)                     3.78                                      5.24
 //   21.75  (3/4)                     3.92                                      5.94
 //   27.0   (0.93)                    3.93                                      7.71
+// ... and of 12.79 on 300 uniform rays of the headline window (the same rule, rejections kept, stop in front of an ending attempt):
+//   rho                 <= 6 accepted, <= 12 attempts      <= 8 accepted, <= 12 attempts      <= 8 accepted, <= 16 attempts
+//    7.25    (1/4)             3.24                               3.24                               3.24
+//   21.75    (3/4)             6.04                               6.04                               6.04
+//   27.1875  (15/16)           7.91, 10 % at the cap              8.05, none at a cap                8.05
+//   28.09375 (31/32)           8.01, 18 % at the cap              8.34                               8.36
 constexpr double PREFIX_RHO_FRACTION = 0.25;
 // Three quarters, the deep records' fraction in a scene WITHOUT object spheres: nothing moves there -- horizon, exit sphere and
 // disk plane change only when the scene is edited, and prefix_replay_ok holds every call to the ball anyway.  (0.93 keeps more
 // still, but that ball reaches r ~ 3 from a camera at 30 and gives up most of the tolerance to such edits.)
 constexpr double PREFIX_RHO_FRACTION_DEEP = 0.75;
+// Fifteen sixteenths, the wide records' fraction where the deep rule takes its three quarters: from the headline camera the ball
+// (27.1875) reaches r = 2.81.  The tolerance to edits it gives up is a matter of speed alone -- prefix_replay_ok refuses, the
+// call runs the plain start -- and an owner gets it back by recording again after refusals (PrefixOwner below).  31/32 adds 0.3
+// attempts for a ball that ends 0.9 above the photon sphere: not taken.
+constexpr double PREFIX_RHO_FRACTION_WIDE = 0.9375;
 // The recorded step ends satisfy |x - x0|^2 <= rho^2 in rounded arithmetic, and the event tests compare rounded radii: a surface
 // counts as clear of the ball only with this relative margin (many orders above the rounding, far below any scene's scale).
 // A surface tangent to the ball is NOT clear.
@@ -86,10 +98,90 @@ inline double prefix_rho_deep_call(double clearance, double r_hor, const double 
     return horizon_nearest ? prefix_rho_deep(clearance, x0, n_spheres) : prefix_rho(clearance, x0);
 }
 
+// ... of a WIDE recording call: fifteen sixteenths exactly where the deep call takes its three quarters (no object sphere, the
+// horizon the nearest surface), and what the deep call returns everywhere else: the quarter, 0 for the degenerate inputs
+inline double prefix_rho_wide_call(double clearance, double r_hor, const double x0[3], int n_spheres)
+{
+    const double r0 = std::sqrt(x0[0] * x0[0] + x0[1] * x0[1] + x0[2] * x0[2]);
+    const bool horizon_nearest = std::isfinite(r0) && r_hor >= 0.0 && clearance >= r0 - r_hor;
+    if (!horizon_nearest || n_spheres > 0) return prefix_rho_deep_call(clearance, r_hor, x0, n_spheres);
+    if (!std::isfinite(clearance) || !(clearance > 0.0) || !(r0 > 0.0)) return 0.0;
+    return PREFIX_RHO_FRACTION_WIDE * std::fmin(clearance, r0);
+}
+
 // may a call whose scene has this clearance replay records written with rho?
 inline bool prefix_replay_ok(double clearance, double rho)
 {
     return std::isfinite(rho) && rho > 0.0 && clearance > rho * (1.0 + PREFIX_MARGIN);
 }
+
+// ------------------------------------------------------------------------------------------------------------------------
+// The owner of a ray set's records (bhg_frame, DeviceFrame's StartSteps through bhg_prefix_owner_next): when to record AGAIN.
+// The rays' own invalidation -- other rays, another origin, parameters that bhg_start_steps_match() rejects -- is the owner's
+// and starts from scratch (a fresh PrefixOwner, a recording call).  What is decided here is the scene's part:
+//   shrink: the last two calls in a row were refused (the scene has come into the ball and stays there: one refused frame, an
+//           object passing through, is not enough) -- record now, by the rule on the call's own scene;
+//   grow:   for PREFIX_OWNER_GROW_CALLS calls in a row the rule gave the call's scene a rho of at least PREFIX_OWNER_GROW_FACTOR
+//           times the kept one (what held the ball small has gone for good) -- record now.
+// and one more, for an owner that records by a cautious rule and names a wider one to be promoted to (the owners' default: deep
+// first, wide later -- the wide ball gives up the tolerance to edits, and an owner's first frames are where scenes get edited):
+//   promote: the last PREFIX_OWNER_PROMOTE_CALLS calls in a row all replayed and the wider rule gives this call's scene more than
+//           the kept rho -- record now, by the wider rule.  Shrink and grow stay with the cautious rule.
+// PROMOTE_CALLS is the rent-or-buy point, by the headline's figures: a replay of wide records saves 0.16 ms
+// on one of deep records; the promoting call costs 1.6 ms more than the replay it replaces (its rays start themselves, and the
+// recording pass), and an edit that then reaches into the wide ball but not into the deep one costs 2.5 ms more (two refused
+// frames, a recording call): 4.1 / 0.16 = 25 frames.  Waiting that long before buying is within a factor two of the best choice
+// whenever the edit comes; 32 leaves room for frames whose replays save less than the headline's.
+// The modes are the C API's (include/bhgeo.h; bhgeo_capi.hip asserts the values).
+constexpr int PREFIX_MODE_NONE = 0, PREFIX_MODE_RECORD = 1, PREFIX_MODE_REPLAY = 2, PREFIX_MODE_RECORD_DEEP = 4, PREFIX_MODE_RECORD_WIDE = 5;
+constexpr int PREFIX_OWNER_SHRINK_CALLS = 2, PREFIX_OWNER_GROW_CALLS = 8, PREFIX_OWNER_PROMOTE_CALLS = 32;
+constexpr double PREFIX_OWNER_GROW_FACTOR = 2.0;
+
+// the rho a recording call by this rule fixes (the step budget apart: see deep_fits in bhgeo_capi.hip)
+inline double prefix_rho_by_rule(int rule, double clearance, double r_hor, const double x0[3], int n_spheres)
+{
+    if (rule == PREFIX_MODE_RECORD_WIDE) return prefix_rho_wide_call(clearance, r_hor, x0, n_spheres);
+    if (rule == PREFIX_MODE_RECORD_DEEP) return prefix_rho_deep_call(clearance, r_hor, x0, n_spheres);
+    return rule == PREFIX_MODE_RECORD ? prefix_rho(clearance, x0) : 0.0;
+}
+
+struct PrefixOwner {
+    double rho = 0.0;       // the held records were written with this radius (0: none are held)
+    int refused_run = 0;    // calls in a row, up to the last one, that asked to replay and were refused
+    int roomy_run = 0;      // calls in a row, this one included, whose scene the rule gives GROW_FACTOR times rho or more
+    int clean_run = 0;      // calls in a row, up to the last one, that replayed
+
+    // What the next call asks for: PREFIX_MODE_REPLAY, `rule` or `promote` (record now, by that rule) or PREFIX_MODE_NONE
+    // (nothing is held).  The last call of this owner asked for last_mode and reported last_used and (a recording call) last_rho;
+    // last_mode = NONE before the first call and after a call without a prefix.  The call being planned has this clearance,
+    // horizon and sphere count.  promote: the wider rule a long clean run earns, or NONE.
+    int next(int rule, double clearance, double r_hor, const double x0[3], int n_spheres, int last_mode, int last_used, double last_rho,
+             int promote = PREFIX_MODE_NONE)
+    {
+        if (last_mode == PREFIX_MODE_RECORD || last_mode == PREFIX_MODE_RECORD_DEEP || last_mode == PREFIX_MODE_RECORD_WIDE) {
+            // (a recording call that wrote nothing -- a step budget the records could exhaust -- left the held ones as they were)
+            if (last_used == last_mode) rho = std::isfinite(last_rho) && last_rho > 0.0 ? last_rho : 0.0;
+            refused_run = roomy_run = clean_run = 0;
+        } else if (last_mode == PREFIX_MODE_REPLAY) {
+            refused_run = last_used == PREFIX_MODE_REPLAY ? 0 : refused_run + 1;
+            clean_run = last_used == PREFIX_MODE_REPLAY ? clean_run + 1 : 0;
+        } else {
+            clean_run = 0;
+        }
+        if (!(rho > 0.0)) return PREFIX_MODE_NONE;
+        const double rule_rho = prefix_rho_by_rule(rule, clearance, r_hor, x0, n_spheres);
+        // (the call that records has room itself: records are never traded for smaller ones that nothing asked for)
+        const bool roomy = rule_rho >= PREFIX_OWNER_GROW_FACTOR * rho;
+        const bool grow = roomy && roomy_run >= PREFIX_OWNER_GROW_CALLS;
+        roomy_run = roomy ? roomy_run + 1 : 0;
+        // (a scene without any clear ball has nothing to record: the held records wait for it to pass)
+        const bool shrink = refused_run >= PREFIX_OWNER_SHRINK_CALLS && rule_rho > 0.0;
+        if (grow || shrink) return rule;
+        if (promote != PREFIX_MODE_NONE && clean_run >= PREFIX_OWNER_PROMOTE_CALLS &&
+            prefix_replay_ok(prefix_rho_by_rule(promote, clearance, r_hor, x0, n_spheres), rho))
+            return promote;      // (more than the kept rho by the margin of the replay test: never for the same ball again)
+        return PREFIX_MODE_REPLAY;
+    }
+};
 
 }  // namespace bhg

@@ -54,7 +54,15 @@ class StartSteps:
     they were written for -- the library tests each call's scene against it and reports what it did (prefix.used).
     prefix_recorded / prefix_replayed / prefix_refused count those answers; BHGEO_START_PREFIX=0 switches the records alone off.
     The records are written by the deep rule (BHG_PREFIX_RECORD_DEEP: rejected attempts kept, three quarters of the clear ball in
-    a scene without object spheres whose nearest surface is the horizon) where the library has it; BHGEO_DEEP_PREFIX=0 goes back to BHG_PREFIX_RECORD."""
+    a scene without object spheres whose nearest surface is the horizon) where the library has it; BHGEO_DEEP_PREFIX=0 goes back to BHG_PREFIX_RECORD.
+    Where the library has the wide rule (BHG_PREFIX_RECORD_WIDE: fifteen sixteenths of that ball) an owner is promoted to it:
+    after 32 traces in a row that all replayed, the next one writes the records again by the wide rule.  BHGEO_WIDE_PREFIX=1
+    records by the wide rule from the first trace, BHGEO_WIDE_PREFIX=0 never.
+    A scene that stays inside the ball (two refused traces in a row) or has left a small ball far behind (eight traces with room
+    for twice the radius) has the records written again too, by the owner's first rule.  Every such trace replays its steps;
+    the library decides (bhg_prefix_owner_next), and prefix_recorded counts them all."""
+
+    _RECORD_MODES = (_ffi.PREFIX_RECORD, _ffi.PREFIX_RECORD_DEEP, _ffi.PREFIX_RECORD_WIDE)
 
     def __init__(self, enabled=True):
         self.enabled = bool(enabled)
@@ -62,7 +70,8 @@ class StartSteps:
         self.key = self.params = self._pending = None
         self.recorded = self.replayed = 0
         self.d_rec = None
-        self.rho = 0.0             # the records in d_rec were written with this radius (0: none are held)
+        self.owner = _ffi.PrefixOwner(0.0, 0, 0)   # the library's state of the records in d_rec (bhg_prefix_owner_next)
+        self._last = None          # the _ffi.Prefix of the last trace as it came back, or None
         self.prefix = None         # the _ffi.Prefix of the trace being planned, or None
         self.prefix_recorded = self.prefix_replayed = self.prefix_refused = 0
 
@@ -73,13 +82,38 @@ class StartSteps:
     def valid(self):
         return self.key is not None
 
-    def plan(self, n, dev, key, params, shared_origin=False):
-        """(d_start_steps, start_mode) of the next trace call, and self.prefix for it.  The steps count as not valid until
-        done(): a call that raises leaves them so."""
+    @property
+    def rho(self):
+        """the records in d_rec were written with this radius (0: none are held)"""
+        last = self._last
+        if last is not None and last.mode in self._RECORD_MODES and last.used == last.mode:
+            return float(last.rho)
+        return float(self.owner.rho)
+
+    def _drop_records(self):
+        self.owner = _ffi.PrefixOwner(0.0, 0, 0)
+        self._last = None
+
+    @staticmethod
+    def _rule():
+        """(the rule the owner records by, the rule a long clean run promotes it to or PREFIX_NONE)"""
+        if os.environ.get("BHGEO_DEEP_PREFIX", "") == "0" or not _ffi.has_deep_prefix():
+            return _ffi.PREFIX_RECORD, _ffi.PREFIX_NONE
+        wide = os.environ.get("BHGEO_WIDE_PREFIX", "")
+        if wide == "0" or not _ffi.has_wide_prefix():
+            return _ffi.PREFIX_RECORD_DEEP, _ffi.PREFIX_NONE
+        if wide == "1":
+            return _ffi.PREFIX_RECORD_WIDE, _ffi.PREFIX_NONE
+        return _ffi.PREFIX_RECORD_DEEP, _ffi.PREFIX_RECORD_WIDE
+
+    def plan(self, n, dev, key, params, shared_origin=False, origin=None, spheres=None):
+        """(d_start_steps, start_mode) of the next trace call, and self.prefix for it (origin, spheres: the call's, which decide
+        with params whether held records are replayed or written again).  The steps count as not valid until done(): a call that
+        raises leaves them so."""
         self.prefix = None
         if not self.enabled or os.environ.get("BHGEO_START_CACHE", "") == "0":
             self.key = None
-            self.rho = 0.0
+            self._drop_records()
             return 0, _ffi.START_NONE
         if self.d_h is None or self.d_h.numel() != n or self.d_h.device != dev:
             self.d_h = torch.empty(n, dtype=torch.float64, device=dev)
@@ -91,15 +125,23 @@ class StartSteps:
         if shared_origin and os.environ.get("BHGEO_START_PREFIX", "") != "0" and _ffi.has_start_prefix():
             if self.d_rec is None:
                 self.d_rec = torch.empty(n * _ffi.PREFIX_BYTES_PER_RAY, dtype=torch.uint8, device=dev)
-                self.rho = 0.0
-            if replay and self.rho > 0.0:
-                self.prefix = _ffi.Prefix(self.d_rec.data_ptr(), self.rho, _ffi.PREFIX_REPLAY, 0)
-            elif not replay:
-                deep = os.environ.get("BHGEO_DEEP_PREFIX", "") != "0" and _ffi.has_deep_prefix()
-                self.prefix = _ffi.Prefix(self.d_rec.data_ptr(), 0.0, _ffi.PREFIX_RECORD_DEEP if deep else _ffi.PREFIX_RECORD, 0)
-                self.rho = 0.0
+                self._drop_records()
+            rule, promote = self._rule()
+            if not replay:
+                # other rays, another origin, other parameters: from scratch
+                self._drop_records()
+                ask = rule
+            elif _ffi.has_wide_prefix():
+                ask = _ffi.prefix_owner_next(self.owner, rule, params, origin, spheres, self._last, promote)
+            else:
+                # (a library from before bhg_prefix_owner_next: records are written once and replayed or refused ever after)
+                self.owner.rho = self.rho
+                ask = _ffi.PREFIX_REPLAY if self.owner.rho > 0.0 else _ffi.PREFIX_NONE
+            self._last = None
+            if ask != _ffi.PREFIX_NONE:
+                self.prefix = _ffi.Prefix(self.d_rec.data_ptr(), self.owner.rho if ask == _ffi.PREFIX_REPLAY else 0.0, ask, 0)
         else:
-            self.rho = 0.0
+            self._drop_records()
         return self.d_h.data_ptr(), (_ffi.START_REPLAY if replay else _ffi.START_RECORD)
 
     def done(self):
@@ -107,11 +149,10 @@ class StartSteps:
             return
         self.key, self.params, replay = self._pending
         self._pending = None
+        self._last = self.prefix
         if self.prefix is not None:
-            if self.prefix.mode in (_ffi.PREFIX_RECORD, _ffi.PREFIX_RECORD_DEEP):
-                wrote = self.prefix.used == self.prefix.mode
-                self.rho = float(self.prefix.rho) if wrote else 0.0
-                self.prefix_recorded += wrote
+            if self.prefix.mode in self._RECORD_MODES:
+                self.prefix_recorded += self.prefix.used == self.prefix.mode
             elif self.prefix.used == _ffi.PREFIX_REPLAY:
                 self.prefix_replayed += 1
             else:
@@ -533,7 +574,8 @@ class DeviceFrame:
         self._dir_traced = self.directions_only and not has_obj and self.disk is None and not (params.disk_r_out > 0.0)
         self._traced = "dir" if self._dir_traced else "end"
         # the initial steps belong to the rays and the origin they start from: recorded by the first trace, replayed after
-        d_h, mode = self.start_steps.plan(self.n, self.dev, (_rays_key(self.d_k0), origin.tobytes()), params, shared_origin=True)
+        d_h, mode = self.start_steps.plan(self.n, self.dev, (_rays_key(self.d_k0), origin.tobytes()), params, shared_origin=True,
+                                          origin=origin, spheres=self.spheres if has_obj else None)
         prefix = self.start_steps.prefix
         if self._dir_traced:
             if self.d_dir is None:

@@ -79,7 +79,9 @@ extern "C" {
                                   BHG_MESH_INSTANCES_MAX: rigid placements of one mesh, moved without a rebuild);
                                   BHG_MESH_REFIT (bhg_mesh_refit, bhg_mesh_refit_device, bhg_mesh_refit_info, bhg_mesh_bvh_refit_host,
                                   bhg_mesh_refit_schedule_host, bhg_mesh_boxes_host, bhg_mesh_range, bhg_frame_refit_mesh, bhg_frame_mesh_refit_info: new vertices into a built mesh, its tree
-                                  refitted on the device).
+                                  refitted on the device);
+                                  BHG_PREFIX_RECORD_WIDE under BHG_START_PREFIX (bhg_prefix_wide_accepted, bhg_prefix_owner_next,
+                                  bhg_frame_prefix_info, struct bhg_prefix_owner: wider start-up records, recorded again after refusals).
                                9: redshift -- bhg_redshift_device / _host, bhg_shade_scene_redshift_device, bhg_frame_set_redshift,
                                   bhg_redshift_size, struct bhg_redshift;
                                   nothing of ABI 8 changed.
@@ -365,8 +367,16 @@ int bhg_start_steps_match(const bhg_params *a, const bhg_params *b);
  *                      sphere or where the exit sphere or the disk plane is nearer.  Same buffer, same 112 bytes per ray, replayed by
  *                      the same BHG_PREFIX_REPLAY; needs max_steps > BHG_PREFIX_DEEP_ATTEMPTS, else nothing is written
  *                      (used = BHG_PREFIX_NONE, rho = 0).
+ *   BHG_PREFIX_RECORD_WIDE: RECORD_DEEP in a wider ball: rho = 15/16 min(clearance, |x0|) exactly
+ *                      where RECORD_DEEP takes its 3/4 -- no object sphere, the horizon the nearest surface -- and up to
+ *                      BHG_PREFIX_WIDE_ACCEPTED accepted steps in the same BHG_PREFIX_DEEP_ATTEMPTS attempts; the 1/4 everywhere
+ *                      else, with records that equal RECORD_DEEP's byte for byte there.  Same buffer, same bytes, same REPLAY,
+ *                      same max_steps > BHG_PREFIX_DEEP_ATTEMPTS.  From a camera at r = 30 the ball reaches r = 2.8: any later
+ *                      exit sphere, disk or object sphere inside it makes REPLAY refuse, which costs speed and nothing else; an
+ *                      owner gets the speed back by recording again (bhg_prefix_owner_next).  A recording call of any rule may
+ *                      go with BHG_START_REPLAY: the start steps are not recorded again.
  *   BHG_PREFIX_NONE:   bhg_trace_start_device.
- * used says what the call did: BHG_PREFIX_RECORD or BHG_PREFIX_RECORD_DEEP (records written by that rule), BHG_PREFIX_REPLAY
+ * used says what the call did: BHG_PREFIX_RECORD, _DEEP or _WIDE (records written by that rule), BHG_PREFIX_REPLAY
  * (records used) or BHG_PREFIX_NONE (refused, or out of scope).  A REPLAY call cannot tell which rule wrote the records it is
  * handed, so it uses none under a step budget that a deep record could exhaust: max_steps <= BHG_PREFIX_DEEP_ATTEMPTS is
  * answered with BHG_PREFIX_NONE, the plain call's results as always.  (Mode 3 is no mode and stays BHG_E_INVALID.)  In scope: x0_shared calls (d_x0 NULL) of BHG_METHOD_DP54 with BHG_RHS_CHRISTOFFEL or
@@ -378,9 +388,11 @@ int bhg_start_steps_match(const bhg_params *a, const bhg_params *b);
 #define BHG_PREFIX_RECORD 1
 #define BHG_PREFIX_REPLAY 2
 #define BHG_PREFIX_RECORD_DEEP 4 /* (3 stays no mode: callers were promised BHG_E_INVALID for it) */
+#define BHG_PREFIX_RECORD_WIDE 5
 #define BHG_PREFIX_K_MAX 4
 #define BHG_PREFIX_DEEP_ACCEPTED 6  /* accepted steps a deep record holds at most */
-#define BHG_PREFIX_DEEP_ATTEMPTS 12 /* attempts a deep record holds at most, rejected ones included */
+#define BHG_PREFIX_DEEP_ATTEMPTS 12 /* attempts a deep or wide record holds at most, rejected ones included */
+#define BHG_PREFIX_WIDE_ACCEPTED 8  /* accepted steps a wide record holds at most */
 #define BHG_PREFIX_BYTES_PER_RAY 112
 typedef struct bhg_prefix {
     void *d_records;  /* device, BHG_PREFIX_BYTES_PER_RAY * n bytes */
@@ -399,6 +411,32 @@ double bhg_prefix_clearance(const bhg_params *p, const double *spheres, int32_t 
 /* BHG_PREFIX_DEEP_ATTEMPTS as the library was built with it.  A library that exports this symbol takes BHG_PREFIX_RECORD_DEEP
  * (one without it answers that mode with BHG_E_INVALID): what a caller that loads the library at run time asks first. */
 int32_t bhg_prefix_deep_attempts(void);
+/* BHG_PREFIX_WIDE_ACCEPTED as the library was built with it: a library that exports this symbol takes BHG_PREFIX_RECORD_WIDE
+ * and has bhg_prefix_owner_next. */
+int32_t bhg_prefix_wide_accepted(void);
+/* When the owner of a ray set's records records them AGAIN because the scene has changed (the rays' own invalidation -- other
+ * rays, another origin, parameters bhg_start_steps_match() rejects -- stays the owner's: start from a zeroed bhg_prefix_owner
+ * and a recording call).  Before every later call the owner hands in the call's scene, the rule it records by (BHG_PREFIX_RECORD,
+ * _DEEP or _WIDE) and the bhg_prefix of its LAST call as that call left it (NULL: there was none), and is told what to ask for:
+ *   BHG_PREFIX_REPLAY with o->rho, or
+ *   rule: record now, in a call that may replay its start steps -- after two refused calls in a row (one refused frame, an object
+ *         passing through, changes nothing), or after eight calls in a row whose scene the rule gives at least twice o->rho
+ *         (what kept the ball small has gone), this call being one more of them, or
+ *   promote (BHG_PREFIX_RECORD_DEEP or _WIDE, or BHG_PREFIX_NONE for no such rule): record now by this wider rule -- after 32
+ *         calls in a row that all replayed, when it gives this call's scene more than o->rho.  The owners of the library and
+ *         the binding record by RECORD_DEEP and are promoted to RECORD_WIDE; BHGEO_WIDE_PREFIX=1 in the environment makes
+ *         them record by RECORD_WIDE from the first call, BHGEO_WIDE_PREFIX=0 never.  Or
+ *   BHG_PREFIX_NONE: no records are held (also for a NULL argument).
+ * HOST only; the same code decides for bhg_frame_render. */
+typedef struct bhg_prefix_owner {
+    double rho;          /* the held records' radius, 0: none */
+    int32_t refused_run; /* refused calls in a row */
+    int32_t roomy_run;   /* calls in a row with room for twice rho */
+    int32_t clean_run;   /* calls in a row that replayed */
+    int32_t reserved;    /* 0 */
+} bhg_prefix_owner;
+int32_t bhg_prefix_owner_next(bhg_prefix_owner *o, int32_t rule, int32_t promote, const bhg_params *p, const double *spheres,
+                              int32_t n_spheres, const double *x0, const bhg_prefix *last);
 
 /* --- the stages either side of the solve, on device ---------------------------------------- */
 /* Camera rays with the reference's multisample jitter (RelativisticRenderEngine.py:185-188,
@@ -542,6 +580,10 @@ int bhg_frame_stats(bhg_frame *frame, uint64_t out[4]);
 /* out = {n_devices, gather mode in use (BHG_FRAME_GATHER_COPY / _RCCL), largest shard in pixels, smallest shard,
  * tile, 1 if dealt by measured cost, renders so far, 1 if the last render traced directions only}. */
 int bhg_frame_info(const bhg_frame *frame, int64_t out[8]);
+/* The bhg_prefix of the last render's trace call on the frame's device number `shard`: what it asked of the rays' start-up
+ * records (mode), what the library answered (used) and the records' rho -- BHG_PREFIX_NONE throughout before the first such
+ * call and with BHGEO_START_CACHE=0 or BHGEO_START_PREFIX=0.  For tests and diagnosis. */
+int bhg_frame_prefix_info(const bhg_frame *frame, int32_t shard, bhg_prefix *last);
 /* Per-render timing.  While profiling is on (a flag: it may be switched from render to render, e.g. on for every 4th
  * frame of a timed loop) every render records a HIP event pair around its trace call on each device's stream;
  * bhg_frame_last_ms waits for them and gives the MEAN trace-call milliseconds per listed device over the profiled
