@@ -76,7 +76,10 @@ EXPORTS = (
     "bhg_shade_mesh_instances_device", "bhg_frame_set_mesh_instances",
     "bhg_mesh_refit", "bhg_mesh_refit_device", "bhg_mesh_refit_info", "bhg_mesh_bvh_refit_host", "bhg_mesh_refit_schedule_host",
     "bhg_mesh_boxes_host", "bhg_mesh_range", "bhg_frame_refit_mesh", "bhg_frame_mesh_refit_info",
+    "bhg_mesh_create_device", "bhg_mesh_rebuild_device", "bhg_mesh_rebuild", "bhg_mesh_build_info", "bhg_mesh_bvh_morton_host",
+    "bhg_mesh_tree_host", "bhg_frame_set_mesh_build", "bhg_frame_mesh_build_info",
 )
+MESH_DEVICE_LEAF_MAX = 64  # the largest leaf_size the device build takes (BHG_MESH_BUILD_DEVICE)
 # the rebuild_ratio of Frame.refit_mesh and the add-on when none is given (DESIGN.md section 22 has the table it is read off: at
 # area_now / area_build = 1.13 the refitted tree traced as fast as a fresh one, at 1.55 it lost more than the rebuild costs)
 MESH_REBUILD_RATIO = 1.5
@@ -786,6 +789,26 @@ def load():
     L.bhg_mesh_range.argtypes = [C.c_void_p, _dp, _dp]
     L.bhg_mesh_boxes_host.restype = C.c_int
     L.bhg_mesh_boxes_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    L.bhg_mesh_create_device.restype = C.c_int
+    L.bhg_mesh_create_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32, C.c_size_t,
+                                         C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]
+    L.bhg_mesh_rebuild_device.restype = C.c_int
+    L.bhg_mesh_rebuild_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.bhg_mesh_rebuild.restype = C.c_int
+    L.bhg_mesh_rebuild.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.bhg_mesh_build_info.restype = C.c_int
+    L.bhg_mesh_build_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_size_t),
+                                      C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]
+    L.bhg_mesh_bvh_morton_host.restype = C.c_int
+    L.bhg_mesh_bvh_morton_host.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.bhg_mesh_tree_host.restype = C.c_int
+    L.bhg_mesh_tree_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.bhg_frame_set_mesh_build.restype = C.c_int
+    L.bhg_frame_set_mesh_build.argtypes = [C.c_void_p, C.c_int]
+    L.bhg_frame_mesh_build_info.restype = C.c_int
+    L.bhg_frame_mesh_build_info.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_size_t),
+                                            C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]
     L.bhg_frame_refit_mesh.restype = C.c_int
     L.bhg_frame_refit_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double]
     L.bhg_frame_mesh_refit_info.restype = C.c_int
@@ -843,7 +866,7 @@ def _mesh_arrays(vertices, triangles):
     return V, np.ascontiguousarray(F, dtype=np.int32)
 
 
-def mesh_bvh_host(vertices, triangles, leaf_size=4):
+def mesh_bvh_host(vertices, triangles, leaf_size=4, _call="bhg_mesh_bvh_host"):
     """bhg_mesh_bvh_host: the flattened tree as the device gets it, built on the host (no context, no GPU) ->
     dict(box[nn,6], skip[nn], first[nn], count[nn], order[nt]).  On a box miss at node i go to skip[i], otherwise to i + 1; a leaf
     holds the triangles order[first : first + count]."""
@@ -854,10 +877,16 @@ def mesh_bvh_host(vertices, triangles, leaf_size=4):
     skip, first, count = (np.empty(cap, np.int32) for _ in range(3))
     order = np.empty(nt, np.int32)
     nn = C.c_size_t(0)
-    _check(load().bhg_mesh_bvh_host(_addr(V), V.shape[0], _addr(F), nt, int(leaf_size), _addr(box), _addr(skip), _addr(first),
-                                    _addr(count), _addr(order), cap, C.byref(nn)))
+    _check(getattr(load(), _call)(_addr(V), V.shape[0], _addr(F), nt, int(leaf_size), _addr(box), _addr(skip), _addr(first),
+                                  _addr(count), _addr(order), cap, C.byref(nn)))
     n = nn.value
     return {"box": box[:n].copy(), "skip": skip[:n].copy(), "first": first[:n].copy(), "count": count[:n].copy(), "order": order}
+
+
+def mesh_bvh_morton_host(vertices, triangles, leaf_size=4):
+    """bhg_mesh_bvh_morton_host: the tree the DEVICE build makes (DESIGN.md section 23), stated on the host (no context, no GPU);
+    mesh_bvh_host's dict.  The triangles in the order of a 63-bit Morton key of their centroids, every range split by count."""
+    return mesh_bvh_host(vertices, triangles, leaf_size, _call="bhg_mesh_bvh_morton_host")
 
 
 def _topology_arrays(tree):
@@ -888,35 +917,127 @@ def mesh_refit_schedule_host(tree):
     return nodes[:n.value].copy(), off
 
 
-def _device_f64(a, shape, what):
+def _device_f64(a, shape, what, dtype="float64"):
     """The device address of a float64, C-contiguous device array of the given shape: anything with data_ptr() (a torch tensor)."""
     if tuple(a.shape) != tuple(shape):
         raise ValueError(f"{what} must have shape {list(shape)}")
-    if "float64" not in str(a.dtype) or not a.is_contiguous() or not getattr(a, "is_cuda", True):
-        raise ValueError(f"{what} must be a contiguous float64 device array")
+    if dtype not in str(a.dtype) or not a.is_contiguous() or not getattr(a, "is_cuda", True):
+        raise ValueError(f"{what} must be a contiguous {dtype} device array")
     return a.data_ptr()
+
+
+def _device_mesh_arrays(vertices, triangles, normals):
+    """(addresses of V, F, N or None, nv, nt) of device arrays [nv, 3] float64, [nt, 3] int32, [nv, 3] float64"""
+    if len(vertices.shape) != 2 or len(triangles.shape) != 2:
+        raise ValueError("vertices must have shape [nv, 3] and triangles [nt, 3]")
+    nv, nt = int(vertices.shape[0]), int(triangles.shape[0])
+    dv = _device_f64(vertices, (nv, 3), "vertices")
+    df = _device_f64(triangles, (nt, 3), "triangles", "int32")
+    dn = None if normals is None else _device_f64(normals, (nv, 3), "vertex_normals")
+    return dv, df, dn, nv, nt
+
+
+def _capacity(capacity):
+    """capacity: None (the counts themselves: 0, 0) or (cap_vertices, cap_triangles)"""
+    if capacity is None:
+        return 0, 0
+    cv, ct = (int(x) for x in capacity)
+    if cv < 0 or ct < 0:
+        raise ValueError("capacity must be (cap_vertices, cap_triangles), both >= 0")
+    return cv, ct
 
 
 class Mesh:
     """bhg_mesh: a triangle mesh on a context's device.  vertices [nv, 3] float64, Cartesian and centred on
     the hole; triangles [nt, 3] int32; vertex_normals [nv, 3] or None (flat shading).  Closes with its context."""
 
-    def __init__(self, ctx: "Context", vertices, triangles, vertex_normals=None, leaf_size=4):
+    def __init__(self, ctx: "Context", vertices, triangles, vertex_normals=None, leaf_size=4, build="host", capacity=None):
+        """build: "host" (bhg_mesh_create, the default) or "device" (the arrays are uploaded and the tree is built there,
+        DESIGN.md section 23).  capacity: (cap_vertices, cap_triangles) a device-built mesh reserves for later rebuild() calls;
+        None: the counts themselves."""
+        if build not in ("host", "device"):
+            raise ValueError('build must be "host" or "device"')
+        if build == "host" and capacity is not None:
+            raise ValueError('capacity goes with build="device": a host-built mesh has its own counts as capacity')
         V, F = _mesh_arrays(vertices, triangles)
         N = None
         if vertex_normals is not None:
             N = np.ascontiguousarray(vertex_normals, dtype=np.float64)
             if N.shape != V.shape:
                 raise ValueError("vertex_normals must have the shape of vertices")
+        if build == "device":
+            import torch
+            dev = torch.device("cuda", ctx.device)
+            up = lambda a: None if a is None else torch.from_numpy(a).to(dev)   # noqa: E731
+            self._adopt(ctx, *self._create_device(ctx, up(V), up(F), up(N), leaf_size, capacity, 0))
+            return
         h = C.c_void_p()
         _check(load().bhg_mesh_create(ctx._h, _addr(V), V.shape[0], _addr(F), F.shape[0], None if N is None else _addr(N),
                                       int(leaf_size), C.byref(h)))
+        self._adopt(ctx, h, V.shape[0], F.shape[0], N is not None)
+
+    def _adopt(self, ctx, h, nv, nt, has_normals):
         self._h = h
         self.ctx = ctx
-        self.n_vertices, self.n_triangles = V.shape[0], F.shape[0]
-        self.has_normals = N is not None
+        self.n_vertices, self.n_triangles = nv, nt
+        self.has_normals = has_normals
         self._instances = []
         ctx._meshes.append(self)
+
+    @staticmethod
+    def _create_device(ctx, d_vertices, d_triangles, d_normals, leaf_size, capacity, stream):
+        dv, df, dn, nv, nt = _device_mesh_arrays(d_vertices, d_triangles, d_normals)
+        cv, ct = _capacity(capacity)
+        h = C.c_void_p()
+        _check(load().bhg_mesh_create_device(ctx._h, C.c_void_p(dv), nv, C.c_void_p(df), nt, C.c_void_p(dn), int(leaf_size), cv, ct,
+                                             C.c_void_p(stream or None), C.byref(h)))
+        return h, nv, nt, dn is not None
+
+    @classmethod
+    def from_device(cls, ctx: "Context", d_vertices, d_triangles, d_normals=None, leaf_size=4, capacity=None, stream=0):
+        """bhg_mesh_create_device: a mesh built on the device from arrays that lie there (torch tensors on the context's device:
+        vertices and normals [nv, 3] float64, triangles [nt, 3] int32, contiguous).  Blocking."""
+        self = cls.__new__(cls)
+        self._adopt(ctx, *cls._create_device(ctx, d_vertices, d_triangles, d_normals, leaf_size, capacity, stream))
+        return self
+
+    def rebuild(self, vertices, triangles, vertex_normals=None, stream=0):
+        """A new triangle list (and vertices, and normals for a mesh created with them) into the mesh, within its capacity: the tree
+        is built anew on the device, in place (bhg_mesh_rebuild / bhg_mesh_rebuild_device).  numpy arrays go
+        through the host call, device arrays (all of them) through the device call on `stream`.  Blocking.  Instance sets of the
+        mesh need a set() afterwards."""
+        dev = hasattr(vertices, "data_ptr")
+        if hasattr(triangles, "data_ptr") != dev or (vertex_normals is not None and hasattr(vertex_normals, "data_ptr") != dev):
+            raise ValueError("vertices, triangles and vertex_normals must all be host arrays or all device arrays")
+        if dev:
+            dv, df, dn, nv, nt = _device_mesh_arrays(vertices, triangles, vertex_normals)
+            _check(load().bhg_mesh_rebuild_device(self.ctx._h, self._h, C.c_void_p(dv), nv, C.c_void_p(df), nt, C.c_void_p(dn),
+                                                  C.c_void_p(stream or None)))
+        else:
+            V, F = _mesh_arrays(vertices, triangles)
+            N = None if vertex_normals is None else np.ascontiguousarray(vertex_normals, dtype=np.float64)
+            if N is not None and N.shape != V.shape:
+                raise ValueError("vertex_normals must have the shape of vertices")
+            nv, nt = V.shape[0], F.shape[0]
+            _check(load().bhg_mesh_rebuild(self.ctx._h, self._h, _addr(V), nv, _addr(F), nt, None if N is None else _addr(N)))
+        self.n_vertices, self.n_triangles = nv, nt
+
+    def build_info(self):
+        """dict(built_on_device, builds, cap_vertices, cap_triangles, allocations) (bhg_mesh_build_info): builds counts the creating
+        build too; allocations the device allocations made over the mesh's life."""
+        dev, builds, cv, ct, allocs = C.c_int32(0), C.c_uint64(0), C.c_size_t(0), C.c_size_t(0), C.c_uint64(0)
+        _check(load().bhg_mesh_build_info(self._h, C.byref(dev), C.byref(builds), C.byref(cv), C.byref(ct), C.byref(allocs)))
+        return {"built_on_device": bool(dev.value), "builds": builds.value, "cap_vertices": cv.value, "cap_triangles": ct.value,
+                "allocations": allocs.value}
+
+    def download_tree(self):
+        """dict(skip[nn], first[nn], count[nn], order[nt]): the device's topology and leaf order (bhg_mesh_tree_host; blocking)"""
+        nn = self.info()[0]
+        skip, first, count = (np.empty(nn, np.int32) for _ in range(3))
+        order = np.empty(self.n_triangles, np.int32)
+        n = C.c_size_t(0)
+        _check(load().bhg_mesh_tree_host(self._h, _addr(skip), _addr(first), _addr(count), _addr(order), nn, C.byref(n)))
+        return {"skip": skip, "first": first, "count": count, "order": order}
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1400,12 +1521,31 @@ class Frame:
             return
         _check(load().bhg_frame_set_object_motion(self._h, C.byref(make_object_motion(velocity, angular_velocity))))
 
-    def set_mesh(self, vertices=None, triangles=None, vertex_normals=None, leaf_size=4, chord=None, material=None):
+    def set_mesh_build(self, on):
+        """The device build for the frame's meshes (bhg_frame_set_mesh_build), default off: each device
+        builds its tree itself from the frame's host copy, a later set_mesh() that fits the held mesh's capacity rebuilds it in
+        place, and refit_mesh()'s rebuild does too.  The images are the host-built frame's, bit for bit."""
+        _check(load().bhg_frame_set_mesh_build(self._h, 1 if on else 0))
+
+    def mesh_build_info(self, shard=0):
+        """Mesh.build_info() of the mesh on the frame's device number `shard` (bhg_frame_mesh_build_info)"""
+        dev, builds, cv, ct, allocs = C.c_int32(0), C.c_uint64(0), C.c_size_t(0), C.c_size_t(0), C.c_uint64(0)
+        _check(load().bhg_frame_mesh_build_info(self._h, int(shard), C.byref(dev), C.byref(builds), C.byref(cv), C.byref(ct),
+                                                C.byref(allocs)))
+        return {"built_on_device": bool(dev.value), "builds": builds.value, "cap_vertices": cv.value, "cap_triangles": ct.value,
+                "allocations": allocs.value}
+
+    def set_mesh(self, vertices=None, triangles=None, vertex_normals=None, leaf_size=4, chord=None, material=None, build=None):
         """A triangle mesh in every later render (bhg_frame_set_mesh): vertices [nv, 3] float64, Cartesian
         and centred on the hole, triangles [nt, 3] int32, vertex_normals [nv, 3] or None (flat shading), chord the sub-chord
         length of the trace (None: a quarter of r_s at render time), material a MeshMaterial or None (white, no emission).
         Everything is copied.  Not with scene spheres, redshift, the thermal disk, object motion or object textures (refused
-        at render).  set_mesh(None): off -- the frame as without a mesh, bit for bit."""
+        at render).  set_mesh(None): off -- the frame as without a mesh, bit for bit.  build: "host" / "device" is
+        set_mesh_build() first; None leaves the switch as it is."""
+        if build not in (None, "host", "device"):
+            raise ValueError('build must be None, "host" or "device"')
+        if build is not None:
+            self.set_mesh_build(build == "device")
         if vertices is None:
             _check(load().bhg_frame_set_mesh(self._h, None, 0, None, 0, None, 0, 0.0, None))
             self._mesh_nv = None

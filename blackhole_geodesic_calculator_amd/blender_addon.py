@@ -61,6 +61,11 @@ Known deviations from the reference, all deliberate:
     bits, the vertex count the same -- sends the vertices alone and every device refits its tree on the device
     (bhg_frame_refit_mesh): an armature, a shape key, cloth, a wave modifier.  This holds for the concatenated mesh and for the
     single datablock of curved_space_mesh_instances alike.  Anything else takes the full path above, silently.
+  * scene.curved_space_mesh_build (default 0): with curved_space_meshes = 1 on the device path, the frame's
+    devices build their trees themselves (bhg_frame_set_mesh_build), and a render whose triangle list, vertex count or UVs
+    changed -- a fluid surface, a boolean, a remesher, animated subdivision -- rebuilds the mesh each device holds in place where
+    its counts fit, instead of building a new tree on the host.  curved_space_mesh_refit keeps deciding the vertices-only case.
+    The images are those of 0, bit for bit.
 """
 import warnings
 import os
@@ -363,6 +368,7 @@ class RelativisticRenderEngine(bpy.types.RenderEngine):
                 "images": images if any_uv else [], "emission": emission, "offsets": offsets,
                 "instances": None if plan is None else plan[1],
                 "refit": float(getattr(depsgraph.scene, "curved_space_mesh_refit", 0) or 0) != 0.0,
+                "build": float(getattr(depsgraph.scene, "curved_space_mesh_build", 0) or 0) != 0.0,
                 # (instanced: the datablock's arrays before the scale, and the scale -- what _set_device_mesh compares)
                 "local": None if plan is None else {"co": local_co, "normals": local_nrm, "scale": plan[0]}}
 
@@ -401,7 +407,11 @@ class RelativisticRenderEngine(bpy.types.RenderEngine):
             all((mesh[k] is None) == (held[k] is None) and (mesh[k] is None or np.array_equal(mesh[k], held[k]))
                 for k in ("triangles", "tri_uv", "tri_tex")) and \
             not same_array("vertices", mesh["vertices"], held["vertices"])
-        self.device_mesh_action = "kept" if same else "refit" if refit else "set"
+        # scene.curved_space_mesh_build: the frame's devices build their trees themselves, and a mesh whose
+        # triangle list, vertex count or UVs changed goes into the mesh they hold, in place, where its counts fit -- "rebuild";
+        # curved_space_mesh_refit keeps deciding the vertices-only case above
+        build = bool(mesh.get("build"))
+        self.device_mesh_action = "kept" if same else "refit" if refit else "rebuild" if build and held is not None else "set"
         if refit:
             from . import _ffi
             fr.refit_mesh(mesh["vertices"], mesh["normals"], rebuild_ratio=_ffi.MESH_REBUILD_RATIO)
@@ -410,6 +420,9 @@ class RelativisticRenderEngine(bpy.types.RenderEngine):
             from . import _ffi
             material = _ffi.MeshMaterial(tri_uv=mesh["tri_uv"], tri_tex=mesh["tri_tex"] if mesh["tri_uv"] is not None else None,
                                          textures=[self._image_pixels(n) for n in mesh["images"]], emission=mesh["emission"])
+            if build != getattr(fr, "mesh_build_on", False):     # (the frame's default is off: a scene without the switch calls nothing)
+                fr.set_mesh_build(build)
+                fr.mesh_build_on = build
             fr.set_mesh(mesh["vertices"], mesh["triangles"], vertex_normals=mesh["normals"], material=material)
             fr.mesh_held = {**{k: mesh[k] for k in ("vertices", "triangles", "normals", "tri_uv", "tri_tex", "emission")}, "ids": ids,
                             "instances": None, "local": local}      # (set_mesh turns instances off)
@@ -730,6 +743,7 @@ class CUSTOM_RENDER_PT_blackhole(RenderButtonsPanel, Panel):
              ("curved_space_meshes", "Mesh objects as triangles (0/1)"),
              ("curved_space_mesh_instances", "Linked duplicates as instances (0/1)"),
              ("curved_space_mesh_refit", "Deforming meshes refit, not rebuilt (0/1)"),
+             ("curved_space_mesh_build", "Mesh trees built on the GPU (0/1)"),
              ("device_shading", "Shade on the GPU (0/1)"), ("render_devices", "GPUs to render on"))
 
     def draw(self, context):
@@ -761,6 +775,7 @@ EXTRA_PROPS = [
     ("curved_space_meshes", bpy.props.FloatProperty(name="curved_space_meshes", default=0)),
     ("curved_space_mesh_instances", bpy.props.FloatProperty(name="curved_space_mesh_instances", default=0)),
     ("curved_space_mesh_refit", bpy.props.FloatProperty(name="curved_space_mesh_refit", default=0)),
+    ("curved_space_mesh_build", bpy.props.FloatProperty(name="curved_space_mesh_build", default=0)),
     ("device_shading", bpy.props.FloatProperty(name="device_shading", default=0)),
     ("render_devices", bpy.props.FloatProperty(name="render_devices", default=1)),
 ]

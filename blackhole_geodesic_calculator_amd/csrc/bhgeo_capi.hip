@@ -26,6 +26,7 @@
 #include "geodesic_kernels.h"
 #include "prefix_clearance.h"
 #include "mesh_bvh.h"
+#include "mesh_build.h"
 #include "mesh_refit.h"
 #include "trace_call.h"
 
@@ -1117,8 +1118,17 @@ struct bhg_mesh {
     std::vector<int32_t> level_off;         // [BVH_MAX_DEPTH + 2]
     int32_t n_inner = 0;
     char *d_refit = nullptr;  // the first refit's allocation, kept: summary | area [nn] | staging of host vertices and normals
-    uint64_t generation = 0;  // +1 per successful refit
+    uint64_t generation = 0;  // +1 per successful refit or rebuild
     double area_build = 0.0, area_now = 0.0;
+    // the device build.  by_capacity: d and d_refit are laid out for cap_vertices / cap_triangles (a mesh of
+    // bhg_mesh_create_device, or one of bhg_mesh_create since its first rebuild) and not for the counts the host builder was given
+    int32_t leaf_size = 0;
+    size_t cap_vertices = 0, cap_triangles = 0;
+    bool by_capacity = false, built_on_device = false;
+    char *d_build = nullptr;  // record | keys in | keys out | values in | staging of host triangles | the sort's own storage
+    size_t sort_bytes = 0;
+    size_t topo_triangles = 0;              // the n_triangles whose Morton topology (at leaf_size) lies in d; 0: none
+    uint64_t builds = 0, allocations = 0;   // builds, the creating one included; device allocations over the mesh's life
 };
 
 // K rigid placements of one mesh: the device records, and what the host works out from them in O(K)
@@ -1874,6 +1884,11 @@ int bhg_mesh_create(bhg_context *c, const double *vertices, size_t n_vertices, c
     m->level_off = level_off;
     m->n_inner = (int32_t)level_nodes.size();
     m->area_build = m->area_now = bhg::area_sum(t.node_box.data(), nn);
+    m->leaf_size = leaf_size;
+    m->cap_vertices = n_vertices;
+    m->cap_triangles = n_triangles;
+    m->builds = 1;
+    m->allocations = 1;
     {
         std::lock_guard<std::mutex> lock(live_meshes_lock);
         m->serial = live_meshes_next++;
@@ -1894,6 +1909,7 @@ void bhg_mesh_destroy(bhg_mesh *m)
         DeviceGuard g(m->device);
         if (m->d) (void)hipFree(m->d);
         if (m->d_refit) (void)hipFree(m->d_refit);
+        if (m->d_build) (void)hipFree(m->d_build);
     }
     delete m;
 }
@@ -1936,9 +1952,14 @@ struct RefitScratch {
 
 int refit_scratch(bhg_mesh *m, RefitScratch &r)
 {
-    const size_t b_sum = (sizeof(bhg::MeshRefitSummary) + 7) & ~size_t(7), b_area = (size_t)m->n_nodes * sizeof(double),
-                 b_v = (size_t)m->n_vertices * 3 * sizeof(double);
-    if (!m->d_refit) HIP_TRY(hipMalloc((void **)&m->d_refit, b_sum + b_area + b_v * (m->has_normals ? 2 : 1)));
+    // (a mesh laid out by capacity holds room for every tree and vertex array a rebuild may bring: section 23)
+    const size_t nn = m->by_capacity ? 2 * m->cap_triangles - 1 : (size_t)m->n_nodes,
+                 nv = m->by_capacity ? m->cap_vertices : (size_t)m->n_vertices;
+    const size_t b_sum = (sizeof(bhg::MeshRefitSummary) + 7) & ~size_t(7), b_area = nn * sizeof(double), b_v = nv * 3 * sizeof(double);
+    if (!m->d_refit) {
+        HIP_TRY(hipMalloc((void **)&m->d_refit, b_sum + b_area + b_v * (m->has_normals ? 2 : 1)));
+        m->allocations++;
+    }
     r.summary = (bhg::MeshRefitSummary *)m->d_refit;
     r.area = (double *)(m->d_refit + b_sum);
     r.vertices = (double *)(m->d_refit + b_sum + b_area);
@@ -2089,6 +2110,450 @@ int bhg_mesh_boxes_host(const bhg_mesh *m, double *node_box, double *tri, size_t
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(node_box, m->view.node_box, (size_t)m->n_nodes * 6 * sizeof(double), hipMemcpyDeviceToHost));
     if (tri) HIP_TRY(hipMemcpy(tri, m->view.tri, (size_t)m->view.n_tris * 9 * sizeof(double), hipMemcpyDeviceToHost));
+    return BHG_OK;
+}
+
+// --- the device-side build: a Morton-order tree, rebuilt in place --------------------------------------
+
+}  // extern "C"
+
+namespace {
+
+size_t round8(size_t b) { return (b + 7) & ~size_t(7); }
+
+// the device image of a mesh laid out by capacity: bhg_mesh_create's arrays in its order, each with room for the largest tree
+// over cap_nt triangles (2 cap_nt - 1 nodes, cap_nt - 1 inner ones: leaf_size 1)
+struct MeshImage {
+    size_t o_tri, o_nrm, o_skip, o_first, o_count, o_order, o_slot, o_sv, o_lv, total;
+};
+
+MeshImage image_by_capacity(size_t cap_nt, bool normals)
+{
+    const size_t nn = 2 * cap_nt - 1;
+    const size_t b_box = nn * 6 * sizeof(double), b_tri = cap_nt * 9 * sizeof(double), b_nrm = normals ? b_tri : 0,
+                 b_node = round8(nn * sizeof(int32_t)), b_idx = round8(cap_nt * sizeof(int32_t)), b_sv = round8(cap_nt * 3 * sizeof(int32_t));
+    MeshImage g;
+    g.o_tri = b_box;
+    g.o_nrm = g.o_tri + b_tri;
+    g.o_skip = g.o_nrm + b_nrm;
+    g.o_first = g.o_skip + b_node;
+    g.o_count = g.o_first + b_node;
+    g.o_order = g.o_count + b_node;
+    g.o_slot = g.o_order + b_idx;
+    g.o_sv = g.o_slot + b_idx;
+    g.o_lv = g.o_sv + b_sv;
+    g.total = g.o_lv + b_idx;
+    return g;
+}
+
+void point_into_image(bhg_mesh *m, char *d, const MeshImage &g)
+{
+    m->d = d;
+    bhg::MeshView &v = m->view;
+    v.node_box = (const double *)d;
+    v.tri = (const double *)(d + g.o_tri);
+    v.tri_normals = m->has_normals ? (const double *)(d + g.o_nrm) : nullptr;
+    v.node_skip = (const int32_t *)(d + g.o_skip);
+    v.node_first = (const int32_t *)(d + g.o_first);
+    v.node_count = (const int32_t *)(d + g.o_count);
+    v.tri_order = (const int32_t *)(d + g.o_order);
+    v.tri_slot = (const int32_t *)(d + g.o_slot);
+    m->slot_vert = (const int32_t *)(d + g.o_sv);
+    m->level_nodes = (const int32_t *)(d + g.o_lv);
+}
+
+// the build's own storage: record | keys in | keys out | values in | staging of host triangles | the sort's storage
+struct BuildStorage {
+    bhg::MeshBuildRecord *record;
+    unsigned long long *keys_in, *keys_out;
+    int32_t *vals_in, *triangles;
+    void *sort_temp;
+};
+
+int build_storage(bhg_mesh *m, BuildStorage &b)
+{
+    const size_t cap = m->cap_triangles;
+    const size_t b_rec = (sizeof(bhg::MeshBuildRecord) + 255) & ~size_t(255), b_key = cap * sizeof(unsigned long long),
+                 b_val = round8(cap * sizeof(int32_t)), b_f = round8(cap * 3 * sizeof(int32_t));
+    const size_t o_sort = (b_rec + 2 * b_key + b_val + b_f + 255) & ~size_t(255);
+    if (!m->d_build) {
+        // (the sort's storage is asked for once, for the capacity)
+        HIP_TRY(bhg::mesh_build_sort_bytes(cap, &m->sort_bytes));
+        HIP_TRY(hipMalloc((void **)&m->d_build, o_sort + m->sort_bytes));
+        m->allocations++;
+    }
+    b.record = (bhg::MeshBuildRecord *)m->d_build;
+    b.keys_in = (unsigned long long *)(m->d_build + b_rec);
+    b.keys_out = (unsigned long long *)(m->d_build + b_rec + b_key);
+    b.vals_in = (int32_t *)(m->d_build + b_rec + 2 * b_key);
+    b.triangles = (int32_t *)(m->d_build + b_rec + 2 * b_key + b_val);
+    b.sort_temp = m->d_build + o_sort;
+    return BHG_OK;
+}
+
+// A mesh of bhg_mesh_create, laid out for its own tree, moves into an image laid out by capacity before its first rebuild: the
+// arrays are copied as they are, so the mesh stays what it was should the rebuild then be refused.  The device is the mesh's.
+int reserve_by_capacity(bhg_mesh *m)
+{
+    if (m->by_capacity) return BHG_OK;
+    const MeshImage g = image_by_capacity(m->cap_triangles, m->has_normals);
+    const size_t nn = (size_t)m->n_nodes, nt = (size_t)m->view.n_tris;
+    char *d = nullptr;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMalloc((void **)&d, g.total));
+    const bhg::MeshView &v = m->view;
+    hipError_t e = hipMemcpy(d, v.node_box, nn * 6 * sizeof(double), hipMemcpyDeviceToDevice);
+    auto copy = [&](size_t off, const void *src, size_t bytes) {
+        if (e == hipSuccess && src && bytes) e = hipMemcpy(d + off, src, bytes, hipMemcpyDeviceToDevice);
+    };
+    copy(g.o_tri, v.tri, nt * 9 * sizeof(double));
+    copy(g.o_nrm, v.tri_normals, nt * 9 * sizeof(double));
+    copy(g.o_skip, v.node_skip, nn * sizeof(int32_t));
+    copy(g.o_first, v.node_first, nn * sizeof(int32_t));
+    copy(g.o_count, v.node_count, nn * sizeof(int32_t));
+    copy(g.o_order, v.tri_order, nt * sizeof(int32_t));
+    copy(g.o_slot, v.tri_slot, nt * sizeof(int32_t));
+    copy(g.o_sv, m->slot_vert, nt * 3 * sizeof(int32_t));
+    copy(g.o_lv, m->level_nodes, (size_t)m->n_inner * sizeof(int32_t));
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return fail_hip(e, "mesh rebuild: the image by capacity");
+    }
+    (void)hipFree(m->d);
+    point_into_image(m, d, g);
+    m->allocations++;
+    // (the refit's scratch is laid out anew with the image: it holds nothing between calls)
+    if (m->d_refit) {
+        (void)hipFree(m->d_refit);
+        m->d_refit = nullptr;
+    }
+    m->by_capacity = true;
+    m->topo_triangles = 0;
+    return BHG_OK;
+}
+
+// what the build calls refuse of their counts and arrays before the device is touched (cap: 0 = none yet, bhg_mesh_create_device)
+int build_counts_check(const void *vertices, size_t nv, const void *triangles, size_t nt)
+{
+    if (!vertices || !triangles) return fail(BHG_E_INVALID, "mesh: vertices / triangles is NULL");
+    if (nv == 0 || nt == 0) return fail(BHG_E_INVALID, "mesh: n_vertices and n_triangles must be > 0");
+    if (nv > 0x7FFFFFFFull || nt > 0x7FFFFFFFull) return fail(BHG_E_INVALID, "mesh: n_vertices and n_triangles must be <= 2^31 - 1");
+    return BHG_OK;
+}
+
+int build_leaf_check(int32_t leaf_size)
+{
+    if (leaf_size < 1 || leaf_size > bhg::MORTON_LEAF_MAX) {
+        char msg[160];
+        std::snprintf(msg, sizeof msg, "mesh device build: leaf_size %d must be in [1, %d] (larger leaves: bhg_mesh_create)", (int)leaf_size,
+                      (int)bhg::MORTON_LEAF_MAX);
+        return fail(BHG_E_INVALID, msg);
+    }
+    return BHG_OK;
+}
+
+int rebuild_check(const bhg_context *c, const bhg_mesh *m, const void *vertices, size_t nv, const void *triangles, size_t nt,
+                  const void *normals)
+{
+    if (!m) return fail(BHG_E_INVALID, "mesh is NULL");
+    BHG_TRY(build_counts_check(vertices, nv, triangles, nt));
+    BHG_TRY(build_leaf_check(m->leaf_size));
+    if (nv > m->cap_vertices || nt > m->cap_triangles) {
+        char msg[200];
+        std::snprintf(msg, sizeof msg, "mesh rebuild: n_vertices %zu / n_triangles %zu exceed the mesh's capacity %zu / %zu", nv, nt,
+                      m->cap_vertices, m->cap_triangles);
+        return fail(BHG_E_INVALID, msg);
+    }
+    if (normals && !m->has_normals)
+        return fail(BHG_E_INVALID, "mesh rebuild: vertex_normals given to a mesh that was created without them");
+    if (!normals && m->has_normals)
+        return fail(BHG_E_INVALID, "mesh rebuild: vertex_normals is NULL for a mesh that was created with them");
+    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
+    if (m->device != c->device) return fail(BHG_E_INVALID, "the mesh lives on another device than the context");
+    return BHG_OK;
+}
+
+// The build proper.  d_v, d_f, d_n: device arrays within the mesh's capacity, not looked at yet.  The mesh is laid out by capacity
+// and owns its build and refit storage (b, r); the device is c's and current.  Nothing of the mesh is written before the scan of
+// all three arrays has been read back and found clean, and no kernel follows a triangle index before that either.
+int build_run(bhg_context *c, bhg_mesh *m, const BuildStorage &b, const RefitScratch &r, const double *d_v, size_t nv, const int32_t *d_f,
+              size_t nt, const double *d_n, hipStream_t s)
+{
+    bhg::MeshBuildArgs ba;
+    std::memset(&ba, 0, sizeof(ba));
+    ba.vertices = d_v;
+    ba.triangles = d_f;
+    ba.n_vertices = (int32_t)nv;
+    ba.n_tris = (int32_t)nt;
+    ba.record = b.record;
+    bhg::MeshRefitArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.vertices = d_v;
+    a.normals = d_n;
+    a.n_vertices = (int32_t)nv;
+    a.summary = r.summary;
+    bhg::MeshRefitSummary sum;
+    bhg::MeshBuildRecord rec;
+    if (c->stream != s) HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemsetAsync(r.summary, 0, sizeof(sum), s));
+    HIP_TRY(hipMemsetAsync(b.record, 0, sizeof(rec), s));
+    HIP_TRY(bhg::launch_mesh_build_scan(ba, s));
+    HIP_TRY(bhg::launch_mesh_refit_scan(a, s));
+    HIP_TRY(hipMemcpyAsync(&rec, b.record, sizeof(rec), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&sum, r.summary, sizeof(sum), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (sum.nonfinite & 1u) return fail(BHG_E_INVALID, "mesh: every vertex must be finite");
+    if (rec.bad_index) return fail(BHG_E_INVALID, "mesh: a triangle index lies outside [0, n_vertices)");
+    if (sum.nonfinite & 2u) return fail(BHG_E_INVALID, "mesh: every vertex normal must be finite");
+    // the topology: a function of (nt, leaf_size), written by the host and kept while both stand
+    const MeshImage g = image_by_capacity(m->cap_triangles, m->has_normals);
+    if (m->topo_triangles != nt) {
+        std::vector<int32_t> skip, first, count, level_nodes, level_off;
+        int32_t depth = 0;
+        bhg::morton_topology(nt, m->leaf_size, skip, first, count, depth);
+        const size_t nn = skip.size();
+        if (!bhg::inner_levels(skip.data(), count.data(), nn, level_nodes, level_off))
+            return fail(BHG_E_INVALID, "mesh device build: the tree is deeper than BVH_MAX_DEPTH");
+        m->topo_triangles = 0;      // (until all four arrays are up)
+        HIP_TRY(hipMemcpyAsync(m->d + g.o_skip, skip.data(), nn * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(m->d + g.o_first, first.data(), nn * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(m->d + g.o_count, count.data(), nn * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        if (!level_nodes.empty())
+            HIP_TRY(hipMemcpyAsync(m->d + g.o_lv, level_nodes.data(), level_nodes.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        // (the vectors go out of scope below: the copies from pageable memory have been staged when the calls return, and the
+        // stream is waited for before this function does)
+        HIP_TRY(hipStreamSynchronize(s));
+        m->n_nodes = (int64_t)nn;
+        m->view.n_nodes = (int32_t)nn;
+        m->depth = depth;
+        m->n_inner = (int32_t)level_nodes.size();
+        m->level_off = level_off;
+        m->topo_triangles = nt;
+    }
+    m->view.n_tris = (int32_t)nt;
+    m->n_vertices = (int32_t)nv;
+    ba.n_nodes = m->view.n_nodes;
+    ba.node_first = m->view.node_first;
+    ba.node_count = m->view.node_count;
+    ba.keys_in = b.keys_in;
+    ba.keys_out = b.keys_out;
+    ba.vals_in = b.vals_in;
+    ba.sort_temp = b.sort_temp;
+    ba.sort_temp_bytes = m->sort_bytes;
+    ba.tri_order = const_cast<int32_t *>(m->view.tri_order);
+    ba.tri_slot = const_cast<int32_t *>(m->view.tri_slot);
+    ba.slot_vert = const_cast<int32_t *>(m->slot_vert);
+    a.n_tris = m->view.n_tris;
+    a.n_nodes = m->view.n_nodes;
+    a.n_inner = m->n_inner;
+    a.slot_vert = m->slot_vert;
+    a.node_skip = m->view.node_skip;
+    a.node_first = m->view.node_first;
+    a.node_count = m->view.node_count;
+    a.level_nodes = m->level_nodes;
+    std::memcpy(a.level_off, m->level_off.data(), sizeof(a.level_off));
+    a.node_box = const_cast<double *>(m->view.node_box);
+    a.tri = const_cast<double *>(m->view.tri);
+    a.tri_normals = const_cast<double *>(m->view.tri_normals);
+    a.area = r.area;
+    // (the scan's flags are zero; the refit max-es d2_max into the same record)
+    HIP_TRY(bhg::launch_mesh_build(ba, s));
+    HIP_TRY(bhg::launch_mesh_refit(a, s));
+    HIP_TRY(hipMemcpyAsync(&sum, r.summary, sizeof(sum), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    std::memcpy(m->box, sum.box, sizeof(m->box));
+    double d2 = 0.0;
+    for (int q = 0; q < 3; q++) {
+        const double gap = std::max(std::max(m->box[q], -m->box[3 + q]), 0.0);
+        d2 += gap * gap;
+    }
+    double far2;
+    std::memcpy(&far2, &sum.d2_max, sizeof(far2));
+    m->d_min = std::sqrt(d2) * (1.0 - 1e-14);
+    m->d_max = std::sqrt(far2) * (1.0 + 1e-14);
+    m->area_build = m->area_now = sum.area;
+    m->built_on_device = true;
+    return BHG_OK;
+}
+
+// a rebuild of a live mesh: the storage, the move into an image by capacity, the build, the counters
+int rebuild_run(bhg_context *c, bhg_mesh *m, const double *v, size_t nv, const int32_t *f, size_t nt, const double *n, bool host_arrays,
+                hipStream_t s)
+{
+    BHG_TRY(reserve_by_capacity(m));
+    BuildStorage b;
+    RefitScratch r;
+    BHG_TRY(build_storage(m, b));
+    BHG_TRY(refit_scratch(m, r));
+    if (host_arrays) {
+        // (the staging arrays are the mesh's own: a rebuild is blocking, so no earlier one still reads them)
+        HIP_TRY(hipMemcpyAsync(r.vertices, v, nv * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(b.triangles, f, nt * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        if (n) HIP_TRY(hipMemcpyAsync(r.normals, n, nv * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+        v = r.vertices;
+        f = b.triangles;
+        if (n) n = r.normals;
+    }
+    BHG_TRY(build_run(c, m, b, r, v, nv, f, nt, n, s));
+    m->generation++;
+    m->builds++;
+    return BHG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bhg_mesh_bvh_morton_host(const double *vertices, size_t n_vertices, const int32_t *triangles, size_t n_triangles, int32_t leaf_size,
+                             double *node_box, int32_t *node_skip, int32_t *node_first, int32_t *node_count, int32_t *tri_order,
+                             size_t cap, size_t *n_nodes)
+{
+    if (const char *why = bhg::mesh_refusal(vertices, n_vertices, triangles, n_triangles, leaf_size)) return fail(BHG_E_INVALID, why);
+    if (!n_nodes) return fail(BHG_E_INVALID, "n_nodes is NULL");
+    bhg::HostBvh t;
+    bhg::build_bvh_morton(vertices, triangles, n_triangles, leaf_size, t);
+    const size_t nn = t.node_skip.size();
+    *n_nodes = nn;
+    if (nn > cap) return fail(BHG_E_INVALID, "the tree has more nodes than cap (2 * n_triangles - 1 always suffices)");
+    if (!node_box || !node_skip || !node_first || !node_count || !tri_order) return fail(BHG_E_INVALID, "an output array is NULL");
+    std::memcpy(node_box, t.node_box.data(), nn * 6 * sizeof(double));
+    std::memcpy(node_skip, t.node_skip.data(), nn * sizeof(int32_t));
+    std::memcpy(node_first, t.node_first.data(), nn * sizeof(int32_t));
+    std::memcpy(node_count, t.node_count.data(), nn * sizeof(int32_t));
+    std::memcpy(tri_order, t.tri_order.data(), n_triangles * sizeof(int32_t));
+    return BHG_OK;
+}
+
+}  // extern "C"
+
+namespace bhg {
+
+// bhg_mesh_create_device, and the same from HOST arrays (bhgeo_frame.hip: a frame holds its mesh on the host), which are uploaded
+// into the new mesh's staging arrays first
+int mesh_create_built_on_device(bhg_context *c, const double *d_vertices, size_t n_vertices, const int32_t *d_triangles,
+                                size_t n_triangles, const double *d_vertex_normals, int32_t leaf_size, size_t cap_vertices,
+                                size_t cap_triangles, bool host_arrays, hipStream_t stream, bhg_mesh **out)
+{
+    if (!out) return fail(BHG_E_INVALID, "out is NULL");
+    *out = nullptr;
+    BHG_TRY(build_counts_check(d_vertices, n_vertices, d_triangles, n_triangles));
+    BHG_TRY(build_leaf_check(leaf_size));
+    if (cap_vertices == 0) cap_vertices = n_vertices;
+    if (cap_triangles == 0) cap_triangles = n_triangles;
+    if (cap_vertices < n_vertices || cap_triangles < n_triangles)
+        return fail(BHG_E_INVALID, "mesh device build: cap_vertices / cap_triangles must be 0 or at least the counts");
+    if (cap_vertices > 0x7FFFFFFFull || cap_triangles > 0x7FFFFFFFull)
+        return fail(BHG_E_INVALID, "mesh device build: cap_vertices and cap_triangles must be <= 2^31 - 1");
+    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
+    ENTER_DEVICE(c->device);
+    bhg_mesh *m = new (std::nothrow) bhg_mesh;
+    if (!m) return fail(BHG_E_NOMEM, "out of host memory");
+    m->device = c->device;
+    m->has_normals = d_vertex_normals != nullptr;
+    m->leaf_size = leaf_size;
+    m->cap_vertices = cap_vertices;
+    m->cap_triangles = cap_triangles;
+    m->by_capacity = true;
+    // everything the mesh will ever hold on the device, now: the image, the build's storage, the refit's
+    const MeshImage g = image_by_capacity(cap_triangles, m->has_normals);
+    char *d = nullptr;
+    BuildStorage b;
+    RefitScratch r;
+    int rc = BHG_OK;
+    const hipError_t e = hipMalloc((void **)&d, g.total);
+    if (e != hipSuccess) rc = fail_hip(e, "bhg_mesh_create_device: device image");
+    if (rc == BHG_OK) {
+        point_into_image(m, d, g);
+        m->allocations++;
+        rc = build_storage(m, b);
+    }
+    if (rc == BHG_OK) rc = refit_scratch(m, r);
+    if (rc == BHG_OK && host_arrays) {
+        const auto up = [&](void *dst, const void *src, size_t bytes) {
+            const hipError_t eu = rc == BHG_OK ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream) : hipSuccess;
+            if (eu != hipSuccess) rc = fail_hip(eu, "bhg_mesh_create_device: upload");
+        };
+        up(r.vertices, d_vertices, n_vertices * 3 * sizeof(double));
+        up(b.triangles, d_triangles, n_triangles * 3 * sizeof(int32_t));
+        if (d_vertex_normals) up(r.normals, d_vertex_normals, n_vertices * 3 * sizeof(double));
+        d_vertices = r.vertices;
+        d_triangles = b.triangles;
+        if (d_vertex_normals) d_vertex_normals = r.normals;
+    }
+    if (rc == BHG_OK) rc = build_run(c, m, b, r, d_vertices, n_vertices, d_triangles, n_triangles, d_vertex_normals, stream);
+    if (rc != BHG_OK) {
+        // (refused or failed: nothing stays allocated; the message is build_run's)
+        if (m->d) (void)hipFree(m->d);
+        if (m->d_build) (void)hipFree(m->d_build);
+        if (m->d_refit) (void)hipFree(m->d_refit);
+        delete m;
+        return rc;
+    }
+    m->builds = 1;
+    {
+        std::lock_guard<std::mutex> lock(live_meshes_lock);
+        m->serial = live_meshes_next++;
+        live_meshes[m] = m->serial;
+    }
+    *out = m;
+    return BHG_OK;
+}
+
+}  // namespace bhg
+
+extern "C" {
+
+int bhg_mesh_create_device(bhg_context *c, const double *d_vertices, size_t n_vertices, const int32_t *d_triangles, size_t n_triangles,
+                           const double *d_vertex_normals, int32_t leaf_size, size_t cap_vertices, size_t cap_triangles, void *stream,
+                           bhg_mesh **out)
+{
+    return bhg::mesh_create_built_on_device(c, d_vertices, n_vertices, d_triangles, n_triangles, d_vertex_normals, leaf_size,
+                                            cap_vertices, cap_triangles, false, (hipStream_t)stream, out);
+}
+
+int bhg_mesh_rebuild_device(bhg_context *c, bhg_mesh *m, const double *d_vertices, size_t n_vertices, const int32_t *d_triangles,
+                            size_t n_triangles, const double *d_vertex_normals, void *stream)
+{
+    BHG_TRY(rebuild_check(c, m, d_vertices, n_vertices, d_triangles, n_triangles, d_vertex_normals));
+    ENTER_DEVICE(c->device);
+    return rebuild_run(c, m, d_vertices, n_vertices, d_triangles, n_triangles, d_vertex_normals, false, (hipStream_t)stream);
+}
+
+int bhg_mesh_rebuild(bhg_context *c, bhg_mesh *m, const double *vertices, size_t n_vertices, const int32_t *triangles, size_t n_triangles,
+                     const double *vertex_normals)
+{
+    BHG_TRY(rebuild_check(c, m, vertices, n_vertices, triangles, n_triangles, vertex_normals));
+    ENTER_DEVICE(c->device);
+    return rebuild_run(c, m, vertices, n_vertices, triangles, n_triangles, vertex_normals, true, c->stream);
+}
+
+int bhg_mesh_build_info(const bhg_mesh *m, int32_t *built_on_device, uint64_t *builds, size_t *cap_vertices, size_t *cap_triangles,
+                        uint64_t *allocations)
+{
+    if (!m) return fail(BHG_E_INVALID, "mesh is NULL");
+    if (built_on_device) *built_on_device = m->built_on_device ? 1 : 0;
+    if (builds) *builds = m->builds;
+    if (cap_vertices) *cap_vertices = m->cap_vertices;
+    if (cap_triangles) *cap_triangles = m->cap_triangles;
+    if (allocations) *allocations = m->allocations;
+    return BHG_OK;
+}
+
+int bhg_mesh_tree_host(const bhg_mesh *m, int32_t *node_skip, int32_t *node_first, int32_t *node_count, int32_t *tri_order, size_t cap,
+                       size_t *n_nodes)
+{
+    if (!m) return fail(BHG_E_INVALID, "mesh is NULL");
+    if (!n_nodes) return fail(BHG_E_INVALID, "n_nodes is NULL");
+    const size_t nn = (size_t)m->n_nodes;
+    *n_nodes = nn;
+    if (cap < nn) return fail(BHG_E_INVALID, "the tree has more nodes than cap (bhg_mesh_info gives n_nodes)");
+    if (!node_skip || !node_first || !node_count || !tri_order) return fail(BHG_E_INVALID, "an output array is NULL");
+    ENTER_DEVICE(m->device);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(node_skip, m->view.node_skip, nn * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(node_first, m->view.node_first, nn * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(node_count, m->view.node_count, nn * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(tri_order, m->view.tri_order, (size_t)m->view.n_tris * sizeof(int32_t), hipMemcpyDeviceToHost));
     return BHG_OK;
 }
 

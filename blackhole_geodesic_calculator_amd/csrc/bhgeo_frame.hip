@@ -54,6 +54,10 @@ int motion_params(const bhg_params *p, const bhg_object_motion *mo, const double
 int mesh_material_check(const bhg_mesh_material *m, size_t nt, bool host_arrays);
 // ... and of the transforms of mesh instances
 int mesh_instance_transforms_check(int32_t n, const double *T);
+// ... a mesh built on the device from host arrays, which are uploaded first
+int mesh_create_built_on_device(bhg_context *c, const double *vertices, size_t n_vertices, const int32_t *triangles, size_t n_triangles,
+                                const double *vertex_normals, int32_t leaf_size, size_t cap_vertices, size_t cap_triangles,
+                                bool host_arrays, hipStream_t stream, bhg_mesh **out);
 }
 
 namespace {
@@ -205,6 +209,8 @@ struct Shard {
     DevBuf m_rgb, m_uv, m_slot, m_img[BHG_MESH_TEXTURES_MAX], tri, bary;
     bool mesh_ready = false;        // mesh and the material buffers hold the frame's current mesh
     bool mesh_refit = false;        // ... but for the vertices (bhg_frame_refit_mesh): the next render refits (or rebuilds) the tree
+    int32_t mesh_leaf = 0;          // leaf_size and normals of `mesh`: what a rebuild in place must find unchanged (section 23)
+    bool mesh_normals = false;
     // the mesh's instances (bhg_frame_set_mesh_instances): this device's set over mesh, the colours, the trace's third record
     bhg_mesh_instances *inst = nullptr;
     int32_t inst_n = 0;
@@ -265,6 +271,7 @@ struct bhg_frame {
         double rebuild_ratio = 0.0;                 // of the latest bhg_frame_refit_mesh
     };
     bool meshed = false;            // bhg_frame_set_mesh; false: no mesh, the plain render
+    bool mesh_build_device = false; // bhg_frame_set_mesh_build: trees are built (and rebuilt in place) on the devices
     Mesh mesh;
     // bhg_frame_set_mesh_instances: host copies (empty: the mesh where its vertices put it)
     std::vector<double> inst;       // [n][12]
@@ -411,11 +418,13 @@ void release_shard_instances(Shard &s)
     s.inst_ready = false;
 }
 
-void release_shard_mesh(Shard &s)
+void release_shard_mesh(Shard &s, bool keep_tree = false)
 {
-    release_shard_instances(s);     // (a set does not outlive its mesh)
-    if (s.mesh) bhg_mesh_destroy(s.mesh);
-    s.mesh = nullptr;
+    if (!keep_tree) {
+        release_shard_instances(s);     // (a set does not outlive its mesh)
+        if (s.mesh) bhg_mesh_destroy(s.mesh);
+        s.mesh = nullptr;
+    }
     for (DevBuf *b : {&s.m_rgb, &s.m_uv, &s.m_slot, &s.tri, &s.bary}) b->release();
     for (DevBuf &b : s.m_img) b.release();
     s.mesh_ready = s.mesh_refit = false;
@@ -426,10 +435,32 @@ void release_shard_mesh(Shard &s)
 int upload_shard_mesh(bhg_frame *f, Shard &s)
 {
     const bhg_frame::Mesh &m = f->mesh;
-    release_shard_mesh(s);
+    const size_t nv = m.vertices.size() / 3, nt = m.triangles.size() / 3;
+    const double *normals = m.normals.empty() ? nullptr : m.normals.data();
+    // with the device build on, a mesh this device holds takes the new arrays in place when they fit its capacity (section 23)
+    bool in_place = false;
+    if (f->mesh_build_device && s.mesh && s.mesh_leaf == m.leaf_size && s.mesh_normals == (normals != nullptr)) {
+        size_t cap_v = 0, cap_t = 0;
+        BHG_TRY(bhg_mesh_build_info(s.mesh, nullptr, nullptr, &cap_v, &cap_t, nullptr));
+        in_place = nv <= cap_v && nt <= cap_t;
+    }
+    release_shard_mesh(s, in_place);
     HIP_TRY(hipSetDevice(s.device));
-    BHG_TRY(bhg_mesh_create(s.ctx, m.vertices.data(), m.vertices.size() / 3, m.triangles.data(), m.triangles.size() / 3,
-                            m.normals.empty() ? nullptr : m.normals.data(), m.leaf_size, &s.mesh));
+    if (in_place) {
+        HIP_TRY(hipStreamSynchronize(s.stream));    // (no kernel of an earlier render still reads the mesh)
+        BHG_TRY(bhg_mesh_rebuild(s.ctx, s.mesh, m.vertices.data(), nv, m.triangles.data(), nt, normals));
+        s.inst_ready = false;
+    } else if (f->mesh_build_device) {
+        // (room to grow: a mesh whose triangle list changes seldom keeps its counts)
+        const size_t most = 0x7FFFFFFFull;
+        const size_t cap_v = std::min(nv * BHG_FRAME_MESH_HEADROOM, most), cap_t = std::min(nt * BHG_FRAME_MESH_HEADROOM, most);
+        BHG_TRY(bhg::mesh_create_built_on_device(s.ctx, m.vertices.data(), nv, m.triangles.data(), nt, normals, m.leaf_size, cap_v, cap_t,
+                                                 true, (hipStream_t)bhg_context_stream(s.ctx), &s.mesh));
+    } else {
+        BHG_TRY(bhg_mesh_create(s.ctx, m.vertices.data(), nv, m.triangles.data(), nt, normals, m.leaf_size, &s.mesh));
+    }
+    s.mesh_leaf = m.leaf_size;
+    s.mesh_normals = normals != nullptr;
     HIP_TRY(hipSetDevice(s.device));
     const auto up = [&](DevBuf &b, const void *src, size_t bytes) -> int {
         if (bytes == 0) return BHG_OK;
@@ -464,7 +495,11 @@ int refit_shard_mesh(bhg_frame *f, Shard &s)
         BHG_TRY(bhg_mesh_refit_info(s.mesh, nullptr, &built, &now));
         rebuild = ratio > 0.0 && built > 0.0 && now > ratio * built;
     }
-    if (rebuild) {
+    if (rebuild && f->mesh_build_device) {
+        // in place, on the device: the set over the mesh goes stale and is set again by upload_shard_instances
+        BHG_TRY(bhg_mesh_rebuild(s.ctx, s.mesh, m.vertices.data(), m.vertices.size() / 3, m.triangles.data(), m.triangles.size() / 3,
+                                 normals));
+    } else if (rebuild) {
         release_shard_instances(s);     // (a set does not outlive its mesh)
         bhg_mesh_destroy(s.mesh);
         s.mesh = nullptr;
@@ -935,6 +970,8 @@ try {
             if (!std::isfinite(vertex_normals[i])) return fail(BHG_E_INVALID, "mesh: every vertex normal must be finite");
     if (!std::isfinite(max_chord) || max_chord < 0.0)
         return fail(BHG_E_INVALID, "max_chord must be finite and >= 0 (0: a quarter of r_s)");
+    if (f->mesh_build_device && leaf_size > bhg::MORTON_LEAF_MAX)
+        return fail(BHG_E_INVALID, "mesh device build: leaf_size must be in [1, 64] while bhg_frame_set_mesh_build is on");
     if (material) BHG_TRY(bhg::mesh_material_check(material, n_triangles, true));
     // the new mesh is copied aside first: a refused host allocation leaves the frame as it was
     bhg_frame::Mesh m;
@@ -1403,6 +1440,24 @@ try {
     return build_root(f);
 } catch (...) {
     return host_exception();
+}
+
+int bhg_frame_set_mesh_build(bhg_frame *f, int on_device)
+{
+    if (!f) return fail(BHG_E_INVALID, "frame is NULL");
+    if (on_device && f->meshed && f->mesh.leaf_size > bhg::MORTON_LEAF_MAX)
+        return fail(BHG_E_INVALID, "mesh device build: the frame's mesh has a leaf_size over 64 (bhg_frame_set_mesh with one in [1, 64] first)");
+    f->mesh_build_device = on_device != 0;
+    return BHG_OK;
+}
+
+int bhg_frame_mesh_build_info(const bhg_frame *f, int32_t shard, int32_t *built_on_device, uint64_t *builds, size_t *cap_vertices,
+                              size_t *cap_triangles, uint64_t *allocations)
+{
+    if (!f) return fail(BHG_E_INVALID, "frame is NULL");
+    if (shard < 0 || (size_t)shard >= f->sh.size()) return fail(BHG_E_INVALID, "shard must be in [0, the frame's devices)");
+    if (!f->sh[(size_t)shard].mesh) return fail(BHG_E_INVALID, "this device holds no mesh (none set, or no render since)");
+    return bhg_mesh_build_info(f->sh[(size_t)shard].mesh, built_on_device, builds, cap_vertices, cap_triangles, allocations);
 }
 
 int bhg_frame_mesh_refit_info(const bhg_frame *f, int32_t shard, uint64_t *generation, double *area_build, double *area_now)

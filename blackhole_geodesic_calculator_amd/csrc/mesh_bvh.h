@@ -1,4 +1,5 @@
-// mesh_bvh.h -- the host-side BVH builder of the triangle-mesh trace.  Host C++ only: no HIP in here.
+// mesh_bvh.h -- the host-side BVH builder of the triangle-mesh trace.  Host C++ only: no HIP in here
+// (the Morton cell and key functions at the end carry __host__ __device__ when a HIP compiler reads them).
 //
 // A binary tree over the triangles' boxes, split at the median (by count) of the longest axis of the centroid bounds, and
 // flattened in depth-first pre-order with one skip link per node:
@@ -234,6 +235,125 @@ inline void build_bvh(const double *V, const int32_t *F, size_t nt, int32_t leaf
             out.node_skip[i] = out.node_skip[r];
         }
     }
+    fit_boxes(V, F, out.node_skip.data(), out.node_first.data(), out.node_count.data(), order.data(), nn, out.node_box.data());
+}
+
+// ---- the Morton tree: the build the device can do, stated here for the host ---------------------------------
+// The triangles are put in the order of a 63-bit Morton key of their centroids (ties by the caller's index), and the tree laid
+// over that order splits every range by COUNT at lo + m / 2, as build_bvh does: its shape is a function of (nt, leaf_size) alone.
+// mesh_build.hip restates morton_cell, morton_key and the leaf order; the topology below is what it is handed.
+
+// (the cell and key functions are the kernels' too: plain C++ that the device compiler takes as it stands)
+#if defined(__HIPCC__)
+#define BHG_HOST_DEVICE __host__ __device__
+#else
+#define BHG_HOST_DEVICE
+#endif
+
+// the leaf sizes the device build takes (its per-leaf sort is one thread's loop)
+constexpr int32_t MORTON_LEAF_MAX = 64;
+
+// 2^21 / ext, or 0 for an axis without a finite extent > 0 (every cell of that axis is 0)
+BHG_HOST_DEVICE inline double morton_scale(double lo, double hi)
+{
+    const double ext = hi - lo;
+    return (ext > 0.0 && ext < INFINITY) ? 2097152.0 / ext : 0.0;
+}
+
+// min(2^21 - 1, (uint64)((c - lo) * scale)), with the cases a conversion leaves open settled: a product that is not > 0 (and so a
+// NaN from 0 * inf, when ext is so small that the scale overflows) gives 0
+BHG_HOST_DEVICE inline uint64_t morton_cell(double c, double lo, double scale)
+{
+    if (!(scale > 0.0)) return 0;
+    const double f = (c - lo) * scale;
+    return f >= 2097151.0 ? (uint64_t)2097151 : (f > 0.0 ? (uint64_t)f : (uint64_t)0);
+}
+
+// bit k of q to bit 3 k
+BHG_HOST_DEVICE inline uint64_t morton_spread(uint64_t q)
+{
+    q &= 0x1FFFFFull;
+    q = (q | q << 32) & 0x1F00000000FFFFull;
+    q = (q | q << 16) & 0x1F0000FF0000FFull;
+    q = (q | q << 8) & 0x100F00F00F00F00Full;
+    q = (q | q << 4) & 0x10C30C30C30C30C3ull;
+    q = (q | q << 2) & 0x1249249249249249ull;
+    return q;
+}
+BHG_HOST_DEVICE inline uint64_t morton_key(uint64_t qx, uint64_t qy, uint64_t qz) { return morton_spread(qx) << 2 | morton_spread(qy) << 1 | morton_spread(qz); }
+
+// node_skip, node_first, node_count and the depth of the count-split tree over nt slots, in build_bvh's pre-order
+inline void morton_topology(size_t nt, int32_t leaf_size, std::vector<int32_t> &node_skip, std::vector<int32_t> &node_first,
+                            std::vector<int32_t> &node_count, int32_t &depth)
+{
+    node_skip.clear();
+    node_first.clear();
+    node_count.clear();
+    depth = 0;
+    struct Range {
+        size_t lo, hi;
+        int32_t depth;
+    };
+    Range stack[BVH_MAX_DEPTH + 2];
+    int sp = 0;
+    stack[sp++] = Range{0, nt, 0};
+    while (sp > 0) {
+        const Range r = stack[--sp];
+        const size_t m = r.hi - r.lo;
+        if (r.depth > depth) depth = r.depth;
+        node_skip.push_back(0);
+        if (m <= (size_t)leaf_size) {
+            node_first.push_back((int32_t)r.lo);
+            node_count.push_back((int32_t)m);
+            continue;
+        }
+        node_first.push_back(-1);
+        node_count.push_back(0);
+        const size_t mid = r.lo + m / 2;
+        stack[sp++] = Range{mid, r.hi, r.depth + 1};
+        stack[sp++] = Range{r.lo, mid, r.depth + 1};
+    }
+    const size_t nn = node_skip.size();
+    for (size_t i = nn; i-- > 0;) {
+        if (node_count[i] > 0) node_skip[i] = (int32_t)(i + 1);
+        else node_skip[i] = node_skip[(size_t)node_skip[i + 1]];
+    }
+}
+
+// the Morton keys of the triangles' centroids (the mesh has passed mesh_refusal)
+inline void morton_keys(const double *V, const int32_t *F, size_t nt, std::vector<uint64_t> &key)
+{
+    std::vector<double> cen(nt * 3);
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (size_t t = 0; t < nt; t++)
+        for (int c = 0; c < 3; c++) {
+            const double x = (V[(size_t)F[t * 3] * 3 + c] + V[(size_t)F[t * 3 + 1] * 3 + c] + V[(size_t)F[t * 3 + 2] * 3 + c]) / 3.0;
+            cen[t * 3 + c] = x;
+            lo[c] = std::min(lo[c], x);
+            hi[c] = std::max(hi[c], x);
+        }
+    double scale[3];
+    for (int c = 0; c < 3; c++) scale[c] = morton_scale(lo[c], hi[c]);
+    key.resize(nt);
+    for (size_t t = 0; t < nt; t++)
+        key[t] = morton_key(morton_cell(cen[t * 3], lo[0], scale[0]), morton_cell(cen[t * 3 + 1], lo[1], scale[1]),
+                            morton_cell(cen[t * 3 + 2], lo[2], scale[2]));
+}
+
+// the mesh has passed mesh_refusal
+inline void build_bvh_morton(const double *V, const int32_t *F, size_t nt, int32_t leaf_size, HostBvh &out)
+{
+    std::vector<uint64_t> key;
+    morton_keys(V, F, nt, key);
+    std::vector<int32_t> &order = out.tri_order;
+    order.resize(nt);
+    for (size_t t = 0; t < nt; t++) order[t] = (int32_t)t;
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return key[(size_t)a] < key[(size_t)b]; });
+    morton_topology(nt, leaf_size, out.node_skip, out.node_first, out.node_count, out.depth);
+    const size_t nn = out.node_skip.size();
+    for (size_t i = 0; i < nn; i++)
+        if (out.node_count[i] > 0) std::sort(order.begin() + out.node_first[i], order.begin() + out.node_first[i] + out.node_count[i]);
+    out.node_box.assign(nn * 6, 0.0);
     fit_boxes(V, F, out.node_skip.data(), out.node_first.data(), out.node_count.data(), order.data(), nn, out.node_box.data());
 }
 

@@ -365,7 +365,7 @@ class DeviceFrame:
             raise ValueError("opacity must be in (0, 1]")
         self.disk_layers = _ffi.make_disk_layers(max_crossings, opacity)
 
-    def set_mesh(self, mesh=None, tri_rgb=None, chord=None, lamps=None, material=None, instances=None, inst_rgb=None):
+    def set_mesh(self, mesh=None, tri_rgb=None, chord=None, lamps=None, material=None, instances=None, inst_rgb=None, build="host"):
         """A triangle mesh in the curved region (bhg_trace_mesh_device, bhg_shade_mesh_device): trace()
         ends a ray where its curve meets a triangle and keeps d_tri_id [n] int32 / d_bary [n, 2]; shade() / shade_f32() /
         render() light the mesh rays (tri_rgb [nt, 3] per triangle, default white; the lamps of set_objects([], lamps=...) or
@@ -377,7 +377,11 @@ class DeviceFrame:
         section 20) in place of tri_rgb -- both together are a ValueError; without it the shade is the existing call.
         instances: [K, 12] or [K, 3, 4] rigid placements of the mesh (bhg_trace_mesh_instances_device,
         bhg_shade_mesh_instances_device) -- trace() also keeps d_inst_id [n]; inst_rgb [K, 3] float32
-        multiplies the albedo per instance.  set_mesh_instances(T) moves them afterwards."""
+        multiplies the albedo per instance.  set_mesh_instances(T) moves them afterwards.
+        build: "host" or "device" (DESIGN.md section 23), for a mesh given as (vertices, triangles); rebuild_mesh() then gives
+        either a new triangle list in place."""
+        if build not in ("host", "device"):
+            raise ValueError('build must be "host" or "device"')
         if material is not None and tri_rgb is not None:
             raise ValueError("material and tri_rgb together: the material carries the triangle colours")
         if inst_rgb is not None and instances is None:
@@ -390,7 +394,7 @@ class DeviceFrame:
             self.mesh = self.d_tri_rgb = self.mesh_chord = self.mesh_material = None
             return
         if not isinstance(mesh, _ffi.Mesh):
-            mesh = _ffi.Mesh(self.ctx, mesh[0], mesh[1])
+            mesh = _ffi.Mesh(self.ctx, mesh[0], mesh[1], build=build)
         if mesh.ctx is not self.ctx:
             raise ValueError("the mesh belongs to another context")
         if chord is not None and not (np.isfinite(float(chord)) and float(chord) > 0.0):
@@ -442,6 +446,42 @@ class DeviceFrame:
         torch.cuda.current_stream(self.dev).synchronize()
         self.mesh.refit(vertices, vertex_normals, stream=self._stream())
         self._traced = None
+        if self.mesh_instances is not None:
+            self.mesh_instances.set(self.mesh_instances.transforms)
+
+    def rebuild_mesh(self, vertices, triangles, vertex_normals=None, material=None, tri_rgb=None):
+        """A new triangle list (vertices, triangles, and vertex normals for a mesh that has them) for the held mesh, within its
+        capacity: its tree is built anew on the device, in place (Mesh.rebuild).  numpy arrays, or tensors
+        on the frame's device.  material / tri_rgb replace the held one; a held per-triangle array that no longer matches
+        n_triangles, with no new one given, is a ValueError (nothing is changed then).  Held instances are set again."""
+        if self.mesh is None:
+            raise ValueError("rebuild_mesh() wants a mesh: set_mesh() first")
+        if material is not None and tri_rgb is not None:
+            raise ValueError("material and tri_rgb together: the material carries the triangle colours")
+        nt = int(triangles.shape[0]) if hasattr(triangles, "shape") else len(triangles)
+        new_material = new_rgb = None
+        if material is not None:
+            material.check_triangles(nt)
+            dev = [None if a is None else torch.as_tensor(a).to(self.dev) for a in material.arrays()]
+            new_material = (material, material.struct([0 if t is None else t.data_ptr() for t in dev]), dev)
+        elif tri_rgb is not None:
+            rgb = np.ascontiguousarray(tri_rgb, dtype=np.float32)
+            if rgb.shape != (nt, 3):
+                raise ValueError("tri_rgb must have shape [n_triangles, 3]")
+            new_rgb = torch.as_tensor(rgb).to(self.dev)
+        elif nt != self.mesh.n_triangles:
+            if self.d_tri_rgb is not None:
+                raise ValueError(f"the held tri_rgb is for {self.mesh.n_triangles} triangles, the new list has {nt}: give tri_rgb=")
+            if self.mesh_material is not None and any(a is not None for a in self.mesh_material[0].arrays()[:3]):
+                raise ValueError(f"the held material's per-triangle arrays are for {self.mesh.n_triangles} triangles, the new list "
+                                 f"has {nt}: give material=")
+        torch.cuda.current_stream(self.dev).synchronize()
+        self.mesh.rebuild(vertices, triangles, vertex_normals, stream=self._stream())
+        self._traced = None
+        if material is not None:
+            self.mesh_material, self.d_tri_rgb = new_material, None
+        elif tri_rgb is not None:
+            self.d_tri_rgb, self.mesh_material = new_rgb, None
         if self.mesh_instances is not None:
             self.mesh_instances.set(self.mesh_instances.transforms)
 

@@ -65,7 +65,7 @@ class GeodesicIntegratorSchwarzschild:
     # ------------------------------------------------------------------------------------
     def trace(self, k0, x0, max_step=np.inf, curve_end=50.0, r_exit=0.0, disk=None, spheres=None, redshift=None,
               polarisation=None, disk_thermal=None, disk_crossings=None, travel_time=False, mesh=None, mesh_chord=None,
-              mesh_instances=None):
+              mesh_instances=None, mesh_build="host"):
         """Batched solve.  k0[N,3] (or [...,3]); x0[3] shared origin or same leading shape as k0.
         r_exit: outward sphere-exit radius (Limited engine's ray_trace, Limited...py:273-278);
         disk=(R_in, R_out): thin disk in z = 0, first crossing inside the annulus ends the ray with
@@ -120,7 +120,11 @@ class GeodesicIntegratorSchwarzschild:
         K rigid placements x_world = R x_local + t instead of where its vertices put it, and the dict also has
             inst_id[...]               int32, the placement hit, -1 for every other ray (tri_id counts within the mesh, bary lies
                                        in the placement's frame)
+        mesh_build="device" (with mesh=(vertices, triangles)): the mesh's tree is built on the device
+        instead of the host; every output is the same, bit for bit.
         """
+        if mesh_build not in ("host", "device"):
+            raise ValueError('mesh_build must be "host" or "device"')
         if mesh_instances is not None and mesh is None:
             raise ValueError("mesh_instances goes with mesh=")
         if mesh is not None:
@@ -129,7 +133,7 @@ class GeodesicIntegratorSchwarzschild:
                                 ("polarisation", polarisation is not None), ("disk_thermal", disk_thermal is not None)):
                 if given:
                     raise ValueError(f"mesh does not go with {name}")
-            return self._trace_mesh(k0, x0, max_step, curve_end, r_exit, disk, mesh, mesh_chord, mesh_instances)
+            return self._trace_mesh(k0, x0, max_step, curve_end, r_exit, disk, mesh, mesh_chord, mesh_instances, mesh_build)
         if travel_time and spheres is not None:
             raise ValueError("travel_time does not go with object spheres")
         if disk_crossings is not None:
@@ -181,10 +185,10 @@ class GeodesicIntegratorSchwarzschild:
             out["t"] = t.reshape(lead)
         return out
 
-    def _trace_mesh(self, k0, x0, max_step, curve_end, r_exit, disk, mesh, mesh_chord, instances=None):
+    def _trace_mesh(self, k0, x0, max_step, curve_end, r_exit, disk, mesh, mesh_chord, instances=None, build="host"):
         """trace(mesh=): a mesh given as arrays lives for this call, and so does the instance set of mesh_instances=."""
         own = not isinstance(mesh, _ffi.Mesh)
-        m = _ffi.Mesh(self._ctx, mesh[0], mesh[1]) if own else mesh
+        m = _ffi.Mesh(self._ctx, mesh[0], mesh[1], build=build) if own else mesh
         inst = inst_id = None
         try:
             k0 = np.asarray(k0, dtype=np.float64)

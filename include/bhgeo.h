@@ -80,6 +80,9 @@ extern "C" {
                                   BHG_MESH_REFIT (bhg_mesh_refit, bhg_mesh_refit_device, bhg_mesh_refit_info, bhg_mesh_bvh_refit_host,
                                   bhg_mesh_refit_schedule_host, bhg_mesh_boxes_host, bhg_mesh_range, bhg_frame_refit_mesh, bhg_frame_mesh_refit_info: new vertices into a built mesh, its tree
                                   refitted on the device);
+                                  BHG_MESH_BUILD_DEVICE (bhg_mesh_create_device, bhg_mesh_rebuild_device, bhg_mesh_rebuild,
+                                  bhg_mesh_build_info, bhg_mesh_bvh_morton_host, bhg_mesh_tree_host: a Morton-order tree built
+                                  on the device, rebuilt in place when the triangle list changes);
                                   BHG_PREFIX_RECORD_WIDE under BHG_START_PREFIX (bhg_prefix_wide_accepted, bhg_prefix_owner_next,
                                   bhg_frame_prefix_info, struct bhg_prefix_owner: wider start-up records, recorded again after refusals).
                                9: redshift -- bhg_redshift_device / _host, bhg_shade_scene_redshift_device, bhg_frame_set_redshift,
@@ -1231,6 +1234,65 @@ int bhg_frame_mesh_refit_info(const bhg_frame *frame, int32_t shard, uint64_t *g
 /* A blocking download of the device's boxes [n_nodes][6] and (tri may be NULL) slot records [nt][9] = v0, e1, e2 per leaf slot,
  * for tests and diagnosis.  cap = the nodes node_box holds. */
 int bhg_mesh_boxes_host(const bhg_mesh *mesh, double *node_box, double *tri, size_t cap);
+
+/* --- the device-side build: a Morton-order tree over a triangle list on the device, rebuilt in place (within ABI 10; DESIGN.md
+ * section 23) ----
+ * For a mesh whose TRIANGLE LIST changes -- a fluid surface, a boolean, a remesher -- a refit does not serve and bhg_mesh_destroy +
+ * bhg_mesh_create builds on the host.  These calls build on the device: the triangles are sorted by a 63-bit Morton key of their
+ * centroids (21 bits per axis in the centroid bounds, ties by the caller's index), the tree of bhg_mesh_bvh_host's kind whose
+ * ranges split by count at lo + m / 2 is laid over that order (its node_skip / node_first / node_count are a function of
+ * n_triangles and leaf_size alone), every leaf's slots are put in rising caller index, and the refit kernels write slot records,
+ * boxes, widening and the area sum.  bhg_mesh_bvh_morton_host states the same tree on the host, bit for bit.  The tree only
+ * accelerates the hit rule: every trace and shade of a device-built mesh gives the bits of one on the host-built mesh.
+ * The mesh of bhg_mesh_create_device is a bhg_mesh like any other: every trace, shade, instance set, refit and query takes it.
+ * All of its device memory -- tree and records for cap_vertices / cap_triangles (0: the counts themselves), the sort's storage, the
+ * refit's -- is allocated at creation, so a rebuild within capacity allocates nothing (allocations of bhg_mesh_build_info counts
+ * the mesh's device allocations over its life).  A mesh of bhg_mesh_create has its own counts as capacity and may be rebuilt at
+ * those or fewer; its first rebuild moves it into an image of that capacity and allocates the build's storage.
+ * The arrays are device arrays of the context's device (bhg_mesh_rebuild: host arrays, uploaded first).  A first device pass
+ * checks every triangle index against [0, n_vertices) and every vertex and normal for non-finite values, and its result is read
+ * back before any kernel follows an index or anything of the mesh is written: a bad array ends in BHG_E_INVALID.
+ * Blocking, with the refit's contract: the calls wait for everything queued on the context's stream and on `stream` before the
+ * first write and for their own work before they return; ordering against readers on OTHER streams is the caller's job.
+ * After a rebuild box, d_min, d_max, n_nodes, depth, area_build and area_now are the new tree's, generation is one higher -- so
+ * every instance set of the mesh is refused until its bhg_mesh_instances_set -- and builds is one higher (1 after creation).
+ * Refused (BHG_E_INVALID, the message names the field), the mesh untouched and for _create_device nothing left allocated and
+ * *out NULL: what bhg_mesh_create refuses; leaf_size outside [1, 64] (the per-leaf sort is one thread's loop: brute-force leaves
+ * stay with bhg_mesh_create); counts over the capacity; a capacity below the counts; normals given to a mesh without them, or
+ * omitted for one with them; a mesh of another context's device. */
+#define BHG_MESH_BUILD_DEVICE 1
+int bhg_mesh_create_device(bhg_context *ctx, const double *d_vertices, size_t n_vertices, const int32_t *d_triangles,
+                           size_t n_triangles, const double *d_vertex_normals /* or NULL */, int32_t leaf_size, size_t cap_vertices,
+                           size_t cap_triangles, void *stream, bhg_mesh **out);
+int bhg_mesh_rebuild_device(bhg_context *ctx, bhg_mesh *mesh, const double *d_vertices, size_t n_vertices, const int32_t *d_triangles,
+                            size_t n_triangles, const double *d_vertex_normals, void *stream);
+int bhg_mesh_rebuild(bhg_context *ctx, bhg_mesh *mesh, const double *vertices, size_t n_vertices, const int32_t *triangles,
+                     size_t n_triangles, const double *vertex_normals);
+/* any output may be NULL */
+int bhg_mesh_build_info(const bhg_mesh *mesh, int32_t *built_on_device, uint64_t *builds, size_t *cap_vertices, size_t *cap_triangles,
+                        uint64_t *allocations);
+/* Host only, no context, no GPU: the Morton tree, with the arguments and outputs of bhg_mesh_bvh_host.  Unlike that builder it
+ * never makes a leaf over leaf_size (identical triangles are separated by their index), and it takes any leaf_size >= 1. */
+int bhg_mesh_bvh_morton_host(const double *vertices, size_t n_vertices, const int32_t *triangles, size_t n_triangles, int32_t leaf_size,
+                             double *node_box, int32_t *node_skip, int32_t *node_first, int32_t *node_count, int32_t *tri_order,
+                             size_t cap, size_t *n_nodes);
+/* A blocking download of the device's node_skip, node_first, node_count [n_nodes] and tri_order [n_triangles], for tests and
+ * diagnosis.  cap = the nodes the three node arrays hold; *n_nodes is set even when cap is too small (BHG_E_INVALID then). */
+int bhg_mesh_tree_host(const bhg_mesh *mesh, int32_t *node_skip, int32_t *node_first, int32_t *node_count, int32_t *tri_order,
+                       size_t cap, size_t *n_nodes);
+/* The device build on the library-owned frame; on_device = 0 (the default: the host builder, everything as before) or 1.  When on:
+ * each device creates its mesh with the device build from the frame's host copy, with a capacity of BHG_FRAME_MESH_HEADROOM
+ * times its counts (a mesh whose triangle list changes seldom keeps its counts); a later bhg_frame_set_mesh whose counts fit the
+ * capacity of the mesh a device holds (with the same leaf_size, and normals given or not as before) rebuilds that mesh in place
+ * instead of destroying and creating it; and the rebuild_ratio path of bhg_frame_refit_mesh rebuilds in place on the device.  The
+ * material is replaced as bhg_frame_set_mesh replaces it.  Every image is the host-built frame's, bit for bit.  Meshes the
+ * devices hold already stay as they are until the next bhg_frame_set_mesh or rebuild.  Refused: a frame whose mesh has a leaf_size
+ * over 64; and, while on, bhg_frame_set_mesh with such a leaf_size. */
+#define BHG_FRAME_MESH_HEADROOM 4
+int bhg_frame_set_mesh_build(bhg_frame *frame, int on_device);
+/* bhg_mesh_build_info of the mesh that device number `shard` of the frame holds; refused as bhg_frame_mesh_refit_info refuses. */
+int bhg_frame_mesh_build_info(const bhg_frame *frame, int32_t shard, int32_t *built_on_device, uint64_t *builds, size_t *cap_vertices,
+                              size_t *cap_triangles, uint64_t *allocations);
 
 /* Acceleration probe: acc[n][3] = -Gamma^i_{mu nu} k^mu k^nu at (x[n][3], k[n][3]); host buffers.
  * Lets tests compare the device RHS with the oracle's term by term.  With rhs_form = BHG_RHS_KERR_BL the triples
