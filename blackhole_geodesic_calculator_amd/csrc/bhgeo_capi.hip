@@ -19,15 +19,11 @@
 #include <new>
 #include <string>
 #include <thread>
-#include <unordered_map>
 #include <vector>
 
-#include "../../include/bhgeo.h"
-#include "geodesic_kernels.h"
+#include "bhgeo_internal.h"
+#include "mesh_object.h"
 #include "prefix_clearance.h"
-#include "mesh_bvh.h"
-#include "mesh_build.h"
-#include "mesh_refit.h"
 #include "trace_call.h"
 
 static_assert(BHG_FLAG_HIT_HORIZON == bhg::BHG_FLAG_HIT_HORIZON_, "flag mismatch");
@@ -69,39 +65,16 @@ static_assert(sizeof(bhg_disk_layers) == 16 && BHG_MAX_CROSSINGS == bhg::BHG_MAX
 static_assert(BHG_OBJECT_LIT == bhg::BHG_OBJECT_LIT_ && BHG_OBJECT_EMISSIVE == bhg::BHG_OBJECT_EMISSIVE_, "object mode mismatch");
 
 namespace {
-
 thread_local std::string g_err = "";
+}  // namespace
 
-int fail(int code, const std::string &msg)
+namespace bhg {
+// for every translation unit of the library (bhgeo_internal.h: fail, fail_hip): the thread-local message of bhg_last_error()
+int set_error(int code, const std::string &msg)
 {
     g_err = msg;
     return code;
 }
-
-int fail_hip(hipError_t e, const char *what)
-{
-    g_err = std::string(what) + ": " + hipGetErrorString(e);
-    (void)hipGetLastError();     // (reported here: not again by the next launch's status)
-    return (e == hipErrorOutOfMemory) ? BHG_E_NOMEM : BHG_E_HIP;
-}
-
-#define HIP_TRY(expr)                                   \
-    do {                                                \
-        hipError_t _e = (expr);                         \
-        if (_e != hipSuccess) return fail_hip(_e, #expr); \
-    } while (0)
-// ... and a refusal or failure of one of the library's own checks and calls: handed on as it is
-#define BHG_TRY(expr)                      \
-    do {                                   \
-        const int _rc = (expr);            \
-        if (_rc != BHG_OK) return _rc;     \
-    } while (0)
-
-}  // namespace
-
-namespace bhg {
-// for the other translation units of the library (bhgeo_frame.hip): set the thread-local message of bhg_last_error()
-int set_error(int code, const std::string &msg) { return fail(code, msg); }
 }  // namespace bhg
 
 namespace {
@@ -201,31 +174,6 @@ private:
     bool stop_ = false, started_ = false;
 };
 
-// Entry points make the context's device current for their own HIP calls and put the caller's current device back on
-// the way out: a host that created a context on device k while working on device j keeps working on j.
-struct DeviceGuard {
-    int prev = -1;
-    hipError_t err = hipSuccess;
-    explicit DeviceGuard(int dev)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) {
-            (void)hipGetLastError();
-            prev = -1;
-        }
-        if (prev != dev) err = hipSetDevice(dev);
-        else prev = -1;  // nothing to restore
-    }
-    ~DeviceGuard()
-    {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-    DeviceGuard(const DeviceGuard &) = delete;
-    DeviceGuard &operator=(const DeviceGuard &) = delete;
-};
-#define ENTER_DEVICE(dev)         \
-    DeviceGuard _device_guard(dev); \
-    if (_device_guard.err != hipSuccess) return fail_hip(_device_guard.err, "hipSetDevice")
-
 }  // namespace
 
 struct bhg_context {
@@ -273,6 +221,9 @@ namespace bhg {
 // for bhgeo_frame.hip: a context's worker threads copy a page-locked staging block into the caller's pageable array (a
 // 16.8-MB frame through ONE thread's memcpy is 1.0-1.7 ms -- as long as the frame's trace)
 void host_copy(bhg_context *c, void *dst, const void *src, size_t bytes, size_t piece) { c->pool.copy(dst, src, bytes, piece); }
+// for bhgeo_mesh.hip, which sees a context from outside
+int context_device(const bhg_context *c) { return c->device; }
+hipStream_t context_stream(const bhg_context *c) { return c->stream; }
 }  // namespace bhg
 
 namespace {
@@ -412,6 +363,8 @@ int validate(const bhg_params *p)
 }  // namespace
 
 namespace bhg {
+int params_check(const bhg_params *p) { return validate(p); }   // (for bhgeo_mesh.hip's trace checks)
+
 // The thermal-disk settings on their own (include/bhgeo.h, "the thermal disk"): what can be checked without the trace
 // parameters.  Also used by bhgeo_frame.hip.
 int thermal_check(const bhg_disk_thermal *th)
@@ -1099,96 +1052,7 @@ int bhg_last_launch(bhg_context *c, int32_t out[4])
 
 }  // extern "C"
 
-// a mesh on one device: the flattened tree of mesh_bvh.h, the triangles in leaf order, the maps between
-// the two numberings
-struct bhg_mesh {
-    int device = 0;
-    char *d = nullptr;        // one allocation
-    bhg::MeshView view{};
-    int64_t n_nodes = 0;
-    int32_t depth = 0;
-    double box[6] = {0, 0, 0, 0, 0, 0};
-    double d_min = 0.0, d_max = 0.0;
-    uint64_t serial = 0;      // its entry in live_meshes, which an instance set checks before it trusts its pointer
-    // the refit: what _create leaves on the device for it beside the view's arrays, and what it keeps count of
-    int32_t n_vertices = 0;
-    bool has_normals = false;
-    const int32_t *slot_vert = nullptr;     // in d, [nt][3]: the caller's vertex indices of the triangle in each leaf slot
-    const int32_t *level_nodes = nullptr;   // in d, [n_inner]: the inner nodes grouped by level (mesh_bvh.h, inner_levels)
-    std::vector<int32_t> level_off;         // [BVH_MAX_DEPTH + 2]
-    int32_t n_inner = 0;
-    char *d_refit = nullptr;  // the first refit's allocation, kept: summary | area [nn] | staging of host vertices and normals
-    uint64_t generation = 0;  // +1 per successful refit or rebuild
-    double area_build = 0.0, area_now = 0.0;
-    // the device build.  by_capacity: d and d_refit are laid out for cap_vertices / cap_triangles (a mesh of
-    // bhg_mesh_create_device, or one of bhg_mesh_create since its first rebuild) and not for the counts the host builder was given
-    int32_t leaf_size = 0;
-    size_t cap_vertices = 0, cap_triangles = 0;
-    bool by_capacity = false, built_on_device = false;
-    char *d_build = nullptr;  // record | keys in | keys out | values in | staging of host triangles | the sort's own storage
-    size_t sort_bytes = 0;
-    size_t topo_triangles = 0;              // the n_triangles whose Morton topology (at leaf_size) lies in d; 0: none
-    uint64_t builds = 0, allocations = 0;   // builds, the creating one included; device allocations over the mesh's life
-};
-
-// K rigid placements of one mesh: the device records, and what the host works out from them in O(K)
-struct bhg_mesh_instances {
-    bhg_context *ctx = nullptr;
-    int device = 0;               // ctx's (the set may be destroyed after its context)
-    const bhg_mesh *mesh = nullptr;
-    uint64_t mesh_serial = 0;
-    uint64_t mesh_generation = 0; // the mesh's at _create / _set: the world boxes come from the local box of that generation
-    int32_t n = 0;
-    double *d_rec = nullptr;      // [n][BHG_MESH_INSTANCE_DOUBLES_]
-    double box[6] = {0, 0, 0, 0, 0, 0};     // the union of the world boxes
-    double d_min = 0.0, d_max = 0.0;
-    // The records are written by _set on the context's stream and read by traces and shades on whatever stream their caller
-    // names: the set orders the two itself, so that no caller has to.
-    //   * h_rec: two page-locked host copies, used in turn; a copy's event (ev_copy) is waited for on the host before its buffer
-    //     is filled again, so a queued copy always reads what its _set wrote;
-    //   * a reader's stream waits for the last copy (ev_copy[last]) before it launches, and leaves ev_read behind it; a reader on
-    //     another stream than the one before waits for that one's ev_read first, so the last ev_read stands for every reader;
-    //   * _set makes the context's stream wait for ev_read before the copy: no kernel still reads what it overwrites.
-    // (mutable: a reader holds the set const, and reads)
-    double *h_rec[2] = {nullptr, nullptr};
-    hipEvent_t ev_copy[2] = {nullptr, nullptr};
-    mutable hipEvent_t ev_read = nullptr;
-    mutable hipStream_t read_stream = nullptr;
-    mutable bool was_read = false;
-    int last = -1;                // the host copy of the latest _set (-1: the creating upload, synchronous)
-};
-
 namespace {
-
-// the meshes that exist, by address and serial number (an address may come back after a destroy; a serial never does)
-std::mutex live_meshes_lock;
-std::unordered_map<const bhg_mesh *, uint64_t> live_meshes;
-uint64_t live_meshes_next = 1;
-
-// BHGEO_MESH_CULL=0: every step of every ray samples its sub-chords, and no instance's world box is looked at (an A/B aid: the
-// results are the same bits)
-bool mesh_culls_on()
-{
-    const char *cull = std::getenv("BHGEO_MESH_CULL");
-    return !(cull && cull[0] == '0' && cull[1] == 0);
-}
-
-// A kernel on stream s is about to read the set's records / has been launched (bhg_mesh_instances has the protocol)
-hipError_t instances_before_read(const bhg_mesh_instances *in, hipStream_t s)
-{
-    if (in->last >= 0)
-        if (hipError_t e = hipStreamWaitEvent(s, in->ev_copy[in->last], 0)) return e;
-    if (in->was_read && in->read_stream != s)
-        if (hipError_t e = hipStreamWaitEvent(s, in->ev_read, 0)) return e;
-    return hipSuccess;
-}
-
-hipError_t instances_after_read(const bhg_mesh_instances *in, hipStream_t s)
-{
-    in->read_stream = s;
-    in->was_read = true;
-    return hipEventRecord(in->ev_read, s);
-}
 
 int validate_spheres(const bhg_params *p, const double *spheres, int32_t n_spheres)
 {
@@ -1366,7 +1230,7 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const TraceCall &tc)
             g.d_min = tc.mesh->d_min;
             g.d_max = tc.mesh->d_max;
             g.max_chord = tc.max_chord;
-            g.cull = mesh_culls_on();
+            g.cull = bhg::mesh_culls_on();
             g.tri_id = tc.tri_id;
             g.bary = tc.bary;
             if (tc.instances) {
@@ -1381,9 +1245,9 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const TraceCall &tc)
                 ia.n = in->n;
                 ia.inst_id = tc.inst_id;
                 ia.cull = g.cull;       // (BHGEO_MESH_CULL=0 takes the instances' world boxes out as well)
-                HIP_TRY(instances_before_read(in, s));
+                HIP_TRY(bhg::instances_before_read(in, s));
                 HIP_TRY(bhg::launch_trace_mesh_instances(a, g, ia, rhs_id, s));
-                HIP_TRY(instances_after_read(in, s));
+                HIP_TRY(bhg::instances_after_read(in, s));
             } else {
                 HIP_TRY(bhg::launch_trace_mesh(a, g, rhs_id, s));
             }
@@ -1752,818 +1616,14 @@ int bhg_travel_time(bhg_context *c, const bhg_params *p, const double *x0, int x
     });
 }
 
-// --- triangle meshes ---------------------------------------------------------------------------------
-
-}  // extern "C"
-
-namespace {
-
-// what the mesh trace covers, checked before the context (a refusal names its figure with or without a device)
-int mesh_trace_check(const bhg_params *p, const bhg_mesh *mesh, double max_chord, const int32_t *tri_id, const double *bary)
-{
-    BHG_TRY(validate(p));
-    if (p->method != BHG_METHOD_DP54) return fail(BHG_E_INVALID, "the mesh trace is DP5(4) only: method must be BHG_METHOD_DP54");
-    if (p->time_like) return fail(BHG_E_INVALID, "the mesh trace covers null rays only: time_like must be 0");
-    if (!mesh) return fail(BHG_E_INVALID, "mesh is NULL");
-    if (!std::isfinite(max_chord) || !(max_chord > 0.0)) return fail(BHG_E_INVALID, "max_chord must be finite and > 0");
-    if (!tri_id || !bary) return fail(BHG_E_INVALID, "tri_id / bary is NULL");
-    return BHG_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int bhg_mesh_bvh_host(const double *vertices, size_t n_vertices, const int32_t *triangles, size_t n_triangles, int32_t leaf_size,
-                      double *node_box, int32_t *node_skip, int32_t *node_first, int32_t *node_count, int32_t *tri_order, size_t cap,
-                      size_t *n_nodes)
-{
-    if (const char *why = bhg::mesh_refusal(vertices, n_vertices, triangles, n_triangles, leaf_size)) return fail(BHG_E_INVALID, why);
-    if (!n_nodes) return fail(BHG_E_INVALID, "n_nodes is NULL");
-    bhg::HostBvh t;
-    bhg::build_bvh(vertices, triangles, n_triangles, leaf_size, t);
-    const size_t nn = t.node_skip.size();
-    *n_nodes = nn;
-    if (nn > cap) return fail(BHG_E_INVALID, "the tree has more nodes than cap (2 * n_triangles - 1 always suffices)");
-    if (!node_box || !node_skip || !node_first || !node_count || !tri_order) return fail(BHG_E_INVALID, "an output array is NULL");
-    std::memcpy(node_box, t.node_box.data(), nn * 6 * sizeof(double));
-    std::memcpy(node_skip, t.node_skip.data(), nn * sizeof(int32_t));
-    std::memcpy(node_first, t.node_first.data(), nn * sizeof(int32_t));
-    std::memcpy(node_count, t.node_count.data(), nn * sizeof(int32_t));
-    std::memcpy(tri_order, t.tri_order.data(), n_triangles * sizeof(int32_t));
-    return BHG_OK;
-}
-
-int bhg_mesh_create(bhg_context *c, const double *vertices, size_t n_vertices, const int32_t *triangles, size_t n_triangles,
-                    const double *vertex_normals, int32_t leaf_size, bhg_mesh **out)
-{
-    if (!out) return fail(BHG_E_INVALID, "out is NULL");
-    *out = nullptr;
-    if (const char *why = bhg::mesh_refusal(vertices, n_vertices, triangles, n_triangles, leaf_size)) return fail(BHG_E_INVALID, why);
-    if (vertex_normals)
-        for (size_t i = 0; i < n_vertices * 3; i++)
-            if (!std::isfinite(vertex_normals[i])) return fail(BHG_E_INVALID, "mesh: every vertex normal must be finite");
-    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
-    ENTER_DEVICE(c->device);
-    bhg::HostBvh t;
-    bhg::build_bvh(vertices, triangles, n_triangles, leaf_size, t);
-    const size_t nn = t.node_skip.size(), nt = n_triangles;
-    // the refit's schedule: the inner nodes by level
-    std::vector<int32_t> level_nodes, level_off;
-    if (!bhg::inner_levels(t.node_skip.data(), t.node_count.data(), nn, level_nodes, level_off))
-        return fail(BHG_E_INVALID, "bhg_mesh_create: the tree is deeper than BVH_MAX_DEPTH");
-    // the device image: boxes | triangles (v0, e1, e2) | vertex normals | skip | first | count | order | slot | and for the refit
-    // the vertex indices per slot | the inner nodes by level
-    const size_t b_box = nn * 6 * sizeof(double), b_tri = nt * 9 * sizeof(double), b_nrm = vertex_normals ? b_tri : 0,
-                 b_node = (nn * sizeof(int32_t) + 7) & ~size_t(7), b_idx = (nt * sizeof(int32_t) + 7) & ~size_t(7),
-                 b_sv = (nt * 3 * sizeof(int32_t) + 7) & ~size_t(7), b_lv = (level_nodes.size() * sizeof(int32_t) + 7) & ~size_t(7);
-    const size_t o_tri = b_box, o_nrm = o_tri + b_tri, o_skip = o_nrm + b_nrm, o_first = o_skip + b_node, o_count = o_first + b_node,
-                 o_order = o_count + b_node, o_slot = o_order + b_idx, o_sv = o_slot + b_idx, o_lv = o_sv + b_sv, total = o_lv + b_lv;
-    std::vector<char> img(total, 0);
-    std::memcpy(img.data(), t.node_box.data(), b_box);
-    double *tri = (double *)(img.data() + o_tri), *nrm = (double *)(img.data() + o_nrm);
-    int32_t *slot_of = (int32_t *)(img.data() + o_slot), *slot_vert = (int32_t *)(img.data() + o_sv);
-    double d_max = 0.0;
-    for (size_t k = 0; k < nt; k++) {
-        const int32_t f = t.tri_order[k];
-        slot_of[f] = (int32_t)k;
-        for (int j = 0; j < 3; j++) slot_vert[k * 3 + j] = triangles[(size_t)f * 3 + j];
-        const double *v0 = vertices + (size_t)triangles[(size_t)f * 3] * 3, *v1 = vertices + (size_t)triangles[(size_t)f * 3 + 1] * 3,
-                     *v2 = vertices + (size_t)triangles[(size_t)f * 3 + 2] * 3;
-        for (int q = 0; q < 3; q++) {
-            tri[k * 9 + q] = v0[q];
-            tri[k * 9 + 3 + q] = v1[q] - v0[q];
-            tri[k * 9 + 6 + q] = v2[q] - v0[q];
-        }
-        for (const double *v : {v0, v1, v2}) d_max = std::max(d_max, std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]));
-        if (vertex_normals)
-            for (int j = 0; j < 3; j++)
-                for (int q = 0; q < 3; q++) nrm[k * 9 + j * 3 + q] = vertex_normals[(size_t)triangles[(size_t)f * 3 + j] * 3 + q];
-    }
-    std::memcpy(img.data() + o_skip, t.node_skip.data(), nn * sizeof(int32_t));
-    std::memcpy(img.data() + o_first, t.node_first.data(), nn * sizeof(int32_t));
-    std::memcpy(img.data() + o_count, t.node_count.data(), nn * sizeof(int32_t));
-    std::memcpy(img.data() + o_order, t.tri_order.data(), nt * sizeof(int32_t));
-    if (!level_nodes.empty()) std::memcpy(img.data() + o_lv, level_nodes.data(), level_nodes.size() * sizeof(int32_t));
-    bhg_mesh *m = new (std::nothrow) bhg_mesh;
-    if (!m) return fail(BHG_E_NOMEM, "out of host memory");
-    hipError_t e = hipMalloc((void **)&m->d, total);
-    if (e == hipSuccess) e = hipMemcpy(m->d, img.data(), total, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (m->d) (void)hipFree(m->d);
-        delete m;
-        return fail_hip(e, "bhg_mesh_create: device image");
-    }
-    m->device = c->device;
-    m->n_nodes = (int64_t)nn;
-    m->depth = t.depth;
-    std::memcpy(m->box, t.node_box.data(), sizeof(m->box));
-    // every point of the mesh lies inside the root box and no farther from the origin than the farthest vertex
-    double d2 = 0.0;
-    for (int q = 0; q < 3; q++) {
-        const double gap = std::max(std::max(m->box[q], -m->box[3 + q]), 0.0);
-        d2 += gap * gap;
-    }
-    m->d_min = std::sqrt(d2) * (1.0 - 1e-14);
-    m->d_max = d_max * (1.0 + 1e-14);
-    bhg::MeshView &v = m->view;
-    v.node_box = (const double *)m->d;
-    v.tri = (const double *)(m->d + o_tri);
-    v.tri_normals = vertex_normals ? (const double *)(m->d + o_nrm) : nullptr;
-    v.node_skip = (const int32_t *)(m->d + o_skip);
-    v.node_first = (const int32_t *)(m->d + o_first);
-    v.node_count = (const int32_t *)(m->d + o_count);
-    v.tri_order = (const int32_t *)(m->d + o_order);
-    v.tri_slot = (const int32_t *)(m->d + o_slot);
-    v.n_nodes = (int32_t)nn;
-    v.n_tris = (int32_t)nt;
-    m->n_vertices = (int32_t)n_vertices;
-    m->has_normals = vertex_normals != nullptr;
-    m->slot_vert = (const int32_t *)(m->d + o_sv);
-    m->level_nodes = (const int32_t *)(m->d + o_lv);
-    m->level_off = level_off;
-    m->n_inner = (int32_t)level_nodes.size();
-    m->area_build = m->area_now = bhg::area_sum(t.node_box.data(), nn);
-    m->leaf_size = leaf_size;
-    m->cap_vertices = n_vertices;
-    m->cap_triangles = n_triangles;
-    m->builds = 1;
-    m->allocations = 1;
-    {
-        std::lock_guard<std::mutex> lock(live_meshes_lock);
-        m->serial = live_meshes_next++;
-        live_meshes[m] = m->serial;
-    }
-    *out = m;
-    return BHG_OK;
-}
-
-void bhg_mesh_destroy(bhg_mesh *m)
-{
-    if (!m) return;
-    {
-        std::lock_guard<std::mutex> lock(live_meshes_lock);
-        live_meshes.erase(m);
-    }
-    {
-        DeviceGuard g(m->device);
-        if (m->d) (void)hipFree(m->d);
-        if (m->d_refit) (void)hipFree(m->d_refit);
-        if (m->d_build) (void)hipFree(m->d_build);
-    }
-    delete m;
-}
-
-int bhg_mesh_info(const bhg_mesh *m, int64_t *n_nodes, int32_t *depth, double box[6])
-{
-    if (!m) return fail(BHG_E_INVALID, "mesh is NULL");
-    if (n_nodes) *n_nodes = m->n_nodes;
-    if (depth) *depth = m->depth;
-    if (box) std::memcpy(box, m->box, sizeof(m->box));
-    return BHG_OK;
-}
-
-// --- the refit of a mesh's tree -----------------------------------------------------------------------
-
-}  // extern "C"
-
-namespace {
-
-// what both refit calls refuse before the device is touched
-int refit_check(const bhg_context *c, const bhg_mesh *m, const double *vertices, const double *vertex_normals)
-{
-    if (!m) return fail(BHG_E_INVALID, "mesh is NULL");
-    if (!vertices) return fail(BHG_E_INVALID, "mesh refit: vertices is NULL");
-    if (vertex_normals && !m->has_normals)
-        return fail(BHG_E_INVALID, "mesh refit: vertex_normals given to a mesh that was created without them");
-    if (!vertex_normals && m->has_normals)
-        return fail(BHG_E_INVALID, "mesh refit: vertex_normals is NULL for a mesh that was created with them");
-    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
-    if (m->device != c->device) return fail(BHG_E_INVALID, "the mesh lives on another device than the context");
-    return BHG_OK;
-}
-
-// the refit's own device memory, allocated by the first refit and kept: summary | area [nn] | vertices [nv][3] | normals [nv][3]
-// (the last two stage the host form's arrays)
-struct RefitScratch {
-    bhg::MeshRefitSummary *summary;
-    double *area, *vertices, *normals;
-};
-
-int refit_scratch(bhg_mesh *m, RefitScratch &r)
-{
-    // (a mesh laid out by capacity holds room for every tree and vertex array a rebuild may bring: section 23)
-    const size_t nn = m->by_capacity ? 2 * m->cap_triangles - 1 : (size_t)m->n_nodes,
-                 nv = m->by_capacity ? m->cap_vertices : (size_t)m->n_vertices;
-    const size_t b_sum = (sizeof(bhg::MeshRefitSummary) + 7) & ~size_t(7), b_area = nn * sizeof(double), b_v = nv * 3 * sizeof(double);
-    if (!m->d_refit) {
-        HIP_TRY(hipMalloc((void **)&m->d_refit, b_sum + b_area + b_v * (m->has_normals ? 2 : 1)));
-        m->allocations++;
-    }
-    r.summary = (bhg::MeshRefitSummary *)m->d_refit;
-    r.area = (double *)(m->d_refit + b_sum);
-    r.vertices = (double *)(m->d_refit + b_sum + b_area);
-    r.normals = m->has_normals ? (double *)(m->d_refit + b_sum + b_area + b_v) : nullptr;
-    return BHG_OK;
-}
-
-// d_v, d_n: device arrays.  scan: they have not been looked at yet (the device form).  The device is c's and current.
-int refit_run(bhg_context *c, bhg_mesh *m, const RefitScratch &r, const double *d_v, const double *d_n, bool scan, hipStream_t s)
-{
-    bhg::MeshRefitArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.vertices = d_v;
-    a.normals = d_n;
-    a.n_vertices = m->n_vertices;
-    a.n_tris = m->view.n_tris;
-    a.n_nodes = m->view.n_nodes;
-    a.n_inner = m->n_inner;
-    a.slot_vert = m->slot_vert;
-    a.node_skip = m->view.node_skip;
-    a.node_first = m->view.node_first;
-    a.node_count = m->view.node_count;
-    a.level_nodes = m->level_nodes;
-    std::memcpy(a.level_off, m->level_off.data(), sizeof(a.level_off));
-    a.node_box = const_cast<double *>(m->view.node_box);
-    a.tri = const_cast<double *>(m->view.tri);
-    a.tri_normals = const_cast<double *>(m->view.tri_normals);
-    a.area = r.area;
-    a.summary = r.summary;
-    bhg::MeshRefitSummary sum;
-    // nothing of the mesh is written before everything queued on the context's stream and on s is done
-    if (c->stream != s) HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemsetAsync(r.summary, 0, sizeof(sum), s));
-    if (scan) {
-        HIP_TRY(bhg::launch_mesh_refit_scan(a, s));
-        HIP_TRY(hipMemcpyAsync(&sum, r.summary, sizeof(sum), hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    if (scan && (sum.nonfinite & 1u)) return fail(BHG_E_INVALID, "mesh: every vertex must be finite");
-    if (scan && (sum.nonfinite & 2u)) return fail(BHG_E_INVALID, "mesh: every vertex normal must be finite");
-    HIP_TRY(bhg::launch_mesh_refit(a, s));
-    HIP_TRY(hipMemcpyAsync(&sum, r.summary, sizeof(sum), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    // box, d_min, d_max: bhg_mesh_create's formulas (the square root is monotone: the largest |v| is the root of the largest |v|^2)
-    std::memcpy(m->box, sum.box, sizeof(m->box));
-    double d2 = 0.0;
-    for (int q = 0; q < 3; q++) {
-        const double gap = std::max(std::max(m->box[q], -m->box[3 + q]), 0.0);
-        d2 += gap * gap;
-    }
-    double far2;
-    std::memcpy(&far2, &sum.d2_max, sizeof(far2));
-    m->d_min = std::sqrt(d2) * (1.0 - 1e-14);
-    m->d_max = std::sqrt(far2) * (1.0 + 1e-14);
-    m->area_now = sum.area;
-    m->generation++;
-    return BHG_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int bhg_mesh_refit(bhg_context *c, bhg_mesh *m, const double *vertices, const double *vertex_normals)
-{
-    BHG_TRY(refit_check(c, m, vertices, vertex_normals));
-    const size_t n3 = (size_t)m->n_vertices * 3;
-    for (size_t i = 0; i < n3; i++)
-        if (!std::isfinite(vertices[i])) return fail(BHG_E_INVALID, "mesh: every vertex must be finite");
-    if (vertex_normals)
-        for (size_t i = 0; i < n3; i++)
-            if (!std::isfinite(vertex_normals[i])) return fail(BHG_E_INVALID, "mesh: every vertex normal must be finite");
-    ENTER_DEVICE(c->device);
-    RefitScratch r;
-    BHG_TRY(refit_scratch(m, r));
-    // (the staging arrays are the refit's own: a refit is blocking, so no earlier one still reads them)
-    HIP_TRY(hipMemcpyAsync(r.vertices, vertices, n3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (vertex_normals) HIP_TRY(hipMemcpyAsync(r.normals, vertex_normals, n3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    return refit_run(c, m, r, r.vertices, r.normals, false, c->stream);
-}
-
-int bhg_mesh_refit_device(bhg_context *c, bhg_mesh *m, const double *d_vertices, const double *d_vertex_normals, void *stream)
-{
-    BHG_TRY(refit_check(c, m, d_vertices, d_vertex_normals));
-    ENTER_DEVICE(c->device);
-    RefitScratch r;
-    BHG_TRY(refit_scratch(m, r));
-    return refit_run(c, m, r, d_vertices, d_vertex_normals, true, (hipStream_t)stream);
-}
-
-int bhg_mesh_refit_info(const bhg_mesh *m, uint64_t *generation, double *area_build, double *area_now)
-{
-    if (!m) return fail(BHG_E_INVALID, "mesh is NULL");
-    if (generation) *generation = m->generation;
-    if (area_build) *area_build = m->area_build;
-    if (area_now) *area_now = m->area_now;
-    return BHG_OK;
-}
-
-int bhg_mesh_range(const bhg_mesh *m, double *d_min, double *d_max)
-{
-    if (!m) return fail(BHG_E_INVALID, "mesh is NULL");
-    if (d_min) *d_min = m->d_min;
-    if (d_max) *d_max = m->d_max;
-    return BHG_OK;
-}
-
-int bhg_mesh_bvh_refit_host(const double *vertices, size_t n_vertices, const int32_t *triangles, size_t n_triangles,
-                            const int32_t *node_skip, const int32_t *node_first, const int32_t *node_count, const int32_t *tri_order,
-                            size_t n_nodes, double *node_box, double *area)
-{
-    if (const char *why = bhg::mesh_refusal(vertices, n_vertices, triangles, n_triangles, 1)) return fail(BHG_E_INVALID, why);
-    if (const char *why = bhg::topology_refusal(node_skip, node_first, node_count, tri_order, n_nodes, n_triangles))
-        return fail(BHG_E_INVALID, why);
-    if (!node_box) return fail(BHG_E_INVALID, "node_box is NULL");
-    std::vector<int32_t> level_nodes, level_off;
-    if (!bhg::inner_levels(node_skip, node_count, n_nodes, level_nodes, level_off))
-        return fail(BHG_E_INVALID, "mesh topology: the tree is deeper than 32 levels");
-    bhg::fit_boxes(vertices, triangles, node_skip, node_first, node_count, tri_order, n_nodes, node_box);
-    if (area) *area = bhg::area_sum(node_box, n_nodes);
-    return BHG_OK;
-}
-
-int bhg_mesh_refit_schedule_host(const int32_t *node_skip, const int32_t *node_first, const int32_t *node_count,
-                                 const int32_t *tri_order, size_t n_nodes, size_t n_triangles, int32_t *level_nodes,
-                                 int32_t *level_off /* [34] */, size_t cap, size_t *n_inner)
-{
-    if (const char *why = bhg::topology_refusal(node_skip, node_first, node_count, tri_order, n_nodes, n_triangles))
-        return fail(BHG_E_INVALID, why);
-    if (!n_inner) return fail(BHG_E_INVALID, "n_inner is NULL");
-    std::vector<int32_t> nodes, off;
-    if (!bhg::inner_levels(node_skip, node_count, n_nodes, nodes, off))
-        return fail(BHG_E_INVALID, "mesh topology: the tree is deeper than 32 levels");
-    *n_inner = nodes.size();
-    if (nodes.size() > cap) return fail(BHG_E_INVALID, "the tree has more inner nodes than cap (n_triangles - 1 always suffices)");
-    if (!level_off || (!level_nodes && !nodes.empty())) return fail(BHG_E_INVALID, "an output array is NULL");
-    if (!nodes.empty()) std::memcpy(level_nodes, nodes.data(), nodes.size() * sizeof(int32_t));
-    std::memcpy(level_off, off.data(), off.size() * sizeof(int32_t));
-    return BHG_OK;
-}
-
-int bhg_mesh_boxes_host(const bhg_mesh *m, double *node_box, double *tri, size_t cap)
-{
-    if (!m) return fail(BHG_E_INVALID, "mesh is NULL");
-    if (!node_box) return fail(BHG_E_INVALID, "node_box is NULL");
-    if (cap < (size_t)m->n_nodes) return fail(BHG_E_INVALID, "the tree has more nodes than cap (bhg_mesh_info gives n_nodes)");
-    ENTER_DEVICE(m->device);
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(node_box, m->view.node_box, (size_t)m->n_nodes * 6 * sizeof(double), hipMemcpyDeviceToHost));
-    if (tri) HIP_TRY(hipMemcpy(tri, m->view.tri, (size_t)m->view.n_tris * 9 * sizeof(double), hipMemcpyDeviceToHost));
-    return BHG_OK;
-}
-
-// --- the device-side build: a Morton-order tree, rebuilt in place --------------------------------------
-
-}  // extern "C"
-
-namespace {
-
-size_t round8(size_t b) { return (b + 7) & ~size_t(7); }
-
-// the device image of a mesh laid out by capacity: bhg_mesh_create's arrays in its order, each with room for the largest tree
-// over cap_nt triangles (2 cap_nt - 1 nodes, cap_nt - 1 inner ones: leaf_size 1)
-struct MeshImage {
-    size_t o_tri, o_nrm, o_skip, o_first, o_count, o_order, o_slot, o_sv, o_lv, total;
-};
-
-MeshImage image_by_capacity(size_t cap_nt, bool normals)
-{
-    const size_t nn = 2 * cap_nt - 1;
-    const size_t b_box = nn * 6 * sizeof(double), b_tri = cap_nt * 9 * sizeof(double), b_nrm = normals ? b_tri : 0,
-                 b_node = round8(nn * sizeof(int32_t)), b_idx = round8(cap_nt * sizeof(int32_t)), b_sv = round8(cap_nt * 3 * sizeof(int32_t));
-    MeshImage g;
-    g.o_tri = b_box;
-    g.o_nrm = g.o_tri + b_tri;
-    g.o_skip = g.o_nrm + b_nrm;
-    g.o_first = g.o_skip + b_node;
-    g.o_count = g.o_first + b_node;
-    g.o_order = g.o_count + b_node;
-    g.o_slot = g.o_order + b_idx;
-    g.o_sv = g.o_slot + b_idx;
-    g.o_lv = g.o_sv + b_sv;
-    g.total = g.o_lv + b_idx;
-    return g;
-}
-
-void point_into_image(bhg_mesh *m, char *d, const MeshImage &g)
-{
-    m->d = d;
-    bhg::MeshView &v = m->view;
-    v.node_box = (const double *)d;
-    v.tri = (const double *)(d + g.o_tri);
-    v.tri_normals = m->has_normals ? (const double *)(d + g.o_nrm) : nullptr;
-    v.node_skip = (const int32_t *)(d + g.o_skip);
-    v.node_first = (const int32_t *)(d + g.o_first);
-    v.node_count = (const int32_t *)(d + g.o_count);
-    v.tri_order = (const int32_t *)(d + g.o_order);
-    v.tri_slot = (const int32_t *)(d + g.o_slot);
-    m->slot_vert = (const int32_t *)(d + g.o_sv);
-    m->level_nodes = (const int32_t *)(d + g.o_lv);
-}
-
-// the build's own storage: record | keys in | keys out | values in | staging of host triangles | the sort's storage
-struct BuildStorage {
-    bhg::MeshBuildRecord *record;
-    unsigned long long *keys_in, *keys_out;
-    int32_t *vals_in, *triangles;
-    void *sort_temp;
-};
-
-int build_storage(bhg_mesh *m, BuildStorage &b)
-{
-    const size_t cap = m->cap_triangles;
-    const size_t b_rec = (sizeof(bhg::MeshBuildRecord) + 255) & ~size_t(255), b_key = cap * sizeof(unsigned long long),
-                 b_val = round8(cap * sizeof(int32_t)), b_f = round8(cap * 3 * sizeof(int32_t));
-    const size_t o_sort = (b_rec + 2 * b_key + b_val + b_f + 255) & ~size_t(255);
-    if (!m->d_build) {
-        // (the sort's storage is asked for once, for the capacity)
-        HIP_TRY(bhg::mesh_build_sort_bytes(cap, &m->sort_bytes));
-        HIP_TRY(hipMalloc((void **)&m->d_build, o_sort + m->sort_bytes));
-        m->allocations++;
-    }
-    b.record = (bhg::MeshBuildRecord *)m->d_build;
-    b.keys_in = (unsigned long long *)(m->d_build + b_rec);
-    b.keys_out = (unsigned long long *)(m->d_build + b_rec + b_key);
-    b.vals_in = (int32_t *)(m->d_build + b_rec + 2 * b_key);
-    b.triangles = (int32_t *)(m->d_build + b_rec + 2 * b_key + b_val);
-    b.sort_temp = m->d_build + o_sort;
-    return BHG_OK;
-}
-
-// A mesh of bhg_mesh_create, laid out for its own tree, moves into an image laid out by capacity before its first rebuild: the
-// arrays are copied as they are, so the mesh stays what it was should the rebuild then be refused.  The device is the mesh's.
-int reserve_by_capacity(bhg_mesh *m)
-{
-    if (m->by_capacity) return BHG_OK;
-    const MeshImage g = image_by_capacity(m->cap_triangles, m->has_normals);
-    const size_t nn = (size_t)m->n_nodes, nt = (size_t)m->view.n_tris;
-    char *d = nullptr;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMalloc((void **)&d, g.total));
-    const bhg::MeshView &v = m->view;
-    hipError_t e = hipMemcpy(d, v.node_box, nn * 6 * sizeof(double), hipMemcpyDeviceToDevice);
-    auto copy = [&](size_t off, const void *src, size_t bytes) {
-        if (e == hipSuccess && src && bytes) e = hipMemcpy(d + off, src, bytes, hipMemcpyDeviceToDevice);
-    };
-    copy(g.o_tri, v.tri, nt * 9 * sizeof(double));
-    copy(g.o_nrm, v.tri_normals, nt * 9 * sizeof(double));
-    copy(g.o_skip, v.node_skip, nn * sizeof(int32_t));
-    copy(g.o_first, v.node_first, nn * sizeof(int32_t));
-    copy(g.o_count, v.node_count, nn * sizeof(int32_t));
-    copy(g.o_order, v.tri_order, nt * sizeof(int32_t));
-    copy(g.o_slot, v.tri_slot, nt * sizeof(int32_t));
-    copy(g.o_sv, m->slot_vert, nt * 3 * sizeof(int32_t));
-    copy(g.o_lv, m->level_nodes, (size_t)m->n_inner * sizeof(int32_t));
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return fail_hip(e, "mesh rebuild: the image by capacity");
-    }
-    (void)hipFree(m->d);
-    point_into_image(m, d, g);
-    m->allocations++;
-    // (the refit's scratch is laid out anew with the image: it holds nothing between calls)
-    if (m->d_refit) {
-        (void)hipFree(m->d_refit);
-        m->d_refit = nullptr;
-    }
-    m->by_capacity = true;
-    m->topo_triangles = 0;
-    return BHG_OK;
-}
-
-// what the build calls refuse of their counts and arrays before the device is touched (cap: 0 = none yet, bhg_mesh_create_device)
-int build_counts_check(const void *vertices, size_t nv, const void *triangles, size_t nt)
-{
-    if (!vertices || !triangles) return fail(BHG_E_INVALID, "mesh: vertices / triangles is NULL");
-    if (nv == 0 || nt == 0) return fail(BHG_E_INVALID, "mesh: n_vertices and n_triangles must be > 0");
-    if (nv > 0x7FFFFFFFull || nt > 0x7FFFFFFFull) return fail(BHG_E_INVALID, "mesh: n_vertices and n_triangles must be <= 2^31 - 1");
-    return BHG_OK;
-}
-
-int build_leaf_check(int32_t leaf_size)
-{
-    if (leaf_size < 1 || leaf_size > bhg::MORTON_LEAF_MAX) {
-        char msg[160];
-        std::snprintf(msg, sizeof msg, "mesh device build: leaf_size %d must be in [1, %d] (larger leaves: bhg_mesh_create)", (int)leaf_size,
-                      (int)bhg::MORTON_LEAF_MAX);
-        return fail(BHG_E_INVALID, msg);
-    }
-    return BHG_OK;
-}
-
-int rebuild_check(const bhg_context *c, const bhg_mesh *m, const void *vertices, size_t nv, const void *triangles, size_t nt,
-                  const void *normals)
-{
-    if (!m) return fail(BHG_E_INVALID, "mesh is NULL");
-    BHG_TRY(build_counts_check(vertices, nv, triangles, nt));
-    BHG_TRY(build_leaf_check(m->leaf_size));
-    if (nv > m->cap_vertices || nt > m->cap_triangles) {
-        char msg[200];
-        std::snprintf(msg, sizeof msg, "mesh rebuild: n_vertices %zu / n_triangles %zu exceed the mesh's capacity %zu / %zu", nv, nt,
-                      m->cap_vertices, m->cap_triangles);
-        return fail(BHG_E_INVALID, msg);
-    }
-    if (normals && !m->has_normals)
-        return fail(BHG_E_INVALID, "mesh rebuild: vertex_normals given to a mesh that was created without them");
-    if (!normals && m->has_normals)
-        return fail(BHG_E_INVALID, "mesh rebuild: vertex_normals is NULL for a mesh that was created with them");
-    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
-    if (m->device != c->device) return fail(BHG_E_INVALID, "the mesh lives on another device than the context");
-    return BHG_OK;
-}
-
-// The build proper.  d_v, d_f, d_n: device arrays within the mesh's capacity, not looked at yet.  The mesh is laid out by capacity
-// and owns its build and refit storage (b, r); the device is c's and current.  Nothing of the mesh is written before the scan of
-// all three arrays has been read back and found clean, and no kernel follows a triangle index before that either.
-int build_run(bhg_context *c, bhg_mesh *m, const BuildStorage &b, const RefitScratch &r, const double *d_v, size_t nv, const int32_t *d_f,
-              size_t nt, const double *d_n, hipStream_t s)
-{
-    bhg::MeshBuildArgs ba;
-    std::memset(&ba, 0, sizeof(ba));
-    ba.vertices = d_v;
-    ba.triangles = d_f;
-    ba.n_vertices = (int32_t)nv;
-    ba.n_tris = (int32_t)nt;
-    ba.record = b.record;
-    bhg::MeshRefitArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.vertices = d_v;
-    a.normals = d_n;
-    a.n_vertices = (int32_t)nv;
-    a.summary = r.summary;
-    bhg::MeshRefitSummary sum;
-    bhg::MeshBuildRecord rec;
-    if (c->stream != s) HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemsetAsync(r.summary, 0, sizeof(sum), s));
-    HIP_TRY(hipMemsetAsync(b.record, 0, sizeof(rec), s));
-    HIP_TRY(bhg::launch_mesh_build_scan(ba, s));
-    HIP_TRY(bhg::launch_mesh_refit_scan(a, s));
-    HIP_TRY(hipMemcpyAsync(&rec, b.record, sizeof(rec), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&sum, r.summary, sizeof(sum), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (sum.nonfinite & 1u) return fail(BHG_E_INVALID, "mesh: every vertex must be finite");
-    if (rec.bad_index) return fail(BHG_E_INVALID, "mesh: a triangle index lies outside [0, n_vertices)");
-    if (sum.nonfinite & 2u) return fail(BHG_E_INVALID, "mesh: every vertex normal must be finite");
-    // the topology: a function of (nt, leaf_size), written by the host and kept while both stand
-    const MeshImage g = image_by_capacity(m->cap_triangles, m->has_normals);
-    if (m->topo_triangles != nt) {
-        std::vector<int32_t> skip, first, count, level_nodes, level_off;
-        int32_t depth = 0;
-        bhg::morton_topology(nt, m->leaf_size, skip, first, count, depth);
-        const size_t nn = skip.size();
-        if (!bhg::inner_levels(skip.data(), count.data(), nn, level_nodes, level_off))
-            return fail(BHG_E_INVALID, "mesh device build: the tree is deeper than BVH_MAX_DEPTH");
-        m->topo_triangles = 0;      // (until all four arrays are up)
-        HIP_TRY(hipMemcpyAsync(m->d + g.o_skip, skip.data(), nn * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(m->d + g.o_first, first.data(), nn * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(m->d + g.o_count, count.data(), nn * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        if (!level_nodes.empty())
-            HIP_TRY(hipMemcpyAsync(m->d + g.o_lv, level_nodes.data(), level_nodes.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        // (the vectors go out of scope below: the copies from pageable memory have been staged when the calls return, and the
-        // stream is waited for before this function does)
-        HIP_TRY(hipStreamSynchronize(s));
-        m->n_nodes = (int64_t)nn;
-        m->view.n_nodes = (int32_t)nn;
-        m->depth = depth;
-        m->n_inner = (int32_t)level_nodes.size();
-        m->level_off = level_off;
-        m->topo_triangles = nt;
-    }
-    m->view.n_tris = (int32_t)nt;
-    m->n_vertices = (int32_t)nv;
-    ba.n_nodes = m->view.n_nodes;
-    ba.node_first = m->view.node_first;
-    ba.node_count = m->view.node_count;
-    ba.keys_in = b.keys_in;
-    ba.keys_out = b.keys_out;
-    ba.vals_in = b.vals_in;
-    ba.sort_temp = b.sort_temp;
-    ba.sort_temp_bytes = m->sort_bytes;
-    ba.tri_order = const_cast<int32_t *>(m->view.tri_order);
-    ba.tri_slot = const_cast<int32_t *>(m->view.tri_slot);
-    ba.slot_vert = const_cast<int32_t *>(m->slot_vert);
-    a.n_tris = m->view.n_tris;
-    a.n_nodes = m->view.n_nodes;
-    a.n_inner = m->n_inner;
-    a.slot_vert = m->slot_vert;
-    a.node_skip = m->view.node_skip;
-    a.node_first = m->view.node_first;
-    a.node_count = m->view.node_count;
-    a.level_nodes = m->level_nodes;
-    std::memcpy(a.level_off, m->level_off.data(), sizeof(a.level_off));
-    a.node_box = const_cast<double *>(m->view.node_box);
-    a.tri = const_cast<double *>(m->view.tri);
-    a.tri_normals = const_cast<double *>(m->view.tri_normals);
-    a.area = r.area;
-    // (the scan's flags are zero; the refit max-es d2_max into the same record)
-    HIP_TRY(bhg::launch_mesh_build(ba, s));
-    HIP_TRY(bhg::launch_mesh_refit(a, s));
-    HIP_TRY(hipMemcpyAsync(&sum, r.summary, sizeof(sum), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    std::memcpy(m->box, sum.box, sizeof(m->box));
-    double d2 = 0.0;
-    for (int q = 0; q < 3; q++) {
-        const double gap = std::max(std::max(m->box[q], -m->box[3 + q]), 0.0);
-        d2 += gap * gap;
-    }
-    double far2;
-    std::memcpy(&far2, &sum.d2_max, sizeof(far2));
-    m->d_min = std::sqrt(d2) * (1.0 - 1e-14);
-    m->d_max = std::sqrt(far2) * (1.0 + 1e-14);
-    m->area_build = m->area_now = sum.area;
-    m->built_on_device = true;
-    return BHG_OK;
-}
-
-// a rebuild of a live mesh: the storage, the move into an image by capacity, the build, the counters
-int rebuild_run(bhg_context *c, bhg_mesh *m, const double *v, size_t nv, const int32_t *f, size_t nt, const double *n, bool host_arrays,
-                hipStream_t s)
-{
-    BHG_TRY(reserve_by_capacity(m));
-    BuildStorage b;
-    RefitScratch r;
-    BHG_TRY(build_storage(m, b));
-    BHG_TRY(refit_scratch(m, r));
-    if (host_arrays) {
-        // (the staging arrays are the mesh's own: a rebuild is blocking, so no earlier one still reads them)
-        HIP_TRY(hipMemcpyAsync(r.vertices, v, nv * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(b.triangles, f, nt * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        if (n) HIP_TRY(hipMemcpyAsync(r.normals, n, nv * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-        v = r.vertices;
-        f = b.triangles;
-        if (n) n = r.normals;
-    }
-    BHG_TRY(build_run(c, m, b, r, v, nv, f, nt, n, s));
-    m->generation++;
-    m->builds++;
-    return BHG_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int bhg_mesh_bvh_morton_host(const double *vertices, size_t n_vertices, const int32_t *triangles, size_t n_triangles, int32_t leaf_size,
-                             double *node_box, int32_t *node_skip, int32_t *node_first, int32_t *node_count, int32_t *tri_order,
-                             size_t cap, size_t *n_nodes)
-{
-    if (const char *why = bhg::mesh_refusal(vertices, n_vertices, triangles, n_triangles, leaf_size)) return fail(BHG_E_INVALID, why);
-    if (!n_nodes) return fail(BHG_E_INVALID, "n_nodes is NULL");
-    bhg::HostBvh t;
-    bhg::build_bvh_morton(vertices, triangles, n_triangles, leaf_size, t);
-    const size_t nn = t.node_skip.size();
-    *n_nodes = nn;
-    if (nn > cap) return fail(BHG_E_INVALID, "the tree has more nodes than cap (2 * n_triangles - 1 always suffices)");
-    if (!node_box || !node_skip || !node_first || !node_count || !tri_order) return fail(BHG_E_INVALID, "an output array is NULL");
-    std::memcpy(node_box, t.node_box.data(), nn * 6 * sizeof(double));
-    std::memcpy(node_skip, t.node_skip.data(), nn * sizeof(int32_t));
-    std::memcpy(node_first, t.node_first.data(), nn * sizeof(int32_t));
-    std::memcpy(node_count, t.node_count.data(), nn * sizeof(int32_t));
-    std::memcpy(tri_order, t.tri_order.data(), n_triangles * sizeof(int32_t));
-    return BHG_OK;
-}
-
-}  // extern "C"
-
-namespace bhg {
-
-// bhg_mesh_create_device, and the same from HOST arrays (bhgeo_frame.hip: a frame holds its mesh on the host), which are uploaded
-// into the new mesh's staging arrays first
-int mesh_create_built_on_device(bhg_context *c, const double *d_vertices, size_t n_vertices, const int32_t *d_triangles,
-                                size_t n_triangles, const double *d_vertex_normals, int32_t leaf_size, size_t cap_vertices,
-                                size_t cap_triangles, bool host_arrays, hipStream_t stream, bhg_mesh **out)
-{
-    if (!out) return fail(BHG_E_INVALID, "out is NULL");
-    *out = nullptr;
-    BHG_TRY(build_counts_check(d_vertices, n_vertices, d_triangles, n_triangles));
-    BHG_TRY(build_leaf_check(leaf_size));
-    if (cap_vertices == 0) cap_vertices = n_vertices;
-    if (cap_triangles == 0) cap_triangles = n_triangles;
-    if (cap_vertices < n_vertices || cap_triangles < n_triangles)
-        return fail(BHG_E_INVALID, "mesh device build: cap_vertices / cap_triangles must be 0 or at least the counts");
-    if (cap_vertices > 0x7FFFFFFFull || cap_triangles > 0x7FFFFFFFull)
-        return fail(BHG_E_INVALID, "mesh device build: cap_vertices and cap_triangles must be <= 2^31 - 1");
-    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
-    ENTER_DEVICE(c->device);
-    bhg_mesh *m = new (std::nothrow) bhg_mesh;
-    if (!m) return fail(BHG_E_NOMEM, "out of host memory");
-    m->device = c->device;
-    m->has_normals = d_vertex_normals != nullptr;
-    m->leaf_size = leaf_size;
-    m->cap_vertices = cap_vertices;
-    m->cap_triangles = cap_triangles;
-    m->by_capacity = true;
-    // everything the mesh will ever hold on the device, now: the image, the build's storage, the refit's
-    const MeshImage g = image_by_capacity(cap_triangles, m->has_normals);
-    char *d = nullptr;
-    BuildStorage b;
-    RefitScratch r;
-    int rc = BHG_OK;
-    const hipError_t e = hipMalloc((void **)&d, g.total);
-    if (e != hipSuccess) rc = fail_hip(e, "bhg_mesh_create_device: device image");
-    if (rc == BHG_OK) {
-        point_into_image(m, d, g);
-        m->allocations++;
-        rc = build_storage(m, b);
-    }
-    if (rc == BHG_OK) rc = refit_scratch(m, r);
-    if (rc == BHG_OK && host_arrays) {
-        const auto up = [&](void *dst, const void *src, size_t bytes) {
-            const hipError_t eu = rc == BHG_OK ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream) : hipSuccess;
-            if (eu != hipSuccess) rc = fail_hip(eu, "bhg_mesh_create_device: upload");
-        };
-        up(r.vertices, d_vertices, n_vertices * 3 * sizeof(double));
-        up(b.triangles, d_triangles, n_triangles * 3 * sizeof(int32_t));
-        if (d_vertex_normals) up(r.normals, d_vertex_normals, n_vertices * 3 * sizeof(double));
-        d_vertices = r.vertices;
-        d_triangles = b.triangles;
-        if (d_vertex_normals) d_vertex_normals = r.normals;
-    }
-    if (rc == BHG_OK) rc = build_run(c, m, b, r, d_vertices, n_vertices, d_triangles, n_triangles, d_vertex_normals, stream);
-    if (rc != BHG_OK) {
-        // (refused or failed: nothing stays allocated; the message is build_run's)
-        if (m->d) (void)hipFree(m->d);
-        if (m->d_build) (void)hipFree(m->d_build);
-        if (m->d_refit) (void)hipFree(m->d_refit);
-        delete m;
-        return rc;
-    }
-    m->builds = 1;
-    {
-        std::lock_guard<std::mutex> lock(live_meshes_lock);
-        m->serial = live_meshes_next++;
-        live_meshes[m] = m->serial;
-    }
-    *out = m;
-    return BHG_OK;
-}
-
-}  // namespace bhg
-
-extern "C" {
-
-int bhg_mesh_create_device(bhg_context *c, const double *d_vertices, size_t n_vertices, const int32_t *d_triangles, size_t n_triangles,
-                           const double *d_vertex_normals, int32_t leaf_size, size_t cap_vertices, size_t cap_triangles, void *stream,
-                           bhg_mesh **out)
-{
-    return bhg::mesh_create_built_on_device(c, d_vertices, n_vertices, d_triangles, n_triangles, d_vertex_normals, leaf_size,
-                                            cap_vertices, cap_triangles, false, (hipStream_t)stream, out);
-}
-
-int bhg_mesh_rebuild_device(bhg_context *c, bhg_mesh *m, const double *d_vertices, size_t n_vertices, const int32_t *d_triangles,
-                            size_t n_triangles, const double *d_vertex_normals, void *stream)
-{
-    BHG_TRY(rebuild_check(c, m, d_vertices, n_vertices, d_triangles, n_triangles, d_vertex_normals));
-    ENTER_DEVICE(c->device);
-    return rebuild_run(c, m, d_vertices, n_vertices, d_triangles, n_triangles, d_vertex_normals, false, (hipStream_t)stream);
-}
-
-int bhg_mesh_rebuild(bhg_context *c, bhg_mesh *m, const double *vertices, size_t n_vertices, const int32_t *triangles, size_t n_triangles,
-                     const double *vertex_normals)
-{
-    BHG_TRY(rebuild_check(c, m, vertices, n_vertices, triangles, n_triangles, vertex_normals));
-    ENTER_DEVICE(c->device);
-    return rebuild_run(c, m, vertices, n_vertices, triangles, n_triangles, vertex_normals, true, c->stream);
-}
-
-int bhg_mesh_build_info(const bhg_mesh *m, int32_t *built_on_device, uint64_t *builds, size_t *cap_vertices, size_t *cap_triangles,
-                        uint64_t *allocations)
-{
-    if (!m) return fail(BHG_E_INVALID, "mesh is NULL");
-    if (built_on_device) *built_on_device = m->built_on_device ? 1 : 0;
-    if (builds) *builds = m->builds;
-    if (cap_vertices) *cap_vertices = m->cap_vertices;
-    if (cap_triangles) *cap_triangles = m->cap_triangles;
-    if (allocations) *allocations = m->allocations;
-    return BHG_OK;
-}
-
-int bhg_mesh_tree_host(const bhg_mesh *m, int32_t *node_skip, int32_t *node_first, int32_t *node_count, int32_t *tri_order, size_t cap,
-                       size_t *n_nodes)
-{
-    if (!m) return fail(BHG_E_INVALID, "mesh is NULL");
-    if (!n_nodes) return fail(BHG_E_INVALID, "n_nodes is NULL");
-    const size_t nn = (size_t)m->n_nodes;
-    *n_nodes = nn;
-    if (cap < nn) return fail(BHG_E_INVALID, "the tree has more nodes than cap (bhg_mesh_info gives n_nodes)");
-    if (!node_skip || !node_first || !node_count || !tri_order) return fail(BHG_E_INVALID, "an output array is NULL");
-    ENTER_DEVICE(m->device);
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(node_skip, m->view.node_skip, nn * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(node_first, m->view.node_first, nn * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(node_count, m->view.node_count, nn * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(tri_order, m->view.tri_order, (size_t)m->view.n_tris * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return BHG_OK;
-}
+// --- triangle meshes: the trace; bhgeo_mesh.hip has the mesh itself -------------------------------------
 
 int bhg_trace_mesh_device(bhg_context *c, const bhg_params *p, const bhg_mesh *mesh, double max_chord, const double *x0_shared,
                           const double *d_x0, const double *d_k0, size_t n, double *d_end, uint8_t *d_flags, uint32_t *d_n_steps,
                           uint32_t *d_n_accepted, int32_t *d_tri_id, double *d_bary, void *stream)
 {
-    BHG_TRY(mesh_trace_check(p, mesh, max_chord, d_tri_id, d_bary));
-    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
-    if (mesh->device != c->device) return fail(BHG_E_INVALID, "the mesh lives on another device than the context");
+    BHG_TRY(bhg::mesh_trace_check(p, mesh, max_chord, d_tri_id, d_bary));
+    BHG_TRY(bhg::mesh_on_device_of(c, mesh));
     if (n && !d_end) return fail(BHG_E_INVALID, "end is NULL");
     return trace_device_impl(c, p, {.kind = TraceKind::MESH, .x0_shared = x0_shared, .d_x0 = d_x0, .d_k0 = d_k0, .n = n, .d_end = d_end,
                                     .d_flags = d_flags, .d_n_steps = d_n_steps, .d_n_accepted = d_n_accepted, .stream = stream,
@@ -2576,9 +1636,8 @@ int bhg_trace_mesh(bhg_context *c, const bhg_params *p, const bhg_mesh *mesh, do
                    const double *k0, size_t n, double *end, uint8_t *flags, uint32_t *n_steps, uint32_t *n_accepted, int32_t *tri_id,
                    double *bary)
 {
-    BHG_TRY(mesh_trace_check(p, mesh, max_chord, tri_id, bary));
-    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
-    if (mesh->device != c->device) return fail(BHG_E_INVALID, "the mesh lives on another device than the context");
+    BHG_TRY(bhg::mesh_trace_check(p, mesh, max_chord, tri_id, bary));
+    BHG_TRY(bhg::mesh_on_device_of(c, mesh));
     if (n == 0) return BHG_OK;
     if (!x0 || !k0 || !end) return fail(BHG_E_INVALID, "x0 / k0 / end is NULL");
     if (n > 0xFFFFFFFFull) return fail(BHG_E_INVALID, "n must be < 2^32 per call");
@@ -2595,230 +1654,14 @@ int bhg_trace_mesh(bhg_context *c, const bhg_params *p, const bhg_mesh *mesh, do
     });
 }
 
-// --- mesh instances -----------------------------------------------------------------------------------
-
-}  // extern "C"
-
-namespace {
-
-// the world box of a local box under x -> R x + t: centre R c + t, half extents |R| h, widened outward by the builder's ulps of
-// the largest magnitude involved -- the box, the translation and the local box, whose roundings in p' = R^T (p - t) it has to cover
-void instance_world_box(const double lb[6], const double T[12], double wb[6])
-{
-    const double c[3] = {0.5 * (lb[0] + lb[3]), 0.5 * (lb[1] + lb[4]), 0.5 * (lb[2] + lb[5])};
-    const double h[3] = {0.5 * (lb[3] - lb[0]), 0.5 * (lb[4] - lb[1]), 0.5 * (lb[5] - lb[2])};
-    double mag = 0.0;
-    for (int q = 0; q < 3; q++) {
-        const double *R = T + 3 * q;
-        const double wc = R[0] * c[0] + R[1] * c[1] + R[2] * c[2] + T[9 + q];
-        const double wh = std::fabs(R[0]) * h[0] + std::fabs(R[1]) * h[1] + std::fabs(R[2]) * h[2];
-        wb[q] = wc - wh;
-        wb[3 + q] = wc + wh;
-        mag = std::max(mag, std::fabs(wc) + wh);
-        mag = std::max(mag, std::fabs(T[9 + q]));
-        mag = std::max(mag, std::max(std::fabs(lb[q]), std::fabs(lb[3 + q])));
-    }
-    const double w = bhg::BVH_BOX_ULPS * 2.220446049250313e-16 * std::max(mag, 2.2250738585072014e-308);
-    for (int q = 0; q < 3; q++) {
-        wb[q] -= w;
-        wb[3 + q] += w;
-    }
-}
-
-}  // namespace
-
-namespace bhg {
-// n rigid transforms, or the reason they are refused (bhgeo_frame.hip checks the frame's with it)
-int mesh_instance_transforms_check(int32_t n, const double *T)
-{
-    if (n < 1 || n > BHG_MESH_INSTANCES_MAX) return fail(BHG_E_INVALID, "mesh instances: n must be in [1, BHG_MESH_INSTANCES_MAX]");
-    if (!T) return fail(BHG_E_INVALID, "mesh instances: transforms is NULL");
-    for (int32_t j = 0; j < n; j++) {
-        const double *R = T + (size_t)j * 12;
-        for (int q = 0; q < 12; q++)
-            if (!std::isfinite(R[q])) return fail(BHG_E_INVALID, "mesh instances: every entry of transforms must be finite");
-        for (int a = 0; a < 3; a++)
-            for (int b = 0; b < 3; b++) {
-                const double g = R[a] * R[b] + R[3 + a] * R[3 + b] + R[6 + a] * R[6 + b];
-                if (!(std::fabs(g - (a == b ? 1.0 : 0.0)) <= 1e-9))
-                    return fail(BHG_E_INVALID, "mesh instances: transforms must be rigid, R^T R within 1e-9 of the identity");
-            }
-        const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
-        if (!(det > 0.0)) return fail(BHG_E_INVALID, "mesh instances: transforms must be rotations, det R > 0");
-    }
-    return BHG_OK;
-}
-}  // namespace bhg
-
-namespace {
-
-using bhg::mesh_instance_transforms_check;
-
-bool mesh_is_live(const bhg_mesh *m, uint64_t serial)
-{
-    std::lock_guard<std::mutex> lock(live_meshes_lock);
-    auto it = live_meshes.find(m);
-    return it != live_meshes.end() && it->second == serial;
-}
-
-// the records of n checked transforms against the mesh's root box, and the set's union box and range of distances
-void instance_records(const bhg_mesh *mesh, int32_t n, const double *T, double *rec, double box[6], double &d_min, double &d_max)
-{
-    double t_max = 0.0, near2 = INFINITY;
-    for (int32_t j = 0; j < n; j++) {
-        double *r = rec + (size_t)j * bhg::BHG_MESH_INSTANCE_DOUBLES_;
-        std::memcpy(r, T + (size_t)j * 12, 12 * sizeof(double));
-        instance_world_box(mesh->box, r, r + 12);
-        double d2 = 0.0;
-        for (int q = 0; q < 3; q++) {
-            box[q] = j ? std::min(box[q], r[12 + q]) : r[12 + q];
-            box[3 + q] = j ? std::max(box[3 + q], r[15 + q]) : r[15 + q];
-            const double gap = std::max(std::max(r[12 + q], -r[15 + q]), 0.0);
-            d2 += gap * gap;
-        }
-        near2 = std::min(near2, d2);
-        t_max = std::max(t_max, std::sqrt(r[9] * r[9] + r[10] * r[10] + r[11] * r[11]));
-    }
-    // a point of instance j lies no farther from the origin than |t_j| + the mesh's farthest vertex, and inside its world box
-    d_min = std::sqrt(near2) * (1.0 - 1e-14);
-    d_max = (t_max + mesh->d_max) * (1.0 + 1e-14);
-}
-
-int instances_trace_check(const bhg_params *p, const bhg_mesh_instances *inst, double max_chord, const int32_t *tri_id,
-                          const int32_t *inst_id, const double *bary)
-{
-    BHG_TRY(validate(p));
-    if (p->method != BHG_METHOD_DP54) return fail(BHG_E_INVALID, "the mesh trace is DP5(4) only: method must be BHG_METHOD_DP54");
-    if (p->time_like) return fail(BHG_E_INVALID, "the mesh trace covers null rays only: time_like must be 0");
-    if (!inst) return fail(BHG_E_INVALID, "mesh instances: inst is NULL");
-    if (!std::isfinite(max_chord) || !(max_chord > 0.0)) return fail(BHG_E_INVALID, "max_chord must be finite and > 0");
-    if (!tri_id || !bary) return fail(BHG_E_INVALID, "tri_id / bary is NULL");
-    if (!inst_id) return fail(BHG_E_INVALID, "inst_id is NULL");
-    return BHG_OK;
-}
-
-// reading: the call traces or shades with the set's world boxes, which a refit of the mesh since the last _set has left stale
-int instances_usable(const bhg_context *c, const bhg_mesh_instances *inst, bool reading = true)
-{
-    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
-    if (inst->ctx != c) return fail(BHG_E_INVALID, "mesh instances: the instance set belongs to another context");
-    if (!mesh_is_live(inst->mesh, inst->mesh_serial)) return fail(BHG_E_INVALID, "mesh instances: the set's mesh has been destroyed");
-    if (reading && inst->mesh_generation != inst->mesh->generation)
-        return fail(BHG_E_INVALID, "mesh instances: the set's mesh has been refitted, call bhg_mesh_instances_set after bhg_mesh_refit");
-    return BHG_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int bhg_mesh_instance_box_host(const double local_box[6], const double transform[12], double world_box[6])
-{
-    if (!local_box || !world_box) return fail(BHG_E_INVALID, "mesh instances: local_box / world_box is NULL");
-    for (int q = 0; q < 6; q++)
-        if (!std::isfinite(local_box[q])) return fail(BHG_E_INVALID, "mesh instances: local_box must be finite");
-    BHG_TRY(mesh_instance_transforms_check(1, transform));
-    instance_world_box(local_box, transform, world_box);
-    return BHG_OK;
-}
-
-int bhg_mesh_instances_create(bhg_context *c, const bhg_mesh *mesh, int32_t n, const double *transforms, bhg_mesh_instances **out)
-{
-    if (!out) return fail(BHG_E_INVALID, "out is NULL");
-    *out = nullptr;
-    BHG_TRY(mesh_instance_transforms_check(n, transforms));
-    if (!mesh) return fail(BHG_E_INVALID, "mesh is NULL");
-    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
-    if (mesh->device != c->device) return fail(BHG_E_INVALID, "the mesh lives on another device than the context");
-    ENTER_DEVICE(c->device);
-    bhg_mesh_instances *in = new (std::nothrow) bhg_mesh_instances;
-    if (!in) return fail(BHG_E_NOMEM, "out of host memory");
-    in->ctx = c;
-    in->device = c->device;
-    in->mesh = mesh;
-    in->mesh_serial = mesh->serial;
-    in->mesh_generation = mesh->generation;
-    in->n = n;
-    const size_t bytes = (size_t)n * bhg::BHG_MESH_INSTANCE_DOUBLES_ * sizeof(double);
-    hipError_t e = hipMalloc((void **)&in->d_rec, bytes);
-    for (int k = 0; k < 2 && e == hipSuccess; k++) {
-        e = hipHostMalloc((void **)&in->h_rec[k], bytes, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&in->ev_copy[k], hipEventDisableTiming);
-    }
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&in->ev_read, hipEventDisableTiming);
-    if (e == hipSuccess) {
-        instance_records(mesh, n, transforms, in->h_rec[0], in->box, in->d_min, in->d_max);
-        e = hipMemcpy(in->d_rec, in->h_rec[0], bytes, hipMemcpyHostToDevice);     // (done when the call returns)
-    }
-    if (e != hipSuccess) {
-        bhg_mesh_instances_destroy(in);
-        return fail_hip(e, "bhg_mesh_instances_create: device records");
-    }
-    *out = in;
-    return BHG_OK;
-}
-
-int bhg_mesh_instances_set(bhg_mesh_instances *in, const double *transforms)
-{
-    if (!in) return fail(BHG_E_INVALID, "mesh instances: inst is NULL");
-    BHG_TRY(mesh_instance_transforms_check(in->n, transforms));
-    BHG_TRY(instances_usable(in->ctx, in, false));
-    ENTER_DEVICE(in->ctx->device);
-    const int k = in->last < 0 ? 1 : in->last ^ 1;
-    const size_t bytes = (size_t)in->n * bhg::BHG_MESH_INSTANCE_DOUBLES_ * sizeof(double);
-    HIP_TRY(hipEventSynchronize(in->ev_copy[k]));     // (the copy that read this host buffer last, two _set calls ago: done)
-    double box[6], d_min, d_max;
-    instance_records(in->mesh, in->n, transforms, in->h_rec[k], box, d_min, d_max);
-    // behind every kernel that reads the records now, whatever its stream; the readers to come wait for ev_copy[k]
-    hipStream_t s = in->ctx->stream;
-    if (in->was_read && in->read_stream != s) HIP_TRY(hipStreamWaitEvent(s, in->ev_read, 0));
-    HIP_TRY(hipMemcpyAsync(in->d_rec, in->h_rec[k], bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(in->ev_copy[k], s));
-    in->last = k;
-    in->mesh_generation = in->mesh->generation;
-    std::memcpy(in->box, box, sizeof(box));
-    in->d_min = d_min;
-    in->d_max = d_max;
-    return BHG_OK;
-}
-
-void bhg_mesh_instances_destroy(bhg_mesh_instances *in)
-{
-    if (!in) return;
-    {
-        DeviceGuard g(in->device);
-        // (what is still queued -- a copy, a kernel that reads the records -- runs out first)
-        for (int k = 0; k < 2; k++) {
-            if (in->ev_copy[k]) {
-                (void)hipEventSynchronize(in->ev_copy[k]);
-                (void)hipEventDestroy(in->ev_copy[k]);
-            }
-            if (in->h_rec[k]) (void)hipHostFree(in->h_rec[k]);
-        }
-        if (in->ev_read) {
-            (void)hipEventSynchronize(in->ev_read);
-            (void)hipEventDestroy(in->ev_read);
-        }
-        if (in->d_rec) (void)hipFree(in->d_rec);
-    }
-    delete in;
-}
-
-int bhg_mesh_instances_info(const bhg_mesh_instances *in, int32_t *n, double box[6])
-{
-    if (!in) return fail(BHG_E_INVALID, "mesh instances: inst is NULL");
-    if (n) *n = in->n;
-    if (box) std::memcpy(box, in->box, sizeof(in->box));
-    return BHG_OK;
-}
-
+// ... and of the rigid placements of a mesh
 int bhg_trace_mesh_instances_device(bhg_context *c, const bhg_params *p, const bhg_mesh_instances *inst, double max_chord,
                                     const double *x0_shared, const double *d_x0, const double *d_k0, size_t n, double *d_end,
                                     uint8_t *d_flags, uint32_t *d_n_steps, uint32_t *d_n_accepted, int32_t *d_tri_id,
                                     int32_t *d_inst_id, double *d_bary, void *stream)
 {
-    BHG_TRY(instances_trace_check(p, inst, max_chord, d_tri_id, d_inst_id, d_bary));
-    BHG_TRY(instances_usable(c, inst));
+    BHG_TRY(bhg::instances_trace_check(p, inst, max_chord, d_tri_id, d_inst_id, d_bary));
+    BHG_TRY(bhg::instances_usable(c, inst));
     if (n && !d_end) return fail(BHG_E_INVALID, "end is NULL");
     return trace_device_impl(c, p, {.kind = TraceKind::MESH, .x0_shared = x0_shared, .d_x0 = d_x0, .d_k0 = d_k0, .n = n, .d_end = d_end,
                                     .d_flags = d_flags, .d_n_steps = d_n_steps, .d_n_accepted = d_n_accepted, .stream = stream,
@@ -2830,8 +1673,8 @@ int bhg_trace_mesh_instances(bhg_context *c, const bhg_params *p, const bhg_mesh
                              int x0_is_shared, const double *k0, size_t n, double *end, uint8_t *flags, uint32_t *n_steps,
                              uint32_t *n_accepted, int32_t *tri_id, int32_t *inst_id, double *bary)
 {
-    BHG_TRY(instances_trace_check(p, inst, max_chord, tri_id, inst_id, bary));
-    BHG_TRY(instances_usable(c, inst));
+    BHG_TRY(bhg::instances_trace_check(p, inst, max_chord, tri_id, inst_id, bary));
+    BHG_TRY(bhg::instances_usable(c, inst));
     if (n == 0) return BHG_OK;
     if (!x0 || !k0 || !end) return fail(BHG_E_INVALID, "x0 / k0 / end is NULL");
     if (n > 0xFFFFFFFFull) return fail(BHG_E_INVALID, "n must be < 2^32 per call");
@@ -3447,7 +2290,7 @@ int shade_mesh(bhg_context *c, const MeshShadeCall &call)
     BHG_TRY(scene_check(s.sc, s.samples, true));
     if (m.instances) {
         // (the set's mesh pointer is only trusted once the set is known to be this context's and its mesh alive)
-        BHG_TRY(instances_usable(c, m.instances));
+        BHG_TRY(bhg::instances_usable(c, m.instances));
         m.mesh = m.instances->mesh;
         m.material = m.mat != nullptr;
     }
@@ -3455,8 +2298,7 @@ int shade_mesh(bhg_context *c, const MeshShadeCall &call)
     if (m.material) {
         BHG_TRY(bhg::mesh_material_check(m.mat, (size_t)m.mesh->view.n_tris, false));
     }
-    if (!c) return fail(BHG_E_INVALID, "ctx is NULL");
-    if (m.mesh->device != c->device) return fail(BHG_E_INVALID, "the mesh lives on another device than the context");
+    BHG_TRY(bhg::mesh_on_device_of(c, m.mesh));
     if (s.n_pixels == 0) return BHG_OK;
     if ((!s.rgba && !s.rgba_f32) || !s.end || !s.flags || !s.sc->d_sky || !m.tri_id || !m.bary)
         return fail(BHG_E_INVALID, "NULL device pointer");
@@ -3492,10 +2334,10 @@ int shade_mesh(bhg_context *c, const MeshShadeCall &call)
     }
     if (m.instances) {
         const hipStream_t st = (hipStream_t)s.stream;
-        HIP_TRY(instances_before_read(m.instances, st));
-        HIP_TRY(bhg::launch_shade_mesh_instances(a, m.mesh->view, m.tri_id, m.bary, ma, m.instances->d_rec, m.instances->n, mesh_culls_on(),
+        HIP_TRY(bhg::instances_before_read(m.instances, st));
+        HIP_TRY(bhg::launch_shade_mesh_instances(a, m.mesh->view, m.tri_id, m.bary, ma, m.instances->d_rec, m.instances->n, bhg::mesh_culls_on(),
                                                  m.inst_id, m.inst_rgb, st));
-        HIP_TRY(instances_after_read(m.instances, st));
+        HIP_TRY(bhg::instances_after_read(m.instances, st));
         return BHG_OK;
     }
     HIP_TRY(bhg::launch_shade_mesh_material(a, m.mesh->view, m.tri_id, m.bary, ma, (hipStream_t)s.stream));

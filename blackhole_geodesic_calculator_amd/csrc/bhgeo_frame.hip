@@ -28,47 +28,12 @@
 #include <string>
 #include <vector>
 
-#include "../../include/bhgeo.h"
-#include "geodesic_kernels.h"
+#include "bhgeo_internal.h"
 #include "mesh_bvh.h"
 #include "prefix_clearance.h"
 #include "tile_dealing.h"
 
-namespace bhg {
-int set_error(int code, const std::string &msg);   // bhgeo_capi.hip: the thread-local message of bhg_last_error()
-void host_copy(bhg_context *c, void *dst, const void *src, size_t bytes, size_t piece);   // bhgeo_capi.hip: multi-threaded memcpy in jobs of `piece` bytes
-// bhgeo_capi.hip: redshift settings checked against the trace parameters (disk_r_in < 0: no disk to check)
-int redshift_params(const bhg_params *p, const bhg_redshift *rs, double disk_r_in, const double *x0, RedshiftParams *out);
-// bhgeo_capi.hip: observer settings checked against the trace parameters and the camera
-int observer_params(const bhg_params *p, const bhg_observer *obs, const double *x0, ObserverParams *out);
-// bhgeo_capi.hip: object textures checked against a scene of n_spheres spheres
-int object_texture_params(const bhg_object_textures *ot, int32_t n_spheres, ObjectTextureParams *out);
-// bhgeo_capi.hip: the thermal-disk settings on their own, and against the trace parameters, the disk and the camera
-int thermal_check(const bhg_disk_thermal *th);
-int thermal_params(const bhg_params *p, const bhg_disk_thermal *th, const bhg_redshift *rs, const bhg_polarisation *pol,
-                   double disk_r_in, const double *x0, ThermalParams *out, RedshiftParams *rp);
-// bhgeo_capi.hip: object motion on its own (finite, for n_spheres spheres), and against the spheres and the trace parameters
-int motion_check(const bhg_object_motion *mo, int32_t n_spheres);
-int motion_params(const bhg_params *p, const bhg_object_motion *mo, const double *spheres, int32_t n_spheres, MotionParams *out);
-// ... and of a mesh material (host_arrays: tri_uv / tri_tex are host arrays and are scanned)
-int mesh_material_check(const bhg_mesh_material *m, size_t nt, bool host_arrays);
-// ... and of the transforms of mesh instances
-int mesh_instance_transforms_check(int32_t n, const double *T);
-// ... a mesh built on the device from host arrays, which are uploaded first
-int mesh_create_built_on_device(bhg_context *c, const double *vertices, size_t n_vertices, const int32_t *triangles, size_t n_triangles,
-                                const double *vertex_normals, int32_t leaf_size, size_t cap_vertices, size_t cap_triangles,
-                                bool host_arrays, hipStream_t stream, bhg_mesh **out);
-}
-
 namespace {
-
-int fail(int code, const std::string &msg) { return bhg::set_error(code, msg); }
-
-int fail_hip(hipError_t e, const char *what)
-{
-    (void)hipGetLastError();     // (reported here: not again by the next launch's status)
-    return bhg::set_error(e == hipErrorOutOfMemory ? BHG_E_NOMEM : BHG_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
 
 // No C++ exception leaves the library through the C ABI: the entry points that use standard containers (the jitter stream and
 // the images are copied into vectors, the tile dealing sorts) are function-try-blocks that end here.
@@ -84,32 +49,6 @@ int host_exception()
         return fail(BHG_E_HIP, "internal error: unknown exception");
     }
 }
-
-#define HIP_TRY(expr)                                     \
-    do {                                                  \
-        hipError_t _e = (expr);                           \
-        if (_e != hipSuccess) return fail_hip(_e, #expr); \
-    } while (0)
-#define BHG_TRY(expr)                 \
-    do {                              \
-        int _rc = (expr);             \
-        if (_rc != BHG_OK) return _rc; \
-    } while (0)
-
-struct DeviceScope {   // the calling thread's current device is put back on the way out of every entry point
-    int prev = -1;
-    DeviceScope()
-    {
-        if (hipGetDevice(&prev) != hipSuccess) {
-            (void)hipGetLastError();
-            prev = -1;
-        }
-    }
-    ~DeviceScope()
-    {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
 
 // ---- RCCL, loaded at run time (libbhgeo.so itself links only the HIP runtime) ---------------------------------------
 typedef void *nccl_comm_t;
@@ -709,7 +648,7 @@ try {
     if (gather == BHG_FRAME_GATHER_RCCL && !distinct)
         return fail(BHG_E_INVALID, "RCCL needs distinct devices (a repeated device gathers by device-to-device copies)");
     if (gather == BHG_FRAME_GATHER_RCCL && !rccl().ok()) return fail(BHG_E_HIP, "librccl.so could not be loaded");
-    DeviceScope scope;
+    DeviceGuard scope;
     struct Guard {        // (an exception on the way -- the jitter copy, the dealing -- must not leave the half-built frame behind)
         bhg_frame *f = nullptr;
         ~Guard() { if (f) destroy_frame(f); }
@@ -790,7 +729,7 @@ try {
 
 void bhg_frame_destroy(bhg_frame *f)
 {
-    DeviceScope scope;
+    DeviceGuard scope;
     destroy_frame(f);
 }
 
@@ -913,7 +852,7 @@ try {
             std::vector<float>().swap(f->otex[j]);
             f->otex_w[j] = f->otex_h[j] = 0;
         }
-        DeviceScope scope;
+        DeviceGuard scope;
         for (auto &s : f->sh) {
             for (DevBuf &b : s.otex) b.release();
             s.otex_ready = false;
@@ -959,15 +898,13 @@ try {
         f->mesh = bhg_frame::Mesh();
         f->inst.clear();
         f->inst_rgb.clear();
-        DeviceScope scope;
+        DeviceGuard scope;
         for (auto &s : f->sh) release_shard_mesh(s);
         return BHG_OK;
     }
     // bhg_mesh_create's checks and the material's, before anything of the frame's changes
     if (const char *why = bhg::mesh_refusal(vertices, n_vertices, triangles, n_triangles, leaf_size)) return fail(BHG_E_INVALID, why);
-    if (vertex_normals)
-        for (size_t i = 0; i < n_vertices * 3; i++)
-            if (!std::isfinite(vertex_normals[i])) return fail(BHG_E_INVALID, "mesh: every vertex normal must be finite");
+    BHG_TRY(bhg::mesh_finite_check(nullptr, vertex_normals, n_vertices * 3));     // (the vertices: mesh_refusal)
     if (!std::isfinite(max_chord) || max_chord < 0.0)
         return fail(BHG_E_INVALID, "max_chord must be finite and >= 0 (0: a quarter of r_s)");
     if (f->mesh_build_device && leaf_size > bhg::MORTON_LEAF_MAX)
@@ -1017,11 +954,7 @@ try {
         return fail(BHG_E_INVALID, "mesh refit: vertex_normals is NULL for a mesh that was created with them");
     if (std::isnan(rebuild_ratio)) return fail(BHG_E_INVALID, "mesh refit: rebuild_ratio is NaN");
     const size_t n3 = m.vertices.size();
-    for (size_t i = 0; i < n3; i++)
-        if (!std::isfinite(vertices[i])) return fail(BHG_E_INVALID, "mesh: every vertex must be finite");
-    if (vertex_normals)
-        for (size_t i = 0; i < n3; i++)
-            if (!std::isfinite(vertex_normals[i])) return fail(BHG_E_INVALID, "mesh: every vertex normal must be finite");
+    BHG_TRY(bhg::mesh_finite_check(vertices, vertex_normals, n3));
     std::copy(vertices, vertices + n3, m.vertices.begin());
     if (vertex_normals) std::copy(vertex_normals, vertex_normals + n3, m.normals.begin());
     m.rebuild_ratio = rebuild_ratio;
@@ -1040,7 +973,7 @@ try {
         // off: the plain mesh render again
         f->inst.clear();
         f->inst_rgb.clear();
-        DeviceScope scope;
+        DeviceGuard scope;
         for (auto &s : f->sh) release_shard_instances(s);
         return BHG_OK;
     }
@@ -1066,7 +999,7 @@ try {
     if ((p->disk_r_out > 0.0) != (f->scene.disk_r_out > 0.0) ||
         (p->disk_r_out > 0.0 && (p->disk_r_in != f->scene.disk_r_in || p->disk_r_out != f->scene.disk_r_out)))
         return fail(BHG_E_INVALID, "the disk of the trace parameters and of the scene differ");
-    DeviceScope scope;
+    DeviceGuard scope;
     const size_t world = f->sh.size(), HW = (size_t)f->cam.width * (size_t)f->cam.height;
     const int S = f->cam.samples;
     const bool has_obj = f->scene.n_spheres > 0, has_disk = f->scene.disk_r_out > 0.0;
@@ -1378,7 +1311,7 @@ try {
 int bhg_frame_synchronize(bhg_frame *f)
 {
     if (!f) return fail(BHG_E_INVALID, "frame is NULL");
-    DeviceScope scope;
+    DeviceGuard scope;
     for (auto &s : f->sh) {
         HIP_TRY(hipSetDevice(s.device));
         HIP_TRY(hipStreamSynchronize(s.stream));
@@ -1392,7 +1325,7 @@ int bhg_frame_stats(bhg_frame *f, uint64_t out[4])
 try {
     if (!f || !out) return fail(BHG_E_INVALID, "bad argument");
     if (!f->rendered) return fail(BHG_E_INVALID, "no render yet");
-    DeviceScope scope;
+    DeviceGuard scope;
     const int W = f->cam.width, T = f->tile, tx = (W + T - 1) / T, ty = (f->cam.height + T - 1) / T;
     f->tile_cost.assign((size_t)tx * ty, 0.0);
     uint64_t rays = 0, att = 0, acc = 0, hor = 0;
@@ -1433,7 +1366,7 @@ try {
     if (!(root_share > 0.0 && root_share <= 1.0)) return fail(BHG_E_INVALID, "root_share must be in (0, 1] (0 = 1)");
     uint64_t st[4];
     BHG_TRY(bhg_frame_stats(f, st));   // (fills tile_cost from the last render's attempted steps)
-    DeviceScope scope;
+    DeviceGuard scope;
     f->dealt_by_cost = true;
     f->root_share = root_share;
     deal_tiles(f);
@@ -1502,7 +1435,7 @@ int bhg_frame_set_profiling(bhg_frame *f, int enable)
 int bhg_frame_last_ms(bhg_frame *f, float *trace_ms, float *root_ms)
 try {
     if (!f || !trace_ms) return fail(BHG_E_INVALID, "bad argument");
-    DeviceScope scope;
+    DeviceGuard scope;
     bool any = false;
     for (size_t r = 0; r < f->sh.size(); r++) {
         Shard &s = f->sh[r];

@@ -1,4 +1,4 @@
-// geodesic_kernels.h -- internal interface between the C-ABI layer (bhgeo_capi.hip) and the
+// geodesic_kernels.h -- internal interface between the C-ABI layer (bhgeo_capi.hip and its units) and the
 // gfx950 kernels (geodesic_kernels.hip).  Not installed; the public surface is include/bhgeo.h.
 #pragma once
 #include <hip/hip_runtime.h>

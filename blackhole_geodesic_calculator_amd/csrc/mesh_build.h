@@ -1,4 +1,4 @@
-// mesh_build.h -- the build of a mesh's tree on the device: what bhgeo_capi.hip hands to mesh_build.hip.
+// mesh_build.h -- the build of a mesh's tree on the device: what bhgeo_mesh.hip hands to mesh_build.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,4 +1,4 @@
-// mesh_refit.h -- the refit of a mesh's tree on the device: what bhgeo_capi.hip hands to mesh_refit.hip.
+// mesh_refit.h -- the refit of a mesh's tree on the device: what bhgeo_mesh.hip hands to mesh_refit.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,7 +1,7 @@
 // mesh_refit.hip -- the refit kernels: new vertices into a tree whose topology stands.
 //
 // Everything here restates a host loop, operation for operation, so that the device leaves the bits the host would:
-//   slot records   bhg_mesh_create's v0, v1 - v0, v2 - v0 and N0, N1, N2 per leaf slot (bhgeo_capi.hip);
+//   slot records   bhg_mesh_create's v0, v1 - v0, v2 - v0 and N0, N1, N2 per leaf slot (bhgeo_mesh.hip);
 //   boxes          fit_boxes of mesh_bvh.h: std::min(b, x) is written out as (x < b ? x : b) and std::max(b, x) as (b < x ? x : b),
 //                  which also settles which zero survives when -0.0 meets +0.0;
 //   area sum       area_sum of mesh_bvh.h: BVH_AREA_LANES strided partial sums, then a halving tree.

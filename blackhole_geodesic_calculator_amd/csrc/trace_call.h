@@ -1,6 +1,6 @@
 // trace_call.h -- a trace call as plain data, and the two pieces of pure arithmetic of the C-API layer (bhgeo_capi.hip): how a
 // call of any size is cut into launches, and where the arrays of a host-buffer call lie in their one device block.  Host only,
-// no HIP: tests/trace_call_driver.cpp runs both under the host sanitizers.
+// no HIP: tests/trace_call_driver.cpp runs both under the host sanitizers.  (mesh_layout.h is its like for bhgeo_mesh.hip.)
 #pragma once
 
 #include <cstddef>

@@ -5,7 +5,7 @@ of the instanced trace and of both shades, bit for bit: the tree only accelerate
 section 19, through a refit, through rebuilds in place within a capacity, and the refusals.
 
 The bad-index cases below are safe to run because no kernel follows a triangle index before the build's scan -- which reads the
-triangle array alone -- has been read back and found clean (csrc/mesh_build.hip, build_run in csrc/bhgeo_capi.hip): they end in
+triangle array alone -- has been read back and found clean (csrc/mesh_build.hip, build_run in csrc/bhgeo_mesh.hip): they end in
 BHG_E_INVALID, and nothing here provokes anything else."""
 import os
 import sys
