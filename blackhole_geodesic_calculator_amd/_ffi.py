@@ -65,7 +65,7 @@ EXPORTS = (
     "bhg_frame_set_object_motion",
     "bhg_math_probe",
     "bhg_trace_start_device", "bhg_start_steps_match", "bhg_trace_prefix_device", "bhg_prefix_clearance",
-    "bhg_prefix_deep_attempts", "bhg_prefix_wide_accepted", "bhg_prefix_owner_next", "bhg_frame_prefix_info",
+    "bhg_prefix_deep_attempts", "bhg_prefix_wide_accepted", "bhg_prefix_owner_next", "bhg_frame_prefix_info", "bhg_prefix_rim_attempts",
     "bhg_trace_crossings_device", "bhg_trace_crossings", "bhg_disk_layers_size", "bhg_shade_disk_layers_device",
     "bhg_travel_time_device", "bhg_travel_time", "bhg_shade_disk_layers_retarded_device",
     "bhg_mesh_create", "bhg_mesh_destroy", "bhg_mesh_info", "bhg_mesh_bvh_host", "bhg_trace_mesh_device", "bhg_trace_mesh",
@@ -95,6 +95,8 @@ PREFIX_K_MAX, PREFIX_BYTES_PER_RAY = 4, 112
 PREFIX_RECORD_DEEP, PREFIX_DEEP_ACCEPTED, PREFIX_DEEP_ATTEMPTS = 4, 6, 12
 # ... by the wide rule (BHG_PREFIX_RECORD_WIDE): the deep rule in fifteen sixteenths of the ball, up to eight accepted steps
 PREFIX_RECORD_WIDE, PREFIX_WIDE_ACCEPTED = 5, 8
+# ... by the rim rule (BHG_PREFIX_RECORD_RIM): the wide rule in the ball that ends just above the horizon, nine accepted steps in fifteen attempts
+PREFIX_RECORD_RIM, PREFIX_RIM_ACCEPTED, PREFIX_RIM_ATTEMPTS = 6, 9, 15
 
 
 class Prefix(C.Structure):
@@ -518,6 +520,9 @@ def load():
         L.bhg_prefix_owner_next.argtypes = [C.POINTER(PrefixOwner), C.c_int32, C.c_int32, C.POINTER(Params), _dp, C.c_int32, _dp, C.POINTER(Prefix)]
         L.bhg_frame_prefix_info.restype = C.c_int
         L.bhg_frame_prefix_info.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Prefix)]
+    if hasattr(L, "bhg_prefix_rim_attempts"):      # (a library from before the rim rule: has_rim_prefix())
+        L.bhg_prefix_rim_attempts.restype = C.c_int32
+        L.bhg_prefix_rim_attempts.argtypes = []
     L.bhg_start_steps_match.restype = C.c_int
     L.bhg_start_steps_match.argtypes = [C.POINTER(Params), C.POINTER(Params)]
     L.bhg_shade_dir_device.restype = C.c_int
@@ -1196,6 +1201,12 @@ def has_wide_prefix() -> bool:
     """Does the loaded library take BHG_PREFIX_RECORD_WIDE and decide an owner's re-recording (it then exports
     bhg_prefix_wide_accepted and bhg_prefix_owner_next)?"""
     return has_deep_prefix() and hasattr(load(), "bhg_prefix_wide_accepted")
+
+
+def has_rim_prefix() -> bool:
+    """Does the loaded library take BHG_PREFIX_RECORD_RIM, as a mode and as the rule bhg_prefix_owner_next promotes to (it then
+    exports bhg_prefix_rim_attempts)?"""
+    return has_wide_prefix() and hasattr(load(), "bhg_prefix_rim_attempts")
 
 
 def prefix_owner_next(owner: "PrefixOwner", rule: int, params: "Params", x0, spheres=None, last: "Prefix" = None,

@@ -42,8 +42,13 @@ static_assert(BHG_PREFIX_WIDE_ACCEPTED == bhg::BHG_PREFIX_WIDE_ACCEPTED_ && BHG_
               "wide start-up record limits mismatch");
 static_assert(BHG_PREFIX_NONE == bhg::PREFIX_MODE_NONE && BHG_PREFIX_RECORD == bhg::PREFIX_MODE_RECORD &&
                   BHG_PREFIX_REPLAY == bhg::PREFIX_MODE_REPLAY && BHG_PREFIX_RECORD_DEEP == bhg::PREFIX_MODE_RECORD_DEEP &&
-                  BHG_PREFIX_RECORD_WIDE == bhg::PREFIX_MODE_RECORD_WIDE,
+                  BHG_PREFIX_RECORD_WIDE == bhg::PREFIX_MODE_RECORD_WIDE && BHG_PREFIX_RECORD_RIM == bhg::PREFIX_MODE_RECORD_RIM,
               "start-up record modes mismatch");
+static_assert(BHG_PREFIX_RIM_ACCEPTED == bhg::BHG_PREFIX_RIM_ACCEPTED_ && BHG_PREFIX_RIM_ATTEMPTS == bhg::BHG_PREFIX_RIM_ATTEMPTS_ &&
+                  BHG_PREFIX_RIM_ACCEPTED == bhg::PREFIX_RIM_ACCEPTED && BHG_PREFIX_RIM_ATTEMPTS == bhg::PREFIX_RIM_ATTEMPTS &&
+                  BHG_PREFIX_WIDE_ACCEPTED <= BHG_PREFIX_RIM_ACCEPTED && BHG_PREFIX_RIM_ACCEPTED <= BHG_PREFIX_RIM_ATTEMPTS &&
+                  BHG_PREFIX_DEEP_ATTEMPTS <= BHG_PREFIX_RIM_ATTEMPTS,
+              "rim start-up record limits mismatch");
 static_assert(BHG_METHOD_DP54 == bhg::BHG_METHOD_DP54_ && BHG_METHOD_RK4 == bhg::BHG_METHOD_RK4_, "method mismatch");
 static_assert(BHG_RHS_CHRISTOFFEL == bhg::BHG_RHS_CHRISTOFFEL_ && BHG_RHS_REDUCED == bhg::BHG_RHS_REDUCED_ &&
                   BHG_RHS_KERR_BL == bhg::BHG_RHS_KERR_BL_,
@@ -1089,9 +1094,10 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const TraceCall &tc)
     if (pf) {
         pf->used = BHG_PREFIX_NONE;
         if (pf->mode != BHG_PREFIX_NONE && pf->mode != BHG_PREFIX_RECORD && pf->mode != BHG_PREFIX_REPLAY &&
-            pf->mode != BHG_PREFIX_RECORD_DEEP && pf->mode != BHG_PREFIX_RECORD_WIDE)
+            pf->mode != BHG_PREFIX_RECORD_DEEP && pf->mode != BHG_PREFIX_RECORD_WIDE && pf->mode != BHG_PREFIX_RECORD_RIM)
             return fail(BHG_E_INVALID,
-                        "prefix mode must be BHG_PREFIX_NONE, BHG_PREFIX_RECORD, BHG_PREFIX_REPLAY, BHG_PREFIX_RECORD_DEEP or BHG_PREFIX_RECORD_WIDE");
+                        "prefix mode must be BHG_PREFIX_NONE, BHG_PREFIX_RECORD, BHG_PREFIX_REPLAY, BHG_PREFIX_RECORD_DEEP, BHG_PREFIX_RECORD_WIDE "
+                        "or BHG_PREFIX_RECORD_RIM");
         if (n && pf->mode != BHG_PREFIX_NONE && !pf->d_records) return fail(BHG_E_INVALID, "prefix mode asks for d_records, which is NULL");
     }
     if (start_mode != BHG_START_NONE && start_mode != BHG_START_RECORD && start_mode != BHG_START_REPLAY)
@@ -1183,7 +1189,7 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const TraceCall &tc)
     // (the planes' stride is the launch's n), a step budget the records cannot exhaust.  Anything else ignores them, as RK4
     // ignores the start steps, and says so in pf->used.
     bool pf_record = false, pf_deep = false;
-    uint32_t pf_acc_max = (uint32_t)BHG_PREFIX_DEEP_ACCEPTED;
+    uint32_t pf_acc_max = (uint32_t)BHG_PREFIX_DEEP_ACCEPTED, pf_att_max = (uint32_t)BHG_PREFIX_DEEP_ATTEMPTS;
     double pf_rho = 0.0;
     if (pf && pf->mode != BHG_PREFIX_NONE && !lanes && !d_x0 && p->method == BHG_METHOD_DP54 &&
         (rhs_id == bhg::BHG_RHS_CHRISTOFFEL_ || rhs_id == bhg::BHG_RHS_REDUCED_) && a.max_steps > (uint32_t)BHG_PREFIX_K_MAX) {
@@ -1203,6 +1209,23 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const TraceCall &tc)
             pf_rho = deep_fits ? bhg::prefix_rho_wide_call(clear, a.r_hor, x0_shared, n_spheres) : 0.0;
             pf_record = pf_deep = pf_rho > 0.0;
             if (pf_rho > bhg::prefix_rho_deep_call(clear, a.r_hor, x0_shared, n_spheres)) pf_acc_max = (uint32_t)BHG_PREFIX_WIDE_ACCEPTED;
+        } else if (pf->mode == BHG_PREFIX_RECORD_RIM) {
+            // (the same recorder in the ball that ends just above the horizon, with both caps raised to what that ball holds; where
+            // the rule keeps the wide call's ball it keeps that call's caps and budget, and the records are that call's byte for byte)
+            const double wide_rho = bhg::prefix_rho_wide_call(clear, a.r_hor, x0_shared, n_spheres);
+            pf_rho = deep_fits ? bhg::prefix_rho_rim_call(clear, a.r_hor, x0_shared, n_spheres) : 0.0;
+            if (pf_rho > wide_rho) {
+                pf_acc_max = (uint32_t)BHG_PREFIX_RIM_ACCEPTED;
+                pf_att_max = (uint32_t)BHG_PREFIX_RIM_ATTEMPTS;
+                if (!(a.max_steps > (uint32_t)BHG_PREFIX_RIM_ATTEMPTS)) pf_rho = 0.0;
+            } else if (pf_rho > bhg::prefix_rho_deep_call(clear, a.r_hor, x0_shared, n_spheres)) {
+                pf_acc_max = (uint32_t)BHG_PREFIX_WIDE_ACCEPTED;
+            }
+            pf_record = pf_deep = pf_rho > 0.0;
+        } else if (deep_fits && a.max_steps <= (uint32_t)BHG_PREFIX_RIM_ATTEMPTS && bhg::prefix_rho_is_rim(pf->rho, a.r_hor, x0_shared)) {
+            // (rim records say so by their rho: from this origin no other rule writes one this large.  They hold up to
+            // BHG_PREFIX_RIM_ATTEMPTS attempts, and a caller that asks for them under a budget those would exhaust is told)
+            return fail(BHG_E_INVALID, "BHG_PREFIX_REPLAY of rim records needs max_steps > BHG_PREFIX_RIM_ATTEMPTS");
         } else if (deep_fits && bhg::prefix_replay_ok(clear, pf->rho)) {
             a.prefix = (const double2 *)pf->d_records;
             pf->used = BHG_PREFIX_REPLAY;
@@ -1299,7 +1322,7 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const TraceCall &tc)
         if (!c->counters_clean) HIP_TRY(hipMemsetAsync(c->counter, 0, 2 * 8 * 256, s));   // first call, or after a failed enqueue
         if (pf_record) {
             // the recording pass, in front of the trace of always (which starts its rays itself: the records are for later calls)
-            HIP_TRY(bhg::launch_record_prefix(a, rhs_id, pf->d_records, pf_rho, pf_deep, pf_acc_max, s));
+            HIP_TRY(bhg::launch_record_prefix(a, rhs_id, pf->d_records, pf_rho, pf_deep, pf_acc_max, pf_att_max, s));
             pf->rho = pf_rho;
             pf->used = pf->mode;
         }
@@ -1471,6 +1494,7 @@ double bhg_prefix_clearance(const bhg_params *p, const double *spheres, int32_t 
 
 int32_t bhg_prefix_deep_attempts(void) { return BHG_PREFIX_DEEP_ATTEMPTS; }
 int32_t bhg_prefix_wide_accepted(void) { return BHG_PREFIX_WIDE_ACCEPTED; }
+int32_t bhg_prefix_rim_attempts(void) { return BHG_PREFIX_RIM_ATTEMPTS; }
 
 // when an owner records again: bhg::PrefixOwner (prefix_clearance.h) on the call's own clearance, for bhg_frame_render and the binding alike
 static_assert(sizeof(bhg_prefix_owner) == 24, "bhg_prefix_owner layout is part of the ABI");
@@ -1478,8 +1502,9 @@ int32_t bhg_prefix_owner_next(bhg_prefix_owner *o, int32_t rule, int32_t promote
                               int32_t n_spheres, const double *x0, const bhg_prefix *last)
 {
     if (!o || !p || !x0 || n_spheres < 0 || (n_spheres > 0 && !spheres)) return BHG_PREFIX_NONE;
-    if (rule != BHG_PREFIX_RECORD && rule != BHG_PREFIX_RECORD_DEEP && rule != BHG_PREFIX_RECORD_WIDE) return BHG_PREFIX_NONE;
-    if (promote != BHG_PREFIX_NONE && promote != BHG_PREFIX_RECORD_DEEP && promote != BHG_PREFIX_RECORD_WIDE) return BHG_PREFIX_NONE;
+    if (!bhg::prefix_mode_records(rule)) return BHG_PREFIX_NONE;
+    if (promote != BHG_PREFIX_NONE && promote != BHG_PREFIX_RECORD_DEEP && promote != BHG_PREFIX_RECORD_WIDE && promote != BHG_PREFIX_RECORD_RIM)
+        return BHG_PREFIX_NONE;
     bhg::TraceArgs a;
     std::memset(&a, 0, sizeof(a));
     fill_trace_args(a, p, nullptr, 0);
@@ -1495,7 +1520,7 @@ int32_t bhg_prefix_owner_next(bhg_prefix_owner *o, int32_t rule, int32_t promote
     o->clean_run = w.clean_run;
     o->refused_run = w.refused_run;
     o->roomy_run = w.roomy_run;
-    return ask;
+    return bhg::prefix_owner_fit_budget(ask, w.rho, a.r_hor, x0, a.max_steps);
 }
 
 // THE list of what a ray's initial step depends on beside the ray itself (initial_record, geodesic_kernels.hip): the

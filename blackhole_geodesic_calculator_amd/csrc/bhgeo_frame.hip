@@ -1027,8 +1027,18 @@ try {
     const char *wp_env = std::getenv("BHGEO_WIDE_PREFIX");
     const bool no_deep = dp_env && dp_env[0] == '0' && dp_env[1] == 0;
     const bool wide_off = wp_env && wp_env[0] == '0' && wp_env[1] == 0, wide_now = wp_env && wp_env[0] == '1' && wp_env[1] == 0;
-    const int32_t record_mode = no_deep ? BHG_PREFIX_RECORD : wide_now ? BHG_PREFIX_RECORD_WIDE : BHG_PREFIX_RECORD_DEEP;
-    const int32_t promote_mode = (no_deep || wide_off || wide_now) ? BHG_PREFIX_NONE : BHG_PREFIX_RECORD_WIDE;
+    // ... and after a further run on wide records by BHG_PREFIX_RECORD_RIM, the next rung of the same ladder.  BHGEO_RIM_PREFIX "1":
+    // by the rim rule from the first render; "0": never, the ladder ends at the wide rule as it did before there was a rim rule (A/B)
+    const char *rp_env = std::getenv("BHGEO_RIM_PREFIX");
+    const bool rim_off = rp_env && rp_env[0] == '0' && rp_env[1] == 0, rim_now = rp_env && rp_env[0] == '1' && rp_env[1] == 0;
+    const int32_t record_mode = no_deep   ? BHG_PREFIX_RECORD
+                                : rim_now ? BHG_PREFIX_RECORD_RIM
+                                : wide_now ? BHG_PREFIX_RECORD_WIDE
+                                           : BHG_PREFIX_RECORD_DEEP;
+    const int32_t promote_mode = (no_deep || rim_now || wide_off) ? BHG_PREFIX_NONE
+                                 : !rim_off                        ? BHG_PREFIX_RECORD_RIM
+                                 : wide_now                        ? BHG_PREFIX_NONE
+                                                                   : BHG_PREFIX_RECORD_WIDE;
     const bool redshift = f->rs.apply != 0;
     if (redshift) {   // (refused before anything is enqueued)
         bhg::RedshiftParams rp;
@@ -1157,6 +1167,8 @@ try {
                 // (r_s is the horizon of every call that writes records: a Kerr render holds none, and none is NONE at once)
                 pf.mode = s.start_owner.next(record_mode, bhg_prefix_clearance(&prm, sph, n_sph, f->cam.origin), prm.r_s, f->cam.origin,
                                              n_sph, s.start_last.mode, s.start_last.used, s.start_last.rho, promote_mode);
+                pf.mode = bhg::prefix_owner_fit_budget(pf.mode, s.start_owner.rho, prm.r_s, f->cam.origin,
+                                                       prm.max_steps ? prm.max_steps : (1ull << 20));
                 pf.rho = s.start_owner.rho;
             }
         } else {

@@ -49,6 +49,8 @@ constexpr int BHG_PREFIX_K_MAX_ = 4;        // accepted steps a start-up record 
 constexpr int BHG_PREFIX_DEEP_ACCEPTED_ = 6;    // ... a DEEP record: accepted steps at most (BHG_PREFIX_DEEP_ACCEPTED)
 constexpr int BHG_PREFIX_DEEP_ATTEMPTS_ = 12;   // ... and attempts, the rejected ones among them (BHG_PREFIX_DEEP_ATTEMPTS)
 constexpr int BHG_PREFIX_WIDE_ACCEPTED_ = 8;    // ... a WIDE record: accepted steps at most, in the same attempts (BHG_PREFIX_WIDE_ACCEPTED)
+constexpr int BHG_PREFIX_RIM_ACCEPTED_ = 9;     // ... a RIM record: accepted steps at most (BHG_PREFIX_RIM_ACCEPTED)
+constexpr int BHG_PREFIX_RIM_ATTEMPTS_ = 15;    // ... and attempts (BHG_PREFIX_RIM_ATTEMPTS)
 // rays per trace launch: the kernels form a ray's result offsets (idx * 48 at most) in 32 bits
 constexpr uint64_t BHG_MAX_RAYS_PER_LAUNCH = 1ull << 26;
 
@@ -376,8 +378,10 @@ hipError_t launch_shade_mesh_instances(const ShadeArgs &a, const MeshView &m, co
 // the recording pass of the start-up records (record_prefix_kernel: one lane per ray; rhs Christoffel or reduced, a.x0 == nullptr):
 // rec [7][a.n] 16-byte planes, rho the radius about a.x0s the recorded steps stay inside.  deep: the record carries on through
 // rejected attempts (deep: at most acc_max accepted steps -- BHG_PREFIX_DEEP_ACCEPTED_, or BHG_PREFIX_WIDE_ACCEPTED_ for
-// BHG_PREFIX_RECORD_WIDE -- in BHG_PREFIX_DEEP_ATTEMPTS_ attempts; acc_max is not looked at otherwise)
-hipError_t launch_record_prefix(const TraceArgs &a, int rhs, void *rec, double rho, bool deep, uint32_t acc_max, hipStream_t s);
+// BHG_PREFIX_RECORD_WIDE -- in att_max = BHG_PREFIX_DEEP_ATTEMPTS_ attempts, or BHG_PREFIX_RIM_ACCEPTED_ in BHG_PREFIX_RIM_ATTEMPTS_ for
+// BHG_PREFIX_RECORD_RIM; neither cap is looked at otherwise)
+hipError_t launch_record_prefix(const TraceArgs &a, int rhs, void *rec, double rho, bool deep, uint32_t acc_max, uint32_t att_max,
+                                hipStream_t s);
 // Kerr: after the last pass of a call, Boyer-Lindquist end states -> Cartesian
 hipError_t launch_kerr_finalize(const TraceArgs &a, double *dir_out, hipStream_t s);
 // the Kerr instantiations live in their own translation unit (geodesic_kernels_kerr.hip: same source, same flags --

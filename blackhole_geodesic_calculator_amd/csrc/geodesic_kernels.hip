@@ -3770,10 +3770,11 @@ hipError_t launch_trace_mesh_instances(const TraceArgs &a, const MeshArgs &m, co
 //   * an accepted attempt that ends farther than rho from the start point (rejections in front of it are kept: same point,
 //     smaller h, bit set), or
 //   * accepted step number acc_max + 1 (a launch argument: BHG_PREFIX_DEEP_ACCEPTED_ by the deep rule, BHG_PREFIX_WIDE_ACCEPTED_
-//     by the wide one, whose larger ball holds up to eight) or attempt number BHG_PREFIX_DEEP_ATTEMPTS_ + 1,
+//     by the wide one, whose larger ball holds up to eight, BHG_PREFIX_RIM_ACCEPTED_ by the rim one) or attempt number att_max + 1
+//     (a launch argument too: BHG_PREFIX_DEEP_ATTEMPTS_, or BHG_PREFIX_RIM_ATTEMPTS_ by the rim rule),
 // and the last plane is (i, attempted, accepted, rejected).  A record is usable when attempted != 0.
 template <int RHS, bool DEEP>
-__global__ void __launch_bounds__(64) record_prefix_kernel(const TraceArgs A, double2 *rec, double rho, uint32_t deep_acc_max)
+__global__ void __launch_bounds__(64) record_prefix_kernel(const TraceArgs A, double2 *rec, double rho, uint32_t deep_acc_max, uint32_t deep_att_max)
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= A.n) return;
@@ -3787,7 +3788,7 @@ __global__ void __launch_bounds__(64) record_prefix_kernel(const TraceArgs A, do
         const double o[3] = {K.x[0], K.x[1], K.x[2]};
         const double rho2 = rho * rho;
         const uint32_t acc_max = DEEP ? deep_acc_max : (uint32_t)BHG_PREFIX_K_MAX_;
-        while (K.n_acc < acc_max && (!DEEP || K.n_att < (uint32_t)BHG_PREFIX_DEEP_ATTEMPTS_)) {
+        while (K.n_acc < acc_max && (!DEEP || K.n_att < deep_att_max)) {
             RayState T = K;
             StepTry P;
             const uint32_t st = dp54_attempt<RHS>(A, T, P);
@@ -3812,14 +3813,15 @@ __global__ void __launch_bounds__(64) record_prefix_kernel(const TraceArgs A, do
     reinterpret_cast<uint4 *>(rec)[6 * n + i] = make_uint4((uint32_t)i, K.n_att, K.n_acc, K.rejected ? 1u : 0u);
 }
 
-hipError_t launch_record_prefix(const TraceArgs &a, int rhs, void *rec, double rho, bool deep, uint32_t acc_max, hipStream_t s)
+hipError_t launch_record_prefix(const TraceArgs &a, int rhs, void *rec, double rho, bool deep, uint32_t acc_max, uint32_t att_max,
+                                hipStream_t s)
 {
-    if (deep && (acc_max < 1u || acc_max > (uint32_t)BHG_PREFIX_DEEP_ATTEMPTS_)) return hipErrorInvalidValue;
+    if (deep && (acc_max < 1u || acc_max > att_max || att_max > (uint32_t)BHG_PREFIX_RIM_ATTEMPTS_)) return hipErrorInvalidValue;
     return launch_lanes(a, rhs, [&](auto R, dim3 grid) {
         if (deep)
-            BHG_LAUNCH((record_prefix_kernel<R.value, true>), grid, dim3(64), 0, s, a, (double2 *)rec, rho, acc_max);
+            BHG_LAUNCH((record_prefix_kernel<R.value, true>), grid, dim3(64), 0, s, a, (double2 *)rec, rho, acc_max, att_max);
         else
-            BHG_LAUNCH((record_prefix_kernel<R.value, false>), grid, dim3(64), 0, s, a, (double2 *)rec, rho, 0u);
+            BHG_LAUNCH((record_prefix_kernel<R.value, false>), grid, dim3(64), 0, s, a, (double2 *)rec, rho, 0u, 0u);
     });
 }
 #endif

@@ -9,7 +9,8 @@
 //   clearance = distance from the start point to the nearest event surface of a call's scene,
 //   rho       = PREFIX_RHO_FRACTION * min(clearance, |x0|), fixed when the records are written
 //               (deep records, BHG_PREFIX_RECORD_DEEP: PREFIX_RHO_FRACTION_DEEP of it while the scene holds no object sphere;
-//               wide records, BHG_PREFIX_RECORD_WIDE: PREFIX_RHO_FRACTION_WIDE of it there),
+//               wide records, BHG_PREFIX_RECORD_WIDE: PREFIX_RHO_FRACTION_WIDE of it there;
+//               rim records, BHG_PREFIX_RECORD_RIM: PREFIX_RHO_FRACTION_RIM of it there),
 //   a call replays only while its own clearance > rho (1 + PREFIX_MARGIN): the one validity test, whichever rule wrote them.
 #pragma once
 #include <cmath>
@@ -43,6 +44,23 @@ constexpr double PREFIX_RHO_FRACTION_DEEP = 0.75;
 // call runs the plain start -- and an owner gets it back by recording again after refusals (PrefixOwner below).  31/32 adds 0.3
 // attempts for a ball that ends 0.9 above the photon sphere: not taken.
 constexpr double PREFIX_RHO_FRACTION_WIDE = 0.9375;
+// 1 - 2^-10, the rim records' fraction where the wide rule takes its fifteen sixteenths: from the headline camera the ball (28.97)
+// ends 0.028 above the horizon.  What kept the wide ball away from the hole was never validity: the one surface the ball nears
+// there is the horizon, which cannot move under kept records (r_s and the spin are on the list of bhg_start_steps_match), the
+// recorder stops in front of the attempt that would end a ray, and the only other role of the fraction is the rounding margin
+// of prefix_replay_ok (2^-10 is 977 PREFIX_MARGINs).  The same rule on 3 000 uniform rays of the headline window
+// (scripts/dev/prefix_rule_restate.py; 12.35 attempts per ray), attempts kept per ray and the share of rays at a cap:
+//   rho                    <= 8 accepted, <= 12 attempts   <= 8, <= 16       <= 9, <= 14       <= 9, <= 15       <= 10, <= 16
+//   27.1875  (15/16)           7.85, 1.1 %                  7.85, 0           7.85, 0           7.85, 0           7.85, 0
+//   28.09375 (31/32)           8.16, 4.7 %                  8.17, 0.2 %       8.17, 0.2 %       8.17, 0.0 %       8.17, 0
+//   28.54688 (63/64)           8.21, 5.8 %                  8.23, 1.0 %       8.24, 0.9 %       8.24, 0.1 %       8.24, 0
+//   28.77344 (127/128)         8.28, 6.9 %                  8.30, 2.2 %       8.32, 1.1 %       8.32, 0.2 %       8.32, 0.0 %
+//   28.97168 (1 - 2^-10)       8.32, 7.5 %                  8.35, 3.3 %       8.38, 1.6 %       8.38, 0.4 %       8.39, 0.2 %
+// so the rim rule keeps up to PREFIX_RIM_ACCEPTED = 9 accepted steps in PREFIX_RIM_ATTEMPTS = 15 attempts, the smallest caps that
+// leave fewer than 1 % of the rays at a cap, and half an attempt per ray more than the wide rule (300 rays of another seed: 8.04 ->
+// 8.45).
+constexpr double PREFIX_RHO_FRACTION_RIM = 1.0 - 1.0 / 1024.0;
+constexpr int PREFIX_RIM_ACCEPTED = 9, PREFIX_RIM_ATTEMPTS = 15;
 // The recorded step ends satisfy |x - x0|^2 <= rho^2 in rounded arithmetic, and the event tests compare rounded radii: a surface
 // counts as clear of the ball only with this relative margin (many orders above the rounding, far below any scene's scale).
 // A surface tangent to the ball is NOT clear.
@@ -109,6 +127,26 @@ inline double prefix_rho_wide_call(double clearance, double r_hor, const double 
     return PREFIX_RHO_FRACTION_WIDE * std::fmin(clearance, r0);
 }
 
+// ... of a RIM recording call: PREFIX_RHO_FRACTION_RIM exactly where the wide call takes its fifteen sixteenths, and what the wide
+// call returns everywhere else
+inline double prefix_rho_rim_call(double clearance, double r_hor, const double x0[3], int n_spheres)
+{
+    const double wide = prefix_rho_wide_call(clearance, r_hor, x0, n_spheres);
+    if (!(wide > prefix_rho_deep_call(clearance, r_hor, x0, n_spheres))) return wide;
+    const double r0 = std::sqrt(x0[0] * x0[0] + x0[1] * x0[1] + x0[2] * x0[2]);
+    return PREFIX_RHO_FRACTION_RIM * std::fmin(clearance, r0);
+}
+
+// Were records of this rho written by the rim rule?  A replaying call is handed a rho and no rule, but from this origin and with
+// this horizon -- both the same as when the records were written, or they may not be replayed at all -- no other rule gives a rho
+// above the wide rule's for the horizon alone.  What it decides is the step budget a replay needs (PREFIX_RIM_ATTEMPTS).
+inline bool prefix_rho_is_rim(double rho, double r_hor, const double x0[3])
+{
+    const double r0 = std::sqrt(x0[0] * x0[0] + x0[1] * x0[1] + x0[2] * x0[2]);
+    if (!std::isfinite(rho) || !std::isfinite(r0) || !(r_hor >= 0.0) || !(r0 > r_hor)) return false;
+    return rho > prefix_rho_wide_call(r0 - r_hor, r_hor, x0, 0);
+}
+
 // may a call whose scene has this clearance replay records written with rho?
 inline bool prefix_replay_ok(double clearance, double rho)
 {
@@ -132,14 +170,27 @@ inline bool prefix_replay_ok(double clearance, double rho)
 // recording pass), and an edit that then reaches into the wide ball but not into the deep one costs 2.5 ms more (two refused
 // frames, a recording call): 4.1 / 0.16 = 25 frames.  Waiting that long before buying is within a factor two of the best choice
 // whenever the edit comes; 32 leaves room for frames whose replays save less than the headline's.
+// The rules form a ladder, deep -> wide -> rim, and an owner that names the RIM rule as its promotion climbs it a rung at a time:
+// a clean run earns the wide rule first (unchanged), and a further clean run on wide records, PREFIX_OWNER_PROMOTE_RIM_CALLS
+// long, the rim rule.  The same arithmetic with (n)'s measured figures: a replay of rim records saves
+// 0.052 ms on one of wide records, a third of what the wide rung saved; the promoting call costs 1.7 ms more than the replay
+// it replaces (the recording pass is 0.07 ms longer) and an edit that then reaches into the rim ball but not into the wide one
+// the same 2.5 ms: 4.2 / 0.052 = 80 frames, and 96 leaves the same room.  The rim rule is earned by a ray set's 131st trace.
 // The modes are the C API's (include/bhgeo.h; bhgeo_capi.hip asserts the values).
-constexpr int PREFIX_MODE_NONE = 0, PREFIX_MODE_RECORD = 1, PREFIX_MODE_REPLAY = 2, PREFIX_MODE_RECORD_DEEP = 4, PREFIX_MODE_RECORD_WIDE = 5;
-constexpr int PREFIX_OWNER_SHRINK_CALLS = 2, PREFIX_OWNER_GROW_CALLS = 8, PREFIX_OWNER_PROMOTE_CALLS = 32;
+constexpr int PREFIX_MODE_NONE = 0, PREFIX_MODE_RECORD = 1, PREFIX_MODE_REPLAY = 2, PREFIX_MODE_RECORD_DEEP = 4, PREFIX_MODE_RECORD_WIDE = 5,
+              PREFIX_MODE_RECORD_RIM = 6;
+constexpr int PREFIX_OWNER_SHRINK_CALLS = 2, PREFIX_OWNER_GROW_CALLS = 8, PREFIX_OWNER_PROMOTE_CALLS = 32, PREFIX_OWNER_PROMOTE_RIM_CALLS = 96;
 constexpr double PREFIX_OWNER_GROW_FACTOR = 2.0;
+
+inline bool prefix_mode_records(int mode)
+{
+    return mode == PREFIX_MODE_RECORD || mode == PREFIX_MODE_RECORD_DEEP || mode == PREFIX_MODE_RECORD_WIDE || mode == PREFIX_MODE_RECORD_RIM;
+}
 
 // the rho a recording call by this rule fixes (the step budget apart: see deep_fits in bhgeo_capi.hip)
 inline double prefix_rho_by_rule(int rule, double clearance, double r_hor, const double x0[3], int n_spheres)
 {
+    if (rule == PREFIX_MODE_RECORD_RIM) return prefix_rho_rim_call(clearance, r_hor, x0, n_spheres);
     if (rule == PREFIX_MODE_RECORD_WIDE) return prefix_rho_wide_call(clearance, r_hor, x0, n_spheres);
     if (rule == PREFIX_MODE_RECORD_DEEP) return prefix_rho_deep_call(clearance, r_hor, x0, n_spheres);
     return rule == PREFIX_MODE_RECORD ? prefix_rho(clearance, x0) : 0.0;
@@ -158,7 +209,7 @@ struct PrefixOwner {
     int next(int rule, double clearance, double r_hor, const double x0[3], int n_spheres, int last_mode, int last_used, double last_rho,
              int promote = PREFIX_MODE_NONE)
     {
-        if (last_mode == PREFIX_MODE_RECORD || last_mode == PREFIX_MODE_RECORD_DEEP || last_mode == PREFIX_MODE_RECORD_WIDE) {
+        if (prefix_mode_records(last_mode)) {
             // (a recording call that wrote nothing -- a step budget the records could exhaust -- left the held ones as they were)
             if (last_used == last_mode) rho = std::isfinite(last_rho) && last_rho > 0.0 ? last_rho : 0.0;
             refused_run = roomy_run = clean_run = 0;
@@ -177,11 +228,29 @@ struct PrefixOwner {
         // (a scene without any clear ball has nothing to record: the held records wait for it to pass)
         const bool shrink = refused_run >= PREFIX_OWNER_SHRINK_CALLS && rule_rho > 0.0;
         if (grow || shrink) return rule;
-        if (promote != PREFIX_MODE_NONE && clean_run >= PREFIX_OWNER_PROMOTE_CALLS &&
-            prefix_replay_ok(prefix_rho_by_rule(promote, clearance, r_hor, x0, n_spheres), rho))
-            return promote;      // (more than the kept rho by the margin of the replay test: never for the same ball again)
+        // (more than the kept rho by the margin of the replay test: never for the same ball again)
+        const auto earned = [&](int by, int calls) {
+            return clean_run >= calls && prefix_replay_ok(prefix_rho_by_rule(by, clearance, r_hor, x0, n_spheres), rho);
+        };
+        if (promote == PREFIX_MODE_RECORD_RIM) {
+            // the ladder: the wide rung first, exactly as an owner that names the wide rule climbs it, the rim rung from there
+            if (earned(PREFIX_MODE_RECORD_WIDE, PREFIX_OWNER_PROMOTE_CALLS)) return PREFIX_MODE_RECORD_WIDE;
+            if (earned(PREFIX_MODE_RECORD_RIM, PREFIX_OWNER_PROMOTE_RIM_CALLS)) return PREFIX_MODE_RECORD_RIM;
+        } else if (promote != PREFIX_MODE_NONE && earned(promote, PREFIX_OWNER_PROMOTE_CALLS)) {
+            return promote;
+        }
         return PREFIX_MODE_REPLAY;
     }
 };
+
+// What an owner asks for under the call's step budget (max_steps as the call resolves it, 0 never): a replay of rim records
+// needs a budget above PREFIX_RIM_ATTEMPTS -- the C layer answers one at or below it with an error, since it can tell such
+// records by their rho -- so the owner asks for nothing in that call and keeps its records for the calls after it.
+inline int prefix_owner_fit_budget(int ask, double rho, double r_hor, const double x0[3], unsigned long long max_steps)
+{
+    if (ask == PREFIX_MODE_REPLAY && max_steps <= (unsigned long long)PREFIX_RIM_ATTEMPTS && prefix_rho_is_rim(rho, r_hor, x0))
+        return PREFIX_MODE_NONE;
+    return ask;
+}
 
 }  // namespace bhg

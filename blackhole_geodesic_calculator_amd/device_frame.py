@@ -58,11 +58,14 @@ class StartSteps:
     Where the library has the wide rule (BHG_PREFIX_RECORD_WIDE: fifteen sixteenths of that ball) an owner is promoted to it:
     after 32 traces in a row that all replayed, the next one writes the records again by the wide rule.  BHGEO_WIDE_PREFIX=1
     records by the wide rule from the first trace, BHGEO_WIDE_PREFIX=0 never.
+    Where the library has the rim rule (BHG_PREFIX_RECORD_RIM: the ball that ends just above the horizon) the ladder has one more
+    rung: 96 further traces in a row that replayed the wide records earn it.  BHGEO_RIM_PREFIX=1 records by the rim rule from the
+    first trace, BHGEO_RIM_PREFIX=0 ends the ladder at the wide rule.
     A scene that stays inside the ball (two refused traces in a row) or has left a small ball far behind (eight traces with room
     for twice the radius) has the records written again too, by the owner's first rule.  Every such trace replays its steps;
     the library decides (bhg_prefix_owner_next), and prefix_recorded counts them all."""
 
-    _RECORD_MODES = (_ffi.PREFIX_RECORD, _ffi.PREFIX_RECORD_DEEP, _ffi.PREFIX_RECORD_WIDE)
+    _RECORD_MODES = (_ffi.PREFIX_RECORD, _ffi.PREFIX_RECORD_DEEP, _ffi.PREFIX_RECORD_WIDE, _ffi.PREFIX_RECORD_RIM)
 
     def __init__(self, enabled=True):
         self.enabled = bool(enabled)
@@ -100,11 +103,15 @@ class StartSteps:
         if os.environ.get("BHGEO_DEEP_PREFIX", "") == "0" or not _ffi.has_deep_prefix():
             return _ffi.PREFIX_RECORD, _ffi.PREFIX_NONE
         wide = os.environ.get("BHGEO_WIDE_PREFIX", "")
+        rim = os.environ.get("BHGEO_RIM_PREFIX", "") if _ffi.has_rim_prefix() else "0"
+        if rim == "1":
+            return _ffi.PREFIX_RECORD_RIM, _ffi.PREFIX_NONE
         if wide == "0" or not _ffi.has_wide_prefix():
             return _ffi.PREFIX_RECORD_DEEP, _ffi.PREFIX_NONE
+        top = _ffi.PREFIX_RECORD_RIM if rim != "0" else None     # (the ladder's last rung; None: it ends at the wide rule)
         if wide == "1":
-            return _ffi.PREFIX_RECORD_WIDE, _ffi.PREFIX_NONE
-        return _ffi.PREFIX_RECORD_DEEP, _ffi.PREFIX_RECORD_WIDE
+            return _ffi.PREFIX_RECORD_WIDE, top or _ffi.PREFIX_NONE
+        return _ffi.PREFIX_RECORD_DEEP, top or _ffi.PREFIX_RECORD_WIDE
 
     def plan(self, n, dev, key, params, shared_origin=False, origin=None, spheres=None):
         """(d_start_steps, start_mode) of the next trace call, and self.prefix for it (origin, spheres: the call's, which decide

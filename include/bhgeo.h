@@ -84,7 +84,8 @@ extern "C" {
                                   bhg_mesh_build_info, bhg_mesh_bvh_morton_host, bhg_mesh_tree_host: a Morton-order tree built
                                   on the device, rebuilt in place when the triangle list changes);
                                   BHG_PREFIX_RECORD_WIDE under BHG_START_PREFIX (bhg_prefix_wide_accepted, bhg_prefix_owner_next,
-                                  bhg_frame_prefix_info, struct bhg_prefix_owner: wider start-up records, recorded again after refusals).
+                                  bhg_frame_prefix_info, struct bhg_prefix_owner: wider start-up records, recorded again after refusals);
+                                  BHG_PREFIX_RECORD_RIM (bhg_prefix_rim_attempts: start-up records to the rim of the clear ball).
                                9: redshift -- bhg_redshift_device / _host, bhg_shade_scene_redshift_device, bhg_frame_set_redshift,
                                   bhg_redshift_size, struct bhg_redshift;
                                   nothing of ABI 8 changed.
@@ -378,8 +379,16 @@ int bhg_start_steps_match(const bhg_params *a, const bhg_params *b);
  *                      exit sphere, disk or object sphere inside it makes REPLAY refuse, which costs speed and nothing else; an
  *                      owner gets the speed back by recording again (bhg_prefix_owner_next).  A recording call of any rule may
  *                      go with BHG_START_REPLAY: the start steps are not recorded again.
+ *   BHG_PREFIX_RECORD_RIM: RECORD_WIDE in the ball that ends just above the horizon: rho =
+ *                      (1 - 2^-10) min(clearance, |x0|) exactly where RECORD_WIDE takes its 15/16, with up to
+ *                      BHG_PREFIX_RIM_ACCEPTED accepted steps in BHG_PREFIX_RIM_ATTEMPTS attempts, and RECORD_WIDE's records byte
+ *                      for byte everywhere else.  Same buffer, same bytes, same REPLAY.  Where it takes the larger ball it needs
+ *                      max_steps > BHG_PREFIX_RIM_ATTEMPTS, else nothing is written (used = BHG_PREFIX_NONE, rho = 0) -- and so
+ *                      does every call that replays such records: they are known by their rho, which no other rule gives from
+ *                      the same origin and horizon, and a REPLAY of them with BHG_PREFIX_DEEP_ATTEMPTS < max_steps <=
+ *                      BHG_PREFIX_RIM_ATTEMPTS is BHG_E_INVALID.
  *   BHG_PREFIX_NONE:   bhg_trace_start_device.
- * used says what the call did: BHG_PREFIX_RECORD, _DEEP or _WIDE (records written by that rule), BHG_PREFIX_REPLAY
+ * used says what the call did: BHG_PREFIX_RECORD, _DEEP, _WIDE or _RIM (records written by that rule), BHG_PREFIX_REPLAY
  * (records used) or BHG_PREFIX_NONE (refused, or out of scope).  A REPLAY call cannot tell which rule wrote the records it is
  * handed, so it uses none under a step budget that a deep record could exhaust: max_steps <= BHG_PREFIX_DEEP_ATTEMPTS is
  * answered with BHG_PREFIX_NONE, the plain call's results as always.  (Mode 3 is no mode and stays BHG_E_INVALID.)  In scope: x0_shared calls (d_x0 NULL) of BHG_METHOD_DP54 with BHG_RHS_CHRISTOFFEL or
@@ -392,10 +401,13 @@ int bhg_start_steps_match(const bhg_params *a, const bhg_params *b);
 #define BHG_PREFIX_REPLAY 2
 #define BHG_PREFIX_RECORD_DEEP 4 /* (3 stays no mode: callers were promised BHG_E_INVALID for it) */
 #define BHG_PREFIX_RECORD_WIDE 5
+#define BHG_PREFIX_RECORD_RIM 6
 #define BHG_PREFIX_K_MAX 4
 #define BHG_PREFIX_DEEP_ACCEPTED 6  /* accepted steps a deep record holds at most */
 #define BHG_PREFIX_DEEP_ATTEMPTS 12 /* attempts a deep or wide record holds at most, rejected ones included */
 #define BHG_PREFIX_WIDE_ACCEPTED 8  /* accepted steps a wide record holds at most */
+#define BHG_PREFIX_RIM_ACCEPTED 9   /* accepted steps a rim record holds at most */
+#define BHG_PREFIX_RIM_ATTEMPTS 15  /* attempts a rim record holds at most, rejected ones included */
 #define BHG_PREFIX_BYTES_PER_RAY 112
 typedef struct bhg_prefix {
     void *d_records;  /* device, BHG_PREFIX_BYTES_PER_RAY * n bytes */
@@ -417,10 +429,13 @@ int32_t bhg_prefix_deep_attempts(void);
 /* BHG_PREFIX_WIDE_ACCEPTED as the library was built with it: a library that exports this symbol takes BHG_PREFIX_RECORD_WIDE
  * and has bhg_prefix_owner_next. */
 int32_t bhg_prefix_wide_accepted(void);
+/* BHG_PREFIX_RIM_ATTEMPTS as the library was built with it: a library that exports this symbol takes BHG_PREFIX_RECORD_RIM, as a
+ * mode and as the promote argument of bhg_prefix_owner_next. */
+int32_t bhg_prefix_rim_attempts(void);
 /* When the owner of a ray set's records records them AGAIN because the scene has changed (the rays' own invalidation -- other
  * rays, another origin, parameters bhg_start_steps_match() rejects -- stays the owner's: start from a zeroed bhg_prefix_owner
  * and a recording call).  Before every later call the owner hands in the call's scene, the rule it records by (BHG_PREFIX_RECORD,
- * _DEEP or _WIDE) and the bhg_prefix of its LAST call as that call left it (NULL: there was none), and is told what to ask for:
+ * _DEEP, _WIDE or _RIM) and the bhg_prefix of its LAST call as that call left it (NULL: there was none), and is told what to ask for:
  *   BHG_PREFIX_REPLAY with o->rho, or
  *   rule: record now, in a call that may replay its start steps -- after two refused calls in a row (one refused frame, an object
  *         passing through, changes nothing), or after eight calls in a row whose scene the rule gives at least twice o->rho
@@ -428,8 +443,12 @@ int32_t bhg_prefix_wide_accepted(void);
  *   promote (BHG_PREFIX_RECORD_DEEP or _WIDE, or BHG_PREFIX_NONE for no such rule): record now by this wider rule -- after 32
  *         calls in a row that all replayed, when it gives this call's scene more than o->rho.  The owners of the library and
  *         the binding record by RECORD_DEEP and are promoted to RECORD_WIDE; BHGEO_WIDE_PREFIX=1 in the environment makes
- *         them record by RECORD_WIDE from the first call, BHGEO_WIDE_PREFIX=0 never.  Or
- *   BHG_PREFIX_NONE: no records are held (also for a NULL argument).
+ *         them record by RECORD_WIDE from the first call, BHGEO_WIDE_PREFIX=0 never.  promote = BHG_PREFIX_RECORD_RIM names the
+ *         whole ladder: RECORD_WIDE is earned first, exactly as above, and RECORD_RIM by 96 further calls in a row that replayed
+ *         the wide records.  That is what the two owners ask for now; BHGEO_RIM_PREFIX=0 ends their ladder at RECORD_WIDE,
+ *         BHGEO_RIM_PREFIX=1 makes them record by RECORD_RIM from the first call.  Or
+ *   BHG_PREFIX_NONE: no records are held (also for a NULL argument) -- or rim records are, and p->max_steps is too small to
+ *         replay them (<= BHG_PREFIX_RIM_ATTEMPTS): the records stay, this call goes without.
  * HOST only; the same code decides for bhg_frame_render. */
 typedef struct bhg_prefix_owner {
     double rho;          /* the held records' radius, 0: none */
