@@ -191,6 +191,8 @@ class DeviceFrame:
         self.d_dir = None
         self._dir_traced = False
         self._traced = None      # what the last trace wrote: None (nothing usable), "dir" or "end"
+        self.polarisation = None      # _ffi.Polarisation (set_polarisation) or None: off
+        self._pol_args = None         # (degree, disk_sense) of set_polarisation: the image's up follows the rotation
         self.W, self.H, self.S = int(width), int(height), int(samples)
         self.fov_x, self.fov_y = float(fov_x), float(fov_y)
         self.origin = np.asarray(origin, dtype=np.float64) - np.asarray(bh_loc, dtype=np.float64)  # :278
@@ -233,7 +235,6 @@ class DeviceFrame:
         self._params = None      # the parameters of the last trace (the redshift shade needs its metric)
         self.observer = None     # _ffi.Observer (set_observer) or None: the reference camera
         self._ray_key = None     # what the observer rays in d_k0 were made for: (origin, r_s, spin, rhs_form)
-        self.polarisation = None      # _ffi.Polarisation (set_polarisation) or None: off
         self.d_qu = None              # [P, 6] fp64 Stokes Q / U images (shade_stokes)
         self.disk_thermal = None      # _ffi.DiskThermal (set_disk_thermal) or None: the disk's colour of the scene
         self.object_textures = None   # set_object_textures: (device textures per sphere, rotations, modes, emission) or None
@@ -256,6 +257,64 @@ class DeviceFrame:
 
     def _stream(self):
         return torch.cuda.current_stream(self.dev).cuda_stream
+
+    # The camera is assigned to (an animation moves it from frame to frame): what was kept for the old one goes with it.  A new
+    # origin leaves the rays (directions only) but not what the last trace wrote -- shade() would weigh the old records with a g
+    # worked out from the new position; a new rotation or field of view also asks render() for new rays, and turns the up of
+    # set_polarisation() with the camera.  Assigning the value that is held keeps everything (set_objects compares likewise: an
+    # owner may write its whole camera every frame).  origin and rot are the frame's own copies, read-only: a camera changed in
+    # place would slip past all this.
+    @property
+    def origin(self):
+        return self._origin
+
+    @origin.setter
+    def origin(self, x):
+        x = np.array(x, dtype=np.float64).reshape(3)
+        x.setflags(write=False)
+        if getattr(self, "_origin", None) is not None and x.tobytes() == self._origin.tobytes():
+            return
+        self._origin = x
+        self._traced = None
+
+    def _directions_changed(self):
+        self._traced = None
+        self._rays_ready = False
+
+    @property
+    def rot(self):
+        return self._rot
+
+    @rot.setter
+    def rot(self, r):
+        r = np.array(r, dtype=np.float64).reshape(3, 3)
+        r.setflags(write=False)
+        if getattr(self, "_rot", None) is not None and r.tobytes() == self._rot.tobytes():
+            return
+        self._rot = r
+        self._directions_changed()
+        if self._pol_args is not None:
+            self.set_polarisation(*self._pol_args)
+
+    @property
+    def fov_x(self):
+        return self._fov_x
+
+    @fov_x.setter
+    def fov_x(self, v):
+        if float(v) != getattr(self, "_fov_x", None):
+            self._fov_x = float(v)
+            self._directions_changed()
+
+    @property
+    def fov_y(self):
+        return self._fov_y
+
+    @fov_y.setter
+    def fov_y(self, v):
+        if float(v) != getattr(self, "_fov_y", None):
+            self._fov_y = float(v)
+            self._directions_changed()
 
     @property
     def d_k0(self):
@@ -314,17 +373,19 @@ class DeviceFrame:
         ones), and with redshift on, g is that observer's.  None: the reference camera.  The rays are made anew at the next
         render(), and whenever the origin or the metric of the trace parameters changes."""
         self.observer = _ffi.make_observer(velocity)
+        self._traced = None      # the last trace followed the other camera's rays: shade() would give them this observer's g
         self._rays_ready = False
         self._ray_key = None
         self.start_steps.invalidate()
 
     def set_polarisation(self, degree=None, disk_sense=1):
         """Disk polarisation for shade_stokes() (bhg_shade_scene_polarised_device): degree is a constant or
-        a table against the emission cosine (make_polarisation), image up the camera's rotated +y.  None: off.  shade() and
-        shade_f32() are the same either way."""
+        a table against the emission cosine (make_polarisation), image up the camera's rotated +y (a rotation assigned later turns
+        it).  None: off.  shade() and shade_f32() are the same either way."""
         if degree is None:
-            self.polarisation = None
+            self.polarisation = self._pol_args = None
             return
+        self._pol_args = (degree, disk_sense)
         self.polarisation = _ffi.make_polarisation(degree, disk_sense, self.rot @ np.array([0.0, 1.0, 0.0]))
 
     def set_disk_thermal(self, t_peak=None, nu=None, weights=None, f_col=1.0, scale=1.0, disk_sense=1):
@@ -802,7 +863,7 @@ class FrameBatch:
             f = DeviceFrame(ctx, W, H, S, pixels=pixels, jitter=jitter, device=dev, start_cache=start_cache,
                             buffers=(self.d_k0[sl], self.d_end[sl], self.d_flags[sl], self.d_steps[sl], self.d_acc[sl]),
                             **cam, **frame_kw)
-            self.d_x0[sl] = torch.as_tensor(f.origin, device=dev)
+            self.d_x0[sl] = torch.as_tensor(np.array(f.origin), device=dev)
             self.frames.append(f)
         self.n = m * n1
         self.dev = dev

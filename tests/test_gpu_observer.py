@@ -290,6 +290,26 @@ def _scene_frame(ctx, kerr, beta):
     return fr, p, sky, ref, rgba.cpu().numpy()
 
 
+def test_set_observer_after_a_trace_drops_what_the_trace_wrote(ctx):
+    """set_observer() asked for new rays but left the last trace standing: shade() before the next trace gave the old camera's
+    rays and records the new observer's g -- an image of neither frame (found by the re-shade walk of
+    tests/test_gpu_frame_sequences.py).  Now shade() asks for a trace, as it does after set_disk() and set_objects()."""
+    r = np.linalg.norm(CAM3)
+    beta = np.array([0.0, np.sqrt(0.5 / (r - 1.0)), 0.0])
+    other = (0.2, 0.0, -0.1)
+    fr, p, _, _, rgba = _scene_frame(ctx, False, beta)
+    assert np.array_equal(fr.shade().cpu().numpy(), rgba)
+    fr.set_observer(other)
+    with pytest.raises(RuntimeError):
+        fr.shade()
+    want = _scene_frame(ctx, False, other)[4]
+    assert not np.array_equal(want, rgba)
+    assert np.array_equal(fr.render(p).cpu().numpy(), want)
+    fr.set_observer(None)
+    with pytest.raises(RuntimeError):
+        fr.shade()
+
+
 @pytest.mark.parametrize("kerr", [False, True])
 def test_orbiting_camera_image_against_reference(ctx, kerr):
     """An observer on an inclined circular orbit through CAM3 (Schwarzschild: |beta| = sqrt(M / (r - 2M)) perpendicular to r^;

@@ -207,6 +207,61 @@ def test_device_frame_replays_until_something_it_depends_on_changes(ctx, sky):
         _same(_results(fr), _fresh(ctx, sky, q, origin=origin), f"replay after {kw} at {origin}")
 
 
+def test_device_frame_camera_assigned_after_a_trace_drops_what_the_trace_wrote(ctx, sky):
+    """origin, rot, fov_x and fov_y are assigned to from frame to frame.  They used to be plain attributes: shade() after a new
+    origin weighed the records of the old trace with a g worked out from the new position (set_disk and set_objects guard the same
+    case), and render() after a new rotation or field of view kept the old rays unless it was told to make them anew (found by
+    tests/test_gpu_frame_sequences.py).  Now shade() asks for a trace, and render() gives the fresh frame's image."""
+    from blackhole_geodesic_calculator_amd.device_frame import DeviceFrame
+    from blackhole_geodesic_calculator_amd.raygen import euler_xyz_matrix
+    p = _params(lambda_end=200.0, r_exit=40.0)
+
+    def fresh(origin=CAM, euler=(0.0, 0.0, 0.0), fov=(0.6, 0.6)):
+        f = DeviceFrame(ctx, W, H, S, fov_x=fov[0], fov_y=fov[1], sampling_seed=42.0, origin=origin, rotation_euler=euler, start_cache=False)
+        f.set_sky(sky)
+        f.set_redshift(("sky",), 4.0)
+        return f.render(p).cpu().numpy()
+
+    fr = _frame(ctx, sky)
+    fr.set_redshift(("sky",), 4.0)          # (the sky's g depends on where the camera is)
+    assert np.array_equal(fr.render(p).cpu().numpy(), fresh())
+    fr.shade()
+    moved = CAM + [0.5, -1.0, 2.0]
+    fr.origin = moved
+    with pytest.raises(RuntimeError):
+        fr.shade()
+    want = fresh(origin=moved)
+    assert not np.array_equal(want, fresh())
+    assert np.array_equal(fr.render(p).cpu().numpy(), want)
+    assert fr.start_steps.recorded == 2     # (the steps belong to the origin; the rays were kept)
+    euler = (0.05, -0.04, 0.1)
+    for kw, assign in ((dict(euler=euler), lambda: setattr(fr, "rot", euler_xyz_matrix(euler))),
+                       (dict(euler=euler, fov=(0.6, 0.5)), lambda: setattr(fr, "fov_y", 0.5)),
+                       (dict(euler=euler, fov=(0.7, 0.5)), lambda: setattr(fr, "fov_x", 0.7))):
+        recorded = fr.start_steps.recorded
+        assign()
+        with pytest.raises(RuntimeError):
+            fr.shade()
+        want = fresh(origin=moved, **kw)
+        assert np.array_equal(fr.render(p).cpu().numpy(), want), kw       # (no regenerate_rays=True: the frame knows)
+        assert fr.start_steps.recorded == recorded + 1
+        assert np.array_equal(fr.render(p).cpu().numpy(), want) and fr.start_steps.recorded == recorded + 1
+    # the held values assigned again (an owner that writes its whole camera every frame) keep the rays, the steps and the trace
+    recorded = fr.start_steps.recorded
+    fr.origin, fr.rot, fr.fov_x, fr.fov_y = np.array(moved), euler_xyz_matrix(euler), 0.7, 0.5
+    assert np.array_equal(fr.shade().cpu().numpy(), want)
+    assert np.array_equal(fr.render(p).cpu().numpy(), want) and fr.start_steps.recorded == recorded
+    # the frame holds its own copies, which cannot be written in place behind its back
+    mine = np.array(moved)
+    fr.origin = mine
+    mine[2] += 1.0
+    assert np.array_equal(fr.origin, moved)
+    with pytest.raises(ValueError):
+        fr.origin[2] = 0.0
+    with pytest.raises(ValueError):
+        fr.rot[0, 0] = 0.0
+
+
 def test_device_frame_new_rays_invalidate(ctx, sky):
     import torch
     from blackhole_geodesic_calculator_amd.raygen import python_random_stream
