@@ -74,6 +74,7 @@ EXPORTS = (
     "bhg_mesh_instances_create", "bhg_mesh_instances_set", "bhg_mesh_instances_destroy", "bhg_mesh_instances_info",
     "bhg_mesh_instance_box_host", "bhg_trace_mesh_instances_device", "bhg_trace_mesh_instances",
     "bhg_shade_mesh_instances_device", "bhg_frame_set_mesh_instances",
+    "bhg_mesh_instances_create_tree", "bhg_mesh_instances_tree_info", "bhg_mesh_instance_tree_host", "bhg_frame_set_mesh_instance_tree",
     "bhg_mesh_refit", "bhg_mesh_refit_device", "bhg_mesh_refit_info", "bhg_mesh_bvh_refit_host", "bhg_mesh_refit_schedule_host",
     "bhg_mesh_boxes_host", "bhg_mesh_range", "bhg_frame_refit_mesh", "bhg_frame_mesh_refit_info",
     "bhg_mesh_create_device", "bhg_mesh_rebuild_device", "bhg_mesh_rebuild", "bhg_mesh_build_info", "bhg_mesh_bvh_morton_host",
@@ -84,7 +85,10 @@ MESH_DEVICE_LEAF_MAX = 64  # the largest leaf_size the device build takes (BHG_M
 # area_now / area_build = 1.13 the refitted tree traced as fast as a fresh one, at 1.55 it lost more than the rebuild costs)
 MESH_REBUILD_RATIO = 1.5
 MESH_INSTANCES_MAX = 64    # BHG_MESH_INSTANCES_MAX: rigid placements an instance set holds at most (BHG_MESH_INSTANCES)
-MESH_MAX_SUBSTEPS = 1024   # BHG_MESH_MAX_SUBSTEPS: sub-chords per accepted step at most (BHG_MESH)
+MESH_INSTANCE_TREE_MAX = 65536   # BHG_MESH_INSTANCE_TREE_MAX: placements a set under a tree holds at most (BHG_MESH_INSTANCE_TREE)
+MESH_INSTANCE_TREE_LEAF = 4      # the leaf_size of such a tree when none is given (DESIGN.md section 24 has the table it is read off:
+                                 # leaves of 4 trace fastest or level on every line, and make the smallest tree)
+MESH_MAX_SUBSTEPS = 1024  # BHG_MESH_MAX_SUBSTEPS: sub-chords per accepted step at most (BHG_MESH)
 MESH_TEXTURES_MAX = 8      # BHG_MESH_TEXTURES_MAX: images a mesh material holds at most (BHG_MESH_MATERIAL)
 MAX_CROSSINGS = 4   # BHG_MAX_CROSSINGS: disk crossings a crossings trace stores per ray (BHG_DISK_CROSSINGS)
 START_NONE, START_RECORD, START_REPLAY = 0, 1, 2   # BHG_START_*: the rays' initial steps kept across calls (BHG_START_STEPS)
@@ -778,6 +782,15 @@ def load():
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bhg_frame_set_mesh_instances.restype = C.c_int
     L.bhg_frame_set_mesh_instances.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.bhg_mesh_instances_create_tree.restype = C.c_int
+    L.bhg_mesh_instances_create_tree.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
+    L.bhg_mesh_instances_tree_info.restype = C.c_int
+    L.bhg_mesh_instances_tree_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.bhg_mesh_instance_tree_host.restype = C.c_int
+    L.bhg_mesh_instance_tree_host.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.bhg_frame_set_mesh_instance_tree.restype = C.c_int
+    L.bhg_frame_set_mesh_instance_tree.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
     L.bhg_mesh_refit.restype = C.c_int
     L.bhg_mesh_refit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bhg_mesh_refit_device.restype = C.c_int
@@ -1143,13 +1156,20 @@ def mesh_instance_box_host(local_box, transform):
 class MeshInstances:
     """bhg_mesh_instances: K rigid placements of one Mesh.  transforms [K, 12] (R row-major, then t) or
     [K, 3, 4] (R | t), x_world = R x_local + t.  set(transforms) moves them: K x 18 doubles go to the device, no tree is touched.
-    Closes with its mesh."""
+    Closes with its mesh.
+    tree=True (bhg_mesh_instances_create_tree): the placements lie under a tree of boxes with leaves of
+    leaf_size, up to MESH_INSTANCE_TREE_MAX of them; every call takes such a set, the results are the linear set's bit for bit,
+    and set() builds the tree's order and boxes anew on the host and sends records and tree in one upload."""
 
-    def __init__(self, mesh: "Mesh", transforms):
+    def __init__(self, mesh: "Mesh", transforms, tree=False, leaf_size=MESH_INSTANCE_TREE_LEAF):
         T = _instance_transforms(transforms)
         h = C.c_void_p()
-        _check(load().bhg_mesh_instances_create(mesh.ctx._h, mesh._h, T.shape[0], _addr(T), C.byref(h)))
+        if tree:
+            _check(load().bhg_mesh_instances_create_tree(mesh.ctx._h, mesh._h, T.shape[0], _addr(T), int(leaf_size), C.byref(h)))
+        else:
+            _check(load().bhg_mesh_instances_create(mesh.ctx._h, mesh._h, T.shape[0], _addr(T), C.byref(h)))
         self._h = h
+        self.tree = bool(tree)
         self.mesh = mesh
         self.n = T.shape[0]
         self.transforms = T.copy()      # (the latest: a refit of the mesh wants them set again)
@@ -1180,6 +1200,29 @@ class MeshInstances:
         n, box = C.c_int32(0), (C.c_double * 6)()
         _check(load().bhg_mesh_instances_info(self._h, C.byref(n), box))
         return n.value, np.array(box[:])
+
+    def tree_info(self):
+        """(n_nodes, depth, leaf_size) of the tree the set lies under; all zeros for a linear set"""
+        nn, depth, leaf = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        _check(load().bhg_mesh_instances_tree_info(self._h, C.byref(nn), C.byref(depth), C.byref(leaf)))
+        return nn.value, depth.value, leaf.value
+
+
+def mesh_instance_tree_host(local_box, transforms, leaf_size=MESH_INSTANCE_TREE_LEAF):
+    """bhg_mesh_instance_tree_host: the tree a set of tree=True builds over the placements `transforms` of a mesh whose root box
+    is local_box (lo, hi) -> (node_box[nn, 6], node_skip[nn], node_first[nn], node_count[nn], inst_order[K], depth); no GPU."""
+    lb = np.ascontiguousarray(local_box, dtype=np.float64).reshape(6)
+    T = _instance_transforms(transforms)
+    K = T.shape[0]
+    cap = max(2 * K - 1, 1)
+    box = np.empty((cap, 6), np.float64)
+    skip, first, count = (np.empty(cap, np.int32) for _ in range(3))
+    order = np.empty(max(K, 1), np.int32)
+    nn, depth = C.c_int32(0), C.c_int32(0)
+    _check(load().bhg_mesh_instance_tree_host(_addr(lb), K, _addr(T), int(leaf_size), _addr(box), _addr(skip), _addr(first),
+                                              _addr(count), _addr(order), C.byref(nn), C.byref(depth)))
+    n = nn.value
+    return box[:n].copy(), skip[:n].copy(), first[:n].copy(), count[:n].copy(), order[:K].copy(), depth.value
 
 
 def start_steps_match(a: "Params", b: "Params") -> bool:
@@ -1607,11 +1650,13 @@ class Frame:
         _check(load().bhg_frame_prefix_info(self._h, int(shard), C.byref(pf)))
         return pf.mode, pf.used, pf.rho
 
-    def set_mesh_instances(self, transforms=None, inst_rgb=None):
+    def set_mesh_instances(self, transforms=None, inst_rgb=None, tree=False, leaf_size=MESH_INSTANCE_TREE_LEAF):
         """Rigid placements of the frame's mesh in every later render (bhg_frame_set_mesh_instances):
         transforms [K, 12] (R row-major, then t) or [K, 3, 4] (R | t), inst_rgb [K, 3] float32 or None.  Calling it again with
         other transforms moves the instances: the records go to the devices, nothing of the mesh is rebuilt or uploaded.
-        None (or no transforms): off -- the plain mesh render, bit for bit.  set_mesh() turns instances off as well."""
+        None (or no transforms): off -- the plain mesh render, bit for bit.  set_mesh() turns instances off as well.
+        tree=True (bhg_frame_set_mesh_instance_tree): the devices' sets lie under trees of boxes with
+        leaves of leaf_size, and K may go up to MESH_INSTANCE_TREE_MAX."""
         if transforms is None or len(transforms) == 0:
             _check(load().bhg_frame_set_mesh_instances(self._h, 0, None, None))
             return
@@ -1621,6 +1666,10 @@ class Frame:
             rgb = np.ascontiguousarray(inst_rgb, dtype=np.float32)
             if rgb.shape != (T.shape[0], 3):
                 raise ValueError("inst_rgb must have shape [K, 3]")
+        if tree:
+            _check(load().bhg_frame_set_mesh_instance_tree(self._h, T.shape[0], _addr(T), None if rgb is None else _addr(rgb),
+                                                           int(leaf_size)))
+            return
         _check(load().bhg_frame_set_mesh_instances(self._h, T.shape[0], _addr(T), None if rgb is None else _addr(rgb)))
 
     def render(self, params: "Params", out=None, to_host=True):

@@ -56,6 +56,9 @@ Known deviations from the reference, all deliberate:
     frame gets the datablock once, in its own coordinates with the scale baked in, and one instance per object (translation minus
     the hole's location).  A later render whose baked arrays and images are the ones held only moves the instances
     (bhg_frame_set_mesh_instances: nothing is rebuilt or uploaded).  Any other scene takes the concatenated path above, silently.
+  * scene.curved_space_mesh_instance_tree (default 0): together with curved_space_mesh_instances, the
+    instances lie under a tree of boxes (bhg_frame_set_mesh_instance_tree) and the rule above holds for up to 65536 objects:
+    more than 64 linked duplicates no longer take the concatenated path.  Off, everything is as without the property.
   * scene.curved_space_mesh_refit (default 0): with curved_space_meshes = 1 on the device path, a render whose
     mesh differs from the one the frame holds in vertex positions only -- the triangle indices, UVs, images and emission the same
     bits, the vertex count the same -- sends the vertices alone and every device refits its tree on the device
@@ -247,7 +250,8 @@ class RelativisticRenderEngine(bpy.types.RenderEngine):
         the module docstring has the rule), else None.  A record is the rigid part of matrix_world nearest to it
         (_ffi.rigid_transform: Blender's matrices are float32) with the hole's location taken off the translation."""
         from . import _ffi
-        if not objects or len(objects) > _ffi.MESH_INSTANCES_MAX:
+        tree = float(getattr(depsgraph.scene, "curved_space_mesh_instance_tree", 0) or 0) != 0.0
+        if not objects or len(objects) > (_ffi.MESH_INSTANCE_TREE_MAX if tree else _ffi.MESH_INSTANCES_MAX):
             return None
         data = [getattr(ob, "data", None) for ob in objects]
         if len(objects) > 1 and (data[0] is None or any(d is not data[0] for d in data)):
@@ -367,6 +371,7 @@ class RelativisticRenderEngine(bpy.types.RenderEngine):
                 "tri_uv": np.ascontiguousarray(np.concatenate(UV)) if any_uv else None, "tri_tex": np.concatenate(TEX),
                 "images": images if any_uv else [], "emission": emission, "offsets": offsets,
                 "instances": None if plan is None else plan[1],
+                "instance_tree": float(getattr(depsgraph.scene, "curved_space_mesh_instance_tree", 0) or 0) != 0.0,
                 "refit": float(getattr(depsgraph.scene, "curved_space_mesh_refit", 0) or 0) != 0.0,
                 "build": float(getattr(depsgraph.scene, "curved_space_mesh_build", 0) or 0) != 0.0,
                 # (instanced: the datablock's arrays before the scale, and the scale -- what _set_device_mesh compares)
@@ -427,13 +432,19 @@ class RelativisticRenderEngine(bpy.types.RenderEngine):
             fr.mesh_held = {**{k: mesh[k] for k in ("vertices", "triangles", "normals", "tri_uv", "tri_tex", "emission")}, "ids": ids,
                             "instances": None, "local": local}      # (set_mesh turns instances off)
         # the placements: moved objects of a held mesh upload their records and nothing else
+        # (scene.curved_space_mesh_instance_tree: under a tree of boxes; the other kind of set is a new set)
         inst, held_inst = mesh.get("instances"), fr.mesh_held.get("instances")
+        tree = bool(mesh.get("instance_tree")) and inst is not None
         if inst is None:
             if held_inst is not None:
                 fr.set_mesh_instances(None)
-        elif held_inst is None or not np.array_equal(inst, held_inst):
-            fr.set_mesh_instances(inst)
+        elif held_inst is None or tree != bool(fr.mesh_held.get("instance_tree")) or not np.array_equal(inst, held_inst):
+            if tree:
+                fr.set_mesh_instances(inst, tree=True)
+            else:
+                fr.set_mesh_instances(inst)
         fr.mesh_held["instances"] = inst
+        fr.mesh_held["instance_tree"] = tree
 
     @staticmethod
     def _custom(ob, key):
@@ -742,6 +753,7 @@ class CUSTOM_RENDER_PT_blackhole(RenderButtonsPanel, Panel):
              ("mark_y_max", "mark_y_max"), ("curved_space_objects", "Objects in curved space (0/1)"),
              ("curved_space_meshes", "Mesh objects as triangles (0/1)"),
              ("curved_space_mesh_instances", "Linked duplicates as instances (0/1)"),
+             ("curved_space_mesh_instance_tree", "Instances under a tree of boxes (0/1)"),
              ("curved_space_mesh_refit", "Deforming meshes refit, not rebuilt (0/1)"),
              ("curved_space_mesh_build", "Mesh trees built on the GPU (0/1)"),
              ("device_shading", "Shade on the GPU (0/1)"), ("render_devices", "GPUs to render on"))
@@ -774,6 +786,7 @@ EXTRA_PROPS = [
     ("curved_space_objects", bpy.props.FloatProperty(name="curved_space_objects", default=0)),
     ("curved_space_meshes", bpy.props.FloatProperty(name="curved_space_meshes", default=0)),
     ("curved_space_mesh_instances", bpy.props.FloatProperty(name="curved_space_mesh_instances", default=0)),
+    ("curved_space_mesh_instance_tree", bpy.props.FloatProperty(name="curved_space_mesh_instance_tree", default=0)),
     ("curved_space_mesh_refit", bpy.props.FloatProperty(name="curved_space_mesh_refit", default=0)),
     ("curved_space_mesh_build", bpy.props.FloatProperty(name="curved_space_mesh_build", default=0)),
     ("device_shading", bpy.props.FloatProperty(name="device_shading", default=0)),

@@ -1262,14 +1262,25 @@ int trace_device_one(bhg_context *c, const bhg_params *p, const TraceCall &tc)
                 std::memcpy(g.box, in->box, sizeof(g.box));
                 g.d_min = in->d_min;
                 g.d_max = in->d_max;
-                bhg::MeshInstanceArgs ia;
-                std::memset(&ia, 0, sizeof(ia));
-                ia.rec = in->d_rec;
-                ia.n = in->n;
-                ia.inst_id = tc.inst_id;
-                ia.cull = g.cull;       // (BHGEO_MESH_CULL=0 takes the instances' world boxes out as well)
                 HIP_TRY(bhg::instances_before_read(in, s));
-                HIP_TRY(bhg::launch_trace_mesh_instances(a, g, ia, rhs_id, s));
+                if (in->leaf_size && bhg::instance_tree_on()) {
+                    // a set under a tree: the records and the tree over them
+                    bhg::MeshInstanceTreeArgs ta;
+                    std::memset(&ta, 0, sizeof(ta));
+                    ta.tree = in->tree;
+                    ta.inst_id = tc.inst_id;
+                    ta.cull = g.cull;
+                    HIP_TRY(bhg::launch_trace_mesh_instance_tree(a, g, ta, rhs_id, s));
+                } else {
+                    // (a set under a tree with BHGEO_INSTANCE_TREE=0 as well: the linear loop has no limit of its own)
+                    bhg::MeshInstanceArgs ia;
+                    std::memset(&ia, 0, sizeof(ia));
+                    ia.rec = in->d_rec;
+                    ia.n = in->n;
+                    ia.inst_id = tc.inst_id;
+                    ia.cull = g.cull;       // (BHGEO_MESH_CULL=0 takes the instances' world boxes out as well)
+                    HIP_TRY(bhg::launch_trace_mesh_instances(a, g, ia, rhs_id, s));
+                }
                 HIP_TRY(bhg::instances_after_read(in, s));
             } else {
                 HIP_TRY(bhg::launch_trace_mesh(a, g, rhs_id, s));
@@ -2360,8 +2371,12 @@ int shade_mesh(bhg_context *c, const MeshShadeCall &call)
     if (m.instances) {
         const hipStream_t st = (hipStream_t)s.stream;
         HIP_TRY(bhg::instances_before_read(m.instances, st));
-        HIP_TRY(bhg::launch_shade_mesh_instances(a, m.mesh->view, m.tri_id, m.bary, ma, m.instances->d_rec, m.instances->n, bhg::mesh_culls_on(),
-                                                 m.inst_id, m.inst_rgb, st));
+        if (m.instances->leaf_size && bhg::instance_tree_on())
+            HIP_TRY(bhg::launch_shade_mesh_instance_tree(a, m.mesh->view, m.tri_id, m.bary, ma, m.instances->tree, bhg::mesh_culls_on(),
+                                                         m.inst_id, m.inst_rgb, st));
+        else
+            HIP_TRY(bhg::launch_shade_mesh_instances(a, m.mesh->view, m.tri_id, m.bary, ma, m.instances->d_rec, m.instances->n,
+                                                     bhg::mesh_culls_on(), m.inst_id, m.inst_rgb, st));
         HIP_TRY(bhg::instances_after_read(m.instances, st));
         return BHG_OK;
     }

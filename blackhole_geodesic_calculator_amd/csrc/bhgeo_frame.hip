@@ -153,6 +153,7 @@ struct Shard {
     // the mesh's instances (bhg_frame_set_mesh_instances): this device's set over mesh, the colours, the trace's third record
     bhg_mesh_instances *inst = nullptr;
     int32_t inst_n = 0;
+    int32_t inst_leaf = 0;          // the leaf_size of the tree inst lies under (0: a linear set)
     DevBuf inst_rgb, inst_id;
     bool inst_ready = false;        // inst holds the frame's current transforms, inst_rgb its colours
     hipEvent_t done = nullptr;
@@ -214,6 +215,7 @@ struct bhg_frame {
     Mesh mesh;
     // bhg_frame_set_mesh_instances: host copies (empty: the mesh where its vertices put it)
     std::vector<double> inst;       // [n][12]
+    int32_t inst_leaf = 0;          // bhg_frame_set_mesh_instance_tree: the leaf_size of the sets' trees (0: linear sets)
     std::vector<float> inst_rgb;    // [n][3], or empty
     // root (device of shard 0)
     DevBuf recv, perm, image;       // [n_dev * pmax][4] float, [H W] int64, [H W][4] float
@@ -352,6 +354,7 @@ void release_shard_instances(Shard &s)
     if (s.inst) bhg_mesh_instances_destroy(s.inst);
     s.inst = nullptr;
     s.inst_n = 0;
+    s.inst_leaf = 0;
     s.inst_rgb.release();
     s.inst_id.release();
     s.inst_ready = false;
@@ -454,17 +457,21 @@ int refit_shard_mesh(bhg_frame *f, Shard &s)
 }
 
 // the frame's instances on this shard's device, over the shard's mesh: a set of the same size is moved (the records go up,
-// nothing else), another size makes a new set
+// nothing else), another size or kind makes a new set
 int upload_shard_instances(bhg_frame *f, Shard &s)
 {
     const int32_t n = (int32_t)(f->inst.size() / 12);
     HIP_TRY(hipSetDevice(s.device));
-    if (s.inst && s.inst_n == n) {
+    if (s.inst && s.inst_n == n && s.inst_leaf == f->inst_leaf) {
         BHG_TRY(bhg_mesh_instances_set(s.inst, f->inst.data()));
     } else {
         release_shard_instances(s);
-        BHG_TRY(bhg_mesh_instances_create(s.ctx, s.mesh, n, f->inst.data(), &s.inst));
+        if (f->inst_leaf)
+            BHG_TRY(bhg_mesh_instances_create_tree(s.ctx, s.mesh, n, f->inst.data(), f->inst_leaf, &s.inst));
+        else
+            BHG_TRY(bhg_mesh_instances_create(s.ctx, s.mesh, n, f->inst.data(), &s.inst));
         s.inst_n = n;
+        s.inst_leaf = f->inst_leaf;
     }
     HIP_TRY(hipSetDevice(s.device));
     if (f->inst_rgb.empty()) {
@@ -965,7 +972,8 @@ try {
     return host_exception();
 }
 
-int bhg_frame_set_mesh_instances(bhg_frame *f, int32_t n, const double *transforms, const float *inst_rgb)
+// bhg_frame_set_mesh_instances (leaf_size 0: linear sets) and bhg_frame_set_mesh_instance_tree
+static int frame_set_instances(bhg_frame *f, int32_t n, const double *transforms, const float *inst_rgb, int32_t leaf_size)
 try {
     if (!f) return fail(BHG_E_INVALID, "frame is NULL");
     if (!f->meshed) return fail(BHG_E_INVALID, "mesh instances: the frame holds no mesh (bhg_frame_set_mesh first)");
@@ -977,7 +985,10 @@ try {
         for (auto &s : f->sh) release_shard_instances(s);
         return BHG_OK;
     }
-    BHG_TRY(bhg::mesh_instance_transforms_check(n, transforms));
+    if (leaf_size)
+        BHG_TRY(bhg::mesh_instance_tree_check(n, transforms, leaf_size));
+    else
+        BHG_TRY(bhg::mesh_instance_transforms_check(n, transforms));
     if (inst_rgb)
         for (int32_t i = 0; i < n * 3; i++)
             if (!std::isfinite(inst_rgb[i])) return fail(BHG_E_INVALID, "mesh instances: every entry of inst_rgb must be finite");
@@ -986,10 +997,23 @@ try {
     if (inst_rgb) rgb.assign(inst_rgb, inst_rgb + (size_t)n * 3);
     f->inst = std::move(T);
     f->inst_rgb = std::move(rgb);
+    f->inst_leaf = leaf_size;
     for (auto &s : f->sh) s.inst_ready = false;
     return BHG_OK;
 } catch (...) {
     return host_exception();
+}
+
+int bhg_frame_set_mesh_instances(bhg_frame *f, int32_t n, const double *transforms, const float *inst_rgb)
+{
+    return frame_set_instances(f, n, transforms, inst_rgb, 0);
+}
+
+int bhg_frame_set_mesh_instance_tree(bhg_frame *f, int32_t n, const double *transforms, const float *inst_rgb, int32_t leaf_size)
+{
+    // (n = 0 turns instances off whatever the leaf_size; otherwise a leaf_size outside [1, 8] is refused with the transforms)
+    if (n != 0 && leaf_size == 0) leaf_size = -1;
+    return frame_set_instances(f, n, transforms, inst_rgb, leaf_size);
 }
 
 int bhg_frame_render(bhg_frame *f, const bhg_params *p, float *rgba_host)

@@ -32,6 +32,8 @@ int mesh_material_check(const bhg_mesh_material *m, size_t nt, bool host_arrays)
 // --- bhgeo_mesh.hip ---
 // the transforms of mesh instances: n rigid ones, or the reason they are refused
 int mesh_instance_transforms_check(int32_t n, const double *T);
+// ... of a set under a tree: n within BHG_MESH_INSTANCE_TREE_MAX, leaf_size within [1, 8], then as above
+int mesh_instance_tree_check(int32_t n, const double *T, int32_t leaf_size);
 // a mesh built on the device; host_arrays: from host arrays, which are uploaded first
 int mesh_create_built_on_device(bhg_context *c, const double *vertices, size_t n_vertices, const int32_t *triangles, size_t n_triangles,
                                 const double *vertex_normals, int32_t leaf_size, size_t cap_vertices, size_t cap_triangles,

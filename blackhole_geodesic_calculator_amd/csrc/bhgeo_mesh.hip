@@ -1,5 +1,5 @@
 // bhgeo_mesh.hip -- the life cycle of the library-side mesh and instance set (bhg_mesh_*, bhg_mesh_instances_* in include/bhgeo.h;
-// DESIGN.md sections 19, 21-23): create on the host or on the device, refit, rebuild in place, destroy, and what they report.  The
+// DESIGN.md sections 19, 21-24): create on the host or on the device, refit, rebuild in place, destroy, and what they report.  The
 // calls that trace or shade with a mesh are bhgeo_capi.hip's; mesh_object.h is what the two units share.
 #include <algorithm>
 #include <cmath>
@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "bhgeo_internal.h"
+#include "instance_tree.h"
 #include "mesh_build.h"
 #include "mesh_bvh.h"
 #include "mesh_layout.h"
@@ -573,9 +574,9 @@ int mesh_create_built_on_device(bhg_context *c, const double *d_vertices, size_t
     return BHG_OK;
 }
 
-int mesh_instance_transforms_check(int32_t n, const double *T)
+// n > 0 transforms: all there, finite, rigid and no reflections
+static int rigid_check(int32_t n, const double *T)
 {
-    if (n < 1 || n > BHG_MESH_INSTANCES_MAX) return fail(BHG_E_INVALID, "mesh instances: n must be in [1, BHG_MESH_INSTANCES_MAX]");
     if (!T) return fail(BHG_E_INVALID, "mesh instances: transforms is NULL");
     for (int32_t j = 0; j < n; j++) {
         const double *R = T + (size_t)j * 12;
@@ -591,6 +592,27 @@ int mesh_instance_transforms_check(int32_t n, const double *T)
         if (!(det > 0.0)) return fail(BHG_E_INVALID, "mesh instances: transforms must be rotations, det R > 0");
     }
     return BHG_OK;
+}
+
+int mesh_instance_transforms_check(int32_t n, const double *T)
+{
+    if (n < 1 || n > BHG_MESH_INSTANCES_MAX) return fail(BHG_E_INVALID, "mesh instances: n must be in [1, BHG_MESH_INSTANCES_MAX]");
+    return rigid_check(n, T);
+}
+
+int mesh_instance_tree_check(int32_t n, const double *T, int32_t leaf_size)
+{
+    if (n < 1 || n > BHG_MESH_INSTANCE_TREE_MAX)
+        return fail(BHG_E_INVALID, "mesh instances: n must be in [1, BHG_MESH_INSTANCE_TREE_MAX] for a set under a tree");
+    if (leaf_size < 1 || leaf_size > INSTANCE_TREE_LEAF_MAX)
+        return fail(BHG_E_INVALID, "mesh instances: the tree's leaf_size must be in [1, 8]");
+    return rigid_check(n, T);
+}
+
+bool instance_tree_on()
+{
+    const char *tree = std::getenv("BHGEO_INSTANCE_TREE");
+    return !(tree && tree[0] == '0' && tree[1] == 0);
 }
 
 }  // namespace bhg
@@ -862,11 +884,22 @@ int bhg_mesh_instance_box_host(const double local_box[6], const double transform
     return BHG_OK;
 }
 
-int bhg_mesh_instances_create(bhg_context *c, const bhg_mesh *mesh, int32_t n, const double *transforms, bhg_mesh_instances **out)
+// the records of a set, and of a set under a tree the order and the boxes, into the host copy h; the topology stands in h already
+static void instances_fill(const bhg_mesh_instances *in, const double *transforms, double *h, double box[6], double &d_min, double &d_max)
 {
-    if (!out) return fail(BHG_E_INVALID, "out is NULL");
-    *out = nullptr;
-    BHG_TRY(bhg::mesh_instance_transforms_check(n, transforms));
+    instance_records(in->mesh, in->n, transforms, h, box, d_min, d_max);
+    if (!in->leaf_size) return;
+    const bhg::InstanceTreeLayout g = bhg::instance_tree_layout((size_t)in->n, bhg::BHG_MESH_INSTANCE_DOUBLES_, (size_t)in->n_nodes);
+    char *b = (char *)h;
+    bhg::instance_tree_fit(h + 12, bhg::BHG_MESH_INSTANCE_DOUBLES_, (size_t)in->n, (const int32_t *)(b + g.node_skip),
+                           (const int32_t *)(b + g.node_first), (const int32_t *)(b + g.node_count), (size_t)in->n_nodes,
+                           (int32_t *)(b + g.inst_order), (double *)(b + g.node_box));
+}
+
+// leaf_size 0: a linear set (bhg_mesh_instances_create); the transforms have been checked
+static int instances_create(bhg_context *c, const bhg_mesh *mesh, int32_t n, const double *transforms, int32_t leaf_size,
+                            bhg_mesh_instances **out)
+{
     if (!mesh) return fail(BHG_E_INVALID, "mesh is NULL");
     BHG_TRY(bhg::mesh_on_device_of(c, mesh));
     ENTER_DEVICE(bhg::context_device(c));
@@ -878,36 +911,114 @@ int bhg_mesh_instances_create(bhg_context *c, const bhg_mesh *mesh, int32_t n, c
     in->mesh_serial = mesh->serial;
     in->mesh_generation = mesh->generation;
     in->n = n;
-    const size_t bytes = (size_t)n * bhg::BHG_MESH_INSTANCE_DOUBLES_ * sizeof(double);
+    size_t bytes = (size_t)n * bhg::BHG_MESH_INSTANCE_DOUBLES_ * sizeof(double);
+    // the tree's topology: a function of (n, leaf_size), worked out here once
+    std::vector<int32_t> skip, first, count;
+    bhg::InstanceTreeLayout g{};
+    if (leaf_size) {
+        bhg::morton_topology((size_t)n, leaf_size, skip, first, count, in->depth);
+        in->leaf_size = leaf_size;
+        in->n_nodes = (int32_t)skip.size();
+        g = bhg::instance_tree_layout((size_t)n, bhg::BHG_MESH_INSTANCE_DOUBLES_, skip.size());
+        bytes = g.total;
+    }
+    in->bytes = bytes;
     hipError_t e = hipMalloc((void **)&in->d_rec, bytes);
     for (int k = 0; k < 2 && e == hipSuccess; k++) {
         e = hipHostMalloc((void **)&in->h_rec[k], bytes, hipHostMallocDefault);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&in->ev_copy[k], hipEventDisableTiming);
+        if (e == hipSuccess && leaf_size) {
+            char *b = (char *)in->h_rec[k];
+            std::memset(b, 0, bytes);     // (the padding between the regions travels too)
+            std::memcpy(b + g.node_skip, skip.data(), skip.size() * sizeof(int32_t));
+            std::memcpy(b + g.node_first, first.data(), first.size() * sizeof(int32_t));
+            std::memcpy(b + g.node_count, count.data(), count.size() * sizeof(int32_t));
+        }
     }
     if (e == hipSuccess) e = hipEventCreateWithFlags(&in->ev_read, hipEventDisableTiming);
     if (e == hipSuccess) {
-        instance_records(mesh, n, transforms, in->h_rec[0], in->box, in->d_min, in->d_max);
+        instances_fill(in, transforms, in->h_rec[0], in->box, in->d_min, in->d_max);
         e = hipMemcpy(in->d_rec, in->h_rec[0], bytes, hipMemcpyHostToDevice);     // (done when the call returns)
     }
     if (e != hipSuccess) {
         bhg_mesh_instances_destroy(in);
         return fail_hip(e, "bhg_mesh_instances_create: device records");
     }
+    if (leaf_size) {
+        const char *d = (const char *)in->d_rec;
+        in->tree = {in->d_rec, (const double *)(d + g.node_box), (const int32_t *)(d + g.node_skip), (const int32_t *)(d + g.node_first),
+                    (const int32_t *)(d + g.node_count), (const int32_t *)(d + g.inst_order), in->n_nodes, n};
+    }
     *out = in;
+    return BHG_OK;
+}
+
+int bhg_mesh_instances_create(bhg_context *c, const bhg_mesh *mesh, int32_t n, const double *transforms, bhg_mesh_instances **out)
+{
+    if (!out) return fail(BHG_E_INVALID, "out is NULL");
+    *out = nullptr;
+    BHG_TRY(bhg::mesh_instance_transforms_check(n, transforms));
+    return instances_create(c, mesh, n, transforms, 0, out);
+}
+
+int bhg_mesh_instances_create_tree(bhg_context *c, const bhg_mesh *mesh, int32_t n, const double *transforms, int32_t leaf_size,
+                                   bhg_mesh_instances **out)
+{
+    if (!out) return fail(BHG_E_INVALID, "out is NULL");
+    *out = nullptr;
+    BHG_TRY(bhg::mesh_instance_tree_check(n, transforms, leaf_size));
+    return instances_create(c, mesh, n, transforms, leaf_size, out);
+}
+
+int bhg_mesh_instances_tree_info(const bhg_mesh_instances *in, int32_t *n_nodes, int32_t *depth, int32_t *leaf_size)
+{
+    if (!in) return fail(BHG_E_INVALID, "mesh instances: inst is NULL");
+    if (n_nodes) *n_nodes = in->n_nodes;
+    if (depth) *depth = in->depth;
+    if (leaf_size) *leaf_size = in->leaf_size;
+    return BHG_OK;
+}
+
+int bhg_mesh_instance_tree_host(const double local_box[6], int32_t n, const double *transforms, int32_t leaf_size, double *node_box,
+                                int32_t *node_skip, int32_t *node_first, int32_t *node_count, int32_t *inst_order, int32_t *n_nodes,
+                                int32_t *depth)
+{
+    if (!local_box) return fail(BHG_E_INVALID, "mesh instances: local_box is NULL");
+    for (int q = 0; q < 6; q++)
+        if (!std::isfinite(local_box[q])) return fail(BHG_E_INVALID, "mesh instances: local_box must be finite");
+    BHG_TRY(bhg::mesh_instance_tree_check(n, transforms, leaf_size));
+    if (!n_nodes) return fail(BHG_E_INVALID, "n_nodes is NULL");
+    if (!node_box || !node_skip || !node_first || !node_count || !inst_order) return fail(BHG_E_INVALID, "an output array is NULL");
+    std::vector<int32_t> skip, first, count;
+    int32_t deep = 0;
+    bhg::morton_topology((size_t)n, leaf_size, skip, first, count, deep);
+    const size_t nn = skip.size();
+    std::memcpy(node_skip, skip.data(), nn * sizeof(int32_t));
+    std::memcpy(node_first, first.data(), nn * sizeof(int32_t));
+    std::memcpy(node_count, count.data(), nn * sizeof(int32_t));
+    std::vector<double> wbox((size_t)n * 6);
+    for (int32_t j = 0; j < n; j++) instance_world_box(local_box, transforms + (size_t)j * 12, &wbox[(size_t)j * 6]);
+    bhg::instance_tree_fit(wbox.data(), 6, (size_t)n, node_skip, node_first, node_count, nn, inst_order, node_box);
+    *n_nodes = (int32_t)nn;
+    if (depth) *depth = deep;
     return BHG_OK;
 }
 
 int bhg_mesh_instances_set(bhg_mesh_instances *in, const double *transforms)
 {
     if (!in) return fail(BHG_E_INVALID, "mesh instances: inst is NULL");
-    BHG_TRY(bhg::mesh_instance_transforms_check(in->n, transforms));
+    if (in->leaf_size)
+        BHG_TRY(bhg::mesh_instance_tree_check(in->n, transforms, in->leaf_size));
+    else
+        BHG_TRY(bhg::mesh_instance_transforms_check(in->n, transforms));
     BHG_TRY(bhg::instances_usable(in->ctx, in, false));
     ENTER_DEVICE(bhg::context_device(in->ctx));
     const int k = in->last < 0 ? 1 : in->last ^ 1;
-    const size_t bytes = (size_t)in->n * bhg::BHG_MESH_INSTANCE_DOUBLES_ * sizeof(double);
+    const size_t bytes = in->bytes;
     HIP_TRY(hipEventSynchronize(in->ev_copy[k]));     // (the copy that read this host buffer last, two _set calls ago: done)
     double box[6], d_min, d_max;
-    instance_records(in->mesh, in->n, transforms, in->h_rec[k], box, d_min, d_max);
+    // (a set under a tree: its order and its boxes are built anew beside the records, and all of it goes up in the one copy)
+    instances_fill(in, transforms, in->h_rec[k], box, d_min, d_max);
     // behind every kernel that reads the records now, whatever its stream; the readers to come wait for ev_copy[k]
     hipStream_t s = bhg::context_stream(in->ctx);
     if (in->was_read && in->read_stream != s) HIP_TRY(hipStreamWaitEvent(s, in->ev_read, 0));

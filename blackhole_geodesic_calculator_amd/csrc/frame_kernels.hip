@@ -1405,8 +1405,35 @@ struct MeshInstanceShade {
     const float *inst_rgb;     // [n][3], or nullptr
 };
 
+// ... and the same over a set that lies under a tree: rec and n as above (the hit's own record is read by
+// inst_id, the records stay in the caller's order), the shadow segments walk the tree
+struct MeshInstanceTreeShade {
+    const double *rec;
+    int32_t n;
+    int32_t boxes;             // 0: the shadow segments look at no box, of the tree's or of an instance
+    const int32_t *inst_id;
+    const float *inst_rgb;
+    InstanceTreeView tree;
+};
+
+// does the segment meet any triangle of any instance?
+__device__ __forceinline__ bool instances_shadow(const MeshView &mesh, const MeshInstanceShade &I, const double from[3], const double to[3])
+{
+    double s_hit;
+    int32_t by;
+    return segment_first_hit_instances<true>(mesh, I.rec, I.n, I.boxes != 0, from, to, s_hit, by) >= 0;
+}
+
+__device__ __forceinline__ bool instances_shadow(const MeshView &mesh, const MeshInstanceTreeShade &I, const double from[3], const double to[3])
+{
+    double s_hit;
+    int32_t by;
+    return segment_first_hit_instance_tree<true>(mesh, I.tree, I.boxes != 0, from, to, s_hit, by) >= 0;
+}
+
+template <class Inst>
 __device__ __forceinline__ void mesh_instance_ray_colour(const ShadeArgs &A, const MeshShade &G, const MeshMaterialArgs &M,
-                                                         const MeshInstanceShade &I, uint64_t i, double rgb[3])
+                                                         const Inst &I, uint64_t i, double rgb[3])
 {
     const uint8_t fl = A.flags[i];
     const int32_t tri = G.tri_id[i], inst = I.inst_id[i];
@@ -1442,9 +1469,7 @@ __device__ __forceinline__ void mesh_instance_ray_colour(const ShadeArgs &A, con
         if (!(ndl > 0.0)) continue;
         const double from[3] = {e[0] + 1e-5 * ld[0], e[1] + 1e-5 * ld[1], e[2] + 1e-5 * ld[2]};
         const double to[3] = {A.lamps[l][0], A.lamps[l][1], A.lamps[l][2]};
-        double s_hit;
-        int32_t by;
-        if (segment_first_hit_instances<true>(G.mesh, I.rec, I.n, I.boxes != 0, from, to, s_hit, by) >= 0) continue;
+        if (instances_shadow(G.mesh, I, from, to)) continue;
         sum += A.lamps[l][3] * A.lamps[l][3] * ndl / d2;
     }
     // (1.0 * sum, as mesh_colour leaves it in a white mesh's channels)
@@ -1480,6 +1505,15 @@ struct MeshInstanceColour {
     }
 };
 
+struct MeshInstanceTreeColour {
+    static constexpr bool STOKES = false;
+    static __device__ __forceinline__ void ray(const ShadeArgs &A, uint64_t i, double rgb[3], double *, const MeshShade &G,
+                                               const MeshMaterialArgs &M, const MeshInstanceTreeShade &I)
+    {
+        mesh_instance_ray_colour(A, G, M, I, i, rgb);
+    }
+};
+
 hipError_t launch_shade_mesh(const ShadeArgs &a, const MeshView &m, const int32_t *tri_id, const double *bary, const float *tri_rgb,
                              hipStream_t s)
 {
@@ -1502,6 +1536,16 @@ hipError_t launch_shade_mesh_instances(const ShadeArgs &a, const MeshView &m, co
 {
     if (a.n_pixels == 0) return hipSuccess;
     launch_shade_pixels<MeshInstanceColour>(a, s, MeshShade{m, tri_id, bary, nullptr}, M, MeshInstanceShade{rec, n_inst, boxes ? 1 : 0, inst_id, inst_rgb});
+    return hipGetLastError();
+}
+
+hipError_t launch_shade_mesh_instance_tree(const ShadeArgs &a, const MeshView &m, const int32_t *tri_id, const double *bary,
+                                           const MeshMaterialArgs &M, const InstanceTreeView &tree, bool boxes,
+                                           const int32_t *inst_id, const float *inst_rgb, hipStream_t s)
+{
+    if (a.n_pixels == 0) return hipSuccess;
+    launch_shade_pixels<MeshInstanceTreeColour>(a, s, MeshShade{m, tri_id, bary, nullptr}, M,
+                                                MeshInstanceTreeShade{tree.rec, tree.n, boxes ? 1 : 0, inst_id, inst_rgb, tree});
     return hipGetLastError();
 }
 

@@ -354,6 +354,16 @@ struct MeshInstanceArgs {
 };
 hipError_t launch_trace_mesh_instances(const TraceArgs &a, const MeshArgs &m, const MeshInstanceArgs &in, int rhs, hipStream_t s);
 hipError_t launch_trace_mesh_instances_kerr(const TraceArgs &a, const MeshArgs &m, const MeshInstanceArgs &in, hipStream_t s);
+// ... over the placements of a set that lies under a tree (trace_mesh_instance_tree_kernel): m as above, the
+// records and the tree over them in an argument struct of their own
+constexpr int BHG_MESH_INSTANCE_TREE_MAX_ = 65536;
+struct MeshInstanceTreeArgs {
+    InstanceTreeView tree;  // mesh_traverse.h; unchanged during the launch
+    int32_t cull;           // 0: no box is looked at, of the tree's or of an instance (BHGEO_MESH_CULL=0, as MeshArgs::cull)
+    int32_t *inst_id;       // [a.n]: the placement of a ray that ends on the mesh, else -1
+};
+hipError_t launch_trace_mesh_instance_tree(const TraceArgs &a, const MeshArgs &m, const MeshInstanceTreeArgs &in, int rhs, hipStream_t s);
+hipError_t launch_trace_mesh_instance_tree_kerr(const TraceArgs &a, const MeshArgs &m, const MeshInstanceTreeArgs &in, hipStream_t s);
 // the mesh shade (MeshColour under shade_pixels_kernel, frame_kernels.hip): a.end / flags / sky / disk / lamps as launch_shade's plain instance wants
 // them, n_spheres = 0; tri_rgb nullptr = white
 hipError_t launch_shade_mesh(const ShadeArgs &a, const MeshView &m, const int32_t *tri_id, const double *bary, const float *tri_rgb,
@@ -375,6 +385,10 @@ hipError_t launch_shade_mesh_material(const ShadeArgs &a, const MeshView &m, con
 hipError_t launch_shade_mesh_instances(const ShadeArgs &a, const MeshView &m, const int32_t *tri_id, const double *bary,
                                        const MeshMaterialArgs &mat, const double *rec, int32_t n_inst, bool boxes,
                                        const int32_t *inst_id, const float *inst_rgb, hipStream_t s);
+// ... over a set under a tree (MeshInstanceTreeColour): the shadow segments walk the tree in any-hit form
+hipError_t launch_shade_mesh_instance_tree(const ShadeArgs &a, const MeshView &m, const int32_t *tri_id, const double *bary,
+                                           const MeshMaterialArgs &mat, const InstanceTreeView &tree, bool boxes,
+                                           const int32_t *inst_id, const float *inst_rgb, hipStream_t s);
 // the recording pass of the start-up records (record_prefix_kernel: one lane per ray; rhs Christoffel or reduced, a.x0 == nullptr):
 // rec [7][a.n] 16-byte planes, rho the radius about a.x0s the recorded steps stay inside.  deep: the record carries on through
 // rejected attempts (deep: at most acc_max accepted steps -- BHG_PREFIX_DEEP_ACCEPTED_, or BHG_PREFIX_WIDE_ACCEPTED_ for

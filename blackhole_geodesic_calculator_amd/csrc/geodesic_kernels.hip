@@ -3572,6 +3572,20 @@ struct MeshPlacements {
     __device__ __forceinline__ void keep(uint64_t i, int32_t inst) const { I.inst_id[i] = inst; }
 };
 
+// The placements of a set under a tree: the walk is per lane, by skip links (mesh_traverse.h).
+struct MeshPlacementTree {
+    const MeshInstanceTreeArgs &I;
+    __device__ __forceinline__ int32_t first_hit(const MeshView &M, const double pa[3], const double pb[3], double &s_hit, int32_t &inst) const
+    {
+        return segment_first_hit_instance_tree<false>(M, I.tree, I.cull != 0, pa, pb, s_hit, inst);
+    }
+    __device__ __forceinline__ void to_local(int32_t inst, const double c[3], double l[3]) const
+    {
+        instance_into_frame(I.tree.rec + (size_t)inst * BHG_MESH_INSTANCE_DOUBLES_, c, l);
+    }
+    __device__ __forceinline__ void keep(uint64_t i, int32_t inst) const { I.inst_id[i] = inst; }
+};
+
 template <int RHS, class Where>
 __device__ __forceinline__ void trace_mesh_ray(const TraceArgs &A, const MeshArgs &G, const Where &W)
 {
@@ -3740,6 +3754,28 @@ hipError_t launch_trace_mesh_instances(const TraceArgs &a, const MeshArgs &m, co
     if (rhs == BHG_RHS_KERR_BL_) return launch_trace_mesh_instances_kerr(a, m, in, s);
     return launch_lanes(a, rhs,
                         [&](auto R, dim3 grid) { BHG_LAUNCH((trace_mesh_instances_kernel<R.value>), grid, dim3(64), 0, s, a, m, in); });
+}
+#endif
+
+// ... the placements under a tree (bhg_trace_mesh_instances_device with a set of bhg_mesh_instances_create_tree)
+template <int RHS>
+__global__ void __launch_bounds__(64) trace_mesh_instance_tree_kernel(const TraceArgs A, const MeshArgs G, const MeshInstanceTreeArgs I)
+{
+    trace_mesh_ray<RHS>(A, G, MeshPlacementTree{I});
+}
+
+#if defined(BHG_TU_KERR)
+hipError_t launch_trace_mesh_instance_tree_kerr(const TraceArgs &a, const MeshArgs &m, const MeshInstanceTreeArgs &in, hipStream_t s)
+{
+    return launch_lanes(a, BHG_RHS_KERR_BL_,
+                        [&](auto R, dim3 grid) { BHG_LAUNCH((trace_mesh_instance_tree_kernel<R.value>), grid, dim3(64), 0, s, a, m, in); });
+}
+#elif !defined(BHG_TU_TIMELIKE)
+hipError_t launch_trace_mesh_instance_tree(const TraceArgs &a, const MeshArgs &m, const MeshInstanceTreeArgs &in, int rhs, hipStream_t s)
+{
+    if (rhs == BHG_RHS_KERR_BL_) return launch_trace_mesh_instance_tree_kerr(a, m, in, s);
+    return launch_lanes(a, rhs,
+                        [&](auto R, dim3 grid) { BHG_LAUNCH((trace_mesh_instance_tree_kernel<R.value>), grid, dim3(64), 0, s, a, m, in); });
 }
 #endif
 

@@ -1,6 +1,6 @@
 // mesh_layout.h -- where a mesh object's arrays lie in its three device allocations (bhgeo_mesh.hip): the image of the tree and the
-// triangles, the refit's scratch, the build's storage.  Host only, no HIP: tests/mesh_layout_driver.cpp runs it under the host
-// sanitizers.
+// triangles, the refit's scratch, the build's storage -- and where an instance set under a tree keeps its records and its tree.
+// Host only, no HIP: tests/mesh_layout_driver.cpp and tests/mesh_instance_tree_driver.cpp run it under the host sanitizers.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -63,6 +63,21 @@ inline BuildLayout build_layout(size_t record_bytes, size_t cap, size_t sort_byt
     const size_t record = l.add(record_bytes, 256), keys_in = l.add(cap * sizeof(uint64_t)), keys_out = l.add(cap * sizeof(uint64_t)),
                  vals_in = l.add(cap * sizeof(int32_t)), triangles = l.add(cap * 3 * sizeof(int32_t)), sort = l.add(sort_bytes, 256);
     return {record, keys_in, keys_out, vals_in, triangles, sort, l.end};
+}
+
+// the one allocation of an instance set that lies under a tree, and each of its two page-locked host copies:
+// records [n][rec_doubles] | node boxes [n_nodes][6] | skip, first, count [n_nodes] | the instances in leaf order [n].  A move
+// uploads all of it in one copy of `total` bytes.
+struct InstanceTreeLayout {
+    size_t records, node_box, node_skip, node_first, node_count, inst_order, total;
+};
+inline InstanceTreeLayout instance_tree_layout(size_t n, size_t rec_doubles, size_t n_nodes)
+{
+    RegionList l;
+    const size_t d = sizeof(double), i = sizeof(int32_t);
+    const size_t records = l.add(n * rec_doubles * d), box = l.add(n_nodes * 6 * d), skip = l.add(n_nodes * i), first = l.add(n_nodes * i),
+                 count = l.add(n_nodes * i), order = l.add(n * i);
+    return {records, box, skip, first, count, order, l.end};
 }
 
 }  // namespace bhg

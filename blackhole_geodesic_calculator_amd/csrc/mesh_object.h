@@ -65,6 +65,13 @@ struct bhg_mesh_instances {
     mutable hipStream_t read_stream = nullptr;
     mutable bool was_read = false;
     int last = -1;                // the host copy of the latest _set (-1: the creating upload, synchronous)
+    // A set of bhg_mesh_instances_create_tree (leaf_size 0: a linear set): d_rec and both host copies are laid
+    // out by instance_tree_layout -- the records first, where a linear set has them, then the tree -- and travel as one copy of
+    // `bytes`.  tree points into d_rec.  The topology is written into both host copies once, by _create_tree; a _set rewrites the
+    // records, the boxes and the order of its copy.
+    int32_t leaf_size = 0, n_nodes = 0, depth = 0;
+    size_t bytes = 0;             // of d_rec and of each host copy
+    bhg::InstanceTreeView tree{};
 };
 
 #pragma GCC visibility push(hidden)
@@ -73,6 +80,8 @@ namespace bhg {
 // BHGEO_MESH_CULL=0: every step of every ray samples its sub-chords, and no instance's world box is looked at (an A/B aid: the
 // results are the same bits)
 bool mesh_culls_on();
+// BHGEO_INSTANCE_TREE=0: a set under a tree is walked by the linear loop over all its records (an A/B aid of the same kind)
+bool instance_tree_on();
 // A kernel on stream s is about to read the set's records / has been launched (bhg_mesh_instances has the protocol)
 hipError_t instances_before_read(const bhg_mesh_instances *in, hipStream_t s);
 hipError_t instances_after_read(const bhg_mesh_instances *in, hipStream_t s);

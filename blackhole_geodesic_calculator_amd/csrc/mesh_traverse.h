@@ -1,6 +1,6 @@
 // mesh_traverse.h -- segment against the flattened BVH of mesh_bvh.h, on the device.  One function for
 // the mesh trace's sub-chords (first hit) and the mesh shade's shadow rays (any hit), and its form over K rigid placements of
-// the one tree.
+// the one tree, walked one after the other or under a tree of their world boxes (section 24).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -145,6 +145,74 @@ __device__ __forceinline__ int32_t segment_first_hit_instances(const MeshView &M
             best_tri = hit;
             inst = j;
         }
+    }
+    s_hit = best;
+    return best_tri;
+}
+
+// ---- ... under a tree of boxes ---------------------------------------------------------------------------
+// The placements of an instance set under the tree of instance_tree.h: the records as above, in the caller's order, and over them
+// nodes in pre-order with one skip link each, whose leaves hold first and count into inst_order[], the caller's instance indices.
+struct InstanceTreeView {
+    const double *rec;           // [n][BHG_MESH_INSTANCE_DOUBLES_]
+    const double *node_box;      // [n_nodes][6]: the exact union of the world boxes below
+    const int32_t *node_skip;    // [n_nodes]
+    const int32_t *node_first;   // [n_nodes]: first slot of inst_order, -1 for an inner node
+    const int32_t *node_count;   // [n_nodes]: placements of a leaf, 0 for an inner node
+    const int32_t *inst_order;   // [n]: leaf slot -> the caller's instance
+    int32_t n_nodes, n;
+};
+
+// The segment p -> q in the world against the placements under the tree: a stackless walk by skip links, as segment_first_hit
+// walks the mesh's own tree.  A node's box is tested with the best s so far, so it is skipped only when it starts behind that s
+// (the test's own slack keeps ties in); at a leaf each placement's own world box comes first -- its six doubles are read, R and t
+// only once the box is met -- and then the segment goes into the placement's frame and against the one tree.
+// First hit (ANY = false): the smallest s wins, then the smaller instance, then the smaller triangle -- section 21's rule, stated
+// without reference to the order of the visit, which here is the tree's and not the caller's: a hit at the same s replaces the
+// best one when its instance is the smaller.  ANY = true: returns at the first hit met.
+// Unlike the linear walk, the placement j in hand differs from lane to lane: the records are read with ordinary (vector) loads,
+// and the constant address space of the linear walk -- scalar loads of a wave-uniform record -- does not apply.  In exchange a
+// lane is free to leave early and to skip what its own segment misses.
+// boxes = false: no box is looked at, of the tree's or of a placement, and every placement is walked (BHGEO_MESH_CULL=0).
+template <bool ANY>
+__device__ __forceinline__ int32_t segment_first_hit_instance_tree(const MeshView &M, const InstanceTreeView &U, bool boxes,
+                                                                   const double p[3], const double q[3], double &s_hit, int32_t &inst)
+{
+    const double d[3] = {q[0] - p[0], q[1] - p[1], q[2] - p[2]};
+    double best = 1.0;
+    int32_t best_tri = -1;
+    for (int32_t i = 0; i < U.n_nodes;) {
+        if (boxes && !segment_meets_box(U.node_box + (size_t)i * 6, p, d, best)) {
+            i = U.node_skip[i];
+            continue;
+        }
+        const int32_t cnt = U.node_count[i], first = U.node_first[i];
+        for (int32_t k = 0; k < cnt; k++) {
+            const int32_t j = U.inst_order[first + k];
+            const double *r = U.rec + (size_t)j * BHG_MESH_INSTANCE_DOUBLES_;
+            if (boxes) {
+                double wb[6];
+#pragma unroll
+                for (int c = 0; c < 6; c++) wb[c] = r[12 + c];
+                if (!segment_meets_box(wb, p, d, best)) continue;
+            }
+            double lp[3], lq[3], s;
+            instance_into_frame(r, p, lp);
+            instance_into_frame(r, q, lq);
+            const int32_t hit = segment_first_hit<ANY>(M, lp, lq, s);
+            if (hit < 0) continue;
+            if (ANY) {
+                s_hit = s;
+                inst = j;
+                return hit;
+            }
+            if (best_tri < 0 || s < best || (s == best && j < inst)) {
+                best = s;
+                best_tri = hit;
+                inst = j;
+            }
+        }
+        i++;
     }
     s_hit = best;
     return best_tri;

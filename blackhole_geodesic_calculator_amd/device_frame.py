@@ -250,6 +250,7 @@ class DeviceFrame:
         self.d_tri_rgb = None         # [nt, 3] fp32 triangle colours, or None (white)
         self.mesh_material = None     # set_mesh(material=): (_ffi.MeshMaterial, its struct over the device copies, the copies)
         self.mesh_instances = None    # _ffi.MeshInstances (set_mesh(instances=)) or None: the mesh where its vertices put it
+        self._instance_kind = (False, _ffi.MESH_INSTANCE_TREE_LEAF)   # (tree, leaf_size) of the sets set_mesh() asked for
         self.d_inst_rgb = None        # [K, 3] float32 or None
         self.d_inst_id = None         # [n] int32 of the last instanced trace
         self.d_tri_id = None          # [n] int32 and
@@ -433,7 +434,8 @@ class DeviceFrame:
             raise ValueError("opacity must be in (0, 1]")
         self.disk_layers = _ffi.make_disk_layers(max_crossings, opacity)
 
-    def set_mesh(self, mesh=None, tri_rgb=None, chord=None, lamps=None, material=None, instances=None, inst_rgb=None, build="host"):
+    def set_mesh(self, mesh=None, tri_rgb=None, chord=None, lamps=None, material=None, instances=None, inst_rgb=None, build="host",
+                 instance_tree=False, instance_leaf_size=_ffi.MESH_INSTANCE_TREE_LEAF):
         """A triangle mesh in the curved region (bhg_trace_mesh_device, bhg_shade_mesh_device): trace()
         ends a ray where its curve meets a triangle and keeps d_tri_id [n] int32 / d_bary [n, 2]; shade() / shade_f32() /
         render() light the mesh rays (tri_rgb [nt, 3] per triangle, default white; the lamps of set_objects([], lamps=...) or
@@ -446,6 +448,8 @@ class DeviceFrame:
         instances: [K, 12] or [K, 3, 4] rigid placements of the mesh (bhg_trace_mesh_instances_device,
         bhg_shade_mesh_instances_device) -- trace() also keeps d_inst_id [n]; inst_rgb [K, 3] float32
         multiplies the albedo per instance.  set_mesh_instances(T) moves them afterwards.
+        instance_tree=True: the set lies under a tree of boxes with leaves of instance_leaf_size, and K
+        may go up to _ffi.MESH_INSTANCE_TREE_MAX; the image is the linear set's, bit for bit.
         build: "host" or "device" (DESIGN.md section 23), for a mesh given as (vertices, triangles); rebuild_mesh() then gives
         either a new triangle list in place."""
         if build not in ("host", "device"):
@@ -458,6 +462,7 @@ class DeviceFrame:
         if self.mesh_instances is not None:
             self.mesh_instances.close()
         self.mesh_instances = self.d_inst_rgb = None
+        self._instance_kind = (bool(instance_tree), int(instance_leaf_size))
         if mesh is None:
             self.mesh = self.d_tri_rgb = self.mesh_chord = self.mesh_material = None
             return
@@ -482,7 +487,7 @@ class DeviceFrame:
             self.lamps = lamps
         self._mesh_check()
         if instances is not None:
-            self.mesh_instances = _ffi.MeshInstances(mesh, instances)
+            self.mesh_instances = _ffi.MeshInstances(mesh, instances, *self._instance_kind)
             if inst_rgb is not None:
                 rgb = np.ascontiguousarray(inst_rgb, dtype=np.float32)
                 if rgb.shape != (self.mesh_instances.n, 3):
@@ -491,7 +496,7 @@ class DeviceFrame:
 
     def set_mesh_instances(self, transforms=None):
         """Move the instances of set_mesh(instances=): K x 18 doubles go to the device, nothing is rebuilt (bhg_mesh_instances_set).
-        Another K makes a new set (inst_rgb is then dropped); None turns instances off -- the mesh where its vertices put it."""
+        Another K makes a new set of the kind set_mesh() asked for (inst_rgb is then dropped); None turns instances off -- the mesh where its vertices put it."""
         if self.mesh is None:
             raise ValueError("set_mesh_instances() wants a mesh: set_mesh() first")
         self._traced = None
@@ -503,7 +508,7 @@ class DeviceFrame:
             self.mesh_instances.close()
         self.mesh_instances = self.d_inst_rgb = None
         if T is not None:
-            self.mesh_instances = _ffi.MeshInstances(self.mesh, T)
+            self.mesh_instances = _ffi.MeshInstances(self.mesh, T, *self._instance_kind)
 
     def refit_mesh(self, vertices, vertex_normals=None):
         """New vertex positions (and vertex normals) for the held mesh, its tree refitted on the device (Mesh.refit; DESIGN.md

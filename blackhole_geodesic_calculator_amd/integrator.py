@@ -65,7 +65,7 @@ class GeodesicIntegratorSchwarzschild:
     # ------------------------------------------------------------------------------------
     def trace(self, k0, x0, max_step=np.inf, curve_end=50.0, r_exit=0.0, disk=None, spheres=None, redshift=None,
               polarisation=None, disk_thermal=None, disk_crossings=None, travel_time=False, mesh=None, mesh_chord=None,
-              mesh_instances=None, mesh_build="host"):
+              mesh_instances=None, mesh_build="host", mesh_instance_tree=False):
         """Batched solve.  k0[N,3] (or [...,3]); x0[3] shared origin or same leading shape as k0.
         r_exit: outward sphere-exit radius (Limited engine's ray_trace, Limited...py:273-278);
         disk=(R_in, R_out): thin disk in z = 0, first crossing inside the annulus ends the ray with
@@ -120,6 +120,8 @@ class GeodesicIntegratorSchwarzschild:
         K rigid placements x_world = R x_local + t instead of where its vertices put it, and the dict also has
             inst_id[...]               int32, the placement hit, -1 for every other ray (tri_id counts within the mesh, bary lies
                                        in the placement's frame)
+        mesh_instance_tree=True (with mesh_instances=): the placements lie under a tree of boxes, K may go
+        up to 65536, and every output is the linear walk's, bit for bit.
         mesh_build="device" (with mesh=(vertices, triangles)): the mesh's tree is built on the device
         instead of the host; every output is the same, bit for bit.
         """
@@ -127,13 +129,16 @@ class GeodesicIntegratorSchwarzschild:
             raise ValueError('mesh_build must be "host" or "device"')
         if mesh_instances is not None and mesh is None:
             raise ValueError("mesh_instances goes with mesh=")
+        if mesh_instance_tree and mesh_instances is None:
+            raise ValueError("mesh_instance_tree goes with mesh_instances=")
         if mesh is not None:
             for name, given in (("spheres", spheres is not None), ("disk_crossings", disk_crossings is not None),
                                 ("travel_time", bool(travel_time)), ("redshift", redshift is not None),
                                 ("polarisation", polarisation is not None), ("disk_thermal", disk_thermal is not None)):
                 if given:
                     raise ValueError(f"mesh does not go with {name}")
-            return self._trace_mesh(k0, x0, max_step, curve_end, r_exit, disk, mesh, mesh_chord, mesh_instances, mesh_build)
+            return self._trace_mesh(k0, x0, max_step, curve_end, r_exit, disk, mesh, mesh_chord, mesh_instances, mesh_build,
+                                    bool(mesh_instance_tree))
         if travel_time and spheres is not None:
             raise ValueError("travel_time does not go with object spheres")
         if disk_crossings is not None:
@@ -185,7 +190,7 @@ class GeodesicIntegratorSchwarzschild:
             out["t"] = t.reshape(lead)
         return out
 
-    def _trace_mesh(self, k0, x0, max_step, curve_end, r_exit, disk, mesh, mesh_chord, instances=None, build="host"):
+    def _trace_mesh(self, k0, x0, max_step, curve_end, r_exit, disk, mesh, mesh_chord, instances=None, build="host", tree=False):
         """trace(mesh=): a mesh given as arrays lives for this call, and so does the instance set of mesh_instances=."""
         own = not isinstance(mesh, _ffi.Mesh)
         m = _ffi.Mesh(self._ctx, mesh[0], mesh[1], build=build) if own else mesh
@@ -200,7 +205,7 @@ class GeodesicIntegratorSchwarzschild:
                 end, flags, steps, acc, tri, bary = self._ctx.trace_mesh(k0.reshape(-1, 3), x0f,
                                                                          self.params(max_step, curve_end, r_exit, disk), m, chord)
             else:
-                inst = _ffi.MeshInstances(m, instances)
+                inst = _ffi.MeshInstances(m, instances, tree=tree)
                 end, flags, steps, acc, tri, inst_id, bary = self._ctx.trace_mesh_instances(
                     k0.reshape(-1, 3), x0f, self.params(max_step, curve_end, r_exit, disk), inst, chord)
         finally:

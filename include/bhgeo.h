@@ -77,6 +77,9 @@ extern "C" {
                                   BHG_MESH_INSTANCES (bhg_mesh_instances_create / _set / _destroy / _info, bhg_mesh_instance_box_host,
                                   bhg_trace_mesh_instances_device, bhg_trace_mesh_instances, bhg_shade_mesh_instances_device, bhg_frame_set_mesh_instances, struct bhg_mesh_instances,
                                   BHG_MESH_INSTANCES_MAX: rigid placements of one mesh, moved without a rebuild);
+                                  BHG_MESH_INSTANCE_TREE (bhg_mesh_instances_create_tree, bhg_mesh_instances_tree_info,
+                                  bhg_mesh_instance_tree_host, bhg_frame_set_mesh_instance_tree, BHG_MESH_INSTANCE_TREE_MAX: an
+                                  instance set under a tree of boxes);
                                   BHG_MESH_REFIT (bhg_mesh_refit, bhg_mesh_refit_device, bhg_mesh_refit_info, bhg_mesh_bvh_refit_host,
                                   bhg_mesh_refit_schedule_host, bhg_mesh_boxes_host, bhg_mesh_range, bhg_frame_refit_mesh, bhg_frame_mesh_refit_info: new vertices into a built mesh, its tree
                                   refitted on the device);
@@ -1193,6 +1196,40 @@ int bhg_shade_mesh_instances_device(bhg_context *ctx, const double *d_end, const
  * turns them off too.  Refused, the frame left as it was: a frame without a mesh; what bhg_mesh_instances_create refuses of n and
  * the transforms; a non-finite inst_rgb.  bhg_frame_render's "a mesh does not go with ..." cases hold as they are. */
 int bhg_frame_set_mesh_instances(bhg_frame *frame, int32_t n, const double *transforms, const float *inst_rgb);
+
+/* --- instance trees: an instance set whose placements lie under a tree of boxes (within ABI 10) -----------
+ * bhg_mesh_instances_create_tree makes a bhg_mesh_instances of up to BHG_MESH_INSTANCE_TREE_MAX placements that every call above
+ * takes -- _set, _destroy, _info, both trace calls, the shade -- and that computes what a set of bhg_mesh_instances_create
+ * computes, bit for bit: the rule (the smallest s, then the smaller instance, then the smaller triangle) does not depend on the
+ * order in which the placements are visited, and the tree only decides which of them a sub-chord or a shadow segment looks at.
+ * The tree lies over the placements' world boxes: binary, every range split by count on the longest axis of its boxes' centres
+ * (ties by instance index) down to leaf_size placements, so its shape depends on (n, leaf_size) alone; a node's box is the exact
+ * union of the world boxes below it.  It is walked per ray, without a stack, by skip links; a box is skipped only when it starts
+ * behind the best s so far.  bhg_mesh_instances_set builds the order and the boxes anew on the host, in O(n log n), and sends
+ * records and tree in one upload (records | boxes | skip | first | count | order) through the set's own buffers: moving needs
+ * no synchronisation, as before, and allocates nothing.  The refit rule of bhg_mesh_refit applies unchanged.
+ * BHGEO_MESH_CULL=0 keeps its meaning -- no box is looked at, of the tree's or of an instance, every placement is walked --,
+ * and BHGEO_INSTANCE_TREE=0 has such a set walked by the linear loop over all its records (A/B aids: the same bits).
+ * Refused, in this order: a NULL out; n outside [1, BHG_MESH_INSTANCE_TREE_MAX]; leaf_size outside [1, 8]; the transforms as
+ * bhg_mesh_instances_create refuses them; a NULL mesh; the context.  bhg_mesh_instances_create and BHG_MESH_INSTANCES_MAX stay
+ * what they are: a set made the old way is walked linearly. */
+#define BHG_MESH_INSTANCE_TREE 1
+#define BHG_MESH_INSTANCE_TREE_MAX 65536
+int bhg_mesh_instances_create_tree(bhg_context *ctx, const bhg_mesh *mesh, int32_t n, const double *transforms /* host [n][12] */,
+                                   int32_t leaf_size, bhg_mesh_instances **out);
+/* the tree of a set: its nodes, its depth (levels below the root) and its leaf_size; all zeros for a linear set.  Any may be NULL */
+int bhg_mesh_instances_tree_info(const bhg_mesh_instances *inst, int32_t *n_nodes, int32_t *depth, int32_t *leaf_size);
+/* The tree such a set builds over n placements of a mesh whose root box is local_box: host arithmetic, no context, no GPU.
+ * node_box [2 n - 1][6], node_skip / node_first / node_count [2 n - 1] (2 n - 1 nodes always suffice), inst_order [n]: the caller's
+ * instance in each leaf slot.  Leaves have count > 0 and first = their first slot; inner nodes count = 0, first = -1. */
+int bhg_mesh_instance_tree_host(const double local_box[6], int32_t n, const double *transforms, int32_t leaf_size, double *node_box,
+                                int32_t *node_skip, int32_t *node_first, int32_t *node_count, int32_t *inst_order, int32_t *n_nodes,
+                                int32_t *depth);
+/* bhg_frame_set_mesh_instances with sets of bhg_mesh_instances_create_tree: up to BHG_MESH_INSTANCE_TREE_MAX placements of the
+ * frame's mesh, in every gather mode.  A second call with the same n moves the instances (one upload per device); n = 0, a call of
+ * bhg_frame_set_mesh_instances or of bhg_frame_set_mesh turns the trees off.  Refused, the frame left as it was: what that call
+ * refuses, with bhg_mesh_instances_create_tree's bounds on n and leaf_size in place of BHG_MESH_INSTANCES_MAX. */
+int bhg_frame_set_mesh_instance_tree(bhg_frame *frame, int32_t n, const double *transforms, const float *inst_rgb, int32_t leaf_size);
 
 /* --- deforming meshes: new vertices into a built mesh, its tree refitted on the device (within ABI 10) ----
  * A refit gives a mesh new vertex positions (and vertex normals).  n_vertices and the triangles are the mesh's own: the tree's
